@@ -1,12 +1,18 @@
 #!/usr/bin/env python3
 """bench.py — benchmarks of the DiffusionIQT hot path on MI355X.  Prints ONE JSON line on rank 0.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2|C4|C5] [--mode both|sample|train|volume]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2|C4|C5] [--mode both|sample|train|volume] [--full]
+                  [--dump-outputs DIR]
+
+A plain run measures the headline figure only: set-up, W warm-up steps, K timed steps, the result line.  `--full` adds everything
+else (the side lines below, the train micro-step of `--mode both`, the instrumented per-kernel / roofline pass, `cpu_baseline`,
+the DDP cost split for N > 1); the --no-* switches trim a --full run.  `--dump-outputs DIR` writes, after the timed steps, what the
+timed path returned in its last step as DIR/<name>.npy (float32; inputs are seeded, so two builds can be compared output for output).
 
 --config C2 (default; BASELINE.json configs[1], SURVEY.md §8 "C2" — the headline): Family-A SRUnet256(dim=64, dim_mults=(1,2,4),
     2 resnet blocks/level, SE, no attention, deep_feature=False — the train.py kwargs) on 32^3 1-channel patches, batch 8 per GPU,
     fp32.  One "step" = one DDPM ancestral sampler step over the batch = one U-Net eval (186.06 GFLOP/patch) + one fused
-    posterior-step kernel; `value` = patches denoised / s.  Beside it: `train` (ImagenTrainer micro-steps: fwd + bwd + bucketed
+    posterior-step kernel; `value` = patches denoised / s.  Beside it (--full): `train` (ImagenTrainer micro-steps: fwd + bwd + bucketed
     grad all-reduce on sync steps + fused Adam every 4th + EMA, 558 GFLOP/patch), `edm` (ElucidatedImagen stochastic Heun on the
     same U-Net), `unet3d_edm` (Family B: Unet3D + ElucidatedImagen.sample, the pairing BASELINE.json's metric string names),
     `api_sample` (the same sampling through trainer.sample(), the reference's call), autocast lines (reduced precision, never `value`).
@@ -19,10 +25,10 @@ anything touches the GPU; the parent never initialises HIP and exits with the ch
 `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N` it uses the ranks it was given.  Every rank holds its own
 batch (weak scaling); sampling shards patches with no data-path collective, training all-reduces gradients over RCCL (xGMI).
 
-`roofline` is for the dominant kernel of the headline loop.  The timed region runs WITHOUT instrumentation; the per-kernel
+`roofline` (--full) is for the dominant kernel of the headline loop.  The timed region runs WITHOUT instrumentation; the per-kernel
 numbers come from a second, instrumented pass of the same steps (HIP events on the launch stream around every conv launch).
-`cpu_baseline` is the CPU oracle (oracle/iqt_oracle.py, a port of the reference algorithm — the reference itself cannot travel
-to the GPU box) timed on the host cores on a bounded sample of the same workload, rank 0, N = 1 only.
+`cpu_baseline` (--full) is the CPU oracle (oracle/iqt_oracle.py, a port of the reference algorithm; the reference itself is not
+part of this repository) timed on the host cores on a bounded sample of the same workload, rank 0, N = 1 only.
 """
 import argparse
 import gc
@@ -165,6 +171,10 @@ def main():
     ap.add_argument("--no-extras", action="store_true", help="headline loops only: the command profiled under profiles/")
     ap.add_argument("--rehearse", action="store_true",
                     help="N ranks on ONE card with gloo collectives (plumbing rehearsal on a 1-GPU box; never a measurement)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the side lines, the train micro-step of --mode both, per-kernel / roofline pass, CPU baseline, DDP split")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -231,8 +241,8 @@ def main():
         return dt
 
     def instrumented(fn, n):
-        """Per-kernel HIP-event timing of n more calls, OUTSIDE any timed region -> {tag: (ms, flops, launches)}."""
-        if args.no_kernel_timer:
+        """Per-kernel HIP-event timing of n more calls, OUTSIDE any timed region -> {tag: (ms, flops, launches)}; --full only."""
+        if not args.full or args.no_kernel_timer:
             return {}
         from diffusioniqt_amd import graphs
         sync_all()
@@ -280,12 +290,15 @@ def main():
     if rehearsal:
         common["rehearsal"] = f"{world} ranks share ONE GPU with gloo collectives: plumbing check, NOT a measurement"
 
+    outputs = {}                                             # what the timed path returned in its last step (--dump-outputs)
     if args.config == "C4":
-        out = bench_c4(args, torch, ops, device, world, timed, instrumented, roofline_of)
+        out = bench_c4(args, torch, ops, device, world, timed, instrumented, roofline_of, outputs)
     elif args.config == "C5":
-        out = bench_c5(args, torch, ops, device, world, timed, instrumented, roofline_of)
+        out = bench_c5(args, torch, ops, device, world, timed, instrumented, roofline_of, outputs)
     else:
-        out = bench_c2(args, torch, dist, D, ops, device, world, rank, timed, instrumented, roofline_of, sync_all)
+        out = bench_c2(args, torch, dist, D, ops, device, world, rank, timed, instrumented, roofline_of, sync_all, outputs)
+    if rank == 0 and args.dump_outputs:
+        write_outputs(args.dump_outputs, outputs)
     if rank == 0:
         print(json.dumps({**out, **common}), flush=True)
     if world > 1:
@@ -295,7 +308,7 @@ def main():
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
-def bench_c4(args, torch, ops, device, world, timed, instrumented, roofline_of):
+def bench_c4(args, torch, ops, device, world, timed, instrumented, roofline_of, outputs=None):
     from diffusioniqt_amd.imagen_pytorch3D import SRUnet256
     K, W, B, S = args.steps or 10, args.warmup if args.warmup is not None else 3, args.batch or 1, 64
     torch.manual_seed(0)
@@ -304,10 +317,14 @@ def bench_c4(args, torch, ops, device, world, timed, instrumented, roofline_of):
     lr, t = torch.randn_like(x), torch.rand(B, device=device)
     assert B == 1, "C4's merged-volume attention takes one volume per call (batch_sample_factor=1)"
 
+    last = {}
+
     def step():
         with torch.no_grad():
-            unet(x, None, t, lowres_cond_img=lr)
+            last["pred"] = unet(x, None, t, lowres_cond_img=lr)
     dt = timed(step, W, K)
+    if outputs is not None:
+        outputs["pred"] = last["pred"].clone()
     ms = 1e3 * dt / K
     summ = instrumented(step, 3)
     res = {"metric": "64³ volumes/sec — U-Net evals (C4: dim 128, LinearAttention at every stage)", "value": round(world * B * K / dt, 3),
@@ -321,6 +338,9 @@ def bench_c4(args, torch, ops, device, world, timed, instrumented, roofline_of):
         res["roofline"]["traffic"] = pmc_traffic_of("C4", res["roofline"]["kernel"])
         res["roofline"]["traffic_note"] = "HBM bytes per average launch from the committed rocprofv3 --pmc passes of `bench.py --config C4` (profiles/)"
 
+    if not args.full:
+        return res
+
     def step_h():
         with torch.autocast('cuda', dtype=torch.float16):
             step()
@@ -329,7 +349,7 @@ def bench_c4(args, torch, ops, device, world, timed, instrumented, roofline_of):
     return res
 
 
-def bench_c5(args, torch, ops, device, world, timed, instrumented, roofline_of):
+def bench_c5(args, torch, ops, device, world, timed, instrumented, roofline_of, outputs=None):
     from diffusioniqt_amd.imagen_video import Unet3D
     from diffusioniqt_amd.elucidated_imagen import ElucidatedImagen
     n_steps = args.steps or 64                 # Heun steps per stage (the config names 64)
@@ -359,6 +379,8 @@ def bench_c5(args, torch, ops, device, world, timed, instrumented, roofline_of):
             elu.hparams = keep
     short()
     dt = timed(cascade, W, K)
+    if outputs is not None:
+        outputs["sample"] = last["out"].clone()
     assert tuple(last["out"].shape) == (B, 1, 64, 64, 64) and torch.isfinite(last["out"]).all()
     summ = instrumented(short, 1)
     ms = 1e3 * dt / K
@@ -379,10 +401,12 @@ def bench_c5(args, torch, ops, device, world, timed, instrumented, roofline_of):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
-def bench_c2(args, torch, dist, D, ops, device, world, rank, timed, instrumented, roofline_of, sync_all):
-    # the side lines (API sampling, autocast, EDM, Unet3D, bf16 trainer) are single-GPU information: a multi-rank run measures the
-    # headline loops (sampler step, training micro-step + gradient all-reduce) only -- less to go wrong in lockstep
-    extras = not args.no_extras and world == 1
+def bench_c2(args, torch, dist, D, ops, device, world, rank, timed, instrumented, roofline_of, sync_all, outputs=None):
+    # the side lines (API sampling, autocast, EDM, Unet3D, bf16 trainer) are single-GPU information (--full): a multi-rank run measures
+    # the headline loops (sampler step, training micro-step + gradient all-reduce) only -- less to go wrong in lockstep
+    extras = args.full and not args.no_extras and world == 1
+    # a plain run times the headline loop alone: with --mode both the training micro-step is a --full line
+    run_train = args.mode == "train" or (args.mode == "both" and args.full)
     from diffusioniqt_amd.imagen_pytorch3D import SRUnet256, Imagen, NullUnet
     from diffusioniqt_amd.trainer import ImagenTrainer
     B, S = args.batch or 8, args.size
@@ -427,6 +451,8 @@ def bench_c2(args, torch, dist, D, ops, device, world, rank, timed, instrumented
             kept[0] = 0
             pred = infer(vol, patch_slice=(rank, world) if world > 1 else None)
             assert torch.isfinite(pred).all()
+            if outputs is not None:
+                outputs["pred"] = pred
         dt = timed(one_volume, 1, 1)
         tot = torch.tensor([kept[0]], device=device, dtype=torch.int64)
         if world > 1:
@@ -453,13 +479,17 @@ def bench_c2(args, torch, dist, D, ops, device, world, rank, timed, instrumented
             pred = imagen.unet_eval(unet, state["img"], conds[i], lowres_cond_img=lr)      # what Imagen.p_sample_loop calls per step
             noise = torch.randn_like(pred)
             state["img"], _ = ops.ddpm_step(state["img"], pred, noise, coefs[i, 0], coefs[i, 1], coefs[i, 2], min_bound, 0.0, 0)
+        state["pred"] = pred
         state["i"] += 1
 
     roof = None
     if args.mode in ("sample", "both"):
         dt = timed(sample_step, W, K)
         result["sample"] = dict(ms_per_step=1e3 * dt / K, patches_per_s=world * B * K / dt)
+        if outputs is not None:                              # the last step's image x_{t-1} and the U-Net's x_start prediction
+            outputs["img"], outputs["pred"] = state["img"].clone(), state["pred"].clone()
         assert torch.isfinite(state["img"]).all()
+    if args.mode in ("sample", "both") and args.full:
         state["img"] = torch.randn(B, 1, S, S, S, device=device)
         n_i = min(K, 8)
         summ = instrumented(sample_step, n_i)
@@ -551,16 +581,20 @@ def bench_c2(args, torch, dist, D, ops, device, world, rank, timed, instrumented
 
     # ---------------- training: K micro-steps through ImagenTrainer.forward ----------------
     ddp = None
-    if args.mode in ("train", "both"):
+    if run_train:
         trainer.training = True
         unet.train()
+        last = {}
 
         def train_step():
-            trainer.forward(hr, lowres_img=lr, unet_number=2, max_batch_size=B)
+            last["out"] = trainer.forward(hr, lowres_img=lr, unet_number=2, max_batch_size=B)
 
         kt = K if args.mode == "train" else max(4, K // 2)
         kt = (kt + 3) // 4 * 4                               # whole accumulation cycles: one all-reduce + Adam per 4 micro-steps
         dt = timed(train_step, max(W, 4) // 4 * 4, kt)
+        if outputs is not None and "sample" not in result:   # the headline is the training micro-step: (loss, pred, x_noisy)
+            loss, pred, x_noisy, _ = last["out"]
+            outputs.update(loss=torch.as_tensor(loss).detach().reshape(1).clone(), pred=pred.clone(), x_noisy=x_noisy.clone())
         result["train"] = dict(ms_per_step=1e3 * dt / kt, steps_per_s=kt / dt, patches_per_s=world * B * kt / dt, steps=kt,
                                mfma_busy_frac=pmc_mfma_busy("train"))
         summ_t = instrumented(train_step, 4)
@@ -572,7 +606,7 @@ def bench_c2(args, torch, dist, D, ops, device, world, rank, timed, instrumented
             tr["traffic"] = pmc_traffic(tr["kernel"], B, S)       # HBM bytes per average launch, committed --pmc passes of `--mode both`
             tr["traffic_note"] = "the kernel alone (without the slab sum), from the committed rocprofv3 --pmc passes of this command (profiles/)"
             result["train_roofline"] = tr
-        if world > 1:
+        if world > 1 and args.full:
             ddp = ddp_stats(torch, dist, ops, trainer, train_step, sync_all, device, world)
         if extras:
             # the same micro-steps with ImagenTrainer's mixed-precision switch (precision='bf16', trainer.py:293-311)
@@ -607,7 +641,7 @@ def bench_c2(args, torch, dist, D, ops, device, world, rank, timed, instrumented
 
     # ---------------- CPU baseline: the oracle on the host cores, bounded sample ----------------
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(torch, unet, S, min_bound)
 
     if rank != 0:
@@ -621,7 +655,7 @@ def bench_c2(args, torch, dist, D, ops, device, world, rank, timed, instrumented
         "steps": K if primary == "sample" else result["train"]["steps"], "warmup": W,
         "ms_per_step": round(result[primary]["ms_per_step"], 3), "dtype": "f32",
         "config": {"workload": f"C2: SRUnet256 dim=64 mults=(1,2,4) 32^3 1ch, batch {B}/GPU, DDPM ancestral sampler step "
-                               f"(1 U-Net eval = {GFLOP_PER_PATCH_EVAL} GFLOP/patch) + ImagenTrainer micro-step",
+                               f"(1 U-Net eval = {GFLOP_PER_PATCH_EVAL} GFLOP/patch)" + (" + ImagenTrainer micro-step" if run_train else ""),
                    "global_batch": world * B, "patch": f"{S}^3", "parallelism": f"dp{world}"},
         "roofline": roof if primary == "sample" else result.get("train_roofline"),
         "cpu_baseline": cpu,
@@ -660,6 +694,19 @@ def bench_c2(args, torch, dist, D, ops, device, world, rank, timed, instrumented
         out["edm"] = r3(result["edm"])
         out["edm"]["note"] = "ElucidatedImagen.sample (stochastic Heun, 2 U-Net evals per step except the last) driving the same C2 U-Net"
     return out
+
+
+def write_outputs(d, arrays, budget=64 * 10**6):
+    """DIR/<name>.npy in float32 for every array; an array above its share of ``budget`` bytes is written as a fixed, seeded sample of
+    its flattened elements (sorted indices from numpy's default_rng(0), so every run and every build picks the same elements)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    per = budget // max(1, len(arrays))
+    for name, t in arrays.items():
+        a = np.ascontiguousarray(t.detach().float().cpu().numpy() if hasattr(t, "detach") else np.asarray(t), dtype=np.float32)
+        if a.nbytes > per:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, per // a.itemsize, replace=False))]
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 def ddp_stats(torch, dist, ops, trainer, train_step, sync_all, device, world):

@@ -22,17 +22,17 @@ stats unet3d_train python3 $R/tools/unet3d_train_bench.py 64 32 8
 NO_LAYER_ATTNS=1 AUTOCAST=fp16 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_c5s2 -o c5s2 -- python3 $R/tools/unet3d_bench.py 64 64 8 > $OUT/c5s2_fp16.log 2>&1
 cp $(find /tmp/p_c5s2 -name "*kernel_stats.csv" | head -1) $OUT/c5s2_fp16_kernel_stats.csv
 echo "done c5s2"
-rocprofv3 --pmc FETCH_SIZE --output-format csv -d /tmp/pmc_fetch -- python3 $R/bench.py --mode both --steps 4 --warmup 4 $B > $OUT/pmc_fetch.log 2>&1
+rocprofv3 --pmc FETCH_SIZE --output-format csv -d /tmp/pmc_fetch -- python3 $R/bench.py --full --mode both --steps 4 --warmup 4 $B > $OUT/pmc_fetch.log 2>&1
 echo "done fetch"
-rocprofv3 --pmc WRITE_SIZE --output-format csv -d /tmp/pmc_write -- python3 $R/bench.py --mode both --steps 4 --warmup 4 $B > $OUT/pmc_write.log 2>&1
+rocprofv3 --pmc WRITE_SIZE --output-format csv -d /tmp/pmc_write -- python3 $R/bench.py --full --mode both --steps 4 --warmup 4 $B > $OUT/pmc_write.log 2>&1
 echo "done write"
-python3 $R/tools/pmc_traffic.py /tmp/pmc_fetch /tmp/pmc_write $OUT/pmc_hbm_traffic.json "bench.py --mode both --steps 4 --warmup 4 $B"
+python3 $R/tools/pmc_traffic.py /tmp/pmc_fetch /tmp/pmc_write $OUT/pmc_hbm_traffic.json "bench.py --full --mode both --steps 4 --warmup 4 $B"
 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE --output-format csv -d /tmp/pmc_sq -- python3 $R/tools/conv_bench.py both 10 > $OUT/pmc_sq.log 2>&1
 cp $(find /tmp/pmc_sq -name "*counter_collection.csv" | head -1) $OUT/pmc_sq_counter_collection.csv
 echo "done sq"
 # ---- round 4 ----
 # C4 eval kernel stats; HBM traffic (two passes each) of the C4 eval, of one C5 stage-2 eval under autocast and of the Family-B eval
-stats c4_eval python3 $R/bench.py --config C4 --steps 3 --warmup 2 --no-cpu-baseline --no-kernel-timer
+stats c4_eval python3 $R/bench.py --full --config C4 --steps 3 --warmup 2 --no-cpu-baseline --no-kernel-timer
 stats sample_autocast python3 $R/tools/autocast_bench.py
 stats train_bf16 python3 $R/tools/train_bf16_only.py 16
 traffic() {  # tag, command...
@@ -42,7 +42,7 @@ traffic() {  # tag, command...
   python3 $R/tools/pmc_traffic.py /tmp/pmcf_$t /tmp/pmcw_$t $OUT/pmc_hbm_traffic_$t.json "$*"
   echo "done traffic $t"
 }
-traffic C4 python3 $R/bench.py --config C4 --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-timer
+traffic C4 python3 $R/bench.py --full --config C4 --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-timer
 NO_LAYER_ATTNS=1 AUTOCAST=fp16 traffic C5 python3 $R/tools/unet3d_bench.py 64 64 8
 traffic unet3d python3 $R/tools/unet3d_bench.py 64 32 8
 # matrix-pipe busy fraction of whole workloads (SQ counters, own passes) and the conv_f9h_kernel counter set
