@@ -27,6 +27,7 @@ PROTOTYPES = {
     "diqt_census_count": (L, [c_char_p]),
     "diqt_get_last_launch": (c_char_p, []),
     "diqt_conv_packed_elems": (Z, [I, I, I, I, I]),
+    "diqt_conv_packed_wino_elems": (Z, [I, I, I, I, I]),
     "diqt_conv_pack_weight": (I, [P, P, I, I, I, I, I, I, P]),
     "diqt_conv3d_fwd": (I, [P, P, P, P, P] + [I] * 15 + [P]),
     "diqt_conv3d_fwd_workspace_bytes": (Z, [I] * 15),
@@ -121,6 +122,13 @@ PROTOTYPES = {
     "diqt_multi_accumulate_host": (I, [P, P, I, I, P]),
     "diqt_conv3d_fwd_stats_blocks": (I, [I] * 15),
     "diqt_conv3d_fwd_kernel_id": (I, [I] * 15),
+    "diqt_conv3d_fwd9_variant": (I, [I] * 15 + [Z]),
+    "diqt_get_last_conv_fwd9_variant": (I, []),
+    "diqt_conv3d_fwd_pk": (I, [P, P, Z, P, P, P, P, P, Z] + [I] * 15 + [P]),
+    "diqt_conv3d_fwd_workspace_bytes_pk": (Z, [I] * 15 + [Z]),
+    "diqt_conv3d_fwd_stats_blocks_pk": (I, [I] * 15 + [Z]),
+    "diqt_conv3d_fwd_gn_supported_pk": (I, [I] * 16 + [Z]),
+    "diqt_conv3d_fwd_gn_pk": (I, [P, P, Z, P, P, P, P, P, Z, P, I] + [I] * 15 + [P]),
     "diqt_conv3d_bwd_weight_kernel_id": (I, [I] * 15),
     "diqt_conv3d_fwd_ex": (I, [P, P, P, P, P, P, P, Z] + [I] * 15 + [P]),
     "diqt_conv3d_fwd_neighbours_stats_blocks": (I, [I, I, I, I, I]),

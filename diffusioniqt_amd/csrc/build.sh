@@ -27,12 +27,12 @@ stamp_of() { cat $(deps_of "$1") | cat - <(echo "$FLAGS $HIPCC $2") | sha256sum 
 OBJS=""
 PIDS=""
 BUILT=""
-for f in conv_fwd9 conv_fwd9_d conv_fwd9_b conv_fwd9_c conv_fwd9_e conv_fwd9_f conv_fwd9_g conv_fwd9_h conv_fwd9_i conv_mfma conv_wgrad conv_wgrad_h conv_pw conv_half conv_f9h conv_f9h_b conv_f9h_c conv_smallcout elementwise bgemm conv_direct attention attn_temporal datapath lib; do
+for f in conv_fwd9 conv_fwd9_d conv_fwd9_b conv_fwd9_c conv_fwd9_e conv_fwd9_f conv_fwd9_g conv_fwd9_h conv_fwd9_i conv_fwd9_j conv_fwd9_k conv_mfma conv_wgrad conv_wgrad_h conv_pw conv_half conv_f9h conv_f9h_b conv_f9h_c conv_smallcout elementwise bgemm conv_direct attention attn_temporal datapath lib; do
   src=$f.hip; xflag=""
   if [ $f = lib ]; then src=lib.cpp; xflag="-x hip"; fi
   # the GroupNorm-apply instantiations of conv_fwd9_kernel: their fully unrolled step loop exceeds LLVM's default size limit for
   # `#pragma unroll` (16384), below which the plain instantiations stay
-  case $f in conv_fwd9_f|conv_fwd9_g|conv_fwd9_h|conv_fwd9_i) xflag="-mllvm -pragma-unroll-threshold=1000000";; esac
+  case $f in conv_fwd9_f|conv_fwd9_g|conv_fwd9_h|conv_fwd9_i|conv_fwd9_k) xflag="-mllvm -pragma-unroll-threshold=1000000";; esac
   want=$(stamp_of $src "$xflag")
   if [ ! -f $f.o ] || [ ! -f $f.stamp ] || [ "$(cat $f.stamp)" != "$want" ]; then
     rm -f $f.o $f.stamp

@@ -29,18 +29,24 @@ struct F9Geom {
     // and a write of the whole activation per conv) disappears.  gcoef = [2][B][Cin] floats: A, then Bc (diqt_gn_coef*).
     const float* gcoef;
     int gnaAct;                  // DIQT_ACT_MISH / DIQT_ACT_SILU, 0: none
+    unsigned wOff;               // floats in front of the panels this variant reads in the packed buffer (Winograd: the direct pack)
 };
 
 // which (F9Geom::variant, activation) pairs have a GroupNorm-apply instantiation: Mish on the 3x3x3 tiles, SiLU on the (1,3,3) ones
 inline bool fwd9_gna_available(int variant, int act) {
-    return (act == 1 /* DIQT_ACT_MISH */ && (variant == 0 || variant == 1)) || (act == 2 /* DIQT_ACT_SILU */ && variant >= 2 && variant <= 4);
+    return (act == 1 /* DIQT_ACT_MISH */ && (variant == 0 || variant == 1 || variant == 7)) || (act == 2 /* DIQT_ACT_SILU */ && variant >= 2 && variant <= 4);
 }
 
+// wino: the launch is a plain or GroupNorm-apply forward launch (no GroupNorm-backward epilogue) whose packed buffer holds the Winograd
+// panels behind the direct ones (diqt_conv_pack_weight modes 2 / 3): 3x3x3 launches with an even output width then take the Winograd
+// variant 7 unless DIQT_CONV_F9W=0.
 // maySplit: the caller has a workspace for split-K slabs (g.ksplit * output elements floats when g.ksplit > 1; the kernel then gets
 // the slab base as y and no bias / residual / statistics).
 // Does conv_fwd9_kernel take this launch (3x3x3 or (1,3,3), Cin % 16 == 0, whole rounds of 512- / 256-voxel tiles, tensors < 1 GiB)?
 bool fwd9_plan(F9Geom& g, size_t& lds, unsigned& grid, int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd,
-               int ph, int pw, int epd, int eph, int epw, size_t packedElems, bool maySplit);
+               int ph, int pw, int epd, int eph, int epw, size_t packedElems, bool maySplit, bool wino);
+// F9Geom::variant of the last conv_fwd9_kernel launch the process issued, -1 if none since the last call (which clears it)
+int fwd9_take_last_variant();
 int fwd9_launch(const float* x, const float* packed, const float* bias, const float* residual, float* y, const F9Geom& g, size_t lds,
                 unsigned grid, void* stream);
 

@@ -21,9 +21,20 @@
 //     a fixed order (with bias / residual) by conv_fwd_reduce_kernel.
 // Measured (MI355X, 64->64 3x3x3 @ 8x32^3): 411 us = 141 TFLOP/s = 0.90 of the f32 MFMA peak (conv_fwd8_kernel: 444 us); MFMA pipe
 // busy 0.92 of the kernel's cycles, 6 % of wave cycles waiting (profiles/r02_pmc_sq_conv.json).
+//   * Winograd F(2,3) along W (variant 7, F9_333W, conv_fwd9_{j,k}.hip): the 3x3x3 forward launches with an even output width.  gfx950
+//     has no reduced-precision f32 MFMA, so the direct tiles sit at their ceiling (0.84-0.90 of peak); the Winograd tile issues 4 MFMA
+//     products per output pair where the direct tiles issue 6.  A rows are output pairs (8 rows x 4 pairs of one plane per wave), a
+//     tap is (kd, kh, j) with j the Winograd position (36 taps per chunk, 8 accumulator tiles per wave); the operand of position j is
+//     one add / subtract of two halo fragments (d0 - d2, d1 + d2, d2 - d1, d1 - d3), the output transform (y0 = m0 + m1 + m2,
+//     y1 = m1 - m2 - m3) is lane-local in the epilogue, in front of bias, residual and statistics.  The weight panels U0 = g0,
+//     U1 = (g0 + g1 + g2) / 2, U2 = (g0 - g1 + g2) / 2, U3 = g2 follow the direct pack in the packed buffer (pack modes 2 / 3); only
+//     the entry points told the buffer's length (diqt_conv3d_fwd_pk / _gn_pk) plan with wino = true, and only when it holds them.
+//     Measured (C2 sampler step, 38 launches per U-Net eval): 3x3x3 conv time 11.16 -> 8.70 ms per eval, 10.03-10.05 ms per step
+//     against 12.49-12.53 on the direct tiles (profiles/r05_*).  DIQT_CONV_F9W=0 forces the direct tiles.
 // Reference call sites: Block.project of every ResnetBlock (/root/reference/imagen_pytorch3D.py:535-566) and the per-frame Conv2d of
 // the pseudo-3D blocks (/root/reference/imagen_video.py:352-381 Conv3d.spatial_conv, 671-697 Block).
 #include "conv_fwd9_kernel.h"
+#include <atomic>
 #include <stdlib.h>
 
 namespace diqt {
@@ -55,8 +66,9 @@ template <class C> static bool f9_try(F9Geom& g, size_t& lds, unsigned& grid, in
 }
 
 bool fwd9_plan(F9Geom& g, size_t& lds, unsigned& grid, int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd,
-               int ph, int pw, int epd, int eph, int epw, size_t packedElems, bool maySplit) {
+               int ph, int pw, int epd, int eph, int epw, size_t packedElems, bool maySplit, bool wino) {
     static const int mode = [] { const char* e = getenv("DIQT_CONV_F9"); return e ? atoi(e) : 1; }();      // 0: never, 2: any tile count
+    static const bool winoOn = [] { const char* e = getenv("DIQT_CONV_F9W"); return e ? atoi(e) != 0 : true; }();   // 0: direct only
     const bool k333 = kd == 3 && kh == 3 && kw == 3, k133 = kd == 1 && kh == 3 && kw == 3, k311 = kd == 3 && kh == 1 && kw == 1;
     if (!mode || !(k333 || k133 || k311) || Cin % F9_CH != 0 || Cin < F9_CH || Cout < 1) return false;
     if (D > 255 || H > 255 || W > 255) return false;                   // packed 8-bit halo coordinates
@@ -69,9 +81,19 @@ bool fwd9_plan(F9Geom& g, size_t& lds, unsigned& grid, int B, int D, int H, int 
     if (xb >= (1ull << 30) || yb >= (1ull << 30) || wb >= (1ull << 30)) return false;
     g.xBytes = (unsigned)xb; g.yBytes = (unsigned)yb; g.wBytes = (unsigned)wb; g.stats = nullptr;
     g.gx = g.gmean = g.grstd = g.ggamma = g.gbeta = g.gscale = g.gshift = nullptr; g.gG = 1; g.gcs = 0; g.gact = 0; g.gnp = nullptr;
-    g.gcoef = nullptr; g.gnaAct = 0;
+    g.gcoef = nullptr; g.gnaAct = 0; g.wOff = 0;
+    // Winograd F(2,3) along W: 1.5x fewer MFMAs per output.  The 256-voxel tile (8 accumulator tiles per wave) replaces both direct
+    // 3x3x3 tiles, split-K included; it reads the Winograd panels behind the direct ones, 36 instead of 27 per chunk.
+    const bool w333 = k333 && wino && winoOn && g.Wo % 2 == 0 && F9_333W::TW % 2 == 0;
+    auto try_wino = [&](bool split) {
+        const unsigned long long wwb = (unsigned long long)packedElems / 27ull * 36ull * 4ull;
+        if (!w333 || wwb >= (1ull << 30) || !f9_try<F9_333W>(g, lds, grid, mode, split)) return false;
+        g.variant = 7; g.wOff = (unsigned)packedElems; g.wBytes = (unsigned)wwb;
+        return true;
+    };
     // un-split launches first (the statistics query of the consumer's GroupNorm plans with maySplit = false and must see the same tiles)
     if (k333) {
+        if (try_wino(false)) return true;
         if (f9_try<F9_333_512>(g, lds, grid, mode, false)) { g.variant = 0; return true; }
         if (f9_try<F9_333_256>(g, lds, grid, mode, false)) { g.variant = 1; return true; }
     } else if (k133) {
@@ -85,6 +107,7 @@ bool fwd9_plan(F9Geom& g, size_t& lds, unsigned& grid, int B, int D, int H, int 
     if (!maySplit) return false;
     // split-K: the small tiles first (fewer slabs for the same number of workgroups)
     if (k333) {
+        if (try_wino(true)) return true;
         if (f9_try<F9_333_256>(g, lds, grid, mode, true)) { g.variant = 1; return true; }
         if (f9_try<F9_333_512>(g, lds, grid, mode, true)) { g.variant = 0; return true; }
     } else if (k133) {
@@ -98,8 +121,13 @@ bool fwd9_plan(F9Geom& g, size_t& lds, unsigned& grid, int B, int D, int H, int 
     return false;
 }
 
+static std::atomic<int> f9_last_variant{-1};      // process-wide: autograd runs backward launches on threads of its own
+int fwd9_take_last_variant() { return f9_last_variant.exchange(-1); }
+
 int fwd9_launch(const float* x, const float* packed, const float* bias, const float* residual, float* y, const F9Geom& g, size_t lds,
                 unsigned grid, void* stream) {
+    f9_last_variant = g.variant;
+    if (g.gx && g.variant == 7) { set_error("conv3d_fwd(v9): no Winograd variant with the GroupNorm-backward epilogue"); return DIQT_E_UNSUPPORTED; }
     if (g.gx) return g.variant == 0 ? fwd9_launch_d(x, packed, bias, residual, y, g, lds, grid, stream)
                                     : fwd9_launch_e(x, packed, bias, residual, y, g, lds, grid, stream);
     if (g.gcoef) {
@@ -108,6 +136,7 @@ int fwd9_launch(const float* x, const float* packed, const float* bias, const fl
             case 1: case 4: return fwd9_launch_g(x, packed, bias, residual, y, g, lds, grid, stream);
             case 2: return fwd9_launch_h(x, packed, bias, residual, y, g, lds, grid, stream);
             case 3: return fwd9_launch_i(x, packed, bias, residual, y, g, lds, grid, stream);
+            case 7: return fwd9_launch_k(x, packed, bias, residual, y, g, lds, grid, stream);
         }
         set_error("conv3d_fwd(v9, GroupNorm-apply prologue): no variant %d", g.variant);
         return DIQT_E_UNSUPPORTED;
@@ -116,6 +145,7 @@ int fwd9_launch(const float* x, const float* packed, const float* bias, const fl
         case 0: return f9_launch<F9_333_512>(x, packed, bias, residual, y, g, lds, grid, stream);
         case 2: case 3: case 4: return fwd9_launch_b(x, packed, bias, residual, y, g, lds, grid, stream);
         case 1: case 5: case 6: return fwd9_launch_c(x, packed, bias, residual, y, g, lds, grid, stream);
+        case 7: return fwd9_launch_j(x, packed, bias, residual, y, g, lds, grid, stream);
     }
     set_error("conv3d_fwd(v9): no variant %d", g.variant);
     return DIQT_E_UNSUPPORTED;

@@ -19,21 +19,33 @@ constexpr int F9_WSLOT = F9_TG * F9_WTAP;
 
 // Filter (KD, KH, KW), tile (TD, TH, TW) and voxel blocks per wave NVB (4: 512-voxel tile, 2: 256).  A voxel BLOCK is 4 rows x 8
 // columns of one plane = the 32 rows of an accumulator tile; block id = (plane * TH/4 + row group) * TW/8 + column group, wave = id / NVB.
-template <int KD_, int KH_, int KW_, int TD_, int TH_, int TW_, int NVB_>
+// WINO: Winograd F(2,3) along W (3x3x3 filters, TD = 4 = one plane per wave): the 32 rows of an accumulator tile are the output PAIRS
+// of a plane (8 rows x 4 pairs, row = l31 / 4, pair = l31 % 4), a tap is (kd, kh, j) with j = 0..3 the Winograd position (its own two
+// accumulator tiles: 8 per wave, as NVB = 4), and the halo rows are padded to an odd width (11 voxels) so that the 2-voxel stride of
+// the pair reads keeps ds_read_b128 at the 4-way bank sharing of the direct layout instead of 8-way.
+template <int KD_, int KH_, int KW_, int TD_, int TH_, int TW_, int NVB_, bool WINO_ = false>
 struct F9Cfg {
+    static constexpr bool WINO = WINO_;
     static constexpr int KD = KD_, KH = KH_, KW = KW_, TD = TD_, TH = TH_, TW = TW_, NVB = NVB_;
-    static constexpr int T = KD * KH * KW, NSTEP = (T + F9_TG - 1) / F9_TG;
-    static constexpr int HD = TD + KD - 1, HH = TH + KH - 1, HWd = TW + KW - 1, HV = HD * HH * HWd;
+    static constexpr int T = WINO ? KD * KH * 4 : KD * KH * KW, NSTEP = (T + F9_TG - 1) / F9_TG;
+    static constexpr int HD = TD + KD - 1, HH = TH + KH - 1, HWd = TW + KW - 1 + (WINO ? 1 : 0), HV = HD * HH * HWd;
     static constexpr int HB = (HV * F9_ROWB + 4095) / 4096 * 4096;      // halo image in whole 1-KiB DMA instructions, the same count per wave
     static constexpr int NPH = HB / 4096;                              // halo DMA pieces per wave and chunk
     static constexpr int NBH = TH / 4, NBW = TW / 8;
     static constexpr int LDS_BYTES = 2 * HB + F9_NWS * F9_WSLOT;
     static_assert(TD * TH * TW == 128 * NVB && TH % 4 == 0 && TW % 8 == 0, "tile = 4 waves x NVB blocks of 4 x 8 voxels");
+    static_assert(!WINO || (KD == 3 && KH == 3 && KW == 3 && TD == 4 && TH == 8 && TW == 8), "Winograd tile: one 8 x 8 plane per wave");
     static_assert(HV * F9_ROWB <= 65536 && LDS_BYTES <= 160 * 1024, "halo image: 16-bit LDS immediates, two images + weight ring in LDS");
     static_assert(NPH <= 16, "halo piece descriptors live in registers");
     static_assert(T >= 3, "the prologue issues the weight groups of two steps");
     __host__ __device__ static constexpr int tapoff(int t) { return ((t / (KW * KH)) * HH + (t / KW) % KH) * HWd + t % KW; }
     __host__ __device__ static constexpr int blockrow(int id) { return ((id / (NBH * NBW)) * HH + ((id / NBW) % NBH) * 4) * HWd + (id % NBW) * 8; }
+    // Winograd tap t = (kd kh, j): halo row of its (kd, kh) and the two input columns d_a, d_b of position j (operand d_a + sgn d_b):
+    // j 0: d0 - d2, 1: d1 + d2, 2: d2 - d1, 3: d1 - d3
+    __host__ __device__ static constexpr int wrow(int t) { return ((t / 4) / KH * HH + (t / 4) % KH) * HWd; }
+    __host__ __device__ static constexpr int wcolA(int t) { return t % 4 == 0 ? 0 : t % 4 == 2 ? 2 : 1; }
+    __host__ __device__ static constexpr int wcolB(int t) { return t % 4 == 0 ? 2 : t % 4 == 1 ? 2 : t % 4 == 2 ? 1 : 3; }
+    __host__ __device__ static constexpr bool wadd(int t) { return t % 4 == 1; }
 };
 
 __device__ __forceinline__ void f9_dma(__amdgpu_buffer_rsrc_t rs, unsigned lds, unsigned voff) {
@@ -85,6 +97,7 @@ __global__ __launch_bounds__(256, 1) void conv_fwd9_kernel(const float* __restri
                                                            const float* __restrict__ bias, const float* __restrict__ residual,
                                                            float* __restrict__ y, F9Geom g) {
     static_assert(!(GNB && GNA) && (!GNA || C::NSTEP >= 3), "GroupNorm-apply prologue: forward launches of filters with >= 5 taps");
+    static_assert(!(C::WINO && GNB), "Winograd tiles: forward launches only");
     constexpr int NSPREAD = GNA ? C::NSTEP - 2 : (C::NSTEP > 1 ? C::NSTEP - 1 : 1);   // steps that issue halo pieces of the next chunk
     auto nh_in_step = [](int s_) constexpr { int n_ = 0; for (int r = 0; r < C::NPH; ++r) n_ += (r * NSPREAD / C::NPH == s_) ? 1 : 0; return n_; };
     constexpr int T = C::T, NSTEP = C::NSTEP, HB = C::HB, NPH = C::NPH, NVB = C::NVB, HH = C::HH, HWd = C::HWd, HV = C::HV;
@@ -226,9 +239,10 @@ __global__ __launch_bounds__(256, 1) void conv_fwd9_kernel(const float* __restri
         }
     };
 
-    f32x16 acc[NVB][2];
+    constexpr int NACC = C::WINO ? 4 : NVB;                // accumulator tile pairs: voxel blocks, or the 4 Winograd positions
+    f32x16 acc[NACC][2];
 #pragma unroll
-    for (int vb = 0; vb < NVB; ++vb)
+    for (int vb = 0; vb < NACC; ++vb)
 #pragma unroll
         for (int ch = 0; ch < 2; ++ch)
 #pragma unroll
@@ -241,7 +255,9 @@ __global__ __launch_bounds__(256, 1) void conv_fwd9_kernel(const float* __restri
 
     // per-lane operand bases: A = halo row of the lane's voxel inside its block (row l31 / 8, column l31 % 8) + its 16-byte half of a
     // k-group; the blocks of this wave start at rows blockrow(wave * NVB + vb) (wave-uniform), taps add compile-time row offsets
-    const unsigned aLane = (unsigned)((l31 >> 3) * HWd + (l31 & 7)) * ROWB + (unsigned)hf * 16u;
+    // (Winograd: the lane's output pair, row l31 / 4, first input column 2 (l31 % 4); the wave's plane is its block)
+    const unsigned aLane = C::WINO ? (unsigned)((l31 >> 2) * HWd + 2 * (l31 & 3)) * ROWB + (unsigned)hf * 16u
+                                   : (unsigned)((l31 >> 3) * HWd + (l31 & 7)) * ROWB + (unsigned)hf * 16u;
     const unsigned bLane = (unsigned)l31 * ROWB + (unsigned)hf * 16u;
     int brow[NVB], bd[NVB], bh4[NVB], bw8[NVB];            // halo row / plane / first row / first column of the wave's blocks
 #pragma unroll
@@ -326,6 +342,65 @@ __global__ __launch_bounds__(256, 1) void conv_fwd9_kernel(const float* __restri
             __builtin_amdgcn_sched_barrier(0);                                                                       \
         }                                                                                                            \
     } while (0)
+            if constexpr (C::WINO) {
+                // ---- Winograd steps: taps 2s, 2s + 1 = (kd kh, j), (kd kh, j + 1); fragments [tap in step][k-group] of the raw inputs
+                //      d_a, d_b and [tap in step][co half][k-group] of the weights, ping-pong between even and odd steps ----
+                const char* hw = smem9 + hcur * HB + aLane + wave * (HH * HWd * ROWB);
+                f32x4v Xa0[2][2], Xb0[2][2], W0[2][2][2], Xa1[2][2], Xb1[2][2], W1[2][2][2];
+// read u (0..15) of step S's fragments: k-group 0 of both taps first (u / 8 = k-group), per tap d_a, d_b, co half 0, co half 1
+#define F9W_RD1(Xa, Xb, Wv, S, WS, u)                                                                                \
+    do {                                                                                                             \
+        const int q_ = (u) / 8, t_ = ((u) / 4) % 2, k_ = (u) % 4, tap_ = 2 * (S) + t_;                              \
+        const char* wb_ = smem9 + 2 * HB + (WS) * WSLOT + t_ * WTAP + bLane;                                         \
+        if (k_ == 0) Xa[t_][q_] = *reinterpret_cast<const f32x4v*>(hw + (C::wrow(tap_) + C::wcolA(tap_)) * ROWB + q_ * 32);   \
+        else if (k_ == 1) Xb[t_][q_] = *reinterpret_cast<const f32x4v*>(hw + (C::wrow(tap_) + C::wcolB(tap_)) * ROWB + q_ * 32); \
+        else Wv[t_][k_ - 2][q_] = *reinterpret_cast<const f32x4v*>(wb_ + (k_ - 2) * 32 * ROWB + q_ * 32);            \
+    } while (0)
+// the 32 MFMAs of step S in 16 fenced groups of two; behind group u read u of the next step (PF) and slice u of the GroupNorm-apply
+// rewrite.  The input transform of k-group q (one add / subtract per operand element) sits in front of its first MFMA.
+#define F9W_STEP(Xa, Xb, Wv, Xn, Xbn, Wn, S, PF, WSN)                                                               \
+    do {                                                                                                             \
+        _Pragma("unroll") for (int u = 0; u < 16; ++u) {                                                             \
+            if (u % 8 == 0) {                       /* in place: d_a becomes the operand */                          \
+                _Pragma("unroll") for (int t_ = 0; t_ < 2; ++t_)                                                     \
+                    Xa[t_][u / 8] = C::wadd(2 * (S) + t_) ? Xa[t_][u / 8] + Xb[t_][u / 8] : Xa[t_][u / 8] - Xb[t_][u / 8];   \
+            }                                                                                                        \
+            _Pragma("unroll") for (int m = 2 * u; m < 2 * u + 2; ++m) {                                              \
+                const int q = m / 16, e = (m / 4) % 4, t_ = (m / 2) % 2, ch = m % 2, j_ = (2 * (S) + t_) % 4;       \
+                acc[j_][ch] = __builtin_amdgcn_mfma_f32_32x32x2f32(Xa[t_][q][e], Wv[t_][ch][q][e], acc[j_][ch], 0, 0, 0);   \
+            }                                                                                                        \
+            if (PF) F9W_RD1(Xn, Xbn, Wn, (S) + 1, WSN, u);                                                           \
+            if constexpr (GNA != 0) gna_slice(S, u, 16, hcur ^ 1);                                                   \
+            __builtin_amdgcn_sched_barrier(0);                                                                       \
+        }                                                                                                            \
+    } while (0)
+#pragma unroll
+                for (int u = 0; u < 16; ++u) F9W_RD1(Xa0, Xb0, W0, 0, wcur, u);     // cold read of the chunk's first step
+#pragma unroll
+                for (int s = 0; s < NSTEP; ++s) {
+                    const int wnext = wcur == NWS - 1 ? 0 : wcur + 1;
+                    const int wnn = wnext == NWS - 1 ? 0 : wnext + 1;
+                    {       // this step's DMA, as below: the weight group two steps ahead, the next chunk's halo pieces
+                        const int s2 = s + 2 < NSTEP ? s + 2 : s + 2 - NSTEP;
+                        const int c2 = s + 2 < NSTEP ? c : cNext;
+                        const unsigned slot = wringBase + (unsigned)wnn * WSLOT;
+                        dma_w(c2, 2 * s2, slot, 0);
+                        dma_w(c2, 2 * s2 + 1, slot, 1);
+#pragma unroll
+                        for (int r = 0; r < NPH; ++r)
+                            if (r * NSPREAD / NPH == s) dma_h(r, hbufN, cNext);
+                    }
+                    if (s % 2 == 0) F9W_STEP(Xa0, Xb0, W0, Xa1, Xb1, W1, s, s + 1 < NSTEP, wnext);
+                    else F9W_STEP(Xa1, Xb1, W1, Xa0, Xb0, W0, s, s + 1 < NSTEP, wnext);
+                    if (GNA != 0 && s + 1 == NSTEP) f9_chunk_end_gna();
+                    else f9_step_end(s + 1 == NSTEP ? 0 : nh_in_step(s));
+                    wcur = wnext;
+                }
+#undef F9W_STEP
+#undef F9W_RD1
+                hcur ^= 1;
+                continue;
+            }
             F9_RD(A0, B0, 0, wcur, 0);                     // cold read of the chunk's first tap (prefetched across chunks would be the next step)
 #pragma unroll
             for (int s = 0; s < NSTEP; ++s) {
@@ -399,8 +474,57 @@ __global__ __launch_bounds__(256, 1) void conv_fwd9_kernel(const float* __restri
                 coef(co1, gA1, gB1, gm1, gr1);
             }
             const auto rs_g = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.gx), 0, GNB ? (int)g.yBytes : 0, 0x00020000);
+            if constexpr (C::WINO) {
+                // Winograd output transform, lane-local: register i of position j's tile is pair (i & 3) of row 2 (i >> 2) + hf of the
+                // wave's plane; y(2p) = m0 + m1 + m2, y(2p + 1) = m1 - m2 - m3, then bias, residual and the statistics of the final y
+                const int od = d0 + wave;
 #pragma unroll
-            for (int vb = 0; vb < NVB; ++vb) {
+                for (int hv = 0; hv < 4; ++hv) {           // four quarters of 4 registers: 16 residual registers at a time
+                    unsigned offs[2][4];
+                    float r0[2][4], r1[2][4];
+#pragma unroll
+                    for (int ii = 0; ii < 4; ++ii) {
+                        const int i = 4 * hv + ii, oh = h0 + 2 * (i >> 2) + hf;
+#pragma unroll
+                        for (int o = 0; o < 2; ++o) {
+                            const int ow = w0 + 2 * (i & 3) + o;
+                            const bool ok = od < g.Do && oh < g.Ho && ow < g.Wo;
+                            offs[o][ii] = ok ? (unsigned)((((tb * g.Do + od) * g.Ho + oh) * g.Wo + ow) * g.Cout) * 4u : OOB;
+                        }
+                    }
+                    if (residual) {
+#pragma unroll
+                        for (int ii = 0; ii < 4; ++ii)
+#pragma unroll
+                            for (int o = 0; o < 2; ++o) {
+                                r0[o][ii] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_r, offs[o][ii] + c0o, 0, 0));
+                                r1[o][ii] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_r, offs[o][ii] + c1o, 0, 0));
+                            }
+                    }
+#pragma unroll
+                    for (int ii = 0; ii < 4; ++ii) {
+                        const int i = 4 * hv + ii;
+                        float v[2][2];                     // [output of the pair][co half]
+#pragma unroll
+                        for (int ch = 0; ch < 2; ++ch) {
+                            v[0][ch] = (acc[0][ch][i] + acc[1][ch][i]) + acc[2][ch][i];
+                            v[1][ch] = (acc[1][ch][i] - acc[2][ch][i]) - acc[3][ch][i];
+                        }
+#pragma unroll
+                        for (int o = 0; o < 2; ++o) {
+                            float v0 = v[o][0] + bias0, v1 = v[o][1] + bias1;
+                            if (residual) { v0 += r0[o][ii]; v1 += r1[o][ii]; }
+                            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v0), rs_y, offs[o][ii] + c0o, 0, 0);
+                            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v1), rs_y, offs[o][ii] + c1o, 0, 0);
+                            if (g.stats && offs[o][ii] != OOB) { cs0 += v0; cq0 = fmaf(v0, v0, cq0); cs1 += v1; cq1 = fmaf(v1, v1, cq1); }
+                        }
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) { acc[j][0][i] = 0.f; acc[j][1][i] = 0.f; }
+                    }
+                }
+            }
+#pragma unroll
+            for (int vb = 0; vb < (C::WINO ? 0 : NVB); ++vb) {
                 const int od = d0 + bd[vb];
                 unsigned offs[16];
                 float r0[16], r1[16];
@@ -484,6 +608,7 @@ using F9_133_B = F9Cfg<1, 3, 3, 2, 16, 16, 4>;
 using F9_133_C = F9Cfg<1, 3, 3, 4, 8, 8, 2>;         // 8x8 frames: 256-voxel tiles
 using F9_311_512 = F9Cfg<3, 1, 1, 8, 8, 8, 4>;       // temporal convs of the pseudo-3D blocks
 using F9_311_256 = F9Cfg<3, 1, 1, 4, 8, 8, 2>;
+using F9_333W = F9Cfg<3, 3, 3, 4, 8, 8, 2, true>;     // Winograd F(2,3) along W, 256-voxel tiles (variant 7)
 
 // launchers of the variants compiled in the other translation units
 int fwd9_launch_b(const float* x, const float* packed, const float* bias, const float* residual, float* y, const F9Geom& g, size_t lds,
@@ -501,6 +626,11 @@ int fwd9_launch_f(const float* x, const float* packed, const float* bias, const 
 int fwd9_launch_g(const float* x, const float* packed, const float* bias, const float* residual, float* y, const F9Geom& g, size_t lds,
                   unsigned grid, void* stream);
 int fwd9_launch_h(const float* x, const float* packed, const float* bias, const float* residual, float* y, const F9Geom& g, size_t lds,
+                  unsigned grid, void* stream);
+// ... and of the Winograd variant, plain and with the GroupNorm-apply prologue (Mish)
+int fwd9_launch_j(const float* x, const float* packed, const float* bias, const float* residual, float* y, const F9Geom& g, size_t lds,
+                  unsigned grid, void* stream);
+int fwd9_launch_k(const float* x, const float* packed, const float* bias, const float* residual, float* y, const F9Geom& g, size_t lds,
                   unsigned grid, void* stream);
 int fwd9_launch_i(const float* x, const float* packed, const float* bias, const float* residual, float* y, const F9Geom& g, size_t lds,
                   unsigned grid, void* stream);

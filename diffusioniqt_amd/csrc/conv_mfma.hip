@@ -102,6 +102,37 @@ __global__ void conv_pack_weight_kernel(const float* __restrict__ w, float* __re
     }
 }
 
+// Winograd F(2,3) panels of a 3x3x3 filter (conv_fwd9_kernel variant 7), behind the direct pack in modes 2 / 3:
+// packedW[((chunk*36 + (kd*3 + kh)*4 + j)*CoutPad + co)*32 + k] = U_j of the kw-taps g0, g1, g2 of the effective filter (mode 0 / 1 as
+// above): U0 = g0, U1 = (g0 + g1 + g2) / 2, U2 = (g0 - g1 + g2) / 2, U3 = g2, in fp32 in this order
+__global__ void conv_pack_wino_kernel(const float* __restrict__ w, float* __restrict__ packed, int Cout, int Cin, int mode,
+                                      int CoutPadEff, size_t total) {
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int k = (int)(i % CK);
+        size_t r = i / CK;
+        const int o = (int)(r % CoutPadEff);
+        r /= CoutPadEff;
+        const int tw = (int)(r % 36), chunk = (int)(r / 36);
+        const int kdh = tw / 4, j = tw % 4, in = chunk * CK + k;
+        float gk[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+        for (int kx = 0; kx < 3; ++kx) {
+            const int tap = kdh * 3 + kx;
+            if (mode == 0) {
+                if (o < Cout && in < Cin) gk[kx] = w[((size_t)o * Cin + in) * 27 + tap];
+            } else {
+                if (o < Cin && in < Cout) gk[kx] = w[((size_t)in * Cin + o) * 27 + (26 - tap)];
+            }
+        }
+        float v;
+        if (j == 0) v = gk[0];
+        else if (j == 1) v = 0.5f * ((gk[0] + gk[1]) + gk[2]);
+        else if (j == 2) v = 0.5f * ((gk[0] - gk[1]) + gk[2]);
+        else v = gk[2];
+        packed[i] = v;
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // forward / backward-data
 // ---------------------------------------------------------------------------------------------
@@ -1606,11 +1637,27 @@ static inline int smallcin_pad(int Cin, int T) {
     return Cin == 3 ? 4 : Cin;
 }
 
+// floats of the Winograd panels that modes 2 / 3 of diqt_conv_pack_weight append for an effective (out, in) filter: 3x3x3 filters
+// with a multiple of 16 input channels (the launches conv_fwd9_kernel takes), 0 otherwise
+extern "C" size_t diqt_conv_packed_wino_elems(int Cout, int Cin, int kd, int kh, int kw) {
+    if (Cout <= 0 || Cin <= 0 || kd != 3 || kh != 3 || kw != 3 || Cin % 16 != 0 || smallcin_pad(Cin, 27)) return 0;
+    return (size_t)cdiv(Cin, CK) * 36 * (cdiv(Cout, NT) * NT) * CK;
+}
+
 extern "C" int diqt_conv_pack_weight(const float* w, float* packed, int Cout, int Cin, int kd, int kh, int kw,
                                      int mode, void* stream) {
     DIQT_REQUIRE(w && packed, DIQT_E_ALIGN, "conv_pack_weight: null pointer");
-    DIQT_REQUIRE(Cout > 0 && Cin > 0 && kd > 0 && kh > 0 && kw > 0 && (mode == 0 || mode == 1), DIQT_E_SHAPE,
+    DIQT_REQUIRE(Cout > 0 && Cin > 0 && kd > 0 && kh > 0 && kw > 0 && mode >= 0 && mode <= 3, DIQT_E_SHAPE,
                  "conv_pack_weight: bad shape/mode");
+    if (mode >= 2) {        // the direct pack of mode - 2, then (if any) the Winograd panels of the same effective filter
+        const int m = mode - 2, outEff = m == 0 ? Cout : Cin, inEff = m == 0 ? Cin : Cout;
+        int rc = diqt_conv_pack_weight(w, packed, Cout, Cin, kd, kh, kw, m, stream);
+        const size_t nW = diqt_conv_packed_wino_elems(outEff, inEff, kd, kh, kw);
+        if (rc || nW == 0) return rc;
+        hipLaunchKernelGGL(conv_pack_wino_kernel, dim3(grid_for(nW, 256)), dim3(256), 0, (hipStream_t)stream, w,
+                           packed + diqt_conv_packed_elems(outEff, inEff, kd, kh, kw), Cout, Cin, m, cdiv(outEff, NT) * NT, nW);
+        return check_launch("conv_pack_weight(Winograd)");
+    }
     const int T = kd * kh * kw;
     if (const int CINP = smallcin_pad(mode == 0 ? Cin : Cout, T)) {
         const int CoutPadE = cdiv(mode == 0 ? Cout : Cin, NT) * NT, nCh = cdiv(T * CINP, CK);
@@ -1653,8 +1700,16 @@ __global__ __launch_bounds__(256) void conv_fwd_reduce_kernel(const float* __res
     }
 }
 
-extern "C" size_t diqt_conv3d_fwd_workspace_bytes(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw,
-                                                  int pd, int ph, int pw, int epd, int eph, int epw) {
+// Does a packed buffer of packed_elems floats hold the Winograd panels behind the direct pack (pack modes 2 / 3)?  1: yes, 0: the
+// direct pack alone, -1: shorter than the direct pack.  Only the _pk entry points ask: the others take the direct tiles.
+static int wino_layout(int Cout, int Cin, int kd, int kh, int kw, size_t packed_elems) {
+    const size_t n = diqt_conv_packed_elems(Cout, Cin, kd, kh, kw), nw = diqt_conv_packed_wino_elems(Cout, Cin, kd, kh, kw);
+    if (packed_elems < n) return -1;
+    return nw > 0 && packed_elems >= n + nw ? 1 : 0;
+}
+
+static size_t fwd_workspace_bytes(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw, int epd,
+                                  int eph, int epw, bool wino) {
     ConvGeom g;
     if (make_geom(g, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw)) return 0;
     const int ks = fwd_ksplit(g);
@@ -1664,7 +1719,7 @@ extern "C" size_t diqt_conv3d_fwd_workspace_bytes(int B, int D, int H, int W, in
         size_t l9;
         unsigned gr9;
         if (Cin % 4 == 0 && !smallcin_pad(Cin, kd * kh * kw) &&
-            fwd9_plan(g9, l9, gr9, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, diqt_conv_packed_elems(Cout, Cin, kd, kh, kw), true) &&
+            fwd9_plan(g9, l9, gr9, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, diqt_conv_packed_elems(Cout, Cin, kd, kh, kw), true, wino) &&
             g9.ksplit > 1) {
             const size_t n9 = (size_t)g9.ksplit * g.B * g.Do * g.Ho * g.Wo * g.Cout * sizeof(float);
             if (n9 > need) need = n9;
@@ -1672,10 +1727,20 @@ extern "C" size_t diqt_conv3d_fwd_workspace_bytes(int B, int D, int H, int W, in
     }
     return need;
 }
+extern "C" size_t diqt_conv3d_fwd_workspace_bytes(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw,
+                                                  int pd, int ph, int pw, int epd, int eph, int epw) {
+    return fwd_workspace_bytes(B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, false);
+}
+extern "C" size_t diqt_conv3d_fwd_workspace_bytes_pk(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw,
+                                                     int pd, int ph, int pw, int epd, int eph, int epw, size_t packed_elems) {
+    return fwd_workspace_bytes(B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw,
+                               wino_layout(Cout, Cin, kd, kh, kw, packed_elems) == 1);
+}
 
 static int conv3d_fwd_impl(const float* x, const float* packed, const float* bias, const float* residual,
                            float* y, void* workspace, size_t workspace_bytes, int B, int D, int H, int W, int Cin, int Cout,
-                           int kd, int kh, int kw, int pd, int ph, int pw, int epd, int eph, int epw, void* stream, float* stats);
+                           int kd, int kh, int kw, int pd, int ph, int pw, int epd, int eph, int epw, void* stream, float* stats,
+                           bool wino = false);
 
 extern "C" int diqt_conv3d_fwd(const float* x, const float* packed, const float* bias, const float* residual,
                                float* y, int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw,
@@ -1722,10 +1787,15 @@ static bool fwd8_plan(const ConvGeom& g, ConvGeom& g8, size_t& lds) {
 // per-tile output statistics are produced by the buffer-path kernel of an unsplit launch; returns the number of tiles per batch
 // entry (the `nblk` of the [B][nblk][2][Cout] partial layout) or 0 when this shape would take another path
 static int fwd_stats_blocks_impl(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw, int epd,
-                                 int eph, int epw, bool neighbours);
+                                 int eph, int epw, bool neighbours, bool wino = false);
 extern "C" int diqt_conv3d_fwd_stats_blocks(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph,
                                             int pw, int epd, int eph, int epw) {
     return fwd_stats_blocks_impl(B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, false);
+}
+extern "C" int diqt_conv3d_fwd_stats_blocks_pk(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph,
+                                               int pw, int epd, int eph, int epw, size_t packed_elems) {
+    return fwd_stats_blocks_impl(B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, false,
+                                 wino_layout(Cout, Cin, kd, kh, kw, packed_elems) == 1);
 }
 // the same for diqt_conv3d_fwd_neighbours (which never takes conv_fwd9_kernel: that kernel has no neighbour addressing)
 extern "C" int diqt_conv3d_fwd_neighbours_stats_blocks(int f, int A, int Cin, int Cout, int k) {
@@ -1733,7 +1803,7 @@ extern "C" int diqt_conv3d_fwd_neighbours_stats_blocks(int f, int A, int Cin, in
     return fwd_stats_blocks_impl(f * f * f, A, A, A, Cin, Cout, k, k, k, k / 2, k / 2, k / 2, 0, 0, 0, true);
 }
 static int fwd_stats_blocks_impl(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw, int epd,
-                                 int eph, int epw, bool neighbours) {
+                                 int eph, int epw, bool neighbours, bool wino) {
     static const bool off = [] { const char* e = getenv("DIQT_CONV_NOSTATS"); return e && e[0] == '1'; }();
     static const bool nobuf = [] { const char* e = getenv("DIQT_CONV_NOBUF"); return e && e[0] == '1'; }();
     ConvGeom g;
@@ -1752,7 +1822,7 @@ static int fwd_stats_blocks_impl(int B, int D, int H, int W, int Cin, int Cout, 
         size_t l9;
         unsigned gr9;
         if (!neighbours && Cin % 4 == 0 && fwd_ksplit(g) <= 1 && !smallcin_pad(Cin, kd * kh * kw) &&
-            fwd9_plan(g9, l9, gr9, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, diqt_conv_packed_elems(Cout, Cin, kd, kh, kw), false))
+            fwd9_plan(g9, l9, gr9, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, diqt_conv_packed_elems(Cout, Cin, kd, kh, kw), false, wino))
             return g9.tilesD * g9.tilesH * g9.tilesW;                          // conv_fwd9_kernel: one row per 512- / 256-voxel tile
     }
     if (fwd8_plan(g, g8, lds8)) return g8.tilesD * g8.tilesH * g8.tilesW;      // the 8-wave kernel writes one row per 256-voxel tile
@@ -1775,7 +1845,7 @@ extern "C" int diqt_conv3d_fwd_kernel_id(int B, int D, int H, int W, int Cin, in
         F9Geom g9;
         size_t l9;
         unsigned gr9;
-        if (fwd9_plan(g9, l9, gr9, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, diqt_conv_packed_elems(Cout, Cin, kd, kh, kw), true))
+        if (fwd9_plan(g9, l9, gr9, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, diqt_conv_packed_elems(Cout, Cin, kd, kh, kw), true, false))
             return 4;                // incl. its split-K form (callers that pass the workspace diqt_conv3d_fwd_workspace_bytes asks for)
     }
     if (fwd_ksplit(g) > 1) return 0;
@@ -1786,6 +1856,24 @@ extern "C" int diqt_conv3d_fwd_kernel_id(int B, int D, int H, int W, int Cin, in
     return 0;
 }
 
+// conv_fwd9_kernel's variant for a launch diqt_conv3d_fwd_kernel_id routes to it, given a packed buffer of packed_elems floats
+// (F9Geom::variant; 7: Winograd F(2,3), only with the panels of pack modes 2 / 3 and diqt_conv3d_fwd_pk), -1 otherwise
+extern "C" int diqt_conv3d_fwd9_variant(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw,
+                                        int epd, int eph, int epw, size_t packed_elems) {
+    if (diqt_conv3d_fwd_kernel_id(B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw) != 4) return -1;
+    F9Geom g9;
+    size_t l9;
+    unsigned gr9;
+    if (!fwd9_plan(g9, l9, gr9, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, diqt_conv_packed_elems(Cout, Cin, kd, kh, kw),
+                   true, wino_layout(Cout, Cin, kd, kh, kw, packed_elems) == 1))
+        return -1;
+    return g9.variant;
+}
+
+// which conv_fwd9_kernel variant the process's last launch of it ran (F9Geom::variant, 7: Winograd), -1 if none since the last
+// call: a test / profiler observable of the launch itself, not of a plan
+extern "C" int diqt_get_last_conv_fwd9_variant() { return fwd9_take_last_variant(); }
+
 extern "C" int diqt_conv3d_fwd_ex(const float* x, const float* packed, const float* bias, const float* residual, float* y,
                                   float* stats, void* workspace, size_t workspace_bytes, int B, int D, int H, int W, int Cin,
                                   int Cout, int kd, int kh, int kw, int pd, int ph, int pw, int epd, int eph, int epw, void* stream) {
@@ -1793,6 +1881,20 @@ extern "C" int diqt_conv3d_fwd_ex(const float* x, const float* packed, const flo
                  DIQT_E_UNSUPPORTED, "conv3d_fwd_ex: this shape does not produce output statistics (diqt_conv3d_fwd_stats_blocks == 0)");
     return conv3d_fwd_impl(x, packed, bias, residual, y, workspace, workspace_bytes, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw,
                            epd, eph, epw, stream, stats);
+}
+// diqt_conv3d_fwd_ex with the length of the packed buffer: a buffer that holds the Winograd panels behind the direct pack (pack modes
+// 2 / 3) lets the 3x3x3 launches with an even output width take conv_fwd9_kernel's Winograd tile; a shorter one than the direct pack
+// is refused.  Statistics rows and workspace: diqt_conv3d_fwd_stats_blocks_pk / _workspace_bytes_pk with the same length.
+extern "C" int diqt_conv3d_fwd_pk(const float* x, const float* packed, size_t packed_elems, const float* bias, const float* residual,
+                                  float* y, float* stats, void* workspace, size_t workspace_bytes, int B, int D, int H, int W, int Cin,
+                                  int Cout, int kd, int kh, int kw, int pd, int ph, int pw, int epd, int eph, int epw, void* stream) {
+    const int lay = wino_layout(Cout, Cin, kd, kh, kw, packed_elems);
+    DIQT_REQUIRE(lay >= 0, DIQT_E_SHAPE, "conv3d_fwd_pk: packed buffer of %zu floats, the direct pack alone needs %zu", packed_elems,
+                 diqt_conv_packed_elems(Cout, Cin, kd, kh, kw));
+    DIQT_REQUIRE(!stats || diqt_conv3d_fwd_stats_blocks_pk(B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, packed_elems) > 0,
+                 DIQT_E_UNSUPPORTED, "conv3d_fwd_pk: this shape does not produce output statistics (diqt_conv3d_fwd_stats_blocks_pk == 0)");
+    return conv3d_fwd_impl(x, packed, bias, residual, y, workspace, workspace_bytes, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw,
+                           epd, eph, epw, stream, stats, lay == 1);
 }
 
 // The backward-data pass of a conv that sits behind a fused GroupNorm + scale/shift + Mish/SiLU (Block.forward: GN -> act -> conv,
@@ -1829,7 +1931,7 @@ extern "C" int diqt_conv3d_fwd_gnbwd_blocks(int B, int D, int H, int W, int Cin,
     size_t l9;
     unsigned gr9;
     if (off || Cin % 4 != 0 || smallcin_pad(Cin, kd * kh * kw) || (kd == 3 && kh == 1 && kw == 1)) return 0;     // (3,1,1): no such instantiation
-    if (!fwd9_plan(g9, l9, gr9, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, diqt_conv_packed_elems(Cout, Cin, kd, kh, kw), false))
+    if (!fwd9_plan(g9, l9, gr9, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, diqt_conv_packed_elems(Cout, Cin, kd, kh, kw), false, false))
         return 0;
     return g9.tilesD * g9.tilesH * g9.tilesW;
 }
@@ -1847,7 +1949,7 @@ extern "C" int diqt_conv3d_fwd_gnbwd(const float* x, const float* packed, float*
     unsigned gr9;
     DIQT_REQUIRE(diqt_conv3d_fwd_gnbwd_blocks(B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw) > 0 &&
                      fwd9_plan(g9, l9, gr9, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw,
-                               diqt_conv_packed_elems(Cout, Cin, kd, kh, kw), false),
+                               diqt_conv_packed_elems(Cout, Cin, kd, kh, kw), false, false),
                  DIQT_E_UNSUPPORTED, "conv3d_fwd_gnbwd: shape not taken by conv_fwd9_kernel (diqt_conv3d_fwd_gnbwd_blocks == 0)");
     g9.stats = partials;
     g9.gx = gn_x; g9.gmean = mean; g9.grstd = rstd; g9.ggamma = gamma; g9.gbeta = beta; g9.gscale = scale; g9.gshift = shift;
@@ -1871,7 +1973,7 @@ extern "C" int diqt_conv3d_fwd_gnbwd(const float* x, const float* packed, float*
 static int conv3d_fwd_one(const float* x, const float* packed, const float* bias, const float* residual,
                           float* y, void* workspace, size_t workspace_bytes, int B, int D, int H, int W, int Cin, int Cout,
                           int kd, int kh, int kw, int pd, int ph, int pw, int epd, int eph, int epw, void* stream, float* stats,
-                          int subF = 0);
+                          int subF = 0, bool wino = false);
 
 // Block.forward on the sampling path (GroupNorm -> (scale + 1) x + shift -> Mish / SiLU -> conv; imagen_pytorch3D.py:546-566,
 // imagen_video.py:680-697) as ONE launch: x is the RAW GroupNorm input and conv_fwd9_kernel's GroupNorm-apply instantiation rewrites
@@ -1879,14 +1981,14 @@ static int conv3d_fwd_one(const float* x, const float* packed, const float* bias
 // write of the whole tensor per conv) is gone.  coef[2][B][Cin] = (A, Bc) from diqt_gn_coef_from_partials / diqt_gn_coef.
 // diqt_conv3d_fwd_gn_supported: 1 when conv_fwd9_kernel takes the launch (given the workspace diqt_conv3d_fwd_workspace_bytes asks
 // for) and has the instantiation for this filter and activation; otherwise run diqt_gn_act_fwd + diqt_conv3d_fwd_ex.
-extern "C" int diqt_conv3d_fwd_gn_supported(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw,
-                                            int epd, int eph, int epw, int act) {
+static int fwd_gn_supported(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw, int epd, int eph,
+                            int epw, int act, bool wino) {
     static const bool off = [] { const char* e = getenv("DIQT_CONV_NOGNA"); return e && e[0] == '1'; }();       // A/B switch
     F9Geom g9;
     size_t l9;
     unsigned gr9;
     if (off || Cin % 4 != 0 || smallcin_pad(Cin, kd * kh * kw)) return 0;
-    if (!fwd9_plan(g9, l9, gr9, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, diqt_conv_packed_elems(Cout, Cin, kd, kh, kw), true))
+    if (!fwd9_plan(g9, l9, gr9, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, diqt_conv_packed_elems(Cout, Cin, kd, kh, kw), true, wino))
         return 0;
     if (!fwd9_gna_available(g9.variant, act)) return 0;
     // Every 64-channel output block of a tile rewrites its own copy of the halo, so the rewrite grows with Cout / 64 while the pass it
@@ -1896,26 +1998,36 @@ extern "C" int diqt_conv3d_fwd_gn_supported(int B, int D, int H, int W, int Cin,
     if (kd == 1) return g9.nNt <= 4 ? 1 : 0;
     return (g9.nNt == 1 || (g9.nNt == 2 && Cin <= 192) || g9.ksplit > 1) ? 1 : 0;
 }
-extern "C" int diqt_conv3d_fwd_gn(const float* x, const float* packed, const float* bias, const float* residual, float* y, float* stats,
-                                  void* workspace, size_t workspace_bytes, const float* coef, int act, int B, int D, int H, int W, int Cin,
-                                  int Cout, int kd, int kh, int kw, int pd, int ph, int pw, int epd, int eph, int epw, void* stream) {
+extern "C" int diqt_conv3d_fwd_gn_supported(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw,
+                                            int epd, int eph, int epw, int act) {
+    return fwd_gn_supported(B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, act, false);
+}
+// ... for diqt_conv3d_fwd_gn_pk with a packed buffer of packed_elems floats (see diqt_conv3d_fwd_pk)
+extern "C" int diqt_conv3d_fwd_gn_supported_pk(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw,
+                                               int epd, int eph, int epw, int act, size_t packed_elems) {
+    return fwd_gn_supported(B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, act,
+                            wino_layout(Cout, Cin, kd, kh, kw, packed_elems) == 1);
+}
+static int fwd_gn(const float* x, const float* packed, const float* bias, const float* residual, float* y, float* stats, void* workspace,
+                  size_t workspace_bytes, const float* coef, int act, int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw,
+                  int pd, int ph, int pw, int epd, int eph, int epw, void* stream, bool wino) {
     DIQT_REQUIRE(x && packed && y && coef, DIQT_E_ALIGN, "conv3d_fwd_gn: null pointer");
     DIQT_REQUIRE(aligned16(x) && aligned16(packed) && aligned16(coef), DIQT_E_ALIGN, "conv3d_fwd_gn: x, packed weights and coef must be 16-byte aligned");
-    DIQT_REQUIRE(diqt_conv3d_fwd_gn_supported(B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, act), DIQT_E_UNSUPPORTED,
+    DIQT_REQUIRE(fwd_gn_supported(B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, act, wino), DIQT_E_UNSUPPORTED,
                  "conv3d_fwd_gn: shape / activation not taken (diqt_conv3d_fwd_gn_supported == 0)");
     F9Geom g9;
     size_t l9;
     unsigned gr9;
     const bool maySplit = workspace && aligned16(workspace);
     const bool ok = fwd9_plan(g9, l9, gr9, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw,
-                              diqt_conv_packed_elems(Cout, Cin, kd, kh, kw), maySplit);
+                              diqt_conv_packed_elems(Cout, Cin, kd, kh, kw), maySplit, wino);
     DIQT_REQUIRE(ok && fwd9_gna_available(g9.variant, act), DIQT_E_WORKSPACE,
                  "conv3d_fwd_gn: this launch needs the split-K workspace of diqt_conv3d_fwd_workspace_bytes");
     g9.gcoef = coef;
     g9.gnaAct = act;
     if (g9.ksplit == 1) {
-        DIQT_REQUIRE(!stats || diqt_conv3d_fwd_stats_blocks(B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw) > 0, DIQT_E_UNSUPPORTED,
-                     "conv3d_fwd_gn: this shape does not produce output statistics");
+        DIQT_REQUIRE(!stats || fwd_stats_blocks_impl(B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, false, wino) > 0,
+                     DIQT_E_UNSUPPORTED, "conv3d_fwd_gn: this shape does not produce output statistics");
         g9.stats = stats;
         return fwd9_launch(x, packed, bias, residual, y, g9, l9, gr9, stream);
     }
@@ -1929,6 +2041,23 @@ extern "C" int diqt_conv3d_fwd_gn(const float* x, const float* packed, const flo
     hipLaunchKernelGGL(conv_fwd_reduce_kernel, dim3(grid_for(n, 256, 2048)), dim3(256), 0, (hipStream_t)stream, slabs, bias, residual, y, n,
                        Cout, g9.ksplit);
     return check_launch("conv3d_fwd_gn(split-K reduce)");
+}
+extern "C" int diqt_conv3d_fwd_gn(const float* x, const float* packed, const float* bias, const float* residual, float* y, float* stats,
+                                  void* workspace, size_t workspace_bytes, const float* coef, int act, int B, int D, int H, int W, int Cin,
+                                  int Cout, int kd, int kh, int kw, int pd, int ph, int pw, int epd, int eph, int epw, void* stream) {
+    return fwd_gn(x, packed, bias, residual, y, stats, workspace, workspace_bytes, coef, act, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw,
+                  epd, eph, epw, stream, false);
+}
+// diqt_conv3d_fwd_gn with the length of the packed buffer (Winograd panels of pack mode 2: see diqt_conv3d_fwd_pk)
+extern "C" int diqt_conv3d_fwd_gn_pk(const float* x, const float* packed, size_t packed_elems, const float* bias, const float* residual,
+                                     float* y, float* stats, void* workspace, size_t workspace_bytes, const float* coef, int act, int B, int D,
+                                     int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw, int epd, int eph,
+                                     int epw, void* stream) {
+    const int lay = wino_layout(Cout, Cin, kd, kh, kw, packed_elems);
+    DIQT_REQUIRE(lay >= 0, DIQT_E_SHAPE, "conv3d_fwd_gn_pk: packed buffer of %zu floats, the direct pack alone needs %zu", packed_elems,
+                 diqt_conv_packed_elems(Cout, Cin, kd, kh, kw));
+    return fwd_gn(x, packed, bias, residual, y, stats, workspace, workspace_bytes, coef, act, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw,
+                  epd, eph, epw, stream, lay == 1);
 }
 
 // 'same' convolution (odd cubic filter k, padding k / 2) over the f^3 sub-volume batch x[f^3][A][A][A][Cin] of ONE merged volume, the
@@ -1962,7 +2091,8 @@ extern "C" int diqt_conv3d_fwd_ws(const float* x, const float* packed, const flo
 // Linear geometry, batch-entry ranges otherwise (a single batch entry >= 1 GiB still takes the pointer-arithmetic kernel).
 static int conv3d_fwd_impl(const float* x, const float* packed, const float* bias, const float* residual,
                            float* y, void* workspace, size_t workspace_bytes, int B, int D, int H, int W, int Cin, int Cout,
-                           int kd, int kh, int kw, int pd, int ph, int pw, int epd, int eph, int epw, void* stream, float* stats) {
+                           int kd, int kh, int kw, int pd, int ph, int pw, int epd, int eph, int epw, void* stream, float* stats,
+                           bool wino) {
     const long long Do = (long long)D + 2 * pd + epd - kd + 1, Ho = (long long)H + 2 * ph + eph - kh + 1, Wo = (long long)W + 2 * pw + epw - kw + 1;
     const unsigned long long lim = (1ull << 30) - 1;
     if (B > 0 && D > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && Do > 0 && Ho > 0 && Wo > 0) {
@@ -1988,7 +2118,7 @@ static int conv3d_fwd_impl(const float* x, const float* packed, const float* bia
                     const int nb = B - b0 < (int)per ? B - b0 : (int)per;
                     const int rc = conv3d_fwd_one(x + (size_t)b0 * (xin / 4), packed, bias, residual ? residual + (size_t)b0 * (yout / 4) : nullptr,
                                                   y + (size_t)b0 * (yout / 4), nullptr, 0, nb, D, H, W, Cin, Cout, kd, kh, kw, pd,
-                                                  ph, pw, epd, eph, epw, stream, nullptr);
+                                                  ph, pw, epd, eph, epw, stream, nullptr, 0, wino);
                     if (rc) return rc;
                 }
                 return DIQT_OK;
@@ -1996,13 +2126,13 @@ static int conv3d_fwd_impl(const float* x, const float* packed, const float* bia
         }
     }
     return conv3d_fwd_one(x, packed, bias, residual, y, workspace, workspace_bytes, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph,
-                          epw, stream, stats);
+                          epw, stream, stats, 0, wino);
 }
 
 static int conv3d_fwd_one(const float* x, const float* packed, const float* bias, const float* residual,
                           float* y, void* workspace, size_t workspace_bytes, int B, int D, int H, int W, int Cin, int Cout,
                           int kd, int kh, int kw, int pd, int ph, int pw, int epd, int eph, int epw, void* stream, float* stats,
-                          int subF) {
+                          int subF, bool wino) {
     DIQT_REQUIRE(x && packed && y, DIQT_E_ALIGN, "conv3d_fwd: null pointer");
     ConvGeom g;
     int rc = make_geom(g, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw);
@@ -2067,7 +2197,7 @@ static int conv3d_fwd_one(const float* x, const float* packed, const float* bias
         unsigned gr9;
         const bool maySplit = workspace && aligned16(workspace);
         if (fwd9_plan(g9, l9, gr9, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, diqt_conv_packed_elems(Cout, Cin, kd, kh, kw),
-                      maySplit)) {
+                      maySplit, wino)) {
             if (g9.ksplit == 1) {
                 g9.stats = stats;
                 return fwd9_launch(x, packed, bias, residual, y, g9, l9, gr9, stream);

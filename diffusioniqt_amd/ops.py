@@ -189,6 +189,15 @@ def _reduce_ws(B, C, device):
 # --------------------------------------------------------------------------------------------
 # convolution / linear
 # --------------------------------------------------------------------------------------------
+def _packed_len(shape, mode):
+    """(direct, Winograd) floats of ``_packed(weight, mode)``: forward packs of 3x3x3 filters carry the Winograd panels of
+    conv_fwd9_kernel's F(2,3) tile behind the direct ones (pack mode 2), which the ``*_pk`` entry points see from the length."""
+    Cout, Cin, kd, kh, kw = shape
+    eff = (Cout, Cin) if mode == 0 else (Cin, Cout)
+    n = _lib.query("diqt_conv_packed_elems", eff[0], eff[1], kd, kh, kw)
+    return n, (_lib.query("diqt_conv_packed_wino_elems", Cout, Cin, kd, kh, kw) if mode == 0 else 0)
+
+
 def _packed(weight5, mode):
     """Packed copy of an OIDHW weight for the MFMA kernel, cached on the tensor until it changes."""
     owner = weight5._base if weight5._base is not None else weight5   # views (nn.Linear) share the cache
@@ -204,10 +213,9 @@ def _packed(weight5, mode):
     if hit is not None and hit[0] == key:
         return hit[1]
     Cout, Cin, kd, kh, kw = weight5.shape
-    eff = (Cout, Cin) if mode == 0 else (Cin, Cout)
-    n = _lib.query("diqt_conv_packed_elems", eff[0], eff[1], kd, kh, kw)
-    packed = torch.empty(n, dtype=torch.float32, device=weight5.device)
-    _lib.call("diqt_conv_pack_weight", weight5.detach(), packed, Cout, Cin, kd, kh, kw, mode, _stream())
+    n, nw = _packed_len(weight5.shape, mode)
+    packed = torch.empty(n + nw, dtype=torch.float32, device=weight5.device)
+    _lib.call("diqt_conv_pack_weight", weight5.detach(), packed, Cout, Cin, kd, kh, kw, 2 if nw else mode, _stream())
     if hit is not None:
         retire(hit[1])
     cache[mode] = (key, born(packed))
@@ -465,15 +473,16 @@ def _conv_fwd_raw(x5, packed, bias, residual, Cout, k, pad, epad=(0, 0, 0), stat
     if TIMER.enabled:
         s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         s.record()
-    n = _lib.query("diqt_conv3d_fwd_workspace_bytes", B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw)
+    npk = packed.numel()
+    n = _lib.query("diqt_conv3d_fwd_workspace_bytes_pk", B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, npk)
     ws = _workspace(n, x5.device) if n else None
     stats = None
     if stats_out is not None:
-        nblk = _lib.query("diqt_conv3d_fwd_stats_blocks", B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw)
+        nblk = _lib.query("diqt_conv3d_fwd_stats_blocks_pk", B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, npk)
         if nblk > 0:
             stats = torch.empty((B, nblk, 2, Cout), dtype=torch.float32, device=x5.device)
             stats_out.append(ColStats(stats, nblk, Do * Ho * Wo))
-    _lib.call("diqt_conv3d_fwd_ex", x5, packed, bias, residual, y, stats, ws, n, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw,
+    _lib.call("diqt_conv3d_fwd_pk", x5, packed, npk, bias, residual, y, stats, ws, n, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw,
               epd, eph, epw, _stream())
     if TIMER.enabled:
         e.record()
@@ -1159,7 +1168,8 @@ def gn_conv3d(x, gamma, beta, scale_shift, groups, act, eps, weight, bias, paddi
     padding = tuple(int(p) for p in ((padding,) * 3 if isinstance(padding, int) else padding))
     extra_pad = tuple(int(p) for p in extra_pad)
     geo = (B, D, H, W, C, Cout, kd, kh, kw, *padding, *extra_pad)
-    if Cin != C or C % groups != 0 or not _lib.query("diqt_conv3d_fwd_gn_supported", *geo, act):
+    npk = sum(_packed_len(weight.shape, 0))
+    if Cin != C or C % groups != 0 or not _lib.query("diqt_conv3d_fwd_gn_supported_pk", *geo, act, npk):
         return None
     _chk(x, gamma, beta, weight, bias, residual, scale_shift.base if isinstance(scale_shift, SSView) else None)
     rows = D * H * W
@@ -1189,15 +1199,17 @@ def gn_conv3d(x, gamma, beta, scale_shift, groups, act, eps, weight, bias, paddi
     if TIMER.enabled:
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         ev0.record()
-    n = _lib.query("diqt_conv3d_fwd_workspace_bytes", *geo)
+    n = _lib.query("diqt_conv3d_fwd_workspace_bytes_pk", *geo, npk)
     ws = _workspace(n, dev) if n else None
     stats = None
     if want_stats:
-        nblk = _lib.query("diqt_conv3d_fwd_stats_blocks", *geo)
+        nblk = _lib.query("diqt_conv3d_fwd_stats_blocks_pk", *geo, npk)
         if nblk > 0:
             stats = torch.empty((B, nblk, 2, Cout), dtype=torch.float32, device=dev)
             y._diqt_stats = ColStats(stats, nblk, Do * Ho * Wo)
-    _lib.call("diqt_conv3d_fwd_gn", x, _packed(weight, 0), bias, residual, y, stats, ws, n, coef, act, *geo, s)
+    packed = _packed(weight, 0)
+    assert packed.numel() == npk
+    _lib.call("diqt_conv3d_fwd_gn_pk", x, packed, npk, bias, residual, y, stats, ws, n, coef, act, *geo, s)
     if TIMER.enabled:
         ev1.record()
         TIMER.records.append((ev0, ev1, 2.0 * B * Do * Ho * Wo * Cout * C * kd * kh * kw, "conv_fwd9_kernel", geo[:9]))

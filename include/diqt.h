@@ -69,9 +69,16 @@ const char* diqt_get_last_launch(void);
 /* number of floats in the packed-weight buffer for a (Cout,Cin,kd,kh,kw) filter */
 size_t diqt_conv_packed_elems(int Cout, int Cin, int kd, int kh, int kw);
 
+/* floats of the Winograd F(2,3) panels that pack modes 2 / 3 append behind the direct pack, for an effective
+ * (out, in) = (Cout, Cin) filter: nonzero for 3x3x3 filters with in % 16 == 0                        */
+size_t diqt_conv_packed_wino_elems(int Cout, int Cin, int kd, int kh, int kw);
+
 /* mode 0: forward packing of w[Cout][Cin][kd][kh][kw];
  * mode 1: backward-data packing (taps flipped, in/out swapped) — feed to diqt_conv3d_fwd with
- *         (Cin,Cout) swapped and pad' = k-1-pad to obtain dX from dY.                               */
+ *         (Cin,Cout) swapped and pad' = k-1-pad to obtain dX from dY.
+ * mode 2 / 3: the packing of mode 0 / 1 followed by the Winograd panels of the same effective filter
+ *         (diqt_conv_packed_elems + diqt_conv_packed_wino_elems floats).  Only the *_pk entry points,
+ *         told the buffer's length, read the panels; every other entry point reads the direct pack. */
 int diqt_conv_pack_weight(const float* w_oidhw, float* packed, int Cout, int Cin,
                           int kd, int kh, int kw, int mode, void* stream);
 
@@ -136,11 +143,29 @@ int diqt_conv3d_fwd_h(const float* x, const void* packed_h, const float* bias, c
  * rocprofv3 reports.                                                                                                               */
 int diqt_conv3d_fwd_kernel_id(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw,
                               int epd, int eph, int epw);
+/* conv_fwd9_kernel's variant for a launch that diqt_conv3d_fwd_kernel_id routes to it, given a packed buffer of
+ * packed_elems floats (7: the Winograd F(2,3) 3x3x3 tile of diqt_conv3d_fwd_pk), else -1 */
+int diqt_conv3d_fwd9_variant(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw,
+                             int epd, int eph, int epw, size_t packed_elems);
+/* the conv_fwd9_kernel variant the process's last launch of it ran, -1 if none since the previous call (read and clear) */
+int diqt_get_last_conv_fwd9_variant(void);
 int diqt_conv3d_fwd_stats_blocks(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw,
                                  int epd, int eph, int epw);
 int diqt_conv3d_fwd_ex(const float* x, const float* packed, const float* bias, const float* residual, float* y, float* stats,
                        void* workspace, size_t workspace_bytes, int B, int D, int H, int W, int Cin, int Cout,
                        int kd, int kh, int kw, int pd, int ph, int pw, int epd, int eph, int epw, void* stream);
+/* diqt_conv3d_fwd_ex told the length of the packed buffer (floats).  A buffer from pack mode 2 (direct pack + Winograd panels)
+ * lets 3x3x3 launches with an even output width run conv_fwd9_kernel's Winograd F(2,3) tile (4 MFMA products per output pair
+ * instead of 6; DIQT_CONV_F9W=0 in the environment keeps the direct tiles); a buffer of diqt_conv_packed_elems floats gives the
+ * direct tiles exactly as diqt_conv3d_fwd_ex; a shorter one is refused (DIQT_E_SHAPE).  The Winograd tile has its own tile count,
+ * so statistics rows and split-K workspace come from the _pk queries with the same length.                                     */
+int diqt_conv3d_fwd_pk(const float* x, const float* packed, size_t packed_elems, const float* bias, const float* residual, float* y,
+                       float* stats, void* workspace, size_t workspace_bytes, int B, int D, int H, int W, int Cin, int Cout,
+                       int kd, int kh, int kw, int pd, int ph, int pw, int epd, int eph, int epw, void* stream);
+int diqt_conv3d_fwd_stats_blocks_pk(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw,
+                                    int epd, int eph, int epw, size_t packed_elems);
+size_t diqt_conv3d_fwd_workspace_bytes_pk(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw,
+                                          int pd, int ph, int pw, int epd, int eph, int epw, size_t packed_elems);
 /* consumers of such partials */
 int diqt_groupnorm_stats_from_partials(const float* partials, float* mean, float* rstd, int B, int nblk, int rows_per_batch,
                                        int C, int G, float eps, void* stream);
@@ -288,6 +313,13 @@ int diqt_conv3d_fwd_gn_supported(int B, int D, int H, int W, int Cin, int Cout, 
 int diqt_conv3d_fwd_gn(const float* x, const float* packed, const float* bias, const float* residual, float* y, float* stats,
                        void* workspace, size_t workspace_bytes, const float* coef, int act, int B, int D, int H, int W, int Cin, int Cout,
                        int kd, int kh, int kw, int pd, int ph, int pw, int epd, int eph, int epw, void* stream);
+/* the same told the length of the packed buffer, as diqt_conv3d_fwd_pk (Winograd tile with Mish on the 3x3x3 launches) */
+int diqt_conv3d_fwd_gn_supported_pk(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw,
+                                    int epd, int eph, int epw, int act, size_t packed_elems);
+int diqt_conv3d_fwd_gn_pk(const float* x, const float* packed, size_t packed_elems, const float* bias, const float* residual, float* y,
+                          float* stats, void* workspace, size_t workspace_bytes, const float* coef, int act, int B, int D, int H,
+                          int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw, int epd, int eph, int epw,
+                          void* stream);
 
 /* Process-wide switch of that fusion (default: off unless DIQT_GNBWD_FUSE=1 in the environment at the first query).  The setter
  * returns the previous value; with the switch off diqt_conv3d_fwd_gnbwd_blocks answers 0 for every shape.  Host-side state only
