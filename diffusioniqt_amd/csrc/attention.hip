@@ -581,9 +581,8 @@ extern "C" int diqt_mqa_attention_fwd_h(const float* q, const void* kv, const fl
     DIQT_REQUIRE(!null_bias || n_extra >= 1, DIQT_E_SHAPE, "mqa_attention_fwd_h: null bias without a null key");
     DIQT_REQUIRE(aligned16(q) && aligned16(kv) && aligned16(out), DIQT_E_ALIGN, "mqa_attention_fwd_h: pointers must be 16-byte aligned");
     DIQT_REQUIRE(G <= 65535, DIQT_E_SHAPE, "mqa_attention_fwd_h: G > 65535");
-    // long un-biased sequences (the joint space-time attention): 4-wave workgroups, two per CU (see the kernel); DIQT_ATTN_H_W8=1: always 8 waves
-    static const bool w8 = [] { const char* e = getenv("DIQT_ATTN_H_W8"); return e && e[0] == '1'; }();
-    const bool four = !w8 && !rel && d == 64 && (long long)n * h >= 4096;
+    // long un-biased sequences (the joint space-time attention): 4-wave workgroups, two per CU (see the kernel)
+    const bool four = !rel && d == 64 && (long long)n * h >= 4096;
     const int rowsPerWg = four ? 128 : AQH;
     const dim3 grid((unsigned)(((long long)n * h + rowsPerWg - 1) / rowsPerWg), G);
     void (*k)(const float*, const unsigned short*, const float*, const float*, float*, int, int, int, int, int, float, int) =
@@ -1547,12 +1546,11 @@ extern "C" int diqt_mqa_attention_bwd(const float* q, const float* kv, const flo
     float* dnull_part = tbl_part + (size_t)rows * TBL;
     {
         // thousands of short sequences with the lone null key (the temporal attentions): everything in one pass, a sequence per wave
-        static const bool noSeq = [] { const char* e = getenv("DIQT_ATTN_NO_SEQ"); return e && e[0] == '1'; }();
         const unsigned long long ob = (unsigned long long)G * R * d * 4ull;
         const int relLds = rel ? TBL : 0;
         const int perw = (32 * d + 3 * 32 * (d + 4) + 64 + 2 * d + TBL + 255) / 256 * 256;
         const size_t lds = ((size_t)4 * perw + relLds + 64) * sizeof(float);
-        if (!noSeq && n_extra == 1 && n_self == n && n <= 32 && 32 % h == 0 && G >= 512 && ob < (1ull << 31) && lds <= 160 * 1024) {
+        if (n_extra == 1 && n_self == n && n <= 32 && 32 % h == 0 && G >= 512 && ob < (1ull << 31) && lds <= 160 * 1024) {
             const int nwg = (G + 3) / 4 < 256 ? (G + 3) / 4 : 256;
             auto kern = d == 64 ? mqa_seq_bwd_kernel<2> : mqa_seq_bwd_kernel<1>;
             hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -1602,8 +1600,7 @@ extern "C" int diqt_mqa_attention_bwd(const float* q, const float* kv, const flo
         // G = 8) need the finer split to fill 256 CUs: every workgroup walks ALL query rows of its batch entry.
         int KW = Mt <= 32 ? 1 : (Mt <= 64 ? 2 : 4);
         while (KW > 1 && (long long)((Mt + 32 * KW - 1) / (32 * KW)) * G < 512) KW >>= 1;
-        static const bool noPerWave = [] { const char* e = getenv("DIQT_ATTN_NO_PERWAVE"); return e && e[0] == '1'; }();
-        const bool perWave = !noPerWave && Mt <= 32 && G >= 2048;      // one sequence per wave (see the kernel)
+        const bool perWave = Mt <= 32 && G >= 2048;      // one sequence per wave (see the kernel)
         if (perWave) KW = 0;
         const int nkt = perWave ? 1 : (Mt > 0 ? (Mt + 32 * KW - 1) / (32 * KW) : 1);
         const dim3 grid((unsigned)nkt, perWave ? (unsigned)((G + 3) / 4) : (unsigned)G);

@@ -20,7 +20,6 @@
 // partial y^T go through LDS and are summed in a fixed order (deterministic), then LayerNorm + residual + store.
 // The null key / value (imagen_video.py:471-481) is one extra score per query, handled on the VALU.
 #include "common.h"
-#include <stdlib.h>
 
 namespace diqt {
 namespace {
@@ -530,10 +529,8 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void temporal_attn_h_kernel(const 
 template <int C, int N>
 int ta_launch(const float* x, const float* g1, const void* wq, const void* wkv, const void* wo, const float* g2, const float* nullkv,
               const float* rel, const float* null_bias, float* y, const TAGeom& g, int bf16, hipStream_t s) {
-    // 8 heads: one head per wave, 8 waves (two per SIMD); DIQT_TATTN_W4=1: the first build, 4 waves x 2 heads.  4 heads: 4 waves x 1 head.
-    static const bool w4 = [] { const char* e = getenv("DIQT_TATTN_W4"); return e && e[0] == '1'; }();
-    static const int wgs = [] { const char* e = getenv("DIQT_TATTN_WGS"); return e ? atoi(e) : 256; }();
-    const int grid = g.nseq < wgs ? g.nseq : wgs;
+    // 8 heads: one head per wave, 8 waves (two per SIMD), or (C = 128) 4 waves x 2 heads.  4 heads: 4 waves x 1 head.
+    const int grid = g.nseq < 256 ? g.nseq : 256;
     auto go = [&](auto kern, int threads, int lds) -> int {
         if (lds > 64 * 1024) {
             hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
@@ -545,7 +542,7 @@ int ta_launch(const float* x, const float* g1, const void* wq, const void* wkv, 
     };
     static_assert(TACfg<C, N, 4>::LDS <= 160 * 1024 && TACfg<C, N, 8>::LDS <= 160 * 1024, "LDS");
     // (C = 128, weights re-read from L2: the 4-wave build measures faster, 604 vs 641 us on 8192 sequences of 64 frames)
-    if (g.h == 8 && !w4 && C != 128)
+    if (g.h == 8 && C != 128)
         return bf16 ? go(temporal_attn_h_kernel<C, N, true, 1, 8>, 512, TACfg<C, N, 8>::LDS) : go(temporal_attn_h_kernel<C, N, false, 1, 8>, 512, TACfg<C, N, 8>::LDS);
     if (g.h == 8)
         return bf16 ? go(temporal_attn_h_kernel<C, N, true, 2, 4>, 256, TACfg<C, N, 4>::LDS) : go(temporal_attn_h_kernel<C, N, false, 2, 4>, 256, TACfg<C, N, 4>::LDS);
@@ -559,8 +556,7 @@ int ta_launch(const float* x, const float* g1, const void* wq, const void* wkv, 
 using namespace diqt;
 
 extern "C" int diqt_temporal_attention_h_supported(int B, int F, int P, int C, int h, int d) {
-    static const bool off = [] { const char* e = getenv("DIQT_NO_TATTN"); return e && e[0] == '1'; }();
-    if (off || d != TD || (h != 4 && h != 8) || (F != 32 && F != 64) || (C != 64 && C != 128 && C != 256)) return 0;
+    if (d != TD || (h != 4 && h != 8) || (F != 32 && F != 64) || (C != 64 && C != 128 && C != 256)) return 0;
     if (B < 1 || P < 1 || (long long)B * P >= (1ll << 30)) return 0;
     return 1;
 }

@@ -1,32 +1,12 @@
 // Planner and launcher of conv_f9h_kernel (conv_f9h_kernel.h has the description) + its 3x3x3 instantiations.
 #include "conv_f9h_kernel.h"
-#include <stdlib.h>
 #include <atomic>
 
-// 0: conv_f9h_kernel never takes a launch, 1 (default; env DIQT_CONV_F9H): launches that fill the chip, 2: any tile count (tests run the
-// kernel on small shapes this way).  mode >= 0 sets it, mode < 0 only queries; returns the previous value.
-static std::atomic<int> g_f9h_mode{-1};
+// 0: conv_f9h_kernel never takes a launch, 1 (default): launches that fill the chip, 2: any tile count (tests run the kernel on small
+// shapes this way).  mode >= 0 sets it, mode < 0 only queries; returns the previous value.
+static std::atomic<int> g_f9h_mode{1};
 extern "C" int diqt_set_conv_f9h_mode(int mode) {
-    int cur = g_f9h_mode.load();
-    if (cur < 0) {
-        const char* e = getenv("DIQT_CONV_F9H");
-        const int v = e ? atoi(e) : 1;
-        g_f9h_mode.compare_exchange_strong(cur, v < 0 ? 1 : v);
-        cur = g_f9h_mode.load();
-    }
-    if (mode >= 0) g_f9h_mode.store(mode);
-    return cur;
-}
-
-static unsigned long long* g_f9dbg = nullptr;   // diagnostic only (DIQT_F9H_DBG=1)
-static unsigned g_f9dbg_n = 0;
-// diagnostic only (not part of include/diqt.h): the cycle stamps of the last DIQT_F9H_DBG=1 launch, 32 per wave, 4 waves per workgroup
-extern "C" int diqt_debug_f9h_stamps(unsigned long long* host_out, unsigned max_waves) {
-    if (!g_f9dbg || !g_f9dbg_n) return 0;
-    const unsigned n = g_f9dbg_n < max_waves ? g_f9dbg_n : max_waves;
-    if (hipDeviceSynchronize() != hipSuccess) return 0;
-    if (hipMemcpy(host_out, g_f9dbg, (size_t)n * 32 * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) return 0;
-    return (int)n;
+    return mode >= 0 ? g_f9h_mode.exchange(mode) : g_f9h_mode.load();
 }
 
 namespace diqt {
@@ -67,14 +47,13 @@ bool f9h_plan(H9Geom& g, size_t& lds, unsigned& grid, int B, int D, int H, int W
     const unsigned long long yb = vox * Cout * (yHalf ? 2ull : 4ull), rb = vox * Cout * 4ull;
     const unsigned long long wb = (unsigned long long)g.nChunks * kd * kh * kw * g.CoutPad * h9::CK * 2ull;
     if (xb >= (1ull << 30) || rb >= (1ull << 31) || wb >= (1ull << 30)) return false;
-    g.xBytes = (unsigned)xb; g.yBytes = (unsigned)yb; g.rBytes = (unsigned)rb; g.wBytes = (unsigned)wb; g.stats = nullptr; g.dbg = nullptr; g.dbgSkip = 0;
+    g.xBytes = (unsigned)xb; g.yBytes = (unsigned)yb; g.rBytes = (unsigned)rb; g.wBytes = (unsigned)wb; g.stats = nullptr;
     // the candidate with the shortest estimate wins; ties go to the earlier one = the measured preference (MI355X, round 4): the 256-voxel
     // tiles at two workgroups per CU are 0-8 % faster than the 512-voxel ones on the 3x3x3 shapes of C2 (58.7 vs 63.4 us on 64 -> 64 @
     // 8 x 32^3 with an fp32 y) and on the 64-channel per-frame convs (208 vs 219 us @ 8 x 64^3), 4 % slower at 128 channels.  Small
     // grids are taken too: 128 -> 128 @ 8 x 8^3 (32 workgroups) 21.7 us against 47.6 us on conv_fwd_h_kernel.
-    static const int force = [] { const char* e = getenv("DIQT_F9H_VARIANT"); return e ? atoi(e) : -1; }();      // experiments: this variant only
     H9Geom best = g; size_t bl = 0; unsigned bg = 0; double be = 1e300; int bv = -1;
-#define F9H_TRY(CFG, V) if (force < 0 || force == V) { H9Geom t = g; size_t l_; unsigned g_; double e_; \
+#define F9H_TRY(CFG, V) { H9Geom t = g; size_t l_; unsigned g_; double e_; \
         if (f9h_try<h9::CFG>(t, l_, g_, e_) && e_ < be) { best = t; bl = l_; bg = g_; be = e_; bv = V; } }
     if (k333) {
         F9H_TRY(H9_333_256, 1)
@@ -97,17 +76,8 @@ bool f9h_plan(H9Geom& g, size_t& lds, unsigned& grid, int B, int D, int H, int W
 
 int f9h_stats_blocks(const H9Geom& g) { return g.tilesD * g.tilesH * g.tilesW * 2; }
 
-int f9h_launch(const void* x, const unsigned short* packed_h, const float* bias, const float* residual, void* y, const H9Geom& g0, size_t lds,
+int f9h_launch(const void* x, const unsigned short* packed_h, const float* bias, const float* residual, void* y, const H9Geom& g, size_t lds,
                unsigned grid, int bf16, bool yHalf, void* stream) {
-    H9Geom g = g0;
-    static const int dbg_mode = [] { const char* e = getenv("DIQT_F9H_DBG"); return e ? atoi(e) : 0; }();
-    const bool dbg_on = dbg_mode > 0;
-    g.dbgSkip = dbg_mode == 2 ? 80 : 0;
-    if (dbg_on) {
-        if (!g_f9dbg) DIQT_REQUIRE(hipMalloc(&g_f9dbg, (size_t)1024 * 32 * sizeof(unsigned long long)) == hipSuccess, DIQT_E_LAUNCH, "conv3d_fwd_h(v9h): debug buffer");
-        DIQT_REQUIRE(hipMemsetAsync(g_f9dbg, 0, (size_t)1024 * 32 * sizeof(unsigned long long), (hipStream_t)stream) == hipSuccess, DIQT_E_LAUNCH, "conv3d_fwd_h(v9h): debug buffer");
-        g.dbg = g_f9dbg; g_f9dbg_n = grid * 4;
-    }
     switch (g.variant) {
         case 0: return h9::launch_cfg<h9::H9_333_512>(x, packed_h, bias, residual, y, g, lds, grid, bf16, yHalf, stream);
         case 1: return h9::launch_b(x, packed_h, bias, residual, y, g, lds, grid, bf16, yHalf, stream);

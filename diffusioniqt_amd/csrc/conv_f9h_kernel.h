@@ -123,23 +123,6 @@ __global__ __launch_bounds__(256, C::OCC) void conv_f9h_kernel(const void* __res
     const auto rs_y = __builtin_amdgcn_make_buffer_rsrc(yv, 0, (int)g.yBytes, 0x00020000);
     const auto rs_r = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(residual), 0, residual ? (int)g.rBytes : 0, 0x00020000);
     const unsigned ldsBase = (unsigned)(size_t)(lds_void*)smem;
-    // diagnostic stamps (g.dbg set by DIQT_F9H_DBG=1 only): 32 slots per wave -- 0 start, 1 prologue done, then per unit (chunk start, before
-    // the barrier, after it), per tile (epilogue done)
-    int dslot = 0;
-    auto stamp = [&]() __attribute__((always_inline)) {
-        if (g.dbg) {
-            const unsigned long long tnow = __builtin_readcyclecounter();
-            // (DIQT_F9H_DBG=2: the stamps from slot 80 on instead of the first 32 -- steady state of a long tile walk)
-            const int ds_ = dslot - g.dbgSkip;
-            if (lane == 0 && dslot == 0) g.dbg[((size_t)blockIdx.x * 4 + wave) * 32 + 28] = __builtin_amdgcn_s_memrealtime();   // 100 MHz
-            if (lane == 0) g.dbg[((size_t)blockIdx.x * 4 + wave) * 32 + 29] = __builtin_amdgcn_s_memrealtime();
-            if (lane == 0 && ds_ >= 0 && ds_ < 28) g.dbg[((size_t)blockIdx.x * 4 + wave) * 32 + ds_] = tnow;
-            if (lane == 0 && dslot == 0) g.dbg[((size_t)blockIdx.x * 4 + wave) * 32 + 30] = tnow;      // slot 30: the wave's start, 31: its latest stamp
-            if (lane == 0) g.dbg[((size_t)blockIdx.x * 4 + wave) * 32 + 31] = tnow;
-            ++dslot;
-        }
-    };
-    stamp();
 
     // ---- tile-independent description of this lane's halo DMA pieces ----
     unsigned posH[NPH];              // hz | hy << 10 | hx << 20 | source octet << 30 (its slot ^ swizzle); rows past the image: hx = 1023 (never inside)
@@ -234,7 +217,6 @@ __global__ __launch_bounds__(256, C::OCC) void conv_f9h_kernel(const void* __res
     for (int s = 0; s < PD - 1; ++s) w_load(s);
     __builtin_amdgcn_s_waitcnt(0x0f70);                    // vmcnt(0)
     __syncthreads();
-    stamp();
 
     int img = 0, fimg = NIMG - 1;
     tile_of(L, tb, d0, h0, w0);
@@ -253,7 +235,6 @@ __global__ __launch_bounds__(256, C::OCC) void conv_f9h_kernel(const void* __res
 #pragma unroll
                 for (int vb = 0; vb < NVB; ++vb) acc[vb] = mfma16<BF>(Wr[t % PD][q], X[vb], acc[vb]);
             };
-            stamp();
             rd(X0, 0, 0);                                  // cold read of the chunk's first half-tap (the image was published by the barrier)
 #pragma unroll
             for (int t = 0; t < T; ++t) {
@@ -283,9 +264,7 @@ __global__ __launch_bounds__(256, C::OCC) void conv_f9h_kernel(const void* __res
             (void)nh_in_tap;
             // End of the unit.  The image of the next unit is complete: its pieces were issued before the weight load whose fragment the
             // last tap has just consumed (loads retire in order).  This wave's reads of image `img` have been consumed by issued MFMAs.
-            stamp();
             asm volatile("s_barrier" ::: "memory");
-            stamp();
             advance_fetch();
             {
                 const int nimg = img + 1 == NIMG ? 0 : img + 1;
@@ -410,7 +389,6 @@ __global__ __launch_bounds__(256, C::OCC) void conv_f9h_kernel(const void* __res
             }
         }
         asm volatile("s_barrier" ::: "memory");              // every wave's scratch reads are done (their stores have been issued)
-        stamp();
         L += Gn;
         if (it + 1 < nMine) tile_of(L, tb, d0, h0, w0);
     }

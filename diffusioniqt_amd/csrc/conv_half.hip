@@ -16,7 +16,6 @@
 // Packed weights: half/bf16 [chunk = ci/32][tap][co padded to 64][32 ci]  (conv_pack_weight_h_kernel).
 #include "common.h"
 #include "conv_f9h.h"
-#include <stdlib.h>
 #include <atomic>
 #include <type_traits>
 
@@ -50,7 +49,6 @@ struct HalfGeom {
     int NS, realChunks;          // persistent kernel, pointwise filters: NS > 1 consecutive 32-channel chunks are staged per step and walked
                                  // like taps (nChunks then counts steps of NS chunks, realChunks the 32-channel chunks)
     unsigned xBytes, yBytes;
-    unsigned long long* dbg;     // diagnostic cycle stamps per workgroup (DIQT_CONVH_DBG=1), NULL in production
 };
 
 __host__ __device__ inline int hcdiv(int a, int b) { return (a + b - 1) / b; }
@@ -239,14 +237,11 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_h_kernel(const float* __restr
         }
     };
 
-    const long long ts0 = g.dbg ? (long long)__builtin_readcyclecounter() : 0;
-    long long tTap = 0, tSync = 0, tq = 0;
     stage_halo_sync(0);
     load_wgroup(0, 0, min(g.TG, T));
     store_wgroup(0, min(g.TG, T));
     __syncthreads();
 
-    const long long ts1 = g.dbg ? (long long)__builtin_readcyclecounter() : 0;
     u32x4 hr[PREF ? HHREG : 1];
     int step = 0;
     for (int chunk = 0; chunk < g.nChunks; ++chunk) {
@@ -266,7 +261,6 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_h_kernel(const float* __restr
                     hr[u] = __builtin_amdgcn_raw_buffer_load_b128(rs_x, idx < nHalo ? t : HBUF_OOB, 0, 0);
                 }
             }
-            if (g.dbg) tq = (long long)__builtin_readcyclecounter();
             // ---- taps of this group: fragments of tap t+1 are read while the MFMAs of tap t issue ----
             const unsigned char* wcur = wbuf + (step & 1) * wbufBytes + b_base;
             const unsigned char* ap = halo + a_base;
@@ -304,7 +298,6 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_h_kernel(const float* __restr
                 acc1 = mfma16<BF>(a1, b11, acc1);
                 if (t + 1 < nTap) { a0 = na0; a1 = na1; b00 = nb00; b01 = nb01; b10 = nb10; b11 = nb11; }
             }
-            if (g.dbg) { const long long tn = (long long)__builtin_readcyclecounter(); tTap += tn - tq; tq = tn; }
             if (more) store_wgroup((step + 1) & 1, nn);      // that buffer was last read in step-1, retired by its barrier
             if (lastGrp && more) {
                 __syncthreads();                             // every wave is done with this chunk's halo image
@@ -325,10 +318,8 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_h_kernel(const float* __restr
                 if (!done) stage_halo_sync((chunk + 1) * HCK);
             }
             __syncthreads();
-            if (g.dbg) tSync += (long long)__builtin_readcyclecounter() - tq;
         }
     }
-    const long long ts2 = g.dbg ? (long long)__builtin_readcyclecounter() : 0;
 
     // ---- epilogue: D[row = voxel][col = co]; row = (r&3) + 8*(r>>2) + 4*h ----
     const int co0 = n0 + l31, co1 = n0 + 32 + l31;
@@ -356,12 +347,6 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_h_kernel(const float* __restr
         if (residual) { v0 += rr0[r]; v1 += rr1[r]; }
         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v0), rs_y, off + c0, 0, 0);
         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v1), rs_y, off + c1, 0, 0);
-    }
-    if (g.dbg && tid == 0) {
-        unsigned long long* d = g.dbg + (size_t)blockIdx.x * 8;
-        d[0] = (unsigned long long)(ts1 - ts0); d[1] = (unsigned long long)tTap; d[2] = (unsigned long long)tSync;
-        d[3] = (unsigned long long)((long long)__builtin_readcyclecounter() - ts2); d[4] = (unsigned long long)((long long)__builtin_readcyclecounter() - ts0);
-        d[5] = (unsigned long long)step;
     }
 }
 
@@ -737,7 +722,6 @@ static bool half_geom(HalfGeom& g, int B, int D, int H, int W, int Cin, int Cout
     g.nGroups = hcdiv(T, g.TG);
     g.nNt = hcdiv(Cout, HNT); g.CoutPad = g.nNt * HNT; g.nChunks = hcdiv(Cin, HCK);
     g.roundOut = 1;
-    g.dbg = nullptr;
     g.NS = 1; g.realChunks = g.nChunks;
     static const int cand[][3] = {{4, 8, 8}, {8, 8, 4}, {8, 4, 8}, {2, 8, 16}, {2, 16, 8}, {1, 16, 16}, {16, 4, 4}, {4, 4, 16}, {4, 16, 4},
                                   {16, 16, 1}, {16, 1, 16}, {32, 4, 2}, {64, 2, 2}, {256, 1, 1}, {1, 1, 256}, {1, 256, 1}, {1, 8, 32},
@@ -929,18 +913,6 @@ __global__ __launch_bounds__(256, 2) void conv_pw_h_kernel(const float* __restri
 
 using namespace diqt;
 
-static unsigned long long* g_hdbg = nullptr;    // diagnostic only (DIQT_CONVH_DBG=1)
-static unsigned g_hdbg_n = 0;
-// diagnostic only (not part of include/diqt.h): per-workgroup cycle stamps of the last DIQT_CONVH_DBG=1 launch:
-// [prologue, tap loops, store + barrier waits, epilogue, lifetime, steps, -, -]
-extern "C" int diqt_debug_convh_stamps(unsigned long long* host_out, unsigned max_wg) {
-    if (!g_hdbg || !g_hdbg_n) return 0;
-    const unsigned n = g_hdbg_n < max_wg ? g_hdbg_n : max_wg;
-    if (hipDeviceSynchronize() != hipSuccess) return 0;
-    if (hipMemcpy(host_out, g_hdbg, (size_t)n * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) return 0;
-    return (int)n;
-}
-
 // number of 16-bit elements of the packed low-precision weight (same [chunk][tap][co pad 64][32] order as the fp32 packing)
 extern "C" size_t diqt_conv_packed_h_elems(int Cout, int Cin, int kd, int kh, int kw) {
     if (Cout <= 0 || Cin <= 0 || kd <= 0 || kh <= 0 || kw <= 0) return 0;
@@ -996,39 +968,27 @@ extern "C" int diqt_conv3d_fwd_h_supported(int B, int D, int H, int W, int Cin, 
     return half_geom(g, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw) ? 1 : 0;
 }
 
-// workgroups of the persistent low-precision kernel (default 256 = one per CU; DIQT_CONVH_WGS): a launch of fewer than twice as many
+// workgroups of the persistent low-precision kernel (default 256 = one per CU): a launch of fewer than twice as many
 // (tile, channel-block) units stays on the one-unit kernel.  n > 0 sets it (tests force the persistent walk on small shapes), n <= 0
 // only queries; returns the previous value.
-static std::atomic<int> g_convh_wgs{0};
+static std::atomic<int> g_convh_wgs{256};
 extern "C" int diqt_set_convh_workgroups(int n) {
-    int cur = g_convh_wgs.load();
-    if (cur == 0) {
-        const char* e = getenv("DIQT_CONVH_WGS");
-        const int v = e && atoi(e) > 0 ? atoi(e) : 256;
-        g_convh_wgs.compare_exchange_strong(cur, v);
-        cur = g_convh_wgs.load();
-    }
-    if (n > 0) g_convh_wgs.store(n);
-    return cur;
+    return n > 0 ? g_convh_wgs.exchange(n) : g_convh_wgs.load();
 }
 
 static bool convh_persistent_takes(const HalfGeom& g, unsigned nwg) {
-    static const bool persist = [] { const char* e = getenv("DIQT_CONVH_PERSIST"); return !(e && e[0] == '0'); }();
-    static const bool nopref = [] { const char* e = getenv("DIQT_CONVH_NOPREF"); return e && e[0] == '1'; }();
     const int HV = g.HD * g.HH * g.HWd;
     // (filters of more than one tap group -- 3x3x3 -- stay on the one-unit kernel: 93.9 vs 102.3 us on 64 -> 64 @ 8 x 32^3, the walk's prefetch
     // registers spill there and 4 units per workgroup amortise little)
-    return persist && !nopref && g.nGroups == 1 && HV * 8 <= 512 * HHREG && nwg >= 2u * (unsigned)diqt_set_convh_workgroups(0);
+    return g.nGroups == 1 && HV * 8 <= 512 * HHREG && nwg >= 2u * (unsigned)diqt_set_convh_workgroups(0);
 }
 
 // 16-bit input on the persistent kernel: 4-wave workgroups (64 voxels x 64 channels per wave, one weight buffer), two per CU, when both fit
 static bool convh_four_waves(const HalfGeom& g, bool xh) {
-    static const bool off = [] { const char* e = getenv("DIQT_CONVH_W8"); return e && e[0] == '1'; }();
-    static const bool pw4 = [] { const char* e = getenv("DIQT_CONVH_PW4"); return !(e && e[0] == '0'); }();
     const int HV = g.HD * g.HH * g.HWd;
-    if (off || half_lds_bytes(g, 1) > 80 * 1024 - 1024) return false;
+    if (half_lds_bytes(g, 1) > 80 * 1024 - 1024) return false;
     if (g.kd * g.kh * g.kw > 1) return xh && HV * 4 <= 256 * 6;
-    return pw4 && !xh && g.NS == 1 && HV * 8 <= 256 * 8;     // pointwise, fp32 rows, one chunk per step: 8 pieces per thread
+    return !xh && g.NS == 1 && HV * 8 <= 256 * 8;     // pointwise, fp32 rows, one chunk per step: 8 pieces per thread
 }
 
 // 1 when diqt_conv3d_fwd_h_io takes 16-bit x and / or y for this shape: the persistent kernel's conditions and Cin, Cout % 8 == 0
@@ -1063,15 +1023,13 @@ extern "C" int diqt_conv3d_fwd_h_stats_blocks(int B, int D, int H, int W, int Ci
 
 // pointwise convs with fp32 rows at both ends and temporal convs with 16-bit input rows: the K-blocked GEMM (conv_pw_h_kernel)
 static bool pwh_takes(const HalfGeom& g, bool xh, bool yh, const float* stats) {
-    static const bool off = [] { const char* e = getenv("DIQT_NO_PWH"); return e && e[0] == '1'; }();
-    static const bool notemporal = [] { const char* e = getenv("DIQT_NO_PWH_T"); return e && e[0] == '1'; }();
-    if (off || yh || stats) return false;
+    if (yh || stats) return false;
     if (g.kh != 1 || g.kw != 1 || g.ph || g.pw || g.Do != g.D || g.Ho != g.H || g.Wo != g.W) return false;
     if (g.Cin % HCK != 0 || g.Cin < 64) return false;
     const long long rows = (long long)g.B * g.D * g.H * g.W;
     if (rows < 2048 || rows * g.Cin * (xh ? 2 : 4) >= (1ll << 31) || rows * g.Cout * 4 >= (1ll << 31)) return false;
     if (g.kd == 1) return !xh && g.pd == 0 && g.Cout >= 32;          // pointwise, fp32 rows (<= 64 channels: the 64-channel build, 5-20 % faster than the tap-oriented kernel)
-    return !notemporal && xh && g.kd <= 4 && g.pd < g.kd && g.Cout >= 32;      // temporal: the 16-bit output of the per-frame conv
+    return xh && g.kd <= 4 && g.pd < g.kd && g.Cout >= 32;      // temporal: the 16-bit output of the per-frame conv
 }
 static int pwh_launch(const void* x, const unsigned short* wp, const float* bias, const float* residual, float* y, const HalfGeom& g, int bf16,
                       bool xh, hipStream_t s) {
@@ -1119,17 +1077,11 @@ static int convh_launch(const void* x, const void* packed_h, const float* bias, 
     if (pwh_takes(g, xh, yh, stats))
         return pwh_launch(x, static_cast<const unsigned short*>(packed_h), bias, residual, static_cast<float*>(y), g, bf16, xh, (hipStream_t)stream);
     const unsigned nwg = (unsigned)((long long)g.B * g.tilesD * g.tilesH * g.tilesW * g.nNt);
-    static const bool dbg_on = [] { const char* e = getenv("DIQT_CONVH_DBG"); return e && e[0] == '1'; }();
-    if (dbg_on && nwg <= 65536 && !xh && !yh) {
-        if (!g_hdbg) DIQT_REQUIRE(hipMalloc(&g_hdbg, (size_t)65536 * 8 * sizeof(unsigned long long)) == hipSuccess, DIQT_E_LAUNCH, "conv3d_fwd_h: debug buffer");
-        g.dbg = g_hdbg; g_hdbg_n = nwg;
-    }
     size_t lds = half_lds_bytes(g);
     const int HV = g.HD * g.HH * g.HWd;
-    static const bool nopref = [] { const char* e = getenv("DIQT_CONVH_NOPREF"); return e && e[0] == '1'; }();
-    const bool pref = !nopref && HV * 8 <= 512 * HHREG;
+    const bool pref = HV * 8 <= 512 * HHREG;
     hipStream_t s = (hipStream_t)stream;
-    if (!g.dbg && convh_persistent_takes(g, nwg)) {
+    if (convh_persistent_takes(g, nwg)) {
         // (two workgroups per CU -- 6 halo pieces per thread, weight groups of <= 5 taps, 128 registers per wave -- measured 1.4x SLOWER
         // on the 64^3 level-0 shapes: the kernel moves 3.5 TB/s of fp32 activations, 0.75 of what a plain copy reaches)
         if (xh || yh) {
@@ -1137,10 +1089,8 @@ static int convh_launch(const void* x, const void* packed_h, const float* bias, 
                          "conv3d_fwd_h_io: 16-bit tensors need Cin, Cout %% 8 == 0; a 16-bit output needs round_out and no residual");
         }
         DIQT_REQUIRE(!stats || !(kd == 1 && kh == 1 && kw == 1), DIQT_E_UNSUPPORTED, "conv3d_fwd_h_io: no statistics from a 1x1x1 conv");
-        static const bool nowide = [] { const char* e = getenv("DIQT_CONVH_NOWIDE"); return e && e[0] == '1'; }();
         // (fp32 rows of a pointwise conv: the 4-wave build below at one chunk per step measures slightly faster than two chunks per step on 8 waves)
-        static const bool pw4first = [] { const char* e = getenv("DIQT_CONVH_PW4"); return !(e && e[0] == '0'); }();
-        if (kd * kh * kw == 1 && g.nChunks >= 2 && !nowide && !(pw4first && !xh)) {
+        if (kd * kh * kw == 1 && g.nChunks >= 2 && xh) {
             // pointwise: 4 MFMAs of a wave per 32-channel chunk and two barriers around them -- stage TWO chunks per step and walk them like
             // taps (their weight panels are consecutive in the packed layout [chunk][tap = 1][co][32])
             g.NS = 2; g.realChunks = g.nChunks; g.nChunks = (g.realChunks + 1) / 2; g.TG = 2; g.nGroups = 1;

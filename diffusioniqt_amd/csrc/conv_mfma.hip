@@ -48,11 +48,8 @@ struct ConvGeom {
     int HD, HH, HWd;            // halo extents
     unsigned xBytes, yBytes;    // tensor extents for the buffer descriptors (BUF kernels; 0 when >= 1 GiB)
     float* stats;               // optional per-tile column sums of the output: [B][tiles per batch][2 (sum, sum of squares)][Cout]
-    int tilesPerWg;             // forward kernel: consecutive tiles per workgroup
-    int stagger;                // experiment: first-round workgroups sleep (slot % stagger) x ~6.4k cycles before starting
     int chunksPerSplit;         // forward split-K over input-channel chunks (grid.y slices; == nChunks when unsplit)
     unsigned long long slabStride;   // floats between the split-K output slabs
-    unsigned long long* dbg;    // diagnostic cycle stamps (NULL in production)
     int subF;                   // > 0: the batch is a cube of subF^3 sub-volumes and halo voxels are read from the NEIGHBOUR sub-volume
 };
 
@@ -145,17 +142,15 @@ constexpr unsigned BUF_OOB = 0x80000000u, BUF_OOB_C = 0x40000000u;
 // tables hold byte offsets (or BUF_OOB for padding voxels / rows outside the output), the hardware range check supplies
 // the zeros and drops the masked stores, and a piece costs ~6 instructions instead of ~25.  These phases share a SIMD
 // with the co-resident workgroup's MFMA stream, which stretches every non-MFMA instruction ~3x (profiles/r01_conv_ablation.md).
-// CKT = channels per staged K-chunk: 32 (78 KB of LDS for a 3x3x3 filter, 2 workgroups per CU) or 16 (44 KB, 3 per CU: a third
-// resident workgroup keeps two waves per SIMD on the MFMA pipe while one stages or stores).  The packed weight layout is the
-// 32-wide one either way; a 16-wide sub-chunk reads half rows of it.
-template <bool VEC4, bool BUF, int CKT>
-__global__ __launch_bounds__(256, CKT == 16 ? 3 : 2) void conv_fwd_kernel(const float* __restrict__ x,
+// A K-chunk is 32 channels: 78 KB of LDS for a 3x3x3 filter, 2 workgroups per CU.
+template <bool VEC4, bool BUF>
+__global__ __launch_bounds__(256, 2) void conv_fwd_kernel(const float* __restrict__ x,
                                                           const float* __restrict__ wp,
                                                           const float* __restrict__ bias,
                                                           const float* __restrict__ residual,
                                                           float* __restrict__ y, ConvGeom g) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    constexpr int LROW = CKT + 4, PCS = CKT / 4, PSH = CKT == 32 ? 3 : 2, SUB = CK / CKT;   // padded row, 16-B pieces per row, log2(PCS), sub-chunks per packed chunk
+    constexpr int LROW = LDSROW, PCS = CK / 4, PSH = 3;   // padded row, 16-B pieces per row, log2(PCS)
     const int HV = g.HD * g.HH * g.HWd;
     float* halo = smem;                                  // [HV][LROW]
     float* wbuf = smem + (size_t)HV * LROW;            // [2][64][LROW]
@@ -166,22 +161,10 @@ __global__ __launch_bounds__(256, CKT == 16 ? 3 : 2) void conv_fwd_kernel(const 
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, h = lane >> 5;
 
-    const unsigned nwg = gridDim.x;
-    if (g.stagger > 1 && blockIdx.x < 512) {
-        const int nsl = __builtin_amdgcn_readfirstlane((int)((blockIdx.x / 8) % g.stagger));
-        for (int i = 0; i < nsl; ++i) __builtin_amdgcn_s_sleep(100);
-    }
-    // a workgroup walks g.tilesPerWg consecutive tiles (1 by default; DIQT_CONV_TPW for the turn-over experiment)
     const unsigned totalTiles = (unsigned)g.B * g.tilesD * g.tilesH * g.tilesW * g.nNt;
-    unsigned long long stamps[8];
-    int nst = 0;
-#define DIQT_STAMP() do { if (g.dbg && nst < 8) stamps[nst++] = __builtin_readcyclecounter(); } while (0)
-    const unsigned long long rt0 = g.dbg ? __builtin_amdgcn_s_memrealtime() : 0ull;
     y += (size_t)blockIdx.y * g.slabStride;   // split-K slab (0 when unsplit)
-    for (int rep = 0; rep < g.tilesPerWg; ++rep) {
-    const unsigned L = xcd_remap(blockIdx.x, nwg) * g.tilesPerWg + rep;
-    if (L >= totalTiles) break;
-    if (rep) __syncthreads();       // the previous tile's epilogue is done with out_off
+    const unsigned L = xcd_remap(blockIdx.x, gridDim.x);
+    if (L >= totalTiles) return;
     const int nt = L % g.nNt;
     int mt = L / g.nNt;
     const int tx = mt % g.tilesW; mt /= g.tilesW;
@@ -225,17 +208,14 @@ __global__ __launch_bounds__(256, CKT == 16 ? 3 : 2) void conv_fwd_kernel(const 
     f32x16 acc0, acc1;
 #pragma unroll
     for (int i = 0; i < 16; ++i) { acc0[i] = 0.f; acc1[i] = 0.f; }
-    DIQT_STAMP();
 
-    const int wrow = tid >> PSH, wc4 = (tid & (PCS - 1)) * 4;      // weight staging: rows wrow (and wrow+32 when CKT == 32)
+    const int wrow = tid >> PSH, wc4 = (tid & (PCS - 1)) * 4;      // weight staging: rows wrow and wrow+32
 
     // split-K (small spatial extents): grid.y slices the input-channel chunks; each slice writes its own output slab
-    const int chunkBeg = blockIdx.y * g.chunksPerSplit * SUB, chunkEnd = min(g.nChunks, (int)(blockIdx.y + 1) * g.chunksPerSplit) * SUB;
+    const int chunkBeg = blockIdx.y * g.chunksPerSplit, chunkEnd = min(g.nChunks, (int)(blockIdx.y + 1) * g.chunksPerSplit);
     for (int chunk = chunkBeg; chunk < chunkEnd; ++chunk) {
-        const int ci0 = chunk * CKT;
-        if (ci0 >= g.Cin) break;      // second half of a ragged last chunk (block-uniform)
+        const int ci0 = chunk * CK;
         __syncthreads();   // all reads of the previous chunk's halo and of both weight buffers are done
-                if (chunk == chunkBeg + 1) DIQT_STAMP();
         // ---- stage halo chunk: loads are UNCONDITIONAL (clamped address, zero-selected afterwards) and issued in batches
         //      of 8 before any LDS store, so a batch costs one memory round trip instead of eight serialized ones ----
         if (BUF) {
@@ -286,24 +266,22 @@ __global__ __launch_bounds__(256, CKT == 16 ? 3 : 2) void conv_fwd_kernel(const 
                         ok[u] ? v[u] : make_float4(0.f, 0.f, 0.f, 0.f);
             }
         }
-        if (chunk == chunkBeg + 1) DIQT_STAMP();
         // ---- weights: panel of tap 0 -> LDS now; panel t+1 is written at the START of tap t (its buffer was last read in
         //      tap t-1, retired by the barrier) from registers loaded during tap t-1, so neither the global latency nor the
         //      LDS write sits between the last MFMA of a tap and its barrier ----
-        const float* wchunk = wp + ((size_t)(chunk / SUB) * T * g.CoutPad + n0) * CK + (chunk % SUB) * CKT;
+        const float* wchunk = wp + ((size_t)chunk * T * g.CoutPad + n0) * CK;
         float4 r0, r1;
         {
             const float4 p0 = *reinterpret_cast<const float4*>(wchunk + (size_t)wrow * CK + wc4);
             *reinterpret_cast<float4*>(wbuf + wrow * LROW + wc4) = p0;
-            if (CKT == 32) *reinterpret_cast<float4*>(wbuf + (wrow + 32) * LROW + wc4) = *reinterpret_cast<const float4*>(wchunk + (size_t)(wrow + 32) * CK + wc4);
+            *reinterpret_cast<float4*>(wbuf + (wrow + 32) * LROW + wc4) = *reinterpret_cast<const float4*>(wchunk + (size_t)(wrow + 32) * CK + wc4);
             if (T > 1) {
                 const float* wt = wchunk + (size_t)g.CoutPad * CK;
                 r0 = *reinterpret_cast<const float4*>(wt + (size_t)wrow * CK + wc4);
-                if (CKT == 32) r1 = *reinterpret_cast<const float4*>(wt + (size_t)(wrow + 32) * CK + wc4);
+                r1 = *reinterpret_cast<const float4*>(wt + (size_t)(wrow + 32) * CK + wc4);
             }
         }
         __syncthreads();
-        DIQT_STAMP();
 
         int tap = 0;
         for (int kz = 0; kz < g.kd; ++kz)
@@ -312,12 +290,12 @@ __global__ __launch_bounds__(256, CKT == 16 ? 3 : 2) void conv_fwd_kernel(const 
                     if (tap + 1 < T) {
                         float* wnext = wbuf + ((tap + 1) & 1) * (NT * LROW);
                         *reinterpret_cast<float4*>(wnext + wrow * LROW + wc4) = r0;
-                        if (CKT == 32) *reinterpret_cast<float4*>(wnext + (wrow + 32) * LROW + wc4) = r1;
+                        *reinterpret_cast<float4*>(wnext + (wrow + 32) * LROW + wc4) = r1;
                     }
                     if (tap + 2 < T) {
                         const float* wt = wchunk + (size_t)(tap + 2) * g.CoutPad * CK;
                         r0 = *reinterpret_cast<const float4*>(wt + (size_t)wrow * CK + wc4);
-                        if (CKT == 32) r1 = *reinterpret_cast<const float4*>(wt + (size_t)(wrow + 32) * CK + wc4);
+                        r1 = *reinterpret_cast<const float4*>(wt + (size_t)(wrow + 32) * CK + wc4);
                     }
                     const float* wcur = wbuf + (tap & 1) * (NT * LROW);
                     const float* ap = halo + (hidx_lane + (kz * g.HH + ky) * g.HWd + kx) * LROW + 4 * h;
@@ -327,9 +305,9 @@ __global__ __launch_bounds__(256, CKT == 16 ? 3 : 2) void conv_fwd_kernel(const 
                     float4 b0 = *reinterpret_cast<const float4*>(bp);
                     float4 b1 = *reinterpret_cast<const float4*>(bp + 32 * LROW);
 #pragma unroll
-                    for (int q = 0; q < CKT / 8; ++q) {
+                    for (int q = 0; q < CK / 8; ++q) {
                         float4 an, b0n, b1n;
-                        if (q < CKT / 8 - 1) {
+                        if (q < CK / 8 - 1) {
                             an = *reinterpret_cast<const float4*>(ap + 8 * (q + 1));
                             b0n = *reinterpret_cast<const float4*>(bp + 8 * (q + 1));
                             b1n = *reinterpret_cast<const float4*>(bp + 32 * LROW + 8 * (q + 1));
@@ -343,11 +321,10 @@ __global__ __launch_bounds__(256, CKT == 16 ? 3 : 2) void conv_fwd_kernel(const 
                         acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b1.z, acc1, 0, 0, 0);
                         acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b0.w, acc0, 0, 0, 0);
                         acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b1.w, acc1, 0, 0, 0);
-                        if (q < CKT / 8 - 1) { a = an; b0 = b0n; b1 = b1n; }
+                        if (q < CK / 8 - 1) { a = an; b0 = b0n; b1 = b1n; }
                     }
                     __syncthreads();
                 }
-        DIQT_STAMP();
     }
 
     // ---- epilogue: D[row=voxel][col=co]; row = (r&3) + 8*(r>>2) + 4*h ----
@@ -413,17 +390,6 @@ __global__ __launch_bounds__(256, CKT == 16 ? 3 : 2) void conv_fwd_kernel(const 
             y[o + co1] = v;
         }
     }
-    DIQT_STAMP();
-    }   // tiles of this workgroup
-    if (g.dbg && tid == 0) {
-        for (int q = 0; q < 8; ++q) g.dbg[(size_t)blockIdx.x * 8 + q] = q < nst ? stamps[q] : 0ull;
-        if (g.stagger == -1) {      // clock probe: slots 1 and 6 carry the constant-rate (100 MHz) counter at start / end
-            g.dbg[(size_t)blockIdx.x * 8 + 1] = rt0;
-            g.dbg[(size_t)blockIdx.x * 8 + 6] = __builtin_amdgcn_s_memrealtime();
-            g.dbg[(size_t)blockIdx.x * 8 + 7] = __builtin_readcyclecounter();
-        }
-    }
-#undef DIQT_STAMP
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1298,9 +1264,6 @@ __global__ __launch_bounds__(NTHR, NTHR / 256) void conv_bwd_weight2_kernel(cons
         }
     };
 
-    long long tsum[5] = {0, 0, 0, 0, 0};
-    long long tprev = g.dbg ? (long long)__builtin_readcyclecounter() : 0;
-#define DIQT_ACC(i) do { if (g.dbg) { const long long tn = (long long)__builtin_readcyclecounter(); tsum[i] += tn - tprev; tprev = tn; } } while (0)
     const int mTW = g.TW - 1, mTH = g.TH - 1, sTH = bg.lTW, sTD = bg.lTW + bg.lTH;
     if (mtBegin < mtEnd) {
         fill_tables(mtBegin, 0);
@@ -1311,14 +1274,10 @@ __global__ __launch_bounds__(NTHR, NTHR / 256) void conv_bwd_weight2_kernel(cons
     for (int mt0 = mtBegin; mt0 < mtEnd; ++mt0) {
         const bool haveNext = mt0 + 1 < mtEnd;
         __syncthreads();                 // all MFMA-phase reads of the previous tile are done
-        DIQT_ACC(0);
         store_tiles();                   // waits for the registers prefetched one tile ago
-        DIQT_ACC(1);
         if (haveNext) fill_tables(mt0 + 1, slot ^ 1);
         __syncthreads();
-        DIQT_ACC(2);
         if (haveNext) issue_loads(slot ^ 1);
-        DIQT_ACC(3);
         if (ntap > 0) {
             // voxel v = 2*s2 + h: bit 0 of v lies in exactly one of the (td, th, tw) bit-fields, so the halo offset of v is
             // offset(2*s2) [wave-uniform, scalar ALU] + offset(h) [per lane, hoisted]
@@ -1353,14 +1312,8 @@ __global__ __launch_bounds__(NTHR, NTHR / 256) void conv_bwd_weight2_kernel(cons
                 mm(a1, b1);
             }
         }
-        DIQT_ACC(4);
         slot ^= 1;
     }
-    if (g.dbg && lane == 0)       // one record per wave: 5 phase sums + SIMD id (HW_REG_HW_ID bits 5:4)
-        for (int q = 0; q < 6; ++q)
-            g.dbg[(((size_t)blockIdx.y * gridDim.x + blockIdx.x) * NWAVE + wave) * 8 + q] =
-                q < 5 ? (unsigned long long)tsum[q] : (unsigned long long)((__builtin_amdgcn_s_getreg((6 - 1) << 11 | 0 << 6 | 4) >> 4) & 3);
-#undef DIQT_ACC
 
     if (doBias) {                        // block-uniform
         __syncthreads();
@@ -1575,7 +1528,6 @@ static int make_geom(ConvGeom& g, int B, int D, int H, int W, int Cin, int Cout,
         DIQT_REQUIRE(rows < (1ll << 31), DIQT_E_SHAPE, "conv3d: too many rows");
         B = 1; D = 1; H = 1; W = (int)rows;
     }
-    g.dbg = nullptr;
     g.subF = 0;
     g.B = B; g.D = D; g.H = H; g.W = W; g.Cin = Cin; g.Cout = Cout;
     g.kd = kd; g.kh = kh; g.kw = kw; g.pd = pd; g.ph = ph; g.pw = pw;
@@ -1585,8 +1537,7 @@ static int make_geom(ConvGeom& g, int B, int D, int H, int W, int Cin, int Cout,
     choose_tile(g.Do, g.Ho, g.Wo, kd, kh, kw, g.TD, g.TH, g.TW);
     g.tilesD = cdiv(g.Do, g.TD); g.tilesH = cdiv(g.Ho, g.TH); g.tilesW = cdiv(g.Wo, g.TW);
     g.nNt = cdiv(Cout, NT); g.CoutPad = g.nNt * NT; g.nChunks = cdiv(Cin, CK);
-    g.chunksPerSplit = g.nChunks; g.slabStride = 0; g.xBytes = 0; g.yBytes = 0; g.tilesPerWg = 1; g.stats = nullptr;
-    { static const int stg = [] { const char* e = getenv("DIQT_CONV_STAGGER"); return e ? atoi(e) : 0; }(); g.stagger = stg; }
+    g.chunksPerSplit = g.nChunks; g.slabStride = 0; g.xBytes = 0; g.yBytes = 0; g.stats = nullptr;
     g.HD = g.TD + kd - 1; g.HH = g.TH + kh - 1; g.HWd = g.TW + kw - 1;
     const long long nwg = (long long)g.B * g.tilesD * g.tilesH * g.tilesW * g.nNt;
     DIQT_REQUIRE(nwg < (1ll << 31), DIQT_E_SHAPE, "conv3d: grid too large");
@@ -1597,26 +1548,6 @@ static int make_geom(ConvGeom& g, int B, int D, int H, int W, int Cin, int Cout,
 }  // namespace diqt
 
 using namespace diqt;
-
-static unsigned long long* g_dbg_ptr = nullptr;   // diagnostic cycle-stamp buffer of the last DIQT_CONV_DBG=1 launch
-static unsigned g_dbg_n = 0;
-
-// diagnostic only (not part of include/diqt.h): copies the cycle stamps of the last DIQT_CONV_DBG=1 launch to the host
-extern "C" int diqt_debug_wgrad3_stamps(unsigned long long* host_out, unsigned max_waves) {
-    if (!wgrad3_dbg_ptr || !wgrad3_dbg_n) return 0;
-    const unsigned n = wgrad3_dbg_n < max_waves ? wgrad3_dbg_n : max_waves;
-    (void)hipDeviceSynchronize();
-    (void)hipMemcpy(host_out, wgrad3_dbg_ptr, (size_t)n * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-    return (int)n;
-}
-
-extern "C" int diqt_debug_conv_stamps(unsigned long long* host_out, unsigned max_wg) {
-    if (!g_dbg_ptr || !g_dbg_n) return 0;
-    const unsigned n = g_dbg_n < max_wg ? g_dbg_n : max_wg;
-    (void)hipDeviceSynchronize();
-    (void)hipMemcpy(host_out, g_dbg_ptr, (size_t)n * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-    return (int)n;
-}
 
 extern "C" size_t diqt_conv_packed_elems(int Cout, int Cin, int kd, int kh, int kw) {
     if (Cout <= 0 || Cin <= 0 || kd <= 0 || kh <= 0 || kw <= 0) return 0;
@@ -1632,8 +1563,7 @@ extern "C" long long diqt_conv3d_lds_bytes(int D, int H, int W, int kd, int kh, 
 
 // forward convs with <= 4 input channels and more than one tap use the tap-packed kernel (and its weight packing)
 static inline int smallcin_pad(int Cin, int T) {
-    static const bool off = [] { const char* e = getenv("DIQT_CONV_NOSMALLCIN"); return e && e[0] == '1'; }();
-    if (off || Cin > 4 || T < 2) return 0;
+    if (Cin > 4 || T < 2) return 0;
     return Cin == 3 ? 4 : Cin;
 }
 
@@ -1676,9 +1606,8 @@ extern "C" int diqt_conv_pack_weight(const float* w, float* packed, int Cout, in
 
 // forward split-K plan: launches with fewer than ~1.5 resident rounds' worth of workgroups slice the Cin chunks
 static int fwd_ksplit(const ConvGeom& g) {
-    static const bool off = [] { const char* e = getenv("DIQT_CONV_NOSPLIT"); return e && e[0] == '1'; }();
     const long long nwg = (long long)g.B * g.tilesD * g.tilesH * g.tilesW * g.nNt;
-    if (off || nwg >= 384 || g.nChunks < 2) return 1;
+    if (nwg >= 384 || g.nChunks < 2) return 1;
     int ks = (int)(512 / nwg);
     if (ks > g.nChunks) ks = g.nChunks;
     if (ks > 16) ks = 16;
@@ -1752,10 +1681,9 @@ extern "C" int diqt_conv3d_fwd(const float* x, const float* packed, const float*
 // 8-wave forward plan: the geometry re-tiled for 256-voxel workgroups, or false when conv_fwd8_kernel does not take the launch
 // (fewer than two resident rounds of 256-voxel tiles, halo beyond the prefetch registers or the LDS, tensors >= 1 GiB, Cin % 4)
 static bool fwd8_plan(const ConvGeom& g, ConvGeom& g8, size_t& lds) {
-    static const int mode = [] { const char* e = getenv("DIQT_CONV_W8"); return e ? atoi(e) : 1; }();      // 0: never
     const int T = g.kd * g.kh * g.kw;
     // measured: +1.2 % on 27-tap filters, -3.5 % on the 9-tap (1,3,3) filters of the pseudo-3D blocks (a chunk there is 3 steps long)
-    if (!mode || (T < 12 && mode != 2) || T < 2 || g.Cin % 4 != 0 || smallcin_pad(g.Cin, T)) return false;
+    if (T < 12 || g.Cin % 4 != 0 || smallcin_pad(g.Cin, T)) return false;
     const unsigned long long xb = (unsigned long long)g.B * g.D * g.H * g.W * g.Cin * 4ull;
     const unsigned long long yb = (unsigned long long)g.B * g.Do * g.Ho * g.Wo * g.Cout * 4ull;
     if (xb >= (1ull << 30) || yb >= (1ull << 30)) return false;
@@ -1778,8 +1706,8 @@ static bool fwd8_plan(const ConvGeom& g, ConvGeom& g8, size_t& lds) {
     g8.HD = g8.TD + g.kd - 1; g8.HH = g8.TH + g.kh - 1; g8.HWd = g8.TW + g.kw - 1;
     const long long nwg8 = (long long)g.B * g8.tilesD * g8.tilesH * g8.tilesW * g.nNt;
     // one workgroup per CU: the launch has to fill whole rounds of 256 (128->192 @ 8x16^3 = 384 workgroups = 1.5 rounds ran 26 % slower
-    // than on the 4-wave kernel, whose two workgroups per CU halve the granularity); mode 2: always
-    if (mode != 2 && (nwg8 < 256 || (double)nwg8 / (double)((nwg8 + 255) / 256 * 256) < 0.94)) return false;
+    // than on the 4-wave kernel, whose two workgroups per CU halve the granularity)
+    if (nwg8 < 256 || (double)nwg8 / (double)((nwg8 + 255) / 256 * 256) < 0.94) return false;
     g8.xBytes = (unsigned)xb; g8.yBytes = (unsigned)yb;
     return true;
 }
@@ -1804,10 +1732,8 @@ extern "C" int diqt_conv3d_fwd_neighbours_stats_blocks(int f, int A, int Cin, in
 }
 static int fwd_stats_blocks_impl(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw, int epd,
                                  int eph, int epw, bool neighbours, bool wino) {
-    static const bool off = [] { const char* e = getenv("DIQT_CONV_NOSTATS"); return e && e[0] == '1'; }();
-    static const bool nobuf = [] { const char* e = getenv("DIQT_CONV_NOBUF"); return e && e[0] == '1'; }();
     ConvGeom g;
-    if (off || nobuf || make_geom(g, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw)) return 0;
+    if (make_geom(g, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw)) return 0;
     if (kd * kh * kw == 1) return 0;                                   // flattened 1x1x1 tiles cross batch entries
     if (Cin % 4 != 0 || smallcin_pad(Cin, kd * kh * kw) || fwd_ksplit(g) > 1) return 0;
     const unsigned long long xb = (unsigned long long)g.B * g.D * g.H * g.W * g.Cin * 4ull;
@@ -1983,11 +1909,10 @@ static int conv3d_fwd_one(const float* x, const float* packed, const float* bias
 // for) and has the instantiation for this filter and activation; otherwise run diqt_gn_act_fwd + diqt_conv3d_fwd_ex.
 static int fwd_gn_supported(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw, int epd, int eph,
                             int epw, int act, bool wino) {
-    static const bool off = [] { const char* e = getenv("DIQT_CONV_NOGNA"); return e && e[0] == '1'; }();       // A/B switch
     F9Geom g9;
     size_t l9;
     unsigned gr9;
-    if (off || Cin % 4 != 0 || smallcin_pad(Cin, kd * kh * kw)) return 0;
+    if (Cin % 4 != 0 || smallcin_pad(Cin, kd * kh * kw)) return 0;
     if (!fwd9_plan(g9, l9, gr9, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, diqt_conv_packed_elems(Cout, Cin, kd, kh, kw), true, wino))
         return 0;
     if (!fwd9_gna_available(g9.variant, act)) return 0;
@@ -2160,37 +2085,19 @@ static int conv3d_fwd_one(const float* x, const float* packed, const float* bias
         }
         DIQT_REQUIRE(false, DIQT_E_UNSUPPORTED, "conv3d_fwd: small-Cin halo needs %zu B of LDS", slds);
     }
-    static const size_t ldspad = [] { const char* e = getenv("DIQT_CONV_LDSPAD"); return e ? (size_t)atoi(e) * 1024 : (size_t)0; }();   // occupancy experiment
-    size_t lds = ((size_t)HV * (LDSROW + 1) + 2 * NT * LDSROW) * sizeof(float) + MTILE * sizeof(int) + ldspad;
+    const size_t lds = ((size_t)HV * (LDSROW + 1) + 2 * NT * LDSROW) * sizeof(float) + MTILE * sizeof(int);
     DIQT_REQUIRE(lds <= 160 * 1024, DIQT_E_UNSUPPORTED, "conv3d_fwd: halo tile needs %zu B of LDS", lds);
     const unsigned long long xb = (unsigned long long)g.B * g.D * g.H * g.W * g.Cin * 4ull;
     const unsigned long long yb = (unsigned long long)g.B * g.Do * g.Ho * g.Wo * g.Cout * 4ull;
-    static const bool nobuf = [] { const char* e = getenv("DIQT_CONV_NOBUF"); return e && e[0] == '1'; }();
-    const bool buf = vec4 && !nobuf && xb < (1ull << 30) && yb < (1ull << 30);
+    const bool buf = vec4 && xb < (1ull << 30) && yb < (1ull << 30);
     if (buf) { g.xBytes = (unsigned)xb; g.yBytes = (unsigned)yb; }
-    // opt-in experiment (DIQT_CONV_CK16=1): 16-channel chunks = 44 KB of LDS for a 3x3x3 filter = three workgroups per CU instead of
-    // two.  Measured 2 % SLOWER on MI355X (64->64 @ 8x32^3: 467 vs 458 us; 128->128 @ 8x16^3: 243 vs 227 us): a third resident
-    // workgroup does not fill the staging bubbles, the doubled barrier count costs more (profiles/r01_conv_ablation.md)
-    static const int ck16_env = [] { const char* e = getenv("DIQT_CONV_CK16"); return e ? atoi(e) : 0; }();
-    const size_t lds16 = ((size_t)HV * (CK / 2 + 4 + 1) + 2 * NT * (CK / 2 + 4)) * sizeof(float) + MTILE * sizeof(int);
-    const bool ck16_ok = buf && lds16 * 3 <= 160 * 1024 && kd * kh * kw > 1;
-    const bool ck16 = ck16_ok && ck16_env == 1;
-    if (ck16) lds = lds16 + ldspad;
-    auto kern = vec4 ? (buf ? (ck16 ? conv_fwd_kernel<true, true, 16> : conv_fwd_kernel<true, true, 32>) : conv_fwd_kernel<true, false, 32>)
-                     : conv_fwd_kernel<false, false, 32>;
-    static unsigned long long* dbg_buf = nullptr;
-    static const bool dbg_on = [] { const char* e = getenv("DIQT_CONV_DBG"); return e && e[0] == '1'; }();
-    if (dbg_on) {     // diagnostic build path only: cycle stamps per workgroup, read back with diqt_debug_conv_stamps()
-        if (!dbg_buf) (void)hipMalloc(&dbg_buf, (size_t)65536 * 8 * sizeof(unsigned long long));
-        if (nwg <= 65536) g.dbg = dbg_buf;
-        g_dbg_ptr = dbg_buf; g_dbg_n = nwg <= 65536 ? nwg : 0;
-    }
+    auto kern = vec4 ? (buf ? conv_fwd_kernel<true, true> : conv_fwd_kernel<true, false>) : conv_fwd_kernel<false, false>;
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         DIQT_REQUIRE(e == hipSuccess, DIQT_E_LAUNCH, "conv3d_fwd: hipFuncSetAttribute: %s", hipGetErrorString(e));
     }
-    if (buf && !ck16 && g.subF == 0) {
+    if (buf && g.subF == 0) {
         // conv_fwd9_kernel first: whole rounds of 512- / 256-voxel tiles, or (small volumes) split-K slabs in the caller's workspace
         F9Geom g9;
         size_t l9;
@@ -2215,11 +2122,6 @@ static int conv3d_fwd_one(const float* x, const float* packed, const float* bias
         }
     }
     const int ks = workspace ? fwd_ksplit(g) : 1;
-    static const int tpw_env = [] { const char* e = getenv("DIQT_CONV_TPW"); return e ? atoi(e) : 0; }();
-    int tpw = tpw_env > 0 ? tpw_env : 1;      // measured: 2 or 4 tiles per workgroup change nothing (457 / 464 / 459 us), see profiles/r01_conv_ablation.md
-    if (dbg_on) tpw = 1;
-    g.tilesPerWg = tpw;
-    const unsigned gridx = (nwg + tpw - 1) / tpw;
     if (ks > 1) {
         const size_t n = (size_t)g.B * g.Do * g.Ho * g.Wo * g.Cout;
         DIQT_REQUIRE(workspace_bytes >= (size_t)ks * n * sizeof(float) && aligned16(workspace), DIQT_E_WORKSPACE,
@@ -2227,7 +2129,7 @@ static int conv3d_fwd_one(const float* x, const float* packed, const float* bias
         g.chunksPerSplit = cdiv(g.nChunks, ks);
         g.slabStride = n;
         float* slabs = static_cast<float*>(workspace);
-        hipLaunchKernelGGL(kern, dim3(gridx, ks), dim3(256), lds, (hipStream_t)stream, x, packed, nullptr, nullptr, slabs, g);
+        hipLaunchKernelGGL(kern, dim3(nwg, ks), dim3(256), lds, (hipStream_t)stream, x, packed, nullptr, nullptr, slabs, g);
         rc = check_launch("conv3d_fwd(split-K)");
         if (rc) return rc;
         hipLaunchKernelGGL(conv_fwd_reduce_kernel, dim3(grid_for(n, 256, 2048)), dim3(256), 0, (hipStream_t)stream, slabs, bias,
@@ -2236,32 +2138,29 @@ static int conv3d_fwd_one(const float* x, const float* packed, const float* bias
     }
     DIQT_REQUIRE(!stats || buf, DIQT_E_UNSUPPORTED, "conv3d_fwd: output statistics need the buffer-path kernel");
     g.stats = stats;
-    if (buf && !ck16) {
+    if (buf) {
         ConvGeom g8;
         size_t lds8;
         if (fwd8_plan(g, g8, lds8)) {
             g8.stats = stats;
-            g8.dbg = nullptr;
             if (lds8 > 64 * 1024) {
                 hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_fwd8_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds8);
                 DIQT_REQUIRE(e == hipSuccess, DIQT_E_LAUNCH, "conv3d_fwd: hipFuncSetAttribute: %s", hipGetErrorString(e));
             }
             const unsigned nwg8 = (unsigned)((long long)g8.B * g8.tilesD * g8.tilesH * g8.tilesW * g8.nNt);
             // persistent tile walk: one workgroup per CU runs all its tiles (needs a 64-channel block that stays with the workgroup)
-            static const bool nopersist = [] { const char* e = getenv("DIQT_CONV_W8_NOPERSIST"); return e && e[0] == '1'; }();
-            const unsigned grid8 = (!nopersist && nwg8 > 256u && 256 % g8.nNt == 0) ? 256u : nwg8;
+            const unsigned grid8 = (nwg8 > 256u && 256 % g8.nNt == 0) ? 256u : nwg8;
             hipLaunchKernelGGL(conv_fwd8_kernel, dim3(grid8), dim3(512), lds8, (hipStream_t)stream, x, packed, bias, residual, y, g8);
             return check_launch("conv3d_fwd(8 waves)");
         }
     }
-    static const bool no1x1 = [] { const char* e = getenv("DIQT_CONV_NO1X1"); return e && e[0] == '1'; }();
-    if (buf && !stats && !dbg_on && !no1x1 && kd * kh * kw == 1 && g.B == 1 && g.D == 1 && g.H == 1 && g.Wo == g.W && g.TW == MTILE) {     // the flattened-rows geometry of make_geom
+    if (buf && !stats && kd * kh * kw == 1 && g.B == 1 && g.D == 1 && g.H == 1 && g.Wo == g.W && g.TW == MTILE) {     // the flattened-rows geometry of make_geom
         if (pw64_ok((long long)g.W, Cin, Cout, x, packed, y))      // few input channels, many output channels: x resident, persistent row walk
             return pw64_launch(x, packed, bias, residual, y, (long long)g.W, Cout, g.CoutPad, stream);
         hipLaunchKernelGGL(conv1x1_fwd_kernel, dim3(nwg), dim3(256), 0, (hipStream_t)stream, x, packed, bias, residual, y, g);
         return check_launch("conv3d_fwd(1x1x1)");
     }
-    hipLaunchKernelGGL(kern, dim3(gridx), dim3(256), lds, (hipStream_t)stream, x, packed, bias, residual, y, g);
+    hipLaunchKernelGGL(kern, dim3(nwg), dim3(256), lds, (hipStream_t)stream, x, packed, bias, residual, y, g);
     return check_launch("conv3d_fwd");
 }
 
@@ -2289,8 +2188,6 @@ constexpr int BW2_MAXT_A = 7, BW2_MAXT_B = 3;   // A: 4 SIMDs x 7 taps per group
 constexpr int BW2_KPAR_A = 1;                   // slabs written per workgroup in mode A (the k-interleaved wave pairs are combined in LDS)
 // version-2 plan; returns false when the shape needs the generic (version-1) kernel
 static bool bw2_plan(const ConvGeom& g, BwGeom2& b2, bool& splitCo, int& ksplit, size_t& lds) {
-    static const bool off = [] { const char* e = getenv("DIQT_BWDW_V1"); return e && e[0] == '1'; }();
-    if (off) return false;
     const int T = g.kd * g.kh * g.kw, HV = g.HD * g.HH * g.HWd;
     splitCo = T <= BW2_MAXT_B;
     if (splitCo ? (HV * 8 > 256 * 8) : (HV * 8 > 512 * 7)) return false;      // register-staged halo pieces: NRX = 8 / 7 per thread
@@ -2306,8 +2203,7 @@ static bool bw2_plan(const ConvGeom& g, BwGeom2& b2, bool& splitCo, int& ksplit,
     b2.coBlocks = cdiv(g.CoutPad, COB);
     b2.MT = g.B * g.tilesD * g.tilesH * g.tilesW;
     const int gx = g.nChunks * b2.coBlocks * b2.tapGroups;
-    static const int wgs = [] { const char* e = getenv("DIQT_BWDW_WGS"); return e ? atoi(e) : 256; }();
-    ksplit = wgs / gx;      // ONE workgroup per CU: the kernel needs >256 VGPRs to keep its LDS reads batched ahead of the MFMAs
+    ksplit = 256 / gx;      // ONE workgroup per CU: the kernel needs >256 VGPRs to keep its LDS reads batched ahead of the MFMAs
     if (ksplit > b2.MT) ksplit = b2.MT;
     if (ksplit < 1) ksplit = 1;
     b2.tilesPerSplit = cdiv(b2.MT, ksplit);
@@ -2332,9 +2228,8 @@ extern "C" size_t diqt_reduce_workspace_bytes(int B, int C);
 struct PwPlan { bool ok; long long V; int ks; bool xFirst; int M, N; };
 static PwPlan pw_plan(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw, int epd,
                       int eph, int epw) {
-    static const bool off = [] { const char* e = getenv("DIQT_BWDW_NOGEMM"); return e && e[0] == '1'; }();
     PwPlan p{};
-    p.ok = !off && kd == 1 && kh == 1 && kw == 1 && pd == 0 && ph == 0 && pw == 0 && epd == 0 && eph == 0 && epw == 0;
+    p.ok = kd == 1 && kh == 1 && kw == 1 && pd == 0 && ph == 0 && pw == 0 && epd == 0 && eph == 0 && epw == 0;
     if (!p.ok) return p;
     p.V = (long long)B * D * H * W;
     p.xFirst = Cin >= Cout;                      // the larger channel count takes the 128-row side of the tile
@@ -2649,12 +2544,6 @@ extern "C" int diqt_conv3d_bwd_weight(const float* x, const float* dy, float* dw
             DIQT_REQUIRE(e == hipSuccess, DIQT_E_LAUNCH, "conv3d_bwd_weight: hipFuncSetAttribute: %s", hipGetErrorString(e));
         }
         ksplit = ks2 * (splitCo ? 1 : BW2_KPAR_A);
-        static unsigned long long* bdbg = nullptr;
-        static const bool bdbg_on = [] { const char* e = getenv("DIQT_CONV_DBG"); return e && e[0] == '1'; }();
-        if (bdbg_on) {
-            if (!bdbg) (void)hipMalloc(&bdbg, (size_t)65536 * 8 * sizeof(unsigned long long));
-            b2.g.dbg = bdbg; g_dbg_ptr = bdbg; g_dbg_n = g.nChunks * b2.coBlocks * b2.tapGroups * ks2 * (splitCo ? 4 : 8);
-        }
         if (dbias) { bias_part = slabs + (size_t)ksplit * g.nChunks * T * g.CoutPad * CK; bias_parts = ks2; }
         hipLaunchKernelGGL(k2, dim3(g.nChunks * b2.coBlocks * b2.tapGroups, ks2), dim3(splitCo ? 256 : 512), lds2, s, x, dy, slabs,
                            bias_part, b2);

@@ -145,8 +145,7 @@ __global__ __launch_bounds__(256, 1) void conv1x1_k64_kernel(const float* __rest
 }
 
 bool pw64_ok(long long rows, int Cin, int Cout, const void* x, const void* packed, const void* y) {
-    static const bool off = [] { const char* e = getenv("DIQT_NO_PW64"); return e && e[0] == '1'; }();
-    if (off || Cin != PW_K || Cout < 256 || rows < 4096) return false;      // measured: 64 -> 512 216 vs 246 us, 64 -> 128 66 vs 61 us
+    if (Cin != PW_K || Cout < 256 || rows < 4096) return false;      // measured: 64 -> 512 216 vs 246 us, 64 -> 128 66 vs 61 us
     if ((unsigned long long)rows * Cin * 4ull >= (1ull << 31) || (unsigned long long)rows * Cout * 4ull >= (1ull << 31)) return false;
     return ((size_t)x & 15) == 0 && ((size_t)packed & 15) == 0 && ((size_t)y & 3) == 0;
 }

@@ -9,7 +9,6 @@
 //   2. per output voxel  y[v][o] = bias[o] + sum_t z[v + t][t, o]  (+ residual)           (a T-point gather in LDS).
 // Exact fp32 FMAs; any Cin (rows need not be 16-byte aligned), T * Cout <= 32.
 #include "common.h"
-#include <stdlib.h>
 
 namespace diqt {
 namespace {
@@ -199,8 +198,7 @@ using namespace diqt;
 
 extern "C" int diqt_conv3d_fwd_smallcout_supported(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph,
                                                    int pw, int epd, int eph, int epw) {
-    static const bool off = [] { const char* e = getenv("DIQT_NO_SMALLCOUT"); return e && e[0] == '1'; }();
-    if (off || !sc_variant(kd, kh, kw, Cout) || Cin < 16) return 0;
+    if (!sc_variant(kd, kh, kw, Cout) || Cin < 16) return 0;
     SCGeom g;
     size_t lds;
     return sc_geom(g, lds, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw) ? 1 : 0;

@@ -9,7 +9,6 @@ struct W3Geom {
     int tilesD, tilesH, tilesW, MT, tilesPerSplit;
     int nCoB, nCiB, CoutPad, nChunks32;
     unsigned xBytes, yBytes;
-    unsigned long long* dbg;     // diagnostic cycle stamps (NULL in production): 8 words per wave
 };
 
 // Does conv_wgrad3_kernel take this shape?  Fills the geometry, the template variant, the split-K count (= slabs written, in the
@@ -18,8 +17,5 @@ bool wgrad3_plan(W3Geom& g, int& variant, int& ksplit, size_t& lds, int B, int D
                  int kw, int pd, int ph, int pw, int epd, int eph, int epw);
 int wgrad3_launch(const float* x, const float* dy, float* slabs, float* bias_part, const W3Geom& g, int variant, int ksplit, size_t lds,
                   void* stream);
-
-extern unsigned long long* wgrad3_dbg_ptr;   // stamps of the last DIQT_CONV_DBG=1 launch (8 words per wave)
-extern unsigned wgrad3_dbg_n;
 
 }  // namespace diqt

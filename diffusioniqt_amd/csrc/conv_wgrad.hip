@@ -24,7 +24,6 @@
 // (/root/reference/imagen_pytorch3D.py:535-566 Block.project, imagen_video.py:352-406).
 #include "common.h"
 #include "conv_wgrad.h"
-#include <stdlib.h>
 
 namespace diqt {
 
@@ -176,10 +175,6 @@ __device__ __forceinline__ void w3_wave(const float* __restrict__ x, const float
     const bool doBias = bias_part != nullptr && cib == 0 && PATH != 1 && ciq == 0;
     float bsum = 0.f;
 
-    // diagnostic stamps (DIQT_CONV_DBG=1): taken at tile boundaries only, outside the unrolled k-loop block
-    const bool dbg = g.dbg != nullptr;
-    long long tK = 0, tB = 0, tStart = dbg ? (long long)__builtin_readcyclecounter() : 0, tPro = 0;
-    const unsigned long long rt0 = dbg ? __builtin_amdgcn_s_memrealtime() : 0ull;
     if (mtBegin < mtEnd) {
         // ---- prologue: tile 0 -> buffer 0 ----
         set_dma_tile();
@@ -195,9 +190,7 @@ __device__ __forceinline__ void w3_wave(const float* __restrict__ x, const float
         const int aLane = (h * 64 + cq * 32 + l31) * 4 + C::XB;
         const int bLane = (h * C::CIW + ciq * 32 + l31) * 4;
         int cur = 0;
-        if (dbg) tPro = (long long)__builtin_readcyclecounter() - tStart;
         for (int mt0 = mtBegin; mt0 < mtEnd; ++mt0) {
-            const long long tt0 = dbg ? (long long)__builtin_readcyclecounter() : 0;
             const bool haveNext = mt0 + 1 < mtEnd;
 #ifdef W3_DEADDMA
             const unsigned deadNext = 0x80000000u;
@@ -260,15 +253,12 @@ __device__ __forceinline__ void w3_wave(const float* __restrict__ x, const float
 #undef W3_RD
 #undef W3_MM
             if (haveNext) advance_tile();
-            const long long tt1 = dbg ? (long long)__builtin_readcyclecounter() : 0;
             __builtin_amdgcn_s_waitcnt(0x0f70);           // this wave's pieces of the next tile have landed
             __syncthreads();                              // ... everybody's have, and everybody is done reading the current buffer
-            if (dbg) { const long long tt2 = (long long)__builtin_readcyclecounter(); tK += tt1 - tt0; tB += tt2 - tt1; }
             cur ^= 1;
         }
     }
 
-    const long long tLoopEnd = dbg ? (long long)__builtin_readcyclecounter() : 0;
     // ---- bias gradient partial: sum over the two voxel parities (lane halves), one row per split-K slice ----
     if (doBias) {
         bsum += __shfl_xor(bsum, 32, 64);
@@ -315,14 +305,6 @@ __device__ __forceinline__ void w3_wave(const float* __restrict__ x, const float
             }
         }
     }
-    if (dbg && lane == 0) {
-        __builtin_amdgcn_s_waitcnt(0x0f70);
-        unsigned long long* o = g.dbg + (((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 4 + wave) * 8;
-        const long long tEnd = (long long)__builtin_readcyclecounter();
-        o[0] = (unsigned long long)(tEnd - tStart); o[1] = (unsigned long long)tK; o[2] = (unsigned long long)tB;
-        o[3] = (unsigned long long)tPro; o[4] = (unsigned long long)(tEnd - tLoopEnd);
-        o[5] = __builtin_amdgcn_s_memrealtime() - rt0; o[6] = (unsigned long long)(E_N + O_N); o[7] = (unsigned long long)(mtEnd - mtBegin);
-    }
 }
 
 template <class C>
@@ -345,11 +327,11 @@ using W3_311 = W3Cfg<3, 1, 1, 8, 2, 4, 1>;
 using W3_111 = W3Cfg<1, 1, 1, 2, 4, 8, 1>;       // pointwise convs / Linear layers: dW = dY^T X over all rows, taken as 64-row tiles
 
 template <class C> static bool w3_fill(W3Geom& g, int B, int D, int H, int W, int Cin, int Cout, int pd, int ph, int pw, int epd,
-                                       int eph, int epw, int& ksplit, size_t& lds, int wgs) {
+                                       int eph, int epw, int& ksplit, size_t& lds) {
     g.B = B; g.D = D; g.H = H; g.W = W; g.Cin = Cin; g.Cout = Cout;
     g.Do = D + 2 * pd + epd - C::KD + 1; g.Ho = H + 2 * ph + eph - C::KH + 1; g.Wo = W + 2 * pw + epw - C::KW + 1;
     if (g.Do <= 0 || g.Ho <= 0 || g.Wo <= 0) return false;
-    g.pd = pd; g.ph = ph; g.pw = pw; g.dbg = nullptr;
+    g.pd = pd; g.ph = ph; g.pw = pw;
     g.tilesD = (g.Do + C::TD - 1) / C::TD; g.tilesH = (g.Ho + C::TH - 1) / C::TH; g.tilesW = (g.Wo + C::TW - 1) / C::TW;
     g.nCoB = (Cout + 63) / 64; g.CoutPad = g.nCoB * 64; g.nChunks32 = (Cin + 31) / 32;
     g.nCiB = (Cin + C::CIW - 1) / C::CIW;
@@ -360,7 +342,7 @@ template <class C> static bool w3_fill(W3Geom& g, int B, int D, int H, int W, in
     if (xb >= (1ull << 30) || yb >= (1ull << 30)) return false;       // 32-bit buffer offsets with an out-of-range sentinel
     g.xBytes = (unsigned)xb; g.yBytes = (unsigned)yb;
     const int gx = g.nCoB * g.nCiB;
-    ksplit = wgs / gx;                                                 // one workgroup per CU, one resident round
+    ksplit = 256 / gx;                                                 // one workgroup per CU, one resident round
     if (ksplit > g.MT) ksplit = g.MT;
     if (ksplit < 1) ksplit = 1;
     g.tilesPerSplit = (g.MT + ksplit - 1) / ksplit;
@@ -370,9 +352,6 @@ template <class C> static bool w3_fill(W3Geom& g, int B, int D, int H, int W, in
     if (stage > lds) lds = stage;
     return lds <= 160 * 1024;
 }
-
-unsigned long long* wgrad3_dbg_ptr = nullptr;
-unsigned wgrad3_dbg_n = 0;
 
 // which instantiation takes the filter (0 none)
 static int w3_variant(int kd, int kh, int kw) {
@@ -385,23 +364,20 @@ static int w3_variant(int kd, int kh, int kw) {
 
 bool wgrad3_plan(W3Geom& g, int& variant, int& ksplit, size_t& lds, int B, int D, int H, int W, int Cin, int Cout, int kd, int kh,
                  int kw, int pd, int ph, int pw, int epd, int eph, int epw) {
-    static const int mode = [] { const char* e = getenv("DIQT_BWDW_V3"); return e ? atoi(e) : 1; }();     // 0: never
-    static const int wgs = [] { const char* e = getenv("DIQT_BWDW_WGS"); return e ? atoi(e) : 256; }();
-    variant = mode ? w3_variant(kd, kh, kw) : 0;
+    variant = w3_variant(kd, kh, kw);
     if (!variant || Cin % 4 != 0 || Cout % 4 != 0 || Cin < 16) return false;
     if (variant == 4) {
         // a pointwise filter sees rows, not a volume: any [B, D, H, W] (Linear layers arrive as one long row axis) is re-cut into
         // V / 64 "batch entries" of one 2 x 4 x 8 tile each
-        static const bool pw3 = [] { const char* e = getenv("DIQT_PW_V3"); return !(e && e[0] == '0'); }();
         const long long V = (long long)B * D * H * W;
-        if (!pw3 || pd || ph || pw || epd || eph || epw || V % 64 != 0 || V / 64 >= (1ll << 30)) return false;
-        return w3_fill<W3_111>(g, (int)(V / 64), 2, 4, 8, Cin, Cout, 0, 0, 0, 0, 0, 0, ksplit, lds, wgs);
+        if (pd || ph || pw || epd || eph || epw || V % 64 != 0 || V / 64 >= (1ll << 30)) return false;
+        return w3_fill<W3_111>(g, (int)(V / 64), 2, 4, 8, Cin, Cout, 0, 0, 0, 0, 0, 0, ksplit, lds);
     }
     if (D > 255 || H > 255 || W > 255) return false;                   // packed 8-bit tile coordinates
     switch (variant) {
-        case 1: return w3_fill<W3_333>(g, B, D, H, W, Cin, Cout, pd, ph, pw, epd, eph, epw, ksplit, lds, wgs);
-        case 2: return w3_fill<W3_133>(g, B, D, H, W, Cin, Cout, pd, ph, pw, epd, eph, epw, ksplit, lds, wgs);
-        default: return w3_fill<W3_311>(g, B, D, H, W, Cin, Cout, pd, ph, pw, epd, eph, epw, ksplit, lds, wgs);
+        case 1: return w3_fill<W3_333>(g, B, D, H, W, Cin, Cout, pd, ph, pw, epd, eph, epw, ksplit, lds);
+        case 2: return w3_fill<W3_133>(g, B, D, H, W, Cin, Cout, pd, ph, pw, epd, eph, epw, ksplit, lds);
+        default: return w3_fill<W3_311>(g, B, D, H, W, Cin, Cout, pd, ph, pw, epd, eph, epw, ksplit, lds);
     }
 }
 
@@ -412,16 +388,7 @@ template <class C> static int w3_launch(const float* x, const float* dy, float* 
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         DIQT_REQUIRE(e == hipSuccess, DIQT_E_LAUNCH, "conv3d_bwd_weight(v3): hipFuncSetAttribute: %s", hipGetErrorString(e));
     }
-    W3Geom gg = g;
-    static const bool dbg_on = [] { const char* e = getenv("DIQT_CONV_DBG"); return e && e[0] == '1'; }();
-    static unsigned long long* dbuf = nullptr;
-    gg.dbg = nullptr;
-    if (dbg_on) {
-        const size_t n = (size_t)g.nCoB * g.nCiB * ksplit * 4;
-        if (!dbuf) (void)hipMalloc(&dbuf, (size_t)65536 * 8 * sizeof(unsigned long long));
-        if (n <= 65536) { gg.dbg = dbuf; wgrad3_dbg_ptr = dbuf; wgrad3_dbg_n = (unsigned)n; }
-    }
-    hipLaunchKernelGGL(kern, dim3(g.nCoB * g.nCiB, ksplit), dim3(256), lds, s, x, dy, slabs, bias_part, gg);
+    hipLaunchKernelGGL(kern, dim3(g.nCoB * g.nCiB, ksplit), dim3(256), lds, s, x, dy, slabs, bias_part, g);
     return check_launch("conv3d_bwd_weight(v3)");
 }
 

@@ -20,7 +20,6 @@
 //     reduce (conv_reduce_dw3_kernel) finishes the gradient -- deterministic.
 #include "common.h"
 #include "conv_wgrad_h.h"
-#include <stdlib.h>
 
 namespace diqt {
 namespace {
@@ -310,9 +309,8 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_h_kernel(const float* __res
 
 bool wgradh_plan(WHGeom& g, int& ksplit, int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw,
                  int epd, int eph, int epw, bool xHalf, bool dyHalf) {
-    static const bool off = [] { const char* e = getenv("DIQT_NO_WGRADH"); return e && e[0] == '1'; }();
     const bool filt = (kd == 3 && kh == 3 && kw == 3) || (kd == 1 && kh == 3 && kw == 3) || (kd == 3 && kh == 1 && kw == 1);
-    if (off || !filt || Cin % 32 != 0 || Cout % 4 != 0 || Cin < 32 || Cout < 32) return false;
+    if (!filt || Cin % 32 != 0 || Cout % 4 != 0 || Cin < 32 || Cout < 32) return false;
     if (B <= 0 || D <= 0 || H <= 0 || W <= 0 || pd < 0 || ph < 0 || pw < 0 || pd > 16 || ph > 16 || pw > 16) return false;
     if (D > 255 || H > 255 || W > 255) return false;                   // packed 10-bit coordinate fields in the kernel
     g.B = B; g.D = D; g.H = H; g.W = W; g.Cin = Cin; g.Cout = Cout; g.pd = pd; g.ph = ph; g.pw = pw;

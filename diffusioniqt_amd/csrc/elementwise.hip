@@ -4,7 +4,6 @@
 // All activations are fp32 channels-last rows x[row][C]; every streaming access is 16 B per lane when
 // C % 4 == 0 and the pointers are 16-byte aligned (the scalar variants cover the rest).
 #include "common.h"
-#include <stdlib.h>
 
 namespace diqt {
 
@@ -119,9 +118,8 @@ __global__ __launch_bounds__(256) void colreduce_kernel(F f, float* __restrict__
 }
 
 static inline int red_nblk(int rows) {
-    static const int cap = [] { const char* e = getenv("DIQT_RED_NBLK"); const int v = e ? atoi(e) : RED_NBLK; return v < 1 || v > RED_NBLK ? RED_NBLK : v; }();
     int n = rows / 64;
-    if (n > cap) n = cap;
+    if (n > RED_NBLK) n = RED_NBLK;
     if (n < 1) n = 1;
     return n;
 }
@@ -1934,8 +1932,7 @@ extern "C" size_t diqt_reduce_workspace_bytes(int B, int C) {
 
 // pooled[b][c] = sum_n softmax_n(x[b][n][:] . w)[n] x[b][n][c]; C in {64, 128, 256}; workspace: diqt_reduce_workspace_bytes(B, C)
 extern "C" int diqt_softmax_pool_supported(int B, int rows, int C) {
-    static const bool off = [] { const char* e = getenv("DIQT_NO_GCPOOL"); return e && e[0] == '1'; }();
-    return !off && B > 0 && rows > 0 && (C == 64 || C == 128 || C == 256) ? 1 : 0;
+    return B > 0 && rows > 0 && (C == 64 || C == 128 || C == 256) ? 1 : 0;
 }
 extern "C" int diqt_softmax_pool(const float* x, const float* w, float* pooled, void* workspace, size_t workspace_bytes, int B, int rows,
                                  int C, void* stream) {

@@ -11,8 +11,6 @@ share K/V, so QK^T is ONE GEMM with M = tokens x heads).
 import math
 from functools import partial
 
-import os
-
 import torch
 from torch import nn
 
@@ -234,9 +232,6 @@ class DynamicPositionBias(nn.Module):
         return pos
 
 
-_UNFUSED_ATTN = os.environ.get("DIQT_UNFUSED_ATTN") == "1"     # A/B switch: training attention through GEMM -> soft-max -> GEMM
-
-
 class Attention(nn.Module):
     """Multi-query attention with a learned null key/value, optional conditioning tokens as extra keys, optional
     relative position bias + causal mask (imagen_video.py:410-525).  x: [G, n, dim]."""
@@ -339,7 +334,7 @@ class Attention(nn.Module):
                                            rel.contiguous() if exists(rel) else None,
                                            null_bias.contiguous() if exists(null_bias) else None, n, h, d, E, n, self.causal, self.scale)
             return self._out(out, residual)
-        if not _UNFUSED_ATTN and ops.mqa_attention_fused_ok(G, n, h, d, n, exists(rel)):
+        if ops.mqa_attention_fused_ok(G, n, h, d, n, exists(rel)):
             # training path: the same fused kernel family with autograd (flash-style backward, no materialised scores)
             out = ops.mqa_attention(q, kv_ext.reshape(G, M, 2 * d), rel, null_bias, n, h, d, E, n, self.causal, self.scale)
             return self._out(out, residual)

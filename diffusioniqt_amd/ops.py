@@ -966,7 +966,6 @@ def _lp_backward(lp):
 
 _NO_TRAIN_FUSE = os.environ.get("DIQT_NO_TRAIN_FUSE") == "1"      # A/B switch: bf16 training Blocks as two autograd nodes
 _NO_TRAIN_HALF = os.environ.get("DIQT_NO_TRAIN_HALF") == "1"      # A/B switch: fp32 tensor (and gradient) between block1 and block2
-_NO_DACT_HALF = os.environ.get("DIQT_NO_DACT_HALF") == "1"      # A/B: the backward-data output in front of a GroupNorm backward stays fp32
 
 
 class _GnActConvHFn(Function):
@@ -1031,7 +1030,7 @@ class _GnActConvHFn(Function):
         # ---- conv: dX on the 16-bit MFMA kernel (flipped weights; conv_f9h_kernel when dY is 16-bit), dW / db with the 16-bit activation ----
         # the gradient w.r.t. the activated tensor only feeds the GroupNorm backward's two passes: in the operand type when the 16-bit
         # kernel writes it (what autocast's conv backward returns anyway) -- half the bytes written here and read twice there
-        dact_half = bool(y_half and not _NO_TRAIN_HALF and not _NO_DACT_HALF and Cin % 8 == 0
+        dact_half = bool(y_half and not _NO_TRAIN_HALF and Cin % 8 == 0
                          and _lib.query("diqt_conv3d_fwd_h_io16_supported", B, D, H, W, Cout, Cin, kd, kh, kw, *bpad, 0, 0, 0, 1, 1))
         dact = _conv_fwd_half(dy, weight, None, None, bpad, (0, 0, 0), ctx.lp, mode=1, x_half=y_half, y_half=dact_half)
         if dact is None:

@@ -1,4 +1,4 @@
-"""Pointwise conv / Linear forward timing.  python tools/pwf_bench.py rows Cin Cout   (DIQT_NO_PW64=1: the per-block kernel)"""
+"""Pointwise conv / Linear forward timing.  python tools/pwf_bench.py rows Cin Cout"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

@@ -1,5 +1,5 @@
 """Unet3D (bench configuration) forward + backward under bf16 autocast: ms per micro-step and the kernels' shares.
-   python tools/u3_bf16_train.py            (DIQT_NO_WGRADH=1 for the fp32 weight-gradient kernels)"""
+   python tools/u3_bf16_train.py"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
