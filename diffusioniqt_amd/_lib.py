@@ -166,6 +166,8 @@ PROTOTYPES = {
     "diqt_psnr": (I, [P, P, Z, P, F, P, P, P]),
     "diqt_ssim3d_workspace_bytes": (Z, [I, I, I, I, I]),
     "diqt_ssim3d": (I, [P, P, I, I, I, I, P, I, P, F, F, F, P, Z, P, P]),
+    "diqt_msssim3d_workspace_bytes": (Z, [I, I, I, I, I, I]),
+    "diqt_msssim3d": (I, [P, P, I, I, I, I, P, I, P, I, F, F, P, Z, P, P]),
     "diqt_abs_quantile": (I, [P, P, I, Z, ctypes.c_uint, F, P]),
     "diqt_dynamic_threshold": (I, [P, P, P, I, Z, P]),
     "diqt_mask_blend": (I, [P, P, P, P, Z, P]),

@@ -3,7 +3,9 @@
 //     z-score / min-max normalisation; the crop origins and the non-zero rejection are decided by the host from a
 //     summed-area table, diffusioniqt_amd/data.py),
 //   * PSNR / SSIM of valid_step (metrics.py:19-31 -> torchmetrics 0.9.0 peak_signal_noise_ratio and
-//     StructuralSimilarityIndexMeasure on min-max normalised 5-D tensors).
+//     StructuralSimilarityIndexMeasure on min-max normalised 5-D tensors),
+//   * MS-SSIM of the evaluation script (metrics.py:32-34 MSSIM, called per volume at test_all.py:56-62 -> torchmetrics 0.9.0
+//     MultiScaleStructuralSimilarityIndexMeasure): the SSIM tile kernel once per scale, which also pools the next scale.
 // All reductions are two-stage with a fixed order (bit-reproducible).
 #include "common.h"
 
@@ -131,11 +133,17 @@ constexpr int ST = 8;           // outputs per tile edge
 constexpr int SK = 11;          // largest filter
 constexpr int SI = ST + SK - 1; // input tile edge (18)
 struct SsimTaps { float w[SK]; int K; };
+// MS-SSIM only (torchmetrics 0.9.0 _multiscale_ssim_compute, one launch per scale): c1 / c2 come from range[0] on the device, the
+// contrast-sensitivity sums go to part[gridDim.x + block], and when pool_p is set the tile also writes the 2x2x2 average pool of the
+// raw voxels it OWNS (its 8^3 output corner; the last tile of an axis owns the rest, at most I voxels, all inside the tile it
+// loaded) with their {p min, p max, t min, t max} to mm[4 * block] -- the next scale's input and data range.
+struct MsScale { const float* range; float k1, k2; float* pool_p; float* pool_t; float* mm; };
 
+template <bool MS>
 __global__ __launch_bounds__(256) void ssim_tile_kernel(const float* __restrict__ p, const float* __restrict__ t,
                                                         const float* __restrict__ stats, double* __restrict__ part, int D, int H,
                                                         int W, int tilesD, int tilesH, int tilesW, SsimTaps taps, float c1,
-                                                        float c2) {
+                                                        float c2, MsScale ms) {
     extern __shared__ float lds[];
     const int K = taps.K, I = ST + K - 1;
     float* raw = lds;                                  // [2][I][I][I]
@@ -153,6 +161,11 @@ __global__ __launch_bounds__(256) void ssim_tile_kernel(const float* __restrict_
     float pl = 0.f, pr = 1.f, tl = 0.f, tr = 1.f;
     if (stats) { pl = stats[0]; pr = stats[1] - stats[0]; tl = stats[2]; tr = stats[3] - stats[2]; }
     const int d0 = td * ST, h0 = th * ST, w0 = tw * ST;
+    if constexpr (MS) {
+        const float r = ms.range[0];
+        c1 = (ms.k1 * r) * (ms.k1 * r);
+        c2 = (ms.k2 * r) * (ms.k2 * r);
+    }
     for (int e = threadIdx.x; e < I * I * I; e += 256) {
         const int k = e % I, j = (e / I) % I, i = e / (I * I);
         const int di = min(d0 + i, D - 1), hj = min(h0 + j, H - 1), wk = min(w0 + k, W - 1);   // clamped reads feed masked outputs only
@@ -183,7 +196,7 @@ __global__ __launch_bounds__(256) void ssim_tile_kernel(const float* __restrict_
         f2[f * SI * ST * ST + (i * ST + j) * ST + k] = s;
     }
     __syncthreads();
-    double acc = 0.0;
+    double acc = 0.0, acc_cs = 0.0;
     for (int e = threadIdx.x; e < ST * ST * ST; e += 256) {        // along D + the SSIM map
         const int k = e % ST, j = (e / ST) % ST, i = e / (ST * ST);
         if (d0 + i >= Do || h0 + j >= Ho || w0 + k >= Wo) continue;
@@ -199,18 +212,114 @@ __global__ __launch_bounds__(256) void ssim_tile_kernel(const float* __restrict_
         const float sp = m[2] - mp2, stt = m[3] - mt2, spt = m[4] - mpt;
         const float upper = 2.f * spt + c2, lower = sp + stt + c2;
         acc += (double)(((2.f * mpt + c1) * upper) / ((mp2 + mt2 + c1) * lower));
+        if constexpr (MS) acc_cs += (double)(upper / lower);
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
     __syncthreads();
     if (threadIdx.x == 0) part[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+    if constexpr (MS) {
+        __shared__ MinMax shm[4];
+        __syncthreads();
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) acc_cs += __shfl_xor(acc_cs, o, 64);
+        if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc_cs;
+        __syncthreads();
+        if (threadIdx.x == 0) part[gridDim.x + blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+        if (!ms.pool_p) return;
+        const int D2 = D / 2, H2 = H / 2, W2 = W / 2;               // avg_pool3d(2): a trailing odd plane / row / column is dropped
+        const int a0 = d0 / 2, b0 = h0 / 2, c0 = w0 / 2;
+        const int na = (td == tilesD - 1 ? D2 : a0 + ST / 2) - a0, nb = (th == tilesH - 1 ? H2 : b0 + ST / 2) - b0,
+                  nc = (tw == tilesW - 1 ? W2 : c0 + ST / 2) - c0;
+        float plo = INFINITY, phi = -INFINITY, tlo = INFINITY, thi = -INFINITY;
+        for (int e = threadIdx.x; e < na * nb * nc; e += 256) {
+            const int c = e % nc, bb = (e / nc) % nb, a = e / (nc * nb);
+            const float* rp = raw + (2 * a * SI + 2 * bb) * SI + 2 * c;
+            const float* rt = rp + SI * SI * SI;
+            const float vp = (((rp[0] + rp[1]) + (rp[SI] + rp[SI + 1])) +
+                              ((rp[SI * SI] + rp[SI * SI + 1]) + (rp[SI * SI + SI] + rp[SI * SI + SI + 1]))) * 0.125f;
+            const float vt = (((rt[0] + rt[1]) + (rt[SI] + rt[SI + 1])) +
+                              ((rt[SI * SI] + rt[SI * SI + 1]) + (rt[SI * SI + SI] + rt[SI * SI + SI + 1]))) * 0.125f;
+            const size_t off = (((size_t)vol * D2 + (a0 + a)) * H2 + (b0 + bb)) * W2 + (c0 + c);
+            ms.pool_p[off] = vp;
+            ms.pool_t[off] = vt;
+            plo = fminf(plo, vp); phi = fmaxf(phi, vp);
+            tlo = fminf(tlo, vt); thi = fmaxf(thi, vt);
+        }
+        const MinMax mp = wg_minmax(plo, phi, shm), mt = wg_minmax(tlo, thi, shm);
+        if (threadIdx.x == 0) {
+            float* o = ms.mm + 4 * (size_t)blockIdx.x;
+            o[0] = mp.lo; o[1] = mp.hi; o[2] = mt.lo; o[3] = mt.hi;
+        }
+    }
 }
 __global__ __launch_bounds__(64) void mean_stage2_kernel(const double* __restrict__ part, int nb, double count, float* __restrict__ out) {
     if (threadIdx.x) return;
     double s = 0.0;
     for (int i = 0; i < nb; ++i) s += part[i];
     out[0] = (float)(s / count);
+}
+
+// ---- MS-SSIM: the small kernels between the per-scale tile launches ---------------------------------------------------------
+constexpr int MS_MAX_SCALES = 16;      // every axis halves per scale: more scales than this need a volume no device holds
+struct MsBetas { float b[MS_MAX_SCALES]; };
+
+// range_0 = max(p.max - p.min, t.max - t.min) from the two minmax_stage1_kernel partial sets (nb each)
+__global__ __launch_bounds__(64) void msssim_range0_kernel(const MinMax* __restrict__ part, int nb, float* __restrict__ range) {
+    float r[2];
+    for (int v = 0; v < 2; ++v) {
+        float lo = INFINITY, hi = -INFINITY;
+        for (int i = threadIdx.x; i < nb; i += 64) { lo = fminf(lo, part[v * nb + i].lo); hi = fmaxf(hi, part[v * nb + i].hi); }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            lo = fminf(lo, __shfl_xor(lo, o, 64));
+            hi = fmaxf(hi, __shfl_xor(hi, o, 64));
+        }
+        r[v] = hi - lo;
+    }
+    if (threadIdx.x == 0) range[0] = fmaxf(r[0], r[1]);
+}
+// One workgroup per scale, fixed summation order: thread i adds partials i, i + 256, ...; then the xor tree; then the four waves.
+// out[1 + 3 s ..] = {ssim_s, cs_s, range_s}; range[s + 1] for the next tile launch; the last scale forms
+// out[0] = prod_j term_j ^ beta_j (term = cs below the last scale, ssim at it; no clamp: a negative term gives NaN, as torch.pow).
+__global__ __launch_bounds__(256) void msssim_final_kernel(const double* __restrict__ part, const float* __restrict__ mm, int nb,
+                                                           double count, float* __restrict__ range, float* __restrict__ out, int s,
+                                                           int scales, MsBetas betas) {
+    __shared__ double sh[2][4];
+    __shared__ MinMax shm[4];
+    const bool last = s + 1 == scales;
+    double a = 0.0, c = 0.0;
+    float plo = INFINITY, phi = -INFINITY, tlo = INFINITY, thi = -INFINITY;
+    for (int i = threadIdx.x; i < nb; i += 256) {
+        a += part[i];
+        c += part[nb + i];
+        if (!last) {
+            const float* m = mm + 4 * (size_t)i;
+            plo = fminf(plo, m[0]); phi = fmaxf(phi, m[1]);
+            tlo = fminf(tlo, m[2]); thi = fmaxf(thi, m[3]);
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        a += __shfl_xor(a, o, 64);
+        c += __shfl_xor(c, o, 64);
+    }
+    if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = a; sh[1][threadIdx.x >> 6] = c; }
+    const MinMax mp = wg_minmax(plo, phi, shm), mt = wg_minmax(tlo, thi, shm);      // (its barriers publish sh too)
+    if (threadIdx.x) return;
+    const float ssim = (float)(((sh[0][0] + sh[0][1]) + (sh[0][2] + sh[0][3])) / count);
+    const float cs = (float)(((sh[1][0] + sh[1][1]) + (sh[1][2] + sh[1][3])) / count);
+    out[1 + 3 * s] = ssim;
+    out[2 + 3 * s] = cs;
+    out[3 + 3 * s] = range[s];
+    if (!last) {
+        range[s + 1] = fmaxf(mp.hi - mp.lo, mt.hi - mt.lo);
+        return;
+    }
+    float prod = 1.f;
+    for (int j = 0; j < scales; ++j) prod *= powf(j == s ? ssim : out[2 + 3 * j], betas.b[j]);
+    out[0] = prod;
 }
 }  // namespace diqt
 
@@ -297,15 +406,107 @@ extern "C" int diqt_ssim3d(const float* pred, const float* target, int N, int D,
     const size_t lds = (size_t)(2 * SI * SI * SI + 5 * SI * SI * ST + 5 * SI * ST * ST) * sizeof(float);
     static bool attr_set = false;
     if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ssim_tile_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ssim_tile_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         DIQT_REQUIRE(e == hipSuccess, DIQT_E_LAUNCH, "ssim3d: LDS attribute: %s", hipGetErrorString(e));
         attr_set = true;
     }
-    hipLaunchKernelGGL(ssim_tile_kernel, dim3((unsigned)blocks), dim3(256), lds, STREAM, pred, target, stats4,
-                       static_cast<double*>(workspace), D, H, W, tD, tH, tW, tp, c1, c2);
+    hipLaunchKernelGGL(ssim_tile_kernel<false>, dim3((unsigned)blocks), dim3(256), lds, STREAM, pred, target, stats4,
+                       static_cast<double*>(workspace), D, H, W, tD, tH, tW, tp, c1, c2, MsScale{});
     int rc = check_launch("ssim3d/tiles");
     if (rc) return rc;
     const double count = (double)N * (D - K + 1) * (H - K + 1) * (W - K + 1);
     hipLaunchKernelGGL(mean_stage2_kernel, dim3(1), dim3(64), 0, STREAM, static_cast<const double*>(workspace), (int)blocks, count, out);
     return check_launch("ssim3d/mean");
+}
+
+// Workspace of diqt_msssim3d: {range[scales + 1] | range_0 min/max partials | part[2 * blocks_0] doubles | mm[4 * blocks_0] |
+// pooled p, t of the odd scales | pooled p, t of the even scales} -- scale s + 1 is written while scale s is read, so two
+// buffers alternate.
+namespace {
+struct MsLayout {
+    size_t mm0, part, mm, pool[2], pool_elems[2], total, blocks0;
+    bool ok;
+};
+constexpr unsigned MS_MM0_BLOCKS = 1024;
+size_t ms_align(size_t n) { return (n + 255) & ~(size_t)255; }
+MsLayout ms_layout(int N, int D, int H, int W, int K, int scales) {
+    MsLayout L{};
+    if (N <= 0 || K < 1 || K > SK || !(K & 1) || scales < 1 || scales > MS_MAX_SCALES || D <= 0 || H <= 0 || W <= 0) return L;
+    if ((D >> (scales - 1)) < K || (H >> (scales - 1)) < K || (W >> (scales - 1)) < K) return L;
+    int a, b, c;
+    ssim_tiles(N, D, H, W, K, a, b, c, L.blocks0);
+    if (L.blocks0 > 0x7fffffffu) return L;
+    L.pool_elems[0] = scales > 1 ? (size_t)N * (D >> 1) * (H >> 1) * (W >> 1) : 0;      // scale 1 (largest of the odd scales)
+    L.pool_elems[1] = scales > 2 ? (size_t)N * (D >> 2) * (H >> 2) * (W >> 2) : 0;      // scale 2
+    L.mm0 = ms_align((MS_MAX_SCALES + 1) * sizeof(float));
+    L.part = L.mm0 + ms_align(2 * MS_MM0_BLOCKS * sizeof(MinMax));
+    L.mm = L.part + ms_align(2 * L.blocks0 * sizeof(double));
+    L.pool[0] = L.mm + ms_align(4 * L.blocks0 * sizeof(float));
+    L.pool[1] = L.pool[0] + ms_align(2 * L.pool_elems[0] * sizeof(float));
+    L.total = L.pool[1] + ms_align(2 * L.pool_elems[1] * sizeof(float));
+    L.ok = true;
+    return L;
+}
+}  // namespace
+extern "C" size_t diqt_msssim3d_workspace_bytes(int N, int D, int H, int W, int K, int scales) {
+    const MsLayout L = ms_layout(N, D, H, W, K, scales);
+    return L.ok ? L.total : 0;
+}
+extern "C" int diqt_msssim3d(const float* pred, const float* target, int N, int D, int H, int W, const float* taps, int K,
+                             const float* betas, int scales, float k1, float k2, void* workspace, size_t workspace_bytes, float* out,
+                             void* stream) {
+    DIQT_REQUIRE(pred && target && taps && betas && out, DIQT_E_ALIGN, "msssim3d: null pointer");
+    DIQT_REQUIRE(K >= 1 && K <= SK && (K & 1), DIQT_E_UNSUPPORTED, "msssim3d: filter size %d (odd, <= %d)", K, SK);
+    DIQT_REQUIRE(scales >= 1 && scales <= MS_MAX_SCALES, DIQT_E_UNSUPPORTED, "msssim3d: %d scales (1 .. %d)", scales, MS_MAX_SCALES);
+    const MsLayout L = ms_layout(N, D, H, W, K, scales);
+    DIQT_REQUIRE(L.ok, DIQT_E_SHAPE, "msssim3d: %dx%dx%d leaves fewer than %d voxels on an axis at scale %d", D, H, W, K, scales - 1);
+    DIQT_REQUIRE(workspace && workspace_bytes >= L.total, DIQT_E_SHAPE, "msssim3d: workspace too small");
+    SsimTaps tp;
+    for (int i = 0; i < SK; ++i) tp.w[i] = i < K ? taps[i] : 0.f;      // taps, betas: HOST pointers
+    tp.K = K;
+    MsBetas bt;
+    for (int i = 0; i < MS_MAX_SCALES; ++i) bt.b[i] = i < scales ? betas[i] : 0.f;
+    const size_t lds = (size_t)(2 * SI * SI * SI + 5 * SI * SI * ST + 5 * SI * ST * ST) * sizeof(float);
+    static bool attr_set = false;
+    if (!attr_set) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ssim_tile_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        DIQT_REQUIRE(e == hipSuccess, DIQT_E_LAUNCH, "msssim3d: LDS attribute: %s", hipGetErrorString(e));
+        attr_set = true;
+    }
+    char* ws = static_cast<char*>(workspace);
+    float* range = reinterpret_cast<float*>(ws);
+    MinMax* mm0 = reinterpret_cast<MinMax*>(ws + L.mm0);
+    double* part = reinterpret_cast<double*>(ws + L.part);
+    float* mm = reinterpret_cast<float*>(ws + L.mm);
+    // range_0: the two-stage min / max of diqt_minmax on each input, then one number
+    const size_t n0 = (size_t)N * D * H * W;
+    const unsigned nb0 = grid_for(n0, 256, MS_MM0_BLOCKS);
+    hipLaunchKernelGGL(minmax_stage1_kernel, dim3(nb0), dim3(256), 0, STREAM, pred, mm0, n0);
+    hipLaunchKernelGGL(minmax_stage1_kernel, dim3(nb0), dim3(256), 0, STREAM, target, mm0 + nb0, n0);
+    hipLaunchKernelGGL(msssim_range0_kernel, dim3(1), dim3(64), 0, STREAM, mm0, (int)nb0, range);
+    int rc = check_launch("msssim3d/range0");
+    if (rc) return rc;
+    const float *p = pred, *t = target;
+    for (int s = 0; s < scales; ++s) {
+        int tD, tH, tW;
+        size_t blocks;
+        ssim_tiles(N, D, H, W, K, tD, tH, tW, blocks);
+        MsScale ms{range + s, k1, k2, nullptr, nullptr, mm};
+        if (s + 1 < scales) {
+            const int b = s & 1;                                       // scale s + 1 lives in pool[s & 1]
+            ms.pool_p = reinterpret_cast<float*>(ws + L.pool[b]);
+            ms.pool_t = ms.pool_p + (size_t)N * (D / 2) * (H / 2) * (W / 2);
+        }
+        hipLaunchKernelGGL(ssim_tile_kernel<true>, dim3((unsigned)blocks), dim3(256), lds, STREAM, p, t, (const float*)nullptr, part, D, H,
+                           W, tD, tH, tW, tp, 0.f, 0.f, ms);
+        rc = check_launch("msssim3d/tiles");
+        if (rc) return rc;
+        const double count = (double)N * (D - K + 1) * (H - K + 1) * (W - K + 1);
+        hipLaunchKernelGGL(msssim_final_kernel, dim3(1), dim3(256), 0, STREAM, part, mm, (int)blocks, count, range, out, s, scales, bt);
+        rc = check_launch("msssim3d/final");
+        if (rc) return rc;
+        p = ms.pool_p; t = ms.pool_t;
+        D /= 2; H /= 2; W /= 2;
+    }
+    return DIQT_OK;
 }

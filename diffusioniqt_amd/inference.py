@@ -14,12 +14,15 @@ Semantics kept from the scripts:
 * without ``batch_sample`` and with ``overlap >= patch`` patches are placed whole (test_all.py:262-263).  The script's
   overlap < patch branch of that mode raises on its first interior patch (a 3-element tensor in a boolean ``or``,
   test_all.py:241) — here it applies the same per-face crop rule as the block mode instead;
-* voxels whose normalised low-res value equals the volume minimum are reset to it (test_all.py:300).
+* voxels whose normalised low-res value equals the volume minimum are reset to it (test_all.py:300);
+* ``evaluate_volume`` scores the stitched volume as the script's ``eval`` does (test_all.py:47-62): centre crop, PSNR, MS-SSIM of
+  the min-max normalised pair — without LPIPS (no VGG weights here).
 """
 import numpy as np
 import torch
 
 from . import ops
+from .metrics import MSSIM, PSNR
 from .utils_mine import convertVolume2subVolume, merge_sub_volumes
 
 
@@ -105,3 +108,39 @@ class VolumeInference:
         min_val = (np.float32(min_raw) - mean32) / std32                                  # monotone map: min of the normalised volume
         ops.background_reset(pred, vol, self.mean, self.std, float(min_val))             # test_all.py:300
         return pred
+
+
+def eval_crop(size0):
+    """test_all.py:49-54: voxels cut from every face of all three axes, decided by the size of axis 0 alone."""
+    return 24 if size0 == 240 else (32 if size0 == 256 else 0)
+
+
+def _minmax_normalised(x):
+    mm = ops.minmax(x)
+    return (x - mm[0]) / (mm[1] - mm[0])
+
+
+@torch.no_grad()
+def evaluate_volume(gt, pred):
+    """``eval(gt, pred)`` of the evaluation script (test_all.py:47-62) without LPIPS, on the device.  gt / pred: ``[D,H,W]`` numpy
+    arrays or tensors — what ``VolumeInference.__call__`` returns is taken as it is, in HBM.  Both are centre-cropped (24 per face
+    for a 240-voxel axis 0, 32 for 256, otherwise not at all); ``psnr = PSNR(gt, pred)`` on the cropped raw volumes; each cropped
+    volume is min-max normalised by its own extrema; ``ssim = MSSIM(gt_n, pred_n)``.  Returns ``(ssim, psnr)`` in the script's
+    order, 0-d tensors on the device ``gt`` came from (the CPU for numpy arrays)."""
+    gt, pred = torch.as_tensor(gt), torch.as_tensor(pred)
+    if gt.ndim != 3 or gt.shape != pred.shape:
+        raise ValueError(f"evaluate_volume: expected two [D,H,W] volumes of one shape, got {tuple(gt.shape)} and {tuple(pred.shape)}")
+    home = gt.device
+    c = eval_crop(gt.shape[0])
+    if c:
+        gt, pred = gt[c:-c, c:-c, c:-c], pred[c:-c, c:-c, c:-c]
+    if any(s // 16 <= 10 for s in gt.shape):                         # MSSIM's size rule, before anything is copied or launched
+        raise ValueError(f"evaluate_volume: the cropped volume {tuple(gt.shape)} is too small for the 5-scale MS-SSIM")
+    if not torch.cuda.is_available():
+        raise RuntimeError("diffusioniqt_amd.inference.evaluate_volume runs on the MI355X only (no CPU fallback)")
+    dev = gt.device if gt.is_cuda else torch.device('cuda')
+    g = gt.to(dev).float().contiguous()[None, None]
+    p = pred.to(dev).float().contiguous()[None, None]
+    psnr = PSNR(g, p)
+    ssim = MSSIM(_minmax_normalised(g), _minmax_normalised(p))
+    return ssim.to(home), psnr.to(home)

@@ -2348,3 +2348,25 @@ def ssim3d(pred, target, taps, stats=None, data_range=1.0, k1=0.01, k2=0.03):
     _lib.call("diqt_ssim3d", pred, target, N, D, H, W, taps.ctypes.data_as(ctypes.c_void_p), K, stats, float(data_range), float(k1),
               float(k2), _workspace(nws, pred.device), nws, out, _stream())
     return out
+
+
+def msssim3d(pred, target, taps, betas, k1=0.01, k2=0.03):
+    """pred/target: contiguous [N, D, H, W]; taps: host float32 numpy array (odd length <= 11); betas: one exponent per scale.
+    Device [1 + 3 * scales] tensor {MS-SSIM, then per scale ssim_s, cs_s, range_s}; nothing is synchronised or copied back."""
+    import ctypes
+    import numpy as np
+    _chk(pred, target)
+    if pred.shape != target.shape:
+        raise RuntimeError(f"msssim3d: shapes differ: {tuple(pred.shape)} vs {tuple(target.shape)}")
+    N, D, H, W = pred.shape
+    taps = np.ascontiguousarray(taps, dtype=np.float32)
+    betas = np.ascontiguousarray(betas, dtype=np.float32)
+    K, scales = int(taps.shape[0]), int(betas.shape[0])
+    nws = _lib.query("diqt_msssim3d_workspace_bytes", N, D, H, W, K, scales)
+    if nws == 0:
+        raise RuntimeError(f"msssim3d: volume {D}x{H}x{W} leaves fewer than {K} voxels on an axis after {scales - 1} poolings "
+                           f"(or scales = {scales} outside 1..16)")
+    out = torch.empty(1 + 3 * scales, device=pred.device, dtype=torch.float32)
+    _lib.call("diqt_msssim3d", pred, target, N, D, H, W, taps.ctypes.data_as(ctypes.c_void_p), K,
+              betas.ctypes.data_as(ctypes.c_void_p), scales, float(k1), float(k2), _workspace(nws, pred.device), nws, out, _stream())
+    return out

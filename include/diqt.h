@@ -601,6 +601,16 @@ int diqt_psnr(const float* pred, const float* target, size_t n, const float* sta
 size_t diqt_ssim3d_workspace_bytes(int N, int D, int H, int W, int K);
 int diqt_ssim3d(const float* pred, const float* target, int N, int D, int H, int W, const float* taps, int K, const float* stats4,
                 float data_range, float k1, float k2, void* workspace, size_t workspace_bytes, float* out, void* stream);
+/* metrics.py:32-34 MSSIM, called on every reconstructed volume by test_all.py:56-62 -> torchmetrics 0.9.0
+ * MultiScaleStructuralSimilarityIndexMeasure (normalize=None, data_range=None) on N volumes [D][H][W]: per scale the SSIM and the
+ * contrast-sensitivity means of diqt_ssim3d's windows with the data range max(p.max - p.min, t.max - t.min) of THAT scale, then a
+ * 2x2x2 average pool; out[0] = prod_s term_s ^ betas[s] (term = cs below the last scale, ssim at it; a negative term gives NaN),
+ * followed by {ssim_s, cs_s, range_s} per scale (1 + 3 scales floats).  One tile launch per scale produces the sums, the pooled
+ * pair and its min / max; a one-workgroup finaliser reduces them in a fixed order.  No host synchronisation.  taps, betas: HOST
+ * pointers; 1 <= scales <= 16.  The workspace query returns 0 when an axis has fewer than K voxels at the last scale. */
+size_t diqt_msssim3d_workspace_bytes(int N, int D, int H, int W, int K, int scales);
+int diqt_msssim3d(const float* pred, const float* target, int N, int D, int H, int W, const float* taps, int K, const float* betas,
+                  int scales, float k1, float k2, void* workspace, size_t workspace_bytes, float* out, void* stream);
 
 /* Gradient accumulation (accelerate's accumulate()/DDP no_sync, trainer.py:300,1118): the per-parameter gradients of one
  * micro-step are added into the flat gradient arena in ONE launch.  table[t] = {src device pointer, dst element offset,
