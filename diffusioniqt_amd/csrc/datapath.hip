@@ -5,7 +5,9 @@
 //   * PSNR / SSIM of valid_step (metrics.py:19-31 -> torchmetrics 0.9.0 peak_signal_noise_ratio and
 //     StructuralSimilarityIndexMeasure on min-max normalised 5-D tensors),
 //   * MS-SSIM of the evaluation script (metrics.py:32-34 MSSIM, called per volume at test_all.py:56-62 -> torchmetrics 0.9.0
-//     MultiScaleStructuralSimilarityIndexMeasure): the SSIM tile kernel once per scale, which also pools the next scale.
+//     MultiScaleStructuralSimilarityIndexMeasure): the SSIM tile kernel once per scale, which also pools the next scale,
+//   * weighted overlap blending of the sliding windows of a whole volume with the per-voxel spread of several samples
+//     (diffusioniqt_amd/inference.py, blend modes; in place of the crop-and-overwrite stitching of test_all.py:235-300).
 // All reductions are two-stage with a fixed order (bit-reproducible).
 #include "common.h"
 
@@ -321,6 +323,93 @@ __global__ __launch_bounds__(256) void msssim_final_kernel(const double* __restr
     for (int j = 0; j < scales; ++j) prod *= powf(j == s ? ssim : out[2 + 3 * j], betas.b[j]);
     out[0] = prod;
 }
+
+// ---- whole-volume inference: weighted overlap blending of the kept windows, with a per-voxel spread over S samples ----------
+// Gather-side: one thread per OUTPUT voxel walks the windows that cover it in candidate order (g0, g1, g2 ascending on the origin
+// lattice g * stride), so nothing is written twice, there is no atomic, and the sum order is a function of the voxel alone.
+// patches[S][N][P][P][P]; slot[G0][G1][G2] = row of the window in `patches`, < 0 for a window that was not kept.  Per sample:
+// b_s = sum(w y) / sum(w), w = (taps[i] taps[j]) taps[k] (the product accumulated with one fma per term); out_mean / out_std =
+// Welford mean / unbiased deviation of b_s in sample order.  A voxel no kept window covers gets `fill`; a voxel whose normalised
+// low-res value equals min_val gets min_val (background_reset_kernel's rule and expression), both with deviation 0.
+// Block (64, 4): a wave owns 64 voxels of one row, so d, h and with them the g0 / g1 ranges, taps[i] taps[j] and the slot row are
+// wave-uniform; only the g2 range is per lane (any stride, also one that does not divide P).  Lanes of one window read consecutive
+// floats.  Every element of `patches` is read exactly once per launch.
+__global__ __launch_bounds__(256) void volume_blend_kernel(const float* __restrict__ patches, const int* __restrict__ slot,
+                                                           const float* __restrict__ taps, const float* __restrict__ vol,
+                                                           float* __restrict__ out_mean, float* __restrict__ out_std, int S, int N,
+                                                           int D, int H, int W, int P, int stride, int G0, int G1, int G2, float mean,
+                                                           float stdv, float min_val, float fill) {
+    extern __shared__ float tp[];                      // [P]
+    for (int e = threadIdx.y * 64 + threadIdx.x; e < P; e += 256) tp[e] = taps[e];
+    __syncthreads();
+    const int x = blockIdx.x * 64 + threadIdx.x;
+    const int h = __builtin_amdgcn_readfirstlane(blockIdx.y * 4 + threadIdx.y), d = blockIdx.z;
+    if (h >= H || x >= W) return;
+    const size_t v = ((size_t)d * H + h) * W + x;
+    float om, os = 0.f;
+    if (vol && (vol[v] - mean) / stdv == min_val) {
+        om = min_val;
+    } else {
+        // covering lattice indices of coordinate c: 0 <= g < G and 0 <= c - g * stride < P
+        const int lo0 = max(0, (d - P + stride) / stride), hi0 = min(G0 - 1, d / stride);
+        const int lo1 = max(0, (h - P + stride) / stride), hi1 = min(G1 - 1, h / stride);
+        const int lo2 = max(0, (x - P + stride) / stride), hi2 = min(G2 - 1, x / stride);
+        const size_t per = (size_t)P * P * P;
+        float m = 0.f, m2 = 0.f, den = 0.f;
+        for (int s = 0; s < S; ++s) {
+            const float* ps = patches + (size_t)s * N * per;
+            float num = 0.f;
+            den = 0.f;                                  // the same terms in the same order for every s
+            for (int g0 = lo0; g0 <= hi0; ++g0) {
+                const int i = d - g0 * stride;
+                const float wi = tp[i];
+                for (int g1 = lo1; g1 <= hi1; ++g1) {
+                    const int j = h - g1 * stride;
+                    const float wij = wi * tp[j];
+                    const int* srow = slot + ((size_t)g0 * G1 + g1) * G2;
+                    const float* prow = ps + ((size_t)i * P + j) * P;
+                    // four windows per trip: their slot reads, then their patch reads, are independent loads in flight together (one
+                    // window per trip is a chain of two dependent loads, and the kernel ran at the memory latency).  A window that is
+                    // not kept (-1), or lies past hi2, reads taps[0] instead and enters with weight 0: adding +0 terms changes no bit.
+                    for (int g2 = lo2; g2 <= hi2; g2 += 4) {
+                        int n[4];
+                        float w[4], y[4];
+#pragma unroll
+                        for (int u = 0; u < 4; ++u) {
+                            const int nn = srow[min(g2 + u, hi2)];
+                            n[u] = g2 + u <= hi2 ? nn : -1;
+                        }
+#pragma unroll
+                        for (int u = 0; u < 4; ++u) {
+                            const bool ok = (unsigned)n[u] < (unsigned)N;
+                            const int k = ok ? x - (g2 + u) * stride : 0;
+                            const float yy = *(ok ? prow + (size_t)n[u] * per + k : taps);
+                            w[u] = ok ? wij * tp[k] : 0.f;
+                            y[u] = ok ? yy : 0.f;
+                        }
+#pragma unroll
+                        for (int u = 0; u < 4; ++u) {
+                            num = fmaf(w[u], y[u], num);
+                            den += w[u];
+                        }
+                    }
+                }
+            }
+            if (den == 0.f) break;
+            const float b = num / den, delta = b - m;
+            m += delta / (float)(s + 1);
+            m2 = fmaf(delta, b - m, m2);
+        }
+        if (den == 0.f) {
+            om = fill;
+        } else {
+            om = m;
+            if (S > 1) os = sqrtf(m2 / (float)(S - 1));
+        }
+    }
+    out_mean[v] = om;
+    if (out_std) out_std[v] = os;
+}
 }  // namespace diqt
 
 using namespace diqt;
@@ -509,4 +598,21 @@ extern "C" int diqt_msssim3d(const float* pred, const float* target, int N, int 
         D /= 2; H /= 2; W /= 2;
     }
     return DIQT_OK;
+}
+
+extern "C" int diqt_volume_blend(const float* patches, const int* slot, const float* taps, const float* vol, float* out_mean,
+                                 float* out_std, int S, int N, int D, int H, int W, int P, int stride, int G0, int G1, int G2,
+                                 float mean, float stdv, float min_val, float fill, void* stream) {
+    DIQT_REQUIRE(slot && taps && out_mean && (patches || N == 0), DIQT_E_ALIGN, "volume_blend: null pointer");
+    DIQT_REQUIRE(D > 0 && H > 0 && W > 0 && P > 0 && P <= D && P <= H && P <= W, DIQT_E_SHAPE, "volume_blend: bad shape");
+    DIQT_REQUIRE(stride > 0 && S > 0 && N >= 0, DIQT_E_SHAPE, "volume_blend: stride %d, samples %d, windows %d", stride, S, N);
+    DIQT_REQUIRE(G0 == (D - P) / stride + 1 && G1 == (H - P) / stride + 1 && G2 == (W - P) / stride + 1, DIQT_E_SHAPE,
+                 "volume_blend: lattice %dx%dx%d does not match range(0, n - P + 1, stride) of %dx%dx%d, P %d, stride %d", G0, G1, G2, D,
+                 H, W, P, stride);
+    DIQT_REQUIRE(!(out_std && S == 1), DIQT_E_SHAPE, "volume_blend: a deviation map needs at least 2 samples");
+    DIQT_REQUIRE(!vol || stdv != 0.f, DIQT_E_SHAPE, "volume_blend: std == 0");
+    DIQT_REQUIRE(D <= 65535 && (H + 3) / 4 <= 65535, DIQT_E_SHAPE, "volume_blend: more than 65535 planes / row groups");
+    hipLaunchKernelGGL(volume_blend_kernel, dim3((W + 63) / 64, (H + 3) / 4, D), dim3(64, 4), (size_t)P * sizeof(float), STREAM, patches,
+                       slot, taps, vol, out_mean, out_std, S, N, D, H, W, P, stride, G0, G1, G2, mean, stdv, min_val, fill);
+    return check_launch("volume_blend");
 }

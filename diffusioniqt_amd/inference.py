@@ -17,6 +17,16 @@ Semantics kept from the scripts:
 * voxels whose normalised low-res value equals the volume minimum are reset to it (test_all.py:300);
 * ``evaluate_volume`` scores the stitched volume as the script's ``eval`` does (test_all.py:47-62): centre crop, PSNR, MS-SSIM of
   the min-max normalised pair — without LPIPS (no VGG weights here).
+
+Beyond the scripts (``blend`` / ``samples``; the defaults leave every line above as it is):
+* ``blend='gaussian'`` / ``'constant'`` replaces crop-and-overwrite by weighted overlap blending: whole windows contribute (no crop
+  margins), each voxel is the weighted mean of the windows that cover it, with the separable weight ``taps[i] taps[j] taps[k]``
+  (``blend_taps``: a Gaussian importance map of sigma ``sigma_scale * P`` with maximum 1, or all ones = the plain mean).  Every kept
+  window's prediction stays in HBM and ONE gather-side launch (``ops.volume_blend``) reduces them per output voxel in candidate
+  order — no atomics, bit-reproducible, independent of ``Eval.batch_size``; the background reset is fused into it.  A voxel that no
+  kept window covers keeps the fill value ``(0 - mean) / std``;
+* ``samples=S`` draws every batch S times (sample 0 of a batch, then sample 1, ...); the result is the per-voxel mean of the S
+  blended volumes and, with ``return_std=True``, their unbiased standard deviation — the uncertainty map of a stochastic sampler.
 """
 import numpy as np
 import torch
@@ -45,10 +55,36 @@ def crop_margins(origins, n, patch, overlap):
     return m
 
 
+BLEND_MODES = (None, 'gaussian', 'constant')
+
+
+def blend_taps(P, kind='gaussian', sigma_scale=0.125):
+    """The 1-D window of a blend mode, fp32 [P]: ``'gaussian'`` = exp(-(i - (P-1)/2)^2 / (2 (sigma_scale P)^2)) evaluated in float64
+    and divided by its maximum; ``'constant'`` = ones.  The 3-D weight of a window voxel is the product of its three taps."""
+    if kind == 'constant':
+        return np.ones(int(P), dtype=np.float32)
+    if kind != 'gaussian':
+        raise ValueError(f"blend_taps: kind must be 'gaussian' or 'constant', got {kind!r}")
+    i = np.arange(int(P), dtype=np.float64)
+    t = np.exp(-(i - (P - 1) / 2.0) ** 2 / (2.0 * (float(sigma_scale) * P) ** 2))
+    return (t / t.max()).astype(np.float32)
+
+
 class VolumeInference:
-    def __init__(self, configs, sample_fn, nonzero_ratio=0.05):
+    def __init__(self, configs, sample_fn, nonzero_ratio=0.05, blend=None, sigma_scale=0.125, samples=1):
         """``sample_fn(lr_patches [B,1,S,S,S]) -> hr_patches`` — e.g. ``lambda x: trainer.sample(batch_size=x.shape[0],
-        start_image_or_video=x, start_at_unet_number=2)[0]`` (test_all.py:234)."""
+        start_image_or_video=x, start_at_unet_number=2)[0]`` (test_all.py:234).  ``blend`` / ``sigma_scale`` / ``samples``: weighted
+        overlap blending and multi-sample statistics, see the module docstring."""
+        if blend not in BLEND_MODES:
+            raise ValueError(f"VolumeInference: blend must be None, 'gaussian' or 'constant', got {blend!r}")
+        if int(samples) != samples or samples < 1:
+            raise ValueError(f"VolumeInference: samples must be a positive integer, got {samples!r}")
+        if samples > 1 and blend is None:
+            raise ValueError("VolumeInference: samples > 1 needs a blend mode ('gaussian' or 'constant'): crop-and-overwrite stitching "
+                             "keeps one draw per voxel")
+        if blend == 'gaussian' and not sigma_scale > 0:
+            raise ValueError(f"VolumeInference: sigma_scale must be positive, got {sigma_scale!r}")
+        self.blend, self.sigma_scale, self.samples = blend, float(sigma_scale), int(samples)
         self.cfg = configs
         self.sample_fn = sample_fn
         self.ratio = nonzero_ratio
@@ -62,10 +98,20 @@ class VolumeInference:
         self.mean, self.std = float(configs['Data']['mean']), float(configs['Data']['std'])
 
     @torch.no_grad()
-    def __call__(self, lowres_raw, patch_slice=None):
+    def __call__(self, lowres_raw, patch_slice=None, return_std=False):
         """lowres_raw: fp32 [D,H,W] raw intensities on the GPU.  Returns the stitched, z-scored prediction [D,H,W].
         ``patch_slice`` (rank, world) restricts the work to every world-th kept patch (multi-GPU sharding; merge the shards with
-        the returned mask-free volumes by taking, per voxel, the value of the rank that owns it — see ``shard_volumes``)."""
+        the returned mask-free volumes by taking, per voxel, the value of the rank that owns it — see ``shard_volumes``).
+        ``return_std`` (blend modes, ``samples >= 2``): returns ``(mean, std)``, the per-voxel statistics over the samples."""
+        if return_std and (self.blend is None or self.samples < 2):
+            raise ValueError("VolumeInference: return_std needs a blend mode and samples >= 2")
+        if self.blend is not None:
+            if patch_slice is not None:
+                raise NotImplementedError("VolumeInference: a blend mode does not split one volume's windows over ranks (that needs a "
+                                          "cross-rank merge of the weighted sums) — shard whole volumes across the GPUs instead, one "
+                                          "VolumeInference call per volume and rank, as bench.py does")
+            mean, dev = self._blended(lowres_raw, return_std)
+            return (mean, dev) if return_std else mean
         vol = lowres_raw.float().contiguous()
         dev = vol.device
         shape = tuple(vol.shape)
@@ -108,6 +154,41 @@ class VolumeInference:
         min_val = (np.float32(min_raw) - mean32) / std32                                  # monotone map: min of the normalised volume
         ops.background_reset(pred, vol, self.mean, self.std, float(min_val))             # test_all.py:300
         return pred
+
+    def _blended(self, lowres_raw, want_std):
+        """The blend modes: every kept window's S predictions are kept in ``patches`` [S,N,P,P,P]; one ``ops.volume_blend`` launch
+        stitches them (weights, mean / deviation over the samples, fill and background reset)."""
+        vol = lowres_raw.float().contiguous()
+        dev = vol.device
+        shape = tuple(vol.shape)
+        P, S = self.patch, self.samples
+        origins = sliding_window_origins(shape, P, self.overlap)
+        lattice = tuple(len(range(0, s - P + 1, self.overlap)) for s in shape)
+        _, nz = ops.patch_gather(vol, torch.from_numpy(origins).to(dev), P, self.mean, self.std, want_patches=False, want_nonzero=True)
+        keep = (nz.cpu().numpy().astype(np.float64) / float(P ** 3)) >= self.ratio          # data.py:187-191
+        kept = origins[keep]
+        N = kept.shape[0]
+        slot = np.full(origins.shape[0], -1, dtype=np.int32)                                 # candidate order = lattice order
+        slot[keep] = np.arange(N, dtype=np.int32)
+        patches = torch.empty((S, N, P, P, P), dtype=torch.float32, device=dev)
+        per_call = 1 if self.block_mode else self.batch
+        for lo in range(0, N, per_call):
+            idx = torch.from_numpy(np.ascontiguousarray(kept[lo:lo + per_call])).to(dev)
+            n = idx.shape[0]
+            x, _ = ops.patch_gather(vol, idx, P, self.mean, self.std)
+            if self.block_mode:                                                           # test_all.py:229-231, 265-266
+                x = convertVolume2subVolume(x, target_shape=(self.factor ** 3, 1, self.sub, self.sub, self.sub))
+            for s in range(S):
+                y = self.sample_fn(x)
+                if self.block_mode:
+                    y = merge_sub_volumes(y.float(), original_shape=(1, 1, P, P, P))
+                patches[s, lo:lo + n] = y.float().reshape(n, P, P, P)
+        mean32, std32 = np.float32(self.mean), np.float32(self.std)
+        fill = (np.float32(0.) - mean32) / std32
+        min_val = (np.float32(float(ops.min_value(vol).item())) - mean32) / std32
+        taps = torch.from_numpy(blend_taps(P, self.blend, self.sigma_scale)).to(dev)
+        return ops.volume_blend(patches, torch.from_numpy(slot.reshape(lattice)).to(dev), taps, vol, self.mean, self.std,
+                                float(min_val), float(fill), self.overlap, want_std)
 
 
 def eval_crop(size0):

@@ -2304,6 +2304,31 @@ def min_value(x):
     return out
 
 
+def volume_blend(patches, slot, taps, vol, mean, std, min_val, fill, stride, want_std):
+    """Weighted overlap blending of ``patches`` [S,N,P,P,P] (S samples of the N kept windows, candidate order) into the [D,H,W] grid of
+    the raw volume ``vol``: ``slot`` [G0,G1,G2] int32 is a window's row in ``patches`` (-1: not kept) on the origin lattice
+    ``g * stride``, ``taps`` [P] the 1-D window on the device.  Returns ``(mean, std | None)``: the per-voxel mean over the samples of
+    the blended value and, with ``want_std`` (S >= 2), its unbiased standard deviation; uncovered voxels hold ``fill``, background
+    voxels (normalised ``vol`` equal to ``min_val``) ``min_val``, both with deviation 0.  One launch, bit-reproducible."""
+    _chk(patches, taps, vol)
+    _chk_int(slot)
+    if not (patches.is_contiguous() and taps.is_contiguous() and vol.is_contiguous()):
+        raise RuntimeError("volume_blend: tensors must be contiguous")
+    if patches.ndim != 5 or slot.ndim != 3 or vol.ndim != 3 or taps.ndim != 1:
+        raise ValueError("volume_blend: expected patches [S,N,P,P,P], slot [G0,G1,G2], taps [P] and vol [D,H,W]")
+    S, N, P = patches.shape[:3]
+    if tuple(patches.shape[2:]) != (P, P, P) or taps.shape[0] != P:
+        raise ValueError(f"volume_blend: patches {tuple(patches.shape)} / taps {tuple(taps.shape)} are not cubic windows of one size")
+    if slot.numel() and int(slot.max()) >= N:                     # the kernel indexes `patches` by it
+        raise ValueError(f"volume_blend: slot names window {int(slot.max())} of {N}")
+    D, H, W = vol.shape
+    out = torch.empty((D, H, W), dtype=torch.float32, device=vol.device)
+    dev = torch.empty_like(out) if want_std else None
+    _lib.call("diqt_volume_blend", patches if N else None, slot, taps, vol, out, dev, S, N, D, H, W, P, int(stride), *slot.shape,
+              float(mean), float(std), float(min_val), float(fill), _stream())
+    return out, dev
+
+
 def patch_pair_crop(lr_vols, hr_vols, sel, P, mode, mean, std):
     """data.py:119-132: crop + normalise ``sel[n] = (volume, i0, j0, k0)`` patch pairs out of the HBM-resident [V,D,H,W]
     volume stacks in one launch.  Returns (lr [n,P,P,P], hr [n,P,P,P])."""

@@ -580,6 +580,16 @@ int diqt_patch_scatter(const float* patches, const int* idx, const int* margins,
 int diqt_background_reset(float* pred, const float* vol, size_t n, float mean, float stdv, float min_val, void* stream);
 /* out[0] = min(x[0..n)); workspace: 1024 floats */
 int diqt_min_value(const float* x, size_t n, float* workspace_1024, float* out, void* stream);
+/* Weighted overlap blending, in place of the crop-and-overwrite stitching and the background reset of test_all.py:235-300:
+ * patches[S][N][P][P][P] holds S samples of the N kept windows in candidate order; slot[G0][G1][G2] (G_a =
+ * len(range(0, n_a - P + 1, stride))) is a window's row in `patches`, or < 0 for one that was not kept; taps[P] (DEVICE) is the
+ * 1-D window.  Per output voxel and sample, over the covering windows in candidate order: b_s = sum(w y) / sum(w) with
+ * w = (taps[i] taps[j]) taps[k]; out_mean = mean of b_s, out_std (may be NULL; must be NULL when S == 1) = their unbiased standard
+ * deviation (Welford, sample order).  A voxel no kept window covers gets `fill` (deviation 0); where vol (RAW, may be NULL) has
+ * (vol - mean) / std == min_val the voxel gets min_val (deviation 0).  One launch, gather-side, no atomics: bit-reproducible.   */
+int diqt_volume_blend(const float* patches, const int* slot, const float* taps, const float* vol, float* out_mean, float* out_std,
+                      int S, int N, int D, int H, int W, int P, int stride, int G0, int G1, int G2, float mean, float stdv,
+                      float min_val, float fill, void* stream);
 
 /* ---- training data path + validation metrics on the device ----------------------------------------------
  * data.py:88-137 supervisedIQT.__getitem__: crop a P^3 patch pair out of HBM-resident [V][D][H][W] low-res / high-res volume
