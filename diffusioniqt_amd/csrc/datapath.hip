@@ -7,7 +7,9 @@
 //   * MS-SSIM of the evaluation script (metrics.py:32-34 MSSIM, called per volume at test_all.py:56-62 -> torchmetrics 0.9.0
 //     MultiScaleStructuralSimilarityIndexMeasure): the SSIM tile kernel once per scale, which also pools the next scale,
 //   * weighted overlap blending of the sliding windows of a whole volume with the per-voxel spread of several samples
-//     (diffusioniqt_amd/inference.py, blend modes; in place of the crop-and-overwrite stitching of test_all.py:235-300).
+//     (diffusioniqt_amd/inference.py, blend modes; in place of the crop-and-overwrite stitching of test_all.py:235-300),
+//   * volume-anchored sampler noise: Philox4x32-10 keyed by the seed and counted by the voxel's position in the VOLUME, so overlapping
+//     windows draw the same noise (diffusioniqt_amd/inference.py, noise='anchored'; in place of one torch.randn per window batch).
 // All reductions are two-stage with a fixed order (bit-reproducible).
 #include "common.h"
 
@@ -410,6 +412,53 @@ __global__ __launch_bounds__(256) void volume_blend_kernel(const float* __restri
     out_mean[v] = om;
     if (out_std) out_std[v] = os;
 }
+
+// ---- volume-anchored noise: a counter-based generator evaluated per output voxel ------------------------------------------------------
+// The value at global voxel (z, y, x) of channel c, draw k, sample s is a pure function of (seed, c, z, y, x, k, s): Philox4x32-10
+// (Salmon et al., SC'11; Random123's constants) with counter {lin & 0xffffffff, lin >> 32, draw, sample}, lin = ((c D + z) H + y) W + x in
+// 64 bits, and key {seed & 0xffffffff, seed >> 32}.  Every window that covers a voxel therefore sees the same number, whatever the batch
+// it came in.  ONE call per voxel, words r0 / r1 used and r2 / r3 dropped: sharing a call between four neighbours would tie the value to
+// the window's alignment along x, and the whole launch is tens of microseconds beside a U-Net evaluation.
+struct Philox { unsigned r0, r1; };
+__device__ __forceinline__ Philox philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0, p1 = (unsigned long long)0xCD9E8D57u * c2;
+        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
+        c1 = (unsigned)p1;
+        c3 = (unsigned)p0;
+        c0 = n0;
+        c2 = n2;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    return Philox{c0, c1};
+}
+// out[b][c][i][j][k] for the window origins[b] = {z0, y0, x0}; one thread per output voxel, consecutive lanes = consecutive k.
+// RAW: the two words as they are (int32 pairs).  Otherwise Box-Muller on u1 = ((r0 >> 9) + 0.5) 2^-23 in (0, 1) and
+// u2 = (r1 >> 8) 2^-24 in [0, 1), both exact in fp32, with the accurate logf / sqrtf / cospif.
+template <bool RAW>
+__global__ __launch_bounds__(256) void anchored_noise_kernel(const int* __restrict__ origins, void* __restrict__ out, size_t total, int C,
+                                                             int P, int D, int H, int W, unsigned k0, unsigned k1, unsigned draw,
+                                                             unsigned sample) {
+    const size_t per = (size_t)P * P * P;
+    for (size_t e = blockIdx.x * (size_t)256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
+        const size_t w = e / per;                              // b * C + c
+        const unsigned v = (unsigned)(e - w * per), pp = (unsigned)P * P;
+        const unsigned i = v / pp, j = (v - i * pp) / P, k = v - i * pp - j * P;
+        const int b = (int)(w / C), c = (int)(w - (size_t)b * C);
+        const int* o = origins + 3 * (size_t)b;
+        const unsigned long long lin = (((unsigned long long)c * D + (unsigned)(o[0] + i)) * H + (unsigned)(o[1] + j)) * W + (unsigned)(o[2] + k);
+        const Philox r = philox4x32_10((unsigned)lin, (unsigned)(lin >> 32), draw, sample, k0, k1);
+        if constexpr (RAW) {
+            static_cast<int2*>(out)[e] = make_int2((int)r.r0, (int)r.r1);
+        } else {
+            const float u1 = ((float)(r.r0 >> 9) + 0.5f) * 1.1920928955078125e-7f;       // 2^-23
+            const float u2 = (float)(r.r1 >> 8) * 5.9604644775390625e-8f;                // 2^-24
+            static_cast<float*>(out)[e] = sqrtf(-2.f * logf(u1)) * cospif(2.f * u2);
+        }
+    }
+}
 }  // namespace diqt
 
 using namespace diqt;
@@ -615,4 +664,21 @@ extern "C" int diqt_volume_blend(const float* patches, const int* slot, const fl
     hipLaunchKernelGGL(volume_blend_kernel, dim3((W + 63) / 64, (H + 3) / 4, D), dim3(64, 4), (size_t)P * sizeof(float), STREAM, patches,
                        slot, taps, vol, out_mean, out_std, S, N, D, H, W, P, stride, G0, G1, G2, mean, stdv, min_val, fill);
     return check_launch("volume_blend");
+}
+
+extern "C" int diqt_anchored_noise(const int* origins, int B, int C, int P, int D, int H, int W, unsigned long long seed, unsigned draw,
+                                   unsigned sample, int raw, void* out, void* stream) {
+    DIQT_REQUIRE(origins && out, DIQT_E_ALIGN, "anchored_noise: null pointer");
+    DIQT_REQUIRE(B > 0 && C > 0 && P > 0 && D > 0 && H > 0 && W > 0 && P <= D && P <= H && P <= W, DIQT_E_SHAPE,
+                 "anchored_noise: bad shape (B %d, C %d, P %d in %dx%dx%d)", B, C, P, D, H, W);
+    DIQT_REQUIRE(P <= 1024, DIQT_E_SHAPE, "anchored_noise: windows of at most 1024^3 voxels");
+    DIQT_REQUIRE(raw == 0 || raw == 1, DIQT_E_UNSUPPORTED, "anchored_noise: raw %d (0 = normals, 1 = the two Philox words)", raw);
+    const size_t total = (size_t)B * C * P * P * P;
+    const unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
+    const unsigned nb = grid_for(total, 256);
+    if (raw)
+        hipLaunchKernelGGL(anchored_noise_kernel<true>, dim3(nb), dim3(256), 0, STREAM, origins, out, total, C, P, D, H, W, k0, k1, draw, sample);
+    else
+        hipLaunchKernelGGL(anchored_noise_kernel<false>, dim3(nb), dim3(256), 0, STREAM, origins, out, total, C, P, D, H, W, k0, k1, draw, sample);
+    return check_launch("anchored_noise");
 }

@@ -144,8 +144,9 @@ class GaussianDiffusionContinuousTimes(nn.Module):
     def get_condition(self, times):
         return maybe(self.log_snr)(times)
 
-    def get_sampling_timesteps(self, batch, *, device):
-        times = torch.linspace(1., 0., self.num_timesteps + 1, device=device)
+    def get_sampling_timesteps(self, batch, *, device, steps=None):
+        """[(t, t_next)] pairs of ``linspace(1, 0, steps + 1)``; ``steps=None`` is the schedule's own ``num_timesteps``."""
+        times = torch.linspace(1., 0., default(steps, self.num_timesteps) + 1, device=device)
         times = times[None, :].repeat(batch, 1)
         times = torch.stack((times[:, :-1], times[:, 1:]), dim=0)
         return times.unbind(dim=-1)
@@ -160,6 +161,23 @@ class GaussianDiffusionContinuousTimes(nn.Module):
         logvar = log(var, eps=1e-20)
         nonzero = 1 - (t_next == 0).float()
         return alpha_next * (1 - c) / alpha, alpha_next * c, nonzero * (0.5 * logvar).exp()
+
+    def ddim_coefficients(self, t, t_next, eta):
+        """The generalised DDIM step (Song et al., ICLR 2021, eq. 12) folded into x_next = kx*x_t + k0*x0 + kn*noise for [B] CPU tensors:
+        with (alpha, sigma) at t, (alpha', sigma') at t_next and c = -expm1(logsnr - logsnr'), s = eta sqrt(sigma'^2 c) is the injected
+        deviation, kx = sqrt(max(sigma'^2 - s^2, 0)) / sigma carries the implied noise (x_t - alpha x0) / sigma over, and
+        k0 = alpha' - kx alpha.  ``eta = 1`` is algebraically ``posterior_coefficients`` (mean and variance), ``eta = 0`` the deterministic
+        sampler.  The fp32 log-SNR values are the ones the network is conditioned on; the algebra on them runs in float64 (at eta = 1 it
+        has the cancellation 1 - c that the fp32 ancestral form carries) and the results are cast to fp32 for the step kernel."""
+        log_snr, log_snr_next = self.log_snr(t).double(), self.log_snr(t_next).double()
+        alpha, sigma = log_snr_to_alpha_sigma(log_snr)
+        alpha_next, sigma_next = log_snr_to_alpha_sigma(log_snr_next)
+        c = -torch.special.expm1(log_snr - log_snr_next)
+        s = float(eta) * torch.sqrt((sigma_next ** 2) * c)
+        kx = torch.sqrt(((sigma_next ** 2) - s ** 2).clamp(min=0.)) / sigma
+        k0 = alpha_next - kx * alpha
+        kn = s * (t_next != 0).double()
+        return kx.float(), k0.float(), kn.float()
 
     def q_posterior(self, x_start, x_t, t, *, t_next=None):
         t_next = default(t_next, lambda: (t - 1. / self.num_timesteps).clamp(min=0.))
@@ -1201,37 +1219,73 @@ class Imagen(nn.Module):
         kw = dict(cond_images=cond_images, cond_scale=cond_scale, lowres_cond_img=lowres_cond_img, self_cond=self_cond)
         return self._graphs.run(unet, fwd, (img, cond), kw)
 
+    @staticmethod
+    def _check_sampler_args(sampler, sample_steps, skip_steps, eta, has_inpainting):
+        """The argument rules of ``sampler`` / ``sample_steps`` / ``eta`` (host only: nothing has touched the device when these raise)."""
+        if sampler not in ('ddpm', 'ddim'):
+            raise ValueError(f"sampler must be 'ddpm' or 'ddim', got {sampler!r}")
+        if exists(sample_steps):
+            if exists(skip_steps):
+                raise ValueError("sample_steps and skip_steps both thin the chain: give one of them")
+            if isinstance(sample_steps, bool) or int(sample_steps) != sample_steps or sample_steps < 1:
+                raise ValueError(f"sample_steps must be a positive integer, got {sample_steps!r}")
+        if sampler == 'ddim':
+            if has_inpainting:
+                raise ValueError("sampler='ddim' does not inpaint: the re-noising schedule of the inpainting loop is the ancestral one")
+            if not 0. <= eta <= 1.:
+                raise ValueError(f"eta must lie in [0, 1], got {eta!r}")
+
     @torch.no_grad()
     def p_sample_loop(self, unet, shape, *, noise_scheduler, lowres_cond_img=None, cond_images=None, inpaint_images=None,
                       inpaint_masks=None, inpaint_resample_times=5, init_images=None, skip_steps=None, cond_scale=1,
-                      pred_objective='noise', dynamic_threshold=True, use_tqdm=True, noise=None):
+                      pred_objective='noise', dynamic_threshold=True, use_tqdm=True, noise=None, sampler='ddpm',
+                      sample_steps=None, eta=0.0):
         """Ancestral sampler (:2059-2160).  Per step: one U-Net eval (HIP) + ONE fused posterior-step kernel;
         the per-step coefficients for all steps are computed on the host up front.  ``noise`` (optional) is a list
-        [init, step_0, ...] of injected tensors with the reference's draw order (:2080, :2051)."""
+        [init, step_0, ...] of injected tensors with the reference's draw order (:2080, :2051), or a callable
+        ``noise(shape) -> fp32 device tensor`` whose successive calls are those draws.
+
+        ``sample_steps=K`` walks ``linspace(1, 0, K + 1)`` instead of the schedule's ``num_timesteps`` (either sampler).
+        ``sampler='ddim'`` replaces the posterior coefficients by ``ddim_coefficients(t, t_next, eta)`` in the SAME step kernel; the x0
+        conversion, the clamp and dynamic thresholding are the ancestral branch's.  With ``eta == 0`` the loop consumes one draw, the
+        initial image (the kernel's noise operand is one zero tensor); with ``eta > 0`` one more per step, as the ancestral sampler."""
         if pred_objective not in ('noise', 'x_start', 'v'):
             raise ValueError(f'unknown objective {pred_objective}')
+        has_inpainting = exists(inpaint_images) and exists(inpaint_masks)                  # (:2090-2091)
+        self._check_sampler_args(sampler, sample_steps, skip_steps, eta, has_inpainting)
         device = self.device
         batch = shape[0]
-        noise = list(noise) if exists(noise) else None
-        draw = (lambda: noise.pop(0).to(device).contiguous()) if exists(noise) else \
-            (lambda: torch.randn(shape, device=device))
+        if callable(noise):
+            draw = lambda: noise(shape).to(device).contiguous()
+        else:
+            noise = list(noise) if exists(noise) else None
+            draw = (lambda: noise.pop(0).to(device).contiguous()) if exists(noise) else \
+                (lambda: torch.randn(shape, device=device))
         img = draw()
         if exists(init_images):
             img = ops.add(img, init_images.to(device).float())
 
-        has_inpainting = exists(inpaint_images) and exists(inpaint_masks)                  # (:2090-2091)
         resample_times = inpaint_resample_times if has_inpainting else 1
         if has_inpainting:
             inpaint_images = inpaint_images.to(device).float().expand(shape).contiguous()
             mask_f = inpaint_masks.to(device).bool().expand(shape).float().contiguous()
 
-        timesteps = list(noise_scheduler.get_sampling_timesteps(batch, device='cpu'))
+        timesteps = list(noise_scheduler.get_sampling_timesteps(batch, device='cpu', steps=sample_steps))
         skip_steps = default(skip_steps, 0)
         if skip_steps > 1:
             timesteps = timesteps[::skip_steps] + [timesteps[-1]]           # (:2105-2107)
 
         # host: coefficients of every step, uploaded once  [T, 3, B] ; log-SNR conditioning [T, B]
-        coefs = torch.stack([torch.stack(noise_scheduler.posterior_coefficients(t, tn)) for t, tn in timesteps])
+        if sampler == 'ddim':
+            coefs = torch.stack([torch.stack(noise_scheduler.ddim_coefficients(t, tn, eta)) for t, tn in timesteps])
+            if eta == 0:                                                    # kn == 0: the step kernel reads one zero tensor, no draw
+                zero = torch.zeros(shape, device=device)
+                step_noise = lambda: zero
+            else:
+                step_noise = draw
+        else:
+            coefs = torch.stack([torch.stack(noise_scheduler.posterior_coefficients(t, tn)) for t, tn in timesteps])
+            step_noise = draw
         conds = torch.stack([noise_scheduler.get_condition(t) for t, _ in timesteps])
         # x0 from a noise / v prediction (:343-357) and the inpainting re-noise coefficients (:324-341), per step [T, 2, B]
         al, sg = log_snr_to_alpha_sigma(conds)
@@ -1265,9 +1319,9 @@ class Imagen(nn.Module):
                     s = ops.abs_quantile(pred, self.dynamic_thresholding_percentile)
                     s.clamp_(min=1. if self.configs['Data']['norm'] == 'min-max' else float(self.min_bound))
                     pred = ops.dynamic_threshold(pred, s)
-                    img, x_start = ops.ddpm_step(img, pred, draw(), coefs[i, 0], coefs[i, 1], coefs[i, 2], -inf, inf, 1)
+                    img, x_start = ops.ddpm_step(img, pred, step_noise(), coefs[i, 0], coefs[i, 1], coefs[i, 2], -inf, inf, 1)
                 else:
-                    img, x_start = ops.ddpm_step(img, pred, draw(), coefs[i, 0], coefs[i, 1], coefs[i, 2], lo, hi, mode)
+                    img, x_start = ops.ddpm_step(img, pred, step_noise(), coefs[i, 0], coefs[i, 1], coefs[i, 2], lo, hi, mode)
                 if has_inpainting and not (r == 0 or all_last):                            # (:2139-2146)
                     img = ops.axpby3(img, draw(), None, renoise[i, 0], renoise[i, 1], None, 0.0, 0.0, 0)
             noisy_dev.append(img)
@@ -1287,17 +1341,21 @@ class Imagen(nn.Module):
                inpaint_masks=None, inpaint_resample_times=5, init_images=None, skip_steps=None, batch_size=1,
                cond_scale=1., lowres_sample_noise_level=None, start_at_unet_number=1, start_image_or_video=None,
                stop_at_unet_number=None, return_all_outputs=False, return_all_unet_outputs=None, return_pil_images=False,
-               device=None, use_tqdm=True, noise=None):
+               device=None, use_tqdm=True, noise=None, sampler='ddpm', sample_steps=None, eta=0.0):
         """imagen_pytorch3D.py:2165-2274 -> (img, [noisy per step], [x0 per step]).  Accepts both spellings
-        ``return_all_outputs`` / ``return_all_unet_outputs`` (test.py:182 uses the latter)."""
+        ``return_all_outputs`` / ``return_all_unet_outputs`` (test.py:182 uses the latter).  ``sampler`` / ``sample_steps`` / ``eta``
+        (one value, or one per U-Net like ``skip_steps``) and the list or callable ``noise``: see ``p_sample_loop``."""
         if exists(return_all_unet_outputs):
             return_all_outputs = return_all_unet_outputs
+        num_unets = len(self.unets)
+        skip_steps = cast_tuple(skip_steps, num_unets)
+        sampler, sample_steps, eta = (cast_tuple(v, num_unets) for v in (sampler, sample_steps, eta))
+        for args in zip(sampler, sample_steps, skip_steps, eta):
+            self._check_sampler_args(*args, exists(inpaint_images) and exists(inpaint_masks))
         device = default(device, self.device)
         self.reset_unets_all_one_device(device=device)
-        num_unets = len(self.unets)
         cond_scale = cast_tuple(cond_scale, num_unets)
         init_images = list(cast_tuple(init_images, num_unets))
-        skip_steps = cast_tuple(skip_steps, num_unets)
         if start_at_unet_number > 1:
             assert start_at_unet_number <= num_unets, 'must start a unet that is less than the total number of unets'
             assert not exists(stop_at_unet_number) or start_at_unet_number <= stop_at_unet_number
@@ -1306,9 +1364,9 @@ class Imagen(nn.Module):
         outputs = []
         lst_pred_noisy = lst_pred = None
         for unet_number, unet, image_size, noise_scheduler, pred_objective, dynamic_threshold, unet_cond_scale, \
-                unet_init_images, unet_skip_steps in zip(range(1, num_unets + 1), self.unets, self.image_sizes,
-                                                         self.noise_schedulers, self.pred_objectives,
-                                                         self.dynamic_thresholding, cond_scale, init_images, skip_steps):
+                unet_init_images, unet_skip_steps, unet_sampler, unet_sample_steps, unet_eta in zip(
+                    range(1, num_unets + 1), self.unets, self.image_sizes, self.noise_schedulers, self.pred_objectives,
+                    self.dynamic_thresholding, cond_scale, init_images, skip_steps, sampler, sample_steps, eta):
             if unet_number < start_at_unet_number:
                 continue
             assert not isinstance(unet, NullUnet), 'one cannot sample from null / placeholder unets'
@@ -1318,7 +1376,8 @@ class Imagen(nn.Module):
                 unet, shape, cond_images=cond_images, inpaint_images=inpaint_images, inpaint_masks=inpaint_masks,
                 inpaint_resample_times=inpaint_resample_times, init_images=unet_init_images, skip_steps=unet_skip_steps,
                 cond_scale=unet_cond_scale, lowres_cond_img=lowres_cond_img, noise_scheduler=noise_scheduler,
-                pred_objective=pred_objective, dynamic_threshold=dynamic_threshold, use_tqdm=use_tqdm, noise=noise)
+                pred_objective=pred_objective, dynamic_threshold=dynamic_threshold, use_tqdm=use_tqdm, noise=noise,
+                sampler=unet_sampler, sample_steps=unet_sample_steps, eta=unet_eta)
             outputs.append(img)
             if exists(stop_at_unet_number) and stop_at_unet_number == unet_number:
                 break

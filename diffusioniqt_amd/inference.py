@@ -26,7 +26,13 @@ Beyond the scripts (``blend`` / ``samples``; the defaults leave every line above
   order — no atomics, bit-reproducible, independent of ``Eval.batch_size``; the background reset is fused into it.  A voxel that no
   kept window covers keeps the fill value ``(0 - mean) / std``;
 * ``samples=S`` draws every batch S times (sample 0 of a batch, then sample 1, ...); the result is the per-voxel mean of the S
-  blended volumes and, with ``return_std=True``, their unbiased standard deviation — the uncertainty map of a stochastic sampler.
+  blended volumes and, with ``return_std=True``, their unbiased standard deviation — the uncertainty map of a stochastic sampler;
+* ``noise='anchored'`` hands the sampler a noise source tied to the VOLUME instead of letting every batch draw its own: the value at
+  global voxel (z, y, x) of draw k and sample s is a pure function of (seed, z, y, x, k, s) (``AnchoredNoise``, one Philox4x32-10 call
+  per voxel in ``ops.anchored_noise``), so all windows that cover a voxel start from — and, in a stochastic sampler, are pushed by —
+  the same numbers, whatever ``Eval.batch_size`` is, whichever windows the non-zero filter kept and in whatever order or on
+  whichever rank they run.  What is left of the disagreement between overlapping windows is what the network does differently with
+  different context; the ``samples = S`` fields are independent of each other and coherent across windows.
 """
 import numpy as np
 import torch
@@ -70,11 +76,53 @@ def blend_taps(P, kind='gaussian', sigma_scale=0.125):
     return (t / t.max()).astype(np.float32)
 
 
+NOISE_MODES = (None, 'anchored')
+
+
+class AnchoredNoise:
+    """Noise anchored to a [D,H,W] volume.  ``source(origins, P, sample)`` is what a sampler takes as ``noise=``: a callable whose
+    call number k (0 = the initial image, then one per stochastic step) returns draw k of the field, cut out at the windows
+    ``origins`` [B,3] of edge P -- ``ops.anchored_noise(origins, C, P, D, H, W, seed, draw=k, sample=sample)``."""
+
+    def __init__(self, volume_shape, seed=0):
+        self.shape = tuple(int(s) for s in volume_shape)
+        if len(self.shape) != 3:
+            raise ValueError(f"AnchoredNoise: volume_shape must be (D, H, W), got {volume_shape!r}")
+        self.seed = int(seed)
+
+    def source(self, origins, P, sample=0, device=None):
+        origins = np.ascontiguousarray(np.asarray(origins).reshape(-1, 3))
+        state = {'draw': 0}
+
+        def noise(shape):
+            shape = tuple(shape)
+            assert len(shape) == 5 and shape[0] == origins.shape[0] and shape[2:] == (P, P, P), \
+                f"AnchoredNoise: the sampler asked for {shape}, the source was made for {origins.shape[0]} windows of edge {P}"
+            out = ops.anchored_noise(origins, shape[1], P, *self.shape, self.seed, draw=state['draw'], sample=sample, device=device)
+            state['draw'] += 1
+            return out
+        return noise
+
+
+def sub_volume_origins(origin, factor, sub):
+    """Origins of the ``factor^3`` sub-volumes of the block at ``origin`` in the order of ``convertVolume2subVolume``
+    (utils_mine.py:25-42): sub-volume n = b2 + f b3 + f^2 b4 starts at origin + sub (b2, b3, b4)."""
+    n = np.arange(factor ** 3)
+    off = np.stack((n % factor, (n // factor) % factor, n // (factor * factor)), axis=1) * sub
+    return (np.asarray(origin).reshape(1, 3) + off).astype(np.int32)
+
+
 class VolumeInference:
-    def __init__(self, configs, sample_fn, nonzero_ratio=0.05, blend=None, sigma_scale=0.125, samples=1):
+    def __init__(self, configs, sample_fn, nonzero_ratio=0.05, blend=None, sigma_scale=0.125, samples=1, noise=None, seed=0):
         """``sample_fn(lr_patches [B,1,S,S,S]) -> hr_patches`` — e.g. ``lambda x: trainer.sample(batch_size=x.shape[0],
         start_image_or_video=x, start_at_unet_number=2)[0]`` (test_all.py:234).  ``blend`` / ``sigma_scale`` / ``samples``: weighted
-        overlap blending and multi-sample statistics, see the module docstring."""
+        overlap blending and multi-sample statistics, see the module docstring.  ``noise='anchored'`` (with ``seed``): every call
+        becomes ``sample_fn(lr_patches, noise=source)`` with the volume-anchored source of that batch's windows and sample index —
+        e.g. ``lambda x, noise=None: trainer.sample(batch_size=x.shape[0], start_image_or_video=x, start_at_unet_number=2,
+        sampler='ddim', sample_steps=50, noise=noise)[0]``."""
+        if noise not in NOISE_MODES:
+            raise ValueError(f"VolumeInference: noise must be None or 'anchored', got {noise!r}")
+        self.noise, self.seed = noise, int(seed)
         if blend not in BLEND_MODES:
             raise ValueError(f"VolumeInference: blend must be None, 'gaussian' or 'constant', got {blend!r}")
         if int(samples) != samples or samples < 1:
@@ -139,10 +187,10 @@ class VolumeInference:
             x, _ = ops.patch_gather(vol, idx, P, self.mean, self.std)
             if self.block_mode:                                                           # test_all.py:229-231, 265-266
                 sub = convertVolume2subVolume(x, target_shape=(self.factor ** 3, 1, self.sub, self.sub, self.sub))
-                y = self.sample_fn(sub)
+                y = self._sample(sub, o, shape, 0)
                 y = merge_sub_volumes(y.float(), original_shape=(1, 1, P, P, P))
             else:
-                y = self.sample_fn(x)
+                y = self._sample(x, o, shape, 0)
             y = y.float().contiguous()
             mg = torch.from_numpy(np.ascontiguousarray(margins[lo:lo + per_call])).to(dev)
             if serial_scatter:
@@ -154,6 +202,15 @@ class VolumeInference:
         min_val = (np.float32(min_raw) - mean32) / std32                                  # monotone map: min of the normalised volume
         ops.background_reset(pred, vol, self.mean, self.std, float(min_val))             # test_all.py:300
         return pred
+
+    def _sample(self, x, origins, volume_shape, s):
+        """One sampler call on the windows at ``origins`` (block mode: ONE block, already split into its sub-volumes), sample ``s``."""
+        if self.noise is None:
+            return self.sample_fn(x)
+        if self.block_mode:
+            origins = sub_volume_origins(origins[0], self.factor, self.sub)
+        src = AnchoredNoise(volume_shape, self.seed).source(origins, self.sub, sample=s, device=x.device)
+        return self.sample_fn(x, noise=src)
 
     def _blended(self, lowres_raw, want_std):
         """The blend modes: every kept window's S predictions are kept in ``patches`` [S,N,P,P,P]; one ``ops.volume_blend`` launch
@@ -173,13 +230,14 @@ class VolumeInference:
         patches = torch.empty((S, N, P, P, P), dtype=torch.float32, device=dev)
         per_call = 1 if self.block_mode else self.batch
         for lo in range(0, N, per_call):
-            idx = torch.from_numpy(np.ascontiguousarray(kept[lo:lo + per_call])).to(dev)
+            o = np.ascontiguousarray(kept[lo:lo + per_call])
+            idx = torch.from_numpy(o).to(dev)
             n = idx.shape[0]
             x, _ = ops.patch_gather(vol, idx, P, self.mean, self.std)
             if self.block_mode:                                                           # test_all.py:229-231, 265-266
                 x = convertVolume2subVolume(x, target_shape=(self.factor ** 3, 1, self.sub, self.sub, self.sub))
             for s in range(S):
-                y = self.sample_fn(x)
+                y = self._sample(x, o, shape, s)
                 if self.block_mode:
                     y = merge_sub_volumes(y.float(), original_shape=(1, 1, P, P, P))
                 patches[s, lo:lo + n] = y.float().reshape(n, P, P, P)

@@ -2329,6 +2329,39 @@ def volume_blend(patches, slot, taps, vol, mean, std, min_val, fill, stride, wan
     return out, dev
 
 
+def anchored_noise(origins, C, P, D, H, W, seed, draw=0, sample=0, raw=False, device=None):
+    """Volume-anchored noise for the windows ``origins`` [B,3] (HOST integers: (z, y, x) of each window's first voxel) of edge P in a
+    C-channel [D,H,W] volume: fp32 normals [B,C,P,P,P], or with ``raw`` the two Philox4x32-10 words per voxel, int32 [B,C,P,P,P,2].
+    The value at a voxel depends on (seed, channel, global position, draw, sample) alone -- include/diqt.h, diqt_anchored_noise -- so
+    windows that overlap agree on the overlap bit for bit.  The origins are checked here, on the host, before anything is launched."""
+    import numpy as np
+    if torch.is_tensor(origins):
+        origins = origins.detach().cpu().numpy()
+    org = np.asarray(origins)
+    if org.ndim != 2 or org.shape[1] != 3 or org.shape[0] < 1 or not np.issubdtype(org.dtype, np.integer):
+        raise ValueError(f"anchored_noise: origins must be an integer [B,3] array with B >= 1, got {org.dtype} {tuple(org.shape)}")
+    C, P, D, H, W = int(C), int(P), int(D), int(H), int(W)
+    if min(C, P, D, H, W) < 1:
+        raise ValueError(f"anchored_noise: C, P and the volume shape must be positive, got C {C}, P {P}, volume {(D, H, W)}")
+    org = org.astype(np.int64)
+    if (org < 0).any() or (org + P > np.array([D, H, W], dtype=np.int64)).any():
+        bad = org[((org < 0) | (org + P > np.array([D, H, W], dtype=np.int64))).any(axis=1)][0]
+        raise ValueError(f"anchored_noise: the window of edge {P} at {tuple(int(v) for v in bad)} leaves the volume {(D, H, W)}")
+    seed, draw, sample = int(seed), int(draw), int(sample)
+    if not (0 <= seed < 2 ** 64 and 0 <= draw < 2 ** 32 and 0 <= sample < 2 ** 32):
+        raise ValueError(f"anchored_noise: seed must fit 64 bits, draw and sample 32 bits (unsigned), got {seed}, {draw}, {sample}")
+    if not torch.cuda.is_available():
+        raise RuntimeError("diffusioniqt_amd.ops.anchored_noise runs on the MI355X only (no CPU fallback)")
+    device = torch.device('cuda' if device is None else device)
+    B = org.shape[0]
+    idx = torch.from_numpy(np.ascontiguousarray(org.astype(np.int32))).to(device)
+    shape = (B, C, P, P, P)
+    with torch.cuda.device(idx.device):
+        out = torch.empty(shape + (2,), dtype=torch.int32, device=device) if raw else torch.empty(shape, dtype=torch.float32, device=device)
+        _lib.call("diqt_anchored_noise", idx, B, C, P, D, H, W, seed, draw, sample, int(bool(raw)), out, _stream())
+    return out
+
+
 def patch_pair_crop(lr_vols, hr_vols, sel, P, mode, mean, std):
     """data.py:119-132: crop + normalise ``sel[n] = (volume, i0, j0, k0)`` patch pairs out of the HBM-resident [V,D,H,W]
     volume stacks in one launch.  Returns (lr [n,P,P,P], hr [n,P,P,P])."""

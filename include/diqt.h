@@ -590,6 +590,16 @@ int diqt_min_value(const float* x, size_t n, float* workspace_1024, float* out, 
 int diqt_volume_blend(const float* patches, const int* slot, const float* taps, const float* vol, float* out_mean, float* out_std,
                       int S, int N, int D, int H, int W, int P, int stride, int G0, int G1, int G2, float mean, float stdv,
                       float min_val, float fill, void* stream);
+/* Volume-anchored sampler noise: out[b][c][i][j][k] for the B windows origins[b] = {z0, y0, x0} (int32, DEVICE) of edge P inside a
+ * C-channel [D][H][W] volume is a pure function of (seed, c, z0 + i, y0 + j, x0 + k, draw, sample) -- every window that covers a voxel
+ * gets the same number, whatever batch or order it arrives in.  Per voxel: lin = ((c D + z) H + y) W + x as an unsigned 64-bit
+ * integer; ONE Philox4x32-10 call (multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85, ten rounds) with
+ * counter {lin & 0xffffffff, lin >> 32, draw, sample} and key {seed & 0xffffffff, seed >> 32}; output words r0, r1 are used, r2, r3
+ * dropped.  raw = 1: out is int32 [B][C][P][P][P][2] = {r0, r1}.  raw = 0: out is fp32 [B][C][P][P][P], the Box-Muller normal
+ * n = sqrtf(-2 logf(u1)) cospif(2 u2) with u1 = ((r0 >> 9) + 0.5) 2^-23 in (0, 1) and u2 = (r1 >> 8) 2^-24 (both exact in fp32).
+ * The caller guarantees that every window lies inside the volume (the origins are on the device; the entry cannot look at them). */
+int diqt_anchored_noise(const int* origins, int B, int C, int P, int D, int H, int W, unsigned long long seed, unsigned draw,
+                        unsigned sample, int raw, void* out, void* stream);
 
 /* ---- training data path + validation metrics on the device ----------------------------------------------
  * data.py:88-137 supervisedIQT.__getitem__: crop a P^3 patch pair out of HBM-resident [V][D][H][W] low-res / high-res volume
