@@ -10,6 +10,9 @@
 //     (diffusioniqt_amd/inference.py, blend modes; in place of the crop-and-overwrite stitching of test_all.py:235-300),
 //   * volume-anchored sampler noise: Philox4x32-10 keyed by the seed and counted by the voxel's position in the VOLUME, so overlapping
 //     windows draw the same noise (diffusioniqt_amd/inference.py, noise='anchored'; in place of one torch.randn per window batch).
+//   * lockstep joint sampling of the overlapping windows: one reverse step of the noisy state of the whole volume per launch -- the
+//     blend walk over the windows' x0 predictions, the sampler step and the anchored noise fused (diffusioniqt_amd/inference.py,
+//     joint=True), and the per-sample finish (fill, background reset, statistics over the samples).
 // All reductions are two-stage with a fixed order (bit-reproducible).
 #include "common.h"
 
@@ -336,6 +339,62 @@ __global__ __launch_bounds__(256) void msssim_final_kernel(const double* __restr
 // Block (64, 4): a wave owns 64 voxels of one row, so d, h and with them the g0 / g1 ranges, taps[i] taps[j] and the slot row are
 // wave-uniform; only the g2 range is per lane (any stride, also one that does not divide P).  Lanes of one window read consecutive
 // floats.  Every element of `patches` is read exactly once per launch.
+// The window walk of one output voxel (d, h, x) over one sample's rows `ps`: num = sum(w c(y)), den = sum(w) over the covering kept
+// windows in candidate order, with c the caller's clamp (the identity for the blend).  Shared by volume_blend_kernel and
+// volume_joint_step_kernel, so the two fuse windows with the same terms in the same order.
+struct Cover { int lo0, hi0, lo1, hi1, lo2, hi2; };
+// covering lattice indices of coordinate c: 0 <= g < G and 0 <= c - g * stride < P
+__device__ __forceinline__ Cover covering(int d, int h, int x, int P, int stride, int G0, int G1, int G2) {
+    return Cover{max(0, (d - P + stride) / stride), min(G0 - 1, d / stride), max(0, (h - P + stride) / stride), min(G1 - 1, h / stride),
+                 max(0, (x - P + stride) / stride), min(G2 - 1, x / stride)};
+}
+struct NoClamp {
+    __device__ __forceinline__ float operator()(float y) const { return y; }
+};
+template <class Clamp>
+__device__ __forceinline__ void window_walk(const float* __restrict__ ps, const int* __restrict__ slot, const float* __restrict__ taps,
+                                            const float* tp, int N, int P, int stride, int G1, int G2, int d, int h, int x,
+                                            const Cover& cv, Clamp c, float& num, float& den) {
+    const size_t per = (size_t)P * P * P;
+    num = 0.f;
+    den = 0.f;
+    for (int g0 = cv.lo0; g0 <= cv.hi0; ++g0) {
+        const int i = d - g0 * stride;
+        const float wi = tp[i];
+        for (int g1 = cv.lo1; g1 <= cv.hi1; ++g1) {
+            const int j = h - g1 * stride;
+            const float wij = wi * tp[j];
+            const int* srow = slot + ((size_t)g0 * G1 + g1) * G2;
+            const float* prow = ps + ((size_t)i * P + j) * P;
+            // four windows per trip: their slot reads, then their patch reads, are independent loads in flight together (one
+            // window per trip is a chain of two dependent loads, and the kernel ran at the memory latency).  A window that is
+            // not kept (-1), or lies past hi2, reads taps[0] instead and enters with weight 0: adding +0 terms changes no bit.
+            for (int g2 = cv.lo2; g2 <= cv.hi2; g2 += 4) {
+                int n[4];
+                float w[4], y[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int nn = srow[min(g2 + u, cv.hi2)];
+                    n[u] = g2 + u <= cv.hi2 ? nn : -1;
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const bool ok = (unsigned)n[u] < (unsigned)N;
+                    const int k = ok ? x - (g2 + u) * stride : 0;
+                    const float yy = *(ok ? prow + (size_t)n[u] * per + k : taps);
+                    w[u] = ok ? wij * tp[k] : 0.f;
+                    y[u] = ok ? c(yy) : 0.f;
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    num = fmaf(w[u], y[u], num);
+                    den += w[u];
+                }
+            }
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void volume_blend_kernel(const float* __restrict__ patches, const int* __restrict__ slot,
                                                            const float* __restrict__ taps, const float* __restrict__ vol,
                                                            float* __restrict__ out_mean, float* __restrict__ out_std, int S, int N,
@@ -352,51 +411,12 @@ __global__ __launch_bounds__(256) void volume_blend_kernel(const float* __restri
     if (vol && (vol[v] - mean) / stdv == min_val) {
         om = min_val;
     } else {
-        // covering lattice indices of coordinate c: 0 <= g < G and 0 <= c - g * stride < P
-        const int lo0 = max(0, (d - P + stride) / stride), hi0 = min(G0 - 1, d / stride);
-        const int lo1 = max(0, (h - P + stride) / stride), hi1 = min(G1 - 1, h / stride);
-        const int lo2 = max(0, (x - P + stride) / stride), hi2 = min(G2 - 1, x / stride);
+        const Cover cv = covering(d, h, x, P, stride, G0, G1, G2);
         const size_t per = (size_t)P * P * P;
         float m = 0.f, m2 = 0.f, den = 0.f;
         for (int s = 0; s < S; ++s) {
-            const float* ps = patches + (size_t)s * N * per;
-            float num = 0.f;
-            den = 0.f;                                  // the same terms in the same order for every s
-            for (int g0 = lo0; g0 <= hi0; ++g0) {
-                const int i = d - g0 * stride;
-                const float wi = tp[i];
-                for (int g1 = lo1; g1 <= hi1; ++g1) {
-                    const int j = h - g1 * stride;
-                    const float wij = wi * tp[j];
-                    const int* srow = slot + ((size_t)g0 * G1 + g1) * G2;
-                    const float* prow = ps + ((size_t)i * P + j) * P;
-                    // four windows per trip: their slot reads, then their patch reads, are independent loads in flight together (one
-                    // window per trip is a chain of two dependent loads, and the kernel ran at the memory latency).  A window that is
-                    // not kept (-1), or lies past hi2, reads taps[0] instead and enters with weight 0: adding +0 terms changes no bit.
-                    for (int g2 = lo2; g2 <= hi2; g2 += 4) {
-                        int n[4];
-                        float w[4], y[4];
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) {
-                            const int nn = srow[min(g2 + u, hi2)];
-                            n[u] = g2 + u <= hi2 ? nn : -1;
-                        }
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) {
-                            const bool ok = (unsigned)n[u] < (unsigned)N;
-                            const int k = ok ? x - (g2 + u) * stride : 0;
-                            const float yy = *(ok ? prow + (size_t)n[u] * per + k : taps);
-                            w[u] = ok ? wij * tp[k] : 0.f;
-                            y[u] = ok ? yy : 0.f;
-                        }
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) {
-                            num = fmaf(w[u], y[u], num);
-                            den += w[u];
-                        }
-                    }
-                }
-            }
+            float num;                                  // den: the same terms in the same order for every s
+            window_walk(patches + (size_t)s * N * per, slot, taps, tp, N, P, stride, G1, G2, d, h, x, cv, NoClamp{}, num, den);
             if (den == 0.f) break;
             const float b = num / den, delta = b - m;
             m += delta / (float)(s + 1);
@@ -434,9 +454,15 @@ __device__ __forceinline__ Philox philox4x32_10(unsigned c0, unsigned c1, unsign
     }
     return Philox{c0, c1};
 }
+// Box-Muller on u1 = ((r0 >> 9) + 0.5) 2^-23 in (0, 1) and u2 = (r1 >> 8) 2^-24 in [0, 1), both exact in fp32, with the accurate
+// logf / sqrtf / cospif.
+__device__ __forceinline__ float philox_normal(Philox r) {
+    const float u1 = ((float)(r.r0 >> 9) + 0.5f) * 1.1920928955078125e-7f;       // 2^-23
+    const float u2 = (float)(r.r1 >> 8) * 5.9604644775390625e-8f;                // 2^-24
+    return sqrtf(-2.f * logf(u1)) * cospif(2.f * u2);
+}
 // out[b][c][i][j][k] for the window origins[b] = {z0, y0, x0}; one thread per output voxel, consecutive lanes = consecutive k.
-// RAW: the two words as they are (int32 pairs).  Otherwise Box-Muller on u1 = ((r0 >> 9) + 0.5) 2^-23 in (0, 1) and
-// u2 = (r1 >> 8) 2^-24 in [0, 1), both exact in fp32, with the accurate logf / sqrtf / cospif.
+// RAW: the two words as they are (int32 pairs), otherwise philox_normal of them.
 template <bool RAW>
 __global__ __launch_bounds__(256) void anchored_noise_kernel(const int* __restrict__ origins, void* __restrict__ out, size_t total, int C,
                                                              int P, int D, int H, int W, unsigned k0, unsigned k1, unsigned draw,
@@ -453,11 +479,103 @@ __global__ __launch_bounds__(256) void anchored_noise_kernel(const int* __restri
         if constexpr (RAW) {
             static_cast<int2*>(out)[e] = make_int2((int)r.r0, (int)r.r1);
         } else {
-            const float u1 = ((float)(r.r0 >> 9) + 0.5f) * 1.1920928955078125e-7f;       // 2^-23
-            const float u2 = (float)(r.r1 >> 8) * 5.9604644775390625e-8f;                // 2^-24
-            static_cast<float*>(out)[e] = sqrtf(-2.f * logf(u1)) * cospif(2.f * u2);
+            static_cast<float*>(out)[e] = philox_normal(r);
         }
     }
+}
+
+// ---- lockstep joint sampling of the overlapping windows: one noisy state for the whole volume ------------------------------------------
+// One reverse step of the VOLUME (MultiDiffusion, Bar-Tal et al. 2023): y[N][P][P][P] holds the kept windows' x0 predictions of this
+// step; per output voxel x0 = sum(w c(y)) / sum(w) over the covering kept windows -- volume_blend_kernel's walk for S = 1 with
+// ddpm_step_kernel's clamp c on every term -- and x_next = kx x_t + k0 x0 + kn n with n the anchored normal of channel 0 at (seed, d, h,
+// x, draw, sample), computed in the thread (no noise tensor, no blended x0 tensor, no separate step launch).  A voxel no kept window
+// covers keeps x_t (nothing ever gathers it) and gets x0_out = 0.  x_t == NULL is the initial state: x_next = the anchored normal of
+// `draw` everywhere, equal to anchored_noise_kernel's bit for bit (same Philox call, same philox_normal).  x_next may alias x_t: every
+// thread reads its own voxel, then writes it.
+// ddpm_step_kernel's `ka * x_t + kb * x0 + kn * noise` as the compiler contracts it there: the x_t product is fused into the rounded
+// x0 product, the rounded noise product is added last.  Spelled out (and kept from further contraction) because the same source
+// expression contracted the other way round in this kernel, one ulp away from the independent-window chain.
+__device__ __forceinline__ float sampler_update(float kx, float xt, float k0, float x0, float kn, float n) {
+#pragma clang fp contract(off)
+    const float b = k0 * x0, c = kn * n;
+    return fmaf(kx, xt, b) + c;
+}
+struct StepClamp {
+    float lo, hi;
+    int mode;
+    __device__ __forceinline__ float operator()(float y) const { return mode == 0 ? fmaxf(y, lo) : fminf(fmaxf(y, lo), hi); }
+};
+__global__ __launch_bounds__(256) void volume_joint_step_kernel(const float* __restrict__ y, const int* __restrict__ slot,
+                                                                const float* __restrict__ taps, const float* x_t, float* x_next,
+                                                                float* __restrict__ x0_out, int N, int D, int H, int W, int P,
+                                                                int stride, int G0, int G1, int G2, float kx, float k0, float kn,
+                                                                float lo, float hi, int clamp_mode, unsigned key0, unsigned key1,
+                                                                unsigned draw, unsigned sample) {
+    extern __shared__ float tp[];                      // [P]
+    if (x_t) {                                         // uniform over the launch
+        for (int e = threadIdx.y * 64 + threadIdx.x; e < P; e += 256) tp[e] = taps[e];
+        __syncthreads();
+    }
+    const int x = blockIdx.x * 64 + threadIdx.x;
+    const int h = __builtin_amdgcn_readfirstlane(blockIdx.y * 4 + threadIdx.y), d = blockIdx.z;
+    if (h >= H || x >= W) return;
+    const size_t v = ((size_t)d * H + h) * W + x;      // = lin of channel 0
+    if (!x_t) {
+        x_next[v] = philox_normal(philox4x32_10((unsigned)v, (unsigned)((unsigned long long)v >> 32), draw, sample, key0, key1));
+        return;
+    }
+    float num, den;
+    window_walk(y, slot, taps, tp, N, P, stride, G1, G2, d, h, x, covering(d, h, x, P, stride, G0, G1, G2),
+                StepClamp{lo, hi, clamp_mode}, num, den);
+    const float xt = x_t[v];
+    if (den == 0.f) {
+        x_next[v] = xt;
+        if (x0_out) x0_out[v] = 0.f;
+        return;
+    }
+    const float x0 = num / den;
+    float n = 0.f;
+    if (kn != 0.f) n = philox_normal(philox4x32_10((unsigned)v, (unsigned)((unsigned long long)v >> 32), draw, sample, key0, key1));
+    if (x0_out) x0_out[v] = x0;
+    x_next[v] = sampler_update(kx, xt, k0, x0, kn, n);
+}
+
+// The end of sample s of S: r = min_val on the background (background_reset_kernel's expression on the RAW vol), else x where a kept
+// window covers the voxel, else fill; then volume_blend_kernel's Welford update of (mean_io, m2_io) with r, and after the last sample
+// the unbiased deviation.  Sample 0 initialises the running pair (nothing is read from mean_io / m2_io then).
+__global__ __launch_bounds__(256) void volume_joint_finish_kernel(const float* __restrict__ xs, const int* __restrict__ slot,
+                                                                  const float* __restrict__ vol, float* __restrict__ mean_io,
+                                                                  float* __restrict__ m2_io, float* __restrict__ out_std, int s, int S,
+                                                                  int D, int H, int W, int P, int stride, int G0, int G1, int G2,
+                                                                  float mean, float stdv, float min_val, float fill) {
+    const int x = blockIdx.x * 64 + threadIdx.x;
+    const int h = __builtin_amdgcn_readfirstlane(blockIdx.y * 4 + threadIdx.y), d = blockIdx.z;
+    if (h >= H || x >= W) return;
+    const size_t v = ((size_t)d * H + h) * W + x;
+    float r;
+    if (vol && (vol[v] - mean) / stdv == min_val) {
+        r = min_val;
+    } else {
+        const Cover cv = covering(d, h, x, P, stride, G0, G1, G2);
+        bool covered = false;
+        for (int g0 = cv.lo0; g0 <= cv.hi0 && !covered; ++g0)
+            for (int g1 = cv.lo1; g1 <= cv.hi1 && !covered; ++g1) {
+                const int* srow = slot + ((size_t)g0 * G1 + g1) * G2;
+                for (int g2 = cv.lo2; g2 <= cv.hi2 && !covered; ++g2) covered = srow[g2] >= 0;
+            }
+        r = covered ? xs[v] : fill;
+    }
+    float m = 0.f, m2 = 0.f;
+    if (s > 0) {
+        m = mean_io[v];
+        if (m2_io) m2 = m2_io[v];
+    }
+    const float delta = r - m;
+    m += delta / (float)(s + 1);
+    m2 = fmaf(delta, r - m, m2);
+    mean_io[v] = m;
+    if (m2_io) m2_io[v] = m2;
+    if (out_std && s == S - 1) out_std[v] = sqrtf(m2 / (float)(S - 1));
 }
 }  // namespace diqt
 
@@ -681,4 +799,52 @@ extern "C" int diqt_anchored_noise(const int* origins, int B, int C, int P, int 
     else
         hipLaunchKernelGGL(anchored_noise_kernel<false>, dim3(nb), dim3(256), 0, STREAM, origins, out, total, C, P, D, H, W, k0, k1, draw, sample);
     return check_launch("anchored_noise");
+}
+
+static int joint_lattice_ok(const char* who, int D, int H, int W, int P, int stride, int G0, int G1, int G2) {
+    DIQT_REQUIRE(D > 0 && H > 0 && W > 0 && P > 0 && P <= D && P <= H && P <= W, DIQT_E_SHAPE, "%s: bad shape", who);
+    DIQT_REQUIRE(stride > 0, DIQT_E_SHAPE, "%s: stride %d", who, stride);
+    DIQT_REQUIRE(G0 == (D - P) / stride + 1 && G1 == (H - P) / stride + 1 && G2 == (W - P) / stride + 1, DIQT_E_SHAPE,
+                 "%s: lattice %dx%dx%d does not match range(0, n - P + 1, stride) of %dx%dx%d, P %d, stride %d", who, G0, G1, G2, D, H, W,
+                 P, stride);
+    return DIQT_OK;
+}
+
+extern "C" int diqt_volume_joint_step(const float* y, const int* slot, const float* taps, const float* x_t, float* x_next, float* x0_out,
+                                      int N, int D, int H, int W, int P, int stride, int G0, int G1, int G2, float kx, float k0, float kn,
+                                      float lo, float hi, int clamp_mode, unsigned long long seed, unsigned draw, unsigned sample,
+                                      void* stream) {
+    DIQT_REQUIRE(x_next, DIQT_E_ALIGN, "volume_joint_step: null pointer");
+    DIQT_REQUIRE(D > 0 && H > 0 && W > 0, DIQT_E_SHAPE, "volume_joint_step: bad shape");
+    DIQT_REQUIRE(D <= 65535 && (H + 3) / 4 <= 65535, DIQT_E_SHAPE, "volume_joint_step: more than 65535 planes / row groups");
+    size_t lds = 0;
+    if (x_t) {                                          // the initial state (x_t == NULL) ignores the window arguments
+        DIQT_REQUIRE(slot && taps && (y || N == 0), DIQT_E_ALIGN, "volume_joint_step: null pointer");
+        DIQT_REQUIRE(N >= 0, DIQT_E_SHAPE, "volume_joint_step: windows %d", N);
+        int rc = joint_lattice_ok("volume_joint_step", D, H, W, P, stride, G0, G1, G2);
+        if (rc) return rc;
+        DIQT_REQUIRE(clamp_mode == 0 || clamp_mode == 1, DIQT_E_UNSUPPORTED, "volume_joint_step: clamp_mode %d (0 = min, 1 = box)",
+                     clamp_mode);
+        lds = (size_t)P * sizeof(float);
+    }
+    hipLaunchKernelGGL(volume_joint_step_kernel, dim3((W + 63) / 64, (H + 3) / 4, D), dim3(64, 4), lds, STREAM, y, slot, taps, x_t,
+                       x_next, x0_out, N, D, H, W, P, stride, G0, G1, G2, kx, k0, kn, lo, hi, clamp_mode, (unsigned)seed,
+                       (unsigned)(seed >> 32), draw, sample);
+    return check_launch("volume_joint_step");
+}
+
+extern "C" int diqt_volume_joint_finish(const float* x, const int* slot, const float* vol, float* mean_io, float* m2_io, float* out_std,
+                                        int s, int S, int D, int H, int W, int P, int stride, int G0, int G1, int G2, float mean,
+                                        float stdv, float min_val, float fill, void* stream) {
+    DIQT_REQUIRE(x && slot && mean_io, DIQT_E_ALIGN, "volume_joint_finish: null pointer");
+    int rc = joint_lattice_ok("volume_joint_finish", D, H, W, P, stride, G0, G1, G2);
+    if (rc) return rc;
+    DIQT_REQUIRE(S > 0 && s >= 0 && s < S, DIQT_E_SHAPE, "volume_joint_finish: sample %d of %d", s, S);
+    DIQT_REQUIRE(!(S == 1 && (m2_io || out_std)) && !(out_std && !m2_io), DIQT_E_SHAPE,
+                 "volume_joint_finish: m2_io and out_std must be NULL for one sample, and a deviation map needs m2_io");
+    DIQT_REQUIRE(!vol || stdv != 0.f, DIQT_E_SHAPE, "volume_joint_finish: std == 0");
+    DIQT_REQUIRE(D <= 65535 && (H + 3) / 4 <= 65535, DIQT_E_SHAPE, "volume_joint_finish: more than 65535 planes / row groups");
+    hipLaunchKernelGGL(volume_joint_finish_kernel, dim3((W + 63) / 64, (H + 3) / 4, D), dim3(64, 4), 0, STREAM, x, slot, vol, mean_io,
+                       m2_io, out_std, s, S, D, H, W, P, stride, G0, G1, G2, mean, stdv, min_val, fill);
+    return check_launch("volume_joint_finish");
 }

@@ -1089,6 +1089,70 @@ class SRUnet256(Unet):
 # ----------------------------------------------------------------------------------------------
 # Imagen: continuous-time DDPM wrapper (imagen_pytorch3D.py:1741-2442)
 # ----------------------------------------------------------------------------------------------
+class WindowDenoiser:
+    """The per-window half of ``Imagen.p_sample_loop``, callable one step at a time (``Imagen.window_denoiser`` makes it): the chain's
+    host tables and the three device pieces a caller needs to run the reverse chain itself -- as ``VolumeInference(joint=True)`` does
+    for one noisy state of a whole volume, fusing the windows' predictions at every step.
+
+    * ``num_steps``; ``coefs``: host fp32 [T,3], the batch-uniform (kx, k0, kn) of x_next = kx x + k0 x0 + kn noise
+      (``ddim_coefficients`` or ``posterior_coefficients``);
+    * ``clamp = (lo, hi, mode)``: what ``p_sample_loop`` hands to ``ops.ddpm_step`` with the prediction -- ``(-inf, inf, 1)`` under dynamic
+      thresholding, the static clamp of the data normalisation otherwise;
+    * ``x0(img, lowres, i, self_cond=None)`` -> fp32 [B,C,P,P,P]: the U-Net at step i's log-SNR (``Imagen.unet_eval``, hipGraph replay
+      included), the objective's x0 conversion and, if configured, per-row dynamic thresholding -- exactly the tensor ``p_sample_loop``
+      passes to ``ops.ddpm_step``;
+    * ``finish(x)``: the final clamp and ``unnormalize_img`` on a tensor of any shape;
+    * ``self_cond``: whether the U-Net takes the previous step's x0."""
+
+    def __init__(self, imagen, unet_number, sampler, sample_steps, eta, cond_scale, unet_context):
+        self.imagen, self.index, self._context = imagen, unet_number - 1, unet_context
+        self.sampler, self.sample_steps, self.eta = sampler, sample_steps, eta
+        self.cond_scale = cast_tuple(cond_scale, len(imagen.unets))[self.index]
+        self.pred_objective = imagen.pred_objectives[self.index]
+        self.dynamic_threshold = bool(imagen.dynamic_thresholding[self.index])
+        self.self_cond = bool(getattr(imagen.unets[self.index], 'self_cond', False))
+        self.lowres_cond = bool(getattr(imagen.unets[self.index], 'lowres_cond', False))
+        tables = self._tables(1)
+        self.coefs = tables[0][:, :, 0].contiguous()                    # [T, 3] on the host
+        self.num_steps = int(self.coefs.shape[0])
+        lo, hi, mode = imagen._clamp_cfg()
+        self.clamp = (-float('inf'), float('inf'), 1) if self.dynamic_threshold else (lo, hi, mode)
+        self._device_tables = {}
+
+    def _tables(self, batch):
+        return Imagen._sampler_tables(self.imagen.noise_schedulers[self.index], batch, self.sampler, self.sample_steps, None, self.eta,
+                                      self.pred_objective)
+
+    @torch.no_grad()
+    def x0(self, img, lowres, i, self_cond=None):
+        imagen = self.imagen
+        B = img.shape[0]
+        if not 0 <= i < self.num_steps:
+            raise ValueError(f"WindowDenoiser.x0: step {i} of {self.num_steps}")
+        key = (B, img.device)
+        if key not in self._device_tables:                               # the [T,B] / [T,2,B] tables of p_sample_loop for this batch size
+            _, conds, x0c, *_ = self._tables(B)
+            self._device_tables[key] = (conds.to(img.device), x0c.to(img.device))
+        conds, x0c = self._device_tables[key]
+        was_training = imagen.training
+        imagen.eval()
+        try:
+            with self._context():
+                imagen.reset_unets_all_one_device(device=img.device)         # as ``sample`` does before it picks the U-Net
+                unet = imagen.unets[self.index]
+                pred = imagen._x0_prediction(unet, img.float().contiguous(), conds[i], x0c[i],
+                                             lowres.float().contiguous() if self.lowres_cond else None,
+                                             self_cond if unet.self_cond else None, None, self.cond_scale, self.pred_objective,
+                                             self.dynamic_threshold)
+        finally:
+            imagen.train(was_training)
+        return pred
+
+    @torch.no_grad()
+    def finish(self, x):
+        return self.imagen._finish_sample(x.contiguous().view(1, -1)).view(x.shape)
+
+
 class Imagen(nn.Module):
     def __init__(
         self, unets, configs, *, image_sizes, min_bound=0, channels=3, timesteps=1000, cond_drop_prob=0.1,
@@ -1235,6 +1299,72 @@ class Imagen(nn.Module):
             if not 0. <= eta <= 1.:
                 raise ValueError(f"eta must lie in [0, 1], got {eta!r}")
 
+    @staticmethod
+    def _sampler_tables(noise_scheduler, batch, sampler, sample_steps, skip_steps, eta, pred_objective):
+        """Host tables of a sampling chain for ``batch`` rows (every row holds the same numbers), CPU fp32: the step coefficients
+        ``coefs`` [T,3,B] of x_next = kx x + k0 x0 + kn noise (``ddim_coefficients`` or ``posterior_coefficients``), the log-SNR
+        conditioning ``conds`` [T,B], the (a, b) of x0 = a x + b pred for a noise / v prediction ``x0c`` [T,2,B] (:343-357), ``last``
+        [T,B] (t_next == 0), and the inpainting loop's re-noise coefficients ``renoise`` [T,2,B] (:324-341) and (alpha, sigma) ``qs``
+        [T,2,B].  ``p_sample_loop`` and ``window_denoiser`` both read these, so the one-call and the step-at-a-time sampler cannot drift."""
+        timesteps = list(noise_scheduler.get_sampling_timesteps(batch, device='cpu', steps=sample_steps))
+        skip_steps = default(skip_steps, 0)
+        if skip_steps > 1:
+            timesteps = timesteps[::skip_steps] + [timesteps[-1]]           # (:2105-2107)
+        if sampler == 'ddim':
+            coefs = torch.stack([torch.stack(noise_scheduler.ddim_coefficients(t, tn, eta)) for t, tn in timesteps])
+        else:
+            coefs = torch.stack([torch.stack(noise_scheduler.posterior_coefficients(t, tn)) for t, tn in timesteps])
+        conds = torch.stack([noise_scheduler.get_condition(t) for t, _ in timesteps])
+        al, sg = log_snr_to_alpha_sigma(conds)
+        al_n, sg_n = log_snr_to_alpha_sigma(torch.stack([noise_scheduler.get_condition(tn) for _, tn in timesteps]))
+        if pred_objective == 'noise':
+            x0c = torch.stack((1. / al.clamp(min=1e-8), -sg / al.clamp(min=1e-8)), dim=1)
+        else:
+            x0c = torch.stack((al, -sg), dim=1)
+        last = torch.stack([(tn == 0) for _, tn in timesteps])                                        # [T, B]
+        renoise = torch.stack((torch.where(last, torch.ones_like(al), al / al_n),
+                               torch.where(last, torch.zeros_like(al), (sg * al_n - sg_n * al) / al_n)), dim=1)
+        return coefs, conds, x0c, last, renoise, torch.stack((al, sg), dim=1)
+
+    def _x0_prediction(self, unet, img, cond, x0c, lowres, self_cond, cond_images, cond_scale, pred_objective, dynamic_threshold):
+        """What a sampling step hands to ``ops.ddpm_step`` as the x0 prediction: one U-Net evaluation at the log-SNR ``cond`` [B], the
+        objective's x0 conversion with ``x0c`` [2,B] (:1996-2003) and, if configured, per-row dynamic thresholding (:2006-2021)."""
+        pred = self.unet_eval(unet, img, cond, cond_images=cond_images, cond_scale=cond_scale, lowres_cond_img=lowres,
+                              self_cond=self_cond)
+        pred = pred.contiguous()
+        if pred_objective != 'x_start':
+            pred = ops.axpby3(img, pred, None, x0c[0], x0c[1], None, 0.0, 0.0, 0)
+        if dynamic_threshold:
+            s = ops.abs_quantile(pred, self.dynamic_thresholding_percentile)
+            s.clamp_(min=1. if self.configs['Data']['norm'] == 'min-max' else float(self.min_bound))
+            pred = ops.dynamic_threshold(pred, s)
+        return pred
+
+    def _finish_sample(self, img):
+        """The end of a chain: the final clamp (:2154-2157) and ``unnormalize_img``.  ``img``: [B, ...]."""
+        lo, hi, mode = self._clamp_cfg()
+        one = torch.ones(img.shape[0], device=img.device)
+        return self.unnormalize_img(ops.axpby3(img, None, None, one, None, None, lo, hi, 1 if mode == 0 else 2))
+
+    def window_denoiser(self, unet_number=2, sampler='ddim', sample_steps=None, eta=0.0, cond_scale=1., inpaint_images=None,
+                        inpaint_masks=None, init_images=None, skip_steps=None, _unet_context=nullcontext):
+        """The per-window half of ``p_sample_loop`` as an object that is called one step at a time -- what
+        ``VolumeInference(..., joint=True)`` drives; see ``WindowDenoiser``.  Inpainting, ``init_images`` and ``skip_steps`` belong to
+        the one-call sampler and are refused here (``ValueError``, before anything touches the device)."""
+        has_inpainting = exists(inpaint_images) and exists(inpaint_masks)
+        self._check_sampler_args(sampler, sample_steps, skip_steps, eta, has_inpainting)
+        if has_inpainting or exists(inpaint_images) or exists(inpaint_masks):
+            raise ValueError("window_denoiser does not inpaint: the joint chain has no per-window re-noising loop")
+        if exists(init_images):
+            raise ValueError("window_denoiser takes no init_images: the joint chain starts from the volume-anchored field")
+        if exists(skip_steps):
+            raise ValueError("window_denoiser takes no skip_steps: thin the chain with sample_steps")
+        if isinstance(unet_number, bool) or int(unet_number) != unet_number or not 1 <= unet_number <= len(self.unets):
+            raise ValueError(f"unet_number must be 1 .. {len(self.unets)}, got {unet_number!r}")
+        if isinstance(self.unets[unet_number - 1], NullUnet):
+            raise ValueError('one cannot sample from null / placeholder unets')
+        return WindowDenoiser(self, int(unet_number), sampler, sample_steps, float(eta), cond_scale, _unet_context)
+
     @torch.no_grad()
     def p_sample_loop(self, unet, shape, *, noise_scheduler, lowres_cond_img=None, cond_images=None, inpaint_images=None,
                       inpaint_masks=None, inpaint_resample_times=5, init_images=None, skip_steps=None, cond_scale=1,
@@ -1270,55 +1400,29 @@ class Imagen(nn.Module):
             inpaint_images = inpaint_images.to(device).float().expand(shape).contiguous()
             mask_f = inpaint_masks.to(device).bool().expand(shape).float().contiguous()
 
-        timesteps = list(noise_scheduler.get_sampling_timesteps(batch, device='cpu', steps=sample_steps))
-        skip_steps = default(skip_steps, 0)
-        if skip_steps > 1:
-            timesteps = timesteps[::skip_steps] + [timesteps[-1]]           # (:2105-2107)
-
-        # host: coefficients of every step, uploaded once  [T, 3, B] ; log-SNR conditioning [T, B]
-        if sampler == 'ddim':
-            coefs = torch.stack([torch.stack(noise_scheduler.ddim_coefficients(t, tn, eta)) for t, tn in timesteps])
-            if eta == 0:                                                    # kn == 0: the step kernel reads one zero tensor, no draw
-                zero = torch.zeros(shape, device=device)
-                step_noise = lambda: zero
-            else:
-                step_noise = draw
+        coefs, conds, x0c, last, renoise, qs = self._sampler_tables(noise_scheduler, batch, sampler, sample_steps, skip_steps, eta,
+                                                                    pred_objective)
+        if sampler == 'ddim' and eta == 0:                                  # kn == 0: the step kernel reads one zero tensor, no draw
+            zero = torch.zeros(shape, device=device)
+            step_noise = lambda: zero
         else:
-            coefs = torch.stack([torch.stack(noise_scheduler.posterior_coefficients(t, tn)) for t, tn in timesteps])
             step_noise = draw
-        conds = torch.stack([noise_scheduler.get_condition(t) for t, _ in timesteps])
-        # x0 from a noise / v prediction (:343-357) and the inpainting re-noise coefficients (:324-341), per step [T, 2, B]
-        al, sg = log_snr_to_alpha_sigma(conds)
-        al_n, sg_n = log_snr_to_alpha_sigma(torch.stack([noise_scheduler.get_condition(tn) for _, tn in timesteps]))
-        if pred_objective == 'noise':
-            x0c = torch.stack((1. / al.clamp(min=1e-8), -sg / al.clamp(min=1e-8)), dim=1)
-        else:
-            x0c = torch.stack((al, -sg), dim=1)
-        last = torch.stack([(tn == 0) for _, tn in timesteps])                                        # [T, B]
-        renoise = torch.stack((torch.where(last, torch.ones_like(al), al / al_n),
-                               torch.where(last, torch.zeros_like(al), (sg * al_n - sg_n * al) / al_n)), dim=1)
-        coefs, conds, x0c, renoise, qs = (t.to(device) for t in (coefs, conds, x0c, renoise, torch.stack((al, sg), dim=1)))
+        coefs, conds, x0c, renoise, qs = (t.to(device) for t in (coefs, conds, x0c, renoise, qs))
         lo, hi, mode = self._clamp_cfg()
         lowres = lowres_cond_img.to(device).float().contiguous() if exists(lowres_cond_img) else None
         inf = float('inf')
 
         noisy_dev, x0_dev = [], []
         x_start = None
-        for i in range(len(timesteps)):
+        for i in range(coefs.shape[0]):
             all_last = bool(last[i].all())
             for r in reversed(range(resample_times)):
                 if has_inpainting:                                                         # (:2119-2123)
                     noised = ops.q_sample(inpaint_images, draw(), qs[i, 0], qs[i, 1])
                     img = ops.mask_blend(img, noised, mask_f)
-                pred = self.unet_eval(unet, img, conds[i], cond_images=cond_images, cond_scale=cond_scale,
-                                      lowres_cond_img=lowres, self_cond=x_start if unet.self_cond else None)
-                pred = pred.contiguous()
-                if pred_objective != 'x_start':                                            # (:1996-2003)
-                    pred = ops.axpby3(img, pred, None, x0c[i, 0], x0c[i, 1], None, 0.0, 0.0, 0)
-                if dynamic_threshold:                                                      # (:2006-2021)
-                    s = ops.abs_quantile(pred, self.dynamic_thresholding_percentile)
-                    s.clamp_(min=1. if self.configs['Data']['norm'] == 'min-max' else float(self.min_bound))
-                    pred = ops.dynamic_threshold(pred, s)
+                pred = self._x0_prediction(unet, img, conds[i], x0c[i], lowres, x_start if unet.self_cond else None, cond_images,
+                                           cond_scale, pred_objective, dynamic_threshold)
+                if dynamic_threshold:
                     img, x_start = ops.ddpm_step(img, pred, step_noise(), coefs[i, 0], coefs[i, 1], coefs[i, 2], -inf, inf, 1)
                 else:
                     img, x_start = ops.ddpm_step(img, pred, step_noise(), coefs[i, 0], coefs[i, 1], coefs[i, 2], lo, hi, mode)
@@ -1331,9 +1435,7 @@ class Imagen(nn.Module):
         # one D2H at the end instead of two per step (:2148-2149); same returned values
         noisy_pred_img = [t.cpu().numpy() for t in noisy_dev]
         pred_img = [t.cpu().numpy() for t in x0_dev]
-        one = torch.ones(batch, device=device)
-        img = ops.axpby3(img, None, None, one, None, None, lo, hi, 1 if mode == 0 else 2)   # final clamp (:2154-2157)
-        return self.unnormalize_img(img), noisy_pred_img, pred_img
+        return self._finish_sample(img), noisy_pred_img, pred_img              # final clamp (:2154-2157)
 
     @torch.no_grad()
     @eval_decorator

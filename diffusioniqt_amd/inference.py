@@ -32,7 +32,17 @@ Beyond the scripts (``blend`` / ``samples``; the defaults leave every line above
   per voxel in ``ops.anchored_noise``), so all windows that cover a voxel start from — and, in a stochastic sampler, are pushed by —
   the same numbers, whatever ``Eval.batch_size`` is, whichever windows the non-zero filter kept and in whatever order or on
   whichever rank they run.  What is left of the disagreement between overlapping windows is what the network does differently with
-  different context; the ``samples = S`` fields are independent of each other and coherent across windows.
+  different context; the ``samples = S`` fields are independent of each other and coherent across windows;
+* ``joint=True`` (with a blend mode and ``noise='anchored'``) removes that remainder at its source: instead of running every window's
+  reverse chain alone and blending finished patches, ONE noisy state of the whole volume is kept and the windows' x0 predictions are
+  fused at EVERY step (MultiDiffusion, Bar-Tal et al. 2023).  The second constructor argument is then a window denoiser
+  (``Imagen.window_denoiser`` / ``ImagenTrainer.window_denoiser``: scalar step coefficients, the clamp, ``x0`` and ``finish``).  Per
+  sample: the state starts as draw 0 of the anchored field; every step gathers the kept windows of the state, evaluates the U-Net on
+  them in ``Eval.batch_size`` batches (N windows x T steps evaluations, as many as the independent windows cost) and ONE
+  ``ops.volume_joint_step`` launch blends the predictions per voxel with the blend weights, takes the sampler step with draw
+  ``i + 1`` and writes the next state in place; ``ops.volume_joint_finish`` applies the fill / background rules and the statistics
+  over the samples.  The draw numbering is ``AnchoredNoise.source``'s, so with stride = patch (no overlap) the joint chain IS the
+  independent one, bit for bit.
 """
 import numpy as np
 import torch
@@ -113,13 +123,15 @@ def sub_volume_origins(origin, factor, sub):
 
 
 class VolumeInference:
-    def __init__(self, configs, sample_fn, nonzero_ratio=0.05, blend=None, sigma_scale=0.125, samples=1, noise=None, seed=0):
+    def __init__(self, configs, sample_fn, nonzero_ratio=0.05, blend=None, sigma_scale=0.125, samples=1, noise=None, seed=0, joint=False):
         """``sample_fn(lr_patches [B,1,S,S,S]) -> hr_patches`` — e.g. ``lambda x: trainer.sample(batch_size=x.shape[0],
         start_image_or_video=x, start_at_unet_number=2)[0]`` (test_all.py:234).  ``blend`` / ``sigma_scale`` / ``samples``: weighted
         overlap blending and multi-sample statistics, see the module docstring.  ``noise='anchored'`` (with ``seed``): every call
         becomes ``sample_fn(lr_patches, noise=source)`` with the volume-anchored source of that batch's windows and sample index —
         e.g. ``lambda x, noise=None: trainer.sample(batch_size=x.shape[0], start_image_or_video=x, start_at_unet_number=2,
-        sampler='ddim', sample_steps=50, noise=noise)[0]``."""
+        sampler='ddim', sample_steps=50, noise=noise)[0]``.  ``joint=True`` (needs a blend mode and ``noise='anchored'``): the second
+        argument is a window denoiser instead -- ``trainer.window_denoiser(sampler='ddim', sample_steps=50)`` -- and the windows are
+        sampled in lockstep on one noisy state of the whole volume, see the module docstring."""
         if noise not in NOISE_MODES:
             raise ValueError(f"VolumeInference: noise must be None or 'anchored', got {noise!r}")
         self.noise, self.seed = noise, int(seed)
@@ -133,6 +145,16 @@ class VolumeInference:
         if blend == 'gaussian' and not sigma_scale > 0:
             raise ValueError(f"VolumeInference: sigma_scale must be positive, got {sigma_scale!r}")
         self.blend, self.sigma_scale, self.samples = blend, float(sigma_scale), int(samples)
+        self.joint = bool(joint)
+        if self.joint:
+            if blend is None or noise != 'anchored':
+                raise ValueError("VolumeInference: joint=True needs a blend mode ('gaussian' or 'constant'), the weights that fuse the "
+                                 "windows' predictions at every step, and noise='anchored', the volume-wide field the one state starts "
+                                 "from and is pushed by")
+            missing = [a for a in ('num_steps', 'coefs', 'clamp', 'x0', 'finish') if not hasattr(sample_fn, a)]
+            if missing:
+                raise ValueError(f"VolumeInference: joint=True takes a window denoiser (Imagen.window_denoiser / "
+                                 f"ImagenTrainer.window_denoiser) as its second argument; {type(sample_fn).__name__} lacks {missing}")
         self.cfg = configs
         self.sample_fn = sample_fn
         self.ratio = nonzero_ratio
@@ -158,7 +180,7 @@ class VolumeInference:
                 raise NotImplementedError("VolumeInference: a blend mode does not split one volume's windows over ranks (that needs a "
                                           "cross-rank merge of the weighted sums) — shard whole volumes across the GPUs instead, one "
                                           "VolumeInference call per volume and rank, as bench.py does")
-            mean, dev = self._blended(lowres_raw, return_std)
+            mean, dev = (self._joint if self.joint else self._blended)(lowres_raw, return_std)
             return (mean, dev) if return_std else mean
         vol = lowres_raw.float().contiguous()
         dev = vol.device
@@ -247,6 +269,59 @@ class VolumeInference:
         taps = torch.from_numpy(blend_taps(P, self.blend, self.sigma_scale)).to(dev)
         return ops.volume_blend(patches, torch.from_numpy(slot.reshape(lattice)).to(dev), taps, vol, self.mean, self.std,
                                 float(min_val), float(fill), self.overlap, want_std)
+
+
+    def _joint(self, lowres_raw, want_std):
+        """``joint=True``: per sample ONE noisy state ``x`` [D,H,W] for the whole volume.  Every step gathers the kept windows of the
+        state (and of the low-res volume, and of the previous fused x0 for a self-conditioned U-Net), lets the window denoiser predict
+        their x0 into one [N,P,P,P] buffer, and ONE ``ops.volume_joint_step`` launch fuses the predictions per voxel, takes the sampler
+        step with draw ``i + 1`` of the anchored field and writes the next state in place.  ``ops.volume_joint_finish`` ends a sample:
+        fill, background reset and the running mean / deviation over the samples."""
+        vol = lowres_raw.float().contiguous()
+        dev = vol.device
+        shape = tuple(vol.shape)
+        P, S, den = self.patch, self.samples, self.sample_fn
+        origins = sliding_window_origins(shape, P, self.overlap)
+        lattice = tuple(len(range(0, s - P + 1, self.overlap)) for s in shape)
+        _, nz = ops.patch_gather(vol, torch.from_numpy(origins).to(dev), P, self.mean, self.std, want_patches=False, want_nonzero=True)
+        keep = (nz.cpu().numpy().astype(np.float64) / float(P ** 3)) >= self.ratio          # data.py:187-191
+        kept = origins[keep]
+        N = kept.shape[0]
+        slot = np.full(origins.shape[0], -1, dtype=np.int32)                                 # candidate order = lattice order
+        slot[keep] = np.arange(N, dtype=np.int32)
+        slot = torch.from_numpy(slot.reshape(lattice)).to(dev)
+        taps = torch.from_numpy(blend_taps(P, self.blend, self.sigma_scale)).to(dev)
+        per_call = 1 if self.block_mode else self.batch
+        batches = [(lo, torch.from_numpy(np.ascontiguousarray(kept[lo:lo + per_call])).to(dev)) for lo in range(0, N, per_call)]
+        sub_shape = (self.factor ** 3, 1, self.sub, self.sub, self.sub)
+        split = (lambda w: convertVolume2subVolume(w, target_shape=sub_shape)) if self.block_mode else (lambda w: w)
+        coefs = den.coefs.tolist()
+        lo_c, hi_c, mode_c = den.clamp
+        self_cond = bool(getattr(den, 'self_cond', False))
+        mean32, std32 = np.float32(self.mean), np.float32(self.std)
+        fill = (np.float32(0.) - mean32) / std32
+        min_val = (np.float32(float(ops.min_value(vol).item())) - mean32) / std32
+        y = torch.empty((N, P, P, P), dtype=torch.float32, device=dev)                       # reused by every step of every sample
+        x0_vol = torch.empty(shape, dtype=torch.float32, device=dev) if self_cond else None
+        mean_io = m2_io = out_std = None
+        for s in range(S):
+            x = ops.volume_joint_init(shape, self.seed, sample=s, device=dev)               # draw 0
+            for i in range(den.num_steps):
+                for lo, idx in batches:
+                    n = idx.shape[0]
+                    xw = split(ops.patch_gather(x, idx, P, 0., 1.)[0])                       # (v - 0) / 1: the state's own bits
+                    lw = split(ops.patch_gather(vol, idx, P, self.mean, self.std)[0])
+                    sc = split(ops.patch_gather(x0_vol, idx, P, 0., 1.)[0]) if self_cond and i > 0 else None
+                    pred = den.x0(xw, lw, i, self_cond=sc).float()
+                    if self.block_mode:                                                   # test_all.py:229-231, 265-266
+                        pred = merge_sub_volumes(pred, original_shape=(1, 1, P, P, P))
+                    y[lo:lo + n] = pred.reshape(n, P, P, P)
+                kx, k0, kn = coefs[i]
+                ops.volume_joint_step(y, slot, taps, x, kx, k0, kn, lo_c, hi_c, mode_c, self.overlap, self.seed, draw=i + 1, sample=s,
+                                      out=x, x0_out=x0_vol)
+            mean_io, m2_io, out_std = ops.volume_joint_finish(den.finish(x), slot, vol, P, self.overlap, self.mean, self.std,
+                                                              float(min_val), float(fill), s, S, mean_io, m2_io, want_std)
+        return mean_io, out_std
 
 
 def eval_crop(size0):

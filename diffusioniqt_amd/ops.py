@@ -2362,6 +2362,105 @@ def anchored_noise(origins, C, P, D, H, W, seed, draw=0, sample=0, raw=False, de
     return out
 
 
+def _noise_key(who, seed, draw, sample):
+    seed, draw, sample = int(seed), int(draw), int(sample)
+    if not (0 <= seed < 2 ** 64 and 0 <= draw < 2 ** 32 and 0 <= sample < 2 ** 32):
+        raise ValueError(f"{who}: seed must fit 64 bits, draw and sample 32 bits (unsigned), got {seed}, {draw}, {sample}")
+    return seed, draw, sample
+
+
+def _joint_lattice(who, slot, shape, P, stride):
+    """The host-side shape rules shared by the two joint-sampling launches (the entry checks the lattice again)."""
+    _chk_int(slot)
+    if slot.ndim != 3 or len(shape) != 3:
+        raise ValueError(f"{who}: expected slot [G0,G1,G2] and a [D,H,W] volume")
+    stride = int(stride)
+    if stride < 1 or P < 1 or any(P > s for s in shape):
+        raise ValueError(f"{who}: windows of edge {P} with stride {stride} do not fit the volume {tuple(shape)}")
+    if tuple(slot.shape) != tuple(len(range(0, s - P + 1, stride)) for s in shape):
+        raise ValueError(f"{who}: slot {tuple(slot.shape)} is not the origin lattice of {tuple(shape)}, P {P}, stride {stride}")
+    return stride
+
+
+def volume_joint_init(shape, seed, sample=0, draw=0, device=None):
+    """The initial state of a joint chain: fp32 [D,H,W], the volume-anchored normal of ``draw`` (channel 0) at every voxel -- the
+    ``x_t == NULL`` launch of ``diqt_volume_joint_step``, bit for bit what ``anchored_noise`` hands to a window there."""
+    shape = tuple(int(s) for s in shape)
+    if len(shape) != 3 or min(shape) < 1:
+        raise ValueError(f"volume_joint_init: shape must be a positive (D, H, W), got {shape!r}")
+    seed, draw, sample = _noise_key("volume_joint_init", seed, draw, sample)
+    if not torch.cuda.is_available():
+        raise RuntimeError("diffusioniqt_amd.ops.volume_joint_init runs on the MI355X only (no CPU fallback)")
+    device = torch.device('cuda' if device is None else device)
+    with torch.cuda.device(device):
+        out = torch.empty(shape, dtype=torch.float32, device=device)
+        _lib.call("diqt_volume_joint_step", None, None, None, None, out, None, 0, *shape, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0, 0.0, 0.0, 0,
+                  seed, draw, sample, _stream())
+    return out
+
+
+def volume_joint_step(y, slot, taps, x_t, kx, k0, kn, lo, hi, clamp_mode, stride, seed, draw, sample=0, out=None, x0_out=None):
+    """One reverse step of the joint chain of a whole volume (include/diqt.h, diqt_volume_joint_step): ``y`` [N,P,P,P] are the kept
+    windows' x0 predictions of this step in candidate order, ``slot`` / ``taps`` / ``stride`` as in ``volume_blend``, ``x_t`` [D,H,W] the
+    state.  Per covered voxel x0 = the weighted mean of the clamped predictions (``clamp_mode`` 0: max(y, lo); 1: clip(y, lo, hi)) and
+    x_next = kx x_t + k0 x0 + kn n with n the volume-anchored normal of (seed, draw, sample); uncovered voxels keep ``x_t``.  ``out``:
+    where x_next goes (``x_t`` itself for an in-place step; None: a new tensor); ``x0_out`` (optional [D,H,W]) receives the fused x0
+    (0 where uncovered).  Returns ``out``.  One launch, bit-reproducible."""
+    _chk(y, taps, x_t)
+    if y.ndim != 4 or x_t.ndim != 3 or taps.ndim != 1:
+        raise ValueError("volume_joint_step: expected y [N,P,P,P], slot [G0,G1,G2], taps [P] and x_t [D,H,W]")
+    if not (y.is_contiguous() and taps.is_contiguous() and x_t.is_contiguous()):
+        raise RuntimeError("volume_joint_step: tensors must be contiguous")
+    N, P = y.shape[:2]
+    if tuple(y.shape[1:]) != (P, P, P) or taps.shape[0] != P:
+        raise ValueError(f"volume_joint_step: y {tuple(y.shape)} / taps {tuple(taps.shape)} are not cubic windows of one size")
+    stride = _joint_lattice("volume_joint_step", slot, x_t.shape, P, stride)
+    if int(clamp_mode) not in (0, 1):
+        raise ValueError(f"volume_joint_step: clamp_mode must be 0 (min) or 1 (box), got {clamp_mode!r}")
+    seed, draw, sample = _noise_key("volume_joint_step", seed, draw, sample)
+    if slot.numel() and int(slot.max()) >= N:                     # the kernel indexes `y` by it
+        raise ValueError(f"volume_joint_step: slot names window {int(slot.max())} of {N}")
+    if out is None:
+        out = torch.empty_like(x_t)
+    for t, name in ((out, 'out'), (x0_out, 'x0_out')):
+        if t is not None:
+            _chk(t)
+            if t.shape != x_t.shape or not t.is_contiguous():
+                raise ValueError(f"volume_joint_step: {name} must be a contiguous tensor of x_t's shape")
+    _lib.call("diqt_volume_joint_step", y if N else None, slot, taps, x_t, out, x0_out, N, *x_t.shape, P, stride, *slot.shape,
+              float(kx), float(k0), float(kn), float(lo), float(hi), int(clamp_mode), seed, draw, sample, _stream())
+    return out
+
+
+def volume_joint_finish(x, slot, vol, P, stride, mean, std, min_val, fill, s, S, mean_io=None, m2_io=None, want_std=False):
+    """The end of sample ``s`` of ``S`` joint chains (include/diqt.h, diqt_volume_joint_finish): the finished state ``x`` [D,H,W] with
+    ``fill`` where no kept window of ``slot`` covers and ``min_val`` on the background of the raw ``vol`` enters the running Welford
+    pair ``(mean_io, m2_io)`` (made here for sample 0, otherwise the pair the previous call returned; ``m2_io`` exists for S >= 2 only).
+    Returns ``(mean_io, m2_io, std)`` with ``std`` the unbiased deviation map after the last sample when ``want_std``, else None."""
+    _chk(x, vol)
+    if x.ndim != 3 or x.shape != vol.shape or not (x.is_contiguous() and vol.is_contiguous()):
+        raise ValueError("volume_joint_finish: x and vol must be contiguous [D,H,W] tensors of one shape")
+    stride = _joint_lattice("volume_joint_finish", slot, x.shape, int(P), stride)
+    s, S = int(s), int(S)
+    if not 0 <= s < S:
+        raise ValueError(f"volume_joint_finish: sample {s} of {S}")
+    if want_std and S < 2:
+        raise ValueError("volume_joint_finish: a deviation map needs at least 2 samples")
+    if s == 0:
+        mean_io = torch.empty_like(x)
+        m2_io = torch.empty_like(x) if S > 1 else None
+    else:
+        if mean_io is None or m2_io is None:
+            raise ValueError("volume_joint_finish: samples after the first continue the (mean_io, m2_io) pair of the previous call")
+        _chk(mean_io, m2_io)
+        if mean_io.shape != x.shape or m2_io.shape != x.shape or not (mean_io.is_contiguous() and m2_io.is_contiguous()):
+            raise ValueError("volume_joint_finish: mean_io / m2_io must be contiguous tensors of x's shape")
+    dev = torch.empty_like(x) if want_std and s == S - 1 else None
+    _lib.call("diqt_volume_joint_finish", x, slot, vol, mean_io, m2_io, dev, s, S, *x.shape, int(P), stride, *slot.shape, float(mean),
+              float(std), float(min_val), float(fill), _stream())
+    return mean_io, m2_io, dev
+
+
 def patch_pair_crop(lr_vols, hr_vols, sel, P, mode, mean, std):
     """data.py:119-132: crop + normalise ``sel[n] = (volume, i0, j0, k0)`` patch pairs out of the HBM-resident [V,D,H,W]
     volume stacks in one launch.  Returns (lr [n,P,P,P], hr [n,P,P,P])."""

@@ -923,6 +923,11 @@ class ImagenTrainer(nn.Module):
             output = self.imagen.sample(*args, device=self.device, **kwargs)
         return output
 
+    def window_denoiser(self, *args, use_non_ema=False, **kwargs):
+        """``Imagen.window_denoiser`` with the U-Net choice of ``sample``: every ``x0`` call runs inside ``use_ema_unets()`` (the EMA
+        weights) unless ``use_non_ema``."""
+        return self.imagen.window_denoiser(*args, _unet_context=nullcontext if use_non_ema else self.use_ema_unets, **kwargs)
+
     def _autocast(self):
         if self.mixed_precision == 'no' or not torch.cuda.is_available():
             return nullcontext()

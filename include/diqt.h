@@ -600,6 +600,27 @@ int diqt_volume_blend(const float* patches, const int* slot, const float* taps, 
  * The caller guarantees that every window lies inside the volume (the origins are on the device; the entry cannot look at them). */
 int diqt_anchored_noise(const int* origins, int B, int C, int P, int D, int H, int W, unsigned long long seed, unsigned draw,
                         unsigned sample, int raw, void* out, void* stream);
+/* Lockstep joint sampling of the overlapping windows (MultiDiffusion, Bar-Tal et al. 2023): ONE reverse step of the noisy state of the
+ * whole [D][H][W] volume.  y[N][P][P][P] holds the kept windows' x0 predictions of this step in candidate order; slot / taps (DEVICE) /
+ * stride / G* are diqt_volume_blend's, with the same lattice check.  Per output voxel, over the covering kept windows in candidate
+ * order: num = fma(w, c(y), num), den += w with w = (taps[i] taps[j]) taps[k] and c the clamp of diqt_ddpm_step (clamp_mode 0:
+ * max(y, lo); 1: min(max(y, lo), hi)) -- diqt_volume_blend's arithmetic for S = 1.  Covered voxel (den != 0): x0 = num / den,
+ * x_next = kx x_t + k0 x0 + kn n in diqt_ddpm_step's operation order, n = the normal of diqt_anchored_noise for channel 0 at (seed,
+ * z, y, x, draw, sample), or 0 when kn == 0; x0_out (may be NULL) = x0.  Uncovered voxel: x_next = x_t, x0_out = 0.  x_next may alias
+ * x_t.  x_t == NULL is the initial state: x_next = that normal of `draw` at EVERY voxel, bit for bit diqt_anchored_noise's, and the
+ * window arguments (y, slot, taps, x0_out, N, P, stride, G*, the coefficients and the clamp) are ignored.  One launch, gather-side,
+ * no atomics: bit-reproducible.                                                                                                  */
+int diqt_volume_joint_step(const float* y, const int* slot, const float* taps, const float* x_t, float* x_next, float* x0_out, int N,
+                           int D, int H, int W, int P, int stride, int G0, int G1, int G2, float kx, float k0, float kn, float lo,
+                           float hi, int clamp_mode, unsigned long long seed, unsigned draw, unsigned sample, void* stream);
+/* The end of sample s (0-based) of S joint chains: per voxel r = min_val where vol (RAW, may be NULL) has (vol - mean) / std ==
+ * min_val (diqt_background_reset's expression), else x (the finished state) where a kept window (slot >= 0) covers the voxel, else
+ * `fill`; then diqt_volume_blend's Welford update in sample order, delta = r - m; m += delta / (s + 1); m2 = fma(delta, r - m, m2)
+ * on (mean_io, m2_io), which sample 0 initialises (they are not read then).  With s == S - 1 and out_std non-NULL, out_std =
+ * sqrt(m2 / (S - 1)).  m2_io and out_std must be NULL for S == 1; m2_io may be NULL when no deviation map is wanted.            */
+int diqt_volume_joint_finish(const float* x, const int* slot, const float* vol, float* mean_io, float* m2_io, float* out_std, int s,
+                             int S, int D, int H, int W, int P, int stride, int G0, int G1, int G2, float mean, float stdv,
+                             float min_val, float fill, void* stream);
 
 /* ---- training data path + validation metrics on the device ----------------------------------------------
  * data.py:88-137 supervisedIQT.__getitem__: crop a P^3 patch pair out of HBM-resident [V][D][H][W] low-res / high-res volume
