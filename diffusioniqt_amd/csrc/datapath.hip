@@ -540,6 +540,38 @@ __global__ __launch_bounds__(256) void volume_joint_step_kernel(const float* __r
     x_next[v] = sampler_update(kx, xt, k0, x0, kn, n);
 }
 
+// One step of a second-order MULTISTEP chain (DPM-Solver++ 2M) on the same state: the third operand of the update is the fused x0
+// of the previous step, x_next = kx x_t + k0 x0 + kp x0_prev, not a normal -- no Philox, no seed.  The walk, the clamp and
+// sampler_update are the step kernel's own, so with kp = 0 the two kernels return the same bits, and at stride = patch the chain is
+// ddpm_step_kernel's with the previous x0 as its third operand.  x0_prev == NULL stands for zeros (step 0).  x_next may alias x_t and
+// x0_out may alias x0_prev (no __restrict__ on the four): every thread reads its own voxel of both, then writes it.
+__global__ __launch_bounds__(256) void volume_joint_multistep_kernel(const float* __restrict__ y, const int* __restrict__ slot,
+                                                                     const float* __restrict__ taps, const float* x_t,
+                                                                     const float* x0_prev, float* x_next, float* x0_out, int N, int D,
+                                                                     int H, int W, int P, int stride, int G0, int G1, int G2, float kx,
+                                                                     float k0, float kp, float lo, float hi, int clamp_mode) {
+    extern __shared__ float tp[];                      // [P]
+    for (int e = threadIdx.y * 64 + threadIdx.x; e < P; e += 256) tp[e] = taps[e];
+    __syncthreads();
+    const int x = blockIdx.x * 64 + threadIdx.x;
+    const int h = __builtin_amdgcn_readfirstlane(blockIdx.y * 4 + threadIdx.y), d = blockIdx.z;
+    if (h >= H || x >= W) return;
+    const size_t v = ((size_t)d * H + h) * W + x;
+    float num, den;
+    window_walk(y, slot, taps, tp, N, P, stride, G1, G2, d, h, x, covering(d, h, x, P, stride, G0, G1, G2),
+                StepClamp{lo, hi, clamp_mode}, num, den);
+    const float xt = x_t[v];
+    if (den == 0.f) {
+        x_next[v] = xt;
+        x0_out[v] = 0.f;
+        return;
+    }
+    const float x0 = num / den;
+    const float prev = x0_prev ? x0_prev[v] : 0.f;
+    x0_out[v] = x0;
+    x_next[v] = sampler_update(kx, xt, k0, x0, kp, prev);
+}
+
 // The end of sample s of S: r = min_val on the background (background_reset_kernel's expression on the RAW vol), else x where a kept
 // window covers the voxel, else fill; then volume_blend_kernel's Welford update of (mean_io, m2_io) with r, and after the last sample
 // the unbiased deviation.  Sample 0 initialises the running pair (nothing is read from mean_io / m2_io then).
@@ -831,6 +863,22 @@ extern "C" int diqt_volume_joint_step(const float* y, const int* slot, const flo
                        x_next, x0_out, N, D, H, W, P, stride, G0, G1, G2, kx, k0, kn, lo, hi, clamp_mode, (unsigned)seed,
                        (unsigned)(seed >> 32), draw, sample);
     return check_launch("volume_joint_step");
+}
+
+extern "C" int diqt_volume_joint_multistep(const float* y, const int* slot, const float* taps, const float* x_t, const float* x0_prev,
+                                           float* x_next, float* x0_out, int N, int D, int H, int W, int P, int stride, int G0, int G1,
+                                           int G2, float kx, float k0, float kp, float lo, float hi, int clamp_mode, void* stream) {
+    DIQT_REQUIRE(x_t && x_next && x0_out && slot && taps && (y || N == 0), DIQT_E_ALIGN, "volume_joint_multistep: null pointer");
+    DIQT_REQUIRE(D > 0 && H > 0 && W > 0, DIQT_E_SHAPE, "volume_joint_multistep: bad shape");
+    DIQT_REQUIRE(D <= 65535 && (H + 3) / 4 <= 65535, DIQT_E_SHAPE, "volume_joint_multistep: more than 65535 planes / row groups");
+    DIQT_REQUIRE(N >= 0, DIQT_E_SHAPE, "volume_joint_multistep: windows %d", N);
+    int rc = joint_lattice_ok("volume_joint_multistep", D, H, W, P, stride, G0, G1, G2);
+    if (rc) return rc;
+    DIQT_REQUIRE(clamp_mode == 0 || clamp_mode == 1, DIQT_E_UNSUPPORTED, "volume_joint_multistep: clamp_mode %d (0 = min, 1 = box)",
+                 clamp_mode);
+    hipLaunchKernelGGL(volume_joint_multistep_kernel, dim3((W + 63) / 64, (H + 3) / 4, D), dim3(64, 4), (size_t)P * sizeof(float), STREAM,
+                       y, slot, taps, x_t, x0_prev, x_next, x0_out, N, D, H, W, P, stride, G0, G1, G2, kx, k0, kp, lo, hi, clamp_mode);
+    return check_launch("volume_joint_multistep");
 }
 
 extern "C" int diqt_volume_joint_finish(const float* x, const int* slot, const float* vol, float* mean_io, float* m2_io, float* out_std,

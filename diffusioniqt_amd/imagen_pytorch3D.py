@@ -169,6 +169,10 @@ class GaussianDiffusionContinuousTimes(nn.Module):
         k0 = alpha' - kx alpha.  ``eta = 1`` is algebraically ``posterior_coefficients`` (mean and variance), ``eta = 0`` the deterministic
         sampler.  The fp32 log-SNR values are the ones the network is conditioned on; the algebra on them runs in float64 (at eta = 1 it
         has the cancellation 1 - c that the fp32 ancestral form carries) and the results are cast to fp32 for the step kernel."""
+        return tuple(k.float() for k in self._ddim_coefficients64(t, t_next, eta))
+
+    def _ddim_coefficients64(self, t, t_next, eta):
+        """``ddim_coefficients`` before the cast to fp32."""
         log_snr, log_snr_next = self.log_snr(t).double(), self.log_snr(t_next).double()
         alpha, sigma = log_snr_to_alpha_sigma(log_snr)
         alpha_next, sigma_next = log_snr_to_alpha_sigma(log_snr_next)
@@ -177,7 +181,32 @@ class GaussianDiffusionContinuousTimes(nn.Module):
         kx = torch.sqrt(((sigma_next ** 2) - s ** 2).clamp(min=0.)) / sigma
         k0 = alpha_next - kx * alpha
         kn = s * (t_next != 0).double()
-        return kx.float(), k0.float(), kn.float()
+        return kx, k0, kn
+
+    def dpmpp2m_coefficients(self, timesteps):
+        """DPM-Solver++ 2M (Lu et al. 2022, algorithm 2: the second-order multistep solver of the data-prediction ODE) on the contiguous
+        chain ``timesteps`` = [(t_i, t_i')] of [B] CPU tensors, folded into x_next = kx*x_t + k0*x0_i + kp*x0_{i-1}: fp32 [T,3,B].  With
+        lambda = log_snr / 2, h_i = lambda(t_i') - lambda(t_i), r = h_{i-1} / h_i and (kx, k0') the deterministic DDIM pair of the
+        step (the first-order solver: kx = sigma'/sigma, k0' = -alpha' expm1(-h)), the update uses D = (1 + 1/(2r)) x0_i - x0_{i-1}/(2r)
+        in the place of x0_i: k0 = k0' (1 + 1/(2r)), kp = -k0'/(2r), so k0 + kp = k0' and a constant x0 makes the step first-order.
+        The first step has no history and the LAST step is first-order too, always: the last interval of linspace(1, 0, K + 1) is a
+        large log-SNR jump (h about 2.6 at K = 10 on the cosine schedule), over which the linear extrapolation of x0 does more harm
+        than good -- without it the solver is worse than DDIM on this time grid.  Those two rows are ``ddim_coefficients(t, t', 0)``
+        bit for bit with kp = 0.  As there, the fp32 log-SNR values the network is conditioned on are widened to float64, the algebra
+        runs in float64 and the results are cast to fp32."""
+        T = len(timesteps)
+        lam = [(self.log_snr(t).double() / 2, self.log_snr(tn).double() / 2) for t, tn in timesteps]
+        rows = []
+        for i, (t, tn) in enumerate(timesteps):
+            kx, k0, _ = self._ddim_coefficients64(t, tn, 0.)
+            if i == 0 or i == T - 1:
+                kp = torch.zeros_like(k0)
+            else:
+                r = (lam[i - 1][1] - lam[i - 1][0]) / (lam[i][1] - lam[i][0])
+                kp = -k0 / (2 * r)
+                k0 = k0 * (1 + 1 / (2 * r))
+            rows.append(torch.stack((kx.float(), k0.float(), kp.float())))
+        return torch.stack(rows)
 
     def q_posterior(self, x_start, x_t, t, *, t_next=None):
         t_next = default(t_next, lambda: (t - 1. / self.num_timesteps).clamp(min=0.))
@@ -1096,6 +1125,8 @@ class WindowDenoiser:
 
     * ``num_steps``; ``coefs``: host fp32 [T,3], the batch-uniform (kx, k0, kn) of x_next = kx x + k0 x0 + kn noise
       (``ddim_coefficients`` or ``posterior_coefficients``);
+    * ``multistep``: True for ``sampler='dpmpp2m'``, whose ``coefs`` rows are the (kx, k0, kp) of x_next = kx x + k0 x0 + kp x0_prev
+      (``dpmpp2m_coefficients``) -- the caller keeps the previous step's fused x0 and draws no step noise;
     * ``clamp = (lo, hi, mode)``: what ``p_sample_loop`` hands to ``ops.ddpm_step`` with the prediction -- ``(-inf, inf, 1)`` under dynamic
       thresholding, the static clamp of the data normalisation otherwise;
     * ``x0(img, lowres, i, self_cond=None)`` -> fp32 [B,C,P,P,P]: the U-Net at step i's log-SNR (``Imagen.unet_eval``, hipGraph replay
@@ -1107,6 +1138,7 @@ class WindowDenoiser:
     def __init__(self, imagen, unet_number, sampler, sample_steps, eta, cond_scale, unet_context):
         self.imagen, self.index, self._context = imagen, unet_number - 1, unet_context
         self.sampler, self.sample_steps, self.eta = sampler, sample_steps, eta
+        self.multistep = sampler == 'dpmpp2m'
         self.cond_scale = cast_tuple(cond_scale, len(imagen.unets))[self.index]
         self.pred_objective = imagen.pred_objectives[self.index]
         self.dynamic_threshold = bool(imagen.dynamic_thresholding[self.index])
@@ -1286,8 +1318,8 @@ class Imagen(nn.Module):
     @staticmethod
     def _check_sampler_args(sampler, sample_steps, skip_steps, eta, has_inpainting):
         """The argument rules of ``sampler`` / ``sample_steps`` / ``eta`` (host only: nothing has touched the device when these raise)."""
-        if sampler not in ('ddpm', 'ddim'):
-            raise ValueError(f"sampler must be 'ddpm' or 'ddim', got {sampler!r}")
+        if sampler not in ('ddpm', 'ddim', 'dpmpp2m'):
+            raise ValueError(f"sampler must be 'ddpm', 'ddim' or 'dpmpp2m', got {sampler!r}")
         if exists(sample_steps):
             if exists(skip_steps):
                 raise ValueError("sample_steps and skip_steps both thin the chain: give one of them")
@@ -1298,11 +1330,20 @@ class Imagen(nn.Module):
                 raise ValueError("sampler='ddim' does not inpaint: the re-noising schedule of the inpainting loop is the ancestral one")
             if not 0. <= eta <= 1.:
                 raise ValueError(f"eta must lie in [0, 1], got {eta!r}")
+        if sampler == 'dpmpp2m':
+            if has_inpainting:
+                raise ValueError("sampler='dpmpp2m' does not inpaint: the re-noising schedule of the inpainting loop is the ancestral one")
+            if eta != 0:
+                raise ValueError(f"sampler='dpmpp2m' is deterministic: eta must be 0, got {eta!r}")
+            if exists(skip_steps):
+                raise ValueError("sampler='dpmpp2m' takes no skip_steps: the thinned pairs are not a contiguous chain, so the previous "
+                                 "step's x0 is no history of the next; thin the chain with sample_steps")
 
     @staticmethod
     def _sampler_tables(noise_scheduler, batch, sampler, sample_steps, skip_steps, eta, pred_objective):
         """Host tables of a sampling chain for ``batch`` rows (every row holds the same numbers), CPU fp32: the step coefficients
-        ``coefs`` [T,3,B] of x_next = kx x + k0 x0 + kn noise (``ddim_coefficients`` or ``posterior_coefficients``), the log-SNR
+        ``coefs`` [T,3,B] of x_next = kx x + k0 x0 + kn noise (``ddim_coefficients`` or ``posterior_coefficients``; for ``'dpmpp2m'``
+        the third operand is the previous step's x0, ``dpmpp2m_coefficients``), the log-SNR
         conditioning ``conds`` [T,B], the (a, b) of x0 = a x + b pred for a noise / v prediction ``x0c`` [T,2,B] (:343-357), ``last``
         [T,B] (t_next == 0), and the inpainting loop's re-noise coefficients ``renoise`` [T,2,B] (:324-341) and (alpha, sigma) ``qs``
         [T,2,B].  ``p_sample_loop`` and ``window_denoiser`` both read these, so the one-call and the step-at-a-time sampler cannot drift."""
@@ -1310,7 +1351,9 @@ class Imagen(nn.Module):
         skip_steps = default(skip_steps, 0)
         if skip_steps > 1:
             timesteps = timesteps[::skip_steps] + [timesteps[-1]]           # (:2105-2107)
-        if sampler == 'ddim':
+        if sampler == 'dpmpp2m':
+            coefs = noise_scheduler.dpmpp2m_coefficients(timesteps)
+        elif sampler == 'ddim':
             coefs = torch.stack([torch.stack(noise_scheduler.ddim_coefficients(t, tn, eta)) for t, tn in timesteps])
         else:
             coefs = torch.stack([torch.stack(noise_scheduler.posterior_coefficients(t, tn)) for t, tn in timesteps])
@@ -1378,7 +1421,10 @@ class Imagen(nn.Module):
         ``sample_steps=K`` walks ``linspace(1, 0, K + 1)`` instead of the schedule's ``num_timesteps`` (either sampler).
         ``sampler='ddim'`` replaces the posterior coefficients by ``ddim_coefficients(t, t_next, eta)`` in the SAME step kernel; the x0
         conversion, the clamp and dynamic thresholding are the ancestral branch's.  With ``eta == 0`` the loop consumes one draw, the
-        initial image (the kernel's noise operand is one zero tensor); with ``eta > 0`` one more per step, as the ancestral sampler."""
+        initial image (the kernel's noise operand is one zero tensor); with ``eta > 0`` one more per step, as the ancestral sampler.
+        ``sampler='dpmpp2m'`` is the second-order multistep solver (``dpmpp2m_coefficients``; ``eta`` 0, no ``skip_steps``, no
+        inpainting): still one U-Net evaluation and the SAME step kernel per step, whose third operand is now the clamped (and, if
+        configured, thresholded) x0 the previous step returned -- one zero tensor on step 0.  It consumes one draw, the initial image."""
         if pred_objective not in ('noise', 'x_start', 'v'):
             raise ValueError(f'unknown objective {pred_objective}')
         has_inpainting = exists(inpaint_images) and exists(inpaint_masks)                  # (:2090-2091)
@@ -1402,7 +1448,8 @@ class Imagen(nn.Module):
 
         coefs, conds, x0c, last, renoise, qs = self._sampler_tables(noise_scheduler, batch, sampler, sample_steps, skip_steps, eta,
                                                                     pred_objective)
-        if sampler == 'ddim' and eta == 0:                                  # kn == 0: the step kernel reads one zero tensor, no draw
+        multistep = sampler == 'dpmpp2m'
+        if multistep or (sampler == 'ddim' and eta == 0):                   # kn == 0: the step kernel reads one zero tensor, no draw
             zero = torch.zeros(shape, device=device)
             step_noise = lambda: zero
         else:
@@ -1422,10 +1469,11 @@ class Imagen(nn.Module):
                     img = ops.mask_blend(img, noised, mask_f)
                 pred = self._x0_prediction(unet, img, conds[i], x0c[i], lowres, x_start if unet.self_cond else None, cond_images,
                                            cond_scale, pred_objective, dynamic_threshold)
+                third = x_start if multistep and i > 0 else step_noise()      # 'dpmpp2m': the previous step's clamped x0
                 if dynamic_threshold:
-                    img, x_start = ops.ddpm_step(img, pred, step_noise(), coefs[i, 0], coefs[i, 1], coefs[i, 2], -inf, inf, 1)
+                    img, x_start = ops.ddpm_step(img, pred, third, coefs[i, 0], coefs[i, 1], coefs[i, 2], -inf, inf, 1)
                 else:
-                    img, x_start = ops.ddpm_step(img, pred, step_noise(), coefs[i, 0], coefs[i, 1], coefs[i, 2], lo, hi, mode)
+                    img, x_start = ops.ddpm_step(img, pred, third, coefs[i, 0], coefs[i, 1], coefs[i, 2], lo, hi, mode)
                 if has_inpainting and not (r == 0 or all_last):                            # (:2139-2146)
                     img = ops.axpby3(img, draw(), None, renoise[i, 0], renoise[i, 1], None, 0.0, 0.0, 0)
             noisy_dev.append(img)

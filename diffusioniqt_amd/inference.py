@@ -42,7 +42,11 @@ Beyond the scripts (``blend`` / ``samples``; the defaults leave every line above
   ``ops.volume_joint_step`` launch blends the predictions per voxel with the blend weights, takes the sampler step with draw
   ``i + 1`` and writes the next state in place; ``ops.volume_joint_finish`` applies the fill / background rules and the statistics
   over the samples.  The draw numbering is ``AnchoredNoise.source``'s, so with stride = patch (no overlap) the joint chain IS the
-  independent one, bit for bit.
+  independent one, bit for bit;
+* ``sampler='dpmpp2m'`` (DPM-Solver++ 2M, the second-order multistep solver; ``Imagen.p_sample_loop``) works in every mode above: the
+  non-joint modes only pass it to ``sample``; a joint chain made with ``window_denoiser(sampler='dpmpp2m', sample_steps=K)`` keeps the
+  fused x0 volume of the previous step and takes ``ops.volume_joint_multistep``, x_next = kx x + k0 x0 + kp x0_prev, per step.  It is
+  deterministic after draw 0, and at stride = patch again the independent chain bit for bit.
 """
 import numpy as np
 import torch
@@ -130,8 +134,9 @@ class VolumeInference:
         becomes ``sample_fn(lr_patches, noise=source)`` with the volume-anchored source of that batch's windows and sample index —
         e.g. ``lambda x, noise=None: trainer.sample(batch_size=x.shape[0], start_image_or_video=x, start_at_unet_number=2,
         sampler='ddim', sample_steps=50, noise=noise)[0]``.  ``joint=True`` (needs a blend mode and ``noise='anchored'``): the second
-        argument is a window denoiser instead -- ``trainer.window_denoiser(sampler='ddim', sample_steps=50)`` -- and the windows are
-        sampled in lockstep on one noisy state of the whole volume, see the module docstring."""
+        argument is a window denoiser instead -- ``trainer.window_denoiser(sampler='ddim', sample_steps=50)`` or, second order,
+        ``trainer.window_denoiser(sampler='dpmpp2m', sample_steps=16)`` -- and the windows are sampled in lockstep on one noisy state
+        of the whole volume, see the module docstring."""
         if noise not in NOISE_MODES:
             raise ValueError(f"VolumeInference: noise must be None or 'anchored', got {noise!r}")
         self.noise, self.seed = noise, int(seed)
@@ -276,7 +281,9 @@ class VolumeInference:
         state (and of the low-res volume, and of the previous fused x0 for a self-conditioned U-Net), lets the window denoiser predict
         their x0 into one [N,P,P,P] buffer, and ONE ``ops.volume_joint_step`` launch fuses the predictions per voxel, takes the sampler
         step with draw ``i + 1`` of the anchored field and writes the next state in place.  ``ops.volume_joint_finish`` ends a sample:
-        fill, background reset and the running mean / deviation over the samples."""
+        fill, background reset and the running mean / deviation over the samples.  A multistep denoiser (``sampler='dpmpp2m'``,
+        ``den.multistep``) takes ``ops.volume_joint_multistep`` instead: the third operand of the update is the fused x0 volume of the
+        previous step (the one self-conditioning reads), kept and overwritten in place, and only draw 0 of the field is used."""
         vol = lowres_raw.float().contiguous()
         dev = vol.device
         shape = tuple(vol.shape)
@@ -302,7 +309,8 @@ class VolumeInference:
         fill = (np.float32(0.) - mean32) / std32
         min_val = (np.float32(float(ops.min_value(vol).item())) - mean32) / std32
         y = torch.empty((N, P, P, P), dtype=torch.float32, device=dev)                       # reused by every step of every sample
-        x0_vol = torch.empty(shape, dtype=torch.float32, device=dev) if self_cond else None
+        multistep = bool(getattr(den, 'multistep', False))                                   # 'dpmpp2m': coefs rows are (kx, k0, kp)
+        x0_vol = torch.empty(shape, dtype=torch.float32, device=dev) if self_cond or multistep else None
         mean_io = m2_io = out_std = None
         for s in range(S):
             x = ops.volume_joint_init(shape, self.seed, sample=s, device=dev)               # draw 0
@@ -317,8 +325,12 @@ class VolumeInference:
                         pred = merge_sub_volumes(pred, original_shape=(1, 1, P, P, P))
                     y[lo:lo + n] = pred.reshape(n, P, P, P)
                 kx, k0, kn = coefs[i]
-                ops.volume_joint_step(y, slot, taps, x, kx, k0, kn, lo_c, hi_c, mode_c, self.overlap, self.seed, draw=i + 1, sample=s,
-                                      out=x, x0_out=x0_vol)
+                if multistep:                                # x0_vol is read as the previous fused x0, then overwritten with this one
+                    ops.volume_joint_multistep(y, slot, taps, x, x0_vol if i else None, kx, k0, kn, lo_c, hi_c, mode_c, self.overlap,
+                                               out=x, x0_out=x0_vol)
+                else:
+                    ops.volume_joint_step(y, slot, taps, x, kx, k0, kn, lo_c, hi_c, mode_c, self.overlap, self.seed, draw=i + 1,
+                                          sample=s, out=x, x0_out=x0_vol)
             mean_io, m2_io, out_std = ops.volume_joint_finish(den.finish(x), slot, vol, P, self.overlap, self.mean, self.std,
                                                               float(min_val), float(fill), s, S, mean_io, m2_io, want_std)
         return mean_io, out_std

@@ -2382,6 +2382,27 @@ def _joint_lattice(who, slot, shape, P, stride):
     return stride
 
 
+def _joint_windows(who, y, slot, taps, x_t, clamp_mode, stride):
+    """The host checks shared by the joint step launches; returns (N, P, stride)."""
+    _chk(y, taps, x_t)
+    if y.ndim != 4 or x_t.ndim != 3 or taps.ndim != 1:
+        raise ValueError(f"{who}: expected y [N,P,P,P], slot [G0,G1,G2], taps [P] and x_t [D,H,W]")
+    if not (y.is_contiguous() and taps.is_contiguous() and x_t.is_contiguous()):
+        raise RuntimeError(f"{who}: tensors must be contiguous")
+    N, P = y.shape[:2]
+    if tuple(y.shape[1:]) != (P, P, P) or taps.shape[0] != P:
+        raise ValueError(f"{who}: y {tuple(y.shape)} / taps {tuple(taps.shape)} are not cubic windows of one size")
+    stride = _joint_lattice(who, slot, x_t.shape, P, stride)
+    if int(clamp_mode) not in (0, 1):
+        raise ValueError(f"{who}: clamp_mode must be 0 (min) or 1 (box), got {clamp_mode!r}")
+    return N, P, stride
+
+
+def _joint_slots(who, slot, N):
+    if slot.numel() and int(slot.max()) >= N:                     # the kernel indexes `y` by it
+        raise ValueError(f"{who}: slot names window {int(slot.max())} of {N}")
+
+
 def volume_joint_init(shape, seed, sample=0, draw=0, device=None):
     """The initial state of a joint chain: fp32 [D,H,W], the volume-anchored normal of ``draw`` (channel 0) at every voxel -- the
     ``x_t == NULL`` launch of ``diqt_volume_joint_step``, bit for bit what ``anchored_noise`` hands to a window there."""
@@ -2406,20 +2427,9 @@ def volume_joint_step(y, slot, taps, x_t, kx, k0, kn, lo, hi, clamp_mode, stride
     x_next = kx x_t + k0 x0 + kn n with n the volume-anchored normal of (seed, draw, sample); uncovered voxels keep ``x_t``.  ``out``:
     where x_next goes (``x_t`` itself for an in-place step; None: a new tensor); ``x0_out`` (optional [D,H,W]) receives the fused x0
     (0 where uncovered).  Returns ``out``.  One launch, bit-reproducible."""
-    _chk(y, taps, x_t)
-    if y.ndim != 4 or x_t.ndim != 3 or taps.ndim != 1:
-        raise ValueError("volume_joint_step: expected y [N,P,P,P], slot [G0,G1,G2], taps [P] and x_t [D,H,W]")
-    if not (y.is_contiguous() and taps.is_contiguous() and x_t.is_contiguous()):
-        raise RuntimeError("volume_joint_step: tensors must be contiguous")
-    N, P = y.shape[:2]
-    if tuple(y.shape[1:]) != (P, P, P) or taps.shape[0] != P:
-        raise ValueError(f"volume_joint_step: y {tuple(y.shape)} / taps {tuple(taps.shape)} are not cubic windows of one size")
-    stride = _joint_lattice("volume_joint_step", slot, x_t.shape, P, stride)
-    if int(clamp_mode) not in (0, 1):
-        raise ValueError(f"volume_joint_step: clamp_mode must be 0 (min) or 1 (box), got {clamp_mode!r}")
+    N, P, stride = _joint_windows("volume_joint_step", y, slot, taps, x_t, clamp_mode, stride)
     seed, draw, sample = _noise_key("volume_joint_step", seed, draw, sample)
-    if slot.numel() and int(slot.max()) >= N:                     # the kernel indexes `y` by it
-        raise ValueError(f"volume_joint_step: slot names window {int(slot.max())} of {N}")
+    _joint_slots("volume_joint_step", slot, N)
     if out is None:
         out = torch.empty_like(x_t)
     for t, name in ((out, 'out'), (x0_out, 'x0_out')):
@@ -2430,6 +2440,28 @@ def volume_joint_step(y, slot, taps, x_t, kx, k0, kn, lo, hi, clamp_mode, stride
     _lib.call("diqt_volume_joint_step", y if N else None, slot, taps, x_t, out, x0_out, N, *x_t.shape, P, stride, *slot.shape,
               float(kx), float(k0), float(kn), float(lo), float(hi), int(clamp_mode), seed, draw, sample, _stream())
     return out
+
+
+def volume_joint_multistep(y, slot, taps, x_t, x0_prev, kx, k0, kp, lo, hi, clamp_mode, stride, out=None, x0_out=None):
+    """One step of a second-order multistep chain on the joint state (include/diqt.h, diqt_volume_joint_multistep): ``volume_joint_step``
+    with the previous step's fused x0 ``x0_prev`` [D,H,W] (None: zeros, the first step) as the third operand instead of a normal,
+    x_next = kx x_t + k0 x0 + kp x0_prev on covered voxels; uncovered voxels keep ``x_t``.  ``out`` / ``x0_out``: where x_next and the
+    fused x0 (0 where uncovered) go -- ``x_t`` and ``x0_prev`` themselves for an in-place step, None: new tensors.  Returns
+    ``(out, x0_out)``.  One launch, bit-reproducible."""
+    N, P, stride = _joint_windows("volume_joint_multistep", y, slot, taps, x_t, clamp_mode, stride)
+    _joint_slots("volume_joint_multistep", slot, N)
+    if out is None:
+        out = torch.empty_like(x_t)
+    if x0_out is None:
+        x0_out = torch.empty_like(x_t)
+    for t, name in ((x0_prev, 'x0_prev'), (out, 'out'), (x0_out, 'x0_out')):
+        if t is not None:
+            _chk(t)
+            if t.shape != x_t.shape or not t.is_contiguous():
+                raise ValueError(f"volume_joint_multistep: {name} must be a contiguous tensor of x_t's shape")
+    _lib.call("diqt_volume_joint_multistep", y if N else None, slot, taps, x_t, x0_prev, out, x0_out, N, *x_t.shape, P, stride,
+              *slot.shape, float(kx), float(k0), float(kp), float(lo), float(hi), int(clamp_mode), _stream())
+    return out, x0_out
 
 
 def volume_joint_finish(x, slot, vol, P, stride, mean, std, min_val, fill, s, S, mean_io=None, m2_io=None, want_std=False):

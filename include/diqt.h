@@ -613,6 +613,18 @@ int diqt_anchored_noise(const int* origins, int B, int C, int P, int D, int H, i
 int diqt_volume_joint_step(const float* y, const int* slot, const float* taps, const float* x_t, float* x_next, float* x0_out, int N,
                            int D, int H, int W, int P, int stride, int G0, int G1, int G2, float kx, float k0, float kn, float lo,
                            float hi, int clamp_mode, unsigned long long seed, unsigned draw, unsigned sample, void* stream);
+/* One step of a second-order multistep chain (DPM-Solver++ 2M; Lu et al. 2022) on the joint state: diqt_volume_joint_step with the
+ * fused x0 of the PREVIOUS step as the third operand instead of a normal -- no Philox, no seed, no draw.  Window walk, clamp, lattice
+ * check and launch geometry are diqt_volume_joint_step's.  Covered voxel (den != 0): x0 = num / den and
+ *     b = k0 * x0;  c = kp * x0_prev[v];  x_next[v] = fmaf(kx, x_t[v], b) + c
+ * with b and c rounded products (no further contraction) -- diqt_ddpm_step's operation order with x0_prev in the place of its noise
+ * operand; x0_out[v] = x0.  Uncovered voxel: x_next = x_t, x0_out = 0.  x0_prev == NULL stands for zeros (the first step).  x_next
+ * may alias x_t and x0_out may alias x0_prev: every thread reads its own voxel of both before it writes it.  x0_out is required.
+ * With kp == 0 and x0_prev == NULL, x_next and x0_out are bit for bit diqt_volume_joint_step's at kn == 0.  Null pointers:
+ * DIQT_E_ALIGN; a lattice that does not match: DIQT_E_SHAPE; clamp_mode outside {0, 1}: DIQT_E_UNSUPPORTED.                       */
+int diqt_volume_joint_multistep(const float* y, const int* slot, const float* taps, const float* x_t, const float* x0_prev,
+                                float* x_next, float* x0_out, int N, int D, int H, int W, int P, int stride, int G0, int G1, int G2,
+                                float kx, float k0, float kp, float lo, float hi, int clamp_mode, void* stream);
 /* The end of sample s (0-based) of S joint chains: per voxel r = min_val where vol (RAW, may be NULL) has (vol - mean) / std ==
  * min_val (diqt_background_reset's expression), else x (the finished state) where a kept window (slot >= 0) covers the voxel, else
  * `fill`; then diqt_volume_blend's Welford update in sample order, delta = r - m; m += delta / (s + 1); m2 = fma(delta, r - m, m2)
