@@ -142,6 +142,7 @@ PROTOTYPES = {
     "diqt_set_convh_workgroups": (I, [I]),
     "diqt_set_conv_f9h_mode": (I, [I]),
     "diqt_conv3d_bwd_weight_h_workspace_bytes": (Z, [I] * 15),
+    "diqt_conv3d_bwd_weight_h_supported": (I, [I] * 16),
     "diqt_conv3d_bwd_weight_h": (I, [P, P, P, P, P, Z] + [I] * 15 + [I, P]),
     "diqt_conv3d_fwd_h_io16_supported": (I, [I] * 17),
     "diqt_conv3d_fwd_h_stats_blocks": (I, [I] * 17),
@@ -186,6 +187,8 @@ PROTOTYPES = {
     "diqt_conv_pack_weight_h_multi": (I, [P, I, I, P]),
     "diqt_conv3d_fwd_h_supported": (I, [I] * 15),
     "diqt_conv3d_fwd_h": (I, [P, P, P, P, P] + [I] * 17 + [P]),
+    "diqt_conv3d_fwd_h_kernel_id": (I, [I] * 19),
+    "diqt_get_last_conv_f9h_variant": (I, []),
 }
 
 _lib = None

@@ -17,6 +17,8 @@ bool f9h_plan(H9Geom& g, size_t& lds, unsigned& grid, int B, int D, int H, int W
               int pw, int epd, int eph, int epw, bool yHalf);
 // rows of column sums per batch entry the kernel writes for this plan
 int f9h_stats_blocks(const H9Geom& g);
+// the variant of the process's last launch, -1 if none since the previous call (read and clear)
+int f9h_take_last_variant();
 int f9h_launch(const void* x, const unsigned short* packed_h, const float* bias, const float* residual, void* y, const H9Geom& g, size_t lds,
                unsigned grid, int bf16, bool yHalf, void* stream);
 

@@ -11,6 +11,9 @@ extern "C" int diqt_set_conv_f9h_mode(int mode) {
 
 namespace diqt {
 
+static std::atomic<int> f9h_last_variant{-1};
+int f9h_take_last_variant() { return f9h_last_variant.exchange(-1); }
+
 // One candidate tiling: tile counts, grid, and an estimate of the launch's duration in (voxel x workgroup-round) units -- rounds of
 // 256 OCC workgroup slots, each round as long as a tile (two workgroups sharing a CU run at half speed each).
 template <class C> static bool f9h_try(H9Geom& g, size_t& lds, unsigned& grid, double& est) {
@@ -78,6 +81,7 @@ int f9h_stats_blocks(const H9Geom& g) { return g.tilesD * g.tilesH * g.tilesW * 
 
 int f9h_launch(const void* x, const unsigned short* packed_h, const float* bias, const float* residual, void* y, const H9Geom& g, size_t lds,
                unsigned grid, int bf16, bool yHalf, void* stream) {
+    f9h_last_variant.store(g.variant);
     switch (g.variant) {
         case 0: return h9::launch_cfg<h9::H9_333_512>(x, packed_h, bias, residual, y, g, lds, grid, bf16, yHalf, stream);
         case 1: return h9::launch_b(x, packed_h, bias, residual, y, g, lds, grid, bf16, yHalf, stream);

@@ -991,38 +991,8 @@ static bool convh_four_waves(const HalfGeom& g, bool xh) {
     return !xh && g.NS == 1 && HV * 8 <= 256 * 8;     // pointwise, fp32 rows, one chunk per step: 8 pieces per thread
 }
 
-// 1 when diqt_conv3d_fwd_h_io takes 16-bit x and / or y for this shape: the persistent kernel's conditions and Cin, Cout % 8 == 0
-extern "C" int diqt_conv3d_fwd_h_io16_supported(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph,
-                                                int pw, int epd, int eph, int epw, int x_half, int y_half) {
-    HalfGeom g;
-    if (x_half) {                 // the LDS-DMA kernel (conv_f9h_kernel): 3x3x3 and (1,3,3) filters over 16-bit x
-        H9Geom g9; size_t l9; unsigned gr9;
-        if (f9h_plan(g9, l9, gr9, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, y_half != 0)) return 1;
-    }
-    if (Cin % 8 != 0 || Cout % 8 != 0 ||
-        !half_geom(g, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, x_half ? 2 : 4, y_half ? 2 : 4))
-        return 0;
-    const unsigned nwg = (unsigned)((long long)g.B * g.tilesD * g.tilesH * g.tilesW * g.nNt);
-    return convh_persistent_takes(g, nwg) ? 1 : 0;
-}
-
-// rows of per-(tile, wave) column sums diqt_conv3d_fwd_h_io writes per batch entry when given `stats` (0: this shape emits none)
-extern "C" int diqt_conv3d_fwd_h_stats_blocks(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph,
-                                              int pw, int epd, int eph, int epw, int x_half, int y_half) {
-    HalfGeom g;
-    if (x_half) {
-        H9Geom g9; size_t l9; unsigned gr9;
-        if (f9h_plan(g9, l9, gr9, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, y_half != 0)) return f9h_stats_blocks(g9);
-    }
-    if (!half_geom(g, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, x_half ? 2 : 4, y_half ? 2 : 4)) return 0;
-    if ((kd == 1 && kh == 1 && kw == 1) || !x_half) return 0;          // flattened rows: tiles straddle batch entries
-    const unsigned nwg = (unsigned)((long long)g.B * g.tilesD * g.tilesH * g.tilesW * g.nNt);
-    return convh_persistent_takes(g, nwg) ? g.tilesD * g.tilesH * g.tilesW * (convh_four_waves(g, x_half != 0) ? 4 : 8) : 0;
-}
-
-
 // pointwise convs with fp32 rows at both ends and temporal convs with 16-bit input rows: the K-blocked GEMM (conv_pw_h_kernel)
-static bool pwh_takes(const HalfGeom& g, bool xh, bool yh, const float* stats) {
+static bool pwh_takes(const HalfGeom& g, bool xh, bool yh, bool stats) {
     if (yh || stats) return false;
     if (g.kh != 1 || g.kw != 1 || g.ph || g.pw || g.Do != g.D || g.Ho != g.H || g.Wo != g.W) return false;
     if (g.Cin % HCK != 0 || g.Cin < 64) return false;
@@ -1056,57 +1026,99 @@ static int pwh_launch(const void* x, const unsigned short* wp, const float* bias
     return check_launch("conv3d_fwd_h(gemm)");
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The one decision of the 16-bit forward dispatch: which kernel a diqt_conv3d_fwd_h / _io call runs, for the current run-time switches.
+// convh_launch launches what this says and diqt_conv3d_fwd_h_kernel_id reports it, so the query and the launch cannot drift.
+// ---------------------------------------------------------------------------------------------------------------------------------
+enum ConvhKernel { CONVH_UNSUPPORTED = 0, CONVH_UNIT_PREFETCH = 1, CONVH_UNIT = 2, CONVH_PERSISTENT8 = 3, CONVH_PERSISTENT8_NS2 = 4,
+                   CONVH_PERSISTENT4 = 5, CONVH_GEMM_POINTWISE = 6, CONVH_GEMM_TEMPORAL = 7, CONVH_F9H = 8 };
+struct ConvhRoute {
+    int id;
+    const char* why;             // id == CONVH_UNSUPPORTED: the reason
+    HalfGeom g;                  // every id but CONVH_F9H (NS / TG / nChunks already set for CONVH_PERSISTENT8_NS2)
+    unsigned nwg;                // (tile, channel-block) units of g
+    bool geom, persistent;       // half_geom takes the shape; convh_persistent_takes(g, nwg) (asked before the GEMM's rule)
+    H9Geom g9; size_t l9; unsigned gr9;      // CONVH_F9H
+};
+
+static void convh_route(ConvhRoute& r, int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw, int epd,
+                        int eph, int epw, bool round_out, bool xh, bool yh, bool has_residual, bool has_stats) {
+    r.id = CONVH_UNSUPPORTED; r.why = ""; r.nwg = 0; r.geom = r.persistent = false;
+    // 16-bit x, 3x3x3 / (1,3,3): the LDS-DMA kernel on conv_fwd9_kernel's structure (conv_f9h_kernel.h)
+    if (xh && round_out && !(yh && has_residual) &&
+        f9h_plan(r.g9, r.l9, r.gr9, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, yh)) {
+        r.id = CONVH_F9H;
+        return;
+    }
+    HalfGeom& g = r.g;
+    if (!half_geom(g, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, xh ? 2 : 4, yh ? 2 : 4)) {
+        r.why = "conv3d_fwd_h: shape not supported by the low-precision kernel (diqt_conv3d_fwd_h_supported == 0)";
+        return;
+    }
+    g.roundOut = round_out ? 1 : 0;
+    r.geom = true;
+    r.nwg = (unsigned)((long long)g.B * g.tilesD * g.tilesH * g.tilesW * g.nNt);
+    r.persistent = convh_persistent_takes(g, r.nwg);
+    if (pwh_takes(g, xh, yh, has_stats)) {
+        r.id = g.kd == 1 ? CONVH_GEMM_POINTWISE : CONVH_GEMM_TEMPORAL;
+        return;
+    }
+    const int HV = g.HD * g.HH * g.HWd;
+    if (!r.persistent) {
+        if (xh || yh || has_stats) {
+            r.why = "conv3d_fwd_h_io: 16-bit tensors only on the persistent kernel (diqt_conv3d_fwd_h_io16_supported)";
+            return;
+        }
+        r.id = HV * 8 <= 512 * HHREG ? CONVH_UNIT_PREFETCH : CONVH_UNIT;
+        return;
+    }
+    // (two workgroups per CU -- 6 halo pieces per thread, weight groups of <= 5 taps, 128 registers per wave -- measured 1.4x SLOWER
+    // on the 64^3 level-0 shapes: the kernel moves 3.5 TB/s of fp32 activations, 0.75 of what a plain copy reaches)
+    if ((xh || yh) && !(Cin % 8 == 0 && Cout % 8 == 0 && (!yh || (round_out && !has_residual)))) {
+        r.why = "conv3d_fwd_h_io: 16-bit tensors need Cin, Cout % 8 == 0; a 16-bit output needs round_out and no residual";
+        return;
+    }
+    if (has_stats && kd == 1 && kh == 1 && kw == 1) { r.why = "conv3d_fwd_h_io: no statistics from a 1x1x1 conv"; return; }
+    if (has_stats && !xh) { r.why = "conv3d_fwd_h_io: statistics are built for x_half = 1"; return; }
+    // (fp32 rows of a pointwise conv: the 4-wave build at one chunk per step measures slightly faster than two chunks per step on 8 waves)
+    const bool ns2 = kd * kh * kw == 1 && g.nChunks >= 2 && xh;
+    if (ns2) {
+        // pointwise: 4 MFMAs of a wave per 32-channel chunk and two barriers around them -- stage TWO chunks per step and walk them like
+        // taps (their weight panels are consecutive in the packed layout [chunk][tap = 1][co][32])
+        g.NS = 2; g.realChunks = g.nChunks; g.nChunks = (g.realChunks + 1) / 2; g.TG = 2; g.nGroups = 1;
+    }
+    r.id = convh_four_waves(g, xh) ? CONVH_PERSISTENT4 : ns2 ? CONVH_PERSISTENT8_NS2 : CONVH_PERSISTENT8;
+}
+
 static int convh_launch(const void* x, const void* packed_h, const float* bias, const float* residual, void* y, int B, int D, int H, int W,
                         int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw, int epd, int eph, int epw, int bf16,
                         int round_out, bool xh, bool yh, float* stats, void* stream) {
     DIQT_REQUIRE(x && packed_h && y, DIQT_E_ALIGN, "conv3d_fwd_h: null pointer");
     DIQT_REQUIRE(aligned16(x) && aligned16(packed_h), DIQT_E_ALIGN, "conv3d_fwd_h: x and the packed weights must be 16-byte aligned");
-    if (xh && round_out && !(yh && residual)) {
-        // 16-bit x, 3x3x3 / (1,3,3): the LDS-DMA kernel on conv_fwd9_kernel's structure (conv_f9h_kernel.h)
-        H9Geom g9; size_t l9; unsigned gr9;
-        if (f9h_plan(g9, l9, gr9, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, yh)) {
-            DIQT_REQUIRE(aligned16(y) && (!residual || aligned16(residual)), DIQT_E_ALIGN, "conv3d_fwd_h_io: y / residual must be 16-byte aligned");
-            g9.stats = stats;
-            return f9h_launch(x, static_cast<const unsigned short*>(packed_h), bias, residual, y, g9, l9, gr9, bf16, yh, stream);
-        }
+    ConvhRoute r;
+    convh_route(r, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, round_out != 0, xh, yh, residual != nullptr, stats != nullptr);
+    DIQT_REQUIRE(r.id != CONVH_UNSUPPORTED, DIQT_E_UNSUPPORTED, "%s", r.why);
+    if (r.id == CONVH_F9H) {
+        DIQT_REQUIRE(aligned16(y) && (!residual || aligned16(residual)), DIQT_E_ALIGN, "conv3d_fwd_h_io: y / residual must be 16-byte aligned");
+        r.g9.stats = stats;
+        return f9h_launch(x, static_cast<const unsigned short*>(packed_h), bias, residual, y, r.g9, r.l9, r.gr9, bf16, yh, stream);
     }
-    HalfGeom g;
-    DIQT_REQUIRE(half_geom(g, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, xh ? 2 : 4, yh ? 2 : 4), DIQT_E_UNSUPPORTED,
-                 "conv3d_fwd_h: shape not supported by the low-precision kernel (diqt_conv3d_fwd_h_supported == 0)");
-    g.roundOut = round_out ? 1 : 0;
-    if (pwh_takes(g, xh, yh, stats))
+    const HalfGeom& g = r.g;
+    if (r.id == CONVH_GEMM_POINTWISE || r.id == CONVH_GEMM_TEMPORAL)
         return pwh_launch(x, static_cast<const unsigned short*>(packed_h), bias, residual, static_cast<float*>(y), g, bf16, xh, (hipStream_t)stream);
-    const unsigned nwg = (unsigned)((long long)g.B * g.tilesD * g.tilesH * g.tilesW * g.nNt);
+    const unsigned nwg = r.nwg;
     size_t lds = half_lds_bytes(g);
-    const int HV = g.HD * g.HH * g.HWd;
-    const bool pref = HV * 8 <= 512 * HHREG;
     hipStream_t s = (hipStream_t)stream;
-    if (convh_persistent_takes(g, nwg)) {
-        // (two workgroups per CU -- 6 halo pieces per thread, weight groups of <= 5 taps, 128 registers per wave -- measured 1.4x SLOWER
-        // on the 64^3 level-0 shapes: the kernel moves 3.5 TB/s of fp32 activations, 0.75 of what a plain copy reaches)
-        if (xh || yh) {
-            DIQT_REQUIRE(Cin % 8 == 0 && Cout % 8 == 0 && (!yh || (round_out && !residual)), DIQT_E_UNSUPPORTED,
-                         "conv3d_fwd_h_io: 16-bit tensors need Cin, Cout %% 8 == 0; a 16-bit output needs round_out and no residual");
-        }
-        DIQT_REQUIRE(!stats || !(kd == 1 && kh == 1 && kw == 1), DIQT_E_UNSUPPORTED, "conv3d_fwd_h_io: no statistics from a 1x1x1 conv");
-        // (fp32 rows of a pointwise conv: the 4-wave build below at one chunk per step measures slightly faster than two chunks per step on 8 waves)
-        if (kd * kh * kw == 1 && g.nChunks >= 2 && xh) {
-            // pointwise: 4 MFMAs of a wave per 32-channel chunk and two barriers around them -- stage TWO chunks per step and walk them like
-            // taps (their weight panels are consecutive in the packed layout [chunk][tap = 1][co][32])
-            g.NS = 2; g.realChunks = g.nChunks; g.nChunks = (g.realChunks + 1) / 2; g.TG = 2; g.nGroups = 1;
-        }
-        lds = half_lds_bytes(g);
+    if (r.id == CONVH_PERSISTENT8 || r.id == CONVH_PERSISTENT8_NS2 || r.id == CONVH_PERSISTENT4) {
         typedef void (*KP)(const float*, const unsigned short*, const float*, const float*, float*, HalfGeom, int, int, float*);
         const int sel = (bf16 ? 4 : 0) + (xh ? 2 : 0) + (yh ? 1 : 0);
         static const KP tab[8] = {conv_fwd_hp_kernel<false, 1, HHREG, HTG, false, false>, conv_fwd_hp_kernel<false, 1, HHREG, HTG, false, true>,
                                   conv_fwd_hp_kernel<false, 1, HHREG / 2, HTG, true, false>,  conv_fwd_hp_kernel<false, 1, HHREG / 2, HTG, true, true>,
                                   conv_fwd_hp_kernel<true, 1, HHREG, HTG, false, false>,  conv_fwd_hp_kernel<true, 1, HHREG, HTG, false, true>,
                                   conv_fwd_hp_kernel<true, 1, HHREG / 2, HTG, true, false>,   conv_fwd_hp_kernel<true, 1, HHREG / 2, HTG, true, true>};
-        DIQT_REQUIRE(!stats || xh, DIQT_E_UNSUPPORTED, "conv3d_fwd_h_io: statistics are built for x_half = 1");
-        const bool four = convh_four_waves(g, xh);
+        const bool four = r.id == CONVH_PERSISTENT4;
         KP kp;
         if (four && !xh) {
-            DIQT_REQUIRE(!stats, DIQT_E_UNSUPPORTED, "conv3d_fwd_h_io: statistics are built for x_half = 1");
             lds = half_lds_bytes(g, 1);
             kp = yh ? (bf16 ? conv_fwd_hp_kernel<true, 1, 8, HTG, false, true, false, 4> : conv_fwd_hp_kernel<false, 1, 8, HTG, false, true, false, 4>)
                     : (bf16 ? conv_fwd_hp_kernel<true, 1, 8, HTG, false, false, false, 4> : conv_fwd_hp_kernel<false, 1, 8, HTG, false, false, false, 4>);
@@ -1131,7 +1143,7 @@ static int convh_launch(const void* x, const void* packed_h, const float* bias, 
                            residual, static_cast<float*>(y), g, (int)nwg, perWg, stats);
         return check_launch("conv3d_fwd_h(persistent)");
     }
-    DIQT_REQUIRE(!xh && !yh && !stats, DIQT_E_UNSUPPORTED, "conv3d_fwd_h_io: 16-bit tensors only on the persistent kernel (diqt_conv3d_fwd_h_io16_supported)");
+    const bool pref = r.id == CONVH_UNIT_PREFETCH;
     void (*kern)(const float*, const unsigned short*, const float*, const float*, float*, HalfGeom) =
         bf16 ? (pref ? conv_fwd_h_kernel<true, true> : conv_fwd_h_kernel<true, false>)
              : (pref ? conv_fwd_h_kernel<false, true> : conv_fwd_h_kernel<false, false>);
@@ -1143,6 +1155,39 @@ static int convh_launch(const void* x, const void* packed_h, const float* bias, 
                        residual, static_cast<float*>(y), g);
     return check_launch("conv3d_fwd_h");
 }
+
+// Diagnostic: the kernel a diqt_conv3d_fwd_h / diqt_conv3d_fwd_h_io call with round_out = 1 runs for this shape, these tensor types and
+// the current run-time switches (convh_route, the launch's own decision)
+extern "C" int diqt_conv3d_fwd_h_kernel_id(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw,
+                                           int epd, int eph, int epw, int x_half, int y_half, int has_residual, int has_stats) {
+    ConvhRoute r;
+    convh_route(r, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, true, x_half != 0, y_half != 0, has_residual != 0, has_stats != 0);
+    return r.id;
+}
+
+// 1 when diqt_conv3d_fwd_h_io takes 16-bit x and / or y for this shape: conv_f9h_kernel, or the persistent kernel's conditions and Cin,
+// Cout % 8 == 0 -- read off the launch's own decision (convh_route) for a call without residual or statistics.  (A shape the GEMM takes
+// ahead of the persistent kernel keeps the persistent kernel's answer: a 16-bit y sends it there.)
+extern "C" int diqt_conv3d_fwd_h_io16_supported(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph,
+                                                int pw, int epd, int eph, int epw, int x_half, int y_half) {
+    ConvhRoute r;
+    convh_route(r, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, true, x_half != 0, y_half != 0, false, false);
+    if (r.id == CONVH_F9H) return 1;
+    return r.geom && r.persistent && Cin % 8 == 0 && Cout % 8 == 0 ? 1 : 0;
+}
+
+// rows of per-(tile, wave) column sums diqt_conv3d_fwd_h_io writes per batch entry when given `stats` (0: this shape emits none, and a
+// call that passes `stats` is refused): the launch's own decision (convh_route), for a call without a residual
+extern "C" int diqt_conv3d_fwd_h_stats_blocks(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph,
+                                              int pw, int epd, int eph, int epw, int x_half, int y_half) {
+    ConvhRoute r;
+    convh_route(r, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, true, x_half != 0, y_half != 0, false, true);
+    if (r.id == CONVH_F9H) return f9h_stats_blocks(r.g9);
+    if (r.id == CONVH_PERSISTENT8 || r.id == CONVH_PERSISTENT4) return r.g.tilesD * r.g.tilesH * r.g.tilesW * (r.id == CONVH_PERSISTENT4 ? 4 : 8);
+    return 0;          // flattened rows of a 1x1x1 conv (tiles straddle batch entries), fp32 x, or a launch off the persistent kernel
+}
+
+extern "C" int diqt_get_last_conv_f9h_variant() { return f9h_take_last_variant(); }
 
 extern "C" int diqt_conv3d_fwd_h(const float* x, const void* packed_h, const float* bias, const float* residual, float* y, int B, int D,
                                  int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw, int epd, int eph,

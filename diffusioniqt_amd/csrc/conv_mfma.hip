@@ -2335,6 +2335,14 @@ extern "C" size_t diqt_conv3d_bwd_weight_h_workspace_bytes(int B, int D, int H, 
     if (!wgradh_plan(g, ks, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw)) return 0;       // 0: shape not taken
     return ((size_t)ks * Cout * Cin * kd * kh * kw + (size_t)ks * g.CoutPad) * sizeof(float);
 }
+// 1 when diqt_conv3d_bwd_weight_h takes this shape with these flag bits of its `bf16` argument (2: 16-bit x, 4: 16-bit dY): the plan the
+// launch itself asks
+extern "C" int diqt_conv3d_bwd_weight_h_supported(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph,
+                                                  int pw, int epd, int eph, int epw, int flags) {
+    WHGeom g;
+    int ks = 0;
+    return wgradh_plan(g, ks, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, (flags & 2) != 0, (flags & 4) != 0) ? 1 : 0;
+}
 extern "C" int diqt_conv3d_bwd_weight_h(const float* x, const float* dy, float* dw, float* dbias, void* workspace, size_t workspace_bytes,
                                         int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw,
                                         int epd, int eph, int epw, int bf16, void* stream) {

@@ -311,6 +311,7 @@ bool wgradh_plan(WHGeom& g, int& ksplit, int B, int D, int H, int W, int Cin, in
                  int epd, int eph, int epw, bool xHalf, bool dyHalf) {
     const bool filt = (kd == 3 && kh == 3 && kw == 3) || (kd == 1 && kh == 3 && kw == 3) || (kd == 3 && kh == 1 && kw == 1);
     if (!filt || Cin % 32 != 0 || Cout % 4 != 0 || Cin < 32 || Cout < 32) return false;
+    if (dyHalf && !xHalf) return false;                                // a 16-bit dY is built together with a 16-bit x
     if (B <= 0 || D <= 0 || H <= 0 || W <= 0 || pd < 0 || ph < 0 || pw < 0 || pd > 16 || ph > 16 || pw > 16) return false;
     if (D > 255 || H > 255 || W > 255) return false;                   // packed 10-bit coordinate fields in the kernel
     g.B = B; g.D = D; g.H = H; g.W = W; g.Cin = Cin; g.Cout = Cout; g.pd = pd; g.ph = ph; g.pw = pw;

@@ -129,6 +129,15 @@ int diqt_set_convh_workgroups(int n);
  * chip, for any tile count when mode = 2, never when 0.  mode >= 0 sets it, mode < 0 only queries; returns the previous value.  Results
  * agree with the other 16-bit kernels bit for bit on integer-valued data (different K order otherwise).                          */
 int diqt_set_conv_f9h_mode(int mode);
+/* Diagnostic, the counterpart of diqt_conv3d_fwd_kernel_id: the kernel a diqt_conv3d_fwd_h / diqt_conv3d_fwd_h_io call with round_out = 1
+ * runs for this shape, these tensor types and the current run-time switches (the launch takes its decision from the same function) --
+ * 0 unsupported (the call returns an error and launches nothing), 1 conv_fwd_h_kernel with halo prefetch, 2 conv_fwd_h_kernel without,
+ * 3 conv_fwd_hp_kernel on 8 waves, 4 the same staging two 32-channel chunks of a pointwise conv per step, 5 conv_fwd_hp_kernel on 4 waves,
+ * 6 conv_pw_h_kernel on a pointwise conv, 7 conv_pw_h_kernel on a temporal conv, 8 conv_f9h_kernel.                                      */
+int diqt_conv3d_fwd_h_kernel_id(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw,
+                                int epd, int eph, int epw, int x_half, int y_half, int has_residual, int has_stats);
+/* the conv_f9h_kernel variant (0..5) the process's last launch of it ran, -1 if none since the previous call (read and clear) */
+int diqt_get_last_conv_f9h_variant(void);
 int diqt_conv3d_fwd_h(const float* x, const void* packed_h, const float* bias, const float* residual, float* y, int B, int D, int H,
                       int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw, int epd, int eph, int epw, int bf16,
                       int round_out, void* stream);
@@ -219,6 +228,10 @@ int diqt_conv3d_bwd_weight(const float* x, const float* dy, float* dw_oidhw, flo
  * that type for the conv's forward and for this pass: half the bytes, the same bits the fp32 values round to).                          */
 size_t diqt_conv3d_bwd_weight_h_workspace_bytes(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph,
                                                 int pw, int epd, int eph, int epw);
+/* 1 when diqt_conv3d_bwd_weight_h takes this shape with these flag bits (2: 16-bit x, 4: 16-bit dY -- only together with a 16-bit x, and
+ * Cout % 8 == 0), else 0: the call returns an error and launches nothing.  flags = 0 agrees with ..._workspace_bytes > 0.               */
+int diqt_conv3d_bwd_weight_h_supported(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw,
+                                       int epd, int eph, int epw, int flags);
 int diqt_conv3d_bwd_weight_h(const float* x, const float* dy, float* dw_oidhw, float* dbias, void* workspace, size_t workspace_bytes,
                              int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw, int epd,
                              int eph, int epw, int bf16, void* stream);

@@ -90,14 +90,21 @@ def route(case):
         bgeo = (B, Do, Ho, Wo, Cout, Cin, *k, *(kk - 1 - p for kk, p in zip(k, pad)), *(-e for e in epad))
         bwd = _fwd_route(bgeo, ops._packed_len((Cout, Cin, *k), 1)[0])            # direct pack only: never the Winograd tile
     if "w" in grads:
-        kid = q("diqt_conv3d_bwd_weight_kernel_id", *geo)
-        T = k[0] * k[1] * k[2]
-        if kid == 0:      # the three routes diqt_conv3d_bwd_weight tries in this order
-            kind = "colsum" if (Cout == 1 and T == 1) else "im2col" if (Cin <= 4 and T > 1 and B * Do * Ho * Wo >= 4096) else "pw"
-        else:
-            kind = {3: "v3", 2: "v2", 1: "v1"}[kid]
-        wg = {"kid": kid, "kind": kind}
+        wg = wgrad_route(case)
     return {"fwd": fwd, "bwd_data": bwd, "wgrad": wg}
+
+
+def wgrad_route(case):
+    """The kernel diqt_conv3d_bwd_weight (fp32) runs for a case."""
+    B, D, H, W, Cin, Cout, k, pad, epad, res, grads = case
+    Do, Ho, Wo = out_extent(case)
+    kid = _lib.query("diqt_conv3d_bwd_weight_kernel_id", *_geo(case))
+    T = k[0] * k[1] * k[2]
+    if kid == 0:      # the three routes diqt_conv3d_bwd_weight tries in this order
+        kind = "colsum" if (Cout == 1 and T == 1) else "im2col" if (Cin <= 4 and T > 1 and B * Do * Ho * Wo >= 4096) else "pw"
+    else:
+        kind = {3: "v3", 2: "v2", 1: "v1"}[kid]
+    return {"kid": kid, "kind": kind}
 
 
 def fwd_tags(r, exact_split=True):

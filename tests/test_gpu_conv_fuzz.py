@@ -23,10 +23,12 @@ FAULT_STATUS = (124, 134, 137, 139, -6, -11)
 _card_faulted = []      # a worker ended by a signal or the timeout: nothing more of this file starts on that card
 
 
-def run_worker(family, seed, env):
+def run_worker(family, seed, env, script="conv_fuzz_worker.py"):
+    """Runs tests/<script> <family> <seed> in a process of its own (tests/test_gpu_conv_fuzz_h.py runs its worker through here too: a
+    fault or timeout in either file stops both)."""
     if _card_faulted:
         pytest.skip("an earlier fuzz worker met a GPU fault or hang (%s): not starting more work on that card" % _card_faulted[0])
-    cmd = [sys.executable, os.path.join(ROOT, "tests", "conv_fuzz_worker.py"), family, str(seed)]
+    cmd = [sys.executable, os.path.join(ROOT, "tests", script), family, str(seed)]
     try:
         r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     except subprocess.TimeoutExpired as e:
