@@ -572,6 +572,75 @@ __global__ __launch_bounds__(256) void volume_joint_multistep_kernel(const float
     x_next[v] = sampler_update(kx, xt, k0, x0, kp, prev);
 }
 
+// The stochastic Heun sampler of the EDM family (elucidated_imagen.py:382-532) on the same state: a churn, a predictor and a corrector
+// per step, two U-Net evaluations, so the state is three volumes -- xh = images_hat, xn = images_next, x0 = the fused prediction (the
+// one self-conditioning reads) -- and the launch takes a `phase`, uniform over the grid:
+//   0 (no y)                       xh = (a n(draw)) + kc n(draw + 1): the initial image sigma0 n, rounded as the sampler stores it, then
+//                                  the churn of step 0;
+//   1 (after the stage-0 windows)  x0 = sum(w c(y)) / sum(w), xn = a xh + b x0: the Euler predictor, (a, b) = (1 + r, -r);
+//   2 (after the stage-1 windows)  x0b = sum(w c(y)) / sum(w), t = a xh + b x0 + c xn, x = t + d x0b: the corrector, (a, b, c, d) =
+//                                  (1 + r/2, -r/2, r2, -r2); then the next step's churn xh = x + kc n(draw) (no Philox call when
+//                                  kc == 0) and x0 = x0b.
+// A voxel no kept window covers: phase 1 writes xn = xh and x0 = 0, phase 2 leaves xh and writes x0 = 0 (nothing ever gathers it).
+// The walk, the clamp and the normals are the step kernel's own.  Every thread reads only its own voxel of xh / xn / x0, then writes
+// it: all three are updated in place (no __restrict__ on them).
+// axpby3_kernel's `v = k0 a; v += k1 b; v += k2 c` as the compiler contracts it there: the first product is rounded, every later one
+// is fused into the running sum.  Spelled out (and kept from further contraction) so that at stride = patch the joint chain is
+// ElucidatedImagen.one_unet_sample's bit for bit.
+__device__ __forceinline__ float axpby_update(float k0, float a, float k1, float b) {
+#pragma clang fp contract(off)
+    const float v = k0 * a;
+    return fmaf(k1, b, v);
+}
+__global__ __launch_bounds__(256) void volume_joint_heun_kernel(const float* __restrict__ y, const int* __restrict__ slot,
+                                                                const float* __restrict__ taps, float* xh, float* xn, float* x0v,
+                                                                int phase, int N, int D, int H, int W, int P, int stride, int G0, int G1,
+                                                                int G2, float a, float b, float c, float d, float kc, float lo, float hi,
+                                                                int clamp_mode, unsigned key0, unsigned key1, unsigned draw,
+                                                                unsigned sample) {
+    extern __shared__ float tp[];                      // [P]
+    if (phase != 0) {                                  // uniform over the launch
+        for (int e = threadIdx.y * 64 + threadIdx.x; e < P; e += 256) tp[e] = taps[e];
+        __syncthreads();
+    }
+    const int x = blockIdx.x * 64 + threadIdx.x;
+    const int h = __builtin_amdgcn_readfirstlane(blockIdx.y * 4 + threadIdx.y), d_ = blockIdx.z;
+    if (h >= H || x >= W) return;
+    const size_t v = ((size_t)d_ * H + h) * W + x;     // = lin of channel 0
+    const unsigned v0 = (unsigned)v, v1 = (unsigned)((unsigned long long)v >> 32);
+    if (phase == 0) {
+        float r = axpby_update(a, philox_normal(philox4x32_10(v0, v1, draw, sample, key0, key1)), 0.f, 0.f);
+        if (kc != 0.f) r = fmaf(kc, philox_normal(philox4x32_10(v0, v1, draw + 1u, sample, key0, key1)), r);
+        xh[v] = r;
+        return;
+    }
+    float num, den;
+    window_walk(y, slot, taps, tp, N, P, stride, G1, G2, d_, h, x, covering(d_, h, x, P, stride, G0, G1, G2),
+                StepClamp{lo, hi, clamp_mode}, num, den);
+    if (phase == 1) {
+        const float h_ = xh[v];
+        if (den == 0.f) {
+            xn[v] = h_;
+            x0v[v] = 0.f;
+            return;
+        }
+        const float x0 = num / den;
+        x0v[v] = x0;
+        xn[v] = axpby_update(a, h_, b, x0);
+        return;
+    }
+    if (den == 0.f) {
+        x0v[v] = 0.f;
+        return;
+    }
+    const float x0b = num / den;
+    const float t = fmaf(c, xn[v], axpby_update(a, xh[v], b, x0v[v]));
+    float r = fmaf(d, x0b, t);                         // axpby3(tmp, out2, 1, d): 1 * tmp is tmp
+    if (kc != 0.f) r = fmaf(kc, philox_normal(philox4x32_10(v0, v1, draw, sample, key0, key1)), r);
+    xh[v] = r;
+    x0v[v] = x0b;
+}
+
 // The end of sample s of S: r = min_val on the background (background_reset_kernel's expression on the RAW vol), else x where a kept
 // window covers the voxel, else fill; then volume_blend_kernel's Welford update of (mean_io, m2_io) with r, and after the last sample
 // the unbiased deviation.  Sample 0 initialises the running pair (nothing is read from mean_io / m2_io then).
@@ -879,6 +948,33 @@ extern "C" int diqt_volume_joint_multistep(const float* y, const int* slot, cons
     hipLaunchKernelGGL(volume_joint_multistep_kernel, dim3((W + 63) / 64, (H + 3) / 4, D), dim3(64, 4), (size_t)P * sizeof(float), STREAM,
                        y, slot, taps, x_t, x0_prev, x_next, x0_out, N, D, H, W, P, stride, G0, G1, G2, kx, k0, kp, lo, hi, clamp_mode);
     return check_launch("volume_joint_multistep");
+}
+
+extern "C" int diqt_volume_joint_heun(const float* y, const int* slot, const float* taps, float* xh, float* xn, float* x0, int phase, int N,
+                                      int D, int H, int W, int P, int stride, int G0, int G1, int G2, float a, float b, float c, float d,
+                                      float kc, float lo, float hi, int clamp_mode, unsigned long long seed, unsigned draw,
+                                      unsigned sample, void* stream) {
+    DIQT_REQUIRE(phase >= 0 && phase <= 2, DIQT_E_UNSUPPORTED, "volume_joint_heun: phase %d (0 = init, 1 = predictor, 2 = corrector)",
+                 phase);
+    DIQT_REQUIRE(xh, DIQT_E_ALIGN, "volume_joint_heun: null pointer");
+    DIQT_REQUIRE(D > 0 && H > 0 && W > 0, DIQT_E_SHAPE, "volume_joint_heun: bad shape");
+    DIQT_REQUIRE(D <= 65535 && (H + 3) / 4 <= 65535, DIQT_E_SHAPE, "volume_joint_heun: more than 65535 planes / row groups");
+    size_t lds = 0;
+    if (phase == 0) {                                   // the initial state ignores the window arguments; it reads draw and draw + 1
+        DIQT_REQUIRE(draw != 0xffffffffu, DIQT_E_SHAPE, "volume_joint_heun: phase 0 uses draw and draw + 1");
+    } else {
+        DIQT_REQUIRE(xn && x0 && slot && taps && (y || N == 0), DIQT_E_ALIGN, "volume_joint_heun: null pointer");
+        DIQT_REQUIRE(N >= 0, DIQT_E_SHAPE, "volume_joint_heun: windows %d", N);
+        int rc = joint_lattice_ok("volume_joint_heun", D, H, W, P, stride, G0, G1, G2);
+        if (rc) return rc;
+        DIQT_REQUIRE(clamp_mode == 0 || clamp_mode == 1, DIQT_E_UNSUPPORTED, "volume_joint_heun: clamp_mode %d (0 = min, 1 = box)",
+                     clamp_mode);
+        lds = (size_t)P * sizeof(float);
+    }
+    hipLaunchKernelGGL(volume_joint_heun_kernel, dim3((W + 63) / 64, (H + 3) / 4, D), dim3(64, 4), lds, STREAM, y, slot, taps, xh, xn, x0,
+                       phase, N, D, H, W, P, stride, G0, G1, G2, a, b, c, d, kc, lo, hi, clamp_mode, (unsigned)seed,
+                       (unsigned)(seed >> 32), draw, sample);
+    return check_launch("volume_joint_heun");
 }
 
 extern "C" int diqt_volume_joint_finish(const float* x, const int* slot, const float* vol, float* mean_io, float* m2_io, float* out_std,

@@ -10,7 +10,7 @@ Superset of the reference: it also drives the true-Conv3d Family-A ``Unet`` (``f
 reference cannot.
 """
 from collections import namedtuple
-from contextlib import contextmanager
+from contextlib import contextmanager, nullcontext
 from functools import partial
 from math import sqrt
 from random import random
@@ -38,6 +38,97 @@ def calc_all_frame_dims(downsample_factors, frames):
         assert frames % divisor == 0
         out.append((frames // divisor,))
     return out
+
+
+class EDMWindowDenoiser:
+    """The per-window half of ``ElucidatedImagen.one_unet_sample`` (the stochastic Heun sampler), callable one U-Net evaluation at a time
+    (``ElucidatedImagen.window_denoiser`` makes it) -- the EDM counterpart of ``imagen_pytorch3D.WindowDenoiser``, with the attributes
+    ``VolumeInference(joint=True)`` checks and ``heun = True``, which sends it down the Heun branch of the joint chain.
+
+    * ``num_steps``; ``sched``: host [T,3] of (sigma, sigma_next, gamma) per step; ``sigma0``: the first sigma;
+    * ``coefs``: host fp32 [T,7], per step ``(kc, 1 + r, -r, 1 + r/2, -r/2, r2, -r2)`` with sigma_hat = sigma + gamma sigma,
+      kc = S_noise sqrt(max(sigma_hat^2 - sigma^2, 0)) (the churn, images_hat = images + kc eps), r = (sigma_next - sigma_hat) / sigma_hat
+      (the predictor, images_next = (1 + r) images_hat - r out) and r2 = (sigma_next - sigma_hat) / (2 sigma_next) (the corrector,
+      ((1 + r/2) images_hat - r/2 out + r2 images_next) - r2 out2; both entries 0 on the step with sigma_next == 0, which has none) --
+      every entry the Python float ``one_unet_sample`` hands to its step kernel, rounded to fp32 once;
+    * ``draw_base``: 1 for a low-res conditioned U-Net (draw 0 of a noise source is the low-res augmentation noise), else 0; the initial
+      image is draw ``draw_base`` and the ``eps`` of step i is draw ``draw_base + 1 + i`` -- the call order of ``sample(noise=callable)``;
+    * ``clamp = (-inf, inf, 1)``: ``x0`` already returns the clamped or thresholded prediction;
+    * ``x0(img, lowres, i, self_cond=None, stage=0, lowres_noise=None)`` -> fp32 [B,C,P,P,P]: ``preconditioned_network_forward`` at
+      sigma_hat of step i (``stage`` 0) or at its sigma_next (``stage`` 1) on the low-res windows noised with ``lowres_noise`` at
+      ``lowres_sample_noise_level`` -- the tensor ``one_unet_sample`` calls ``out`` / ``out2``, hipGraph replay included;
+    * ``finish(x)``: clamp(-1, 1) and ``unnormalize_img`` on a tensor of any shape;
+    * ``self_cond``: whether the U-Net takes the last x0 estimate."""
+    heun = True
+
+    def __init__(self, imagen, unet_number, cond_scale, clamp, sigma_min, sigma_max, unet_context):
+        self.imagen, self.index, self._context = imagen, unet_number - 1, unet_context
+        hp = self.hp = imagen.hparams[self.index]
+        self.cond_scale = cast_tuple(cond_scale, len(imagen.unets))[self.index]
+        self.clamp_x0 = bool(clamp)
+        self.dynamic_threshold = bool(imagen.dynamic_thresholding[self.index])
+        unet = imagen.unets[self.index]
+        self.self_cond = bool(getattr(unet, 'self_cond', False))
+        self.lowres_cond = bool(getattr(unet, 'lowres_cond', False))
+        self.draw_base = 1 if self.lowres_cond else 0
+        # the schedule and the step scalars exactly as one_unet_sample computes them
+        sigma_min, sigma_max = default(sigma_min, hp.sigma_min), default(sigma_max, hp.sigma_max)
+        sigmas = imagen.sample_schedule(hp.num_sample_steps, hp.rho, sigma_min, sigma_max)
+        gammas = torch.where((sigmas >= hp.S_tmin) & (sigmas <= hp.S_tmax), min(hp.S_churn / hp.num_sample_steps, sqrt(2) - 1), 0.)
+        self._steps = list(zip(sigmas[:-1].tolist(), sigmas[1:].tolist(), gammas[:-1].tolist()))
+        self.sched = torch.tensor(self._steps, dtype=torch.float64)                       # [T, 3] on the host: the fp32 values, widened
+        self.sigma0 = sigmas[0].item()
+        self.num_steps = len(self._steps)
+        rows = []
+        for sigma, sigma_next, gamma in self._steps:
+            sigma_hat = sigma + gamma * sigma
+            r = (sigma_next - sigma_hat) / sigma_hat
+            r2 = 0.5 * (sigma_next - sigma_hat) / sigma_next if sigma_next != 0 else 0.
+            rows.append([hp.S_noise * sqrt(max(sigma_hat ** 2 - sigma ** 2, 0.)), 1. + r, -r, 1. + 0.5 * r, -0.5 * r, r2, -r2])
+        self.coefs = torch.tensor(rows, dtype=torch.float64).to(torch.float32)            # [T, 7] on the host, each rounded once
+        self.clamp = (-float('inf'), float('inf'), 1)
+
+    def sigma_of(self, i, stage):
+        """The sigma the U-Net is evaluated at: sigma_hat of step i (stage 0) or its sigma_next (stage 1)."""
+        sigma, sigma_next, gamma = self._steps[i]
+        return float(sigma_next) if stage else float(sigma + gamma * sigma)
+
+    @torch.no_grad()
+    def x0(self, img, lowres, i, self_cond=None, stage=0, lowres_noise=None):
+        elu = self.imagen
+        if not 0 <= i < self.num_steps:
+            raise ValueError(f"EDMWindowDenoiser.x0: step {i} of {self.num_steps}")
+        if stage not in (0, 1) or (stage == 1 and self._steps[i][1] == 0):
+            raise ValueError(f"EDMWindowDenoiser.x0: stage {stage!r} of step {i} (0 = at sigma_hat, 1 = at sigma_next, when that is not 0)")
+        if self.lowres_cond and (lowres is None or lowres_noise is None):
+            raise ValueError("EDMWindowDenoiser.x0: a low-res conditioned U-Net needs the low-res windows and their augmentation noise")
+        dev, B = img.device, img.shape[0]
+        was_training = elu.training
+        elu.eval()
+        try:
+            with self._context():
+                elu.reset_unets_all_one_device(device=dev)                    # as ``sample`` does before it picks the U-Net
+                unet = elu.unets[self.index]
+                lowres_cond_img = lowres_noise_times = None
+                if self.lowres_cond:                                          # sample(): :652-657
+                    t_cpu = torch.full((B,), float(elu.lowres_sample_noise_level))
+                    lowres_noise_times = t_cpu.to(dev)
+                    size = elu.image_sizes[self.index]
+                    lowres_cond_img = elu.normalize_img(elu._resize(lowres.to(dev), size, img.shape[2])).float().to(dev)
+                    lowres_cond_img = elu._noise_lowres(lowres_cond_img, t_cpu, lowres_noise.to(dev).float())
+                sc = dict(self_cond=self_cond) if self.self_cond else {}
+                return elu.preconditioned_network_forward(
+                    unet.forward_with_cond_scale, img.float().contiguous(), self.sigma_of(i, stage), sigma_data=self.hp.sigma_data,
+                    clamp=self.clamp_x0, dynamic_threshold=self.dynamic_threshold, cond_scale=self.cond_scale,
+                    **elu._unet_kwargs(unet, lowres_cond_img, lowres_noise_times), **sc)
+        finally:
+            elu.train(was_training)
+
+    @torch.no_grad()
+    def finish(self, x):
+        flat = x.contiguous().view(1, -1)
+        one = torch.ones(1, device=x.device)
+        return self.imagen.unnormalize_img(ops.axpby3(flat, None, None, one, None, None, -1., 1., 2)).view(x.shape)
 
 
 class ElucidatedImagen(nn.Module):
@@ -196,7 +287,8 @@ class ElucidatedImagen(nn.Module):
     def one_unet_sample(self, unet, shape, *, unet_number, clamp=True, dynamic_threshold=True, cond_scale=1., use_tqdm=True,
                         inpaint_images=None, inpaint_masks=None, inpaint_resample_times=5, init_images=None,
                         skip_steps=None, sigma_min=None, sigma_max=None, noise=None, **kwargs):
-        """Stochastic Heun sampler (:382-532).  ``noise``: optional injected list [init, step_0, ...]."""
+        """Stochastic Heun sampler (:382-532).  ``noise``: optional injected list [init, step_0, ...], or a callable
+        ``noise(shape) -> fp32 device tensor`` whose successive calls are those draws (one ``eps`` per step, also when gamma is 0)."""
         assert not exists(inpaint_images) and not exists(inpaint_masks), 'inpainting: SURVEY.md §8(f) next'
         hp = self.hparams[unet_number - 1]
         sigma_min, sigma_max = default(sigma_min, hp.sigma_min), default(sigma_max, hp.sigma_max)
@@ -205,8 +297,11 @@ class ElucidatedImagen(nn.Module):
         sched = list(zip(sigmas[:-1].tolist(), sigmas[1:].tolist(), gammas[:-1].tolist()))[default(skip_steps, 0):]
         dev = self.device
         B = shape[0]
-        noise = list(noise) if exists(noise) else None
-        draw = (lambda: noise.pop(0).to(dev).float().contiguous()) if exists(noise) else (lambda: torch.randn(shape, device=dev))
+        if callable(noise):
+            draw = lambda: noise(shape).to(dev).float().contiguous()
+        else:
+            noise = list(noise) if exists(noise) else None
+            draw = (lambda: noise.pop(0).to(dev).float().contiguous()) if exists(noise) else (lambda: torch.randn(shape, device=dev))
         vec = lambda v: torch.full((B,), float(v), device=dev)
         images = ops.axpby3(draw(), None, None, vec(sigmas[0].item()), None, None)
         if exists(init_images):
@@ -235,6 +330,23 @@ class ElucidatedImagen(nn.Module):
         images = ops.axpby3(images, None, None, vec(1.), None, None, -1., 1., 2)    # clamp(-1, 1)   (:527)
         return self.unnormalize_img(images)
 
+    def window_denoiser(self, unet_number=2, cond_scale=1., clamp=True, sigma_min=None, sigma_max=None, inpaint_images=None,
+                        inpaint_masks=None, init_images=None, skip_steps=None, _unet_context=nullcontext):
+        """The per-window half of ``one_unet_sample`` as an object that is called one U-Net evaluation at a time -- what
+        ``VolumeInference(..., joint=True)`` drives for the EDM family; see ``EDMWindowDenoiser``.  Inpainting, ``init_images`` and
+        ``skip_steps`` belong to the one-call sampler and are refused here (``ValueError``, before anything touches the device)."""
+        if exists(inpaint_images) or exists(inpaint_masks):
+            raise ValueError("window_denoiser does not inpaint: the joint chain has no per-window re-noising loop")
+        if exists(init_images):
+            raise ValueError("window_denoiser takes no init_images: the joint chain starts from the volume-anchored field")
+        if exists(skip_steps):
+            raise ValueError("window_denoiser takes no skip_steps: thin the chain with num_sample_steps")
+        if isinstance(unet_number, bool) or int(unet_number) != unet_number or not 1 <= unet_number <= len(self.unets):
+            raise ValueError(f"unet_number must be 1 .. {len(self.unets)}, got {unet_number!r}")
+        if isinstance(self.unets[unet_number - 1], NullUnet):
+            raise ValueError('one cannot sample from null / placeholder unets')
+        return EDMWindowDenoiser(self, int(unet_number), cond_scale, clamp, sigma_min, sigma_max, _unet_context)
+
     def _resize(self, x, size, frames=None):
         """resize_video_to (imagen_video.py:137-158): nearest, no-op when the spatial size already matches."""
         if x.shape[-1] == size:
@@ -255,8 +367,15 @@ class ElucidatedImagen(nn.Module):
                batch_size=1, cond_scale=1., lowres_sample_noise_level=None, start_at_unet_number=1, start_image_or_video=None,
                stop_at_unet_number=None, return_all_unet_outputs=False, return_pil_images=False, use_tqdm=True, device=None,
                noise=None):
-        """:536-702.  ``noise``: optional injected list [lowres_noise, init, step_0, ...] per sampled unet (tests)."""
+        """:536-702.  ``noise``: optional injected list [lowres_noise, init, step_0, ...] per sampled unet (tests), or -- when exactly
+        one U-Net is sampled -- a callable ``noise(shape) -> fp32 device tensor`` whose successive calls are those draws in that order
+        (``inference.AnchoredNoise.source``: call k is draw k of the volume-anchored field)."""
         assert texts is None and text_embeds is None and not return_pil_images
+        if callable(noise):
+            sampled = range(start_at_unet_number, default(stop_at_unet_number, len(self.unets)) + 1)
+            if len(sampled) != 1:
+                raise ValueError(f"sample: a callable noise source is made for one window size, so exactly one U-Net may be sampled with "
+                                 f"it (start_at_unet_number == stop_at_unet_number or the last one); this call samples {len(sampled)}")
         device = default(device, self.device)
         self.reset_unets_all_one_device(device=device)
         lowres_sample_noise_level = default(lowres_sample_noise_level, self.lowres_sample_noise_level)
@@ -266,7 +385,8 @@ class ElucidatedImagen(nn.Module):
         all_frame_dims = calc_all_frame_dims(self.temporal_downsample_factor, video_frames)
         init_images = [maybe(self.normalize_img)(i) for i in cast_tuple(init_images, num_unets)]
         skip_steps, sigma_min, sigma_max = (cast_tuple(v, num_unets) for v in (skip_steps, sigma_min, sigma_max))
-        noise = list(noise) if exists(noise) else None
+        noise_fn = noise if callable(noise) else None
+        noise = list(noise) if exists(noise) and not exists(noise_fn) else None
         if start_at_unet_number > 1:
             assert start_at_unet_number <= num_unets, 'must start a unet that is less than the total number of unets'
             assert not exists(stop_at_unet_number) or start_at_unet_number <= stop_at_unet_number
@@ -284,13 +404,16 @@ class ElucidatedImagen(nn.Module):
                 t_cpu = torch.full((batch_size,), float(lowres_sample_noise_level))
                 lowres_noise_times = t_cpu.to(device)                              # the RAW time at sampling (:652, 680)
                 lowres_cond_img = self.normalize_img(self._resize(img, image_size, frame_dims[0])).float().to(device)
-                ln = noise.pop(0).to(device).float() if exists(noise) else torch.randn_like(lowres_cond_img)
+                if exists(noise_fn):
+                    ln = noise_fn(tuple(lowres_cond_img.shape)).to(device).float()
+                else:
+                    ln = noise.pop(0).to(device).float() if exists(noise) else torch.randn_like(lowres_cond_img)
                 lowres_cond_img = self._noise_lowres(lowres_cond_img, t_cpu, ln)
             if exists(unet_init):
                 unet_init = self._resize(unet_init, image_size, frame_dims[0])
             shape = (batch_size, self.channels, *frame_dims, image_size, image_size)
             n_draws = len(list(zip(range(self.hparams[unet_number - 1].num_sample_steps)))) - default(unet_skip, 0) + 1
-            unet_noise = [noise.pop(0) for _ in range(n_draws)] if exists(noise) else None
+            unet_noise = noise_fn if exists(noise_fn) else ([noise.pop(0) for _ in range(n_draws)] if exists(noise) else None)
             img = self.one_unet_sample(unet, shape, unet_number=unet_number, init_images=unet_init, skip_steps=unet_skip,
                                        sigma_min=smin, sigma_max=smax, cond_scale=unet_cond_scale, dynamic_threshold=dynamic_threshold,
                                        use_tqdm=use_tqdm, noise=unet_noise,

@@ -46,7 +46,16 @@ Beyond the scripts (``blend`` / ``samples``; the defaults leave every line above
 * ``sampler='dpmpp2m'`` (DPM-Solver++ 2M, the second-order multistep solver; ``Imagen.p_sample_loop``) works in every mode above: the
   non-joint modes only pass it to ``sample``; a joint chain made with ``window_denoiser(sampler='dpmpp2m', sample_steps=K)`` keeps the
   fused x0 volume of the previous step and takes ``ops.volume_joint_multistep``, x_next = kx x + k0 x0 + kp x0_prev, per step.  It is
-  deterministic after draw 0, and at stride = patch again the independent chain bit for bit.
+  deterministic after draw 0, and at stride = patch again the independent chain bit for bit;
+* the EDM family (``ElucidatedImagen``) takes the same modes.  ``ElucidatedImagen.sample(noise=source)`` accepts the anchored source
+  (exactly one U-Net sampled): draw 0 is the low-res augmentation noise, draw 1 the initial image, draw 2 + i the eps of Heun step i.  A
+  joint chain made with ``ElucidatedImagen.window_denoiser()`` / ``ImagenTrainer.window_denoiser()`` (``den.heun``) runs the stochastic
+  Heun sampler on three volumes -- images_hat, images_next and the fused prediction -- and fuses the windows after BOTH U-Net
+  evaluations of a step: ``ops.volume_joint_heun_init`` (initial image + first churn), then per step the windows of images_hat evaluated
+  at sigma_hat and ``ops.volume_joint_heun`` phase 1 (predictor), the windows of images_next evaluated at sigma_next and phase 2
+  (corrector + the next step's churn) -- 2 T - 1 fused launches for T steps, twice the U-Net evaluations of a first-order chain.  The
+  low-res noise of a batch is draw 0 of the field at its windows, recomputed per evaluation; the draw numbering is the source's, so
+  at stride = patch the joint chain is ``sample(noise=source)`` per window, bit for bit.
 """
 import numpy as np
 import torch
@@ -313,6 +322,11 @@ class VolumeInference:
         x0_vol = torch.empty(shape, dtype=torch.float32, device=dev) if self_cond or multistep else None
         mean_io = m2_io = out_std = None
         for s in range(S):
+            if getattr(den, 'heun', False):                  # the EDM family: three volumes, two evaluations per step (_heun_chain)
+                x = self._heun_chain(den, vol, batches, kept, split, y, slot, taps, s)
+                mean_io, m2_io, out_std = ops.volume_joint_finish(den.finish(x), slot, vol, P, self.overlap, self.mean, self.std,
+                                                                  float(min_val), float(fill), s, S, mean_io, m2_io, want_std)
+                continue
             x = ops.volume_joint_init(shape, self.seed, sample=s, device=dev)               # draw 0
             for i in range(den.num_steps):
                 for lo, idx in batches:
@@ -334,6 +348,51 @@ class VolumeInference:
             mean_io, m2_io, out_std = ops.volume_joint_finish(den.finish(x), slot, vol, P, self.overlap, self.mean, self.std,
                                                               float(min_val), float(fill), s, S, mean_io, m2_io, want_std)
         return mean_io, out_std
+
+    def _heun_chain(self, den, vol, batches, kept, split, y, slot, taps, s):
+        """Sample ``s`` of the joint chain of an EDM window denoiser (``den.heun``; ``ElucidatedImagen.window_denoiser``): the stochastic
+        Heun sampler on three volumes -- ``xh`` (images_hat), ``xn`` (images_next) and ``x0`` (the fused prediction, which
+        self-conditioning gathers) -- advanced in place by ``ops.volume_joint_heun``.  Phase 0 makes the initial image and the churn of
+        step 0; every step gathers the ``xh`` windows, evaluates them at sigma_hat into ``y`` and takes the predictor (phase 1), then,
+        unless sigma_next is 0, gathers the ``xn`` windows, evaluates them at sigma_next and takes the corrector together with the next
+        step's churn (phase 2): 2 T - 1 fused launches for T steps.  The low-res augmentation noise of a batch is draw 0 of the anchored
+        field at its windows, recomputed where it is used; the initial image is draw ``den.draw_base`` and the eps of step i draw
+        ``den.draw_base + 1 + i`` -- the numbering ``AnchoredNoise.source`` gives ``ElucidatedImagen.sample(noise=source)``.  Returns the
+        volume the chain ends in."""
+        dev, shape, P = vol.device, tuple(vol.shape), self.patch
+        coefs = den.coefs.tolist()
+        lo_c, hi_c, mode_c = den.clamp
+        self_cond, base, T = bool(getattr(den, 'self_cond', False)), int(den.draw_base), den.num_steps
+        xh = ops.volume_joint_heun_init(shape, den.sigma0, coefs[0][0], self.seed, draw=base, sample=s, device=dev)
+        xn, x0_vol = torch.empty_like(xh), torch.empty_like(xh)
+
+        def evaluate(state, i, stage):
+            for lo, idx in batches:
+                n = idx.shape[0]
+                xw = split(ops.patch_gather(state, idx, P, 0., 1.)[0])                   # (v - 0) / 1: the state's own bits
+                lw = split(ops.patch_gather(vol, idx, P, self.mean, self.std)[0])
+                sc = split(ops.patch_gather(x0_vol, idx, P, 0., 1.)[0]) if self_cond and (i > 0 or stage == 1) else None
+                ln = None
+                if base:                                     # block mode: the sub-volumes' own origins, as in _sample
+                    org = sub_volume_origins(kept[lo], self.factor, self.sub) if self.block_mode else kept[lo:lo + n]
+                    ln = ops.anchored_noise(org, lw.shape[1], self.sub, *shape, self.seed, draw=0, sample=s, device=dev)
+                pred = den.x0(xw, lw, i, self_cond=sc, stage=stage, lowres_noise=ln).float()
+                if self.block_mode:                                                   # test_all.py:229-231, 265-266
+                    pred = merge_sub_volumes(pred, original_shape=(1, 1, P, P, P))
+                y[lo:lo + n] = pred.reshape(n, P, P, P)
+
+        corrected = False
+        for i in range(T):
+            _, a1, b1, a2, b2, c2, d2 = coefs[i]
+            evaluate(xh, i, 0)
+            ops.volume_joint_heun(y, slot, taps, xh, xn, x0_vol, 1, (a1, b1), 0., lo_c, hi_c, mode_c, self.overlap)
+            corrected = float(den.sched[i][1]) != 0
+            if corrected:                                    # no corrector on the step that ends at sigma 0
+                evaluate(xn, i, 1)
+                more = i + 1 < T
+                ops.volume_joint_heun(y, slot, taps, xh, xn, x0_vol, 2, (a2, b2, c2, d2), coefs[i + 1][0] if more else 0., lo_c, hi_c,
+                                      mode_c, self.overlap, self.seed, draw=base + 2 + i if more else 0, sample=s)
+        return xh if corrected else xn
 
 
 def eval_crop(size0):

@@ -2464,6 +2464,55 @@ def volume_joint_multistep(y, slot, taps, x_t, x0_prev, kx, k0, kp, lo, hi, clam
     return out, x0_out
 
 
+def volume_joint_heun_init(shape, sigma0, kc, seed, draw=0, sample=0, device=None):
+    """The first ``images_hat`` of a joint Heun chain (phase 0 of ``diqt_volume_joint_heun``): fp32 [D,H,W],
+    ``(sigma0 n(draw)) + kc n(draw + 1)`` with n the volume-anchored normals of channel 0 -- the initial image as
+    ``ElucidatedImagen.one_unet_sample`` stores it, then the churn of step 0."""
+    shape = tuple(int(s) for s in shape)
+    if len(shape) != 3 or min(shape) < 1:
+        raise ValueError(f"volume_joint_heun_init: shape must be a positive (D, H, W), got {shape!r}")
+    seed, draw, sample = _noise_key("volume_joint_heun_init", seed, draw, sample)
+    if draw + 1 >= 2 ** 32:
+        raise ValueError(f"volume_joint_heun_init: draw + 1 must fit 32 bits (unsigned), got draw {draw}")
+    if not torch.cuda.is_available():
+        raise RuntimeError("diffusioniqt_amd.ops.volume_joint_heun_init runs on the MI355X only (no CPU fallback)")
+    device = torch.device('cuda' if device is None else device)
+    with torch.cuda.device(device):
+        out = torch.empty(shape, dtype=torch.float32, device=device)
+        _lib.call("diqt_volume_joint_heun", None, None, None, out, None, None, 0, 0, *shape, 0, 0, 0, 0, 0, float(sigma0), 0.0, 0.0, 0.0,
+                  float(kc), 0.0, 0.0, 0, seed, draw, sample, _stream())
+    return out
+
+
+def volume_joint_heun(y, slot, taps, xh, xn, x0, phase, coefs, kc, lo, hi, clamp_mode, stride, seed=0, draw=0, sample=0):
+    """The predictor (``phase`` 1) or the corrector with the next churn (``phase`` 2) of the stochastic Heun sampler on the joint state
+    of a whole volume (include/diqt.h, diqt_volume_joint_heun), IN PLACE on the three [D,H,W] volumes ``xh`` (images_hat), ``xn``
+    (images_next) and ``x0`` (the fused prediction).  ``y`` / ``slot`` / ``taps`` / ``stride`` / the clamp as in ``volume_joint_step``.
+    Phase 1, ``coefs = (a, b)``: x0 = the weighted mean of the clamped predictions, xn = a xh + b x0.  Phase 2, ``coefs = (a, b, c, d)``:
+    x = (a xh + b x0 + c xn) + d x0b with x0b the weighted mean, then xh = x + kc n with n the volume-anchored normal of (seed, draw,
+    sample) (xh = x when ``kc`` is 0) and x0 = x0b.  Uncovered voxels: phase 1 copies xh to xn, phase 2 leaves xh; both write x0 = 0.
+    Returns ``(xh, xn, x0)``.  One launch, bit-reproducible."""
+    phase = int(phase)
+    if phase not in (1, 2):
+        raise ValueError(f"volume_joint_heun: phase must be 1 (predictor) or 2 (corrector), got {phase!r}; phase 0 is volume_joint_heun_init")
+    N, P, stride = _joint_windows("volume_joint_heun", y, slot, taps, xh, clamp_mode, stride)
+    seed, draw, sample = _noise_key("volume_joint_heun", seed, draw, sample)
+    _joint_slots("volume_joint_heun", slot, N)
+    coefs = tuple(float(v) for v in coefs)
+    if len(coefs) != 2 * phase:
+        raise ValueError(f"volume_joint_heun: phase {phase} takes {2 * phase} coefficients, got {len(coefs)}")
+    for t, name in ((xn, 'xn'), (x0, 'x0')):
+        _chk(t)
+        if t.shape != xh.shape or not t.is_contiguous():
+            raise ValueError(f"volume_joint_heun: {name} must be a contiguous tensor of xh's shape")
+    if len({xh.data_ptr(), xn.data_ptr(), x0.data_ptr()}) != 3:
+        raise ValueError("volume_joint_heun: xh, xn and x0 are three different volumes")
+    _lib.call("diqt_volume_joint_heun", y if N else None, slot, taps, xh, xn, x0, phase, N, *xh.shape, P, stride, *slot.shape,
+              *(coefs + (0.0, 0.0))[:4], float(kc) if phase == 2 else 0.0, float(lo), float(hi), int(clamp_mode), seed, draw, sample,
+              _stream())
+    return xh, xn, x0
+
+
 def volume_joint_finish(x, slot, vol, P, stride, mean, std, min_val, fill, s, S, mean_io=None, m2_io=None, want_std=False):
     """The end of sample ``s`` of ``S`` joint chains (include/diqt.h, diqt_volume_joint_finish): the finished state ``x`` [D,H,W] with
     ``fill`` where no kept window of ``slot`` covers and ``min_val`` on the background of the raw ``vol`` enters the running Welford

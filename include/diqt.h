@@ -638,6 +638,26 @@ int diqt_volume_joint_step(const float* y, const int* slot, const float* taps, c
 int diqt_volume_joint_multistep(const float* y, const int* slot, const float* taps, const float* x_t, const float* x0_prev,
                                 float* x_next, float* x0_out, int N, int D, int H, int W, int P, int stride, int G0, int G1, int G2,
                                 float kx, float k0, float kp, float lo, float hi, int clamp_mode, void* stream);
+/* The stochastic Heun sampler of the EDM family (Karras et al. 2022; elucidated_imagen.py:382-532) on the joint state: a churn, a
+ * predictor and a corrector per step, two U-Net evaluations.  The state is three [D][H][W] volumes, all updated in place (every thread
+ * reads only its own voxel of each, then writes it): xh = images_hat, xn = images_next, x0 = the fused prediction.  Window walk,
+ * clamp, lattice check, launch geometry and the normals n(draw) are diqt_volume_joint_step's.  `phase`, uniform over the launch:
+ *   0  xh = fmaf(kc, n(draw + 1), a * n(draw)) with the product rounded first (a = sigma0: the initial image as the sampler stores
+ *      it, then the churn of step 0; no second Philox call when kc == 0).  Every voxel; y, slot, taps, xn, x0, N, P, stride, G*, b, c,
+ *      d and the clamp are ignored.
+ *   1  after the stage-0 evaluations (y = the windows' predictions at sigma_hat): covered voxel x0 = num / den,
+ *      xn = fmaf(b, x0, a * xh), the Euler predictor with (a, b) = (1 + r, -r); uncovered voxel xn = xh, x0 = 0.  c, d, kc, seed,
+ *      draw and sample are ignored.
+ *   2  after the stage-1 evaluations (y = the predictions at sigma_next): covered voxel x0b = num / den,
+ *      t = fmaf(c, xn, fmaf(b, x0, a * xh)), x = fmaf(d, x0b, t), the corrector with (a, b, c, d) = (1 + r/2, -r/2, r2, -r2); then the
+ *      next step's churn xh = fmaf(kc, n(draw), x) (xh = x, no Philox call, when kc == 0) and x0 = x0b.  Uncovered voxel: xh is left
+ *      as it is, x0 = 0.
+ * These are the roundings of the diqt_axpby3 sequence of the per-window sampler, so with stride = P and unit taps the chain is that
+ * sampler's bit for bit.  Null pointers: DIQT_E_ALIGN; a lattice that does not match: DIQT_E_SHAPE; phase outside {0, 1, 2} or
+ * clamp_mode outside {0, 1}: DIQT_E_UNSUPPORTED; phase 0 with draw == 2^32 - 1: DIQT_E_SHAPE.                                      */
+int diqt_volume_joint_heun(const float* y, const int* slot, const float* taps, float* xh, float* xn, float* x0, int phase, int N, int D,
+                           int H, int W, int P, int stride, int G0, int G1, int G2, float a, float b, float c, float d, float kc,
+                           float lo, float hi, int clamp_mode, unsigned long long seed, unsigned draw, unsigned sample, void* stream);
 /* The end of sample s (0-based) of S joint chains: per voxel r = min_val where vol (RAW, may be NULL) has (vol - mean) / std ==
  * min_val (diqt_background_reset's expression), else x (the finished state) where a kept window (slot >= 0) covers the voxel, else
  * `fill`; then diqt_volume_blend's Welford update in sample order, delta = r - m; m += delta / (s + 1); m2 = fma(delta, r - m, m2)
