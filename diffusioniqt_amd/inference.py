@@ -4,59 +4,65 @@ gathered / normalised / rejected by one kernel, sampled in batches, stitched by 
 overlap-crop rules, and the background is reset in place.  One job per volume; several volumes or patch ranges shard over
 GPUs with no collective.
 
-Semantics kept from the scripts:
+The script semantics (the defaults; every mode below keeps the first four lines):
 * candidate origins: ``range(0, N - P + 1, overlap)`` per axis, i outermost (data.py:157-160; ``Eval.overlap`` is the STRIDE);
 * a candidate is dropped when fewer than 5 % of its RAW voxels are non-zero (data.py:187-191);
 * patches are z-scored with ``Data.mean/std`` (data.py:165-169); the output volume starts at ``(0 - mean) / std``;
+* voxels whose normalised low-res value equals the volume minimum are reset to it (test_all.py:300);
 * ``Train.batch_sample``: the window is ``patch_size_sub * batch_sample_factor`` (96), each block is split into 27 sub-volumes
   for the sampler and merged back (utils_mine.py:25-67); blocks overlap, and each writes its interior ``[op : P - op]``
   (``op = overlap // 2``) except on faces that touch the volume boundary (test_all.py:267-296);
 * without ``batch_sample`` and with ``overlap >= patch`` patches are placed whole (test_all.py:262-263).  The script's
   overlap < patch branch of that mode raises on its first interior patch (a 3-element tensor in a boolean ``or``,
   test_all.py:241) — here it applies the same per-face crop rule as the block mode instead;
-* voxels whose normalised low-res value equals the volume minimum are reset to it (test_all.py:300);
 * ``evaluate_volume`` scores the stitched volume as the script's ``eval`` does (test_all.py:47-62): centre crop, PSNR, MS-SSIM of
   the min-max normalised pair — without LPIPS (no VGG weights here).
 
-Beyond the scripts (``blend`` / ``samples``; the defaults leave every line above as it is):
-* ``blend='gaussian'`` / ``'constant'`` replaces crop-and-overwrite by weighted overlap blending: whole windows contribute (no crop
-  margins), each voxel is the weighted mean of the windows that cover it, with the separable weight ``taps[i] taps[j] taps[k]``
-  (``blend_taps``: a Gaussian importance map of sigma ``sigma_scale * P`` with maximum 1, or all ones = the plain mean).  Every kept
-  window's prediction stays in HBM and ONE gather-side launch (``ops.volume_blend``) reduces them per output voxel in candidate
-  order — no atomics, bit-reproducible, independent of ``Eval.batch_size``; the background reset is fused into it.  A voxel that no
-  kept window covers keeps the fill value ``(0 - mean) / std``;
-* ``samples=S`` draws every batch S times (sample 0 of a batch, then sample 1, ...); the result is the per-voxel mean of the S
-  blended volumes and, with ``return_std=True``, their unbiased standard deviation — the uncertainty map of a stochastic sampler;
-* ``noise='anchored'`` hands the sampler a noise source tied to the VOLUME instead of letting every batch draw its own: the value at
-  global voxel (z, y, x) of draw k and sample s is a pure function of (seed, z, y, x, k, s) (``AnchoredNoise``, one Philox4x32-10 call
-  per voxel in ``ops.anchored_noise``), so all windows that cover a voxel start from — and, in a stochastic sampler, are pushed by —
-  the same numbers, whatever ``Eval.batch_size`` is, whichever windows the non-zero filter kept and in whatever order or on
-  whichever rank they run.  What is left of the disagreement between overlapping windows is what the network does differently with
-  different context; the ``samples = S`` fields are independent of each other and coherent across windows;
-* ``joint=True`` (with a blend mode and ``noise='anchored'``) removes that remainder at its source: instead of running every window's
-  reverse chain alone and blending finished patches, ONE noisy state of the whole volume is kept and the windows' x0 predictions are
-  fused at EVERY step (MultiDiffusion, Bar-Tal et al. 2023).  The second constructor argument is then a window denoiser
-  (``Imagen.window_denoiser`` / ``ImagenTrainer.window_denoiser``: scalar step coefficients, the clamp, ``x0`` and ``finish``).  Per
-  sample: the state starts as draw 0 of the anchored field; every step gathers the kept windows of the state, evaluates the U-Net on
-  them in ``Eval.batch_size`` batches (N windows x T steps evaluations, as many as the independent windows cost) and ONE
-  ``ops.volume_joint_step`` launch blends the predictions per voxel with the blend weights, takes the sampler step with draw
-  ``i + 1`` and writes the next state in place; ``ops.volume_joint_finish`` applies the fill / background rules and the statistics
-  over the samples.  The draw numbering is ``AnchoredNoise.source``'s, so with stride = patch (no overlap) the joint chain IS the
-  independent one, bit for bit;
-* ``sampler='dpmpp2m'`` (DPM-Solver++ 2M, the second-order multistep solver; ``Imagen.p_sample_loop``) works in every mode above: the
-  non-joint modes only pass it to ``sample``; a joint chain made with ``window_denoiser(sampler='dpmpp2m', sample_steps=K)`` keeps the
-  fused x0 volume of the previous step and takes ``ops.volume_joint_multistep``, x_next = kx x + k0 x0 + kp x0_prev, per step.  It is
-  deterministic after draw 0, and at stride = patch again the independent chain bit for bit;
-* the EDM family (``ElucidatedImagen``) takes the same modes.  ``ElucidatedImagen.sample(noise=source)`` accepts the anchored source
-  (exactly one U-Net sampled): draw 0 is the low-res augmentation noise, draw 1 the initial image, draw 2 + i the eps of Heun step i.  A
-  joint chain made with ``ElucidatedImagen.window_denoiser()`` / ``ImagenTrainer.window_denoiser()`` (``den.heun``) runs the stochastic
-  Heun sampler on three volumes -- images_hat, images_next and the fused prediction -- and fuses the windows after BOTH U-Net
-  evaluations of a step: ``ops.volume_joint_heun_init`` (initial image + first churn), then per step the windows of images_hat evaluated
-  at sigma_hat and ``ops.volume_joint_heun`` phase 1 (predictor), the windows of images_next evaluated at sigma_next and phase 2
-  (corrector + the next step's churn) -- 2 T - 1 fused launches for T steps, twice the U-Net evaluations of a first-order chain.  The
-  low-res noise of a batch is draw 0 of the field at its windows, recomputed per evaluation; the draw numbering is the source's, so
-  at stride = patch the joint chain is ``sample(noise=source)`` per window, bit for bit.
+Blend (``blend='gaussian'`` / ``'constant'``) replaces crop-and-overwrite by weighted overlap blending: whole windows contribute (no
+crop margins), each voxel is the weighted mean of the windows that cover it, with the separable weight ``taps[i] taps[j] taps[k]``
+(``blend_taps``: a Gaussian importance map of sigma ``sigma_scale * P`` with maximum 1, or all ones = the plain mean).  Every kept
+window's prediction stays in HBM and ONE gather-side launch (``ops.volume_blend``) reduces them per output voxel in candidate order —
+no atomics, bit-reproducible, independent of ``Eval.batch_size``; the background reset is fused into it.  A voxel that no kept window
+covers keeps the fill value ``(0 - mean) / std``.
+
+Samples (``samples=S``, with a blend mode) draws every batch S times (sample 0 of a batch, then sample 1, ...); the result is the
+per-voxel mean of the S blended volumes and, with ``return_std=True``, their unbiased standard deviation — the uncertainty map of a
+stochastic sampler.
+
+Anchored noise (``noise='anchored'``) hands the sampler a noise source tied to the VOLUME instead of letting every batch draw its own:
+the value at global voxel (z, y, x) of draw k and sample s is a pure function of (seed, z, y, x, k, s) (``AnchoredNoise``, one
+Philox4x32-10 call per voxel in ``ops.anchored_noise``), so all windows that cover a voxel start from — and, in a stochastic sampler,
+are pushed by — the same numbers, whatever ``Eval.batch_size`` is, whichever windows the non-zero filter kept and in whatever order
+or on whichever rank they run.  What is left of the disagreement between overlapping windows is what the network does differently
+with different context; the ``samples = S`` fields are independent of each other and coherent across windows.  Any sampler that
+takes ``noise=source`` works, in every mode: ``sampler='dpmpp2m'`` (DPM-Solver++ 2M, the second-order multistep solver;
+``Imagen.p_sample_loop``) is only passed on to ``sample``, and ``ElucidatedImagen.sample(noise=source)`` accepts the source when
+exactly one U-Net is sampled: draw 0 is the low-res augmentation noise, draw 1 the initial image, draw 2 + i the eps of Heun step i.
+
+Joint (``joint=True``, with a blend mode and ``noise='anchored'``) removes that remainder at its source: instead of running every
+window's reverse chain alone and blending finished patches, ONE noisy state of the whole volume is kept and the windows' x0
+predictions are fused at EVERY step (MultiDiffusion, Bar-Tal et al. 2023).  The second constructor argument is then a window
+denoiser (``Imagen.window_denoiser`` / ``ImagenTrainer.window_denoiser``: scalar step coefficients, the clamp, ``x0`` and ``finish``; the
+whole protocol is in the docstring of ``VolumeInference``).  Per sample a chain runs on whole volumes: every evaluation gathers the kept
+windows of the state, runs the U-Net on them in ``Eval.batch_size`` batches, and ONE fused launch blends the predictions per voxel with
+the blend weights and advances the state in place; ``ops.volume_joint_finish`` applies the fill / background rules and the statistics
+over the samples.  The draw numbering is ``AnchoredNoise.source``'s, so with stride = patch (no overlap) every joint chain IS the
+independent one, bit for bit.  The three chains:
+* first order (``window_denoiser(sampler='ddim', sample_steps=K)`` or the ancestral default): the state starts as draw 0 of the
+  anchored field and ``ops.volume_joint_step`` takes the sampler step with draw ``i + 1`` — N windows x T steps evaluations, as many
+  as the independent windows cost;
+* multistep (``window_denoiser(sampler='dpmpp2m', sample_steps=K)``, ``den.multistep``): keeps the fused x0 volume of the previous step
+  and takes ``ops.volume_joint_multistep``, x_next = kx x + k0 x0 + kp x0_prev, per step.  It is deterministic after draw 0;
+* Heun (the EDM family, ``ElucidatedImagen.window_denoiser()``, ``den.heun``): the stochastic Heun sampler on three volumes --
+  images_hat, images_next and the fused prediction -- fusing the windows after BOTH U-Net evaluations of a step:
+  ``ops.volume_joint_heun_init`` (initial image + first churn), then per step the windows of images_hat evaluated at sigma_hat and
+  ``ops.volume_joint_heun`` phase 1 (predictor), the windows of images_next evaluated at sigma_next and phase 2 (corrector + the next
+  step's churn) -- 2 T - 1 fused launches for T steps, twice the U-Net evaluations of a first-order chain.  The low-res noise of a
+  batch is draw 0 of the field at its windows, recomputed per evaluation; at stride = patch the chain is ``sample(noise=source)`` per
+  window.
 """
+from types import SimpleNamespace
+
 import numpy as np
 import torch
 
@@ -135,7 +141,67 @@ def sub_volume_origins(origin, factor, sub):
     return (np.asarray(origin).reshape(1, 3) + off).astype(np.int32)
 
 
+class _Windows:
+    """The window plan of one ``VolumeInference`` call: the volume ``shape`` / ``device``; the candidate ``origins`` on their ``lattice``
+    (candidate order = lattice order); ``keep``, the 5 % filter's verdict from ONE ``ops.patch_gather`` over all candidates; ``kept``
+    [N,3] (after ``patch_slice``); ``fill`` / ``min_val``, the normalised empty voxel and volume minimum in fp32 arithmetic, as Python
+    floats; under a blend mode the device ``slot`` table (a kept window's row, -1: dropped) and ``taps``; ``batches``, the ``(lo, host
+    origins, device origins)`` of every sampler call -- ``Eval.batch_size`` windows, or ONE block in block mode (overlapping blocks are
+    written one launch at a time in candidate order: later blocks overwrite, as in the script).  ``_joint`` adds ``x0_vol``."""
+
+    def __init__(self, inf, vol, patch_slice=None):
+        dev, P = vol.device, inf.patch
+        self.shape, self.device = tuple(vol.shape), dev
+        self.origins = sliding_window_origins(self.shape, P, inf.overlap)
+        self.lattice = tuple(len(range(0, s - P + 1, inf.overlap)) for s in self.shape)
+        _, nz = ops.patch_gather(vol, torch.from_numpy(self.origins).to(dev), P, inf.mean, inf.std, want_patches=False, want_nonzero=True)
+        self.keep = (nz.cpu().numpy().astype(np.float64) / float(P ** 3)) >= inf.ratio      # data.py:187-191
+        self.kept = self.origins[self.keep]
+        if patch_slice is not None:
+            rank, world = patch_slice
+            self.kept = self.kept[rank::world]
+        self.N = self.kept.shape[0]
+        mean32, std32 = np.float32(inf.mean), np.float32(inf.std)
+        self.fill = float((np.float32(0.) - mean32) / std32)
+        self.min_val = float((np.float32(float(ops.min_value(vol).item())) - mean32) / std32)   # monotone map: min of the normalised volume
+        self.slot = self.taps = None
+        if inf.blend is not None:
+            slot = np.full(self.origins.shape[0], -1, dtype=np.int32)
+            slot[self.keep] = np.arange(self.N, dtype=np.int32)
+            self.slot = torch.from_numpy(slot.reshape(self.lattice)).to(dev)
+            self.taps = torch.from_numpy(blend_taps(P, inf.blend, inf.sigma_scale)).to(dev)
+        per_call = 1 if inf.block_mode else inf.batch
+        hosts = [(lo, np.ascontiguousarray(self.kept[lo:lo + per_call])) for lo in range(0, self.N, per_call)]
+        self.batches = [(lo, o, torch.from_numpy(o).to(dev)) for lo, o in hosts]
+        self._block = (inf.factor, inf.sub) if inf.block_mode else None
+
+    def noise_origins(self, origins):
+        """Where the noise of the batch at ``origins`` belongs: block mode (ONE block, sampled split) -> its sub-volumes' origins."""
+        return sub_volume_origins(origins[0], *self._block) if self._block else origins
+
+
 class VolumeInference:
+    """The stitched, z-scored prediction of one raw volume; the modes are in the module docstring.  What ``joint=True`` reads of its
+    window denoiser ``den``:
+    * required (the constructor checks them): ``num_steps``; ``coefs``, a host tensor with one row (kx, k0, kn) per step; ``clamp = (lo,
+      hi, mode)``, passed to the fused launch; ``x0(img, lowres, i, self_cond=None)``, the x0 prediction of a batch of windows at step i;
+      ``finish(x)``, applied to the volume a chain ends in;
+    * optional, False when absent: ``self_cond`` (the windows of the last fused x0 volume are passed as ``self_cond=``), ``multistep``
+      (``coefs`` rows are (kx, k0, kp)) and ``heun``;
+    * with ``heun``: ``coefs`` rows (kc, a1, b1, a2, b2, c2, d2); ``sigma0``; ``sched`` rows (sigma, sigma_next, gamma), sigma_next == 0
+      meaning no corrector; ``draw_base`` (1 when draw 0 is the low-res augmentation noise: the initial image is draw ``draw_base``, the
+      eps of step i draw ``draw_base + 1 + i``); ``x0`` also takes ``stage=`` (0: at sigma_hat, 1: at sigma_next) and ``lowres_noise=``."""
+    _DENOISER = ('num_steps', 'coefs', 'clamp', 'x0', 'finish')
+
+    @staticmethod
+    def _protocol(den):
+        """``den`` as the chains use it: the host tables as Python numbers, the optional attributes defaulted."""
+        p = SimpleNamespace(num_steps=den.num_steps, coefs=den.coefs.tolist(), clamp=tuple(den.clamp), x0=den.x0, finish=den.finish,
+                            **{a: bool(getattr(den, a, False)) for a in ('self_cond', 'multistep', 'heun')})
+        if p.heun:
+            p.draw_base, p.sigma0, p.sched = int(den.draw_base), den.sigma0, den.sched
+        return p
+
     def __init__(self, configs, sample_fn, nonzero_ratio=0.05, blend=None, sigma_scale=0.125, samples=1, noise=None, seed=0, joint=False):
         """``sample_fn(lr_patches [B,1,S,S,S]) -> hr_patches`` — e.g. ``lambda x: trainer.sample(batch_size=x.shape[0],
         start_image_or_video=x, start_at_unet_number=2)[0]`` (test_all.py:234).  ``blend`` / ``sigma_scale`` / ``samples``: weighted
@@ -144,8 +210,7 @@ class VolumeInference:
         e.g. ``lambda x, noise=None: trainer.sample(batch_size=x.shape[0], start_image_or_video=x, start_at_unet_number=2,
         sampler='ddim', sample_steps=50, noise=noise)[0]``.  ``joint=True`` (needs a blend mode and ``noise='anchored'``): the second
         argument is a window denoiser instead -- ``trainer.window_denoiser(sampler='ddim', sample_steps=50)`` or, second order,
-        ``trainer.window_denoiser(sampler='dpmpp2m', sample_steps=16)`` -- and the windows are sampled in lockstep on one noisy state
-        of the whole volume, see the module docstring."""
+        ``trainer.window_denoiser(sampler='dpmpp2m', sample_steps=16)`` -- see the class docstring."""
         if noise not in NOISE_MODES:
             raise ValueError(f"VolumeInference: noise must be None or 'anchored', got {noise!r}")
         self.noise, self.seed = noise, int(seed)
@@ -165,7 +230,7 @@ class VolumeInference:
                 raise ValueError("VolumeInference: joint=True needs a blend mode ('gaussian' or 'constant'), the weights that fuse the "
                                  "windows' predictions at every step, and noise='anchored', the volume-wide field the one state starts "
                                  "from and is pushed by")
-            missing = [a for a in ('num_steps', 'coefs', 'clamp', 'x0', 'finish') if not hasattr(sample_fn, a)]
+            missing = [a for a in self._DENOISER if not hasattr(sample_fn, a)]
             if missing:
                 raise ValueError(f"VolumeInference: joint=True takes a window denoiser (Imagen.window_denoiser / "
                                  f"ImagenTrainer.window_denoiser) as its second argument; {type(sample_fn).__name__} lacks {missing}")
@@ -184,8 +249,10 @@ class VolumeInference:
     @torch.no_grad()
     def __call__(self, lowres_raw, patch_slice=None, return_std=False):
         """lowres_raw: fp32 [D,H,W] raw intensities on the GPU.  Returns the stitched, z-scored prediction [D,H,W].
-        ``patch_slice`` (rank, world) restricts the work to every world-th kept patch (multi-GPU sharding; merge the shards with
-        the returned mask-free volumes by taking, per voxel, the value of the rank that owns it — see ``shard_volumes``).
+        ``patch_slice`` (rank, world) restricts the work to every world-th kept patch (multi-GPU sharding); a rank's volume holds the
+        fill value ``(0 - mean) / std`` where it wrote nothing.  Without overlap (stride >= patch) a voxel has one owner and shards
+        merge as ``torch.where(a != fill, a, b)``; with overlap the owner is the rank of the last kept window in candidate order whose
+        cropped interior covers the voxel, and nothing here does that merge -- shard whole volumes over the ranks instead.
         ``return_std`` (blend modes, ``samples >= 2``): returns ``(mean, std)``, the per-voxel statistics over the samples."""
         if return_std and (self.blend is None or self.samples < 2):
             raise ValueError("VolumeInference: return_std needs a blend mode and samples >= 2")
@@ -197,201 +264,133 @@ class VolumeInference:
             mean, dev = (self._joint if self.joint else self._blended)(lowres_raw, return_std)
             return (mean, dev) if return_std else mean
         vol = lowres_raw.float().contiguous()
-        dev = vol.device
-        shape = tuple(vol.shape)
+        win = _Windows(self, vol, patch_slice)
         P = self.patch
-        origins = sliding_window_origins(shape, P, self.overlap)
-        idx_all = torch.from_numpy(origins).to(dev)
-        _, nz = ops.patch_gather(vol, idx_all, P, self.mean, self.std, want_patches=False, want_nonzero=True)
-        keep = (nz.cpu().numpy().astype(np.float64) / float(P ** 3)) >= self.ratio          # data.py:187-191
-        kept = origins[keep]
-        if patch_slice is not None:
-            rank, world = patch_slice
-            kept = kept[rank::world]
-        margins = crop_margins(kept, shape, P, self.overlap)
-        mean32, std32 = np.float32(self.mean), np.float32(self.std)
-        pred = torch.full(shape, float((np.float32(0.) - mean32) / std32), dtype=torch.float32, device=dev)
-        # overlapping blocks are written one launch at a time in candidate order (later blocks overwrite, as in the script);
-        # non-overlapping patches go out in one launch per batch
-        per_call = 1 if self.block_mode else self.batch
+        margins = crop_margins(win.kept, win.shape, P, self.overlap)
+        pred = torch.full(win.shape, win.fill, dtype=torch.float32, device=win.device)
         # cropped interiors (width P - 2*(overlap//2), stride overlap) of neighbouring windows still overlap when the stride is
         # below half a patch: one scatter launch per patch, in candidate order, keeps "later overwrites" deterministic
         serial_scatter = (not self.block_mode) and self.overlap < P and P - 2 * (self.overlap // 2) > self.overlap
-        for lo in range(0, kept.shape[0], per_call):
-            o = np.ascontiguousarray(kept[lo:lo + per_call])
-            idx = torch.from_numpy(o).to(dev)
+        for lo, o, idx in win.batches:
             x, _ = ops.patch_gather(vol, idx, P, self.mean, self.std)
-            if self.block_mode:                                                           # test_all.py:229-231, 265-266
-                sub = convertVolume2subVolume(x, target_shape=(self.factor ** 3, 1, self.sub, self.sub, self.sub))
-                y = self._sample(sub, o, shape, 0)
-                y = merge_sub_volumes(y.float(), original_shape=(1, 1, P, P, P))
-            else:
-                y = self._sample(x, o, shape, 0)
-            y = y.float().contiguous()
-            mg = torch.from_numpy(np.ascontiguousarray(margins[lo:lo + per_call])).to(dev)
+            y = self._merge(self._sample(self._split(x), win, o, 0)).contiguous()
+            mg = torch.from_numpy(np.ascontiguousarray(margins[lo:lo + len(o)])).to(win.device)
             if serial_scatter:
-                for j in range(o.shape[0]):
+                for j in range(len(o)):
                     ops.patch_scatter(y[j:j + 1], idx[j:j + 1], mg[j:j + 1], pred, P)
             else:
                 ops.patch_scatter(y, idx, mg, pred, P)
-        min_raw = float(ops.min_value(vol).item())
-        min_val = (np.float32(min_raw) - mean32) / std32                                  # monotone map: min of the normalised volume
-        ops.background_reset(pred, vol, self.mean, self.std, float(min_val))             # test_all.py:300
+        ops.background_reset(pred, vol, self.mean, self.std, win.min_val)                # test_all.py:300
         return pred
 
-    def _sample(self, x, origins, volume_shape, s):
+    def _split(self, w):                                      # block mode: the block as the sampler sees it (test_all.py:229-231)
+        return convertVolume2subVolume(w, target_shape=(self.factor ** 3, 1, self.sub, self.sub, self.sub)) if self.block_mode else w
+
+    def _merge(self, y):                                      # fp32; block mode: the sub-volumes back as one block (test_all.py:265-266)
+        return merge_sub_volumes(y.float(), original_shape=(1, 1) + (self.patch,) * 3) if self.block_mode else y.float()
+
+    def _sample(self, x, win, origins, s):
         """One sampler call on the windows at ``origins`` (block mode: ONE block, already split into its sub-volumes), sample ``s``."""
         if self.noise is None:
             return self.sample_fn(x)
-        if self.block_mode:
-            origins = sub_volume_origins(origins[0], self.factor, self.sub)
-        src = AnchoredNoise(volume_shape, self.seed).source(origins, self.sub, sample=s, device=x.device)
+        src = AnchoredNoise(win.shape, self.seed).source(win.noise_origins(origins), self.sub, sample=s, device=x.device)
         return self.sample_fn(x, noise=src)
+
+    def _evaluate(self, win, volumes, call, out):
+        """The evaluation loop of the blend and joint paths.  Per batch: gather its windows from every ``(volume, mean, std)`` of
+        ``volumes`` (a None volume gives None), split them in block mode, ``call(*windows, host origins)``, merge the result back and
+        store it in rows ``lo : lo + n`` of ``out`` [N,P,P,P] -- of ``out[0]``, ``out[1]``, ... in turn when ``call`` yields several."""
+        P = self.patch
+        for lo, o, idx in win.batches:
+            n = len(o)
+            w = [None if v is None else self._split(ops.patch_gather(v, idx, P, m, sd)[0]) for v, m, sd in volumes]
+            res = call(*w, o)
+            for dst, pred in ((out, res),) if torch.is_tensor(res) else zip(out, res):
+                dst[lo:lo + n] = self._merge(pred).reshape(n, P, P, P)
 
     def _blended(self, lowres_raw, want_std):
         """The blend modes: every kept window's S predictions are kept in ``patches`` [S,N,P,P,P]; one ``ops.volume_blend`` launch
         stitches them (weights, mean / deviation over the samples, fill and background reset)."""
         vol = lowres_raw.float().contiguous()
-        dev = vol.device
-        shape = tuple(vol.shape)
+        win = _Windows(self, vol)
         P, S = self.patch, self.samples
-        origins = sliding_window_origins(shape, P, self.overlap)
-        lattice = tuple(len(range(0, s - P + 1, self.overlap)) for s in shape)
-        _, nz = ops.patch_gather(vol, torch.from_numpy(origins).to(dev), P, self.mean, self.std, want_patches=False, want_nonzero=True)
-        keep = (nz.cpu().numpy().astype(np.float64) / float(P ** 3)) >= self.ratio          # data.py:187-191
-        kept = origins[keep]
-        N = kept.shape[0]
-        slot = np.full(origins.shape[0], -1, dtype=np.int32)                                 # candidate order = lattice order
-        slot[keep] = np.arange(N, dtype=np.int32)
-        patches = torch.empty((S, N, P, P, P), dtype=torch.float32, device=dev)
-        per_call = 1 if self.block_mode else self.batch
-        for lo in range(0, N, per_call):
-            o = np.ascontiguousarray(kept[lo:lo + per_call])
-            idx = torch.from_numpy(o).to(dev)
-            n = idx.shape[0]
-            x, _ = ops.patch_gather(vol, idx, P, self.mean, self.std)
-            if self.block_mode:                                                           # test_all.py:229-231, 265-266
-                x = convertVolume2subVolume(x, target_shape=(self.factor ** 3, 1, self.sub, self.sub, self.sub))
-            for s in range(S):
-                y = self._sample(x, o, shape, s)
-                if self.block_mode:
-                    y = merge_sub_volumes(y.float(), original_shape=(1, 1, P, P, P))
-                patches[s, lo:lo + n] = y.float().reshape(n, P, P, P)
-        mean32, std32 = np.float32(self.mean), np.float32(self.std)
-        fill = (np.float32(0.) - mean32) / std32
-        min_val = (np.float32(float(ops.min_value(vol).item())) - mean32) / std32
-        taps = torch.from_numpy(blend_taps(P, self.blend, self.sigma_scale)).to(dev)
-        return ops.volume_blend(patches, torch.from_numpy(slot.reshape(lattice)).to(dev), taps, vol, self.mean, self.std,
-                                float(min_val), float(fill), self.overlap, want_std)
-
+        patches = torch.empty((S, win.N, P, P, P), dtype=torch.float32, device=win.device)
+        self._evaluate(win, [(vol, self.mean, self.std)], lambda x, o: (self._sample(x, win, o, s) for s in range(S)), patches)
+        return ops.volume_blend(patches, win.slot, win.taps, vol, self.mean, self.std, win.min_val, win.fill, self.overlap, want_std)
 
     def _joint(self, lowres_raw, want_std):
-        """``joint=True``: per sample ONE noisy state ``x`` [D,H,W] for the whole volume.  Every step gathers the kept windows of the
-        state (and of the low-res volume, and of the previous fused x0 for a self-conditioned U-Net), lets the window denoiser predict
-        their x0 into one [N,P,P,P] buffer, and ONE ``ops.volume_joint_step`` launch fuses the predictions per voxel, takes the sampler
-        step with draw ``i + 1`` of the anchored field and writes the next state in place.  ``ops.volume_joint_finish`` ends a sample:
-        fill, background reset and the running mean / deviation over the samples.  A multistep denoiser (``sampler='dpmpp2m'``,
-        ``den.multistep``) takes ``ops.volume_joint_multistep`` instead: the third operand of the update is the fused x0 volume of the
-        previous step (the one self-conditioning reads), kept and overwritten in place, and only draw 0 of the field is used."""
+        """``joint=True``: per sample one chain on whole volumes, then ``ops.volume_joint_finish`` (fill, background reset, running mean
+        / deviation over the samples).  ``evaluate(state, cond, x0)`` sends the kept windows of the state, of the low-res volume and of
+        ``cond`` (the fused x0 volume, for self-conditioning; or None) through ``x0(xw, lw, sc, origins)`` into ``y`` [N,P,P,P]."""
         vol = lowres_raw.float().contiguous()
-        dev = vol.device
-        shape = tuple(vol.shape)
-        P, S, den = self.patch, self.samples, self.sample_fn
-        origins = sliding_window_origins(shape, P, self.overlap)
-        lattice = tuple(len(range(0, s - P + 1, self.overlap)) for s in shape)
-        _, nz = ops.patch_gather(vol, torch.from_numpy(origins).to(dev), P, self.mean, self.std, want_patches=False, want_nonzero=True)
-        keep = (nz.cpu().numpy().astype(np.float64) / float(P ** 3)) >= self.ratio          # data.py:187-191
-        kept = origins[keep]
-        N = kept.shape[0]
-        slot = np.full(origins.shape[0], -1, dtype=np.int32)                                 # candidate order = lattice order
-        slot[keep] = np.arange(N, dtype=np.int32)
-        slot = torch.from_numpy(slot.reshape(lattice)).to(dev)
-        taps = torch.from_numpy(blend_taps(P, self.blend, self.sigma_scale)).to(dev)
-        per_call = 1 if self.block_mode else self.batch
-        batches = [(lo, torch.from_numpy(np.ascontiguousarray(kept[lo:lo + per_call])).to(dev)) for lo in range(0, N, per_call)]
-        sub_shape = (self.factor ** 3, 1, self.sub, self.sub, self.sub)
-        split = (lambda w: convertVolume2subVolume(w, target_shape=sub_shape)) if self.block_mode else (lambda w: w)
-        coefs = den.coefs.tolist()
-        lo_c, hi_c, mode_c = den.clamp
-        self_cond = bool(getattr(den, 'self_cond', False))
-        mean32, std32 = np.float32(self.mean), np.float32(self.std)
-        fill = (np.float32(0.) - mean32) / std32
-        min_val = (np.float32(float(ops.min_value(vol).item())) - mean32) / std32
-        y = torch.empty((N, P, P, P), dtype=torch.float32, device=dev)                       # reused by every step of every sample
-        multistep = bool(getattr(den, 'multistep', False))                                   # 'dpmpp2m': coefs rows are (kx, k0, kp)
-        x0_vol = torch.empty(shape, dtype=torch.float32, device=dev) if self_cond or multistep else None
+        P, S, den = self.patch, self.samples, self._protocol(self.sample_fn)
+        win = _Windows(self, vol)
+        chain = self._heun_chain if den.heun else self._multistep_chain if den.multistep else self._step_chain
+        y = torch.empty((win.N, P, P, P), dtype=torch.float32, device=win.device)          # reused by every step of every sample
+        # and so is the fused x0 volume of the first-order and multistep chains; the Heun chain makes its three volumes per sample
+        win.x0_vol = torch.empty_like(vol) if (den.self_cond or den.multistep) and not den.heun else None
+
+        def evaluate(state, cond, x0):
+            self._evaluate(win, [(state, 0., 1.), (vol, self.mean, self.std), (cond, 0., 1.)], x0, y)   # (v - 0) / 1: the state's own bits
+
         mean_io = m2_io = out_std = None
         for s in range(S):
-            if getattr(den, 'heun', False):                  # the EDM family: three volumes, two evaluations per step (_heun_chain)
-                x = self._heun_chain(den, vol, batches, kept, split, y, slot, taps, s)
-                mean_io, m2_io, out_std = ops.volume_joint_finish(den.finish(x), slot, vol, P, self.overlap, self.mean, self.std,
-                                                                  float(min_val), float(fill), s, S, mean_io, m2_io, want_std)
-                continue
-            x = ops.volume_joint_init(shape, self.seed, sample=s, device=dev)               # draw 0
-            for i in range(den.num_steps):
-                for lo, idx in batches:
-                    n = idx.shape[0]
-                    xw = split(ops.patch_gather(x, idx, P, 0., 1.)[0])                       # (v - 0) / 1: the state's own bits
-                    lw = split(ops.patch_gather(vol, idx, P, self.mean, self.std)[0])
-                    sc = split(ops.patch_gather(x0_vol, idx, P, 0., 1.)[0]) if self_cond and i > 0 else None
-                    pred = den.x0(xw, lw, i, self_cond=sc).float()
-                    if self.block_mode:                                                   # test_all.py:229-231, 265-266
-                        pred = merge_sub_volumes(pred, original_shape=(1, 1, P, P, P))
-                    y[lo:lo + n] = pred.reshape(n, P, P, P)
-                kx, k0, kn = coefs[i]
-                if multistep:                                # x0_vol is read as the previous fused x0, then overwritten with this one
-                    ops.volume_joint_multistep(y, slot, taps, x, x0_vol if i else None, kx, k0, kn, lo_c, hi_c, mode_c, self.overlap,
-                                               out=x, x0_out=x0_vol)
-                else:
-                    ops.volume_joint_step(y, slot, taps, x, kx, k0, kn, lo_c, hi_c, mode_c, self.overlap, self.seed, draw=i + 1,
-                                          sample=s, out=x, x0_out=x0_vol)
-            mean_io, m2_io, out_std = ops.volume_joint_finish(den.finish(x), slot, vol, P, self.overlap, self.mean, self.std,
-                                                              float(min_val), float(fill), s, S, mean_io, m2_io, want_std)
+            x = chain(den, win, evaluate, y, s)
+            mean_io, m2_io, out_std = ops.volume_joint_finish(den.finish(x), win.slot, vol, P, self.overlap, self.mean, self.std,
+                                                              win.min_val, win.fill, s, S, mean_io, m2_io, want_std)
         return mean_io, out_std
 
-    def _heun_chain(self, den, vol, batches, kept, split, y, slot, taps, s):
-        """Sample ``s`` of the joint chain of an EDM window denoiser (``den.heun``; ``ElucidatedImagen.window_denoiser``): the stochastic
-        Heun sampler on three volumes -- ``xh`` (images_hat), ``xn`` (images_next) and ``x0`` (the fused prediction, which
-        self-conditioning gathers) -- advanced in place by ``ops.volume_joint_heun``.  Phase 0 makes the initial image and the churn of
-        step 0; every step gathers the ``xh`` windows, evaluates them at sigma_hat into ``y`` and takes the predictor (phase 1), then,
-        unless sigma_next is 0, gathers the ``xn`` windows, evaluates them at sigma_next and takes the corrector together with the next
-        step's churn (phase 2): 2 T - 1 fused launches for T steps.  The low-res augmentation noise of a batch is draw 0 of the anchored
-        field at its windows, recomputed where it is used; the initial image is draw ``den.draw_base`` and the eps of step i draw
-        ``den.draw_base + 1 + i`` -- the numbering ``AnchoredNoise.source`` gives ``ElucidatedImagen.sample(noise=source)``.  Returns the
-        volume the chain ends in."""
-        dev, shape, P = vol.device, tuple(vol.shape), self.patch
-        coefs = den.coefs.tolist()
-        lo_c, hi_c, mode_c = den.clamp
-        self_cond, base, T = bool(getattr(den, 'self_cond', False)), int(den.draw_base), den.num_steps
-        xh = ops.volume_joint_heun_init(shape, den.sigma0, coefs[0][0], self.seed, draw=base, sample=s, device=dev)
+    def _step_chain(self, den, win, evaluate, y, s):
+        """Sample ``s`` of a first-order chain: the state ``x`` starts as draw 0 of the anchored field; per step ONE
+        ``ops.volume_joint_step`` launch fuses the predictions in ``y`` per voxel, takes the sampler step with draw ``i + 1`` and writes
+        the next state in place (and the fused x0 ``win.x0_vol``, which self-conditioning gathers at the next step).  Returns ``x``."""
+        x = ops.volume_joint_init(win.shape, self.seed, sample=s, device=win.device)        # draw 0
+        for i in range(den.num_steps):
+            evaluate(x, win.x0_vol if den.self_cond and i > 0 else None, lambda xw, lw, sc, o: den.x0(xw, lw, i, self_cond=sc))
+            kx, k0, kn = den.coefs[i]
+            ops.volume_joint_step(y, win.slot, win.taps, x, kx, k0, kn, *den.clamp, self.overlap, self.seed, draw=i + 1, sample=s,
+                                  out=x, x0_out=win.x0_vol)
+        return x
+
+    def _multistep_chain(self, den, win, evaluate, y, s):
+        """Sample ``s`` of a multistep chain (``sampler='dpmpp2m'``): as ``_step_chain`` with ``ops.volume_joint_multistep``, whose
+        third operand is the fused x0 volume of the previous step (``win.x0_vol``, the one self-conditioning reads) -- read, then
+        overwritten with this step's, in place.  Only draw 0 of the field is used."""
+        x = ops.volume_joint_init(win.shape, self.seed, sample=s, device=win.device)        # draw 0
+        for i in range(den.num_steps):
+            evaluate(x, win.x0_vol if den.self_cond and i > 0 else None, lambda xw, lw, sc, o: den.x0(xw, lw, i, self_cond=sc))
+            kx, k0, kp = den.coefs[i]
+            ops.volume_joint_multistep(y, win.slot, win.taps, x, win.x0_vol if i else None, kx, k0, kp, *den.clamp, self.overlap,
+                                       out=x, x0_out=win.x0_vol)
+        return x
+
+    def _heun_chain(self, den, win, evaluate, y, s):
+        """Sample ``s`` of the chain of an EDM window denoiser (module docstring): ``xh`` (images_hat), ``xn`` (images_next) and ``x0_vol``
+        (the fused prediction, which self-conditioning gathers) are advanced in place by ``ops.volume_joint_heun``; ``predict`` evaluates
+        the windows of one of them into ``y``, with draw 0 of the field at each batch as its low-res noise.  The initial image is draw
+        ``den.draw_base``, the eps of step i draw ``den.draw_base + 1 + i``.  Returns the volume the chain ends in."""
+        base, T = den.draw_base, den.num_steps
+        xh = ops.volume_joint_heun_init(win.shape, den.sigma0, den.coefs[0][0], self.seed, draw=base, sample=s, device=win.device)
         xn, x0_vol = torch.empty_like(xh), torch.empty_like(xh)
 
-        def evaluate(state, i, stage):
-            for lo, idx in batches:
-                n = idx.shape[0]
-                xw = split(ops.patch_gather(state, idx, P, 0., 1.)[0])                   # (v - 0) / 1: the state's own bits
-                lw = split(ops.patch_gather(vol, idx, P, self.mean, self.std)[0])
-                sc = split(ops.patch_gather(x0_vol, idx, P, 0., 1.)[0]) if self_cond and (i > 0 or stage == 1) else None
-                ln = None
-                if base:                                     # block mode: the sub-volumes' own origins, as in _sample
-                    org = sub_volume_origins(kept[lo], self.factor, self.sub) if self.block_mode else kept[lo:lo + n]
-                    ln = ops.anchored_noise(org, lw.shape[1], self.sub, *shape, self.seed, draw=0, sample=s, device=dev)
-                pred = den.x0(xw, lw, i, self_cond=sc, stage=stage, lowres_noise=ln).float()
-                if self.block_mode:                                                   # test_all.py:229-231, 265-266
-                    pred = merge_sub_volumes(pred, original_shape=(1, 1, P, P, P))
-                y[lo:lo + n] = pred.reshape(n, P, P, P)
+        def predict(state, i, stage):
+            def x0(xw, lw, sc, o):
+                ln = ops.anchored_noise(win.noise_origins(o), lw.shape[1], self.sub, *win.shape, self.seed, draw=0, sample=s,
+                                        device=win.device) if base else None
+                return den.x0(xw, lw, i, self_cond=sc, stage=stage, lowres_noise=ln)
+            evaluate(state, x0_vol if den.self_cond and (i > 0 or stage == 1) else None, x0)
 
         corrected = False
         for i in range(T):
-            _, a1, b1, a2, b2, c2, d2 = coefs[i]
-            evaluate(xh, i, 0)
-            ops.volume_joint_heun(y, slot, taps, xh, xn, x0_vol, 1, (a1, b1), 0., lo_c, hi_c, mode_c, self.overlap)
+            _, a1, b1, a2, b2, c2, d2 = den.coefs[i]
+            predict(xh, i, 0)
+            ops.volume_joint_heun(y, win.slot, win.taps, xh, xn, x0_vol, 1, (a1, b1), 0., *den.clamp, self.overlap)
             corrected = float(den.sched[i][1]) != 0
             if corrected:                                    # no corrector on the step that ends at sigma 0
-                evaluate(xn, i, 1)
+                predict(xn, i, 1)
                 more = i + 1 < T
-                ops.volume_joint_heun(y, slot, taps, xh, xn, x0_vol, 2, (a2, b2, c2, d2), coefs[i + 1][0] if more else 0., lo_c, hi_c,
-                                      mode_c, self.overlap, self.seed, draw=base + 2 + i if more else 0, sample=s)
+                ops.volume_joint_heun(y, win.slot, win.taps, xh, xn, x0_vol, 2, (a2, b2, c2, d2), den.coefs[i + 1][0] if more else 0.,
+                                      *den.clamp, self.overlap, self.seed, draw=base + 2 + i if more else 0, sample=s)
         return xh if corrected else xn
 
 
