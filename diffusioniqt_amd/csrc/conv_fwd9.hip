@@ -31,6 +31,33 @@
 //     the entry points told the buffer's length (diqt_conv3d_fwd_pk / _gn_pk) plan with wino = true, and only when it holds them.
 //     Measured (C2 sampler step, 38 launches per U-Net eval): 3x3x3 conv time 11.16 -> 8.70 ms per eval, 10.03-10.05 ms per step
 //     against 12.49-12.53 on the direct tiles (profiles/r05_*).  DIQT_CONV_F9W=0 forces the direct tiles.
+//     Round 6 (profiles/r06_*) went after the idle fifth of the matrix pipe AROUND the MFMA stream, on an attribution estimated from
+//     instruction counts (step heads 4-5 %, tile epilogue 3-4 %, chunk start and GroupNorm slices 1-2 % each).  The measurements
+//     did not bear it out: everything together is worth 0.6 % of a launch.  A/B per launch (tools/conv_bench.py gn, GroupNorm-apply build / plain
+//     build, min-max of 3 alternating rounds on one box, us; parent 346.1-347.6 / 301.3-301.9 at 64->64 @ 8x32^3):
+//       1. MFMA-first step heads -- kept.  The step's DMA block (weight group two steps ahead, halo pieces, their address arithmetic,
+//          pinned by an opaque zero) sits behind the second MFMA group, the transform of k-group 0 at the tail of the step before,
+//          and every group issues its MFMAs before its fragment read and rewrite slice: 0-1 instructions between a step's barrier
+//          and its first MFMA (9-13 before; plain build 6 against 12: the ring-index scalars remain).  Alone 345.2-348.0 / 300.5-301.0; without the MFMA-first fence inside the groups the
+//          scheduler hoists the block and the reads in front of the MFMAs again: 354.7-356.6 / 305.1-305.8, 2 % SLOWER.
+//       2. whole-tile epilogue -- kept.  Tiles inside the volume take one byte offset per lane and co half, scalar soffsets for the
+//          32 (row pair, column) displacements, no range tests, unconditional statistics; ragged tiles keep the masked path.
+//          Alone 345.3-345.9 / 299.8-300.7; with item 1: 344.3-345.1 / 299.5-300.2 (16^3: 173.2-173.6 against 174.2-174.7, 8^3
+//          split-K: 99.7-100.3 against 100.1-100.4).
+//       3. chunk-start weight prefetch -- not built: with the heads worth 0.3 %, 16 cold reads per 36.8k-cycle chunk cannot show.
+//       4. -fno-slp-vectorize for the GroupNorm-apply unit -- dropped: 0.8 % slower, and the backend then contracts other mul / add
+//          pairs of the rewrite, so the output bits change.
+//     Two probes, not kept: reading the input column that the two taps of a step share once (34 of 308 ds_read_b128 per chunk)
+//     changed nothing (348.8-349.7 against 347.4-347.7 that session), so the LDS read count is not the limit; issuing the DMA block
+//     behind group 6 instead of group 1 changed nothing either (346.1-348.9), so neither is the weight group's latency inside its
+//     step.  What remains of the idle share is therefore inside the stream: the skew of the four waves at the 18 barriers per
+//     chunk and the MFMA issue itself (SQ_WAIT_INST_ANY is 0.70 of the wave cycles before and after).  The register allocation of
+//     the plain build is brittle at 256 VGPRs: moving the transform into a helper macro, with the same operations, parked fragments
+//     in AGPRs (v_accvgpr_read inside the chunk loop, 2x slower);
+//     tools/f9_asm_metrics.py prints that count, the step heads and the epilogue size from a -save-temps .s file.
+//     C2 sampler step, three alternating runs per build on one box: 10.100-10.104 ms on the parent, 9.962-10.015 ms now (-1.1 % on
+//     the means, outputs identical byte for byte); the Winograd kernel 8.757 -> 8.710 ms per eval, MFMA-busy / busy 23.88 -> 24.16
+//     (direct tiles 26.5-28.1): the pipe is still busy only about 0.8 of the time.
 // Reference call sites: Block.project of every ResnetBlock (/root/reference/imagen_pytorch3D.py:535-566) and the per-frame Conv2d of
 // the pseudo-3D blocks (/root/reference/imagen_video.py:352-381 Conv3d.spatial_conv, 671-697 Block).
 #include "conv_fwd9_kernel.h"

@@ -4,6 +4,7 @@
 #pragma once
 #include "common.h"
 #include "conv_fwd9.h"
+#include <type_traits>
 
 namespace diqt {
 
@@ -137,8 +138,8 @@ __global__ __launch_bounds__(256, 1) void conv_fwd9_kernel(const float* __restri
     // this lane's weight piece of a tap panel: co row 16 w + lane / 4, channel quad lane % 4 of the 16-channel sub-chunk
     const unsigned relW = (unsigned)((n0 + 16 * wave + (lane >> 2)) * 128 + (lane & 3) * 16);
     const unsigned tapStrideW = (unsigned)g.CoutPad * 128u;          // bytes between the panels of consecutive taps (32-wide packed rows)
-    auto dma_w = [&](int c16, int tap, unsigned ldsSlot, int tapInStep) __attribute__((always_inline)) {
-        const unsigned voff = ((unsigned)(c16 >> 1) * T + (unsigned)tap) * tapStrideW + (unsigned)(c16 & 1) * 64u + relW;
+    auto dma_w = [&](int c16, int tap, unsigned ldsSlot, int tapInStep, unsigned z = 0u) __attribute__((always_inline)) {
+        const unsigned voff = ((unsigned)(c16 >> 1) * T + (unsigned)tap + z) * tapStrideW + (unsigned)(c16 & 1) * 64u + relW;
         f9_dma(rs_w, ldsSlot + (unsigned)tapInStep * WTAP + (unsigned)wave * 1024u, voff);
     };
 
@@ -163,8 +164,8 @@ __global__ __launch_bounds__(256, 1) void conv_fwd9_kernel(const float* __restri
         deadX = live ? 0u : OOB;
         if constexpr (GNA != 0) fb = b_;
     };
-    auto dma_h = [&](int r, unsigned hbuf, int c16) __attribute__((always_inline)) {     // r static
-        const unsigned p = posH[r];
+    auto dma_h = [&](int r, unsigned hbuf, int c16, unsigned z = 0u) __attribute__((always_inline)) {     // r static
+        const unsigned p = posH[r] | z;
         const int iz = bz + (int)(p & 255u), iy = by + (int)((p >> 8) & 255u), ix = bxx + (int)((p >> 16) & 255u);
         const unsigned m = (unsigned)(iz | iy | ix) | (unsigned)((Dm1 - iz) | (Hm1 - iy) | (Wm1 - ix)) | (p << 7) | deadX;
         const unsigned voff = (baseX + relH[r] + (unsigned)c16 * ROWB) | (m & OOB);
@@ -356,12 +357,15 @@ __global__ __launch_bounds__(256, 1) void conv_fwd9_kernel(const float* __restri
         else if (k_ == 1) Xb[t_][q_] = *reinterpret_cast<const f32x4v*>(hw + (C::wrow(tap_) + C::wcolB(tap_)) * ROWB + q_ * 32); \
         else Wv[t_][k_ - 2][q_] = *reinterpret_cast<const f32x4v*>(wb_ + (k_ - 2) * 32 * ROWB + q_ * 32);            \
     } while (0)
-// the 32 MFMAs of step S in 16 fenced groups of two; behind group u read u of the next step (PF) and slice u of the GroupNorm-apply
-// rewrite.  The input transform of k-group q (one add / subtract per operand element) sits in front of its first MFMA.
+// the 32 MFMAs of step S in 16 groups of two, each group in two fenced halves: the MFMAs, then what issues under them -- read u of
+// the next step (PF), slice u of the GroupNorm-apply rewrite and, behind group 1, the step's DMA block (f9w_dma).  A step ends in a
+// barrier with the matrix pipe drained, so nothing but the MFMAs' own operands stands between it and the step's first MFMA: the
+// input transform (one add / subtract per operand element) of k-group 0 is done at the tail of the step before (its fragments are
+// reads 0..7 of that step; the chunk's first step transforms behind its cold read), that of k-group 1 in front of group 8.
 #define F9W_STEP(Xa, Xb, Wv, Xn, Xbn, Wn, S, PF, WSN)                                                               \
     do {                                                                                                             \
         _Pragma("unroll") for (int u = 0; u < 16; ++u) {                                                             \
-            if (u % 8 == 0) {                       /* in place: d_a becomes the operand */                          \
+            if (u == 8 || (u == 0 && (S) == 0)) {      /* in place: d_a becomes the operand */                          \
                 _Pragma("unroll") for (int t_ = 0; t_ < 2; ++t_)                                                     \
                     Xa[t_][u / 8] = C::wadd(2 * (S) + t_) ? Xa[t_][u / 8] + Xb[t_][u / 8] : Xa[t_][u / 8] - Xb[t_][u / 8];   \
             }                                                                                                        \
@@ -369,8 +373,14 @@ __global__ __launch_bounds__(256, 1) void conv_fwd9_kernel(const float* __restri
                 const int q = m / 16, e = (m / 4) % 4, t_ = (m / 2) % 2, ch = m % 2, j_ = (2 * (S) + t_) % 4;       \
                 acc[j_][ch] = __builtin_amdgcn_mfma_f32_32x32x2f32(Xa[t_][q][e], Wv[t_][ch][q][e], acc[j_][ch], 0, 0, 0);   \
             }                                                                                                        \
+            __builtin_amdgcn_sched_barrier(0);                                                                       \
+            if (u == 1) f9w_dma(S);                                                                                  \
             if (PF) F9W_RD1(Xn, Xbn, Wn, (S) + 1, WSN, u);                                                           \
             if constexpr (GNA != 0) gna_slice(S, u, 16, hcur ^ 1);                                                   \
+            if ((PF) && u == 15) {                  /* k-group 0 of the next step (read behind groups 0..7) */       \
+                _Pragma("unroll") for (int t_ = 0; t_ < 2; ++t_)                                                     \
+                    Xn[t_][0] = C::wadd(2 * (S) + 2 + t_) ? Xn[t_][0] + Xbn[t_][0] : Xn[t_][0] - Xbn[t_][0];         \
+            }                                                                                                        \
             __builtin_amdgcn_sched_barrier(0);                                                                       \
         }                                                                                                            \
     } while (0)
@@ -380,16 +390,28 @@ __global__ __launch_bounds__(256, 1) void conv_fwd9_kernel(const float* __restri
                 for (int s = 0; s < NSTEP; ++s) {
                     const int wnext = wcur == NWS - 1 ? 0 : wcur + 1;
                     const int wnn = wnext == NWS - 1 ? 0 : wnext + 1;
-                    {       // this step's DMA, as below: the weight group two steps ahead, the next chunk's halo pieces
-                        const int s2 = s + 2 < NSTEP ? s + 2 : s + 2 - NSTEP;
-                        const int c2 = s + 2 < NSTEP ? c : cNext;
+                    // This step's DMA, issued behind the step's second MFMA group: the weight group two steps ahead, then the next
+                    // chunk's halo pieces (this program order is what the counted wait at the step's end relies on).  `z` is a zero
+                    // the compiler cannot see through: the address arithmetic depends on it and so stays behind the MFMAs, too.
+                    //  * the ring slot written here was last read by the fragment reads of step s - 2 (for the MFMAs of step s - 1,
+                    //    all issued before the barrier that ended step s - 1): issuing later only widens that distance;
+                    //  * the group is read from step s + 1 on; `vmcnt(nh_in_step(s))` at this step's end leaves only the halo pieces
+                    //    issued behind it in flight, whatever the position of the block inside the step, and the barrier publishes it;
+                    //  * the GroupNorm-apply rewrite in step s touches the pieces issued in step s - 2: the same wave's counted wait
+                    //    at the end of step s - 1 left only the pieces of step s - 1 in flight, so they have landed before slice 0
+                    //    (group 0) reads them back -- before or behind this step's block makes no difference.
+                    auto f9w_dma = [&](int s_) __attribute__((always_inline)) {        // s_ static
+                        const int s2 = s_ + 2 < NSTEP ? s_ + 2 : s_ + 2 - NSTEP;
+                        const int c2 = s_ + 2 < NSTEP ? c : cNext;
                         const unsigned slot = wringBase + (unsigned)wnn * WSLOT;
-                        dma_w(c2, 2 * s2, slot, 0);
-                        dma_w(c2, 2 * s2 + 1, slot, 1);
+                        unsigned z = 0u;
+                        asm volatile("" : "+s"(z));
+                        dma_w(c2, 2 * s2, slot, 0, z);
+                        dma_w(c2, 2 * s2 + 1, slot, 1, z);
 #pragma unroll
                         for (int r = 0; r < NPH; ++r)
-                            if (r * NSPREAD / NPH == s) dma_h(r, hbufN, cNext);
-                    }
+                            if (r * NSPREAD / NPH == s_) dma_h(r, hbufN, cNext, z);
+                    };
                     if (s % 2 == 0) F9W_STEP(Xa0, Xb0, W0, Xa1, Xb1, W1, s, s + 1 < NSTEP, wnext);
                     else F9W_STEP(Xa1, Xb1, W1, Xa0, Xb0, W0, s, s + 1 < NSTEP, wnext);
                     if (GNA != 0 && s + 1 == NSTEP) f9_chunk_end_gna();
@@ -478,8 +500,72 @@ __global__ __launch_bounds__(256, 1) void conv_fwd9_kernel(const float* __restri
                 // Winograd output transform, lane-local: register i of position j's tile is pair (i & 3) of row 2 (i >> 2) + hf of the
                 // wave's plane; y(2p) = m0 + m1 + m2, y(2p + 1) = m1 - m2 - m3, then bias, residual and the statistics of the final y
                 const int od = d0 + wave;
+                // A tile that lies whole inside the volume (wave-uniform; every tile of the C2 shapes) needs no range test per element:
+                // one byte offset per lane and co half (row h0 + hf of the plane, column w0; the out-of-range mark of a co half beyond
+                // Cout rides in it), the 32 (row pair, column) displacements of the lane's registers are scalars in soffset, and the
+                // statistics take every element.  Same values in the same order as the masked path below.
+                const bool whole = d0 + C::TD <= g.Do && h0 + C::TH <= g.Ho && w0 + C::TW <= g.Wo;
+                if (whole) {
+                    const unsigned voxB = (unsigned)g.Cout * 4u, rowB = (unsigned)g.Wo * voxB;
+                    const unsigned vbase = (unsigned)(((tb * g.Do + od) * g.Ho + h0) * g.Wo + w0) * voxB + (unsigned)hf * rowB;
+                    const unsigned vo0 = vbase + c0o, vo1 = vbase + c1o;
+                    auto quarter = [&](int hv, auto withRes) __attribute__((always_inline)) {      // hv static
+                        float v0[2][4], v1[2][4];
+                        unsigned so[2][4];
 #pragma unroll
-                for (int hv = 0; hv < 4; ++hv) {           // four quarters of 4 registers: 16 residual registers at a time
+                        for (int ii = 0; ii < 4; ++ii)
+#pragma unroll
+                            for (int o = 0; o < 2; ++o) so[o][ii] = (unsigned)(2 * hv) * rowB + (unsigned)(2 * ii + o) * voxB;
+                        if constexpr (decltype(withRes)::value) {
+#pragma unroll
+                            for (int ii = 0; ii < 4; ++ii)
+#pragma unroll
+                                for (int o = 0; o < 2; ++o) {
+                                    v0[o][ii] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_r, vo0, so[o][ii], 0));
+                                    v1[o][ii] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_r, vo1, so[o][ii], 0));
+                                }
+                        }
+#pragma unroll
+                        for (int ii = 0; ii < 4; ++ii) {
+                            const int i = 4 * hv + ii;
+                            float v[2][2];                 // [output of the pair][co half]
+#pragma unroll
+                            for (int ch = 0; ch < 2; ++ch) {
+                                v[0][ch] = (acc[0][ch][i] + acc[1][ch][i]) + acc[2][ch][i];
+                                v[1][ch] = (acc[1][ch][i] - acc[2][ch][i]) - acc[3][ch][i];
+                            }
+#pragma unroll
+                            for (int o = 0; o < 2; ++o) {
+                                float a0 = v[o][0] + bias0, a1 = v[o][1] + bias1;
+                                if constexpr (decltype(withRes)::value) { a0 += v0[o][ii]; a1 += v1[o][ii]; }
+                                v0[o][ii] = a0; v1[o][ii] = a1;
+                                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, a0), rs_y, vo0, so[o][ii], 0);
+                                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, a1), rs_y, vo1, so[o][ii], 0);
+                            }
+#pragma unroll
+                            for (int j = 0; j < 4; ++j) { acc[j][0][i] = 0.f; acc[j][1][i] = 0.f; }
+                        }
+                        if (g.stats) {                     // kernel-uniform; the order of the masked path: i, then the pair's outputs
+#pragma unroll
+                            for (int ii = 0; ii < 4; ++ii)
+#pragma unroll
+                                for (int o = 0; o < 2; ++o) {
+                                    cs0 += v0[o][ii]; cq0 = fmaf(v0[o][ii], v0[o][ii], cq0);
+                                    cs1 += v1[o][ii]; cq1 = fmaf(v1[o][ii], v1[o][ii], cq1);
+                                }
+                        }
+                    };
+                    if (residual) {                        // kernel-uniform
+#pragma unroll
+                        for (int hv = 0; hv < 4; ++hv) quarter(hv, std::true_type{});
+                    } else {
+#pragma unroll
+                        for (int hv = 0; hv < 4; ++hv) quarter(hv, std::false_type{});
+                    }
+                }
+                if (!whole)
+#pragma unroll
+                for (int hv = 0; hv < 4; ++hv) {           // ragged tiles: four quarters of 4 registers, 16 residual registers at a time
                     unsigned offs[2][4];
                     float r0[2][4], r1[2][4];
 #pragma unroll
