@@ -153,6 +153,8 @@ PROTOTYPES = {
     "diqt_temporal_attention_h": (I, [P] * 10 + [I, I, I, I, I, I, I, F, I, I, P]),
     "diqt_mqa_attention_fwd_lse": (I, [P, P, P, P, P, P, I, I, I, I, I, I, I, F, P]),
     "diqt_mqa_attention_bwd_workspace_bytes": (Z, [I, I, I, I, I, I, I]),
+    "diqt_mqa_attention_bwd_route": (I, [I] * 9),
+    "diqt_mqa_attention_fwd_h_route": (I, [I] * 5),
     "diqt_mqa_attention_bwd": (I, [P] * 11 + [P, Z, I, I, I, I, I, I, I, F, P]),
     "diqt_weighted_colsum": (I, [P, P, P, P, Z, I, I, I, P]),
     "diqt_softmax_pool_supported": (I, [I, I, I]),
@@ -245,7 +247,7 @@ SWITCH_EPOCH = 0      # counts diqt_set_* calls: a captured hipGraph froze the k
 
 
 def query(name, *args):
-    """Calls a value-returning entry point.  The shape queries (``*_supported``, ``*_bytes``, ``*_blocks``, ``*_elems``, ``*_kernel_id``) are
+    """Calls a value-returning entry point.  The shape queries (``*_supported``, ``*_bytes``, ``*_blocks``, ``*_elems``, ``*_kernel_id``, ``*_route``) are
     pure functions of their integer arguments and of the library's run-time switches, so their results are memoised -- a conv launch asks
     three or four of them, and launch-bound steps (744 launches per bf16 training micro-step) pay for every ctypes round trip.  Any
     ``diqt_set_*`` call (a switch changes) empties the memo; ``diqt_get_*`` is never cached."""

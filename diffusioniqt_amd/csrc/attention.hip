@@ -571,6 +571,21 @@ extern "C" int diqt_cast_to_h(const float* x, void* y, size_t n, int bf16, void*
     return check_launch("cast_to_h");
 }
 
+// the one decision of diqt_mqa_attention_fwd_h.  Long un-biased sequences (the joint space-time attention): 4-wave workgroups, two per CU
+// (see the kernel)
+static bool attn_fwd_h_four_waves(int n, int h, int d, bool rel) { return !rel && d == 64 && (long long)n * h >= 4096; }
+
+// field: 0 waves per workgroup (4 or 8), 1 query rows per workgroup, 2 the HASREL instantiation; -1 for an unknown field
+extern "C" int diqt_mqa_attention_fwd_h_route(int n, int h, int d, int has_rel, int field) {
+    const bool four = attn_fwd_h_four_waves(n, h, d, has_rel != 0);
+    switch (field) {
+        case 0: return four ? 4 : 8;
+        case 1: return four ? 128 : AQH;
+        case 2: return has_rel ? 1 : 0;
+    }
+    return -1;
+}
+
 extern "C" int diqt_mqa_attention_fwd_h(const float* q, const void* kv, const float* rel, const float* null_bias, float* out, int G,
                                         int n, int h, int d, int n_extra, int n_self, int causal, float scale, int bf16, int round_out,
                                         void* stream) {
@@ -581,8 +596,7 @@ extern "C" int diqt_mqa_attention_fwd_h(const float* q, const void* kv, const fl
     DIQT_REQUIRE(!null_bias || n_extra >= 1, DIQT_E_SHAPE, "mqa_attention_fwd_h: null bias without a null key");
     DIQT_REQUIRE(aligned16(q) && aligned16(kv) && aligned16(out), DIQT_E_ALIGN, "mqa_attention_fwd_h: pointers must be 16-byte aligned");
     DIQT_REQUIRE(G <= 65535, DIQT_E_SHAPE, "mqa_attention_fwd_h: G > 65535");
-    // long un-biased sequences (the joint space-time attention): 4-wave workgroups, two per CU (see the kernel)
-    const bool four = !rel && d == 64 && (long long)n * h >= 4096;
+    const bool four = attn_fwd_h_four_waves(n, h, d, rel != nullptr);
     const int rowsPerWg = four ? 128 : AQH;
     const dim3 grid((unsigned)(((long long)n * h + rowsPerWg - 1) / rowsPerWg), G);
     void (*k)(const float*, const unsigned short*, const float*, const float*, float*, int, int, int, int, int, float, int) =
@@ -861,6 +875,9 @@ __global__ __launch_bounds__(256) void attn_bias_reduce_kernel(const float* __re
     }
 }
 
+// the XCD remap of mqa_flash_bwd_dkv_kernel needs whole groups of eight batch entries (one predicate for the kernel and the host's plan)
+__host__ __device__ __forceinline__ bool dkv_xcd_remap(unsigned gridY) { return (gridY & 7u) == 0; }
+
 template <int ND>
 __global__ __launch_bounds__(256, 1) void mqa_flash_bwd_dkv_kernel(const float* __restrict__ q, const float* __restrict__ kv,
                                                                    const float* __restrict__ rel, const float* __restrict__ null_bias,
@@ -873,7 +890,7 @@ __global__ __launch_bounds__(256, 1) void mqa_flash_bwd_dkv_kernel(const float* 
     // walk the same Q / dO tiles at the same pace, so they belong behind ONE L2: batch entry g = xcd + 8 * (...) instead of every
     // XCD streaming every entry's Q and dO (the joint space-time attentions: 8 entries x 64 key tiles, 8.4 MB of Q + dO each).
     int g = blockIdx.y, bx = blockIdx.x;
-    if ((gridDim.y & 7) == 0) {
+    if (dkv_xcd_remap(gridDim.y)) {
         const unsigned id = blockIdx.y * gridDim.x + blockIdx.x, slot = id >> 3;
         g = (int)((id & 7u) + 8u * (slot / gridDim.x));
         bx = (int)(slot % gridDim.x);
@@ -1505,9 +1522,119 @@ __global__ __launch_bounds__(256, 1) void mqa_seq_bwd_kernel(const float* __rest
     if (dnull_part && hf == 0) dnull_part[wrow * 32 + l31] = dnb;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Every decision of diqt_mqa_attention_bwd as a pure function of the shape: the launcher below takes its path, grids, LDS sizes and
+// kernel arguments from here and nowhere else, and diqt_mqa_attention_bwd_route hands the same plan to the tests (no GPU needed).
+// ---------------------------------------------------------------------------------------------------------------------------------
+struct AttnBwdPlan {
+    int path;                   // 0: refused, 1: mqa_seq_bwd_kernel, 2: mqa_flash_bwd_dq_kernel then mqa_flash_bwd_dkv_kernel
+    int nwg;                    // workgroups of the kernel that writes the bias-gradient partials (seq / dq): 4 workspace rows each
+    int KW, perWave, EV, nkt;   // the dkv launch (path 2; -1 / 0 on path 1): key tiles per workgroup, sequence per wave, VALU extra keys, grid.x
+    int relLds;                 // floats of the bias table the seq / dkv kernel keeps in LDS
+    int remap;                  // the dkv kernel's XCD remap applies (dkv_xcd_remap of its grid.y)
+    int dkvGy;                  // grid.y of the dkv launch
+    int TBL, gx, gy, rows;      // relative-bias table entries, dq grid, rows of the partial tables in the workspace
+    size_t ldsSeq, ldsDq, ldsDkv;
+    bool dkvRaiseLds;           // ldsDkv is above the 64 KiB a kernel gets without hipFuncSetAttribute
+    char why[160];              // the text of a refusal
+    unsigned long long ob;      // bytes of q / out / dq
+};
+
+// rows of the bias-gradient partial tables in the workspace: 4 (one per wave) x the dQ grid -- the one place that counts them
 static int attn_bwd_rows(int G, int n, int h) {
     const int gx = (int)(((long long)n * h + AQ - 1) / AQ), gy = G < 256 ? G : 256;
     return gy * gx * 4;
+}
+
+// A refusal leaves its code and text in the plan and touches nothing else (the route query stays pure); the launcher reports it.
+#define ATTN_PLAN_REQUIRE(cond, code, ...)                       \
+    do {                                                         \
+        if (!(cond)) {                                           \
+            snprintf(p.why, sizeof(p.why), __VA_ARGS__);         \
+            return (code);                                       \
+        }                                                        \
+    } while (0)
+
+static int attn_bwd_plan(AttnBwdPlan& p, int G, int n, int h, int d, int n_extra, int n_self, bool rel, bool null_bias) {
+    p = AttnBwdPlan{};
+    ATTN_PLAN_REQUIRE(G > 0 && n > 0 && h > 0 && n_extra >= 0 && n_self >= 0 && n_extra + n_self > 0, DIQT_E_SHAPE, "mqa_attention_bwd: bad shape");
+    ATTN_PLAN_REQUIRE(d == 32 || d == 64, DIQT_E_UNSUPPORTED, "mqa_attention_bwd: dim_head %d (32 or 64 are built)", d);
+    ATTN_PLAN_REQUIRE(!rel || n_self == n, DIQT_E_SHAPE, "mqa_attention_bwd: causal / relative bias need n_self == n");
+    ATTN_PLAN_REQUIRE(!null_bias || n_extra >= 1, DIQT_E_SHAPE, "mqa_attention_bwd: null bias without a null key");
+    ATTN_PLAN_REQUIRE(G <= 65535, DIQT_E_SHAPE, "mqa_attention_bwd: G > 65535");
+    // attn_bias_reduce_kernel keeps 256 x h floats in LDS and is launched without raising the 64-KiB default; the dK/dV kernel's
+    // LDS copy of null_bias has 64 slots
+    ATTN_PLAN_REQUIRE(h <= 64, DIQT_E_UNSUPPORTED, "mqa_attention_bwd: %d heads (at most 64)", h);
+    const long long TBLl = rel ? (2ll * n_self - 1) * h : 0;
+    ATTN_PLAN_REQUIRE((unsigned long long)TBLl * 4ull * sizeof(float) <= 24 * 1024, DIQT_E_UNSUPPORTED,
+                      "mqa_attention_bwd: relative-bias table of %lld entries per wave does not fit the LDS budget", TBLl);
+    const int TBL = (int)TBLl;
+    const int R = n * h, M = n_extra + n_self;
+    p.TBL = TBL;
+    p.gx = (R + AQ - 1) / AQ;
+    p.gy = G < 256 ? G : 256;
+    p.rows = attn_bwd_rows(G, n, h);
+    p.ob = (unsigned long long)G * R * d * 4ull;
+    {
+        // thousands of short sequences with the lone null key (the temporal attentions): everything in one pass, a sequence per wave
+        const int relLds = rel ? TBL : 0;
+        const int perw = (32 * d + 3 * 32 * (d + 4) + 64 + 2 * d + TBL + 255) / 256 * 256;
+        const size_t lds = ((size_t)4 * perw + relLds + 64) * sizeof(float);
+        if (n_extra == 1 && n_self == n && n <= 32 && 32 % h == 0 && G >= 512 && p.ob < (1ull << 31) && lds <= 160 * 1024) {
+            p.path = 1;
+            p.nwg = (G + 3) / 4 < 256 ? (G + 3) / 4 : 256;          // (nwg * 4 <= rows: fits the workspace of the two-kernel path)
+            p.relLds = relLds;
+            p.ldsSeq = lds;
+            p.KW = -1;
+            return DIQT_OK;
+        }
+    }
+    p.nwg = p.gx * p.gy;
+    p.ldsDq = (size_t)4 * TBL * sizeof(float);
+    // keys that go through the MFMA tiles: a lone null key, or a few extra keys in front of at least as many self-key tiles, are VALU work
+    const int EV = (n_extra == 1 || (n_extra >= 1 && n_extra <= 8 && n_extra <= (n_self + 31) / 32)) ? n_extra : 0;
+    const int Mt = M - EV;
+    // key tiles per workgroup; the other 4 / KW waves split the query tiles.  Few batch entries (the joint 2048-token attentions:
+    // G = 8) need the finer split to fill 256 CUs: every workgroup walks ALL query rows of its batch entry.
+    int KW = Mt <= 32 ? 1 : (Mt <= 64 ? 2 : 4);
+    while (KW > 1 && (long long)((Mt + 32 * KW - 1) / (32 * KW)) * G < 512) KW >>= 1;
+    const bool perWave = Mt <= 32 && G >= 2048;      // one sequence per wave (see the kernel)
+    if (perWave) KW = 0;
+    const int nkt = perWave ? 1 : (Mt > 0 ? (Mt + 32 * KW - 1) / (32 * KW) : 1);
+    const int ROW = d + 4;
+    size_t lds = (size_t)4 * (2 * 32 * ROW + 128 + 2 * d) * sizeof(float);
+    const int relLds = TBL;         // the bias table in LDS behind the staging regions (h <= 64 and <= 1536 entries by the refusals above)
+    const size_t red = (size_t)(perWave ? 0 : 4 - KW) * (2 * (d / 32) * 16 * 64 + 128) * sizeof(float);
+    ATTN_PLAN_REQUIRE(red <= lds, DIQT_E_UNSUPPORTED, "mqa_attention_bwd: combine region larger than the staging regions");
+    lds += (size_t)(relLds + 64) * sizeof(float);          // bias tables behind the staging regions
+    p.path = 2;
+    p.KW = KW; p.perWave = perWave ? 1 : 0; p.EV = EV; p.nkt = nkt; p.relLds = relLds; p.ldsDkv = lds;
+    p.dkvGy = perWave ? (G + 3) / 4 : G;
+    p.dkvRaiseLds = lds > 64 * 1024;
+    p.remap = dkv_xcd_remap((unsigned)p.dkvGy) ? 1 : 0;
+    return DIQT_OK;
+}
+
+// field: 0 path (0 refused, 1 seq, 2 two-kernel), 1 the error code of a refusal (0 otherwise), 2 nwg, 3 KW, 4 perWave, 5 EV, 6 nkt, 7 relLds,
+// 8 XCD remap, 9 grid.y of the dkv launch, 10 rows of the bias-gradient partial tables in the workspace; -1 for an unknown field.  Pure:
+// a refusal does not touch the library's last-error text.
+extern "C" int diqt_mqa_attention_bwd_route(int G, int n, int h, int d, int n_extra, int n_self, int has_rel, int has_null, int field) {
+    AttnBwdPlan p;
+    const int rc = attn_bwd_plan(p, G, n, h, d, n_extra, n_self, has_rel != 0, has_null != 0);
+    switch (field) {
+        case 0: return p.path;
+        case 1: return rc;
+        case 2: return p.nwg;
+        case 3: return p.KW;
+        case 4: return p.perWave;
+        case 5: return p.EV;
+        case 6: return p.nkt;
+        case 7: return p.relLds;
+        case 8: return p.remap;
+        case 9: return p.dkvGy;
+        case 10: return p.rows;
+    }
+    return -1;
 }
 
 extern "C" size_t diqt_mqa_attention_bwd_workspace_bytes(int G, int n, int h, int d, int n_extra, int n_self, int has_rel) {
@@ -1524,98 +1651,69 @@ extern "C" int diqt_mqa_attention_bwd(const float* q, const float* kv, const flo
                                       void* workspace, size_t workspace_bytes, int G, int n, int h, int d, int n_extra, int n_self,
                                       int causal, float scale, void* stream) {
     DIQT_REQUIRE(q && kv && out && dout && lse && dq && dkv && workspace, DIQT_E_ALIGN, "mqa_attention_bwd: null pointer");
-    DIQT_REQUIRE(G > 0 && n > 0 && h > 0 && n_extra >= 0 && n_self >= 0 && n_extra + n_self > 0, DIQT_E_SHAPE, "mqa_attention_bwd: bad shape");
-    DIQT_REQUIRE(d == 32 || d == 64, DIQT_E_UNSUPPORTED, "mqa_attention_bwd: dim_head %d (32 or 64 are built)", d);
-    DIQT_REQUIRE(!(causal || rel) || n_self == n, DIQT_E_SHAPE, "mqa_attention_bwd: causal / relative bias need n_self == n");
-    DIQT_REQUIRE(!null_bias || n_extra >= 1, DIQT_E_SHAPE, "mqa_attention_bwd: null bias without a null key");
+    AttnBwdPlan p;
+    {
+        const int rc = attn_bwd_plan(p, G, n, h, d, n_extra, n_self, rel != nullptr, null_bias != nullptr);
+        DIQT_REQUIRE(rc == DIQT_OK, rc, "%s", p.why);
+    }
+    DIQT_REQUIRE(!causal || n_self == n, DIQT_E_SHAPE, "mqa_attention_bwd: causal / relative bias need n_self == n");
     DIQT_REQUIRE(!rel || drel, DIQT_E_ALIGN, "mqa_attention_bwd: relative bias without a gradient buffer");
     DIQT_REQUIRE(!null_bias || dnull, DIQT_E_ALIGN, "mqa_attention_bwd: null bias without a gradient buffer");
     DIQT_REQUIRE(aligned16(q) && aligned16(kv) && aligned16(out) && aligned16(dout) && aligned16(dq) && aligned16(dkv) && aligned16(workspace),
                  DIQT_E_ALIGN, "mqa_attention_bwd: pointers must be 16-byte aligned");
-    DIQT_REQUIRE(G <= 65535, DIQT_E_SHAPE, "mqa_attention_bwd: G > 65535");
     const size_t need = diqt_mqa_attention_bwd_workspace_bytes(G, n, h, d, n_extra, n_self, rel ? 1 : 0);
     DIQT_REQUIRE(workspace_bytes >= need, DIQT_E_WORKSPACE, "mqa_attention_bwd: workspace %zu < %zu", workspace_bytes, need);
-    const int TBL = rel ? (2 * n_self - 1) * h : 0;
-    DIQT_REQUIRE((size_t)4 * TBL * sizeof(float) <= 24 * 1024, DIQT_E_UNSUPPORTED,
-                 "mqa_attention_bwd: relative-bias table of %d entries per wave does not fit the LDS budget", TBL);
     hipStream_t s = (hipStream_t)stream;
-    const int R = n * h, M = n_extra + n_self;
-    const int gx = (R + AQ - 1) / AQ, gy = G < 256 ? G : 256, rows = gy * gx * 4;
+    const int TBL = p.TBL, R = n * h;
     float* delta = static_cast<float*>(workspace);
     float* tbl_part = delta + (size_t)G * R;
-    float* dnull_part = tbl_part + (size_t)rows * TBL;
-    {
-        // thousands of short sequences with the lone null key (the temporal attentions): everything in one pass, a sequence per wave
-        const unsigned long long ob = (unsigned long long)G * R * d * 4ull;
-        const int relLds = rel ? TBL : 0;
-        const int perw = (32 * d + 3 * 32 * (d + 4) + 64 + 2 * d + TBL + 255) / 256 * 256;
-        const size_t lds = ((size_t)4 * perw + relLds + 64) * sizeof(float);
-        if (n_extra == 1 && n_self == n && n <= 32 && 32 % h == 0 && G >= 512 && ob < (1ull << 31) && lds <= 160 * 1024) {
-            const int nwg = (G + 3) / 4 < 256 ? (G + 3) / 4 : 256;
-            auto kern = d == 64 ? mqa_seq_bwd_kernel<2> : mqa_seq_bwd_kernel<1>;
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            DIQT_REQUIRE(e == hipSuccess, DIQT_E_LAUNCH, "mqa_attention_bwd(seq): hipFuncSetAttribute: %s", hipGetErrorString(e));
-            float* dnp = tbl_part + (size_t)nwg * 4 * TBL;                          // (nwg * 4 <= rows: fits the workspace of the two-kernel path)
-            hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(256), lds, s, q, kv, rel, null_bias, out, dout, lse, dq, dkv, tbl_part,
-                               null_bias ? dnp : (float*)nullptr, n, h, causal, scale, G, relLds, (unsigned)ob);
-            int rc = check_launch("mqa_attention_bwd(seq)");
+    float* dnull_part = tbl_part + (size_t)p.rows * TBL;
+    const int ntb = rel ? (TBL + 63) / 64 : 0;
+    const size_t lds_r = (size_t)(256 * h > 256 ? 256 * h : 256) * sizeof(float);
+    if (p.path == 1) {
+        auto kern = d == 64 ? mqa_seq_bwd_kernel<2> : mqa_seq_bwd_kernel<1>;
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.ldsSeq);
+        DIQT_REQUIRE(e == hipSuccess, DIQT_E_LAUNCH, "mqa_attention_bwd(seq): hipFuncSetAttribute: %s", hipGetErrorString(e));
+        float* dnp = tbl_part + (size_t)p.nwg * 4 * TBL;
+        hipLaunchKernelGGL(kern, dim3((unsigned)p.nwg), dim3(256), p.ldsSeq, s, q, kv, rel, null_bias, out, dout, lse, dq, dkv, tbl_part,
+                           null_bias ? dnp : (float*)nullptr, n, h, causal, scale, G, p.relLds, (unsigned)p.ob);
+        int rc = check_launch("mqa_attention_bwd(seq)");
+        if (rc) return rc;
+        if (rel || null_bias) {
+            // lane l of a wave's row always carries head l % h here (32 % h == 0): gx = 1 and an unbounded R give exactly that mapping
+            hipLaunchKernelGGL(attn_bias_reduce_kernel, dim3((unsigned)(ntb + (null_bias ? 1 : 0))), dim3(256), lds_r, s, tbl_part, dnp,
+                               rel ? drel : (float*)nullptr, null_bias ? dnull : (float*)nullptr, p.nwg * 4, TBL, 1, h, 0x7fffffff, ntb);
+            rc = check_launch("mqa_attention_bwd(seq, bias reduce)");
             if (rc) return rc;
-            if (rel || null_bias) {
-                const int ntb = rel ? (TBL + 63) / 64 : 0;
-                const size_t lds_r = (size_t)(256 * h > 256 ? 256 * h : 256) * sizeof(float);
-                // lane l of a wave's row always carries head l % h here (32 % h == 0): gx = 1 and an unbounded R give exactly that mapping
-                hipLaunchKernelGGL(attn_bias_reduce_kernel, dim3((unsigned)(ntb + (null_bias ? 1 : 0))), dim3(256), lds_r, s, tbl_part, dnp,
-                                   rel ? drel : (float*)nullptr, null_bias ? dnull : (float*)nullptr, nwg * 4, TBL, 1, h, 0x7fffffff, ntb);
-                rc = check_launch("mqa_attention_bwd(seq, bias reduce)");
-                if (rc) return rc;
-            }
-            return DIQT_OK;
         }
+        return DIQT_OK;
     }
     {
-        const dim3 grid(gx, gy);
-        const size_t lds = (size_t)4 * TBL * sizeof(float);
+        const dim3 grid(p.gx, p.gy);
         if (d == 64)
-            hipLaunchKernelGGL(mqa_flash_bwd_dq_kernel<2>, grid, dim3(256), lds, s, q, kv, rel, null_bias, out, dout, lse, dq, delta, tbl_part,
+            hipLaunchKernelGGL(mqa_flash_bwd_dq_kernel<2>, grid, dim3(256), p.ldsDq, s, q, kv, rel, null_bias, out, dout, lse, dq, delta, tbl_part,
                                null_bias ? dnull_part : (float*)nullptr, G, n, h, n_extra, n_self, causal, scale);
         else
-            hipLaunchKernelGGL(mqa_flash_bwd_dq_kernel<1>, grid, dim3(256), lds, s, q, kv, rel, null_bias, out, dout, lse, dq, delta, tbl_part,
+            hipLaunchKernelGGL(mqa_flash_bwd_dq_kernel<1>, grid, dim3(256), p.ldsDq, s, q, kv, rel, null_bias, out, dout, lse, dq, delta, tbl_part,
                                null_bias ? dnull_part : (float*)nullptr, G, n, h, n_extra, n_self, causal, scale);
         int rc = check_launch("mqa_attention_bwd(dq)");
         if (rc) return rc;
     }
     if (rel || null_bias) {
-        const int ntb = rel ? (TBL + 63) / 64 : 0;
-        const size_t lds_r = (size_t)(256 * h > 256 ? 256 * h : 256) * sizeof(float);
         hipLaunchKernelGGL(attn_bias_reduce_kernel, dim3((unsigned)(ntb + (null_bias ? 1 : 0))), dim3(256), lds_r, s, tbl_part, dnull_part,
-                           rel ? drel : (float*)nullptr, null_bias ? dnull : (float*)nullptr, rows, TBL, gx, h, R, ntb);
+                           rel ? drel : (float*)nullptr, null_bias ? dnull : (float*)nullptr, p.rows, TBL, p.gx, h, R, ntb);
         int rc = check_launch("mqa_attention_bwd(bias reduce)");
         if (rc) return rc;
     }
     {
-        // keys that go through the MFMA tiles: a lone null key, or a few extra keys in front of at least as many self-key tiles, are VALU work
-        const int EV = (n_extra == 1 || (n_extra >= 1 && n_extra <= 8 && n_extra <= (n_self + 31) / 32)) ? n_extra : 0;
-        const int Mt = M - EV;
-        // key tiles per workgroup; the other 4 / KW waves split the query tiles.  Few batch entries (the joint 2048-token attentions:
-        // G = 8) need the finer split to fill 256 CUs: every workgroup walks ALL query rows of its batch entry.
-        int KW = Mt <= 32 ? 1 : (Mt <= 64 ? 2 : 4);
-        while (KW > 1 && (long long)((Mt + 32 * KW - 1) / (32 * KW)) * G < 512) KW >>= 1;
-        const bool perWave = Mt <= 32 && G >= 2048;      // one sequence per wave (see the kernel)
-        if (perWave) KW = 0;
-        const int nkt = perWave ? 1 : (Mt > 0 ? (Mt + 32 * KW - 1) / (32 * KW) : 1);
-        const dim3 grid((unsigned)nkt, perWave ? (unsigned)((G + 3) / 4) : (unsigned)G);
-        const int ROW = d + 4;
-        size_t lds = (size_t)4 * (2 * 32 * ROW + 128 + 2 * d) * sizeof(float);
-        const int relLds = (rel && h <= 64 && (2 * n_self - 1) * h <= 4096) ? (2 * n_self - 1) * h : 0;      // bias tables in LDS (<= 16 KB)
-        const size_t red = (size_t)(perWave ? 0 : 4 - KW) * (2 * (d / 32) * 16 * 64 + 128) * sizeof(float);
-        DIQT_REQUIRE(red <= lds, DIQT_E_UNSUPPORTED, "mqa_attention_bwd: combine region larger than the staging regions");
-        lds += (size_t)(relLds + 64) * sizeof(float);          // bias tables behind the staging regions
+        const dim3 grid((unsigned)p.nkt, (unsigned)p.dkvGy);
         auto kern = d == 64 ? mqa_flash_bwd_dkv_kernel<2> : mqa_flash_bwd_dkv_kernel<1>;
-        if (lds > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (p.dkvRaiseLds) {
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.ldsDkv);
             DIQT_REQUIRE(e == hipSuccess, DIQT_E_LAUNCH, "mqa_attention_bwd: hipFuncSetAttribute: %s", hipGetErrorString(e));
         }
-        hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, q, kv, rel, null_bias, dout, lse, delta, dkv, n, h, n_extra, n_self, causal, scale, KW, G, relLds, EV);
+        hipLaunchKernelGGL(kern, grid, dim3(256), p.ldsDkv, s, q, kv, rel, null_bias, dout, lse, delta, dkv, n, h, n_extra, n_self, causal, scale,
+                           p.KW, G, p.relLds, p.EV);
         return check_launch("mqa_attention_bwd(dkv)");
     }
 }

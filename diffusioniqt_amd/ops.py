@@ -2029,7 +2029,7 @@ def mqa_attention(q, kv_ext, rel, null_bias, n, h, d, n_extra, n_self, causal, s
 
 def mqa_attention_fused_ok(G, n, h, d, n_self, has_rel):
     """Shapes the fused training kernels take (otherwise: GEMM -> attn_softmax -> GEMM)."""
-    return d in (32, 64) and G <= 65535 and (not has_rel or 4 * (2 * n_self - 1) * h * 4 <= 24 * 1024)
+    return d in (32, 64) and G <= 65535 and h <= 64 and (not has_rel or 4 * (2 * n_self - 1) * h * 4 <= 24 * 1024)
 
 
 def attn_softmax(sim, rel, null_bias, n, h, n_extra, n_self, causal):

@@ -765,6 +765,13 @@ int diqt_temporal_attention_h(const float* x, const float* norm_g, const void* w
 int diqt_mqa_attention_fwd_lse(const float* q, const float* kv, const float* rel, const float* null_bias, float* out, float* lse,
                                int G, int n, int h, int d, int n_extra, int n_self, int causal, float scale, void* stream);
 size_t diqt_mqa_attention_bwd_workspace_bytes(int G, int n, int h, int d, int n_extra, int n_self, int has_rel);
+/* The plan diqt_mqa_attention_bwd launches from, as a pure shape query (no GPU): `field` 0 the path (0 refused, 1 the one-pass
+ * short-sequence kernel, 2 the dQ kernel followed by the dK/dV kernel), 1 the error code of a refusal (0 otherwise), 2 the workgroups
+ * that write bias-gradient partials, and of the dK/dV launch 3 key tiles per workgroup KW (0: a sequence per wave), 4 sequence per wave,
+ * 5 extra keys taken by the VALU, 6 grid.x, 7 floats of the bias table kept in LDS, 8 whether its XCD remap applies, 9 grid.y; 10 the
+ * rows of bias-gradient partials the workspace holds.  Refused: dim_head other than 32 / 64, more than 64 heads, G > 65535, a table
+ * of more than 1536 entries.  Leaves diqt_last_error alone.                                                                          */
+int diqt_mqa_attention_bwd_route(int G, int n, int h, int d, int n_extra, int n_self, int has_rel, int has_null, int field);
 int diqt_mqa_attention_bwd(const float* q, const float* kv, const float* rel, const float* null_bias, const float* out,
                            const float* dout, const float* lse, float* dq, float* dkv, float* drel, float* dnull,
                            void* workspace, size_t workspace_bytes, int G, int n, int h, int d, int n_extra, int n_self,
@@ -777,6 +784,9 @@ int diqt_mqa_attention_bwd(const float* q, const float* kv, const float* rel, co
  * Otherwise the arguments and layouts of diqt_mqa_attention_fwd.                                      */
 int diqt_mqa_attention_fwd_h(const float* q, const void* kv_h, const float* rel, const float* null_bias, float* out, int G, int n,
                              int h, int d, int n_extra, int n_self, int causal, float scale, int bf16, int round_out, void* stream);
+/* The one decision of diqt_mqa_attention_fwd_h as a pure shape query: `field` 0 waves per workgroup (4 or 8), 1 query rows per
+ * workgroup, 2 whether the relative-bias instantiation runs.                                                                       */
+int diqt_mqa_attention_fwd_h_route(int n, int h, int d, int has_rel, int field);
 /* y[i] = (fp16 | bf16) x[i]: the 16-bit copy of the K|V rows that diqt_mqa_attention_fwd_h streams (n even).                   */
 int diqt_cast_to_h(const float* x, void* y_h, size_t n, int bf16, void* stream);
 

@@ -46,6 +46,18 @@ def test_shape_queries_without_a_gpu():
     assert _lib.query("diqt_conv3d_fwd_h_supported", 8, 32, 32, 32, 2, 64, 3, 3, 3, 1, 1, 1, 0, 0, 0) == 0      # tap-packed fp32 kernel
     assert _lib.query("diqt_conv3d_fwd_h_supported", 64, 64, 64, 64, 64, 64, 3, 3, 3, 1, 1, 1, 0, 0, 0) == 0    # 4 GiB tensors
     assert _lib.query("diqt_conv3d_fwd_h_supported", 1, 16, 16, 16, 32, 32, 15, 15, 15, 7, 7, 7, 0, 0, 0) == 0  # halo beyond the LDS
+    # the plans the fused-attention launchers run from: path (0 refused, 1 one-pass short-sequence kernel, 2 dQ then dK/dV kernel), error code,
+    # partial-writing workgroups, KW, sequence per wave, VALU extra keys, key-tile workgroups, LDS table floats, XCD remap, grid.y
+    route = lambda *a: [_lib.query("diqt_mqa_attention_bwd_route", *a, f) for f in range(11)]
+    assert route(2100, 32, 8, 64, 1, 32, 1, 1) == [1, 0, 256, -1, 0, 0, 0, 504, 0, 0, 2048]            # the temporal attention of Unet3D
+    assert route(8, 2048, 8, 64, 5, 2048, 0, 0) == [2, 0, 8 * 128, 1, 0, 5, 64, 0, 1, 8, 4096]          # the joint space-time attention
+    assert route(2050, 6, 3, 32, 1, 6, 0, 0)[:7] == [2, 0, 256, 0, 1, 1, 1]                        # heads that do not divide 32: a sequence per wave
+    assert route(1, 100, 8, 64, 1, 100, 1, 1)[:2] == [0, -3] and route(1, 96, 8, 64, 1, 96, 1, 1)[0] == 2     # (2 n - 1) h <= 1536
+    assert route(1, 8, 2, 48, 1, 8, 0, 0)[:2] == [0, -3] and route(65536, 8, 2, 32, 1, 8, 0, 0)[:2] == [0, -1]
+    assert _lib.query("diqt_mqa_attention_bwd_route", 1, 8, 2, 32, 1, 8, 0, 0, 99) == -1
+    fwd_h = lambda *a: [_lib.query("diqt_mqa_attention_fwd_h_route", *a, f) for f in range(3)]
+    assert fwd_h(512, 8, 64, 0) == [4, 128, 0] and fwd_h(1365, 3, 64, 0) == [8, 256, 0]
+    assert fwd_h(512, 8, 64, 1) == [8, 256, 1] and fwd_h(512, 8, 32, 0) == [8, 256, 0]
 
 
 def test_bad_arguments_return_error_codes_not_crashes():

@@ -11,6 +11,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests.attn_fuzz_plan import mqa_ref as _mqa_ref      # float64 restatement of Attention.forward's products (imagen_video.py:483-520)
+
 pytestmark = pytest.mark.gpu
 
 
@@ -514,23 +516,6 @@ def test_fused_mqa_attention_forward(ops, G, n, h, d, E, use_rel, causal):
     got = ops.mqa_attention_nograd(q.to(DEV), kv.to(DEV), rel.to(DEV) if use_rel else None, nb.to(DEV) if use_rel else None,
                                    n, h, d, E, n, causal, scale)
     close(got, ref, tol=3e-5, what="fused MQA attention")
-
-
-def _mqa_ref(q, kv, rel, nb, n, h, d, E, causal, scale):
-    """float64 restatement of Attention.forward's products (imagen_video.py:483-520) on leaf tensors that require grad"""
-    G = q.shape[0]
-    qd = q.reshape(G, n, h, d)
-    k, v = kv[..., :d], kv[..., d:]
-    sim = torch.einsum('gihd,gjd->gihj', qd, k) * scale
-    if rel is not None:
-        i = torch.arange(n)[:, None]; j = torch.arange(n)[None, :]
-        bias = rel[(i - j + n - 1)].permute(0, 2, 1)[None]                                  # [1, n, h, n] indexed (i, hh, j)
-        sim = torch.cat((sim[..., :E - 1], sim[..., E - 1:E] + nb[None, None, :, None], sim[..., E:] + bias), dim=-1)
-    if causal:
-        i = torch.arange(n)[:, None]; j = torch.arange(n)[None, :]
-        mask = torch.cat((torch.zeros(n, E, dtype=torch.bool), j > i), dim=1)[None, :, None, :]
-        sim = sim.masked_fill(mask, float('-inf'))
-    return torch.einsum('gihj,gjd->gihd', sim.softmax(dim=-1), v).reshape(G, n, h * d)
 
 
 @pytest.mark.parametrize("G,n,h,d,E,use_rel,causal", [
