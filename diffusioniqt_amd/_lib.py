@@ -167,6 +167,8 @@ PROTOTYPES = {
     "diqt_anchored_noise": (I, [P, I, I, I, I, I, I, ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_uint, I, P, P]),
     "diqt_volume_joint_step": (I, [P] * 6 + [I] * 9 + [F] * 5 + [I, ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_uint, P]),
     "diqt_volume_joint_multistep": (I, [P] * 7 + [I] * 9 + [F] * 5 + [I, P]),
+    "diqt_multistep_sde_step": (I, [P] * 9 + [I, Z, P]),
+    "diqt_volume_joint_multistep_sde": (I, [P] * 7 + [I] * 9 + [F] * 6 + [I, ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_uint, P]),
     "diqt_volume_joint_heun": (I, [P] * 6 + [I] * 10 + [F] * 7 + [I, ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_uint, P]),
     "diqt_volume_joint_finish": (I, [P] * 6 + [I] * 10 + [F, F, F, F, P]),
     "diqt_patch_pair_crop_workspace_bytes": (Z, [I, I]),

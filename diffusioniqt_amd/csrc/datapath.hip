@@ -12,7 +12,9 @@
 //     windows draw the same noise (diffusioniqt_amd/inference.py, noise='anchored'; in place of one torch.randn per window batch).
 //   * lockstep joint sampling of the overlapping windows: one reverse step of the noisy state of the whole volume per launch -- the
 //     blend walk over the windows' x0 predictions, the sampler step and the anchored noise fused (diffusioniqt_amd/inference.py,
-//     joint=True), and the per-sample finish (fill, background reset, statistics over the samples).
+//     joint=True), and the per-sample finish (fill, background reset, statistics over the samples),
+//   * the sigma-space DPM-Solver++ 2M step of the EDM family (ElucidatedImagen(sampler='dpmpp2m'), ODE and SDE), per window batch and
+//     on the joint state.
 // All reductions are two-stage with a fixed order (bit-reproducible).
 #include "common.h"
 
@@ -572,6 +574,79 @@ __global__ __launch_bounds__(256) void volume_joint_multistep_kernel(const float
     x_next[v] = sampler_update(kx, xt, k0, x0, kp, prev);
 }
 
+// DPM-Solver++ 2M in sigma space (the EDM family; ElucidatedImagen.dpmpp2m_coefficients), ODE (kn == 0) and midpoint SDE (kn != 0):
+// x_next = kx x + k0 D_i + kp D_{i-1} + kn n.  The first three terms are sampler_update's, in its order; the rounded kn n product is
+// added last, and not at all when kn == 0 (no operand read, no Philox call).  ONE definition for the per-window step and the joint
+// step, so at stride = patch the joint chain is the per-window loop bit for bit.
+__device__ __forceinline__ float sampler_update_sde(float kx, float x, float k0, float d0, float kp, float dprev, float kn, float n) {
+#pragma clang fp contract(off)
+    float u = sampler_update(kx, x, k0, d0, kp, dprev);
+    if (kn != 0.f) {
+        const float c = kn * n;
+        u = u + c;
+    }
+    return u;
+}
+// The per-window step: x / x0 / x0_prev / noise [B][per], one coefficient row per sample (device [B] each).  x0_prev == NULL and
+// noise == NULL stand for zeros and are not read; noise is not read either for a sample whose kn is 0.  There is no clamp: x0 arrives
+// clamped or thresholded.  x_next may alias x (every thread reads its own element, then writes it).  Block (64, 4) = 256 consecutive
+// elements of sample blockIdx.y.
+__global__ __launch_bounds__(256) void multistep_sde_step_kernel(const float* x, const float* __restrict__ x0,
+                                                                 const float* __restrict__ x0_prev, const float* __restrict__ noise,
+                                                                 const float* __restrict__ kx, const float* __restrict__ k0,
+                                                                 const float* __restrict__ kp, const float* __restrict__ kn,
+                                                                 float* x_next, size_t per) {
+    const int b = blockIdx.y;
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.y * 64 + threadIdx.x;
+    if (e >= per) return;
+    const size_t v = (size_t)b * per + e;
+    const float cn = noise ? kn[b] : 0.f;              // no noise: the term is dropped, as for kn == 0
+    const float prev = x0_prev ? x0_prev[v] : 0.f;
+    const float n = cn != 0.f ? noise[v] : 0.f;
+    x_next[v] = sampler_update_sde(kx[b], x[v], k0[b], x0[v], kp[b], prev, cn, n);
+}
+// volume_joint_multistep_kernel plus the anchored normal of (seed, draw, sample) at the voxel, channel 0 (the step kernel's own Philox
+// call and philox_normal; none when kn == 0).  x_t == NULL is the initial state, x_next = kn n(draw) at EVERY voxel as one rounded
+// product: the initial image sigma0 n as the per-window sampler stores it.  Uncovered voxels keep x_t and get x0_out = 0.  x_next may
+// alias x_t and x0_out may alias x0_prev (no __restrict__ on the four).
+__global__ __launch_bounds__(256) void volume_joint_multistep_sde_kernel(const float* __restrict__ y, const int* __restrict__ slot,
+                                                                         const float* __restrict__ taps, const float* x_t,
+                                                                         const float* x0_prev, float* x_next, float* x0_out, int N,
+                                                                         int D, int H, int W, int P, int stride, int G0, int G1, int G2,
+                                                                         float kx, float k0, float kp, float kn, float lo, float hi,
+                                                                         int clamp_mode, unsigned key0, unsigned key1, unsigned draw,
+                                                                         unsigned sample) {
+    extern __shared__ float tp[];                      // [P]
+    if (x_t) {                                         // uniform over the launch
+        for (int e = threadIdx.y * 64 + threadIdx.x; e < P; e += 256) tp[e] = taps[e];
+        __syncthreads();
+    }
+    const int x = blockIdx.x * 64 + threadIdx.x;
+    const int h = __builtin_amdgcn_readfirstlane(blockIdx.y * 4 + threadIdx.y), d = blockIdx.z;
+    if (h >= H || x >= W) return;
+    const size_t v = ((size_t)d * H + h) * W + x;      // = lin of channel 0
+    const unsigned v0 = (unsigned)v, v1 = (unsigned)((unsigned long long)v >> 32);
+    if (!x_t) {
+        x_next[v] = kn * philox_normal(philox4x32_10(v0, v1, draw, sample, key0, key1));
+        return;
+    }
+    float num, den;
+    window_walk(y, slot, taps, tp, N, P, stride, G1, G2, d, h, x, covering(d, h, x, P, stride, G0, G1, G2),
+                StepClamp{lo, hi, clamp_mode}, num, den);
+    const float xt = x_t[v];
+    if (den == 0.f) {
+        x_next[v] = xt;
+        x0_out[v] = 0.f;
+        return;
+    }
+    const float x0 = num / den;
+    const float prev = x0_prev ? x0_prev[v] : 0.f;
+    float n = 0.f;
+    if (kn != 0.f) n = philox_normal(philox4x32_10(v0, v1, draw, sample, key0, key1));
+    x0_out[v] = x0;
+    x_next[v] = sampler_update_sde(kx, xt, k0, x0, kp, prev, kn, n);
+}
+
 // The stochastic Heun sampler of the EDM family (elucidated_imagen.py:382-532) on the same state: a churn, a predictor and a corrector
 // per step, two U-Net evaluations, so the state is three volumes -- xh = images_hat, xn = images_next, x0 = the fused prediction (the
 // one self-conditioning reads) -- and the launch takes a `phase`, uniform over the grid:
@@ -948,6 +1023,41 @@ extern "C" int diqt_volume_joint_multistep(const float* y, const int* slot, cons
     hipLaunchKernelGGL(volume_joint_multistep_kernel, dim3((W + 63) / 64, (H + 3) / 4, D), dim3(64, 4), (size_t)P * sizeof(float), STREAM,
                        y, slot, taps, x_t, x0_prev, x_next, x0_out, N, D, H, W, P, stride, G0, G1, G2, kx, k0, kp, lo, hi, clamp_mode);
     return check_launch("volume_joint_multistep");
+}
+
+extern "C" int diqt_multistep_sde_step(const float* x, const float* x0, const float* x0_prev, const float* noise, const float* kx,
+                                       const float* k0, const float* kp, const float* kn, float* x_next, int B, size_t per_batch,
+                                       void* stream) {
+    DIQT_REQUIRE(x && x0 && kx && k0 && kp && kn && x_next, DIQT_E_ALIGN, "multistep_sde_step: null pointer");
+    DIQT_REQUIRE(B > 0 && per_batch > 0, DIQT_E_SHAPE, "multistep_sde_step: bad shape (B %d, per_batch %zu)", B, per_batch);
+    DIQT_REQUIRE(B <= 65535 && (per_batch + 255) / 256 <= 0x7fffffffu, DIQT_E_SHAPE,
+                 "multistep_sde_step: more than 65535 samples or 2^31 - 1 blocks per sample");
+    hipLaunchKernelGGL(multistep_sde_step_kernel, dim3((unsigned)((per_batch + 255) / 256), B), dim3(64, 4), 0, STREAM, x, x0, x0_prev,
+                       noise, kx, k0, kp, kn, x_next, per_batch);
+    return check_launch("multistep_sde_step");
+}
+
+extern "C" int diqt_volume_joint_multistep_sde(const float* y, const int* slot, const float* taps, const float* x_t, const float* x0_prev,
+                                               float* x_next, float* x0_out, int N, int D, int H, int W, int P, int stride, int G0,
+                                               int G1, int G2, float kx, float k0, float kp, float kn, float lo, float hi,
+                                               int clamp_mode, unsigned long long seed, unsigned draw, unsigned sample, void* stream) {
+    DIQT_REQUIRE(x_next, DIQT_E_ALIGN, "volume_joint_multistep_sde: null pointer");
+    DIQT_REQUIRE(D > 0 && H > 0 && W > 0, DIQT_E_SHAPE, "volume_joint_multistep_sde: bad shape");
+    DIQT_REQUIRE(D <= 65535 && (H + 3) / 4 <= 65535, DIQT_E_SHAPE, "volume_joint_multistep_sde: more than 65535 planes / row groups");
+    size_t lds = 0;
+    if (x_t) {                                          // the initial state (x_t == NULL) ignores the window arguments
+        DIQT_REQUIRE(x0_out && slot && taps && (y || N == 0), DIQT_E_ALIGN, "volume_joint_multistep_sde: null pointer");
+        DIQT_REQUIRE(N >= 0, DIQT_E_SHAPE, "volume_joint_multistep_sde: windows %d", N);
+        int rc = joint_lattice_ok("volume_joint_multistep_sde", D, H, W, P, stride, G0, G1, G2);
+        if (rc) return rc;
+        DIQT_REQUIRE(clamp_mode == 0 || clamp_mode == 1, DIQT_E_UNSUPPORTED, "volume_joint_multistep_sde: clamp_mode %d (0 = min, 1 = box)",
+                     clamp_mode);
+        lds = (size_t)P * sizeof(float);
+    }
+    hipLaunchKernelGGL(volume_joint_multistep_sde_kernel, dim3((W + 63) / 64, (H + 3) / 4, D), dim3(64, 4), lds, STREAM, y, slot, taps,
+                       x_t, x0_prev, x_next, x0_out, N, D, H, W, P, stride, G0, G1, G2, kx, k0, kp, kn, lo, hi, clamp_mode,
+                       (unsigned)seed, (unsigned)(seed >> 32), draw, sample);
+    return check_launch("volume_joint_multistep_sde");
 }
 
 extern "C" int diqt_volume_joint_heun(const float* y, const int* slot, const float* taps, float* xh, float* xn, float* x0, int phase, int N,

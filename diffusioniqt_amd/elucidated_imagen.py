@@ -12,7 +12,7 @@ reference cannot.
 from collections import namedtuple
 from contextlib import contextmanager, nullcontext
 from functools import partial
-from math import sqrt
+from math import exp, expm1, log, sqrt
 from random import random
 
 import torch
@@ -61,9 +61,10 @@ class EDMWindowDenoiser:
     * ``self_cond``: whether the U-Net takes the last x0 estimate."""
     heun = True
 
-    def __init__(self, imagen, unet_number, cond_scale, clamp, sigma_min, sigma_max, unet_context):
+    def _configure(self, imagen, unet_number, cond_scale, clamp, unet_context):
+        """What every EDM window denoiser holds, whatever its sampler."""
         self.imagen, self.index, self._context = imagen, unet_number - 1, unet_context
-        hp = self.hp = imagen.hparams[self.index]
+        self.hp = imagen.hparams[self.index]
         self.cond_scale = cast_tuple(cond_scale, len(imagen.unets))[self.index]
         self.clamp_x0 = bool(clamp)
         self.dynamic_threshold = bool(imagen.dynamic_thresholding[self.index])
@@ -71,6 +72,11 @@ class EDMWindowDenoiser:
         self.self_cond = bool(getattr(unet, 'self_cond', False))
         self.lowres_cond = bool(getattr(unet, 'lowres_cond', False))
         self.draw_base = 1 if self.lowres_cond else 0
+        self.clamp = (-float('inf'), float('inf'), 1)
+
+    def __init__(self, imagen, unet_number, cond_scale, clamp, sigma_min, sigma_max, unet_context):
+        self._configure(imagen, unet_number, cond_scale, clamp, unet_context)
+        hp = self.hp
         # the schedule and the step scalars exactly as one_unet_sample computes them
         sigma_min, sigma_max = default(sigma_min, hp.sigma_min), default(sigma_max, hp.sigma_max)
         sigmas = imagen.sample_schedule(hp.num_sample_steps, hp.rho, sigma_min, sigma_max)
@@ -86,7 +92,6 @@ class EDMWindowDenoiser:
             r2 = 0.5 * (sigma_next - sigma_hat) / sigma_next if sigma_next != 0 else 0.
             rows.append([hp.S_noise * sqrt(max(sigma_hat ** 2 - sigma ** 2, 0.)), 1. + r, -r, 1. + 0.5 * r, -0.5 * r, r2, -r2])
         self.coefs = torch.tensor(rows, dtype=torch.float64).to(torch.float32)            # [T, 7] on the host, each rounded once
-        self.clamp = (-float('inf'), float('inf'), 1)
 
     def sigma_of(self, i, stage):
         """The sigma the U-Net is evaluated at: sigma_hat of step i (stage 0) or its sigma_next (stage 1)."""
@@ -95,11 +100,15 @@ class EDMWindowDenoiser:
 
     @torch.no_grad()
     def x0(self, img, lowres, i, self_cond=None, stage=0, lowres_noise=None):
-        elu = self.imagen
         if not 0 <= i < self.num_steps:
             raise ValueError(f"EDMWindowDenoiser.x0: step {i} of {self.num_steps}")
         if stage not in (0, 1) or (stage == 1 and self._steps[i][1] == 0):
             raise ValueError(f"EDMWindowDenoiser.x0: stage {stage!r} of step {i} (0 = at sigma_hat, 1 = at sigma_next, when that is not 0)")
+        return self._denoise(img, lowres, self.sigma_of(i, stage), self_cond, lowres_noise)
+
+    def _denoise(self, img, lowres, sigma, self_cond, lowres_noise):
+        """``preconditioned_network_forward`` of the windows ``img`` at ``sigma``, as ``sample`` sets it up for this U-Net."""
+        elu = self.imagen
         if self.lowres_cond and (lowres is None or lowres_noise is None):
             raise ValueError("EDMWindowDenoiser.x0: a low-res conditioned U-Net needs the low-res windows and their augmentation noise")
         dev, B = img.device, img.shape[0]
@@ -118,7 +127,7 @@ class EDMWindowDenoiser:
                     lowres_cond_img = elu._noise_lowres(lowres_cond_img, t_cpu, lowres_noise.to(dev).float())
                 sc = dict(self_cond=self_cond) if self.self_cond else {}
                 return elu.preconditioned_network_forward(
-                    unet.forward_with_cond_scale, img.float().contiguous(), self.sigma_of(i, stage), sigma_data=self.hp.sigma_data,
+                    unet.forward_with_cond_scale, img.float().contiguous(), sigma, sigma_data=self.hp.sigma_data,
                     clamp=self.clamp_x0, dynamic_threshold=self.dynamic_threshold, cond_scale=self.cond_scale,
                     **elu._unet_kwargs(unet, lowres_cond_img, lowres_noise_times), **sc)
         finally:
@@ -129,6 +138,39 @@ class EDMWindowDenoiser:
         flat = x.contiguous().view(1, -1)
         one = torch.ones(1, device=x.device)
         return self.imagen.unnormalize_img(ops.axpby3(flat, None, None, one, None, None, -1., 1., 2)).view(x.shape)
+
+
+class EDMMultistepWindowDenoiser(EDMWindowDenoiser):
+    """The per-window half of ``one_unet_sample(sampler='dpmpp2m')`` (``window_denoiser(sampler='dpmpp2m', sample_steps=K, eta=...)``):
+    ONE U-Net evaluation per step.  ``multistep = True`` and ``heun = False``; ``sigma0`` tells ``VolumeInference`` that the chain lives in
+    sigma space (the state starts as sigma0 n and a step may add noise).
+
+    * ``num_steps``; ``sigmas``: host float64 [T + 1], the fp32 schedule widened; ``sigma0``;
+    * ``coefs``: host fp32 [T,4], rows (kx, k0, kp, kn) of ``ElucidatedImagen.dpmpp2m_coefficients``;
+    * ``draw_base``: as the Heun denoiser numbers it -- the initial image is draw ``draw_base``, the normal of step i draw
+      ``draw_base + 1 + i`` (taken only where kn != 0: every step but the last with ``eta > 0``, none with ``eta == 0``);
+    * ``x0(img, lowres, i, self_cond=None, lowres_noise=None)``: ``preconditioned_network_forward`` at sigma_i itself;
+    * ``clamp``, ``finish``, ``self_cond``: the Heun denoiser's."""
+    heun = False
+    multistep = True
+
+    def __init__(self, imagen, unet_number, cond_scale, clamp, sigma_min, sigma_max, unet_context, sample_steps, eta):
+        self._configure(imagen, unet_number, cond_scale, clamp, unet_context)
+        self.eta = float(eta)
+        sigmas, self.coefs = imagen._dpmpp2m_tables(self.index, sample_steps, eta, sigma_min, sigma_max)
+        self.sigmas = sigmas.double()
+        self._sigmas = sigmas.tolist()
+        self.sigma0 = self._sigmas[0]
+        self.num_steps = len(self._sigmas) - 1
+
+    def sigma_of(self, i, stage=0):
+        return float(self._sigmas[i])
+
+    @torch.no_grad()
+    def x0(self, img, lowres, i, self_cond=None, lowres_noise=None):
+        if not 0 <= i < self.num_steps:
+            raise ValueError(f"EDMMultistepWindowDenoiser.x0: step {i} of {self.num_steps}")
+        return self._denoise(img, lowres, self.sigma_of(i), self_cond, lowres_noise)
 
 
 class ElucidatedImagen(nn.Module):
@@ -246,6 +288,60 @@ class ElucidatedImagen(nn.Module):
         sigmas = (sigma_max ** inv_rho + steps / (N - 1) * (sigma_min ** inv_rho - sigma_max ** inv_rho)) ** rho
         return torch.nn.functional.pad(sigmas, (0, 1), value=0.)
 
+    def dpmpp2m_coefficients(self, sigmas, eta=0., S_noise=1.):
+        """DPM-Solver++ 2M (Lu et al. 2022) in sigma space on the chain ``sigmas`` [T + 1] (``sample_schedule``), folded into
+        x_next = kx x + k0 D_i + kp D_{i-1} + kn n: host fp32 [T,4], rows (kx, k0, kp, kn).  With h = log(sigma / sigma'),
+        c = -expm1(-h - eta h) and r = h_{i-1} / h_i:  kx = (sigma' / sigma) exp(-eta h), k0 = c (1 + 1/(2r)), kp = -c / (2r),
+        kn = S_noise sigma' sqrt(-expm1(-2 eta h)).  ``eta == 0``: the ODE solver, kn == 0 on every row; ``eta > 0``: the midpoint
+        2M-SDE.  k0 + kp = c on every row.  Row 0 has no history, (kx, c, 0, kn) -- at eta 0 the Euler predictor (1 + r, -r) of the
+        Heun sampler -- and the row with sigma' == 0 (h infinite, r 0) is (0, 1, 0, 0), first order by definition.  The algebra runs in
+        float64 on the widened fp32 ``sigmas``; each entry is rounded to fp32 once (the rule of ``dpmpp2m_coefficients`` in
+        imagen_pytorch3D.py)."""
+        s = torch.as_tensor(sigmas).detach().cpu().double().tolist()
+        eta, S_noise = float(eta), float(S_noise)
+        rows, h_prev = [], None
+        for i, (sigma, sigma_next) in enumerate(zip(s[:-1], s[1:])):
+            if sigma_next == 0:
+                rows.append([0., 1., 0., 0.])
+                h_prev = None
+                continue
+            h = log(sigma / sigma_next)
+            c = -expm1(-h - eta * h)
+            k0, kp = c, 0.
+            if i > 0 and h_prev is not None:
+                r = h_prev / h
+                k0, kp = c * (1. + 1. / (2. * r)), -c / (2. * r)
+            rows.append([sigma_next / sigma * exp(-eta * h), k0, kp, S_noise * sigma_next * sqrt(-expm1(-2. * eta * h))])
+            h_prev = h
+        return torch.tensor(rows, dtype=torch.float64).to(torch.float32)
+
+    SAMPLERS = ('heun', 'dpmpp2m')
+
+    @classmethod
+    def _check_sampler_args(cls, sampler, sample_steps, skip_steps, eta):
+        """The argument rules of ``sampler`` / ``sample_steps`` / ``eta`` for one U-Net (``ValueError``; nothing touches the device)."""
+        if sampler not in cls.SAMPLERS:
+            raise ValueError(f"sampler must be 'heun' or 'dpmpp2m', got {sampler!r}")
+        if isinstance(eta, bool) or not isinstance(eta, (int, float)) or not 0. <= eta <= 1.:
+            raise ValueError(f"eta must be a number in [0, 1], got {eta!r}")
+        if sampler == 'heun':
+            if eta != 0 or exists(sample_steps):
+                raise ValueError("sampler='heun' takes neither eta nor sample_steps: its stochasticity is S_churn and its length "
+                                 "num_sample_steps")
+            return
+        if exists(sample_steps) and (isinstance(sample_steps, bool) or int(sample_steps) != sample_steps or sample_steps < 2):
+            raise ValueError(f"sample_steps must be an integer >= 2, got {sample_steps!r}")
+        if exists(skip_steps):
+            raise ValueError("sampler='dpmpp2m' takes no skip_steps: a history term over a cut chain is meaningless -- shorten the chain "
+                             "with sample_steps")
+
+    def _dpmpp2m_tables(self, index, sample_steps, eta, sigma_min, sigma_max):
+        """(sigmas [T + 1] fp32, coefs [T,4] fp32) of ``sampler='dpmpp2m'`` for U-Net ``index``, both on the host."""
+        hp = self.hparams[index]
+        sigmas = self.sample_schedule(int(default(sample_steps, hp.num_sample_steps)), hp.rho, default(sigma_min, hp.sigma_min),
+                                      default(sigma_max, hp.sigma_max))
+        return sigmas, self.dpmpp2m_coefficients(sigmas, eta, hp.S_noise)
+
     def threshold_x_start(self, x_start, dynamic_threshold=True):
         """elucidated_imagen.py:298-311: clamp(-1, 1), or per-sample s = max(quantile(|x0|, p), 1) then clamp(-s, s) / s."""
         x_start = x_start.contiguous()
@@ -286,10 +382,22 @@ class ElucidatedImagen(nn.Module):
     @torch.no_grad()
     def one_unet_sample(self, unet, shape, *, unet_number, clamp=True, dynamic_threshold=True, cond_scale=1., use_tqdm=True,
                         inpaint_images=None, inpaint_masks=None, inpaint_resample_times=5, init_images=None,
-                        skip_steps=None, sigma_min=None, sigma_max=None, noise=None, **kwargs):
+                        skip_steps=None, sigma_min=None, sigma_max=None, noise=None, sampler='heun', sample_steps=None, eta=0.,
+                        **kwargs):
         """Stochastic Heun sampler (:382-532).  ``noise``: optional injected list [init, step_0, ...], or a callable
-        ``noise(shape) -> fp32 device tensor`` whose successive calls are those draws (one ``eps`` per step, also when gamma is 0)."""
+        ``noise(shape) -> fp32 device tensor`` whose successive calls are those draws (one ``eps`` per step, also when gamma is 0).
+
+        ``sampler='dpmpp2m'``: DPM-Solver++ 2M in sigma space (``dpmpp2m_coefficients``) on ``sample_schedule(sample_steps or
+        num_sample_steps, ...)`` -- ONE U-Net evaluation per step, at sigma_i itself, and ONE ``ops.multistep_sde_step`` launch whose
+        history operand is the clamped (or thresholded) prediction of the previous step; self-conditioning reads that same tensor.
+        ``eta == 0`` is the ODE solver (the draws are the initial image alone), ``0 < eta <= 1`` the midpoint 2M-SDE (one more draw per
+        step whose kn != 0: every step but the last).  S_churn / S_tmin / S_tmax play no part; S_noise scales kn.  No ``skip_steps``."""
         assert not exists(inpaint_images) and not exists(inpaint_masks), 'inpainting: SURVEY.md §8(f) next'
+        self._check_sampler_args(sampler, sample_steps, skip_steps, eta)
+        if sampler == 'dpmpp2m':
+            return self._dpmpp2m_sample(unet, shape, unet_number=unet_number, clamp=clamp, dynamic_threshold=dynamic_threshold,
+                                        cond_scale=cond_scale, init_images=init_images, sigma_min=sigma_min, sigma_max=sigma_max,
+                                        noise=noise, sample_steps=sample_steps, eta=eta, **kwargs)
         hp = self.hparams[unet_number - 1]
         sigma_min, sigma_max = default(sigma_min, hp.sigma_min), default(sigma_max, hp.sigma_max)
         sigmas = self.sample_schedule(hp.num_sample_steps, hp.rho, sigma_min, sigma_max)
@@ -330,11 +438,42 @@ class ElucidatedImagen(nn.Module):
         images = ops.axpby3(images, None, None, vec(1.), None, None, -1., 1., 2)    # clamp(-1, 1)   (:527)
         return self.unnormalize_img(images)
 
+    def _dpmpp2m_sample(self, unet, shape, *, unet_number, clamp, dynamic_threshold, cond_scale, init_images, sigma_min, sigma_max, noise,
+                        sample_steps, eta, **kwargs):
+        """``one_unet_sample(sampler='dpmpp2m')``; the arguments are checked there."""
+        hp = self.hparams[unet_number - 1]
+        sigmas, coefs = self._dpmpp2m_tables(unet_number - 1, sample_steps, eta, sigma_min, sigma_max)
+        sigmas = sigmas.tolist()
+        dev, B = self.device, shape[0]
+        if callable(noise):
+            draw = lambda: noise(shape).to(dev).float().contiguous()
+        else:
+            noise = list(noise) if exists(noise) else None
+            draw = (lambda: noise.pop(0).to(dev).float().contiguous()) if exists(noise) else (lambda: torch.randn(shape, device=dev))
+        images = ops.axpby3(draw(), None, None, torch.full((B,), float(sigmas[0]), device=dev), None, None)
+        if exists(init_images):
+            images = ops.add(images, init_images.to(dev).float())
+        fwd = partial(self.preconditioned_network_forward, unet.forward_with_cond_scale, sigma_data=hp.sigma_data, clamp=clamp,
+                      dynamic_threshold=dynamic_threshold, cond_scale=cond_scale, **kwargs)
+        self_cond_on = bool(getattr(unet, 'self_cond', False))
+        stochastic = (coefs[:, 3] != 0).tolist()
+        k = coefs[:, :, None].expand(-1, -1, B).contiguous().to(dev)              # [T,4,B]: one coefficient row per sample
+        x_start = None
+        for i in range(coefs.shape[0]):
+            out = fwd(images, float(sigmas[i]), **(dict(self_cond=x_start) if self_cond_on else {}))
+            images = ops.multistep_sde_step(images, out, x_start, draw() if stochastic[i] else None, k[i, 0], k[i, 1], k[i, 2], k[i, 3])
+            x_start = out
+        images = ops.axpby3(images, None, None, torch.ones(B, device=dev), None, None, -1., 1., 2)    # clamp(-1, 1)
+        return self.unnormalize_img(images)
+
     def window_denoiser(self, unet_number=2, cond_scale=1., clamp=True, sigma_min=None, sigma_max=None, inpaint_images=None,
-                        inpaint_masks=None, init_images=None, skip_steps=None, _unet_context=nullcontext):
+                        inpaint_masks=None, init_images=None, skip_steps=None, _unet_context=nullcontext, sampler='heun',
+                        sample_steps=None, eta=0.):
         """The per-window half of ``one_unet_sample`` as an object that is called one U-Net evaluation at a time -- what
-        ``VolumeInference(..., joint=True)`` drives for the EDM family; see ``EDMWindowDenoiser``.  Inpainting, ``init_images`` and
+        ``VolumeInference(..., joint=True)`` drives for the EDM family; see ``EDMWindowDenoiser`` and, for ``sampler='dpmpp2m'``
+        (``sample_steps`` / ``eta`` as in ``one_unet_sample``), ``EDMMultistepWindowDenoiser``.  Inpainting, ``init_images`` and
         ``skip_steps`` belong to the one-call sampler and are refused here (``ValueError``, before anything touches the device)."""
+        self._check_sampler_args(sampler, sample_steps, None, eta)
         if exists(inpaint_images) or exists(inpaint_masks):
             raise ValueError("window_denoiser does not inpaint: the joint chain has no per-window re-noising loop")
         if exists(init_images):
@@ -345,6 +484,9 @@ class ElucidatedImagen(nn.Module):
             raise ValueError(f"unet_number must be 1 .. {len(self.unets)}, got {unet_number!r}")
         if isinstance(self.unets[unet_number - 1], NullUnet):
             raise ValueError('one cannot sample from null / placeholder unets')
+        if sampler == 'dpmpp2m':
+            return EDMMultistepWindowDenoiser(self, int(unet_number), cond_scale, clamp, sigma_min, sigma_max, _unet_context, sample_steps,
+                                              eta)
         return EDMWindowDenoiser(self, int(unet_number), cond_scale, clamp, sigma_min, sigma_max, _unet_context)
 
     def _resize(self, x, size, frames=None):
@@ -366,11 +508,20 @@ class ElucidatedImagen(nn.Module):
                inpaint_resample_times=5, init_images=None, skip_steps=None, sigma_min=None, sigma_max=None, video_frames=None,
                batch_size=1, cond_scale=1., lowres_sample_noise_level=None, start_at_unet_number=1, start_image_or_video=None,
                stop_at_unet_number=None, return_all_unet_outputs=False, return_pil_images=False, use_tqdm=True, device=None,
-               noise=None):
+               noise=None, sampler='heun', sample_steps=None, eta=0.):
         """:536-702.  ``noise``: optional injected list [lowres_noise, init, step_0, ...] per sampled unet (tests), or -- when exactly
         one U-Net is sampled -- a callable ``noise(shape) -> fp32 device tensor`` whose successive calls are those draws in that order
-        (``inference.AnchoredNoise.source``: call k is draw k of the volume-anchored field)."""
+        (``inference.AnchoredNoise.source``: call k is draw k of the volume-anchored field).
+
+        ``sampler`` ('heun', the default, or 'dpmpp2m'), ``sample_steps`` and ``eta`` -- one value, or one per U-Net like ``skip_steps``
+        -- are ``one_unet_sample``'s.  Under 'dpmpp2m' the draws of a U-Net are the low-res augmentation noise (if it is low-res
+        conditioned), the initial image, then one per step whose kn != 0 (none with ``eta == 0``); the churn hyper-parameters (S_churn,
+        S_tmin, S_tmax) play no part.  Refused with ``ValueError`` before anything touches the device: an unknown sampler, ``eta``
+        outside [0, 1], ``eta`` or ``sample_steps`` with 'heun', ``sample_steps < 2``, ``skip_steps`` with 'dpmpp2m'."""
         assert texts is None and text_embeds is None and not return_pil_images
+        samplers, steps_per_unet, etas = (cast_tuple(v, len(self.unets)) for v in (sampler, sample_steps, eta))
+        for args in zip(samplers, steps_per_unet, cast_tuple(skip_steps, len(self.unets)), etas):
+            self._check_sampler_args(*args)
         if callable(noise):
             sampled = range(start_at_unet_number, default(stop_at_unet_number, len(self.unets)) + 1)
             if len(sampled) != 1:
@@ -393,9 +544,10 @@ class ElucidatedImagen(nn.Module):
             assert exists(start_image_or_video), 'starting image or video must be supplied if only doing upscaling'
             img = self._resize(start_image_or_video.to(device), self.image_sizes[start_at_unet_number - 2])
         outputs = []
-        for unet_number, unet, image_size, frame_dims, dynamic_threshold, unet_cond_scale, unet_init, unet_skip, smin, smax in zip(
+        for (unet_number, unet, image_size, frame_dims, dynamic_threshold, unet_cond_scale, unet_init, unet_skip, smin, smax, unet_sampler,
+             unet_steps, unet_eta) in zip(
                 range(1, num_unets + 1), self.unets, self.image_sizes, all_frame_dims, self.dynamic_thresholding, cond_scale,
-                init_images, skip_steps, sigma_min, sigma_max):
+                init_images, skip_steps, sigma_min, sigma_max, samplers, steps_per_unet, etas):
             if unet_number < start_at_unet_number:
                 continue
             assert not isinstance(unet, NullUnet), 'cannot sample from null unet'
@@ -413,10 +565,14 @@ class ElucidatedImagen(nn.Module):
                 unet_init = self._resize(unet_init, image_size, frame_dims[0])
             shape = (batch_size, self.channels, *frame_dims, image_size, image_size)
             n_draws = len(list(zip(range(self.hparams[unet_number - 1].num_sample_steps)))) - default(unet_skip, 0) + 1
+            multistep = {}
+            if unet_sampler == 'dpmpp2m':                                          # the initial image, then one draw per row with kn != 0
+                multistep = dict(sampler=unet_sampler, sample_steps=unet_steps, eta=unet_eta)
+                n_draws = 1 + int((self._dpmpp2m_tables(unet_number - 1, unet_steps, unet_eta, smin, smax)[1][:, 3] != 0).sum())
             unet_noise = noise_fn if exists(noise_fn) else ([noise.pop(0) for _ in range(n_draws)] if exists(noise) else None)
             img = self.one_unet_sample(unet, shape, unet_number=unet_number, init_images=unet_init, skip_steps=unet_skip,
                                        sigma_min=smin, sigma_max=smax, cond_scale=unet_cond_scale, dynamic_threshold=dynamic_threshold,
-                                       use_tqdm=use_tqdm, noise=unet_noise,
+                                       use_tqdm=use_tqdm, noise=unet_noise, **multistep,
                                        **({'cond_images': cond_images.to(device).float()} if exists(cond_images) else {}),
                                        **self._unet_kwargs(unet, lowres_cond_img, lowres_noise_times))
             outputs.append(img)

@@ -47,7 +47,7 @@ whole protocol is in the docstring of ``VolumeInference``).  Per sample a chain 
 windows of the state, runs the U-Net on them in ``Eval.batch_size`` batches, and ONE fused launch blends the predictions per voxel with
 the blend weights and advances the state in place; ``ops.volume_joint_finish`` applies the fill / background rules and the statistics
 over the samples.  The draw numbering is ``AnchoredNoise.source``'s, so with stride = patch (no overlap) every joint chain IS the
-independent one, bit for bit.  The three chains:
+independent one, bit for bit.  The four chains:
 * first order (``window_denoiser(sampler='ddim', sample_steps=K)`` or the ancestral default): the state starts as draw 0 of the
   anchored field and ``ops.volume_joint_step`` takes the sampler step with draw ``i + 1`` — N windows x T steps evaluations, as many
   as the independent windows cost;
@@ -59,7 +59,11 @@ independent one, bit for bit.  The three chains:
   ``ops.volume_joint_heun`` phase 1 (predictor), the windows of images_next evaluated at sigma_next and phase 2 (corrector + the next
   step's churn) -- 2 T - 1 fused launches for T steps, twice the U-Net evaluations of a first-order chain.  The low-res noise of a
   batch is draw 0 of the field at its windows, recomputed per evaluation; at stride = patch the chain is ``sample(noise=source)`` per
-  window.
+  window;
+* sigma-space multistep (``ElucidatedImagen.window_denoiser(sampler='dpmpp2m', sample_steps=K, eta=...)``, ``den.multistep`` with a
+  ``den.sigma0``): DPM-Solver++ 2M for the EDM family, ODE (``eta = 0``) or midpoint SDE -- the state starts as ``sigma0 n`` and
+  ``ops.volume_joint_multistep_sde`` takes x_next = kx x + k0 x0 + kp x0_prev + kn n per step: T evaluations per window and T + 1
+  fused launches where the Heun chain costs 2 T - 1 of each.
 """
 from types import SimpleNamespace
 
@@ -190,7 +194,10 @@ class VolumeInference:
       (``coefs`` rows are (kx, k0, kp)) and ``heun``;
     * with ``heun``: ``coefs`` rows (kc, a1, b1, a2, b2, c2, d2); ``sigma0``; ``sched`` rows (sigma, sigma_next, gamma), sigma_next == 0
       meaning no corrector; ``draw_base`` (1 when draw 0 is the low-res augmentation noise: the initial image is draw ``draw_base``, the
-      eps of step i draw ``draw_base + 1 + i``); ``x0`` also takes ``stage=`` (0: at sigma_hat, 1: at sigma_next) and ``lowres_noise=``."""
+      eps of step i draw ``draw_base + 1 + i``); ``x0`` also takes ``stage=`` (0: at sigma_hat, 1: at sigma_next) and ``lowres_noise=``;
+    * with ``multistep`` and a ``sigma0`` (the EDM family's ``sampler='dpmpp2m'``): ``coefs`` rows (kx, k0, kp, kn); the state starts as
+      ``sigma0`` times draw ``draw_base`` and step i adds kn times draw ``draw_base + 1 + i`` (no Philox call where kn == 0); ``x0`` also
+      takes ``lowres_noise=``.  A multistep denoiser without ``sigma0`` (``Imagen``'s) runs the chain above, unchanged."""
     _DENOISER = ('num_steps', 'coefs', 'clamp', 'x0', 'finish')
 
     @staticmethod
@@ -200,6 +207,9 @@ class VolumeInference:
                             **{a: bool(getattr(den, a, False)) for a in ('self_cond', 'multistep', 'heun')})
         if p.heun:
             p.draw_base, p.sigma0, p.sched = int(den.draw_base), den.sigma0, den.sched
+        p.sigma_space = p.multistep and not p.heun and hasattr(den, 'sigma0')
+        if p.sigma_space:
+            p.draw_base, p.sigma0 = int(den.draw_base), float(den.sigma0)
         return p
 
     def __init__(self, configs, sample_fn, nonzero_ratio=0.05, blend=None, sigma_scale=0.125, samples=1, noise=None, seed=0, joint=False):
@@ -325,7 +335,8 @@ class VolumeInference:
         vol = lowres_raw.float().contiguous()
         P, S, den = self.patch, self.samples, self._protocol(self.sample_fn)
         win = _Windows(self, vol)
-        chain = self._heun_chain if den.heun else self._multistep_chain if den.multistep else self._step_chain
+        chain = self._heun_chain if den.heun else self._sigma_multistep_chain if den.sigma_space else \
+            self._multistep_chain if den.multistep else self._step_chain
         y = torch.empty((win.N, P, P, P), dtype=torch.float32, device=win.device)          # reused by every step of every sample
         # and so is the fused x0 volume of the first-order and multistep chains; the Heun chain makes its three volumes per sample
         win.x0_vol = torch.empty_like(vol) if (den.self_cond or den.multistep) and not den.heun else None
@@ -362,6 +373,26 @@ class VolumeInference:
             kx, k0, kp = den.coefs[i]
             ops.volume_joint_multistep(y, win.slot, win.taps, x, win.x0_vol if i else None, kx, k0, kp, *den.clamp, self.overlap,
                                        out=x, x0_out=win.x0_vol)
+        return x
+
+    def _sigma_multistep_chain(self, den, win, evaluate, y, s):
+        """Sample ``s`` of the sigma-space multistep chain (``ElucidatedImagen.window_denoiser(sampler='dpmpp2m')``): the state starts as
+        ``sigma0 n(draw_base)``; per step the windows are evaluated at sigma_i, with draw 0 of the field at each batch as its low-res
+        noise (recomputed per evaluation, as ``_heun_chain`` does), and ONE ``ops.volume_joint_multistep_sde`` launch with draw
+        ``draw_base + 1 + i`` advances the state and ``win.x0_vol`` (the history term, and what self-conditioning gathers) in place --
+        T evaluations per window and T + 1 fused launches."""
+        base = den.draw_base
+        x, _ = ops.volume_joint_multistep_sde(None, None, None, None, None, 0., 0., 0., den.sigma0, *den.clamp, self.overlap, self.seed,
+                                              draw=base, sample=s, shape=win.shape, device=win.device)
+        for i in range(den.num_steps):
+            def x0(xw, lw, sc, o):
+                ln = ops.anchored_noise(win.noise_origins(o), lw.shape[1], self.sub, *win.shape, self.seed, draw=0, sample=s,
+                                        device=win.device) if base else None
+                return den.x0(xw, lw, i, self_cond=sc, lowres_noise=ln)
+            evaluate(x, win.x0_vol if den.self_cond and i > 0 else None, x0)
+            kx, k0, kp, kn = den.coefs[i]
+            ops.volume_joint_multistep_sde(y, win.slot, win.taps, x, win.x0_vol if i else None, kx, k0, kp, kn, *den.clamp, self.overlap,
+                                           self.seed, draw=base + 1 + i, sample=s, out=x, x0_out=win.x0_vol)
         return x
 
     def _heun_chain(self, den, win, evaluate, y, s):

@@ -2464,6 +2464,68 @@ def volume_joint_multistep(y, slot, taps, x_t, x0_prev, kx, k0, kp, lo, hi, clam
     return out, x0_out
 
 
+def multistep_sde_step(x, x0, x0_prev, noise, kx, k0, kp, kn, out=None):
+    """One step of DPM-Solver++ 2M in sigma space on a window batch (include/diqt.h, diqt_multistep_sde_step): ``x`` / ``x0`` [B, ...]
+    the state and this step's (clamped or thresholded) prediction, ``x0_prev`` the previous step's and ``noise`` the step's normals (each
+    may be None: zeros, not read), ``kx`` / ``k0`` / ``kp`` / ``kn`` device [B], one coefficient row per sample.
+    x_next = kx x + k0 x0 + kp x0_prev (+ kn noise where kn != 0).  ``out``: where x_next goes (``x`` itself for an in-place step;
+    None: a new tensor).  Returns ``out``.  One launch."""
+    _chk(x, x0, x0_prev, noise, kx, k0, kp, kn, out)
+    if x.ndim < 2 or x.numel() == 0:
+        raise ValueError(f"multistep_sde_step: x must be a non-empty [B, ...] tensor, got {tuple(x.shape)}")
+    B = x.shape[0]
+    if B > 65535:
+        raise ValueError(f"multistep_sde_step: at most 65535 samples per launch, got {B}")
+    if out is None:
+        out = torch.empty_like(x)
+    for t, name in ((x0, 'x0'), (x0_prev, 'x0_prev'), (noise, 'noise'), (out, 'out')):
+        if t is not None and t.shape != x.shape:
+            raise ValueError(f"multistep_sde_step: {name} must have x's shape {tuple(x.shape)}, got {tuple(t.shape)}")
+    for t, name in ((kx, 'kx'), (k0, 'k0'), (kp, 'kp'), (kn, 'kn')):
+        if tuple(t.shape) != (B,):
+            raise ValueError(f"multistep_sde_step: {name} must be a [B] = [{B}] tensor, got {tuple(t.shape)}")
+    _lib.call("diqt_multistep_sde_step", x, x0, x0_prev, noise, kx, k0, kp, kn, out, B, x.numel() // B, _stream())
+    return out
+
+
+def volume_joint_multistep_sde(y, slot, taps, x_t, x0_prev, kx, k0, kp, kn, lo, hi, clamp_mode, stride, seed, draw, sample=0, out=None,
+                               x0_out=None, shape=None, device=None):
+    """One step of the sigma-space DPM-Solver++ 2M chain on the joint state (include/diqt.h, diqt_volume_joint_multistep_sde):
+    ``volume_joint_multistep`` plus ``kn n`` with n the volume-anchored normal of (seed, draw, sample), added last and only when
+    ``kn != 0`` -- with ``kn == 0`` the bits of ``volume_joint_multistep``.  ``x_t = None`` is the initial state: returns
+    ``(kn n(draw), None)`` on a new [D,H,W] = ``shape`` volume (``y``, ``slot``, ``taps`` and the other coefficients are not looked at);
+    otherwise ``out`` / ``x0_out`` are where x_next and the fused x0 (0 where uncovered) go -- ``x_t`` and ``x0_prev`` themselves for an
+    in-place step, None: new tensors -- and ``(out, x0_out)`` is returned.  One launch, bit-reproducible."""
+    seed, draw, sample = _noise_key("volume_joint_multistep_sde", seed, draw, sample)
+    if x_t is None:
+        shape = tuple(int(s) for s in (shape or ()))
+        if len(shape) != 3 or min(shape) < 1:
+            raise ValueError(f"volume_joint_multistep_sde: the initial state needs shape = a positive (D, H, W), got {shape!r}")
+        if not torch.cuda.is_available():
+            raise RuntimeError("diffusioniqt_amd.ops.volume_joint_multistep_sde runs on the MI355X only (no CPU fallback)")
+        device = torch.device('cuda' if device is None else device)
+        with torch.cuda.device(device):
+            out = torch.empty(shape, dtype=torch.float32, device=device)
+            _lib.call("diqt_volume_joint_multistep_sde", None, None, None, None, None, out, None, 0, *shape, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0,
+                      float(kn), 0.0, 0.0, 0, seed, draw, sample, _stream())
+        return out, None
+    N, P, stride = _joint_windows("volume_joint_multistep_sde", y, slot, taps, x_t, clamp_mode, stride)
+    _joint_slots("volume_joint_multistep_sde", slot, N)
+    if out is None:
+        out = torch.empty_like(x_t)
+    if x0_out is None:
+        x0_out = torch.empty_like(x_t)
+    for t, name in ((x0_prev, 'x0_prev'), (out, 'out'), (x0_out, 'x0_out')):
+        if t is not None:
+            _chk(t)
+            if t.shape != x_t.shape or not t.is_contiguous():
+                raise ValueError(f"volume_joint_multistep_sde: {name} must be a contiguous tensor of x_t's shape")
+    _lib.call("diqt_volume_joint_multistep_sde", y if N else None, slot, taps, x_t, x0_prev, out, x0_out, N, *x_t.shape, P, stride,
+              *slot.shape, float(kx), float(k0), float(kp), float(kn), float(lo), float(hi), int(clamp_mode), seed, draw, sample,
+              _stream())
+    return out, x0_out
+
+
 def volume_joint_heun_init(shape, sigma0, kc, seed, draw=0, sample=0, device=None):
     """The first ``images_hat`` of a joint Heun chain (phase 0 of ``diqt_volume_joint_heun``): fp32 [D,H,W],
     ``(sigma0 n(draw)) + kc n(draw + 1)`` with n the volume-anchored normals of channel 0 -- the initial image as

@@ -638,6 +638,27 @@ int diqt_volume_joint_step(const float* y, const int* slot, const float* taps, c
 int diqt_volume_joint_multistep(const float* y, const int* slot, const float* taps, const float* x_t, const float* x0_prev,
                                 float* x_next, float* x0_out, int N, int D, int H, int W, int P, int stride, int G0, int G1, int G2,
                                 float kx, float k0, float kp, float lo, float hi, int clamp_mode, void* stream);
+/* DPM-Solver++ 2M in sigma space for the EDM family (ElucidatedImagen(sampler='dpmpp2m')), ODE and midpoint SDE: one step of ONE window
+ * batch, in place of the diqt_axpby3 sequence of a Heun step (two U-Net evaluations, three or four launches).  x / x0 / x0_prev / noise
+ * are [B][per_batch], kx / k0 / kp / kn DEVICE [B] (one coefficient row per sample):
+ *     b = k0 * x0;  c = kp * x0_prev;  u = fmaf(kx, x, b) + c;  if (kn != 0) u = u + kn * noise
+ * with b, c and kn * noise rounded products (no further contraction) -- diqt_volume_joint_multistep's update, then the noise term last.
+ * x0_prev == NULL and noise == NULL stand for zeros and are not read; noise is not read for a sample whose kn is 0.  There is no
+ * clamp (x0 arrives clamped or thresholded).  x_next may alias x.  Null pointers: DIQT_E_ALIGN; B <= 0, per_batch == 0 or B > 65535:
+ * DIQT_E_SHAPE.                                                                                                                   */
+int diqt_multistep_sde_step(const float* x, const float* x0, const float* x0_prev, const float* noise, const float* kx, const float* k0,
+                            const float* kp, const float* kn, float* x_next, int B, size_t per_batch, void* stream);
+/* The same step on the joint state, in place of diqt_volume_joint_heun's two phases per step: diqt_volume_joint_multistep plus the
+ * volume-anchored normal n of diqt_volume_joint_step (channel 0 at (seed, z, y, x, draw, sample)).  Covered voxel: x0 = num / den and
+ * the update of diqt_multistep_sde_step with that n (no Philox call when kn == 0, and then x_next and x0_out are bit for bit
+ * diqt_volume_joint_multistep's); x0_out = x0.  Uncovered voxel: x_next = x_t, x0_out = 0.  x_t == NULL is the initial state:
+ * x_next = kn * n(draw) at EVERY voxel (one rounded product: the initial image sigma0 n as the per-window sampler stores it), and the
+ * window arguments, x0_prev, x0_out, the other coefficients and the clamp are ignored.  x_next may alias x_t and x0_out may alias
+ * x0_prev.  Error codes are diqt_volume_joint_multistep's.                                                                          */
+int diqt_volume_joint_multistep_sde(const float* y, const int* slot, const float* taps, const float* x_t, const float* x0_prev,
+                                    float* x_next, float* x0_out, int N, int D, int H, int W, int P, int stride, int G0, int G1, int G2,
+                                    float kx, float k0, float kp, float kn, float lo, float hi, int clamp_mode, unsigned long long seed,
+                                    unsigned draw, unsigned sample, void* stream);
 /* The stochastic Heun sampler of the EDM family (Karras et al. 2022; elucidated_imagen.py:382-532) on the joint state: a churn, a
  * predictor and a corrector per step, two U-Net evaluations.  The state is three [D][H][W] volumes, all updated in place (every thread
  * reads only its own voxel of each, then writes it): xh = images_hat, xn = images_next, x0 = the fused prediction.  Window walk,
