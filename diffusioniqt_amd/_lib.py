@@ -123,6 +123,7 @@ PROTOTYPES = {
     "diqt_conv3d_fwd_stats_blocks": (I, [I] * 15),
     "diqt_conv3d_fwd_kernel_id": (I, [I] * 15),
     "diqt_conv3d_fwd9_variant": (I, [I] * 15 + [Z]),
+    "diqt_conv3d_fwd_route": (I, [I] * 15 + [Z, I, I, I, I, I]),
     "diqt_get_last_conv_fwd9_variant": (I, []),
     "diqt_conv3d_fwd_pk": (I, [P, P, Z, P, P, P, P, P, Z] + [I] * 15 + [P]),
     "diqt_conv3d_fwd_workspace_bytes_pk": (Z, [I] * 15 + [Z]),

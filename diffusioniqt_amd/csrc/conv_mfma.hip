@@ -26,6 +26,7 @@
 #include "conv_pw.h"
 #include "conv_fwd9.h"
 #include <type_traits>
+#include <stdio.h>
 #include <stdlib.h>
 #include <atomic>
 
@@ -1637,47 +1638,6 @@ static int wino_layout(int Cout, int Cin, int kd, int kh, int kw, size_t packed_
     return nw > 0 && packed_elems >= n + nw ? 1 : 0;
 }
 
-static size_t fwd_workspace_bytes(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw, int epd,
-                                  int eph, int epw, bool wino) {
-    ConvGeom g;
-    if (make_geom(g, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw)) return 0;
-    const int ks = fwd_ksplit(g);
-    size_t need = ks > 1 ? (size_t)ks * g.B * g.Do * g.Ho * g.Wo * g.Cout * sizeof(float) : 0;
-    {
-        F9Geom g9;
-        size_t l9;
-        unsigned gr9;
-        if (Cin % 4 == 0 && !smallcin_pad(Cin, kd * kh * kw) &&
-            fwd9_plan(g9, l9, gr9, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, diqt_conv_packed_elems(Cout, Cin, kd, kh, kw), true, wino) &&
-            g9.ksplit > 1) {
-            const size_t n9 = (size_t)g9.ksplit * g.B * g.Do * g.Ho * g.Wo * g.Cout * sizeof(float);
-            if (n9 > need) need = n9;
-        }
-    }
-    return need;
-}
-extern "C" size_t diqt_conv3d_fwd_workspace_bytes(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw,
-                                                  int pd, int ph, int pw, int epd, int eph, int epw) {
-    return fwd_workspace_bytes(B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, false);
-}
-extern "C" size_t diqt_conv3d_fwd_workspace_bytes_pk(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw,
-                                                     int pd, int ph, int pw, int epd, int eph, int epw, size_t packed_elems) {
-    return fwd_workspace_bytes(B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw,
-                               wino_layout(Cout, Cin, kd, kh, kw, packed_elems) == 1);
-}
-
-static int conv3d_fwd_impl(const float* x, const float* packed, const float* bias, const float* residual,
-                           float* y, void* workspace, size_t workspace_bytes, int B, int D, int H, int W, int Cin, int Cout,
-                           int kd, int kh, int kw, int pd, int ph, int pw, int epd, int eph, int epw, void* stream, float* stats,
-                           bool wino = false);
-
-extern "C" int diqt_conv3d_fwd(const float* x, const float* packed, const float* bias, const float* residual,
-                               float* y, int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw,
-                               int pd, int ph, int pw, int epd, int eph, int epw, void* stream) {
-    return conv3d_fwd_impl(x, packed, bias, residual, y, nullptr, 0, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph,
-                           epw, stream, nullptr);
-}
-
 // 8-wave forward plan: the geometry re-tiled for 256-voxel workgroups, or false when conv_fwd8_kernel does not take the launch
 // (fewer than two resident rounds of 256-voxel tiles, halo beyond the prefetch registers or the LDS, tensors >= 1 GiB, Cin % 4)
 static bool fwd8_plan(const ConvGeom& g, ConvGeom& g8, size_t& lds) {
@@ -1712,124 +1672,8 @@ static bool fwd8_plan(const ConvGeom& g, ConvGeom& g8, size_t& lds) {
     return true;
 }
 
-// per-tile output statistics are produced by the buffer-path kernel of an unsplit launch; returns the number of tiles per batch
-// entry (the `nblk` of the [B][nblk][2][Cout] partial layout) or 0 when this shape would take another path
-static int fwd_stats_blocks_impl(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw, int epd,
-                                 int eph, int epw, bool neighbours, bool wino = false);
-extern "C" int diqt_conv3d_fwd_stats_blocks(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph,
-                                            int pw, int epd, int eph, int epw) {
-    return fwd_stats_blocks_impl(B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, false);
-}
-extern "C" int diqt_conv3d_fwd_stats_blocks_pk(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph,
-                                               int pw, int epd, int eph, int epw, size_t packed_elems) {
-    return fwd_stats_blocks_impl(B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, false,
-                                 wino_layout(Cout, Cin, kd, kh, kw, packed_elems) == 1);
-}
-// the same for diqt_conv3d_fwd_neighbours (which never takes conv_fwd9_kernel: that kernel has no neighbour addressing)
-extern "C" int diqt_conv3d_fwd_neighbours_stats_blocks(int f, int A, int Cin, int Cout, int k) {
-    if (f < 1 || A < 1 || k < 1 || !(k & 1)) return 0;
-    return fwd_stats_blocks_impl(f * f * f, A, A, A, Cin, Cout, k, k, k, k / 2, k / 2, k / 2, 0, 0, 0, true);
-}
-static int fwd_stats_blocks_impl(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw, int epd,
-                                 int eph, int epw, bool neighbours, bool wino) {
-    ConvGeom g;
-    if (make_geom(g, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw)) return 0;
-    if (kd * kh * kw == 1) return 0;                                   // flattened 1x1x1 tiles cross batch entries
-    if (Cin % 4 != 0 || smallcin_pad(Cin, kd * kh * kw) || fwd_ksplit(g) > 1) return 0;
-    const unsigned long long xb = (unsigned long long)g.B * g.D * g.H * g.W * g.Cin * 4ull;
-    const unsigned long long yb = (unsigned long long)g.B * g.Do * g.Ho * g.Wo * g.Cout * 4ull;
-    if (xb >= (1ull << 30) || yb >= (1ull << 30)) return 0;
-    const size_t lds = ((size_t)g.HD * g.HH * g.HWd * (LDSROW + 1) + 2 * NT * LDSROW) * sizeof(float) + MTILE * sizeof(int);
-    if (lds > 160 * 1024) return 0;
-    ConvGeom g8;
-    size_t lds8;
-    {
-        F9Geom g9;
-        size_t l9;
-        unsigned gr9;
-        if (!neighbours && Cin % 4 == 0 && fwd_ksplit(g) <= 1 && !smallcin_pad(Cin, kd * kh * kw) &&
-            fwd9_plan(g9, l9, gr9, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, diqt_conv_packed_elems(Cout, Cin, kd, kh, kw), false, wino))
-            return g9.tilesD * g9.tilesH * g9.tilesW;                          // conv_fwd9_kernel: one row per 512- / 256-voxel tile
-    }
-    if (fwd8_plan(g, g8, lds8)) return g8.tilesD * g8.tilesH * g8.tilesW;      // the 8-wave kernel writes one row per 256-voxel tile
-    return g.tilesD * g.tilesH * g.tilesW;
-}
-
-// which kernel diqt_conv3d_fwd* dispatches this shape to (for profilers / bench.py, so that per-kernel numbers carry the names
-// rocprofv3 reports): 0 conv_fwd_kernel, 1 conv_fwd_smallcin_kernel, 2 conv1x1_fwd_kernel, 3 conv_fwd8_kernel, 4 conv_fwd9_kernel, -1 bad shape
-extern "C" int diqt_conv3d_fwd_kernel_id(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw,
-                                         int epd, int eph, int epw) {
-    ConvGeom g;
-    if (make_geom(g, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw)) return -1;
-    const int T = kd * kh * kw;
-    if (smallcin_pad(Cin, T)) return 1;
-    const unsigned long long xb = (unsigned long long)g.B * g.D * g.H * g.W * g.Cin * 4ull;
-    const unsigned long long yb = (unsigned long long)g.B * g.Do * g.Ho * g.Wo * g.Cout * 4ull;
-    const bool buf = Cin % 4 == 0 && xb < (1ull << 30) && yb < (1ull << 30);
-    if (!buf) return 0;
-    {
-        F9Geom g9;
-        size_t l9;
-        unsigned gr9;
-        if (fwd9_plan(g9, l9, gr9, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, diqt_conv_packed_elems(Cout, Cin, kd, kh, kw), true, false))
-            return 4;                // incl. its split-K form (callers that pass the workspace diqt_conv3d_fwd_workspace_bytes asks for)
-    }
-    if (fwd_ksplit(g) > 1) return 0;
-    ConvGeom g8;
-    size_t lds8;
-    if (fwd8_plan(g, g8, lds8)) return 3;
-    if (T == 1 && g.B == 1 && g.D == 1 && g.H == 1 && g.Wo == g.W && g.TW == MTILE) return 2;
-    return 0;
-}
-
-// conv_fwd9_kernel's variant for a launch diqt_conv3d_fwd_kernel_id routes to it, given a packed buffer of packed_elems floats
-// (F9Geom::variant; 7: Winograd F(2,3), only with the panels of pack modes 2 / 3 and diqt_conv3d_fwd_pk), -1 otherwise
-extern "C" int diqt_conv3d_fwd9_variant(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw,
-                                        int epd, int eph, int epw, size_t packed_elems) {
-    if (diqt_conv3d_fwd_kernel_id(B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw) != 4) return -1;
-    F9Geom g9;
-    size_t l9;
-    unsigned gr9;
-    if (!fwd9_plan(g9, l9, gr9, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, diqt_conv_packed_elems(Cout, Cin, kd, kh, kw),
-                   true, wino_layout(Cout, Cin, kd, kh, kw, packed_elems) == 1))
-        return -1;
-    return g9.variant;
-}
-
-// which conv_fwd9_kernel variant the process's last launch of it ran (F9Geom::variant, 7: Winograd), -1 if none since the last
-// call: a test / profiler observable of the launch itself, not of a plan
-extern "C" int diqt_get_last_conv_fwd9_variant() { return fwd9_take_last_variant(); }
-
-extern "C" int diqt_conv3d_fwd_ex(const float* x, const float* packed, const float* bias, const float* residual, float* y,
-                                  float* stats, void* workspace, size_t workspace_bytes, int B, int D, int H, int W, int Cin,
-                                  int Cout, int kd, int kh, int kw, int pd, int ph, int pw, int epd, int eph, int epw, void* stream) {
-    DIQT_REQUIRE(!stats || diqt_conv3d_fwd_stats_blocks(B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw) > 0,
-                 DIQT_E_UNSUPPORTED, "conv3d_fwd_ex: this shape does not produce output statistics (diqt_conv3d_fwd_stats_blocks == 0)");
-    return conv3d_fwd_impl(x, packed, bias, residual, y, workspace, workspace_bytes, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw,
-                           epd, eph, epw, stream, stats);
-}
-// diqt_conv3d_fwd_ex with the length of the packed buffer: a buffer that holds the Winograd panels behind the direct pack (pack modes
-// 2 / 3) lets the 3x3x3 launches with an even output width take conv_fwd9_kernel's Winograd tile; a shorter one than the direct pack
-// is refused.  Statistics rows and workspace: diqt_conv3d_fwd_stats_blocks_pk / _workspace_bytes_pk with the same length.
-extern "C" int diqt_conv3d_fwd_pk(const float* x, const float* packed, size_t packed_elems, const float* bias, const float* residual,
-                                  float* y, float* stats, void* workspace, size_t workspace_bytes, int B, int D, int H, int W, int Cin,
-                                  int Cout, int kd, int kh, int kw, int pd, int ph, int pw, int epd, int eph, int epw, void* stream) {
-    const int lay = wino_layout(Cout, Cin, kd, kh, kw, packed_elems);
-    DIQT_REQUIRE(lay >= 0, DIQT_E_SHAPE, "conv3d_fwd_pk: packed buffer of %zu floats, the direct pack alone needs %zu", packed_elems,
-                 diqt_conv_packed_elems(Cout, Cin, kd, kh, kw));
-    DIQT_REQUIRE(!stats || diqt_conv3d_fwd_stats_blocks_pk(B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, packed_elems) > 0,
-                 DIQT_E_UNSUPPORTED, "conv3d_fwd_pk: this shape does not produce output statistics (diqt_conv3d_fwd_stats_blocks_pk == 0)");
-    return conv3d_fwd_impl(x, packed, bias, residual, y, workspace, workspace_bytes, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw,
-                           epd, eph, epw, stream, stats, lay == 1);
-}
-
-// The backward-data pass of a conv that sits behind a fused GroupNorm + scale/shift + Mish/SiLU (Block.forward: GN -> act -> conv,
-// imagen_pytorch3D.py:535-566 / imagen_video.py:671-697): y = conv(x = dY of the conv, flipped packed weights) is the gradient w.r.t.
-// the activated tensor, and the epilogue of conv_fwd9_kernel -- which holds that gradient in registers -- also reads the GroupNorm
-// input gn_x at the same voxels and writes the per-tile partial sums of the GroupNorm backward (sum dz, sum dz xhat per channel):
-// partials[B][nblk][2][Cout], nblk = diqt_conv3d_fwd_gnbwd_blocks(...) (0: this shape does not run on conv_fwd9_kernel un-split; use
-// diqt_conv3d_fwd + diqt_gn_act_bwd).  diqt_gn_act_bwd_from_partials finishes the GroupNorm backward without its reduction pass.
-// Process-wide switch of that fusion: -1 = not set yet (the first query reads DIQT_GNBWD_FUSE, default off), 0 / 1 = set by the caller.
+// Process-wide switch of the GroupNorm-backward epilogue (diqt_conv3d_fwd_gnbwd below): -1 = not set yet (the first query reads
+// DIQT_GNBWD_FUSE, default off), 0 / 1 = set by the caller.
 // Both modes are product paths (the parity suite runs the whole-network gradient tests in each, tests/test_gpu_fullsize.py).
 static std::atomic<int> g_gnbwd_fuse{-1};
 extern "C" int diqt_get_gnbwd_fuse(void) {
@@ -1846,170 +1690,305 @@ extern "C" int diqt_set_gnbwd_fuse(int on) {
     g_gnbwd_fuse.store(on ? 1 : 0, std::memory_order_relaxed);
     return prev;
 }
-extern "C" int diqt_conv3d_fwd_gnbwd_blocks(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw,
-                                            int epd, int eph, int epw) {
-    // Opt-in (DIQT_GNBWD_FUSE=1 or diqt_set_gnbwd_fuse(1)): the epilogue saves the GroupNorm backward's reduction pass (35 us and 134 MB per
-    // GroupNorm at the 32^3 level) but costs the launch as much: the activation derivative per output element (exp + two reciprocals at
-    // quarter rate) is ~8.6k instructions per tile on a kernel with one wave per SIMD and nothing to overlap them with.  42.1-42.3 ms
-    // per training micro-step either way, A/B on one box.
-    const bool off = !diqt_get_gnbwd_fuse();
-    F9Geom g9;
-    size_t l9;
-    unsigned gr9;
-    if (off || Cin % 4 != 0 || smallcin_pad(Cin, kd * kh * kw) || (kd == 3 && kh == 1 && kw == 1)) return 0;     // (3,1,1): no such instantiation
-    if (!fwd9_plan(g9, l9, gr9, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, diqt_conv_packed_elems(Cout, Cin, kd, kh, kw), false, false))
-        return 0;
-    return g9.tilesD * g9.tilesH * g9.tilesW;
-}
-extern "C" int diqt_conv3d_fwd_gnbwd(const float* x, const float* packed, float* y, float* partials, const float* gn_x, const float* mean,
-                                     const float* rstd, const float* gamma, const float* beta, const float* scale, const float* shift,
-                                     int cond_stride, int G, int act, int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw,
-                                     int pd, int ph, int pw, int epd, int eph, int epw, void* stream) {
-    DIQT_REQUIRE(x && packed && y && partials && gn_x && mean && rstd, DIQT_E_ALIGN, "conv3d_fwd_gnbwd: null pointer");
-    DIQT_REQUIRE(aligned16(x) && aligned16(packed), DIQT_E_ALIGN, "conv3d_fwd_gnbwd: x and packed weights must be 16-byte aligned");
-    DIQT_REQUIRE(G > 0 && Cout % G == 0 && (act == DIQT_ACT_MISH || act == DIQT_ACT_SILU), DIQT_E_UNSUPPORTED,
-                 "conv3d_fwd_gnbwd: Mish / SiLU, groups dividing the channels");
-    DIQT_REQUIRE((scale == nullptr) == (shift == nullptr) && (!scale || cond_stride >= Cout), DIQT_E_SHAPE, "conv3d_fwd_gnbwd: scale / shift");
-    F9Geom g9;
-    size_t l9;
-    unsigned gr9;
-    DIQT_REQUIRE(diqt_conv3d_fwd_gnbwd_blocks(B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw) > 0 &&
-                     fwd9_plan(g9, l9, gr9, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw,
-                               diqt_conv_packed_elems(Cout, Cin, kd, kh, kw), false, false),
-                 DIQT_E_UNSUPPORTED, "conv3d_fwd_gnbwd: shape not taken by conv_fwd9_kernel (diqt_conv3d_fwd_gnbwd_blocks == 0)");
-    g9.stats = partials;
-    g9.gx = gn_x; g9.gmean = mean; g9.grstd = rstd; g9.ggamma = gamma; g9.gbeta = beta; g9.gscale = scale; g9.gshift = shift;
-    g9.gG = G; g9.gcs = cond_stride; g9.gact = act;
-    // the epilogue's parameters go through a small device ring (stream-ordered copy: every launch gets its own slot, 256 launches
-    // deep), so the kernel carries ONE pointer for them through its main loop
-    static F9GnParams* ring = nullptr;
-    static unsigned slot = 0;
-    if (!ring) {
-        hipError_t e = hipMalloc(&ring, 256 * sizeof(F9GnParams));
-        DIQT_REQUIRE(e == hipSuccess, DIQT_E_LAUNCH, "conv3d_fwd_gnbwd: hipMalloc: %s", hipGetErrorString(e));
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The one decision of the fp32 forward dispatch: which kernel a diqt_conv3d_fwd* / _fwd_gn* / _fwd_gnbwd call runs, with which plan,
+// how many statistics rows it writes and how much workspace it uses -- for one ask (what the caller brings and wants).  convf_launch
+// launches what this says and every shape query reads it for a fixed ask, so a query and the launch cannot drift.
+// ---------------------------------------------------------------------------------------------------------------------------------
+enum FwdKernel { FWD_UNSUPPORTED = -1, FWD_GENERIC = 0, FWD_SMALLCIN = 1, FWD_1X1 = 2, FWD_8WAVE = 3, FWD_F9 = 4 };   // as diqt_conv3d_fwd_kernel_id numbers them
+struct FwdAsk {
+    bool wino = false;           // the packed buffer holds the Winograd panels behind the direct pack (the _pk entry points, wino_layout)
+    bool hasWorkspace = false;   // the caller passes the workspace of diqt_conv3d_fwd_workspace_bytes*: the launch may split K
+    bool hasStats = false;       // the caller wants the per-tile column sums of the output; the route grants FwdRoute::statsRows rows, and an
+                                 // ask that is granted none is routed as the same ask without them
+    int subF = 0;                // diqt_conv3d_fwd_neighbours: sub-volumes per axis (0: a plain batch)
+    int gnAct = 0;               // diqt_conv3d_fwd_gn: the activation of the GroupNorm-apply prologue (0: none)
+    bool gnbwd = false;          // diqt_conv3d_fwd_gnbwd: the GroupNorm-backward epilogue (statsRows: the rows of its partial sums)
+    bool xAligned16 = true;      // x is 16-byte aligned (the queries assume it)
+};
+struct FwdRoute {
+    int kernel, rc;              // FWD_UNSUPPORTED: the launch returns rc, with `why` as the message (empty: make_geom has set it)
+    char why[192];
+    bool geom;                   // make_geom took the shape: g is filled in
+    int ksplit, statsRows;       // split-K shares (> 1: slabs in the workspace, then conv_fwd_reduce_kernel); [B][statsRows][2][Cout] statistics
+    size_t wsBytes;              // workspace this launch uses
+    ConvGeom g;                  // FWD_GENERIC / _SMALLCIN / _1X1 (for _1X1 the choice of pw64_launch depends on pointers: a launch-time detail)
+    bool vec4, buf;              // Cin % 4 == 0 and x aligned; ... and both tensors < 1 GiB: the 32-bit buffer descriptors
+    size_t lds;
+    unsigned nwg;
+    int cinp, nCh;               // FWD_SMALLCIN: padded input channels, 32-wide chunks of taps x channels
+    ConvGeom g8; size_t lds8; unsigned grid8;       // FWD_8WAVE
+    F9Geom g9; size_t l9; unsigned gr9;             // FWD_F9
+};
+
+static void convf_route(FwdRoute& r, int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw, int epd,
+                        int eph, int epw, const FwdAsk& a) {
+    r.kernel = FWD_UNSUPPORTED; r.why[0] = 0; r.ksplit = 1; r.statsRows = 0; r.wsBytes = 0; r.vec4 = r.buf = false;
+    ConvGeom& g = r.g;
+    r.rc = make_geom(g, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw);
+    r.geom = r.rc == DIQT_OK;
+    if (!r.geom) return;
+    r.rc = DIQT_E_UNSUPPORTED;
+    g.subF = a.subF;
+    const int T = kd * kh * kw;
+    const bool f9only = a.gnAct != 0 || a.gnbwd;       // launches only conv_fwd9_kernel has instantiations for
+    // The GroupNorm-backward epilogue is opt-in (DIQT_GNBWD_FUSE=1 or diqt_set_gnbwd_fuse(1)): it saves the GroupNorm backward's reduction
+    // pass (35 us and 134 MB per GroupNorm at the 32^3 level) but costs the launch as much: the activation derivative per output element
+    // (exp + two reciprocals at quarter rate) is ~8.6k instructions per tile on a kernel with one wave per SIMD and nothing to overlap
+    // them with.  42.1-42.3 ms per training micro-step either way, A/B on one box.
+    if (a.gnbwd && !diqt_get_gnbwd_fuse()) { snprintf(r.why, sizeof(r.why), "conv3d_fwd_gnbwd: the fusion is switched off (diqt_set_gnbwd_fuse)"); return; }
+    const char* const f9why = a.gnbwd ? "conv3d_fwd_gnbwd: shape not taken by conv_fwd9_kernel un-split (diqt_conv3d_fwd_gnbwd_blocks == 0)"
+                                      : "conv3d_fwd_gn: shape / activation not taken (diqt_conv3d_fwd_gn_supported == 0), or a split-K launch "
+                                        "without the workspace of diqt_conv3d_fwd_workspace_bytes";
+    const int HV = g.HD * g.HH * g.HWd;
+    r.nwg = (unsigned)((long long)g.B * g.tilesD * g.tilesH * g.tilesW * g.nNt);
+    r.cinp = smallcin_pad(Cin, T);
+    if (r.cinp) {
+        if (f9only) { snprintf(r.why, sizeof(r.why), "%s", f9why); return; }
+        r.nCh = cdiv(T * r.cinp, CK);
+        r.lds = ((size_t)((HV * r.cinp + 3) & ~3) + (size_t)MTILE * LDSROW + (size_t)NT * LDSROW) * sizeof(float) + (MTILE + CK) * sizeof(int);
+        if (r.lds > 80 * 1024) { snprintf(r.why, sizeof(r.why), "conv3d_fwd: small-Cin halo needs %zu B of LDS", r.lds); return; }
+        r.kernel = FWD_SMALLCIN;
+        return;
     }
-    const F9GnParams hp{mean, rstd, gamma, beta, scale, shift, G, cond_stride, act, 0};
-    F9GnParams* dp = ring + (slot++ & 255u);
-    hipError_t e = hipMemcpyAsync(dp, &hp, sizeof(hp), hipMemcpyHostToDevice, (hipStream_t)stream);
-    DIQT_REQUIRE(e == hipSuccess, DIQT_E_LAUNCH, "conv3d_fwd_gnbwd: hipMemcpyAsync: %s", hipGetErrorString(e));
-    g9.gnp = dp;
-    return fwd9_launch(x, packed, nullptr, nullptr, y, g9, l9, gr9, stream);
+    r.lds = ((size_t)HV * (LDSROW + 1) + 2 * NT * LDSROW) * sizeof(float) + MTILE * sizeof(int);
+    if (r.lds > 160 * 1024) { snprintf(r.why, sizeof(r.why), "conv3d_fwd: halo tile needs %zu B of LDS", r.lds); return; }
+    const unsigned long long xb = (unsigned long long)g.B * g.D * g.H * g.W * g.Cin * 4ull;
+    const unsigned long long yb = (unsigned long long)g.B * g.Do * g.Ho * g.Wo * g.Cout * 4ull;
+    r.vec4 = Cin % 4 == 0 && a.xAligned16;
+    r.buf = r.vec4 && xb < (1ull << 30) && yb < (1ull << 30);
+    if (r.buf) { g.xBytes = (unsigned)xb; g.yBytes = (unsigned)yb; }
+    const size_t slab = (size_t)g.B * g.Do * g.Ho * g.Wo * g.Cout * sizeof(float);      // one split-K share of the output
+    const int ksGeneric = fwd_ksplit(g);
+    // per-tile output statistics come from the buffer-path kernels, of a shape conv_fwd_kernel would not split, whose tiles stay inside
+    // a batch entry (the flattened 1x1x1 tiles cross them)
+    const bool stats = a.hasStats && r.buf && T != 1 && ksGeneric == 1;
+    if (r.buf && a.subF == 0) {
+        // conv_fwd9_kernel first: whole rounds of 512- / 256-voxel tiles, or (small volumes) split-K slabs in the caller's workspace.
+        // Split launches write no statistics: a plain ask that is granted them plans un-split and goes on to the kernels below, the
+        // GroupNorm-apply ask keeps its split and is granted none.  (conv_fwd9_kernel has no neighbour addressing.)
+        const bool maySplit = a.hasWorkspace && !a.gnbwd && (a.gnAct != 0 || !stats);
+        if (fwd9_plan(r.g9, r.l9, r.gr9, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, diqt_conv_packed_elems(Cout, Cin, kd, kh, kw),
+                      maySplit, a.wino && !a.gnbwd)) {
+            bool take = true;
+            if (a.gnbwd) take = !(kd == 3 && kh == 1 && kw == 1);                      // (3,1,1): no such instantiation
+            if (a.gnAct) {
+                // Every 64-channel output block of a tile rewrites its own copy of the halo, so the rewrite grows with Cout / 64 while the
+                // pass it replaces does not.  Measured on MI355X (tools/conv_bench.py gn, us saved per launch): 3x3x3 64->64 @ 8x32^3 +7,
+                // 128->64 +12, 128->128 @ 8x16^3 +2, 192->128 +3, split-K 256->256 @ 8x8^3 +4 (the saved launch is latency-bound there), but
+                // 256->128 @ 8x16^3 -6, 256->256 @ 32^3 -23, 512->512 @ 16^3 -6; (1,3,3): 64->64 @ 32x32 frames +19, 128->128 +10,
+                // 256->256 @ 8x8 +5.
+                const int nNt = r.g9.nNt;
+                take = fwd9_gna_available(r.g9.variant, a.gnAct) &&
+                       (kd == 1 ? nNt <= 4 : (nNt == 1 || (nNt == 2 && Cin <= 192) || r.g9.ksplit > 1));
+            }
+            if (take) {
+                r.kernel = FWD_F9;
+                r.ksplit = r.g9.ksplit;
+                r.wsBytes = r.ksplit > 1 ? r.ksplit * slab : 0;
+                if (a.gnbwd || (stats && r.ksplit == 1)) r.statsRows = r.g9.tilesD * r.g9.tilesH * r.g9.tilesW;     // one row per 512- / 256-voxel tile
+                return;
+            }
+        }
+    }
+    if (f9only) { snprintf(r.why, sizeof(r.why), "%s", f9why); return; }
+    if (a.hasWorkspace && ksGeneric > 1) {
+        r.kernel = FWD_GENERIC;
+        r.ksplit = ksGeneric;
+        r.wsBytes = ksGeneric * slab;
+        g.chunksPerSplit = cdiv(g.nChunks, ksGeneric);
+        g.slabStride = slab / sizeof(float);
+        return;
+    }
+    if (r.buf && fwd8_plan(g, r.g8, r.lds8)) {
+        r.kernel = FWD_8WAVE;
+        const unsigned nwg8 = (unsigned)((long long)r.g8.B * r.g8.tilesD * r.g8.tilesH * r.g8.tilesW * r.g8.nNt);
+        // persistent tile walk: one workgroup per CU runs all its tiles (needs a 64-channel block that stays with the workgroup)
+        r.grid8 = (nwg8 > 256u && 256 % r.g8.nNt == 0) ? 256u : nwg8;
+        if (stats) r.statsRows = r.g8.tilesD * r.g8.tilesH * r.g8.tilesW;               // one row per 256-voxel tile
+        return;
+    }
+    if (r.buf && T == 1 && g.B == 1 && g.D == 1 && g.H == 1 && g.Wo == g.W && g.TW == MTILE) {     // the flattened-rows geometry of make_geom
+        r.kernel = FWD_1X1;
+        return;
+    }
+    r.kernel = FWD_GENERIC;
+    if (stats) r.statsRows = g.tilesD * g.tilesH * g.tilesW;
 }
 
-static int conv3d_fwd_one(const float* x, const float* packed, const float* bias, const float* residual,
-                          float* y, void* workspace, size_t workspace_bytes, int B, int D, int H, int W, int Cin, int Cout,
-                          int kd, int kh, int kw, int pd, int ph, int pw, int epd, int eph, int epw, void* stream, float* stats,
-                          int subF = 0, bool wino = false);
-
-// Block.forward on the sampling path (GroupNorm -> (scale + 1) x + shift -> Mish / SiLU -> conv; imagen_pytorch3D.py:546-566,
-// imagen_video.py:680-697) as ONE launch: x is the RAW GroupNorm input and conv_fwd9_kernel's GroupNorm-apply instantiation rewrites
-// every halo piece in the LDS as act(A x + Bc) right after its DMA landed -- the elementwise pass over the activation (a read and a
-// write of the whole tensor per conv) is gone.  coef[2][B][Cin] = (A, Bc) from diqt_gn_coef_from_partials / diqt_gn_coef.
-// diqt_conv3d_fwd_gn_supported: 1 when conv_fwd9_kernel takes the launch (given the workspace diqt_conv3d_fwd_workspace_bytes asks
-// for) and has the instantiation for this filter and activation; otherwise run diqt_gn_act_fwd + diqt_conv3d_fwd_ex.
-static int fwd_gn_supported(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw, int epd, int eph,
-                            int epw, int act, bool wino) {
-    F9Geom g9;
-    size_t l9;
-    unsigned gr9;
-    if (Cin % 4 != 0 || smallcin_pad(Cin, kd * kh * kw)) return 0;
-    if (!fwd9_plan(g9, l9, gr9, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, diqt_conv_packed_elems(Cout, Cin, kd, kh, kw), true, wino))
-        return 0;
-    if (!fwd9_gna_available(g9.variant, act)) return 0;
-    // Every 64-channel output block of a tile rewrites its own copy of the halo, so the rewrite grows with Cout / 64 while the pass it
-    // replaces does not.  Measured on MI355X (tools/conv_bench.py gn, us saved per launch): 3x3x3 64->64 @ 8x32^3 +7, 128->64 +12,
-    // 128->128 @ 8x16^3 +2, 192->128 +3, split-K 256->256 @ 8x8^3 +4 (the saved launch is latency-bound there), but 256->128 @ 8x16^3
-    // -6, 256->256 @ 32^3 -23, 512->512 @ 16^3 -6; (1,3,3): 64->64 @ 32x32 frames +19, 128->128 +10, 256->256 @ 8x8 +5.
-    if (kd == 1) return g9.nNt <= 4 ? 1 : 0;
-    return (g9.nNt == 1 || (g9.nNt == 2 && Cin <= 192) || g9.ksplit > 1) ? 1 : 0;
-}
-extern "C" int diqt_conv3d_fwd_gn_supported(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw,
-                                            int epd, int eph, int epw, int act) {
-    return fwd_gn_supported(B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, act, false);
-}
-// ... for diqt_conv3d_fwd_gn_pk with a packed buffer of packed_elems floats (see diqt_conv3d_fwd_pk)
-extern "C" int diqt_conv3d_fwd_gn_supported_pk(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw,
-                                               int epd, int eph, int epw, int act, size_t packed_elems) {
-    return fwd_gn_supported(B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, act,
-                            wino_layout(Cout, Cin, kd, kh, kw, packed_elems) == 1);
-}
-static int fwd_gn(const float* x, const float* packed, const float* bias, const float* residual, float* y, float* stats, void* workspace,
-                  size_t workspace_bytes, const float* coef, int act, int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw,
-                  int pd, int ph, int pw, int epd, int eph, int epw, void* stream, bool wino) {
-    DIQT_REQUIRE(x && packed && y && coef, DIQT_E_ALIGN, "conv3d_fwd_gn: null pointer");
-    DIQT_REQUIRE(aligned16(x) && aligned16(packed) && aligned16(coef), DIQT_E_ALIGN, "conv3d_fwd_gn: x, packed weights and coef must be 16-byte aligned");
-    DIQT_REQUIRE(fwd_gn_supported(B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, act, wino), DIQT_E_UNSUPPORTED,
-                 "conv3d_fwd_gn: shape / activation not taken (diqt_conv3d_fwd_gn_supported == 0)");
-    F9Geom g9;
-    size_t l9;
-    unsigned gr9;
-    const bool maySplit = workspace && aligned16(workspace);
-    const bool ok = fwd9_plan(g9, l9, gr9, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw,
-                              diqt_conv_packed_elems(Cout, Cin, kd, kh, kw), maySplit, wino);
-    DIQT_REQUIRE(ok && fwd9_gna_available(g9.variant, act), DIQT_E_WORKSPACE,
-                 "conv3d_fwd_gn: this launch needs the split-K workspace of diqt_conv3d_fwd_workspace_bytes");
-    g9.gcoef = coef;
-    g9.gnaAct = act;
-    if (g9.ksplit == 1) {
-        DIQT_REQUIRE(!stats || fwd_stats_blocks_impl(B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, false, wino) > 0,
-                     DIQT_E_UNSUPPORTED, "conv3d_fwd_gn: this shape does not produce output statistics");
-        g9.stats = stats;
-        return fwd9_launch(x, packed, bias, residual, y, g9, l9, gr9, stream);
+// Launches what the route says.  The caller has set what its entry point adds to r.g9 (GroupNorm-apply coefficients, GroupNorm-backward
+// epilogue); `stats` is the statistics / partial-sums buffer of the ask (the route granted r.statsRows rows).
+static int convf_launch(FwdRoute& r, const float* x, const float* packed, const float* bias, const float* residual, float* y, float* stats,
+                        void* workspace, size_t workspace_bytes, void* stream) {
+    if (r.kernel == FWD_UNSUPPORTED) {
+        if (r.why[0]) set_error("%s", r.why);
+        return r.rc;
     }
-    const size_t n = (size_t)B * g9.Do * g9.Ho * g9.Wo * Cout;
-    DIQT_REQUIRE(!stats && workspace_bytes >= (size_t)g9.ksplit * n * sizeof(float), DIQT_E_WORKSPACE,
-                 "conv3d_fwd_gn: split-K launch: no statistics, workspace of %zu bytes", (size_t)g9.ksplit * n * sizeof(float));
+    DIQT_REQUIRE(!stats || r.statsRows > 0, DIQT_E_UNSUPPORTED,
+                 "conv3d_fwd: this launch does not produce output statistics (its diqt_conv3d_fwd*_stats_blocks* query answers 0)");
+    DIQT_REQUIRE(r.ksplit == 1 || (workspace && aligned16(workspace) && workspace_bytes >= r.wsBytes), DIQT_E_WORKSPACE,
+                 "conv3d_fwd: split-K needs a 16-byte aligned workspace of %zu bytes, got %zu", r.wsBytes, workspace_bytes);
+    hipStream_t s = (hipStream_t)stream;
+    const bool split = r.ksplit > 1;
     float* slabs = static_cast<float*>(workspace);
-    g9.stats = nullptr;
-    int rc = fwd9_launch(x, packed, nullptr, nullptr, slabs, g9, l9, gr9, stream);
+    const size_t n = (size_t)r.g.B * r.g.Do * r.g.Ho * r.g.Wo * r.g.Cout;
+    int rc = DIQT_OK;
+    const char* reduceTag = "conv3d_fwd(split-K reduce)";
+    switch (r.kernel) {
+    case FWD_SMALLCIN: {
+        void (*ks)(const float*, const float*, const float*, const float*, float*, ConvGeom, int) =
+            r.cinp == 1 ? conv_fwd_smallcin_kernel<1> : (r.cinp == 2 ? conv_fwd_smallcin_kernel<2> : conv_fwd_smallcin_kernel<4>);
+        if (r.lds > 64 * 1024) {
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ks), hipFuncAttributeMaxDynamicSharedMemorySize, (int)r.lds);
+            DIQT_REQUIRE(e == hipSuccess, DIQT_E_LAUNCH, "conv3d_fwd: hipFuncSetAttribute: %s", hipGetErrorString(e));
+        }
+        hipLaunchKernelGGL(ks, dim3(r.nwg), dim3(256), r.lds, s, x, packed, bias, residual, y, r.g, r.nCh);
+        return check_launch("conv3d_fwd(small Cin)");
+    }
+    case FWD_F9:
+        r.g9.stats = stats;
+        if (!split) return fwd9_launch(x, packed, bias, residual, y, r.g9, r.l9, r.gr9, stream);
+        rc = fwd9_launch(x, packed, nullptr, nullptr, slabs, r.g9, r.l9, r.gr9, stream);
+        reduceTag = r.g9.gcoef ? "conv3d_fwd_gn(split-K reduce)" : "conv3d_fwd(v9 split-K reduce)";
+        break;
+    case FWD_8WAVE:
+        r.g8.stats = stats;
+        if (r.lds8 > 64 * 1024) {
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_fwd8_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)r.lds8);
+            DIQT_REQUIRE(e == hipSuccess, DIQT_E_LAUNCH, "conv3d_fwd: hipFuncSetAttribute: %s", hipGetErrorString(e));
+        }
+        hipLaunchKernelGGL(conv_fwd8_kernel, dim3(r.grid8), dim3(512), r.lds8, s, x, packed, bias, residual, y, r.g8);
+        return check_launch("conv3d_fwd(8 waves)");
+    case FWD_1X1:
+        if (pw64_ok((long long)r.g.W, r.g.Cin, r.g.Cout, x, packed, y))      // few input channels, many output channels: x resident, persistent row walk
+            return pw64_launch(x, packed, bias, residual, y, (long long)r.g.W, r.g.Cout, r.g.CoutPad, stream);
+        hipLaunchKernelGGL(conv1x1_fwd_kernel, dim3(r.nwg), dim3(256), 0, s, x, packed, bias, residual, y, r.g);
+        return check_launch("conv3d_fwd(1x1x1)");
+    default: {
+        auto kern = r.vec4 ? (r.buf ? conv_fwd_kernel<true, true> : conv_fwd_kernel<true, false>) : conv_fwd_kernel<false, false>;
+        if (r.lds > 64 * 1024) {
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)r.lds);
+            DIQT_REQUIRE(e == hipSuccess, DIQT_E_LAUNCH, "conv3d_fwd: hipFuncSetAttribute: %s", hipGetErrorString(e));
+        }
+        r.g.stats = stats;
+        if (!split) {
+            hipLaunchKernelGGL(kern, dim3(r.nwg), dim3(256), r.lds, s, x, packed, bias, residual, y, r.g);
+            return check_launch("conv3d_fwd");
+        }
+        hipLaunchKernelGGL(kern, dim3(r.nwg, r.ksplit), dim3(256), r.lds, s, x, packed, nullptr, nullptr, slabs, r.g);
+        rc = check_launch("conv3d_fwd(split-K)");
+    }
+    }
     if (rc) return rc;
-    hipLaunchKernelGGL(conv_fwd_reduce_kernel, dim3(grid_for(n, 256, 2048)), dim3(256), 0, (hipStream_t)stream, slabs, bias, residual, y, n,
-                       Cout, g9.ksplit);
-    return check_launch("conv3d_fwd_gn(split-K reduce)");
-}
-extern "C" int diqt_conv3d_fwd_gn(const float* x, const float* packed, const float* bias, const float* residual, float* y, float* stats,
-                                  void* workspace, size_t workspace_bytes, const float* coef, int act, int B, int D, int H, int W, int Cin,
-                                  int Cout, int kd, int kh, int kw, int pd, int ph, int pw, int epd, int eph, int epw, void* stream) {
-    return fwd_gn(x, packed, bias, residual, y, stats, workspace, workspace_bytes, coef, act, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw,
-                  epd, eph, epw, stream, false);
-}
-// diqt_conv3d_fwd_gn with the length of the packed buffer (Winograd panels of pack mode 2: see diqt_conv3d_fwd_pk)
-extern "C" int diqt_conv3d_fwd_gn_pk(const float* x, const float* packed, size_t packed_elems, const float* bias, const float* residual,
-                                     float* y, float* stats, void* workspace, size_t workspace_bytes, const float* coef, int act, int B, int D,
-                                     int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw, int epd, int eph,
-                                     int epw, void* stream) {
-    const int lay = wino_layout(Cout, Cin, kd, kh, kw, packed_elems);
-    DIQT_REQUIRE(lay >= 0, DIQT_E_SHAPE, "conv3d_fwd_gn_pk: packed buffer of %zu floats, the direct pack alone needs %zu", packed_elems,
-                 diqt_conv_packed_elems(Cout, Cin, kd, kh, kw));
-    return fwd_gn(x, packed, bias, residual, y, stats, workspace, workspace_bytes, coef, act, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw,
-                  epd, eph, epw, stream, lay == 1);
+    hipLaunchKernelGGL(conv_fwd_reduce_kernel, dim3(grid_for(n, 256, 2048)), dim3(256), 0, s, slabs, bias, residual, y, n, r.g.Cout, r.ksplit);
+    return check_launch(reduceTag);
 }
 
-// 'same' convolution (odd cubic filter k, padding k / 2) over the f^3 sub-volume batch x[f^3][A][A][A][Cin] of ONE merged volume, the
-// halo of a sub-volume read in place from its neighbours (conv_src_voxel): what the reference computes as
-// boundary_pad(x) -> unpadded Conv3d (imagen_pytorch3D.py:37-46, 550-566 with boundary=True).  Same kernels, same bits per output
-// element as running the padded copies; workspace / stats as diqt_conv3d_fwd_ex for (B = f^3, D = H = W = A, pad = k / 2).
-extern "C" int diqt_conv3d_fwd_neighbours(const float* x, const float* packed, const float* bias, const float* residual, float* y,
-                                          float* stats, void* workspace, size_t workspace_bytes, int f, int A, int Cin, int Cout,
-                                          int k, void* stream) {
-    DIQT_REQUIRE(f >= 1 && A >= 1 && k >= 1 && (k & 1) && k / 2 <= A, DIQT_E_SHAPE, "conv3d_fwd_neighbours: bad shape (f %d, A %d, k %d)", f, A, k);
-    const int B = f * f * f, p = k / 2;
-    DIQT_REQUIRE((unsigned long long)B * A * A * A * (unsigned long long)(Cin > Cout ? Cin : Cout) * 4ull < (1ull << 30), DIQT_E_UNSUPPORTED,
-                 "conv3d_fwd_neighbours: the sub-volume batch must stay below 1 GiB (it cannot be cut into independent launches)");
-    DIQT_REQUIRE(!stats || diqt_conv3d_fwd_neighbours_stats_blocks(f, A, Cin, Cout, k) > 0, DIQT_E_UNSUPPORTED,
-                 "conv3d_fwd_neighbours: this shape does not produce output statistics (diqt_conv3d_fwd_neighbours_stats_blocks == 0)");
-    return conv3d_fwd_one(x, packed, bias, residual, y, workspace, workspace_bytes, B, A, A, A, Cin, Cout, k, k, k, p, p, p, 0, 0, 0, stream,
-                          stats, f);
+// ---- the shape queries: the route of a fixed ask ----
+static FwdAsk query_ask(int Cout, int Cin, int kd, int kh, int kw, size_t packed_elems, bool hasStats) {
+    FwdAsk a;
+    a.wino = wino_layout(Cout, Cin, kd, kh, kw, packed_elems) == 1;
+    a.hasWorkspace = true;
+    a.hasStats = hasStats;
+    return a;
 }
 
-extern "C" int diqt_conv3d_fwd_ws(const float* x, const float* packed, const float* bias, const float* residual,
-                                  float* y, void* workspace, size_t workspace_bytes, int B, int D, int H, int W, int Cin,
-                                  int Cout, int kd, int kh, int kw, int pd, int ph, int pw, int epd, int eph, int epw,
-                                  void* stream) {
-    return conv3d_fwd_impl(x, packed, bias, residual, y, workspace, workspace_bytes, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph,
-                           pw, epd, eph, epw, stream, nullptr);
+// Workspace of the forward launches of a shape: the larger of conv_fwd9_kernel's and conv_fwd_kernel's split-K slabs, so that one
+// buffer serves every ask (diqt_conv3d_fwd_neighbours and a launch that is granted statistics do not take the kernel a plain one takes)
+extern "C" size_t diqt_conv3d_fwd_workspace_bytes_pk(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw,
+                                                     int epd, int eph, int epw, size_t packed_elems) {
+    FwdRoute r;
+    convf_route(r, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, query_ask(Cout, Cin, kd, kh, kw, packed_elems, false));
+    if (!r.geom) return 0;
+    const int ks = fwd_ksplit(r.g);
+    const size_t generic = ks > 1 ? (size_t)ks * r.g.B * r.g.Do * r.g.Ho * r.g.Wo * r.g.Cout * sizeof(float) : 0;
+    return generic > r.wsBytes ? generic : r.wsBytes;
+}
+extern "C" size_t diqt_conv3d_fwd_workspace_bytes(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw,
+                                                  int epd, int eph, int epw) {
+    return diqt_conv3d_fwd_workspace_bytes_pk(B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, 0);
 }
 
+// Rows of per-tile output statistics a launch that passes `stats` writes per batch entry (the `nblk` of the [B][nblk][2][Cout] layout),
+// 0: this shape takes a path without statistics and `stats` must be NULL
+extern "C" int diqt_conv3d_fwd_stats_blocks_pk(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw,
+                                               int epd, int eph, int epw, size_t packed_elems) {
+    FwdRoute r;
+    convf_route(r, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, query_ask(Cout, Cin, kd, kh, kw, packed_elems, true));
+    return r.statsRows;
+}
+extern "C" int diqt_conv3d_fwd_stats_blocks(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw, int epd,
+                                            int eph, int epw) {
+    return diqt_conv3d_fwd_stats_blocks_pk(B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, 0);
+}
+// the same for diqt_conv3d_fwd_neighbours
+extern "C" int diqt_conv3d_fwd_neighbours_stats_blocks(int f, int A, int Cin, int Cout, int k) {
+    if (f < 1 || A < 1 || k < 1 || !(k & 1)) return 0;
+    FwdAsk a = query_ask(Cout, Cin, k, k, k, 0, true);
+    a.subF = f;
+    FwdRoute r;
+    convf_route(r, f * f * f, A, A, A, Cin, Cout, k, k, k, k / 2, k / 2, k / 2, 0, 0, 0, a);
+    return r.statsRows;
+}
+
+// which kernel diqt_conv3d_fwd* dispatches this shape to (for profilers / bench.py, so that per-kernel numbers carry the names
+// rocprofv3 reports): 0 conv_fwd_kernel, 1 conv_fwd_smallcin_kernel, 2 conv1x1_fwd_kernel, 3 conv_fwd8_kernel, 4 conv_fwd9_kernel, -1 bad
+// shape -- the route of a caller that passes the workspace diqt_conv3d_fwd_workspace_bytes asks for, no statistics, the direct pack
+extern "C" int diqt_conv3d_fwd_kernel_id(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw, int epd, int eph, int epw) {
+    FwdRoute r;
+    convf_route(r, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, query_ask(Cout, Cin, kd, kh, kw, 0, false));
+    return r.kernel;
+}
+
+// conv_fwd9_kernel's variant for a launch diqt_conv3d_fwd_kernel_id routes to it, given a packed buffer of packed_elems floats
+// (F9Geom::variant; 7: Winograd F(2,3), only with the panels of pack modes 2 / 3 and diqt_conv3d_fwd_pk), -1 otherwise
+extern "C" int diqt_conv3d_fwd9_variant(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw, int epd,
+                                        int eph, int epw, size_t packed_elems) {
+    if (diqt_conv3d_fwd_kernel_id(B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw) != FWD_F9) return -1;
+    FwdRoute r;
+    convf_route(r, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, query_ask(Cout, Cin, kd, kh, kw, packed_elems, false));
+    return r.kernel == FWD_F9 ? r.g9.variant : -1;
+}
+
+// Diagnostic: the route itself, for the ask of a diqt_conv3d_fwd_pk (gn_act = 0, sub_f = 0), diqt_conv3d_fwd_neighbours (sub_f > 0) or
+// diqt_conv3d_fwd_gn_pk (gn_act) call with a packed buffer of packed_elems floats, with / without a workspace and a statistics buffer.
+// field 0: kernel id (as diqt_conv3d_fwd_kernel_id), 1: split-K shares, 2: conv_fwd9_kernel's variant or -1, 3: statistics rows granted,
+// 4: workspace bytes the launch uses; another field: -1
+extern "C" int diqt_conv3d_fwd_route(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw, int epd, int eph,
+                                     int epw, size_t packed_elems, int has_workspace, int has_stats, int sub_f, int gn_act, int field) {
+    FwdAsk a = query_ask(Cout, Cin, kd, kh, kw, packed_elems, has_stats != 0);
+    a.hasWorkspace = has_workspace != 0;
+    a.subF = sub_f;
+    a.gnAct = gn_act;
+    FwdRoute r;
+    convf_route(r, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, a);
+    switch (field) {
+        case 0: return r.kernel;
+        case 1: return r.ksplit;
+        case 2: return r.kernel == FWD_F9 ? r.g9.variant : -1;
+        case 3: return r.statsRows;
+        case 4: return r.wsBytes > 0x7fffffffu ? 0x7fffffff : (int)r.wsBytes;
+    }
+    return -1;
+}
+
+// which conv_fwd9_kernel variant the process's last launch of it ran (F9Geom::variant, 7: Winograd), -1 if none since the last
+// call: a test / profiler observable of the launch itself, not of a plan
+extern "C" int diqt_get_last_conv_fwd9_variant() { return fwd9_take_last_variant(); }
+
+// One launch (tensors the 32-bit buffer descriptors can address, or the pointer-arithmetic kernel): route, then launch
+static int conv3d_fwd_one(const float* x, const float* packed, const float* bias, const float* residual, float* y, void* workspace,
+                          size_t workspace_bytes, int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw,
+                          int epd, int eph, int epw, void* stream, float* stats, int subF = 0, bool wino = false) {
+    DIQT_REQUIRE(x && packed && y, DIQT_E_ALIGN, "conv3d_fwd: null pointer");
+    DIQT_REQUIRE(aligned16(packed), DIQT_E_ALIGN, "conv3d_fwd: packed weights must be 16-byte aligned");
+    FwdAsk a;
+    a.wino = wino; a.hasWorkspace = workspace != nullptr; a.hasStats = stats != nullptr; a.subF = subF; a.xAligned16 = aligned16(x);
+    FwdRoute r;
+    convf_route(r, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, a);
+    return convf_launch(r, x, packed, bias, residual, y, stats, workspace, workspace_bytes, stream);
+}
 
 // The fast kernels address x and y through 32-bit buffer descriptors (tensors < 1 GiB).  Larger launches -- big patch batches are the
 // natural way to use 288 GB of HBM -- are cut into independent sub-launches below that size: row ranges for the flattened 1x1x1 /
@@ -2017,7 +1996,7 @@ extern "C" int diqt_conv3d_fwd_ws(const float* x, const float* packed, const flo
 static int conv3d_fwd_impl(const float* x, const float* packed, const float* bias, const float* residual,
                            float* y, void* workspace, size_t workspace_bytes, int B, int D, int H, int W, int Cin, int Cout,
                            int kd, int kh, int kw, int pd, int ph, int pw, int epd, int eph, int epw, void* stream, float* stats,
-                           bool wino) {
+                           bool wino = false) {
     const long long Do = (long long)D + 2 * pd + epd - kd + 1, Ho = (long long)H + 2 * ph + eph - kh + 1, Wo = (long long)W + 2 * pw + epw - kw + 1;
     const unsigned long long lim = (1ull << 30) - 1;
     if (B > 0 && D > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && Do > 0 && Ho > 0 && Wo > 0) {
@@ -2054,114 +2033,147 @@ static int conv3d_fwd_impl(const float* x, const float* packed, const float* bia
                           epw, stream, stats, 0, wino);
 }
 
-static int conv3d_fwd_one(const float* x, const float* packed, const float* bias, const float* residual,
-                          float* y, void* workspace, size_t workspace_bytes, int B, int D, int H, int W, int Cin, int Cout,
-                          int kd, int kh, int kw, int pd, int ph, int pw, int epd, int eph, int epw, void* stream, float* stats,
-                          int subF, bool wino) {
-    DIQT_REQUIRE(x && packed && y, DIQT_E_ALIGN, "conv3d_fwd: null pointer");
-    ConvGeom g;
-    int rc = make_geom(g, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw);
-    if (rc) return rc;
-    g.subF = subF;
-    g.chunksPerSplit = g.nChunks;
-    g.slabStride = 0;
-    DIQT_REQUIRE(aligned16(packed), DIQT_E_ALIGN, "conv3d_fwd: packed weights must be 16-byte aligned");
-    const bool vec4 = (Cin % 4 == 0) && aligned16(x);
-    const int HV = g.HD * g.HH * g.HWd;
-    const unsigned nwg = (unsigned)((long long)g.B * g.tilesD * g.tilesH * g.tilesW * g.nNt);
-    if (const int CINP = smallcin_pad(Cin, kd * kh * kw)) {
-        const int nCh = cdiv(kd * kh * kw * CINP, CK);
-        const size_t slds = ((size_t)((HV * CINP + 3) & ~3) + (size_t)MTILE * LDSROW + (size_t)NT * LDSROW) * sizeof(float) +
-                            (MTILE + CK) * sizeof(int);
-        if (slds <= 80 * 1024) {
-            void (*ks)(const float*, const float*, const float*, const float*, float*, ConvGeom, int) =
-                CINP == 1 ? conv_fwd_smallcin_kernel<1> : (CINP == 2 ? conv_fwd_smallcin_kernel<2> : conv_fwd_smallcin_kernel<4>);
-            if (slds > 64 * 1024) {
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ks), hipFuncAttributeMaxDynamicSharedMemorySize, (int)slds);
-                DIQT_REQUIRE(e == hipSuccess, DIQT_E_LAUNCH, "conv3d_fwd: hipFuncSetAttribute: %s", hipGetErrorString(e));
-            }
-            hipLaunchKernelGGL(ks, dim3(nwg), dim3(256), slds, (hipStream_t)stream, x, packed, bias, residual, y, g, nCh);
-            return check_launch("conv3d_fwd(small Cin)");
+extern "C" int diqt_conv3d_fwd(const float* x, const float* packed, const float* bias, const float* residual,
+                               float* y, int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw,
+                               int pd, int ph, int pw, int epd, int eph, int epw, void* stream) {
+    return conv3d_fwd_impl(x, packed, bias, residual, y, nullptr, 0, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph,
+                           epw, stream, nullptr);
+}
+extern "C" int diqt_conv3d_fwd_ws(const float* x, const float* packed, const float* bias, const float* residual,
+                                  float* y, void* workspace, size_t workspace_bytes, int B, int D, int H, int W, int Cin,
+                                  int Cout, int kd, int kh, int kw, int pd, int ph, int pw, int epd, int eph, int epw,
+                                  void* stream) {
+    return conv3d_fwd_impl(x, packed, bias, residual, y, workspace, workspace_bytes, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph,
+                           pw, epd, eph, epw, stream, nullptr);
+}
+// ... that also emits the per-tile statistics of its output (a launch that is granted no rows refuses `stats`)
+extern "C" int diqt_conv3d_fwd_ex(const float* x, const float* packed, const float* bias, const float* residual, float* y,
+                                  float* stats, void* workspace, size_t workspace_bytes, int B, int D, int H, int W, int Cin,
+                                  int Cout, int kd, int kh, int kw, int pd, int ph, int pw, int epd, int eph, int epw, void* stream) {
+    return conv3d_fwd_impl(x, packed, bias, residual, y, workspace, workspace_bytes, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw,
+                           epd, eph, epw, stream, stats);
+}
+// diqt_conv3d_fwd_ex with the length of the packed buffer: a buffer that holds the Winograd panels behind the direct pack (pack modes
+// 2 / 3) lets the 3x3x3 launches with an even output width take conv_fwd9_kernel's Winograd tile; a shorter one than the direct pack
+// is refused.  Statistics rows and workspace: diqt_conv3d_fwd_stats_blocks_pk / _workspace_bytes_pk with the same length.
+extern "C" int diqt_conv3d_fwd_pk(const float* x, const float* packed, size_t packed_elems, const float* bias, const float* residual,
+                                  float* y, float* stats, void* workspace, size_t workspace_bytes, int B, int D, int H, int W, int Cin,
+                                  int Cout, int kd, int kh, int kw, int pd, int ph, int pw, int epd, int eph, int epw, void* stream) {
+    const int lay = wino_layout(Cout, Cin, kd, kh, kw, packed_elems);
+    DIQT_REQUIRE(lay >= 0, DIQT_E_SHAPE, "conv3d_fwd_pk: packed buffer of %zu floats, the direct pack alone needs %zu", packed_elems,
+                 diqt_conv_packed_elems(Cout, Cin, kd, kh, kw));
+    return conv3d_fwd_impl(x, packed, bias, residual, y, workspace, workspace_bytes, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw,
+                           epd, eph, epw, stream, stats, lay == 1);
+}
+
+// 'same' convolution (odd cubic filter k, padding k / 2) over the f^3 sub-volume batch x[f^3][A][A][A][Cin] of ONE merged volume, the
+// halo of a sub-volume read in place from its neighbours (conv_src_voxel): what the reference computes as
+// boundary_pad(x) -> unpadded Conv3d (imagen_pytorch3D.py:37-46, 550-566 with boundary=True).  Same kernels, same bits per output
+// element as running the padded copies; workspace / stats as diqt_conv3d_fwd_ex for (B = f^3, D = H = W = A, pad = k / 2).
+extern "C" int diqt_conv3d_fwd_neighbours(const float* x, const float* packed, const float* bias, const float* residual, float* y,
+                                          float* stats, void* workspace, size_t workspace_bytes, int f, int A, int Cin, int Cout,
+                                          int k, void* stream) {
+    DIQT_REQUIRE(f >= 1 && A >= 1 && k >= 1 && (k & 1) && k / 2 <= A, DIQT_E_SHAPE, "conv3d_fwd_neighbours: bad shape (f %d, A %d, k %d)", f, A, k);
+    const int B = f * f * f, p = k / 2;
+    DIQT_REQUIRE((unsigned long long)B * A * A * A * (unsigned long long)(Cin > Cout ? Cin : Cout) * 4ull < (1ull << 30), DIQT_E_UNSUPPORTED,
+                 "conv3d_fwd_neighbours: the sub-volume batch must stay below 1 GiB (it cannot be cut into independent launches)");
+    return conv3d_fwd_one(x, packed, bias, residual, y, workspace, workspace_bytes, B, A, A, A, Cin, Cout, k, k, k, p, p, p, 0, 0, 0, stream,
+                          stats, f);
+}
+
+// The backward-data pass of a conv that sits behind a fused GroupNorm + scale/shift + Mish/SiLU (Block.forward: GN -> act -> conv,
+// imagen_pytorch3D.py:535-566 / imagen_video.py:671-697): y = conv(x = dY of the conv, flipped packed weights) is the gradient w.r.t.
+// the activated tensor, and the epilogue of conv_fwd9_kernel -- which holds that gradient in registers -- also reads the GroupNorm
+// input gn_x at the same voxels and writes the per-tile partial sums of the GroupNorm backward (sum dz, sum dz xhat per channel):
+// partials[B][nblk][2][Cout], nblk = diqt_conv3d_fwd_gnbwd_blocks(...) (0: this shape does not run on conv_fwd9_kernel un-split; use
+// diqt_conv3d_fwd + diqt_gn_act_bwd).  diqt_gn_act_bwd_from_partials finishes the GroupNorm backward without its reduction pass.
+extern "C" int diqt_conv3d_fwd_gnbwd_blocks(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw, int epd,
+                                            int eph, int epw) {
+    FwdAsk a;
+    a.gnbwd = true;             // the direct pack, no workspace: never split
+    FwdRoute r;
+    convf_route(r, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, a);
+    return r.statsRows;
+}
+extern "C" int diqt_conv3d_fwd_gnbwd(const float* x, const float* packed, float* y, float* partials, const float* gn_x, const float* mean,
+                                     const float* rstd, const float* gamma, const float* beta, const float* scale, const float* shift,
+                                     int cond_stride, int G, int act, int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd,
+                                     int ph, int pw, int epd, int eph, int epw, void* stream) {
+    DIQT_REQUIRE(x && packed && y && partials && gn_x && mean && rstd, DIQT_E_ALIGN, "conv3d_fwd_gnbwd: null pointer");
+    DIQT_REQUIRE(aligned16(x) && aligned16(packed), DIQT_E_ALIGN, "conv3d_fwd_gnbwd: x and packed weights must be 16-byte aligned");
+    DIQT_REQUIRE(G > 0 && Cout % G == 0 && (act == DIQT_ACT_MISH || act == DIQT_ACT_SILU), DIQT_E_UNSUPPORTED,
+                 "conv3d_fwd_gnbwd: Mish / SiLU, groups dividing the channels");
+    DIQT_REQUIRE((scale == nullptr) == (shift == nullptr) && (!scale || cond_stride >= Cout), DIQT_E_SHAPE, "conv3d_fwd_gnbwd: scale / shift");
+    FwdAsk a;
+    a.gnbwd = true;
+    FwdRoute r;
+    convf_route(r, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, a);
+    if (r.kernel == FWD_F9) {
+        F9Geom& g9 = r.g9;
+        g9.gx = gn_x; g9.gmean = mean; g9.grstd = rstd; g9.ggamma = gamma; g9.gbeta = beta; g9.gscale = scale; g9.gshift = shift;
+        g9.gG = G; g9.gcs = cond_stride; g9.gact = act;
+        // the epilogue's parameters go through a small device ring (stream-ordered copy: every launch gets its own slot, 256 launches
+        // deep), so the kernel carries ONE pointer for them through its main loop
+        static F9GnParams* ring = nullptr;
+        static unsigned slot = 0;
+        if (!ring) {
+            hipError_t e = hipMalloc(&ring, 256 * sizeof(F9GnParams));
+            DIQT_REQUIRE(e == hipSuccess, DIQT_E_LAUNCH, "conv3d_fwd_gnbwd: hipMalloc: %s", hipGetErrorString(e));
         }
-        DIQT_REQUIRE(false, DIQT_E_UNSUPPORTED, "conv3d_fwd: small-Cin halo needs %zu B of LDS", slds);
+        const F9GnParams hp{mean, rstd, gamma, beta, scale, shift, G, cond_stride, act, 0};
+        F9GnParams* dp = ring + (slot++ & 255u);
+        hipError_t e = hipMemcpyAsync(dp, &hp, sizeof(hp), hipMemcpyHostToDevice, (hipStream_t)stream);
+        DIQT_REQUIRE(e == hipSuccess, DIQT_E_LAUNCH, "conv3d_fwd_gnbwd: hipMemcpyAsync: %s", hipGetErrorString(e));
+        g9.gnp = dp;
     }
-    const size_t lds = ((size_t)HV * (LDSROW + 1) + 2 * NT * LDSROW) * sizeof(float) + MTILE * sizeof(int);
-    DIQT_REQUIRE(lds <= 160 * 1024, DIQT_E_UNSUPPORTED, "conv3d_fwd: halo tile needs %zu B of LDS", lds);
-    const unsigned long long xb = (unsigned long long)g.B * g.D * g.H * g.W * g.Cin * 4ull;
-    const unsigned long long yb = (unsigned long long)g.B * g.Do * g.Ho * g.Wo * g.Cout * 4ull;
-    const bool buf = vec4 && xb < (1ull << 30) && yb < (1ull << 30);
-    if (buf) { g.xBytes = (unsigned)xb; g.yBytes = (unsigned)yb; }
-    auto kern = vec4 ? (buf ? conv_fwd_kernel<true, true> : conv_fwd_kernel<true, false>) : conv_fwd_kernel<false, false>;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        DIQT_REQUIRE(e == hipSuccess, DIQT_E_LAUNCH, "conv3d_fwd: hipFuncSetAttribute: %s", hipGetErrorString(e));
-    }
-    if (buf && g.subF == 0) {
-        // conv_fwd9_kernel first: whole rounds of 512- / 256-voxel tiles, or (small volumes) split-K slabs in the caller's workspace
-        F9Geom g9;
-        size_t l9;
-        unsigned gr9;
-        const bool maySplit = workspace && aligned16(workspace);
-        if (fwd9_plan(g9, l9, gr9, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, diqt_conv_packed_elems(Cout, Cin, kd, kh, kw),
-                      maySplit, wino)) {
-            if (g9.ksplit == 1) {
-                g9.stats = stats;
-                return fwd9_launch(x, packed, bias, residual, y, g9, l9, gr9, stream);
-            }
-            const size_t n = (size_t)g.B * g.Do * g.Ho * g.Wo * g.Cout;
-            if (!stats && workspace_bytes >= (size_t)g9.ksplit * n * sizeof(float)) {
-                float* slabs = static_cast<float*>(workspace);
-                g9.stats = nullptr;
-                rc = fwd9_launch(x, packed, nullptr, nullptr, slabs, g9, l9, gr9, stream);
-                if (rc) return rc;
-                hipLaunchKernelGGL(conv_fwd_reduce_kernel, dim3(grid_for(n, 256, 2048)), dim3(256), 0, (hipStream_t)stream, slabs, bias,
-                                   residual, y, n, g.Cout, g9.ksplit);
-                return check_launch("conv3d_fwd(v9 split-K reduce)");
-            }
-        }
-    }
-    const int ks = workspace ? fwd_ksplit(g) : 1;
-    if (ks > 1) {
-        const size_t n = (size_t)g.B * g.Do * g.Ho * g.Wo * g.Cout;
-        DIQT_REQUIRE(workspace_bytes >= (size_t)ks * n * sizeof(float) && aligned16(workspace), DIQT_E_WORKSPACE,
-                     "conv3d_fwd: split-K workspace %zu < %zu", workspace_bytes, (size_t)ks * n * sizeof(float));
-        g.chunksPerSplit = cdiv(g.nChunks, ks);
-        g.slabStride = n;
-        float* slabs = static_cast<float*>(workspace);
-        hipLaunchKernelGGL(kern, dim3(nwg, ks), dim3(256), lds, (hipStream_t)stream, x, packed, nullptr, nullptr, slabs, g);
-        rc = check_launch("conv3d_fwd(split-K)");
-        if (rc) return rc;
-        hipLaunchKernelGGL(conv_fwd_reduce_kernel, dim3(grid_for(n, 256, 2048)), dim3(256), 0, (hipStream_t)stream, slabs, bias,
-                           residual, y, n, g.Cout, ks);
-        return check_launch("conv3d_fwd(split-K reduce)");
-    }
-    DIQT_REQUIRE(!stats || buf, DIQT_E_UNSUPPORTED, "conv3d_fwd: output statistics need the buffer-path kernel");
-    g.stats = stats;
-    if (buf) {
-        ConvGeom g8;
-        size_t lds8;
-        if (fwd8_plan(g, g8, lds8)) {
-            g8.stats = stats;
-            if (lds8 > 64 * 1024) {
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_fwd8_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds8);
-                DIQT_REQUIRE(e == hipSuccess, DIQT_E_LAUNCH, "conv3d_fwd: hipFuncSetAttribute: %s", hipGetErrorString(e));
-            }
-            const unsigned nwg8 = (unsigned)((long long)g8.B * g8.tilesD * g8.tilesH * g8.tilesW * g8.nNt);
-            // persistent tile walk: one workgroup per CU runs all its tiles (needs a 64-channel block that stays with the workgroup)
-            const unsigned grid8 = (nwg8 > 256u && 256 % g8.nNt == 0) ? 256u : nwg8;
-            hipLaunchKernelGGL(conv_fwd8_kernel, dim3(grid8), dim3(512), lds8, (hipStream_t)stream, x, packed, bias, residual, y, g8);
-            return check_launch("conv3d_fwd(8 waves)");
-        }
-    }
-    if (buf && !stats && kd * kh * kw == 1 && g.B == 1 && g.D == 1 && g.H == 1 && g.Wo == g.W && g.TW == MTILE) {     // the flattened-rows geometry of make_geom
-        if (pw64_ok((long long)g.W, Cin, Cout, x, packed, y))      // few input channels, many output channels: x resident, persistent row walk
-            return pw64_launch(x, packed, bias, residual, y, (long long)g.W, Cout, g.CoutPad, stream);
-        hipLaunchKernelGGL(conv1x1_fwd_kernel, dim3(nwg), dim3(256), 0, (hipStream_t)stream, x, packed, bias, residual, y, g);
-        return check_launch("conv3d_fwd(1x1x1)");
-    }
-    hipLaunchKernelGGL(kern, dim3(nwg), dim3(256), lds, (hipStream_t)stream, x, packed, bias, residual, y, g);
-    return check_launch("conv3d_fwd");
+    return convf_launch(r, x, packed, nullptr, nullptr, y, partials, nullptr, 0, stream);
+}
+
+// Block.forward on the sampling path (GroupNorm -> (scale + 1) x + shift -> Mish / SiLU -> conv; imagen_pytorch3D.py:546-566,
+// imagen_video.py:680-697) as ONE launch: x is the RAW GroupNorm input and conv_fwd9_kernel's GroupNorm-apply instantiation rewrites
+// every halo piece in the LDS as act(A x + Bc) right after its DMA landed -- the elementwise pass over the activation (a read and a
+// write of the whole tensor per conv) is gone.  coef[2][B][Cin] = (A, Bc) from diqt_gn_coef_from_partials / diqt_gn_coef.
+// diqt_conv3d_fwd_gn_supported: 1 when conv_fwd9_kernel takes the launch (given the workspace diqt_conv3d_fwd_workspace_bytes asks
+// for) and has the instantiation for this filter and activation; otherwise run diqt_gn_act_fwd + diqt_conv3d_fwd_ex.
+// ... for diqt_conv3d_fwd_gn_pk with a packed buffer of packed_elems floats (see diqt_conv3d_fwd_pk)
+extern "C" int diqt_conv3d_fwd_gn_supported_pk(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw,
+                                               int epd, int eph, int epw, int act, size_t packed_elems) {
+    if (act == 0) return 0;
+    FwdAsk a = query_ask(Cout, Cin, kd, kh, kw, packed_elems, false);
+    a.gnAct = act;
+    FwdRoute r;
+    convf_route(r, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, a);
+    return r.kernel == FWD_F9 ? 1 : 0;
+}
+extern "C" int diqt_conv3d_fwd_gn_supported(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw, int epd,
+                                            int eph, int epw, int act) {
+    return diqt_conv3d_fwd_gn_supported_pk(B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, act, 0);
+}
+// diqt_conv3d_fwd_gn with the length of the packed buffer (Winograd panels of pack mode 2: see diqt_conv3d_fwd_pk).  Statistics rows:
+// diqt_conv3d_fwd_route with gn_act, field 3 (none from a split-K launch).
+extern "C" int diqt_conv3d_fwd_gn_pk(const float* x, const float* packed, size_t packed_elems, const float* bias, const float* residual,
+                                     float* y, float* stats, void* workspace, size_t workspace_bytes, const float* coef, int act,
+                                     int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw, int epd, int eph,
+                                     int epw, void* stream) {
+    const int lay = wino_layout(Cout, Cin, kd, kh, kw, packed_elems);
+    DIQT_REQUIRE(lay >= 0, DIQT_E_SHAPE, "conv3d_fwd_gn_pk: packed buffer of %zu floats, the direct pack alone needs %zu", packed_elems,
+                 diqt_conv_packed_elems(Cout, Cin, kd, kh, kw));
+    DIQT_REQUIRE(x && packed && y && coef, DIQT_E_ALIGN, "conv3d_fwd_gn: null pointer");
+    DIQT_REQUIRE(aligned16(x) && aligned16(packed) && aligned16(coef), DIQT_E_ALIGN, "conv3d_fwd_gn: x, packed weights and coef must be 16-byte aligned");
+    DIQT_REQUIRE(act != 0, DIQT_E_UNSUPPORTED, "conv3d_fwd_gn: no activation given");
+    FwdAsk a;
+    a.wino = lay == 1; a.hasWorkspace = workspace != nullptr; a.hasStats = stats != nullptr; a.gnAct = act;
+    FwdRoute r;
+    convf_route(r, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, a);
+    r.g9.gcoef = coef;
+    r.g9.gnaAct = act;
+    return convf_launch(r, x, packed, bias, residual, y, stats, workspace, workspace_bytes, stream);
+}
+extern "C" int diqt_conv3d_fwd_gn(const float* x, const float* packed, const float* bias, const float* residual, float* y, float* stats,
+                                  void* workspace, size_t workspace_bytes, const float* coef, int act, int B, int D, int H, int W, int Cin, int Cout,
+                                  int kd, int kh, int kw, int pd, int ph, int pw, int epd, int eph, int epw, void* stream) {
+    return diqt_conv3d_fwd_gn_pk(x, packed, diqt_conv_packed_elems(Cout, Cin, kd, kh, kw), bias, residual, y, stats, workspace, workspace_bytes,
+                                 coef, act, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, stream);
 }
 
 static int bw_plan(BwGeom& bg, int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd,

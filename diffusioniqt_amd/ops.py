@@ -486,11 +486,12 @@ def _conv_fwd_raw(x5, packed, bias, residual, Cout, k, pad, epad=(0, 0, 0), stat
               epd, eph, epw, _stream())
     if TIMER.enabled:
         e.record()
-        # the tag names the kernel the C side dispatches to, so that bench.py's per-kernel numbers line up with rocprofv3's
+        # the tag names the kernel the C side dispatched to (the launch's own decision for what it was given), so that bench.py's
+        # per-kernel numbers line up with rocprofv3's; a split-K launch's interval includes the slab sum
         taps = kd * kh * kw
-        kid = _lib.query("diqt_conv3d_fwd_kernel_id", B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw)
-        # (a split-K launch -- n > 0 -- is conv_fwd9_kernel or conv_fwd_kernel writing slabs; its interval includes the slab sum)
-        tag = ("conv_fwd_kernel", "conv_fwd_smallcin_kernel", "conv1x1_fwd_kernel", "conv_fwd8_kernel", "conv_fwd9_kernel")[kid if kid > 0 and (n == 0 or kid == 4) else 0]
+        kid = _lib.query("diqt_conv3d_fwd_route", B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, npk, int(ws is not None),
+                         int(stats is not None), 0, 0, 0)
+        tag = ("conv_fwd_kernel", "conv_fwd_smallcin_kernel", "conv1x1_fwd_kernel", "conv_fwd8_kernel", "conv_fwd9_kernel")[kid]
         TIMER.records.append((s, e, 2.0 * B * Do * Ho * Wo * Cout * Cin * taps, tag, (B, D, H, W, Cin, Cout, kd, kh, kw)))
     return y
 
@@ -1202,7 +1203,9 @@ def gn_conv3d(x, gamma, beta, scale_shift, groups, act, eps, weight, bias, paddi
     ws = _workspace(n, dev) if n else None
     stats = None
     if want_stats:
-        nblk = _lib.query("diqt_conv3d_fwd_stats_blocks_pk", *geo, npk)
+        # the rows this launch is granted (field 3 of its route): none where conv_fwd9_kernel splits K -- the consumer's GroupNorm then
+        # reduces y itself (diqt_groupnorm_stats_coef)
+        nblk = _lib.query("diqt_conv3d_fwd_route", *geo, npk, int(ws is not None), 1, 0, act, 3)
         if nblk > 0:
             stats = torch.empty((B, nblk, 2, Cout), dtype=torch.float32, device=dev)
             y._diqt_stats = ColStats(stats, nblk, Do * Ho * Wo)

@@ -156,6 +156,16 @@ int diqt_conv3d_fwd_kernel_id(int B, int D, int H, int W, int Cin, int Cout, int
  * packed_elems floats (7: the Winograd F(2,3) 3x3x3 tile of diqt_conv3d_fwd_pk), else -1 */
 int diqt_conv3d_fwd9_variant(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw,
                              int epd, int eph, int epw, size_t packed_elems);
+/* Diagnostic: the decision every fp32 forward launch and every query above reads (one function in conv_mfma.hip), as a pure shape
+ * query for one ask: a diqt_conv3d_fwd_pk call (sub_f = 0, gn_act = 0), a diqt_conv3d_fwd_neighbours call (sub_f = f) or a
+ * diqt_conv3d_fwd_gn_pk call (gn_act = its activation) with a packed buffer of packed_elems floats, with / without a workspace and
+ * a statistics buffer.  `field` 0 the kernel, numbered as diqt_conv3d_fwd_kernel_id (-1: the call is refused), 1 the split-K shares,
+ * 2 conv_fwd9_kernel's variant or -1, 3 the statistics rows granted to this ask (0: the launch is the one without statistics and
+ * `stats` must be NULL; a GroupNorm-apply launch that splits K is granted none), 4 the workspace bytes the launch uses (saturating
+ * at INT_MAX); another field: -1.                                                                                                  */
+int diqt_conv3d_fwd_route(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw,
+                          int epd, int eph, int epw, size_t packed_elems, int has_workspace, int has_stats, int sub_f, int gn_act,
+                          int field);
 /* the conv_fwd9_kernel variant the process's last launch of it ran, -1 if none since the previous call (read and clear) */
 int diqt_get_last_conv_fwd9_variant(void);
 int diqt_conv3d_fwd_stats_blocks(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw,
@@ -312,7 +322,8 @@ int diqt_conv3d_fwd_gnbwd_blocks(int B, int D, int H, int W, int Cin, int Cout, 
  * diqt_gn_coef (from existing statistics) fold the normalisation into y = act(A x + Bc), coef[2][B][C] = (A, Bc); diqt_conv3d_fwd_gn
  * takes the RAW GroupNorm input x and applies the coefficients while it stages its input tiles (arguments otherwise as
  * diqt_conv3d_fwd_ex).  diqt_conv3d_fwd_gn_supported = 0: use diqt_gn_act_fwd + diqt_conv3d_fwd_ex.  act: DIQT_ACT_MISH on 3x3x3
- * filters, DIQT_ACT_SILU on (1,3,3) filters.                                                                                       */
+ * filters, DIQT_ACT_SILU on (1,3,3) filters.  `stats`: the rows diqt_conv3d_fwd_route grants this ask (gn_act = act, field 3) -- those
+ * of diqt_conv3d_fwd_stats_blocks* where the launch runs un-split, none where it splits K.                                         */
 int diqt_gn_coef_from_partials(const float* partials, int nblk, int rows, const float* gamma, const float* beta, const float* scale,
                                const float* shift, int cond_stride, float* mean, float* rstd, float* coef, int B, int C, int G,
                                float eps, void* stream);

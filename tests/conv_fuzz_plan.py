@@ -12,7 +12,6 @@ the three ways through ``_Conv3dFn.backward``.  Families:
 Caps (see tests/test_conv_fuzz_plan.py): at most 65536 output voxels and Cin*T, Cout*T <= 10368 per case (where the suite's 2e-5 / 5e-5
 bounds are known to hold), at most 8e9 multiply-adds per case and 1.5e11 per seed (the float64 reference).
 """
-import os
 import random
 
 from diffusioniqt_amd import _lib, ops
@@ -60,12 +59,11 @@ def _geo(case):
     return (B, D, H, W, Cin, Cout, *k, *pad, *epad)
 
 
-def _fwd_route(geo, npk):
-    """What _conv_fwd_raw asks before diqt_conv3d_fwd_pk, for a packed buffer of npk floats."""
-    q = _lib.query
-    kid = q("diqt_conv3d_fwd_kernel_id", *geo)
-    return {"kernel": "id%d" % kid, "kid": kid, "variant": q("diqt_conv3d_fwd9_variant", *geo, npk),
-            "split": q("diqt_conv3d_fwd_workspace_bytes_pk", *geo, npk) > 0, "stats_blocks": q("diqt_conv3d_fwd_stats_blocks_pk", *geo, npk)}
+def _fwd_route(geo, npk, has_stats=False):
+    """The launch of _conv_fwd_raw's diqt_conv3d_fwd_pk call with a packed buffer of npk floats, the workspace the query asks for and
+    (has_stats) a wish for statistics: the library's own decision, diqt_conv3d_fwd_route."""
+    kid, ksplit, variant, rows = (_lib.query("diqt_conv3d_fwd_route", *geo, npk, 1, int(has_stats), 0, 0, field) for field in range(4))
+    return {"kernel": "id%d" % kid, "kid": kid, "variant": variant, "split": ksplit > 1, "stats_blocks": rows}
 
 
 def route(case):
@@ -77,13 +75,11 @@ def route(case):
     if Cout <= 2 and not want_stats(case) and q("diqt_conv3d_fwd_smallcout_supported", *geo):
         fwd = {"kernel": "smallcout", "kid": None, "variant": -1, "split": False, "stats_blocks": 0}
     else:
-        fwd = _fwd_route(geo, sum(ops._packed_len((Cout, Cin, *k), 0)))          # direct pack + Winograd panels
-        if fwd["kid"] == 4 and fwd["split"] and want_stats(case) and fwd["stats_blocks"] > 0 and os.environ.get("DIQT_CONV_F9") != "2":
-            # diqt_conv3d_fwd_kernel_id says conv_fwd9_kernel in its split-K form, but the statistics query grants the caller the
-            # per-tile sums of an un-split conv_fwd_kernel launch (fwd_ksplit == 1), and a launch that is handed a statistics buffer
-            # does not split: it runs conv_fwd_kernel.  (conv_fwd8_kernel cannot take it: of its tiles only the 4x8x8 family holds a
-            # 3x3x3 halo in registers, and conv_fwd9's split means fewer than 241 of those.)
-            fwd.update(kernel="id0", kid=0, variant=-1, split=False, stats_fallback=True)
+        npk = sum(ops._packed_len((Cout, Cin, *k), 0))                           # direct pack + Winograd panels
+        fwd, plain = _fwd_route(geo, npk, want_stats(case)), _fwd_route(geo, npk)
+        if plain["kid"] == 4 and plain["split"] and fwd["kid"] == 0 and not fwd["split"]:
+            # the launch without statistics is conv_fwd9_kernel in its split-K form; granted statistics, it runs un-split conv_fwd_kernel
+            fwd["stats_fallback"] = True
     bwd = wg = None
     Do, Ho, Wo = out_extent(case)
     if "x" in grads:
@@ -107,7 +103,7 @@ def wgrad_route(case):
     return {"kid": kid, "kind": kind}
 
 
-def fwd_tags(r, exact_split=True):
+def fwd_tags(r):
     """Launch tags a forward-type pass planned as ``r`` shows in the census.  id 2 is conv1x1_fwd_kernel or its K = 64 sibling: no query
     tells them apart, either tag is accepted (returned as a tuple of alternatives)."""
     if r["kernel"] == "smallcout":
@@ -116,13 +112,7 @@ def fwd_tags(r, exact_split=True):
     if kid == 1:
         return ({"conv3d_fwd(small Cin)": 1},)
     if kid == 4:
-        split = {"conv3d_fwd(v9)": 1, "conv3d_fwd(v9 split-K reduce)": 1}
-        if not r["split"]:
-            return ({"conv3d_fwd(v9)": 1},)
-        # With its tile-count rules on, an un-split conv_fwd9 launch has >= 241 tiles of >= 256 voxels at >= 0.9 useful, hence >= 434
-        # 128-voxel workgroups on conv_fwd_kernel: above fwd_ksplit's 384, so a workspace request can only be conv_fwd9's own split.
-        # Under DIQT_CONV_F9=2 that does not hold: the workspace may be the request of the fallback kernel's split-K plan.
-        return (split,) if exact_split else (split, {"conv3d_fwd(v9)": 1})
+        return ({"conv3d_fwd(v9)": 1, "conv3d_fwd(v9 split-K reduce)": 1},) if r["split"] else ({"conv3d_fwd(v9)": 1},)
     if kid == 3:
         return ({"conv3d_fwd(8 waves)": 1},)
     if kid == 2:

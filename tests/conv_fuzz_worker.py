@@ -158,12 +158,12 @@ def main(family, seed):
         obs = "fwd=%s/v%d bwd=%s/v%d wg=%s" % ("+".join(sorted(o["fwd_obs"])), o["fvar"], "+".join(sorted(o["bwd_obs"])) or "-", o["bvar"],
                                                "+".join(sorted(o["wg_obs"])) or "-")
         for run in (o, o2):
-            if run["fwd_obs"] not in plan.fwd_tags(rt["fwd"], exact_split=not f9small) or run["fvar"] != rt["fwd"]["variant"]:
+            if run["fwd_obs"] not in plan.fwd_tags(rt["fwd"]) or run["fvar"] != rt["fwd"]["variant"]:
                 why.append("forward route")
             if rt["bwd_data"] is None:
                 if run["bwd_obs"] or run["bvar"] != -1:
                     why.append("backward-data ran without need")
-            elif run["bwd_obs"] not in plan.fwd_tags(rt["bwd_data"], exact_split=not f9small) or run["bvar"] != rt["bwd_data"]["variant"]:
+            elif run["bwd_obs"] not in plan.fwd_tags(rt["bwd_data"]) or run["bvar"] != rt["bwd_data"]["variant"]:
                 why.append("backward-data route")
             if run["wg_obs"] != (plan.wgrad_tags(rt["wgrad"]) if rt["wgrad"] else {}):
                 why.append("weight-gradient route")

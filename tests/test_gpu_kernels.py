@@ -910,6 +910,37 @@ def test_groupnorm_apply_inside_the_conv_staging_matches_the_two_kernel_path(ops
     assert torch.equal(y3, y), "the result must not depend on whether output statistics are requested"
 
 
+def test_groupnorm_apply_on_a_split_k_launch_runs_without_output_statistics(ops):
+    """A per-frame conv of a 32-channel pseudo-3D level, (2, 16^3, 32 -> 256, (1,3,3), SiLU): the GroupNorm-apply launch is
+    conv_fwd9_kernel's split-K form (variant 4, two shares), which writes no statistics, while the plain launch of the shape is granted
+    32 rows (it runs un-split).  ``ops.gn_conv3d(..., want_stats=True)`` asks the route of ITS launch and runs without them (it used
+    to pass the plain launch's rows and was refused); the consumer's GroupNorm then reduces the tensor itself."""
+    from diffusioniqt_amd import _lib
+    B, D, H, W, Cin, Cout, k, pads = 2, 16, 16, 16, 32, 256, (1, 3, 3), (0, 1, 1)
+    g = torch.Generator().manual_seed(Cin + 3 * Cout + k[0])
+    x = torch.randn(B, Cin, D, H, W, generator=g) * 1.7 + 0.4
+    gamma, beta = torch.randn(Cin, generator=g), torch.randn(Cin, generator=g) * 0.3
+    ss = torch.randn(B, 2 * Cin, generator=g) * 0.3
+    w = torch.randn(Cout, Cin, *k, generator=g) / math.sqrt(Cin * 9)
+    bias = torch.randn(Cout, generator=g) * 0.1
+    h = F.group_norm(x.double(), 8, gamma.double(), beta.double(), eps=1e-5)
+    h = F.silu(h * (ss.double()[:, :Cin, None, None, None] + 1) + ss.double()[:, Cin:, None, None, None])
+    ref = F.conv3d(h, w.double(), bias.double(), padding=pads)
+    xd, gd, bd, wd, cd, sd = cl(x), gamma.to(DEV), beta.to(DEV), w.to(DEV), bias.to(DEV), ss.to(DEV)
+    with torch.no_grad():
+        _lib.query("diqt_get_last_conv_fwd9_variant")
+        y = ops.gn_conv3d(xd, gd, bd, sd, 8, ops.ACT_SILU, 1e-5, wd, cd, pads, want_stats=True)
+        assert y is not None, "shape not taken by the GroupNorm-apply instantiation of conv_fwd9_kernel"
+        assert _lib.query("diqt_get_last_conv_fwd9_variant") == 4
+        y2 = ops.conv3d(ops.groupnorm_act(xd, gd, bd, sd, 8, ops.ACT_SILU), wd, cd, pads, want_stats=True)
+        y3 = ops.gn_conv3d(xd, gd, bd, sd, 8, ops.ACT_SILU, 1e-5, wd, cd, pads)
+    assert getattr(y, "_diqt_stats", None) is None, "a split-K launch writes no statistics"
+    assert getattr(y2, "_diqt_stats", None) is not None, "the plain launch of this shape is granted statistics: not the shape this test is about"
+    close(cf(y), ref, tol=3e-5, what="fused GroupNorm + act + conv vs float64")
+    close(cf(y), cf(y2).double(), tol=1e-5, what="fused vs two-kernel path")
+    assert torch.equal(y3, y), "the result must not depend on whether output statistics are requested"
+
+
 @pytest.mark.parametrize("B,sp,Cin,Cout,k,pad,epad,res", [
     (2, (6, 20, 20), 65, 1, (1, 3, 3), (0, 1, 1), (0, 0, 0), False),      # the pseudo-3D final conv: 65 channels (rows not 16-byte aligned)
     (1, (5, 9, 33), 64, 1, (1, 1, 1), (0, 0, 0), (0, 0, 0), True),        # GlobalContext.to_k, ragged tiles, residual
