@@ -126,6 +126,10 @@ PROTOTYPES = {
     "diqt_conv3d_fwd_route": (I, [I] * 15 + [Z, I, I, I, I, I]),
     "diqt_get_last_conv_fwd9_variant": (I, []),
     "diqt_conv3d_fwd_pk": (I, [P, P, Z, P, P, P, P, P, Z] + [I] * 15 + [P]),
+    "diqt_conv1x1_fwd_ex_supported": (I, [I] * 10),
+    "diqt_conv1x1_fwd_ex_stats_blocks": (I, [I] * 9),
+    "diqt_conv1x1_pack_d2s": (I, [P, P, P, P, I, I, P]),
+    "diqt_conv1x1_fwd_ex": (I, [P, P, P, P, P, P, P] + [I] * 8 + [P]),
     "diqt_conv3d_fwd_workspace_bytes_pk": (Z, [I] * 15 + [Z]),
     "diqt_conv3d_fwd_stats_blocks_pk": (I, [I] * 15 + [Z]),
     "diqt_conv3d_fwd_gn_supported_pk": (I, [I] * 16 + [Z]),

@@ -661,9 +661,28 @@ __global__ __launch_bounds__(512, 2) void conv_fwd8_kernel(const float* __restri
 // them (one barrier per chunk, no memory latency between chunks).  Same tile (128 rows x 64 co, 4 waves), packed weights,
 // fragment order and buffer-descriptor epilogue as conv_fwd_kernel.
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256, 2) void conv1x1_fwd_kernel(const float* __restrict__ x, const float* __restrict__ wp,
-                                                             const float* __restrict__ bias, const float* __restrict__ residual,
-                                                             float* __restrict__ y, ConvGeom g) {
+// What the extended epilogues (conv1x1_ex_kernel) read besides the plain launch's arguments
+struct C1Ex {
+    int D, H, W, Cp;            // depth-to-space: the coarse extents of a batch entry and the fine channel count C' = Cout / 8
+    int rowsPerSample, nblk;    // statistics: rows (coarse voxels) of a batch entry -- a multiple of 128 -- and rows of column sums per entry
+    float* stats;               // [B][nblk][2][C] column sums of the final output (C = C' with depth-to-space, else Cout)
+    const float* h;             // gated residual: y = gate[b][co] * h[row][co] + (acc + bias)
+    const float* gate;
+};
+
+// ACT / D2S / STATS / GATE = 0: the plain launch (bias, optional residual).  Otherwise the epilogue of conv1x1_ex_kernel:
+//   ACT    DIQT_ACT_MISH on acc + bias (act_fwd, the expression of act_fwd_kernel)
+//   D2S    depth-to-space by 2: weights and bias are packed in the order j = q C' + c' of the deep channel co = 8 c' + q
+//          (conv1x1_pack_d2s_kernel), so a 64-wide tile is ONE q = (qd, qh, qw) and 64 consecutive fine channels: only the
+//          row -> byte offset map changes (a 128-entry table in the LDS the main loop is done with), stores stay coalesced
+//   STATS  one row of column sums (sum, sum of squares) of the final output per 128-row tile (and per q): a lane sums its 16
+//          registers, then the two lane halves, then the four waves through LDS -- a fixed order, no atomics
+//   GATE   the SE gate and residual of gate_residual_stats_kernel with this conv as the residual branch
+template <int ACT, bool D2S, bool STATS, bool GATE>
+__device__ __forceinline__ void conv1x1_tile(const float* __restrict__ x, const float* __restrict__ wp,
+                                             const float* __restrict__ bias, const float* __restrict__ residual,
+                                             float* __restrict__ y, const ConvGeom& g, const C1Ex& e) {
+    constexpr bool EX = ACT != 0 || D2S || STATS || GATE;
     __shared__ __attribute__((aligned(16))) float As[2][MTILE * LDSROW];
     __shared__ __attribute__((aligned(16))) float Ws[2][NT * LDSROW];
     const int tid = threadIdx.x;
@@ -743,27 +762,133 @@ __global__ __launch_bounds__(256, 2) void conv1x1_fwd_kernel(const float* __rest
     const float bias0 = (bias && co0 < g.Cout) ? bias[co0] : 0.f;
     const float bias1 = (bias && co1 < g.Cout) ? bias[co1] : 0.f;
     const auto rs_y = __builtin_amdgcn_make_buffer_rsrc(y, 0, (int)g.yBytes, 0x00020000);
-    const auto rs_r = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(residual), 0, residual ? (int)g.yBytes : 0, 0x00020000);
-    const unsigned c0 = co0 < g.Cout ? (unsigned)co0 * 4u : BUF_OOB_C, c1 = co1 < g.Cout ? (unsigned)co1 * 4u : BUF_OOB_C;
-    // residual: all 32 loads in flight before the first add (a load + wait + add per element serialises 16 L2 round trips)
-    float rr0[16], rr1[16];
-    if (residual) {            // wave-uniform
+    if constexpr (!EX) {
+        const auto rs_r = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(residual), 0, residual ? (int)g.yBytes : 0, 0x00020000);
+        const unsigned c0 = co0 < g.Cout ? (unsigned)co0 * 4u : BUF_OOB_C, c1 = co1 < g.Cout ? (unsigned)co1 * 4u : BUF_OOB_C;
+        // residual: all 32 loads in flight before the first add (a load + wait + add per element serialises 16 L2 round trips)
+        float rr0[16], rr1[16];
+        if (residual) {            // wave-uniform
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const long long row = r0 + wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                const unsigned off = row < rows ? (unsigned)(row * g.Cout * 4) : BUF_OOB;
+                rr0[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_r, off + c0, 0, 0));
+                rr1[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_r, off + c1, 0, 0));
+            }
+        }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const long long row = r0 + wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
             const unsigned off = row < rows ? (unsigned)(row * g.Cout * 4) : BUF_OOB;
-            rr0[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_r, off + c0, 0, 0));
-            rr1[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_r, off + c1, 0, 0));
+            float v0 = acc0[r] + bias0, v1 = acc1[r] + bias1;
+            if (residual) { v0 += rr0[r]; v1 += rr1[r]; }
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v0), rs_y, off + c0, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v1), rs_y, off + c1, 0, 0);
+        }
+    } else {
+        // output channel of packed column j: the fine channel (j mod C') of sub-voxel q = j / C' with depth-to-space, else j itself
+        const int Cy = D2S ? e.Cp : g.Cout;
+        const int ch0 = D2S ? co0 % e.Cp : co0, ch1 = ch0 + 32;               // C' % 64 == 0: both halves of the tile share q
+        const bool ok0 = co0 < g.Cout, ok1 = co1 < g.Cout;
+        const unsigned c0 = ok0 ? (unsigned)ch0 * 4u : BUF_OOB_C, c1 = ok1 ? (unsigned)ch1 * 4u : BUF_OOB_C;
+        unsigned* rowOff = reinterpret_cast<unsigned*>(&As[0][0]);            // the main loop's last barrier retired every read of As / Ws
+        if (tid < MTILE) {
+            const long long row = r0 + tid;
+            unsigned off = BUF_OOB;
+            if (row < rows) {
+                if constexpr (D2S) {
+                    const int q = n0 / e.Cp, qw = q & 1, qh = (q >> 1) & 1, qd = q >> 2;      // q = (qd 2 + qh) 2 + qw, as shuffle_nd_vec_kernel
+                    long long t = row;
+                    const int w = (int)(t % e.W); t /= e.W;
+                    const int hh = (int)(t % e.H); t /= e.H;
+                    const int d = (int)(t % e.D);
+                    const long long b = t / e.D;
+                    const long long fine = ((b * (2 * e.D) + 2 * d + qd) * (2 * e.H) + 2 * hh + qh) * (2 * e.W) + 2 * w + qw;
+                    off = (unsigned)(fine * e.Cp * 4);
+                } else {
+                    off = (unsigned)(row * g.Cout * 4);
+                }
+            }
+            rowOff[tid] = off;
+        }
+        __syncthreads();
+        const int bIdx = (STATS || GATE) ? (int)(r0 / e.rowsPerSample) : 0;   // rowsPerSample % 128 == 0: a tile stays inside a batch entry
+        float hh0[16], hh1[16], g0 = 0.f, g1 = 0.f;
+        if constexpr (GATE) {
+            const auto rs_h = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(e.h), 0, (int)g.yBytes, 0x00020000);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const unsigned off = rowOff[wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * h];
+                hh0[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_h, off + c0, 0, 0));
+                hh1[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_h, off + c1, 0, 0));
+            }
+            if (ok0) g0 = e.gate[(size_t)bIdx * g.Cout + co0];
+            if (ok1) g1 = e.gate[(size_t)bIdx * g.Cout + co1];
+        }
+        float s0 = 0.f, s1 = 0.f, q0 = 0.f, q1 = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const unsigned off = rowOff[wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * h];
+            float v0 = acc0[r] + bias0, v1 = acc1[r] + bias1;
+            if constexpr (ACT != 0) { v0 = act_fwd(v0, ACT); v1 = act_fwd(v1, ACT); }
+            if constexpr (GATE) {                                              // gate_residual_stats_kernel: v = h * gate; v += res
+#pragma clang fp contract(off)                                                 // ... which multiplies, then adds (v_pk_mul_f32, v_pk_add_f32)
+                float t0 = hh0[r] * g0, t1 = hh1[r] * g1;
+                t0 += v0; t1 += v1;
+                v0 = t0; v1 = t1;
+            }
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v0), rs_y, off + c0, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v1), rs_y, off + c1, 0, 0);
+            if constexpr (STATS) {
+                s0 += v0; s1 += v1;
+                q0 = fmaf(v0, v0, q0); q1 = fmaf(v1, v1, q1);
+            }
+        }
+        if constexpr (STATS) {
+            s0 += __shfl_xor(s0, 32, 64); s1 += __shfl_xor(s1, 32, 64);
+            q0 += __shfl_xor(q0, 32, 64); q1 += __shfl_xor(q1, 32, 64);
+            float* red = &Ws[0][0];                                            // [wave][sum 0..31, sq 0..31, sum 32..63, sq 32..63]
+            if (h == 0) {
+                float* mine = red + wave * 128 + l31;
+                mine[0] = s0; mine[32] = q0; mine[64] = s1; mine[96] = q1;
+            }
+            __syncthreads();
+            if (tid < 128) {
+                const float tot = ((red[tid] + red[128 + tid]) + red[256 + tid]) + red[384 + tid];
+                const int half = tid >> 6, sq = (tid >> 5) & 1, l = tid & 31;
+                const int tileInSample = (int)((r0 % e.rowsPerSample) / MTILE);
+                const int blk = D2S ? tileInSample * 8 + n0 / e.Cp : tileInSample;
+                const int ch = (D2S ? n0 % e.Cp : n0) + half * 32 + l;
+                if (n0 + half * 32 + l < g.Cout) e.stats[(((size_t)bIdx * e.nblk + blk) * 2 + sq) * Cy + ch] = tot;
+            }
         }
     }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const long long row = r0 + wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-        const unsigned off = row < rows ? (unsigned)(row * g.Cout * 4) : BUF_OOB;
-        float v0 = acc0[r] + bias0, v1 = acc1[r] + bias1;
-        if (residual) { v0 += rr0[r]; v1 += rr1[r]; }
-        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v0), rs_y, off + c0, 0, 0);
-        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v1), rs_y, off + c1, 0, 0);
+}
+
+__global__ __launch_bounds__(256, 2) void conv1x1_fwd_kernel(const float* __restrict__ x, const float* __restrict__ wp,
+                                                             const float* __restrict__ bias, const float* __restrict__ residual,
+                                                             float* __restrict__ y, ConvGeom g) {
+    conv1x1_tile<0, false, false, false>(x, wp, bias, residual, y, g, C1Ex{});
+}
+
+template <int ACT, bool D2S, bool STATS, bool GATE>
+__global__ __launch_bounds__(256, 2) void conv1x1_ex_kernel(const float* __restrict__ x, const float* __restrict__ wp,
+                                                            const float* __restrict__ bias, float* __restrict__ y, ConvGeom g, C1Ex e) {
+    conv1x1_tile<ACT, D2S, STATS, GATE>(x, wp, bias, nullptr, y, g, e);
+}
+
+// packed weights / bias of the depth-to-space form: column j = q C' + c' holds the deep channel co = 8 c' + q
+// (packed[(chunk * Cout + j) * 32 + k], Cout % 512 == 0 so there is no channel padding)
+__global__ void conv1x1_pack_d2s_kernel(const float* __restrict__ w, const float* __restrict__ bias, float* __restrict__ packed,
+                                        float* __restrict__ biasPacked, int Cout, int Cin, size_t total) {
+    const int Cp = Cout / 8;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int k = (int)(i % CK);
+        const size_t r = i / CK;
+        const int j = (int)(r % Cout), chunk = (int)(r / Cout);
+        const int co = (j % Cp) * 8 + j / Cp, in = chunk * CK + k;
+        packed[i] = in < Cin ? w[(size_t)co * Cin + in] : 0.f;
+        if (bias && biasPacked && chunk == 0 && k == 0) biasPacked[j] = bias[co];
     }
 }
 
@@ -2064,6 +2189,83 @@ extern "C" int diqt_conv3d_fwd_pk(const float* x, const float* packed, size_t pa
                  diqt_conv_packed_elems(Cout, Cin, kd, kh, kw));
     return conv3d_fwd_impl(x, packed, bias, residual, y, workspace, workspace_bytes, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw,
                            epd, eph, epw, stream, stats, lay == 1);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// 1x1x1 convs with an extended epilogue (conv1x1_ex_kernel; fp32 sampling path).  Entry points of their own: diqt_conv3d_fwd* and its
+// route are untouched, and a caller whose shape the query refuses keeps the separate launches.
+//   act      0 or DIQT_ACT_MISH, applied to acc + bias
+//   d2s      depth-to-space by 2 of the result: y[B][2D][2H][2W][Cout / 8]; `packed` / `bias` come from diqt_conv1x1_pack_d2s
+//   stats    rows of column sums [B][nblk][2][C] of the final output (C = Cout / 8 with d2s), nblk = diqt_conv1x1_fwd_ex_stats_blocks
+//   gated    y = gate[b][co] * h[row][co] + (acc + bias), the SE tail of a ResnetBlock whose residual branch is this conv; always with stats
+// ---------------------------------------------------------------------------------------------------------------------------------
+static bool c1ex_plan(ConvGeom& g, C1Ex& e, int B, int D, int H, int W, int Cin, int Cout, int act, int d2s, int stats, int gated) {
+    if (B <= 0 || D <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || Cin % 4 != 0) return false;
+    if (act != 0 && act != DIQT_ACT_MISH) return false;
+    if (gated && (d2s || act != 0 || !stats)) return false;
+    if (!gated && !(act == DIQT_ACT_MISH && d2s) && !(act == 0 && !d2s && stats)) return false;       // the instantiated forms
+    const long long rps = (long long)D * H * W, rows = rps * B;
+    if (rows >= (1ll << 31)) return false;
+    if ((unsigned long long)rows * Cin * 4ull >= (1ull << 30) || (unsigned long long)rows * Cout * 4ull >= (1ull << 30)) return false;
+    if (d2s && (Cout % 8 != 0 || (Cout / 8) % NT != 0)) return false;          // a 64-wide tile must hold one q
+    if (stats && rps % MTILE != 0) return false;                               // a 128-row tile must stay inside a batch entry
+    if (make_geom(g, B, D, H, W, Cin, Cout, 1, 1, 1, 0, 0, 0)) return false;
+    g.xBytes = (unsigned)((unsigned long long)rows * Cin * 4ull);
+    g.yBytes = (unsigned)((unsigned long long)rows * Cout * 4ull);
+    e = C1Ex{};
+    e.D = D; e.H = H; e.W = W; e.Cp = d2s ? Cout / 8 : Cout;
+    e.rowsPerSample = (int)rps;
+    e.nblk = stats ? (int)(rps / MTILE) * (d2s ? 8 : 1) : 0;
+    return true;
+}
+extern "C" int diqt_conv1x1_fwd_ex_supported(int B, int D, int H, int W, int Cin, int Cout, int act, int d2s, int stats, int gated) {
+    ConvGeom g; C1Ex e;
+    return c1ex_plan(g, e, B, D, H, W, Cin, Cout, act, d2s, stats, gated) ? 1 : 0;
+}
+// rows of column sums per batch entry a launch with `stats` writes (0: refused -- rows per batch entry that are no multiple of 128, ...)
+extern "C" int diqt_conv1x1_fwd_ex_stats_blocks(int B, int D, int H, int W, int Cin, int Cout, int act, int d2s, int gated) {
+    ConvGeom g; C1Ex e;
+    return c1ex_plan(g, e, B, D, H, W, Cin, Cout, act, d2s, 1, gated) ? e.nblk : 0;
+}
+extern "C" int diqt_conv1x1_pack_d2s(const float* w, const float* bias, float* packed, float* bias_packed, int Cout, int Cin, void* stream) {
+    DIQT_REQUIRE(w && packed && (!bias || bias_packed), DIQT_E_ALIGN, "conv1x1_pack_d2s: null pointer");
+    DIQT_REQUIRE(Cout > 0 && Cin > 0 && Cout % (8 * NT) == 0, DIQT_E_SHAPE, "conv1x1_pack_d2s: Cout / 8 must be a multiple of %d", NT);
+    const size_t total = (size_t)cdiv(Cin, CK) * Cout * CK;
+    hipLaunchKernelGGL(conv1x1_pack_d2s_kernel, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, w, bias, packed, bias_packed,
+                       Cout, Cin, total);
+    return check_launch("conv1x1_pack_d2s");
+}
+extern "C" int diqt_conv1x1_fwd_ex(const float* x, const float* packed, const float* bias, const float* h, const float* gate, float* y,
+                                   float* stats, int B, int D, int H, int W, int Cin, int Cout, int act, int d2s, void* stream) {
+    DIQT_REQUIRE(x && packed && y, DIQT_E_ALIGN, "conv1x1_fwd_ex: null pointer");
+    DIQT_REQUIRE(aligned16(x) && aligned16(packed), DIQT_E_ALIGN, "conv1x1_fwd_ex: x and the packed weights must be 16-byte aligned");
+    DIQT_REQUIRE((h == nullptr) == (gate == nullptr), DIQT_E_ALIGN, "conv1x1_fwd_ex: h and gate come together");
+    const int gated = h != nullptr;
+    ConvGeom g; C1Ex e;
+    DIQT_REQUIRE(c1ex_plan(g, e, B, D, H, W, Cin, Cout, act, d2s, stats != nullptr, gated), DIQT_E_UNSUPPORTED,
+                 "conv1x1_fwd_ex: shape / form not taken (diqt_conv1x1_fwd_ex_supported == 0)");
+    e.stats = stats; e.h = h; e.gate = gate;
+    const unsigned nwg = (unsigned)((long long)g.tilesW * g.nNt);
+    hipStream_t s = (hipStream_t)stream;
+    if (gated) {
+        hipLaunchKernelGGL((conv1x1_ex_kernel<0, false, true, true>), dim3(nwg), dim3(256), 0, s, x, packed, bias, y, g, e);
+        return check_launch("conv1x1_fwd_ex(gated residual + stats)");
+    }
+    if (d2s && act == DIQT_ACT_MISH) {
+        if (stats) {
+            hipLaunchKernelGGL((conv1x1_ex_kernel<DIQT_ACT_MISH, true, true, false>), dim3(nwg), dim3(256), 0, s, x, packed, bias, y, g, e);
+            return check_launch("conv1x1_fwd_ex(mish + d2s + stats)");
+        }
+        hipLaunchKernelGGL((conv1x1_ex_kernel<DIQT_ACT_MISH, true, false, false>), dim3(nwg), dim3(256), 0, s, x, packed, bias, y, g, e);
+        return check_launch("conv1x1_fwd_ex(mish + d2s)");
+    }
+    if (!d2s && act == 0 && stats) {
+        hipLaunchKernelGGL((conv1x1_ex_kernel<0, false, true, false>), dim3(nwg), dim3(256), 0, s, x, packed, bias, y, g, e);
+        return check_launch("conv1x1_fwd_ex(stats)");
+    }
+    set_error("conv1x1_fwd_ex: no instantiation for act %d, d2s %d, stats %d (the forms: Mish + d2s [+ stats], stats, gated)", act, d2s,
+              stats != nullptr);
+    return DIQT_E_UNSUPPORTED;
 }
 
 // 'same' convolution (odd cubic filter k, padding k / 2) over the f^3 sub-volume batch x[f^3][A][A][A][Cin] of ONE merged volume, the

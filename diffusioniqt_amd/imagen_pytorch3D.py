@@ -319,6 +319,12 @@ class PixelShuffleUpsample(nn.Module):
         nn.init.zeros_(conv.bias.data)
 
     def forward(self, x):
+        conv = self.net[0]
+        if not torch.is_grad_enabled() and conv.groups == 1 and tuple(conv.stride) == (1, 1, 1):
+            # sampling: conv + Mish + depth-to-space as one launch (None: shape not taken -- the three launches below)
+            y = ops.conv1x1_act_shuffle(x, conv.weight, conv.bias, ACT_MISH)
+            if y is not None:
+                return y
         return self.net(x)
 
 
@@ -469,6 +475,14 @@ class BatchedTimeMLPs:
     train_batched = True       # False: per-block time MLPs when autograd records (A/B and tests)
 
 
+def _glue_pays(*shape):
+    """Sampling path, fp32: does a tensor of this shape take the forms that change where its column sums come from (the skip concatenation
+    that writes them, the gated-residual ``res_conv``)?  From 4 MiB on -- a tensor that no longer sits in one XCD's L2, so the pass saved
+    is a trip to HBM.  Below that the separate launches stay, and with them the small-shape bit-parity of the sampling path with the
+    autograd path (same statistics kernels, same summation order), which the parity suite pins."""
+    return not torch.is_grad_enabled() and ops.lp_mode() is None and 4 * math.prod(shape) >= (4 << 20)
+
+
 class ResnetBlock(nn.Module):
     """imagen_pytorch3D.py:568-614."""
 
@@ -499,6 +513,14 @@ class ResnetBlock(nn.Module):
               and (ops.conv_half_out_ok((*x.shape[:4], b2.weight.shape[1]), b2.weight, b2.padding)
                    or ops.train_half_out_ok((*x.shape[:4], b2.weight.shape[1]), b2.weight, b2.padding, self.block2.groupnorm.num_groups)))
         h, x = self.block1(x, emit_stats=True, tap=True, out_half=oh)
+        rc = self.res_conv
+        if isinstance(self.se, SE3D) and isinstance(rc, Conv3d) and x.dim() == 5 and _glue_pays(*x.shape[:4], rc.weight.shape[0]) \
+                and rc.groups == 1 and tuple(rc.stride) == (1, 1, 1) and tuple(rc.kernel_size) == (1, 1, 1):
+            # sampling: res_conv runs LAST, its epilogue applies the SE gate to h, adds and writes the block output with its column sums:
+            # `res` is never written and read back (None: shape not taken -- the launches below)
+            h2 = self.block2(h, scale_shift=scale_shift, emit_stats=True)
+            y = ops.se_conv1x1_residual(h2, self.se.fc[0].weight, self.se.fc[2].weight, x, rc.weight, rc.bias)
+            return y if y is not None else self.se(h2, residual=rc(x))
         res = self.res_conv(x)
         if isinstance(self.se, SE3D):
             # ... and the SE pooling from this one's.  Under autocast sampling / low-precision training block2's output only meets the SE
@@ -1023,6 +1045,11 @@ class Unet(nn.Module):
         vol = block(vol)
         return ops.split_volume(vol, f, A) if f > 1 else vol
 
+    def _cat_skip(self, x, skip):
+        """cat(x, skip * scale) in one pass; sampling: with the column sums of the result for the init block's GroupNorm"""
+        return ops.concat_channels(x, skip, 1.0, self.skip_connect_scale,
+                                   want_stats=_glue_pays(*x.shape[:-1], x.shape[-1] + skip.shape[-1]))
+
     def forward(self, x, time_steps=None, time=None, *, lowres_cond_img=None, cond_images=None, self_cond=None,
                 cond_drop_prob=0.):
         """(x[B,C,S,S,S], time_steps (ignored, as in the reference), time = log-SNR [B]) -> [B,C_out,S,S,S].
@@ -1078,7 +1105,7 @@ class Unet(nn.Module):
         for upsample, init_block, resnet_blocks in self.ups:
             if exists(upsample):
                 x = upsample(x)
-                x = ops.concat_channels(x, hiddens.pop(), 1.0, self.skip_connect_scale)      # cat(x, skip * scale) in one pass
+                x = self._cat_skip(x, hiddens.pop())
             x = init_block(x, t)
             for resnet_block in resnet_blocks:
                 x = resnet_block(x, t)

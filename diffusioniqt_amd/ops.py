@@ -641,6 +641,116 @@ def conv3d(x, weight, bias=None, padding=(0, 0, 0), residual=None, extra_pad=(0,
     return y
 
 
+def _packed_d2s(weight5, bias):
+    """(packed weights, packed bias) of a 1x1x1 conv whose output goes through depth-to-space by 2, in the column order (q, c') of the
+    deep channel 8 c' + q that ``diqt_conv1x1_fwd_ex`` wants; cached on the weight like ``_packed`` until either tensor changes."""
+    owner = weight5._base if weight5._base is not None else weight5
+    cache = getattr(owner, "_diqt_pack", None)
+    if cache is None:
+        cache = {}
+        try:
+            owner._diqt_pack = cache
+        except Exception:
+            pass
+    key = ("d2s", weight5.data_ptr(), weight5._version, _WEIGHT_EPOCH) + \
+        ((bias.data_ptr(), bias._version) if bias is not None else (0, -1))
+    hit = cache.get("d2s")
+    if hit is not None and hit[0] == key:
+        return hit[1], hit[2]
+    Cout, Cin = weight5.shape[:2]
+    packed = torch.empty(_lib.query("diqt_conv_packed_elems", Cout, Cin, 1, 1, 1), dtype=torch.float32, device=weight5.device)
+    bpk = torch.empty(Cout, dtype=torch.float32, device=weight5.device) if bias is not None else None
+    _lib.call("diqt_conv1x1_pack_d2s", weight5.detach(), bias.detach() if bias is not None else None, packed, bpk, Cout, Cin, _stream())
+    if hit is not None:
+        retire(hit[1], hit[2])
+    cache["d2s"] = (key, born(packed), born(bpk) if bpk is not None else None)
+    return packed, bpk
+
+
+def _conv1x1_ex_ok(x, weight, *more):
+    if torch.is_grad_enabled() or lp_mode() is not None or x.dim() != 5 or x.dtype != torch.float32 or not x.is_cuda:
+        return False
+    if tuple(weight.shape[2:]) != (1, 1, 1) or weight.shape[1] != x.shape[-1] or weight.dtype != torch.float32:
+        return False
+    return all(t is None or (t.dtype == torch.float32 and t.is_cuda) for t in more)
+
+
+def conv1x1_act_shuffle(x, weight, bias, act=ACT_MISH, want_stats=False):
+    """Sampling path (no autograd, fp32): depth_to_space(act(conv1x1(x))) -- the pixel-shuffle up-sampler -- as ONE launch: the conv's
+    epilogue applies the activation and stores each 64-channel tile straight into its fine voxels.  Bit-identical to
+    ``conv3d`` -> ``activation`` -> ``depth_to_space``.  ``want_stats``: the launch also writes the column sums of its output
+    (``_diqt_stats``) where the shape allows.  Returns None when the shape is not taken (the caller keeps the three launches)."""
+    if not _conv1x1_ex_ok(x, weight, bias):
+        return None
+    B, D, H, W, Cin = x.shape
+    Cout = weight.shape[0]
+    if not _lib.query("diqt_conv1x1_fwd_ex_supported", B, D, H, W, Cin, Cout, act, 1, 0, 0):
+        return None
+    x = x.contiguous()
+    _chk(x, weight, bias)
+    packed, bpk = _packed_d2s(weight, bias)
+    y = torch.empty((B, 2 * D, 2 * H, 2 * W, Cout // 8), dtype=torch.float32, device=x.device)
+    stats = None
+    nblk = _lib.query("diqt_conv1x1_fwd_ex_stats_blocks", B, D, H, W, Cin, Cout, act, 1, 0) if want_stats else 0
+    if nblk > 0:
+        stats = torch.empty((B, nblk, 2, Cout // 8), dtype=torch.float32, device=x.device)
+        y._diqt_stats = ColStats(stats, nblk, 8 * D * H * W)
+    _lib.call("diqt_conv1x1_fwd_ex", x, packed, bpk, None, None, y, stats, B, D, H, W, Cin, Cout, act, 1, _stream())
+    return y
+
+
+def conv1x1_stats(x, weight, bias):
+    """Sampling path: conv1x1(x) whose epilogue also writes the column sums of its output (``_diqt_stats``) for the GroupNorm that
+    consumes it.  Returns None when the shape is not taken (rows per batch entry that are no multiple of 128, ...)."""
+    if not _conv1x1_ex_ok(x, weight, bias):
+        return None
+    B, D, H, W, Cin = x.shape
+    Cout = weight.shape[0]
+    nblk = _lib.query("diqt_conv1x1_fwd_ex_stats_blocks", B, D, H, W, Cin, Cout, 0, 0, 0)
+    if nblk <= 0:
+        return None
+    x = x.contiguous()
+    _chk(x, weight, bias)
+    y = torch.empty((B, D, H, W, Cout), dtype=torch.float32, device=x.device)
+    stats = torch.empty((B, nblk, 2, Cout), dtype=torch.float32, device=x.device)
+    _lib.call("diqt_conv1x1_fwd_ex", x, _packed(weight, 0), bias, None, None, y, stats, B, D, H, W, Cin, Cout, 0, 0, _stream())
+    y._diqt_stats = ColStats(stats, nblk, D * H * W)
+    return y
+
+
+def se_conv1x1_residual(h, w1, w2, x, weight, bias):
+    """Sampling path: h * sigmoid(relu(mean(h) w1^T) w2^T) + conv1x1(x) -- the tail of a ResnetBlock with an SE block and a 1x1
+    ``res_conv`` -- in two launches: the gate from the column sums h carries (the first launch of ``se_gate_residual``), then the conv,
+    whose epilogue applies the gate to h, adds, and writes the block output with its column sums (``_diqt_stats``): the residual branch
+    is never written to memory and read back.  Bit-identical to ``conv3d`` + ``se_gate_residual``.  None: shape not taken."""
+    pre = getattr(h, "_diqt_stats", None)
+    if pre is None or h.dim() != 5 or not _conv1x1_ex_ok(x, weight, bias, h, w1, w2):
+        return None
+    B, D, H, W, Cin = x.shape
+    C = weight.shape[0]
+    rows = D * H * W
+    if tuple(h.shape) != (B, D, H, W, C) or pre.rows != rows or pre.partials.shape != (B, pre.nblk, 2, C):
+        return None
+    if not (256 % min(C, 256) == 0 and (C <= 256 or C % 256 == 0)):        # the one-launch pool + MLP of _SEResidualFn
+        return None
+    nblk = _lib.query("diqt_conv1x1_fwd_ex_stats_blocks", B, D, H, W, Cin, C, 0, 0, 1)
+    if nblk <= 0:
+        return None
+    x = x.contiguous()
+    _chk(x, weight, bias, h, w1, w2)
+    dev, s = x.device, _stream()
+    Cr = w1.shape[0]
+    pooled = torch.empty((B, C), dtype=torch.float32, device=dev)
+    hidden = torch.empty((B, Cr), dtype=torch.float32, device=dev)
+    gate = torch.empty((B, C), dtype=torch.float32, device=dev)
+    _lib.call("diqt_se_pool_mlp_fwd", pre.partials, pre.nblk, rows, pooled, w1, w2, hidden, gate, B, C, Cr, s)
+    y = torch.empty((B, D, H, W, C), dtype=torch.float32, device=dev)
+    stats = torch.empty((B, nblk, 2, C), dtype=torch.float32, device=dev)
+    _lib.call("diqt_conv1x1_fwd_ex", x, _packed(weight, 0), bias, h, gate, y, stats, B, D, H, W, Cin, C, 0, 0, s)
+    y._diqt_stats = ColStats(stats, nblk, rows)
+    return y
+
+
 def conv3d_neighbours(x, weight, bias, f, residual=None, want_stats=False):
     """Inference-only 'same' conv over the f^3 sub-volume batch x[f^3, A, A, A, Cin] of one merged volume whose halo voxels come
     from the NEIGHBOUR sub-volumes (zero only outside the merged volume) -- the reference's ``boundary_pad`` + unpadded Conv3d

@@ -181,6 +181,17 @@ int diqt_conv3d_fwd_ex(const float* x, const float* packed, const float* bias, c
 int diqt_conv3d_fwd_pk(const float* x, const float* packed, size_t packed_elems, const float* bias, const float* residual, float* y,
                        float* stats, void* workspace, size_t workspace_bytes, int B, int D, int H, int W, int Cin, int Cout,
                        int kd, int kh, int kw, int pd, int ph, int pw, int epd, int eph, int epw, void* stream);
+/* 1x1x1 conv with an extended epilogue (fp32, no workspace, never split): act 0 / DIQT_ACT_MISH on acc + bias; d2s: depth-to-space by 2
+ * of the result, y[B][2D][2H][2W][Cout / 8], with `packed` / `bias` from diqt_conv1x1_pack_d2s (Cout / 8 a multiple of 64); stats: rows
+ * of column sums [B][nblk][2][C] of the final output, nblk = diqt_conv1x1_fwd_ex_stats_blocks (0: D H W is no multiple of 128); h and
+ * gate (together): y = gate[b][co] * h[row][co] + (acc + bias), always with stats.  The forms: Mish + d2s [+ stats], stats, gated;
+ * diqt_conv1x1_fwd_ex_supported = 0: use diqt_conv3d_fwd* and the separate passes.  Results equal those passes bit for bit; only the
+ * summation order of the statistics is this kernel's own (fixed, no atomics).                                                        */
+int diqt_conv1x1_fwd_ex_supported(int B, int D, int H, int W, int Cin, int Cout, int act, int d2s, int stats, int gated);
+int diqt_conv1x1_fwd_ex_stats_blocks(int B, int D, int H, int W, int Cin, int Cout, int act, int d2s, int gated);
+int diqt_conv1x1_pack_d2s(const float* w, const float* bias, float* packed, float* bias_packed, int Cout, int Cin, void* stream);
+int diqt_conv1x1_fwd_ex(const float* x, const float* packed, const float* bias, const float* h, const float* gate, float* y, float* stats,
+                        int B, int D, int H, int W, int Cin, int Cout, int act, int d2s, void* stream);
 int diqt_conv3d_fwd_stats_blocks_pk(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw,
                                     int epd, int eph, int epw, size_t packed_elems);
 size_t diqt_conv3d_fwd_workspace_bytes_pk(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw,
