@@ -343,7 +343,7 @@ __global__ __launch_bounds__(256) void msssim_final_kernel(const double* __restr
 // floats.  Every element of `patches` is read exactly once per launch.
 // The window walk of one output voxel (d, h, x) over one sample's rows `ps`: num = sum(w c(y)), den = sum(w) over the covering kept
 // windows in candidate order, with c the caller's clamp (the identity for the blend).  Shared by volume_blend_kernel and
-// volume_joint_step_kernel, so the two fuse windows with the same terms in the same order.
+// the joint kernels (joint_fuse), so they fuse windows with the same terms in the same order.
 struct Cover { int lo0, hi0, lo1, hi1, lo2, hi2; };
 // covering lattice indices of coordinate c: 0 <= g < G and 0 <= c - g * stride < P
 __device__ __forceinline__ Cover covering(int d, int h, int x, int P, int stride, int G0, int G1, int G2) {
@@ -397,18 +397,34 @@ __device__ __forceinline__ void window_walk(const float* __restrict__ ps, const 
     }
 }
 
+// The output voxel of a thread of the (64, 4) block on the grid (ceil(W / 64), ceil(H / 4), D): x per lane, h and d wave-uniform, v its
+// index in a [D][H][W] volume (= the Philox `lin` of channel 0), inside = false for the lanes and rows past the volume.
+struct Voxel { int x, h, d; size_t v; bool inside; };
+__device__ __forceinline__ Voxel block_voxel(int H, int W) {
+    const int x = blockIdx.x * 64 + threadIdx.x;
+    const int h = __builtin_amdgcn_readfirstlane(blockIdx.y * 4 + threadIdx.y), d = blockIdx.z;
+    return Voxel{x, h, d, ((size_t)d * H + h) * W + x, h < H && x < W};
+}
+// The head of every kernel that walks windows: taps -> LDS tp[P] when this launch walks (`walks` is uniform over the launch; a launch
+// that does not -- an initial state -- gets no LDS and reads no taps), a barrier BEFORE any thread may leave, then the thread's voxel.
+__device__ __forceinline__ Voxel walk_prologue(float* tp, const float* __restrict__ taps, int P, bool walks, int H, int W) {
+    if (walks) {
+        for (int e = threadIdx.y * 64 + threadIdx.x; e < P; e += 256) tp[e] = taps[e];
+        __syncthreads();
+    }
+    return block_voxel(H, W);
+}
+
 __global__ __launch_bounds__(256) void volume_blend_kernel(const float* __restrict__ patches, const int* __restrict__ slot,
                                                            const float* __restrict__ taps, const float* __restrict__ vol,
                                                            float* __restrict__ out_mean, float* __restrict__ out_std, int S, int N,
                                                            int D, int H, int W, int P, int stride, int G0, int G1, int G2, float mean,
                                                            float stdv, float min_val, float fill) {
     extern __shared__ float tp[];                      // [P]
-    for (int e = threadIdx.y * 64 + threadIdx.x; e < P; e += 256) tp[e] = taps[e];
-    __syncthreads();
-    const int x = blockIdx.x * 64 + threadIdx.x;
-    const int h = __builtin_amdgcn_readfirstlane(blockIdx.y * 4 + threadIdx.y), d = blockIdx.z;
-    if (h >= H || x >= W) return;
-    const size_t v = ((size_t)d * H + h) * W + x;
+    const Voxel p = walk_prologue(tp, taps, P, true, H, W);
+    if (!p.inside) return;
+    const int x = p.x, h = p.h, d = p.d;
+    const size_t v = p.v;
     float om, os = 0.f;
     if (vol && (vol[v] - mean) / stdv == min_val) {
         om = min_val;
@@ -490,10 +506,8 @@ __global__ __launch_bounds__(256) void anchored_noise_kernel(const int* __restri
 // One reverse step of the VOLUME (MultiDiffusion, Bar-Tal et al. 2023): y[N][P][P][P] holds the kept windows' x0 predictions of this
 // step; per output voxel x0 = sum(w c(y)) / sum(w) over the covering kept windows -- volume_blend_kernel's walk for S = 1 with
 // ddpm_step_kernel's clamp c on every term -- and x_next = kx x_t + k0 x0 + kn n with n the anchored normal of channel 0 at (seed, d, h,
-// x, draw, sample), computed in the thread (no noise tensor, no blended x0 tensor, no separate step launch).  A voxel no kept window
-// covers keeps x_t (nothing ever gathers it) and gets x0_out = 0.  x_t == NULL is the initial state: x_next = the anchored normal of
-// `draw` everywhere, equal to anchored_noise_kernel's bit for bit (same Philox call, same philox_normal).  x_next may alias x_t: every
-// thread reads its own voxel, then writes it.
+// x, draw, sample), computed in the thread (no noise tensor, no blended x0 tensor, no separate step launch).  The multistep and Heun
+// samplers put other updates behind the same fuse; volume_joint_linear_kernel and volume_joint_heun_kernel say which.
 // ddpm_step_kernel's `ka * x_t + kb * x0 + kn * noise` as the compiler contracts it there: the x_t product is fused into the rounded
 // x0 product, the rounded noise product is added last.  Spelled out (and kept from further contraction) because the same source
 // expression contracted the other way round in this kernel, one ulp away from the independent-window chain.
@@ -507,73 +521,21 @@ struct StepClamp {
     int mode;
     __device__ __forceinline__ float operator()(float y) const { return mode == 0 ? fmaxf(y, lo) : fminf(fmaxf(y, lo), hi); }
 };
-__global__ __launch_bounds__(256) void volume_joint_step_kernel(const float* __restrict__ y, const int* __restrict__ slot,
-                                                                const float* __restrict__ taps, const float* x_t, float* x_next,
-                                                                float* __restrict__ x0_out, int N, int D, int H, int W, int P,
-                                                                int stride, int G0, int G1, int G2, float kx, float k0, float kn,
-                                                                float lo, float hi, int clamp_mode, unsigned key0, unsigned key1,
-                                                                unsigned draw, unsigned sample) {
-    extern __shared__ float tp[];                      // [P]
-    if (x_t) {                                         // uniform over the launch
-        for (int e = threadIdx.y * 64 + threadIdx.x; e < P; e += 256) tp[e] = taps[e];
-        __syncthreads();
-    }
-    const int x = blockIdx.x * 64 + threadIdx.x;
-    const int h = __builtin_amdgcn_readfirstlane(blockIdx.y * 4 + threadIdx.y), d = blockIdx.z;
-    if (h >= H || x >= W) return;
-    const size_t v = ((size_t)d * H + h) * W + x;      // = lin of channel 0
-    if (!x_t) {
-        x_next[v] = philox_normal(philox4x32_10((unsigned)v, (unsigned)((unsigned long long)v >> 32), draw, sample, key0, key1));
-        return;
-    }
+// The fuse of the joint kernels at voxel p, over the covering kept windows with c the step clamp: covered() says whether there is one,
+// x0() = sum(w c(y)) / sum(w) is then the fused prediction.  The quotient is taken where the caller asks for it -- after it has issued
+// its own loads, so that the division runs under their latency.
+struct Fused {
     float num, den;
-    window_walk(y, slot, taps, tp, N, P, stride, G1, G2, d, h, x, covering(d, h, x, P, stride, G0, G1, G2),
-                StepClamp{lo, hi, clamp_mode}, num, den);
-    const float xt = x_t[v];
-    if (den == 0.f) {
-        x_next[v] = xt;
-        if (x0_out) x0_out[v] = 0.f;
-        return;
-    }
-    const float x0 = num / den;
-    float n = 0.f;
-    if (kn != 0.f) n = philox_normal(philox4x32_10((unsigned)v, (unsigned)((unsigned long long)v >> 32), draw, sample, key0, key1));
-    if (x0_out) x0_out[v] = x0;
-    x_next[v] = sampler_update(kx, xt, k0, x0, kn, n);
+    __device__ __forceinline__ bool covered() const { return den != 0.f; }
+    __device__ __forceinline__ float x0() const { return num / den; }
+};
+__device__ __forceinline__ Fused joint_fuse(const float* __restrict__ y, const int* __restrict__ slot, const float* __restrict__ taps,
+                                            const float* tp, int N, int P, int stride, int G0, int G1, int G2, const Voxel& p,
+                                            StepClamp c) {
+    Fused f;
+    window_walk(y, slot, taps, tp, N, P, stride, G1, G2, p.d, p.h, p.x, covering(p.d, p.h, p.x, P, stride, G0, G1, G2), c, f.num, f.den);
+    return f;
 }
-
-// One step of a second-order MULTISTEP chain (DPM-Solver++ 2M) on the same state: the third operand of the update is the fused x0
-// of the previous step, x_next = kx x_t + k0 x0 + kp x0_prev, not a normal -- no Philox, no seed.  The walk, the clamp and
-// sampler_update are the step kernel's own, so with kp = 0 the two kernels return the same bits, and at stride = patch the chain is
-// ddpm_step_kernel's with the previous x0 as its third operand.  x0_prev == NULL stands for zeros (step 0).  x_next may alias x_t and
-// x0_out may alias x0_prev (no __restrict__ on the four): every thread reads its own voxel of both, then writes it.
-__global__ __launch_bounds__(256) void volume_joint_multistep_kernel(const float* __restrict__ y, const int* __restrict__ slot,
-                                                                     const float* __restrict__ taps, const float* x_t,
-                                                                     const float* x0_prev, float* x_next, float* x0_out, int N, int D,
-                                                                     int H, int W, int P, int stride, int G0, int G1, int G2, float kx,
-                                                                     float k0, float kp, float lo, float hi, int clamp_mode) {
-    extern __shared__ float tp[];                      // [P]
-    for (int e = threadIdx.y * 64 + threadIdx.x; e < P; e += 256) tp[e] = taps[e];
-    __syncthreads();
-    const int x = blockIdx.x * 64 + threadIdx.x;
-    const int h = __builtin_amdgcn_readfirstlane(blockIdx.y * 4 + threadIdx.y), d = blockIdx.z;
-    if (h >= H || x >= W) return;
-    const size_t v = ((size_t)d * H + h) * W + x;
-    float num, den;
-    window_walk(y, slot, taps, tp, N, P, stride, G1, G2, d, h, x, covering(d, h, x, P, stride, G0, G1, G2),
-                StepClamp{lo, hi, clamp_mode}, num, den);
-    const float xt = x_t[v];
-    if (den == 0.f) {
-        x_next[v] = xt;
-        x0_out[v] = 0.f;
-        return;
-    }
-    const float x0 = num / den;
-    const float prev = x0_prev ? x0_prev[v] : 0.f;
-    x0_out[v] = x0;
-    x_next[v] = sampler_update(kx, xt, k0, x0, kp, prev);
-}
-
 // DPM-Solver++ 2M in sigma space (the EDM family; ElucidatedImagen.dpmpp2m_coefficients), ODE (kn == 0) and midpoint SDE (kn != 0):
 // x_next = kx x + k0 D_i + kp D_{i-1} + kn n.  The first three terms are sampler_update's, in its order; the rounded kn n product is
 // added last, and not at all when kn == 0 (no operand read, no Philox call).  ONE definition for the per-window step and the joint
@@ -605,46 +567,54 @@ __global__ __launch_bounds__(256) void multistep_sde_step_kernel(const float* x,
     const float n = cn != 0.f ? noise[v] : 0.f;
     x_next[v] = sampler_update_sde(kx[b], x[v], k0[b], x0[v], kp[b], prev, cn, n);
 }
-// volume_joint_multistep_kernel plus the anchored normal of (seed, draw, sample) at the voxel, channel 0 (the step kernel's own Philox
-// call and philox_normal; none when kn == 0).  x_t == NULL is the initial state, x_next = kn n(draw) at EVERY voxel as one rounded
-// product: the initial image sigma0 n as the per-window sampler stores it.  Uncovered voxels keep x_t and get x0_out = 0.  x_next may
-// alias x_t and x0_out may alias x0_prev (no __restrict__ on the four).
-__global__ __launch_bounds__(256) void volume_joint_multistep_sde_kernel(const float* __restrict__ y, const int* __restrict__ slot,
-                                                                         const float* __restrict__ taps, const float* x_t,
-                                                                         const float* x0_prev, float* x_next, float* x0_out, int N,
-                                                                         int D, int H, int W, int P, int stride, int G0, int G1, int G2,
-                                                                         float kx, float k0, float kp, float kn, float lo, float hi,
-                                                                         int clamp_mode, unsigned key0, unsigned key1, unsigned draw,
-                                                                         unsigned sample) {
+
+// ONE kernel for the three linear updates of the joint state (diqt_volume_joint_step, _multistep and _multistep_sde): the fuse, then
+// per covered voxel, with prev = x0_prev[v] (0 for x0_prev == NULL) and n the anchored normal of (seed, draw, sample) at the voxel,
+// channel 0 (anchored_noise_kernel's Philox call and philox_normal; n = 0 and no call when kn == 0),
+//   third_is_normal (the first-order step)   x_next = sampler_update(kx, xt, k0, x0, kn, n): the kn n product is added also when it is 0;
+//   otherwise (the multistep forms)          x_next = sampler_update_sde(kx, xt, k0, x0, kp, prev, kn, n): the history term is
+//                                            sampler_update's third operand and kn n a fourth term, added last and only when kn != 0.
+// `third_is_normal` is uniform over the launch.  The identities the entries rely on, each exact in IEEE arithmetic:
+//   * the 2M chain of the VP family (diqt_volume_joint_multistep) is the second form with kn = 0: nothing follows the history term;
+//   * the second form with kp = 0 and no history is NOT the first: it is (u + +0) + kn n, and where u and kn n are both -0 that is +0
+//     while the first form's u + kn n is -0 -- hence the flag, not a fold (tests/test_gpu_volume_joint_bits.py plants such voxels);
+//   * x_t == NULL is the initial state, x_next = kn n(draw) at EVERY voxel as one rounded product -- sigma0 n as the per-window sampler
+//     stores it; diqt_volume_joint_step asks for it with kn = 1, and 1 n is n bit for bit: anchored_noise_kernel's field.
+// A voxel no kept window covers keeps x_t (nothing ever gathers it) and gets x0_out = 0.  x0_out == NULL (the first form only; the
+// entries of the others require it): the fused x0 is not stored.  x_next may alias x_t and x0_out may alias x0_prev (no __restrict__
+// on the four): every thread reads its own voxel of both, then writes it.  At stride = patch the first form is ddpm_step_kernel's
+// chain and the second the per-window loop above, bit for bit.
+__global__ __launch_bounds__(256) void volume_joint_linear_kernel(const float* __restrict__ y, const int* __restrict__ slot,
+                                                                  const float* __restrict__ taps, const float* x_t,
+                                                                  const float* x0_prev, float* x_next, float* x0_out, int N, int D,
+                                                                  int H, int W, int P, int stride, int G0, int G1, int G2, float kx,
+                                                                  float k0, float kp, float kn, float lo, float hi, int clamp_mode,
+                                                                  int third_is_normal, unsigned key0, unsigned key1, unsigned draw,
+                                                                  unsigned sample) {
     extern __shared__ float tp[];                      // [P]
-    if (x_t) {                                         // uniform over the launch
-        for (int e = threadIdx.y * 64 + threadIdx.x; e < P; e += 256) tp[e] = taps[e];
-        __syncthreads();
-    }
-    const int x = blockIdx.x * 64 + threadIdx.x;
-    const int h = __builtin_amdgcn_readfirstlane(blockIdx.y * 4 + threadIdx.y), d = blockIdx.z;
-    if (h >= H || x >= W) return;
-    const size_t v = ((size_t)d * H + h) * W + x;      // = lin of channel 0
+    const Voxel p = walk_prologue(tp, taps, P, x_t != nullptr, H, W);
+    if (!p.inside) return;
+    const size_t v = p.v;
     const unsigned v0 = (unsigned)v, v1 = (unsigned)((unsigned long long)v >> 32);
     if (!x_t) {
         x_next[v] = kn * philox_normal(philox4x32_10(v0, v1, draw, sample, key0, key1));
         return;
     }
-    float num, den;
-    window_walk(y, slot, taps, tp, N, P, stride, G1, G2, d, h, x, covering(d, h, x, P, stride, G0, G1, G2),
-                StepClamp{lo, hi, clamp_mode}, num, den);
+    const Fused f = joint_fuse(y, slot, taps, tp, N, P, stride, G0, G1, G2, p, StepClamp{lo, hi, clamp_mode});
     const float xt = x_t[v];
-    if (den == 0.f) {
+    if (!f.covered()) {
         x_next[v] = xt;
-        x0_out[v] = 0.f;
+        if (x0_out) x0_out[v] = 0.f;
         return;
     }
-    const float x0 = num / den;
+    const float x0 = f.x0();
     const float prev = x0_prev ? x0_prev[v] : 0.f;
     float n = 0.f;
     if (kn != 0.f) n = philox_normal(philox4x32_10(v0, v1, draw, sample, key0, key1));
-    x0_out[v] = x0;
-    x_next[v] = sampler_update_sde(kx, xt, k0, x0, kp, prev, kn, n);
+    const float r = third_is_normal ? sampler_update(kx, xt, k0, x0, kn, n) : sampler_update_sde(kx, xt, k0, x0, kp, prev, kn, n);
+    // both stores after the last use of a load: a store counts in vmcnt on gfx950, so a wait for x_t behind a store waits for the store too
+    if (x0_out) x0_out[v] = x0;
+    x_next[v] = r;
 }
 
 // The stochastic Heun sampler of the EDM family (elucidated_imagen.py:382-532) on the same state: a churn, a predictor and a corrector
@@ -657,7 +627,7 @@ __global__ __launch_bounds__(256) void volume_joint_multistep_sde_kernel(const f
 //                                  (1 + r/2, -r/2, r2, -r2); then the next step's churn xh = x + kc n(draw) (no Philox call when
 //                                  kc == 0) and x0 = x0b.
 // A voxel no kept window covers: phase 1 writes xn = xh and x0 = 0, phase 2 leaves xh and writes x0 = 0 (nothing ever gathers it).
-// The walk, the clamp and the normals are the step kernel's own.  Every thread reads only its own voxel of xh / xn / x0, then writes
+// The prologue, the fuse and the normals are the linear kernel's own.  Every thread reads only its own voxel of xh / xn / x0, then writes
 // it: all three are updated in place (no __restrict__ on them).
 // axpby3_kernel's `v = k0 a; v += k1 b; v += k2 c` as the compiler contracts it there: the first product is rounded, every later one
 // is fused into the running sum.  Spelled out (and kept from further contraction) so that at stride = patch the joint chain is
@@ -674,14 +644,9 @@ __global__ __launch_bounds__(256) void volume_joint_heun_kernel(const float* __r
                                                                 int clamp_mode, unsigned key0, unsigned key1, unsigned draw,
                                                                 unsigned sample) {
     extern __shared__ float tp[];                      // [P]
-    if (phase != 0) {                                  // uniform over the launch
-        for (int e = threadIdx.y * 64 + threadIdx.x; e < P; e += 256) tp[e] = taps[e];
-        __syncthreads();
-    }
-    const int x = blockIdx.x * 64 + threadIdx.x;
-    const int h = __builtin_amdgcn_readfirstlane(blockIdx.y * 4 + threadIdx.y), d_ = blockIdx.z;
-    if (h >= H || x >= W) return;
-    const size_t v = ((size_t)d_ * H + h) * W + x;     // = lin of channel 0
+    const Voxel p = walk_prologue(tp, taps, P, phase != 0, H, W);
+    if (!p.inside) return;
+    const size_t v = p.v;
     const unsigned v0 = (unsigned)v, v1 = (unsigned)((unsigned long long)v >> 32);
     if (phase == 0) {
         float r = axpby_update(a, philox_normal(philox4x32_10(v0, v1, draw, sample, key0, key1)), 0.f, 0.f);
@@ -689,26 +654,24 @@ __global__ __launch_bounds__(256) void volume_joint_heun_kernel(const float* __r
         xh[v] = r;
         return;
     }
-    float num, den;
-    window_walk(y, slot, taps, tp, N, P, stride, G1, G2, d_, h, x, covering(d_, h, x, P, stride, G0, G1, G2),
-                StepClamp{lo, hi, clamp_mode}, num, den);
+    const Fused f = joint_fuse(y, slot, taps, tp, N, P, stride, G0, G1, G2, p, StepClamp{lo, hi, clamp_mode});
     if (phase == 1) {
         const float h_ = xh[v];
-        if (den == 0.f) {
+        if (!f.covered()) {
             xn[v] = h_;
             x0v[v] = 0.f;
             return;
         }
-        const float x0 = num / den;
+        const float x0 = f.x0();
         x0v[v] = x0;
         xn[v] = axpby_update(a, h_, b, x0);
         return;
     }
-    if (den == 0.f) {
+    if (!f.covered()) {
         x0v[v] = 0.f;
         return;
     }
-    const float x0b = num / den;
+    const float x0b = f.x0();
     const float t = fmaf(c, xn[v], axpby_update(a, xh[v], b, x0v[v]));
     float r = fmaf(d, x0b, t);                         // axpby3(tmp, out2, 1, d): 1 * tmp is tmp
     if (kc != 0.f) r = fmaf(kc, philox_normal(philox4x32_10(v0, v1, draw, sample, key0, key1)), r);
@@ -724,15 +687,14 @@ __global__ __launch_bounds__(256) void volume_joint_finish_kernel(const float* _
                                                                   float* __restrict__ m2_io, float* __restrict__ out_std, int s, int S,
                                                                   int D, int H, int W, int P, int stride, int G0, int G1, int G2,
                                                                   float mean, float stdv, float min_val, float fill) {
-    const int x = blockIdx.x * 64 + threadIdx.x;
-    const int h = __builtin_amdgcn_readfirstlane(blockIdx.y * 4 + threadIdx.y), d = blockIdx.z;
-    if (h >= H || x >= W) return;
-    const size_t v = ((size_t)d * H + h) * W + x;
+    const Voxel p = block_voxel(H, W);
+    if (!p.inside) return;
+    const size_t v = p.v;
     float r;
     if (vol && (vol[v] - mean) / stdv == min_val) {
         r = min_val;
     } else {
-        const Cover cv = covering(d, h, x, P, stride, G0, G1, G2);
+        const Cover cv = covering(p.d, p.h, p.x, P, stride, G0, G1, G2);
         bool covered = false;
         for (int g0 = cv.lo0; g0 <= cv.hi0 && !covered; ++g0)
             for (int g1 = cv.lo1; g1 <= cv.hi1 && !covered; ++g1) {
@@ -986,43 +948,56 @@ static int joint_lattice_ok(const char* who, int D, int H, int W, int P, int str
     return DIQT_OK;
 }
 
+// What the four launches on the joint state share: the checks in the order every entry has made them -- the output volume, the shape,
+// the grid limits, and for a launch that walks windows (an initial state looks at none of the window arguments) the window pointers
+// (`window_ptrs`: the entry's own list), N, the lattice and the clamp mode -- then the grid of (64, 4) blocks and the LDS for the taps.
+struct JointGrid { dim3 grid; size_t lds; };
+static int joint_launch_plan(const char* who, const void* out, bool walks, bool window_ptrs, int N, int D, int H, int W, int P, int stride,
+                             int G0, int G1, int G2, int clamp_mode, JointGrid& g) {
+    DIQT_REQUIRE(out, DIQT_E_ALIGN, "%s: null pointer", who);
+    DIQT_REQUIRE(D > 0 && H > 0 && W > 0, DIQT_E_SHAPE, "%s: bad shape", who);
+    DIQT_REQUIRE(D <= 65535 && (H + 3) / 4 <= 65535, DIQT_E_SHAPE, "%s: more than 65535 planes / row groups", who);
+    if (walks) {
+        DIQT_REQUIRE(window_ptrs, DIQT_E_ALIGN, "%s: null pointer", who);
+        DIQT_REQUIRE(N >= 0, DIQT_E_SHAPE, "%s: windows %d", who, N);
+        int rc = joint_lattice_ok(who, D, H, W, P, stride, G0, G1, G2);
+        if (rc) return rc;
+        DIQT_REQUIRE(clamp_mode == 0 || clamp_mode == 1, DIQT_E_UNSUPPORTED, "%s: clamp_mode %d (0 = min, 1 = box)", who, clamp_mode);
+    }
+    g = JointGrid{dim3((W + 63) / 64, (H + 3) / 4, D), walks ? (size_t)P * sizeof(float) : 0};
+    return DIQT_OK;
+}
+// volume_joint_linear_kernel behind its three entries; `third_is_normal` and the operands an entry does not have (x0_prev, kp, kn, the
+// noise key) are the entry's to fill in.
+static int joint_linear_launch(const char* who, bool window_ptrs, const float* y, const int* slot, const float* taps, const float* x_t,
+                               const float* x0_prev, float* x_next, float* x0_out, int N, int D, int H, int W, int P, int stride, int G0,
+                               int G1, int G2, float kx, float k0, float kp, float kn, float lo, float hi, int clamp_mode,
+                               int third_is_normal, unsigned long long seed, unsigned draw, unsigned sample, void* stream) {
+    JointGrid g;
+    int rc = joint_launch_plan(who, x_next, x_t != nullptr, window_ptrs, N, D, H, W, P, stride, G0, G1, G2, clamp_mode, g);
+    if (rc) return rc;
+    hipLaunchKernelGGL(volume_joint_linear_kernel, g.grid, dim3(64, 4), g.lds, STREAM, y, slot, taps, x_t, x0_prev, x_next, x0_out, N, D,
+                       H, W, P, stride, G0, G1, G2, kx, k0, kp, kn, lo, hi, clamp_mode, third_is_normal, (unsigned)seed,
+                       (unsigned)(seed >> 32), draw, sample);
+    return check_launch(who);
+}
+
 extern "C" int diqt_volume_joint_step(const float* y, const int* slot, const float* taps, const float* x_t, float* x_next, float* x0_out,
                                       int N, int D, int H, int W, int P, int stride, int G0, int G1, int G2, float kx, float k0, float kn,
                                       float lo, float hi, int clamp_mode, unsigned long long seed, unsigned draw, unsigned sample,
                                       void* stream) {
-    DIQT_REQUIRE(x_next, DIQT_E_ALIGN, "volume_joint_step: null pointer");
-    DIQT_REQUIRE(D > 0 && H > 0 && W > 0, DIQT_E_SHAPE, "volume_joint_step: bad shape");
-    DIQT_REQUIRE(D <= 65535 && (H + 3) / 4 <= 65535, DIQT_E_SHAPE, "volume_joint_step: more than 65535 planes / row groups");
-    size_t lds = 0;
-    if (x_t) {                                          // the initial state (x_t == NULL) ignores the window arguments
-        DIQT_REQUIRE(slot && taps && (y || N == 0), DIQT_E_ALIGN, "volume_joint_step: null pointer");
-        DIQT_REQUIRE(N >= 0, DIQT_E_SHAPE, "volume_joint_step: windows %d", N);
-        int rc = joint_lattice_ok("volume_joint_step", D, H, W, P, stride, G0, G1, G2);
-        if (rc) return rc;
-        DIQT_REQUIRE(clamp_mode == 0 || clamp_mode == 1, DIQT_E_UNSUPPORTED, "volume_joint_step: clamp_mode %d (0 = min, 1 = box)",
-                     clamp_mode);
-        lds = (size_t)P * sizeof(float);
-    }
-    hipLaunchKernelGGL(volume_joint_step_kernel, dim3((W + 63) / 64, (H + 3) / 4, D), dim3(64, 4), lds, STREAM, y, slot, taps, x_t,
-                       x_next, x0_out, N, D, H, W, P, stride, G0, G1, G2, kx, k0, kn, lo, hi, clamp_mode, (unsigned)seed,
-                       (unsigned)(seed >> 32), draw, sample);
-    return check_launch("volume_joint_step");
+    // the initial state (x_t == NULL) is the plain normal: 1 n
+    return joint_linear_launch("volume_joint_step", slot && taps && (y || N == 0), y, slot, taps, x_t, nullptr, x_next, x0_out, N, D, H, W,
+                               P, stride, G0, G1, G2, kx, k0, 0.f, x_t ? kn : 1.f, lo, hi, clamp_mode, 1, seed, draw, sample, stream);
 }
 
 extern "C" int diqt_volume_joint_multistep(const float* y, const int* slot, const float* taps, const float* x_t, const float* x0_prev,
                                            float* x_next, float* x0_out, int N, int D, int H, int W, int P, int stride, int G0, int G1,
                                            int G2, float kx, float k0, float kp, float lo, float hi, int clamp_mode, void* stream) {
+    // no initial state here, and every pointer is looked at before the shape
     DIQT_REQUIRE(x_t && x_next && x0_out && slot && taps && (y || N == 0), DIQT_E_ALIGN, "volume_joint_multistep: null pointer");
-    DIQT_REQUIRE(D > 0 && H > 0 && W > 0, DIQT_E_SHAPE, "volume_joint_multistep: bad shape");
-    DIQT_REQUIRE(D <= 65535 && (H + 3) / 4 <= 65535, DIQT_E_SHAPE, "volume_joint_multistep: more than 65535 planes / row groups");
-    DIQT_REQUIRE(N >= 0, DIQT_E_SHAPE, "volume_joint_multistep: windows %d", N);
-    int rc = joint_lattice_ok("volume_joint_multistep", D, H, W, P, stride, G0, G1, G2);
-    if (rc) return rc;
-    DIQT_REQUIRE(clamp_mode == 0 || clamp_mode == 1, DIQT_E_UNSUPPORTED, "volume_joint_multistep: clamp_mode %d (0 = min, 1 = box)",
-                 clamp_mode);
-    hipLaunchKernelGGL(volume_joint_multistep_kernel, dim3((W + 63) / 64, (H + 3) / 4, D), dim3(64, 4), (size_t)P * sizeof(float), STREAM,
-                       y, slot, taps, x_t, x0_prev, x_next, x0_out, N, D, H, W, P, stride, G0, G1, G2, kx, k0, kp, lo, hi, clamp_mode);
-    return check_launch("volume_joint_multistep");
+    return joint_linear_launch("volume_joint_multistep", true, y, slot, taps, x_t, x0_prev, x_next, x0_out, N, D, H, W, P, stride, G0, G1,
+                               G2, kx, k0, kp, 0.f, lo, hi, clamp_mode, 0, 0, 0, 0, stream);
 }
 
 extern "C" int diqt_multistep_sde_step(const float* x, const float* x0, const float* x0_prev, const float* noise, const float* kx,
@@ -1041,23 +1016,8 @@ extern "C" int diqt_volume_joint_multistep_sde(const float* y, const int* slot, 
                                                float* x_next, float* x0_out, int N, int D, int H, int W, int P, int stride, int G0,
                                                int G1, int G2, float kx, float k0, float kp, float kn, float lo, float hi,
                                                int clamp_mode, unsigned long long seed, unsigned draw, unsigned sample, void* stream) {
-    DIQT_REQUIRE(x_next, DIQT_E_ALIGN, "volume_joint_multistep_sde: null pointer");
-    DIQT_REQUIRE(D > 0 && H > 0 && W > 0, DIQT_E_SHAPE, "volume_joint_multistep_sde: bad shape");
-    DIQT_REQUIRE(D <= 65535 && (H + 3) / 4 <= 65535, DIQT_E_SHAPE, "volume_joint_multistep_sde: more than 65535 planes / row groups");
-    size_t lds = 0;
-    if (x_t) {                                          // the initial state (x_t == NULL) ignores the window arguments
-        DIQT_REQUIRE(x0_out && slot && taps && (y || N == 0), DIQT_E_ALIGN, "volume_joint_multistep_sde: null pointer");
-        DIQT_REQUIRE(N >= 0, DIQT_E_SHAPE, "volume_joint_multistep_sde: windows %d", N);
-        int rc = joint_lattice_ok("volume_joint_multistep_sde", D, H, W, P, stride, G0, G1, G2);
-        if (rc) return rc;
-        DIQT_REQUIRE(clamp_mode == 0 || clamp_mode == 1, DIQT_E_UNSUPPORTED, "volume_joint_multistep_sde: clamp_mode %d (0 = min, 1 = box)",
-                     clamp_mode);
-        lds = (size_t)P * sizeof(float);
-    }
-    hipLaunchKernelGGL(volume_joint_multistep_sde_kernel, dim3((W + 63) / 64, (H + 3) / 4, D), dim3(64, 4), lds, STREAM, y, slot, taps,
-                       x_t, x0_prev, x_next, x0_out, N, D, H, W, P, stride, G0, G1, G2, kx, k0, kp, kn, lo, hi, clamp_mode,
-                       (unsigned)seed, (unsigned)(seed >> 32), draw, sample);
-    return check_launch("volume_joint_multistep_sde");
+    return joint_linear_launch("volume_joint_multistep_sde", x0_out && slot && taps && (y || N == 0), y, slot, taps, x_t, x0_prev, x_next,
+                               x0_out, N, D, H, W, P, stride, G0, G1, G2, kx, k0, kp, kn, lo, hi, clamp_mode, 0, seed, draw, sample, stream);
 }
 
 extern "C" int diqt_volume_joint_heun(const float* y, const int* slot, const float* taps, float* xh, float* xn, float* x0, int phase, int N,
@@ -1066,24 +1026,13 @@ extern "C" int diqt_volume_joint_heun(const float* y, const int* slot, const flo
                                       unsigned sample, void* stream) {
     DIQT_REQUIRE(phase >= 0 && phase <= 2, DIQT_E_UNSUPPORTED, "volume_joint_heun: phase %d (0 = init, 1 = predictor, 2 = corrector)",
                  phase);
-    DIQT_REQUIRE(xh, DIQT_E_ALIGN, "volume_joint_heun: null pointer");
-    DIQT_REQUIRE(D > 0 && H > 0 && W > 0, DIQT_E_SHAPE, "volume_joint_heun: bad shape");
-    DIQT_REQUIRE(D <= 65535 && (H + 3) / 4 <= 65535, DIQT_E_SHAPE, "volume_joint_heun: more than 65535 planes / row groups");
-    size_t lds = 0;
-    if (phase == 0) {                                   // the initial state ignores the window arguments; it reads draw and draw + 1
-        DIQT_REQUIRE(draw != 0xffffffffu, DIQT_E_SHAPE, "volume_joint_heun: phase 0 uses draw and draw + 1");
-    } else {
-        DIQT_REQUIRE(xn && x0 && slot && taps && (y || N == 0), DIQT_E_ALIGN, "volume_joint_heun: null pointer");
-        DIQT_REQUIRE(N >= 0, DIQT_E_SHAPE, "volume_joint_heun: windows %d", N);
-        int rc = joint_lattice_ok("volume_joint_heun", D, H, W, P, stride, G0, G1, G2);
-        if (rc) return rc;
-        DIQT_REQUIRE(clamp_mode == 0 || clamp_mode == 1, DIQT_E_UNSUPPORTED, "volume_joint_heun: clamp_mode %d (0 = min, 1 = box)",
-                     clamp_mode);
-        lds = (size_t)P * sizeof(float);
-    }
-    hipLaunchKernelGGL(volume_joint_heun_kernel, dim3((W + 63) / 64, (H + 3) / 4, D), dim3(64, 4), lds, STREAM, y, slot, taps, xh, xn, x0,
-                       phase, N, D, H, W, P, stride, G0, G1, G2, a, b, c, d, kc, lo, hi, clamp_mode, (unsigned)seed,
-                       (unsigned)(seed >> 32), draw, sample);
+    JointGrid g;
+    int rc = joint_launch_plan("volume_joint_heun", xh, phase != 0, xn && x0 && slot && taps && (y || N == 0), N, D, H, W, P, stride, G0,
+                               G1, G2, clamp_mode, g);
+    if (rc) return rc;
+    DIQT_REQUIRE(phase != 0 || draw != 0xffffffffu, DIQT_E_SHAPE, "volume_joint_heun: phase 0 uses draw and draw + 1");
+    hipLaunchKernelGGL(volume_joint_heun_kernel, g.grid, dim3(64, 4), g.lds, STREAM, y, slot, taps, xh, xn, x0, phase, N, D, H, W, P, stride,
+                       G0, G1, G2, a, b, c, d, kc, lo, hi, clamp_mode, (unsigned)seed, (unsigned)(seed >> 32), draw, sample);
     return check_launch("volume_joint_heun");
 }
 

@@ -335,8 +335,7 @@ class VolumeInference:
         vol = lowres_raw.float().contiguous()
         P, S, den = self.patch, self.samples, self._protocol(self.sample_fn)
         win = _Windows(self, vol)
-        chain = self._heun_chain if den.heun else self._sigma_multistep_chain if den.sigma_space else \
-            self._multistep_chain if den.multistep else self._step_chain
+        chain = self._heun_chain if den.heun else self._linear_chain
         y = torch.empty((win.N, P, P, P), dtype=torch.float32, device=win.device)          # reused by every step of every sample
         # and so is the fused x0 volume of the first-order and multistep chains; the Heun chain makes its three volumes per sample
         win.x0_vol = torch.empty_like(vol) if (den.self_cond or den.multistep) and not den.heun else None
@@ -351,48 +350,37 @@ class VolumeInference:
                                                               win.min_val, win.fill, s, S, mean_io, m2_io, want_std)
         return mean_io, out_std
 
-    def _step_chain(self, den, win, evaluate, y, s):
-        """Sample ``s`` of a first-order chain: the state ``x`` starts as draw 0 of the anchored field; per step ONE
-        ``ops.volume_joint_step`` launch fuses the predictions in ``y`` per voxel, takes the sampler step with draw ``i + 1`` and writes
-        the next state in place (and the fused x0 ``win.x0_vol``, which self-conditioning gathers at the next step).  Returns ``x``."""
-        x = ops.volume_joint_init(win.shape, self.seed, sample=s, device=win.device)        # draw 0
-        for i in range(den.num_steps):
-            evaluate(x, win.x0_vol if den.self_cond and i > 0 else None, lambda xw, lw, sc, o: den.x0(xw, lw, i, self_cond=sc))
-            kx, k0, kn = den.coefs[i]
-            ops.volume_joint_step(y, win.slot, win.taps, x, kx, k0, kn, *den.clamp, self.overlap, self.seed, draw=i + 1, sample=s,
-                                  out=x, x0_out=win.x0_vol)
-        return x
+    def _window_x0(self, den, win, s, i, edm=False, **kw):
+        """``x0(xw, lw, sc, origins)`` as ``evaluate`` calls it: the denoiser's x0 prediction of step ``i``.  An EDM denoiser (``edm``)
+        also takes ``lowres_noise=``: draw 0 of the field at the batch's windows when the chain's own draws start at 1 (recomputed per
+        evaluation, nothing is kept), else None."""
+        def x0(xw, lw, sc, o):
+            if not edm:
+                return den.x0(xw, lw, i, self_cond=sc, **kw)
+            ln = ops.anchored_noise(win.noise_origins(o), lw.shape[1], self.sub, *win.shape, self.seed, draw=0, sample=s,
+                                    device=win.device) if den.draw_base else None
+            return den.x0(xw, lw, i, self_cond=sc, lowres_noise=ln, **kw)
+        return x0
 
-    def _multistep_chain(self, den, win, evaluate, y, s):
-        """Sample ``s`` of a multistep chain (``sampler='dpmpp2m'``): as ``_step_chain`` with ``ops.volume_joint_multistep``, whose
-        third operand is the fused x0 volume of the previous step (``win.x0_vol``, the one self-conditioning reads) -- read, then
-        overwritten with this step's, in place.  Only draw 0 of the field is used."""
-        x = ops.volume_joint_init(win.shape, self.seed, sample=s, device=win.device)        # draw 0
+    def _linear_chain(self, den, win, evaluate, y, s):
+        """Sample ``s`` of a chain whose step is ONE fused launch, in place on the state ``x`` and on ``win.x0_vol`` (the fused x0, which
+        self-conditioning gathers at the next step and the multistep families read as their history term before it is overwritten).
+        The family chooses the first state and the launch; the draws are the module docstring's."""
+        if den.sigma_space:                                  # sigma0 n(draw_base)
+            x, _ = ops.volume_joint_multistep_sde(None, None, None, None, None, 0., 0., 0., den.sigma0, *den.clamp, self.overlap, self.seed,
+                                                  draw=den.draw_base, sample=s, shape=win.shape, device=win.device)
+        else:                                                # n(0)
+            x = ops.volume_joint_init(win.shape, self.seed, sample=s, device=win.device)
+        head, tail, io = (y, win.slot, win.taps, x), (*den.clamp, self.overlap), dict(out=x, x0_out=win.x0_vol)
         for i in range(den.num_steps):
-            evaluate(x, win.x0_vol if den.self_cond and i > 0 else None, lambda xw, lw, sc, o: den.x0(xw, lw, i, self_cond=sc))
-            kx, k0, kp = den.coefs[i]
-            ops.volume_joint_multistep(y, win.slot, win.taps, x, win.x0_vol if i else None, kx, k0, kp, *den.clamp, self.overlap,
-                                       out=x, x0_out=win.x0_vol)
-        return x
-
-    def _sigma_multistep_chain(self, den, win, evaluate, y, s):
-        """Sample ``s`` of the sigma-space multistep chain (``ElucidatedImagen.window_denoiser(sampler='dpmpp2m')``): the state starts as
-        ``sigma0 n(draw_base)``; per step the windows are evaluated at sigma_i, with draw 0 of the field at each batch as its low-res
-        noise (recomputed per evaluation, as ``_heun_chain`` does), and ONE ``ops.volume_joint_multistep_sde`` launch with draw
-        ``draw_base + 1 + i`` advances the state and ``win.x0_vol`` (the history term, and what self-conditioning gathers) in place --
-        T evaluations per window and T + 1 fused launches."""
-        base = den.draw_base
-        x, _ = ops.volume_joint_multistep_sde(None, None, None, None, None, 0., 0., 0., den.sigma0, *den.clamp, self.overlap, self.seed,
-                                              draw=base, sample=s, shape=win.shape, device=win.device)
-        for i in range(den.num_steps):
-            def x0(xw, lw, sc, o):
-                ln = ops.anchored_noise(win.noise_origins(o), lw.shape[1], self.sub, *win.shape, self.seed, draw=0, sample=s,
-                                        device=win.device) if base else None
-                return den.x0(xw, lw, i, self_cond=sc, lowres_noise=ln)
-            evaluate(x, win.x0_vol if den.self_cond and i > 0 else None, x0)
-            kx, k0, kp, kn = den.coefs[i]
-            ops.volume_joint_multistep_sde(y, win.slot, win.taps, x, win.x0_vol if i else None, kx, k0, kp, kn, *den.clamp, self.overlap,
-                                           self.seed, draw=base + 1 + i, sample=s, out=x, x0_out=win.x0_vol)
+            evaluate(x, win.x0_vol if den.self_cond and i > 0 else None, self._window_x0(den, win, s, i, edm=den.sigma_space))
+            prev = win.x0_vol if i else None
+            if den.sigma_space:                              # coefs[i] = (kx, k0, kp, kn): + kp x0_prev + kn n(draw_base + 1 + i)
+                ops.volume_joint_multistep_sde(*head, prev, *den.coefs[i], *tail, self.seed, draw=den.draw_base + 1 + i, sample=s, **io)
+            elif den.multistep:                              # (kx, k0, kp): + kp x0_prev; only draw 0 of the field is used
+                ops.volume_joint_multistep(*head, prev, *den.coefs[i], *tail, **io)
+            else:                                            # (kx, k0, kn): + kn n(i + 1)
+                ops.volume_joint_step(*head, *den.coefs[i], *tail, self.seed, draw=i + 1, sample=s, **io)
         return x
 
     def _heun_chain(self, den, win, evaluate, y, s):
@@ -405,11 +393,7 @@ class VolumeInference:
         xn, x0_vol = torch.empty_like(xh), torch.empty_like(xh)
 
         def predict(state, i, stage):
-            def x0(xw, lw, sc, o):
-                ln = ops.anchored_noise(win.noise_origins(o), lw.shape[1], self.sub, *win.shape, self.seed, draw=0, sample=s,
-                                        device=win.device) if base else None
-                return den.x0(xw, lw, i, self_cond=sc, stage=stage, lowres_noise=ln)
-            evaluate(state, x0_vol if den.self_cond and (i > 0 or stage == 1) else None, x0)
+            evaluate(state, x0_vol if den.self_cond and (i > 0 or stage == 1) else None, self._window_x0(den, win, s, i, edm=True, stage=stage))
 
         corrected = False
         for i in range(T):

@@ -2516,21 +2516,45 @@ def _joint_slots(who, slot, N):
         raise ValueError(f"{who}: slot names window {int(slot.max())} of {N}")
 
 
-def volume_joint_init(shape, seed, sample=0, draw=0, device=None):
-    """The initial state of a joint chain: fp32 [D,H,W], the volume-anchored normal of ``draw`` (channel 0) at every voxel -- the
-    ``x_t == NULL`` launch of ``diqt_volume_joint_step``, bit for bit what ``anchored_noise`` hands to a window there."""
+def _joint_initial(who, entry, head, floats, shape, need, seed, draw, sample, device, draws=1):
+    """The initial state of a joint chain, one path for its three makers: a new fp32 [D,H,W] = ``shape`` volume on ``device``, filled by
+    the window-less launch of ``entry`` -- ``head(out)`` are its arguments before the shape, ``floats`` its coefficients; the lattice and
+    the clamp are zeros.  ``need``: how the shape error begins; ``draws``: how many consecutive draws the launch reads."""
     shape = tuple(int(s) for s in shape)
     if len(shape) != 3 or min(shape) < 1:
-        raise ValueError(f"volume_joint_init: shape must be a positive (D, H, W), got {shape!r}")
-    seed, draw, sample = _noise_key("volume_joint_init", seed, draw, sample)
+        raise ValueError(f"{who}: {need} a positive (D, H, W), got {shape!r}")
+    seed, draw, sample = _noise_key(who, seed, draw, sample)
+    if draw + draws > 2 ** 32:
+        raise ValueError(f"{who}: draw + 1 must fit 32 bits (unsigned), got draw {draw}")
     if not torch.cuda.is_available():
-        raise RuntimeError("diffusioniqt_amd.ops.volume_joint_init runs on the MI355X only (no CPU fallback)")
+        raise RuntimeError(f"diffusioniqt_amd.ops.{who} runs on the MI355X only (no CPU fallback)")
     device = torch.device('cuda' if device is None else device)
     with torch.cuda.device(device):
         out = torch.empty(shape, dtype=torch.float32, device=device)
-        _lib.call("diqt_volume_joint_step", None, None, None, None, out, None, 0, *shape, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0, 0.0, 0.0, 0,
-                  seed, draw, sample, _stream())
+        _lib.call(entry, *head(out), *shape, 0, 0, 0, 0, 0, *(float(v) for v in floats), 0, seed, draw, sample, _stream())
     return out
+
+
+def _joint_volumes(who, x_t, x0_prev, out, x0_out, need_x0=True):
+    """``(out, x0_out)`` as a joint step launch takes them: new tensors like ``x_t`` where None (``x0_out`` only with ``need_x0``), after
+    the check that they and ``x0_prev`` are contiguous fp32 device tensors of x_t's shape."""
+    if out is None:
+        out = torch.empty_like(x_t)
+    if x0_out is None and need_x0:
+        x0_out = torch.empty_like(x_t)
+    for t, name in ((x0_prev, 'x0_prev'), (out, 'out'), (x0_out, 'x0_out')):
+        if t is not None:
+            _chk(t)
+            if t.shape != x_t.shape or not t.is_contiguous():
+                raise ValueError(f"{who}: {name} must be a contiguous tensor of x_t's shape")
+    return out, x0_out
+
+
+def volume_joint_init(shape, seed, sample=0, draw=0, device=None):
+    """The initial state of a joint chain: fp32 [D,H,W], the volume-anchored normal of ``draw`` (channel 0) at every voxel -- the
+    ``x_t == NULL`` launch of ``diqt_volume_joint_step``, bit for bit what ``anchored_noise`` hands to a window there."""
+    return _joint_initial("volume_joint_init", "diqt_volume_joint_step", lambda out: (None, None, None, None, out, None, 0),
+                          (0.0, 0.0, 0.0, 0.0, 0.0), shape, "shape must be", seed, draw, sample, device)
 
 
 def volume_joint_step(y, slot, taps, x_t, kx, k0, kn, lo, hi, clamp_mode, stride, seed, draw, sample=0, out=None, x0_out=None):
@@ -2543,13 +2567,7 @@ def volume_joint_step(y, slot, taps, x_t, kx, k0, kn, lo, hi, clamp_mode, stride
     N, P, stride = _joint_windows("volume_joint_step", y, slot, taps, x_t, clamp_mode, stride)
     seed, draw, sample = _noise_key("volume_joint_step", seed, draw, sample)
     _joint_slots("volume_joint_step", slot, N)
-    if out is None:
-        out = torch.empty_like(x_t)
-    for t, name in ((out, 'out'), (x0_out, 'x0_out')):
-        if t is not None:
-            _chk(t)
-            if t.shape != x_t.shape or not t.is_contiguous():
-                raise ValueError(f"volume_joint_step: {name} must be a contiguous tensor of x_t's shape")
+    out, x0_out = _joint_volumes("volume_joint_step", x_t, None, out, x0_out, need_x0=False)
     _lib.call("diqt_volume_joint_step", y if N else None, slot, taps, x_t, out, x0_out, N, *x_t.shape, P, stride, *slot.shape,
               float(kx), float(k0), float(kn), float(lo), float(hi), int(clamp_mode), seed, draw, sample, _stream())
     return out
@@ -2563,15 +2581,7 @@ def volume_joint_multistep(y, slot, taps, x_t, x0_prev, kx, k0, kp, lo, hi, clam
     ``(out, x0_out)``.  One launch, bit-reproducible."""
     N, P, stride = _joint_windows("volume_joint_multistep", y, slot, taps, x_t, clamp_mode, stride)
     _joint_slots("volume_joint_multistep", slot, N)
-    if out is None:
-        out = torch.empty_like(x_t)
-    if x0_out is None:
-        x0_out = torch.empty_like(x_t)
-    for t, name in ((x0_prev, 'x0_prev'), (out, 'out'), (x0_out, 'x0_out')):
-        if t is not None:
-            _chk(t)
-            if t.shape != x_t.shape or not t.is_contiguous():
-                raise ValueError(f"volume_joint_multistep: {name} must be a contiguous tensor of x_t's shape")
+    out, x0_out = _joint_volumes("volume_joint_multistep", x_t, x0_prev, out, x0_out)
     _lib.call("diqt_volume_joint_multistep", y if N else None, slot, taps, x_t, x0_prev, out, x0_out, N, *x_t.shape, P, stride,
               *slot.shape, float(kx), float(k0), float(kp), float(lo), float(hi), int(clamp_mode), _stream())
     return out, x0_out
@@ -2611,28 +2621,12 @@ def volume_joint_multistep_sde(y, slot, taps, x_t, x0_prev, kx, k0, kp, kn, lo, 
     in-place step, None: new tensors -- and ``(out, x0_out)`` is returned.  One launch, bit-reproducible."""
     seed, draw, sample = _noise_key("volume_joint_multistep_sde", seed, draw, sample)
     if x_t is None:
-        shape = tuple(int(s) for s in (shape or ()))
-        if len(shape) != 3 or min(shape) < 1:
-            raise ValueError(f"volume_joint_multistep_sde: the initial state needs shape = a positive (D, H, W), got {shape!r}")
-        if not torch.cuda.is_available():
-            raise RuntimeError("diffusioniqt_amd.ops.volume_joint_multistep_sde runs on the MI355X only (no CPU fallback)")
-        device = torch.device('cuda' if device is None else device)
-        with torch.cuda.device(device):
-            out = torch.empty(shape, dtype=torch.float32, device=device)
-            _lib.call("diqt_volume_joint_multistep_sde", None, None, None, None, None, out, None, 0, *shape, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0,
-                      float(kn), 0.0, 0.0, 0, seed, draw, sample, _stream())
-        return out, None
+        return _joint_initial("volume_joint_multistep_sde", "diqt_volume_joint_multistep_sde",
+                              lambda out: (None, None, None, None, None, out, None, 0), (0.0, 0.0, 0.0, kn, 0.0, 0.0), shape or (),
+                              "the initial state needs shape =", seed, draw, sample, device), None
     N, P, stride = _joint_windows("volume_joint_multistep_sde", y, slot, taps, x_t, clamp_mode, stride)
     _joint_slots("volume_joint_multistep_sde", slot, N)
-    if out is None:
-        out = torch.empty_like(x_t)
-    if x0_out is None:
-        x0_out = torch.empty_like(x_t)
-    for t, name in ((x0_prev, 'x0_prev'), (out, 'out'), (x0_out, 'x0_out')):
-        if t is not None:
-            _chk(t)
-            if t.shape != x_t.shape or not t.is_contiguous():
-                raise ValueError(f"volume_joint_multistep_sde: {name} must be a contiguous tensor of x_t's shape")
+    out, x0_out = _joint_volumes("volume_joint_multistep_sde", x_t, x0_prev, out, x0_out)
     _lib.call("diqt_volume_joint_multistep_sde", y if N else None, slot, taps, x_t, x0_prev, out, x0_out, N, *x_t.shape, P, stride,
               *slot.shape, float(kx), float(k0), float(kp), float(kn), float(lo), float(hi), int(clamp_mode), seed, draw, sample,
               _stream())
@@ -2643,20 +2637,8 @@ def volume_joint_heun_init(shape, sigma0, kc, seed, draw=0, sample=0, device=Non
     """The first ``images_hat`` of a joint Heun chain (phase 0 of ``diqt_volume_joint_heun``): fp32 [D,H,W],
     ``(sigma0 n(draw)) + kc n(draw + 1)`` with n the volume-anchored normals of channel 0 -- the initial image as
     ``ElucidatedImagen.one_unet_sample`` stores it, then the churn of step 0."""
-    shape = tuple(int(s) for s in shape)
-    if len(shape) != 3 or min(shape) < 1:
-        raise ValueError(f"volume_joint_heun_init: shape must be a positive (D, H, W), got {shape!r}")
-    seed, draw, sample = _noise_key("volume_joint_heun_init", seed, draw, sample)
-    if draw + 1 >= 2 ** 32:
-        raise ValueError(f"volume_joint_heun_init: draw + 1 must fit 32 bits (unsigned), got draw {draw}")
-    if not torch.cuda.is_available():
-        raise RuntimeError("diffusioniqt_amd.ops.volume_joint_heun_init runs on the MI355X only (no CPU fallback)")
-    device = torch.device('cuda' if device is None else device)
-    with torch.cuda.device(device):
-        out = torch.empty(shape, dtype=torch.float32, device=device)
-        _lib.call("diqt_volume_joint_heun", None, None, None, out, None, None, 0, 0, *shape, 0, 0, 0, 0, 0, float(sigma0), 0.0, 0.0, 0.0,
-                  float(kc), 0.0, 0.0, 0, seed, draw, sample, _stream())
-    return out
+    return _joint_initial("volume_joint_heun_init", "diqt_volume_joint_heun", lambda out: (None, None, None, out, None, None, 0, 0),
+                          (sigma0, 0.0, 0.0, 0.0, kc, 0.0, 0.0), shape, "shape must be", seed, draw, sample, device, draws=2)
 
 
 def volume_joint_heun(y, slot, taps, xh, xn, x0, phase, coefs, kc, lo, hi, clamp_mode, stride, seed=0, draw=0, sample=0):

@@ -14,7 +14,8 @@ tests/golden/volume_launch_trace.json holds, per case, the count per op name and
 the ``min_value`` records removed (where in the order the volume minimum is launched is free; that it is launched exactly once, on
 the raw volume, is asserted separately).  The golden was recorded from commit 3a43fdc, the last one before the three window setups and
 four evaluation loops of inference.py became one plan and one loop, and is the behaviour that refactor had to keep: it is not to be
-regenerated from later code.  A digest that differs means launches, arguments, order or buffers changed; set
+regenerated from later code; the ``joint-sigma-*`` cases were added from commit 51a6a1a, the last one with a chain per sampler family in
+inference.py, on the same terms.  A digest that differs means launches, arguments, order or buffers changed; set
 ``DIQT_LAUNCH_TRACE_DUMP=<dir>`` to write the full traces there (a mismatch writes them to a temporary directory by itself) and
 diff them against a dump of the older tree -- the recorder only patches module attributes, so this file runs on either."""
 import collections
@@ -105,6 +106,8 @@ RETURNS = {
     'volume_joint_step': lambda a: a['out'] if a['out'] is not None else zeros(*a['x_t'].shape),
     'volume_joint_multistep': lambda a: (a['out'] if a['out'] is not None else zeros(*a['x_t'].shape),
                                          a['x0_out'] if a['x0_out'] is not None else zeros(*a['x_t'].shape)),
+    'volume_joint_multistep_sde': lambda a: (zeros(*a['shape']), None) if a['x_t'] is None else (
+        a['out'] if a['out'] is not None else zeros(*a['x_t'].shape), a['x0_out'] if a['x0_out'] is not None else zeros(*a['x_t'].shape)),
     'volume_joint_heun_init': lambda a: zeros(*a['shape']),
     'volume_joint_heun': lambda a: (a['xh'], a['xn'], a['x0']),
     'volume_joint_finish': lambda a: (a['mean_io'] if a['s'] else zeros(*a['x'].shape),
@@ -171,9 +174,24 @@ class StubHeunDenoiser(StubDenoiser):
                                       'lowres_noise': lowres_noise}, torch.zeros_like(img))
 
 
+class StubSigmaDenoiser(StubDenoiser):
+    """Three steps of the EDM family's multistep chain: ODE (kn = 0) on the first, SDE on the others."""
+    sigma0 = 1.5
+
+    def __init__(self, rec, self_cond, draw_base):
+        super().__init__(rec, self_cond, True)
+        self.draw_base = draw_base
+        self.coefs = torch.tensor([[0.5, 0.25, 0.0, 0.0], [0.75, 0.375, -0.125, 0.0625], [0.875, 0.4375, -0.25, 0.03125]])
+
+    def x0(self, img, lowres, i, self_cond=None, lowres_noise=None):
+        return self.rec.record('x0', {'img': img, 'lowres': lowres, 'i': i, 'self_cond': self_cond, 'lowres_noise': lowres_noise},
+                               torch.zeros_like(img))
+
+
 def _joint(chain, block, self_cond):
     stub = {'step': lambda rec: StubDenoiser(rec, self_cond, False), 'multistep': lambda rec: StubDenoiser(rec, self_cond, True),
-            'heun': lambda rec: StubHeunDenoiser(rec, self_cond)}[chain]
+            'heun': lambda rec: StubHeunDenoiser(rec, self_cond), 'sigma-base0': lambda rec: StubSigmaDenoiser(rec, self_cond, 0),
+            'sigma-base1': lambda rec: StubSigmaDenoiser(rec, self_cond, 1)}[chain]
     if block:
         return dict(vol=R.block_volume, cfg=R.block_cfg(), fn=stub, kw=dict(blend='gaussian', noise='anchored', joint=True, seed=SEED), call={})
     return dict(vol=R.shared_volume, cfg=R.shared_cfg(8, batch_size=3), fn=stub,
@@ -190,6 +208,8 @@ CASES = {
     'blend-constant-block': dict(vol=R.block_volume, cfg=R.block_cfg(), fn=sampler_of, kw=dict(blend='constant'), call={}),
     **{f"joint-{chain}-{'selfcond' if sc else 'plain'}": _joint(chain, False, sc) for chain in ('step', 'multistep', 'heun') for sc in (False, True)},
     **{f"joint-{chain}-block-selfcond": _joint(chain, True, True) for chain in ('step', 'multistep', 'heun')},
+    # the sigma-space multistep chain, two samples each: recorded from commit 51a6a1a, the last one with a chain per sampler family
+    **{f"joint-{chain}-{'selfcond' if sc else 'plain'}": _joint(chain, False, sc) for chain in ('sigma-base0', 'sigma-base1') for sc in (False, True)},
 }
 
 
@@ -264,10 +284,14 @@ def test_the_cases_reach_every_branch():
     assert counts['joint-heun-plain']['volume_joint_heun'] == 2 * (2 * 3 - 1) and counts['joint-heun-plain']['volume_joint_heun_init'] == 2
     assert counts['joint-heun-selfcond']['patch_gather'] > counts['joint-heun-plain']['patch_gather']
     assert counts['joint-heun-block-selfcond']['split'] == 3 * counts['joint-heun-block-selfcond']['merge'] - 27
+    for base in (0, 1):                                       # T + 1 fused launches per sample; low-res noise only behind draw_base 1
+        plain, sc = counts[f'joint-sigma-base{base}-plain'], counts[f'joint-sigma-base{base}-selfcond']
+        assert plain['volume_joint_multistep_sde'] == 2 * (3 + 1) and sc['patch_gather'] > plain['patch_gather']
+        assert plain.get('anchored_noise', 0) == base * plain['x0'] and plain['x0'] > 2 * 3
 
 
-if __name__ == '__main__':                                    # python -m tests.test_volume_launch_trace_host DIR: dump every full trace
+if __name__ == '__main__':              # python -m tests.test_volume_launch_trace_host DIR: dump every full trace, print every summary
     import sys
     for case in CASES:
         t = run_case(case)
-        print(case, len(t), dump(case, t, sys.argv[1]))
+        print(case, len(t), dump(case, t, sys.argv[1]), json.dumps(summary(t), sort_keys=True))
