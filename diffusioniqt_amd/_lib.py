@@ -135,6 +135,7 @@ PROTOTYPES = {
     "diqt_conv3d_fwd_gn_supported_pk": (I, [I] * 16 + [Z]),
     "diqt_conv3d_fwd_gn_pk": (I, [P, P, Z, P, P, P, P, P, Z, P, I] + [I] * 15 + [P]),
     "diqt_conv3d_bwd_weight_kernel_id": (I, [I] * 15),
+    "diqt_conv3d_bwd_weight_route": (I, [I] * 15 + [I, I, I]),
     "diqt_conv3d_fwd_ex": (I, [P, P, P, P, P, P, P, Z] + [I] * 15 + [P]),
     "diqt_conv3d_fwd_neighbours_stats_blocks": (I, [I, I, I, I, I]),
     "diqt_conv3d_fwd_neighbours": (I, [P, P, P, P, P, P, P, Z, I, I, I, I, I, P]),

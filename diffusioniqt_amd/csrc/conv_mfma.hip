@@ -2440,23 +2440,16 @@ extern "C" int diqt_weighted_colsum(const float* x, const float* w, float* out, 
 extern "C" size_t diqt_reduce_workspace_bytes(int B, int C);
 
 struct PwPlan { bool ok; long long V; int ks; bool xFirst; int M, N; };
-static PwPlan pw_plan(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw, int epd,
-                      int eph, int epw) {
+// `flat`: a 1x1x1 filter without padding (V rows in, V rows out); `v3Takes`: wgrad3_plan takes the shape
+static PwPlan pw_plan(long long V, int Cin, int Cout, bool flat, bool v3Takes) {
     PwPlan p{};
-    p.ok = kd == 1 && kh == 1 && kw == 1 && pd == 0 && ph == 0 && pw == 0 && epd == 0 && eph == 0 && epw == 0;
-    if (!p.ok) return p;
-    p.V = (long long)B * D * H * W;
+    p.V = V;
     p.xFirst = Cin >= Cout;                      // the larger channel count takes the 128-row side of the tile
     p.M = p.xFirst ? Cin : Cout; p.N = p.xFirst ? Cout : Cin;
-    if (p.M <= 64 || p.V < 4096) { p.ok = false; return p; }      // small problems stay on the conv kernel
-    {
-        // conv_wgrad3_kernel's pointwise variant (LDS-DMA double-buffered 64-row tiles, one wave per SIMD) takes the shapes it can:
-        // the batched GEMM runs these K = all-rows products at ~30 TFLOP/s
-        W3Geom g3;
-        int v3 = 0, ks3 = 0;
-        size_t lds3 = 0;
-        if (wgrad3_plan(g3, v3, ks3, lds3, B, D, H, W, Cin, Cout, 1, 1, 1, 0, 0, 0, 0, 0, 0)) { p.ok = false; return p; }
-    }
+    // small problems stay on the conv kernel.  conv_wgrad3_kernel's pointwise variant (LDS-DMA double-buffered 64-row tiles, one wave per
+    // SIMD) takes the shapes it can: the batched GEMM runs these K = all-rows products at ~30 TFLOP/s
+    p.ok = flat && p.M > 64 && p.V >= 4096 && !v3Takes;
+    if (!p.ok) return p;
     const int tiles = cdiv(p.M, 128) * cdiv(p.N, 64);
     int ks = 1;
     while (ks * 2 * tiles <= 256 && p.V % (ks * 2) == 0 && p.V / (ks * 2) >= 256) ks *= 2;      // one workgroup per CU
@@ -2541,13 +2534,40 @@ static ScPlan sc_plan(const ConvGeom& g) {
     return p;
 }
 
+// ---- what the weight-gradient launches below share ----
+// out[c] = sum over the rows of m[rows][C], in two stages through `part` ([blocks][C] floats).  The summation order follows the block rule:
+// 256 rows per block for the one-channel column sum, 16 elsewhere (wide layers at the coarse levels have few rows: still fill the chip)
+static unsigned colsum_blocks(long long rows, int rowsPerBlock) {
+    const long long n = (rows + rowsPerBlock - 1) / rowsPerBlock;
+    return n > 1024 ? 1024u : (unsigned)n;
+}
+static int colsum_rows(const float* m, float* part, float* out, long long rows, int C, int rowsPerBlock, hipStream_t s) {
+    const unsigned nblk = colsum_blocks(rows, rowsPerBlock);
+    hipLaunchKernelGGL(colsum_stage1_kernel, dim3(nblk), dim3(256), 256 * sizeof(float), s, m, part, (size_t)rows, C);
+    int rc = check_launch("colsum_stage1");
+    if (rc) return rc;
+    hipLaunchKernelGGL(colsum_stage2_kernel, dim3(cdiv(C, 4)), dim3(256), 0, s, part, out, (int)nblk, C);
+    return check_launch("colsum_stage2");
+}
+// dw = the fixed-order sum of `ks` slabs of `elems` floats in dw's own layout (conv_wgrad3_kernel, conv_wgrad_h_kernel; elems % 4 == 0:
+// their plans ask Cin % 4 == 0), dbias = the sum of the [ks][CoutPad] partials at bias_part (NULL: no bias gradient)
+static int reduce_dw3(const float* slabs, const float* bias_part, float* dw, float* dbias, size_t elems, int ks, int Cout, int CoutPad,
+                      hipStream_t s, const char* tag) {
+    const size_t n4 = elems / 4;
+    hipLaunchKernelGGL(conv_reduce_dw3_kernel, dim3((unsigned)((n4 + 63) / 64)), dim3(512), 0, s, slabs, dw, n4, ks, Cout, CoutPad, bias_part,
+                       bias_part ? dbias : nullptr, ks);
+    return check_launch(tag);
+}
+
 // ---- weight gradient with 16-bit MFMA operands (bf16 training): conv_wgrad_h.hip + the fixed-order slab sum of conv_wgrad3_kernel ----
+// its workspace: `ks` slabs of dW, the [ks][CoutPad] bias partials behind them
+static size_t wgradh_bytes(int ks, size_t dwElems, int CoutPad) { return ((size_t)ks * dwElems + (size_t)ks * CoutPad) * sizeof(float); }
 extern "C" size_t diqt_conv3d_bwd_weight_h_workspace_bytes(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd,
                                                            int ph, int pw, int epd, int eph, int epw) {
     WHGeom g;
     int ks = 0;
     if (!wgradh_plan(g, ks, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw)) return 0;       // 0: shape not taken
-    return ((size_t)ks * Cout * Cin * kd * kh * kw + (size_t)ks * g.CoutPad) * sizeof(float);
+    return wgradh_bytes(ks, (size_t)Cout * Cin * kd * kh * kw, g.CoutPad);
 }
 // 1 when diqt_conv3d_bwd_weight_h takes this shape with these flag bits of its `bf16` argument (2: 16-bit x, 4: 16-bit dY): the plan the
 // launch itself asks
@@ -2568,230 +2588,209 @@ extern "C" int diqt_conv3d_bwd_weight_h(const float* x, const float* dy, float* 
     bf16 &= 1;
     DIQT_REQUIRE(wgradh_plan(g, ks, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, xHalf, dyHalf), DIQT_E_UNSUPPORTED,
                  "conv3d_bwd_weight_h: shape not taken (diqt_conv3d_bwd_weight_h_workspace_bytes == 0)");
-    const int T = kd * kh * kw;
-    const size_t need = ((size_t)ks * Cout * Cin * T + (size_t)ks * g.CoutPad) * sizeof(float);
+    const size_t dwElems = (size_t)Cout * Cin * kd * kh * kw;
+    const size_t need = wgradh_bytes(ks, dwElems, g.CoutPad);
     DIQT_REQUIRE(workspace_bytes >= need, DIQT_E_WORKSPACE, "conv3d_bwd_weight_h: workspace %zu < %zu", workspace_bytes, need);
     float* slabs = static_cast<float*>(workspace);
-    float* bias_part = dbias ? slabs + (size_t)ks * Cout * Cin * T : nullptr;
+    float* bias_part = dbias ? slabs + (size_t)ks * dwElems : nullptr;
     int rc = wgradh_launch(x, dy, slabs, bias_part, g, ks, bf16, stream);
     if (rc) return rc;
-    const size_t n4 = (size_t)Cout * Cin * T / 4;
-    hipLaunchKernelGGL(conv_reduce_dw3_kernel, dim3((unsigned)((n4 + 63) / 64)), dim3(512), 0, (hipStream_t)stream, slabs, dw, n4, ks, Cout,
-                       g.CoutPad, bias_part, bias_part ? dbias : nullptr, ks);
-    return check_launch("conv_reduce_dw3(h)");
+    return reduce_dw3(slabs, bias_part, dw, dbias, dwElems, ks, Cout, g.CoutPad, (hipStream_t)stream, "conv_reduce_dw3(h)");
 }
 
-extern "C" size_t diqt_conv3d_bwd_weight_workspace_bytes(int B, int D, int H, int W, int Cin, int Cout, int kd,
-                                                         int kh, int kw, int pd, int ph, int pw, int epd, int eph,
-                                                         int epw) {
-    BwGeom bg;
-    int ksplit;
-    if (bw_plan(bg, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, ksplit)) return 0;
-    BwGeom2 b2;
-    bool splitCo;
-    int ks2 = 0;
-    size_t lds2;
-    if (bw2_plan(bg.g, b2, splitCo, ks2, lds2) && ks2 * (splitCo ? 1 : BW2_KPAR_A) > ksplit) ksplit = ks2 * (splitCo ? 1 : BW2_KPAR_A);
-    {
-        W3Geom g3;
-        int v3 = 0, ks3 = 0;
-        size_t lds3 = 0;
-        if (wgrad3_plan(g3, v3, ks3, lds3, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw) && ks3 > ksplit) ksplit = ks3;
-    }
-    const size_t slab = (size_t)bg.g.nChunks * kd * kh * kw * bg.g.CoutPad * CK * sizeof(float);
-    const size_t colsum = (size_t)1024 * Cout * sizeof(float);
-    size_t need = (size_t)ksplit * slab + (size_t)ksplit * bg.g.CoutPad * sizeof(float);   // + bias partials (v2)
-    const PwPlan pp = pw_plan(B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw);
-    if (pp.ok) {
-        const size_t gemm = (size_t)pp.ks * Cout * Cin * sizeof(float);
-        if (gemm > need) need = gemm;
-    }
-    if (Cout == 1 && kd * kh * kw == 1) {
-        const size_t red = diqt_reduce_workspace_bytes(1, Cin);
-        if (red > need) need = red;
-    }
-    const ScPlan sp = sc_plan(bg.g);
-    if (sp.ok) {
-        const size_t sc = ((size_t)sp.V * sp.Kp + (size_t)sp.ks * sp.Kp * Cout) * sizeof(float);
-        if (sc > need) need = sc;
-    }
-    return need > colsum ? need : colsum;
-}
+// ---- The one decision of the fp32 weight-gradient dispatch: which of its six paths a diqt_conv3d_bwd_weight call runs, with which plan,
+//      where the bias gradient comes from and how the workspace is cut -- for one ask (what the caller brings and wants).  Every plan is
+//      computed once.  convw_launch launches what this says and every shape query reads it for a fixed ask: they cannot drift. ----
+enum WgPath { WG_REFUSED = -1, WG_COLSUM = 0, WG_IM2COL = 1, WG_PW = 2, WG_V3 = 3, WG_V2 = 4, WG_V1 = 5 };    // in the order they are tried
+struct WgAsk {
+    bool aligned16 = true;       // x, dy and dw are 16-byte aligned (the queries assume it): conv_wgrad3_kernel needs all three
+    bool wantBias = false;       // the caller passes dbias
+};
+struct WgRoute {
+    int path, kid, rc;           // kid: as diqt_conv3d_bwd_weight_kernel_id numbers them (-1: bad shape, bw_plan has set the message);
+    char why[96];                // WG_REFUSED with kid >= 0: the launch returns rc with `why` as the message
+    int ksplit, colsumRows;      // split-K shares = slabs in the workspace, summed in a fixed order; rows per block of a column-sum pair
+    bool biasOnKernel;           // the bias gradient rides on the kernel as [ks2 or ksplit][CoutPad] partials at biasOff; otherwise a wanted
+                                 // one is the column-sum pair, through the start of the workspace once the kernel's data is consumed
+    size_t slabOff, biasOff;     // floats from the start of the workspace: the slabs (WG_IM2COL: behind the im2col matrix), the bias partials
+    size_t wsBytes, wsQuery;     // workspace this launch uses; what diqt_conv3d_bwd_weight_workspace_bytes answers and every launch insists on
+    long long rows;              // output voxels = rows of dY
+    BwGeom bg; size_t lds1;                            // WG_V1 (bg.g: the geometry of every path)
+    BwGeom2 b2; bool splitCo; int ks2; size_t lds2;    // WG_V2 (ks2: grid.y)
+    W3Geom g3; int v3; size_t lds3;                    // WG_V3
+    PwPlan pp; ScPlan sp;                              // WG_PW, WG_IM2COL
+};
 
-// which kernel diqt_conv3d_bwd_weight dispatches this shape to (for profilers / bench.py, so that per-kernel numbers carry the names
-// rocprofv3 reports): 3 conv_wgrad3_kernel, 2 conv_bwd_weight2_kernel, 1 conv_bwd_weight_kernel, 0 one of the GEMM / column-sum
-// paths (1x1x1 filters, <= 4 input channels, Cout == 1), -1 bad shape
-extern "C" int diqt_conv3d_bwd_weight_kernel_id(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph,
-                                                int pw, int epd, int eph, int epw) {
-    BwGeom bg;
-    int ksplit;
-    if (bw_plan(bg, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, ksplit)) return -1;
-    if (Cout == 1 && kd * kh * kw == 1) return 0;
-    if (sc_plan(bg.g).ok || pw_plan(B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw).ok) return 0;
-    W3Geom g3;
-    int v3 = 0, ks3 = 0;
-    size_t lds3 = 0;
-    if (wgrad3_plan(g3, v3, ks3, lds3, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw)) return 3;
-    BwGeom2 b2;
-    bool splitCo;
-    int ks2;
-    size_t lds2;
-    return bw2_plan(bg.g, b2, splitCo, ks2, lds2) ? 2 : 1;
-}
-
-extern "C" int diqt_conv3d_bwd_weight(const float* x, const float* dy, float* dw, float* dbias, void* workspace,
-                                      size_t workspace_bytes, int B, int D, int H, int W, int Cin, int Cout, int kd,
-                                      int kh, int kw, int pd, int ph, int pw, int epd, int eph, int epw, void* stream) {
-    DIQT_REQUIRE(x && dy && dw && workspace, DIQT_E_ALIGN, "conv3d_bwd_weight: null pointer");
-    BwGeom bg;
-    int ksplit;
-    int rc = bw_plan(bg, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, ksplit);
-    if (rc) return rc;
-    const ConvGeom& g = bg.g;
+static void convw_route(WgRoute& r, int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw, int epd,
+                        int eph, int epw, const WgAsk& a) {
+    r.path = WG_REFUSED; r.kid = -1; r.why[0] = 0; r.ksplit = 1; r.colsumRows = 16; r.ks2 = 0; r.biasOnKernel = false;
+    r.slabOff = r.biasOff = r.wsBytes = r.wsQuery = 0;
+    int ks1 = 0, ks3 = 0;
+    r.rc = bw_plan(r.bg, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, ks1);
+    if (r.rc) return;
+    const ConvGeom& g = r.bg.g;
     const int T = kd * kh * kw;
-    const size_t need = diqt_conv3d_bwd_weight_workspace_bytes(B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw);
-    DIQT_REQUIRE(workspace_bytes >= need, DIQT_E_WORKSPACE, "conv3d_bwd_weight: workspace %zu < %zu", workspace_bytes, need);
-    DIQT_REQUIRE(aligned16(workspace), DIQT_E_ALIGN, "conv3d_bwd_weight: workspace must be 16-byte aligned");
-    const PwPlan pp = pw_plan(B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw);
-    if (Cout == 1 && kd == 1 && kh == 1 && kw == 1 && pd == 0 && ph == 0 && pw == 0 && epd == 0 && eph == 0 && epw == 0 &&
-        workspace_bytes >= diqt_reduce_workspace_bytes(1, Cin) && (long long)B * D * H * W < (1ll << 31)) {
-        // final 1x1x1 conv to one channel: dW[0][ci] = sum_v dY[v] X[v][ci] is a weighted column sum, dbias = sum_v dY[v]
-        const int rows = (int)((long long)B * D * H * W);
-        rc = diqt_weighted_colsum(x, dy, dw, workspace, workspace_bytes, 1, rows, Cin, stream);
-        if (rc) return rc;
-        if (dbias) {
-            float* part = static_cast<float*>(workspace);
-            unsigned nblk = (unsigned)((rows + 255) / 256);
-            if (nblk > 1024) nblk = 1024;
-            hipLaunchKernelGGL(colsum_stage1_kernel, dim3(nblk), dim3(256), 256 * sizeof(float), (hipStream_t)stream, dy, part, (size_t)rows, 1);
-            rc = check_launch("colsum_stage1");
-            if (rc) return rc;
-            hipLaunchKernelGGL(colsum_stage2_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, part, dbias, (int)nblk, 1);
-            rc = check_launch("colsum_stage2");
-        }
-        return rc;
+    const bool flat = T == 1 && !(pd | ph | pw | epd | eph | epw);      // rows in = rows out (make_geom has flattened them: < 2^31)
+    r.rows = (long long)g.B * g.Do * g.Ho * g.Wo;
+    const bool ok2 = bw2_plan(g, r.b2, r.splitCo, r.ks2, r.lds2);
+    const bool ok3 = wgrad3_plan(r.g3, r.v3, ks3, r.lds3, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw);
+    r.pp = pw_plan(r.rows, Cin, Cout, flat, ok3);
+    r.sp = sc_plan(g);
+    r.lds1 = ((size_t)g.TD * g.HH * g.HWd * (CK + 1) + (size_t)MTILE * (NT + 1)) * sizeof(float);
+    const int slabs2 = r.ks2 * (r.splitCo ? 1 : BW2_KPAR_A);
+    const size_t F = sizeof(float), dwElems = (size_t)Cout * Cin * T;
+    const size_t slab = (size_t)g.nChunks * T * g.CoutPad * CK;          // floats of a slab of conv_bwd_weight_kernel / conv_bwd_weight2_kernel
+    auto at_least = [](size_t& v, size_t m) { if (m > v) v = m; };
+    // The query's figure: room for the most shares any of the three kernels plans, in the widest slab layout, with bias partials, or for
+    // a GEMM path's buffers, and never less than the 1024 rows of a column sum -- one buffer size per shape, whatever the ask.
+    int most = ok2 && slabs2 > ks1 ? slabs2 : ks1;
+    if (ok3 && ks3 > most) most = ks3;
+    r.wsQuery = (size_t)most * (slab + g.CoutPad) * F;
+    if (r.pp.ok) at_least(r.wsQuery, (size_t)r.pp.ks * dwElems * F);
+    if (Cout == 1 && T == 1) at_least(r.wsQuery, diqt_reduce_workspace_bytes(1, Cin));
+    if (r.sp.ok) at_least(r.wsQuery, ((size_t)r.sp.V * r.sp.Kp + (size_t)r.sp.ks * r.sp.Kp * Cout) * F);
+    at_least(r.wsQuery, (size_t)1024 * Cout * F);
+    if (Cout == 1 && flat) {                 // final 1x1x1 conv to one channel: dW[0][ci] = sum_v dY[v] X[v][ci] is a weighted column sum
+        r.path = WG_COLSUM; r.kid = 0; r.colsumRows = 256;
+        r.wsBytes = diqt_reduce_workspace_bytes(1, Cin);
+    } else if (r.sp.ok) {
+        r.path = WG_IM2COL; r.kid = 0; r.ksplit = r.sp.ks; r.slabOff = (size_t)r.sp.V * r.sp.Kp;
+        r.wsBytes = (r.slabOff + (size_t)r.sp.ks * r.sp.Kp * Cout) * F;
+    } else if (r.pp.ok) {
+        r.path = WG_PW; r.kid = 0; r.ksplit = r.pp.ks;
+        r.wsBytes = (size_t)r.pp.ks * dwElems * F;
+    } else if (a.aligned16 && ok3) {         // version 3 (conv_wgrad.hip): one wave per SIMD, LDS-DMA double-buffered tiles; slabs in dw's layout
+        r.path = WG_V3; r.kid = 3; r.ksplit = ks3; r.biasOff = ks3 * dwElems; r.biasOnKernel = a.wantBias;
+        r.wsBytes = (r.biasOff + (a.wantBias ? (size_t)ks3 * g.CoutPad : 0)) * F;
+    } else if (ok2) {
+        r.path = WG_V2; r.kid = 2; r.ksplit = slabs2; r.biasOff = slabs2 * slab; r.biasOnKernel = a.wantBias;
+        r.wsBytes = (r.biasOff + (a.wantBias ? (size_t)r.ks2 * g.CoutPad : 0)) * F;
+    } else {                                 // conv_bwd_weight_kernel is all that is left: refused only here if its tile does not fit the LDS
+        r.kid = 1; r.ksplit = ks1;
+        if (r.lds1 <= 160 * 1024) { r.path = WG_V1; r.wsBytes = ks1 * slab * F; }
+        else { r.rc = DIQT_E_UNSUPPORTED; snprintf(r.why, sizeof(r.why), "conv3d_bwd_weight: tile needs %zu B of LDS", r.lds1); }
     }
-    const ScPlan sp = sc_plan(g);
-    if (sp.ok) {
-        float* col = static_cast<float*>(workspace);
-        float* slabs = col + (size_t)sp.V * sp.Kp;
-        const size_t total = (size_t)sp.V * sp.Kp;
-        hipLaunchKernelGGL(im2col_smallcin_kernel, dim3(grid_for(total, 256, 16384)), dim3(256), 0, (hipStream_t)stream, x, col, g,
-                           sp.CINP, sp.Kp, total);
+    if (a.wantBias && !r.biasOnKernel && r.path != WG_REFUSED) at_least(r.wsBytes, (size_t)colsum_blocks(r.rows, r.colsumRows) * Cout * F);      // the column-sum pair
+}
+
+// Launches what the route says, after the refusals in the order every call meets them: bad shape, short workspace, unaligned workspace, LDS
+static int convw_launch(const WgRoute& r, const float* x, const float* dy, float* dw, float* dbias, void* workspace, size_t workspace_bytes,
+                        void* stream) {
+    if (r.kid < 0) return r.rc;
+    DIQT_REQUIRE(workspace_bytes >= r.wsQuery, DIQT_E_WORKSPACE, "conv3d_bwd_weight: workspace %zu < %zu", workspace_bytes, r.wsQuery);
+    DIQT_REQUIRE(aligned16(workspace), DIQT_E_ALIGN, "conv3d_bwd_weight: workspace must be 16-byte aligned");
+    DIQT_REQUIRE(r.path != WG_REFUSED, r.rc, "%s", r.why);
+    hipStream_t s = (hipStream_t)stream;
+    const ConvGeom& g = r.bg.g;
+    const int Cin = g.Cin, Cout = g.Cout, T = g.kd * g.kh * g.kw;
+    float* ws = static_cast<float*>(workspace);
+    float* slabs = ws + r.slabOff;
+    float* bias_part = r.biasOnKernel ? ws + r.biasOff : nullptr;
+    const bool vec4 = (Cin % 4 == 0) && aligned16(x) && aligned16(dy);
+    int rc = DIQT_OK;
+    switch (r.path) {
+    case WG_COLSUM:
+        rc = diqt_weighted_colsum(x, dy, dw, workspace, workspace_bytes, 1, (int)r.rows, Cin, stream);
+        break;
+    case WG_IM2COL: {
+        const ScPlan& sp = r.sp;
+        const size_t total = r.slabOff;      // the im2col matrix col[V][Kp] at the start of the workspace
+        hipLaunchKernelGGL(im2col_smallcin_kernel, dim3(grid_for(total, 256, 16384)), dim3(256), 0, s, x, ws, g, sp.CINP, sp.Kp, total);
         rc = check_launch("conv3d_bwd_weight(im2col)");
         if (rc) return rc;
         const long long kslice = sp.V / sp.ks;
-        rc = diqt_bgemm(col, dy, slabs, sp.ks, sp.Kp, Cout, (int)kslice, 1, 0, kslice * sp.Kp, kslice * Cout, (long long)sp.Kp * Cout,
+        rc = diqt_bgemm(ws, dy, slabs, sp.ks, sp.Kp, Cout, (int)kslice, 1, 0, kslice * sp.Kp, kslice * Cout, (long long)sp.Kp * Cout,
                         sp.Kp, Cout, Cout, 1.f, 0.f, stream);
         if (rc) return rc;
-        hipLaunchKernelGGL(smallcin_dw_reduce_kernel, dim3(grid_for((size_t)Cout * Cin * T, 256, 1024)), dim3(256), 0, (hipStream_t)stream,
-                           slabs, dw, Cout, Cin, T, sp.CINP, sp.Kp, sp.ks);
+        hipLaunchKernelGGL(smallcin_dw_reduce_kernel, dim3(grid_for((size_t)Cout * Cin * T, 256, 1024)), dim3(256), 0, s, slabs, dw, Cout, Cin,
+                           T, sp.CINP, sp.Kp, sp.ks);
         rc = check_launch("conv3d_bwd_weight(small Cin reduce)");
-        if (rc) return rc;
-        if (dbias) {
-            const size_t rows = (size_t)sp.V;
-            unsigned nblk = (unsigned)((rows + 15) / 16);
-            if (nblk > 1024) nblk = 1024;
-            hipLaunchKernelGGL(colsum_stage1_kernel, dim3(nblk), dim3(256), 256 * sizeof(float), (hipStream_t)stream, dy, col, rows, Cout);
-            rc = check_launch("colsum_stage1");
-            if (rc) return rc;
-            hipLaunchKernelGGL(colsum_stage2_kernel, dim3(cdiv(Cout, 4)), dim3(256), 0, (hipStream_t)stream, col, dbias, (int)nblk, Cout);
-            rc = check_launch("colsum_stage2");
-        }
-        return rc;
+        break;
     }
-    if (pp.ok) {
-        float* slabs = static_cast<float*>(workspace);
+    case WG_PW: {
+        const PwPlan& pp = r.pp;
         const long long kslice = pp.V / pp.ks;
-        const float* Am = pp.xFirst ? x : dy;
-        const float* Bmm = pp.xFirst ? dy : x;
+        const float *Am = pp.xFirst ? x : dy, *Bmm = pp.xFirst ? dy : x;
         const int ldA = pp.xFirst ? Cin : Cout, ldB = pp.xFirst ? Cout : Cin;
         rc = diqt_bgemm(Am, Bmm, slabs, pp.ks, pp.M, pp.N, (int)kslice, 1, 0, kslice * ldA, kslice * ldB, (long long)pp.M * pp.N,
                         ldA, ldB, pp.N, 1.f, 0.f, stream);
         if (rc) return rc;
-        hipLaunchKernelGGL(pw_reduce_kernel, dim3((unsigned)cdiv(Cout * Cin, 64)), dim3(256), 0, (hipStream_t)stream, slabs,
-                           dw, Cout, Cin, pp.ks, pp.xFirst ? 1 : 0);
+        hipLaunchKernelGGL(pw_reduce_kernel, dim3((unsigned)cdiv(Cout * Cin, 64)), dim3(256), 0, s, slabs, dw, Cout, Cin, pp.ks,
+                           pp.xFirst ? 1 : 0);
         rc = check_launch("conv3d_bwd_weight(1x1x1 reduce)");
-        if (rc) return rc;
-        if (dbias) {
-            const size_t rows = (size_t)pp.V;
-            // wide layers at the coarse levels have few rows: slice them finely so the column sums still fill the chip
-            unsigned nblk = (unsigned)((rows + 15) / 16);
-            if (nblk > 1024) nblk = 1024;
-            hipLaunchKernelGGL(colsum_stage1_kernel, dim3(nblk), dim3(256), 256 * sizeof(float), (hipStream_t)stream, dy, slabs, rows, Cout);
-            rc = check_launch("colsum_stage1");
-            if (rc) return rc;
-            hipLaunchKernelGGL(colsum_stage2_kernel, dim3(cdiv(Cout, 4)), dim3(256), 0, (hipStream_t)stream, slabs, dbias, (int)nblk, Cout);
-            rc = check_launch("colsum_stage2");
-        }
-        return rc;
+        break;
     }
-    const bool vec4 = (Cin % 4 == 0) && aligned16(x) && aligned16(dy);
-    const size_t lds = ((size_t)g.TD * g.HH * g.HWd * (CK + 1) + (size_t)MTILE * (NT + 1)) * sizeof(float);
-    DIQT_REQUIRE(lds <= 160 * 1024, DIQT_E_UNSUPPORTED, "conv3d_bwd_weight: tile needs %zu B of LDS", lds);
-    auto kern = vec4 ? conv_bwd_weight_kernel<true> : conv_bwd_weight_kernel<false>;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        DIQT_REQUIRE(e == hipSuccess, DIQT_E_LAUNCH, "conv3d_bwd_weight: hipFuncSetAttribute: %s", hipGetErrorString(e));
-    }
-    hipStream_t s = (hipStream_t)stream;
-    float* slabs = static_cast<float*>(workspace);
-    BwGeom2 b2;
-    bool splitCo = false;
-    int ks2 = 0;
-    size_t lds2 = 0;
-    float* bias_part = nullptr;      // v2 kernel: per-split-K bias-gradient partials behind the slabs
-    int bias_parts = 0;
-    W3Geom g3;
-    int v3 = 0, ks3 = 0;
-    size_t lds3 = 0;
-    if (aligned16(x) && aligned16(dy) && aligned16(dw) && wgrad3_plan(g3, v3, ks3, lds3, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw)) {
-        // version 3 (conv_wgrad.hip): one wave per SIMD, LDS-DMA double-buffered tiles; same slab layout and reduce
-        if (dbias) { bias_part = slabs + (size_t)ks3 * Cout * Cin * T; bias_parts = ks3; }
-        rc = wgrad3_launch(x, dy, slabs, bias_part, g3, v3, ks3, lds3, stream);
+    case WG_V3:
+        rc = wgrad3_launch(x, dy, slabs, bias_part, r.g3, r.v3, r.ksplit, r.lds3, stream);
         if (rc) return rc;
-        const size_t n4 = (size_t)Cout * Cin * T / 4;          // Cin % 4 == 0 (wgrad3_plan)
-        hipLaunchKernelGGL(conv_reduce_dw3_kernel, dim3((unsigned)((n4 + 63) / 64)), dim3(512), 0, s, slabs, dw, n4, ks3, Cout, g.CoutPad,
-                           bias_part, bias_part ? dbias : nullptr, bias_parts);
-        return check_launch("conv_reduce_dw3");
-    } else if (bw2_plan(g, b2, splitCo, ks2, lds2)) {
-        void (*k2)(const float*, const float*, float*, float*, BwGeom2) =
-            splitCo ? (vec4 ? conv_bwd_weight2_kernel<true, 8, 16, BW2_MAXT_B, true, 256> : conv_bwd_weight2_kernel<false, 8, 16, BW2_MAXT_B, true, 256>)
-                    : (b2.maxtA == 3
-                           ? (vec4 ? conv_bwd_weight2_kernel<true, 7, 2, 3, false, 512> : conv_bwd_weight2_kernel<false, 7, 2, 3, false, 512>)
-                           : (vec4 ? conv_bwd_weight2_kernel<true, 7, 2, BW2_MAXT_A, false, 512> : conv_bwd_weight2_kernel<false, 7, 2, BW2_MAXT_A, false, 512>));
-        if (lds2 > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k2), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
+        return reduce_dw3(slabs, bias_part, dw, dbias, (size_t)Cout * Cin * T, r.ksplit, Cout, g.CoutPad, s, "conv_reduce_dw3");
+    case WG_V1: {      // (ahead of WG_V2: the code object keeps its kernels in the order they are first named)
+        auto kern = vec4 ? conv_bwd_weight_kernel<true> : conv_bwd_weight_kernel<false>;
+        if (r.lds1 > 64 * 1024) {
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)r.lds1);
             DIQT_REQUIRE(e == hipSuccess, DIQT_E_LAUNCH, "conv3d_bwd_weight: hipFuncSetAttribute: %s", hipGetErrorString(e));
         }
-        ksplit = ks2 * (splitCo ? 1 : BW2_KPAR_A);
-        if (dbias) { bias_part = slabs + (size_t)ksplit * g.nChunks * T * g.CoutPad * CK; bias_parts = ks2; }
-        hipLaunchKernelGGL(k2, dim3(g.nChunks * b2.coBlocks * b2.tapGroups, ks2), dim3(splitCo ? 256 : 512), lds2, s, x, dy, slabs,
-                           bias_part, b2);
-        rc = check_launch("conv3d_bwd_weight(v2)");
-    } else {
-        const dim3 grid(g.nChunks * g.nNt * g.kd * bg.tapGroups, ksplit);
-        hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, x, dy, slabs, bg);
+        hipLaunchKernelGGL(kern, dim3(g.nChunks * g.nNt * g.kd * r.bg.tapGroups, r.ksplit), dim3(256), r.lds1, s, x, dy, slabs, r.bg);
         rc = check_launch("conv3d_bwd_weight");
+        break;
+    }
+    default: {         // WG_V2
+        const bool splitCo = r.splitCo;      // 128 output channels x <= 3 taps per workgroup (256 threads), else 32 x up to 28 (512)
+        void (*k2)(const float*, const float*, float*, float*, BwGeom2) =
+            splitCo ? (vec4 ? conv_bwd_weight2_kernel<true, 8, 16, BW2_MAXT_B, true, 256> : conv_bwd_weight2_kernel<false, 8, 16, BW2_MAXT_B, true, 256>)
+                    : (r.b2.maxtA == 3
+                           ? (vec4 ? conv_bwd_weight2_kernel<true, 7, 2, 3, false, 512> : conv_bwd_weight2_kernel<false, 7, 2, 3, false, 512>)
+                           : (vec4 ? conv_bwd_weight2_kernel<true, 7, 2, BW2_MAXT_A, false, 512> : conv_bwd_weight2_kernel<false, 7, 2, BW2_MAXT_A, false, 512>));
+        if (r.lds2 > 64 * 1024) {
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k2), hipFuncAttributeMaxDynamicSharedMemorySize, (int)r.lds2);
+            DIQT_REQUIRE(e == hipSuccess, DIQT_E_LAUNCH, "conv3d_bwd_weight: hipFuncSetAttribute: %s", hipGetErrorString(e));
+        }
+        hipLaunchKernelGGL(k2, dim3(g.nChunks * r.b2.coBlocks * r.b2.tapGroups, r.ks2), dim3(splitCo ? 256 : 512), r.lds2, s, x, dy, slabs,
+                           bias_part, r.b2);
+        rc = check_launch("conv3d_bwd_weight(v2)");
+        break;
+    }
     }
     if (rc) return rc;
-    const size_t total = (size_t)Cout * Cin * T;
-    hipLaunchKernelGGL(conv_reduce_dw_kernel, dim3(grid_for(total, 256)), dim3(256), 0, s, slabs, dw, Cout, Cin, T,
-                       g.CoutPad, g.nChunks, ksplit, bias_part, bias_part ? dbias : nullptr, bias_parts);
-    rc = check_launch("conv_reduce_dw");
-    if (rc) return rc;
-    if (dbias && !bias_part) {
-        const size_t rows = (size_t)g.B * g.Do * g.Ho * g.Wo;
-        unsigned nblk = (unsigned)((rows + 15) / 16);
-        if (nblk > 1024) nblk = 1024;
-        if (nblk < 1) nblk = 1;
-        // the slabs were consumed by the reduce kernel above (same stream) -> reuse the workspace
-        hipLaunchKernelGGL(colsum_stage1_kernel, dim3(nblk), dim3(256), 256 * sizeof(float), s, dy, slabs, rows, Cout);
-        rc = check_launch("colsum_stage1");
+    if (r.path == WG_V2 || r.path == WG_V1) {
+        hipLaunchKernelGGL(conv_reduce_dw_kernel, dim3(grid_for((size_t)Cout * Cin * T, 256)), dim3(256), 0, s, slabs, dw, Cout, Cin, T,
+                           g.CoutPad, g.nChunks, r.ksplit, bias_part, bias_part ? dbias : nullptr, bias_part ? r.ks2 : 0);
+        rc = check_launch("conv_reduce_dw");
         if (rc) return rc;
-        hipLaunchKernelGGL(colsum_stage2_kernel, dim3(cdiv(Cout, 4)), dim3(256), 0, s, slabs, dbias, (int)nblk, Cout);
-        rc = check_launch("colsum_stage2");
     }
+    // a bias gradient that did not ride on the kernel: the column sums of dY, through the start of the workspace (its data is consumed)
+    if (dbias && !bias_part) rc = colsum_rows(dy, ws, dbias, r.rows, Cout, r.colsumRows, s);
     return rc;
+}
+
+// the shape queries: the route of a caller with aligned pointers
+extern "C" size_t diqt_conv3d_bwd_weight_workspace_bytes(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph,
+                                                         int pw, int epd, int eph, int epw) {
+    WgRoute r;
+    convw_route(r, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, WgAsk());
+    return r.wsQuery;
+}
+// Diagnostic: the route itself, for the ask of a call whose x, dy and dw are (aligned) / are not all 16-byte aligned, with (want_bias) or
+// without dbias.  field 0: kernel id (as diqt_conv3d_bwd_weight_kernel_id), 1: path (WgPath; -1: the launch refuses), 2: split-K shares,
+// 3: the bias gradient rides on the kernel, 4: workspace bytes the launch uses, 5: the launch's return code; another field: -1
+extern "C" int diqt_conv3d_bwd_weight_route(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw,
+                                            int epd, int eph, int epw, int aligned, int want_bias, int field) {
+    WgRoute r;
+    convw_route(r, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, WgAsk{aligned != 0, want_bias != 0});
+    const int fields[6] = {r.kid, r.path, r.ksplit, r.biasOnKernel ? 1 : 0, r.wsBytes > 0x7fffffffu ? 0x7fffffff : (int)r.wsBytes, r.rc};
+    return field >= 0 && field < 6 ? fields[field] : -1;
+}
+// 3 conv_wgrad3_kernel, 2 conv_bwd_weight2_kernel, 1 conv_bwd_weight_kernel, 0 one of the GEMM / column-sum paths, -1 bad shape
+extern "C" int diqt_conv3d_bwd_weight_kernel_id(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph,
+                                                int pw, int epd, int eph, int epw) {
+    return diqt_conv3d_bwd_weight_route(B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, 1, 0, 0);
+}
+
+extern "C" int diqt_conv3d_bwd_weight(const float* x, const float* dy, float* dw, float* dbias, void* workspace, size_t workspace_bytes,
+                                      int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw,
+                                      int epd, int eph, int epw, void* stream) {
+    DIQT_REQUIRE(x && dy && dw && workspace, DIQT_E_ALIGN, "conv3d_bwd_weight: null pointer");
+    WgRoute r;
+    convw_route(r, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, WgAsk{aligned16(x) && aligned16(dy) && aligned16(dw), dbias != nullptr});
+    return convw_launch(r, x, dy, dw, dbias, workspace, workspace_bytes, stream);
 }

@@ -496,6 +496,33 @@ def _conv_fwd_raw(x5, packed, bias, residual, Cout, k, pad, epad=(0, 0, 0), stat
     return y
 
 
+def _conv_bwd_weight_raw(x, dy, dw, db, geo, h_flags=None):
+    """dW (and db unless None) of a conv from x and dY, on the fp32 entry or (``h_flags``: its ``bf16`` argument) on the 16-bit one: the
+    workspace the entry's query asks for, the call and the timer record.  False: the 16-bit entry does not take the shape, nothing ran."""
+    half = h_flags is not None
+    n = _lib.query("diqt_conv3d_bwd_weight_h_workspace_bytes" if half else "diqt_conv3d_bwd_weight_workspace_bytes", *geo)
+    if half and not n:
+        return False
+    ws = _workspace(n, x.device)
+    if TIMER.enabled:
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+    if half:
+        _lib.call("diqt_conv3d_bwd_weight_h", x, dy, dw, db, ws, n, *geo, h_flags, _stream())
+    else:
+        _lib.call("diqt_conv3d_bwd_weight", x, dy, dw, db, ws, n, *geo, _stream())
+    if TIMER.enabled:
+        e.record()
+        # tagged with rocprofv3's name of the kernel the entry dispatches to; the interval also holds the fixed-order split-K slab sum
+        # that finishes the gradient
+        tag = "conv_wgrad_h_kernel" if half else ("conv_bwd_weight_gemm", "conv_bwd_weight_kernel", "conv_bwd_weight2_kernel",
+                                                  "conv_wgrad3_kernel")[max(_lib.query("diqt_conv3d_bwd_weight_kernel_id", *geo), 0)]
+        B, Cin, Cout, kd, kh, kw = geo[0], *geo[4:9]
+        Do, Ho, Wo = dy.shape[1:4]
+        TIMER.records.append((s, e, 2.0 * B * Do * Ho * Wo * Cout * Cin * kd * kh * kw, tag, tuple(geo[:9])))
+    return True
+
+
 class GnCtx:
     """What the backward-data pass of a conv needs to know about the fused GroupNorm + activation that produced its input."""
     __slots__ = ("x", "mean", "rstd", "gamma", "beta", "ss", "groups", "act")
@@ -584,38 +611,11 @@ class _Conv3dFn(Function):
             dw = torch.empty_like(weight)
             db = torch.empty(Cout, dtype=torch.float32, device=x.device) if ctx.has_bias else None
             lpb = _lp_backward(ctx.lp)
-            nh = _lib.query("diqt_conv3d_bwd_weight_h_workspace_bytes", B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw) \
-                if lpb is not None else 0
-            if nh:
-                # bf16 training: the weight gradient on the bf16 MFMA too (x and dY rounded to bf16 while staged, fp32 accumulation; the
-                # reference's autocast backward runs in the forward's type); other shapes stay on the fp32 kernel
-                ws = _workspace(nh, x.device)
-                if TIMER.enabled:
-                    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    s.record()
-                _lib.call("diqt_conv3d_bwd_weight_h", x, dy, dw, db, ws, nh, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, lpb,
-                          _stream())
-                if TIMER.enabled:
-                    e.record()
-                    Do, Ho, Wo = dy.shape[1:4]
-                    TIMER.records.append((s, e, 2.0 * B * Do * Ho * Wo * Cout * Cin * kd * kh * kw, "conv_wgrad_h_kernel",
-                                          (B, D, H, W, Cin, Cout, kd, kh, kw)))
-                return dx, dw, db, None, (dy if ctx.has_res else None), None, None, None
-            n = _lib.query("diqt_conv3d_bwd_weight_workspace_bytes", B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw)
-            ws = _workspace(n, x.device)
-            if TIMER.enabled:
-                s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                s.record()
-            _lib.call("diqt_conv3d_bwd_weight", x, dy, dw, db, ws, n, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw,
-                      epd, eph, epw, _stream())
-            if TIMER.enabled:
-                e.record()
-                Do, Ho, Wo = dy.shape[1:4]
-                # tagged with rocprofv3's name of the kernel diqt_conv3d_bwd_weight dispatches to; the interval also holds the
-                # fixed-order split-K slab sum that finishes the gradient
-                kid = _lib.query("diqt_conv3d_bwd_weight_kernel_id", B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw)
-                tag = ("conv_bwd_weight_gemm", "conv_bwd_weight_kernel", "conv_bwd_weight2_kernel", "conv_wgrad3_kernel")[max(kid, 0)]
-                TIMER.records.append((s, e, 2.0 * B * Do * Ho * Wo * Cout * Cin * kd * kh * kw, tag, (B, D, H, W, Cin, Cout, kd, kh, kw)))
+            geo = (B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw)
+            # bf16 training: the weight gradient on the bf16 MFMA too (x and dY rounded to bf16 while staged, fp32 accumulation; the
+            # reference's autocast backward runs in the forward's type); other shapes stay on the fp32 kernel
+            if lpb is None or not _conv_bwd_weight_raw(x, dy, dw, db, geo, lpb):
+                _conv_bwd_weight_raw(x, dy, dw, db, geo)
         return dx, dw, db, None, (dy if ctx.has_res else None), None, None, None
 
 
@@ -1150,17 +1150,8 @@ class _GnActConvHFn(Function):
         dw = torch.empty_like(weight)
         db = torch.empty(Cout, dtype=torch.float32, device=x.device) if has_bias else None
         geo = (B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, 0, 0, 0)
-        nh = _lib.query("diqt_conv3d_bwd_weight_h_workspace_bytes", *geo)
-        assert nh > 0
-        if TIMER.enabled:
-            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            t0.record()
-        _lib.call("diqt_conv3d_bwd_weight_h", y16, dy, dw, db, _workspace(nh, x.device), nh, *geo, ctx.lp | 2 | (4 if y_half else 0),
-                  _stream())                                # bit 1: x is 16-bit, bit 2: dY is 16-bit
-        if TIMER.enabled:
-            t1.record()
-            Do, Ho, Wo = dy.shape[1:4]
-            TIMER.records.append((t0, t1, 2.0 * B * Do * Ho * Wo * Cout * Cin * kd * kh * kw, "conv_wgrad_h_kernel", geo[:9]))
+        took = _conv_bwd_weight_raw(y16, dy, dw, db, geo, ctx.lp | 2 | (4 if y_half else 0))      # bit 1: x is 16-bit, bit 2: dY is 16-bit
+        assert took
         # ---- GroupNorm + activation backward (as _GnActFn.backward; a 16-bit x gets a 16-bit gradient) ----
         if dtap is not None:
             dtap = dtap.contiguous()

@@ -227,9 +227,18 @@ long long diqt_conv3d_lds_bytes(int D, int H, int W, int kd, int kh, int kw, int
 
 /* Which kernel diqt_conv3d_bwd_weight dispatches a shape to (profilers / bench.py: per-kernel numbers under rocprofv3's names):
  * 3 conv_wgrad3_kernel (one wave per SIMD, LDS-DMA double-buffered tiles), 2 conv_bwd_weight2_kernel, 1 conv_bwd_weight_kernel,
- * 0 a GEMM / column-sum path (1x1x1 filters, <= 4 input channels, Cout == 1), -1 bad shape. */
+ * 0 a GEMM / column-sum path (un-padded 1x1x1 filters, <= 4 input channels), -1 bad shape: the route below for aligned pointers. */
 int diqt_conv3d_bwd_weight_kernel_id(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw,
                                      int epd, int eph, int epw);
+/* Diagnostic: the decision diqt_conv3d_bwd_weight itself obeys, for a call whose x, dy and dw are all 16-byte aligned (`aligned`) or not,
+ * with (`want_bias`) or without dbias.  field 0: kernel id as above; 1: path, in the order the launch tries them -- 0 weighted column sum
+ * (un-padded 1x1x1 filter, Cout == 1), 1 im2col + split-K GEMM (<= 4 input channels), 2 1x1x1 split-K GEMM, 3 conv_wgrad3_kernel,
+ * 4 conv_bwd_weight2_kernel, 5 conv_bwd_weight_kernel, -1 the launch refuses; 2: split-K shares; 3: 1 when the bias gradient rides on the
+ * kernel (partials behind the slabs) instead of taking the two-stage column sum; 4: workspace bytes this launch uses (at most
+ * diqt_conv3d_bwd_weight_workspace_bytes, which every launch asks for; clamped to INT_MAX); 5: the launch's return code for a valid call
+ * (DIQT_OK or the refusal's code); another field: -1. */
+int diqt_conv3d_bwd_weight_route(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw,
+                                 int epd, int eph, int epw, int aligned, int want_bias, int field);
 
 /* dW[Cout][Cin][kd][kh][kw] (OIDHW, overwritten) and dbias[Cout] (may be NULL) from x and dY.
  * Deterministic: split-K partial slabs in `workspace` are reduced in a fixed order.                  */

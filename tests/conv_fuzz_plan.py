@@ -91,16 +91,11 @@ def route(case):
 
 
 def wgrad_route(case):
-    """The kernel diqt_conv3d_bwd_weight (fp32) runs for a case."""
-    B, D, H, W, Cin, Cout, k, pad, epad, res, grads = case
-    Do, Ho, Wo = out_extent(case)
-    kid = _lib.query("diqt_conv3d_bwd_weight_kernel_id", *_geo(case))
-    T = k[0] * k[1] * k[2]
-    if kid == 0:      # the three routes diqt_conv3d_bwd_weight tries in this order
-        kind = "colsum" if (Cout == 1 and T == 1) else "im2col" if (Cin <= 4 and T > 1 and B * Do * Ho * Wo >= 4096) else "pw"
-    else:
-        kind = {3: "v3", 2: "v2", 1: "v1"}[kid]
-    return {"kid": kid, "kind": kind}
+    """The path diqt_conv3d_bwd_weight (fp32) takes for a case (aligned tensors, as torch allocates them): the library's own decision,
+    diqt_conv3d_bwd_weight_route."""
+    kid, path = (_lib.query("diqt_conv3d_bwd_weight_route", *_geo(case), 1, 1, field) for field in (0, 1))
+    assert path >= 0, (case, "the launch refuses")
+    return {"kid": kid, "kind": ("colsum", "im2col", "pw", "v3", "v2", "v1")[path]}
 
 
 def fwd_tags(r):
