@@ -176,6 +176,9 @@ PROTOTYPES = {
     "diqt_multistep_sde_step": (I, [P] * 9 + [I, Z, P]),
     "diqt_volume_joint_multistep_sde": (I, [P] * 7 + [I] * 9 + [F] * 6 + [I, ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_uint, P]),
     "diqt_volume_joint_heun": (I, [P] * 6 + [I] * 10 + [F] * 7 + [I, ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_uint, P]),
+    "diqt_edm_inpaint_churn": (I, [P] * 8 + [I, Z, P]),
+    "diqt_volume_joint_heun_inpaint": (I, [P] * 8 + [I] * 10 + [F] * 8 + [I, ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_uint,
+                                                                          ctypes.c_uint, P]),
     "diqt_volume_joint_finish": (I, [P] * 6 + [I] * 10 + [F, F, F, F, P]),
     "diqt_patch_pair_crop_workspace_bytes": (Z, [I, I]),
     "diqt_patch_pair_crop": (I, [P, P, P, P, P, P, Z, I, I, I, I, I, I, I, F, F, P]),

@@ -637,6 +637,33 @@ __device__ __forceinline__ float axpby_update(float k0, float a, float k1, float
     const float v = k0 * a;
     return fmaf(k1, b, v);
 }
+// The two updates of the inpainting loop around that sampler (RePaint; elucidated_imagen.py:473-530), with the roundings of the
+// diqt_axpby3 calls they stand for -- ONE definition for the per-window pass and the joint pass:
+//   inpaint_renoise   images + (sigma - sigma_next) n, the re-noise that ends a pass:   axpby3(x, n, 1, kr), 1 x is x bit for bit;
+//   inpaint_churn     the known value under the mask, then the churn of the next pass:  axpby3(sel(m, known, t), eps, 1, kc).  The
+//                     product is fused in also when kc == 0, as axpby3 does it (an unmasked -0 plus a +0 product is +0 there too).
+__device__ __forceinline__ float inpaint_renoise(float x, float kr, float n) { return axpby_update(1.f, x, kr, n); }
+__device__ __forceinline__ float inpaint_churn(bool m, float known, float t, float kc, float eps) {
+    return axpby_update(1.f, m ? known : t, kc, eps);
+}
+// The per-window pass: x / renoise / known / eps / out [B][per], mask one byte per element, kr / kc device [B].  renoise == NULL: no
+// re-noise (kr is not read).  out may alias x (every thread reads its own element, then writes it).  Block (64, 4) = 256 consecutive
+// elements of sample blockIdx.y; the store follows the last use of a load.
+__global__ __launch_bounds__(256) void edm_inpaint_churn_kernel(const float* x, const float* __restrict__ renoise,
+                                                                const float* __restrict__ known,
+                                                                const unsigned char* __restrict__ mask,
+                                                                const float* __restrict__ eps, const float* __restrict__ kr,
+                                                                const float* __restrict__ kc, float* out, size_t per) {
+    const int b = blockIdx.y;
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.y * 64 + threadIdx.x;
+    if (e >= per) return;
+    const size_t v = (size_t)b * per + e;
+    const bool m = mask[v] != 0;
+    const float kn = known[v], ep = eps[v];
+    float t = x[v];
+    if (renoise) t = inpaint_renoise(t, kr[b], renoise[v]);
+    out[v] = inpaint_churn(m, kn, t, kc[b], ep);
+}
 __global__ __launch_bounds__(256) void volume_joint_heun_kernel(const float* __restrict__ y, const int* __restrict__ slot,
                                                                 const float* __restrict__ taps, float* xh, float* xn, float* x0v,
                                                                 int phase, int N, int D, int H, int W, int P, int stride, int G0, int G1,
@@ -675,6 +702,58 @@ __global__ __launch_bounds__(256) void volume_joint_heun_kernel(const float* __r
     const float t = fmaf(c, xn[v], axpby_update(a, xh[v], b, x0v[v]));
     float r = fmaf(d, x0b, t);                         // axpby3(tmp, out2, 1, d): 1 * tmp is tmp
     if (kc != 0.f) r = fmaf(kc, philox_normal(philox4x32_10(v0, v1, draw, sample, key0, key1)), r);
+    xh[v] = r;
+    x0v[v] = x0b;
+}
+// The same chain with the inpainting loop on the joint state (diqt_volume_joint_heun_inpaint): known [D][H][W] in state space, mask one
+// byte per voxel.  The predictor is phase 1 of the kernel above; the phases here, numbered as there, paste and churn with the helpers
+// of the per-window pass:
+//   0 (no y)                       xh = sel(m, known, a n(draw)) + kc n(draw + 1);
+//   2 (after the stage-1 windows)  the corrector above up to x; where kr != 0, x = x + kr n(draw_r), the re-noise that ends a pass which
+//                                  is not the last of its step; then xh = sel(m, known, x) + kc n(draw) and x0 = x0b;
+//   3 (no y, no window walk)       xh = sel(m, known, xn) + kc n(draw): the further passes of the step that ends at sigma 0, which has no
+//                                  corrector.  Every voxel: an uncovered one holds xn = xh since phase 1, and nothing gathers it.
+// With kc == 0 the churn is the selection alone and there is no Philox call, as above.  A voxel no kept window covers: phase 2 leaves
+// xh and writes x0 = 0.  xh and x0 are updated in place; the stores follow the last use of a load.
+__global__ __launch_bounds__(256) void volume_joint_heun_inpaint_kernel(const float* __restrict__ y, const int* __restrict__ slot,
+                                                                        const float* __restrict__ taps, float* xh, const float* xn,
+                                                                        float* x0v, const float* __restrict__ known,
+                                                                        const unsigned char* __restrict__ mask, int phase, int N, int D,
+                                                                        int H, int W, int P, int stride, int G0, int G1, int G2, float a,
+                                                                        float b, float c, float d, float kr, float kc, float lo,
+                                                                        float hi, int clamp_mode, unsigned key0, unsigned key1,
+                                                                        unsigned draw, unsigned draw_r, unsigned sample) {
+    extern __shared__ float tp[];                      // [P]
+    const Voxel p = walk_prologue(tp, taps, P, phase == 2, H, W);
+    if (!p.inside) return;
+    const size_t v = p.v;
+    const unsigned v0 = (unsigned)v, v1 = (unsigned)((unsigned long long)v >> 32);
+    if (phase != 2) {
+        const bool m = mask[v] != 0;
+        const float kn = known[v];
+        unsigned dc = draw;
+        float t;
+        if (phase == 0) {
+            t = axpby_update(a, philox_normal(philox4x32_10(v0, v1, draw, sample, key0, key1)), 0.f, 0.f);
+            dc = draw + 1u;
+        } else {
+            t = xn[v];
+        }
+        xh[v] = kc != 0.f ? inpaint_churn(m, kn, t, kc, philox_normal(philox4x32_10(v0, v1, dc, sample, key0, key1))) : (m ? kn : t);
+        return;
+    }
+    const Fused f = joint_fuse(y, slot, taps, tp, N, P, stride, G0, G1, G2, p, StepClamp{lo, hi, clamp_mode});
+    if (!f.covered()) {
+        x0v[v] = 0.f;
+        return;
+    }
+    const float x0b = f.x0();
+    const bool m = mask[v] != 0;
+    const float kn = known[v];
+    const float t = fmaf(c, xn[v], axpby_update(a, xh[v], b, x0v[v]));
+    float r = fmaf(d, x0b, t);
+    if (kr != 0.f) r = inpaint_renoise(r, kr, philox_normal(philox4x32_10(v0, v1, draw_r, sample, key0, key1)));
+    r = kc != 0.f ? inpaint_churn(m, kn, r, kc, philox_normal(philox4x32_10(v0, v1, draw, sample, key0, key1))) : (m ? kn : r);
     xh[v] = r;
     x0v[v] = x0b;
 }
@@ -1034,6 +1113,37 @@ extern "C" int diqt_volume_joint_heun(const float* y, const int* slot, const flo
     hipLaunchKernelGGL(volume_joint_heun_kernel, g.grid, dim3(64, 4), g.lds, STREAM, y, slot, taps, xh, xn, x0, phase, N, D, H, W, P, stride,
                        G0, G1, G2, a, b, c, d, kc, lo, hi, clamp_mode, (unsigned)seed, (unsigned)(seed >> 32), draw, sample);
     return check_launch("volume_joint_heun");
+}
+
+extern "C" int diqt_edm_inpaint_churn(const float* x, const float* renoise, const float* known, const unsigned char* mask,
+                                      const float* eps, const float* kr, const float* kc, float* out, int B, size_t per_batch,
+                                      void* stream) {
+    DIQT_REQUIRE(x && known && mask && eps && kc && out && (kr || !renoise), DIQT_E_ALIGN, "edm_inpaint_churn: null pointer");
+    DIQT_REQUIRE(B > 0 && per_batch > 0, DIQT_E_SHAPE, "edm_inpaint_churn: bad shape (B %d, per_batch %zu)", B, per_batch);
+    DIQT_REQUIRE(B <= 65535 && (per_batch + 255) / 256 <= 0x7fffffffu, DIQT_E_SHAPE,
+                 "edm_inpaint_churn: more than 65535 samples or 2^31 - 1 blocks per sample");
+    hipLaunchKernelGGL(edm_inpaint_churn_kernel, dim3((unsigned)((per_batch + 255) / 256), B), dim3(64, 4), 0, STREAM, x, renoise, known,
+                       mask, eps, kr, kc, out, per_batch);
+    return check_launch("edm_inpaint_churn");
+}
+
+extern "C" int diqt_volume_joint_heun_inpaint(const float* y, const int* slot, const float* taps, float* xh, const float* xn, float* x0,
+                                              const float* known, const unsigned char* mask, int phase, int N, int D, int H, int W,
+                                              int P, int stride, int G0, int G1, int G2, float a, float b, float c, float d, float kr,
+                                              float kc, float lo, float hi, int clamp_mode, unsigned long long seed, unsigned draw,
+                                              unsigned draw_r, unsigned sample, void* stream) {
+    DIQT_REQUIRE(phase == 0 || phase == 2 || phase == 3, DIQT_E_UNSUPPORTED,
+                 "volume_joint_heun_inpaint: phase %d (0 = init, 2 = corrector, 3 = re-churn; the predictor is volume_joint_heun's)", phase);
+    DIQT_REQUIRE(known && mask && (phase != 3 || xn), DIQT_E_ALIGN, "volume_joint_heun_inpaint: null pointer");
+    JointGrid g;
+    int rc = joint_launch_plan("volume_joint_heun_inpaint", xh, phase == 2, xn && x0 && slot && taps && (y || N == 0), N, D, H, W, P,
+                               stride, G0, G1, G2, clamp_mode, g);
+    if (rc) return rc;
+    DIQT_REQUIRE(phase != 0 || draw != 0xffffffffu, DIQT_E_SHAPE, "volume_joint_heun_inpaint: phase 0 uses draw and draw + 1");
+    hipLaunchKernelGGL(volume_joint_heun_inpaint_kernel, g.grid, dim3(64, 4), g.lds, STREAM, y, slot, taps, xh, xn, x0, known, mask, phase,
+                       N, D, H, W, P, stride, G0, G1, G2, a, b, c, d, kr, kc, lo, hi, clamp_mode, (unsigned)seed, (unsigned)(seed >> 32),
+                       draw, draw_r, sample);
+    return check_launch("volume_joint_heun_inpaint");
 }
 
 extern "C" int diqt_volume_joint_finish(const float* x, const int* slot, const float* vol, float* mean_io, float* m2_io, float* out_std,

@@ -57,7 +57,9 @@ class EDMWindowDenoiser:
     * ``x0(img, lowres, i, self_cond=None, stage=0, lowres_noise=None)`` -> fp32 [B,C,P,P,P]: ``preconditioned_network_forward`` at
       sigma_hat of step i (``stage`` 0) or at its sigma_next (``stage`` 1) on the low-res windows noised with ``lowres_noise`` at
       ``lowres_sample_noise_level`` -- the tensor ``one_unet_sample`` calls ``out`` / ``out2``, hipGraph replay included;
-    * ``finish(x)``: clamp(-1, 1) and ``unnormalize_img`` on a tensor of any shape;
+    * ``finish(x)``: clamp(-1, 1) and ``unnormalize_img`` on a tensor of any shape; ``finish(x, known, mask)`` pastes the known values
+      (state space) under the 0/1 mask between the two, and ``normalize(x)`` = ``imagen.normalize_img`` takes a known volume there -- what
+      ``VolumeInference(joint=True, inpaint=...)`` needs;
     * ``self_cond``: whether the U-Net takes the last x0 estimate."""
     heun = True
 
@@ -133,11 +135,21 @@ class EDMWindowDenoiser:
         finally:
             elu.train(was_training)
 
+    def normalize(self, x):
+        """A known volume (in the units ``finish`` returns) in state space: ``imagen.normalize_img``, what ``one_unet_sample`` does to
+        ``inpaint_images`` (:447)."""
+        return self.imagen.normalize_img(x)
+
     @torch.no_grad()
-    def finish(self, x):
+    def finish(self, x, known=None, mask=None):
+        """``known`` (state space) / ``mask`` (0/1 fp32), both of x's shape: the chain inpainted, and the known values go under the mask
+        between the clamp and ``unnormalize_img`` (:527-532)."""
         flat = x.contiguous().view(1, -1)
         one = torch.ones(1, device=x.device)
-        return self.imagen.unnormalize_img(ops.axpby3(flat, None, None, one, None, None, -1., 1., 2)).view(x.shape)
+        flat = ops.axpby3(flat, None, None, one, None, None, -1., 1., 2)
+        if known is not None:
+            flat = ops.mask_blend(flat, known.contiguous().view(1, -1), mask.contiguous().view(1, -1))
+        return self.imagen.unnormalize_img(flat).view(x.shape)
 
 
 class EDMMultistepWindowDenoiser(EDMWindowDenoiser):
@@ -335,6 +347,28 @@ class ElucidatedImagen(nn.Module):
             raise ValueError("sampler='dpmpp2m' takes no skip_steps: a history term over a cut chain is meaningless -- shorten the chain "
                              "with sample_steps")
 
+    @staticmethod
+    def _check_inpaint_args(sampler, inpaint_images, inpaint_masks, inpaint_resample_times):
+        """The argument rules of inpainting for one U-Net (``ValueError`` naming "inpaint"; nothing touches the device).  Returns whether
+        the call inpaints."""
+        if exists(inpaint_images) != exists(inpaint_masks):
+            raise ValueError("inpaint_images and inpaint_masks must be both passed in to do inpainting")
+        if not exists(inpaint_images):
+            return False
+        if sampler != 'heun':
+            raise ValueError(f"sampler={sampler!r} does not inpaint: the re-noising loop (inpaint_resample_times) belongs to the stochastic "
+                             f"Heun sampler -- use sampler='heun'")
+        R = inpaint_resample_times
+        if isinstance(R, bool) or not isinstance(R, int) or R < 1:
+            raise ValueError(f"inpaint_resample_times must be a positive integer, got {R!r}")
+        return True
+
+    @staticmethod
+    def inpaint_draws(steps, resample_times):
+        """How many normals the inpainting loop takes over ``steps`` sampler steps, after the initial image: per (step, r) the ``eps`` and,
+        unless r == 0 or it is the last step, the re-noise normal."""
+        return steps * resample_times + (steps - 1) * (resample_times - 1)
+
     def _dpmpp2m_tables(self, index, sample_steps, eta, sigma_min, sigma_max):
         """(sigmas [T + 1] fp32, coefs [T,4] fp32) of ``sampler='dpmpp2m'`` for U-Net ``index``, both on the host."""
         hp = self.hparams[index]
@@ -391,9 +425,20 @@ class ElucidatedImagen(nn.Module):
         num_sample_steps, ...)`` -- ONE U-Net evaluation per step, at sigma_i itself, and ONE ``ops.multistep_sde_step`` launch whose
         history operand is the clamped (or thresholded) prediction of the previous step; self-conditioning reads that same tensor.
         ``eta == 0`` is the ODE solver (the draws are the initial image alone), ``0 < eta <= 1`` the midpoint 2M-SDE (one more draw per
-        step whose kn != 0: every step but the last).  S_churn / S_tmin / S_tmax play no part; S_noise scales kn.  No ``skip_steps``."""
-        assert not exists(inpaint_images) and not exists(inpaint_masks), 'inpainting: SURVEY.md §8(f) next'
+        step whose kn != 0: every step but the last).  S_churn / S_tmin / S_tmax play no part; S_noise scales kn.  No ``skip_steps``.
+
+        ``inpaint_images`` [B,C,D,H,W] (in the units ``sample`` returns) with ``inpaint_masks`` [B,D,H,W] (True: known): the RePaint loop
+        of ``_heun_inpaint_sample``, ``inpaint_resample_times`` passes per step.  The draws are then the initial image and, per
+        (step, r), the ``eps`` and -- unless r == 0 or it is the last step -- the re-noise normal (``inpaint_draws``).  Only with
+        ``sampler='heun'``; one of the two without the other, another sampler or a count that is not a positive integer: ``ValueError``
+        before anything touches the device."""
         self._check_sampler_args(sampler, sample_steps, skip_steps, eta)
+        has_inpainting = self._check_inpaint_args(sampler, inpaint_images, inpaint_masks, inpaint_resample_times)
+        if has_inpainting:
+            return self._heun_inpaint_sample(unet, shape, unet_number=unet_number, clamp=clamp, dynamic_threshold=dynamic_threshold,
+                                             cond_scale=cond_scale, inpaint_images=inpaint_images, inpaint_masks=inpaint_masks,
+                                             inpaint_resample_times=int(inpaint_resample_times), init_images=init_images,
+                                             skip_steps=skip_steps, sigma_min=sigma_min, sigma_max=sigma_max, noise=noise, **kwargs)
         if sampler == 'dpmpp2m':
             return self._dpmpp2m_sample(unet, shape, unet_number=unet_number, clamp=clamp, dynamic_threshold=dynamic_threshold,
                                         cond_scale=cond_scale, init_images=init_images, sigma_min=sigma_min, sigma_max=sigma_max,
@@ -466,6 +511,75 @@ class ElucidatedImagen(nn.Module):
         images = ops.axpby3(images, None, None, torch.ones(B, device=dev), None, None, -1., 1., 2)    # clamp(-1, 1)
         return self.unnormalize_img(images)
 
+    def _inpaint_operands(self, inpaint_images, inpaint_masks, shape):
+        """:446-449 on the device: the known images through ``normalize_img`` and the nearest resize to the U-Net's size, the masks
+        [B,D,H,W] -> [B,1,D,H,W], resized as floats, then thresholded.  Returns (known fp32, mask as 0/1 fp32, mask as bytes), each of
+        ``shape`` and contiguous (the mask is repeated over the channels)."""
+        dev = self.device
+        known = self._resize(self.normalize_img(inpaint_images.to(dev).float()), shape[-1], shape[2])
+        masks = self._resize(inpaint_masks.to(dev)[:, None].float(), shape[-1], shape[2]).bool()
+        if tuple(known.shape) != tuple(shape) or tuple(masks.shape) != (shape[0], 1, *shape[2:]):
+            raise ValueError(f"inpaint_images {tuple(inpaint_images.shape)} / inpaint_masks {tuple(inpaint_masks.shape)} do not resize to the "
+                             f"sampled shape {tuple(shape)} and its [B,D,H,W] mask")
+        masks = masks.expand(shape)
+        return known.contiguous(), masks.float().contiguous(), masks.to(torch.uint8).contiguous()
+
+    def _heun_inpaint_sample(self, unet, shape, *, unet_number, clamp, dynamic_threshold, cond_scale, inpaint_images, inpaint_masks,
+                             inpaint_resample_times, init_images, skip_steps, sigma_min, sigma_max, noise, **kwargs):
+        """``one_unet_sample`` with inpainting (:441-449, 473-530; RePaint, Lugmayr et al. 2022): every step runs
+        ``inpaint_resample_times`` passes, r = R - 1 .. 0.  A pass draws ``eps``, pastes the known image under the mask and churns,
+        runs the two Heun evaluations as ever, and -- unless r == 0 or it is the last step -- draws once more and re-noises,
+        images += (sigma - sigma_next) n.  The re-noise that ends a pass, the paste and the churn that begins the next are ONE
+        ``ops.edm_inpaint_churn`` launch.  The self-conditioning estimate carries across passes.  At the end: clamp, the known values
+        under the mask, ``unnormalize_img``.  The arguments are checked in ``one_unet_sample``."""
+        hp = self.hparams[unet_number - 1]
+        sigma_min, sigma_max = default(sigma_min, hp.sigma_min), default(sigma_max, hp.sigma_max)
+        sigmas = self.sample_schedule(hp.num_sample_steps, hp.rho, sigma_min, sigma_max)
+        gammas = torch.where((sigmas >= hp.S_tmin) & (sigmas <= hp.S_tmax), min(hp.S_churn / hp.num_sample_steps, sqrt(2) - 1), 0.)
+        sched = list(zip(sigmas[:-1].tolist(), sigmas[1:].tolist(), gammas[:-1].tolist()))[default(skip_steps, 0):]
+        dev = self.device
+        B = shape[0]
+        if callable(noise):
+            draw = lambda: noise(shape).to(dev).float().contiguous()
+        else:
+            noise = list(noise) if exists(noise) else None
+            draw = (lambda: noise.pop(0).to(dev).float().contiguous()) if exists(noise) else (lambda: torch.randn(shape, device=dev))
+        vec = lambda v: torch.full((B,), float(v), device=dev)
+        known, mask_f, mask_b = self._inpaint_operands(inpaint_images, inpaint_masks, shape)
+        images = ops.axpby3(draw(), None, None, vec(sigmas[0].item()), None, None)
+        if exists(init_images):
+            images = ops.add(images, init_images.to(dev).float())
+        fwd = partial(self.preconditioned_network_forward, unet.forward_with_cond_scale, sigma_data=hp.sigma_data, clamp=clamp,
+                      dynamic_threshold=dynamic_threshold, cond_scale=cond_scale, **kwargs)
+        self_cond_on = bool(getattr(unet, 'self_cond', False))
+        sc = (lambda x0: dict(self_cond=x0)) if self_cond_on else (lambda x0: {})
+        x_start = renoise = kr = None
+        for ind, (sigma, sigma_next, gamma) in enumerate(sched):
+            is_last_timestep = ind == len(sched) - 1
+            sigma_hat = sigma + gamma * sigma
+            kc = vec(hp.S_noise * sqrt(max(sigma_hat ** 2 - sigma ** 2, 0.)))
+            r = (sigma_next - sigma_hat) / sigma_hat
+            for resample in reversed(range(inpaint_resample_times)):
+                eps = draw()
+                # the re-noise of the pass before (if it had one), the paste, the churn: one pass over the state, in place
+                images_hat = ops.edm_inpaint_churn(images, renoise, known, mask_b, eps, kr, kc, out=images)
+                renoise = kr = None
+                out = fwd(images_hat, float(sigma_hat), **sc(x_start))
+                images_next = ops.axpby3(images_hat, out, None, vec(1. + r), vec(-r), None)
+                x_start = out
+                if sigma_next != 0:
+                    out2 = fwd(images_next, float(sigma_next), **sc(out))
+                    r2 = 0.5 * (sigma_next - sigma_hat) / sigma_next
+                    tmp = ops.axpby3(images_hat, out, images_next, vec(1. + 0.5 * r), vec(-0.5 * r), vec(r2))
+                    images_next = ops.axpby3(tmp, out2, None, vec(1.), vec(-r2), None)
+                    x_start = out2
+                images = images_next
+                if not (resample == 0 or is_last_timestep):                       # renoise in repaint and then resample (:520-523)
+                    renoise, kr = draw(), vec(sigma - sigma_next)
+        images = ops.axpby3(images, None, None, vec(1.), None, None, -1., 1., 2)    # clamp(-1, 1)   (:527)
+        images = ops.mask_blend(images, known, mask_f)                              # (:529-530)
+        return self.unnormalize_img(images)
+
     def window_denoiser(self, unet_number=2, cond_scale=1., clamp=True, sigma_min=None, sigma_max=None, inpaint_images=None,
                         inpaint_masks=None, init_images=None, skip_steps=None, _unet_context=nullcontext, sampler='heun',
                         sample_steps=None, eta=0.):
@@ -517,11 +631,25 @@ class ElucidatedImagen(nn.Module):
         -- are ``one_unet_sample``'s.  Under 'dpmpp2m' the draws of a U-Net are the low-res augmentation noise (if it is low-res
         conditioned), the initial image, then one per step whose kn != 0 (none with ``eta == 0``); the churn hyper-parameters (S_churn,
         S_tmin, S_tmax) play no part.  Refused with ``ValueError`` before anything touches the device: an unknown sampler, ``eta``
-        outside [0, 1], ``eta`` or ``sample_steps`` with 'heun', ``sample_steps < 2``, ``skip_steps`` with 'dpmpp2m'."""
+        outside [0, 1], ``eta`` or ``sample_steps`` with 'heun', ``sample_steps < 2``, ``skip_steps`` with 'dpmpp2m'.
+
+        ``inpaint_images`` / ``inpaint_masks`` / ``inpaint_resample_times`` (:580-592): every sampled U-Net keeps the known voxels through
+        the RePaint loop of ``one_unet_sample``; ``batch_size`` 1 broadcasts to the number of images.  A U-Net's draws are then the
+        low-res noise (if any), the initial image and ``inpaint_draws(steps, R)`` loop normals, in the reference's call order.  One of
+        images / masks alone, inpainting with 'dpmpp2m', or a count that is not a positive integer: ``ValueError`` naming "inpaint",
+        before anything touches the device."""
         assert texts is None and text_embeds is None and not return_pil_images
         samplers, steps_per_unet, etas = (cast_tuple(v, len(self.unets)) for v in (sampler, sample_steps, eta))
         for args in zip(samplers, steps_per_unet, cast_tuple(skip_steps, len(self.unets)), etas):
             self._check_sampler_args(*args)
+        sampled_samplers = samplers[start_at_unet_number - 1:default(stop_at_unet_number, len(self.unets))]
+        has_inpainting = any([self._check_inpaint_args(s, inpaint_images, inpaint_masks, inpaint_resample_times)
+                              for s in sampled_samplers or samplers[-1:]])
+        if has_inpainting:
+            if batch_size == 1:                                                    # broadcast along the inpainted images (:580-583)
+                batch_size = inpaint_images.shape[0]
+            if inpaint_images.shape[0] != batch_size:
+                raise ValueError(f"the number of inpaint_images ({inpaint_images.shape[0]}) must equal batch_size ({batch_size})")
         if callable(noise):
             sampled = range(start_at_unet_number, default(stop_at_unet_number, len(self.unets)) + 1)
             if len(sampled) != 1:
@@ -569,10 +697,14 @@ class ElucidatedImagen(nn.Module):
             if unet_sampler == 'dpmpp2m':                                          # the initial image, then one draw per row with kn != 0
                 multistep = dict(sampler=unet_sampler, sample_steps=unet_steps, eta=unet_eta)
                 n_draws = 1 + int((self._dpmpp2m_tables(unet_number - 1, unet_steps, unet_eta, smin, smax)[1][:, 3] != 0).sum())
+            inpaint = {}
+            if has_inpainting:                                                     # the initial image, then the draws of the loop
+                inpaint = dict(inpaint_images=inpaint_images, inpaint_masks=inpaint_masks, inpaint_resample_times=inpaint_resample_times)
+                n_draws = 1 + self.inpaint_draws(n_draws - 1, inpaint_resample_times)
             unet_noise = noise_fn if exists(noise_fn) else ([noise.pop(0) for _ in range(n_draws)] if exists(noise) else None)
             img = self.one_unet_sample(unet, shape, unet_number=unet_number, init_images=unet_init, skip_steps=unet_skip,
                                        sigma_min=smin, sigma_max=smax, cond_scale=unet_cond_scale, dynamic_threshold=dynamic_threshold,
-                                       use_tqdm=use_tqdm, noise=unet_noise, **multistep,
+                                       use_tqdm=use_tqdm, noise=unet_noise, **multistep, **inpaint,
                                        **({'cond_images': cond_images.to(device).float()} if exists(cond_images) else {}),
                                        **self._unet_kwargs(unet, lowres_cond_img, lowres_noise_times))
             outputs.append(img)

@@ -64,6 +64,13 @@ independent one, bit for bit.  The four chains:
   ``den.sigma0``): DPM-Solver++ 2M for the EDM family, ODE (``eta = 0``) or midpoint SDE -- the state starts as ``sigma0 n`` and
   ``ops.volume_joint_multistep_sde`` takes x_next = kx x + k0 x0 + kp x0_prev + kn n per step: T evaluations per window and T + 1
   fused launches where the Heun chain costs 2 T - 1 of each.
+
+Inpainting (``inpaint=(known, mask)``, ``inpaint_resample_times=R``) keeps the voxels of ``known`` under ``mask`` fixed while the rest of
+the volume is generated (RePaint, Lugmayr et al. 2022; the loop of the reference's ``ElucidatedImagen.one_unet_sample``).  In the crop
+and blend modes every sampler call gets its windows of the two volumes and inpaints on its own -- each window resamples its own border of a
+known region that crosses it.  With ``joint=True`` and the Heun denoiser the loop runs on the one state: R passes per step, the pass
+boundary (re-noise, paste, churn) riding in the corrector launch (``ops.volume_joint_heun_inpaint``), 2 R T - 1 fused launches after the
+initial state for T steps, and one paste per sample before ``ops.volume_joint_finish``.
 """
 from types import SimpleNamespace
 
@@ -195,6 +202,8 @@ class VolumeInference:
     * with ``heun``: ``coefs`` rows (kc, a1, b1, a2, b2, c2, d2); ``sigma0``; ``sched`` rows (sigma, sigma_next, gamma), sigma_next == 0
       meaning no corrector; ``draw_base`` (1 when draw 0 is the low-res augmentation noise: the initial image is draw ``draw_base``, the
       eps of step i draw ``draw_base + 1 + i``); ``x0`` also takes ``stage=`` (0: at sigma_hat, 1: at sigma_next) and ``lowres_noise=``;
+      with ``inpaint=`` also ``normalize(x)`` (a known volume into state space) and ``finish(x, known, mask)`` (the paste of the known
+      values, state space, under the 0/1 mask between the clamp and the un-normalisation);
     * with ``multistep`` and a ``sigma0`` (the EDM family's ``sampler='dpmpp2m'``): ``coefs`` rows (kx, k0, kp, kn); the state starts as
       ``sigma0`` times draw ``draw_base`` and step i adds kn times draw ``draw_base + 1 + i`` (no Philox call where kn == 0); ``x0`` also
       takes ``lowres_noise=``.  A multistep denoiser without ``sigma0`` (``Imagen``'s) runs the chain above, unchanged."""
@@ -212,7 +221,36 @@ class VolumeInference:
             p.draw_base, p.sigma0 = int(den.draw_base), float(den.sigma0)
         return p
 
-    def __init__(self, configs, sample_fn, nonzero_ratio=0.05, blend=None, sigma_scale=0.125, samples=1, noise=None, seed=0, joint=False):
+    @staticmethod
+    def _check_inpaint(inpaint, resample_times, joint, sample_fn):
+        """The argument rules of ``inpaint`` (``ValueError``; nothing touches the device).  Returns None or (known fp32, mask bool), host
+        or device tensors as they were given."""
+        if inpaint is None:
+            return None
+        if not isinstance(inpaint, (tuple, list)) or len(inpaint) != 2:
+            raise ValueError(f"VolumeInference: inpaint must be (known, mask), got {type(inpaint).__name__}")
+        known, mask = (torch.as_tensor(t) for t in inpaint)
+        if known.ndim != 3 or not known.is_floating_point() or mask.dtype != torch.bool or mask.shape != known.shape:
+            raise ValueError(f"VolumeInference: inpaint must be (known float [D,H,W], mask bool [D,H,W]) of one shape, got {known.dtype} "
+                             f"{tuple(known.shape)} and {mask.dtype} {tuple(mask.shape)}")
+        if isinstance(resample_times, bool) or not isinstance(resample_times, int) or resample_times < 1:
+            raise ValueError(f"VolumeInference: inpaint_resample_times must be a positive integer, got {resample_times!r}")
+        if joint and not (getattr(sample_fn, 'heun', False) and hasattr(sample_fn, 'normalize')):
+            raise ValueError("VolumeInference: joint=True inpaints with an EDM Heun denoiser (ElucidatedImagen.window_denoiser()) only: the "
+                             "first-order and multistep chains have no re-noising loop")
+        return known.float(), mask
+
+    def _inpaint_volumes(self, win):
+        """The known volume and the mask as 0/1 floats on the volume's device (``__call__`` has checked their shape)."""
+        known, mask = self.inpaint
+        return known.to(win.device).contiguous(), mask.to(win.device).float().contiguous()
+
+    def _inpaint_windows(self, kw, mw):
+        """What a sampler call takes besides ``x``: the batch's windows of the known volume and of the mask, thresholded."""
+        return dict(inpaint_images=kw, inpaint_masks=mw[:, 0] > 0.5, inpaint_resample_times=self.resample_times)
+
+    def __init__(self, configs, sample_fn, nonzero_ratio=0.05, blend=None, sigma_scale=0.125, samples=1, noise=None, seed=0, joint=False,
+                 inpaint=None, inpaint_resample_times=5):
         """``sample_fn(lr_patches [B,1,S,S,S]) -> hr_patches`` — e.g. ``lambda x: trainer.sample(batch_size=x.shape[0],
         start_image_or_video=x, start_at_unet_number=2)[0]`` (test_all.py:234).  ``blend`` / ``sigma_scale`` / ``samples``: weighted
         overlap blending and multi-sample statistics, see the module docstring.  ``noise='anchored'`` (with ``seed``): every call
@@ -220,7 +258,20 @@ class VolumeInference:
         e.g. ``lambda x, noise=None: trainer.sample(batch_size=x.shape[0], start_image_or_video=x, start_at_unet_number=2,
         sampler='ddim', sample_steps=50, noise=noise)[0]``.  ``joint=True`` (needs a blend mode and ``noise='anchored'``): the second
         argument is a window denoiser instead -- ``trainer.window_denoiser(sampler='ddim', sample_steps=50)`` or, second order,
-        ``trainer.window_denoiser(sampler='dpmpp2m', sample_steps=16)`` -- see the class docstring."""
+        ``trainer.window_denoiser(sampler='dpmpp2m', sample_steps=16)`` -- see the class docstring.
+
+        ``inpaint=(known, mask)`` with ``inpaint_resample_times=R``: ``known`` fp32 [D,H,W] in the units ``__call__`` returns (the
+        z-scored prediction) and ``mask`` bool [D,H,W], True where ``known`` is to be kept while the rest is generated (RePaint).  In the
+        crop and blend modes every call becomes ``sample_fn(x[, noise=src], inpaint_images=kw, inpaint_masks=mw,
+        inpaint_resample_times=R)`` with the batch's windows of the two volumes; with ``joint=True`` and an EDM Heun denoiser
+        (``ElucidatedImagen.window_denoiser()``) the loop runs on the one state, so a known region that crosses window borders is
+        resampled once, not once per window.  A known voxel comes back exactly, except where the fill or the background reset applies:
+        they come last, as in every mode, and override known values on uncovered and background voxels.  ``ValueError`` naming "inpaint"
+        before anything touches the device: a pair that is not (float [D,H,W], bool [D,H,W]) of one shape -- or, in ``__call__``, not the
+        volume's --, ``inpaint_resample_times`` that is not a positive integer, joint mode with a denoiser that is not ``heun`` (the
+        first-order and multistep chains have no re-noising loop)."""
+        self.inpaint = self._check_inpaint(inpaint, inpaint_resample_times, joint, sample_fn)
+        self.resample_times = inpaint_resample_times
         if noise not in NOISE_MODES:
             raise ValueError(f"VolumeInference: noise must be None or 'anchored', got {noise!r}")
         self.noise, self.seed = noise, int(seed)
@@ -266,6 +317,9 @@ class VolumeInference:
         ``return_std`` (blend modes, ``samples >= 2``): returns ``(mean, std)``, the per-voxel statistics over the samples."""
         if return_std and (self.blend is None or self.samples < 2):
             raise ValueError("VolumeInference: return_std needs a blend mode and samples >= 2")
+        if self.inpaint is not None and tuple(self.inpaint[0].shape) != tuple(lowres_raw.shape):
+            raise ValueError(f"VolumeInference: the inpaint volumes {tuple(self.inpaint[0].shape)} are not the volume's shape "
+                             f"{tuple(lowres_raw.shape)}")
         if self.blend is not None:
             if patch_slice is not None:
                 raise NotImplementedError("VolumeInference: a blend mode does not split one volume's windows over ranks (that needs a "
@@ -281,9 +335,11 @@ class VolumeInference:
         # cropped interiors (width P - 2*(overlap//2), stride overlap) of neighbouring windows still overlap when the stride is
         # below half a patch: one scatter launch per patch, in candidate order, keeps "later overwrites" deterministic
         serial_scatter = (not self.block_mode) and self.overlap < P and P - 2 * (self.overlap // 2) > self.overlap
+        known = self._inpaint_volumes(win) if self.inpaint is not None else ()
         for lo, o, idx in win.batches:
             x, _ = ops.patch_gather(vol, idx, P, self.mean, self.std)
-            y = self._merge(self._sample(self._split(x), win, o, 0)).contiguous()
+            kmw = [self._split(ops.patch_gather(v, idx, P, 0., 1.)[0]) for v in known]            # (v - 0) / 1: the volumes' own bits
+            y = self._merge(self._sample(self._split(x), win, o, 0, *kmw)).contiguous()
             mg = torch.from_numpy(np.ascontiguousarray(margins[lo:lo + len(o)])).to(win.device)
             if serial_scatter:
                 for j in range(len(o)):
@@ -299,12 +355,14 @@ class VolumeInference:
     def _merge(self, y):                                      # fp32; block mode: the sub-volumes back as one block (test_all.py:265-266)
         return merge_sub_volumes(y.float(), original_shape=(1, 1) + (self.patch,) * 3) if self.block_mode else y.float()
 
-    def _sample(self, x, win, origins, s):
-        """One sampler call on the windows at ``origins`` (block mode: ONE block, already split into its sub-volumes), sample ``s``."""
+    def _sample(self, x, win, origins, s, kw=None, mw=None):
+        """One sampler call on the windows at ``origins`` (block mode: ONE block, already split into its sub-volumes), sample ``s``;
+        ``kw`` / ``mw``: the same windows of the known volume and of the 0/1 mask when the call inpaints."""
+        inpaint = {} if kw is None else self._inpaint_windows(kw, mw)
         if self.noise is None:
-            return self.sample_fn(x)
+            return self.sample_fn(x, **inpaint)
         src = AnchoredNoise(win.shape, self.seed).source(win.noise_origins(origins), self.sub, sample=s, device=x.device)
-        return self.sample_fn(x, noise=src)
+        return self.sample_fn(x, noise=src, **inpaint)
 
     def _evaluate(self, win, volumes, call, out):
         """The evaluation loop of the blend and joint paths.  Per batch: gather its windows from every ``(volume, mean, std)`` of
@@ -325,7 +383,12 @@ class VolumeInference:
         win = _Windows(self, vol)
         P, S = self.patch, self.samples
         patches = torch.empty((S, win.N, P, P, P), dtype=torch.float32, device=win.device)
-        self._evaluate(win, [(vol, self.mean, self.std)], lambda x, o: (self._sample(x, win, o, s) for s in range(S)), patches)
+        known = [(v, 0., 1.) for v in self._inpaint_volumes(win)] if self.inpaint is not None else []
+
+        def call(x, *rest):                                  # the windows of the known volume and the mask (if any), then the origins
+            *kmw, o = rest
+            return (self._sample(x, win, o, s, *kmw) for s in range(S))
+        self._evaluate(win, [(vol, self.mean, self.std)] + known, call, patches)
         return ops.volume_blend(patches, win.slot, win.taps, vol, self.mean, self.std, win.min_val, win.fill, self.overlap, want_std)
 
     def _joint(self, lowres_raw, want_std):
@@ -343,10 +406,15 @@ class VolumeInference:
         def evaluate(state, cond, x0):
             self._evaluate(win, [(state, 0., 1.), (vol, self.mean, self.std), (cond, 0., 1.)], x0, y)   # (v - 0) / 1: the state's own bits
 
+        inp = ()
+        if self.inpaint is not None:                         # the known volume in state space, the mask as bytes (the kernels') and 0/1
+            known, mask_f = self._inpaint_volumes(win)
+            inp = (self.sample_fn.normalize(known).contiguous(), mask_f.to(torch.uint8), mask_f)
         mean_io = m2_io = out_std = None
         for s in range(S):
-            x = chain(den, win, evaluate, y, s)
-            mean_io, m2_io, out_std = ops.volume_joint_finish(den.finish(x), win.slot, vol, P, self.overlap, self.mean, self.std,
+            x = chain(den, win, evaluate, y, s, *inp[:2])
+            # with inpainting the denoiser pastes the known values between its clamp and its un-normalisation
+            mean_io, m2_io, out_std = ops.volume_joint_finish(den.finish(x, *inp[::2]), win.slot, vol, P, self.overlap, self.mean, self.std,
                                                               win.min_val, win.fill, s, S, mean_io, m2_io, want_std)
         return mean_io, out_std
 
@@ -383,29 +451,57 @@ class VolumeInference:
                 ops.volume_joint_step(*head, *den.coefs[i], *tail, self.seed, draw=i + 1, sample=s, **io)
         return x
 
-    def _heun_chain(self, den, win, evaluate, y, s):
+    def _heun_chain(self, den, win, evaluate, y, s, known=None, mask=None):
         """Sample ``s`` of the chain of an EDM window denoiser (module docstring): ``xh`` (images_hat), ``xn`` (images_next) and ``x0_vol``
         (the fused prediction, which self-conditioning gathers) are advanced in place by ``ops.volume_joint_heun``; ``predict`` evaluates
         the windows of one of them into ``y``, with draw 0 of the field at each batch as its low-res noise.  The initial image is draw
-        ``den.draw_base``, the eps of step i draw ``den.draw_base + 1 + i``.  Returns the volume the chain ends in."""
+        ``den.draw_base``, the eps of step i draw ``den.draw_base + 1 + i``.  Returns the volume the chain ends in.
+
+        With ``known`` (fp32 [D,H,W] in state space) and ``mask`` (uint8 [D,H,W]) the chain inpaints: every step runs
+        ``self.resample_times`` passes, each the two evaluations above; the pass boundary -- the re-noise of a pass that is neither the
+        last of its step nor in the last step, the paste, the churn of the next pass -- rides in the corrector launch
+        (``ops.volume_joint_heun_inpaint`` phase 2), or is a launch of its own (phase 3) on the step that ends at sigma 0, which has no
+        corrector.  The state's draws are numbered by ONE counter that advances as the per-window sampler calls its source: the initial
+        image, then per pass the eps and, where there is one, the re-noise normal -- so at stride = patch the chain is
+        ``sample(noise=source, inpaint_images=...)`` per window."""
         base, T = den.draw_base, den.num_steps
-        xh = ops.volume_joint_heun_init(win.shape, den.sigma0, den.coefs[0][0], self.seed, draw=base, sample=s, device=win.device)
+        R = self.resample_times if known is not None else 1
+        if known is None:
+            xh = ops.volume_joint_heun_init(win.shape, den.sigma0, den.coefs[0][0], self.seed, draw=base, sample=s, device=win.device)
+        else:
+            xh = ops.volume_joint_heun_inpaint_init(known, mask, den.sigma0, den.coefs[0][0], self.seed, draw=base, sample=s)
         xn, x0_vol = torch.empty_like(xh), torch.empty_like(xh)
 
-        def predict(state, i, stage):
-            evaluate(state, x0_vol if den.self_cond and (i > 0 or stage == 1) else None, self._window_x0(den, win, s, i, edm=True, stage=stage))
+        def predict(state, i, stage, first):
+            evaluate(state, x0_vol if den.self_cond and not first else None, self._window_x0(den, win, s, i, edm=True, stage=stage))
 
-        corrected = False
+        corrected, draw = False, base + 2                    # the next draw of the state: the initial image and the first eps are taken
         for i in range(T):
             _, a1, b1, a2, b2, c2, d2 = den.coefs[i]
-            predict(xh, i, 0)
-            ops.volume_joint_heun(y, win.slot, win.taps, xh, xn, x0_vol, 1, (a1, b1), 0., *den.clamp, self.overlap)
-            corrected = float(den.sched[i][1]) != 0
-            if corrected:                                    # no corrector on the step that ends at sigma 0
-                predict(xn, i, 1)
-                more = i + 1 < T
-                ops.volume_joint_heun(y, win.slot, win.taps, xh, xn, x0_vol, 2, (a2, b2, c2, d2), den.coefs[i + 1][0] if more else 0.,
-                                      *den.clamp, self.overlap, self.seed, draw=base + 2 + i if more else 0, sample=s)
+            sigma, sigma_next = float(den.sched[i][0]), float(den.sched[i][1])
+            for r in reversed(range(R)):
+                predict(xh, i, 0, i == 0 and r == R - 1)
+                ops.volume_joint_heun(y, win.slot, win.taps, xh, xn, x0_vol, 1, (a1, b1), 0., *den.clamp, self.overlap)
+                corrected = sigma_next != 0
+                more = r > 0 or i + 1 < T                    # another pass follows: this launch churns for it
+                renoise = r > 0 and i + 1 < T
+                kc = (den.coefs[i][0] if r > 0 else den.coefs[i + 1][0]) if more else 0.
+                if corrected:                                # no corrector on the step that ends at sigma 0
+                    predict(xn, i, 1, False)
+                    if known is None:
+                        ops.volume_joint_heun(y, win.slot, win.taps, xh, xn, x0_vol, 2, (a2, b2, c2, d2), kc, *den.clamp, self.overlap,
+                                              self.seed, draw=draw if more else 0, sample=s)
+                    else:
+                        ops.volume_joint_heun_inpaint(y, win.slot, win.taps, xh, xn, x0_vol, known, mask, 2, (a2, b2, c2, d2),
+                                                      sigma - sigma_next if renoise else 0., kc, *den.clamp, self.overlap, self.seed,
+                                                      draw=draw + renoise if more else 0, draw_r=draw if renoise else 0, sample=s)
+                elif known is not None and more:
+                    if renoise:
+                        raise ValueError("VolumeInference: inpaint: a step that ends at sigma 0 before the last one has no corrector to "
+                                         "carry its re-noise")
+                    ops.volume_joint_heun_inpaint(None, None, None, xh, xn, x0_vol, known, mask, 3, (), 0., kc, *den.clamp, self.overlap,
+                                                  self.seed, draw=draw, sample=s)
+                draw += int(renoise) + int(more)
         return xh if corrected else xn
 
 

@@ -2507,10 +2507,11 @@ def _joint_slots(who, slot, N):
         raise ValueError(f"{who}: slot names window {int(slot.max())} of {N}")
 
 
-def _joint_initial(who, entry, head, floats, shape, need, seed, draw, sample, device, draws=1):
-    """The initial state of a joint chain, one path for its three makers: a new fp32 [D,H,W] = ``shape`` volume on ``device``, filled by
+def _joint_initial(who, entry, head, floats, shape, need, seed, draw, sample, device, draws=1, more_draws=()):
+    """The initial state of a joint chain, one path for its makers: a new fp32 [D,H,W] = ``shape`` volume on ``device``, filled by
     the window-less launch of ``entry`` -- ``head(out)`` are its arguments before the shape, ``floats`` its coefficients; the lattice and
-    the clamp are zeros.  ``need``: how the shape error begins; ``draws``: how many consecutive draws the launch reads."""
+    the clamp are zeros.  ``need``: how the shape error begins; ``draws``: how many consecutive draws the launch reads; ``more_draws``:
+    the further draw indices of an entry that takes some between ``draw`` and ``sample``."""
     shape = tuple(int(s) for s in shape)
     if len(shape) != 3 or min(shape) < 1:
         raise ValueError(f"{who}: {need} a positive (D, H, W), got {shape!r}")
@@ -2522,7 +2523,7 @@ def _joint_initial(who, entry, head, floats, shape, need, seed, draw, sample, de
     device = torch.device('cuda' if device is None else device)
     with torch.cuda.device(device):
         out = torch.empty(shape, dtype=torch.float32, device=device)
-        _lib.call(entry, *head(out), *shape, 0, 0, 0, 0, 0, *(float(v) for v in floats), 0, seed, draw, sample, _stream())
+        _lib.call(entry, *head(out), *shape, 0, 0, 0, 0, 0, *(float(v) for v in floats), 0, seed, draw, *more_draws, sample, _stream())
     return out
 
 
@@ -2658,6 +2659,98 @@ def volume_joint_heun(y, slot, taps, xh, xn, x0, phase, coefs, kc, lo, hi, clamp
     _lib.call("diqt_volume_joint_heun", y if N else None, slot, taps, xh, xn, x0, phase, N, *xh.shape, P, stride, *slot.shape,
               *(coefs + (0.0, 0.0))[:4], float(kc) if phase == 2 else 0.0, float(lo), float(hi), int(clamp_mode), seed, draw, sample,
               _stream())
+    return xh, xn, x0
+
+
+def _chk_mask(who, mask, like):
+    if not mask.is_cuda:
+        raise RuntimeError(f"diffusioniqt_amd.ops.{who} runs on the MI355X only (no CPU fallback); the mask is a CPU tensor")
+    if mask.dtype not in (torch.uint8, torch.bool) or tuple(mask.shape) != tuple(like.shape) or not mask.is_contiguous():
+        raise ValueError(f"{who}: mask must be a contiguous uint8 or bool tensor of shape {tuple(like.shape)}, got {mask.dtype} "
+                         f"{tuple(mask.shape)}")
+
+
+def edm_inpaint_churn(x, renoise, known, mask, eps, kr, kc, out=None):
+    """One pass boundary of the EDM inpainting loop on a window batch (include/diqt.h, diqt_edm_inpaint_churn): ``x`` [B, ...] the state,
+    ``renoise`` the re-noise normals of the pass that just ended (None: no re-noise, ``kr`` may be None too), ``known`` the known image in
+    state space, ``mask`` one byte per element (uint8 or bool; non-zero: known), ``eps`` the churn normals, ``kr`` / ``kc`` device [B].
+    out = sel(mask, known, x + kr renoise) + kc eps with the roundings of the two ``axpby3`` calls it replaces.  ``out``: where it goes
+    (``x`` itself for an in-place pass; None: a new tensor).  Returns ``out``.  One launch."""
+    _chk(x, renoise, known, eps, kr, kc, out)
+    if x.ndim < 2 or x.numel() == 0:
+        raise ValueError(f"edm_inpaint_churn: x must be a non-empty [B, ...] tensor, got {tuple(x.shape)}")
+    B = x.shape[0]
+    if B > 65535:
+        raise ValueError(f"edm_inpaint_churn: at most 65535 samples per launch, got {B}")
+    if out is None:
+        out = torch.empty_like(x)
+    for t, name in ((renoise, 'renoise'), (known, 'known'), (eps, 'eps'), (out, 'out')):
+        if t is not None and t.shape != x.shape:
+            raise ValueError(f"edm_inpaint_churn: {name} must have x's shape {tuple(x.shape)}, got {tuple(t.shape)}")
+    _chk_mask("edm_inpaint_churn", mask, x)
+    if renoise is not None and kr is None:
+        raise ValueError("edm_inpaint_churn: a re-noise needs its coefficients kr")
+    for t, name in ((kr, 'kr'), (kc, 'kc')):
+        if t is not None and tuple(t.shape) != (B,):
+            raise ValueError(f"edm_inpaint_churn: {name} must be a [B] = [{B}] tensor, got {tuple(t.shape)}")
+    _lib.call("diqt_edm_inpaint_churn", x, renoise, known, mask, eps, kr, kc, out, B, x.numel() // B, _stream())
+    return out
+
+
+def _joint_known(who, known, mask, shape):
+    _chk(known)
+    if tuple(known.shape) != tuple(shape):
+        raise ValueError(f"{who}: known must be a [D,H,W] = {tuple(shape)} volume, got {tuple(known.shape)}")
+    _chk_mask(who, mask, known)
+
+
+def volume_joint_heun_inpaint_init(known, mask, sigma0, kc, seed, draw=0, sample=0):
+    """The first ``images_hat`` of a joint Heun chain that inpaints (phase 0 of ``diqt_volume_joint_heun_inpaint``): a new fp32 [D,H,W]
+    volume, ``sel(mask, known, sigma0 n(draw)) + kc n(draw + 1)`` -- ``volume_joint_heun_init`` with the known volume (in state space,
+    fp32 [D,H,W]) pasted under ``mask`` (uint8 or bool [D,H,W]) before the churn of step 0."""
+    _joint_known("volume_joint_heun_inpaint_init", known, mask, known.shape)      # the mask against known; the shape itself below
+    return _joint_initial("volume_joint_heun_inpaint_init", "diqt_volume_joint_heun_inpaint",
+                          lambda out: (None, None, None, out, None, None, known, mask, 0, 0), (sigma0, 0.0, 0.0, 0.0, 0.0, kc, 0.0, 0.0),
+                          known.shape, "known must be", seed, draw, sample, known.device, draws=2, more_draws=(0,))
+
+
+def volume_joint_heun_inpaint(y, slot, taps, xh, xn, x0, known, mask, phase, coefs, kr, kc, lo, hi, clamp_mode, stride, seed=0, draw=0,
+                              draw_r=0, sample=0):
+    """The corrector (``phase`` 2) or the re-churn (``phase`` 3) of a joint Heun chain that inpaints (include/diqt.h,
+    diqt_volume_joint_heun_inpaint), IN PLACE on ``xh`` and ``x0``; the predictor is ``volume_joint_heun(phase=1)``.  ``known`` fp32
+    [D,H,W] in state space, ``mask`` uint8 or bool [D,H,W].  Phase 2, ``coefs = (a, b, c, d)``: ``volume_joint_heun``'s corrector up to
+    x, then x += kr n(draw_r) where ``kr != 0`` (the re-noise of a pass that is not the last of its step), then
+    xh = sel(mask, known, x) + kc n(draw) and x0 = the fused prediction.  Phase 3 (``y`` / ``slot`` / ``taps`` may be None, ``coefs``
+    empty): xh = sel(mask, known, xn) + kc n(draw) at every voxel -- the further passes of the step that ends at sigma 0.
+    Returns ``(xh, xn, x0)``.  One launch, bit-reproducible."""
+    who = "volume_joint_heun_inpaint"
+    phase = int(phase)
+    if phase not in (2, 3):
+        raise ValueError(f"{who}: phase must be 2 (corrector) or 3 (re-churn), got {phase!r}; phase 0 is volume_joint_heun_inpaint_init "
+                         f"and the predictor volume_joint_heun(phase=1)")
+    seed, draw, sample = _noise_key(who, seed, draw, sample)
+    draw_r = _noise_key(who, seed, draw_r, sample)[1]
+    coefs = tuple(float(v) for v in coefs)
+    if len(coefs) != (4 if phase == 2 else 0):
+        raise ValueError(f"{who}: phase {phase} takes {4 if phase == 2 else 0} coefficients, got {len(coefs)}")
+    _chk(xh)
+    if xh.ndim != 3:
+        raise ValueError(f"{who}: xh must be a [D,H,W] volume")
+    for t, name in ((xn, 'xn'), (x0, 'x0')):
+        _chk(t)
+        if t.shape != xh.shape or not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be a contiguous tensor of xh's shape")
+    if len({xh.data_ptr(), xn.data_ptr(), x0.data_ptr()}) != 3:
+        raise ValueError(f"{who}: xh, xn and x0 are three different volumes")
+    _joint_known(who, known, mask, xh.shape)
+    if phase == 3:
+        _lib.call("diqt_volume_joint_heun_inpaint", None, None, None, xh, xn, x0, known, mask, 3, 0, *xh.shape, 0, 0, 0, 0, 0, 0.0, 0.0,
+                  0.0, 0.0, 0.0, float(kc), 0.0, 0.0, 0, seed, draw, 0, sample, _stream())
+        return xh, xn, x0
+    N, P, stride = _joint_windows(who, y, slot, taps, xh, clamp_mode, stride)
+    _joint_slots(who, slot, N)
+    _lib.call("diqt_volume_joint_heun_inpaint", y if N else None, slot, taps, xh, xn, x0, known, mask, 2, N, *xh.shape, P, stride,
+              *slot.shape, *coefs, float(kr), float(kc), float(lo), float(hi), int(clamp_mode), seed, draw, draw_r, sample, _stream())
     return xh, xn, x0
 
 

@@ -710,6 +710,35 @@ int diqt_volume_joint_multistep_sde(const float* y, const int* slot, const float
 int diqt_volume_joint_heun(const float* y, const int* slot, const float* taps, float* xh, float* xn, float* x0, int phase, int N, int D,
                            int H, int W, int P, int stride, int G0, int G1, int G2, float a, float b, float c, float d, float kc,
                            float lo, float hi, int clamp_mode, unsigned long long seed, unsigned draw, unsigned sample, void* stream);
+/* One pass boundary of the inpainting (RePaint) loop around that sampler, per window batch (elucidated_imagen.py:479-486 and 520-523:
+ * `images = images + (sigma - sigma_next) * repaint_noise`, then `images_hat = images + added_noise` with the known image under the
+ * mask) -- the re-noise that ends pass r, the paste and the churn that begins the next pass in ONE launch, in place of two diqt_axpby3
+ * and one selection with two temporaries.  x / renoise / known / eps / out are [B][per_batch], mask one byte per element (non-zero:
+ * known), kr / kc DEVICE [B]:
+ *     t = renoise ? fmaf(kr, renoise, x) : x;  u = mask ? known : t;  out = fmaf(kc, eps, u)
+ * -- the roundings of diqt_axpby3(x, renoise, 1, kr) and diqt_axpby3(u, eps, 1, kc) with a pure selection between them; the churn
+ * product is fused in also when kc == 0, as diqt_axpby3 does it.  renoise == NULL: no re-noise, kr is not read.  out may alias x (every
+ * thread reads its own element, then writes it).  Null pointers: DIQT_E_ALIGN; B <= 0, per_batch == 0 or B > 65535: DIQT_E_SHAPE.   */
+int diqt_edm_inpaint_churn(const float* x, const float* renoise, const float* known, const unsigned char* mask, const float* eps,
+                           const float* kr, const float* kc, float* out, int B, size_t per_batch, void* stream);
+/* The same loop on the joint state: diqt_volume_joint_heun plus known [D][H][W] (in state space), mask (uint8 [D][H][W]), kr and a
+ * second draw index.  The predictor is phase 1 of diqt_volume_joint_heun, unchanged.  `phase` here:
+ *   0  xh = sel(m, known, a * n(draw)) + kc * n(draw + 1): the initial image, the paste, the churn of step 0.  Every voxel; the
+ *      window arguments, xn, x0, b, c, d, kr, draw_r and the clamp are ignored.
+ *   2  the corrector of diqt_volume_joint_heun's phase 2 up to x; where kr != 0, x = fmaf(kr, n(draw_r), x), the re-noise that ends a
+ *      pass that is not the last of its step; then xh = sel(m, known, x) + kc * n(draw) and x0 = x0b.  Uncovered voxel: xh is left
+ *      as it is, x0 = 0.
+ *   3  xh = sel(m, known, xn) + kc * n(draw): the further passes of the step that ends at sigma 0, which has no corrector.  Every
+ *      voxel, no window walk; the window arguments, x0, a .. d, kr, draw_r and the clamp are ignored.
+ * sel and the two updates are diqt_edm_inpaint_churn's; with kc == 0 the churn is the selection alone and no normal is computed (the
+ * per-window pass differs from that in the sign of a zero at most).  Null pointers: DIQT_E_ALIGN; a lattice that does not match
+ * (phase 2): DIQT_E_SHAPE; a phase outside {0, 2, 3} or clamp_mode outside {0, 1}: DIQT_E_UNSUPPORTED; phase 0 with draw == 2^32 - 1:
+ * DIQT_E_SHAPE.                                                                                                                   */
+int diqt_volume_joint_heun_inpaint(const float* y, const int* slot, const float* taps, float* xh, const float* xn, float* x0,
+                                   const float* known, const unsigned char* mask, int phase, int N, int D, int H, int W, int P,
+                                   int stride, int G0, int G1, int G2, float a, float b, float c, float d, float kr, float kc, float lo,
+                                   float hi, int clamp_mode, unsigned long long seed, unsigned draw, unsigned draw_r, unsigned sample,
+                                   void* stream);
 /* The end of sample s (0-based) of S joint chains: per voxel r = min_val where vol (RAW, may be NULL) has (vol - mean) / std ==
  * min_val (diqt_background_reset's expression), else x (the finished state) where a kept window (slot >= 0) covers the voxel, else
  * `fill`; then diqt_volume_blend's Welford update in sample order, delta = r - m; m += delta / (s + 1); m2 = fma(delta, r - m, m2)
