@@ -179,6 +179,9 @@ PROTOTYPES = {
     "diqt_edm_inpaint_churn": (I, [P] * 8 + [I, Z, P]),
     "diqt_volume_joint_heun_inpaint": (I, [P] * 8 + [I] * 10 + [F] * 8 + [I, ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_uint,
                                                                           ctypes.c_uint, P]),
+    "diqt_ddpm_inpaint_paste": (I, [P] * 10 + [I, Z, P]),
+    "diqt_volume_joint_step_inpaint": (I, [P] * 7 + [I] * 11 + [F] * 9 + [I, ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_uint,
+                                                                          ctypes.c_uint, ctypes.c_uint, P]),
     "diqt_volume_joint_finish": (I, [P] * 6 + [I] * 10 + [F, F, F, F, P]),
     "diqt_patch_pair_crop_workspace_bytes": (Z, [I, I]),
     "diqt_patch_pair_crop": (I, [P, P, P, P, P, P, Z, I, I, I, I, I, I, I, F, F, P]),

@@ -664,6 +664,34 @@ __global__ __launch_bounds__(256) void edm_inpaint_churn_kernel(const float* x, 
     if (renoise) t = inpaint_renoise(t, kr[b], renoise[v]);
     out[v] = inpaint_churn(m, kn, t, kc[b], ep);
 }
+// The same loop around the ancestral sampler of the DDPM family (Imagen.p_sample_loop; the reference's imagen_pytorch3D.py:2116-2146),
+// again ONE definition for the per-window pass and the joint pass:
+//   ddpm_renoise   q_sample_from_to(img, t_next, t), the re-noise that ends a pass:  axpby3(img, n, renoise[i,0], renoise[i,1]);
+//   ddpm_paste     q_sample(known, t) under the mask, t elsewhere: q_sample IS axpby3(known, nq, alpha, sigma), and mask_blend after it a
+//                  pure selection -- an unmasked element keeps its bits (a -0 stays -0), there is no product to add.
+__device__ __forceinline__ float ddpm_renoise(float x, float kr0, float kr1, float n) { return axpby_update(kr0, x, kr1, n); }
+__device__ __forceinline__ float ddpm_paste(bool m, float known, float al, float sg, float nq, float t) {
+    return m ? axpby_update(al, known, sg, nq) : t;
+}
+// The per-window pass boundary: x / renoise / known / qnoise / out [B][per], mask one byte per element, kr0 / kr1 / al / sg device
+// [B].  renoise == NULL: no re-noise (kr0 / kr1 are not read).  out may alias x.  Geometry and the order of loads and the store as in
+// edm_inpaint_churn_kernel.
+__global__ __launch_bounds__(256) void ddpm_inpaint_paste_kernel(const float* x, const float* __restrict__ renoise,
+                                                                 const float* __restrict__ known,
+                                                                 const unsigned char* __restrict__ mask,
+                                                                 const float* __restrict__ qnoise, const float* __restrict__ kr0,
+                                                                 const float* __restrict__ kr1, const float* __restrict__ al,
+                                                                 const float* __restrict__ sg, float* out, size_t per) {
+    const int b = blockIdx.y;
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.y * 64 + threadIdx.x;
+    if (e >= per) return;
+    const size_t v = (size_t)b * per + e;
+    const bool m = mask[v] != 0;
+    const float kn = known[v], nq = qnoise[v];
+    float t = x[v];
+    if (renoise) t = ddpm_renoise(t, kr0[b], kr1[b], renoise[v]);
+    out[v] = ddpm_paste(m, kn, al[b], sg[b], nq, t);
+}
 __global__ __launch_bounds__(256) void volume_joint_heun_kernel(const float* __restrict__ y, const int* __restrict__ slot,
                                                                 const float* __restrict__ taps, float* xh, float* xn, float* x0v,
                                                                 int phase, int N, int D, int H, int W, int P, int stride, int G0, int G1,
@@ -756,6 +784,57 @@ __global__ __launch_bounds__(256) void volume_joint_heun_inpaint_kernel(const fl
     r = kc != 0.f ? inpaint_churn(m, kn, r, kc, philox_normal(philox4x32_10(v0, v1, draw, sample, key0, key1))) : (m ? kn : r);
     xh[v] = r;
     x0v[v] = x0b;
+}
+// The inpainting loop of the DDPM family on the joint state (diqt_volume_joint_step_inpaint): the first-order step of
+// volume_joint_linear_kernel with the pass boundary of ddpm_inpaint_paste_kernel behind it, x updated in place.  `phase` and `flags` are
+// uniform over the launch:
+//   phase 0 (no y, every voxel)   x = ddpm_paste(m, known, al, sg, n(draw_q), n(draw)): the initial image under the first paste;
+//   phase 1 (after the windows)   x0 = sum(w c(y)) / sum(w); u = sampler_update(kx, x, k0, x0, kn, n(draw)) (the product added also when
+//                                 it is 0, no Philox call when kn == 0); flags & 1: u = ddpm_renoise(u, kr0, kr1, n(draw_r)), the re-noise
+//                                 that ends a pass; flags & 2: x = ddpm_paste(m, known, al, sg, n(draw_q), u), the paste that begins the
+//                                 next pass with ITS step's (al, sg); else x = u.  x0_out (may be NULL) = x0.
+// A masked voxel with a paste following stores a value that does not depend on u: it computes n(draw_q) alone -- no step, no other
+// normal.  A voxel no kept window covers: phase 1 leaves x and writes x0_out = 0.  The stores follow the last use of a load.
+__global__ __launch_bounds__(256) void volume_joint_step_inpaint_kernel(const float* __restrict__ y, const int* __restrict__ slot,
+                                                                        const float* __restrict__ taps, float* x, float* x0_out,
+                                                                        const float* __restrict__ known,
+                                                                        const unsigned char* __restrict__ mask, int phase, int flags,
+                                                                        int N, int D, int H, int W, int P, int stride, int G0, int G1,
+                                                                        int G2, float kx, float k0, float kn, float kr0, float kr1,
+                                                                        float al, float sg, float lo, float hi, int clamp_mode,
+                                                                        unsigned key0, unsigned key1, unsigned draw, unsigned draw_r,
+                                                                        unsigned draw_q, unsigned sample) {
+    extern __shared__ float tp[];                      // [P]
+    const Voxel p = walk_prologue(tp, taps, P, phase == 1, H, W);
+    if (!p.inside) return;
+    const size_t v = p.v;
+    const unsigned v0 = (unsigned)v, v1 = (unsigned)((unsigned long long)v >> 32);
+    if (phase == 0) {
+        float r;
+        if (mask[v] != 0) r = ddpm_paste(true, known[v], al, sg, philox_normal(philox4x32_10(v0, v1, draw_q, sample, key0, key1)), 0.f);
+        else r = philox_normal(philox4x32_10(v0, v1, draw, sample, key0, key1));
+        x[v] = r;
+        return;
+    }
+    const Fused f = joint_fuse(y, slot, taps, tp, N, P, stride, G0, G1, G2, p, StepClamp{lo, hi, clamp_mode});
+    if (!f.covered()) {
+        if (x0_out) x0_out[v] = 0.f;
+        return;
+    }
+    const bool pasted = (flags & 2) && mask[v] != 0;
+    const float xt = x[v], kv = known[v];
+    const float x0 = f.x0();
+    float r;
+    if (pasted) {
+        r = ddpm_paste(true, kv, al, sg, philox_normal(philox4x32_10(v0, v1, draw_q, sample, key0, key1)), 0.f);
+    } else {
+        float n = 0.f;
+        if (kn != 0.f) n = philox_normal(philox4x32_10(v0, v1, draw, sample, key0, key1));
+        r = sampler_update(kx, xt, k0, x0, kn, n);
+        if (flags & 1) r = ddpm_renoise(r, kr0, kr1, philox_normal(philox4x32_10(v0, v1, draw_r, sample, key0, key1)));
+    }
+    if (x0_out) x0_out[v] = x0;
+    x[v] = r;
 }
 
 // The end of sample s of S: r = min_val on the background (background_reset_kernel's expression on the RAW vol), else x where a kept
@@ -1144,6 +1223,38 @@ extern "C" int diqt_volume_joint_heun_inpaint(const float* y, const int* slot, c
                        N, D, H, W, P, stride, G0, G1, G2, a, b, c, d, kr, kc, lo, hi, clamp_mode, (unsigned)seed, (unsigned)(seed >> 32),
                        draw, draw_r, sample);
     return check_launch("volume_joint_heun_inpaint");
+}
+
+extern "C" int diqt_ddpm_inpaint_paste(const float* x, const float* renoise, const float* known, const unsigned char* mask,
+                                       const float* qnoise, const float* kr0, const float* kr1, const float* al, const float* sg,
+                                       float* out, int B, size_t per_batch, void* stream) {
+    DIQT_REQUIRE(x && known && mask && qnoise && al && sg && out && ((kr0 && kr1) || !renoise), DIQT_E_ALIGN,
+                 "ddpm_inpaint_paste: null pointer");
+    DIQT_REQUIRE(B > 0 && per_batch > 0, DIQT_E_SHAPE, "ddpm_inpaint_paste: bad shape (B %d, per_batch %zu)", B, per_batch);
+    DIQT_REQUIRE(B <= 65535 && (per_batch + 255) / 256 <= 0x7fffffffu, DIQT_E_SHAPE,
+                 "ddpm_inpaint_paste: more than 65535 samples or 2^31 - 1 blocks per sample");
+    hipLaunchKernelGGL(ddpm_inpaint_paste_kernel, dim3((unsigned)((per_batch + 255) / 256), B), dim3(64, 4), 0, STREAM, x, renoise, known,
+                       mask, qnoise, kr0, kr1, al, sg, out, per_batch);
+    return check_launch("ddpm_inpaint_paste");
+}
+
+extern "C" int diqt_volume_joint_step_inpaint(const float* y, const int* slot, const float* taps, float* x, float* x0_out,
+                                              const float* known, const unsigned char* mask, int phase, int flags, int N, int D, int H,
+                                              int W, int P, int stride, int G0, int G1, int G2, float kx, float k0, float kn, float kr0,
+                                              float kr1, float al, float sg, float lo, float hi, int clamp_mode, unsigned long long seed,
+                                              unsigned draw, unsigned draw_r, unsigned draw_q, unsigned sample, void* stream) {
+    DIQT_REQUIRE(phase == 0 || phase == 1, DIQT_E_UNSUPPORTED, "volume_joint_step_inpaint: phase %d (0 = init and paste, 1 = step)", phase);
+    DIQT_REQUIRE(flags >= 0 && flags <= 3, DIQT_E_UNSUPPORTED, "volume_joint_step_inpaint: flags %d (bit 0 = re-noise, bit 1 = paste)",
+                 flags);
+    DIQT_REQUIRE(known && mask, DIQT_E_ALIGN, "volume_joint_step_inpaint: null pointer");
+    JointGrid g;
+    int rc = joint_launch_plan("volume_joint_step_inpaint", x, phase == 1, slot && taps && (y || N == 0), N, D, H, W, P, stride, G0, G1,
+                               G2, clamp_mode, g);
+    if (rc) return rc;
+    hipLaunchKernelGGL(volume_joint_step_inpaint_kernel, g.grid, dim3(64, 4), g.lds, STREAM, y, slot, taps, x, x0_out, known, mask, phase,
+                       flags, N, D, H, W, P, stride, G0, G1, G2, kx, k0, kn, kr0, kr1, al, sg, lo, hi, clamp_mode, (unsigned)seed,
+                       (unsigned)(seed >> 32), draw, draw_r, draw_q, sample);
+    return check_launch("volume_joint_step_inpaint");
 }
 
 extern "C" int diqt_volume_joint_finish(const float* x, const int* slot, const float* vol, float* mean_io, float* m2_io, float* out_std,

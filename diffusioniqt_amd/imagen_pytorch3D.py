@@ -1160,11 +1160,17 @@ class WindowDenoiser:
       included), the objective's x0 conversion and, if configured, per-row dynamic thresholding -- exactly the tensor ``p_sample_loop``
       passes to ``ops.ddpm_step``;
     * ``finish(x)``: the final clamp and ``unnormalize_img`` on a tensor of any shape;
-    * ``self_cond``: whether the U-Net takes the previous step's x0."""
+    * ``self_cond``: whether the U-Net takes the previous step's x0;
+    * ``sampler='ddpm'`` only -- what ``VolumeInference(joint=True, inpaint=...)`` needs of the one sampler with a re-noising loop:
+      ``normalize(x)`` = ``imagen.normalize_img`` (a known volume into state space; ``sample`` takes its ``inpaint_images`` there
+      already, as the reference does), host fp32 ``qs`` [T,2] = the (alpha, sigma) of ``q_sample`` at every step and ``renoise`` [T,2] =
+      the coefficients of ``q_sample_from_to(img, t_next, t)`` (the row of the step that ends at t = 0 is unused), and
+      ``finish(x, known, mask)`` (see there; ``paste_known``)."""
 
-    def __init__(self, imagen, unet_number, sampler, sample_steps, eta, cond_scale, unet_context):
+    def __init__(self, imagen, unet_number, sampler, sample_steps, eta, cond_scale, unet_context, paste_known=False):
         self.imagen, self.index, self._context = imagen, unet_number - 1, unet_context
         self.sampler, self.sample_steps, self.eta = sampler, sample_steps, eta
+        self.paste_known = paste_known
         self.multistep = sampler == 'dpmpp2m'
         self.cond_scale = cast_tuple(cond_scale, len(imagen.unets))[self.index]
         self.pred_objective = imagen.pred_objectives[self.index]
@@ -1174,6 +1180,9 @@ class WindowDenoiser:
         tables = self._tables(1)
         self.coefs = tables[0][:, :, 0].contiguous()                    # [T, 3] on the host
         self.num_steps = int(self.coefs.shape[0])
+        if sampler == 'ddpm':
+            self.renoise, self.qs = (t[:, :, 0].contiguous() for t in tables[4:6])     # [T, 2] each, on the host
+            self.normalize = imagen.normalize_img
         lo, hi, mode = imagen._clamp_cfg()
         self.clamp = (-float('inf'), float('inf'), 1) if self.dynamic_threshold else (lo, hi, mode)
         self._device_tables = {}
@@ -1208,8 +1217,15 @@ class WindowDenoiser:
         return pred
 
     @torch.no_grad()
-    def finish(self, x):
-        return self.imagen._finish_sample(x.contiguous().view(1, -1)).view(x.shape)
+    def finish(self, x, known=None, mask=None):
+        """``known`` (state space) / ``mask`` (0/1 fp32), both of x's shape: the chain inpainted.  The reference's loop does not paste
+        the known image after the chain (:2154-2159) and by default neither does this; with ``paste_known`` the known values go under
+        the mask between the clamp and ``unnormalize_img``."""
+        flat = x.contiguous().view(1, -1)
+        if known is None or not self.paste_known:
+            return self.imagen._finish_sample(flat).view(x.shape)
+        flat = ops.mask_blend(self.imagen._final_clamp(flat), known.contiguous().view(1, -1), mask.contiguous().view(1, -1))
+        return self.imagen.unnormalize_img(flat).view(x.shape)
 
 
 class Imagen(nn.Module):
@@ -1412,15 +1428,28 @@ class Imagen(nn.Module):
 
     def _finish_sample(self, img):
         """The end of a chain: the final clamp (:2154-2157) and ``unnormalize_img``.  ``img``: [B, ...]."""
+        return self.unnormalize_img(self._final_clamp(img))
+
+    def _final_clamp(self, img):
         lo, hi, mode = self._clamp_cfg()
         one = torch.ones(img.shape[0], device=img.device)
-        return self.unnormalize_img(ops.axpby3(img, None, None, one, None, None, lo, hi, 1 if mode == 0 else 2))
+        return ops.axpby3(img, None, None, one, None, None, lo, hi, 1 if mode == 0 else 2)
+
+    @staticmethod
+    def inpaint_draws(num_steps, resample_times):
+        """How many draws the ancestral chain of ``num_steps`` steps takes when it inpaints with ``resample_times`` passes per step: the
+        initial image; per pass the q-noise and the step noise (taken also on the step that ends at t = 0, where its coefficient is 0);
+        one re-noise per pass that is neither the last of its step nor in the last step."""
+        T, R = int(num_steps), int(resample_times)
+        return 1 + 2 * T * R + (T - 1) * (R - 1)
 
     def window_denoiser(self, unet_number=2, sampler='ddim', sample_steps=None, eta=0.0, cond_scale=1., inpaint_images=None,
-                        inpaint_masks=None, init_images=None, skip_steps=None, _unet_context=nullcontext):
+                        inpaint_masks=None, init_images=None, skip_steps=None, _unet_context=nullcontext, paste_known=False):
         """The per-window half of ``p_sample_loop`` as an object that is called one step at a time -- what
         ``VolumeInference(..., joint=True)`` drives; see ``WindowDenoiser``.  Inpainting, ``init_images`` and ``skip_steps`` belong to
-        the one-call sampler and are refused here (``ValueError``, before anything touches the device)."""
+        the one-call sampler and are refused here (``ValueError``, before anything touches the device); the volume path inpaints on its
+        own state with ``VolumeInference(inpaint=...)`` and a ``sampler='ddpm'`` denoiser, whose ``finish`` pastes the known values
+        after the chain only with ``paste_known=True`` (the reference does not: :2154-2159)."""
         has_inpainting = exists(inpaint_images) and exists(inpaint_masks)
         self._check_sampler_args(sampler, sample_steps, skip_steps, eta, has_inpainting)
         if has_inpainting or exists(inpaint_images) or exists(inpaint_masks):
@@ -1433,7 +1462,7 @@ class Imagen(nn.Module):
             raise ValueError(f"unet_number must be 1 .. {len(self.unets)}, got {unet_number!r}")
         if isinstance(self.unets[unet_number - 1], NullUnet):
             raise ValueError('one cannot sample from null / placeholder unets')
-        return WindowDenoiser(self, int(unet_number), sampler, sample_steps, float(eta), cond_scale, _unet_context)
+        return WindowDenoiser(self, int(unet_number), sampler, sample_steps, float(eta), cond_scale, _unet_context, bool(paste_known))
 
     @torch.no_grad()
     def p_sample_loop(self, unet, shape, *, noise_scheduler, lowres_cond_img=None, cond_images=None, inpaint_images=None,
@@ -1451,7 +1480,13 @@ class Imagen(nn.Module):
         initial image (the kernel's noise operand is one zero tensor); with ``eta > 0`` one more per step, as the ancestral sampler.
         ``sampler='dpmpp2m'`` is the second-order multistep solver (``dpmpp2m_coefficients``; ``eta`` 0, no ``skip_steps``, no
         inpainting): still one U-Net evaluation and the SAME step kernel per step, whose third operand is now the clamped (and, if
-        configured, thresholded) x0 the previous step returned -- one zero tensor on step 0.  It consumes one draw, the initial image."""
+        configured, thresholded) x0 the previous step returned -- one zero tensor on step 0.  It consumes one draw, the initial image.
+
+        ``inpaint_images`` / ``inpaint_masks`` (``sampler='ddpm'``; the images in state space, as the reference takes them): every step
+        runs ``inpaint_resample_times`` passes, r = R - 1 .. 0 (:2116-2146).  A pass draws the q-noise and pastes
+        ``q_sample(inpaint_images, t)`` under the mask, steps as ever (one more draw) and -- unless r == 0 or the step ends at t = 0 --
+        draws once more for the re-noise ``q_sample_from_to(img, t_next, t)``; that re-noise and the paste of the next pass are ONE
+        ``ops.ddpm_inpaint_paste`` launch.  ``inpaint_draws`` counts the draws."""
         if pred_objective not in ('noise', 'x_start', 'v'):
             raise ValueError(f'unknown objective {pred_objective}')
         has_inpainting = exists(inpaint_images) and exists(inpaint_masks)                  # (:2090-2091)
@@ -1471,7 +1506,7 @@ class Imagen(nn.Module):
         resample_times = inpaint_resample_times if has_inpainting else 1
         if has_inpainting:
             inpaint_images = inpaint_images.to(device).float().expand(shape).contiguous()
-            mask_f = inpaint_masks.to(device).bool().expand(shape).float().contiguous()
+            mask_b = inpaint_masks.to(device).bool().expand(shape).to(torch.uint8).contiguous()    # one byte per element, made once
 
         coefs, conds, x0c, last, renoise, qs = self._sampler_tables(noise_scheduler, batch, sampler, sample_steps, skip_steps, eta,
                                                                     pred_objective)
@@ -1488,12 +1523,17 @@ class Imagen(nn.Module):
 
         noisy_dev, x0_dev = [], []
         x_start = None
+        renoise_n = None                       # the normals of the re-noise that ended the pass before, until the next paste takes them
         for i in range(coefs.shape[0]):
             all_last = bool(last[i].all())
             for r in reversed(range(resample_times)):
-                if has_inpainting:                                                         # (:2119-2123)
-                    noised = ops.q_sample(inpaint_images, draw(), qs[i, 0], qs[i, 1])
-                    img = ops.mask_blend(img, noised, mask_f)
+                if has_inpainting:
+                    # the paste (:2119-2123) and, riding with it, the re-noise of the pass before (:2139-2146): ONE launch.  The first
+                    # pass of a step gets a new tensor (``img`` is the one ``noisy_dev`` or the caller's noise holds), the others run
+                    # in place on the step kernel's output
+                    img = ops.ddpm_inpaint_paste(img, renoise_n, inpaint_images, mask_b, draw(), renoise[i, 0], renoise[i, 1], qs[i, 0],
+                                                 qs[i, 1], out=None if r == resample_times - 1 else img)
+                    renoise_n = None
                 pred = self._x0_prediction(unet, img, conds[i], x0c[i], lowres, x_start if unet.self_cond else None, cond_images,
                                            cond_scale, pred_objective, dynamic_threshold)
                 third = x_start if multistep and i > 0 else step_noise()      # 'dpmpp2m': the previous step's clamped x0
@@ -1501,8 +1541,8 @@ class Imagen(nn.Module):
                     img, x_start = ops.ddpm_step(img, pred, third, coefs[i, 0], coefs[i, 1], coefs[i, 2], -inf, inf, 1)
                 else:
                     img, x_start = ops.ddpm_step(img, pred, third, coefs[i, 0], coefs[i, 1], coefs[i, 2], lo, hi, mode)
-                if has_inpainting and not (r == 0 or all_last):                            # (:2139-2146)
-                    img = ops.axpby3(img, draw(), None, renoise[i, 0], renoise[i, 1], None, 0.0, 0.0, 0)
+                if has_inpainting and not (r == 0 or all_last):                            # (:2139-2146): applied by the next paste
+                    renoise_n = draw()
             noisy_dev.append(img)
             x0_dev.append(x_start)
         noisy_dev.append(img)

@@ -70,7 +70,12 @@ the volume is generated (RePaint, Lugmayr et al. 2022; the loop of the reference
 and blend modes every sampler call gets its windows of the two volumes and inpaints on its own -- each window resamples its own border of a
 known region that crosses it.  With ``joint=True`` and the Heun denoiser the loop runs on the one state: R passes per step, the pass
 boundary (re-noise, paste, churn) riding in the corrector launch (``ops.volume_joint_heun_inpaint``), 2 R T - 1 fused launches after the
-initial state for T steps, and one paste per sample before ``ops.volume_joint_finish``.
+initial state for T steps, and one paste per sample before ``ops.volume_joint_finish``.  With ``joint=True`` and the ancestral denoiser
+of the DDPM family (``Imagen.window_denoiser(sampler='ddpm')``; the loop of the reference's ``Imagen.p_sample_loop``) it runs on the one
+state too: the initial image under the first paste, then R passes per step, each one evaluation and ONE ``ops.volume_joint_step_inpaint``
+launch that carries the step, the re-noise and the paste of the next pass -- 1 + R T fused launches.  That family's loop does not paste
+the known values after the chain, so a known voxel comes back denoised, not exactly, unless the denoiser was made with
+``paste_known=True``.
 """
 from types import SimpleNamespace
 
@@ -199,6 +204,8 @@ class VolumeInference:
       ``finish(x)``, applied to the volume a chain ends in;
     * optional, False when absent: ``self_cond`` (the windows of the last fused x0 volume are passed as ``self_cond=``), ``multistep``
       (``coefs`` rows are (kx, k0, kp)) and ``heun``;
+    * first order with ``inpaint=``: host tables ``qs`` [T,2] (alpha, sigma) and ``renoise`` [T,2], ``normalize(x)`` (a known volume
+      into state space) and ``finish(x, known, mask)`` (``known`` in state space, ``mask`` 0/1; whether it pastes is the denoiser's);
     * with ``heun``: ``coefs`` rows (kc, a1, b1, a2, b2, c2, d2); ``sigma0``; ``sched`` rows (sigma, sigma_next, gamma), sigma_next == 0
       meaning no corrector; ``draw_base`` (1 when draw 0 is the low-res augmentation noise: the initial image is draw ``draw_base``, the
       eps of step i draw ``draw_base + 1 + i``); ``x0`` also takes ``stage=`` (0: at sigma_hat, 1: at sigma_next) and ``lowres_noise=``;
@@ -219,6 +226,8 @@ class VolumeInference:
         p.sigma_space = p.multistep and not p.heun and hasattr(den, 'sigma0')
         if p.sigma_space:
             p.draw_base, p.sigma0 = int(den.draw_base), float(den.sigma0)
+        if hasattr(den, 'qs') and hasattr(den, 'renoise'):   # the ancestral sampler's inpainting tables
+            p.qs, p.renoise = den.qs.tolist(), den.renoise.tolist()
         return p
 
     @staticmethod
@@ -235,9 +244,12 @@ class VolumeInference:
                              f"{tuple(known.shape)} and {mask.dtype} {tuple(mask.shape)}")
         if isinstance(resample_times, bool) or not isinstance(resample_times, int) or resample_times < 1:
             raise ValueError(f"VolumeInference: inpaint_resample_times must be a positive integer, got {resample_times!r}")
-        if joint and not (getattr(sample_fn, 'heun', False) and hasattr(sample_fn, 'normalize')):
-            raise ValueError("VolumeInference: joint=True inpaints with an EDM Heun denoiser (ElucidatedImagen.window_denoiser()) only: the "
-                             "first-order and multistep chains have no re-noising loop")
+        heun = getattr(sample_fn, 'heun', False)
+        ancestral = not heun and not getattr(sample_fn, 'multistep', False) and hasattr(sample_fn, 'qs') and hasattr(sample_fn, 'renoise')
+        if joint and not ((heun or ancestral) and hasattr(sample_fn, 'normalize')):
+            raise ValueError("VolumeInference: joint=True inpaints with an EDM Heun denoiser (ElucidatedImagen.window_denoiser()) or the "
+                             "ancestral one of the DDPM family (Imagen.window_denoiser(sampler='ddpm')) only: the other first-order "
+                             "chains and the multistep chains have no re-noising loop")
         return known.float(), mask
 
     def _inpaint_volumes(self, win):
@@ -264,12 +276,16 @@ class VolumeInference:
         z-scored prediction) and ``mask`` bool [D,H,W], True where ``known`` is to be kept while the rest is generated (RePaint).  In the
         crop and blend modes every call becomes ``sample_fn(x[, noise=src], inpaint_images=kw, inpaint_masks=mw,
         inpaint_resample_times=R)`` with the batch's windows of the two volumes; with ``joint=True`` and an EDM Heun denoiser
-        (``ElucidatedImagen.window_denoiser()``) the loop runs on the one state, so a known region that crosses window borders is
-        resampled once, not once per window.  A known voxel comes back exactly, except where the fill or the background reset applies:
-        they come last, as in every mode, and override known values on uncovered and background voxels.  ``ValueError`` naming "inpaint"
-        before anything touches the device: a pair that is not (float [D,H,W], bool [D,H,W]) of one shape -- or, in ``__call__``, not the
-        volume's --, ``inpaint_resample_times`` that is not a positive integer, joint mode with a denoiser that is not ``heun`` (the
-        first-order and multistep chains have no re-noising loop)."""
+        (``ElucidatedImagen.window_denoiser()``) or the ancestral denoiser of the DDPM family
+        (``Imagen.window_denoiser(sampler='ddpm')``) the loop runs on the one state, so a known region that crosses window borders is
+        resampled once, not once per window.  With the EDM family -- and with ``Imagen`` in joint mode when its denoiser was made with
+        ``paste_known=True`` -- a known voxel comes back exactly, except where the fill or the background reset applies: they come
+        last, as in every mode, and override known values on uncovered and background voxels.  ``Imagen``'s own loop ends on a
+        denoising step without a paste (as the reference's does), so there a known voxel comes back as the last step left it.
+        ``ValueError`` naming "inpaint" before anything touches the device: a pair that is not (float [D,H,W], bool [D,H,W]) of one
+        shape -- or, in ``__call__``, not the volume's --, ``inpaint_resample_times`` that is not a positive integer, joint mode with a
+        denoiser that is neither ``heun`` nor one with the ancestral sampler's ``qs`` / ``renoise`` tables (DDIM and the multistep
+        chains have no re-noising loop)."""
         self.inpaint = self._check_inpaint(inpaint, inpaint_resample_times, joint, sample_fn)
         self.resample_times = inpaint_resample_times
         if noise not in NOISE_MODES:
@@ -430,10 +446,33 @@ class VolumeInference:
             return den.x0(xw, lw, i, self_cond=sc, lowres_noise=ln, **kw)
         return x0
 
-    def _linear_chain(self, den, win, evaluate, y, s):
+    def _linear_chain(self, den, win, evaluate, y, s, known=None, mask=None):
         """Sample ``s`` of a chain whose step is ONE fused launch, in place on the state ``x`` and on ``win.x0_vol`` (the fused x0, which
         self-conditioning gathers at the next step and the multistep families read as their history term before it is overwritten).
-        The family chooses the first state and the launch; the draws are the module docstring's."""
+        The family chooses the first state and the launch; the draws are the module docstring's.
+
+        With ``known`` (fp32 [D,H,W] in state space) and ``mask`` (uint8 [D,H,W]) the ancestral chain inpaints (``_check_inpaint`` has
+        admitted the denoiser): the initial image under the first paste (``ops.volume_joint_step_inpaint_init``), then T steps of
+        ``self.resample_times`` passes, each one evaluation and ONE ``ops.volume_joint_step_inpaint`` launch that carries the step, the
+        re-noise of a pass that is neither the last of its step nor in the step that ends at t = 0 (flags bit 0) and the paste of the
+        next pass with that pass's (alpha, sigma) (bit 1) -- 1 + R T fused launches.  ONE draw counter advances as the per-window
+        ``p_sample_loop`` calls its source: the initial image, then per pass the q-noise, the step noise (counted also where kn == 0)
+        and, where there is one, the re-noise -- so at stride = patch the chain is ``sample(noise=source, inpaint_images=...)`` per
+        window."""
+        if known is not None:
+            T = den.num_steps
+            passes = [(i, r) for i in range(T) for r in reversed(range(self.resample_times))]
+            x = ops.volume_joint_step_inpaint_init(known, mask, *den.qs[0], self.seed, draw=0, draw_q=1, sample=s)
+            draw = 2                                         # the next draw of the state: the initial image and the first q-noise are taken
+            for n, (i, r) in enumerate(passes):
+                evaluate(x, win.x0_vol if den.self_cond and n > 0 else None, self._window_x0(den, win, s, i))
+                renoise, more = r > 0 and i + 1 < T, n + 1 < len(passes)
+                ops.volume_joint_step_inpaint(y, win.slot, win.taps, x, known, mask, int(renoise) + 2 * int(more), *den.coefs[i],
+                                              den.renoise[i] if renoise else (0., 0.), den.qs[passes[n + 1][0]] if more else (0., 0.),
+                                              *den.clamp, self.overlap, self.seed, draw=draw, draw_r=draw + 1 if renoise else 0,
+                                              draw_q=draw + 1 + renoise if more else 0, sample=s, x0_out=win.x0_vol)
+                draw += 1 + int(renoise) + int(more)
+            return x
         if den.sigma_space:                                  # sigma0 n(draw_base)
             x, _ = ops.volume_joint_multistep_sde(None, None, None, None, None, 0., 0., 0., den.sigma0, *den.clamp, self.overlap, self.seed,
                                                   draw=den.draw_base, sample=s, shape=win.shape, device=win.device)

@@ -2754,6 +2754,72 @@ def volume_joint_heun_inpaint(y, slot, taps, xh, xn, x0, known, mask, phase, coe
     return xh, xn, x0
 
 
+def ddpm_inpaint_paste(x, renoise, known, mask, qnoise, kr0, kr1, al, sg, out=None):
+    """One pass boundary of the DDPM inpainting loop on a window batch (include/diqt.h, diqt_ddpm_inpaint_paste): ``x`` [B, ...] the
+    state, ``renoise`` the re-noise normals of the pass that just ended (None: no re-noise, ``kr0`` / ``kr1`` may be None too), ``known``
+    the known image in state space, ``mask`` one byte per element (uint8 or bool; non-zero: known), ``qnoise`` the normals of the known
+    image's forward sample, ``kr0`` / ``kr1`` / ``al`` / ``sg`` device [B].  out = sel(mask, al known + sg qnoise, kr0 x + kr1 renoise)
+    with the roundings of the ``axpby3``, ``q_sample`` and ``mask_blend`` calls it replaces.  ``out``: where it goes (``x`` itself for an
+    in-place pass; None: a new tensor).  Returns ``out``.  One launch."""
+    who = "ddpm_inpaint_paste"
+    _chk(x, renoise, known, qnoise, kr0, kr1, al, sg, out)
+    if x.ndim < 2 or x.numel() == 0:
+        raise ValueError(f"{who}: x must be a non-empty [B, ...] tensor, got {tuple(x.shape)}")
+    B = x.shape[0]
+    if B > 65535:
+        raise ValueError(f"{who}: at most 65535 samples per launch, got {B}")
+    if out is None:
+        out = torch.empty_like(x)
+    for t, name in ((renoise, 'renoise'), (known, 'known'), (qnoise, 'qnoise'), (out, 'out')):
+        if t is not None and t.shape != x.shape:
+            raise ValueError(f"{who}: {name} must have x's shape {tuple(x.shape)}, got {tuple(t.shape)}")
+    _chk_mask(who, mask, x)
+    if renoise is not None and (kr0 is None or kr1 is None):
+        raise ValueError(f"{who}: a re-noise needs its coefficients kr0 and kr1")
+    for t, name in ((kr0, 'kr0'), (kr1, 'kr1'), (al, 'al'), (sg, 'sg')):
+        if t is not None and tuple(t.shape) != (B,):
+            raise ValueError(f"{who}: {name} must be a [B] = [{B}] tensor, got {tuple(t.shape)}")
+    _lib.call("diqt_ddpm_inpaint_paste", x, renoise, known, mask, qnoise, kr0, kr1, al, sg, out, B, x.numel() // B, _stream())
+    return out
+
+
+def volume_joint_step_inpaint_init(known, mask, al, sg, seed, draw=0, draw_q=1, sample=0):
+    """The first state of a joint first-order chain that inpaints (phase 0 of ``diqt_volume_joint_step_inpaint``): a new fp32 [D,H,W]
+    volume, ``sel(mask, al known + sg n(draw_q), n(draw))`` -- ``volume_joint_init`` under the first paste of the known volume (in state
+    space, fp32 [D,H,W]; ``mask`` uint8 or bool [D,H,W])."""
+    who = "volume_joint_step_inpaint_init"
+    _joint_known(who, known, mask, known.shape)              # the mask against known; the shape itself below
+    draw_q = _noise_key(who, seed, draw_q, sample)[1]
+    return _joint_initial(who, "diqt_volume_joint_step_inpaint", lambda out: (None, None, None, out, None, known, mask, 0, 0, 0),
+                          (0.0, 0.0, 0.0, 0.0, 0.0, al, sg, 0.0, 0.0), known.shape, "known must be", seed, draw, sample, known.device,
+                          more_draws=(0, draw_q))
+
+
+def volume_joint_step_inpaint(y, slot, taps, x, known, mask, flags, kx, k0, kn, kr, q, lo, hi, clamp_mode, stride, seed, draw, draw_r=0,
+                              draw_q=0, sample=0, x0_out=None):
+    """One pass of a joint first-order chain that inpaints (include/diqt.h, diqt_volume_joint_step_inpaint, phase 1), IN PLACE on the
+    state ``x`` [D,H,W]: ``volume_joint_step``'s u = kx x + k0 x0 + kn n(draw) on covered voxels; with ``flags`` bit 0
+    u = kr[0] u + kr[1] n(draw_r), the re-noise that ends a pass; with bit 1 x = sel(mask, q[0] known + q[1] n(draw_q), u), the paste
+    that begins the next pass (``q`` = the (alpha, sigma) of that pass's step), else x = u.  ``known`` fp32 [D,H,W] in state space,
+    ``mask`` uint8 or bool [D,H,W]; ``x0_out`` (optional [D,H,W]) receives the fused x0 (0 where uncovered).  Uncovered voxels keep
+    ``x``.  Returns ``x``.  One launch, bit-reproducible."""
+    who = "volume_joint_step_inpaint"
+    flags = int(flags)
+    if flags not in (0, 1, 2, 3):
+        raise ValueError(f"{who}: flags must be 0 .. 3 (bit 0: re-noise, bit 1: paste), got {flags!r}")
+    N, P, stride = _joint_windows(who, y, slot, taps, x, clamp_mode, stride)
+    seed, draw, sample = _noise_key(who, seed, draw, sample)
+    draw_r, draw_q = (_noise_key(who, seed, d, sample)[1] for d in (draw_r, draw_q))
+    _joint_slots(who, slot, N)
+    _, x0_out = _joint_volumes(who, x, None, x, x0_out, need_x0=False)
+    _joint_known(who, known, mask, x.shape)
+    (kr0, kr1), (al, sg) = (float(v) for v in kr), (float(v) for v in q)
+    _lib.call("diqt_volume_joint_step_inpaint", y if N else None, slot, taps, x, x0_out, known, mask, 1, flags, N, *x.shape, P, stride,
+              *slot.shape, float(kx), float(k0), float(kn), kr0, kr1, al, sg, float(lo), float(hi), int(clamp_mode), seed, draw, draw_r,
+              draw_q, sample, _stream())
+    return x
+
+
 def volume_joint_finish(x, slot, vol, P, stride, mean, std, min_val, fill, s, S, mean_io=None, m2_io=None, want_std=False):
     """The end of sample ``s`` of ``S`` joint chains (include/diqt.h, diqt_volume_joint_finish): the finished state ``x`` [D,H,W] with
     ``fill`` where no kept window of ``slot`` covers and ``min_val`` on the background of the raw ``vol`` enters the running Welford

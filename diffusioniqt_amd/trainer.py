@@ -925,7 +925,7 @@ class ImagenTrainer(nn.Module):
 
     def window_denoiser(self, *args, use_non_ema=False, **kwargs):
         """``Imagen.window_denoiser`` with the U-Net choice of ``sample``: every ``x0`` call runs inside ``use_ema_unets()`` (the EMA
-        weights) unless ``use_non_ema``."""
+        weights) unless ``use_non_ema``.  Every other argument, ``paste_known`` included, is passed through."""
         return self.imagen.window_denoiser(*args, _unet_context=nullcontext if use_non_ema else self.use_ema_unets, **kwargs)
 
     def _autocast(self):

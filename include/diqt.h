@@ -739,6 +739,38 @@ int diqt_volume_joint_heun_inpaint(const float* y, const int* slot, const float*
                                    int stride, int G0, int G1, int G2, float a, float b, float c, float d, float kr, float kc, float lo,
                                    float hi, int clamp_mode, unsigned long long seed, unsigned draw, unsigned draw_r, unsigned sample,
                                    void* stream);
+/* One pass boundary of the inpainting (RePaint) loop around the ancestral sampler of the DDPM family, per window batch
+ * (imagen_pytorch3D.py:2139-2146, `renoised_img = noise_scheduler.q_sample_from_to(img, times_next, times)`, then :2119-2123 of the
+ * next pass, `noised_inpaint_images = noise_scheduler.q_sample(inpaint_images, t = times)` under the mask) -- the re-noise that ends
+ * pass r and the paste that begins the next pass in ONE launch, in place of diqt_axpby3, diqt_q_sample and diqt_mask_blend with two
+ * temporaries and a float mask.  x / renoise / known / qnoise / out are [B][per_batch], mask one byte per element (non-zero: known),
+ * kr0 / kr1 / al / sg DEVICE [B]:
+ *     t = renoise ? fmaf(kr1, renoise, kr0 * x) : x;  out = mask ? fmaf(sg, qnoise, al * known) : t
+ * -- the roundings of diqt_axpby3(x, renoise, kr0, kr1) and of diqt_q_sample(known, qnoise, al, sg), which is diqt_axpby3, with
+ * diqt_mask_blend's pure selection behind them.  renoise == NULL: no re-noise, kr0 and kr1 are not read (the first paste of a chain,
+ * the first pass of a step, every pass of the step that ends at t = 0).  out may alias x (every thread reads its own element, then
+ * writes it).  Error codes and limits are diqt_edm_inpaint_churn's.                                                                */
+int diqt_ddpm_inpaint_paste(const float* x, const float* renoise, const float* known, const unsigned char* mask, const float* qnoise,
+                            const float* kr0, const float* kr1, const float* al, const float* sg, float* out, int B, size_t per_batch,
+                            void* stream);
+/* The same loop on the joint state: the first-order step of diqt_volume_joint_step, in place on x, plus known [D][H][W] (in state
+ * space), mask (uint8 [D][H][W]), the pass boundary's coefficients and three draw indices.  `phase`:
+ *   0  x = m ? fmaf(sg, n(draw_q), al * known) : n(draw): the initial image (:2080) under the first paste (:2119-2123).  Every voxel;
+ *      the window arguments, x0_out, flags, kx .. kr1, draw_r and the clamp are ignored.
+ *   1  x0 = sum(w c(y)) / sum(w) and u = kx x + k0 x0 + kn n(draw) exactly as diqt_volume_joint_step forms them (the product added
+ *      also when it is 0, no normal computed when kn == 0); `flags` bit 0: u = fmaf(kr1, n(draw_r), kr0 * u), the re-noise that ends a
+ *      pass which is not the last of its step (:2139-2146); bit 1: x = m ? fmaf(sg, n(draw_q), al * known) : u, the paste that begins
+ *      the next pass, (al, sg) being THAT pass's step's; else x = u.  x0_out (may be NULL) = x0.  Uncovered voxel: x is left as it
+ *      is, x0_out = 0.
+ * The two updates are diqt_ddpm_inpaint_paste's, so at stride = patch the chain is the per-window loop bit for bit.  A thread computes
+ * only the normals whose result it stores: a masked voxel with a paste following n(draw_q) alone.  known / mask / x null, or a window
+ * pointer in phase 1: DIQT_E_ALIGN; a lattice that does not match (phase 1): DIQT_E_SHAPE; a phase outside {0, 1}, flags outside
+ * 0 .. 3 or clamp_mode outside {0, 1}: DIQT_E_UNSUPPORTED.                                                                        */
+int diqt_volume_joint_step_inpaint(const float* y, const int* slot, const float* taps, float* x, float* x0_out, const float* known,
+                                   const unsigned char* mask, int phase, int flags, int N, int D, int H, int W, int P, int stride,
+                                   int G0, int G1, int G2, float kx, float k0, float kn, float kr0, float kr1, float al, float sg,
+                                   float lo, float hi, int clamp_mode, unsigned long long seed, unsigned draw, unsigned draw_r,
+                                   unsigned draw_q, unsigned sample, void* stream);
 /* The end of sample s (0-based) of S joint chains: per voxel r = min_val where vol (RAW, may be NULL) has (vol - mean) / std ==
  * min_val (diqt_background_reset's expression), else x (the finished state) where a kept window (slot >= 0) covers the voxel, else
  * `fill`; then diqt_volume_blend's Welford update in sample order, delta = r - m; m += delta / (s + 1); m2 = fma(delta, r - m, m2)
