@@ -206,6 +206,14 @@ PROTOTYPES = {
     "diqt_conv3d_fwd_h": (I, [P, P, P, P, P] + [I] * 17 + [P]),
     "diqt_conv3d_fwd_h_kernel_id": (I, [I] * 19),
     "diqt_get_last_conv_f9h_variant": (I, []),
+    "diqt_conv_packed_split16_elems": (Z, [I, I, I, I, I]),
+    "diqt_conv_pack_weight_split16": (I, [P, P, P, I, I, I, I, I, P]),
+    "diqt_conv3d_fwd_split16_supported": (I, [I] * 15),
+    "diqt_conv3d_fwd_gn_split16_supported": (I, [I] * 16),
+    "diqt_conv3d_fwd_split16_stats_blocks": (I, [I] * 15),
+    "diqt_conv3d_fwd_split16_variant": (I, [I] * 15),
+    "diqt_conv3d_fwd_split16": (I, [P, P, P, P, P, P, P] + [I] * 15 + [P]),
+    "diqt_conv3d_fwd_gn_split16": (I, [P, P, P, P, P, P, P, P, I] + [I] * 15 + [P]),
 }
 
 _lib = None

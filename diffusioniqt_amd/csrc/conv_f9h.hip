@@ -35,7 +35,7 @@ template <class C> static bool f9h_try(H9Geom& g, size_t& lds, unsigned& grid, d
 }
 
 bool f9h_plan(H9Geom& g, size_t& lds, unsigned& grid, int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph,
-              int pw, int epd, int eph, int epw, bool yHalf) {
+              int pw, int epd, int eph, int epw, bool yHalf, bool split) {
     const int mode = diqt_set_conv_f9h_mode(-1);
     const bool k333 = kd == 3 && kh == 3 && kw == 3, k133 = kd == 1 && kh == 3 && kw == 3;
     if (!mode || !(k333 || k133) || Cin % h9::CK != 0 || Cout % 8 != 0 || Cout < 8) return false;
@@ -58,7 +58,11 @@ bool f9h_plan(H9Geom& g, size_t& lds, unsigned& grid, int B, int D, int H, int W
     H9Geom best = g; size_t bl = 0; unsigned bg = 0; double be = 1e300; int bv = -1;
 #define F9H_TRY(CFG, V) { H9Geom t = g; size_t l_; unsigned g_; double e_; \
         if (f9h_try<h9::CFG>(t, l_, g_, e_) && e_ < be) { best = t; bl = l_; bg = g_; be = e_; bv = V; } }
-    if (k333) {
+    if (split) {
+        // the three-product split of an fp32 conv (Cin counts the 16-bit channels: heads and tails): 3x3x3 only, one workgroup per CU
+        if (!k333 || yHalf) return false;
+        F9H_TRY(H9S_333_256, 6)
+    } else if (k333) {
         F9H_TRY(H9_333_256, 1)
         F9H_TRY(H9_333_512, 0)
     } else {
@@ -89,6 +93,12 @@ int f9h_launch(const void* x, const unsigned short* packed_h, const float* bias,
     }
     set_error("conv3d_fwd_h(v9h): no variant %d", g.variant);
     return DIQT_E_UNSUPPORTED;
+}
+
+int f9h_launch_split(const void* x16, const unsigned short* packed_s, const float* bias, const float* residual, float* y, const H9Geom& g,
+                     size_t lds, unsigned grid, void* stream) {
+    f9h_last_variant.store(g.variant);
+    return h9::launch_split(x16, packed_s, bias, residual, y, g, lds, grid, stream);
 }
 
 }  // namespace diqt

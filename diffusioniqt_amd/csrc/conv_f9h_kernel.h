@@ -1,5 +1,5 @@
 // conv_f9h_kernel -- the 16-bit forward conv (fp16 / bf16 operands, fp32 accumulate) rebuilt on conv_fwd9_kernel's structure (round 4).
-// Included by the translation units that instantiate its variants (conv_f9h.hip, conv_f9h_b.hip, conv_f9h_c.hip).
+// Included by the translation units that instantiate its variants (conv_f9h.hip, conv_f9h_b.hip, conv_f9h_c.hip; conv_split16.hip: the SPLIT build).
 //
 // What bounded the round-3 kernels (conv_fwd_h_kernel / conv_fwd_hp_kernel): every operand byte went global -> VGPR -> LDS under one or
 // two barriers per 4-36 MFMAs of a wave, two waves per SIMD at 256 registers, and a 4-way bank conflict on every fragment read
@@ -95,14 +95,23 @@ template <bool BF> __device__ __forceinline__ unsigned pack2(float a, float b) {
 template <bool BF> __device__ __forceinline__ float round_through(float a) { return BF ? (float)(__bf16)a : (float)(_Float16)a; }
 
 // x: 16-bit NDHWC; wp: the packed 16-bit weights of conv_pack_weight_h_kernel, [chunk][tap][co pad 64][32 ci]; y: fp32 or (YH) 16-bit
-template <class C, bool BF, bool YH>
+// SPLIT (fp16 operands, fp32 y): an fp32 conv carried on the 16-bit pipe by the three-product split.  A 32-channel chunk of x and of wp
+// holds 16 fp32 channels as [16 heads xh = fp16(x) | 16 tails xl = fp16((x - xh) 2^11)] (conv_split16.hip writes both), so the k-half q = 0
+// of a tap is heads x heads and the body issues per tap  acc += wh xh (odd taps: acc2),  acc1 += wl xh,  acc1 += wh xl  (the tail x tail
+// term is dropped); the epilogue forms (acc + acc2) + 2^-11 acc1 and does NOT round to the operand type.  Everything else is the 16-bit kernel.
+template <class C, bool BF, bool YH, bool SPLIT = false>
 __global__ __launch_bounds__(256, C::OCC) void conv_f9h_kernel(const void* __restrict__ xv, const unsigned short* __restrict__ wp,
                                                           const float* __restrict__ bias, const float* __restrict__ residual,
                                                           void* __restrict__ yv, H9Geom g) {
     constexpr int T = C::T, HB = C::HB, NPH = C::NPH, NVB = C::NVB, HH = C::HH, HWd = C::HWd, HV = C::HV, NIMG = C::NIMG;
     constexpr int KH = C::KH, KW = C::KW;
+    // SPLIT: a ring of 3 slots (a tap is 3 NVB MFMAs there, so two taps ahead is as far in cycles as 4-6 taps of the 16-bit build): the
+    // 48 registers pay for the third accumulator set
+    constexpr int PD = SPLIT ? 3 : h9::PD;
+    static_assert(T % PD == 0, "the ring slot of a tap is static");
     constexpr int NSP = NIMG == 2 ? T - PD : T;       // taps of a chunk that issue halo pieces (two images: all older than the last tap's weight load)
     constexpr unsigned YE = YH ? 2u : 4u;
+    static_assert(!SPLIT || (!BF && !YH), "the split build has fp16 operands and an fp32 y");
     static_assert(NSP >= 1, "halo pieces need a tap to ride on");
     auto nh_in_tap = [](int t_) constexpr { int n_ = 0; for (int r = 0; r < C::NPH; ++r) n_ += (r * NSP / C::NPH == t_) ? 1 : 0; return n_; };
     extern __shared__ __attribute__((aligned(1024))) char smem[];
@@ -196,10 +205,17 @@ __global__ __launch_bounds__(256, C::OCC) void conv_f9h_kernel(const void* __res
     const int cb = n0 + 32 * wb + 4 * hf;
     const auto rs_b = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(bias), 0, bias ? g.Cout * 4 : 0, 0x00020000);
     f32x16 acc[NVB];
+    f32x16 acc1[SPLIT ? NVB : 1];                             // SPLIT: the head x tail products, scaled by 2^11
+    f32x16 acc2[SPLIT ? NVB : 1];                             // SPLIT: the head x head products of the odd taps -- the fp32 chains of the
+                                                              // dominant term are half as long (their rounding is what is left of the error)
 #pragma unroll
     for (int vb = 0; vb < NVB; ++vb)
 #pragma unroll
         for (int i = 0; i < 16; ++i) acc[vb][i] = 0.f;
+#pragma unroll
+    for (int vb = 0; vb < (SPLIT ? NVB : 1); ++vb)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) { acc1[vb][i] = 0.f; acc2[vb][i] = 0.f; }
 
     // ---- prologue: the first NIMG - 1 units' halo images, the first PD - 1 weight panels ----
     int fit = 0, fc = 0;                                   // (tile iteration, chunk) of the unit being fetched
@@ -233,7 +249,14 @@ __global__ __launch_bounds__(256, C::OCC) void conv_f9h_kernel(const void* __res
             };
             auto mm = [&](u32x4 (&X)[NVB], int t, int q) __attribute__((always_inline)) {
 #pragma unroll
-                for (int vb = 0; vb < NVB; ++vb) acc[vb] = mfma16<BF>(Wr[t % PD][q], X[vb], acc[vb]);
+                for (int vb = 0; vb < NVB; ++vb) {
+                    if (SPLIT && (t & 1)) acc2[vb] = mfma16<BF>(Wr[t % PD][q], X[vb], acc2[vb]);
+                    else acc[vb] = mfma16<BF>(Wr[t % PD][q], X[vb], acc[vb]);
+                }
+            };
+            auto mm1 = [&](u32x4 (&X)[NVB], int t, int q) __attribute__((always_inline)) {      // SPLIT: the cross products
+#pragma unroll
+                for (int vb = 0; vb < (SPLIT ? NVB : 1); ++vb) acc1[vb] = mfma16<BF>(Wr[t % PD][q], X[vb], acc1[vb]);
             };
             rd(X0, 0, 0);                                  // cold read of the chunk's first half-tap (the image was published by the barrier)
 #pragma unroll
@@ -246,6 +269,7 @@ __global__ __launch_bounds__(256, C::OCC) void conv_f9h_kernel(const void* __res
                 __builtin_amdgcn_sched_barrier(0);
                 rd(X1, t, 1);
                 mm(X0, t, 0);
+                if constexpr (SPLIT) mm1(X0, t, 1);        // tails of w x heads of x
                 // (in program order BEHIND the first half's fragment reads and in front of the second half's: to the compiler a halo DMA is
                 // a store into the LDS that no fragment read may cross)
 #pragma unroll
@@ -253,12 +277,13 @@ __global__ __launch_bounds__(256, C::OCC) void conv_f9h_kernel(const void* __res
                     if (r * NSP / NPH == t) dma_h(r, fbase, fc);
                 w_load((t + PD - 1) % PD);
                 if (t + 1 < T) rd(X0, t + 1, 0);
-                mm(X1, t, 1);
+                if constexpr (SPLIT) mm1(X1, t, 0);        // heads of w x tails of x: two fragment reads per three MFMAs
+                else mm(X1, t, 1);
 #pragma unroll
-                for (int u = 0; u < 2 * NVB; ++u) {
+                for (int u = 0; u < (SPLIT ? 3 : 2) * NVB; ++u) {
                     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
                     if (u >= NVB && u < NVB + 4) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+                    if (u < 2 * NVB) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
                 }
             }
             (void)nh_in_tap;
@@ -314,11 +339,17 @@ __global__ __launch_bounds__(256, C::OCC) void conv_f9h_kernel(const void* __res
                     } else {
                         f32x4v p;
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) p[e] = round_through<BF>(acc[vb][4 * g4 + e] + b4[g4][e]);
+                        for (int e = 0; e < 4; ++e) {
+                            if constexpr (SPLIT) p[e] = fmaf(acc1[vb][4 * g4 + e], 0x1p-11f, acc[vb][4 * g4 + e] + acc2[vb][4 * g4 + e]) + b4[g4][e];
+                            else p[e] = round_through<BF>(acc[vb][4 * g4 + e] + b4[g4][e]);
+                        }
                         *reinterpret_cast<f32x4v*>(scrb + l31 * SROW + 32 * g4 + 16 * hf) = p;
                     }
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) acc[vb][4 * g4 + e] = 0.f;
+                    for (int e = 0; e < 4; ++e) {
+                        acc[vb][4 * g4 + e] = 0.f;
+                        if constexpr (SPLIT) { acc1[vb][4 * g4 + e] = 0.f; acc2[vb][4 * g4 + e] = 0.f; }
+                    }
                 }
 #pragma unroll
                 for (int k = 0; k < NK; ++k) {
@@ -399,6 +430,7 @@ __global__ __launch_bounds__(256, C::OCC) void conv_f9h_kernel(const void* __res
 // the variants (filter, tile, images); H9Geom::variant indexes this list
 using H9_333_512 = Cfg<3, 3, 3, 8, 8, 8, 2>;
 using H9_333_256 = Cfg<3, 3, 3, 4, 8, 8, 2, 2>;      // 256-voxel tiles, TWO workgroups per CU (256 registers per wave): one's epilogue / barrier waits under the other's MFMAs
+using H9S_333_256 = Cfg<3, 3, 3, 4, 8, 8, 2>;         // the split build's 256-voxel tile: ONE workgroup per CU (two accumulator sets)
 using H9_133_A = Cfg<1, 3, 3, 1, 16, 32, 3>;
 using H9_133_B = Cfg<1, 3, 3, 2, 16, 16, 3>;
 using H9_133_C = Cfg<1, 3, 3, 4, 8, 8, 3>;
@@ -415,10 +447,22 @@ template <class C> static int launch_cfg(const void* x, const unsigned short* wp
     return check_launch("conv3d_fwd_h(v9h)");
 }
 
+template <class C> static int launch_split_cfg(const void* x, const unsigned short* wp, const float* bias, const float* residual, void* y,
+                                               const H9Geom& g, size_t lds, unsigned grid, void* stream) {
+    const auto kern = conv_f9h_kernel<C, false, false, true>;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    DIQT_REQUIRE(e == hipSuccess, DIQT_E_LAUNCH, "conv3d_fwd_split16(v9h): hipFuncSetAttribute: %s", hipGetErrorString(e));
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, (hipStream_t)stream, x, wp, bias, residual, y, g);
+    return check_launch("conv3d_fwd_split16(v9h)");
+}
+
 int launch_b(const void* x, const unsigned short* wp, const float* bias, const float* residual, void* y, const H9Geom& g, size_t lds,
              unsigned grid, int bf16, bool yHalf, void* stream);
 int launch_c(const void* x, const unsigned short* wp, const float* bias, const float* residual, void* y, const H9Geom& g, size_t lds,
              unsigned grid, int bf16, bool yHalf, void* stream);
+// the split build (conv_split16.hip): variant 6 (H9S_333_256)
+int launch_split(const void* x, const unsigned short* wp, const float* bias, const float* residual, void* y, const H9Geom& g, size_t lds,
+                 unsigned grid, void* stream);
 
 }  // namespace h9
 }  // namespace diqt

@@ -343,6 +343,15 @@ class LearnedSinusoidalPosEmb(nn.Module):
         return ops.learned_sinusoidal(x, self.weights)
 
 
+def _split16_pays(x, weight):
+    """Sampling path, fp32: does this Block ask for the three-product split of its 3x3x3 conv (``ops.gn_conv3d(split16=True)``)?  No
+    autograd, no autocast, and a launch the route's planner grants: at least 128 (256-voxel tile, 64-channel block) units, i.e. the
+    32^3 and 16^3 levels of the C2 / C4 U-Nets.  Tiny networks keep the kernels and the bits the parity suite pins."""
+    if torch.is_grad_enabled() or ops.lp_mode() is not None or x.dim() != 5 or tuple(weight.shape[2:]) != (3, 3, 3):
+        return False
+    return bool(ops._lib.query("diqt_conv3d_fwd_split16_supported", *x.shape, weight.shape[0], 3, 3, 3, 1, 1, 1, 0, 0, 0))
+
+
 def boundary_pad(x, batch_sample_factor=3):
     """imagen_pytorch3D.py:37-46 on channels-last sub-volume batches: merge -> zero halo -> overlapping blocks."""
     A = x.shape[1]
@@ -373,7 +382,7 @@ class Block(nn.Module):
             y = None
             if pr.groups == 1 and tuple(pr.stride) == (1, 1, 1):
                 y = ops.gn_conv3d(x, gn.weight, gn.bias, scale_shift, gn.num_groups, ACT_MISH, gn.eps, pr.weight, pr.bias, pr.padding,
-                                  residual, want_stats=emit_stats)
+                                  residual, want_stats=emit_stats, split16=_split16_pays(x, pr.weight))
                 if y is None:       # under autocast: GroupNorm-apply writes the operand type, the conv runs on the LDS-DMA 16-bit kernel
                     y = ops.gn_conv3d_h(x, gn.weight, gn.bias, scale_shift, gn.num_groups, ACT_MISH, gn.eps, pr.weight, pr.bias,
                                         pr.padding, residual, want_stats=emit_stats, out_half=out_half)

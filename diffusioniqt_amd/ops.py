@@ -248,6 +248,73 @@ def _packed_h(weight5, bf16, mode=0):
     return packed
 
 
+SPLIT16 = True        # False: ``split16=True`` requests are ignored (A/B timing and tests; the launches then take the default route)
+
+
+def _packed_split16(weight5):
+    """Head / scaled-tail fp16 pack of an OIDHW weight for the three-product split route (``diqt_conv_pack_weight_split16``), cached
+    like ``_packed``.  None: the layer is refused -- a weight with |w| >= 65504, decided once per weight version at pack time and cached
+    with the pack -- or a pack would have to be made (and its verdict read back) during a graph capture."""
+    owner = weight5._base if weight5._base is not None else weight5
+    cache = getattr(owner, "_diqt_pack", None)
+    if cache is None:
+        cache = {}
+        try:
+            owner._diqt_pack = cache
+        except Exception:
+            pass
+    slot = 's16'
+    key = (slot, weight5.data_ptr(), weight5._version, _WEIGHT_EPOCH)
+    hit = cache.get(slot)
+    if hit is not None and hit[0] == key:
+        return hit[1]
+    if torch.cuda.is_current_stream_capturing():
+        return None
+    Cout, Cin, kd, kh, kw = weight5.shape
+    n = _lib.query("diqt_conv_packed_split16_elems", Cout, Cin, kd, kh, kw)
+    packed = torch.empty(n, dtype=torch.int16, device=weight5.device)
+    refused = torch.empty(1, dtype=torch.int32, device=weight5.device)
+    _lib.call("diqt_conv_pack_weight_split16", weight5.detach(), packed, refused, Cout, Cin, kd, kh, kw, _stream())
+    if hit is not None:
+        retire(hit[1])
+    packed = None if int(refused.item()) else born(packed)
+    cache[slot] = (key, packed)
+    return packed
+
+
+def _conv_fwd_split16(x5, weight, bias, residual, pad, epad, want_stats, coef=None, act=0):
+    """fp32 3x3x3 forward on the fp16 matrix pipe by the three-product split (conv_split16.hip): the pass that splits x (with
+    ``coef``: and applies act(A x + Bc), the GroupNorm-apply of ``gn_conv3d``), then ``conv_f9h_kernel``'s split build.  None when the
+    request is switched off (``SPLIT16``), the shape is not granted or the weight is refused; y carries ``_diqt_stats`` when asked."""
+    B, D, H, W, Cin = x5.shape
+    Cout, _, kd, kh, kw = weight.shape
+    geo = (B, D, H, W, Cin, Cout, kd, kh, kw, *pad, *epad)
+    if not SPLIT16 or not _lib.query("diqt_conv3d_fwd_gn_split16_supported", *geo, act):
+        return None
+    packed = _packed_split16(weight)
+    if packed is None:
+        return None
+    Do, Ho, Wo = D + 2 * pad[0] + epad[0] - kd + 1, H + 2 * pad[1] + epad[1] - kh + 1, W + 2 * pad[2] + epad[2] - kw + 1
+    y = torch.empty((B, Do, Ho, Wo, Cout), dtype=torch.float32, device=x5.device)
+    x16 = torch.empty((B, D, H, W, 2 * Cin), dtype=torch.float16, device=x5.device)
+    if TIMER.enabled:
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+    stats = None
+    if want_stats:
+        nblk = _lib.query("diqt_conv3d_fwd_split16_stats_blocks", *geo)
+        stats = torch.empty((B, nblk, 2, Cout), dtype=torch.float32, device=x5.device)
+        y._diqt_stats = ColStats(stats, nblk, Do * Ho * Wo)
+    if coef is None:
+        _lib.call("diqt_conv3d_fwd_split16", x5, x16, packed, bias, residual, y, stats, *geo, _stream())
+    else:
+        _lib.call("diqt_conv3d_fwd_gn_split16", x5, x16, packed, bias, residual, y, stats, coef, act, *geo, _stream())
+    if TIMER.enabled:
+        e.record()
+        TIMER.records.append((s, e, 2.0 * B * Do * Ho * Wo * Cout * Cin * kd * kh * kw, "conv_f9h_kernel_split16", geo[:9]))
+    return y
+
+
 def repack_cached_h(module, bf16):
     """Re-derives every cached 16-bit packed copy (``_packed_h``) of ``module``'s weights for operand type ``bf16`` in ONE launch per 64
     weights (``diqt_conv_pack_weight_h_multi``) into fresh tensors keyed on the current weight epoch.  graphs.TrainStepGraphs calls it as the
@@ -619,13 +686,20 @@ class _Conv3dFn(Function):
         return dx, dw, db, None, (dy if ctx.has_res else None), None, None, None
 
 
-def conv3d(x, weight, bias=None, padding=(0, 0, 0), residual=None, extra_pad=(0, 0, 0), want_stats=False):
+def conv3d(x, weight, bias=None, padding=(0, 0, 0), residual=None, extra_pad=(0, 0, 0), want_stats=False, split16=False):
     """Stride-1 conv on channels-last x[B,D,H,W,Cin] with an OIDHW weight (MFMA implicit GEMM).
-    Filters whose halo tile cannot fit the 160 KiB LDS (e.g. 15^3 cross-embed taps) take the direct kernel."""
+    Filters whose halo tile cannot fit the 160 KiB LDS (e.g. 15^3 cross-embed taps) take the direct kernel.
+    ``split16`` (no autograd, no autocast): ask for the three-product split on the fp16 matrix pipe (``_conv_fwd_split16``); a launch
+    it does not grant takes the default route."""
     if isinstance(padding, int):
         padding = (padding,) * 3
     padding = tuple(int(p) for p in padding)
     extra_pad = tuple(int(p) for p in extra_pad)
+    if split16 and SPLIT16 and not torch.is_grad_enabled() and lp_mode() is None and x.dim() == 5 and x.shape[-1] == weight.shape[1]:
+        _chk(x, weight, bias, residual)
+        y = _conv_fwd_split16(x, weight, bias, residual, padding, extra_pad, want_stats)
+        if y is not None:
+            return y
     _, D, H, W, _ = x.shape
     kd, kh, kw = weight.shape[2:]
     if _lib.query("diqt_conv3d_lds_bytes", D, H, W, kd, kh, kw, *padding, *extra_pad) > 160 * 1024:
@@ -1257,11 +1331,14 @@ def groupnorm_act(x, gamma, beta, scale_shift=None, groups=8, act=ACT_MISH, eps=
     return (y, alias) if tap else y
 
 
-def gn_conv3d(x, gamma, beta, scale_shift, groups, act, eps, weight, bias, padding, residual=None, extra_pad=(0, 0, 0), want_stats=False):
+def gn_conv3d(x, gamma, beta, scale_shift, groups, act, eps, weight, bias, padding, residual=None, extra_pad=(0, 0, 0), want_stats=False,
+              split16=False):
     """Sampling path (no autograd, fp32): conv3d(act(GN(x) * (scale + 1) + shift)) as ONE conv launch -- the GroupNorm statistics
     (from the producer's column sums when x carries them) are folded into per-(batch, channel) coefficients by one tiny launch and
     ``conv_fwd9_kernel`` applies them to its input tiles while staging them (``diqt_conv3d_fwd_gn``).  Returns None when the shape is
-    not taken (the caller then runs ``groupnorm_act`` + ``conv3d``)."""
+    not taken (the caller then runs ``groupnorm_act`` + ``conv3d``).  ``split16``: ask for the three-product split on the fp16 matrix
+    pipe instead -- the same coefficients, applied by the pass that splits x (``_conv_fwd_split16``); a launch it does not grant takes
+    the route above."""
     if torch.is_grad_enabled() or lp_mode() is not None or x.dim() != 5:
         return None
     B, D, H, W, C = x.shape
@@ -1270,7 +1347,10 @@ def gn_conv3d(x, gamma, beta, scale_shift, groups, act, eps, weight, bias, paddi
     extra_pad = tuple(int(p) for p in extra_pad)
     geo = (B, D, H, W, C, Cout, kd, kh, kw, *padding, *extra_pad)
     npk = sum(_packed_len(weight.shape, 0))
-    if Cin != C or C % groups != 0 or not _lib.query("diqt_conv3d_fwd_gn_supported_pk", *geo, act, npk):
+    # (the split route has its own planner: it also takes activations and shapes the GroupNorm-apply build of conv_fwd9_kernel does not)
+    use_split = bool(split16 and SPLIT16 and _lib.query("diqt_conv3d_fwd_gn_split16_supported", *geo, act))
+    default_ok = bool(_lib.query("diqt_conv3d_fwd_gn_supported_pk", *geo, act, npk))
+    if Cin != C or C % groups != 0 or not (use_split or default_ok):
         return None
     _chk(x, gamma, beta, weight, bias, residual, scale_shift.base if isinstance(scale_shift, SSView) else None)
     rows = D * H * W
@@ -1295,6 +1375,12 @@ def gn_conv3d(x, gamma, beta, scale_shift, groups, act, eps, weight, bias, paddi
     else:
         ws, n = _reduce_ws(B, C, dev)
         _lib.call("diqt_groupnorm_stats_coef", x, gamma, beta, scale, shift, cs, mean, rstd, coef, ws, n, B, rows, C, groups, float(eps), s)
+    if use_split:
+        y = _conv_fwd_split16(x, weight, bias, residual, padding, extra_pad, want_stats, coef, act)
+        if y is not None:
+            return y
+    if not default_ok:
+        return None
     Do, Ho, Wo = D + 2 * padding[0] + extra_pad[0] - kd + 1, H + 2 * padding[1] + extra_pad[1] - kh + 1, W + 2 * padding[2] + extra_pad[2] - kw + 1
     y = torch.empty((B, Do, Ho, Wo, Cout), dtype=torch.float32, device=dev)
     if TIMER.enabled:

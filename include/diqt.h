@@ -136,11 +136,37 @@ int diqt_set_conv_f9h_mode(int mode);
  * 6 conv_pw_h_kernel on a pointwise conv, 7 conv_pw_h_kernel on a temporal conv, 8 conv_f9h_kernel.                                      */
 int diqt_conv3d_fwd_h_kernel_id(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw,
                                 int epd, int eph, int epw, int x_half, int y_half, int has_residual, int has_stats);
-/* the conv_f9h_kernel variant (0..5) the process's last launch of it ran, -1 if none since the previous call (read and clear) */
+/* the conv_f9h_kernel variant (0..5; 6: the split build of diqt_conv3d_fwd_split16) the process's last launch of it ran, -1 if none since the previous call (read and clear) */
 int diqt_get_last_conv_f9h_variant(void);
 int diqt_conv3d_fwd_h(const float* x, const void* packed_h, const float* bias, const float* residual, float* y, int B, int D, int H,
                       int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw, int epd, int eph, int epw, int bf16,
                       int round_out, void* stream);
+
+/* fp32 3x3x3 forward conv on the fp16 matrix pipe by the three-product split (conv_split16.hip): each operand is an fp16 head plus an fp16
+ * tail scaled by 2^11, x w ~= xh wh + 2^-11 (xh wl + xl wh), summed in fp32 -- fp32-sized error (below the Winograd tile's), three
+ * 16-bit MFMAs for sixteen f32 ones.  Domain: |w| < 65504 (the pack sets *refused = 1 otherwise: keep the layer on diqt_conv3d_fwd*);
+ * an activation beyond +-65504 is clamped (finite output, accuracy lost).  x, y, bias, residual, stats: fp32 as for diqt_conv3d_fwd_pk.
+ * x16: scratch of B D H W Cin * 4 bytes for the split activations (NDHWC, per 16 channels [16 heads | 16 tails]).  packed: 16-bit
+ * [ci/16][tap][co padded to 64][16 heads | 16 tails], diqt_conv_packed_split16_elems elements.  ..._supported: Cin % 16 == 0,
+ * Cout % 8 == 0, what conv_f9h_kernel's planner takes at 2 Cin channels, and at least 128 (tile, 64-channel block) units unless
+ * diqt_set_conv_f9h_mode(2).  stats (may be NULL): [B][diqt_conv3d_fwd_split16_stats_blocks][2][Cout] column sums of y.
+ * The _gn form applies act(A x + Bc), coef = [2][B][Cin] as for diqt_conv3d_fwd_gn, in the pass that splits x.                  */
+size_t diqt_conv_packed_split16_elems(int Cout, int Cin, int kd, int kh, int kw);
+int diqt_conv_pack_weight_split16(const float* w_oidhw, void* packed, int* refused, int Cout, int Cin, int kd, int kh, int kw, void* stream);
+int diqt_conv3d_fwd_split16_supported(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw,
+                                      int epd, int eph, int epw);
+int diqt_conv3d_fwd_gn_split16_supported(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw,
+                                         int epd, int eph, int epw, int act);
+int diqt_conv3d_fwd_split16_stats_blocks(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw,
+                                         int epd, int eph, int epw);
+int diqt_conv3d_fwd_split16_variant(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw,
+                                    int epd, int eph, int epw);
+int diqt_conv3d_fwd_split16(const float* x, void* x16, const void* packed, const float* bias, const float* residual, float* y, float* stats,
+                            int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw, int epd, int eph,
+                            int epw, void* stream);
+int diqt_conv3d_fwd_gn_split16(const float* x, void* x16, const void* packed, const float* bias, const float* residual, float* y,
+                               float* stats, const float* coef, int act, int B, int D, int H, int W, int Cin, int Cout, int kd, int kh,
+                               int kw, int pd, int ph, int pw, int epd, int eph, int epw, void* stream);
 
 /* Forward conv that also emits per-tile column sums of its OUTPUT for the consumer's GroupNorm statistics / SE pooling
  * (Block -> Block and Block -> SE3D inside ResnetBlock, imagen_pytorch3D.py:568-632): stats[B][nblk][2][Cout] =

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Micro-benchmark of the MFMA conv kernels on the dominant C2 shape (B=8, 32^3, 64->64, 3x3x3) — for
-rocprofv3 --pmc passes and A/B timing.  Usage: python tools/conv_bench.py [fwd|bwdw|both] [iters] [B S Cin Cout]"""
+rocprofv3 --pmc passes and A/B timing.  Usage: python tools/conv_bench.py [fwd|bwdw|both|gn|s16|fwdh] [iters] [B S Cin Cout]"""
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -50,6 +50,17 @@ if mode == "gn":                # Block on the sampling path: GroupNorm-apply in
         ms_u = timeit(lambda: ops.conv3d(ops.groupnorm_act(x, gamma, beta, ss, 8, act), w, bias, PADS), iters)
     print(f"GN+act+conv B={B} {SP} k={KS} {Cin}->{Cout}: fused {ms_f*1e3:.1f} us (incl. statistics pass + coefficient launch), "
           f"two-kernel path {ms_u*1e3:.1f} us, conv alone {ms_c*1e3:.1f} us = {flops/ms_c/1e9:.1f} TFLOP/s")
+if mode == "s16":               # Block on the sampling path: the three-product split (pre-pass + conv_f9h_kernel) vs the Winograd GroupNorm-apply launch
+    gamma, beta = torch.randn(Cin, device=dev), torch.randn(Cin, device=dev)
+    ss = torch.randn(B, 2 * Cin, device=dev) * 0.3
+    gn = lambda s16: ops.gn_conv3d(x, gamma, beta, ss, 8, ops.ACT_MISH, 1e-5, w, bias, PADS, want_stats=True, split16=s16)
+    with torch.no_grad():
+        assert gn(True) is not None and "split16" in _lib.last_launch(), "shape not granted to the split route"
+        assert gn(False) is not None and "split16" not in _lib.last_launch(), "no default GroupNorm-apply route for this shape"
+        ms_s, ms_w = timeit(lambda: gn(True), iters), timeit(lambda: gn(False), iters)
+        ms_s2, ms_w2 = timeit(lambda: gn(True), iters), timeit(lambda: gn(False), iters)
+    print(f"GN+act+conv B={B} {SP} {Cin}->{Cout}: split16 {ms_s*1e3:.1f} / {ms_s2*1e3:.1f} us, Winograd {ms_w*1e3:.1f} / {ms_w2*1e3:.1f} us "
+          f"(both incl. statistics / coefficient launch; two alternating rounds)")
 if mode in ("fwdh",):           # fp16 / bf16 operand kernel (LP=fp16|bf16)
     with torch.no_grad(), ops.low_precision(os.environ.get("LP", "fp16")):
         ms = timeit(lambda: ops.conv3d(x, w, bias, PADS), iters)
