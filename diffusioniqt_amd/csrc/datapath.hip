@@ -617,6 +617,139 @@ __global__ __launch_bounds__(256) void volume_joint_linear_kernel(const float* _
     x_next[v] = r;
 }
 
+// ---- data consistency (DDNM, Wang et al. 2023) for a block-average measurement -----------------------------------------------------------
+// A cell is (fz, fy, fx) voxels, n = fz fy fx in 2 .. 64; the measurement is the cell mean A x, and it arrives replicated on the
+// high-res grid (meas_up[v] = the measurement of v's cell).  The projection x0' = x0 + w A+(y - A x0) of the values a over one cell,
+// ONE definition for the per-window kernel and the joint kernel (so at stride = patch the joint chain is the per-window loop bit for
+// bit), fp32 and kept from contraction:
+//   cell_mean    s = 0; s = s + a[v] over the cell's voxels in lexicographic (z, y, x) order; m = s / (float)n.  `a(i, j, k)` is the
+//                value at offset (i, j, k) inside the cell;
+//   cell_shift   a'[v] = fmaf(w, meas_up[v] - m, a[v]), w the consistency weight in (0, 1].
+struct Cell { int fz, fy, fx; };
+template <class Value>
+__device__ __forceinline__ float cell_mean(Cell c, Value a) {
+#pragma clang fp contract(off)
+    float s = 0.f;
+    for (int i = 0; i < c.fz; ++i)
+        for (int j = 0; j < c.fy; ++j)
+            for (int k = 0; k < c.fx; ++k) s = s + a(i, j, k);
+    return s / (float)(c.fz * c.fy * c.fx);
+}
+__device__ __forceinline__ float cell_shift(float w, float meas, float m, float a) {
+#pragma clang fp contract(off)
+    const float r = meas - m;
+    return fmaf(w, r, a);
+}
+// diqt_ddpm_step's clamp with a third mode: 2 = none (the value's own bits).
+struct ProjectClamp {
+    float lo, hi;
+    int mode;
+    __device__ __forceinline__ float operator()(float y) const { return mode == 2 ? y : StepClamp{lo, hi, mode}(y); }
+};
+// The operator A alone: out [D / fz][H / fy][W / fx] = cell_mean of x [D][H][W].  One thread per cell, consecutive lanes = consecutive
+// cells along x.
+__global__ __launch_bounds__(256) void cell_mean_kernel(const float* __restrict__ x, float* __restrict__ out, size_t cells, int H, int W,
+                                                        Cell c) {
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= cells) return;
+    const int cw = W / c.fx, ch = H / c.fy;
+    const int cx = (int)(e % cw), cy = (int)((e / cw) % ch);
+    const size_t cz = e / ((size_t)cw * ch);
+    const float* base = x + ((cz * c.fz) * H + (size_t)cy * c.fy) * W + (size_t)cx * c.fx;
+    out[e] = cell_mean(c, [&](int i, int j, int k) { return base[((size_t)i * H + j) * W + k]; });
+}
+// The per-window step: x0 / meas_up / out are `cubes` cubes of edge P; a = c(x0), then the projection.  One thread per cell: it reads
+// its cell's n values twice (the sum, then the shift) and writes only them, so out may alias x0 (no __restrict__ on the two).
+__global__ __launch_bounds__(256) void cell_project_kernel(const float* x0, const float* __restrict__ meas_up, float* out, size_t cells,
+                                                           int P, Cell c, float w, ProjectClamp clamp) {
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= cells) return;
+    const int cw = P / c.fx, ch = P / c.fy, cd = P / c.fz;
+    const int cx = (int)(e % cw), cy = (int)((e / cw) % ch), cz = (int)((e / ((size_t)cw * ch)) % cd);
+    const size_t cube = e / ((size_t)cw * ch * cd);
+    const size_t base = ((cube * P + (size_t)cz * c.fz) * P + (size_t)cy * c.fy) * P + (size_t)cx * c.fx;
+    auto at = [&](int i, int j, int k) { return base + ((size_t)i * P + j) * P + k; };
+    const float m = cell_mean(c, [&](int i, int j, int k) { return clamp(x0[at(i, j, k)]); });
+    for (int i = 0; i < c.fz; ++i)
+        for (int j = 0; j < c.fy; ++j)
+            for (int k = 0; k < c.fx; ++k) {
+                const size_t v = at(i, j, k);
+                out[v] = cell_shift(w, meas_up[v], m, clamp(x0[v]));
+            }
+}
+// volume_joint_linear_kernel with the projection between the fuse and the update (diqt_volume_joint_consistent_step): per voxel the
+// fuse x0 = num / den exactly as there; a cell whose voxels are ALL covered takes x0' = cell_shift(w, meas_up, cell_mean(x0), x0) and
+// each of its voxels the update with x0' in the place of x0; a cell with an uncovered voxel is left alone -- its covered voxels take
+// the update with their plain x0, its uncovered ones keep x_t and get x0_out = 0.  The two update forms, the normals, the draw
+// numbering and "no Philox call when kn == 0" are the linear kernel's; there is no initial state here and x0_out is required.
+// Geometry: a block of (64, 4) threads owns a BOX of whole cells, (fz, cy fy, cx fx) voxels with cx = ceil(64 / fx) and
+// cy = ceil(4 / (fz fy)) -- at least 256 voxels where the volume has them, at most 4096 -- on the grid (ceil(W / bx), ceil(H / by),
+// D / fz); a thread takes the box's voxels e = t, t + 256, ... (x fastest: lanes read consecutive floats).  Pass 1 fuses every voxel of
+// the box into LDS (x0s[e], and den[e] = 0 for an uncovered voxel or one past the volume); after a barrier pass 2 revisits the SAME
+// voxels: the thread sums its voxel's cell out of LDS -- every voxel of a cell forms the same sum in the same order -- and updates it.
+// A thread reads and writes only its own voxels of x_t / x0_prev / x_next / x0_out, each read before it is written, so x_next may alias
+// x_t and x0_out may alias x0_prev; whole cells lie in one block, so there is no atomic and no waiting across blocks.  D, H and W are
+// multiples of the cell, so a cell is inside the volume or outside it as a whole.
+struct CellBox { int by, bx; };                        // the box is (fz, by, bx) voxels
+__host__ __device__ __forceinline__ CellBox cell_box(Cell c) {
+    const int zy = c.fz * c.fy;
+    return CellBox{c.fy * ((4 + zy - 1) / zy), c.fx * ((64 + c.fx - 1) / c.fx)};
+}
+__global__ __launch_bounds__(256) void volume_joint_consistent_kernel(const float* __restrict__ y, const int* __restrict__ slot,
+                                                                      const float* __restrict__ taps, const float* x_t,
+                                                                      const float* x0_prev, const float* __restrict__ meas_up,
+                                                                      float* x_next, float* x0_out, int N, int D, int H, int W, int P,
+                                                                      int stride, int G0, int G1, int G2, Cell c, float w, float kx,
+                                                                      float k0, float kp, float kn, float lo, float hi, int clamp_mode,
+                                                                      int third_is_normal, unsigned key0, unsigned key1, unsigned draw,
+                                                                      unsigned sample) {
+    extern __shared__ float tp[];                      // [P], then x0s [nb] and den [nb]
+    const CellBox b = cell_box(c);
+    const int nb = c.fz * b.by * b.bx, t = threadIdx.y * 64 + threadIdx.x;
+    float* x0s = tp + P;
+    float* dens = x0s + nb;
+    for (int e = t; e < P; e += 256) tp[e] = taps[e];
+    __syncthreads();
+    const int z0 = blockIdx.z * c.fz, y0 = blockIdx.y * b.by, xb = blockIdx.x * b.bx;
+    for (int e = t; e < nb; e += 256) {
+        const int lx = e % b.bx, ly = (e / b.bx) % b.by, lz = e / (b.bx * b.by);
+        const Voxel p{xb + lx, y0 + ly, z0 + lz, 0, y0 + ly < H && xb + lx < W};
+        Fused f{0.f, 0.f};
+        if (p.inside) f = joint_fuse(y, slot, taps, tp, N, P, stride, G0, G1, G2, p, StepClamp{lo, hi, clamp_mode});
+        x0s[e] = f.covered() ? f.x0() : 0.f;
+        dens[e] = f.den;
+    }
+    __syncthreads();
+    for (int e = t; e < nb; e += 256) {
+        const int lx = e % b.bx, ly = (e / b.bx) % b.by, lz = e / (b.bx * b.by);
+        const int x = xb + lx, h = y0 + ly, d = z0 + lz;
+        if (h >= H || x >= W) continue;
+        const size_t v = ((size_t)d * H + h) * W + x;
+        const float xt = x_t[v];
+        if (dens[e] == 0.f) {
+            x_next[v] = xt;
+            x0_out[v] = 0.f;
+            continue;
+        }
+        // the cell of this voxel inside the box: lz is its z offset (the box is one cell deep)
+        const int cb = ((ly / c.fy) * c.fy) * b.bx + (lx / c.fx) * c.fx;
+        bool all = true;
+        const float m = cell_mean(c, [&](int i, int j, int k) {
+            const int q = cb + (i * b.by + j) * b.bx + k;
+            all = all && dens[q] != 0.f;
+            return x0s[q];
+        });
+        float x0 = x0s[e];
+        if (all) x0 = cell_shift(w, meas_up[v], m, x0);
+        const float prev = x0_prev ? x0_prev[v] : 0.f;
+        float n = 0.f;
+        if (kn != 0.f) n = philox_normal(philox4x32_10((unsigned)v, (unsigned)((unsigned long long)v >> 32), draw, sample, key0, key1));
+        const float r = third_is_normal ? sampler_update(kx, xt, k0, x0, kn, n) : sampler_update_sde(kx, xt, k0, x0, kp, prev, kn, n);
+        x0_out[v] = x0;
+        x_next[v] = r;
+    }
+}
+
 // The stochastic Heun sampler of the EDM family (elucidated_imagen.py:382-532) on the same state: a churn, a predictor and a corrector
 // per step, two U-Net evaluations, so the state is three volumes -- xh = images_hat, xn = images_next, x0 = the fused prediction (the
 // one self-conditioning reads) -- and the launch takes a `phase`, uniform over the grid:
@@ -1176,6 +1309,72 @@ extern "C" int diqt_volume_joint_multistep_sde(const float* y, const int* slot, 
                                                int clamp_mode, unsigned long long seed, unsigned draw, unsigned sample, void* stream) {
     return joint_linear_launch("volume_joint_multistep_sde", x0_out && slot && taps && (y || N == 0), y, slot, taps, x_t, x0_prev, x_next,
                                x0_out, N, D, H, W, P, stride, G0, G1, G2, kx, k0, kp, kn, lo, hi, clamp_mode, 0, seed, draw, sample, stream);
+}
+
+// The cell and the weight of the data-consistency entries: n = fz fy fx in 2 .. 64 and 0 < w <= 1, else DIQT_E_UNSUPPORTED.
+static int cell_ok(const char* who, int fz, int fy, int fx, float w) {
+    DIQT_REQUIRE(fz >= 1 && fy >= 1 && fx >= 1 && fz <= 64 && fy <= 64 && fx <= 64 && fz * fy * fx >= 2 && fz * fy * fx <= 64,
+                 DIQT_E_UNSUPPORTED, "%s: cell %dx%dx%d (every factor >= 1, 2 <= fz fy fx <= 64)", who, fz, fy, fx);
+    DIQT_REQUIRE(w > 0.f && w <= 1.f, DIQT_E_UNSUPPORTED, "%s: weight %g outside (0, 1]", who, (double)w);
+    return DIQT_OK;
+}
+
+extern "C" int diqt_cell_mean(const float* x, float* out, int D, int H, int W, int fz, int fy, int fx, void* stream) {
+    DIQT_REQUIRE(x && out, DIQT_E_ALIGN, "cell_mean: null pointer");
+    int rc = cell_ok("cell_mean", fz, fy, fx, 1.f);
+    if (rc) return rc;
+    DIQT_REQUIRE(D > 0 && H > 0 && W > 0 && D % fz == 0 && H % fy == 0 && W % fx == 0, DIQT_E_SHAPE,
+                 "cell_mean: the cell %dx%dx%d does not divide the volume %dx%dx%d", fz, fy, fx, D, H, W);
+    const size_t cells = (size_t)(D / fz) * (H / fy) * (W / fx);
+    DIQT_REQUIRE((cells + 255) / 256 <= 0x7fffffffu, DIQT_E_SHAPE, "cell_mean: more than 2^31 - 1 blocks");
+    hipLaunchKernelGGL(cell_mean_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, STREAM, x, out, cells, H, W, Cell{fz, fy, fx});
+    return check_launch("cell_mean");
+}
+
+extern "C" int diqt_cell_project(const float* x0, const float* meas_up, float* out, size_t cubes, int P, int fz, int fy, int fx,
+                                 float weight, float lo, float hi, int clamp_mode, void* stream) {
+    DIQT_REQUIRE(x0 && meas_up && out, DIQT_E_ALIGN, "cell_project: null pointer");
+    int rc = cell_ok("cell_project", fz, fy, fx, weight);
+    if (rc) return rc;
+    DIQT_REQUIRE(clamp_mode >= 0 && clamp_mode <= 2, DIQT_E_UNSUPPORTED, "cell_project: clamp_mode %d (0 = min, 1 = box, 2 = none)",
+                 clamp_mode);
+    DIQT_REQUIRE(cubes > 0 && P > 0 && P % fz == 0 && P % fy == 0 && P % fx == 0, DIQT_E_SHAPE,
+                 "cell_project: the cell %dx%dx%d does not divide the %zu cubes of edge %d", fz, fy, fx, cubes, P);
+    const size_t cells = cubes * (size_t)(P / fz) * (P / fy) * (P / fx);
+    DIQT_REQUIRE((cells + 255) / 256 <= 0x7fffffffu, DIQT_E_SHAPE, "cell_project: more than 2^31 - 1 blocks");
+    hipLaunchKernelGGL(cell_project_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, STREAM, x0, meas_up, out, cells, P,
+                       Cell{fz, fy, fx}, weight, ProjectClamp{lo, hi, clamp_mode});
+    return check_launch("cell_project");
+}
+
+extern "C" int diqt_volume_joint_consistent_step(const float* y, const int* slot, const float* taps, const float* x_t,
+                                                 const float* x0_prev, const float* meas_up, float* x_next, float* x0_out, int form,
+                                                 int N, int D, int H, int W, int P, int stride, int G0, int G1, int G2, int fz, int fy,
+                                                 int fx, float weight, float kx, float k0, float kp, float kn, float lo, float hi,
+                                                 int clamp_mode, unsigned long long seed, unsigned draw, unsigned sample, void* stream) {
+    const char* who = "volume_joint_consistent_step";
+    DIQT_REQUIRE(x_t && meas_up && x_next && x0_out && slot && taps && (y || N == 0), DIQT_E_ALIGN, "%s: null pointer", who);
+    DIQT_REQUIRE(form >= 0 && form <= 2, DIQT_E_UNSUPPORTED, "%s: form %d (0 = first order, 1 = multistep, 2 = multistep with noise)", who,
+                 form);
+    int rc = cell_ok(who, fz, fy, fx, weight);
+    if (rc) return rc;
+    DIQT_REQUIRE(D > 0 && H > 0 && W > 0 && D % fz == 0 && H % fy == 0 && W % fx == 0, DIQT_E_SHAPE,
+                 "%s: the cell %dx%dx%d does not divide the volume %dx%dx%d", who, fz, fy, fx, D, H, W);
+    JointGrid g;                                       // the shape, lattice and clamp checks of the plain step; the grid is the boxes'
+    rc = joint_launch_plan(who, x_next, true, true, N, D, H, W, P, stride, G0, G1, G2, clamp_mode, g);
+    if (rc) return rc;
+    const Cell c{fz, fy, fx};
+    const CellBox b = cell_box(c);
+    const size_t lds = ((size_t)P + 2 * (size_t)fz * b.by * b.bx) * sizeof(float);
+    DIQT_REQUIRE(lds <= 65536, DIQT_E_SHAPE, "%s: P %d needs %zu bytes of LDS", who, P, lds);
+    DIQT_REQUIRE((H + b.by - 1) / b.by <= 65535, DIQT_E_SHAPE, "%s: more than 65535 rows of boxes", who);
+    // first order: no history; multistep: no normal (and with it no key)
+    const bool first = form == 0, noisy = form != 1;
+    hipLaunchKernelGGL(volume_joint_consistent_kernel, dim3((W + b.bx - 1) / b.bx, (H + b.by - 1) / b.by, D / fz), dim3(64, 4), lds, STREAM,
+                       y, slot, taps, x_t, first ? nullptr : x0_prev, meas_up, x_next, x0_out, N, D, H, W, P, stride, G0, G1, G2, c, weight,
+                       kx, k0, first ? 0.f : kp, noisy ? kn : 0.f, lo, hi, clamp_mode, first ? 1 : 0, (unsigned)seed,
+                       (unsigned)(seed >> 32), draw, sample);
+    return check_launch(who);
 }
 
 extern "C" int diqt_volume_joint_heun(const float* y, const int* slot, const float* taps, float* xh, float* xn, float* x0, int phase, int N,

@@ -22,7 +22,7 @@ from . import ops
 from .graphs import GraphCache
 from .imagen_pytorch3D import (GaussianDiffusionContinuousTimes, Unet, NullUnet, exists, default, cast_tuple, identity, maybe,
                                normalize_neg_one_to_one, unnormalize_zero_to_one, eval_decorator, to_channels_last,
-                               to_channels_first, log_snr_to_alpha_sigma)
+                               to_channels_first, log_snr_to_alpha_sigma, check_consistency)
 from .imagen_video import Unet3D
 
 Hparams_fields = ['num_sample_steps', 'sigma_min', 'sigma_max', 'sigma_data', 'rho', 'P_mean', 'P_std', 'S_churn', 'S_tmin',
@@ -139,6 +139,8 @@ class EDMWindowDenoiser:
         """A known volume (in the units ``finish`` returns) in state space: ``imagen.normalize_img``, what ``one_unet_sample`` does to
         ``inpaint_images`` (:447)."""
         return self.imagen.normalize_img(x)
+
+    state_space = normalize                                # the name every window denoiser has it under (``consistency=`` reads it)
 
     @torch.no_grad()
     def finish(self, x, known=None, mask=None):
@@ -417,7 +419,7 @@ class ElucidatedImagen(nn.Module):
     def one_unet_sample(self, unet, shape, *, unet_number, clamp=True, dynamic_threshold=True, cond_scale=1., use_tqdm=True,
                         inpaint_images=None, inpaint_masks=None, inpaint_resample_times=5, init_images=None,
                         skip_steps=None, sigma_min=None, sigma_max=None, noise=None, sampler='heun', sample_steps=None, eta=0.,
-                        **kwargs):
+                        consistency=None, consistency_weight=1., **kwargs):
         """Stochastic Heun sampler (:382-532).  ``noise``: optional injected list [init, step_0, ...], or a callable
         ``noise(shape) -> fp32 device tensor`` whose successive calls are those draws (one ``eps`` per step, also when gamma is 0).
 
@@ -431,9 +433,18 @@ class ElucidatedImagen(nn.Module):
         of ``_heun_inpaint_sample``, ``inpaint_resample_times`` passes per step.  The draws are then the initial image and, per
         (step, r), the ``eps`` and -- unless r == 0 or it is the last step -- the re-noise normal (``inpaint_draws``).  Only with
         ``sampler='heun'``; one of the two without the other, another sampler or a count that is not a positive integer: ``ValueError``
-        before anything touches the device."""
+        before anything touches the device.
+
+        ``consistency=(meas_up, cell)`` with ``consistency_weight`` (``sampler='dpmpp2m'`` only; ``check_consistency``): data-consistent
+        sampling for a block-average measurement (DDNM).  ``meas_up`` [B,C,P,P,P], the measurement replicated onto the high-res grid
+        (``ops.cell_replicate``), arrives in state space here (``sample`` takes it in the units it returns, like ``inpaint_images``).
+        Every step's clamped or thresholded prediction goes through ``ops.cell_project`` before ``ops.multistep_sde_step``; the
+        history operand and self-conditioning read the projected tensor.  The Heun sampler has two predictions per step and is
+        refused."""
         self._check_sampler_args(sampler, sample_steps, skip_steps, eta)
         has_inpainting = self._check_inpaint_args(sampler, inpaint_images, inpaint_masks, inpaint_resample_times)
+        consistency = check_consistency('one_unet_sample', consistency, consistency_weight, shape, has_inpainting, init_images,
+                                        skip_steps, sampler)
         if has_inpainting:
             return self._heun_inpaint_sample(unet, shape, unet_number=unet_number, clamp=clamp, dynamic_threshold=dynamic_threshold,
                                              cond_scale=cond_scale, inpaint_images=inpaint_images, inpaint_masks=inpaint_masks,
@@ -442,7 +453,7 @@ class ElucidatedImagen(nn.Module):
         if sampler == 'dpmpp2m':
             return self._dpmpp2m_sample(unet, shape, unet_number=unet_number, clamp=clamp, dynamic_threshold=dynamic_threshold,
                                         cond_scale=cond_scale, init_images=init_images, sigma_min=sigma_min, sigma_max=sigma_max,
-                                        noise=noise, sample_steps=sample_steps, eta=eta, **kwargs)
+                                        noise=noise, sample_steps=sample_steps, eta=eta, consistency=consistency, **kwargs)
         hp = self.hparams[unet_number - 1]
         sigma_min, sigma_max = default(sigma_min, hp.sigma_min), default(sigma_max, hp.sigma_max)
         sigmas = self.sample_schedule(hp.num_sample_steps, hp.rho, sigma_min, sigma_max)
@@ -484,8 +495,9 @@ class ElucidatedImagen(nn.Module):
         return self.unnormalize_img(images)
 
     def _dpmpp2m_sample(self, unet, shape, *, unet_number, clamp, dynamic_threshold, cond_scale, init_images, sigma_min, sigma_max, noise,
-                        sample_steps, eta, **kwargs):
-        """``one_unet_sample(sampler='dpmpp2m')``; the arguments are checked there."""
+                        sample_steps, eta, consistency=None, **kwargs):
+        """``one_unet_sample(sampler='dpmpp2m')``; the arguments are checked there (``consistency``: None or the checked
+        ``(meas_up, cell, weight)``, ``meas_up`` in state space)."""
         hp = self.hparams[unet_number - 1]
         sigmas, coefs = self._dpmpp2m_tables(unet_number - 1, sample_steps, eta, sigma_min, sigma_max)
         sigmas = sigmas.tolist()
@@ -503,9 +515,14 @@ class ElucidatedImagen(nn.Module):
         self_cond_on = bool(getattr(unet, 'self_cond', False))
         stochastic = (coefs[:, 3] != 0).tolist()
         k = coefs[:, :, None].expand(-1, -1, B).contiguous().to(dev)              # [T,4,B]: one coefficient row per sample
+        if exists(consistency):
+            meas_up, cell, weight = consistency
+            meas_up = meas_up.to(dev).float().contiguous()
         x_start = None
         for i in range(coefs.shape[0]):
             out = fwd(images, float(sigmas[i]), **(dict(self_cond=x_start) if self_cond_on else {}))
+            if exists(consistency):                                             # ``out`` arrives clamped or thresholded
+                out = ops.cell_project(out, meas_up, cell, weight)
             images = ops.multistep_sde_step(images, out, x_start, draw() if stochastic[i] else None, k[i, 0], k[i, 1], k[i, 2], k[i, 3])
             x_start = out
         images = ops.axpby3(images, None, None, torch.ones(B, device=dev), None, None, -1., 1., 2)    # clamp(-1, 1)
@@ -622,7 +639,7 @@ class ElucidatedImagen(nn.Module):
                inpaint_resample_times=5, init_images=None, skip_steps=None, sigma_min=None, sigma_max=None, video_frames=None,
                batch_size=1, cond_scale=1., lowres_sample_noise_level=None, start_at_unet_number=1, start_image_or_video=None,
                stop_at_unet_number=None, return_all_unet_outputs=False, return_pil_images=False, use_tqdm=True, device=None,
-               noise=None, sampler='heun', sample_steps=None, eta=0.):
+               noise=None, sampler='heun', sample_steps=None, eta=0., consistency=None, consistency_weight=1.):
         """:536-702.  ``noise``: optional injected list [lowres_noise, init, step_0, ...] per sampled unet (tests), or -- when exactly
         one U-Net is sampled -- a callable ``noise(shape) -> fp32 device tensor`` whose successive calls are those draws in that order
         (``inference.AnchoredNoise.source``: call k is draw k of the volume-anchored field).
@@ -637,7 +654,13 @@ class ElucidatedImagen(nn.Module):
         the RePaint loop of ``one_unet_sample``; ``batch_size`` 1 broadcasts to the number of images.  A U-Net's draws are then the
         low-res noise (if any), the initial image and ``inpaint_draws(steps, R)`` loop normals, in the reference's call order.  One of
         images / masks alone, inpainting with 'dpmpp2m', or a count that is not a positive integer: ``ValueError`` naming "inpaint",
-        before anything touches the device."""
+        before anything touches the device.
+
+        ``consistency=(meas_up, cell)`` / ``consistency_weight``: ``one_unet_sample``'s, for every sampled U-Net (so they must generate
+        one size); ``meas_up`` [B,C,P,P,P] in the units this returns (``normalize_img`` takes it to state space, as it does
+        ``inpaint_images``).  ``ValueError`` naming "consistency" before anything touches the device: with the Heun sampler, together
+        with inpainting, ``init_images`` or ``skip_steps``, a weight outside (0, 1], a cell that does not divide the image size or with
+        n outside 2 .. 64, a ``meas_up`` of another shape."""
         assert texts is None and text_embeds is None and not return_pil_images
         samplers, steps_per_unet, etas = (cast_tuple(v, len(self.unets)) for v in (sampler, sample_steps, eta))
         for args in zip(samplers, steps_per_unet, cast_tuple(skip_steps, len(self.unets)), etas):
@@ -645,6 +668,15 @@ class ElucidatedImagen(nn.Module):
         sampled_samplers = samplers[start_at_unet_number - 1:default(stop_at_unet_number, len(self.unets))]
         has_inpainting = any([self._check_inpaint_args(s, inpaint_images, inpaint_masks, inpaint_resample_times)
                               for s in sampled_samplers or samplers[-1:]])
+        if exists(consistency):
+            span = range(start_at_unet_number, default(stop_at_unet_number, len(self.unets)) + 1)
+            frames = calc_all_frame_dims(self.temporal_downsample_factor, video_frames)
+            for n in span:
+                check_consistency('sample', consistency, consistency_weight,
+                                  (batch_size, self.channels, *frames[n - 1], self.image_sizes[n - 1], self.image_sizes[n - 1]),
+                                  exists(inpaint_images), cast_tuple(init_images, len(self.unets))[n - 1],
+                                  cast_tuple(skip_steps, len(self.unets))[n - 1], samplers[n - 1])
+            consistency = (self.normalize_img(consistency[0]), consistency[1])
         if has_inpainting:
             if batch_size == 1:                                                    # broadcast along the inpainted images (:580-583)
                 batch_size = inpaint_images.shape[0]
@@ -697,6 +729,8 @@ class ElucidatedImagen(nn.Module):
             if unet_sampler == 'dpmpp2m':                                          # the initial image, then one draw per row with kn != 0
                 multistep = dict(sampler=unet_sampler, sample_steps=unet_steps, eta=unet_eta)
                 n_draws = 1 + int((self._dpmpp2m_tables(unet_number - 1, unet_steps, unet_eta, smin, smax)[1][:, 3] != 0).sum())
+            if exists(consistency):
+                multistep.update(consistency=consistency, consistency_weight=consistency_weight)
             inpaint = {}
             if has_inpainting:                                                     # the initial image, then the draws of the loop
                 inpaint = dict(inpaint_images=inpaint_images, inpaint_masks=inpaint_masks, inpaint_resample_times=inpaint_resample_times)

@@ -1151,6 +1151,32 @@ class SRUnet256(Unet):
         super().__init__(*args, **{**default_kwargs, **kwargs})
 
 
+def check_consistency(who, consistency, weight, shape, has_inpainting=False, init_images=None, skip_steps=None, sampler=None):
+    """The argument rules of ``consistency=(meas_up, cell)`` / ``consistency_weight`` of the one-call samplers of both families
+    (``ValueError`` naming "consistency"; nothing touches the device).  ``shape`` = the [B,C,P,P,P] the sampler generates: ``meas_up``
+    must be a float tensor of exactly that shape, the cell must divide P.  Data consistency (DDNM) replaces the cell means of every x0
+    prediction by the measurement's; inpainting pastes known values into the state, ``init_images`` / ``skip_steps`` start or thin the
+    chain elsewhere and the EDM Heun sampler has two predictions per step: none of them is offered with it.  Returns None (off) or
+    ``(meas_up, cell, weight)``."""
+    if consistency is None:
+        return None
+    if not isinstance(consistency, (tuple, list)) or len(consistency) != 2:
+        raise ValueError(f"{who}: consistency must be (meas_up, cell), got {type(consistency).__name__}")
+    if sampler == 'heun':
+        raise ValueError(f"{who}: consistency is not offered with the Heun sampler (two predictions per step): use sampler='dpmpp2m'")
+    if has_inpainting:
+        raise ValueError(f"{who}: consistency and inpainting are not offered together")
+    if exists(init_images) or exists(skip_steps):
+        raise ValueError(f"{who}: consistency takes neither init_images nor skip_steps")
+    meas_up, cell = consistency
+    cell, weight = ops.consistency_cell(who, cell, weight, [(shape[2 + a], a) for a in range(3)])
+    if not torch.is_tensor(meas_up) or not meas_up.is_floating_point() or tuple(meas_up.shape) != tuple(shape):
+        got = f"{meas_up.dtype} {tuple(meas_up.shape)}" if torch.is_tensor(meas_up) else type(meas_up).__name__
+        raise ValueError(f"{who}: the consistency measurement must be a float tensor of the sampled shape {tuple(shape)} (replicated "
+                         f"onto the high-res grid, ops.cell_replicate), got {got}")
+    return meas_up, cell, weight
+
+
 # ----------------------------------------------------------------------------------------------
 # Imagen: continuous-time DDPM wrapper (imagen_pytorch3D.py:1741-2442)
 # ----------------------------------------------------------------------------------------------
@@ -1170,6 +1196,7 @@ class WindowDenoiser:
       passes to ``ops.ddpm_step``;
     * ``finish(x)``: the final clamp and ``unnormalize_img`` on a tensor of any shape;
     * ``self_cond``: whether the U-Net takes the previous step's x0;
+    * ``state_space(x)`` = ``imagen.normalize_img``: a volume in the units ``finish`` returns, in state space (every sampler);
     * ``sampler='ddpm'`` only -- what ``VolumeInference(joint=True, inpaint=...)`` needs of the one sampler with a re-noising loop:
       ``normalize(x)`` = ``imagen.normalize_img`` (a known volume into state space; ``sample`` takes its ``inpaint_images`` there
       already, as the reference does), host fp32 ``qs`` [T,2] = the (alpha, sigma) of ``q_sample`` at every step and ``renoise`` [T,2] =
@@ -1199,6 +1226,12 @@ class WindowDenoiser:
     def _tables(self, batch):
         return Imagen._sampler_tables(self.imagen.noise_schedulers[self.index], batch, self.sampler, self.sample_steps, None, self.eta,
                                       self.pred_objective)
+
+    def state_space(self, x):
+        """A volume in the units ``finish`` returns, in state space (``imagen.normalize_img``) -- every sampler has it: what
+        ``VolumeInference(joint=True, consistency=...)`` does to the measurement.  (``normalize``, the same map, exists for
+        ``sampler='ddpm'`` only and marks the denoiser that can inpaint.)"""
+        return self.imagen.normalize_img(x)
 
     @torch.no_grad()
     def x0(self, img, lowres, i, self_cond=None):
@@ -1477,7 +1510,7 @@ class Imagen(nn.Module):
     def p_sample_loop(self, unet, shape, *, noise_scheduler, lowres_cond_img=None, cond_images=None, inpaint_images=None,
                       inpaint_masks=None, inpaint_resample_times=5, init_images=None, skip_steps=None, cond_scale=1,
                       pred_objective='noise', dynamic_threshold=True, use_tqdm=True, noise=None, sampler='ddpm',
-                      sample_steps=None, eta=0.0):
+                      sample_steps=None, eta=0.0, consistency=None, consistency_weight=1.0):
         """Ancestral sampler (:2059-2160).  Per step: one U-Net eval (HIP) + ONE fused posterior-step kernel;
         the per-step coefficients for all steps are computed on the host up front.  ``noise`` (optional) is a list
         [init, step_0, ...] of injected tensors with the reference's draw order (:2080, :2051), or a callable
@@ -1495,11 +1528,19 @@ class Imagen(nn.Module):
         runs ``inpaint_resample_times`` passes, r = R - 1 .. 0 (:2116-2146).  A pass draws the q-noise and pastes
         ``q_sample(inpaint_images, t)`` under the mask, steps as ever (one more draw) and -- unless r == 0 or the step ends at t = 0 --
         draws once more for the re-noise ``q_sample_from_to(img, t_next, t)``; that re-noise and the paste of the next pass are ONE
-        ``ops.ddpm_inpaint_paste`` launch.  ``inpaint_draws`` counts the draws."""
+        ``ops.ddpm_inpaint_paste`` launch.  ``inpaint_draws`` counts the draws.
+
+        ``consistency=(meas_up, cell)`` with ``consistency_weight`` (any sampler; ``check_consistency``): data-consistent sampling for a
+        block-average measurement (DDNM).  ``meas_up`` [B,C,P,P,P] is the measurement replicated onto the high-res grid
+        (``ops.cell_replicate``), in state space like ``inpaint_images``.  Per step the x0 prediction (thresholded, if configured) goes
+        through ``ops.cell_project`` with the chain's clamp -- the cell means of the clamped prediction are moved onto the measurement's
+        -- and ``ops.ddpm_step`` then runs with the clamp switched off (an infinite box is the identity bit for bit): clamping after the
+        projection would undo it.  The x0 the step returns, which self-conditioning and ``'dpmpp2m'`` read, is the projected one."""
         if pred_objective not in ('noise', 'x_start', 'v'):
             raise ValueError(f'unknown objective {pred_objective}')
         has_inpainting = exists(inpaint_images) and exists(inpaint_masks)                  # (:2090-2091)
         self._check_sampler_args(sampler, sample_steps, skip_steps, eta, has_inpainting)
+        consistency = check_consistency('p_sample_loop', consistency, consistency_weight, shape, has_inpainting, init_images, skip_steps)
         device = self.device
         batch = shape[0]
         if callable(noise):
@@ -1529,6 +1570,11 @@ class Imagen(nn.Module):
         lo, hi, mode = self._clamp_cfg()
         lowres = lowres_cond_img.to(device).float().contiguous() if exists(lowres_cond_img) else None
         inf = float('inf')
+        if dynamic_threshold:                                               # the prediction arrives thresholded: no clamp in the step
+            lo, hi, mode = -inf, inf, 1
+        if exists(consistency):
+            meas_up, cell, weight = consistency
+            meas_up = meas_up.to(device).float().contiguous()
 
         noisy_dev, x0_dev = [], []
         x_start = None
@@ -1546,7 +1592,8 @@ class Imagen(nn.Module):
                 pred = self._x0_prediction(unet, img, conds[i], x0c[i], lowres, x_start if unet.self_cond else None, cond_images,
                                            cond_scale, pred_objective, dynamic_threshold)
                 third = x_start if multistep and i > 0 else step_noise()      # 'dpmpp2m': the previous step's clamped x0
-                if dynamic_threshold:
+                if exists(consistency):                                       # the clamp, then the projection; the step clamps no more
+                    pred = ops.cell_project(pred, meas_up, cell, weight, clamp=(lo, hi, mode))
                     img, x_start = ops.ddpm_step(img, pred, third, coefs[i, 0], coefs[i, 1], coefs[i, 2], -inf, inf, 1)
                 else:
                     img, x_start = ops.ddpm_step(img, pred, third, coefs[i, 0], coefs[i, 1], coefs[i, 2], lo, hi, mode)
@@ -1567,10 +1614,15 @@ class Imagen(nn.Module):
                inpaint_masks=None, inpaint_resample_times=5, init_images=None, skip_steps=None, batch_size=1,
                cond_scale=1., lowres_sample_noise_level=None, start_at_unet_number=1, start_image_or_video=None,
                stop_at_unet_number=None, return_all_outputs=False, return_all_unet_outputs=None, return_pil_images=False,
-               device=None, use_tqdm=True, noise=None, sampler='ddpm', sample_steps=None, eta=0.0):
+               device=None, use_tqdm=True, noise=None, sampler='ddpm', sample_steps=None, eta=0.0, consistency=None,
+               consistency_weight=1.0):
         """imagen_pytorch3D.py:2165-2274 -> (img, [noisy per step], [x0 per step]).  Accepts both spellings
         ``return_all_outputs`` / ``return_all_unet_outputs`` (test.py:182 uses the latter).  ``sampler`` / ``sample_steps`` / ``eta``
-        (one value, or one per U-Net like ``skip_steps``) and the list or callable ``noise``: see ``p_sample_loop``."""
+        (one value, or one per U-Net like ``skip_steps``) and the list or callable ``noise``: see ``p_sample_loop``, as for
+        ``consistency=(meas_up, cell)`` / ``consistency_weight``, which every sampled U-Net gets (so they must generate one size).  Its
+        refusals are ``ValueError`` naming "consistency", raised before anything touches the device: together with inpainting,
+        ``init_images`` or ``skip_steps``, a weight outside (0, 1], a cell that does not divide the image size or with
+        n outside 2 .. 64, a ``meas_up`` that is not [B,C,P,P,P]."""
         if exists(return_all_unet_outputs):
             return_all_outputs = return_all_unet_outputs
         num_unets = len(self.unets)
@@ -1578,6 +1630,9 @@ class Imagen(nn.Module):
         sampler, sample_steps, eta = (cast_tuple(v, num_unets) for v in (sampler, sample_steps, eta))
         for args in zip(sampler, sample_steps, skip_steps, eta):
             self._check_sampler_args(*args, exists(inpaint_images) and exists(inpaint_masks))
+        for n in range(start_at_unet_number, default(stop_at_unet_number, num_unets) + 1) if exists(consistency) else ():
+            check_consistency('sample', consistency, consistency_weight, (batch_size, self.channels) + (self.image_sizes[n - 1],) * 3,
+                              exists(inpaint_images) and exists(inpaint_masks), cast_tuple(init_images, num_unets)[n - 1], skip_steps[n - 1])
         device = default(device, self.device)
         self.reset_unets_all_one_device(device=device)
         cond_scale = cast_tuple(cond_scale, num_unets)
@@ -1603,7 +1658,8 @@ class Imagen(nn.Module):
                 inpaint_resample_times=inpaint_resample_times, init_images=unet_init_images, skip_steps=unet_skip_steps,
                 cond_scale=unet_cond_scale, lowres_cond_img=lowres_cond_img, noise_scheduler=noise_scheduler,
                 pred_objective=pred_objective, dynamic_threshold=dynamic_threshold, use_tqdm=use_tqdm, noise=noise,
-                sampler=unet_sampler, sample_steps=unet_sample_steps, eta=unet_eta)
+                sampler=unet_sampler, sample_steps=unet_sample_steps, eta=unet_eta, consistency=consistency,
+                consistency_weight=consistency_weight)
             outputs.append(img)
             if exists(stop_at_unet_number) and stop_at_unet_number == unet_number:
                 break

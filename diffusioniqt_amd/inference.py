@@ -76,6 +76,24 @@ state too: the initial image under the first paste, then R passes per step, each
 launch that carries the step, the re-noise and the paste of the next pass -- 1 + R T fused launches.  That family's loop does not paste
 the known values after the chain, so a known voxel comes back denoised, not exactly, unless the denoiser was made with
 ``paste_known=True``.
+
+Consistency (``consistency=(measurement, cell)``, ``consistency_weight=w``) ties the generated volume to an acquisition whose
+degradation is a block average -- thick slices: ``measurement`` [D/fz, H/fy, W/fx] holds the mean of every cell of ``cell`` = (fz, fy, fx)
+high-res voxels, n = fz fy fx in 2 .. 64.  After every U-Net evaluation the x0 prediction is replaced by x0 + w A+(y - A x0) (DDNM, Wang,
+Yu, Zhang 2023; A the cell mean, A+ replication): the cell means move onto the measurement, the detail inside a cell -- the null space
+of A, what the network is for -- stays.  ``w = 1`` is DDNM, ``w < 1`` its relaxation for a noisy measurement.  The measurement is
+replicated onto the high-res grid once (``ops.cell_replicate``) and z-scored like the low-res volume.  In the crop and blend modes every
+sampler call gets its windows of that volume as ``consistency=(windows, cell)`` and projects on its own (``ops.cell_project``), so the
+stride and the window must be multiples of the cell: no cell may straddle a window.  With ``joint=True`` the projection is part of the
+fused launch (``ops.volume_joint_consistent_step`` in place of the three linear steps, as many launches as before), on the fused x0 of
+the one state: it is defined for every cell of the volume whose voxels are all covered, windows that share a cell are corrected by the
+same amount, and only the volume has to be a multiple of the cell.  What is exactly consistent (w = 1, to fp32 rounding) is the last
+corrected prediction.  The sigma-space chain ends at sigma = 0 with (kx, k0) = (0, 1): the state it ends in IS that prediction.  The
+schedules of the DDPM family end at a finite log-SNR, so their last step keeps a little of the state (4 ddim steps of the cosine
+schedule end on kx = 0.032, k0 = 0.971) and the final cell means are kx A x_t + k0 y.  What comes after the chain -- the denoiser's
+final clamp, and in ``ops.volume_joint_finish`` the fill of uncovered voxels and the background reset -- is not projected again, and
+cells they touch are no longer exactly consistent.  Not offered: the EDM Heun sampler (two predictions per step), and consistency
+together with inpainting.
 """
 from types import SimpleNamespace
 
@@ -252,6 +270,39 @@ class VolumeInference:
                              "chains and the multistep chains have no re-noising loop")
         return known.float(), mask
 
+    @staticmethod
+    def _check_consistency(consistency, weight, inpaint, joint, sample_fn):
+        """The argument rules of ``consistency`` (``ValueError`` naming "consistency"; nothing touches the device).  Returns None or
+        (measurement fp32, cell, weight), the tensor on the host or the device as it was given."""
+        if consistency is None:
+            return None
+        if not isinstance(consistency, (tuple, list)) or len(consistency) != 2:
+            raise ValueError(f"VolumeInference: consistency must be (measurement, cell), got {type(consistency).__name__}")
+        if inpaint is not None:
+            raise ValueError("VolumeInference: consistency and inpaint are not offered together")
+        meas, cell = consistency
+        cell, weight = ops.consistency_cell("VolumeInference", cell, weight)
+        meas = torch.as_tensor(meas)
+        if meas.ndim != 3 or not meas.is_floating_point():
+            raise ValueError(f"VolumeInference: the consistency measurement must be a float [D/fz, H/fy, W/fx] tensor, got {meas.dtype} "
+                             f"{tuple(meas.shape)}")
+        if joint and getattr(sample_fn, 'heun', False):
+            raise ValueError("VolumeInference: consistency is not offered with the EDM Heun denoiser (two predictions per step and three "
+                             "joint volumes): use window_denoiser(sampler='dpmpp2m')")
+        if joint and not hasattr(sample_fn, 'state_space'):
+            raise ValueError("VolumeInference: joint=True with consistency needs a denoiser with state_space(x), the map of the "
+                             "measurement into the space of the state")
+        return meas.float(), cell, weight
+
+    def _consistency_volume(self, win):
+        """The measurement on the high-res grid, z-scored like the low-res volume, on the volume's device: fp32 [D,H,W]."""
+        meas, cell, _ = self.consistency                     # ``__call__`` has checked its shape
+        return ((ops.cell_replicate(meas.to(win.device), cell) - self.mean) / self.std).contiguous()
+
+    def _consistency_windows(self, cw):
+        """What a sampler call takes besides ``x``: the batch's windows of the replicated measurement."""
+        return dict(consistency=(cw, self.consistency[1]), consistency_weight=self.consistency[2])
+
     def _inpaint_volumes(self, win):
         """The known volume and the mask as 0/1 floats on the volume's device (``__call__`` has checked their shape)."""
         known, mask = self.inpaint
@@ -262,7 +313,7 @@ class VolumeInference:
         return dict(inpaint_images=kw, inpaint_masks=mw[:, 0] > 0.5, inpaint_resample_times=self.resample_times)
 
     def __init__(self, configs, sample_fn, nonzero_ratio=0.05, blend=None, sigma_scale=0.125, samples=1, noise=None, seed=0, joint=False,
-                 inpaint=None, inpaint_resample_times=5):
+                 inpaint=None, inpaint_resample_times=5, consistency=None, consistency_weight=1.0):
         """``sample_fn(lr_patches [B,1,S,S,S]) -> hr_patches`` — e.g. ``lambda x: trainer.sample(batch_size=x.shape[0],
         start_image_or_video=x, start_at_unet_number=2)[0]`` (test_all.py:234).  ``blend`` / ``sigma_scale`` / ``samples``: weighted
         overlap blending and multi-sample statistics, see the module docstring.  ``noise='anchored'`` (with ``seed``): every call
@@ -285,8 +336,18 @@ class VolumeInference:
         ``ValueError`` naming "inpaint" before anything touches the device: a pair that is not (float [D,H,W], bool [D,H,W]) of one
         shape -- or, in ``__call__``, not the volume's --, ``inpaint_resample_times`` that is not a positive integer, joint mode with a
         denoiser that is neither ``heun`` nor one with the ancestral sampler's ``qs`` / ``renoise`` tables (DDIM and the multistep
-        chains have no re-noising loop)."""
+        chains have no re-noising loop).
+
+        ``consistency=(measurement, cell)`` with ``consistency_weight=w``: ``measurement`` a float tensor [D/fz, H/fy, W/fx] of RAW
+        intensities (host or device), the block average of the volume to be generated over cells of ``cell`` = (fz, fy, fx) voxels;
+        every x0 prediction has its cell means moved onto it (module docstring).  In the crop and blend modes every call becomes
+        ``sample_fn(x[, noise=src], consistency=(windows, cell), consistency_weight=w)``; with ``joint=True`` the projection rides in
+        the fused launch of the three linear chains.  ``ValueError`` naming "consistency" before anything touches the device: a pair
+        that is not (float [.,.,.] tensor, (fz, fy, fx) integers >= 1 with 2 <= fz fy fx <= 64), a weight outside (0, 1], together with
+        ``inpaint``, joint mode with a Heun denoiser, a stride or window the cell does not divide (crop and blend modes) -- and, in
+        ``__call__``, a measurement that is not the volume's shape divided by the cell."""
         self.inpaint = self._check_inpaint(inpaint, inpaint_resample_times, joint, sample_fn)
+        self.consistency = self._check_consistency(consistency, consistency_weight, self.inpaint, joint, sample_fn)
         self.resample_times = inpaint_resample_times
         if noise not in NOISE_MODES:
             raise ValueError(f"VolumeInference: noise must be None or 'anchored', got {noise!r}")
@@ -322,6 +383,12 @@ class VolumeInference:
         self.overlap = int(configs['Eval']['overlap'])
         self.batch = int(configs['Eval'].get('batch_size', 27))
         self.mean, self.std = float(configs['Data']['mean']), float(configs['Data']['std'])
+        if self.consistency is not None and not self.joint:
+            for f in self.consistency[1]:                    # per axis: origins are multiples of the stride, a sampler call sees `sub`
+                if self.overlap % f or self.sub % f:
+                    raise ValueError(f"VolumeInference: the consistency cell {self.consistency[1]} must divide the stride "
+                                     f"{self.overlap} and the window {self.sub}: a per-window projection is defined for cells inside "
+                                     f"a window only (joint=True projects on the whole volume)")
 
     @torch.no_grad()
     def __call__(self, lowres_raw, patch_slice=None, return_std=False):
@@ -336,6 +403,10 @@ class VolumeInference:
         if self.inpaint is not None and tuple(self.inpaint[0].shape) != tuple(lowres_raw.shape):
             raise ValueError(f"VolumeInference: the inpaint volumes {tuple(self.inpaint[0].shape)} are not the volume's shape "
                              f"{tuple(lowres_raw.shape)}")
+        if self.consistency is not None and \
+                tuple(s * f for s, f in zip(self.consistency[0].shape, self.consistency[1])) != tuple(lowres_raw.shape):
+            raise ValueError(f"VolumeInference: the consistency measurement {tuple(self.consistency[0].shape)} times the cell "
+                             f"{self.consistency[1]} is not the volume's shape {tuple(lowres_raw.shape)}")
         if self.blend is not None:
             if patch_slice is not None:
                 raise NotImplementedError("VolumeInference: a blend mode does not split one volume's windows over ranks (that needs a "
@@ -352,6 +423,8 @@ class VolumeInference:
         # below half a patch: one scatter launch per patch, in candidate order, keeps "later overwrites" deterministic
         serial_scatter = (not self.block_mode) and self.overlap < P and P - 2 * (self.overlap // 2) > self.overlap
         known = self._inpaint_volumes(win) if self.inpaint is not None else ()
+        if self.consistency is not None:
+            known = (self._consistency_volume(win),)
         for lo, o, idx in win.batches:
             x, _ = ops.patch_gather(vol, idx, P, self.mean, self.std)
             kmw = [self._split(ops.patch_gather(v, idx, P, 0., 1.)[0]) for v in known]            # (v - 0) / 1: the volumes' own bits
@@ -373,8 +446,9 @@ class VolumeInference:
 
     def _sample(self, x, win, origins, s, kw=None, mw=None):
         """One sampler call on the windows at ``origins`` (block mode: ONE block, already split into its sub-volumes), sample ``s``;
-        ``kw`` / ``mw``: the same windows of the known volume and of the 0/1 mask when the call inpaints."""
-        inpaint = {} if kw is None else self._inpaint_windows(kw, mw)
+        ``kw`` / ``mw``: the same windows of the known volume and of the 0/1 mask when the call inpaints -- or ``kw`` alone, the
+        windows of the replicated measurement, when it is held to one."""
+        inpaint = {} if kw is None else self._consistency_windows(kw) if mw is None else self._inpaint_windows(kw, mw)
         if self.noise is None:
             return self.sample_fn(x, **inpaint)
         src = AnchoredNoise(win.shape, self.seed).source(win.noise_origins(origins), self.sub, sample=s, device=x.device)
@@ -400,8 +474,10 @@ class VolumeInference:
         P, S = self.patch, self.samples
         patches = torch.empty((S, win.N, P, P, P), dtype=torch.float32, device=win.device)
         known = [(v, 0., 1.) for v in self._inpaint_volumes(win)] if self.inpaint is not None else []
+        if self.consistency is not None:
+            known = [(self._consistency_volume(win), 0., 1.)]
 
-        def call(x, *rest):                                  # the windows of the known volume and the mask (if any), then the origins
+        def call(x, *rest):                                  # the windows of the known volume and the mask, or of the measurement (if any), then the origins
             *kmw, o = rest
             return (self._sample(x, win, o, s, *kmw) for s in range(S))
         self._evaluate(win, [(vol, self.mean, self.std)] + known, call, patches)
@@ -417,7 +493,8 @@ class VolumeInference:
         chain = self._heun_chain if den.heun else self._linear_chain
         y = torch.empty((win.N, P, P, P), dtype=torch.float32, device=win.device)          # reused by every step of every sample
         # and so is the fused x0 volume of the first-order and multistep chains; the Heun chain makes its three volumes per sample
-        win.x0_vol = torch.empty_like(vol) if (den.self_cond or den.multistep) and not den.heun else None
+        # (the consistent launch always writes its corrected x0)
+        win.x0_vol = torch.empty_like(vol) if (den.self_cond or den.multistep or self.consistency is not None) and not den.heun else None
 
         def evaluate(state, cond, x0):
             self._evaluate(win, [(state, 0., 1.), (vol, self.mean, self.std), (cond, 0., 1.)], x0, y)   # (v - 0) / 1: the state's own bits
@@ -426,6 +503,9 @@ class VolumeInference:
         if self.inpaint is not None:                         # the known volume in state space, the mask as bytes (the kernels') and 0/1
             known, mask_f = self._inpaint_volumes(win)
             inp = (self.sample_fn.normalize(known).contiguous(), mask_f.to(torch.uint8), mask_f)
+        win.meas_up = None                                   # the replicated measurement in state space, for the fused launch
+        if self.consistency is not None:
+            win.meas_up = self.sample_fn.state_space(self._consistency_volume(win)).contiguous()
         mean_io = m2_io = out_std = None
         for s in range(S):
             x = chain(den, win, evaluate, y, s, *inp[:2])
@@ -482,7 +562,14 @@ class VolumeInference:
         for i in range(den.num_steps):
             evaluate(x, win.x0_vol if den.self_cond and i > 0 else None, self._window_x0(den, win, s, i, edm=den.sigma_space))
             prev = win.x0_vol if i else None
-            if den.sigma_space:                              # coefs[i] = (kx, k0, kp, kn): + kp x0_prev + kn n(draw_base + 1 + i)
+            if win.meas_up is not None:                      # the same three updates behind the projection of the fused x0
+                form = 2 if den.sigma_space else 1 if den.multistep else 0
+                kx, k0, k2, k3 = (*den.coefs[i], 0.)[:4]     # rows (kx, k0, kn), (kx, k0, kp) or (kx, k0, kp, kn)
+                draw = den.draw_base + 1 + i if den.sigma_space else i + 1
+                ops.volume_joint_consistent_step(*head, prev, win.meas_up, self.consistency[1], self.consistency[2], form, kx, k0,
+                                                 0. if form == 0 else k2, k2 if form == 0 else k3, *tail, self.seed, draw=draw, sample=s,
+                                                 **io)
+            elif den.sigma_space:                            # coefs[i] = (kx, k0, kp, kn): + kp x0_prev + kn n(draw_base + 1 + i)
                 ops.volume_joint_multistep_sde(*head, prev, *den.coefs[i], *tail, self.seed, draw=den.draw_base + 1 + i, sample=s, **io)
             elif den.multistep:                              # (kx, k0, kp): + kp x0_prev; only draw 0 of the field is used
                 ops.volume_joint_multistep(*head, prev, *den.coefs[i], *tail, **io)

@@ -2711,6 +2711,103 @@ def volume_joint_multistep_sde(y, slot, taps, x_t, x0_prev, kx, k0, kp, kn, lo, 
     return out, x0_out
 
 
+def consistency_cell(who, cell, weight=1.0, extents=()):
+    """The host rules of the data-consistency arguments (``ValueError`` naming "consistency"; nothing touches the device): ``cell`` =
+    (fz, fy, fx) integers >= 1 with 2 <= fz fy fx <= 64, ``weight`` a number in (0, 1] (0 is refused: it would differ from "off" in the
+    sign of a zero), and every (size, axis) of ``extents`` a multiple of that axis' factor.  Returns ``(cell, weight)`` as ints / float."""
+    import numbers
+    ok = isinstance(cell, (tuple, list)) and len(cell) == 3 and all(
+        not isinstance(f, bool) and isinstance(f, numbers.Integral) and f >= 1 for f in cell)
+    if not ok or not 2 <= cell[0] * cell[1] * cell[2] <= 64:
+        raise ValueError(f"{who}: the consistency cell must be (fz, fy, fx), integers >= 1 with 2 <= fz fy fx <= 64, got {cell!r}")
+    if isinstance(weight, bool) or not isinstance(weight, (int, float)) or not 0. < weight <= 1.:
+        raise ValueError(f"{who}: the consistency weight must be a number in (0, 1], got {weight!r}")
+    cell = tuple(int(f) for f in cell)
+    for size, axis in extents:
+        if int(size) % cell[axis]:
+            raise ValueError(f"{who}: the consistency cell {cell} does not divide the size {int(size)} of axis {axis}")
+    return cell, float(weight)
+
+
+def cell_mean(vol, cell):
+    """The block average of a [D,H,W] volume over cells of ``cell`` = (fz, fy, fx) voxels (include/diqt.h, diqt_cell_mean): fp32
+    [D/fz, H/fy, W/fx], each value the cell's sum in (z, y, x) order divided by n -- the measurement operator of the ``consistency``
+    modes, e.g. to simulate a thick-slice acquisition.  One launch."""
+    _chk(vol)
+    if vol.ndim != 3 or not vol.is_contiguous() or vol.numel() == 0:
+        raise ValueError(f"cell_mean: vol must be a non-empty contiguous [D,H,W] tensor, got {tuple(vol.shape)}")
+    cell, _ = consistency_cell("cell_mean", cell, 1.0, [(s, a) for a, s in enumerate(vol.shape)])
+    out = torch.empty(tuple(s // f for s, f in zip(vol.shape, cell)), dtype=torch.float32, device=vol.device)
+    _lib.call("diqt_cell_mean", vol, out, *vol.shape, *cell, _stream())
+    return out
+
+
+def cell_replicate(meas, cell):
+    """A measurement [D/fz, H/fy, W/fx] replicated onto the high-res grid [D,H,W] (every voxel holds its cell's value): what the
+    ``consistency`` kernels read as ``meas_up``.  ``repeat_interleave`` on the three axes; no kernel of this library."""
+    if not torch.is_tensor(meas) or meas.ndim != 3 or not meas.is_floating_point():
+        raise ValueError(f"cell_replicate: the consistency measurement must be a float [D/fz, H/fy, W/fx] tensor, got "
+                         f"{tuple(meas.shape) if torch.is_tensor(meas) else type(meas).__name__}")
+    cell, _ = consistency_cell("cell_replicate", cell)
+    out = meas.float()
+    for axis, f in enumerate(cell):
+        out = out.repeat_interleave(f, dim=axis)
+    return out.contiguous()
+
+
+def cell_project(x0, meas_up, cell, weight=1.0, clamp=None, out=None):
+    """The data-consistency projection of a window batch (include/diqt.h, diqt_cell_project): ``x0`` / ``meas_up`` [B,C,P,P,P] the
+    prediction and the replicated measurement in the same space, ``cell`` = (fz, fy, fx), ``clamp`` = (lo, hi, mode) with
+    ``ddpm_step``'s meaning (None: no clamp).  a = clamp(x0); per cell m = the mean of a; out = a + weight (meas_up - m).  ``out``:
+    where it goes (``x0`` itself for an in-place projection; None: a new tensor).  Returns ``out``.  One launch."""
+    who = "cell_project"
+    _chk(x0, meas_up, out)
+    if x0.ndim != 5 or x0.numel() == 0 or len(set(x0.shape[2:])) != 1:
+        raise ValueError(f"{who}: x0 must be a non-empty [B,C,P,P,P] tensor of cubes, got {tuple(x0.shape)}")
+    if out is None:
+        out = torch.empty_like(x0)
+    for t, name in ((meas_up, 'meas_up'), (out, 'out')):
+        if t.shape != x0.shape:
+            raise ValueError(f"{who}: {name} must have x0's shape {tuple(x0.shape)}, got {tuple(t.shape)}")
+    if not (x0.is_contiguous() and meas_up.is_contiguous() and out.is_contiguous()):
+        raise RuntimeError(f"{who}: tensors must be contiguous")
+    P = x0.shape[2]
+    cell, weight = consistency_cell(who, cell, weight, [(P, a) for a in range(3)])
+    lo, hi, mode = (0., 0., 2) if clamp is None else clamp                # the entry's third mode: no clamp
+    if clamp is not None and int(mode) not in (0, 1):
+        raise ValueError(f"{who}: clamp mode must be 0 (min) or 1 (box), got {mode!r}")
+    _lib.call("diqt_cell_project", x0, meas_up, out, x0.shape[0] * x0.shape[1], P, *cell, weight, float(lo), float(hi), int(mode), _stream())
+    return out
+
+
+def volume_joint_consistent_step(y, slot, taps, x_t, x0_prev, meas_up, cell, weight, form, kx, k0, kp, kn, lo, hi, clamp_mode, stride,
+                                 seed=0, draw=0, sample=0, out=None, x0_out=None):
+    """One step of a joint chain with the data-consistency projection between the fuse and the update (include/diqt.h,
+    diqt_volume_joint_consistent_step).  ``form`` 0 / 1 / 2: the update of ``volume_joint_step`` (``x0_prev`` and ``kp`` are not looked
+    at) / ``volume_joint_multistep`` (``kn`` and the noise key are not) / ``volume_joint_multistep_sde``.  ``meas_up`` [D,H,W]: the
+    replicated measurement in state space; ``cell`` = (fz, fy, fx) must divide the volume, ``weight`` in (0, 1].  Every cell whose
+    voxels are all covered has the mean of its fused x0 moved onto the measurement (by ``weight`` of the way) before the update; a
+    cell with an uncovered voxel steps as in the plain launch.  ``out`` / ``x0_out``: where x_next and the corrected x0 (0 where
+    uncovered) go -- ``x_t`` and ``x0_prev`` themselves for an in-place step, None: new tensors.  Returns ``(out, x0_out)``.  One launch,
+    bit-reproducible."""
+    who = "volume_joint_consistent_step"
+    form = int(form)
+    if form not in (0, 1, 2):
+        raise ValueError(f"{who}: form must be 0 (first order), 1 (multistep) or 2 (multistep with noise), got {form!r}")
+    N, P, stride = _joint_windows(who, y, slot, taps, x_t, clamp_mode, stride)
+    seed, draw, sample = _noise_key(who, seed, draw, sample)
+    _joint_slots(who, slot, N)
+    cell, weight = consistency_cell(who, cell, weight, [(s, a) for a, s in enumerate(x_t.shape)])
+    _chk(meas_up)
+    if meas_up.shape != x_t.shape or not meas_up.is_contiguous():
+        raise ValueError(f"{who}: meas_up must be a contiguous tensor of x_t's shape")
+    out, x0_out = _joint_volumes(who, x_t, None if form == 0 else x0_prev, out, x0_out)
+    _lib.call("diqt_volume_joint_consistent_step", y if N else None, slot, taps, x_t, None if form == 0 else x0_prev, meas_up, out, x0_out,
+              form, N, *x_t.shape, P, stride, *slot.shape, *cell, weight, float(kx), float(k0), float(kp), float(kn), float(lo), float(hi),
+              int(clamp_mode), seed, draw, sample, _stream())
+    return out, x0_out
+
+
 def volume_joint_heun_init(shape, sigma0, kc, seed, draw=0, sample=0, device=None):
     """The first ``images_hat`` of a joint Heun chain (phase 0 of ``diqt_volume_joint_heun``): fp32 [D,H,W],
     ``(sigma0 n(draw)) + kc n(draw + 1)`` with n the volume-anchored normals of channel 0 -- the initial image as

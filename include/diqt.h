@@ -716,6 +716,42 @@ int diqt_volume_joint_multistep_sde(const float* y, const int* slot, const float
                                     float* x_next, float* x0_out, int N, int D, int H, int W, int P, int stride, int G0, int G1, int G2,
                                     float kx, float k0, float kp, float kn, float lo, float hi, int clamp_mode, unsigned long long seed,
                                     unsigned draw, unsigned sample, void* stream);
+/* Data-consistent sampling for a block-average measurement (DDNM; Wang, Yu, Zhang, ICLR 2023).  A cell is (fz, fy, fx) voxels, every
+ * factor >= 1 and n = fz fy fx in 2 .. 64; voxel (z, y, x) belongs to cell (z / fz, y / fy, x / fx).  The measurement is the cell mean
+ * (the operator A) and the kernels read it REPLICATED on the high-res grid: meas_up[v] = the measurement of v's cell (A+ applied to
+ * it).  The projection of the values a over one cell, in fp32 with no contraction, ONE definition for every entry below:
+ *     s = 0;  s = s + a[v] over the cell's voxels in lexicographic (z, y, x) order;  m = s / (float)n;
+ *     a'[v] = fmaf(w, meas_up[v] - m, a[v])     for every voxel of the cell, w the consistency weight, 0 < w <= 1
+ * (w = 1: x0' = x0 + A+(y - A x0), the cell means land on the measurement and the detail inside a cell is untouched; w < 1: DDNM's
+ * relaxation for a noisy measurement).  Error codes shared by the three entries: a null pointer: DIQT_E_ALIGN; a cell with a factor
+ * < 1 or n outside 2 .. 64, or w outside (0, 1]: DIQT_E_UNSUPPORTED; an extent the cell does not divide: DIQT_E_SHAPE.
+ *
+ * diqt_cell_mean: out [D / fz][H / fy][W / fx] = m of x [D][H][W] -- A itself, to simulate a measurement.  out may not alias x.     */
+int diqt_cell_mean(const float* x, float* out, int D, int H, int W, int fz, int fy, int fx, void* stream);
+/* The per-window step: x0 / meas_up / out hold `cubes` cubes of edge P ([B][C P^3]: B C cubes).  a = c(x0) with c the clamp of
+ * diqt_ddpm_step (clamp_mode 0: max(x0, lo); 1: min(max(x0, lo), hi)) or, clamp_mode 2, the identity; then the projection.  The clamp
+ * belongs here because the projection must come after it: the step that follows takes the result unclamped.  out may alias x0 (a
+ * thread reads and writes the voxels of its own cells only); meas_up may not alias out.  P % fz, P % fy or P % fx != 0 or cubes == 0:
+ * DIQT_E_SHAPE; clamp_mode outside {0, 1, 2}: DIQT_E_UNSUPPORTED.                                                                  */
+int diqt_cell_project(const float* x0, const float* meas_up, float* out, size_t cubes, int P, int fz, int fy, int fx, float weight,
+                      float lo, float hi, int clamp_mode, void* stream);
+/* The three linear updates of the joint state with the projection between the fuse and the update; meas_up is [D][H][W] in state
+ * space.  `form`, uniform over the launch: 0 = diqt_volume_joint_step (x0_prev and kp are ignored), 1 = diqt_volume_joint_multistep
+ * (kn, seed, draw and sample are ignored), 2 = diqt_volume_joint_multistep_sde.  Window walk, clamp, lattice check, the normals and
+ * the update of each form are that entry's.  Per cell: every voxel is fused as there, x0 = num / den under the step clamp.  A cell
+ * whose voxels are ALL covered (den != 0) takes the projection of its fused x0, and each of its voxels the form's update with x0' in
+ * the place of x0.  A cell with an uncovered voxel is left alone: its covered voxels take the update with their plain x0, its
+ * uncovered voxels keep x_t and get x0_out = 0.  x0_out is required and receives x0' (self-conditioning and the multistep history see
+ * the corrected prediction).  There is no initial state (x_t == NULL is DIQT_E_ALIGN): the plain entries make it.  x_next may alias
+ * x_t and x0_out may alias x0_prev: a thread reads and writes only the voxels of cells its block owns, each read before it is written;
+ * meas_up may alias neither output.  No atomics, no waiting across blocks: bit-reproducible, and with stride = P and unit taps the
+ * chain is diqt_cell_project followed by the per-window step, bit for bit.  D % fz, H % fy or W % fx != 0, or a lattice that does
+ * not match: DIQT_E_SHAPE; form outside {0, 1, 2} or clamp_mode outside {0, 1}: DIQT_E_UNSUPPORTED.                                */
+int diqt_volume_joint_consistent_step(const float* y, const int* slot, const float* taps, const float* x_t, const float* x0_prev,
+                                      const float* meas_up, float* x_next, float* x0_out, int form, int N, int D, int H, int W, int P,
+                                      int stride, int G0, int G1, int G2, int fz, int fy, int fx, float weight, float kx, float k0,
+                                      float kp, float kn, float lo, float hi, int clamp_mode, unsigned long long seed, unsigned draw,
+                                      unsigned sample, void* stream);
 /* The stochastic Heun sampler of the EDM family (Karras et al. 2022; elucidated_imagen.py:382-532) on the joint state: a churn, a
  * predictor and a corrector per step, two U-Net evaluations.  The state is three [D][H][W] volumes, all updated in place (every thread
  * reads only its own voxel of each, then writes it): xh = images_hat, xn = images_next, x0 = the fused prediction.  Window walk,
