@@ -78,27 +78,14 @@ class EDMWindowDenoiser:
 
     def __init__(self, imagen, unet_number, cond_scale, clamp, sigma_min, sigma_max, unet_context):
         self._configure(imagen, unet_number, cond_scale, clamp, unet_context)
-        hp = self.hp
-        # the schedule and the step scalars exactly as one_unet_sample computes them
-        sigma_min, sigma_max = default(sigma_min, hp.sigma_min), default(sigma_max, hp.sigma_max)
-        sigmas = imagen.sample_schedule(hp.num_sample_steps, hp.rho, sigma_min, sigma_max)
-        gammas = torch.where((sigmas >= hp.S_tmin) & (sigmas <= hp.S_tmax), min(hp.S_churn / hp.num_sample_steps, sqrt(2) - 1), 0.)
-        self._steps = list(zip(sigmas[:-1].tolist(), sigmas[1:].tolist(), gammas[:-1].tolist()))
+        self._steps, self._hats, rows, self.sigma0 = imagen._heun_tables(self.index, sigma_min, sigma_max)   # one_unet_sample's own
         self.sched = torch.tensor(self._steps, dtype=torch.float64)                       # [T, 3] on the host: the fp32 values, widened
-        self.sigma0 = sigmas[0].item()
         self.num_steps = len(self._steps)
-        rows = []
-        for sigma, sigma_next, gamma in self._steps:
-            sigma_hat = sigma + gamma * sigma
-            r = (sigma_next - sigma_hat) / sigma_hat
-            r2 = 0.5 * (sigma_next - sigma_hat) / sigma_next if sigma_next != 0 else 0.
-            rows.append([hp.S_noise * sqrt(max(sigma_hat ** 2 - sigma ** 2, 0.)), 1. + r, -r, 1. + 0.5 * r, -0.5 * r, r2, -r2])
         self.coefs = torch.tensor(rows, dtype=torch.float64).to(torch.float32)            # [T, 7] on the host, each rounded once
 
     def sigma_of(self, i, stage):
         """The sigma the U-Net is evaluated at: sigma_hat of step i (stage 0) or its sigma_next (stage 1)."""
-        sigma, sigma_next, gamma = self._steps[i]
-        return float(sigma_next) if stage else float(sigma + gamma * sigma)
+        return float(self._steps[i][1] if stage else self._hats[i])
 
     @torch.no_grad()
     def x0(self, img, lowres, i, self_cond=None, stage=0, lowres_noise=None):
@@ -121,12 +108,9 @@ class EDMWindowDenoiser:
                 elu.reset_unets_all_one_device(device=dev)                    # as ``sample`` does before it picks the U-Net
                 unet = elu.unets[self.index]
                 lowres_cond_img = lowres_noise_times = None
-                if self.lowres_cond:                                          # sample(): :652-657
-                    t_cpu = torch.full((B,), float(elu.lowres_sample_noise_level))
-                    lowres_noise_times = t_cpu.to(dev)
-                    size = elu.image_sizes[self.index]
-                    lowres_cond_img = elu.normalize_img(elu._resize(lowres.to(dev), size, img.shape[2])).float().to(dev)
-                    lowres_cond_img = elu._noise_lowres(lowres_cond_img, t_cpu, lowres_noise.to(dev).float())
+                if self.lowres_cond:
+                    lowres_cond_img, lowres_noise_times = elu._lowres_conditioning(
+                        lowres, elu.lowres_sample_noise_level, elu.image_sizes[self.index], img.shape[2], B, dev, lambda x: lowres_noise)
                 sc = dict(self_cond=self_cond) if self.self_cond else {}
                 return elu.preconditioned_network_forward(
                     unet.forward_with_cond_scale, img.float().contiguous(), sigma, sigma_data=self.hp.sigma_data,
@@ -145,13 +129,9 @@ class EDMWindowDenoiser:
     @torch.no_grad()
     def finish(self, x, known=None, mask=None):
         """``known`` (state space) / ``mask`` (0/1 fp32), both of x's shape: the chain inpainted, and the known values go under the mask
-        between the clamp and ``unnormalize_img`` (:527-532)."""
-        flat = x.contiguous().view(1, -1)
-        one = torch.ones(1, device=x.device)
-        flat = ops.axpby3(flat, None, None, one, None, None, -1., 1., 2)
-        if known is not None:
-            flat = ops.mask_blend(flat, known.contiguous().view(1, -1), mask.contiguous().view(1, -1))
-        return self.imagen.unnormalize_img(flat).view(x.shape)
+        between the clamp and ``unnormalize_img`` (:527-532): ``_finish_chain`` on the flat view, a batch of one."""
+        flat = lambda t: t.contiguous().view(1, -1)
+        return self.imagen._finish_chain(flat(x), *((flat(known), flat(mask)) if known is not None else ())).view(x.shape)
 
 
 class EDMMultistepWindowDenoiser(EDMWindowDenoiser):
@@ -378,6 +358,25 @@ class ElucidatedImagen(nn.Module):
                                       default(sigma_max, hp.sigma_max))
         return sigmas, self.dpmpp2m_coefficients(sigmas, eta, hp.S_noise)
 
+    def _heun_tables(self, index, sigma_min, sigma_max, skip_steps=None):
+        """The host table of the stochastic Heun sampler for U-Net ``index``, the one ``one_unet_sample`` and ``EDMWindowDenoiser`` both
+        read, so the one-call and the step-at-a-time sampler cannot drift: ``(sched, hats, coefs, sigma0)`` -- per step after
+        ``skip_steps`` the row (sigma, sigma_next, gamma), sigma_hat = sigma + gamma sigma and the seven scalars
+        ``(kc, 1 + r, -r, 1 + r/2, -r/2, r2, -r2)`` that ``EDMWindowDenoiser`` documents, and the first sigma of the whole schedule.
+        Python floats throughout: the schedule's fp32 values widened, the scalars in double (a consumer rounds them to fp32 once)."""
+        hp = self.hparams[index]
+        sigmas = self.sample_schedule(hp.num_sample_steps, hp.rho, default(sigma_min, hp.sigma_min), default(sigma_max, hp.sigma_max))
+        gammas = torch.where((sigmas >= hp.S_tmin) & (sigmas <= hp.S_tmax), min(hp.S_churn / hp.num_sample_steps, sqrt(2) - 1), 0.)
+        sched = list(zip(sigmas[:-1].tolist(), sigmas[1:].tolist(), gammas[:-1].tolist()))[default(skip_steps, 0):]
+        hats, coefs = [], []
+        for sigma, sigma_next, gamma in sched:
+            sigma_hat = sigma + gamma * sigma
+            r = (sigma_next - sigma_hat) / sigma_hat
+            r2 = 0.5 * (sigma_next - sigma_hat) / sigma_next if sigma_next != 0 else 0.       # no corrector on the step to sigma 0
+            hats.append(sigma_hat)
+            coefs.append((hp.S_noise * sqrt(max(sigma_hat ** 2 - sigma ** 2, 0.)), 1. + r, -r, 1. + 0.5 * r, -0.5 * r, r2, -r2))
+        return sched, hats, coefs, sigmas[0].item()
+
     def threshold_x_start(self, x_start, dynamic_threshold=True):
         """elucidated_imagen.py:298-311: clamp(-1, 1), or per-sample s = max(quantile(|x0|, p), 1) then clamp(-s, s) / s."""
         x_start = x_start.contiguous()
@@ -430,7 +429,7 @@ class ElucidatedImagen(nn.Module):
         step whose kn != 0: every step but the last).  S_churn / S_tmin / S_tmax play no part; S_noise scales kn.  No ``skip_steps``.
 
         ``inpaint_images`` [B,C,D,H,W] (in the units ``sample`` returns) with ``inpaint_masks`` [B,D,H,W] (True: known): the RePaint loop
-        of ``_heun_inpaint_sample``, ``inpaint_resample_times`` passes per step.  The draws are then the initial image and, per
+        of the Heun sampler below, ``inpaint_resample_times`` passes per step.  The draws are then the initial image and, per
         (step, r), the ``eps`` and -- unless r == 0 or it is the last step -- the re-noise normal (``inpaint_draws``).  Only with
         ``sampler='heun'``; one of the two without the other, another sampler or a count that is not a positive integer: ``ValueError``
         before anything touches the device.
@@ -445,74 +444,83 @@ class ElucidatedImagen(nn.Module):
         has_inpainting = self._check_inpaint_args(sampler, inpaint_images, inpaint_masks, inpaint_resample_times)
         consistency = check_consistency('one_unet_sample', consistency, consistency_weight, shape, has_inpainting, init_images,
                                         skip_steps, sampler)
-        if has_inpainting:
-            return self._heun_inpaint_sample(unet, shape, unet_number=unet_number, clamp=clamp, dynamic_threshold=dynamic_threshold,
-                                             cond_scale=cond_scale, inpaint_images=inpaint_images, inpaint_masks=inpaint_masks,
-                                             inpaint_resample_times=int(inpaint_resample_times), init_images=init_images,
-                                             skip_steps=skip_steps, sigma_min=sigma_min, sigma_max=sigma_max, noise=noise, **kwargs)
         if sampler == 'dpmpp2m':
             return self._dpmpp2m_sample(unet, shape, unet_number=unet_number, clamp=clamp, dynamic_threshold=dynamic_threshold,
                                         cond_scale=cond_scale, init_images=init_images, sigma_min=sigma_min, sigma_max=sigma_max,
                                         noise=noise, sample_steps=sample_steps, eta=eta, consistency=consistency, **kwargs)
-        hp = self.hparams[unet_number - 1]
-        sigma_min, sigma_max = default(sigma_min, hp.sigma_min), default(sigma_max, hp.sigma_max)
-        sigmas = self.sample_schedule(hp.num_sample_steps, hp.rho, sigma_min, sigma_max)
-        gammas = torch.where((sigmas >= hp.S_tmin) & (sigmas <= hp.S_tmax), min(hp.S_churn / hp.num_sample_steps, sqrt(2) - 1), 0.)
-        sched = list(zip(sigmas[:-1].tolist(), sigmas[1:].tolist(), gammas[:-1].tolist()))[default(skip_steps, 0):]
+        # Inpainting (:441-449, 473-530; RePaint, Lugmayr et al. 2022) is this loop with ``inpaint_resample_times`` passes per step,
+        # r = R - 1 .. 0, where plain sampling has one: a pass draws ``eps``, pastes the known image under the mask and churns, runs the
+        # two Heun evaluations as ever and -- unless r == 0 or it is the last step -- draws once more and re-noises,
+        # images += (sigma - sigma_next) n.  The re-noise that ends a pass, the paste and the churn that begins the next are ONE
+        # ``ops.edm_inpaint_churn`` launch, in place; without known values the churn is ``ops.axpby3`` into a new tensor, and there
+        # are no masks, no re-noise draw and no paste at the end.  The self-conditioning estimate carries across passes.
+        known = mask_f = mask_b = None
+        if has_inpainting:
+            known, mask_f, mask_b = self._inpaint_operands(inpaint_images, inpaint_masks, shape)
+        sched, hats, coefs, sigma0 = self._heun_tables(unet_number - 1, sigma_min, sigma_max, skip_steps)
+        draw, images, fwd, sc = self._start_chain(unet, shape, unet_number, sigma0, noise, init_images, clamp=clamp,
+                                                  dynamic_threshold=dynamic_threshold, cond_scale=cond_scale, **kwargs)
+        vec = lambda v: torch.full((shape[0],), float(v), device=self.device)
+        x_start = renoise = kr = None
+        for ind, ((sigma, sigma_next, _), sigma_hat, (kc, a, b, a_half, b_half, r2, neg_r2)) in enumerate(zip(sched, hats, coefs)):
+            kc = vec(kc)
+            for resample in reversed(range(int(inpaint_resample_times) if has_inpainting else 1)):
+                eps = draw()
+                if has_inpainting:   # the re-noise of the pass before (if it had one), the paste, the churn: one pass over the state
+                    images_hat = ops.edm_inpaint_churn(images, renoise, known, mask_b, eps, kr, kc, out=images)
+                    renoise = kr = None
+                else:
+                    images_hat = ops.axpby3(images, eps, None, vec(1.), kc, None)
+                out = fwd(images_hat, float(sigma_hat), **sc(x_start))
+                # x_next = x_hat + (s_next - s_hat) * (x_hat - D)/s_hat
+                images_next = ops.axpby3(images_hat, out, None, vec(a), vec(b), None)
+                x_start = out
+                if sigma_next != 0:                                               # 2nd-order correction (:502-516)
+                    out2 = fwd(images_next, float(sigma_next), **sc(out))
+                    tmp = ops.axpby3(images_hat, out, images_next, vec(a_half), vec(b_half), vec(r2))
+                    images_next = ops.axpby3(tmp, out2, None, vec(1.), vec(neg_r2), None)
+                    x_start = out2
+                images = images_next
+                if has_inpainting and not (resample == 0 or ind == len(sched) - 1):   # renoise in repaint and then resample (:520-523)
+                    renoise, kr = draw(), vec(sigma - sigma_next)
+        return self._finish_chain(images, known, mask_f)
+
+    def _start_chain(self, unet, shape, unet_number, sigma0, noise, init_images, **kwargs):
+        """The prologue of a per-window chain, whatever its sampler: ``(draw, images, fwd, sc)`` -- ``draw()``, the next normal of
+        ``noise`` (a list [init, step_0, ...], a callable ``noise(shape)`` or None for ``torch.randn``); the initial image
+        ``sigma0 * draw()`` plus ``init_images``; ``fwd(images, sigma, **sc(x0))``, ``preconditioned_network_forward`` of ``unet`` under
+        ``kwargs``, with ``sc(x0)`` the self-conditioning keyword (:483, 505, 524: the last x0 estimate) if the U-Net takes one."""
         dev = self.device
-        B = shape[0]
         if callable(noise):
             draw = lambda: noise(shape).to(dev).float().contiguous()
         else:
             noise = list(noise) if exists(noise) else None
             draw = (lambda: noise.pop(0).to(dev).float().contiguous()) if exists(noise) else (lambda: torch.randn(shape, device=dev))
-        vec = lambda v: torch.full((B,), float(v), device=dev)
-        images = ops.axpby3(draw(), None, None, vec(sigmas[0].item()), None, None)
+        images = ops.axpby3(draw(), None, None, torch.full((shape[0],), float(sigma0), device=dev), None, None)
         if exists(init_images):
             images = ops.add(images, init_images.to(dev).float())
-        fwd = partial(self.preconditioned_network_forward, unet.forward_with_cond_scale, sigma_data=hp.sigma_data, clamp=clamp,
-                      dynamic_threshold=dynamic_threshold, cond_scale=cond_scale, **kwargs)
-        self_cond_on = bool(getattr(unet, 'self_cond', False))                   # self-conditioning (:483, 505, 524): the last x0 estimate
-        sc = (lambda x0: dict(self_cond=x0)) if self_cond_on else (lambda x0: {})
-        x_start = None
-        for sigma, sigma_next, gamma in sched:
-            eps = draw()
-            sigma_hat = sigma + gamma * sigma
-            images_hat = ops.axpby3(images, eps, None, vec(1.), vec(hp.S_noise * sqrt(max(sigma_hat ** 2 - sigma ** 2, 0.))), None)
-            out = fwd(images_hat, float(sigma_hat), **sc(x_start))
-            r = (sigma_next - sigma_hat) / sigma_hat
-            # x_next = x_hat + (s_next - s_hat) * (x_hat - D)/s_hat
-            images_next = ops.axpby3(images_hat, out, None, vec(1. + r), vec(-r), None)
-            x_start = out
-            if sigma_next != 0:                                                   # 2nd-order correction (:502-516)
-                out2 = fwd(images_next, float(sigma_next), **sc(out))
-                r2 = 0.5 * (sigma_next - sigma_hat) / sigma_next
-                tmp = ops.axpby3(images_hat, out, images_next, vec(1. + 0.5 * r), vec(-0.5 * r), vec(r2))
-                images_next = ops.axpby3(tmp, out2, None, vec(1.), vec(-r2), None)
-                x_start = out2
-            images = images_next
-        images = ops.axpby3(images, None, None, vec(1.), None, None, -1., 1., 2)    # clamp(-1, 1)   (:527)
+        fwd = partial(self.preconditioned_network_forward, unet.forward_with_cond_scale, sigma_data=self.hparams[unet_number - 1].sigma_data,
+                      **kwargs)
+        sc = (lambda x0: dict(self_cond=x0)) if getattr(unet, 'self_cond', False) else (lambda x0: {})
+        return draw, images, fwd, sc
+
+    def _finish_chain(self, images, known=None, mask=None):
+        """The end of a chain: clamp(-1, 1) (:527), the known values (state space) under the 0/1 fp32 ``mask`` if the chain inpainted
+        (:529-530), ``unnormalize_img``."""
+        images = ops.axpby3(images, None, None, torch.ones(images.shape[0], device=images.device), None, None, -1., 1., 2)
+        if exists(known):
+            images = ops.mask_blend(images, known, mask)
         return self.unnormalize_img(images)
 
     def _dpmpp2m_sample(self, unet, shape, *, unet_number, clamp, dynamic_threshold, cond_scale, init_images, sigma_min, sigma_max, noise,
                         sample_steps, eta, consistency=None, **kwargs):
         """``one_unet_sample(sampler='dpmpp2m')``; the arguments are checked there (``consistency``: None or the checked
         ``(meas_up, cell, weight)``, ``meas_up`` in state space)."""
-        hp = self.hparams[unet_number - 1]
         sigmas, coefs = self._dpmpp2m_tables(unet_number - 1, sample_steps, eta, sigma_min, sigma_max)
         sigmas = sigmas.tolist()
         dev, B = self.device, shape[0]
-        if callable(noise):
-            draw = lambda: noise(shape).to(dev).float().contiguous()
-        else:
-            noise = list(noise) if exists(noise) else None
-            draw = (lambda: noise.pop(0).to(dev).float().contiguous()) if exists(noise) else (lambda: torch.randn(shape, device=dev))
-        images = ops.axpby3(draw(), None, None, torch.full((B,), float(sigmas[0]), device=dev), None, None)
-        if exists(init_images):
-            images = ops.add(images, init_images.to(dev).float())
-        fwd = partial(self.preconditioned_network_forward, unet.forward_with_cond_scale, sigma_data=hp.sigma_data, clamp=clamp,
-                      dynamic_threshold=dynamic_threshold, cond_scale=cond_scale, **kwargs)
-        self_cond_on = bool(getattr(unet, 'self_cond', False))
+        draw, images, fwd, sc = self._start_chain(unet, shape, unet_number, sigmas[0], noise, init_images, clamp=clamp,
+                                                  dynamic_threshold=dynamic_threshold, cond_scale=cond_scale, **kwargs)
         stochastic = (coefs[:, 3] != 0).tolist()
         k = coefs[:, :, None].expand(-1, -1, B).contiguous().to(dev)              # [T,4,B]: one coefficient row per sample
         if exists(consistency):
@@ -520,13 +528,12 @@ class ElucidatedImagen(nn.Module):
             meas_up = meas_up.to(dev).float().contiguous()
         x_start = None
         for i in range(coefs.shape[0]):
-            out = fwd(images, float(sigmas[i]), **(dict(self_cond=x_start) if self_cond_on else {}))
+            out = fwd(images, float(sigmas[i]), **sc(x_start))
             if exists(consistency):                                             # ``out`` arrives clamped or thresholded
                 out = ops.cell_project(out, meas_up, cell, weight)
             images = ops.multistep_sde_step(images, out, x_start, draw() if stochastic[i] else None, k[i, 0], k[i, 1], k[i, 2], k[i, 3])
             x_start = out
-        images = ops.axpby3(images, None, None, torch.ones(B, device=dev), None, None, -1., 1., 2)    # clamp(-1, 1)
-        return self.unnormalize_img(images)
+        return self._finish_chain(images)
 
     def _inpaint_operands(self, inpaint_images, inpaint_masks, shape):
         """:446-449 on the device: the known images through ``normalize_img`` and the nearest resize to the U-Net's size, the masks
@@ -540,62 +547,6 @@ class ElucidatedImagen(nn.Module):
                              f"sampled shape {tuple(shape)} and its [B,D,H,W] mask")
         masks = masks.expand(shape)
         return known.contiguous(), masks.float().contiguous(), masks.to(torch.uint8).contiguous()
-
-    def _heun_inpaint_sample(self, unet, shape, *, unet_number, clamp, dynamic_threshold, cond_scale, inpaint_images, inpaint_masks,
-                             inpaint_resample_times, init_images, skip_steps, sigma_min, sigma_max, noise, **kwargs):
-        """``one_unet_sample`` with inpainting (:441-449, 473-530; RePaint, Lugmayr et al. 2022): every step runs
-        ``inpaint_resample_times`` passes, r = R - 1 .. 0.  A pass draws ``eps``, pastes the known image under the mask and churns,
-        runs the two Heun evaluations as ever, and -- unless r == 0 or it is the last step -- draws once more and re-noises,
-        images += (sigma - sigma_next) n.  The re-noise that ends a pass, the paste and the churn that begins the next are ONE
-        ``ops.edm_inpaint_churn`` launch.  The self-conditioning estimate carries across passes.  At the end: clamp, the known values
-        under the mask, ``unnormalize_img``.  The arguments are checked in ``one_unet_sample``."""
-        hp = self.hparams[unet_number - 1]
-        sigma_min, sigma_max = default(sigma_min, hp.sigma_min), default(sigma_max, hp.sigma_max)
-        sigmas = self.sample_schedule(hp.num_sample_steps, hp.rho, sigma_min, sigma_max)
-        gammas = torch.where((sigmas >= hp.S_tmin) & (sigmas <= hp.S_tmax), min(hp.S_churn / hp.num_sample_steps, sqrt(2) - 1), 0.)
-        sched = list(zip(sigmas[:-1].tolist(), sigmas[1:].tolist(), gammas[:-1].tolist()))[default(skip_steps, 0):]
-        dev = self.device
-        B = shape[0]
-        if callable(noise):
-            draw = lambda: noise(shape).to(dev).float().contiguous()
-        else:
-            noise = list(noise) if exists(noise) else None
-            draw = (lambda: noise.pop(0).to(dev).float().contiguous()) if exists(noise) else (lambda: torch.randn(shape, device=dev))
-        vec = lambda v: torch.full((B,), float(v), device=dev)
-        known, mask_f, mask_b = self._inpaint_operands(inpaint_images, inpaint_masks, shape)
-        images = ops.axpby3(draw(), None, None, vec(sigmas[0].item()), None, None)
-        if exists(init_images):
-            images = ops.add(images, init_images.to(dev).float())
-        fwd = partial(self.preconditioned_network_forward, unet.forward_with_cond_scale, sigma_data=hp.sigma_data, clamp=clamp,
-                      dynamic_threshold=dynamic_threshold, cond_scale=cond_scale, **kwargs)
-        self_cond_on = bool(getattr(unet, 'self_cond', False))
-        sc = (lambda x0: dict(self_cond=x0)) if self_cond_on else (lambda x0: {})
-        x_start = renoise = kr = None
-        for ind, (sigma, sigma_next, gamma) in enumerate(sched):
-            is_last_timestep = ind == len(sched) - 1
-            sigma_hat = sigma + gamma * sigma
-            kc = vec(hp.S_noise * sqrt(max(sigma_hat ** 2 - sigma ** 2, 0.)))
-            r = (sigma_next - sigma_hat) / sigma_hat
-            for resample in reversed(range(inpaint_resample_times)):
-                eps = draw()
-                # the re-noise of the pass before (if it had one), the paste, the churn: one pass over the state, in place
-                images_hat = ops.edm_inpaint_churn(images, renoise, known, mask_b, eps, kr, kc, out=images)
-                renoise = kr = None
-                out = fwd(images_hat, float(sigma_hat), **sc(x_start))
-                images_next = ops.axpby3(images_hat, out, None, vec(1. + r), vec(-r), None)
-                x_start = out
-                if sigma_next != 0:
-                    out2 = fwd(images_next, float(sigma_next), **sc(out))
-                    r2 = 0.5 * (sigma_next - sigma_hat) / sigma_next
-                    tmp = ops.axpby3(images_hat, out, images_next, vec(1. + 0.5 * r), vec(-0.5 * r), vec(r2))
-                    images_next = ops.axpby3(tmp, out2, None, vec(1.), vec(-r2), None)
-                    x_start = out2
-                images = images_next
-                if not (resample == 0 or is_last_timestep):                       # renoise in repaint and then resample (:520-523)
-                    renoise, kr = draw(), vec(sigma - sigma_next)
-        images = ops.axpby3(images, None, None, vec(1.), None, None, -1., 1., 2)    # clamp(-1, 1)   (:527)
-        images = ops.mask_blend(images, known, mask_f)                              # (:529-530)
-        return self.unnormalize_img(images)
 
     def window_denoiser(self, unet_number=2, cond_scale=1., clamp=True, sigma_min=None, sigma_max=None, inpaint_images=None,
                         inpaint_masks=None, init_images=None, skip_steps=None, _unet_context=nullcontext, sampler='heun',
@@ -632,6 +583,14 @@ class ElucidatedImagen(nn.Module):
         alpha, sigma = log_snr_to_alpha_sigma(log_snr)
         dev = lowres.device
         return ops.q_sample(lowres.contiguous(), noise.contiguous(), alpha.to(dev), sigma.to(dev))
+
+    def _lowres_conditioning(self, lowres, noise_level, size, frames, batch, device, draw):
+        """What a low-res conditioned U-Net is handed at sampling (:652-657, 680): ``(lowres_cond_img, lowres_noise_times)`` -- ``lowres``
+        resized to ``size`` / ``frames``, through ``normalize_img`` and noised at ``noise_level`` with ``draw(image)``, the augmentation
+        normals for the prepared image; and the RAW time, [batch] on ``device``."""
+        t_cpu = torch.full((batch,), float(noise_level))
+        lowres = self.normalize_img(self._resize(lowres.to(device), size, frames)).float().to(device)
+        return self._noise_lowres(lowres, t_cpu, draw(lowres).to(device).float()), t_cpu.to(device)
 
     @torch.no_grad()
     @eval_decorator
@@ -713,29 +672,27 @@ class ElucidatedImagen(nn.Module):
             assert not isinstance(unet, NullUnet), 'cannot sample from null unet'
             lowres_cond_img = lowres_noise_times = None
             if unet.lowres_cond:
-                t_cpu = torch.full((batch_size,), float(lowres_sample_noise_level))
-                lowres_noise_times = t_cpu.to(device)                              # the RAW time at sampling (:652, 680)
-                lowres_cond_img = self.normalize_img(self._resize(img, image_size, frame_dims[0])).float().to(device)
-                if exists(noise_fn):
-                    ln = noise_fn(tuple(lowres_cond_img.shape)).to(device).float()
-                else:
-                    ln = noise.pop(0).to(device).float() if exists(noise) else torch.randn_like(lowres_cond_img)
-                lowres_cond_img = self._noise_lowres(lowres_cond_img, t_cpu, ln)
+                lowres_cond_img, lowres_noise_times = self._lowres_conditioning(
+                    img, lowres_sample_noise_level, image_size, frame_dims[0], batch_size, device,
+                    lambda x: noise_fn(tuple(x.shape)) if exists(noise_fn) else (noise.pop(0) if exists(noise) else torch.randn_like(x)))
             if exists(unet_init):
                 unet_init = self._resize(unet_init, image_size, frame_dims[0])
             shape = (batch_size, self.channels, *frame_dims, image_size, image_size)
-            n_draws = len(list(zip(range(self.hparams[unet_number - 1].num_sample_steps)))) - default(unet_skip, 0) + 1
-            multistep = {}
-            if unet_sampler == 'dpmpp2m':                                          # the initial image, then one draw per row with kn != 0
-                multistep = dict(sampler=unet_sampler, sample_steps=unet_steps, eta=unet_eta)
-                n_draws = 1 + int((self._dpmpp2m_tables(unet_number - 1, unet_steps, unet_eta, smin, smax)[1][:, 3] != 0).sum())
+            multistep = dict(sampler=unet_sampler, sample_steps=unet_steps, eta=unet_eta) if unet_sampler == 'dpmpp2m' else {}
             if exists(consistency):
                 multistep.update(consistency=consistency, consistency_weight=consistency_weight)
             inpaint = {}
-            if has_inpainting:                                                     # the initial image, then the draws of the loop
+            if has_inpainting:
                 inpaint = dict(inpaint_images=inpaint_images, inpaint_masks=inpaint_masks, inpaint_resample_times=inpaint_resample_times)
-                n_draws = 1 + self.inpaint_draws(n_draws - 1, inpaint_resample_times)
-            unet_noise = noise_fn if exists(noise_fn) else ([noise.pop(0) for _ in range(n_draws)] if exists(noise) else None)
+            unet_noise = noise_fn
+            if exists(noise):    # this U-Net's share of the list, counted on its host table: the initial image, then one draw per Heun
+                if unet_sampler == 'dpmpp2m':                                      # step or per row with kn != 0
+                    n_draws = int((self._dpmpp2m_tables(unet_number - 1, unet_steps, unet_eta, smin, smax)[1][:, 3] != 0).sum())
+                else:
+                    n_draws = len(self._heun_tables(unet_number - 1, smin, smax, unet_skip)[0])
+                if has_inpainting:
+                    n_draws = self.inpaint_draws(n_draws, inpaint_resample_times)
+                unet_noise = [noise.pop(0) for _ in range(1 + n_draws)]
             img = self.one_unet_sample(unet, shape, unet_number=unet_number, init_images=unet_init, skip_steps=unet_skip,
                                        sigma_min=smin, sigma_max=smax, cond_scale=unet_cond_scale, dynamic_threshold=dynamic_threshold,
                                        use_tqdm=use_tqdm, noise=unet_noise, **multistep, **inpaint,

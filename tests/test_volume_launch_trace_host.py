@@ -20,67 +20,18 @@ inference.py, on the same terms.  A digest that differs means launches, argument
 diff them against a dump of the older tree -- the recorder only patches module attributes, so this file runs on either."""
 import collections
 import hashlib
-import inspect
 import json
 import os
-import tempfile
 
-import numpy as np
 import pytest
 import torch
 
 from tests import volume_blend_reference as R
+from tests import launch_trace
+from tests.launch_trace import Recorder, canonical, dump, zeros
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'volume_launch_trace.json')
 SEED = 5
-
-
-def f32(v):
-    v = float(np.float32(v))
-    return v if np.isfinite(v) else str(v)
-
-
-class Recorder:
-    def __init__(self):
-        self.trace, self._tags, self._seen, self._alive = [], {}, collections.Counter(), []
-
-    def tag(self, t, role):
-        """The tag of the storage ``t`` lives in, made from ``role`` at first sight.  Every tagged tensor is kept alive, so no later
-        allocation can take its address."""
-        key = t.untyped_storage().data_ptr()
-        if key not in self._tags:
-            self._tags[key] = f"{role}#{self._seen[role]}"
-            self._seen[role] += 1
-            self._alive.append(t)
-        return self._tags[key]
-
-    def describe(self, v, role):
-        if v is None or isinstance(v, (bool, str)):
-            return v
-        if isinstance(v, (int, np.integer)):
-            return int(v)
-        if isinstance(v, (float, np.floating)):
-            return f32(v)
-        if isinstance(v, np.ndarray):
-            return {'host': v.tolist()}
-        if torch.is_tensor(v):
-            if role.endswith(('.slot', '.taps')):
-                return {'shape': list(v.shape), 'dtype': str(v.dtype), 'sha': hashlib.sha256(v.contiguous().numpy().tobytes()).hexdigest()[:16]}
-            if not v.is_floating_point():
-                return {'index': v.tolist()}
-            return {'t': self.tag(v, role), 'shape': list(v.shape), 'dtype': str(v.dtype), 'off': v.storage_offset()}
-        if isinstance(v, (tuple, list)):
-            return [self.describe(e, role) for e in v]
-        if callable(v):
-            return 'callable'
-        return str(v)
-
-    def record(self, op, args, result=None):
-        """Append the call; tag what it returned (``result`` tensors the call did not receive are fresh ones) and hand it back."""
-        rec = {'op': op, **{k: self.describe(v, f"{op}.{k}") for k, v in args.items()}}
-        rec['->'] = self.describe(result, op)
-        self.trace.append(rec)
-        return result
 
 
 def gather_cpu(vol, idx, P, mean, std, want_patches, want_nonzero):
@@ -88,10 +39,6 @@ def gather_cpu(vol, idx, P, mean, std, want_patches, want_nonzero):
     out = ((w - mean) / std)[:, None].contiguous() if want_patches else None
     nz = (w != 0).sum(dim=(1, 2, 3)).to(torch.int32) if want_nonzero else None
     return out, nz
-
-
-def zeros(*shape):
-    return torch.zeros(tuple(int(s) for s in shape), dtype=torch.float32)
 
 
 # what each stand-in returns, from the arguments bound to the real op's signature
@@ -116,23 +63,11 @@ RETURNS = {
 }
 
 
-class RecordingOps:
+class RecordingOps(launch_trace.RecordingOps):
     """Stands in for ``diffusioniqt_amd.ops`` inside ``inference``: an op that is not in ``RETURNS`` is an AttributeError."""
 
     def __init__(self, rec):
-        from diffusioniqt_amd import ops
-        self._rec, self._real = rec, ops
-
-    def __getattr__(self, name):
-        if name not in RETURNS:
-            raise AttributeError(f"the launch trace has no stand-in for ops.{name}")
-        sig = inspect.signature(getattr(self._real, name))
-
-        def op(*args, **kw):
-            bound = sig.bind(*args, **kw)
-            bound.apply_defaults()
-            return self._rec.record(name, bound.arguments, RETURNS[name](bound.arguments))
-        return op
+        super().__init__(rec, RETURNS)
 
 
 def sampler_of(rec):
@@ -233,23 +168,10 @@ def run_case(name):
     return rec.trace
 
 
-def canonical(trace):
-    return json.dumps(trace, sort_keys=True, separators=(',', ':'))
-
-
 def summary(trace):
     counts = collections.Counter(r['op'] for r in trace)
     rest = [r for r in trace if r['op'] != 'min_value']
     return {'counts': dict(sorted(counts.items())), 'sha256': hashlib.sha256(canonical(rest).encode()).hexdigest()}
-
-
-def dump(name, trace, where=None):
-    where = where or tempfile.mkdtemp(prefix='volume_launch_trace_')
-    os.makedirs(where, exist_ok=True)
-    path = os.path.join(where, name + '.json')
-    with open(path, 'w') as f:
-        f.write('[\n' + ',\n'.join(canonical([r])[1:-1] for r in trace) + '\n]\n')       # one record per line: diff-able
-    return path
 
 
 @pytest.mark.parametrize('name', list(CASES))
@@ -261,7 +183,7 @@ def test_launch_trace_is_the_recorded_one(name):
     got = summary(trace)
     where = os.environ.get('DIQT_LAUNCH_TRACE_DUMP')
     if where or got != golden[name]:
-        print(f"{name}: full trace written to {dump(name, trace, where)}")
+        print(f"{name}: full trace written to {dump(name, trace, where, 'volume_launch_trace_')}")
     print(f"{name}: {len(trace)} records, {got['counts']}")
     mins = [r for r in trace if r['op'] == 'min_value']
     assert len(mins) == 1 and mins[0]['x']['t'] == 'vol#0' and mins[0]['x']['off'] == 0     # once per call, on the raw volume
