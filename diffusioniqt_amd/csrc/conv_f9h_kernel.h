@@ -50,6 +50,13 @@ constexpr unsigned OOB = 0x80000000u;
 constexpr int CK = 32, ROWB = 64;        // channels per chunk, bytes per halo row / weight row
 constexpr int PD = 9;                    // slots of the weight-fragment ring (prefetch distance PD - 1 taps)
 constexpr int SCRW = 32 * 144;           // epilogue transpose scratch per wave: 32 voxel rows x (128 B of fp32 channels + 16 B pad)
+constexpr int BIASB = 256;               // SPLIT: the workgroup's 64 bias values, staged behind the images (the launcher adds it to the LDS size)
+
+// Time stamps of a diagnostic build (tools/probes/split_account_probe.hip defines the macro before it includes this header); in the
+// library no stamp exists.
+#ifndef DIQT_F9H_STAMP
+#define DIQT_F9H_STAMP(it, c, point)
+#endif
 
 template <int KD_, int KH_, int KW_, int TD_, int TH_, int TW_, int NIMG_, int OCC_ = 1>
 struct Cfg {
@@ -98,8 +105,17 @@ template <bool BF> __device__ __forceinline__ float round_through(float a) { ret
 // SPLIT (fp16 operands, fp32 y): an fp32 conv carried on the 16-bit pipe by the three-product split.  A 32-channel chunk of x and of wp
 // holds 16 fp32 channels as [16 heads xh = fp16(x) | 16 tails xl = fp16((x - xh) 2^11)] (conv_split16.hip writes both), so the k-half q = 0
 // of a tap is heads x heads and the body issues per tap  acc += wh xh (odd taps: acc2),  acc1 += wl xh,  acc1 += wh xl  (the tail x tail
-// term is dropped); the epilogue forms (acc + acc2) + 2^-11 acc1 and does NOT round to the operand type.  Everything else is the 16-bit kernel.
-template <class C, bool BF, bool YH, bool SPLIT = false>
+// term is dropped); the epilogue forms (acc + acc2) + 2^-11 acc1 and does NOT round to the operand type.  Everything else is the 16-bit kernel,
+// but for the tile boundary (round 9), which the split build runs with one wave per SIMD and nothing to hide it behind:
+//   * RS >= 0 makes `residual != nullptr` (bit 0) and `g.stats != nullptr` (bit 1) compile-time facts (launch_split_cfg dispatches the
+//     four instantiations); RS < 0: both are tested at run time, per store (the 16-bit builds);
+//   * the bias of the workgroup's channel block is staged in LDS by the prologue (the persistent walk keeps its channel block): no
+//     global load and no vmcnt(0) opens an epilogue;
+//   * a tile's accumulators start from a zero C operand in the first products of its first chunk (which is peeled for that) instead of
+//     being zeroed register by register: 0 + product, as before;
+//   * the stores of a block take ONE per-lane offset per store instruction that does not depend on the tile (the tile and the block
+//     go into the scalar offset), and a block's residual loads are issued together, a block ahead of their use.
+template <class C, bool BF, bool YH, bool SPLIT = false, int RS = -1>
 __global__ __launch_bounds__(256, C::OCC) void conv_f9h_kernel(const void* __restrict__ xv, const unsigned short* __restrict__ wp,
                                                           const float* __restrict__ bias, const float* __restrict__ residual,
                                                           void* __restrict__ yv, H9Geom g) {
@@ -122,7 +138,8 @@ __global__ __launch_bounds__(256, C::OCC) void conv_f9h_kernel(const void* __res
     const unsigned total = (unsigned)g.MT * g.nNt;
     unsigned L = xcd_remap(blockIdx.x, Gn);
     if (L >= total) return;
-    const unsigned L0 = L;                               // first tile of this workgroup (L walks on with the tiles being computed)
+    DIQT_F9H_STAMP(0, 0, 7);
+    const unsigned L0 = L;                              // first tile of this workgroup (L walks on with the tiles being computed)
     const int nMine = (int)((total - 1 - L) / Gn) + 1;
     const int n0 = (int)(L % g.nNt) * 64;
     const int nChunks = g.nChunks;
@@ -208,14 +225,12 @@ __global__ __launch_bounds__(256, C::OCC) void conv_f9h_kernel(const void* __res
     f32x16 acc1[SPLIT ? NVB : 1];                             // SPLIT: the head x tail products, scaled by 2^11
     f32x16 acc2[SPLIT ? NVB : 1];                             // SPLIT: the head x head products of the odd taps -- the fp32 chains of the
                                                               // dominant term are half as long (their rounding is what is left of the error)
+    if constexpr (!SPLIT) {                                   // (SPLIT: every set starts from a zero C operand in the tile's first chunk)
 #pragma unroll
-    for (int vb = 0; vb < NVB; ++vb)
+        for (int vb = 0; vb < NVB; ++vb)
 #pragma unroll
-        for (int i = 0; i < 16; ++i) acc[vb][i] = 0.f;
-#pragma unroll
-    for (int vb = 0; vb < (SPLIT ? NVB : 1); ++vb)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) { acc1[vb][i] = 0.f; acc2[vb][i] = 0.f; }
+            for (int i = 0; i < 16; ++i) acc[vb][i] = 0.f;
+    }
 
     // ---- prologue: the first NIMG - 1 units' halo images, the first PD - 1 weight panels ----
     int fit = 0, fc = 0;                                   // (tile iteration, chunk) of the unit being fetched
@@ -231,13 +246,24 @@ __global__ __launch_bounds__(256, C::OCC) void conv_f9h_kernel(const void* __res
     }
 #pragma unroll
     for (int s = 0; s < PD - 1; ++s) w_load(s);
+    if constexpr (SPLIT) {                                 // bias[n0 .. n0 + 63] (zeros past Cout or without a bias) behind the images
+        if (tid < 64)
+            reinterpret_cast<float*>(smem + C::LDS_BYTES)[tid] =
+                __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_b, (unsigned)(n0 + tid) * 4u, 0, 0));
+    }
     __builtin_amdgcn_s_waitcnt(0x0f70);                    // vmcnt(0)
     __syncthreads();
 
     int img = 0, fimg = NIMG - 1;
+    const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     tile_of(L, tb, d0, h0, w0);
     for (int it = 0; it < nMine; ++it) {
-        for (int c = 0; c < nChunks; ++c) {
+        // a unit = one chunk of a tile.  SPLIT: the tile's first chunk is peeled (the two statically unrolled passes: chunk 0, then the
+        // rest) -- FIRST: the first product of every accumulator set takes a zero C operand
+#pragma unroll
+        for (int pass = 0; pass < (SPLIT ? 2 : 1); ++pass)
+        for (int c = SPLIT ? pass : 0; c < (SPLIT && pass == 0 ? 1 : nChunks); ++c) {
+            const bool FIRST = SPLIT && pass == 0;
             const unsigned fbase = ldsBase + (unsigned)fimg * HB;
             u32x4 X0[NVB], X1[NVB];
             auto rd = [&](u32x4 (&X)[NVB], int t, int q) __attribute__((always_inline)) {       // t, q static
@@ -250,14 +276,23 @@ __global__ __launch_bounds__(256, C::OCC) void conv_f9h_kernel(const void* __res
             auto mm = [&](u32x4 (&X)[NVB], int t, int q) __attribute__((always_inline)) {
 #pragma unroll
                 for (int vb = 0; vb < NVB; ++vb) {
-                    if (SPLIT && (t & 1)) acc2[vb] = mfma16<BF>(Wr[t % PD][q], X[vb], acc2[vb]);
-                    else acc[vb] = mfma16<BF>(Wr[t % PD][q], X[vb], acc[vb]);
+                    if (SPLIT && (t & 1)) {
+                        if (FIRST && t == 1) acc2[vb] = mfma16<BF>(Wr[t % PD][q], X[vb], zero16);
+                        else acc2[vb] = mfma16<BF>(Wr[t % PD][q], X[vb], acc2[vb]);
+                    } else {
+                        if (FIRST && t == 0) acc[vb] = mfma16<BF>(Wr[t % PD][q], X[vb], zero16);
+                        else acc[vb] = mfma16<BF>(Wr[t % PD][q], X[vb], acc[vb]);
+                    }
                 }
             };
-            auto mm1 = [&](u32x4 (&X)[NVB], int t, int q) __attribute__((always_inline)) {      // SPLIT: the cross products
+            auto mm1 = [&](u32x4 (&X)[NVB], int t, int q, bool z) __attribute__((always_inline)) {      // SPLIT: the cross products (z: from zero)
 #pragma unroll
-                for (int vb = 0; vb < (SPLIT ? NVB : 1); ++vb) acc1[vb] = mfma16<BF>(Wr[t % PD][q], X[vb], acc1[vb]);
+                for (int vb = 0; vb < (SPLIT ? NVB : 1); ++vb) {
+                    if (z) acc1[vb] = mfma16<BF>(Wr[t % PD][q], X[vb], zero16);
+                    else acc1[vb] = mfma16<BF>(Wr[t % PD][q], X[vb], acc1[vb]);
+                }
             };
+            DIQT_F9H_STAMP(it, c, 0);
             rd(X0, 0, 0);                                  // cold read of the chunk's first half-tap (the image was published by the barrier)
 #pragma unroll
             for (int t = 0; t < T; ++t) {
@@ -269,7 +304,7 @@ __global__ __launch_bounds__(256, C::OCC) void conv_f9h_kernel(const void* __res
                 __builtin_amdgcn_sched_barrier(0);
                 rd(X1, t, 1);
                 mm(X0, t, 0);
-                if constexpr (SPLIT) mm1(X0, t, 1);        // tails of w x heads of x
+                if constexpr (SPLIT) mm1(X0, t, 1, FIRST && t == 0);        // tails of w x heads of x
                 // (in program order BEHIND the first half's fragment reads and in front of the second half's: to the compiler a halo DMA is
                 // a store into the LDS that no fragment read may cross)
 #pragma unroll
@@ -277,7 +312,7 @@ __global__ __launch_bounds__(256, C::OCC) void conv_f9h_kernel(const void* __res
                     if (r * NSP / NPH == t) dma_h(r, fbase, fc);
                 w_load((t + PD - 1) % PD);
                 if (t + 1 < T) rd(X0, t + 1, 0);
-                if constexpr (SPLIT) mm1(X1, t, 0);        // heads of w x tails of x: two fragment reads per three MFMAs
+                if constexpr (SPLIT) mm1(X1, t, 0, false); // heads of w x tails of x: two fragment reads per three MFMAs
                 else mm(X1, t, 1);
 #pragma unroll
                 for (int u = 0; u < (SPLIT ? 3 : 2) * NVB; ++u) {
@@ -285,11 +320,14 @@ __global__ __launch_bounds__(256, C::OCC) void conv_f9h_kernel(const void* __res
                     if (u >= NVB && u < NVB + 4) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
                     if (u < 2 * NVB) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
                 }
+                if (t == PD - 1) { DIQT_F9H_STAMP(it, c, 1); }
             }
             (void)nh_in_tap;
+            DIQT_F9H_STAMP(it, c, 2);
             // End of the unit.  The image of the next unit is complete: its pieces were issued before the weight load whose fragment the
             // last tap has just consumed (loads retire in order).  This wave's reads of image `img` have been consumed by issued MFMAs.
             asm volatile("s_barrier" ::: "memory");
+            DIQT_F9H_STAMP(it, c, 3);
             advance_fetch();
             {
                 const int nimg = img + 1 == NIMG ? 0 : img + 1;
@@ -308,7 +346,115 @@ __global__ __launch_bounds__(256, C::OCC) void conv_f9h_kernel(const void* __res
         //      16-byte pieces of 32 different rows per instruction the stores were bound by the L2's request rate (one per clock and channel:
         //      64 KB per tile and CU took 7k cycles, every CU in its epilogue at the same time).  Residual and statistics ride on the
         //      transposed layout: coalesced residual loads, 2 x PW partial sums per lane, shuffles over the lanes that share a piece ----
-        {
+        if constexpr (SPLIT) {
+            // The split build's form of it (fp32 y: four store instructions per block, 8 lanes per voxel, pieces of 4 channels), the same
+            // values in the same order.  A store's offset is  [tile + block: scalar] + [row rj, column ri of the block, piece: per lane,
+            // tile-independent], the per-lane part replaced by OOB where the voxel or the piece is outside; a block's offsets are made,
+            // and its residual loads issued, while the block before it is stored (the loads wait behind a counted vmcnt, not behind 0).
+            constexpr int SROW = 144;
+            const bool hasRes = RS < 0 ? residual != nullptr : (RS & 1) != 0;
+            const bool wantStats = RS < 0 ? g.stats != nullptr : (RS & 2) != 0;
+            char* const scrb = smem + fimg * HB + wave * SCRW;
+            const int piece = lane & 7, vl = lane >> 3;
+            const int cop = n0 + 32 * wb + piece * 4;
+            const bool cok = cop < g.Cout;
+            const unsigned C4 = (unsigned)g.Cout * 4u;
+            int rjk[4], rik[4];
+            unsigned lo[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int vloc = 8 * k + vl, tqr = vloc >> 2;
+                rjk[k] = 2 * (tqr >> 2) + ((tqr ^ (tqr >> 1) ^ (tqr >> 2)) & 1);
+                rik[k] = 4 * (k & 1) + (vl & 3);                             // (= 4 ((tqr >> 1) & 1) + (vloc & 3): vl >> 2 is 0 or 1)
+                lo[k] = cok ? (unsigned)(rjk[k] * g.Wo + rik[k]) * C4 + (unsigned)cop * 4u : OOB;
+            }
+            const unsigned tileOff = (unsigned)(((tb * g.Do + d0) * g.Ho + h0) * g.Wo + w0) * C4;
+            auto offs = [&](int vb, unsigned (&vo)[4], unsigned& so) __attribute__((always_inline)) {
+                const int id = wa * NVB + vb;
+                const int bd = id / (C::NBH * C::NBW), bh = ((id / C::NBW) % C::NBH) * 4, bw = (id % C::NBW) * 8;
+                so = tileOff + (unsigned)((bd * g.Ho + bh) * g.Wo + bw) * C4;
+                const int hlim = d0 + bd < g.Do ? g.Ho - h0 - bh : 0, wlim = g.Wo - w0 - bw;      // (a plane past Do: no row is inside)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) vo[k] = ((int)(rjk[k] < hlim) & (int)(rik[k] < wlim)) ? lo[k] : OOB;
+            };
+            float ssum[4], ssq[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { ssum[e] = 0.f; ssq[e] = 0.f; }
+            f32x4v b4[4];
+#pragma unroll
+            for (int g4 = 0; g4 < 4; ++g4)
+                b4[g4] = *reinterpret_cast<const f32x4v*>(smem + C::LDS_BYTES + (32 * wb + 4 * hf + 8 * g4) * 4);
+            unsigned vo[2][4], so[2];
+            f32x4v rr[2][4];
+            offs(0, vo[0], so[0]);
+            if (hasRes) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) rr[0][k] = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(rs_r, vo[0][k], so[0], 0));
+            }
+            DIQT_F9H_STAMP(it, 0, 4);
+#pragma unroll
+            for (int vb = 0; vb < NVB; ++vb) {
+                const int cur = vb & 1, nxt = cur ^ 1;
+#pragma unroll
+                for (int g4 = 0; g4 < 4; ++g4) {
+                    f32x4v p;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        p[e] = fmaf(acc1[vb][4 * g4 + e], 0x1p-11f, acc[vb][4 * g4 + e] + acc2[vb][4 * g4 + e]) + b4[g4][e];
+                    *reinterpret_cast<f32x4v*>(scrb + l31 * SROW + 32 * g4 + 16 * hf) = p;
+                }
+                if (vb + 1 < NVB) {
+                    offs(vb + 1, vo[nxt], so[nxt]);
+                    if (hasRes) {
+#pragma unroll
+                        for (int k = 0; k < 4; ++k)
+                            rr[nxt][k] = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(rs_r, vo[nxt][k], so[nxt], 0));
+                    }
+                }
+                u32x4 d[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) d[k] = *reinterpret_cast<const u32x4*>(scrb + (8 * k + vl) * SROW + piece * 16);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    if (hasRes) {
+                        f32x4v f = __builtin_bit_cast(f32x4v, d[k]);
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) f[e] += rr[cur][k][e];
+                        d[k] = __builtin_bit_cast(u32x4, f);
+                    }
+                    if (wantStats) {
+                        // (a lane whose piece is past Cout never writes its sums: `stored` may stand in for `voxel inside`)
+                        const float okf = vo[cur][k] != OOB ? 1.f : 0.f;
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            const unsigned wd = d[k][e];
+                            const float v = __builtin_bit_cast(float, wd);
+                            const float mv = okf * v;
+                            ssum[e] += mv;
+                            ssq[e] = fmaf(mv, v, ssq[e]);
+                        }
+                    }
+                    __builtin_amdgcn_raw_buffer_store_b128(d[k], rs_y, vo[cur][k], so[cur], 0);
+                }
+            }
+            DIQT_F9H_STAMP(it, 0, 5);
+            if (wantStats) {
+                const int tpb = g.tilesD * g.tilesH * g.tilesW, mtile = (int)(L / g.nNt);
+                float* srow = g.stats + ((size_t)(mtile / tpb) * (2 * tpb) + (size_t)(mtile % tpb) * 2 + wa) * 2 * g.Cout;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+#pragma unroll
+                    for (int o = 8; o < 64; o <<= 1) {
+                        ssum[e] += __shfl_xor(ssum[e], o, 64);
+                        ssq[e] += __shfl_xor(ssq[e], o, 64);
+                    }
+                }
+                if (lane < 8 && cok) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) { srow[cop + e] = ssum[e]; srow[g.Cout + cop + e] = ssq[e]; }
+                }
+            }
+        } else {
             constexpr int NK = YH ? 2 : 4, PW = YH ? 8 : 4, LPV = YH ? 4 : 8;       // store instructions per block, channels per piece, lanes per voxel
             constexpr int SROW = YH ? 80 : 144;                                      // scratch row bytes (64 / 128 + pad)
             // scratch: the image the last unit was computed from (`fimg` after the rotation) -- free until the next unit's taps issue the
@@ -420,11 +566,13 @@ __global__ __launch_bounds__(256, C::OCC) void conv_f9h_kernel(const void* __res
             }
         }
         asm volatile("s_barrier" ::: "memory");              // every wave's scratch reads are done (their stores have been issued)
+        DIQT_F9H_STAMP(it, 0, 6);
         L += Gn;
         if (it + 1 < nMine) tile_of(L, tb, d0, h0, w0);
     }
     // the (dead) halo pieces issued during the last units write zeros into this workgroup's LDS: they have to land before it is released
     __builtin_amdgcn_s_waitcnt(0x0f70);                    // vmcnt(0)
+    DIQT_F9H_STAMP(0, 0, 8);
 }
 
 // the variants (filter, tile, images); H9Geom::variant indexes this list
@@ -449,7 +597,13 @@ template <class C> static int launch_cfg(const void* x, const unsigned short* wp
 
 template <class C> static int launch_split_cfg(const void* x, const unsigned short* wp, const float* bias, const float* residual, void* y,
                                                const H9Geom& g, size_t lds, unsigned grid, void* stream) {
-    const auto kern = conv_f9h_kernel<C, false, false, true>;
+    // residual and statistics are template facts of the split build (RS); the staged bias sits behind the plan's images
+    static_assert(C::LDS_BYTES + BIASB <= 160 * 1024, "LDS budget with the staged bias");
+    typedef void (*KP)(const void*, const unsigned short*, const float*, const float*, void*, H9Geom);
+    static const KP kerns[4] = {conv_f9h_kernel<C, false, false, true, 0>, conv_f9h_kernel<C, false, false, true, 1>,
+                                conv_f9h_kernel<C, false, false, true, 2>, conv_f9h_kernel<C, false, false, true, 3>};
+    const KP kern = kerns[(residual ? 1 : 0) | (g.stats ? 2 : 0)];
+    lds += BIASB;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     DIQT_REQUIRE(e == hipSuccess, DIQT_E_LAUNCH, "conv3d_fwd_split16(v9h): hipFuncSetAttribute: %s", hipGetErrorString(e));
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, (hipStream_t)stream, x, wp, bias, residual, y, g);

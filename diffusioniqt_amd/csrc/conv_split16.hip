@@ -9,8 +9,8 @@
 //     [16 heads | 16 scaled tails] = 64 B: a halo row of conv_f9h_kernel's LDS image.  Heads are clamped to +-65504 and the tail is
 //     taken from the clamped head (and clamped too): a value beyond the fp16 range loses accuracy, no inf or NaN is made;
 //   * the split build of conv_f9h_kernel (256-voxel tiles, one workgroup per CU: three accumulator sets of NVB = 4 tiles -- head x
-//     head of the even and of the odd taps, the cross terms -- and a 3-slot weight ring, 488 registers without scratch; at NVB = 8 the
-//     allocator spills) and the entry points.
+//     head of the even and of the odd taps, the cross terms -- and a 3-slot weight ring, 498-512 registers without scratch in its four
+//     residual x statistics instantiations; at NVB = 8 the allocator spills) and the entry points.
 #include "conv_f9h_kernel.h"
 
 namespace diqt {
