@@ -640,6 +640,28 @@ __device__ __forceinline__ float cell_shift(float w, float meas, float m, float 
     const float r = meas - m;
     return fmaf(w, r, a);
 }
+// The same projection for a measurement with a slice profile (ops.cell_profile): y = sum u[q] x[q] over the cell, u >= 0 and sum u = 1,
+// q the voxel's lexicographic (z, y, x) index inside its cell; the cells stay disjoint, so A A^T = |u|^2 I and A+ = A^T / |u|^2.  The
+// table is [2][n]: u, then the gain g[q] = u[q] / sum u^2.  ONE definition again, fp32 and kept from contraction:
+//   cell_wmean   s = 0; s = fmaf(u[q], a[q], s) over the cell's voxels in lexicographic order; m = s.  No division;
+//   cell_wshift  t = w g[q], one rounded product; a'[v] = fmaf(t, meas_up[v] - m, a[v]).  A gap voxel (g = 0) keeps a[v]: the product
+//                is a zero and a[v] + (+-0) is a[v] (only a[v] = -0 under a +0 product comes out as +0, as fmaf has it).
+template <class Value>
+__device__ __forceinline__ float cell_wmean(Cell c, const float* u, Value a) {
+#pragma clang fp contract(off)
+    float s = 0.f;
+    int q = 0;
+    for (int i = 0; i < c.fz; ++i)
+        for (int j = 0; j < c.fy; ++j)
+            for (int k = 0; k < c.fx; ++k, ++q) s = fmaf(u[q], a(i, j, k), s);
+    return s;
+}
+__device__ __forceinline__ float cell_wshift(float w, float g, float meas, float m, float a) {
+#pragma clang fp contract(off)
+    const float t = w * g;
+    const float r = meas - m;
+    return fmaf(t, r, a);
+}
 // diqt_ddpm_step's clamp with a third mode: 2 = none (the value's own bits).
 struct ProjectClamp {
     float lo, hi;
@@ -677,6 +699,40 @@ __global__ __launch_bounds__(256) void cell_project_kernel(const float* x0, cons
                 out[v] = cell_shift(w, meas_up[v], m, clamp(x0[v]));
             }
 }
+// cell_mean_kernel with the slice profile: out = cell_wmean of x under table[0 .. n) (diqt_cell_wmean).  Every lane reads the same
+// table entry at the same time.
+__global__ __launch_bounds__(256) void cell_wmean_kernel(const float* __restrict__ x, const float* __restrict__ table,
+                                                         float* __restrict__ out, size_t cells, int H, int W, Cell c) {
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= cells) return;
+    const int cw = W / c.fx, ch = H / c.fy;
+    const int cx = (int)(e % cw), cy = (int)((e / cw) % ch);
+    const size_t cz = e / ((size_t)cw * ch);
+    const float* base = x + ((cz * c.fz) * H + (size_t)cy * c.fy) * W + (size_t)cx * c.fx;
+    out[e] = cell_wmean(c, table, [&](int i, int j, int k) { return base[((size_t)i * H + j) * W + k]; });
+}
+// cell_project_kernel with the slice profile (diqt_cell_project_profile): table [2][n] = u, then g.  The same thread-per-cell walk,
+// so out may alias x0 here too.
+__global__ __launch_bounds__(256) void cell_project_profile_kernel(const float* x0, const float* __restrict__ meas_up,
+                                                                   const float* __restrict__ table, float* out, size_t cells, int P,
+                                                                   Cell c, float w, ProjectClamp clamp) {
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= cells) return;
+    const int cw = P / c.fx, ch = P / c.fy, cd = P / c.fz;
+    const int cx = (int)(e % cw), cy = (int)((e / cw) % ch), cz = (int)((e / ((size_t)cw * ch)) % cd);
+    const size_t cube = e / ((size_t)cw * ch * cd);
+    const size_t base = ((cube * P + (size_t)cz * c.fz) * P + (size_t)cy * c.fy) * P + (size_t)cx * c.fx;
+    auto at = [&](int i, int j, int k) { return base + ((size_t)i * P + j) * P + k; };
+    const float m = cell_wmean(c, table, [&](int i, int j, int k) { return clamp(x0[at(i, j, k)]); });
+    const float* g = table + c.fz * c.fy * c.fx;
+    int q = 0;
+    for (int i = 0; i < c.fz; ++i)
+        for (int j = 0; j < c.fy; ++j)
+            for (int k = 0; k < c.fx; ++k, ++q) {
+                const size_t v = at(i, j, k);
+                out[v] = cell_wshift(w, g[q], meas_up[v], m, clamp(x0[v]));
+            }
+}
 // volume_joint_linear_kernel with the projection between the fuse and the update (diqt_volume_joint_consistent_step): per voxel the
 // fuse x0 = num / den exactly as there; a cell whose voxels are ALL covered takes x0' = cell_shift(w, meas_up, cell_mean(x0), x0) and
 // each of its voxels the update with x0' in the place of x0; a cell with an uncovered voxel is left alone -- its covered voxels take
@@ -690,25 +746,34 @@ __global__ __launch_bounds__(256) void cell_project_kernel(const float* x0, cons
 // A thread reads and writes only its own voxels of x_t / x0_prev / x_next / x0_out, each read before it is written, so x_next may alias
 // x_t and x0_out may alias x0_prev; whole cells lie in one block, so there is no atomic and no waiting across blocks.  D, H and W are
 // multiples of the cell, so a cell is inside the volume or outside it as a whole.
+// PROFILE (diqt_volume_joint_consistent_profile_step): cell_wmean / cell_wshift in the place of cell_mean / cell_shift, the 2n floats
+// of `table` copied into LDS behind dens in the prologue; a cell is still corrected only when ALL n of its voxels are covered, whatever
+// their weights.  Nothing else differs, and the uniform instantiation never looks at `table`.
 struct CellBox { int by, bx; };                        // the box is (fz, by, bx) voxels
 __host__ __device__ __forceinline__ CellBox cell_box(Cell c) {
     const int zy = c.fz * c.fy;
     return CellBox{c.fy * ((4 + zy - 1) / zy), c.fx * ((64 + c.fx - 1) / c.fx)};
 }
+template <bool PROFILE>
 __global__ __launch_bounds__(256) void volume_joint_consistent_kernel(const float* __restrict__ y, const int* __restrict__ slot,
                                                                       const float* __restrict__ taps, const float* x_t,
                                                                       const float* x0_prev, const float* __restrict__ meas_up,
-                                                                      float* x_next, float* x0_out, int N, int D, int H, int W, int P,
+                                                                      const float* __restrict__ table, float* x_next, float* x0_out,
+                                                                      int N, int D, int H, int W, int P,
                                                                       int stride, int G0, int G1, int G2, Cell c, float w, float kx,
                                                                       float k0, float kp, float kn, float lo, float hi, int clamp_mode,
                                                                       int third_is_normal, unsigned key0, unsigned key1, unsigned draw,
                                                                       unsigned sample) {
-    extern __shared__ float tp[];                      // [P], then x0s [nb] and den [nb]
+    extern __shared__ float tp[];                      // [P], then x0s [nb] and den [nb]; PROFILE: then the table [2][n]
     const CellBox b = cell_box(c);
     const int nb = c.fz * b.by * b.bx, t = threadIdx.y * 64 + threadIdx.x;
     float* x0s = tp + P;
     float* dens = x0s + nb;
+    float* tab = dens + nb;
+    const int n = c.fz * c.fy * c.fx;
     for (int e = t; e < P; e += 256) tp[e] = taps[e];
+    if constexpr (PROFILE)
+        for (int e = t; e < 2 * n; e += 256) tab[e] = table[e];
     __syncthreads();
     const int z0 = blockIdx.z * c.fz, y0 = blockIdx.y * b.by, xb = blockIdx.x * b.bx;
     for (int e = t; e < nb; e += 256) {
@@ -734,13 +799,21 @@ __global__ __launch_bounds__(256) void volume_joint_consistent_kernel(const floa
         // the cell of this voxel inside the box: lz is its z offset (the box is one cell deep)
         const int cb = ((ly / c.fy) * c.fy) * b.bx + (lx / c.fx) * c.fx;
         bool all = true;
-        const float m = cell_mean(c, [&](int i, int j, int k) {
+        auto value = [&](int i, int j, int k) {
             const int q = cb + (i * b.by + j) * b.bx + k;
             all = all && dens[q] != 0.f;
             return x0s[q];
-        });
+        };
         float x0 = x0s[e];
-        if (all) x0 = cell_shift(w, meas_up[v], m, x0);
+        if constexpr (PROFILE) {
+            const float m = cell_wmean(c, tab, value);
+            // this voxel's index inside its cell
+            const float g = tab[n + (lz * c.fy + ly % c.fy) * c.fx + lx % c.fx];
+            if (all) x0 = cell_wshift(w, g, meas_up[v], m, x0);
+        } else {
+            const float m = cell_mean(c, value);
+            if (all) x0 = cell_shift(w, meas_up[v], m, x0);
+        }
         const float prev = x0_prev ? x0_prev[v] : 0.f;
         float n = 0.f;
         if (kn != 0.f) n = philox_normal(philox4x32_10((unsigned)v, (unsigned)((unsigned long long)v >> 32), draw, sample, key0, key1));
@@ -1331,6 +1404,20 @@ extern "C" int diqt_cell_mean(const float* x, float* out, int D, int H, int W, i
     return check_launch("cell_mean");
 }
 
+extern "C" int diqt_cell_wmean(const float* x, const float* table, float* out, int D, int H, int W, int fz, int fy, int fx,
+                               void* stream) {
+    DIQT_REQUIRE(x && table && out, DIQT_E_ALIGN, "cell_wmean: null pointer");
+    int rc = cell_ok("cell_wmean", fz, fy, fx, 1.f);
+    if (rc) return rc;
+    DIQT_REQUIRE(D > 0 && H > 0 && W > 0 && D % fz == 0 && H % fy == 0 && W % fx == 0, DIQT_E_SHAPE,
+                 "cell_wmean: the cell %dx%dx%d does not divide the volume %dx%dx%d", fz, fy, fx, D, H, W);
+    const size_t cells = (size_t)(D / fz) * (H / fy) * (W / fx);
+    DIQT_REQUIRE((cells + 255) / 256 <= 0x7fffffffu, DIQT_E_SHAPE, "cell_wmean: more than 2^31 - 1 blocks");
+    hipLaunchKernelGGL(cell_wmean_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, STREAM, x, table, out, cells, H, W,
+                       Cell{fz, fy, fx});
+    return check_launch("cell_wmean");
+}
+
 extern "C" int diqt_cell_project(const float* x0, const float* meas_up, float* out, size_t cubes, int P, int fz, int fy, int fx,
                                  float weight, float lo, float hi, int clamp_mode, void* stream) {
     DIQT_REQUIRE(x0 && meas_up && out, DIQT_E_ALIGN, "cell_project: null pointer");
@@ -1347,12 +1434,28 @@ extern "C" int diqt_cell_project(const float* x0, const float* meas_up, float* o
     return check_launch("cell_project");
 }
 
-extern "C" int diqt_volume_joint_consistent_step(const float* y, const int* slot, const float* taps, const float* x_t,
-                                                 const float* x0_prev, const float* meas_up, float* x_next, float* x0_out, int form,
-                                                 int N, int D, int H, int W, int P, int stride, int G0, int G1, int G2, int fz, int fy,
-                                                 int fx, float weight, float kx, float k0, float kp, float kn, float lo, float hi,
-                                                 int clamp_mode, unsigned long long seed, unsigned draw, unsigned sample, void* stream) {
-    const char* who = "volume_joint_consistent_step";
+extern "C" int diqt_cell_project_profile(const float* x0, const float* meas_up, const float* table, float* out, size_t cubes, int P,
+                                         int fz, int fy, int fx, float weight, float lo, float hi, int clamp_mode, void* stream) {
+    DIQT_REQUIRE(x0 && meas_up && table && out, DIQT_E_ALIGN, "cell_project_profile: null pointer");
+    int rc = cell_ok("cell_project_profile", fz, fy, fx, weight);
+    if (rc) return rc;
+    DIQT_REQUIRE(clamp_mode >= 0 && clamp_mode <= 2, DIQT_E_UNSUPPORTED,
+                 "cell_project_profile: clamp_mode %d (0 = min, 1 = box, 2 = none)", clamp_mode);
+    DIQT_REQUIRE(cubes > 0 && P > 0 && P % fz == 0 && P % fy == 0 && P % fx == 0, DIQT_E_SHAPE,
+                 "cell_project_profile: the cell %dx%dx%d does not divide the %zu cubes of edge %d", fz, fy, fx, cubes, P);
+    const size_t cells = cubes * (size_t)(P / fz) * (P / fy) * (P / fx);
+    DIQT_REQUIRE((cells + 255) / 256 <= 0x7fffffffu, DIQT_E_SHAPE, "cell_project_profile: more than 2^31 - 1 blocks");
+    hipLaunchKernelGGL(cell_project_profile_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, STREAM, x0, meas_up, table, out,
+                       cells, P, Cell{fz, fy, fx}, weight, ProjectClamp{lo, hi, clamp_mode});
+    return check_launch("cell_project_profile");
+}
+
+// diqt_volume_joint_consistent_step and its profile twin: `table` == NULL is the uniform operator (the twin's entry refuses NULL).
+static int joint_consistent_launch(const char* who, const float* y, const int* slot, const float* taps, const float* x_t,
+                                   const float* x0_prev, const float* meas_up, const float* table, float* x_next, float* x0_out,
+                                   int form, int N, int D, int H, int W, int P, int stride, int G0, int G1, int G2, int fz, int fy,
+                                   int fx, float weight, float kx, float k0, float kp, float kn, float lo, float hi, int clamp_mode,
+                                   unsigned long long seed, unsigned draw, unsigned sample, void* stream) {
     DIQT_REQUIRE(x_t && meas_up && x_next && x0_out && slot && taps && (y || N == 0), DIQT_E_ALIGN, "%s: null pointer", who);
     DIQT_REQUIRE(form >= 0 && form <= 2, DIQT_E_UNSUPPORTED, "%s: form %d (0 = first order, 1 = multistep, 2 = multistep with noise)", who,
                  form);
@@ -1365,16 +1468,45 @@ extern "C" int diqt_volume_joint_consistent_step(const float* y, const int* slot
     if (rc) return rc;
     const Cell c{fz, fy, fx};
     const CellBox b = cell_box(c);
-    const size_t lds = ((size_t)P + 2 * (size_t)fz * b.by * b.bx) * sizeof(float);
+    const size_t lds = ((size_t)P + 2 * (size_t)fz * b.by * b.bx + (table ? 2 * (size_t)fz * fy * fx : 0)) * sizeof(float);
     DIQT_REQUIRE(lds <= 65536, DIQT_E_SHAPE, "%s: P %d needs %zu bytes of LDS", who, P, lds);
     DIQT_REQUIRE((H + b.by - 1) / b.by <= 65535, DIQT_E_SHAPE, "%s: more than 65535 rows of boxes", who);
     // first order: no history; multistep: no normal (and with it no key)
     const bool first = form == 0, noisy = form != 1;
-    hipLaunchKernelGGL(volume_joint_consistent_kernel, dim3((W + b.bx - 1) / b.bx, (H + b.by - 1) / b.by, D / fz), dim3(64, 4), lds, STREAM,
-                       y, slot, taps, x_t, first ? nullptr : x0_prev, meas_up, x_next, x0_out, N, D, H, W, P, stride, G0, G1, G2, c, weight,
-                       kx, k0, first ? 0.f : kp, noisy ? kn : 0.f, lo, hi, clamp_mode, first ? 1 : 0, (unsigned)seed,
-                       (unsigned)(seed >> 32), draw, sample);
+    const dim3 grid((W + b.bx - 1) / b.bx, (H + b.by - 1) / b.by, D / fz);
+    if (table)
+        hipLaunchKernelGGL(volume_joint_consistent_kernel<true>, grid, dim3(64, 4), lds, STREAM, y, slot, taps, x_t,
+                           first ? nullptr : x0_prev, meas_up, table, x_next, x0_out, N, D, H, W, P, stride, G0, G1, G2, c, weight, kx, k0,
+                           first ? 0.f : kp, noisy ? kn : 0.f, lo, hi, clamp_mode, first ? 1 : 0, (unsigned)seed,
+                           (unsigned)(seed >> 32), draw, sample);
+    else
+        hipLaunchKernelGGL(volume_joint_consistent_kernel<false>, grid, dim3(64, 4), lds, STREAM, y, slot, taps, x_t,
+                           first ? nullptr : x0_prev, meas_up, table, x_next, x0_out, N, D, H, W, P, stride, G0, G1, G2, c, weight, kx, k0,
+                           first ? 0.f : kp, noisy ? kn : 0.f, lo, hi, clamp_mode, first ? 1 : 0, (unsigned)seed,
+                           (unsigned)(seed >> 32), draw, sample);
     return check_launch(who);
+}
+
+extern "C" int diqt_volume_joint_consistent_step(const float* y, const int* slot, const float* taps, const float* x_t,
+                                                 const float* x0_prev, const float* meas_up, float* x_next, float* x0_out, int form,
+                                                 int N, int D, int H, int W, int P, int stride, int G0, int G1, int G2, int fz, int fy,
+                                                 int fx, float weight, float kx, float k0, float kp, float kn, float lo, float hi,
+                                                 int clamp_mode, unsigned long long seed, unsigned draw, unsigned sample, void* stream) {
+    return joint_consistent_launch("volume_joint_consistent_step", y, slot, taps, x_t, x0_prev, meas_up, nullptr, x_next, x0_out, form, N,
+                                   D, H, W, P, stride, G0, G1, G2, fz, fy, fx, weight, kx, k0, kp, kn, lo, hi, clamp_mode, seed, draw,
+                                   sample, stream);
+}
+
+extern "C" int diqt_volume_joint_consistent_profile_step(const float* y, const int* slot, const float* taps, const float* x_t,
+                                                         const float* x0_prev, const float* meas_up, const float* table, float* x_next,
+                                                         float* x0_out, int form, int N, int D, int H, int W, int P, int stride, int G0,
+                                                         int G1, int G2, int fz, int fy, int fx, float weight, float kx, float k0,
+                                                         float kp, float kn, float lo, float hi, int clamp_mode,
+                                                         unsigned long long seed, unsigned draw, unsigned sample, void* stream) {
+    DIQT_REQUIRE(table, DIQT_E_ALIGN, "volume_joint_consistent_profile_step: null pointer");
+    return joint_consistent_launch("volume_joint_consistent_profile_step", y, slot, taps, x_t, x0_prev, meas_up, table, x_next, x0_out,
+                                   form, N, D, H, W, P, stride, G0, G1, G2, fz, fy, fx, weight, kx, k0, kp, kn, lo, hi, clamp_mode, seed,
+                                   draw, sample, stream);
 }
 
 extern "C" int diqt_volume_joint_heun(const float* y, const int* slot, const float* taps, float* xh, float* xn, float* x0, int phase, int N,

@@ -418,7 +418,7 @@ class ElucidatedImagen(nn.Module):
     def one_unet_sample(self, unet, shape, *, unet_number, clamp=True, dynamic_threshold=True, cond_scale=1., use_tqdm=True,
                         inpaint_images=None, inpaint_masks=None, inpaint_resample_times=5, init_images=None,
                         skip_steps=None, sigma_min=None, sigma_max=None, noise=None, sampler='heun', sample_steps=None, eta=0.,
-                        consistency=None, consistency_weight=1., **kwargs):
+                        consistency=None, consistency_weight=1., consistency_profile=None, **kwargs):
         """Stochastic Heun sampler (:382-532).  ``noise``: optional injected list [init, step_0, ...], or a callable
         ``noise(shape) -> fp32 device tensor`` whose successive calls are those draws (one ``eps`` per step, also when gamma is 0).
 
@@ -439,15 +439,19 @@ class ElucidatedImagen(nn.Module):
         (``ops.cell_replicate``), arrives in state space here (``sample`` takes it in the units it returns, like ``inpaint_images``).
         Every step's clamped or thresholded prediction goes through ``ops.cell_project`` before ``ops.multistep_sde_step``; the
         history operand and self-conditioning read the projected tensor.  The Heun sampler has two predictions per step and is
-        refused."""
+        refused.  ``consistency_profile=(pz, py, px)`` (with ``consistency``; ``ops.cell_profile``): the measurement is the weighted
+        cell mean of a slice profile, zeros for a gap, and every ``ops.cell_project`` of the chain is one
+        ``ops.cell_project_profile`` -- a gap voxel is never moved."""
         self._check_sampler_args(sampler, sample_steps, skip_steps, eta)
         has_inpainting = self._check_inpaint_args(sampler, inpaint_images, inpaint_masks, inpaint_resample_times)
         consistency = check_consistency('one_unet_sample', consistency, consistency_weight, shape, has_inpainting, init_images,
-                                        skip_steps, sampler)
+                                        skip_steps, sampler, profile=consistency_profile)
+        consistency, table = (consistency[:3], consistency[3]) if exists(consistency) else (None, None)
         if sampler == 'dpmpp2m':
             return self._dpmpp2m_sample(unet, shape, unet_number=unet_number, clamp=clamp, dynamic_threshold=dynamic_threshold,
                                         cond_scale=cond_scale, init_images=init_images, sigma_min=sigma_min, sigma_max=sigma_max,
-                                        noise=noise, sample_steps=sample_steps, eta=eta, consistency=consistency, **kwargs)
+                                        noise=noise, sample_steps=sample_steps, eta=eta, consistency=consistency,
+                                        consistency_profile=table, **kwargs)
         # Inpainting (:441-449, 473-530; RePaint, Lugmayr et al. 2022) is this loop with ``inpaint_resample_times`` passes per step,
         # r = R - 1 .. 0, where plain sampling has one: a pass draws ``eps``, pastes the known image under the mask and churns, runs the
         # two Heun evaluations as ever and -- unless r == 0 or it is the last step -- draws once more and re-noises,
@@ -513,9 +517,10 @@ class ElucidatedImagen(nn.Module):
         return self.unnormalize_img(images)
 
     def _dpmpp2m_sample(self, unet, shape, *, unet_number, clamp, dynamic_threshold, cond_scale, init_images, sigma_min, sigma_max, noise,
-                        sample_steps, eta, consistency=None, **kwargs):
+                        sample_steps, eta, consistency=None, consistency_profile=None, **kwargs):
         """``one_unet_sample(sampler='dpmpp2m')``; the arguments are checked there (``consistency``: None or the checked
-        ``(meas_up, cell, weight)``, ``meas_up`` in state space)."""
+        ``(meas_up, cell, weight)``, ``meas_up`` in state space; ``consistency_profile``: None or the checked host table of
+        ``ops.cell_profile``)."""
         sigmas, coefs = self._dpmpp2m_tables(unet_number - 1, sample_steps, eta, sigma_min, sigma_max)
         sigmas = sigmas.tolist()
         dev, B = self.device, shape[0]
@@ -526,11 +531,13 @@ class ElucidatedImagen(nn.Module):
         if exists(consistency):
             meas_up, cell, weight = consistency
             meas_up = meas_up.to(dev).float().contiguous()
+            table = consistency_profile.to(dev) if exists(consistency_profile) else None    # once per chain
         x_start = None
         for i in range(coefs.shape[0]):
             out = fwd(images, float(sigmas[i]), **sc(x_start))
             if exists(consistency):                                             # ``out`` arrives clamped or thresholded
-                out = ops.cell_project(out, meas_up, cell, weight)
+                out = ops.cell_project_profile(out, meas_up, cell, table, weight) if exists(table) else \
+                    ops.cell_project(out, meas_up, cell, weight)
             images = ops.multistep_sde_step(images, out, x_start, draw() if stochastic[i] else None, k[i, 0], k[i, 1], k[i, 2], k[i, 3])
             x_start = out
         return self._finish_chain(images)
@@ -598,7 +605,8 @@ class ElucidatedImagen(nn.Module):
                inpaint_resample_times=5, init_images=None, skip_steps=None, sigma_min=None, sigma_max=None, video_frames=None,
                batch_size=1, cond_scale=1., lowres_sample_noise_level=None, start_at_unet_number=1, start_image_or_video=None,
                stop_at_unet_number=None, return_all_unet_outputs=False, return_pil_images=False, use_tqdm=True, device=None,
-               noise=None, sampler='heun', sample_steps=None, eta=0., consistency=None, consistency_weight=1.):
+               noise=None, sampler='heun', sample_steps=None, eta=0., consistency=None, consistency_weight=1.,
+               consistency_profile=None):
         """:536-702.  ``noise``: optional injected list [lowres_noise, init, step_0, ...] per sampled unet (tests), or -- when exactly
         one U-Net is sampled -- a callable ``noise(shape) -> fp32 device tensor`` whose successive calls are those draws in that order
         (``inference.AnchoredNoise.source``: call k is draw k of the volume-anchored field).
@@ -619,7 +627,8 @@ class ElucidatedImagen(nn.Module):
         one size); ``meas_up`` [B,C,P,P,P] in the units this returns (``normalize_img`` takes it to state space, as it does
         ``inpaint_images``).  ``ValueError`` naming "consistency" before anything touches the device: with the Heun sampler, together
         with inpainting, ``init_images`` or ``skip_steps``, a weight outside (0, 1], a cell that does not divide the image size or with
-        n outside 2 .. 64, a ``meas_up`` of another shape."""
+        n outside 2 .. 64, a ``meas_up`` of another shape.  ``consistency_profile=(pz, py, px)``: ``one_unet_sample``'s slice profile;
+        without ``consistency``, or one ``ops.cell_profile`` refuses, it is the same ``ValueError``."""
         assert texts is None and text_embeds is None and not return_pil_images
         samplers, steps_per_unet, etas = (cast_tuple(v, len(self.unets)) for v in (sampler, sample_steps, eta))
         for args in zip(samplers, steps_per_unet, cast_tuple(skip_steps, len(self.unets)), etas):
@@ -627,6 +636,8 @@ class ElucidatedImagen(nn.Module):
         sampled_samplers = samplers[start_at_unet_number - 1:default(stop_at_unet_number, len(self.unets))]
         has_inpainting = any([self._check_inpaint_args(s, inpaint_images, inpaint_masks, inpaint_resample_times)
                               for s in sampled_samplers or samplers[-1:]])
+        if exists(consistency_profile) and not exists(consistency):
+            check_consistency('sample', None, consistency_weight, None, profile=consistency_profile)
         if exists(consistency):
             span = range(start_at_unet_number, default(stop_at_unet_number, len(self.unets)) + 1)
             frames = calc_all_frame_dims(self.temporal_downsample_factor, video_frames)
@@ -634,7 +645,7 @@ class ElucidatedImagen(nn.Module):
                 check_consistency('sample', consistency, consistency_weight,
                                   (batch_size, self.channels, *frames[n - 1], self.image_sizes[n - 1], self.image_sizes[n - 1]),
                                   exists(inpaint_images), cast_tuple(init_images, len(self.unets))[n - 1],
-                                  cast_tuple(skip_steps, len(self.unets))[n - 1], samplers[n - 1])
+                                  cast_tuple(skip_steps, len(self.unets))[n - 1], samplers[n - 1], profile=consistency_profile)
             consistency = (self.normalize_img(consistency[0]), consistency[1])
         if has_inpainting:
             if batch_size == 1:                                                    # broadcast along the inpainted images (:580-583)
@@ -681,6 +692,8 @@ class ElucidatedImagen(nn.Module):
             multistep = dict(sampler=unet_sampler, sample_steps=unet_steps, eta=unet_eta) if unet_sampler == 'dpmpp2m' else {}
             if exists(consistency):
                 multistep.update(consistency=consistency, consistency_weight=consistency_weight)
+                if exists(consistency_profile):
+                    multistep.update(consistency_profile=consistency_profile)
             inpaint = {}
             if has_inpainting:
                 inpaint = dict(inpaint_images=inpaint_images, inpaint_masks=inpaint_masks, inpaint_resample_times=inpaint_resample_times)

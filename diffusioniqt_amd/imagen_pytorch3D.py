@@ -1151,14 +1151,18 @@ class SRUnet256(Unet):
         super().__init__(*args, **{**default_kwargs, **kwargs})
 
 
-def check_consistency(who, consistency, weight, shape, has_inpainting=False, init_images=None, skip_steps=None, sampler=None):
+def check_consistency(who, consistency, weight, shape, has_inpainting=False, init_images=None, skip_steps=None, sampler=None,
+                      profile=None):
     """The argument rules of ``consistency=(meas_up, cell)`` / ``consistency_weight`` of the one-call samplers of both families
     (``ValueError`` naming "consistency"; nothing touches the device).  ``shape`` = the [B,C,P,P,P] the sampler generates: ``meas_up``
     must be a float tensor of exactly that shape, the cell must divide P.  Data consistency (DDNM) replaces the cell means of every x0
     prediction by the measurement's; inpainting pastes known values into the state, ``init_images`` / ``skip_steps`` start or thin the
-    chain elsewhere and the EDM Heun sampler has two predictions per step: none of them is offered with it.  Returns None (off) or
-    ``(meas_up, cell, weight)``."""
+    chain elsewhere and the EDM Heun sampler has two predictions per step: none of them is offered with it.  ``profile`` =
+    (pz, py, px), the slice profile of ``consistency_profile`` (``ops.cell_profile``'s rules; it needs ``consistency``).  Returns None
+    (off) or ``(meas_up, cell, weight, table)``, ``table`` None without a profile, else ``ops.cell_profile``'s host table."""
     if consistency is None:
+        if profile is not None:
+            raise ValueError(f"{who}: consistency_profile needs consistency=(meas_up, cell)")
         return None
     if not isinstance(consistency, (tuple, list)) or len(consistency) != 2:
         raise ValueError(f"{who}: consistency must be (meas_up, cell), got {type(consistency).__name__}")
@@ -1174,7 +1178,7 @@ def check_consistency(who, consistency, weight, shape, has_inpainting=False, ini
         got = f"{meas_up.dtype} {tuple(meas_up.shape)}" if torch.is_tensor(meas_up) else type(meas_up).__name__
         raise ValueError(f"{who}: the consistency measurement must be a float tensor of the sampled shape {tuple(shape)} (replicated "
                          f"onto the high-res grid, ops.cell_replicate), got {got}")
-    return meas_up, cell, weight
+    return meas_up, cell, weight, None if profile is None else ops.cell_profile(cell, profile)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -1510,7 +1514,7 @@ class Imagen(nn.Module):
     def p_sample_loop(self, unet, shape, *, noise_scheduler, lowres_cond_img=None, cond_images=None, inpaint_images=None,
                       inpaint_masks=None, inpaint_resample_times=5, init_images=None, skip_steps=None, cond_scale=1,
                       pred_objective='noise', dynamic_threshold=True, use_tqdm=True, noise=None, sampler='ddpm',
-                      sample_steps=None, eta=0.0, consistency=None, consistency_weight=1.0):
+                      sample_steps=None, eta=0.0, consistency=None, consistency_weight=1.0, consistency_profile=None):
         """Ancestral sampler (:2059-2160).  Per step: one U-Net eval (HIP) + ONE fused posterior-step kernel;
         the per-step coefficients for all steps are computed on the host up front.  ``noise`` (optional) is a list
         [init, step_0, ...] of injected tensors with the reference's draw order (:2080, :2051), or a callable
@@ -1535,12 +1539,19 @@ class Imagen(nn.Module):
         (``ops.cell_replicate``), in state space like ``inpaint_images``.  Per step the x0 prediction (thresholded, if configured) goes
         through ``ops.cell_project`` with the chain's clamp -- the cell means of the clamped prediction are moved onto the measurement's
         -- and ``ops.ddpm_step`` then runs with the clamp switched off (an infinite box is the identity bit for bit): clamping after the
-        projection would undo it.  The x0 the step returns, which self-conditioning and ``'dpmpp2m'`` read, is the projected one."""
+        projection would undo it.  The x0 the step returns, which self-conditioning and ``'dpmpp2m'`` read, is the projected one.
+
+        ``consistency_profile=(pz, py, px)`` (with ``consistency``; ``ops.cell_profile``): the measurement of a cell is the weighted
+        mean u . x of its voxels, u the normalised product of the three per-axis weights -- a slice profile, with zeros for a gap
+        between slices (``ops.cell_measure`` is that operator).  Every ``ops.cell_project`` of the chain is then one
+        ``ops.cell_project_profile``: the weighted means are moved onto the measurement, a gap voxel is never moved.  A uniform profile
+        given here takes this path too (equal to no profile up to rounding, not bit for bit)."""
         if pred_objective not in ('noise', 'x_start', 'v'):
             raise ValueError(f'unknown objective {pred_objective}')
         has_inpainting = exists(inpaint_images) and exists(inpaint_masks)                  # (:2090-2091)
         self._check_sampler_args(sampler, sample_steps, skip_steps, eta, has_inpainting)
-        consistency = check_consistency('p_sample_loop', consistency, consistency_weight, shape, has_inpainting, init_images, skip_steps)
+        consistency = check_consistency('p_sample_loop', consistency, consistency_weight, shape, has_inpainting, init_images, skip_steps,
+                                        profile=consistency_profile)
         device = self.device
         batch = shape[0]
         if callable(noise):
@@ -1573,8 +1584,9 @@ class Imagen(nn.Module):
         if dynamic_threshold:                                               # the prediction arrives thresholded: no clamp in the step
             lo, hi, mode = -inf, inf, 1
         if exists(consistency):
-            meas_up, cell, weight = consistency
+            meas_up, cell, weight, table = consistency
             meas_up = meas_up.to(device).float().contiguous()
+            table = table.to(device) if exists(table) else None                # once per chain
 
         noisy_dev, x0_dev = [], []
         x_start = None
@@ -1593,7 +1605,10 @@ class Imagen(nn.Module):
                                            cond_scale, pred_objective, dynamic_threshold)
                 third = x_start if multistep and i > 0 else step_noise()      # 'dpmpp2m': the previous step's clamped x0
                 if exists(consistency):                                       # the clamp, then the projection; the step clamps no more
-                    pred = ops.cell_project(pred, meas_up, cell, weight, clamp=(lo, hi, mode))
+                    if exists(table):
+                        pred = ops.cell_project_profile(pred, meas_up, cell, table, weight, clamp=(lo, hi, mode))
+                    else:
+                        pred = ops.cell_project(pred, meas_up, cell, weight, clamp=(lo, hi, mode))
                     img, x_start = ops.ddpm_step(img, pred, third, coefs[i, 0], coefs[i, 1], coefs[i, 2], -inf, inf, 1)
                 else:
                     img, x_start = ops.ddpm_step(img, pred, third, coefs[i, 0], coefs[i, 1], coefs[i, 2], lo, hi, mode)
@@ -1615,14 +1630,15 @@ class Imagen(nn.Module):
                cond_scale=1., lowres_sample_noise_level=None, start_at_unet_number=1, start_image_or_video=None,
                stop_at_unet_number=None, return_all_outputs=False, return_all_unet_outputs=None, return_pil_images=False,
                device=None, use_tqdm=True, noise=None, sampler='ddpm', sample_steps=None, eta=0.0, consistency=None,
-               consistency_weight=1.0):
+               consistency_weight=1.0, consistency_profile=None):
         """imagen_pytorch3D.py:2165-2274 -> (img, [noisy per step], [x0 per step]).  Accepts both spellings
         ``return_all_outputs`` / ``return_all_unet_outputs`` (test.py:182 uses the latter).  ``sampler`` / ``sample_steps`` / ``eta``
         (one value, or one per U-Net like ``skip_steps``) and the list or callable ``noise``: see ``p_sample_loop``, as for
         ``consistency=(meas_up, cell)`` / ``consistency_weight``, which every sampled U-Net gets (so they must generate one size).  Its
         refusals are ``ValueError`` naming "consistency", raised before anything touches the device: together with inpainting,
         ``init_images`` or ``skip_steps``, a weight outside (0, 1], a cell that does not divide the image size or with
-        n outside 2 .. 64, a ``meas_up`` that is not [B,C,P,P,P]."""
+        n outside 2 .. 64, a ``meas_up`` that is not [B,C,P,P,P]; also a ``consistency_profile`` (``p_sample_loop``) without
+        ``consistency`` or one ``ops.cell_profile`` refuses."""
         if exists(return_all_unet_outputs):
             return_all_outputs = return_all_unet_outputs
         num_unets = len(self.unets)
@@ -1630,9 +1646,12 @@ class Imagen(nn.Module):
         sampler, sample_steps, eta = (cast_tuple(v, num_unets) for v in (sampler, sample_steps, eta))
         for args in zip(sampler, sample_steps, skip_steps, eta):
             self._check_sampler_args(*args, exists(inpaint_images) and exists(inpaint_masks))
+        if exists(consistency_profile) and not exists(consistency):
+            check_consistency('sample', None, consistency_weight, None, profile=consistency_profile)
         for n in range(start_at_unet_number, default(stop_at_unet_number, num_unets) + 1) if exists(consistency) else ():
             check_consistency('sample', consistency, consistency_weight, (batch_size, self.channels) + (self.image_sizes[n - 1],) * 3,
-                              exists(inpaint_images) and exists(inpaint_masks), cast_tuple(init_images, num_unets)[n - 1], skip_steps[n - 1])
+                              exists(inpaint_images) and exists(inpaint_masks), cast_tuple(init_images, num_unets)[n - 1], skip_steps[n - 1],
+                              profile=consistency_profile)
         device = default(device, self.device)
         self.reset_unets_all_one_device(device=device)
         cond_scale = cast_tuple(cond_scale, num_unets)
@@ -1659,7 +1678,7 @@ class Imagen(nn.Module):
                 cond_scale=unet_cond_scale, lowres_cond_img=lowres_cond_img, noise_scheduler=noise_scheduler,
                 pred_objective=pred_objective, dynamic_threshold=dynamic_threshold, use_tqdm=use_tqdm, noise=noise,
                 sampler=unet_sampler, sample_steps=unet_sample_steps, eta=unet_eta, consistency=consistency,
-                consistency_weight=consistency_weight)
+                consistency_weight=consistency_weight, consistency_profile=consistency_profile)
             outputs.append(img)
             if exists(stop_at_unet_number) and stop_at_unet_number == unet_number:
                 break

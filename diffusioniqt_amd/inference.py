@@ -94,6 +94,18 @@ schedule end on kx = 0.032, k0 = 0.971) and the final cell means are kx A x_t + 
 final clamp, and in ``ops.volume_joint_finish`` the fill of uncovered voxels and the background reset -- is not projected again, and
 cells they touch are no longer exactly consistent.  Not offered: the EDM Heun sampler (two predictions per step), and consistency
 together with inpainting.
+
+A slice profile (``consistency_profile=(pz, py, px)``, with ``consistency``) replaces the plain mean: the measurement of a cell is
+u . x, u_q = pz_i py_j px_k / (sum pz sum py sum px) -- the weights of the voxels under a slice, roughly Gaussian or trapezoidal for a
+2-D multi-slice scan, with zeros where a gap between slices leaves voxels unmeasured.  ``ops.cell_profile`` validates it and makes the
+host table (u, and the gains g = u / sum u^2); ``ops.cell_measure(vol, cell, table)`` is that operator and simulates the acquisition.
+The cells stay disjoint, so A+ = A^T / |u|^2 and the projection is x0' = x0 + w g (y - u . x0) per voxel: a gap voxel (u = 0) is never
+moved, and exact consistency at w = 1 means u . x0' = y (to fp32 rounding).  Since sum u = 1, A commutes with the z-score and
+``state_space``, so the replicated measurement, its window gathers, the covered-cell rule (ALL n voxels, whatever their weights) and
+the divisibility rules are those above.  The crop and blend modes hand ``consistency_profile=`` on to the sampler
+(``ops.cell_project_profile`` per step); ``joint=True`` launches ``ops.volume_joint_consistent_profile_step`` in the place of
+``ops.volume_joint_consistent_step``, as many launches as before.  A uniform profile given explicitly takes this path too.  Profiles
+that overlap between neighbouring cells (slice cross-talk) are not offered.
 """
 from types import SimpleNamespace
 
@@ -301,7 +313,10 @@ class VolumeInference:
 
     def _consistency_windows(self, cw):
         """What a sampler call takes besides ``x``: the batch's windows of the replicated measurement."""
-        return dict(consistency=(cw, self.consistency[1]), consistency_weight=self.consistency[2])
+        kw = dict(consistency=(cw, self.consistency[1]), consistency_weight=self.consistency[2])
+        if self.consistency_profile is not None:             # only when one was given: the keyword set is otherwise as it was
+            kw.update(consistency_profile=self.consistency_profile)
+        return kw
 
     def _inpaint_volumes(self, win):
         """The known volume and the mask as 0/1 floats on the volume's device (``__call__`` has checked their shape)."""
@@ -313,7 +328,7 @@ class VolumeInference:
         return dict(inpaint_images=kw, inpaint_masks=mw[:, 0] > 0.5, inpaint_resample_times=self.resample_times)
 
     def __init__(self, configs, sample_fn, nonzero_ratio=0.05, blend=None, sigma_scale=0.125, samples=1, noise=None, seed=0, joint=False,
-                 inpaint=None, inpaint_resample_times=5, consistency=None, consistency_weight=1.0):
+                 inpaint=None, inpaint_resample_times=5, consistency=None, consistency_weight=1.0, consistency_profile=None):
         """``sample_fn(lr_patches [B,1,S,S,S]) -> hr_patches`` — e.g. ``lambda x: trainer.sample(batch_size=x.shape[0],
         start_image_or_video=x, start_at_unet_number=2)[0]`` (test_all.py:234).  ``blend`` / ``sigma_scale`` / ``samples``: weighted
         overlap blending and multi-sample statistics, see the module docstring.  ``noise='anchored'`` (with ``seed``): every call
@@ -345,9 +360,21 @@ class VolumeInference:
         the fused launch of the three linear chains.  ``ValueError`` naming "consistency" before anything touches the device: a pair
         that is not (float [.,.,.] tensor, (fz, fy, fx) integers >= 1 with 2 <= fz fy fx <= 64), a weight outside (0, 1], together with
         ``inpaint``, joint mode with a Heun denoiser, a stride or window the cell does not divide (crop and blend modes) -- and, in
-        ``__call__``, a measurement that is not the volume's shape divided by the cell."""
+        ``__call__``, a measurement that is not the volume's shape divided by the cell.
+
+        ``consistency_profile=(pz, py, px)`` (with ``consistency``): the slice profile of the measurement, three sequences of finite
+        weights >= 0 of lengths fz, fy, fx, each with a positive sum; a zero is a voxel in a slice gap (module docstring;
+        ``ops.cell_measure`` simulates such an acquisition).  The weighted cell means u . x0 are moved onto the measurement -- at
+        w = 1 exactly, u . x0' = y -- and a gap voxel is never moved.  In the crop and blend modes every sampler call also gets
+        ``consistency_profile=``; with ``joint=True`` the fused launch is ``ops.volume_joint_consistent_profile_step``.  A profile
+        without ``consistency``, or one ``ops.cell_profile`` refuses: ``ValueError`` naming "consistency"."""
         self.inpaint = self._check_inpaint(inpaint, inpaint_resample_times, joint, sample_fn)
         self.consistency = self._check_consistency(consistency, consistency_weight, self.inpaint, joint, sample_fn)
+        if consistency_profile is not None and self.consistency is None:
+            raise ValueError("VolumeInference: consistency_profile needs consistency=(measurement, cell)")
+        # the profile as given (what a sampler call takes) and its host table (what the fused launch takes, moved once per volume)
+        self.consistency_profile = consistency_profile
+        self.consistency_table = None if consistency_profile is None else ops.cell_profile(self.consistency[1], consistency_profile)
         self.resample_times = inpaint_resample_times
         if noise not in NOISE_MODES:
             raise ValueError(f"VolumeInference: noise must be None or 'anchored', got {noise!r}")
@@ -506,6 +533,7 @@ class VolumeInference:
         win.meas_up = None                                   # the replicated measurement in state space, for the fused launch
         if self.consistency is not None:
             win.meas_up = self.sample_fn.state_space(self._consistency_volume(win)).contiguous()
+        win.table = None if self.consistency_table is None else self.consistency_table.to(win.device)
         mean_io = m2_io = out_std = None
         for s in range(S):
             x = chain(den, win, evaluate, y, s, *inp[:2])
@@ -566,9 +594,14 @@ class VolumeInference:
                 form = 2 if den.sigma_space else 1 if den.multistep else 0
                 kx, k0, k2, k3 = (*den.coefs[i], 0.)[:4]     # rows (kx, k0, kn), (kx, k0, kp) or (kx, k0, kp, kn)
                 draw = den.draw_base + 1 + i if den.sigma_space else i + 1
-                ops.volume_joint_consistent_step(*head, prev, win.meas_up, self.consistency[1], self.consistency[2], form, kx, k0,
-                                                 0. if form == 0 else k2, k2 if form == 0 else k3, *tail, self.seed, draw=draw, sample=s,
-                                                 **io)
+                if win.table is not None:
+                    ops.volume_joint_consistent_profile_step(*head, prev, win.meas_up, self.consistency[1], win.table,
+                                                             self.consistency[2], form, kx, k0, 0. if form == 0 else k2,
+                                                             k2 if form == 0 else k3, *tail, self.seed, draw=draw, sample=s, **io)
+                else:
+                    ops.volume_joint_consistent_step(*head, prev, win.meas_up, self.consistency[1], self.consistency[2], form, kx, k0,
+                                                     0. if form == 0 else k2, k2 if form == 0 else k3, *tail, self.seed, draw=draw,
+                                                     sample=s, **io)
             elif den.sigma_space:                            # coefs[i] = (kx, k0, kp, kn): + kp x0_prev + kn n(draw_base + 1 + i)
                 ops.volume_joint_multistep_sde(*head, prev, *den.coefs[i], *tail, self.seed, draw=den.draw_base + 1 + i, sample=s, **io)
             elif den.multistep:                              # (kx, k0, kp): + kp x0_prev; only draw 0 of the field is used

@@ -2729,6 +2729,58 @@ def consistency_cell(who, cell, weight=1.0, extents=()):
     return cell, float(weight)
 
 
+def cell_profile(cell, profile):
+    """The host table of a slice profile for the ``consistency_profile`` modes (``ValueError`` naming "consistency"; nothing touches
+    the device).  ``profile`` = (pz, py, px): three sequences of finite numbers >= 0 of lengths fz, fy, fx, each with a positive sum
+    -- the separable weight of a voxel under its cell's measurement, zeros for a slice gap.  Returns a contiguous fp32 host tensor
+    [2, n], n = fz fy fx, in lexicographic (z, y, x) order: row 0 the weights u = pz_i py_j px_k / (sum pz sum py sum px) (so sum u = 1
+    and the measurement of a cell is u . x), row 1 the gains g = u / sum u^2 of the projection x0' = x0 + w g (y - u . x0).  float64
+    arithmetic, every entry rounded once to fp32; the uniform profile gives u = 1 / n and g = 1.  Move it to the device once per
+    chain."""
+    import math
+    import numbers
+    who = "cell_profile"
+    cell, _ = consistency_cell(who, cell)
+    if not isinstance(profile, (tuple, list)) or len(profile) != 3:
+        raise ValueError(f"{who}: the consistency profile must be (pz, py, px), three sequences of weights, got {type(profile).__name__}")
+    axes = []
+    for axis, (p, f) in enumerate(zip(profile, cell)):
+        if not isinstance(p, (tuple, list)) or len(p) != f:
+            raise ValueError(f"{who}: axis {axis} of the consistency profile must be a sequence of {f} numbers (the cell is {cell})")
+        if not all(not isinstance(v, bool) and isinstance(v, numbers.Real) and math.isfinite(v) and v >= 0 for v in p):
+            raise ValueError(f"{who}: the weights of the consistency profile must be finite numbers >= 0, got {p!r} on axis {axis}")
+        p = [float(v) for v in p]
+        total = 0.0
+        for v in p:
+            total += v
+        if not (total > 0.0 and math.isfinite(total)):
+            raise ValueError(f"{who}: axis {axis} of the consistency profile must have a positive finite sum, got {p!r}")
+        axes.append((p, total))
+    (pz, sz), (py, sy), (px, sx) = axes
+    den = sz * sy * sx
+    u = [a * b * c / den for a in pz for b in py for c in px]
+    sq = 0.0
+    for v in u:
+        sq += v * v
+    if not (sq > 0.0 and math.isfinite(sq)):
+        raise ValueError(f"{who}: the consistency profile {profile!r} has no usable norm (sum u^2 = {sq!r})")
+    table = torch.tensor([u, [v / sq for v in u]], dtype=torch.float64).to(torch.float32).contiguous()
+    if not bool(torch.isfinite(table).all()):
+        raise ValueError(f"{who}: the consistency profile {profile!r} does not fit fp32")
+    return table
+
+
+def _cell_table(who, table, cell, like):
+    """The check of a ``cell_profile`` table handed to a kernel: fp32 [2, n], contiguous, on ``like``'s device."""
+    n = cell[0] * cell[1] * cell[2]
+    if not torch.is_tensor(table) or table.dtype != torch.float32 or tuple(table.shape) != (2, n) or not table.is_contiguous():
+        raise ValueError(f"{who}: the consistency profile table must be a contiguous fp32 [2, {n}] tensor (ops.cell_profile), got "
+                         f"{(table.dtype, tuple(table.shape)) if torch.is_tensor(table) else type(table).__name__}")
+    if table.device != like.device:
+        raise ValueError(f"{who}: the consistency profile table is on {table.device}, the data on {like.device}")
+    _chk(table)
+
+
 def cell_mean(vol, cell):
     """The block average of a [D,H,W] volume over cells of ``cell`` = (fz, fy, fx) voxels (include/diqt.h, diqt_cell_mean): fp32
     [D/fz, H/fy, W/fx], each value the cell's sum in (z, y, x) order divided by n -- the measurement operator of the ``consistency``
@@ -2739,6 +2791,21 @@ def cell_mean(vol, cell):
     cell, _ = consistency_cell("cell_mean", cell, 1.0, [(s, a) for a, s in enumerate(vol.shape)])
     out = torch.empty(tuple(s // f for s, f in zip(vol.shape, cell)), dtype=torch.float32, device=vol.device)
     _lib.call("diqt_cell_mean", vol, out, *vol.shape, *cell, _stream())
+    return out
+
+
+def cell_measure(vol, cell, table):
+    """The measurement of a [D,H,W] volume under a slice profile (include/diqt.h, diqt_cell_wmean): fp32 [D/fz, H/fy, W/fx], each
+    value u . x over its cell with u = ``table[0]`` (``cell_profile``, on ``vol``'s device), the sum fused-multiply-added in (z, y, x)
+    order -- the measurement operator of the ``consistency_profile`` modes, e.g. to simulate a thick-slice acquisition with a slice
+    profile and gaps.  One launch."""
+    _chk(vol)
+    if vol.ndim != 3 or not vol.is_contiguous() or vol.numel() == 0:
+        raise ValueError(f"cell_measure: vol must be a non-empty contiguous [D,H,W] tensor, got {tuple(vol.shape)}")
+    cell, _ = consistency_cell("cell_measure", cell, 1.0, [(s, a) for a, s in enumerate(vol.shape)])
+    _cell_table("cell_measure", table, cell, vol)
+    out = torch.empty(tuple(s // f for s, f in zip(vol.shape, cell)), dtype=torch.float32, device=vol.device)
+    _lib.call("diqt_cell_wmean", vol, table, out, *vol.shape, *cell, _stream())
     return out
 
 
@@ -2780,6 +2847,33 @@ def cell_project(x0, meas_up, cell, weight=1.0, clamp=None, out=None):
     return out
 
 
+def cell_project_profile(x0, meas_up, cell, table, weight=1.0, clamp=None, out=None):
+    """``cell_project`` for a measurement with a slice profile (include/diqt.h, diqt_cell_project_profile): ``table`` [2, n] =
+    ``cell_profile``'s weights u and gains g, on ``x0``'s device.  a = clamp(x0); per cell m = u . a; out = a + weight g (meas_up - m):
+    at weight 1 the weighted cell means land on the measurement, and a voxel in a gap (u = 0) is never moved.  Everything else --
+    shapes, ``clamp``, ``out`` -- as there.  Returns ``out``.  One launch."""
+    who = "cell_project_profile"
+    _chk(x0, meas_up, out)
+    if x0.ndim != 5 or x0.numel() == 0 or len(set(x0.shape[2:])) != 1:
+        raise ValueError(f"{who}: x0 must be a non-empty [B,C,P,P,P] tensor of cubes, got {tuple(x0.shape)}")
+    if out is None:
+        out = torch.empty_like(x0)
+    for t, name in ((meas_up, 'meas_up'), (out, 'out')):
+        if t.shape != x0.shape:
+            raise ValueError(f"{who}: {name} must have x0's shape {tuple(x0.shape)}, got {tuple(t.shape)}")
+    if not (x0.is_contiguous() and meas_up.is_contiguous() and out.is_contiguous()):
+        raise RuntimeError(f"{who}: tensors must be contiguous")
+    P = x0.shape[2]
+    cell, weight = consistency_cell(who, cell, weight, [(P, a) for a in range(3)])
+    _cell_table(who, table, cell, x0)
+    lo, hi, mode = (0., 0., 2) if clamp is None else clamp                # the entry's third mode: no clamp
+    if clamp is not None and int(mode) not in (0, 1):
+        raise ValueError(f"{who}: clamp mode must be 0 (min) or 1 (box), got {mode!r}")
+    _lib.call("diqt_cell_project_profile", x0, meas_up, table, out, x0.shape[0] * x0.shape[1], P, *cell, weight, float(lo), float(hi),
+              int(mode), _stream())
+    return out
+
+
 def volume_joint_consistent_step(y, slot, taps, x_t, x0_prev, meas_up, cell, weight, form, kx, k0, kp, kn, lo, hi, clamp_mode, stride,
                                  seed=0, draw=0, sample=0, out=None, x0_out=None):
     """One step of a joint chain with the data-consistency projection between the fuse and the update (include/diqt.h,
@@ -2805,6 +2899,32 @@ def volume_joint_consistent_step(y, slot, taps, x_t, x0_prev, meas_up, cell, wei
     _lib.call("diqt_volume_joint_consistent_step", y if N else None, slot, taps, x_t, None if form == 0 else x0_prev, meas_up, out, x0_out,
               form, N, *x_t.shape, P, stride, *slot.shape, *cell, weight, float(kx), float(k0), float(kp), float(kn), float(lo), float(hi),
               int(clamp_mode), seed, draw, sample, _stream())
+    return out, x0_out
+
+
+def volume_joint_consistent_profile_step(y, slot, taps, x_t, x0_prev, meas_up, cell, table, weight, form, kx, k0, kp, kn, lo, hi,
+                                         clamp_mode, stride, seed=0, draw=0, sample=0, out=None, x0_out=None):
+    """``volume_joint_consistent_step`` for a measurement with a slice profile (include/diqt.h,
+    diqt_volume_joint_consistent_profile_step): ``table`` [2, n] = ``cell_profile``'s weights and gains, on ``x_t``'s device.  Every
+    cell whose voxels are ALL covered -- whatever their weights -- has the weighted mean u . x0 of its fused x0 moved onto the
+    measurement (by ``weight`` of the way, each voxel by its gain) before the update; everything else as there.  Returns
+    ``(out, x0_out)``.  One launch, bit-reproducible."""
+    who = "volume_joint_consistent_profile_step"
+    form = int(form)
+    if form not in (0, 1, 2):
+        raise ValueError(f"{who}: form must be 0 (first order), 1 (multistep) or 2 (multistep with noise), got {form!r}")
+    N, P, stride = _joint_windows(who, y, slot, taps, x_t, clamp_mode, stride)
+    seed, draw, sample = _noise_key(who, seed, draw, sample)
+    _joint_slots(who, slot, N)
+    cell, weight = consistency_cell(who, cell, weight, [(s, a) for a, s in enumerate(x_t.shape)])
+    _chk(meas_up)
+    if meas_up.shape != x_t.shape or not meas_up.is_contiguous():
+        raise ValueError(f"{who}: meas_up must be a contiguous tensor of x_t's shape")
+    _cell_table(who, table, cell, x_t)
+    out, x0_out = _joint_volumes(who, x_t, None if form == 0 else x0_prev, out, x0_out)
+    _lib.call("diqt_volume_joint_consistent_profile_step", y if N else None, slot, taps, x_t, None if form == 0 else x0_prev, meas_up,
+              table, out, x0_out, form, N, *x_t.shape, P, stride, *slot.shape, *cell, weight, float(kx), float(k0), float(kp), float(kn),
+              float(lo), float(hi), int(clamp_mode), seed, draw, sample, _stream())
     return out, x0_out
 
 

@@ -752,6 +752,30 @@ int diqt_volume_joint_consistent_step(const float* y, const int* slot, const flo
                                       int stride, int G0, int G1, int G2, int fz, int fy, int fx, float weight, float kx, float k0,
                                       float kp, float kn, float lo, float hi, int clamp_mode, unsigned long long seed, unsigned draw,
                                       unsigned sample, void* stream);
+/* The same three entries for a measurement with a SLICE PROFILE: per cell y = sum u[q] x[q], u >= 0 and sum u = 1, q the voxel's
+ * lexicographic (z, y, x) index inside its cell (a voxel in a slice gap has u = 0).  The cells stay disjoint, so A A^T = |u|^2 I and
+ * A+ = A^T / |u|^2.  `table` is device fp32 [2][n]: u[0 .. n), then the gain g[q] = u[q] / sum u^2 (the uniform profile: u = 1 / n and
+ * g = 1).  meas_up is replicated as above.  The projection, in fp32 with no contraction, ONE definition for the three entries:
+ *     s = 0;  s = fmaf(u[q], a[q], s) over the cell's voxels in lexicographic order;  m = s           (no division)
+ *     t = w * g[q] (one rounded product);  a'[v] = fmaf(t, meas_up[v] - m, a[v])
+ * (w = 1: u . a' = y to fp32 rounding; a gap voxel is never moved).  The error codes are those of the uniform entries, a null table
+ * being a null pointer; the table's values are the caller's (ops.cell_profile makes them on the host).
+ *
+ * diqt_cell_wmean: out [D / fz][H / fy][W / fx] = m of x [D][H][W] -- A itself.  out may not alias x.                              */
+int diqt_cell_wmean(const float* x, const float* table, float* out, int D, int H, int W, int fz, int fy, int fx, void* stream);
+/* diqt_cell_project with that arithmetic: the same cubes, clamp modes and aliasing (out may alias x0; meas_up and table may not
+ * alias out).                                                                                                                       */
+int diqt_cell_project_profile(const float* x0, const float* meas_up, const float* table, float* out, size_t cubes, int P, int fz, int fy,
+                              int fx, float weight, float lo, float hi, int clamp_mode, void* stream);
+/* diqt_volume_joint_consistent_step with that arithmetic between the fuse and the update: the forms, the window walk, the normals,
+ * the aliasing rules and the error codes are its own, and a cell is corrected only when ALL n of its voxels are covered, whatever
+ * their weights.  The table rides in LDS (2n floats more than the uniform entry).  With stride = P and unit taps the chain is
+ * diqt_cell_project_profile followed by the per-window step, bit for bit.                                                          */
+int diqt_volume_joint_consistent_profile_step(const float* y, const int* slot, const float* taps, const float* x_t, const float* x0_prev,
+                                              const float* meas_up, const float* table, float* x_next, float* x0_out, int form, int N,
+                                              int D, int H, int W, int P, int stride, int G0, int G1, int G2, int fz, int fy, int fx,
+                                              float weight, float kx, float k0, float kp, float kn, float lo, float hi, int clamp_mode,
+                                              unsigned long long seed, unsigned draw, unsigned sample, void* stream);
 /* The stochastic Heun sampler of the EDM family (Karras et al. 2022; elucidated_imagen.py:382-532) on the joint state: a churn, a
  * predictor and a corrector per step, two U-Net evaluations.  The state is three [D][H][W] volumes, all updated in place (every thread
  * reads only its own voxel of each, then writes it): xh = images_hat, xn = images_next, x0 = the fused prediction.  Window walk,
