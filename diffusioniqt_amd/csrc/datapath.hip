@@ -733,6 +733,50 @@ __global__ __launch_bounds__(256) void cell_project_profile_kernel(const float* 
                 out[v] = cell_wshift(w, g[q], meas_up[v], m, clamp(x0[v]));
             }
 }
+// Noise-aware consistency (DDNM+, Wang et al. 2023, 3.3): the measurement carries noise of a known deviation, so a step projects with
+// its own weight and takes its fresh normals REDUCED in the range of A: eps' = eps - shrink g (u . eps) per cell.  That is the
+// projection above applied to the normals with a zero measurement -- m = cell_mean(eps), eps' = cell_shift(shrink, 0, m, eps), or
+// cell_wmean / cell_wshift(shrink, g, 0, m, eps) -- so no new arithmetic is defined here.  The normals are never clamped.
+// diqt_cell_project_noise: cell_project_kernel / cell_project_profile_kernel (PROFILE) and, in the same thread-per-cell walk, the
+// shaping of `noise`, a tensor of x0's shape.  A thread reads and writes only its own cell of either pair, each value read before it is
+// written, so out_x0 may alias x0 and out_noise may alias noise.
+template <bool PROFILE>
+__global__ __launch_bounds__(256) void cell_project_noise_kernel(const float* x0, const float* __restrict__ meas_up, const float* noise,
+                                                                 const float* __restrict__ table, float* out_x0, float* out_noise,
+                                                                 size_t cells, int P, Cell c, float w, float shrink,
+                                                                 ProjectClamp clamp) {
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= cells) return;
+    const int cw = P / c.fx, ch = P / c.fy, cd = P / c.fz;
+    const int cx = (int)(e % cw), cy = (int)((e / cw) % ch), cz = (int)((e / ((size_t)cw * ch)) % cd);
+    const size_t cube = e / ((size_t)cw * ch * cd);
+    const size_t base = ((cube * P + (size_t)cz * c.fz) * P + (size_t)cy * c.fy) * P + (size_t)cx * c.fx;
+    auto at = [&](int i, int j, int k) { return base + ((size_t)i * P + j) * P + k; };
+    auto a = [&](int i, int j, int k) { return clamp(x0[at(i, j, k)]); };
+    auto z = [&](int i, int j, int k) { return noise[at(i, j, k)]; };
+    float m, mz;
+    if constexpr (PROFILE) {
+        m = cell_wmean(c, table, a);
+        mz = cell_wmean(c, table, z);
+    } else {
+        m = cell_mean(c, a);
+        mz = cell_mean(c, z);
+    }
+    int q = 0;
+    for (int i = 0; i < c.fz; ++i)
+        for (int j = 0; j < c.fy; ++j)
+            for (int k = 0; k < c.fx; ++k, ++q) {
+                const size_t v = at(i, j, k);
+                if constexpr (PROFILE) {
+                    const float g = table[c.fz * c.fy * c.fx + q];
+                    out_x0[v] = cell_wshift(w, g, meas_up[v], m, clamp(x0[v]));
+                    out_noise[v] = cell_wshift(shrink, g, 0.f, mz, noise[v]);
+                } else {
+                    out_x0[v] = cell_shift(w, meas_up[v], m, clamp(x0[v]));
+                    out_noise[v] = cell_shift(shrink, 0.f, mz, noise[v]);
+                }
+            }
+}
 // volume_joint_linear_kernel with the projection between the fuse and the update (diqt_volume_joint_consistent_step): per voxel the
 // fuse x0 = num / den exactly as there; a cell whose voxels are ALL covered takes x0' = cell_shift(w, meas_up, cell_mean(x0), x0) and
 // each of its voxels the update with x0' in the place of x0; a cell with an uncovered voxel is left alone -- its covered voxels take
@@ -754,7 +798,13 @@ __host__ __device__ __forceinline__ CellBox cell_box(Cell c) {
     const int zy = c.fz * c.fy;
     return CellBox{c.fy * ((4 + zy - 1) / zy), c.fx * ((64 + c.fx - 1) / c.fx)};
 }
-template <bool PROFILE>
+// NOISE (diqt_volume_joint_consistent_noise_step; forms 0 and 2 with kn != 0 only): the step's normals are shaped as in
+// cell_project_noise_kernel.  Pass 1 draws a covered voxel's normal -- the Philox call of the update, moved, not a second one -- into a
+// third LDS array ns[nb] behind the table; pass 2 reads it back, forms the cell's sum of ns in the order of the sum of x0s and, in a
+// cell whose voxels are ALL covered, takes eps' = cell_shift(shrink, 0, m, eps) (PROFILE: cell_wshift with the voxel's gain).  A cell
+// with an uncovered voxel keeps its plain x0 and its plain normals.  `shrink` is the LAST argument and the other instantiations never
+// look at it, nor at ns: they are what they were.
+template <bool PROFILE, bool NOISE>
 __global__ __launch_bounds__(256) void volume_joint_consistent_kernel(const float* __restrict__ y, const int* __restrict__ slot,
                                                                       const float* __restrict__ taps, const float* x_t,
                                                                       const float* x0_prev, const float* __restrict__ meas_up,
@@ -763,14 +813,15 @@ __global__ __launch_bounds__(256) void volume_joint_consistent_kernel(const floa
                                                                       int stride, int G0, int G1, int G2, Cell c, float w, float kx,
                                                                       float k0, float kp, float kn, float lo, float hi, int clamp_mode,
                                                                       int third_is_normal, unsigned key0, unsigned key1, unsigned draw,
-                                                                      unsigned sample) {
-    extern __shared__ float tp[];                      // [P], then x0s [nb] and den [nb]; PROFILE: then the table [2][n]
+                                                                      unsigned sample, float shrink) {
+    extern __shared__ float tp[];                      // [P], then x0s [nb] and den [nb]; PROFILE: the table [2][n]; NOISE: ns [nb]
     const CellBox b = cell_box(c);
     const int nb = c.fz * b.by * b.bx, t = threadIdx.y * 64 + threadIdx.x;
     float* x0s = tp + P;
     float* dens = x0s + nb;
     float* tab = dens + nb;
     const int n = c.fz * c.fy * c.fx;
+    float* ns = tab + (PROFILE ? 2 * n : 0);
     for (int e = t; e < P; e += 256) tp[e] = taps[e];
     if constexpr (PROFILE)
         for (int e = t; e < 2 * n; e += 256) tab[e] = table[e];
@@ -783,6 +834,14 @@ __global__ __launch_bounds__(256) void volume_joint_consistent_kernel(const floa
         if (p.inside) f = joint_fuse(y, slot, taps, tp, N, P, stride, G0, G1, G2, p, StepClamp{lo, hi, clamp_mode});
         x0s[e] = f.covered() ? f.x0() : 0.f;
         dens[e] = f.den;
+        if constexpr (NOISE) {                         // covered implies inside: v is a voxel of the volume
+            float z = 0.f;
+            if (f.covered()) {
+                const size_t v = ((size_t)p.d * H + p.h) * W + p.x;
+                z = philox_normal(philox4x32_10((unsigned)v, (unsigned)((unsigned long long)v >> 32), draw, sample, key0, key1));
+            }
+            ns[e] = z;
+        }
     }
     __syncthreads();
     for (int e = t; e < nb; e += 256) {
@@ -804,20 +863,31 @@ __global__ __launch_bounds__(256) void volume_joint_consistent_kernel(const floa
             all = all && dens[q] != 0.f;
             return x0s[q];
         };
+        auto normal = [&](int i, int j, int k) { return ns[cb + (i * b.by + j) * b.bx + k]; };
         float x0 = x0s[e];
+        float eps = 0.f;
+        if constexpr (NOISE) eps = ns[e];
         if constexpr (PROFILE) {
             const float m = cell_wmean(c, tab, value);
             // this voxel's index inside its cell
             const float g = tab[n + (lz * c.fy + ly % c.fy) * c.fx + lx % c.fx];
             if (all) x0 = cell_wshift(w, g, meas_up[v], m, x0);
+            if constexpr (NOISE) {
+                const float mz = cell_wmean(c, tab, normal);
+                if (all) eps = cell_wshift(shrink, g, 0.f, mz, eps);
+            }
         } else {
             const float m = cell_mean(c, value);
             if (all) x0 = cell_shift(w, meas_up[v], m, x0);
+            if constexpr (NOISE) {
+                const float mz = cell_mean(c, normal);
+                if (all) eps = cell_shift(shrink, 0.f, mz, eps);
+            }
         }
         const float prev = x0_prev ? x0_prev[v] : 0.f;
-        float n = 0.f;
-        if (kn != 0.f) n = philox_normal(philox4x32_10((unsigned)v, (unsigned)((unsigned long long)v >> 32), draw, sample, key0, key1));
-        const float r = third_is_normal ? sampler_update(kx, xt, k0, x0, kn, n) : sampler_update_sde(kx, xt, k0, x0, kp, prev, kn, n);
+        if constexpr (!NOISE)
+            if (kn != 0.f) eps = philox_normal(philox4x32_10((unsigned)v, (unsigned)((unsigned long long)v >> 32), draw, sample, key0, key1));
+        const float r = third_is_normal ? sampler_update(kx, xt, k0, x0, kn, eps) : sampler_update_sde(kx, xt, k0, x0, kp, prev, kn, eps);
         x0_out[v] = x0;
         x_next[v] = r;
     }
@@ -1450,12 +1520,38 @@ extern "C" int diqt_cell_project_profile(const float* x0, const float* meas_up, 
     return check_launch("cell_project_profile");
 }
 
+extern "C" int diqt_cell_project_noise(const float* x0, const float* meas_up, const float* noise, const float* table, float* out_x0,
+                                       float* out_noise, size_t cubes, int P, int fz, int fy, int fx, float weight, float shrink,
+                                       float lo, float hi, int clamp_mode, void* stream) {
+    DIQT_REQUIRE(x0 && meas_up && noise && out_x0 && out_noise, DIQT_E_ALIGN, "cell_project_noise: null pointer");
+    int rc = cell_ok("cell_project_noise", fz, fy, fx, weight);
+    if (rc) return rc;
+    DIQT_REQUIRE(shrink > 0.f && shrink <= 1.f, DIQT_E_UNSUPPORTED, "cell_project_noise: shrink %g outside (0, 1]", (double)shrink);
+    DIQT_REQUIRE(clamp_mode >= 0 && clamp_mode <= 2, DIQT_E_UNSUPPORTED, "cell_project_noise: clamp_mode %d (0 = min, 1 = box, 2 = none)",
+                 clamp_mode);
+    DIQT_REQUIRE(cubes > 0 && P > 0 && P % fz == 0 && P % fy == 0 && P % fx == 0, DIQT_E_SHAPE,
+                 "cell_project_noise: the cell %dx%dx%d does not divide the %zu cubes of edge %d", fz, fy, fx, cubes, P);
+    const size_t cells = cubes * (size_t)(P / fz) * (P / fy) * (P / fx);
+    DIQT_REQUIRE((cells + 255) / 256 <= 0x7fffffffu, DIQT_E_SHAPE, "cell_project_noise: more than 2^31 - 1 blocks");
+    const dim3 grid((unsigned)((cells + 255) / 256));
+    if (table)
+        hipLaunchKernelGGL(cell_project_noise_kernel<true>, grid, dim3(256), 0, STREAM, x0, meas_up, noise, table, out_x0, out_noise, cells,
+                           P, Cell{fz, fy, fx}, weight, shrink, ProjectClamp{lo, hi, clamp_mode});
+    else
+        hipLaunchKernelGGL(cell_project_noise_kernel<false>, grid, dim3(256), 0, STREAM, x0, meas_up, noise, table, out_x0, out_noise, cells,
+                           P, Cell{fz, fy, fx}, weight, shrink, ProjectClamp{lo, hi, clamp_mode});
+    return check_launch("cell_project_noise");
+}
+
 // diqt_volume_joint_consistent_step and its profile twin: `table` == NULL is the uniform operator (the twin's entry refuses NULL).
+// `shaped` is diqt_volume_joint_consistent_noise_step (which has checked `shrink`, the form and kn): the NOISE instantiations and
+// their third LDS array; the other entries never look at `shrink`.
 static int joint_consistent_launch(const char* who, const float* y, const int* slot, const float* taps, const float* x_t,
                                    const float* x0_prev, const float* meas_up, const float* table, float* x_next, float* x0_out,
                                    int form, int N, int D, int H, int W, int P, int stride, int G0, int G1, int G2, int fz, int fy,
                                    int fx, float weight, float kx, float k0, float kp, float kn, float lo, float hi, int clamp_mode,
-                                   unsigned long long seed, unsigned draw, unsigned sample, void* stream) {
+                                   unsigned long long seed, unsigned draw, unsigned sample, void* stream, bool shaped = false,
+                                   float shrink = 0.f) {
     DIQT_REQUIRE(x_t && meas_up && x_next && x0_out && slot && taps && (y || N == 0), DIQT_E_ALIGN, "%s: null pointer", who);
     DIQT_REQUIRE(form >= 0 && form <= 2, DIQT_E_UNSUPPORTED, "%s: form %d (0 = first order, 1 = multistep, 2 = multistep with noise)", who,
                  form);
@@ -1468,22 +1564,21 @@ static int joint_consistent_launch(const char* who, const float* y, const int* s
     if (rc) return rc;
     const Cell c{fz, fy, fx};
     const CellBox b = cell_box(c);
-    const size_t lds = ((size_t)P + 2 * (size_t)fz * b.by * b.bx + (table ? 2 * (size_t)fz * fy * fx : 0)) * sizeof(float);
+    const size_t lds = ((size_t)P + (shaped ? 3 : 2) * (size_t)fz * b.by * b.bx + (table ? 2 * (size_t)fz * fy * fx : 0)) * sizeof(float);
     DIQT_REQUIRE(lds <= 65536, DIQT_E_SHAPE, "%s: P %d needs %zu bytes of LDS", who, P, lds);
     DIQT_REQUIRE((H + b.by - 1) / b.by <= 65535, DIQT_E_SHAPE, "%s: more than 65535 rows of boxes", who);
     // first order: no history; multistep: no normal (and with it no key)
     const bool first = form == 0, noisy = form != 1;
     const dim3 grid((W + b.bx - 1) / b.bx, (H + b.by - 1) / b.by, D / fz);
-    if (table)
-        hipLaunchKernelGGL(volume_joint_consistent_kernel<true>, grid, dim3(64, 4), lds, STREAM, y, slot, taps, x_t,
-                           first ? nullptr : x0_prev, meas_up, table, x_next, x0_out, N, D, H, W, P, stride, G0, G1, G2, c, weight, kx, k0,
-                           first ? 0.f : kp, noisy ? kn : 0.f, lo, hi, clamp_mode, first ? 1 : 0, (unsigned)seed,
-                           (unsigned)(seed >> 32), draw, sample);
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(64, 4), lds, STREAM, y, slot, taps, x_t, first ? nullptr : x0_prev, meas_up, table, x_next,
+                           x0_out, N, D, H, W, P, stride, G0, G1, G2, c, weight, kx, k0, first ? 0.f : kp, noisy ? kn : 0.f, lo, hi,
+                           clamp_mode, first ? 1 : 0, (unsigned)seed, (unsigned)(seed >> 32), draw, sample, shrink);
+    };
+    if (shaped)
+        table ? launch(volume_joint_consistent_kernel<true, true>) : launch(volume_joint_consistent_kernel<false, true>);
     else
-        hipLaunchKernelGGL(volume_joint_consistent_kernel<false>, grid, dim3(64, 4), lds, STREAM, y, slot, taps, x_t,
-                           first ? nullptr : x0_prev, meas_up, table, x_next, x0_out, N, D, H, W, P, stride, G0, G1, G2, c, weight, kx, k0,
-                           first ? 0.f : kp, noisy ? kn : 0.f, lo, hi, clamp_mode, first ? 1 : 0, (unsigned)seed,
-                           (unsigned)(seed >> 32), draw, sample);
+        table ? launch(volume_joint_consistent_kernel<true, false>) : launch(volume_joint_consistent_kernel<false, false>);
     return check_launch(who);
 }
 
@@ -1507,6 +1602,21 @@ extern "C" int diqt_volume_joint_consistent_profile_step(const float* y, const i
     return joint_consistent_launch("volume_joint_consistent_profile_step", y, slot, taps, x_t, x0_prev, meas_up, table, x_next, x0_out,
                                    form, N, D, H, W, P, stride, G0, G1, G2, fz, fy, fx, weight, kx, k0, kp, kn, lo, hi, clamp_mode, seed,
                                    draw, sample, stream);
+}
+
+extern "C" int diqt_volume_joint_consistent_noise_step(const float* y, const int* slot, const float* taps, const float* x_t,
+                                                       const float* x0_prev, const float* meas_up, const float* table, float* x_next,
+                                                       float* x0_out, int form, int N, int D, int H, int W, int P, int stride, int G0,
+                                                       int G1, int G2, int fz, int fy, int fx, float weight, float shrink, float kx,
+                                                       float k0, float kp, float kn, float lo, float hi, int clamp_mode,
+                                                       unsigned long long seed, unsigned draw, unsigned sample, void* stream) {
+    const char* who = "volume_joint_consistent_noise_step";
+    DIQT_REQUIRE(form == 0 || form == 2, DIQT_E_UNSUPPORTED, "%s: form %d (0 = first order, 2 = multistep with noise: those with a normal)",
+                 who, form);
+    DIQT_REQUIRE(kn != 0.f, DIQT_E_UNSUPPORTED, "%s: kn == 0, a step without a normal has nothing to shape", who);
+    DIQT_REQUIRE(shrink > 0.f && shrink <= 1.f, DIQT_E_UNSUPPORTED, "%s: shrink %g outside (0, 1]", who, (double)shrink);
+    return joint_consistent_launch(who, y, slot, taps, x_t, x0_prev, meas_up, table, x_next, x0_out, form, N, D, H, W, P, stride, G0, G1, G2,
+                                   fz, fy, fx, weight, kx, k0, kp, kn, lo, hi, clamp_mode, seed, draw, sample, stream, true, shrink);
 }
 
 extern "C" int diqt_volume_joint_heun(const float* y, const int* slot, const float* taps, float* xh, float* xn, float* x0, int phase, int N,

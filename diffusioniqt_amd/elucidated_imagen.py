@@ -22,7 +22,7 @@ from . import ops
 from .graphs import GraphCache
 from .imagen_pytorch3D import (GaussianDiffusionContinuousTimes, Unet, NullUnet, exists, default, cast_tuple, identity, maybe,
                                normalize_neg_one_to_one, unnormalize_zero_to_one, eval_decorator, to_channels_last,
-                               to_channels_first, log_snr_to_alpha_sigma, check_consistency)
+                               to_channels_first, log_snr_to_alpha_sigma, check_consistency, naming_consistency_noise)
 from .imagen_video import Unet3D
 
 Hparams_fields = ['num_sample_steps', 'sigma_min', 'sigma_max', 'sigma_data', 'rho', 'P_mean', 'P_std', 'S_churn', 'S_tmin',
@@ -418,7 +418,7 @@ class ElucidatedImagen(nn.Module):
     def one_unet_sample(self, unet, shape, *, unet_number, clamp=True, dynamic_threshold=True, cond_scale=1., use_tqdm=True,
                         inpaint_images=None, inpaint_masks=None, inpaint_resample_times=5, init_images=None,
                         skip_steps=None, sigma_min=None, sigma_max=None, noise=None, sampler='heun', sample_steps=None, eta=0.,
-                        consistency=None, consistency_weight=1., consistency_profile=None, **kwargs):
+                        consistency=None, consistency_weight=1., consistency_profile=None, consistency_noise=None, **kwargs):
         """Stochastic Heun sampler (:382-532).  ``noise``: optional injected list [init, step_0, ...], or a callable
         ``noise(shape) -> fp32 device tensor`` whose successive calls are those draws (one ``eps`` per step, also when gamma is 0).
 
@@ -441,17 +441,26 @@ class ElucidatedImagen(nn.Module):
         history operand and self-conditioning read the projected tensor.  The Heun sampler has two predictions per step and is
         refused.  ``consistency_profile=(pz, py, px)`` (with ``consistency``; ``ops.cell_profile``): the measurement is the weighted
         cell mean of a slice profile, zeros for a gap, and every ``ops.cell_project`` of the chain is one
-        ``ops.cell_project_profile`` -- a gap voxel is never moved."""
+        ``ops.cell_project_profile`` -- a gap voxel is never moved.  ``consistency_noise=sigma`` (with ``consistency``; DDNM+): the
+        standard deviation of the measurement's noise in state space, like ``meas_up`` here.  ``ops.consistency_noise_schedule``
+        makes (w_i, shrink_i) once per chain from the host table (``consistency_weight`` is the cap); on their fp32 values a step with
+        w_i = 0 (kn = 0: the last) skips the projection, one with shrink_i = 0 projects with w_i, and any other runs ONE
+        ``ops.cell_project_noise``, which also reduces the step's normals in the range of A (into a new tensor).  The draws are
+        unchanged.  ``ValueError`` naming "consistency_noise": without ``consistency``, not a finite number > 0, eta = 0 (no
+        stochastic step: use a constant ``consistency_weight``), and everything ``consistency`` refuses."""
         self._check_sampler_args(sampler, sample_steps, skip_steps, eta)
         has_inpainting = self._check_inpaint_args(sampler, inpaint_images, inpaint_masks, inpaint_resample_times)
-        consistency = check_consistency('one_unet_sample', consistency, consistency_weight, shape, has_inpainting, init_images,
-                                        skip_steps, sampler, profile=consistency_profile)
+        with naming_consistency_noise(consistency_noise):
+            consistency = check_consistency('one_unet_sample', consistency, consistency_weight, shape, has_inpainting, init_images,
+                                            skip_steps, sampler, profile=consistency_profile)
+        if exists(consistency_noise):
+            consistency_noise = ops.consistency_noise_sigma('one_unet_sample', consistency_noise, exists(consistency), eta != 0)
         consistency, table = (consistency[:3], consistency[3]) if exists(consistency) else (None, None)
         if sampler == 'dpmpp2m':
             return self._dpmpp2m_sample(unet, shape, unet_number=unet_number, clamp=clamp, dynamic_threshold=dynamic_threshold,
                                         cond_scale=cond_scale, init_images=init_images, sigma_min=sigma_min, sigma_max=sigma_max,
                                         noise=noise, sample_steps=sample_steps, eta=eta, consistency=consistency,
-                                        consistency_profile=table, **kwargs)
+                                        consistency_profile=table, consistency_noise=consistency_noise, **kwargs)
         # Inpainting (:441-449, 473-530; RePaint, Lugmayr et al. 2022) is this loop with ``inpaint_resample_times`` passes per step,
         # r = R - 1 .. 0, where plain sampling has one: a pass draws ``eps``, pastes the known image under the mask and churns, runs the
         # two Heun evaluations as ever and -- unless r == 0 or it is the last step -- draws once more and re-noises,
@@ -517,11 +526,15 @@ class ElucidatedImagen(nn.Module):
         return self.unnormalize_img(images)
 
     def _dpmpp2m_sample(self, unet, shape, *, unet_number, clamp, dynamic_threshold, cond_scale, init_images, sigma_min, sigma_max, noise,
-                        sample_steps, eta, consistency=None, consistency_profile=None, **kwargs):
+                        sample_steps, eta, consistency=None, consistency_profile=None, consistency_noise=None, **kwargs):
         """``one_unet_sample(sampler='dpmpp2m')``; the arguments are checked there (``consistency``: None or the checked
         ``(meas_up, cell, weight)``, ``meas_up`` in state space; ``consistency_profile``: None or the checked host table of
-        ``ops.cell_profile``)."""
+        ``ops.cell_profile``; ``consistency_noise``: None or the checked deviation in state space)."""
         sigmas, coefs = self._dpmpp2m_tables(unet_number - 1, sample_steps, eta, sigma_min, sigma_max)
+        schedule = None
+        if exists(consistency_noise):                                           # once per chain, from the host table
+            schedule = ops.consistency_noise_dispatch(ops.consistency_noise_schedule(
+                coefs.double(), ops.cell_norm(consistency[1], consistency_profile), consistency_noise, consistency[2]))
         sigmas = sigmas.tolist()
         dev, B = self.device, shape[0]
         draw, images, fwd, sc = self._start_chain(unet, shape, unet_number, sigmas[0], noise, init_images, clamp=clamp,
@@ -535,10 +548,16 @@ class ElucidatedImagen(nn.Module):
         x_start = None
         for i in range(coefs.shape[0]):
             out = fwd(images, float(sigmas[i]), **sc(x_start))
-            if exists(consistency):                                             # ``out`` arrives clamped or thresholded
+            if exists(schedule):                                                # consistency_noise: this step's own weight and shrink
+                weight, shrink = schedule[i]
+            shaped = None
+            if exists(schedule) and weight > 0 and shrink > 0:                  # one launch: the projection and the shaped normals;
+                out, shaped = ops.cell_project_noise(out, meas_up, draw(), cell, weight, shrink, table)   # kn != 0 here: the step's draw
+            elif exists(consistency) and weight > 0:                            # ``out`` arrives clamped or thresholded
                 out = ops.cell_project_profile(out, meas_up, cell, table, weight) if exists(table) else \
                     ops.cell_project(out, meas_up, cell, weight)
-            images = ops.multistep_sde_step(images, out, x_start, draw() if stochastic[i] else None, k[i, 0], k[i, 1], k[i, 2], k[i, 3])
+            eps = shaped if exists(shaped) else draw() if stochastic[i] else None
+            images = ops.multistep_sde_step(images, out, x_start, eps, k[i, 0], k[i, 1], k[i, 2], k[i, 3])
             x_start = out
         return self._finish_chain(images)
 
@@ -606,7 +625,7 @@ class ElucidatedImagen(nn.Module):
                batch_size=1, cond_scale=1., lowres_sample_noise_level=None, start_at_unet_number=1, start_image_or_video=None,
                stop_at_unet_number=None, return_all_unet_outputs=False, return_pil_images=False, use_tqdm=True, device=None,
                noise=None, sampler='heun', sample_steps=None, eta=0., consistency=None, consistency_weight=1.,
-               consistency_profile=None):
+               consistency_profile=None, consistency_noise=None):
         """:536-702.  ``noise``: optional injected list [lowres_noise, init, step_0, ...] per sampled unet (tests), or -- when exactly
         one U-Net is sampled -- a callable ``noise(shape) -> fp32 device tensor`` whose successive calls are those draws in that order
         (``inference.AnchoredNoise.source``: call k is draw k of the volume-anchored field).
@@ -628,7 +647,9 @@ class ElucidatedImagen(nn.Module):
         ``inpaint_images``).  ``ValueError`` naming "consistency" before anything touches the device: with the Heun sampler, together
         with inpainting, ``init_images`` or ``skip_steps``, a weight outside (0, 1], a cell that does not divide the image size or with
         n outside 2 .. 64, a ``meas_up`` of another shape.  ``consistency_profile=(pz, py, px)``: ``one_unet_sample``'s slice profile;
-        without ``consistency``, or one ``ops.cell_profile`` refuses, it is the same ``ValueError``."""
+        without ``consistency``, or one ``ops.cell_profile`` refuses, it is the same ``ValueError``.  ``consistency_noise=sigma``:
+        ``one_unet_sample``'s, in the units of ``meas_up`` as passed here (it is multiplied by the slope of ``normalize_img``); every
+        refusal above then also names "consistency_noise", as do its own."""
         assert texts is None and text_embeds is None and not return_pil_images
         samplers, steps_per_unet, etas = (cast_tuple(v, len(self.unets)) for v in (sampler, sample_steps, eta))
         for args in zip(samplers, steps_per_unet, cast_tuple(skip_steps, len(self.unets)), etas):
@@ -636,16 +657,24 @@ class ElucidatedImagen(nn.Module):
         sampled_samplers = samplers[start_at_unet_number - 1:default(stop_at_unet_number, len(self.unets))]
         has_inpainting = any([self._check_inpaint_args(s, inpaint_images, inpaint_masks, inpaint_resample_times)
                               for s in sampled_samplers or samplers[-1:]])
+        if exists(consistency_noise) and not exists(consistency):
+            ops.consistency_noise_sigma('sample', consistency_noise, False)
         if exists(consistency_profile) and not exists(consistency):
             check_consistency('sample', None, consistency_weight, None, profile=consistency_profile)
         if exists(consistency):
             span = range(start_at_unet_number, default(stop_at_unet_number, len(self.unets)) + 1)
             frames = calc_all_frame_dims(self.temporal_downsample_factor, video_frames)
             for n in span:
-                check_consistency('sample', consistency, consistency_weight,
-                                  (batch_size, self.channels, *frames[n - 1], self.image_sizes[n - 1], self.image_sizes[n - 1]),
-                                  exists(inpaint_images), cast_tuple(init_images, len(self.unets))[n - 1],
-                                  cast_tuple(skip_steps, len(self.unets))[n - 1], samplers[n - 1], profile=consistency_profile)
+                with naming_consistency_noise(consistency_noise):
+                    check_consistency('sample', consistency, consistency_weight,
+                                      (batch_size, self.channels, *frames[n - 1], self.image_sizes[n - 1], self.image_sizes[n - 1]),
+                                      exists(inpaint_images), cast_tuple(init_images, len(self.unets))[n - 1],
+                                      cast_tuple(skip_steps, len(self.unets))[n - 1], samplers[n - 1], profile=consistency_profile)
+                if exists(consistency_noise):
+                    ops.consistency_noise_sigma('sample', consistency_noise, True, etas[n - 1] != 0)
+            if exists(consistency_noise):                                          # into state space with the measurement: the map's slope
+                unit = self.normalize_img(torch.tensor([0., 1.], dtype=torch.float64))
+                consistency_noise = float(consistency_noise) * abs(float(unit[1] - unit[0]))
             consistency = (self.normalize_img(consistency[0]), consistency[1])
         if has_inpainting:
             if batch_size == 1:                                                    # broadcast along the inpainted images (:580-583)
@@ -694,6 +723,8 @@ class ElucidatedImagen(nn.Module):
                 multistep.update(consistency=consistency, consistency_weight=consistency_weight)
                 if exists(consistency_profile):
                     multistep.update(consistency_profile=consistency_profile)
+                if exists(consistency_noise):
+                    multistep.update(consistency_noise=consistency_noise)
             inpaint = {}
             if has_inpainting:
                 inpaint = dict(inpaint_images=inpaint_images, inpaint_masks=inpaint_masks, inpaint_resample_times=inpaint_resample_times)

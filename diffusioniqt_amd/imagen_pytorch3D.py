@@ -1181,6 +1181,22 @@ def check_consistency(who, consistency, weight, shape, has_inpainting=False, ini
     return meas_up, cell, weight, None if profile is None else ops.cell_profile(cell, profile)
 
 
+class naming_consistency_noise:
+    """``with naming_consistency_noise(sigma):`` around the ``consistency`` checks: a refusal raised inside while
+    ``consistency_noise`` is given also names "consistency_noise", which rides on ``consistency`` and inherits its refusals."""
+
+    def __init__(self, sigma):
+        self.sigma = sigma
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, kind, err, tb):
+        if kind is ValueError and self.sigma is not None and 'consistency_noise' not in str(err):
+            raise ValueError(f"{err} (consistency_noise={self.sigma!r} rides on consistency)") from None
+        return False
+
+
 # ----------------------------------------------------------------------------------------------
 # Imagen: continuous-time DDPM wrapper (imagen_pytorch3D.py:1741-2442)
 # ----------------------------------------------------------------------------------------------
@@ -1514,7 +1530,8 @@ class Imagen(nn.Module):
     def p_sample_loop(self, unet, shape, *, noise_scheduler, lowres_cond_img=None, cond_images=None, inpaint_images=None,
                       inpaint_masks=None, inpaint_resample_times=5, init_images=None, skip_steps=None, cond_scale=1,
                       pred_objective='noise', dynamic_threshold=True, use_tqdm=True, noise=None, sampler='ddpm',
-                      sample_steps=None, eta=0.0, consistency=None, consistency_weight=1.0, consistency_profile=None):
+                      sample_steps=None, eta=0.0, consistency=None, consistency_weight=1.0, consistency_profile=None,
+                      consistency_noise=None):
         """Ancestral sampler (:2059-2160).  Per step: one U-Net eval (HIP) + ONE fused posterior-step kernel;
         the per-step coefficients for all steps are computed on the host up front.  ``noise`` (optional) is a list
         [init, step_0, ...] of injected tensors with the reference's draw order (:2080, :2051), or a callable
@@ -1545,13 +1562,26 @@ class Imagen(nn.Module):
         mean u . x of its voxels, u the normalised product of the three per-axis weights -- a slice profile, with zeros for a gap
         between slices (``ops.cell_measure`` is that operator).  Every ``ops.cell_project`` of the chain is then one
         ``ops.cell_project_profile``: the weighted means are moved onto the measurement, a gap voxel is never moved.  A uniform profile
-        given here takes this path too (equal to no profile up to rounding, not bit for bit)."""
+        given here takes this path too (equal to no profile up to rounding, not bit for bit).
+
+        ``consistency_noise=sigma`` (with ``consistency``; DDNM+): the standard deviation of the measurement's noise, in the units of
+        ``meas_up``.  ``ops.consistency_noise_schedule`` makes (w_i, shrink_i) once per chain from the host table, rows
+        (kx, k0, 0, kn), with ``consistency_weight`` as the cap.  Per step, on the fp32 values: w_i = 0 (kn = 0: the last step) is the
+        plain ``ops.ddpm_step`` with the chain's own clamp and no projection; shrink_i = 0 the projection above with w_i; otherwise ONE
+        ``ops.cell_project_noise`` replaces the projection launch -- it also reduces the step's normals in the range of A (into a new
+        tensor: an injected noise tensor is never modified).  The draws are those of the chain without it.  ``ValueError`` naming
+        "consistency_noise": without ``consistency``, not a finite number > 0, or a chain with no stochastic step (``'ddim'`` with
+        eta = 0, ``'dpmpp2m'``) -- use a constant ``consistency_weight`` there."""
         if pred_objective not in ('noise', 'x_start', 'v'):
             raise ValueError(f'unknown objective {pred_objective}')
         has_inpainting = exists(inpaint_images) and exists(inpaint_masks)                  # (:2090-2091)
         self._check_sampler_args(sampler, sample_steps, skip_steps, eta, has_inpainting)
-        consistency = check_consistency('p_sample_loop', consistency, consistency_weight, shape, has_inpainting, init_images, skip_steps,
-                                        profile=consistency_profile)
+        with naming_consistency_noise(consistency_noise):
+            consistency = check_consistency('p_sample_loop', consistency, consistency_weight, shape, has_inpainting, init_images,
+                                            skip_steps, profile=consistency_profile)
+        if exists(consistency_noise):
+            consistency_noise = ops.consistency_noise_sigma('p_sample_loop', consistency_noise, exists(consistency),
+                                                            not (sampler == 'dpmpp2m' or (sampler == 'ddim' and eta == 0)))
         device = self.device
         batch = shape[0]
         if callable(noise):
@@ -1571,6 +1601,12 @@ class Imagen(nn.Module):
 
         coefs, conds, x0c, last, renoise, qs = self._sampler_tables(noise_scheduler, batch, sampler, sample_steps, skip_steps, eta,
                                                                     pred_objective)
+        schedule = None
+        if exists(consistency_noise):                                       # once per chain, from the host table; rows are batch-uniform
+            assert bool((coefs == coefs[:, :, :1]).all())
+            rows = [(float(r[0]), float(r[1]), 0., float(r[2])) for r in coefs[:, :, 0].double()]
+            schedule = ops.consistency_noise_dispatch(ops.consistency_noise_schedule(
+                rows, ops.cell_norm(consistency[1], consistency[3]), consistency_noise, consistency[2]))
         multistep = sampler == 'dpmpp2m'
         if multistep or (sampler == 'ddim' and eta == 0):                   # kn == 0: the step kernel reads one zero tensor, no draw
             zero = torch.zeros(shape, device=device)
@@ -1604,7 +1640,12 @@ class Imagen(nn.Module):
                 pred = self._x0_prediction(unet, img, conds[i], x0c[i], lowres, x_start if unet.self_cond else None, cond_images,
                                            cond_scale, pred_objective, dynamic_threshold)
                 third = x_start if multistep and i > 0 else step_noise()      # 'dpmpp2m': the previous step's clamped x0
-                if exists(consistency):                                       # the clamp, then the projection; the step clamps no more
+                if exists(schedule):                                          # consistency_noise: this step's own weight and shrink
+                    weight, shrink = schedule[i]
+                if exists(schedule) and weight > 0 and shrink > 0:            # one launch: the projection and the shaped normals
+                    pred, third = ops.cell_project_noise(pred, meas_up, third, cell, weight, shrink, table, clamp=(lo, hi, mode))
+                    img, x_start = ops.ddpm_step(img, pred, third, coefs[i, 0], coefs[i, 1], coefs[i, 2], -inf, inf, 1)
+                elif exists(consistency) and weight > 0:                      # the clamp, then the projection; the step clamps no more
                     if exists(table):
                         pred = ops.cell_project_profile(pred, meas_up, cell, table, weight, clamp=(lo, hi, mode))
                     else:
@@ -1630,7 +1671,7 @@ class Imagen(nn.Module):
                cond_scale=1., lowres_sample_noise_level=None, start_at_unet_number=1, start_image_or_video=None,
                stop_at_unet_number=None, return_all_outputs=False, return_all_unet_outputs=None, return_pil_images=False,
                device=None, use_tqdm=True, noise=None, sampler='ddpm', sample_steps=None, eta=0.0, consistency=None,
-               consistency_weight=1.0, consistency_profile=None):
+               consistency_weight=1.0, consistency_profile=None, consistency_noise=None):
         """imagen_pytorch3D.py:2165-2274 -> (img, [noisy per step], [x0 per step]).  Accepts both spellings
         ``return_all_outputs`` / ``return_all_unet_outputs`` (test.py:182 uses the latter).  ``sampler`` / ``sample_steps`` / ``eta``
         (one value, or one per U-Net like ``skip_steps``) and the list or callable ``noise``: see ``p_sample_loop``, as for
@@ -1638,7 +1679,8 @@ class Imagen(nn.Module):
         refusals are ``ValueError`` naming "consistency", raised before anything touches the device: together with inpainting,
         ``init_images`` or ``skip_steps``, a weight outside (0, 1], a cell that does not divide the image size or with
         n outside 2 .. 64, a ``meas_up`` that is not [B,C,P,P,P]; also a ``consistency_profile`` (``p_sample_loop``) without
-        ``consistency`` or one ``ops.cell_profile`` refuses."""
+        ``consistency`` or one ``ops.cell_profile`` refuses.  ``consistency_noise=sigma`` (``p_sample_loop``; the units of ``meas_up``
+        as passed): every refusal above then also names "consistency_noise", as do its own."""
         if exists(return_all_unet_outputs):
             return_all_outputs = return_all_unet_outputs
         num_unets = len(self.unets)
@@ -1646,12 +1688,18 @@ class Imagen(nn.Module):
         sampler, sample_steps, eta = (cast_tuple(v, num_unets) for v in (sampler, sample_steps, eta))
         for args in zip(sampler, sample_steps, skip_steps, eta):
             self._check_sampler_args(*args, exists(inpaint_images) and exists(inpaint_masks))
+        if exists(consistency_noise) and not exists(consistency):
+            ops.consistency_noise_sigma('sample', consistency_noise, False)
         if exists(consistency_profile) and not exists(consistency):
             check_consistency('sample', None, consistency_weight, None, profile=consistency_profile)
         for n in range(start_at_unet_number, default(stop_at_unet_number, num_unets) + 1) if exists(consistency) else ():
-            check_consistency('sample', consistency, consistency_weight, (batch_size, self.channels) + (self.image_sizes[n - 1],) * 3,
-                              exists(inpaint_images) and exists(inpaint_masks), cast_tuple(init_images, num_unets)[n - 1], skip_steps[n - 1],
-                              profile=consistency_profile)
+            with naming_consistency_noise(consistency_noise):
+                check_consistency('sample', consistency, consistency_weight, (batch_size, self.channels) + (self.image_sizes[n - 1],) * 3,
+                                  exists(inpaint_images) and exists(inpaint_masks), cast_tuple(init_images, num_unets)[n - 1],
+                                  skip_steps[n - 1], profile=consistency_profile)
+            if exists(consistency_noise):
+                ops.consistency_noise_sigma('sample', consistency_noise, True,
+                                            not (sampler[n - 1] == 'dpmpp2m' or (sampler[n - 1] == 'ddim' and eta[n - 1] == 0)))
         device = default(device, self.device)
         self.reset_unets_all_one_device(device=device)
         cond_scale = cast_tuple(cond_scale, num_unets)
@@ -1678,7 +1726,7 @@ class Imagen(nn.Module):
                 cond_scale=unet_cond_scale, lowres_cond_img=lowres_cond_img, noise_scheduler=noise_scheduler,
                 pred_objective=pred_objective, dynamic_threshold=dynamic_threshold, use_tqdm=use_tqdm, noise=noise,
                 sampler=unet_sampler, sample_steps=unet_sample_steps, eta=unet_eta, consistency=consistency,
-                consistency_weight=consistency_weight, consistency_profile=consistency_profile)
+                consistency_weight=consistency_weight, consistency_profile=consistency_profile, consistency_noise=consistency_noise)
             outputs.append(img)
             if exists(stop_at_unet_number) and stop_at_unet_number == unet_number:
                 break

@@ -106,6 +106,19 @@ the divisibility rules are those above.  The crop and blend modes hand ``consist
 (``ops.cell_project_profile`` per step); ``joint=True`` launches ``ops.volume_joint_consistent_profile_step`` in the place of
 ``ops.volume_joint_consistent_step``, as many launches as before.  A uniform profile given explicitly takes this path too.  Profiles
 that overlap between neighbouring cells (slice cross-talk) are not offered.
+
+A noisy measurement (``consistency_noise=sigma``, with ``consistency``; DDNM+, Wang et al. 2023, 3.3): sigma is the standard deviation
+of the measurement's noise in the raw units of the measurement.  A constant weight pastes that noise into every prediction and the
+stochastic samplers add their full fresh noise on top of it.  With sigma known, ``ops.consistency_noise_schedule`` gives every step of
+a chain x_next = kx x + k0 x0' + kp x0'_prev + kn eps its own weight w_i <= ``consistency_weight`` (now a cap) and a reduction of the
+fresh normals in the range of A, eps' = eps - shrink_i g (u . eps) per cell, so that there the measurement noise the step carries plus
+the fresh noise left is kn^2, what the sampler intends; the null space of A keeps its normals.  The budget is per step: noise already
+inside the state is not tracked.  A step with kn = 0 -- the last of every chain -- gets weight 0 and runs unprojected, so the final
+volume is no longer exactly consistent with the (noisy) measurement, by design.  Units: sigma / std is the z-scored value the crop and
+blend modes hand on as ``consistency_noise=``; ``joint=True`` multiplies it by the slope of the denoiser's affine ``state_space`` map,
+state_space(1) - state_space(0), and dispatches per step: weight 0 the family's plain launch, shrink 0 the consistent launch,
+otherwise ``ops.volume_joint_consistent_noise_step`` -- one launch per step as before, the same draws.  Deterministic chains (ddim with
+eta = 0, dpmpp2m without eta) and the Heun sampler are refused; sigma is given, not estimated.
 """
 from types import SimpleNamespace
 
@@ -113,6 +126,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .imagen_pytorch3D import naming_consistency_noise
 from .metrics import MSSIM, PSNR
 from .utils_mine import convertVolume2subVolume, merge_sub_volumes
 
@@ -316,6 +330,8 @@ class VolumeInference:
         kw = dict(consistency=(cw, self.consistency[1]), consistency_weight=self.consistency[2])
         if self.consistency_profile is not None:             # only when one was given: the keyword set is otherwise as it was
             kw.update(consistency_profile=self.consistency_profile)
+        if self.consistency_noise is not None:               # z-scored like the measurement the sampler gets
+            kw.update(consistency_noise=self.consistency_noise / self.std)
         return kw
 
     def _inpaint_volumes(self, win):
@@ -328,7 +344,8 @@ class VolumeInference:
         return dict(inpaint_images=kw, inpaint_masks=mw[:, 0] > 0.5, inpaint_resample_times=self.resample_times)
 
     def __init__(self, configs, sample_fn, nonzero_ratio=0.05, blend=None, sigma_scale=0.125, samples=1, noise=None, seed=0, joint=False,
-                 inpaint=None, inpaint_resample_times=5, consistency=None, consistency_weight=1.0, consistency_profile=None):
+                 inpaint=None, inpaint_resample_times=5, consistency=None, consistency_weight=1.0, consistency_profile=None,
+                 consistency_noise=None):
         """``sample_fn(lr_patches [B,1,S,S,S]) -> hr_patches`` — e.g. ``lambda x: trainer.sample(batch_size=x.shape[0],
         start_image_or_video=x, start_at_unet_number=2)[0]`` (test_all.py:234).  ``blend`` / ``sigma_scale`` / ``samples``: weighted
         overlap blending and multi-sample statistics, see the module docstring.  ``noise='anchored'`` (with ``seed``): every call
@@ -367,14 +384,30 @@ class VolumeInference:
         ``ops.cell_measure`` simulates such an acquisition).  The weighted cell means u . x0 are moved onto the measurement -- at
         w = 1 exactly, u . x0' = y -- and a gap voxel is never moved.  In the crop and blend modes every sampler call also gets
         ``consistency_profile=``; with ``joint=True`` the fused launch is ``ops.volume_joint_consistent_profile_step``.  A profile
-        without ``consistency``, or one ``ops.cell_profile`` refuses: ``ValueError`` naming "consistency"."""
-        self.inpaint = self._check_inpaint(inpaint, inpaint_resample_times, joint, sample_fn)
-        self.consistency = self._check_consistency(consistency, consistency_weight, self.inpaint, joint, sample_fn)
-        if consistency_profile is not None and self.consistency is None:
-            raise ValueError("VolumeInference: consistency_profile needs consistency=(measurement, cell)")
-        # the profile as given (what a sampler call takes) and its host table (what the fused launch takes, moved once per volume)
-        self.consistency_profile = consistency_profile
-        self.consistency_table = None if consistency_profile is None else ops.cell_profile(self.consistency[1], consistency_profile)
+        without ``consistency``, or one ``ops.cell_profile`` refuses: ``ValueError`` naming "consistency".
+
+        ``consistency_noise=sigma`` (with ``consistency``): the standard deviation of the measurement's noise in raw units (module
+        docstring).  Every step projects with its own weight, capped by ``consistency_weight``, and shapes its fresh noise; the last
+        step is unprojected.  The crop and blend modes hand ``consistency_noise=sigma / std`` on to the sampler; ``joint=True``
+        dispatches per step inside the chain.  ``ValueError`` naming "consistency_noise" before anything touches the device: without
+        ``consistency``, a bool, a non-number, a non-finite or non-positive value, a joint denoiser with no stochastic step."""
+        with naming_consistency_noise(consistency_noise):    # it rides on consistency: what that refuses names it too
+            self.inpaint = self._check_inpaint(inpaint, inpaint_resample_times, joint, sample_fn)
+            self.consistency = self._check_consistency(consistency, consistency_weight, self.inpaint, joint, sample_fn)
+            if consistency_profile is not None and self.consistency is None:
+                raise ValueError("VolumeInference: consistency_profile needs consistency=(measurement, cell)")
+            # the profile as given (what a sampler call takes) and its host table (what the fused launch takes, moved once per volume)
+            self.consistency_profile = consistency_profile
+            self.consistency_table = None if consistency_profile is None else ops.cell_profile(self.consistency[1], consistency_profile)
+        self.consistency_noise = None
+        if consistency_noise is not None:
+            noisy = True                                     # crop and blend modes: the sampler call knows its own chain
+            if joint and hasattr(sample_fn, 'coefs') and not getattr(sample_fn, 'heun', False):
+                # kn is the last entry of a first-order row (kx, k0, kn) and of a sigma-space row (kx, k0, kp, kn); the DDPM family's
+                # multistep rows (kx, k0, kp) have none
+                has_kn = hasattr(sample_fn, 'sigma0') or not getattr(sample_fn, 'multistep', False)
+                noisy = has_kn and any(float(r[-1]) != 0.0 for r in sample_fn.coefs.tolist())
+            self.consistency_noise = ops.consistency_noise_sigma("VolumeInference", consistency_noise, self.consistency is not None, noisy)
         self.resample_times = inpaint_resample_times
         if noise not in NOISE_MODES:
             raise ValueError(f"VolumeInference: noise must be None or 'anchored', got {noise!r}")
@@ -413,9 +446,10 @@ class VolumeInference:
         if self.consistency is not None and not self.joint:
             for f in self.consistency[1]:                    # per axis: origins are multiples of the stride, a sampler call sees `sub`
                 if self.overlap % f or self.sub % f:
-                    raise ValueError(f"VolumeInference: the consistency cell {self.consistency[1]} must divide the stride "
-                                     f"{self.overlap} and the window {self.sub}: a per-window projection is defined for cells inside "
-                                     f"a window only (joint=True projects on the whole volume)")
+                    with naming_consistency_noise(consistency_noise):
+                        raise ValueError(f"VolumeInference: the consistency cell {self.consistency[1]} must divide the stride "
+                                         f"{self.overlap} and the window {self.sub}: a per-window projection is defined for cells "
+                                         f"inside a window only (joint=True projects on the whole volume)")
 
     @torch.no_grad()
     def __call__(self, lowres_raw, patch_slice=None, return_std=False):
@@ -432,8 +466,9 @@ class VolumeInference:
                              f"{tuple(lowres_raw.shape)}")
         if self.consistency is not None and \
                 tuple(s * f for s, f in zip(self.consistency[0].shape, self.consistency[1])) != tuple(lowres_raw.shape):
-            raise ValueError(f"VolumeInference: the consistency measurement {tuple(self.consistency[0].shape)} times the cell "
-                             f"{self.consistency[1]} is not the volume's shape {tuple(lowres_raw.shape)}")
+            with naming_consistency_noise(self.consistency_noise):
+                raise ValueError(f"VolumeInference: the consistency measurement {tuple(self.consistency[0].shape)} times the cell "
+                                 f"{self.consistency[1]} is not the volume's shape {tuple(lowres_raw.shape)}")
         if self.blend is not None:
             if patch_slice is not None:
                 raise NotImplementedError("VolumeInference: a blend mode does not split one volume's windows over ranks (that needs a "
@@ -534,6 +569,13 @@ class VolumeInference:
         if self.consistency is not None:
             win.meas_up = self.sample_fn.state_space(self._consistency_volume(win)).contiguous()
         win.table = None if self.consistency_table is None else self.consistency_table.to(win.device)
+        win.noise_schedule = None                            # per step (w_i, shrink_i) in fp32, made once per volume on the host
+        if self.consistency_noise is not None:
+            unit = self.sample_fn.state_space(torch.tensor([0., 1.], dtype=torch.float64))
+            sigma = self.consistency_noise / self.std * abs(float(unit[1] - unit[0]))
+            rows = [(r[0], r[1], 0., r[2]) if len(r) == 3 else tuple(r) for r in den.coefs]
+            win.noise_schedule = ops.consistency_noise_dispatch(ops.consistency_noise_schedule(
+                rows, ops.cell_norm(self.consistency[1], self.consistency_table), sigma, self.consistency[2]))
         mean_io = m2_io = out_std = None
         for s in range(S):
             x = chain(den, win, evaluate, y, s, *inp[:2])
@@ -590,16 +632,25 @@ class VolumeInference:
         for i in range(den.num_steps):
             evaluate(x, win.x0_vol if den.self_cond and i > 0 else None, self._window_x0(den, win, s, i, edm=den.sigma_space))
             prev = win.x0_vol if i else None
-            if win.meas_up is not None:                      # the same three updates behind the projection of the fused x0
+            weight, shrink = 0., 0.
+            if win.meas_up is not None:                      # the constant weight, or consistency_noise's own of this step
+                weight, shrink = (self.consistency[2], 0.) if win.noise_schedule is None else win.noise_schedule[i]
+            if win.meas_up is not None and weight > 0 and shrink > 0:      # consistency_noise: the step's own weight, its normals shaped
+                form = 2 if den.sigma_space else 0
+                kx, k0, k2, k3 = (*den.coefs[i], 0.)[:4]
+                ops.volume_joint_consistent_noise_step(*head, prev, win.meas_up, self.consistency[1], win.table, weight, shrink, form, kx, k0,
+                                                       0. if form == 0 else k2, k2 if form == 0 else k3, *tail, self.seed,
+                                                       draw=den.draw_base + 1 + i if den.sigma_space else i + 1, sample=s, **io)
+            elif win.meas_up is not None and weight > 0:     # the same three updates behind the projection of the fused x0
                 form = 2 if den.sigma_space else 1 if den.multistep else 0
                 kx, k0, k2, k3 = (*den.coefs[i], 0.)[:4]     # rows (kx, k0, kn), (kx, k0, kp) or (kx, k0, kp, kn)
                 draw = den.draw_base + 1 + i if den.sigma_space else i + 1
                 if win.table is not None:
                     ops.volume_joint_consistent_profile_step(*head, prev, win.meas_up, self.consistency[1], win.table,
-                                                             self.consistency[2], form, kx, k0, 0. if form == 0 else k2,
+                                                             weight, form, kx, k0, 0. if form == 0 else k2,
                                                              k2 if form == 0 else k3, *tail, self.seed, draw=draw, sample=s, **io)
                 else:
-                    ops.volume_joint_consistent_step(*head, prev, win.meas_up, self.consistency[1], self.consistency[2], form, kx, k0,
+                    ops.volume_joint_consistent_step(*head, prev, win.meas_up, self.consistency[1], weight, form, kx, k0,
                                                      0. if form == 0 else k2, k2 if form == 0 else k3, *tail, self.seed, draw=draw,
                                                      sample=s, **io)
             elif den.sigma_space:                            # coefs[i] = (kx, k0, kp, kn): + kp x0_prev + kn n(draw_base + 1 + i)

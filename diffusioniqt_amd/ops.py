@@ -2928,6 +2928,142 @@ def volume_joint_consistent_profile_step(y, slot, taps, x_t, x0_prev, meas_up, c
     return out, x0_out
 
 
+def consistency_noise_sigma(who, sigma_y, has_consistency=True, stochastic=True):
+    """The host rules of ``consistency_noise=`` (``ValueError`` naming "consistency_noise"; nothing touches the device): it rides on
+    ``consistency``, is a finite number > 0 (0 would leave the last step's 0 / 0 undefined; "off" is None) and needs a chain with a
+    stochastic row -- a deterministic sampler gets weight 0 on every step.  Returns it as a float."""
+    import math
+    import numbers
+    if not has_consistency:
+        raise ValueError(f"{who}: consistency_noise needs consistency=(measurement, cell)")
+    if isinstance(sigma_y, bool) or not isinstance(sigma_y, numbers.Real) or not math.isfinite(sigma_y) or not sigma_y > 0:
+        raise ValueError(f"{who}: consistency_noise must be a finite number > 0, the standard deviation of the measurement's noise "
+                         f"(None: a noise-free measurement), got {sigma_y!r}")
+    if not stochastic:
+        raise ValueError(f"{who}: consistency_noise needs a sampler with fresh noise per step (ddpm, ddim or dpmpp2m with eta > 0): a "
+                         f"deterministic chain would never project; use a constant consistency_weight < 1 there")
+    return float(sigma_y)
+
+
+def cell_norm(cell, table=None):
+    """s = |u|_2, the one non-zero singular value of the cell measurement A (A A^T = s^2 I), as a float (float64 arithmetic):
+    1 / sqrt(n) for the plain mean, sqrt(sum u^2) over the fp32 weights of a ``cell_profile`` table summed in float64."""
+    import math
+    cell, _ = consistency_cell("cell_norm", cell)
+    n = cell[0] * cell[1] * cell[2]
+    if table is None:
+        return 1.0 / math.sqrt(n)
+    if not torch.is_tensor(table) or table.dtype != torch.float32 or tuple(table.shape) != (2, n):
+        raise ValueError(f"cell_norm: the consistency profile table must be an fp32 [2, {n}] tensor (ops.cell_profile)")
+    sq = 0.0
+    for v in table[0].tolist():                          # fp32 values, widened exactly
+        sq += v * v
+    return math.sqrt(sq)
+
+
+def consistency_noise_schedule(rows, s, sigma_y, weight):
+    """The per-step weights and noise reductions of noise-aware data consistency (DDNM+, Wang et al. 2023, 3.3) for a chain
+    x_next = kx x + k0 x0' + kp x0'_prev + kn eps: float64 [T, 2] = (w_i, shrink_i).  ``rows`` [T, 4] = (kx, k0, kp, kn) per step
+    (first-order tables pass kp = 0), ``s`` = ``cell_norm``, ``sigma_y`` the standard deviation of the measurement's noise in the units
+    the chain projects in, ``weight`` the cap (``consistency_weight``).  With w_{-1} = 0, per row: kn == 0 gives w_i = 0 (a plain step);
+    otherwise b = kn s / sigma_y, w_i = min(weight, max(0, (b - kp w_{i-1}) / k0)), a_i = k0 w_i + kp w_{i-1},
+    rho_i = sqrt(max(0, 1 - (a_i / b)^2)), shrink_i = 1 - rho_i: in the range of A the measurement noise the step carries,
+    (a_i sigma_y / s)^2, plus the fresh noise left there, (rho_i kn)^2, is kn^2.  A row with kn != 0 and k0 <= 0 is a ``ValueError``.
+    Pure host arithmetic in float64."""
+    import math
+    rows = [[float(v) for v in r] for r in (rows.tolist() if torch.is_tensor(rows) else rows)]
+    if any(len(r) != 4 for r in rows):
+        raise ValueError("consistency_noise_schedule: rows must be [T, 4] = (kx, k0, kp, kn)")
+    s, sigma_y, weight = float(s), float(sigma_y), float(weight)
+    out = torch.zeros(len(rows), 2, dtype=torch.float64)
+    w_prev = 0.0
+    for i, (kx, k0, kp, kn) in enumerate(rows):
+        w_i = shrink = 0.0
+        if kn != 0.0:
+            if not k0 > 0.0:
+                raise ValueError(f"consistency_noise_schedule: consistency_noise needs k0 > 0 on a stochastic row, row {i} has {k0!r}")
+            b = kn * s / sigma_y
+            w_i = min(weight, max(0.0, (b - kp * w_prev) / k0))
+            a = k0 * w_i + kp * w_prev
+            shrink = 1.0 - math.sqrt(max(0.0, 1.0 - (a / b) ** 2))
+        out[i, 0], out[i, 1] = w_i, shrink
+        w_prev = w_i
+    return out
+
+
+def consistency_noise_dispatch(schedule):
+    """A schedule as the chains dispatch on it: the (w_i, shrink_i) rounded to fp32, as Python floats."""
+    return [tuple(r) for r in schedule.to(torch.float32).tolist()]
+
+
+def cell_project_noise(x0, meas_up, noise, cell, weight, shrink, table=None, clamp=None, out=None, out_noise=None):
+    """One step's projection of noise-aware data consistency (include/diqt.h, diqt_cell_project_noise): ``cell_project`` (``table``
+    None) or ``cell_project_profile`` of ``x0`` with ``weight`` and ``clamp``, and the step's normals ``noise`` -- a tensor of
+    ``x0``'s shape -- reduced in the range of A, noise' = noise - shrink g (u . noise) per cell, which is the same projection of
+    ``noise`` onto a zero measurement with ``shrink`` and no clamp, bit for bit.  ``weight`` and ``shrink`` in (0, 1].  ``out`` /
+    ``out_noise``: where x0' and noise' go (``x0`` / ``noise`` themselves for in place; None: new tensors -- a caller's noise tensor is
+    never modified unless it is handed in as ``out_noise``).  Returns ``(x0', noise')``.  One launch."""
+    who = "cell_project_noise"
+    if isinstance(shrink, bool) or not isinstance(shrink, (int, float)) or not 0. < shrink <= 1.:
+        raise ValueError(f"{who}: the consistency_noise shrink must be a number in (0, 1], got {shrink!r}")
+    _chk(x0, meas_up, noise, out, out_noise)
+    if x0.ndim != 5 or x0.numel() == 0 or len(set(x0.shape[2:])) != 1:
+        raise ValueError(f"{who}: x0 must be a non-empty [B,C,P,P,P] tensor of cubes, got {tuple(x0.shape)}")
+    if out is None:
+        out = torch.empty_like(x0)
+    if out_noise is None:
+        out_noise = torch.empty_like(x0)
+    for t, name in ((meas_up, 'meas_up'), (noise, 'noise'), (out, 'out'), (out_noise, 'out_noise')):
+        if t.shape != x0.shape:
+            raise ValueError(f"{who}: {name} must have x0's shape {tuple(x0.shape)}, got {tuple(t.shape)}")
+    if not all(t.is_contiguous() for t in (x0, meas_up, noise, out, out_noise)):
+        raise RuntimeError(f"{who}: tensors must be contiguous")
+    if out_noise.data_ptr() in (x0.data_ptr(), out.data_ptr(), meas_up.data_ptr()) or out.data_ptr() in (noise.data_ptr(),
+                                                                                                         meas_up.data_ptr()):
+        raise ValueError(f"{who}: out may alias only x0, out_noise only noise")
+    P = x0.shape[2]
+    cell, weight = consistency_cell(who, cell, weight, [(P, a) for a in range(3)])
+    if table is not None:
+        _cell_table(who, table, cell, x0)
+    lo, hi, mode = (0., 0., 2) if clamp is None else clamp                # the entry's third mode: no clamp
+    if clamp is not None and int(mode) not in (0, 1):
+        raise ValueError(f"{who}: clamp mode must be 0 (min) or 1 (box), got {mode!r}")
+    _lib.call("diqt_cell_project_noise", x0, meas_up, noise, table, out, out_noise, x0.shape[0] * x0.shape[1], P, *cell, weight,
+              float(shrink), float(lo), float(hi), int(mode), _stream())
+    return out, out_noise
+
+
+def volume_joint_consistent_noise_step(y, slot, taps, x_t, x0_prev, meas_up, cell, table, weight, shrink, form, kx, k0, kp, kn, lo, hi,
+                                       clamp_mode, stride, seed=0, draw=0, sample=0, out=None, x0_out=None):
+    """``volume_joint_consistent_step`` (``table`` None) or ``volume_joint_consistent_profile_step`` with the step's normal shaped as
+    in ``cell_project_noise`` before it enters the update (include/diqt.h, diqt_volume_joint_consistent_noise_step): in every cell
+    whose voxels are ALL covered, eps' = eps - ``shrink`` g (u . eps); a cell with an uncovered voxel keeps its plain x0 and its plain
+    normals.  ``form`` 0 or 2 with ``kn != 0`` and ``shrink`` in (0, 1] only.  The normals are the plain launch's (same key, same draw
+    number).  Returns ``(out, x0_out)``.  One launch, bit-reproducible."""
+    who = "volume_joint_consistent_noise_step"
+    form = int(form)
+    if form not in (0, 2):
+        raise ValueError(f"{who}: form must be 0 (first order) or 2 (multistep with noise), got {form!r}")
+    if float(kn) == 0.0:
+        raise ValueError(f"{who}: kn == 0: a step without a normal has no consistency_noise shaping")
+    if isinstance(shrink, bool) or not isinstance(shrink, (int, float)) or not 0. < shrink <= 1.:
+        raise ValueError(f"{who}: the consistency_noise shrink must be a number in (0, 1], got {shrink!r}")
+    N, P, stride = _joint_windows(who, y, slot, taps, x_t, clamp_mode, stride)
+    seed, draw, sample = _noise_key(who, seed, draw, sample)
+    _joint_slots(who, slot, N)
+    cell, weight = consistency_cell(who, cell, weight, [(s, a) for a, s in enumerate(x_t.shape)])
+    _chk(meas_up)
+    if meas_up.shape != x_t.shape or not meas_up.is_contiguous():
+        raise ValueError(f"{who}: meas_up must be a contiguous tensor of x_t's shape")
+    if table is not None:
+        _cell_table(who, table, cell, x_t)
+    out, x0_out = _joint_volumes(who, x_t, None if form == 0 else x0_prev, out, x0_out)
+    _lib.call("diqt_volume_joint_consistent_noise_step", y if N else None, slot, taps, x_t, None if form == 0 else x0_prev, meas_up, table,
+              out, x0_out, form, N, *x_t.shape, P, stride, *slot.shape, *cell, weight, float(shrink), float(kx), float(k0), float(kp),
+              float(kn), float(lo), float(hi), int(clamp_mode), seed, draw, sample, _stream())
+    return out, x0_out
+
+
 def volume_joint_heun_init(shape, sigma0, kc, seed, draw=0, sample=0, device=None):
     """The first ``images_hat`` of a joint Heun chain (phase 0 of ``diqt_volume_joint_heun``): fp32 [D,H,W],
     ``(sigma0 n(draw)) + kc n(draw + 1)`` with n the volume-anchored normals of channel 0 -- the initial image as

@@ -776,6 +776,33 @@ int diqt_volume_joint_consistent_profile_step(const float* y, const int* slot, c
                                               int D, int H, int W, int P, int stride, int G0, int G1, int G2, int fz, int fy, int fx,
                                               float weight, float kx, float k0, float kp, float kn, float lo, float hi, int clamp_mode,
                                               unsigned long long seed, unsigned draw, unsigned sample, void* stream);
+/* NOISE-AWARE consistency (DDNM+, Wang et al. 2023, section 3.3) for a measurement with noise of a known standard deviation: a step
+ * projects with its own weight and takes its fresh normals reduced in the range of A,
+ *     eps' = eps - shrink g (u . eps)   per cell,   0 < shrink <= 1,
+ * which is the projection above applied to the normals with a zero measurement, in the same fp32 arithmetic and the same order:
+ *     uniform (table == NULL): m = cell mean of eps;  eps'[v] = fmaf(shrink, 0 - m, eps[v])
+ *     profile:                 m = u . eps;  t = shrink * g[q];  eps'[v] = fmaf(t, 0 - m, eps[v])
+ * The normals are never clamped.  The weights and shrinks of a chain come from the host (ops.consistency_noise_schedule).
+ *
+ * diqt_cell_project_noise: diqt_cell_project (table == NULL) or diqt_cell_project_profile on x0 -- the same clamp modes -- and the
+ * shaping of `noise`, a tensor of x0's shape, in ONE launch: bit for bit the projection entry on (x0, meas_up, weight, clamp) and the
+ * same entry on (noise, zeros, shrink, no clamp).  out_x0 may alias x0 and out_noise may alias noise; nothing else may alias an
+ * output.  0 < weight <= 1 and 0 < shrink <= 1, else DIQT_E_UNSUPPORTED.                                                            */
+int diqt_cell_project_noise(const float* x0, const float* meas_up, const float* noise, const float* table, float* out_x0,
+                            float* out_noise, size_t cubes, int P, int fz, int fy, int fx, float weight, float shrink, float lo, float hi,
+                            int clamp_mode, void* stream);
+/* diqt_volume_joint_consistent_profile_step with a nullable table (NULL: the uniform operator of diqt_volume_joint_consistent_step)
+ * and the step's normal shaped before it enters the update.  Forms 0 and 2 only: form 1, kn == 0 or a shrink outside (0, 1] is
+ * DIQT_E_UNSUPPORTED.  The normal of a voxel is the one the plain entries draw (same key, same draw number, one Philox call); it is
+ * kept in a third LDS array of the box (at most 16 KiB more) and a cell whose voxels are ALL covered takes eps' above, its sum formed
+ * in the order of the x0 sum.  A cell with an uncovered voxel keeps its plain x0 and its plain normals.  Aliasing, geometry and the
+ * other error codes are the consistent entries'.  With stride = P and unit taps the chain is diqt_cell_project_noise followed by the
+ * per-window step, bit for bit.                                                                                                    */
+int diqt_volume_joint_consistent_noise_step(const float* y, const int* slot, const float* taps, const float* x_t, const float* x0_prev,
+                                            const float* meas_up, const float* table, float* x_next, float* x0_out, int form, int N,
+                                            int D, int H, int W, int P, int stride, int G0, int G1, int G2, int fz, int fy, int fx,
+                                            float weight, float shrink, float kx, float k0, float kp, float kn, float lo, float hi,
+                                            int clamp_mode, unsigned long long seed, unsigned draw, unsigned sample, void* stream);
 /* The stochastic Heun sampler of the EDM family (Karras et al. 2022; elucidated_imagen.py:382-532) on the joint state: a churn, a
  * predictor and a corrector per step, two U-Net evaluations.  The state is three [D][H][W] volumes, all updated in place (every thread
  * reads only its own voxel of each, then writes it): xh = images_hat, xn = images_next, x0 = the fused prediction.  Window walk,
