@@ -893,6 +893,151 @@ __global__ __launch_bounds__(256) void volume_joint_consistent_kernel(const floa
     }
 }
 
+// ---- data consistency for a tile-local linear operator (ops.tile_operator) ------------------------------------------------------------
+// The volume splits into disjoint tiles of (fz, fy, fx) voxels and every tile is measured by the same m x n matrix A, m >= 1 rows of any
+// rank -- orthogonal thick-slice stacks, a block-DCT low-pass, a partial-volume model.  The projection x0' = x0 + w A+(y - A x0) is
+//     x0' = x0 + w (t - P x0),    t = A+ y on the high-res grid (where meas_up stood),    P = A+ A,
+// P the n x n orthogonal projector onto the row space of A: symmetric to the bit (the host makes it so), at most 64 x 64 floats whatever
+// m is.  ONE definition for the per-window kernel and the joint kernel, fp32 and kept from contraction; for a voxel with in-tile index
+// q = (i fy + j) fx + k:
+//   tile_apply   s = 0; s = fmaf(p[r stride], a[r], s) over the tile's voxels r in lexicographic (z, y, x) order;
+//   then         a'[v] = cell_shift(w, t[v], s, a[v]) = fmaf(w, t[v] - s, a[v]).
+// The projection reads p = P + q with stride n, that is P[r][q] and not P[q][r] (equal by symmetry): lanes that walk x inside a tile read
+// consecutive LDS words, lanes of different tiles with equal q read ONE word (a broadcast), and the 64-word window [r n, r n + n) of a
+// step meets a bank twice only when a 32-lane group holds both q and q + 32.  P[q][r] would put n words between neighbouring lanes.
+// The operator itself (tile_measure_kernel) reads p = A + row n with stride 1.
+template <class Value>
+__device__ __forceinline__ float tile_apply(Cell c, const float* p, int stride, Value a) {
+#pragma clang fp contract(off)
+    float s = 0.f;
+    int r = 0;
+    for (int i = 0; i < c.fz; ++i)
+        for (int j = 0; j < c.fy; ++j)
+            for (int k = 0; k < c.fx; ++k, ++r) s = fmaf(p[r * stride], a(i, j, k), s);
+    return s;
+}
+// A itself: out [m][D / fz][H / fy][W / fx], out[row][tile] = tile_apply of row `row` of A [m][n] on the tile of x [D][H][W].  One
+// thread per output value, the tile index fastest.  Once per volume (to simulate an acquisition), not a step of a chain.
+__global__ __launch_bounds__(256) void tile_measure_kernel(const float* __restrict__ x, const float* __restrict__ A,
+                                                           float* __restrict__ out, size_t tiles, int m, int H, int W, Cell c) {
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= tiles * m) return;
+    const size_t row = e / tiles, tile = e % tiles;
+    const int cw = W / c.fx, ch = H / c.fy;
+    const int cx = (int)(tile % cw), cy = (int)((tile / cw) % ch);
+    const size_t cz = tile / ((size_t)cw * ch);
+    const float* base = x + ((cz * c.fz) * H + (size_t)cy * c.fy) * W + (size_t)cx * c.fx;
+    out[e] = tile_apply(c, A + row * (c.fz * c.fy * c.fx), 1, [&](int i, int j, int k) { return base[((size_t)i * H + j) * W + k]; });
+}
+// The back-projection t = A+ y: out [D][H][W], out[v] = sum over the rows of Ap[q][row] y[row][tile of v], Ap = A+ [n][m], the sum
+// fused-multiply-added in row order.  One thread per voxel.  Once per volume too.
+__global__ __launch_bounds__(256) void tile_backproject_kernel(const float* __restrict__ y, const float* __restrict__ Ap,
+                                                               float* __restrict__ out, size_t total, size_t tiles, int m, int H, int W,
+                                                               Cell c) {
+#pragma clang fp contract(off)
+    const size_t v = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (v >= total) return;
+    const int x = (int)(v % W), h = (int)((v / W) % H);
+    const size_t d = v / ((size_t)W * H);
+    const int q = ((int)(d % c.fz) * c.fy + h % c.fy) * c.fx + x % c.fx;
+    const size_t tile = ((d / c.fz) * (H / c.fy) + h / c.fy) * (W / c.fx) + x / c.fx;
+    float s = 0.f;
+    for (int row = 0; row < m; ++row) s = fmaf(Ap[(size_t)q * m + row], y[row * tiles + tile], s);
+    out[v] = s;
+}
+// The per-window step (diqt_tile_project): x0 / target / out are a [D][H][W] stack of cubes (D = cubes P, H = W = P; tiles never cross
+// a cube since fz divides P); a = clamp(x0), then the projection.  One thread per cell would run n^2 serial FMAs; here a block of 256
+// threads owns a BOX of whole tiles, `b` = cell_box clipped to the cube's edge, stages a into LDS (as [nb], then P [n][n]) and gives
+// every voxel of the box a thread, as the joint kernel does.  A block reads its own voxels of x0 before the barrier and writes only
+// them after it, so out may alias x0.  The grid is flat: box (bx, by, bz) = blockIdx.x split by gx and gy.
+__global__ __launch_bounds__(256) void tile_project_kernel(const float* x0, const float* __restrict__ target,
+                                                           const float* __restrict__ table, float* out, int H, int W, int gx, int gy,
+                                                           Cell c, CellBox b, float w, ProjectClamp clamp) {
+    extern __shared__ float as[];
+    const int n = c.fz * c.fy * c.fx, nb = c.fz * b.by * b.bx, t = threadIdx.x;
+    float* tab = as + nb;
+    for (int e = t; e < n * n; e += 256) tab[e] = table[e];
+    const int y0 = (int)((blockIdx.x / gx) % gy) * b.by, xb = (int)(blockIdx.x % gx) * b.bx;
+    const size_t z0 = (size_t)(blockIdx.x / ((unsigned)gx * gy)) * c.fz;
+    auto voxel = [&](int lx, int ly, int lz) { return ((z0 + lz) * H + (y0 + ly)) * W + (xb + lx); };
+    for (int e = t; e < nb; e += 256) {
+        const int lx = e % b.bx, ly = (e / b.bx) % b.by, lz = e / (b.bx * b.by);
+        as[e] = y0 + ly < H && xb + lx < W ? clamp(x0[voxel(lx, ly, lz)]) : 0.f;
+    }
+    __syncthreads();
+    for (int e = t; e < nb; e += 256) {
+        const int lx = e % b.bx, ly = (e / b.bx) % b.by, lz = e / (b.bx * b.by);
+        if (y0 + ly >= H || xb + lx >= W) continue;    // H and W are multiples of the tile: a tile is inside or outside as a whole
+        const size_t v = voxel(lx, ly, lz);
+        const int cb = ((ly / c.fy) * c.fy) * b.bx + (lx / c.fx) * c.fx;
+        const int q = (lz * c.fy + ly % c.fy) * c.fx + lx % c.fx;
+        const float s = tile_apply(c, tab + q, n, [&](int i, int j, int k) { return as[cb + (i * b.by + j) * b.bx + k]; });
+        out[v] = cell_shift(w, target[v], s, as[e]);
+    }
+}
+// volume_joint_consistent_kernel for a tile operator (diqt_volume_joint_consistent_tile_step): the same box, pass 1 as there (no
+// NOISE), the n x n floats of `table` = P copied into LDS behind dens in the prologue; pass 2 forms tile_apply over the voxel's tile
+// out of x0s in the place of cell_mean and shifts by meas_up = t.  The forms, the normals, the covered rule (ALL n voxels), the
+// uncovered voxels and the aliasing are that kernel's.  `shrink` is not looked at (one launch helper serves both kernels).
+__global__ __launch_bounds__(256) void volume_joint_consistent_tile_kernel(const float* __restrict__ y, const int* __restrict__ slot,
+                                                                           const float* __restrict__ taps, const float* x_t,
+                                                                           const float* x0_prev, const float* __restrict__ meas_up,
+                                                                           const float* __restrict__ table, float* x_next, float* x0_out,
+                                                                           int N, int D, int H, int W, int P, int stride, int G0, int G1,
+                                                                           int G2, Cell c, float w, float kx, float k0, float kp, float kn,
+                                                                           float lo, float hi, int clamp_mode, int third_is_normal,
+                                                                           unsigned key0, unsigned key1, unsigned draw, unsigned sample,
+                                                                           float shrink) {
+    extern __shared__ float tp[];                      // [P], then x0s [nb] and den [nb], then the table [n][n]
+    const CellBox b = cell_box(c);
+    const int nb = c.fz * b.by * b.bx, t = threadIdx.y * 64 + threadIdx.x;
+    float* x0s = tp + P;
+    float* dens = x0s + nb;
+    float* tab = dens + nb;
+    const int n = c.fz * c.fy * c.fx;
+    for (int e = t; e < P; e += 256) tp[e] = taps[e];
+    for (int e = t; e < n * n; e += 256) tab[e] = table[e];
+    __syncthreads();
+    const int z0 = blockIdx.z * c.fz, y0 = blockIdx.y * b.by, xb = blockIdx.x * b.bx;
+    for (int e = t; e < nb; e += 256) {
+        const int lx = e % b.bx, ly = (e / b.bx) % b.by, lz = e / (b.bx * b.by);
+        const Voxel p{xb + lx, y0 + ly, z0 + lz, 0, y0 + ly < H && xb + lx < W};
+        Fused f{0.f, 0.f};
+        if (p.inside) f = joint_fuse(y, slot, taps, tp, N, P, stride, G0, G1, G2, p, StepClamp{lo, hi, clamp_mode});
+        x0s[e] = f.covered() ? f.x0() : 0.f;
+        dens[e] = f.den;
+    }
+    __syncthreads();
+    for (int e = t; e < nb; e += 256) {
+        const int lx = e % b.bx, ly = (e / b.bx) % b.by, lz = e / (b.bx * b.by);
+        const int x = xb + lx, h = y0 + ly, d = z0 + lz;
+        if (h >= H || x >= W) continue;
+        const size_t v = ((size_t)d * H + h) * W + x;
+        const float xt = x_t[v];
+        if (dens[e] == 0.f) {
+            x_next[v] = xt;
+            x0_out[v] = 0.f;
+            continue;
+        }
+        const int cb = ((ly / c.fy) * c.fy) * b.bx + (lx / c.fx) * c.fx;
+        const int q = (lz * c.fy + ly % c.fy) * c.fx + lx % c.fx;      // this voxel's index inside its tile
+        bool all = true;
+        const float s = tile_apply(c, tab + q, n, [&](int i, int j, int k) {
+            const int u = cb + (i * b.by + j) * b.bx + k;
+            all = all && dens[u] != 0.f;
+            return x0s[u];
+        });
+        float x0 = x0s[e];
+        if (all) x0 = cell_shift(w, meas_up[v], s, x0);
+        const float prev = x0_prev ? x0_prev[v] : 0.f;
+        float eps = 0.f;
+        if (kn != 0.f) eps = philox_normal(philox4x32_10((unsigned)v, (unsigned)((unsigned long long)v >> 32), draw, sample, key0, key1));
+        const float r = third_is_normal ? sampler_update(kx, xt, k0, x0, kn, eps) : sampler_update_sde(kx, xt, k0, x0, kp, prev, kn, eps);
+        x0_out[v] = x0;
+        x_next[v] = r;
+    }
+}
+
 // The stochastic Heun sampler of the EDM family (elucidated_imagen.py:382-532) on the same state: a churn, a predictor and a corrector
 // per step, two U-Net evaluations, so the state is three volumes -- xh = images_hat, xn = images_next, x0 = the fused prediction (the
 // one self-conditioning reads) -- and the launch takes a `phase`, uniform over the grid:
@@ -1546,12 +1691,13 @@ extern "C" int diqt_cell_project_noise(const float* x0, const float* meas_up, co
 // diqt_volume_joint_consistent_step and its profile twin: `table` == NULL is the uniform operator (the twin's entry refuses NULL).
 // `shaped` is diqt_volume_joint_consistent_noise_step (which has checked `shrink`, the form and kn): the NOISE instantiations and
 // their third LDS array; the other entries never look at `shrink`.
+// `tile` is diqt_volume_joint_consistent_tile_step: `table` is the n x n projector of a tile operator and the kernel its own.
 static int joint_consistent_launch(const char* who, const float* y, const int* slot, const float* taps, const float* x_t,
                                    const float* x0_prev, const float* meas_up, const float* table, float* x_next, float* x0_out,
                                    int form, int N, int D, int H, int W, int P, int stride, int G0, int G1, int G2, int fz, int fy,
                                    int fx, float weight, float kx, float k0, float kp, float kn, float lo, float hi, int clamp_mode,
                                    unsigned long long seed, unsigned draw, unsigned sample, void* stream, bool shaped = false,
-                                   float shrink = 0.f) {
+                                   float shrink = 0.f, bool tile = false) {
     DIQT_REQUIRE(x_t && meas_up && x_next && x0_out && slot && taps && (y || N == 0), DIQT_E_ALIGN, "%s: null pointer", who);
     DIQT_REQUIRE(form >= 0 && form <= 2, DIQT_E_UNSUPPORTED, "%s: form %d (0 = first order, 1 = multistep, 2 = multistep with noise)", who,
                  form);
@@ -1564,7 +1710,8 @@ static int joint_consistent_launch(const char* who, const float* y, const int* s
     if (rc) return rc;
     const Cell c{fz, fy, fx};
     const CellBox b = cell_box(c);
-    const size_t lds = ((size_t)P + (shaped ? 3 : 2) * (size_t)fz * b.by * b.bx + (table ? 2 * (size_t)fz * fy * fx : 0)) * sizeof(float);
+    const size_t n = (size_t)fz * fy * fx;
+    const size_t lds = ((size_t)P + (shaped ? 3 : 2) * (size_t)fz * b.by * b.bx + (tile ? n * n : table ? 2 * n : 0)) * sizeof(float);
     DIQT_REQUIRE(lds <= 65536, DIQT_E_SHAPE, "%s: P %d needs %zu bytes of LDS", who, P, lds);
     DIQT_REQUIRE((H + b.by - 1) / b.by <= 65535, DIQT_E_SHAPE, "%s: more than 65535 rows of boxes", who);
     // first order: no history; multistep: no normal (and with it no key)
@@ -1575,7 +1722,9 @@ static int joint_consistent_launch(const char* who, const float* y, const int* s
                            x0_out, N, D, H, W, P, stride, G0, G1, G2, c, weight, kx, k0, first ? 0.f : kp, noisy ? kn : 0.f, lo, hi,
                            clamp_mode, first ? 1 : 0, (unsigned)seed, (unsigned)(seed >> 32), draw, sample, shrink);
     };
-    if (shaped)
+    if (tile)
+        launch(volume_joint_consistent_tile_kernel);
+    else if (shaped)
         table ? launch(volume_joint_consistent_kernel<true, true>) : launch(volume_joint_consistent_kernel<false, true>);
     else
         table ? launch(volume_joint_consistent_kernel<true, false>) : launch(volume_joint_consistent_kernel<false, false>);
@@ -1617,6 +1766,71 @@ extern "C" int diqt_volume_joint_consistent_noise_step(const float* y, const int
     DIQT_REQUIRE(shrink > 0.f && shrink <= 1.f, DIQT_E_UNSUPPORTED, "%s: shrink %g outside (0, 1]", who, (double)shrink);
     return joint_consistent_launch(who, y, slot, taps, x_t, x0_prev, meas_up, table, x_next, x0_out, form, N, D, H, W, P, stride, G0, G1, G2,
                                    fz, fy, fx, weight, kx, k0, kp, kn, lo, hi, clamp_mode, seed, draw, sample, stream, true, shrink);
+}
+
+extern "C" int diqt_tile_measure(const float* x, const float* A, float* out, int m, int D, int H, int W, int fz, int fy, int fx,
+                                 void* stream) {
+    DIQT_REQUIRE(x && A && out, DIQT_E_ALIGN, "tile_measure: null pointer");
+    int rc = cell_ok("tile_measure", fz, fy, fx, 1.f);
+    if (rc) return rc;
+    DIQT_REQUIRE(m >= 1, DIQT_E_SHAPE, "tile_measure: %d rows", m);
+    DIQT_REQUIRE(D > 0 && H > 0 && W > 0 && D % fz == 0 && H % fy == 0 && W % fx == 0, DIQT_E_SHAPE,
+                 "tile_measure: the cell %dx%dx%d does not divide the volume %dx%dx%d", fz, fy, fx, D, H, W);
+    const size_t tiles = (size_t)(D / fz) * (H / fy) * (W / fx);
+    DIQT_REQUIRE((tiles * m + 255) / 256 <= 0x7fffffffu, DIQT_E_SHAPE, "tile_measure: more than 2^31 - 1 blocks");
+    hipLaunchKernelGGL(tile_measure_kernel, dim3((unsigned)((tiles * m + 255) / 256)), dim3(256), 0, STREAM, x, A, out, tiles, m, H, W,
+                       Cell{fz, fy, fx});
+    return check_launch("tile_measure");
+}
+
+extern "C" int diqt_tile_backproject(const float* y, const float* Ap, float* out, int m, int D, int H, int W, int fz, int fy, int fx,
+                                     void* stream) {
+    DIQT_REQUIRE(y && Ap && out, DIQT_E_ALIGN, "tile_backproject: null pointer");
+    int rc = cell_ok("tile_backproject", fz, fy, fx, 1.f);
+    if (rc) return rc;
+    DIQT_REQUIRE(m >= 1, DIQT_E_SHAPE, "tile_backproject: %d rows", m);
+    DIQT_REQUIRE(D > 0 && H > 0 && W > 0 && D % fz == 0 && H % fy == 0 && W % fx == 0, DIQT_E_SHAPE,
+                 "tile_backproject: the cell %dx%dx%d does not divide the volume %dx%dx%d", fz, fy, fx, D, H, W);
+    const size_t total = (size_t)D * H * W;
+    DIQT_REQUIRE((total + 255) / 256 <= 0x7fffffffu, DIQT_E_SHAPE, "tile_backproject: more than 2^31 - 1 blocks");
+    hipLaunchKernelGGL(tile_backproject_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, STREAM, y, Ap, out, total,
+                       total / ((size_t)fz * fy * fx), m, H, W, Cell{fz, fy, fx});
+    return check_launch("tile_backproject");
+}
+
+extern "C" int diqt_tile_project(const float* x0, const float* target, const float* table, float* out, size_t cubes, int P, int fz, int fy,
+                                 int fx, float weight, float lo, float hi, int clamp_mode, void* stream) {
+    DIQT_REQUIRE(x0 && target && table && out, DIQT_E_ALIGN, "tile_project: null pointer");
+    int rc = cell_ok("tile_project", fz, fy, fx, weight);
+    if (rc) return rc;
+    DIQT_REQUIRE(clamp_mode >= 0 && clamp_mode <= 2, DIQT_E_UNSUPPORTED, "tile_project: clamp_mode %d (0 = min, 1 = box, 2 = none)",
+                 clamp_mode);
+    DIQT_REQUIRE(cubes > 0 && P > 0 && P % fz == 0 && P % fy == 0 && P % fx == 0, DIQT_E_SHAPE,
+                 "tile_project: the cell %dx%dx%d does not divide the %zu cubes of edge %d", fz, fy, fx, cubes, P);
+    const Cell c{fz, fy, fx};
+    CellBox b = cell_box(c);                           // clipped to the cube: P is a multiple of fy and fx, so the box stays whole tiles
+    b.by = b.by < P ? b.by : P;
+    b.bx = b.bx < P ? b.bx : P;
+    const size_t n = (size_t)fz * fy * fx, lds = ((size_t)fz * b.by * b.bx + n * n) * sizeof(float);
+    DIQT_REQUIRE(lds <= 65536, DIQT_E_SHAPE, "tile_project: the cell %dx%dx%d needs %zu bytes of LDS", fz, fy, fx, lds);
+    const int gx = (P + b.bx - 1) / b.bx, gy = (P + b.by - 1) / b.by;
+    const size_t blocks = (size_t)gx * gy * (cubes * (size_t)(P / fz));
+    DIQT_REQUIRE(blocks <= 0x7fffffffu, DIQT_E_SHAPE, "tile_project: more than 2^31 - 1 blocks");
+    hipLaunchKernelGGL(tile_project_kernel, dim3((unsigned)blocks), dim3(256), lds, STREAM, x0, target, table, out, P, P, gx, gy, c, b,
+                       weight, ProjectClamp{lo, hi, clamp_mode});
+    return check_launch("tile_project");
+}
+
+extern "C" int diqt_volume_joint_consistent_tile_step(const float* y, const int* slot, const float* taps, const float* x_t,
+                                                      const float* x0_prev, const float* meas_up, const float* table, float* x_next,
+                                                      float* x0_out, int form, int N, int D, int H, int W, int P, int stride, int G0,
+                                                      int G1, int G2, int fz, int fy, int fx, float weight, float kx, float k0, float kp,
+                                                      float kn, float lo, float hi, int clamp_mode, unsigned long long seed,
+                                                      unsigned draw, unsigned sample, void* stream) {
+    DIQT_REQUIRE(table, DIQT_E_ALIGN, "volume_joint_consistent_tile_step: null pointer");
+    return joint_consistent_launch("volume_joint_consistent_tile_step", y, slot, taps, x_t, x0_prev, meas_up, table, x_next, x0_out, form,
+                                   N, D, H, W, P, stride, G0, G1, G2, fz, fy, fx, weight, kx, k0, kp, kn, lo, hi, clamp_mode, seed, draw,
+                                   sample, stream, false, 0.f, true);
 }
 
 extern "C" int diqt_volume_joint_heun(const float* y, const int* slot, const float* taps, float* xh, float* xn, float* x0, int phase, int N,

@@ -22,7 +22,8 @@ from . import ops
 from .graphs import GraphCache
 from .imagen_pytorch3D import (GaussianDiffusionContinuousTimes, Unet, NullUnet, exists, default, cast_tuple, identity, maybe,
                                normalize_neg_one_to_one, unnormalize_zero_to_one, eval_decorator, to_channels_last,
-                               to_channels_first, log_snr_to_alpha_sigma, check_consistency, naming_consistency_noise)
+                               to_channels_first, log_snr_to_alpha_sigma, check_consistency, check_consistency_operator,
+                               naming_consistency_noise)
 from .imagen_video import Unet3D
 
 Hparams_fields = ['num_sample_steps', 'sigma_min', 'sigma_max', 'sigma_data', 'rho', 'P_mean', 'P_std', 'S_churn', 'S_tmin',
@@ -418,7 +419,8 @@ class ElucidatedImagen(nn.Module):
     def one_unet_sample(self, unet, shape, *, unet_number, clamp=True, dynamic_threshold=True, cond_scale=1., use_tqdm=True,
                         inpaint_images=None, inpaint_masks=None, inpaint_resample_times=5, init_images=None,
                         skip_steps=None, sigma_min=None, sigma_max=None, noise=None, sampler='heun', sample_steps=None, eta=0.,
-                        consistency=None, consistency_weight=1., consistency_profile=None, consistency_noise=None, **kwargs):
+                        consistency=None, consistency_weight=1., consistency_profile=None, consistency_noise=None,
+                        consistency_operator=None, **kwargs):
         """Stochastic Heun sampler (:382-532).  ``noise``: optional injected list [init, step_0, ...], or a callable
         ``noise(shape) -> fp32 device tensor`` whose successive calls are those draws (one ``eps`` per step, also when gamma is 0).
 
@@ -447,12 +449,19 @@ class ElucidatedImagen(nn.Module):
         w_i = 0 (kn = 0: the last) skips the projection, one with shrink_i = 0 projects with w_i, and any other runs ONE
         ``ops.cell_project_noise``, which also reduces the step's normals in the range of A (into a new tensor).  The draws are
         unchanged.  ``ValueError`` naming "consistency_noise": without ``consistency``, not a finite number > 0, eta = 0 (no
-        stochastic step: use a constant ``consistency_weight``), and everything ``consistency`` refuses."""
+        stochastic step: use a constant ``consistency_weight``), and everything ``consistency`` refuses.
+        ``consistency_operator=A`` (with ``consistency``; ``ops.tile_operator``): every tile of ``cell`` voxels is measured by the
+        m x n matrix A (orthogonal stacks: ``ops.stack_operator``); ``consistency=(target_up, cell)`` then carries t = A+ y
+        (``ops.tile_backproject``) in state space and every ``ops.cell_project`` of the chain is one ``ops.tile_project``.
+        ``ValueError`` naming "consistency_operator": without ``consistency``, together with ``consistency_profile`` or
+        ``consistency_noise``, or an operator ``ops.tile_operator`` refuses."""
         self._check_sampler_args(sampler, sample_steps, skip_steps, eta)
         has_inpainting = self._check_inpaint_args(sampler, inpaint_images, inpaint_masks, inpaint_resample_times)
+        check_consistency_operator('one_unet_sample', consistency_operator, exists(consistency), consistency_profile,
+                                   consistency_noise)
         with naming_consistency_noise(consistency_noise):
             consistency = check_consistency('one_unet_sample', consistency, consistency_weight, shape, has_inpainting, init_images,
-                                            skip_steps, sampler, profile=consistency_profile)
+                                            skip_steps, sampler, profile=consistency_profile, operator=consistency_operator)
         if exists(consistency_noise):
             consistency_noise = ops.consistency_noise_sigma('one_unet_sample', consistency_noise, exists(consistency), eta != 0)
         consistency, table = (consistency[:3], consistency[3]) if exists(consistency) else (None, None)
@@ -460,7 +469,8 @@ class ElucidatedImagen(nn.Module):
             return self._dpmpp2m_sample(unet, shape, unet_number=unet_number, clamp=clamp, dynamic_threshold=dynamic_threshold,
                                         cond_scale=cond_scale, init_images=init_images, sigma_min=sigma_min, sigma_max=sigma_max,
                                         noise=noise, sample_steps=sample_steps, eta=eta, consistency=consistency,
-                                        consistency_profile=table, consistency_noise=consistency_noise, **kwargs)
+                                        consistency_profile=table, consistency_noise=consistency_noise,
+                                        tile=exists(consistency_operator), **kwargs)
         # Inpainting (:441-449, 473-530; RePaint, Lugmayr et al. 2022) is this loop with ``inpaint_resample_times`` passes per step,
         # r = R - 1 .. 0, where plain sampling has one: a pass draws ``eps``, pastes the known image under the mask and churns, runs the
         # two Heun evaluations as ever and -- unless r == 0 or it is the last step -- draws once more and re-noises,
@@ -526,10 +536,11 @@ class ElucidatedImagen(nn.Module):
         return self.unnormalize_img(images)
 
     def _dpmpp2m_sample(self, unet, shape, *, unet_number, clamp, dynamic_threshold, cond_scale, init_images, sigma_min, sigma_max, noise,
-                        sample_steps, eta, consistency=None, consistency_profile=None, consistency_noise=None, **kwargs):
+                        sample_steps, eta, consistency=None, consistency_profile=None, consistency_noise=None, tile=False, **kwargs):
         """``one_unet_sample(sampler='dpmpp2m')``; the arguments are checked there (``consistency``: None or the checked
         ``(meas_up, cell, weight)``, ``meas_up`` in state space; ``consistency_profile``: None or the checked host table of
-        ``ops.cell_profile``; ``consistency_noise``: None or the checked deviation in state space)."""
+        ``ops.cell_profile``; ``consistency_noise``: None or the checked deviation in state space; ``tile``: the table is a
+        ``consistency_operator``'s projector and ``meas_up`` its t)."""
         sigmas, coefs = self._dpmpp2m_tables(unet_number - 1, sample_steps, eta, sigma_min, sigma_max)
         schedule = None
         if exists(consistency_noise):                                           # once per chain, from the host table
@@ -554,7 +565,8 @@ class ElucidatedImagen(nn.Module):
             if exists(schedule) and weight > 0 and shrink > 0:                  # one launch: the projection and the shaped normals;
                 out, shaped = ops.cell_project_noise(out, meas_up, draw(), cell, weight, shrink, table)   # kn != 0 here: the step's draw
             elif exists(consistency) and weight > 0:                            # ``out`` arrives clamped or thresholded
-                out = ops.cell_project_profile(out, meas_up, cell, table, weight) if exists(table) else \
+                out = ops.tile_project(out, meas_up, cell, table, weight) if tile else \
+                    ops.cell_project_profile(out, meas_up, cell, table, weight) if exists(table) else \
                     ops.cell_project(out, meas_up, cell, weight)
             eps = shaped if exists(shaped) else draw() if stochastic[i] else None
             images = ops.multistep_sde_step(images, out, x_start, eps, k[i, 0], k[i, 1], k[i, 2], k[i, 3])
@@ -625,7 +637,7 @@ class ElucidatedImagen(nn.Module):
                batch_size=1, cond_scale=1., lowres_sample_noise_level=None, start_at_unet_number=1, start_image_or_video=None,
                stop_at_unet_number=None, return_all_unet_outputs=False, return_pil_images=False, use_tqdm=True, device=None,
                noise=None, sampler='heun', sample_steps=None, eta=0., consistency=None, consistency_weight=1.,
-               consistency_profile=None, consistency_noise=None):
+               consistency_profile=None, consistency_noise=None, consistency_operator=None):
         """:536-702.  ``noise``: optional injected list [lowres_noise, init, step_0, ...] per sampled unet (tests), or -- when exactly
         one U-Net is sampled -- a callable ``noise(shape) -> fp32 device tensor`` whose successive calls are those draws in that order
         (``inference.AnchoredNoise.source``: call k is draw k of the volume-anchored field).
@@ -649,7 +661,9 @@ class ElucidatedImagen(nn.Module):
         n outside 2 .. 64, a ``meas_up`` of another shape.  ``consistency_profile=(pz, py, px)``: ``one_unet_sample``'s slice profile;
         without ``consistency``, or one ``ops.cell_profile`` refuses, it is the same ``ValueError``.  ``consistency_noise=sigma``:
         ``one_unet_sample``'s, in the units of ``meas_up`` as passed here (it is multiplied by the slope of ``normalize_img``); every
-        refusal above then also names "consistency_noise", as do its own."""
+        refusal above then also names "consistency_noise", as do its own.  ``consistency_operator=A``: ``one_unet_sample``'s
+        tile-local linear measurement; ``consistency`` then carries t = A+ y in the units this returns, and its refusals name
+        "consistency_operator"."""
         assert texts is None and text_embeds is None and not return_pil_images
         samplers, steps_per_unet, etas = (cast_tuple(v, len(self.unets)) for v in (sampler, sample_steps, eta))
         for args in zip(samplers, steps_per_unet, cast_tuple(skip_steps, len(self.unets)), etas):
@@ -657,6 +671,7 @@ class ElucidatedImagen(nn.Module):
         sampled_samplers = samplers[start_at_unet_number - 1:default(stop_at_unet_number, len(self.unets))]
         has_inpainting = any([self._check_inpaint_args(s, inpaint_images, inpaint_masks, inpaint_resample_times)
                               for s in sampled_samplers or samplers[-1:]])
+        check_consistency_operator('sample', consistency_operator, exists(consistency), consistency_profile, consistency_noise)
         if exists(consistency_noise) and not exists(consistency):
             ops.consistency_noise_sigma('sample', consistency_noise, False)
         if exists(consistency_profile) and not exists(consistency):
@@ -669,7 +684,8 @@ class ElucidatedImagen(nn.Module):
                     check_consistency('sample', consistency, consistency_weight,
                                       (batch_size, self.channels, *frames[n - 1], self.image_sizes[n - 1], self.image_sizes[n - 1]),
                                       exists(inpaint_images), cast_tuple(init_images, len(self.unets))[n - 1],
-                                      cast_tuple(skip_steps, len(self.unets))[n - 1], samplers[n - 1], profile=consistency_profile)
+                                      cast_tuple(skip_steps, len(self.unets))[n - 1], samplers[n - 1], profile=consistency_profile,
+                                      operator=consistency_operator)
                 if exists(consistency_noise):
                     ops.consistency_noise_sigma('sample', consistency_noise, True, etas[n - 1] != 0)
             if exists(consistency_noise):                                          # into state space with the measurement: the map's slope
@@ -725,6 +741,8 @@ class ElucidatedImagen(nn.Module):
                     multistep.update(consistency_profile=consistency_profile)
                 if exists(consistency_noise):
                     multistep.update(consistency_noise=consistency_noise)
+                if exists(consistency_operator):
+                    multistep.update(consistency_operator=consistency_operator)
             inpaint = {}
             if has_inpainting:
                 inpaint = dict(inpaint_images=inpaint_images, inpaint_masks=inpaint_masks, inpaint_resample_times=inpaint_resample_times)

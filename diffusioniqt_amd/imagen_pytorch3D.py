@@ -1151,15 +1151,35 @@ class SRUnet256(Unet):
         super().__init__(*args, **{**default_kwargs, **kwargs})
 
 
+def check_consistency_operator(who, operator, has_consistency, profile=None, noise=None):
+    """The host rules of ``consistency_operator=`` beside its neighbours (``ValueError`` naming "consistency_operator"; nothing
+    touches the device): it rides on ``consistency``, whose first member then carries t = A+ y, and goes with neither
+    ``consistency_profile`` nor ``consistency_noise``."""
+    if operator is None:
+        return
+    if not has_consistency:
+        raise ValueError(f"{who}: consistency_operator needs consistency=(measurement, cell)")
+    if profile is not None:
+        raise ValueError(f"{who}: consistency_operator and consistency_profile are not offered together: a profile is the single row "
+                         f"u of a measurement; give the operator all its rows")
+    if noise is not None:
+        raise ValueError(f"{who}: consistency_operator and consistency_noise are not offered together (DDNM+ for a general A needs a "
+                         f"weight per singular direction)")
+
+
 def check_consistency(who, consistency, weight, shape, has_inpainting=False, init_images=None, skip_steps=None, sampler=None,
-                      profile=None):
+                      profile=None, operator=None):
     """The argument rules of ``consistency=(meas_up, cell)`` / ``consistency_weight`` of the one-call samplers of both families
     (``ValueError`` naming "consistency"; nothing touches the device).  ``shape`` = the [B,C,P,P,P] the sampler generates: ``meas_up``
     must be a float tensor of exactly that shape, the cell must divide P.  Data consistency (DDNM) replaces the cell means of every x0
     prediction by the measurement's; inpainting pastes known values into the state, ``init_images`` / ``skip_steps`` start or thin the
     chain elsewhere and the EDM Heun sampler has two predictions per step: none of them is offered with it.  ``profile`` =
     (pz, py, px), the slice profile of ``consistency_profile`` (``ops.cell_profile``'s rules; it needs ``consistency``).  Returns None
-    (off) or ``(meas_up, cell, weight, table)``, ``table`` None without a profile, else ``ops.cell_profile``'s host table."""
+    (off) or ``(meas_up, cell, weight, table)``, ``table`` None without a profile, else ``ops.cell_profile``'s host table.
+    ``operator`` = the ``consistency_operator`` (an [m, n] matrix or ``ops.tile_operator``'s object; with neither a profile nor
+    ``consistency_noise``, ``check_consistency_operator``): ``meas_up`` then carries t = A+ y and ``table`` is the operator's fp32
+    [n, n] projector, which ``ops.tile_project`` takes."""
+    check_consistency_operator(who, operator, consistency is not None, profile)
     if consistency is None:
         if profile is not None:
             raise ValueError(f"{who}: consistency_profile needs consistency=(meas_up, cell)")
@@ -1178,6 +1198,8 @@ def check_consistency(who, consistency, weight, shape, has_inpainting=False, ini
         got = f"{meas_up.dtype} {tuple(meas_up.shape)}" if torch.is_tensor(meas_up) else type(meas_up).__name__
         raise ValueError(f"{who}: the consistency measurement must be a float tensor of the sampled shape {tuple(shape)} (replicated "
                          f"onto the high-res grid, ops.cell_replicate), got {got}")
+    if operator is not None:
+        return meas_up, cell, weight, ops.tile_operator(cell, operator).table
     return meas_up, cell, weight, None if profile is None else ops.cell_profile(cell, profile)
 
 
@@ -1531,7 +1553,7 @@ class Imagen(nn.Module):
                       inpaint_masks=None, inpaint_resample_times=5, init_images=None, skip_steps=None, cond_scale=1,
                       pred_objective='noise', dynamic_threshold=True, use_tqdm=True, noise=None, sampler='ddpm',
                       sample_steps=None, eta=0.0, consistency=None, consistency_weight=1.0, consistency_profile=None,
-                      consistency_noise=None):
+                      consistency_noise=None, consistency_operator=None):
         """Ancestral sampler (:2059-2160).  Per step: one U-Net eval (HIP) + ONE fused posterior-step kernel;
         the per-step coefficients for all steps are computed on the host up front.  ``noise`` (optional) is a list
         [init, step_0, ...] of injected tensors with the reference's draw order (:2080, :2051), or a callable
@@ -1571,14 +1593,22 @@ class Imagen(nn.Module):
         ``ops.cell_project_noise`` replaces the projection launch -- it also reduces the step's normals in the range of A (into a new
         tensor: an injected noise tensor is never modified).  The draws are those of the chain without it.  ``ValueError`` naming
         "consistency_noise": without ``consistency``, not a finite number > 0, or a chain with no stochastic step (``'ddim'`` with
-        eta = 0, ``'dpmpp2m'``) -- use a constant ``consistency_weight`` there."""
+        eta = 0, ``'dpmpp2m'``) -- use a constant ``consistency_weight`` there.
+
+        ``consistency_operator=A`` (with ``consistency``; ``ops.tile_operator``): every tile of ``cell`` voxels is measured by the
+        m x n matrix A -- orthogonal thick-slice stacks (``ops.stack_operator``), a block-DCT low-pass, any rank.
+        ``consistency=(target_up, cell)`` then carries t = A+ y on the high-res grid (``ops.tile_backproject``) where it carried
+        ``meas_up``, and every ``ops.cell_project`` of the chain is one ``ops.tile_project``, x0' = x0 + w (t - P x0) with P = A+ A.
+        ``ValueError`` naming "consistency_operator": without ``consistency``, together with ``consistency_profile`` or
+        ``consistency_noise``, or an operator ``ops.tile_operator`` refuses."""
         if pred_objective not in ('noise', 'x_start', 'v'):
             raise ValueError(f'unknown objective {pred_objective}')
         has_inpainting = exists(inpaint_images) and exists(inpaint_masks)                  # (:2090-2091)
         self._check_sampler_args(sampler, sample_steps, skip_steps, eta, has_inpainting)
+        check_consistency_operator('p_sample_loop', consistency_operator, exists(consistency), consistency_profile, consistency_noise)
         with naming_consistency_noise(consistency_noise):
             consistency = check_consistency('p_sample_loop', consistency, consistency_weight, shape, has_inpainting, init_images,
-                                            skip_steps, profile=consistency_profile)
+                                            skip_steps, profile=consistency_profile, operator=consistency_operator)
         if exists(consistency_noise):
             consistency_noise = ops.consistency_noise_sigma('p_sample_loop', consistency_noise, exists(consistency),
                                                             not (sampler == 'dpmpp2m' or (sampler == 'ddim' and eta == 0)))
@@ -1646,7 +1676,9 @@ class Imagen(nn.Module):
                     pred, third = ops.cell_project_noise(pred, meas_up, third, cell, weight, shrink, table, clamp=(lo, hi, mode))
                     img, x_start = ops.ddpm_step(img, pred, third, coefs[i, 0], coefs[i, 1], coefs[i, 2], -inf, inf, 1)
                 elif exists(consistency) and weight > 0:                      # the clamp, then the projection; the step clamps no more
-                    if exists(table):
+                    if exists(consistency_operator):
+                        pred = ops.tile_project(pred, meas_up, cell, table, weight, clamp=(lo, hi, mode))
+                    elif exists(table):
                         pred = ops.cell_project_profile(pred, meas_up, cell, table, weight, clamp=(lo, hi, mode))
                     else:
                         pred = ops.cell_project(pred, meas_up, cell, weight, clamp=(lo, hi, mode))
@@ -1671,7 +1703,7 @@ class Imagen(nn.Module):
                cond_scale=1., lowres_sample_noise_level=None, start_at_unet_number=1, start_image_or_video=None,
                stop_at_unet_number=None, return_all_outputs=False, return_all_unet_outputs=None, return_pil_images=False,
                device=None, use_tqdm=True, noise=None, sampler='ddpm', sample_steps=None, eta=0.0, consistency=None,
-               consistency_weight=1.0, consistency_profile=None, consistency_noise=None):
+               consistency_weight=1.0, consistency_profile=None, consistency_noise=None, consistency_operator=None):
         """imagen_pytorch3D.py:2165-2274 -> (img, [noisy per step], [x0 per step]).  Accepts both spellings
         ``return_all_outputs`` / ``return_all_unet_outputs`` (test.py:182 uses the latter).  ``sampler`` / ``sample_steps`` / ``eta``
         (one value, or one per U-Net like ``skip_steps``) and the list or callable ``noise``: see ``p_sample_loop``, as for
@@ -1680,7 +1712,9 @@ class Imagen(nn.Module):
         ``init_images`` or ``skip_steps``, a weight outside (0, 1], a cell that does not divide the image size or with
         n outside 2 .. 64, a ``meas_up`` that is not [B,C,P,P,P]; also a ``consistency_profile`` (``p_sample_loop``) without
         ``consistency`` or one ``ops.cell_profile`` refuses.  ``consistency_noise=sigma`` (``p_sample_loop``; the units of ``meas_up``
-        as passed): every refusal above then also names "consistency_noise", as do its own."""
+        as passed): every refusal above then also names "consistency_noise", as do its own.  ``consistency_operator=A``
+        (``p_sample_loop``): a tile-local linear measurement; ``consistency`` then carries t = A+ y, and its refusals name
+        "consistency_operator"."""
         if exists(return_all_unet_outputs):
             return_all_outputs = return_all_unet_outputs
         num_unets = len(self.unets)
@@ -1688,6 +1722,7 @@ class Imagen(nn.Module):
         sampler, sample_steps, eta = (cast_tuple(v, num_unets) for v in (sampler, sample_steps, eta))
         for args in zip(sampler, sample_steps, skip_steps, eta):
             self._check_sampler_args(*args, exists(inpaint_images) and exists(inpaint_masks))
+        check_consistency_operator('sample', consistency_operator, exists(consistency), consistency_profile, consistency_noise)
         if exists(consistency_noise) and not exists(consistency):
             ops.consistency_noise_sigma('sample', consistency_noise, False)
         if exists(consistency_profile) and not exists(consistency):
@@ -1696,7 +1731,7 @@ class Imagen(nn.Module):
             with naming_consistency_noise(consistency_noise):
                 check_consistency('sample', consistency, consistency_weight, (batch_size, self.channels) + (self.image_sizes[n - 1],) * 3,
                                   exists(inpaint_images) and exists(inpaint_masks), cast_tuple(init_images, num_unets)[n - 1],
-                                  skip_steps[n - 1], profile=consistency_profile)
+                                  skip_steps[n - 1], profile=consistency_profile, operator=consistency_operator)
             if exists(consistency_noise):
                 ops.consistency_noise_sigma('sample', consistency_noise, True,
                                             not (sampler[n - 1] == 'dpmpp2m' or (sampler[n - 1] == 'ddim' and eta[n - 1] == 0)))
@@ -1726,7 +1761,8 @@ class Imagen(nn.Module):
                 cond_scale=unet_cond_scale, lowres_cond_img=lowres_cond_img, noise_scheduler=noise_scheduler,
                 pred_objective=pred_objective, dynamic_threshold=dynamic_threshold, use_tqdm=use_tqdm, noise=noise,
                 sampler=unet_sampler, sample_steps=unet_sample_steps, eta=unet_eta, consistency=consistency,
-                consistency_weight=consistency_weight, consistency_profile=consistency_profile, consistency_noise=consistency_noise)
+                consistency_weight=consistency_weight, consistency_profile=consistency_profile, consistency_noise=consistency_noise,
+                consistency_operator=consistency_operator)
             outputs.append(img)
             if exists(stop_at_unet_number) and stop_at_unet_number == unet_number:
                 break

@@ -119,6 +119,21 @@ blend modes hand on as ``consistency_noise=``; ``joint=True`` multiplies it by t
 state_space(1) - state_space(0), and dispatches per step: weight 0 the family's plain launch, shrink 0 the consistent launch,
 otherwise ``ops.volume_joint_consistent_noise_step`` -- one launch per step as before, the same draws.  Deterministic chains (ddim with
 eta = 0, dpmpp2m without eta) and the Heun sampler are refused; sigma is given, not estimated.
+
+A tile-local linear operator (``consistency_operator=A``, with ``consistency``) is the general case: the volume splits into disjoint
+tiles of ``cell`` voxels and every tile is measured by the same m x n matrix A, any number of rows, any rank -- two or three
+orthogonal thick-slice stacks of one anatomy (``ops.stack_operator``; ``ops.stack_rows`` lays the stack volumes out as the
+[m, D/fz, H/fy, W/fx] measurement), a block-DCT low-pass, a partial-volume model.  ``ops.tile_operator`` validates A and makes, in
+float64, A+ and the n x n orthogonal projector P = A+ A (fp32 table, symmetric to the bit); ``ops.tile_measure`` is A and simulates the
+acquisition.  The projection is x0' = x0 + w (t - P x0) with t = A+ y (``ops.tile_backproject``, once per volume), a volume on the
+high-res grid where the replicated measurement stood: the constant must lie in the row space of A (P 1 = 1, checked), so t passes
+through the z-score and ``state_space`` as a plain volume, and the window gathers, the covered rule (ALL n voxels of a tile) and the
+divisibility rules are those above.  The crop and blend modes hand windows of t and ``consistency_operator=`` on to the sampler
+(``ops.tile_project`` per step); ``joint=True`` launches ``ops.volume_joint_consistent_tile_step``, as many launches as before.  At
+w = 1 the corrected prediction satisfies P x0' = t (to fp32 rounding), which is A x0' = y when y lies in the range of A; stacks that
+contradict each other are fitted in the least-squares sense.  Not offered: an operator that crosses tile borders (true k-space
+truncation, overlapping slice profiles), ``consistency_profile`` or ``consistency_noise`` together with an operator, the Heun sampler,
+consistency together with inpainting; the stacks are taken as registered to each other and A as known.
 """
 from types import SimpleNamespace
 
@@ -126,7 +141,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .imagen_pytorch3D import naming_consistency_noise
+from .imagen_pytorch3D import check_consistency_operator, naming_consistency_noise
 from .metrics import MSSIM, PSNR
 from .utils_mine import convertVolume2subVolume, merge_sub_volumes
 
@@ -297,9 +312,10 @@ class VolumeInference:
         return known.float(), mask
 
     @staticmethod
-    def _check_consistency(consistency, weight, inpaint, joint, sample_fn):
+    def _check_consistency(consistency, weight, inpaint, joint, sample_fn, rows=False):
         """The argument rules of ``consistency`` (``ValueError`` naming "consistency"; nothing touches the device).  Returns None or
-        (measurement fp32, cell, weight), the tensor on the host or the device as it was given."""
+        (measurement fp32, cell, weight), the tensor on the host or the device as it was given.  ``rows``: a ``consistency_operator``
+        is given and the measurement is [m, D/fz, H/fy, W/fx], one volume per row of the operator."""
         if consistency is None:
             return None
         if not isinstance(consistency, (tuple, list)) or len(consistency) != 2:
@@ -309,7 +325,10 @@ class VolumeInference:
         meas, cell = consistency
         cell, weight = ops.consistency_cell("VolumeInference", cell, weight)
         meas = torch.as_tensor(meas)
-        if meas.ndim != 3 or not meas.is_floating_point():
+        if rows and (meas.ndim != 4 or not meas.is_floating_point()):
+            raise ValueError(f"VolumeInference: with consistency_operator the consistency measurement must be a float "
+                             f"[m, D/fz, H/fy, W/fx] tensor, one volume per row of the operator, got {meas.dtype} {tuple(meas.shape)}")
+        if not rows and (meas.ndim != 3 or not meas.is_floating_point()):
             raise ValueError(f"VolumeInference: the consistency measurement must be a float [D/fz, H/fy, W/fx] tensor, got {meas.dtype} "
                              f"{tuple(meas.shape)}")
         if joint and getattr(sample_fn, 'heun', False):
@@ -323,6 +342,9 @@ class VolumeInference:
     def _consistency_volume(self, win):
         """The measurement on the high-res grid, z-scored like the low-res volume, on the volume's device: fp32 [D,H,W]."""
         meas, cell, _ = self.consistency                     # ``__call__`` has checked its shape
+        if self.consistency_op is not None:                  # t = A+ y, made once per volume: P 1 = 1, so the z-score of t is the t of
+            t = ops.tile_backproject(meas.to(win.device).contiguous(), self.consistency_op)    # the z-scored acquisition
+            return ((t - self.mean) / self.std).contiguous()
         return ((ops.cell_replicate(meas.to(win.device), cell) - self.mean) / self.std).contiguous()
 
     def _consistency_windows(self, cw):
@@ -332,6 +354,8 @@ class VolumeInference:
             kw.update(consistency_profile=self.consistency_profile)
         if self.consistency_noise is not None:               # z-scored like the measurement the sampler gets
             kw.update(consistency_noise=self.consistency_noise / self.std)
+        if self.consistency_op is not None:
+            kw.update(consistency_operator=self.consistency_op)
         return kw
 
     def _inpaint_volumes(self, win):
@@ -345,7 +369,7 @@ class VolumeInference:
 
     def __init__(self, configs, sample_fn, nonzero_ratio=0.05, blend=None, sigma_scale=0.125, samples=1, noise=None, seed=0, joint=False,
                  inpaint=None, inpaint_resample_times=5, consistency=None, consistency_weight=1.0, consistency_profile=None,
-                 consistency_noise=None):
+                 consistency_noise=None, consistency_operator=None):
         """``sample_fn(lr_patches [B,1,S,S,S]) -> hr_patches`` — e.g. ``lambda x: trainer.sample(batch_size=x.shape[0],
         start_image_or_video=x, start_at_unet_number=2)[0]`` (test_all.py:234).  ``blend`` / ``sigma_scale`` / ``samples``: weighted
         overlap blending and multi-sample statistics, see the module docstring.  ``noise='anchored'`` (with ``seed``): every call
@@ -390,10 +414,28 @@ class VolumeInference:
         docstring).  Every step projects with its own weight, capped by ``consistency_weight``, and shapes its fresh noise; the last
         step is unprojected.  The crop and blend modes hand ``consistency_noise=sigma / std`` on to the sampler; ``joint=True``
         dispatches per step inside the chain.  ``ValueError`` naming "consistency_noise" before anything touches the device: without
-        ``consistency``, a bool, a non-number, a non-finite or non-positive value, a joint denoiser with no stochastic step."""
+        ``consistency``, a bool, a non-number, a non-finite or non-positive value, a joint denoiser with no stochastic step.
+
+        ``consistency_operator=A`` (with ``consistency``): a tile-local linear measurement (module docstring) -- ``A`` an [m, n]
+        matrix or what ``ops.tile_operator`` / ``ops.stack_operator`` return; the measurement of ``consistency=(y, cell)`` is then
+        [m, D/fz, H/fy, W/fx] in raw units (``ops.stack_rows`` lays stacks out so, ``ops.tile_measure`` simulates them).
+        t = A+ y is made once per volume and z-scored; the crop and blend modes hand windows of t and ``consistency_operator=`` on to
+        the sampler, ``joint=True`` launches ``ops.volume_joint_consistent_tile_step``.  ``ValueError`` naming
+        "consistency_operator" before anything touches the device: without ``consistency``, together with ``consistency_profile``
+        (a profile is one row of an operator) or ``consistency_noise``, a measurement whose leading dimension is not m, and
+        whatever ``ops.tile_operator`` refuses."""
+        check_consistency_operator("VolumeInference", consistency_operator, consistency is not None, consistency_profile,
+                                   consistency_noise)
         with naming_consistency_noise(consistency_noise):    # it rides on consistency: what that refuses names it too
             self.inpaint = self._check_inpaint(inpaint, inpaint_resample_times, joint, sample_fn)
-            self.consistency = self._check_consistency(consistency, consistency_weight, self.inpaint, joint, sample_fn)
+            self.consistency = self._check_consistency(consistency, consistency_weight, self.inpaint, joint, sample_fn,
+                                                       consistency_operator is not None)
+            self.consistency_op = None
+            if consistency_operator is not None:
+                self.consistency_op = ops.tile_operator(self.consistency[1], consistency_operator)
+                if self.consistency[0].shape[0] != self.consistency_op.m:
+                    raise ValueError(f"VolumeInference: the consistency_operator has m = {self.consistency_op.m} rows, the consistency "
+                                     f"measurement {tuple(self.consistency[0].shape)} has {self.consistency[0].shape[0]} volumes")
             if consistency_profile is not None and self.consistency is None:
                 raise ValueError("VolumeInference: consistency_profile needs consistency=(measurement, cell)")
             # the profile as given (what a sampler call takes) and its host table (what the fused launch takes, moved once per volume)
@@ -465,7 +507,7 @@ class VolumeInference:
             raise ValueError(f"VolumeInference: the inpaint volumes {tuple(self.inpaint[0].shape)} are not the volume's shape "
                              f"{tuple(lowres_raw.shape)}")
         if self.consistency is not None and \
-                tuple(s * f for s, f in zip(self.consistency[0].shape, self.consistency[1])) != tuple(lowres_raw.shape):
+                tuple(s * f for s, f in zip(self.consistency[0].shape[-3:], self.consistency[1])) != tuple(lowres_raw.shape):
             with naming_consistency_noise(self.consistency_noise):
                 raise ValueError(f"VolumeInference: the consistency measurement {tuple(self.consistency[0].shape)} times the cell "
                                  f"{self.consistency[1]} is not the volume's shape {tuple(lowres_raw.shape)}")
@@ -569,6 +611,8 @@ class VolumeInference:
         if self.consistency is not None:
             win.meas_up = self.sample_fn.state_space(self._consistency_volume(win)).contiguous()
         win.table = None if self.consistency_table is None else self.consistency_table.to(win.device)
+        if self.consistency_op is not None:                  # the operator's projector in the table's place (never both)
+            win.table = self.consistency_op.table.to(win.device)
         win.noise_schedule = None                            # per step (w_i, shrink_i) in fp32, made once per volume on the host
         if self.consistency_noise is not None:
             unit = self.sample_fn.state_space(torch.tensor([0., 1.], dtype=torch.float64))
@@ -645,7 +689,11 @@ class VolumeInference:
                 form = 2 if den.sigma_space else 1 if den.multistep else 0
                 kx, k0, k2, k3 = (*den.coefs[i], 0.)[:4]     # rows (kx, k0, kn), (kx, k0, kp) or (kx, k0, kp, kn)
                 draw = den.draw_base + 1 + i if den.sigma_space else i + 1
-                if win.table is not None:
+                if self.consistency_op is not None:
+                    ops.volume_joint_consistent_tile_step(*head, prev, win.meas_up, self.consistency[1], win.table, weight, form, kx,
+                                                          k0, 0. if form == 0 else k2, k2 if form == 0 else k3, *tail, self.seed,
+                                                          draw=draw, sample=s, **io)
+                elif win.table is not None:
                     ops.volume_joint_consistent_profile_step(*head, prev, win.meas_up, self.consistency[1], win.table,
                                                              weight, form, kx, k0, 0. if form == 0 else k2,
                                                              k2 if form == 0 else k3, *tail, self.seed, draw=draw, sample=s, **io)

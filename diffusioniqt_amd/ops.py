@@ -2928,6 +2928,212 @@ def volume_joint_consistent_profile_step(y, slot, taps, x_t, x0_prev, meas_up, c
     return out, x0_out
 
 
+class TileOperator:
+    """What ``tile_operator`` returns: ``cell`` = (fz, fy, fx); ``A`` [m, n] and ``pinv`` = A+ [n, m], float64 host tensors; ``table``
+    the fp32 host [n, n] projector P = A+ A, symmetric to the bit, which the projecting kernels read; ``rank``; ``gain`` =
+    max_q sum_r |P[q][r]| over the fp32 table (float), the factor of the rounding bounds; ``m`` and ``n``."""
+
+    def __init__(self, cell, A, pinv, table, rank, gain):
+        self.cell, self.A, self.pinv, self.table, self.rank, self.gain = cell, A, pinv, table, rank, gain
+        self.m, self.n = A.shape
+
+    def __repr__(self):
+        return f"TileOperator(cell={self.cell}, m={self.m}, rank={self.rank}, gain={self.gain:.3g})"
+
+
+def tile_projector(A):
+    """float64 ``(A+, P, rank)`` of a finite [m, n] matrix by its SVD (host): a singular value counts as zero at or below
+    1e-10 s_max; one in (1e-10, 1e-6) s_max leaves the rank ambiguous and is refused, as is rank 0 (``ValueError`` naming
+    "consistency_operator").  P = A+ A symmetrised, (P + P^T) / 2: the orthogonal projector onto the row space of A."""
+    who = "tile_operator (consistency_operator)"
+    U, S, Vh = torch.linalg.svd(A, full_matrices=False)
+    smax = float(S[0]) if S.numel() else 0.0
+    if not smax > 0.0:
+        raise ValueError(f"{who}: the operator has rank 0")
+    rel = S / smax
+    if bool(((rel > 1e-10) & (rel < 1e-6)).any()):
+        raise ValueError(f"{who}: a singular value of {float(rel[(rel > 1e-10) & (rel < 1e-6)][0]):.3g} s_max leaves the rank "
+                         f"ambiguous (zero is <= 1e-10 s_max, a real one >= 1e-6 s_max)")
+    keep = rel > 1e-10
+    pinv = (Vh[keep].T / S[keep]) @ U[:, keep].T
+    proj = pinv @ A
+    return pinv.contiguous(), (proj + proj.T) / 2, int(keep.sum())
+
+
+def tile_operator(cell, A):
+    """The host side of a tile-local linear measurement for the ``consistency_operator`` modes (``ValueError`` naming
+    "consistency_operator"; nothing touches the device).  The volume splits into disjoint tiles of ``cell`` = (fz, fy, fx) voxels and
+    every tile is measured by ``A``, array-like [m, n], finite, m >= 1, n = fz fy fx in 2 .. 64, its columns in lexicographic
+    (z, y, x) order q = (i fy + j) fx + k.  float64: ``tile_projector``, then the fp32 table.  Refused besides: an operator blind to
+    the tile mean, max |P 1 - 1| > 1e-9 -- with 1 in the row space, A+(a y + b A 1) = a t + b 1, so the back-projected measurement t
+    passes through the z-score and the denoiser's affine ``state_space`` map as a plain volume (a pseudo-inverse of this size is
+    accurate to about 1e-13; an operator that misses the constant misses it by O(1 / n) >= 1 / 64).  A single row with a slice
+    profile is such an operator: that is ``consistency_profile``.  A ``TileOperator`` of the same cell is returned as it is."""
+    who = "tile_operator (consistency_operator)"
+    cell, _ = consistency_cell(who, cell)
+    if isinstance(A, TileOperator):
+        if A.cell != cell:
+            raise ValueError(f"{who}: the operator was made for the cell {A.cell}, not {cell}")
+        return A
+    n = cell[0] * cell[1] * cell[2]
+    try:
+        A = torch.as_tensor(A, dtype=torch.float64).detach().cpu().contiguous()     # a list is read as float64, not through fp32
+    except (TypeError, ValueError, RuntimeError):
+        raise ValueError(f"{who}: the operator must be an [m, {n}] array of numbers, got {type(A).__name__}") from None
+    if A.ndim != 2 or A.shape[0] < 1 or A.shape[1] != n:
+        raise ValueError(f"{who}: the operator must be [m, {n}] with m >= 1 (the cell {cell} has n = {n} voxels), got {tuple(A.shape)}")
+    if not bool(torch.isfinite(A).all()):
+        raise ValueError(f"{who}: the operator must be finite")
+    pinv, proj, rank = tile_projector(A)
+    miss = float((proj.sum(1) - 1.0).abs().max())
+    if miss > 1e-9:
+        raise ValueError(f"{who}: the operator is blind to the tile mean (max |P 1 - 1| = {miss:.3g}): the constant must lie in its "
+                         f"row space; a single row with a slice profile is consistency_profile, not an operator")
+    table = proj.to(torch.float32).contiguous()
+    return TileOperator(cell, A, pinv, table, rank, float(table.double().abs().sum(1).max()))
+
+
+def stack_operator(cell, axes):
+    """The ``tile_operator`` of orthogonal thick-slice stacks: for each axis of ``axes`` (distinct values of 0, 1, 2, in that order)
+    one row per line of the tile along that axis -- the lines in lexicographic order of their other two coordinates -- with weight
+    1 / f_axis on the line's voxels: a stack with thick slices along that axis and full resolution in plane."""
+    who = "stack_operator (consistency_operator)"
+    cell, _ = consistency_cell(who, cell)
+    if not isinstance(axes, (tuple, list)) or not axes or len(set(axes)) != len(axes) or any(
+            isinstance(a, bool) or a not in (0, 1, 2) for a in axes):
+        raise ValueError(f"{who}: axes must be distinct values of 0, 1, 2, got {axes!r}")
+    n = cell[0] * cell[1] * cell[2]
+    q = torch.arange(n).reshape(cell)
+    rows = []
+    for a in axes:
+        for line in q.movedim(a, -1).reshape(-1, cell[a]):
+            r = torch.zeros(n, dtype=torch.float64)
+            r[line] = 1.0 / cell[a]
+            rows.append(r)
+    return tile_operator(cell, torch.stack(rows))
+
+
+def stack_rows(stacks, cell, axes):
+    """The stack volumes a user has as the [m, D/fz, H/fy, W/fx] measurement of ``stack_operator(cell, axes)``: ``stacks[i]`` is the
+    volume of ``axes[i]``, [D,H,W] with that axis divided by its factor ([D/fz, H, W] for axis 0, ...).  A pure reshape and
+    permute."""
+    who = "stack_rows (consistency_operator)"
+    cell, _ = consistency_cell(who, cell)
+    if not isinstance(stacks, (tuple, list)) or not isinstance(axes, (tuple, list)) or len(stacks) != len(axes) or not stacks or any(
+            isinstance(a, bool) or a not in (0, 1, 2) for a in axes) or not all(torch.is_tensor(v) and v.ndim == 3 for v in stacks):
+        raise ValueError(f"{who}: one [.,.,.] tensor per axis of {axes!r} (values of 0, 1, 2)")
+    full = tuple(s * (cell[b] if b == axes[0] else 1) for b, s in enumerate(stacks[0].shape))      # the volume the stacks were cut from
+    out = []
+    for vol, a in zip(stacks, axes):
+        want = tuple(s // cell[a] if b == a else s for b, s in enumerate(full))
+        if any(s % f for s, f in zip(full, cell)) or tuple(vol.shape) != want:
+            raise ValueError(f"{who}: the stack of axis {a} must be {want} (the volume {full}, the cell {cell}), got {tuple(vol.shape)}")
+        # [D/fz, i, H/fy, j, W/fx, k] with the stack's own axis of length 1, then the in-tile coordinates in front
+        dims = [d for s, f in zip(full, cell) for d in (s // f, f)]
+        dims[2 * a + 1] = 1
+        out.append(vol.reshape(dims).permute(1, 3, 5, 0, 2, 4).reshape(-1, *dims[0::2]))
+    return torch.cat(out).contiguous()
+
+
+def _tile_volume(who, vol, operator):
+    _chk(vol)
+    if not isinstance(operator, TileOperator):
+        raise ValueError(f"{who}: operator must be what ops.tile_operator returns (consistency_operator), got {type(operator).__name__}")
+    return operator.cell
+
+
+def tile_measure(vol, operator):
+    """The measurement of a [D,H,W] volume under a tile operator (include/diqt.h, diqt_tile_measure): fp32 [m, D/fz, H/fy, W/fx],
+    row r of A applied to every tile, the sum fused-multiply-added in (z, y, x) order with A rounded to fp32 -- it simulates the
+    acquisition.  One launch."""
+    who = "tile_measure"
+    cell = _tile_volume(who, vol, operator)
+    if vol.ndim != 3 or not vol.is_contiguous() or vol.numel() == 0:
+        raise ValueError(f"{who}: vol must be a non-empty contiguous [D,H,W] tensor, got {tuple(vol.shape)}")
+    consistency_cell(who, cell, 1.0, [(s, a) for a, s in enumerate(vol.shape)])
+    out = torch.empty((operator.m, *(s // f for s, f in zip(vol.shape, cell))), dtype=torch.float32, device=vol.device)
+    _lib.call("diqt_tile_measure", vol, operator.A.to(vol.device, torch.float32).contiguous(), out, operator.m, *vol.shape, *cell, _stream())
+    return out
+
+
+def tile_backproject(y, operator):
+    """t = A+ y on the high-res grid (include/diqt.h, diqt_tile_backproject): ``y`` fp32 [m, D/fz, H/fy, W/fx] as ``tile_measure``
+    or ``stack_rows`` lay it out, the result fp32 [D,H,W] -- what the ``consistency_operator`` kernels read where the replicated
+    measurement stood.  A+ rounded to fp32, the sum fused-multiply-added in row order.  One launch."""
+    who = "tile_backproject"
+    cell = _tile_volume(who, y, operator)
+    if y.ndim != 4 or y.shape[0] != operator.m or not y.is_contiguous() or y.numel() == 0:
+        raise ValueError(f"{who}: y must be a non-empty contiguous [{operator.m}, D/fz, H/fy, W/fx] tensor (consistency_operator: one "
+                         f"value per row of the operator and tile), got {tuple(y.shape)}")
+    shape = tuple(s * f for s, f in zip(y.shape[1:], cell))
+    out = torch.empty(shape, dtype=torch.float32, device=y.device)
+    _lib.call("diqt_tile_backproject", y, operator.pinv.to(y.device, torch.float32).contiguous(), out, operator.m, *shape, *cell, _stream())
+    return out
+
+
+def _tile_table(who, table, cell, like):
+    """The check of a ``tile_operator`` table handed to a kernel: fp32 [n, n], contiguous, on ``like``'s device."""
+    n = cell[0] * cell[1] * cell[2]
+    if not torch.is_tensor(table) or table.dtype != torch.float32 or tuple(table.shape) != (n, n) or not table.is_contiguous():
+        raise ValueError(f"{who}: the consistency_operator table must be a contiguous fp32 [{n}, {n}] tensor (ops.tile_operator), got "
+                         f"{(table.dtype, tuple(table.shape)) if torch.is_tensor(table) else type(table).__name__}")
+    if table.device != like.device:
+        raise ValueError(f"{who}: the consistency_operator table is on {table.device}, the data on {like.device}")
+    _chk(table)
+
+
+def tile_project(x0, target, cell, table, weight=1.0, clamp=None, out=None):
+    """``cell_project`` for a tile operator (include/diqt.h, diqt_tile_project): ``target`` [B,C,P,P,P] = windows of the
+    back-projected measurement t = A+ y, ``table`` [n, n] = ``tile_operator``'s P, on ``x0``'s device.  a = clamp(x0); per tile
+    out = a + weight (t - P a): at weight 1, P out = t, and A out = y for a y in the range of A.  Everything else -- shapes,
+    ``clamp``, ``out`` -- as there.  Returns ``out``.  One launch."""
+    who = "tile_project"
+    _chk(x0, target, out)
+    if x0.ndim != 5 or x0.numel() == 0 or len(set(x0.shape[2:])) != 1:
+        raise ValueError(f"{who}: x0 must be a non-empty [B,C,P,P,P] tensor of cubes, got {tuple(x0.shape)}")
+    if out is None:
+        out = torch.empty_like(x0)
+    for t, name in ((target, 'target'), (out, 'out')):
+        if t.shape != x0.shape:
+            raise ValueError(f"{who}: {name} must have x0's shape {tuple(x0.shape)}, got {tuple(t.shape)}")
+    if not (x0.is_contiguous() and target.is_contiguous() and out.is_contiguous()):
+        raise RuntimeError(f"{who}: tensors must be contiguous")
+    P = x0.shape[2]
+    cell, weight = consistency_cell(who, cell, weight, [(P, a) for a in range(3)])
+    _tile_table(who, table, cell, x0)
+    lo, hi, mode = (0., 0., 2) if clamp is None else clamp                # the entry's third mode: no clamp
+    if clamp is not None and int(mode) not in (0, 1):
+        raise ValueError(f"{who}: clamp mode must be 0 (min) or 1 (box), got {mode!r}")
+    _lib.call("diqt_tile_project", x0, target, table, out, x0.shape[0] * x0.shape[1], P, *cell, weight, float(lo), float(hi), int(mode),
+              _stream())
+    return out
+
+
+def volume_joint_consistent_tile_step(y, slot, taps, x_t, x0_prev, meas_up, cell, table, weight, form, kx, k0, kp, kn, lo, hi,
+                                      clamp_mode, stride, seed=0, draw=0, sample=0, out=None, x0_out=None):
+    """``volume_joint_consistent_step`` for a tile operator (include/diqt.h, diqt_volume_joint_consistent_tile_step): ``meas_up``
+    [D,H,W] = the back-projected measurement t in state space, ``table`` [n, n] = ``tile_operator``'s P, on ``x_t``'s device.  Every
+    tile whose voxels are ALL covered has its fused x0 moved to x0 + ``weight`` (t - P x0) before the update; everything else as
+    there.  Returns ``(out, x0_out)``.  One launch, bit-reproducible."""
+    who = "volume_joint_consistent_tile_step"
+    form = int(form)
+    if form not in (0, 1, 2):
+        raise ValueError(f"{who}: form must be 0 (first order), 1 (multistep) or 2 (multistep with noise), got {form!r}")
+    N, P, stride = _joint_windows(who, y, slot, taps, x_t, clamp_mode, stride)
+    seed, draw, sample = _noise_key(who, seed, draw, sample)
+    _joint_slots(who, slot, N)
+    cell, weight = consistency_cell(who, cell, weight, [(s, a) for a, s in enumerate(x_t.shape)])
+    _chk(meas_up)
+    if meas_up.shape != x_t.shape or not meas_up.is_contiguous():
+        raise ValueError(f"{who}: meas_up must be a contiguous tensor of x_t's shape")
+    _tile_table(who, table, cell, x_t)
+    out, x0_out = _joint_volumes(who, x_t, None if form == 0 else x0_prev, out, x0_out)
+    _lib.call("diqt_volume_joint_consistent_tile_step", y if N else None, slot, taps, x_t, None if form == 0 else x0_prev, meas_up,
+              table, out, x0_out, form, N, *x_t.shape, P, stride, *slot.shape, *cell, weight, float(kx), float(k0), float(kp), float(kn),
+              float(lo), float(hi), int(clamp_mode), seed, draw, sample, _stream())
+    return out, x0_out
+
+
 def consistency_noise_sigma(who, sigma_y, has_consistency=True, stochastic=True):
     """The host rules of ``consistency_noise=`` (``ValueError`` naming "consistency_noise"; nothing touches the device): it rides on
     ``consistency``, is a finite number > 0 (0 would leave the last step's 0 / 0 undefined; "off" is None) and needs a chain with a

@@ -803,6 +803,35 @@ int diqt_volume_joint_consistent_noise_step(const float* y, const int* slot, con
                                             int D, int H, int W, int P, int stride, int G0, int G1, int G2, int fz, int fy, int fx,
                                             float weight, float shrink, float kx, float k0, float kp, float kn, float lo, float hi,
                                             int clamp_mode, unsigned long long seed, unsigned draw, unsigned sample, void* stream);
+/* Data consistency for a TILE-LOCAL LINEAR OPERATOR (ops.tile_operator): the volume splits into disjoint tiles of (fz, fy, fx) voxels,
+ * n = fz fy fx in 2 .. 64, and every tile is measured by the same m x n matrix A, m >= 1 rows of any rank (orthogonal thick-slice
+ * stacks, a block-DCT low-pass, a partial-volume model).  x0' = x0 + w A+(y - A x0) = x0 + w (t - P x0) with t = A+ y on the high-res
+ * grid and P = A+ A, the n x n orthogonal projector onto the row space of A.  `table` is device fp32 [n][n] = P, symmetric to the bit
+ * (the caller's: ops.tile_operator makes it on the host).  The projection of the values a of one tile, in fp32 with no contraction, ONE
+ * definition for the two projecting entries; q, r = lexicographic (z, y, x) indices inside the tile:
+ *     s = 0;  s = fmaf(P[r][q], a[r], s) for r = 0 .. n - 1;  a'[q] = fmaf(w, t[q] - s, a[q])
+ * The error codes are those of the cell entries (null pointer, n outside 2 .. 64 or a weight outside (0, 1], a cell that does not
+ * divide the volume, m < 1 is DIQT_E_SHAPE).
+ *
+ * diqt_tile_measure: out [m][D / fz][H / fy][W / fx] = A applied to every tile of x [D][H][W], A device fp32 [m][n]:
+ * s = fmaf(A[row][r], x[r], s) in the order of r.  diqt_tile_backproject: out [D][H][W] = t = A+ y, y as diqt_tile_measure writes it,
+ * Ap device fp32 [n][m]: s = fmaf(Ap[q][row], y[row], s) in row order.  Neither output may alias an input.                          */
+int diqt_tile_measure(const float* x, const float* A, float* out, int m, int D, int H, int W, int fz, int fy, int fx, void* stream);
+int diqt_tile_backproject(const float* y, const float* Ap, float* out, int m, int D, int H, int W, int fz, int fy, int fx, void* stream);
+/* diqt_cell_project's cubes, clamp modes and aliasing (out may alias x0; target and table may not alias out) with that arithmetic:
+ * a = clamp(x0), then the projection onto `target` = t.  A block stages whole tiles in LDS (at most 16 KiB of values and 16 KiB of
+ * table) and every voxel has a thread.                                                                                              */
+int diqt_tile_project(const float* x0, const float* target, const float* table, float* out, size_t cubes, int P, int fz, int fy, int fx,
+                      float weight, float lo, float hi, int clamp_mode, void* stream);
+/* diqt_volume_joint_consistent_step with that arithmetic between the fuse and the update, meas_up = t: the forms, the window walk, the
+ * normals, the aliasing rules and the error codes are its own, and a tile is corrected only when ALL n of its voxels are covered.  The
+ * table rides in LDS behind the box (n^2 floats, at most 16 KiB; a plan above 64 KiB is DIQT_E_SHAPE).  With stride = P and unit taps
+ * the chain is diqt_tile_project followed by the per-window step, bit for bit.                                                      */
+int diqt_volume_joint_consistent_tile_step(const float* y, const int* slot, const float* taps, const float* x_t, const float* x0_prev,
+                                           const float* meas_up, const float* table, float* x_next, float* x0_out, int form, int N, int D,
+                                           int H, int W, int P, int stride, int G0, int G1, int G2, int fz, int fy, int fx, float weight,
+                                           float kx, float k0, float kp, float kn, float lo, float hi, int clamp_mode,
+                                           unsigned long long seed, unsigned draw, unsigned sample, void* stream);
 /* The stochastic Heun sampler of the EDM family (Karras et al. 2022; elucidated_imagen.py:382-532) on the joint state: a churn, a
  * predictor and a corrector per step, two U-Net evaluations.  The state is three [D][H][W] volumes, all updated in place (every thread
  * reads only its own voxel of each, then writes it): xh = images_hat, xn = images_next, x0 = the fused prediction.  Window walk,
