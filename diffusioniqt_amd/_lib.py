@@ -44,6 +44,8 @@ PROTOTYPES = {
     "diqt_conv3d_direct_bwd_weight_ws": (I, [P, P, P, P, P, Z] + [I] * 19 + [P]),
     "diqt_reduce_workspace_bytes": (Z, [I, I]),
     "diqt_groupnorm_stats": (I, [P, P, P, P, Z, I, I, I, I, F, P]),
+    "diqt_colreduce_route": (I, [I, I, I]),
+    "diqt_gn_apply_route": (I, [I, I, I, I, I]),
     "diqt_gn_act_fwd": (I, [P, P, P, P, P, P, P, I, P, I, I, I, I, I, P]),
     "diqt_gn_act_fwd_h": (I, [P, P, P, P, P, P, P, I, P, I, I, I, I, I, I, I, P]),
     "diqt_gn_act_bwd": (I, [P, P, P, P, P, P, P, P, I, P, P, P, P, P, P, Z, I, I, I, I, I, P]),
@@ -109,6 +111,7 @@ PROTOTYPES = {
     "diqt_ema_lerp": (I, [P, P, Z, F, P]),
     "diqt_softmax_fwd": (I, [P, P, Z, I, I, F, P]),
     "diqt_softmax_bwd": (I, [P, P, P, Z, I, I, F, P]),
+    "diqt_softmax_route": (I, [Z, I, I, I]),
     "diqt_space_to_depth_nd": (I, [P, P] + [I] * 8 + [P]),
     "diqt_depth_to_space_nd": (I, [P, P] + [I] * 8 + [P]),
     "diqt_transpose_mid": (I, [P, P, I, I, I, I, P]),

@@ -19,6 +19,13 @@ __device__ __forceinline__ float4 ld4_any(const void* p, size_t i, int ty) {
     const h2v a = __builtin_bit_cast(h2v, ux), b = __builtin_bit_cast(h2v, uy);
     return make_float4((float)a[0], (float)a[1], (float)b[0], (float)b[1]);
 }
+// one element of such a tensor (the scalar path of colreduce_kernel: C > 1024 with a 16-bit x or dy)
+__device__ __forceinline__ float ld1_any(const void* p, size_t i, int ty) {
+    if (ty == 0) return static_cast<const float*>(p)[i];
+    const unsigned short u = static_cast<const unsigned short*>(p)[i];
+    if (ty == 2) return __uint_as_float((unsigned)u << 16);
+    return (float)__builtin_bit_cast(_Float16, u);
+}
 // the type as a template argument (TY >= 0): no branch in front of the load, so the loads of an unrolled loop are issued together --
 // with the run-time switch the GroupNorm-backward reduction over a 16-bit x AND a 16-bit dy ran at 1.9 TB/s (34.7 us vs 27.4 us fp32 dy)
 template <int TY>
@@ -44,6 +51,9 @@ __device__ __forceinline__ void st4_t(void* p, size_t i, float4 v, int ty) { st4
 // ---------------------------------------------------------------------------------------------
 // generic per-(b,c) column reduction: partial[b][blk][NV][C] = sum over the block's rows of f(...)
 // ---------------------------------------------------------------------------------------------
+// the channel-quad path of colreduce_kernel (256 / (C/4) rows in parallel per workgroup); otherwise one thread per channel
+__host__ __device__ inline bool colreduce_vec(int C) { return (C & 3) == 0 && C <= 1024; }
+
 template <int NV, class F>
 __global__ __launch_bounds__(256) void colreduce_kernel(F f, float* __restrict__ partial, int rows, int C) {
     __shared__ float4 sh[NV][256];
@@ -53,7 +63,7 @@ __global__ __launch_bounds__(256) void colreduce_kernel(F f, float* __restrict__
     int r1 = r0 + rowsPer;
     if (r1 > rows) r1 = rows;
     float* dst = partial + ((size_t)b * nblk + blk) * NV * C;
-    if ((C & 3) == 0 && C <= 1024) {
+    if (colreduce_vec(C)) {
         const int tpr = C >> 2, rpar = 256 / tpr;
         const int rr = threadIdx.x / tpr, cq = threadIdx.x % tpr;
         float acc[NV][4];
@@ -122,6 +132,20 @@ static inline int red_nblk(int rows) {
     if (n > RED_NBLK) n = RED_NBLK;
     if (n < 1) n = 1;
     return n;
+}
+// The plan every colreduce_kernel launch runs from, as a pure shape query: `field` 0 workgroups per batch element (red_nblk), 1 rows per
+// workgroup (the kernel's ceil(rows / nblk): with more than 64 * 256 rows the last workgroups can start past `rows` and write zeros),
+// 2 whether the channel-quad path runs, 3 the rows a workgroup reads in parallel on that path (0 on the scalar path).
+extern "C" int diqt_colreduce_route(int rows, int C, int field) {
+    if (rows <= 0 || C <= 0) return -1;
+    const int nblk = red_nblk(rows);
+    switch (field) {
+        case 0: return nblk;
+        case 1: return (rows + nblk - 1) / nblk;
+        case 2: return colreduce_vec(C) ? 1 : 0;
+        case 3: return colreduce_vec(C) ? 256 / (C >> 2) : 0;
+        default: return -1;
+    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -436,7 +460,8 @@ struct GnBwdF {
         onej(xv.z, dv.z, 2, o[0][2], o[1][2]);
         onej(xv.w, dv.w, 3, o[0][3], o[1][3]);
     }
-    __device__ void scalar(size_t i, int b, int c, float (&o)[2]) const { one(x[i], dy[i], b, c, o[0], o[1]); }
+    // (x and dy by their types: indexed as fp32, a 16-bit tensor was read past its end -- 1028 channels in fp16, found by the fuzz)
+    __device__ void scalar(size_t i, int b, int c, float (&o)[2]) const { one(ld1_any(x, i, xty), ld1_any(dy, i, dyty), b, c, o[0], o[1]); }
 };
 
 // the same with the tensor types fixed at compile time (see ld4_t)
@@ -2053,6 +2078,19 @@ static unsigned gn_grid(size_t per, int C, int B) {
     return (n + m - 1) / m * m;
 }
 
+// The two decisions of the GroupNorm apply launches (diqt_gn_act_fwd / _fwd_h and the dx pass of the backwards) as a pure shape query:
+// `field` 0 whether the vectorised kernel runs (vec_ok; all_aligned: every tensor it checks is 16-byte aligned), 1 grid.x (gn_grid).
+extern "C" int diqt_gn_apply_route(int B, int rows, int C, int all_aligned, int field) {
+    if (B <= 0 || rows <= 0 || C <= 0) return -1;
+    const size_t per = (size_t)rows * C;
+    const void* p = reinterpret_cast<const void*>(static_cast<uintptr_t>(all_aligned ? 16 : 4));
+    switch (field) {
+        case 0: return vec_ok(p, nullptr, nullptr, per, C) ? 1 : 0;
+        case 1: return (int)gn_grid(per, C, B);
+        default: return -1;
+    }
+}
+
 extern "C" int diqt_gn_act_fwd(const float* x, const float* mean, const float* rstd, const float* gamma,
                                const float* beta, const float* scale, const float* shift, int cond_stride, float* y,
                                int B, int rows, int C, int G, int act, void* stream) {
@@ -2122,7 +2160,7 @@ static int gn_act_bwd_impl(const float* x, const float* dy, const float* mean, c
     int rc = DIQT_OK;
     if (ext_partials) {
         DIQT_REQUIRE(ext_nblk > 0, DIQT_E_SHAPE, "gn_act_bwd_from_partials: nblk");
-    } else if (vec || C % 4 != 0 || C > 1024) {
+    } else if (vec || !colreduce_vec(C)) {
         // the 16-bit combinations a low-precision training step produces get their types at compile time
 #define DIQT_GNB_RED(XT, DYT) { GnBwdFT<XT, DYT> ft; static_cast<GnBwdF&>(ft) = f; \
         hipLaunchKernelGGL((colreduce_kernel<2, GnBwdFT<XT, DYT>>), dim3(nblk, B), dim3(256), 0, STREAM, ft, partial, rows, C); }
@@ -2230,6 +2268,10 @@ extern "C" int diqt_chan_layernorm_bwd_ex(const float* x, const float* dy, const
                                           size_t workspace_bytes, int rows, int C, void* stream) {
     DIQT_REQUIRE(x && dy && g && mean && rstd && dx, DIQT_E_ALIGN, "chan_layernorm_bwd: null pointer");
     DIQT_REQUIRE(rows > 0 && C > 0, DIQT_E_SHAPE, "chan_layernorm_bwd: bad shape");
+    // colreduce_kernel stores 16 bytes per lane into the workspace and, on its channel-quad path, IdentF loads dy 16 bytes per lane
+    // (ChanLnDgF and the dx kernel read x, dy and dx_add one float at a time: no requirement on those); refused before anything launches
+    DIQT_REQUIRE(!dg || (aligned16(workspace) && (!db || !colreduce_vec(C) || aligned16(dy))), DIQT_E_ALIGN,
+                 "chan_layernorm_bwd: misaligned workspace or dy");
     hipLaunchKernelGGL(chan_ln_bwd_dx_kernel, dim3(grid_for((size_t)rows, 4, 4096)), dim3(256), 0, STREAM, x, dy, g, mean,
                        rstd, dx, rows, C, dx_add);
     int rc = check_launch("chan_layernorm_bwd/dx");
@@ -2787,18 +2829,28 @@ extern "C" int diqt_ema_lerp(float* ema, const float* param, size_t n, float one
     return check_launch("ema_lerp");
 }
 
+// the one kernel choice of diqt_softmax_fwd / diqt_softmax_bwd: 0 a 1024-thread workgroup per long row, 1 a wave per row, 2 a
+// 1024-thread workgroup per outer index (forward only), 3 a thread per column
+static int softmax_route(size_t outer, int n, int inner, bool backward) {
+    if (inner == 1) return outer <= 1024 && n >= 4096 ? 0 : 1;
+    if (!backward && inner <= 1024 && 1024 % inner == 0 && n >= 64 && outer <= 65535) return 2;
+    return 3;
+}
+extern "C" int diqt_softmax_route(size_t outer, int n, int inner, int backward) {
+    if (n <= 0 || inner <= 0) return -1;
+    return softmax_route(outer, n, inner, backward != 0);
+}
+
 extern "C" int diqt_softmax_fwd(const float* x, float* y, size_t outer, int n, int inner, float scale, void* stream) {
     DIQT_REQUIRE(x && y, DIQT_E_ALIGN, "softmax_fwd: null pointer");
     DIQT_REQUIRE(n > 0 && inner > 0, DIQT_E_SHAPE, "softmax_fwd: bad shape");
     if (outer == 0) return DIQT_OK;
-    if (inner == 1 && outer <= 1024 && n >= 4096)
-        hipLaunchKernelGGL(softmax_longrow_kernel, dim3((unsigned)outer), dim3(1024), 0, STREAM, x, y, n, scale);
-    else if (inner == 1)
-        hipLaunchKernelGGL(softmax_row_kernel, dim3(grid_for(outer, 4, 8192)), dim3(256), 0, STREAM, x, y, outer, n, scale);
-    else if (inner <= 1024 && 1024 % inner == 0 && n >= 64 && outer <= 65535)
-        hipLaunchKernelGGL(softmax_col_wg_kernel, dim3((unsigned)outer), dim3(1024), 0, STREAM, x, y, n, inner, scale);
-    else
-        hipLaunchKernelGGL(softmax_col_kernel, dim3(grid_for(outer * inner, 256)), dim3(256), 0, STREAM, x, y, outer, n, inner, scale);
+    switch (softmax_route(outer, n, inner, false)) {
+        case 0: hipLaunchKernelGGL(softmax_longrow_kernel, dim3((unsigned)outer), dim3(1024), 0, STREAM, x, y, n, scale); break;
+        case 1: hipLaunchKernelGGL(softmax_row_kernel, dim3(grid_for(outer, 4, 8192)), dim3(256), 0, STREAM, x, y, outer, n, scale); break;
+        case 2: hipLaunchKernelGGL(softmax_col_wg_kernel, dim3((unsigned)outer), dim3(1024), 0, STREAM, x, y, n, inner, scale); break;
+        default: hipLaunchKernelGGL(softmax_col_kernel, dim3(grid_for(outer * inner, 256)), dim3(256), 0, STREAM, x, y, outer, n, inner, scale);
+    }
     return check_launch("softmax_fwd");
 }
 extern "C" int diqt_softmax_bwd(const float* y, const float* dy, float* dx, size_t outer, int n, int inner, float scale,
@@ -2806,12 +2858,11 @@ extern "C" int diqt_softmax_bwd(const float* y, const float* dy, float* dx, size
     DIQT_REQUIRE(y && dy && dx, DIQT_E_ALIGN, "softmax_bwd: null pointer");
     DIQT_REQUIRE(n > 0 && inner > 0 && scale != 0.f, DIQT_E_SHAPE, "softmax_bwd: bad shape");
     if (outer == 0) return DIQT_OK;
-    if (inner == 1 && outer <= 1024 && n >= 4096)
-        hipLaunchKernelGGL(softmax_longrow_bwd_kernel, dim3((unsigned)outer), dim3(1024), 0, STREAM, y, dy, dx, n, scale);
-    else if (inner == 1)
-        hipLaunchKernelGGL(softmax_row_bwd_kernel, dim3(grid_for(outer, 4, 8192)), dim3(256), 0, STREAM, y, dy, dx, outer, n, scale);
-    else
-        hipLaunchKernelGGL(softmax_col_bwd_kernel, dim3(grid_for(outer * inner, 256)), dim3(256), 0, STREAM, y, dy, dx, outer, n, inner, scale);
+    switch (softmax_route(outer, n, inner, true)) {
+        case 0: hipLaunchKernelGGL(softmax_longrow_bwd_kernel, dim3((unsigned)outer), dim3(1024), 0, STREAM, y, dy, dx, n, scale); break;
+        case 1: hipLaunchKernelGGL(softmax_row_bwd_kernel, dim3(grid_for(outer, 4, 8192)), dim3(256), 0, STREAM, y, dy, dx, outer, n, scale); break;
+        default: hipLaunchKernelGGL(softmax_col_bwd_kernel, dim3(grid_for(outer * inner, 256)), dim3(256), 0, STREAM, y, dy, dx, outer, n, inner, scale);
+    }
     return check_launch("softmax_bwd");
 }
 
@@ -2982,6 +3033,9 @@ extern "C" int diqt_attn_softmax_bwd_ws(const float* p, const float* dp, float* 
                                         int causal, void* stream) {
     DIQT_REQUIRE(p && dp && dsim, DIQT_E_ALIGN, "attn_softmax_bwd: null pointer");
     DIQT_REQUIRE(G > 0 && n > 0 && h > 0 && n_extra >= 0 && n_self >= 0 && n_extra + n_self > 0, DIQT_E_SHAPE, "attn_softmax_bwd: bad shape");
+    // as the forward: the table is indexed by i - j + n_self - 1 with i < n (an index past the table otherwise)
+    DIQT_REQUIRE(!drel || n_self == n, DIQT_E_SHAPE, "attn_softmax_bwd: a relative-bias gradient needs n_self == n");
+    DIQT_REQUIRE(!dnull_bias || n_extra >= 1, DIQT_E_SHAPE, "attn_softmax_bwd: null-bias gradient without a null key");
     const size_t rows = (size_t)G * n * h;
     const size_t need = diqt_attn_softmax_bwd_workspace_bytes(G, n, h, n_extra, n_self);
     if (!(drel || dnull_bias) || need == 0 || !workspace || workspace_bytes < need)
@@ -3002,6 +3056,9 @@ extern "C" int diqt_attn_softmax_bwd(const float* p, const float* dp, float* dsi
                                      int n, int h, int n_extra, int n_self, int causal, void* stream) {
     DIQT_REQUIRE(p && dp && dsim, DIQT_E_ALIGN, "attn_softmax_bwd: null pointer");
     DIQT_REQUIRE(G > 0 && n > 0 && h > 0 && n_extra >= 0 && n_self >= 0 && n_extra + n_self > 0, DIQT_E_SHAPE, "attn_softmax_bwd: bad shape");
+    // as the forward: the table is indexed by i - j + n_self - 1 with i < n (an index past the table otherwise)
+    DIQT_REQUIRE(!drel || n_self == n, DIQT_E_SHAPE, "attn_softmax_bwd: a relative-bias gradient needs n_self == n");
+    DIQT_REQUIRE(!dnull_bias || n_extra >= 1, DIQT_E_SHAPE, "attn_softmax_bwd: null-bias gradient without a null key");
     const size_t rows = (size_t)G * n * h;
     hipLaunchKernelGGL(attn_softmax_bwd_kernel, dim3(grid_for(rows, 4, 16384)), dim3(256), 0, STREAM, p, dp, dsim, drel, dnull_bias,
                        rows, n, h, n_extra, n_self, causal);

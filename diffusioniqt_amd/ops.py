@@ -1461,6 +1461,8 @@ class _ChanLayerNormFn(Function):
         db = torch.empty_like(g) if ctx.has_bias else None
         ws, n = _reduce_ws(1, C, x.device)
         dy = dy.contiguous()
+        if db is not None and C % 4 == 0 and dy.data_ptr() % 16:
+            dy = dy.clone()          # a contiguous view at an odd offset: the bias-gradient reduction loads dy 16 bytes per lane
         if dtap is not None:
             dtap = dtap.contiguous()
         _lib.call("diqt_chan_layernorm_bwd_ex", x, dy, dtap, g, mean, rstd, dx, dg, db, ws, n, rows, C, _stream())

@@ -333,6 +333,14 @@ int diqt_conv3d_direct_bwd_weight_ws(const float* x, const float* dy, float* dw,
 size_t diqt_reduce_workspace_bytes(int B, int C);
 int diqt_groupnorm_stats(const float* x, float* mean, float* rstd, void* workspace, size_t workspace_bytes,
                          int B, int rows_per_batch, int C, int G, float eps, void* stream);
+/* The plan of every column reduction over [rows][C] (GroupNorm statistics and backward, LayerNorm dg / db, channel means), as a pure
+ * shape query (no GPU): `field` 0 workgroups per batch element, 1 rows per workgroup (past 64 * 256 rows the last workgroups may start
+ * beyond `rows` and write zero partials), 2 whether the channel-quad path runs (C % 4 == 0, C <= 1024), 3 the rows a workgroup reads in
+ * parallel on that path (0 otherwise).  -1: bad shape or field.                                                                      */
+int diqt_colreduce_route(int rows, int C, int field);
+/* The decisions of the GroupNorm apply launches (diqt_gn_act_fwd / _fwd_h, the dx pass of diqt_gn_act_bwd*): `field` 0 whether the
+ * vectorised kernel runs (C % 4 == 0, rows * C % 4 == 0 and `all_aligned`: every tensor pointer 16-byte aligned), 1 grid.x.         */
+int diqt_gn_apply_route(int B, int rows_per_batch, int C, int all_aligned, int field);
 
 /* y = act( ((x-mean)*rstd*gamma+beta) * (scale+1) + shift ); scale/shift are both NULL or point at
  * rows of `cond_stride` floats per batch element (the reference chunks one [B][2C] time embedding,
@@ -444,7 +452,8 @@ int diqt_chan_layernorm_bwd(const float* x, const float* dy, const float* g, con
                             const float* rstd, float* dx, float* dg, float* db, void* workspace,
                             size_t workspace_bytes, int rows, int C, void* stream);
 /* ... plus dx_add (optional, same shape as x): dx = LayerNorm backward + dx_add, the residual branch's gradient of `fn(LN(x)) + x`
- * (Attention / ChanFeedForward blocks, imagen_video.py:410-525, 994-1029) summed in the same pass.                                   */
+ * (Attention / ChanFeedForward blocks, imagen_video.py:410-525, 994-1029) summed in the same pass.  With dg the workspace must be
+ * 16-byte aligned, and with db and C % 4 == 0, C <= 1024 so must dy (DIQT_E_ALIGN otherwise, nothing launched).                       */
 int diqt_chan_layernorm_bwd_ex(const float* x, const float* dy, const float* dx_add, const float* g, const float* mean,
                                const float* rstd, float* dx, float* dg, float* db, void* workspace,
                                size_t workspace_bytes, int rows, int C, void* stream);
@@ -970,11 +979,15 @@ int diqt_ema_lerp(float* ema, const float* param, size_t n, float one_minus_deca
 int diqt_softmax_fwd(const float* x, float* y, size_t outer, int n, int inner, float scale, void* stream);
 int diqt_softmax_bwd(const float* y, const float* dy, float* dx, size_t outer, int n, int inner, float scale,
                      void* stream);
+/* The kernel either of them launches, as a pure shape query: 0 a workgroup per long row (inner 1, n >= 4096, outer <= 1024), 1 a wave
+ * per row (inner 1), 2 a workgroup per outer index (forward only: inner divides 1024, n >= 64, outer <= 65535), 3 a thread per column. */
+int diqt_softmax_route(size_t outer, int n, int inner, int backward);
 /* Multi-query attention probabilities (imagen_video.Attention :490-518): sim[G][n][h][M] holds scores of n queries x h
  * heads against M = n_extra + n_self keys ordered [context..., null, self...]; adds rel[(i-j+n_self-1)][h] (T5-style
  * DynamicPositionBias table, may be NULL) on self keys and null_bias[h] (may be NULL) on the null key (the last extra
  * key), masks self keys j > i when causal, and soft-maxes over M in place layout.  bwd also accumulates drel / dnull
- * (zeroed by the caller; float atomics).                                                                         */
+ * (zeroed by the caller; float atomics).  DIQT_E_SHAPE: fwd with causal or rel, bwd with drel, when n_self != n (the table
+ * index would leave the table); null_bias / dnull_bias without an extra key.                                     */
 int diqt_attn_softmax_fwd(const float* sim, const float* rel, const float* null_bias, float* p,
                           int G, int n, int h, int n_extra, int n_self, int causal, void* stream);
 int diqt_attn_softmax_bwd(const float* p, const float* dp, float* dsim, float* drel, float* dnull_bias,

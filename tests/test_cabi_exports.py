@@ -55,6 +55,12 @@ def test_shape_queries_without_a_gpu():
     assert route(1, 100, 8, 64, 1, 100, 1, 1)[:2] == [0, -3] and route(1, 96, 8, 64, 1, 96, 1, 1)[0] == 2     # (2 n - 1) h <= 1536
     assert route(1, 8, 2, 48, 1, 8, 0, 0)[:2] == [0, -3] and route(65536, 8, 2, 32, 1, 8, 0, 0)[:2] == [0, -1]
     assert _lib.query("diqt_mqa_attention_bwd_route", 1, 8, 2, 32, 1, 8, 0, 0, 99) == -1
+    # the routes of csrc/elementwise.hip: soft-max kernel (0 long row, 1 wave per row, 2 column workgroup, 3 thread per column); column
+    # reduction [workgroups, rows per workgroup, channel-quad path, rows in parallel]; GroupNorm apply [vectorised, grid.x]
+    sm = lambda *a: _lib.query("diqt_softmax_route", *a)
+    assert [sm(8, 32768, 1, 0), sm(8, 32768, 1, 1), sm(1025, 4096, 1, 0), sm(16, 512, 64, 0), sm(16, 512, 64, 1), sm(16, 512, 96, 0), sm(65536, 64, 2, 0)] == [0, 0, 1, 2, 3, 3, 3]
+    assert [_lib.query("diqt_colreduce_route", 16385, 64, f) for f in range(4)] == [256, 65, 1, 16] and [_lib.query("diqt_colreduce_route", 216, 6, f) for f in range(4)] == [3, 72, 0, 0]
+    assert [_lib.query("diqt_gn_apply_route", 3, 216, 64, 1, f) for f in range(2)] == [1, 14] and [_lib.query("diqt_gn_apply_route", 3, 216, 192, 0, f) for f in range(2)] == [0, 42]
     fwd_h = lambda *a: [_lib.query("diqt_mqa_attention_fwd_h_route", *a, f) for f in range(3)]
     assert fwd_h(512, 8, 64, 0) == [4, 128, 0] and fwd_h(1365, 3, 64, 0) == [8, 256, 0]
     assert fwd_h(512, 8, 64, 1) == [8, 256, 1] and fwd_h(512, 8, 32, 0) == [8, 256, 0]
