@@ -190,6 +190,9 @@ PROTOTYPES = {
     "diqt_tile_project": (I, [P, P, P, P, Z] + [I] * 4 + [F, F, F, I, P]),
     "diqt_volume_joint_consistent_tile_step": (I, [P] * 9 + [I] * 13 + [F] * 7 + [I, ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_uint,
                                                                                   P]),
+    "diqt_tile_project_noise": (I, [P] * 6 + [Z] + [I] * 4 + [F, F, I, P]),
+    "diqt_volume_joint_consistent_tile_noise_step": (I, [P] * 9 + [I] * 13 + [F] * 6 + [I, ctypes.c_ulonglong, ctypes.c_uint,
+                                                                                        ctypes.c_uint, P]),
     "diqt_cell_project_noise": (I, [P] * 6 + [Z] + [I] * 4 + [F, F, F, F, I, P]),
     "diqt_volume_joint_consistent_noise_step": (I, [P] * 9 + [I] * 13 + [F] * 8 + [I, ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_uint,
                                                                                    P]),

@@ -1037,6 +1037,130 @@ __global__ __launch_bounds__(256) void volume_joint_consistent_tile_kernel(const
         x_next[v] = r;
     }
 }
+// ---- noise-aware consistency for a tile operator (DDNM+ per singular direction, ops.tile_noise_operator) --------------------------------
+// Every row of A carries noise of its own deviation, so a step weighs every right singular direction v_j of the whitened operator on
+// its own: `tables` is [2][n][n] = M, G of this step, M = V diag(lambda) V^T and G = V diag(shrink) V^T, both symmetric to the bit
+// (ops.tile_noise_tables makes them on the host).  ONE definition for the two kernels below, fp32 and kept from contraction; for the
+// voxel with in-tile index q, a = the tile's (clamped or fused) predictions, t = the back-projected measurement, eps = the normals:
+//     d[r] = t[r] - a[r];   s = tile_apply(c, M + q, n, d);   a'[q] = a[q] + s;   g = tile_apply(c, G + q, n, eps);   eps'[q] = eps[q] - g.
+// d is formed once per voxel and staged in LDS, so the two sums read LDS only: the tables as [r][q] (the pattern of tile_apply above),
+// d and eps at one address per tile (a broadcast inside a tile).  The normals are never clamped.
+// The per-window step (diqt_tile_project_noise): tile_project_kernel's box walk; LDS holds a [nb], d [nb], eps [nb], then M and G.
+// A block reads only its own voxels of x0, target and noise, all before the barrier, and writes only them after it: out may alias x0
+// and out_noise may alias noise.
+__global__ __launch_bounds__(256) void tile_project_noise_kernel(const float* x0, const float* __restrict__ target, const float* noise,
+                                                                 const float* __restrict__ tables, float* out, float* out_noise, int H,
+                                                                 int W, int gx, int gy, Cell c, CellBox b, ProjectClamp clamp) {
+#pragma clang fp contract(off)
+    extern __shared__ float as[];
+    const int n = c.fz * c.fy * c.fx, nb = c.fz * b.by * b.bx, t = threadIdx.x;
+    float* ds = as + nb;
+    float* zs = ds + nb;
+    float* tab = zs + nb;
+    for (int e = t; e < 2 * n * n; e += 256) tab[e] = tables[e];
+    const int y0 = (int)((blockIdx.x / gx) % gy) * b.by, xb = (int)(blockIdx.x % gx) * b.bx;
+    const size_t z0 = (size_t)(blockIdx.x / ((unsigned)gx * gy)) * c.fz;
+    auto voxel = [&](int lx, int ly, int lz) { return ((z0 + lz) * H + (y0 + ly)) * W + (xb + lx); };
+    for (int e = t; e < nb; e += 256) {
+        const int lx = e % b.bx, ly = (e / b.bx) % b.by, lz = e / (b.bx * b.by);
+        float a = 0.f, d = 0.f, z = 0.f;
+        if (y0 + ly < H && xb + lx < W) {
+            const size_t v = voxel(lx, ly, lz);
+            a = clamp(x0[v]);
+            d = target[v] - a;
+            z = noise[v];
+        }
+        as[e] = a;
+        ds[e] = d;
+        zs[e] = z;
+    }
+    __syncthreads();
+    for (int e = t; e < nb; e += 256) {
+        const int lx = e % b.bx, ly = (e / b.bx) % b.by, lz = e / (b.bx * b.by);
+        if (y0 + ly >= H || xb + lx >= W) continue;    // H and W are multiples of the tile: a tile is inside or outside as a whole
+        const size_t v = voxel(lx, ly, lz);
+        const int cb = ((ly / c.fy) * c.fy) * b.bx + (lx / c.fx) * c.fx;
+        const int q = (lz * c.fy + ly % c.fy) * c.fx + lx % c.fx;
+        const float s = tile_apply(c, tab + q, n, [&](int i, int j, int k) { return ds[cb + (i * b.by + j) * b.bx + k]; });
+        const float g = tile_apply(c, tab + n * n + q, n, [&](int i, int j, int k) { return zs[cb + (i * b.by + j) * b.bx + k]; });
+        out[v] = as[e] + s;
+        out_noise[v] = zs[e] - g;
+    }
+}
+// volume_joint_consistent_tile_kernel with that arithmetic (diqt_volume_joint_consistent_tile_noise_step; forms 0 and 2 with kn != 0
+// only).  Pass 1 fuses each voxel as there and, for a covered one, reads t = meas_up[v] and draws the normal -- the Philox call of the
+// update, moved, not a second one (the NOISE instantiations of volume_joint_consistent_kernel do the same) -- leaving x0, d, den and
+// eps in LDS; the tables [2][n][n] ride behind them.  Pass 2 runs the two tile_apply sums; a tile whose voxels are ALL covered takes
+// x0' and eps', a tile with an uncovered voxel keeps its plain x0 and its plain normals.  The forms, the uncovered voxels and the
+// aliasing are that kernel's.  `w` and `shrink` are not looked at (one launch helper serves all these kernels).
+__global__ __launch_bounds__(256) void volume_joint_consistent_tile_noise_kernel(
+    const float* __restrict__ y, const int* __restrict__ slot, const float* __restrict__ taps, const float* x_t, const float* x0_prev,
+    const float* __restrict__ meas_up, const float* __restrict__ tables, float* x_next, float* x0_out, int N, int D, int H, int W, int P,
+    int stride, int G0, int G1, int G2, Cell c, float w, float kx, float k0, float kp, float kn, float lo, float hi, int clamp_mode,
+    int third_is_normal, unsigned key0, unsigned key1, unsigned draw, unsigned sample, float shrink) {
+#pragma clang fp contract(off)
+    extern __shared__ float tp[];                      // [P], then x0s, ds, dens and ns [nb] each, then the tables [2][n][n]
+    const CellBox b = cell_box(c);
+    const int nb = c.fz * b.by * b.bx, t = threadIdx.y * 64 + threadIdx.x;
+    float* x0s = tp + P;
+    float* ds = x0s + nb;
+    float* dens = ds + nb;
+    float* ns = dens + nb;
+    float* tab = ns + nb;
+    const int n = c.fz * c.fy * c.fx;
+    for (int e = t; e < P; e += 256) tp[e] = taps[e];
+    for (int e = t; e < 2 * n * n; e += 256) tab[e] = tables[e];
+    __syncthreads();
+    const int z0 = blockIdx.z * c.fz, y0 = blockIdx.y * b.by, xb = blockIdx.x * b.bx;
+    for (int e = t; e < nb; e += 256) {
+        const int lx = e % b.bx, ly = (e / b.bx) % b.by, lz = e / (b.bx * b.by);
+        const Voxel p{xb + lx, y0 + ly, z0 + lz, 0, y0 + ly < H && xb + lx < W};
+        Fused f{0.f, 0.f};
+        if (p.inside) f = joint_fuse(y, slot, taps, tp, N, P, stride, G0, G1, G2, p, StepClamp{lo, hi, clamp_mode});
+        float x0 = 0.f, d = 0.f, z = 0.f;
+        if (f.covered()) {                             // covered implies inside: v is a voxel of the volume
+            const size_t v = ((size_t)p.d * H + p.h) * W + p.x;
+            x0 = f.x0();
+            d = meas_up[v] - x0;
+            z = philox_normal(philox4x32_10((unsigned)v, (unsigned)((unsigned long long)v >> 32), draw, sample, key0, key1));
+        }
+        x0s[e] = x0;
+        ds[e] = d;
+        dens[e] = f.den;
+        ns[e] = z;
+    }
+    __syncthreads();
+    for (int e = t; e < nb; e += 256) {
+        const int lx = e % b.bx, ly = (e / b.bx) % b.by, lz = e / (b.bx * b.by);
+        const int x = xb + lx, h = y0 + ly, d = z0 + lz;
+        if (h >= H || x >= W) continue;
+        const size_t v = ((size_t)d * H + h) * W + x;
+        const float xt = x_t[v];
+        if (dens[e] == 0.f) {
+            x_next[v] = xt;
+            x0_out[v] = 0.f;
+            continue;
+        }
+        const int cb = ((ly / c.fy) * c.fy) * b.bx + (lx / c.fx) * c.fx;
+        const int q = (lz * c.fy + ly % c.fy) * c.fx + lx % c.fx;      // this voxel's index inside its tile
+        bool all = true;
+        const float s = tile_apply(c, tab + q, n, [&](int i, int j, int k) {
+            const int u = cb + (i * b.by + j) * b.bx + k;
+            all = all && dens[u] != 0.f;
+            return ds[u];
+        });
+        const float g = tile_apply(c, tab + n * n + q, n, [&](int i, int j, int k) { return ns[cb + (i * b.by + j) * b.bx + k]; });
+        float x0 = x0s[e], eps = ns[e];
+        if (all) {
+            x0 = x0 + s;
+            eps = eps - g;
+        }
+        const float prev = x0_prev ? x0_prev[v] : 0.f;
+        const float r = third_is_normal ? sampler_update(kx, xt, k0, x0, kn, eps) : sampler_update_sde(kx, xt, k0, x0, kp, prev, kn, eps);
+        x0_out[v] = x0;
+        x_next[v] = r;
+    }
+}
 
 // The stochastic Heun sampler of the EDM family (elucidated_imagen.py:382-532) on the same state: a churn, a predictor and a corrector
 // per step, two U-Net evaluations, so the state is three volumes -- xh = images_hat, xn = images_next, x0 = the fused prediction (the
@@ -1692,12 +1816,14 @@ extern "C" int diqt_cell_project_noise(const float* x0, const float* meas_up, co
 // `shaped` is diqt_volume_joint_consistent_noise_step (which has checked `shrink`, the form and kn): the NOISE instantiations and
 // their third LDS array; the other entries never look at `shrink`.
 // `tile` is diqt_volume_joint_consistent_tile_step: `table` is the n x n projector of a tile operator and the kernel its own.
+// `tile_noise` is diqt_volume_joint_consistent_tile_noise_step (which has checked the form and kn): `table` is [2][n][n] = M, G, the
+// kernel has four box arrays and looks at neither `weight` nor `shrink`.
 static int joint_consistent_launch(const char* who, const float* y, const int* slot, const float* taps, const float* x_t,
                                    const float* x0_prev, const float* meas_up, const float* table, float* x_next, float* x0_out,
                                    int form, int N, int D, int H, int W, int P, int stride, int G0, int G1, int G2, int fz, int fy,
                                    int fx, float weight, float kx, float k0, float kp, float kn, float lo, float hi, int clamp_mode,
                                    unsigned long long seed, unsigned draw, unsigned sample, void* stream, bool shaped = false,
-                                   float shrink = 0.f, bool tile = false) {
+                                   float shrink = 0.f, bool tile = false, bool tile_noise = false) {
     DIQT_REQUIRE(x_t && meas_up && x_next && x0_out && slot && taps && (y || N == 0), DIQT_E_ALIGN, "%s: null pointer", who);
     DIQT_REQUIRE(form >= 0 && form <= 2, DIQT_E_UNSUPPORTED, "%s: form %d (0 = first order, 1 = multistep, 2 = multistep with noise)", who,
                  form);
@@ -1711,7 +1837,8 @@ static int joint_consistent_launch(const char* who, const float* y, const int* s
     const Cell c{fz, fy, fx};
     const CellBox b = cell_box(c);
     const size_t n = (size_t)fz * fy * fx;
-    const size_t lds = ((size_t)P + (shaped ? 3 : 2) * (size_t)fz * b.by * b.bx + (tile ? n * n : table ? 2 * n : 0)) * sizeof(float);
+    const size_t lds = ((size_t)P + (tile_noise ? 4 : shaped ? 3 : 2) * (size_t)fz * b.by * b.bx +
+                        (tile_noise ? 2 * n * n : tile ? n * n : table ? 2 * n : 0)) * sizeof(float);
     DIQT_REQUIRE(lds <= 65536, DIQT_E_SHAPE, "%s: P %d needs %zu bytes of LDS", who, P, lds);
     DIQT_REQUIRE((H + b.by - 1) / b.by <= 65535, DIQT_E_SHAPE, "%s: more than 65535 rows of boxes", who);
     // first order: no history; multistep: no normal (and with it no key)
@@ -1722,7 +1849,9 @@ static int joint_consistent_launch(const char* who, const float* y, const int* s
                            x0_out, N, D, H, W, P, stride, G0, G1, G2, c, weight, kx, k0, first ? 0.f : kp, noisy ? kn : 0.f, lo, hi,
                            clamp_mode, first ? 1 : 0, (unsigned)seed, (unsigned)(seed >> 32), draw, sample, shrink);
     };
-    if (tile)
+    if (tile_noise)
+        launch(volume_joint_consistent_tile_noise_kernel);
+    else if (tile)
         launch(volume_joint_consistent_tile_kernel);
     else if (shaped)
         table ? launch(volume_joint_consistent_kernel<true, true>) : launch(volume_joint_consistent_kernel<false, true>);
@@ -1831,6 +1960,46 @@ extern "C" int diqt_volume_joint_consistent_tile_step(const float* y, const int*
     return joint_consistent_launch("volume_joint_consistent_tile_step", y, slot, taps, x_t, x0_prev, meas_up, table, x_next, x0_out, form,
                                    N, D, H, W, P, stride, G0, G1, G2, fz, fy, fx, weight, kx, k0, kp, kn, lo, hi, clamp_mode, seed, draw,
                                    sample, stream, false, 0.f, true);
+}
+
+extern "C" int diqt_tile_project_noise(const float* x0, const float* target, const float* noise, const float* tables, float* out,
+                                       float* out_noise, size_t cubes, int P, int fz, int fy, int fx, float lo, float hi, int clamp_mode,
+                                       void* stream) {
+    DIQT_REQUIRE(x0 && target && noise && tables && out && out_noise, DIQT_E_ALIGN, "tile_project_noise: null pointer");
+    int rc = cell_ok("tile_project_noise", fz, fy, fx, 1.f);
+    if (rc) return rc;
+    DIQT_REQUIRE(clamp_mode >= 0 && clamp_mode <= 2, DIQT_E_UNSUPPORTED, "tile_project_noise: clamp_mode %d (0 = min, 1 = box, 2 = none)",
+                 clamp_mode);
+    DIQT_REQUIRE(cubes > 0 && P > 0 && P % fz == 0 && P % fy == 0 && P % fx == 0, DIQT_E_SHAPE,
+                 "tile_project_noise: the cell %dx%dx%d does not divide the %zu cubes of edge %d", fz, fy, fx, cubes, P);
+    const Cell c{fz, fy, fx};
+    CellBox b = cell_box(c);                           // clipped to the cube, as diqt_tile_project does
+    b.by = b.by < P ? b.by : P;
+    b.bx = b.bx < P ? b.bx : P;
+    const size_t n = (size_t)fz * fy * fx, lds = (3 * (size_t)fz * b.by * b.bx + 2 * n * n) * sizeof(float);
+    DIQT_REQUIRE(lds <= 65536, DIQT_E_SHAPE, "tile_project_noise: the cell %dx%dx%d needs %zu bytes of LDS", fz, fy, fx, lds);
+    const int gx = (P + b.bx - 1) / b.bx, gy = (P + b.by - 1) / b.by;
+    const size_t blocks = (size_t)gx * gy * (cubes * (size_t)(P / fz));
+    DIQT_REQUIRE(blocks <= 0x7fffffffu, DIQT_E_SHAPE, "tile_project_noise: more than 2^31 - 1 blocks");
+    hipLaunchKernelGGL(tile_project_noise_kernel, dim3((unsigned)blocks), dim3(256), lds, STREAM, x0, target, noise, tables, out,
+                       out_noise, P, P, gx, gy, c, b, ProjectClamp{lo, hi, clamp_mode});
+    return check_launch("tile_project_noise");
+}
+
+extern "C" int diqt_volume_joint_consistent_tile_noise_step(const float* y, const int* slot, const float* taps, const float* x_t,
+                                                            const float* x0_prev, const float* meas_up, const float* tables,
+                                                            float* x_next, float* x0_out, int form, int N, int D, int H, int W, int P,
+                                                            int stride, int G0, int G1, int G2, int fz, int fy, int fx, float kx, float k0,
+                                                            float kp, float kn, float lo, float hi, int clamp_mode,
+                                                            unsigned long long seed, unsigned draw, unsigned sample, void* stream) {
+    const char* who = "volume_joint_consistent_tile_noise_step";
+    DIQT_REQUIRE(tables, DIQT_E_ALIGN, "%s: null pointer", who);
+    DIQT_REQUIRE(form == 0 || form == 2, DIQT_E_UNSUPPORTED, "%s: form %d (0 = first order, 2 = multistep with noise: those with a normal)",
+                 who, form);
+    DIQT_REQUIRE(kn != 0.f, DIQT_E_UNSUPPORTED, "%s: kn == 0, a step without a normal has nothing to shape", who);
+    return joint_consistent_launch(who, y, slot, taps, x_t, x0_prev, meas_up, tables, x_next, x0_out, form, N, D, H, W, P, stride, G0, G1,
+                                   G2, fz, fy, fx, 1.f, kx, k0, kp, kn, lo, hi, clamp_mode, seed, draw, sample, stream, false, 0.f, false,
+                                   true);
 }
 
 extern "C" int diqt_volume_joint_heun(const float* y, const int* slot, const float* taps, float* xh, float* xn, float* x0, int phase, int N,

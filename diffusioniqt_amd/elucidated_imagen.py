@@ -23,7 +23,8 @@ from .graphs import GraphCache
 from .imagen_pytorch3D import (GaussianDiffusionContinuousTimes, Unet, NullUnet, exists, default, cast_tuple, identity, maybe,
                                normalize_neg_one_to_one, unnormalize_zero_to_one, eval_decorator, to_channels_last,
                                to_channels_first, log_snr_to_alpha_sigma, check_consistency, check_consistency_operator,
-                               naming_consistency_noise)
+                               naming_consistency_noise, naming_consistency_row_noise, check_consistency_row_noise,
+                               scale_consistency_row_noise, consistency_row_noise_chain)
 from .imagen_video import Unet3D
 
 Hparams_fields = ['num_sample_steps', 'sigma_min', 'sigma_max', 'sigma_data', 'rho', 'P_mean', 'P_std', 'S_churn', 'S_tmin',
@@ -420,7 +421,7 @@ class ElucidatedImagen(nn.Module):
                         inpaint_images=None, inpaint_masks=None, inpaint_resample_times=5, init_images=None,
                         skip_steps=None, sigma_min=None, sigma_max=None, noise=None, sampler='heun', sample_steps=None, eta=0.,
                         consistency=None, consistency_weight=1., consistency_profile=None, consistency_noise=None,
-                        consistency_operator=None, **kwargs):
+                        consistency_operator=None, consistency_row_noise=None, **kwargs):
         """Stochastic Heun sampler (:382-532).  ``noise``: optional injected list [init, step_0, ...], or a callable
         ``noise(shape) -> fp32 device tensor`` whose successive calls are those draws (one ``eps`` per step, also when gamma is 0).
 
@@ -454,14 +455,24 @@ class ElucidatedImagen(nn.Module):
         m x n matrix A (orthogonal stacks: ``ops.stack_operator``); ``consistency=(target_up, cell)`` then carries t = A+ y
         (``ops.tile_backproject``) in state space and every ``ops.cell_project`` of the chain is one ``ops.tile_project``.
         ``ValueError`` naming "consistency_operator": without ``consistency``, together with ``consistency_profile`` or
-        ``consistency_noise``, or an operator ``ops.tile_operator`` refuses."""
+        ``consistency_noise``, or an operator ``ops.tile_operator`` refuses.
+        ``consistency_row_noise=sigma`` (with ``consistency_operator``; DDNM+ per singular direction): the deviation of the noise of
+        each row of A, one number or m of them, in state space like ``target_up``.  ``ops.tile_noise_tables`` makes (M_i, G_i) and
+        the dispatch once per chain: every lambda 0 skips the projection, one common weight and no shrink is ``ops.tile_project``,
+        any other step runs ONE ``ops.tile_project_noise`` on the step's draw.  ``ValueError`` naming "consistency_row_noise":
+        without ``consistency_operator``, with ``consistency_noise`` or ``consistency_profile``, eta = 0, values
+        ``ops.tile_noise_operator`` refuses, an LDS plan above 64 KiB, and everything ``consistency`` / ``consistency_operator``
+        refuse."""
         self._check_sampler_args(sampler, sample_steps, skip_steps, eta)
         has_inpainting = self._check_inpaint_args(sampler, inpaint_images, inpaint_masks, inpaint_resample_times)
-        check_consistency_operator('one_unet_sample', consistency_operator, exists(consistency), consistency_profile,
-                                   consistency_noise)
-        with naming_consistency_noise(consistency_noise):
-            consistency = check_consistency('one_unet_sample', consistency, consistency_weight, shape, has_inpainting, init_images,
-                                            skip_steps, sampler, profile=consistency_profile, operator=consistency_operator)
+        check_consistency_row_noise('one_unet_sample', consistency_row_noise, consistency_operator, consistency_profile,
+                                    consistency_noise, eta != 0)
+        with naming_consistency_row_noise(consistency_row_noise):
+            check_consistency_operator('one_unet_sample', consistency_operator, exists(consistency), consistency_profile,
+                                       consistency_noise)
+            with naming_consistency_noise(consistency_noise):
+                consistency = check_consistency('one_unet_sample', consistency, consistency_weight, shape, has_inpainting, init_images,
+                                                skip_steps, sampler, profile=consistency_profile, operator=consistency_operator)
         if exists(consistency_noise):
             consistency_noise = ops.consistency_noise_sigma('one_unet_sample', consistency_noise, exists(consistency), eta != 0)
         consistency, table = (consistency[:3], consistency[3]) if exists(consistency) else (None, None)
@@ -470,7 +481,9 @@ class ElucidatedImagen(nn.Module):
                                         cond_scale=cond_scale, init_images=init_images, sigma_min=sigma_min, sigma_max=sigma_max,
                                         noise=noise, sample_steps=sample_steps, eta=eta, consistency=consistency,
                                         consistency_profile=table, consistency_noise=consistency_noise,
-                                        tile=exists(consistency_operator), **kwargs)
+                                        tile=exists(consistency_operator),
+                                        row_noise=(consistency_operator, consistency_row_noise) if exists(consistency_row_noise)
+                                        else None, **kwargs)
         # Inpainting (:441-449, 473-530; RePaint, Lugmayr et al. 2022) is this loop with ``inpaint_resample_times`` passes per step,
         # r = R - 1 .. 0, where plain sampling has one: a pass draws ``eps``, pastes the known image under the mask and churns, runs the
         # two Heun evaluations as ever and -- unless r == 0 or it is the last step -- draws once more and re-noises,
@@ -536,12 +549,19 @@ class ElucidatedImagen(nn.Module):
         return self.unnormalize_img(images)
 
     def _dpmpp2m_sample(self, unet, shape, *, unet_number, clamp, dynamic_threshold, cond_scale, init_images, sigma_min, sigma_max, noise,
-                        sample_steps, eta, consistency=None, consistency_profile=None, consistency_noise=None, tile=False, **kwargs):
+                        sample_steps, eta, consistency=None, consistency_profile=None, consistency_noise=None, tile=False, row_noise=None,
+                        **kwargs):
         """``one_unet_sample(sampler='dpmpp2m')``; the arguments are checked there (``consistency``: None or the checked
         ``(meas_up, cell, weight)``, ``meas_up`` in state space; ``consistency_profile``: None or the checked host table of
         ``ops.cell_profile``; ``consistency_noise``: None or the checked deviation in state space; ``tile``: the table is a
-        ``consistency_operator``'s projector and ``meas_up`` its t)."""
+        ``consistency_operator``'s projector and ``meas_up`` its t; ``row_noise``: None or (operator,
+        ``consistency_row_noise`` in state space))."""
         sigmas, coefs = self._dpmpp2m_tables(unet_number - 1, sample_steps, eta, sigma_min, sigma_max)
+        kinds = None
+        if exists(row_noise):                                                   # once per chain: every step's tables, one upload
+            row_op, tables, kinds = consistency_row_noise_chain('one_unet_sample', row_noise[1], row_noise[0], consistency[1],
+                                                                consistency[2], coefs.double(), shape[2], self.device)
+            consistency_profile = row_op.table                                  # P of the whitened operator, for a constant-weight step
         schedule = None
         if exists(consistency_noise):                                           # once per chain, from the host table
             schedule = ops.consistency_noise_dispatch(ops.consistency_noise_schedule(
@@ -561,8 +581,12 @@ class ElucidatedImagen(nn.Module):
             out = fwd(images, float(sigmas[i]), **sc(x_start))
             if exists(schedule):                                                # consistency_noise: this step's own weight and shrink
                 weight, shrink = schedule[i]
+            if exists(kinds):                                                   # consistency_row_noise: plain, constant weight or tables
+                kind, weight = kinds[i]
             shaped = None
-            if exists(schedule) and weight > 0 and shrink > 0:                  # one launch: the projection and the shaped normals;
+            if exists(kinds) and kind == 'noise':                               # one launch on the step's draw (kn != 0 here)
+                out, shaped = ops.tile_project_noise(out, meas_up, draw(), cell, tables[i])
+            elif exists(schedule) and weight > 0 and shrink > 0:                # one launch: the projection and the shaped normals;
                 out, shaped = ops.cell_project_noise(out, meas_up, draw(), cell, weight, shrink, table)   # kn != 0 here: the step's draw
             elif exists(consistency) and weight > 0:                            # ``out`` arrives clamped or thresholded
                 out = ops.tile_project(out, meas_up, cell, table, weight) if tile else \
@@ -637,7 +661,7 @@ class ElucidatedImagen(nn.Module):
                batch_size=1, cond_scale=1., lowres_sample_noise_level=None, start_at_unet_number=1, start_image_or_video=None,
                stop_at_unet_number=None, return_all_unet_outputs=False, return_pil_images=False, use_tqdm=True, device=None,
                noise=None, sampler='heun', sample_steps=None, eta=0., consistency=None, consistency_weight=1.,
-               consistency_profile=None, consistency_noise=None, consistency_operator=None):
+               consistency_profile=None, consistency_noise=None, consistency_operator=None, consistency_row_noise=None):
         """:536-702.  ``noise``: optional injected list [lowres_noise, init, step_0, ...] per sampled unet (tests), or -- when exactly
         one U-Net is sampled -- a callable ``noise(shape) -> fp32 device tensor`` whose successive calls are those draws in that order
         (``inference.AnchoredNoise.source``: call k is draw k of the volume-anchored field).
@@ -663,7 +687,8 @@ class ElucidatedImagen(nn.Module):
         ``one_unet_sample``'s, in the units of ``meas_up`` as passed here (it is multiplied by the slope of ``normalize_img``); every
         refusal above then also names "consistency_noise", as do its own.  ``consistency_operator=A``: ``one_unet_sample``'s
         tile-local linear measurement; ``consistency`` then carries t = A+ y in the units this returns, and its refusals name
-        "consistency_operator"."""
+        "consistency_operator".  ``consistency_row_noise=sigma``: ``one_unet_sample``'s, in the units of ``target_up`` as passed
+        here (multiplied by the slope of ``normalize_img``); every refusal above then also names "consistency_row_noise"."""
         assert texts is None and text_embeds is None and not return_pil_images
         samplers, steps_per_unet, etas = (cast_tuple(v, len(self.unets)) for v in (sampler, sample_steps, eta))
         for args in zip(samplers, steps_per_unet, cast_tuple(skip_steps, len(self.unets)), etas):
@@ -671,7 +696,9 @@ class ElucidatedImagen(nn.Module):
         sampled_samplers = samplers[start_at_unet_number - 1:default(stop_at_unet_number, len(self.unets))]
         has_inpainting = any([self._check_inpaint_args(s, inpaint_images, inpaint_masks, inpaint_resample_times)
                               for s in sampled_samplers or samplers[-1:]])
-        check_consistency_operator('sample', consistency_operator, exists(consistency), consistency_profile, consistency_noise)
+        check_consistency_row_noise('sample', consistency_row_noise, consistency_operator, consistency_profile, consistency_noise)
+        with naming_consistency_row_noise(consistency_row_noise):
+            check_consistency_operator('sample', consistency_operator, exists(consistency), consistency_profile, consistency_noise)
         if exists(consistency_noise) and not exists(consistency):
             ops.consistency_noise_sigma('sample', consistency_noise, False)
         if exists(consistency_profile) and not exists(consistency):
@@ -680,7 +707,7 @@ class ElucidatedImagen(nn.Module):
             span = range(start_at_unet_number, default(stop_at_unet_number, len(self.unets)) + 1)
             frames = calc_all_frame_dims(self.temporal_downsample_factor, video_frames)
             for n in span:
-                with naming_consistency_noise(consistency_noise):
+                with naming_consistency_row_noise(consistency_row_noise), naming_consistency_noise(consistency_noise):
                     check_consistency('sample', consistency, consistency_weight,
                                       (batch_size, self.channels, *frames[n - 1], self.image_sizes[n - 1], self.image_sizes[n - 1]),
                                       exists(inpaint_images), cast_tuple(init_images, len(self.unets))[n - 1],
@@ -688,9 +715,16 @@ class ElucidatedImagen(nn.Module):
                                       operator=consistency_operator)
                 if exists(consistency_noise):
                     ops.consistency_noise_sigma('sample', consistency_noise, True, etas[n - 1] != 0)
+                if exists(consistency_row_noise):
+                    check_consistency_row_noise('sample', consistency_row_noise, consistency_operator, stochastic=etas[n - 1] != 0)
+                    ops.tile_noise_plan('sample', ops.tile_noise_operator(consistency[1], consistency_operator,
+                                                                          consistency_row_noise).cell, 0, self.image_sizes[n - 1])
             if exists(consistency_noise):                                          # into state space with the measurement: the map's slope
                 unit = self.normalize_img(torch.tensor([0., 1.], dtype=torch.float64))
                 consistency_noise = float(consistency_noise) * abs(float(unit[1] - unit[0]))
+            if exists(consistency_row_noise):                                      # the same change of units
+                unit = self.normalize_img(torch.tensor([0., 1.], dtype=torch.float64))
+                consistency_row_noise = scale_consistency_row_noise(consistency_row_noise, float(unit[1] - unit[0]))
             consistency = (self.normalize_img(consistency[0]), consistency[1])
         if has_inpainting:
             if batch_size == 1:                                                    # broadcast along the inpainted images (:580-583)
@@ -743,6 +777,8 @@ class ElucidatedImagen(nn.Module):
                     multistep.update(consistency_noise=consistency_noise)
                 if exists(consistency_operator):
                     multistep.update(consistency_operator=consistency_operator)
+                if exists(consistency_row_noise):
+                    multistep.update(consistency_row_noise=consistency_row_noise)
             inpaint = {}
             if has_inpainting:
                 inpaint = dict(inpaint_images=inpaint_images, inpaint_masks=inpaint_masks, inpaint_resample_times=inpaint_resample_times)

@@ -1164,7 +1164,7 @@ def check_consistency_operator(who, operator, has_consistency, profile=None, noi
                          f"u of a measurement; give the operator all its rows")
     if noise is not None:
         raise ValueError(f"{who}: consistency_operator and consistency_noise are not offered together (DDNM+ for a general A needs a "
-                         f"weight per singular direction)")
+                         f"weight per singular direction: that is consistency_row_noise)")
 
 
 def check_consistency(who, consistency, weight, shape, has_inpainting=False, init_images=None, skip_steps=None, sampler=None,
@@ -1217,6 +1217,61 @@ class naming_consistency_noise:
         if kind is ValueError and self.sigma is not None and 'consistency_noise' not in str(err):
             raise ValueError(f"{err} (consistency_noise={self.sigma!r} rides on consistency)") from None
         return False
+
+
+class naming_consistency_row_noise:
+    """``naming_consistency_noise`` for ``consistency_row_noise``, which rides on ``consistency_operator`` and so on ``consistency``:
+    what those refuse keeps its wording and also names "consistency_row_noise"."""
+
+    def __init__(self, row_noise):
+        self.row_noise = row_noise
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, kind, err, tb):
+        if kind is ValueError and self.row_noise is not None and 'consistency_row_noise' not in str(err):
+            raise ValueError(f"{err} (consistency_row_noise={self.row_noise!r} rides on consistency_operator)") from None
+        return False
+
+
+def check_consistency_row_noise(who, row_noise, operator, profile=None, noise=None, stochastic=True):
+    """The host rules of ``consistency_row_noise=`` beside its neighbours (``ValueError`` naming "consistency_row_noise"; nothing
+    touches the device): it rides on ``consistency_operator``, goes with neither ``consistency_noise`` (the one-number model of the
+    cell mean) nor ``consistency_profile``, and needs a chain with a stochastic row, as ``consistency_noise`` does.  Its values are
+    checked by ``ops.tile_noise_operator``."""
+    if row_noise is None:
+        return
+    if operator is None:
+        raise ValueError(f"{who}: consistency_row_noise needs consistency_operator=A (and consistency=(target_up, cell)): it is the "
+                         f"noise of each row of A; the noise of a plain cell mean is consistency_noise")
+    if noise is not None or profile is not None:
+        raise ValueError(f"{who}: consistency_row_noise is not offered together with consistency_noise or consistency_profile: give "
+                         f"the operator all its rows and every row its deviation")
+    if not stochastic:
+        raise ValueError(f"{who}: consistency_row_noise needs a sampler with fresh noise per step (ddpm, ddim or dpmpp2m with eta > 0): "
+                         f"a deterministic chain would never project; use a constant consistency_weight < 1 there")
+
+
+def scale_consistency_row_noise(row_noise, slope, std=1.):
+    """``consistency_row_noise`` (one number or a sequence, already checked) divided by ``std`` and multiplied by |``slope``|, the
+    change of units that the measurement itself takes -- in this order, which is ``consistency_noise``'s."""
+    if torch.is_tensor(row_noise) or type(row_noise).__module__ == 'numpy':
+        row_noise = row_noise.tolist()
+    if isinstance(row_noise, (tuple, list)):
+        return [float(v) / float(std) * abs(float(slope)) for v in row_noise]
+    return float(row_noise) / float(std) * abs(float(slope))
+
+
+def consistency_row_noise_chain(who, row_noise, operator, cell, weight, rows, edge, device):
+    """What a per-window chain needs of ``consistency_row_noise``, made once per chain on the host: ``(op, tables, kinds)`` --
+    ``ops.tile_noise_operator``, then ``ops.tile_noise_tables`` of ``ops.tile_noise_schedule`` over ``rows`` [T, 4] =
+    (kx, k0, kp, kn) with sigma_min in the units of ``target_up``, the tables uploaded as ONE [T, 2, n, n] tensor.  ``edge`` is the
+    cubes' edge (the LDS plan is checked before anything touches the device)."""
+    op = ops.tile_noise_operator(cell, operator, row_noise)
+    ops.tile_noise_plan(who, op.cell, 0, edge)
+    tables, kinds = ops.tile_noise_tables(op, ops.tile_noise_schedule(op, rows, float(op.row_noise.min()), weight))
+    return op, tables.to(device), kinds
 
 
 # ----------------------------------------------------------------------------------------------
@@ -1553,7 +1608,7 @@ class Imagen(nn.Module):
                       inpaint_masks=None, inpaint_resample_times=5, init_images=None, skip_steps=None, cond_scale=1,
                       pred_objective='noise', dynamic_threshold=True, use_tqdm=True, noise=None, sampler='ddpm',
                       sample_steps=None, eta=0.0, consistency=None, consistency_weight=1.0, consistency_profile=None,
-                      consistency_noise=None, consistency_operator=None):
+                      consistency_noise=None, consistency_operator=None, consistency_row_noise=None):
         """Ancestral sampler (:2059-2160).  Per step: one U-Net eval (HIP) + ONE fused posterior-step kernel;
         the per-step coefficients for all steps are computed on the host up front.  ``noise`` (optional) is a list
         [init, step_0, ...] of injected tensors with the reference's draw order (:2080, :2051), or a callable
@@ -1600,15 +1655,30 @@ class Imagen(nn.Module):
         ``consistency=(target_up, cell)`` then carries t = A+ y on the high-res grid (``ops.tile_backproject``) where it carried
         ``meas_up``, and every ``ops.cell_project`` of the chain is one ``ops.tile_project``, x0' = x0 + w (t - P x0) with P = A+ A.
         ``ValueError`` naming "consistency_operator": without ``consistency``, together with ``consistency_profile`` or
-        ``consistency_noise``, or an operator ``ops.tile_operator`` refuses."""
+        ``consistency_noise``, or an operator ``ops.tile_operator`` refuses.
+
+        ``consistency_row_noise=sigma`` (with ``consistency`` and ``consistency_operator``; DDNM+ per singular direction): the
+        standard deviation of the noise of each row of A, one number or m of them, in the units of ``target_up``; the caller makes
+        t with ``ops.tile_noise_operator``'s effective pseudo-inverse.  ``ops.tile_noise_schedule`` / ``ops.tile_noise_tables``
+        make the per-step tables (M_i, G_i) once per chain (uploaded as one tensor) and the dispatch: every lambda 0 (kn = 0: the
+        last step) is the plain ``ops.ddpm_step``, one common weight w and no shrink the ``ops.tile_project`` above with w,
+        otherwise ONE ``ops.tile_project_noise`` replaces the projection launch and also shapes the step's normals (into a new
+        tensor).  The draws are unchanged.  ``ValueError`` naming "consistency_row_noise": without ``consistency_operator``,
+        together with ``consistency_noise`` or ``consistency_profile``, values ``ops.tile_noise_operator`` refuses, a chain with
+        no stochastic step (use a constant ``consistency_weight``), a cell whose launch plans more than 64 KiB of LDS, and
+        everything ``consistency`` / ``consistency_operator`` refuse."""
         if pred_objective not in ('noise', 'x_start', 'v'):
             raise ValueError(f'unknown objective {pred_objective}')
         has_inpainting = exists(inpaint_images) and exists(inpaint_masks)                  # (:2090-2091)
         self._check_sampler_args(sampler, sample_steps, skip_steps, eta, has_inpainting)
-        check_consistency_operator('p_sample_loop', consistency_operator, exists(consistency), consistency_profile, consistency_noise)
-        with naming_consistency_noise(consistency_noise):
-            consistency = check_consistency('p_sample_loop', consistency, consistency_weight, shape, has_inpainting, init_images,
-                                            skip_steps, profile=consistency_profile, operator=consistency_operator)
+        check_consistency_row_noise('p_sample_loop', consistency_row_noise, consistency_operator, consistency_profile, consistency_noise,
+                                    not (sampler == 'dpmpp2m' or (sampler == 'ddim' and eta == 0)))
+        with naming_consistency_row_noise(consistency_row_noise):
+            check_consistency_operator('p_sample_loop', consistency_operator, exists(consistency), consistency_profile,
+                                       consistency_noise)
+            with naming_consistency_noise(consistency_noise):
+                consistency = check_consistency('p_sample_loop', consistency, consistency_weight, shape, has_inpainting, init_images,
+                                                skip_steps, profile=consistency_profile, operator=consistency_operator)
         if exists(consistency_noise):
             consistency_noise = ops.consistency_noise_sigma('p_sample_loop', consistency_noise, exists(consistency),
                                                             not (sampler == 'dpmpp2m' or (sampler == 'ddim' and eta == 0)))
@@ -1637,6 +1707,13 @@ class Imagen(nn.Module):
             rows = [(float(r[0]), float(r[1]), 0., float(r[2])) for r in coefs[:, :, 0].double()]
             schedule = ops.consistency_noise_dispatch(ops.consistency_noise_schedule(
                 rows, ops.cell_norm(consistency[1], consistency[3]), consistency_noise, consistency[2]))
+        kinds = None
+        if exists(consistency_row_noise):                                   # once per chain too: the tables of every step, one upload
+            assert bool((coefs == coefs[:, :, :1]).all())
+            rows = [(float(r[0]), float(r[1]), 0., float(r[2])) for r in coefs[:, :, 0].double()]
+            row_op, tables, kinds = consistency_row_noise_chain('p_sample_loop', consistency_row_noise, consistency_operator,
+                                                                consistency[1], consistency[2], rows, shape[2], device)
+            consistency = (*consistency[:3], row_op.table)                  # P of the whitened operator, for a constant-weight step
         multistep = sampler == 'dpmpp2m'
         if multistep or (sampler == 'ddim' and eta == 0):                   # kn == 0: the step kernel reads one zero tensor, no draw
             zero = torch.zeros(shape, device=device)
@@ -1672,7 +1749,12 @@ class Imagen(nn.Module):
                 third = x_start if multistep and i > 0 else step_noise()      # 'dpmpp2m': the previous step's clamped x0
                 if exists(schedule):                                          # consistency_noise: this step's own weight and shrink
                     weight, shrink = schedule[i]
-                if exists(schedule) and weight > 0 and shrink > 0:            # one launch: the projection and the shaped normals
+                if exists(kinds):                                             # consistency_row_noise: plain, constant weight or tables
+                    kind, weight = kinds[i]
+                if exists(kinds) and kind == 'noise':                         # one launch: both tables of this step
+                    pred, third = ops.tile_project_noise(pred, meas_up, third, cell, tables[i], clamp=(lo, hi, mode))
+                    img, x_start = ops.ddpm_step(img, pred, third, coefs[i, 0], coefs[i, 1], coefs[i, 2], -inf, inf, 1)
+                elif exists(schedule) and weight > 0 and shrink > 0:          # one launch: the projection and the shaped normals
                     pred, third = ops.cell_project_noise(pred, meas_up, third, cell, weight, shrink, table, clamp=(lo, hi, mode))
                     img, x_start = ops.ddpm_step(img, pred, third, coefs[i, 0], coefs[i, 1], coefs[i, 2], -inf, inf, 1)
                 elif exists(consistency) and weight > 0:                      # the clamp, then the projection; the step clamps no more
@@ -1703,7 +1785,8 @@ class Imagen(nn.Module):
                cond_scale=1., lowres_sample_noise_level=None, start_at_unet_number=1, start_image_or_video=None,
                stop_at_unet_number=None, return_all_outputs=False, return_all_unet_outputs=None, return_pil_images=False,
                device=None, use_tqdm=True, noise=None, sampler='ddpm', sample_steps=None, eta=0.0, consistency=None,
-               consistency_weight=1.0, consistency_profile=None, consistency_noise=None, consistency_operator=None):
+               consistency_weight=1.0, consistency_profile=None, consistency_noise=None, consistency_operator=None,
+               consistency_row_noise=None):
         """imagen_pytorch3D.py:2165-2274 -> (img, [noisy per step], [x0 per step]).  Accepts both spellings
         ``return_all_outputs`` / ``return_all_unet_outputs`` (test.py:182 uses the latter).  ``sampler`` / ``sample_steps`` / ``eta``
         (one value, or one per U-Net like ``skip_steps``) and the list or callable ``noise``: see ``p_sample_loop``, as for
@@ -1714,7 +1797,9 @@ class Imagen(nn.Module):
         ``consistency`` or one ``ops.cell_profile`` refuses.  ``consistency_noise=sigma`` (``p_sample_loop``; the units of ``meas_up``
         as passed): every refusal above then also names "consistency_noise", as do its own.  ``consistency_operator=A``
         (``p_sample_loop``): a tile-local linear measurement; ``consistency`` then carries t = A+ y, and its refusals name
-        "consistency_operator"."""
+        "consistency_operator".  ``consistency_row_noise=sigma`` (``p_sample_loop``; with ``consistency_operator``, the units of
+        ``target_up`` as passed): the noise of each row of A; every refusal above then also names "consistency_row_noise", as do
+        its own."""
         if exists(return_all_unet_outputs):
             return_all_outputs = return_all_unet_outputs
         num_unets = len(self.unets)
@@ -1722,19 +1807,26 @@ class Imagen(nn.Module):
         sampler, sample_steps, eta = (cast_tuple(v, num_unets) for v in (sampler, sample_steps, eta))
         for args in zip(sampler, sample_steps, skip_steps, eta):
             self._check_sampler_args(*args, exists(inpaint_images) and exists(inpaint_masks))
-        check_consistency_operator('sample', consistency_operator, exists(consistency), consistency_profile, consistency_noise)
+        check_consistency_row_noise('sample', consistency_row_noise, consistency_operator, consistency_profile, consistency_noise)
+        with naming_consistency_row_noise(consistency_row_noise):
+            check_consistency_operator('sample', consistency_operator, exists(consistency), consistency_profile, consistency_noise)
         if exists(consistency_noise) and not exists(consistency):
             ops.consistency_noise_sigma('sample', consistency_noise, False)
         if exists(consistency_profile) and not exists(consistency):
             check_consistency('sample', None, consistency_weight, None, profile=consistency_profile)
         for n in range(start_at_unet_number, default(stop_at_unet_number, num_unets) + 1) if exists(consistency) else ():
-            with naming_consistency_noise(consistency_noise):
+            with naming_consistency_row_noise(consistency_row_noise), naming_consistency_noise(consistency_noise):
                 check_consistency('sample', consistency, consistency_weight, (batch_size, self.channels) + (self.image_sizes[n - 1],) * 3,
                                   exists(inpaint_images) and exists(inpaint_masks), cast_tuple(init_images, num_unets)[n - 1],
                                   skip_steps[n - 1], profile=consistency_profile, operator=consistency_operator)
             if exists(consistency_noise):
                 ops.consistency_noise_sigma('sample', consistency_noise, True,
                                             not (sampler[n - 1] == 'dpmpp2m' or (sampler[n - 1] == 'ddim' and eta[n - 1] == 0)))
+            if exists(consistency_row_noise):
+                check_consistency_row_noise('sample', consistency_row_noise, consistency_operator, stochastic=not (
+                    sampler[n - 1] == 'dpmpp2m' or (sampler[n - 1] == 'ddim' and eta[n - 1] == 0)))
+                ops.tile_noise_plan('sample', ops.tile_noise_operator(consistency[1], consistency_operator, consistency_row_noise).cell,
+                                    0, self.image_sizes[n - 1])
         device = default(device, self.device)
         self.reset_unets_all_one_device(device=device)
         cond_scale = cast_tuple(cond_scale, num_unets)
@@ -1762,7 +1854,7 @@ class Imagen(nn.Module):
                 pred_objective=pred_objective, dynamic_threshold=dynamic_threshold, use_tqdm=use_tqdm, noise=noise,
                 sampler=unet_sampler, sample_steps=unet_sample_steps, eta=unet_eta, consistency=consistency,
                 consistency_weight=consistency_weight, consistency_profile=consistency_profile, consistency_noise=consistency_noise,
-                consistency_operator=consistency_operator)
+                consistency_operator=consistency_operator, consistency_row_noise=consistency_row_noise)
             outputs.append(img)
             if exists(stop_at_unet_number) and stop_at_unet_number == unet_number:
                 break

@@ -134,6 +134,20 @@ w = 1 the corrected prediction satisfies P x0' = t (to fp32 rounding), which is 
 contradict each other are fitted in the least-squares sense.  Not offered: an operator that crosses tile borders (true k-space
 truncation, overlapping slice profiles), ``consistency_profile`` or ``consistency_noise`` together with an operator, the Heun sampler,
 consistency together with inpainting; the stacks are taken as registered to each other and A as known.
+
+Noisy rows (``consistency_row_noise=sigma``, with ``consistency`` and ``consistency_operator``; DDNM+ per singular direction): sigma
+is the standard deviation of the noise of each row of A in raw units, one number or m of them -- for stacks one value per stack,
+repeated over that stack's rows; stacks of one subject usually differ in slice thickness and with it in noise.  Whitening is
+unit-free: omega_r = sigma_min / sigma_r, A_w = diag(omega) A = U S V^T (``ops.tile_noise_operator``, float64), and
+t = (A_w+ diag omega) y comes from ``ops.tile_backproject`` as before.  Along v_j the noise of t has the deviation sigma_min / s_j,
+so direction j takes ``ops.consistency_noise_schedule`` with s_j as it is (``ops.tile_noise_schedule``), and a step applies
+x0' = x0 + M_i (t - x0), eps' = eps - G_i eps with M_i = V diag(lambda_i) V^T and G_i = V diag(shrink_i) V^T
+(``ops.tile_noise_tables``: fp32, symmetric to the bit, made once per chain and uploaded as one [T, 2, n, n] tensor).  Units are
+those of ``consistency_noise``: sigma / std goes to the sampler calls of the crop and blend modes, ``joint=True`` multiplies by the
+|slope| of ``state_space``.  Per step, on the fp32 values: every lambda 0 is the family's plain launch (the last step: unprojected),
+every shrink 0 with one common lambda the constant-weight tile launch, otherwise ``ops.tile_project_noise`` /
+``ops.volume_joint_consistent_tile_noise_step`` -- as many launches and the same draws as before.  Not offered: correlated row
+noise, sigma estimated from the data, measurement noise tracked across steps, a cell whose launch plans more than 64 KiB of LDS.
 """
 from types import SimpleNamespace
 
@@ -141,7 +155,8 @@ import numpy as np
 import torch
 
 from . import ops
-from .imagen_pytorch3D import check_consistency_operator, naming_consistency_noise
+from .imagen_pytorch3D import (check_consistency_operator, check_consistency_row_noise, naming_consistency_noise,
+                               naming_consistency_row_noise, scale_consistency_row_noise)
 from .metrics import MSSIM, PSNR
 from .utils_mine import convertVolume2subVolume, merge_sub_volumes
 
@@ -356,6 +371,8 @@ class VolumeInference:
             kw.update(consistency_noise=self.consistency_noise / self.std)
         if self.consistency_op is not None:
             kw.update(consistency_operator=self.consistency_op)
+        if self.consistency_row_noise is not None:           # z-scored like the measurement the sampler gets
+            kw.update(consistency_row_noise=scale_consistency_row_noise(self.consistency_row_noise, 1., self.std))
         return kw
 
     def _inpaint_volumes(self, win):
@@ -369,7 +386,7 @@ class VolumeInference:
 
     def __init__(self, configs, sample_fn, nonzero_ratio=0.05, blend=None, sigma_scale=0.125, samples=1, noise=None, seed=0, joint=False,
                  inpaint=None, inpaint_resample_times=5, consistency=None, consistency_weight=1.0, consistency_profile=None,
-                 consistency_noise=None, consistency_operator=None):
+                 consistency_noise=None, consistency_operator=None, consistency_row_noise=None):
         """``sample_fn(lr_patches [B,1,S,S,S]) -> hr_patches`` — e.g. ``lambda x: trainer.sample(batch_size=x.shape[0],
         start_image_or_video=x, start_at_unet_number=2)[0]`` (test_all.py:234).  ``blend`` / ``sigma_scale`` / ``samples``: weighted
         overlap blending and multi-sample statistics, see the module docstring.  ``noise='anchored'`` (with ``seed``): every call
@@ -423,10 +440,31 @@ class VolumeInference:
         the sampler, ``joint=True`` launches ``ops.volume_joint_consistent_tile_step``.  ``ValueError`` naming
         "consistency_operator" before anything touches the device: without ``consistency``, together with ``consistency_profile``
         (a profile is one row of an operator) or ``consistency_noise``, a measurement whose leading dimension is not m, and
-        whatever ``ops.tile_operator`` refuses."""
-        check_consistency_operator("VolumeInference", consistency_operator, consistency is not None, consistency_profile,
-                                   consistency_noise)
-        with naming_consistency_noise(consistency_noise):    # it rides on consistency: what that refuses names it too
+        whatever ``ops.tile_operator`` refuses.
+
+        ``consistency_row_noise=sigma`` (with ``consistency_operator``): the standard deviation of the noise of each row of A in raw
+        units, one number or m of them (module docstring).  Every step weighs every singular direction of the whitened operator on its
+        own and shapes its fresh noise there; the last step is unprojected.  The crop and blend modes hand
+        ``consistency_row_noise=sigma / std`` on; ``joint=True`` dispatches per step.  ``ValueError`` naming
+        "consistency_row_noise" before anything touches the device: without ``consistency_operator``, together with
+        ``consistency_noise`` or ``consistency_profile``, a value ``ops.tile_noise_operator`` refuses, a joint denoiser with no
+        stochastic step, a cell whose launch plans more than 64 KiB of LDS, and whatever ``consistency`` and
+        ``consistency_operator`` refuse."""
+        def stochastic():                                    # crop and blend modes: the sampler call knows its own chain
+            if joint and hasattr(sample_fn, 'coefs') and not getattr(sample_fn, 'heun', False):
+                # kn is the last entry of a first-order row (kx, k0, kn) and of a sigma-space row (kx, k0, kp, kn); the DDPM family's
+                # multistep rows (kx, k0, kp) have none
+                has_kn = hasattr(sample_fn, 'sigma0') or not getattr(sample_fn, 'multistep', False)
+                return has_kn and any(float(r[-1]) != 0.0 for r in sample_fn.coefs.tolist())
+            return True
+
+        check_consistency_row_noise("VolumeInference", consistency_row_noise, consistency_operator, consistency_profile,
+                                    consistency_noise, consistency_row_noise is None or stochastic())
+        with naming_consistency_row_noise(consistency_row_noise):
+            check_consistency_operator("VolumeInference", consistency_operator, consistency is not None, consistency_profile,
+                                       consistency_noise)
+        with naming_consistency_row_noise(consistency_row_noise), naming_consistency_noise(consistency_noise):
+            # they ride on consistency: what that refuses names them too
             self.inpaint = self._check_inpaint(inpaint, inpaint_resample_times, joint, sample_fn)
             self.consistency = self._check_consistency(consistency, consistency_weight, self.inpaint, joint, sample_fn,
                                                        consistency_operator is not None)
@@ -436,20 +474,18 @@ class VolumeInference:
                 if self.consistency[0].shape[0] != self.consistency_op.m:
                     raise ValueError(f"VolumeInference: the consistency_operator has m = {self.consistency_op.m} rows, the consistency "
                                      f"measurement {tuple(self.consistency[0].shape)} has {self.consistency[0].shape[0]} volumes")
+                if consistency_row_noise is not None:        # the whitened operator: its effective A+ makes t, its P the table
+                    self.consistency_op = ops.tile_noise_operator(self.consistency[1], self.consistency_op, consistency_row_noise)
             if consistency_profile is not None and self.consistency is None:
                 raise ValueError("VolumeInference: consistency_profile needs consistency=(measurement, cell)")
             # the profile as given (what a sampler call takes) and its host table (what the fused launch takes, moved once per volume)
             self.consistency_profile = consistency_profile
             self.consistency_table = None if consistency_profile is None else ops.cell_profile(self.consistency[1], consistency_profile)
+        self.consistency_row_noise = consistency_row_noise   # as given (what a sampler call takes, divided by std)
         self.consistency_noise = None
         if consistency_noise is not None:
-            noisy = True                                     # crop and blend modes: the sampler call knows its own chain
-            if joint and hasattr(sample_fn, 'coefs') and not getattr(sample_fn, 'heun', False):
-                # kn is the last entry of a first-order row (kx, k0, kn) and of a sigma-space row (kx, k0, kp, kn); the DDPM family's
-                # multistep rows (kx, k0, kp) have none
-                has_kn = hasattr(sample_fn, 'sigma0') or not getattr(sample_fn, 'multistep', False)
-                noisy = has_kn and any(float(r[-1]) != 0.0 for r in sample_fn.coefs.tolist())
-            self.consistency_noise = ops.consistency_noise_sigma("VolumeInference", consistency_noise, self.consistency is not None, noisy)
+            self.consistency_noise = ops.consistency_noise_sigma("VolumeInference", consistency_noise, self.consistency is not None,
+                                                                 stochastic())
         self.resample_times = inpaint_resample_times
         if noise not in NOISE_MODES:
             raise ValueError(f"VolumeInference: noise must be None or 'anchored', got {noise!r}")
@@ -485,10 +521,12 @@ class VolumeInference:
         self.overlap = int(configs['Eval']['overlap'])
         self.batch = int(configs['Eval'].get('batch_size', 27))
         self.mean, self.std = float(configs['Data']['mean']), float(configs['Data']['std'])
+        if self.consistency_row_noise is not None:           # the fused launch rides the window's taps; a sampler call sees cubes of `sub`
+            ops.tile_noise_plan("VolumeInference", self.consistency[1], self.sub, None if self.joint else self.sub)
         if self.consistency is not None and not self.joint:
             for f in self.consistency[1]:                    # per axis: origins are multiples of the stride, a sampler call sees `sub`
                 if self.overlap % f or self.sub % f:
-                    with naming_consistency_noise(consistency_noise):
+                    with naming_consistency_row_noise(consistency_row_noise), naming_consistency_noise(consistency_noise):
                         raise ValueError(f"VolumeInference: the consistency cell {self.consistency[1]} must divide the stride "
                                          f"{self.overlap} and the window {self.sub}: a per-window projection is defined for cells "
                                          f"inside a window only (joint=True projects on the whole volume)")
@@ -508,7 +546,7 @@ class VolumeInference:
                              f"{tuple(lowres_raw.shape)}")
         if self.consistency is not None and \
                 tuple(s * f for s, f in zip(self.consistency[0].shape[-3:], self.consistency[1])) != tuple(lowres_raw.shape):
-            with naming_consistency_noise(self.consistency_noise):
+            with naming_consistency_row_noise(self.consistency_row_noise), naming_consistency_noise(self.consistency_noise):
                 raise ValueError(f"VolumeInference: the consistency measurement {tuple(self.consistency[0].shape)} times the cell "
                                  f"{self.consistency[1]} is not the volume's shape {tuple(lowres_raw.shape)}")
         if self.blend is not None:
@@ -620,6 +658,14 @@ class VolumeInference:
             rows = [(r[0], r[1], 0., r[2]) if len(r) == 3 else tuple(r) for r in den.coefs]
             win.noise_schedule = ops.consistency_noise_dispatch(ops.consistency_noise_schedule(
                 rows, ops.cell_norm(self.consistency[1], self.consistency_table), sigma, self.consistency[2]))
+        win.row_tables = win.row_kinds = None                # consistency_row_noise: [T, 2, n, n] on the device, one upload, and the
+        if self.consistency_row_noise is not None:           # per-step dispatch, made once per volume on the host
+            unit = self.sample_fn.state_space(torch.tensor([0., 1.], dtype=torch.float64))
+            sigma = float(self.consistency_op.row_noise.min()) / self.std * abs(float(unit[1] - unit[0]))
+            rows = [(r[0], r[1], 0., r[2]) if len(r) == 3 else tuple(r) for r in den.coefs]
+            tables, win.row_kinds = ops.tile_noise_tables(
+                self.consistency_op, ops.tile_noise_schedule(self.consistency_op, rows, sigma, self.consistency[2]))
+            win.row_tables = tables.to(win.device)
         mean_io = m2_io = out_std = None
         for s in range(S):
             x = chain(den, win, evaluate, y, s, *inp[:2])
@@ -679,7 +725,16 @@ class VolumeInference:
             weight, shrink = 0., 0.
             if win.meas_up is not None:                      # the constant weight, or consistency_noise's own of this step
                 weight, shrink = (self.consistency[2], 0.) if win.noise_schedule is None else win.noise_schedule[i]
-            if win.meas_up is not None and weight > 0 and shrink > 0:      # consistency_noise: the step's own weight, its normals shaped
+            kind = None
+            if win.row_kinds is not None:                    # consistency_row_noise: plain (weight 0), constant weight, or the tables
+                kind, weight = win.row_kinds[i]
+            if kind == 'noise':                              # every direction's own weight, the normals shaped: one launch
+                form = 2 if den.sigma_space else 0
+                kx, k0, k2, k3 = (*den.coefs[i], 0.)[:4]
+                ops.volume_joint_consistent_tile_noise_step(*head, prev, win.meas_up, self.consistency[1], win.row_tables[i], form, kx, k0,
+                                                            0. if form == 0 else k2, k2 if form == 0 else k3, *tail, self.seed,
+                                                            draw=den.draw_base + 1 + i if den.sigma_space else i + 1, sample=s, **io)
+            elif win.meas_up is not None and weight > 0 and shrink > 0:    # consistency_noise: the step's own weight, its normals shaped
                 form = 2 if den.sigma_space else 0
                 kx, k0, k2, k3 = (*den.coefs[i], 0.)[:4]
                 ops.volume_joint_consistent_noise_step(*head, prev, win.meas_up, self.consistency[1], win.table, weight, shrink, form, kx, k0,

@@ -3272,6 +3272,218 @@ def volume_joint_consistent_noise_step(y, slot, taps, x_t, x0_prev, meas_up, cel
     return out, x0_out
 
 
+class TileNoiseOperator(TileOperator):
+    """What ``tile_noise_operator`` returns: a ``TileOperator`` (so ``tile_measure`` and ``tile_backproject`` take it) whose ``A`` is
+    the matrix as given -- ``tile_measure`` still simulates the acquisition -- and whose ``pinv`` is the EFFECTIVE pseudo-inverse
+    A_w+ diag(omega) [n, m] of the whitened operator A_w = diag(omega) A, omega_r = sigma_min / sigma_r.  ``table`` (P = A_w+ A_w),
+    ``rank`` and ``gain`` as there.  Float64 host tensors besides: ``singular`` [rank], the non-zero singular values of A_w,
+    ``basis`` [rank, n], its right singular vectors as rows, ``weights`` [m] = omega and ``row_noise`` [m] = sigma."""
+
+    def __init__(self, cell, A, pinv, table, rank, gain, singular, basis, weights, row_noise):
+        super().__init__(cell, A, pinv, table, rank, gain)
+        self.singular, self.basis, self.weights, self.row_noise = singular, basis, weights, row_noise
+
+    def __repr__(self):
+        return f"TileNoiseOperator(cell={self.cell}, m={self.m}, rank={self.rank}, gain={self.gain:.3g})"
+
+
+def tile_noise_operator(cell, A, row_noise):
+    """The host side of ``consistency_row_noise=`` (DDNM+ for a tile operator; ``ValueError`` naming "consistency_row_noise"; nothing
+    touches the device).  ``A`` as ``tile_operator`` takes it (a ``TileOperator`` gives its ``A``); ``row_noise`` the standard
+    deviation of the noise of each row of A: one finite number > 0, or a sequence of m of them (stacks: one value per stack, repeated
+    over its rows).  Whitening is unit-free: omega_r = sigma_min / sigma_r in (0, 1], A_w = diag(omega) A, and in float64 the SVD
+    A_w = U S V^T under ``tile_projector``'s zero and ambiguity thresholds.  t = (A_w+ diag omega) y is what ``tile_backproject``
+    makes of the raw y with the object returned; P = A_w+ A_w projects onto the row space of A as before, so the "blind to the tile
+    mean" refusal is ``tile_operator``'s.  With one number omega = 1 and everything is ``tile_operator``'s.  A
+    ``TileNoiseOperator`` given deviations proportional to its own (the same noise in other units: a z-score, a ``state_space``
+    slope) keeps its decomposition to the bit and takes the new values as ``row_noise``; otherwise it gives its matrix."""
+    import math
+    import numbers
+    who = "tile_noise_operator (consistency_row_noise)"
+    try:
+        base = tile_operator(cell, A)
+        if isinstance(A, TileNoiseOperator):                              # its pinv is an effective one: start again from the matrix
+            base = tile_operator(cell, A.A)
+    except ValueError as err:
+        raise ValueError(f"{err} (consistency_row_noise rides on consistency_operator)") from None
+    m = base.m
+
+    def number(v):
+        return not isinstance(v, bool) and isinstance(v, numbers.Real) and math.isfinite(v) and v > 0
+
+    if torch.is_tensor(row_noise) or type(row_noise).__module__ == 'numpy':
+        row_noise = row_noise.tolist()
+    if isinstance(row_noise, (tuple, list)):
+        if len(row_noise) != m or not all(number(v) for v in row_noise):
+            raise ValueError(f"{who}: consistency_row_noise must be one finite number > 0 or {m} of them, one per row of the operator, "
+                             f"got {row_noise!r}")
+        sigma = [float(v) for v in row_noise]
+    elif number(row_noise):
+        sigma = [float(row_noise)] * m
+    else:
+        raise ValueError(f"{who}: consistency_row_noise must be one finite number > 0 or a sequence of {m} of them, the standard "
+                         f"deviation of the noise of each row of the operator, got {row_noise!r}")
+    sigma = torch.tensor(sigma, dtype=torch.float64)
+    if isinstance(A, TileNoiseOperator):
+        ratio = sigma / A.row_noise
+        if bool(((ratio - ratio[0]).abs() <= 1e-12 * ratio[0]).all()):    # a change of units: whitening is unit-free
+            return TileNoiseOperator(A.cell, A.A, A.pinv, A.table, A.rank, A.gain, A.singular, A.basis, A.weights, sigma)
+    omega = sigma.min() / sigma
+    Aw = omega[:, None] * base.A
+    try:
+        pinv_w, proj, rank = tile_projector(Aw)
+    except ValueError as err:
+        raise ValueError(f"{err} (after whitening by consistency_row_noise)") from None
+    _, S, Vh = torch.linalg.svd(Aw, full_matrices=False)
+    keep = S / S[0] > 1e-10
+    table = proj.to(torch.float32).contiguous()
+    return TileNoiseOperator(base.cell, base.A, (pinv_w * omega[None, :]).contiguous(), table, rank,
+                             float(table.double().abs().sum(1).max()), S[keep].contiguous(), Vh[keep].contiguous(), omega, sigma)
+
+
+def _tile_noise_op(who, operator):
+    if not isinstance(operator, TileNoiseOperator):
+        raise ValueError(f"{who}: operator must be what ops.tile_noise_operator returns (consistency_row_noise), got "
+                         f"{type(operator).__name__}")
+
+
+def tile_noise_schedule(operator, rows, sigma, weight):
+    """The per-step, per-direction weights and noise reductions of ``consistency_row_noise``: float64 [T, rank, 2] =
+    (lambda_ij, shrink_ij).  Along the right singular vector v_j of the whitened operator the noise of t has the deviation
+    sigma_min / s_j, so direction j takes the scalar recursion as it is: ``consistency_noise_schedule(rows, s_j, sigma, weight)``,
+    history term, cap and the zero on rows with kn = 0 included.  ``sigma`` = sigma_min, the smallest row deviation, in the units the
+    chain projects in.  Null-space directions are not listed: their lambda and shrink are 0."""
+    who = "tile_noise_schedule"
+    _tile_noise_op(who, operator)
+    return torch.stack([consistency_noise_schedule(rows, float(s), sigma, weight) for s in operator.singular.tolist()], dim=1)
+
+
+def tile_noise_tables(operator, schedule):
+    """The tables the ``consistency_row_noise`` launches read, and how each step dispatches: ``(tables, kinds)``.  ``tables`` is the
+    fp32 host tensor [T, 2, n, n] = (M_i, G_i), M_i = V diag(lambda_i) V^T and G_i = V diag(shrink_i) V^T formed in float64,
+    symmetrised as (X + X^T) / 2 and rounded once to fp32 -- lambda is continuous in s, so the result does not depend on the basis the
+    SVD picked inside a repeated singular value.  ``kinds[i]`` = (kind, w), on the fp32 values of the schedule: ``('plain', 0.)`` when
+    every lambda is 0 (the family's plain step, no projection), ``('tile', w)`` when every shrink is 0 and every lambda equals w (the
+    constant-weight tile launch with P), else ``('noise', 0.)`` (the launches that read the tables)."""
+    who = "tile_noise_tables"
+    _tile_noise_op(who, operator)
+    if not torch.is_tensor(schedule) or schedule.ndim != 3 or tuple(schedule.shape[1:]) != (operator.rank, 2):
+        raise ValueError(f"{who}: the consistency_row_noise schedule must be [T, {operator.rank}, 2] (ops.tile_noise_schedule)")
+    schedule = schedule.double()
+    V = operator.basis.T                                                        # [n, rank]
+    tables = torch.einsum('qj,tjc,rj->tcqr', V, schedule, V)
+    tables = ((tables + tables.transpose(2, 3)) / 2).to(torch.float32).contiguous()
+    kinds = []
+    for step in schedule.to(torch.float32):                               # [rank, 2] of one step, as the device will see them
+        lam, shrink = step[:, 0].tolist(), step[:, 1].tolist()
+        if all(v == 0. for v in lam):
+            kinds.append(('plain', 0.))
+        elif all(v == 0. for v in shrink) and all(v == lam[0] for v in lam):
+            kinds.append(('tile', lam[0]))
+        else:
+            kinds.append(('noise', 0.))
+    return tables, kinds
+
+
+def tile_noise_lds(cell, P, edge=None):
+    """The bytes of LDS a ``consistency_row_noise`` launch plans for ``cell``: the fused joint launch (``edge`` None; ``P`` taps,
+    four box arrays, 2 n^2 table floats) or the per-window launch on cubes of edge ``edge`` (three box arrays clipped to the cube).
+    The entries refuse a plan above 65536 with DIQT_E_SHAPE."""
+    fz, fy, fx = cell
+    by, bx = fy * -(-4 // (fz * fy)), fx * -(-64 // fx)
+    n = fz * fy * fx
+    if edge is None:
+        return 4 * (int(P) + 4 * fz * by * bx + 2 * n * n)
+    return 4 * (3 * fz * min(by, edge) * min(bx, edge) + 2 * n * n)
+
+
+def tile_noise_plan(who, cell, P, edge=None):
+    """``ValueError`` naming "consistency_row_noise" for a cell whose launch plan exceeds 64 KiB of LDS (``tile_noise_lds``)."""
+    need = tile_noise_lds(cell, P, edge)
+    if need > 65536:
+        raise ValueError(f"{who}: consistency_row_noise with the cell {tuple(cell)} plans {need} bytes of LDS (the box arrays and two "
+                         f"{cell[0] * cell[1] * cell[2]}^2 tables), above the 65536 a launch may have")
+
+
+def _tile_noise_tables(who, tables, cell, like, device=True):
+    """The check of one step's ``tile_noise_tables`` handed to a kernel: fp32 [2, n, n], contiguous, on ``like``'s device
+    (``device`` False: the shape rules only)."""
+    n = cell[0] * cell[1] * cell[2]
+    if not torch.is_tensor(tables) or tables.dtype != torch.float32 or tuple(tables.shape) != (2, n, n) or not tables.is_contiguous():
+        raise ValueError(f"{who}: the consistency_row_noise tables of a step must be a contiguous fp32 [2, {n}, {n}] tensor "
+                         f"(ops.tile_noise_tables), got "
+                         f"{(tables.dtype, tuple(tables.shape)) if torch.is_tensor(tables) else type(tables).__name__}")
+    if tables.device != like.device:
+        raise ValueError(f"{who}: the consistency_row_noise tables are on {tables.device}, the data on {like.device}")
+    if device:
+        _chk(tables)
+
+
+def tile_project_noise(x0, target, noise, cell, tables_i, clamp=None, out=None, out_noise=None):
+    """One step's projection of ``consistency_row_noise`` (include/diqt.h, diqt_tile_project_noise): ``target`` [B,C,P,P,P] = windows
+    of t, ``noise`` the step's normals, a tensor of ``x0``'s shape, ``tables_i`` [2, n, n] = (M_i, G_i) of this step on ``x0``'s
+    device.  a = clamp(x0); per tile x0' = a + M_i (t - a) and noise' = noise - G_i noise (never clamped).  ``out`` / ``out_noise``:
+    where they go (``x0`` / ``noise`` themselves for in place; None: new tensors -- a caller's noise tensor is never modified unless
+    it is handed in as ``out_noise``).  Returns ``(x0', noise')``.  One launch."""
+    who = "tile_project_noise"
+    if torch.is_tensor(x0) and x0.ndim == 5:                              # the cell's and the tables' own rules first: they need no device
+        _tile_noise_tables(who, tables_i, consistency_cell(who, cell, 1.0, [(x0.shape[2], a) for a in range(3)])[0], x0, device=False)
+    _chk(x0, target, noise, out, out_noise)
+    if x0.ndim != 5 or x0.numel() == 0 or len(set(x0.shape[2:])) != 1:
+        raise ValueError(f"{who}: x0 must be a non-empty [B,C,P,P,P] tensor of cubes, got {tuple(x0.shape)}")
+    if out is None:
+        out = torch.empty_like(x0)
+    if out_noise is None:
+        out_noise = torch.empty_like(x0)
+    for t, name in ((target, 'target'), (noise, 'noise'), (out, 'out'), (out_noise, 'out_noise')):
+        if t.shape != x0.shape:
+            raise ValueError(f"{who}: {name} must have x0's shape {tuple(x0.shape)}, got {tuple(t.shape)}")
+    if not all(t.is_contiguous() for t in (x0, target, noise, out, out_noise)):
+        raise RuntimeError(f"{who}: tensors must be contiguous")
+    if out_noise.data_ptr() in (x0.data_ptr(), out.data_ptr(), target.data_ptr()) or out.data_ptr() in (noise.data_ptr(),
+                                                                                                        target.data_ptr()):
+        raise ValueError(f"{who}: out may alias only x0, out_noise only noise")
+    P = x0.shape[2]
+    cell, _ = consistency_cell(who, cell, 1.0, [(P, a) for a in range(3)])
+    _tile_noise_tables(who, tables_i, cell, x0)
+    tile_noise_plan(who, cell, 0, P)
+    lo, hi, mode = (0., 0., 2) if clamp is None else clamp                # the entry's third mode: no clamp
+    if clamp is not None and int(mode) not in (0, 1):
+        raise ValueError(f"{who}: clamp mode must be 0 (min) or 1 (box), got {mode!r}")
+    _lib.call("diqt_tile_project_noise", x0, target, noise, tables_i, out, out_noise, x0.shape[0] * x0.shape[1], P, *cell, float(lo),
+              float(hi), int(mode), _stream())
+    return out, out_noise
+
+
+def volume_joint_consistent_tile_noise_step(y, slot, taps, x_t, x0_prev, meas_up, cell, tables_i, form, kx, k0, kp, kn, lo, hi,
+                                            clamp_mode, stride, seed=0, draw=0, sample=0, out=None, x0_out=None):
+    """``volume_joint_consistent_tile_step`` for ``consistency_row_noise`` (include/diqt.h,
+    diqt_volume_joint_consistent_tile_noise_step): ``meas_up`` [D,H,W] = t in state space, ``tables_i`` [2, n, n] = (M_i, G_i) of this
+    step on ``x_t``'s device.  Every tile whose voxels are ALL covered has its fused x0 moved to x0 + M_i (t - x0) and its normals to
+    eps - G_i eps before the update; a tile with an uncovered voxel keeps both.  ``form`` 0 or 2 with ``kn != 0`` only.  The normals
+    are the plain launch's (same key, same draw number).  Returns ``(out, x0_out)``.  One launch, bit-reproducible."""
+    who = "volume_joint_consistent_tile_noise_step"
+    form = int(form)
+    if form not in (0, 2):
+        raise ValueError(f"{who}: form must be 0 (first order) or 2 (multistep with noise), got {form!r}")
+    if float(kn) == 0.0:
+        raise ValueError(f"{who}: kn == 0: a step without a normal has no consistency_row_noise shaping")
+    N, P, stride = _joint_windows(who, y, slot, taps, x_t, clamp_mode, stride)
+    seed, draw, sample = _noise_key(who, seed, draw, sample)
+    _joint_slots(who, slot, N)
+    cell, _ = consistency_cell(who, cell, 1.0, [(s, a) for a, s in enumerate(x_t.shape)])
+    _chk(meas_up)
+    if meas_up.shape != x_t.shape or not meas_up.is_contiguous():
+        raise ValueError(f"{who}: meas_up must be a contiguous tensor of x_t's shape")
+    _tile_noise_tables(who, tables_i, cell, x_t)
+    tile_noise_plan(who, cell, P)
+    out, x0_out = _joint_volumes(who, x_t, None if form == 0 else x0_prev, out, x0_out)
+    _lib.call("diqt_volume_joint_consistent_tile_noise_step", y if N else None, slot, taps, x_t, None if form == 0 else x0_prev, meas_up,
+              tables_i, out, x0_out, form, N, *x_t.shape, P, stride, *slot.shape, *cell, float(kx), float(k0), float(kp), float(kn),
+              float(lo), float(hi), int(clamp_mode), seed, draw, sample, _stream())
+    return out, x0_out
+
+
 def volume_joint_heun_init(shape, sigma0, kc, seed, draw=0, sample=0, device=None):
     """The first ``images_hat`` of a joint Heun chain (phase 0 of ``diqt_volume_joint_heun``): fp32 [D,H,W],
     ``(sigma0 n(draw)) + kc n(draw + 1)`` with n the volume-anchored normals of channel 0 -- the initial image as

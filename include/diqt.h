@@ -841,6 +841,31 @@ int diqt_volume_joint_consistent_tile_step(const float* y, const int* slot, cons
                                            int H, int W, int P, int stride, int G0, int G1, int G2, int fz, int fy, int fx, float weight,
                                            float kx, float k0, float kp, float kn, float lo, float hi, int clamp_mode,
                                            unsigned long long seed, unsigned draw, unsigned sample, void* stream);
+/* NOISE-AWARE consistency for a tile operator (DDNM+ with one weight per singular direction; ops.tile_noise_operator,
+ * ops.tile_noise_tables): the rows of A carry noise of their own deviations, so a step moves every right singular direction of the
+ * whitened operator by its own lambda and reduces the step's normals there by its own shrink.  `tables` is device fp32 [2][n][n] =
+ * M, G of ONE step, M = V diag(lambda) V^T and G = V diag(shrink) V^T, each symmetric to the bit (the caller's).  The arithmetic on the
+ * values a, the back-projected measurement t and the normals eps of one tile, fp32 with no contraction, ONE definition for both entries:
+ *     d[r] = t[r] - a[r];  s = 0;  s = fmaf(M[r][q], d[r], s) for r = 0 .. n - 1;  a'[q] = a[q] + s;
+ *     g = 0;  g = fmaf(G[r][q], eps[r], g) for r = 0 .. n - 1;  eps'[q] = eps[q] - g.     The normals are never clamped.
+ * diqt_tile_project_noise is the per-window step (imagen_pytorch3D.py, Imagen.p_sample_loop; elucidated_imagen.py,
+ * ElucidatedImagen._dpmpp2m_sample): diqt_tile_project's cubes and clamp modes, a = clamp(x0), `noise` a tensor of x0's shape.  A
+ * block reads its voxels before its barrier and writes them after it: out may alias x0 and out_noise may alias noise; nothing else may
+ * alias an output.  LDS: three box arrays and 2 n^2 floats; a plan above 64 KiB is DIQT_E_SHAPE.  Null pointer DIQT_E_ALIGN, a cell
+ * with n outside 2 .. 64 or a clamp_mode outside 0 .. 2 DIQT_E_UNSUPPORTED, a cell that does not divide P DIQT_E_SHAPE.              */
+int diqt_tile_project_noise(const float* x0, const float* target, const float* noise, const float* tables, float* out, float* out_noise,
+                            size_t cubes, int P, int fz, int fy, int fx, float lo, float hi, int clamp_mode, void* stream);
+/* diqt_volume_joint_consistent_tile_step with that arithmetic between the fuse and the update (inference.py, VolumeInference._chain):
+ * a = the fused x0, meas_up = t, eps = the step's Philox normals (key, draw and sample as the plain launch: the same normals), drawn
+ * in pass 1.  A tile is corrected and its normals shaped only when ALL n of its voxels are covered; otherwise it keeps its plain x0 and
+ * its plain normals.  Forms 0 and 2 with kn != 0 only (DIQT_E_UNSUPPORTED otherwise); window walk, aliasing pairs, uncovered voxels,
+ * the x0_out requirement and the other error codes are diqt_volume_joint_consistent_tile_step's.  LDS: the taps, four box arrays and
+ * 2 n^2 floats (n = 64: 32 KiB of tables); a plan above 64 KiB -- n = 64 with a box of 2048 voxels or more -- is DIQT_E_SHAPE.       */
+int diqt_volume_joint_consistent_tile_noise_step(const float* y, const int* slot, const float* taps, const float* x_t,
+                                                 const float* x0_prev, const float* meas_up, const float* tables, float* x_next,
+                                                 float* x0_out, int form, int N, int D, int H, int W, int P, int stride, int G0, int G1,
+                                                 int G2, int fz, int fy, int fx, float kx, float k0, float kp, float kn, float lo, float hi,
+                                                 int clamp_mode, unsigned long long seed, unsigned draw, unsigned sample, void* stream);
 /* The stochastic Heun sampler of the EDM family (Karras et al. 2022; elucidated_imagen.py:382-532) on the joint state: a churn, a
  * predictor and a corrector per step, two U-Net evaluations.  The state is three [D][H][W] volumes, all updated in place (every thread
  * reads only its own voxel of each, then writes it): xh = images_hat, xn = images_next, x0 = the fused prediction.  Window walk,
