@@ -196,6 +196,11 @@ PROTOTYPES = {
     "diqt_cell_project_noise": (I, [P] * 6 + [Z] + [I] * 4 + [F, F, F, F, I, P]),
     "diqt_volume_joint_consistent_noise_step": (I, [P] * 9 + [I] * 13 + [F] * 8 + [I, ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_uint,
                                                                                    P]),
+    "diqt_slab_measure": (I, [P, P, P] + [I] * 8 + [P]),
+    "diqt_slab_project": (I, [P, P, P, P, Z] + [I] * 6 + [F, F, F, I, P]),
+    "diqt_volume_joint_slab_coeffs": (I, [P] * 6 + [Z, P] + [I] * 14 + [F, F, I, P]),
+    "diqt_volume_joint_consistent_slab_step": (I, [P] * 8 + [Z, P, P] + [I] * 15 + [F] * 7 + [I, ctypes.c_ulonglong, ctypes.c_uint,
+                                                                                              ctypes.c_uint, P]),
     "diqt_volume_joint_heun": (I, [P] * 6 +[I] * 10 + [F] * 7 + [I, ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_uint, P]),
     "diqt_edm_inpaint_churn": (I, [P] * 8 + [I, Z, P]),
     "diqt_volume_joint_heun_inpaint": (I, [P] * 8 + [I] * 10 + [F] * 8 + [I, ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_uint,

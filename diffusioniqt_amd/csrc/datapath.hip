@@ -1162,6 +1162,304 @@ __global__ __launch_bounds__(256) void volume_joint_consistent_tile_noise_kernel
     }
 }
 
+// ---- data consistency for OVERLAPPING slice profiles (the slab operator, ops.slab_profile) --------------------------------------------
+// Slice s of column (cy, cx) measures y_s = sum_i u_z[i] (u_yx . x[s fz - r + i, cell]), i = 0 .. L - 1, L = fz + 2r, 1 <= r, 2r <= fz: a
+// slice overlaps its two neighbours only, a voxel lies under at most two slices, and along z A A^T = q G with G Toeplitz tridiagonal
+// (d = sum u_z^2, e = sum_{i < 2r} u_z[i] u_z[i + fz]) on every maximal run of consecutive ACTIVE rows -- rows whose whole support lies
+// inside the domain and is covered.  The table is flat fp32: u_z [L], u_yx [fy fx], g_yx = u_yx / q [fy fx], e, then for run position
+// j = 0 .. jmax - 1 the multipliers m_j = e / pi_{j-1} (m_0 = 0) and the inverse pivots ip_j = 1 / pi_j of the LDL^T sweep, made on the
+// host: no kernel divides.  ONE definition for the per-window kernel and the joint kernels, fp32 and kept from contraction:
+//   slab_plane     pm = 0; pm = fmaf(u_yx[q], a[q], pm) over the cell's fy fx voxels of one plane in (y, x) order;
+//   the row        acc = 0; acc = fmaf(u_z[i], pm[s fz - r + i], acc) over ascending i; rho_s = y_s - acc;
+//   slab_forward   zeta = rho at j = 0, else fmaf(-m_j, zeta_{s-1}, rho_s), over ascending s; a run restarts at j = 0;
+//   slab_backward  c_s = fmaf(-e, c_{s+1}, zeta_s) * ip_j over descending s, c_{s+1} = 0 at the end of a run;
+//   slab_shift     at depth z = k fz + o: t = 0; t = fmaf(u_z[.], c_s, t) over the active ones of s = k - 1 (o < r), k, k + 1
+//                  (o >= fz - r) inside [0, S), ascending; a' = fmaf(w * g_yx[q], t, a), w * g_yx one rounded product.  A voxel under no
+//                  active row keeps a's bits.
+struct Slab { int fz, fy, fx, r, jmax; };
+struct SlabTable { const float *uz, *uyx, *gyx, *m, *ip; };
+__device__ __forceinline__ SlabTable slab_table(Slab s, const float* t) {
+    const int L = s.fz + 2 * s.r, n = s.fy * s.fx;
+    return SlabTable{t, t + L, t + L + n, t + L + 2 * n + 1, t + L + 2 * n + 1 + s.jmax};
+}
+__device__ __forceinline__ float slab_e(Slab s, const float* t) { return t[s.fz + 2 * s.r + 2 * s.fy * s.fx]; }
+template <class Value>
+__device__ __forceinline__ float slab_plane(Slab s, const float* uyx, Value a) {
+#pragma clang fp contract(off)
+    float pm = 0.f;
+    int q = 0;
+    for (int j = 0; j < s.fy; ++j)
+        for (int k = 0; k < s.fx; ++k, ++q) pm = fmaf(uyx[q], a(j, k), pm);
+    return pm;
+}
+__device__ __forceinline__ float slab_forward(float m, float zprev, float rho, int j) {
+#pragma clang fp contract(off)
+    return j == 0 ? rho : fmaf(-m, zprev, rho);
+}
+__device__ __forceinline__ float slab_backward(float e, float cnext, float zeta, float ip) {
+#pragma clang fp contract(off)
+    const float t = fmaf(-e, cnext, zeta);
+    return t * ip;
+}
+// coef(s) is c_s and active(s) whether row s is active; both are asked only for 0 <= s < S.
+template <class Coef, class Active>
+__device__ __forceinline__ float slab_shift(Slab s, const float* uz, int S, int z, float w, float g, float a, Coef coef, Active active) {
+#pragma clang fp contract(off)
+    const int k = z / s.fz, o = z - k * s.fz;
+    float t = 0.f;
+    bool any = false;
+    if (o < s.r && k >= 1 && active(k - 1)) {
+        t = fmaf(uz[o + s.fz + s.r], coef(k - 1), t);
+        any = true;
+    }
+    if (active(k)) {
+        t = fmaf(uz[o + s.r], coef(k), t);
+        any = true;
+    }
+    if (o >= s.fz - s.r && k + 1 < S && active(k + 1)) {
+        t = fmaf(uz[o - s.fz + s.r], coef(k + 1), t);
+        any = true;
+    }
+    if (!any) return a;
+    const float wg = w * g;
+    return fmaf(wg, t, a);
+}
+// The operator itself (diqt_slab_measure): out [D / fz][H / fy][W / fx]; a row that leaves the volume takes the truncated sum (the
+// planes outside are skipped: they would add +0).  One thread per output, consecutive lanes = consecutive cells along x.
+__global__ __launch_bounds__(256) void slab_measure_kernel(const float* __restrict__ x, const float* __restrict__ table,
+                                                           float* __restrict__ out, size_t rows, int D, int H, int W, Slab sl) {
+#pragma clang fp contract(off)
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= rows) return;
+    const SlabTable tb = slab_table(sl, table);
+    const int cw = W / sl.fx, ch = H / sl.fy;
+    const int cx = (int)(e % cw), cy = (int)((e / cw) % ch), s = (int)(e / ((size_t)cw * ch));
+    const int L = sl.fz + 2 * sl.r;
+    float acc = 0.f;
+    for (int i = 0; i < L; ++i) {
+        const int z = s * sl.fz - sl.r + i;
+        if (z < 0 || z >= D) continue;
+        const float* base = x + ((size_t)z * H + (size_t)cy * sl.fy) * W + (size_t)cx * sl.fx;
+        const float pm = slab_plane(sl, tb.uyx, [&](int j, int k) { return base[(size_t)j * W + k]; });
+        acc = fmaf(tb.uz[i], pm, acc);
+    }
+    out[e] = acc;
+}
+// The per-window step (diqt_slab_project): `cubes` cubes of edge P, S = P / fz slices each; the domain is the cube, so rows 1 .. S - 2
+// are active and form ONE run (j = s - 1); rows 0 and S - 1 leave the cube and are never enforced.  One thread owns one column
+// (cube, cy, cx), consecutive lanes = consecutive cx.  It walks z once, adding every plane value to the (at most two) rows above it --
+// ascending z is ascending i for each of them -- then sweeps forward and backward over its S floats of LDS (col[s * 256], one bank per
+// lane), and walks z once more to write.  a = clamp(x0); every read of the column precedes its first write, so out may alias x0.
+__global__ __launch_bounds__(256) void slab_project_kernel(const float* x0, const float* __restrict__ meas_up,
+                                                           const float* __restrict__ table, float* out, size_t cols, int P, Slab sl,
+                                                           float w, ProjectClamp clamp) {
+#pragma clang fp contract(off)
+    extern __shared__ float slab_lds[];                 // [S][256]
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= cols) return;
+    const SlabTable tb = slab_table(sl, table);
+    const float ee = slab_e(sl, table);
+    const int S = P / sl.fz, cw = P / sl.fx, ch = P / sl.fy;
+    const int cx = (int)(e % cw), cy = (int)((e / cw) % ch);
+    const size_t cube = e / ((size_t)cw * ch);
+    const size_t base = ((cube * P) * P + (size_t)cy * sl.fy) * P + (size_t)cx * sl.fx;
+    auto at = [&](int z, int j, int k) { return base + ((size_t)z * P + j) * P + k; };
+    float* col = slab_lds + threadIdx.x;
+    for (int s = 0; s < S; ++s) col[s * 256] = 0.f;
+    for (int z = 0; z < P; ++z) {
+        const float pm = slab_plane(sl, tb.uyx, [&](int j, int k) { return clamp(x0[at(z, j, k)]); });
+        const int k = z / sl.fz, o = z - k * sl.fz;
+        if (o < sl.r && k >= 1) col[(k - 1) * 256] = fmaf(tb.uz[o + sl.fz + sl.r], pm, col[(k - 1) * 256]);
+        col[k * 256] = fmaf(tb.uz[o + sl.r], pm, col[k * 256]);
+        if (o >= sl.fz - sl.r && k + 1 < S) col[(k + 1) * 256] = fmaf(tb.uz[o - sl.fz + sl.r], pm, col[(k + 1) * 256]);
+    }
+    float run = 0.f;
+    for (int s = 1; s <= S - 2; ++s) {
+        const float rho = meas_up[at(s * sl.fz, 0, 0)] - col[s * 256];
+        run = slab_forward(tb.m[s - 1], run, rho, s - 1);
+        col[s * 256] = run;
+    }
+    run = 0.f;
+    for (int s = S - 2; s >= 1; --s) {
+        run = slab_backward(ee, run, col[s * 256], tb.ip[s - 1]);
+        col[s * 256] = run;
+    }
+    auto coef = [&](int s) { return col[s * 256]; };
+    auto active = [&](int s) { return s >= 1 && s <= S - 2; };
+    for (int z = 0; z < P; ++z) {
+        int q = 0;
+        for (int j = 0; j < sl.fy; ++j)
+            for (int k = 0; k < sl.fx; ++k, ++q) {
+                const size_t v = at(z, j, k);
+                out[v] = slab_shift(sl, tb.uz, S, z, w, tb.gyx[q], clamp(x0[v]), coef, active);
+            }
+    }
+}
+// The joint path needs a solve along the whole depth of the volume, so it is three launches per step where a box of cells takes one.
+// FIRST (diqt_volume_joint_slab_coeffs): per (z, cy, cx) the fy fx voxels of the plane are fused as in the linear kernel (joint_fuse,
+// the same StepClamp); pm = slab_plane of the fused x0 and covered = all of them have a window.  An uncovered plane stores pm = 0.
+// A block owns one plane of volume_joint_consistent_kernel's box, (by, bx) voxels of whole in-plane cells: every voxel is fused by a
+// thread of its own into LDS (lanes along x, so the windows' rows are read as in the other joint kernels), then one thread per cell
+// forms the plane value from LDS.
+__global__ __launch_bounds__(256) void volume_joint_slab_planes_kernel(const float* __restrict__ y, const int* __restrict__ slot,
+                                                                       const float* __restrict__ taps, const float* __restrict__ table,
+                                                                       float* __restrict__ pm_out, float* __restrict__ cov_out, int N,
+                                                                       int D, int H, int W, int P, int stride, int G0, int G1, int G2,
+                                                                       Slab sl, float lo, float hi, int clamp_mode) {
+    extern __shared__ float tp[];                      // [P], then x0s [nb] and den [nb]
+    const CellBox b = cell_box(Cell{1, sl.fy, sl.fx});
+    const int nb = b.by * b.bx, t = threadIdx.y * 64 + threadIdx.x;
+    float* x0s = tp + P;
+    float* dens = x0s + nb;
+    for (int e = t; e < P; e += 256) tp[e] = taps[e];
+    __syncthreads();
+    const int d = blockIdx.z, y0 = blockIdx.y * b.by, xb = blockIdx.x * b.bx;
+    for (int e = t; e < nb; e += 256) {
+        const int lx = e % b.bx, ly = e / b.bx;
+        const Voxel p{xb + lx, y0 + ly, d, 0, y0 + ly < H && xb + lx < W};
+        Fused f{0.f, 0.f};
+        if (p.inside) f = joint_fuse(y, slot, taps, tp, N, P, stride, G0, G1, G2, p, StepClamp{lo, hi, clamp_mode});
+        x0s[e] = f.covered() ? f.x0() : 0.f;
+        dens[e] = f.den;
+    }
+    __syncthreads();
+    const SlabTable tb = slab_table(sl, table);
+    const int cw = W / sl.fx, ch = H / sl.fy, cbx = b.bx / sl.fx, cby = b.by / sl.fy;
+    for (int e = t; e < cby * cbx; e += 256) {
+        const int lx = e % cbx, ly = e / cbx;
+        const int cx = xb / sl.fx + lx, cy = y0 / sl.fy + ly;
+        if (cx >= cw || cy >= ch) continue;            // H and W are multiples of the cell: a cell is inside the volume as a whole
+        bool all = true;
+        const float pm = slab_plane(sl, tb.uyx, [&](int j, int k) {
+            const int q = (ly * sl.fy + j) * b.bx + lx * sl.fx + k;
+            all = all && dens[q] != 0.f;
+            return x0s[q];
+        });
+        const size_t o = ((size_t)d * ch + cy) * cw + cx;
+        pm_out[o] = all ? pm : 0.f;
+        cov_out[o] = all ? 1.f : 0.f;
+    }
+}
+// SECOND (the same entry): per column (cy, cx) the rows, the residuals and the two sweeps over the whole depth.  Row s is active when
+// its support [s fz - r, s fz + fz + r) lies inside [0, D) and every plane of it is covered; a run restarts at j = 0 after an inactive
+// row.  Block (64, 4): 64 columns, and the rows of a column are shared out over threadIdx.y for the part that is parallel -- the row
+// sums and residuals, rho into `coef` and the activity into `act` -- then, after the barrier, the thread with threadIdx.y == 0 sweeps
+// its column: up (zeta into `coef`, the run position j + 1 into `act`, 0 for an inactive row) and down (c into `coef`; inactive rows
+// end with c = 0).  The sweeps read eight rows at a time ahead of the recurrence, whose steps do not depend on the loads.  What the
+// sweeping thread reads was written by threads of its own block before the barrier; no other block touches the column.
+// coef / act [D / fz][H / fy][W / fx]; y_s is read at voxel (s fz, cy fy, cx fx).
+__global__ __launch_bounds__(256) void volume_joint_slab_solve_kernel(const float* __restrict__ pm, const float* __restrict__ cov,
+                                                                      const float* __restrict__ meas_up, const float* __restrict__ table,
+                                                                      float* coef, float* act, size_t cols, int D, int H, int W,
+                                                                      Slab sl) {
+#pragma clang fp contract(off)
+    const size_t e = (size_t)blockIdx.x * 64 + threadIdx.x;
+    const bool inside = e < cols;
+    const SlabTable tb = slab_table(sl, table);
+    const float ee = slab_e(sl, table);
+    const int S = D / sl.fz, cw = W / sl.fx, L = sl.fz + 2 * sl.r;
+    const int cx = inside ? (int)(e % cw) : 0, cy = inside ? (int)(e / cw) : 0;
+    if (inside)
+        for (int s = threadIdx.y; s < S; s += 4) {
+            const int z0 = s * sl.fz - sl.r;
+            bool on = z0 >= 0 && z0 + L <= D;
+            float acc = 0.f;
+            if (on)
+                for (int i = 0; i < L; ++i) {
+                    const size_t p = (size_t)(z0 + i) * cols + e;
+                    on = on && cov[p] != 0.f;
+                    acc = fmaf(tb.uz[i], pm[p], acc);
+                }
+            const float ys = meas_up[((size_t)(s * sl.fz) * H + (size_t)cy * sl.fy) * W + (size_t)cx * sl.fx];
+            coef[(size_t)s * cols + e] = on ? ys - acc : 0.f;
+            act[(size_t)s * cols + e] = on ? 1.f : 0.f;
+        }
+    __syncthreads();
+    if (!inside || threadIdx.y != 0) return;
+    int j = 0;
+    float run = 0.f;
+    for (int s0 = 0; s0 < S; s0 += 8) {
+        float rho[8], on[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const size_t o = (size_t)min(s0 + u, S - 1) * cols + e;
+            rho[u] = coef[o];
+            on[u] = act[o];
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            if (s0 + u >= S) break;
+            const size_t o = (size_t)(s0 + u) * cols + e;
+            if (on[u] != 0.f) {
+                run = slab_forward(tb.m[j], run, rho[u], j);
+                coef[o] = run;
+                act[o] = (float)(j + 1);
+                ++j;
+            } else {
+                j = 0;
+            }
+        }
+    }
+    run = 0.f;
+    for (int s0 = S - 1; s0 >= 0; s0 -= 8) {
+        float zeta[8], pos[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const size_t o = (size_t)max(s0 - u, 0) * cols + e;
+            zeta[u] = coef[o];
+            pos[u] = act[o];
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            if (s0 - u < 0) break;
+            const int at = (int)pos[u];
+            if (at) {
+                run = slab_backward(ee, run, zeta[u], tb.ip[at - 1]);
+                coef[(size_t)(s0 - u) * cols + e] = run;
+            } else {
+                run = 0.f;
+            }
+        }
+    }
+}
+// THIRD (diqt_volume_joint_consistent_slab_step): volume_joint_linear_kernel's three update forms with slab_shift between the fuse and
+// the update, c and the activity read from the coefficient volumes of the second launch.  A covered voxel under no active row takes
+// the update with its plain x0; an uncovered voxel keeps x_t and gets x0_out = 0; normals and draw numbering are the linear kernel's.
+// Every thread reads only its own voxel of x_t / x0_prev, then writes it: x_next may alias x_t and x0_out may alias x0_prev.
+__global__ __launch_bounds__(256) void volume_joint_slab_kernel(const float* __restrict__ y, const int* __restrict__ slot,
+                                                                const float* __restrict__ taps, const float* x_t, const float* x0_prev,
+                                                                const float* __restrict__ table, const float* __restrict__ coef,
+                                                                const float* __restrict__ act, float* x_next, float* x0_out, int N, int D,
+                                                                int H, int W, int P, int stride, int G0, int G1, int G2, Slab sl, float w,
+                                                                float kx, float k0, float kp, float kn, float lo, float hi, int clamp_mode,
+                                                                int third_is_normal, unsigned key0, unsigned key1, unsigned draw,
+                                                                unsigned sample) {
+    extern __shared__ float tp[];                      // [P]
+    const Voxel p = walk_prologue(tp, taps, P, true, H, W);
+    if (!p.inside) return;
+    const size_t v = p.v;
+    const unsigned v0 = (unsigned)v, v1 = (unsigned)((unsigned long long)v >> 32);
+    const Fused f = joint_fuse(y, slot, taps, tp, N, P, stride, G0, G1, G2, p, StepClamp{lo, hi, clamp_mode});
+    const float xt = x_t[v];
+    if (!f.covered()) {
+        x_next[v] = xt;
+        x0_out[v] = 0.f;
+        return;
+    }
+    const SlabTable tb = slab_table(sl, table);
+    const int cw = W / sl.fx, ch = H / sl.fy, cy = p.h / sl.fy, cx = p.x / sl.fx;
+    const size_t cols = (size_t)cw * ch, col = (size_t)cy * cw + cx;
+    const float g = tb.gyx[(p.h - cy * sl.fy) * sl.fx + (p.x - cx * sl.fx)];
+    const float x0 = slab_shift(sl, tb.uz, D / sl.fz, p.d, w, g, f.x0(), [&](int s) { return coef[(size_t)s * cols + col]; },
+                                [&](int s) { return act[(size_t)s * cols + col] != 0.f; });
+    const float prev = x0_prev ? x0_prev[v] : 0.f;
+    float n = 0.f;
+    if (kn != 0.f) n = philox_normal(philox4x32_10(v0, v1, draw, sample, key0, key1));
+    const float r = third_is_normal ? sampler_update(kx, xt, k0, x0, kn, n) : sampler_update_sde(kx, xt, k0, x0, kp, prev, kn, n);
+    x0_out[v] = x0;
+    x_next[v] = r;
+}
+
 // The stochastic Heun sampler of the EDM family (elucidated_imagen.py:382-532) on the same state: a churn, a predictor and a corrector
 // per step, two U-Net evaluations, so the state is three volumes -- xh = images_hat, xn = images_next, x0 = the fused prediction (the
 // one self-conditioning reads) -- and the launch takes a `phase`, uniform over the grid:
@@ -2000,6 +2298,121 @@ extern "C" int diqt_volume_joint_consistent_tile_noise_step(const float* y, cons
     return joint_consistent_launch(who, y, slot, taps, x_t, x0_prev, meas_up, tables, x_next, x0_out, form, N, D, H, W, P, stride, G0, G1,
                                    G2, fz, fy, fx, 1.f, kx, k0, kp, kn, lo, hi, clamp_mode, seed, draw, sample, stream, false, 0.f, false,
                                    true);
+}
+
+// The cell, the reach and the table length of the slab entries: cell_ok's rules, 1 <= r, 2r <= fz and jmax >= 1.
+static int slab_ok(const char* who, int fz, int fy, int fx, int r, int jmax, float w) {
+    int rc = cell_ok(who, fz, fy, fx, w);
+    if (rc) return rc;
+    DIQT_REQUIRE(r >= 1 && 2 * r <= fz, DIQT_E_UNSUPPORTED, "%s: reach %d (1 <= r and 2r <= fz = %d)", who, r, fz);
+    DIQT_REQUIRE(jmax >= 1, DIQT_E_UNSUPPORTED, "%s: a table of %d run positions", who, jmax);
+    return DIQT_OK;
+}
+
+extern "C" int diqt_slab_measure(const float* x, const float* table, float* out, int D, int H, int W, int fz, int fy, int fx, int r,
+                                 int jmax, void* stream) {
+    DIQT_REQUIRE(x && table && out, DIQT_E_ALIGN, "slab_measure: null pointer");
+    int rc = slab_ok("slab_measure", fz, fy, fx, r, jmax, 1.f);
+    if (rc) return rc;
+    DIQT_REQUIRE(D > 0 && H > 0 && W > 0 && D % fz == 0 && H % fy == 0 && W % fx == 0, DIQT_E_SHAPE,
+                 "slab_measure: the cell %dx%dx%d does not divide the volume %dx%dx%d", fz, fy, fx, D, H, W);
+    const size_t rows = (size_t)(D / fz) * (H / fy) * (W / fx);
+    DIQT_REQUIRE((rows + 255) / 256 <= 0x7fffffffu, DIQT_E_SHAPE, "slab_measure: more than 2^31 - 1 blocks");
+    hipLaunchKernelGGL(slab_measure_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, STREAM, x, table, out, rows, D, H, W,
+                       Slab{fz, fy, fx, r, jmax});
+    return check_launch("slab_measure");
+}
+
+extern "C" int diqt_slab_project(const float* x0, const float* meas_up, const float* table, float* out, size_t cubes, int P, int fz,
+                                 int fy, int fx, int r, int jmax, float weight, float lo, float hi, int clamp_mode, void* stream) {
+    DIQT_REQUIRE(x0 && meas_up && table && out, DIQT_E_ALIGN, "slab_project: null pointer");
+    int rc = slab_ok("slab_project", fz, fy, fx, r, jmax, weight);
+    if (rc) return rc;
+    DIQT_REQUIRE(clamp_mode >= 0 && clamp_mode <= 2, DIQT_E_UNSUPPORTED, "slab_project: clamp_mode %d (0 = min, 1 = box, 2 = none)",
+                 clamp_mode);
+    DIQT_REQUIRE(cubes > 0 && P > 0 && P % fz == 0 && P % fy == 0 && P % fx == 0, DIQT_E_SHAPE,
+                 "slab_project: the cell %dx%dx%d does not divide the %zu cubes of edge %d", fz, fy, fx, cubes, P);
+    const int S = P / fz;
+    DIQT_REQUIRE(jmax >= S, DIQT_E_SHAPE, "slab_project: the table has %d run positions, a cube has %d slices", jmax, S);
+    const size_t lds = (size_t)S * 256 * sizeof(float);
+    DIQT_REQUIRE(lds <= 65536, DIQT_E_SHAPE, "slab_project: %d slices need %zu bytes of LDS", S, lds);
+    const size_t cols = cubes * (size_t)(P / fy) * (P / fx);
+    DIQT_REQUIRE((cols + 255) / 256 <= 0x7fffffffu, DIQT_E_SHAPE, "slab_project: more than 2^31 - 1 blocks");
+    hipLaunchKernelGGL(slab_project_kernel, dim3((unsigned)((cols + 255) / 256)), dim3(256), lds, STREAM, x0, meas_up, table, out, cols, P,
+                       Slab{fz, fy, fx, r, jmax}, weight, ProjectClamp{lo, hi, clamp_mode});
+    return check_launch("slab_project");
+}
+
+// The workspace of the two joint slab entries, in floats: pm [D][ch][cw], covered [D][ch][cw], then the run positions [D / fz][ch][cw].
+static size_t slab_workspace_floats(int D, int H, int W, int fz, int fy, int fx) {
+    return (size_t)(2 * (size_t)D + D / fz) * (H / fy) * (W / fx);
+}
+static int joint_slab_ok(const char* who, int D, int H, int W, int fz, int fy, int fx, int jmax, size_t workspace_floats) {
+    DIQT_REQUIRE(D > 0 && H > 0 && W > 0 && D % fz == 0 && H % fy == 0 && W % fx == 0, DIQT_E_SHAPE,
+                 "%s: the cell %dx%dx%d does not divide the volume %dx%dx%d", who, fz, fy, fx, D, H, W);
+    DIQT_REQUIRE(jmax >= D / fz, DIQT_E_SHAPE, "%s: the table has %d run positions, the volume has %d slices", who, jmax, D / fz);
+    DIQT_REQUIRE(workspace_floats >= slab_workspace_floats(D, H, W, fz, fy, fx), DIQT_E_SHAPE, "%s: the workspace holds %zu floats, %zu needed",
+                 who, workspace_floats, slab_workspace_floats(D, H, W, fz, fy, fx));
+    return DIQT_OK;
+}
+
+extern "C" int diqt_volume_joint_slab_coeffs(const float* y, const int* slot, const float* taps, const float* meas_up, const float* table,
+                                             float* workspace, size_t workspace_floats, float* coef, int N, int D, int H, int W, int P,
+                                             int stride, int G0, int G1, int G2, int fz, int fy, int fx, int r, int jmax, float lo,
+                                             float hi, int clamp_mode, void* stream) {
+    const char* who = "volume_joint_slab_coeffs";
+    DIQT_REQUIRE(meas_up && table && workspace && coef && slot && taps && (y || N == 0), DIQT_E_ALIGN, "%s: null pointer", who);
+    int rc = slab_ok(who, fz, fy, fx, r, jmax, 1.f);
+    if (rc) return rc;
+    JointGrid g;
+    rc = joint_launch_plan(who, coef, true, true, N, D, H, W, P, stride, G0, G1, G2, clamp_mode, g);
+    if (rc) return rc;
+    rc = joint_slab_ok(who, D, H, W, fz, fy, fx, jmax, workspace_floats);
+    if (rc) return rc;
+    const int cw = W / fx, ch = H / fy;
+    const size_t cols = (size_t)cw * ch, planes = (size_t)D * cols;
+    DIQT_REQUIRE((cols + 63) / 64 <= 0x7fffffffu, DIQT_E_SHAPE, "%s: more than 2^31 - 1 blocks", who);
+    const Slab sl{fz, fy, fx, r, jmax};
+    const CellBox b = cell_box(Cell{1, fy, fx});
+    const size_t lds = ((size_t)P + 2 * (size_t)b.by * b.bx) * sizeof(float);
+    DIQT_REQUIRE(lds <= 65536, DIQT_E_SHAPE, "%s: P %d needs %zu bytes of LDS", who, P, lds);
+    DIQT_REQUIRE((H + b.by - 1) / b.by <= 65535, DIQT_E_SHAPE, "%s: more than 65535 rows of boxes", who);
+    hipLaunchKernelGGL(volume_joint_slab_planes_kernel, dim3((W + b.bx - 1) / b.bx, (H + b.by - 1) / b.by, D), dim3(64, 4), lds, STREAM, y,
+                       slot, taps, table, workspace, workspace + planes, N, D, H, W, P, stride, G0, G1, G2, sl, lo, hi, clamp_mode);
+    rc = check_launch(who);
+    if (rc) return rc;
+    hipLaunchKernelGGL(volume_joint_slab_solve_kernel, dim3((unsigned)((cols + 63) / 64)), dim3(64, 4), 0, STREAM, workspace,
+                       workspace + planes, meas_up, table, coef, workspace + 2 * planes, cols, D, H, W, sl);
+    return check_launch(who);
+}
+
+extern "C" int diqt_volume_joint_consistent_slab_step(const float* y, const int* slot, const float* taps, const float* x_t,
+                                                      const float* x0_prev, const float* table, const float* coef, const float* workspace,
+                                                      size_t workspace_floats, float* x_next, float* x0_out, int form, int N, int D, int H,
+                                                      int W, int P, int stride, int G0, int G1, int G2, int fz, int fy, int fx, int r,
+                                                      int jmax, float weight, float kx, float k0, float kp, float kn, float lo, float hi,
+                                                      int clamp_mode, unsigned long long seed, unsigned draw, unsigned sample,
+                                                      void* stream) {
+    const char* who = "volume_joint_consistent_slab_step";
+    DIQT_REQUIRE(x_t && table && coef && workspace && x_next && x0_out && slot && taps && (y || N == 0), DIQT_E_ALIGN, "%s: null pointer",
+                 who);
+    DIQT_REQUIRE(form >= 0 && form <= 2, DIQT_E_UNSUPPORTED, "%s: form %d (0 = first order, 1 = multistep, 2 = multistep with noise)", who,
+                 form);
+    int rc = slab_ok(who, fz, fy, fx, r, jmax, weight);
+    if (rc) return rc;
+    JointGrid g;
+    rc = joint_launch_plan(who, x_next, true, true, N, D, H, W, P, stride, G0, G1, G2, clamp_mode, g);
+    if (rc) return rc;
+    rc = joint_slab_ok(who, D, H, W, fz, fy, fx, jmax, workspace_floats);
+    if (rc) return rc;
+    // first order: no history; multistep: no normal (and with it no key)
+    const bool first = form == 0, noisy = form != 1;
+    const size_t planes = (size_t)D * (H / fy) * (W / fx);
+    hipLaunchKernelGGL(volume_joint_slab_kernel, g.grid, dim3(64, 4), g.lds, STREAM, y, slot, taps, x_t, first ? nullptr : x0_prev, table,
+                       coef, workspace + 2 * planes, x_next, x0_out, N, D, H, W, P, stride, G0, G1, G2, Slab{fz, fy, fx, r, jmax}, weight,
+                       kx, k0, first ? 0.f : kp, noisy ? kn : 0.f, lo, hi, clamp_mode, first ? 1 : 0, (unsigned)seed,
+                       (unsigned)(seed >> 32), draw, sample);
+    return check_launch(who);
 }
 
 extern "C" int diqt_volume_joint_heun(const float* y, const int* slot, const float* taps, float* xh, float* xn, float* x0, int phase, int N,

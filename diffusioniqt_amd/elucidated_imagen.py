@@ -24,7 +24,7 @@ from .imagen_pytorch3D import (GaussianDiffusionContinuousTimes, Unet, NullUnet,
                                normalize_neg_one_to_one, unnormalize_zero_to_one, eval_decorator, to_channels_last,
                                to_channels_first, log_snr_to_alpha_sigma, check_consistency, check_consistency_operator,
                                naming_consistency_noise, naming_consistency_row_noise, check_consistency_row_noise,
-                               scale_consistency_row_noise, consistency_row_noise_chain)
+                               scale_consistency_row_noise, consistency_row_noise_chain, check_consistency_slab)
 from .imagen_video import Unet3D
 
 Hparams_fields = ['num_sample_steps', 'sigma_min', 'sigma_max', 'sigma_data', 'rho', 'P_mean', 'P_std', 'S_churn', 'S_tmin',
@@ -421,7 +421,7 @@ class ElucidatedImagen(nn.Module):
                         inpaint_images=None, inpaint_masks=None, inpaint_resample_times=5, init_images=None,
                         skip_steps=None, sigma_min=None, sigma_max=None, noise=None, sampler='heun', sample_steps=None, eta=0.,
                         consistency=None, consistency_weight=1., consistency_profile=None, consistency_noise=None,
-                        consistency_operator=None, consistency_row_noise=None, **kwargs):
+                        consistency_operator=None, consistency_row_noise=None, consistency_slab=None, **kwargs):
         """Stochastic Heun sampler (:382-532).  ``noise``: optional injected list [init, step_0, ...], or a callable
         ``noise(shape) -> fp32 device tensor`` whose successive calls are those draws (one ``eps`` per step, also when gamma is 0).
 
@@ -462,9 +462,16 @@ class ElucidatedImagen(nn.Module):
         any other step runs ONE ``ops.tile_project_noise`` on the step's draw.  ``ValueError`` naming "consistency_row_noise":
         without ``consistency_operator``, with ``consistency_noise`` or ``consistency_profile``, eta = 0, values
         ``ops.tile_noise_operator`` refuses, an LDS plan above 64 KiB, and everything ``consistency`` / ``consistency_operator``
-        refuse."""
+        refuse.
+        ``consistency_slab=(pz, py, px)`` (with ``consistency``; ``ops.slab_profile``): slice profiles that overlap between
+        neighbouring cells along z (``pz`` has fz + 2r entries, 1 <= r <= fz / 2); every ``ops.cell_project`` of the chain is one
+        ``ops.slab_project``, DDNM on the slices whose support lies inside the cube by one tridiagonal solve per column.
+        ``ValueError`` naming "consistency_slab": without ``consistency``, together with any of the four keywords above, a profile
+        ``ops.slab_profile`` refuses, and everything ``consistency`` refuses."""
         self._check_sampler_args(sampler, sample_steps, skip_steps, eta)
         has_inpainting = self._check_inpaint_args(sampler, inpaint_images, inpaint_masks, inpaint_resample_times)
+        check_consistency_slab('one_unet_sample', consistency_slab, exists(consistency), consistency_profile, consistency_noise,
+                               consistency_operator, consistency_row_noise)
         check_consistency_row_noise('one_unet_sample', consistency_row_noise, consistency_operator, consistency_profile,
                                     consistency_noise, eta != 0)
         with naming_consistency_row_noise(consistency_row_noise):
@@ -472,7 +479,8 @@ class ElucidatedImagen(nn.Module):
                                        consistency_noise)
             with naming_consistency_noise(consistency_noise):
                 consistency = check_consistency('one_unet_sample', consistency, consistency_weight, shape, has_inpainting, init_images,
-                                                skip_steps, sampler, profile=consistency_profile, operator=consistency_operator)
+                                                skip_steps, sampler, profile=consistency_profile, operator=consistency_operator,
+                                                slab=consistency_slab)
         if exists(consistency_noise):
             consistency_noise = ops.consistency_noise_sigma('one_unet_sample', consistency_noise, exists(consistency), eta != 0)
         consistency, table = (consistency[:3], consistency[3]) if exists(consistency) else (None, None)
@@ -481,7 +489,7 @@ class ElucidatedImagen(nn.Module):
                                         cond_scale=cond_scale, init_images=init_images, sigma_min=sigma_min, sigma_max=sigma_max,
                                         noise=noise, sample_steps=sample_steps, eta=eta, consistency=consistency,
                                         consistency_profile=table, consistency_noise=consistency_noise,
-                                        tile=exists(consistency_operator),
+                                        tile=exists(consistency_operator), slab=exists(consistency_slab),
                                         row_noise=(consistency_operator, consistency_row_noise) if exists(consistency_row_noise)
                                         else None, **kwargs)
         # Inpainting (:441-449, 473-530; RePaint, Lugmayr et al. 2022) is this loop with ``inpaint_resample_times`` passes per step,
@@ -550,10 +558,10 @@ class ElucidatedImagen(nn.Module):
 
     def _dpmpp2m_sample(self, unet, shape, *, unet_number, clamp, dynamic_threshold, cond_scale, init_images, sigma_min, sigma_max, noise,
                         sample_steps, eta, consistency=None, consistency_profile=None, consistency_noise=None, tile=False, row_noise=None,
-                        **kwargs):
+                        slab=False, **kwargs):
         """``one_unet_sample(sampler='dpmpp2m')``; the arguments are checked there (``consistency``: None or the checked
         ``(meas_up, cell, weight)``, ``meas_up`` in state space; ``consistency_profile``: None or the checked host table of
-        ``ops.cell_profile``; ``consistency_noise``: None or the checked deviation in state space; ``tile``: the table is a
+        ``ops.cell_profile``, or (``slab``) the table of a ``consistency_slab``; ``consistency_noise``: None or the checked deviation in state space; ``tile``: the table is a
         ``consistency_operator``'s projector and ``meas_up`` its t; ``row_noise``: None or (operator,
         ``consistency_row_noise`` in state space))."""
         sigmas, coefs = self._dpmpp2m_tables(unet_number - 1, sample_steps, eta, sigma_min, sigma_max)
@@ -590,6 +598,7 @@ class ElucidatedImagen(nn.Module):
                 out, shaped = ops.cell_project_noise(out, meas_up, draw(), cell, weight, shrink, table)   # kn != 0 here: the step's draw
             elif exists(consistency) and weight > 0:                            # ``out`` arrives clamped or thresholded
                 out = ops.tile_project(out, meas_up, cell, table, weight) if tile else \
+                    ops.slab_project(out, meas_up, cell, table, weight) if slab else \
                     ops.cell_project_profile(out, meas_up, cell, table, weight) if exists(table) else \
                     ops.cell_project(out, meas_up, cell, weight)
             eps = shaped if exists(shaped) else draw() if stochastic[i] else None
@@ -661,7 +670,8 @@ class ElucidatedImagen(nn.Module):
                batch_size=1, cond_scale=1., lowres_sample_noise_level=None, start_at_unet_number=1, start_image_or_video=None,
                stop_at_unet_number=None, return_all_unet_outputs=False, return_pil_images=False, use_tqdm=True, device=None,
                noise=None, sampler='heun', sample_steps=None, eta=0., consistency=None, consistency_weight=1.,
-               consistency_profile=None, consistency_noise=None, consistency_operator=None, consistency_row_noise=None):
+               consistency_profile=None, consistency_noise=None, consistency_operator=None, consistency_row_noise=None,
+               consistency_slab=None):
         """:536-702.  ``noise``: optional injected list [lowres_noise, init, step_0, ...] per sampled unet (tests), or -- when exactly
         one U-Net is sampled -- a callable ``noise(shape) -> fp32 device tensor`` whose successive calls are those draws in that order
         (``inference.AnchoredNoise.source``: call k is draw k of the volume-anchored field).
@@ -688,7 +698,9 @@ class ElucidatedImagen(nn.Module):
         refusal above then also names "consistency_noise", as do its own.  ``consistency_operator=A``: ``one_unet_sample``'s
         tile-local linear measurement; ``consistency`` then carries t = A+ y in the units this returns, and its refusals name
         "consistency_operator".  ``consistency_row_noise=sigma``: ``one_unet_sample``'s, in the units of ``target_up`` as passed
-        here (multiplied by the slope of ``normalize_img``); every refusal above then also names "consistency_row_noise"."""
+        here (multiplied by the slope of ``normalize_img``); every refusal above then also names "consistency_row_noise".
+        ``consistency_slab=(pz, py, px)``: ``one_unet_sample``'s overlapping slice profiles; its refusals, and those of
+        ``consistency`` when it is given, name "consistency_slab"."""
         assert texts is None and text_embeds is None and not return_pil_images
         samplers, steps_per_unet, etas = (cast_tuple(v, len(self.unets)) for v in (sampler, sample_steps, eta))
         for args in zip(samplers, steps_per_unet, cast_tuple(skip_steps, len(self.unets)), etas):
@@ -696,6 +708,8 @@ class ElucidatedImagen(nn.Module):
         sampled_samplers = samplers[start_at_unet_number - 1:default(stop_at_unet_number, len(self.unets))]
         has_inpainting = any([self._check_inpaint_args(s, inpaint_images, inpaint_masks, inpaint_resample_times)
                               for s in sampled_samplers or samplers[-1:]])
+        check_consistency_slab('sample', consistency_slab, exists(consistency), consistency_profile, consistency_noise,
+                               consistency_operator, consistency_row_noise)
         check_consistency_row_noise('sample', consistency_row_noise, consistency_operator, consistency_profile, consistency_noise)
         with naming_consistency_row_noise(consistency_row_noise):
             check_consistency_operator('sample', consistency_operator, exists(consistency), consistency_profile, consistency_noise)
@@ -712,7 +726,7 @@ class ElucidatedImagen(nn.Module):
                                       (batch_size, self.channels, *frames[n - 1], self.image_sizes[n - 1], self.image_sizes[n - 1]),
                                       exists(inpaint_images), cast_tuple(init_images, len(self.unets))[n - 1],
                                       cast_tuple(skip_steps, len(self.unets))[n - 1], samplers[n - 1], profile=consistency_profile,
-                                      operator=consistency_operator)
+                                      operator=consistency_operator, slab=consistency_slab)
                 if exists(consistency_noise):
                     ops.consistency_noise_sigma('sample', consistency_noise, True, etas[n - 1] != 0)
                 if exists(consistency_row_noise):
@@ -779,6 +793,8 @@ class ElucidatedImagen(nn.Module):
                     multistep.update(consistency_operator=consistency_operator)
                 if exists(consistency_row_noise):
                     multistep.update(consistency_row_noise=consistency_row_noise)
+                if exists(consistency_slab):
+                    multistep.update(consistency_slab=consistency_slab)
             inpaint = {}
             if has_inpainting:
                 inpaint = dict(inpaint_images=inpaint_images, inpaint_masks=inpaint_masks, inpaint_resample_times=inpaint_resample_times)

@@ -1167,8 +1167,38 @@ def check_consistency_operator(who, operator, has_consistency, profile=None, noi
                          f"weight per singular direction: that is consistency_row_noise)")
 
 
+def check_consistency_slab(who, slab, has_consistency, profile=None, noise=None, operator=None, row_noise=None):
+    """The host rules of ``consistency_slab=`` beside its neighbours (``ValueError`` naming "consistency_slab"; nothing touches the
+    device): it rides on ``consistency`` and goes with none of ``consistency_profile`` (the profile cut at the cell border),
+    ``consistency_noise``, ``consistency_operator`` and ``consistency_row_noise`` (noise-aware weights are not offered for it)."""
+    if slab is None:
+        return
+    if not has_consistency:
+        raise ValueError(f"{who}: consistency_slab needs consistency=(meas_up, cell)")
+    for other, name in ((profile, 'consistency_profile'), (noise, 'consistency_noise'), (operator, 'consistency_operator'),
+                        (row_noise, 'consistency_row_noise')):
+        if other is not None:
+            raise ValueError(f"{who}: consistency_slab and {name} are not offered together")
+
+
+class naming_consistency_slab:
+    """``naming_consistency_noise`` for ``consistency_slab``, which rides on ``consistency``: what that refuses keeps its wording and
+    also names "consistency_slab"."""
+
+    def __init__(self, slab):
+        self.slab = slab
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, kind, err, tb):
+        if kind is ValueError and self.slab is not None and 'consistency_slab' not in str(err):
+            raise ValueError(f"{err} (consistency_slab rides on consistency)") from None
+        return False
+
+
 def check_consistency(who, consistency, weight, shape, has_inpainting=False, init_images=None, skip_steps=None, sampler=None,
-                      profile=None, operator=None):
+                      profile=None, operator=None, slab=None):
     """The argument rules of ``consistency=(meas_up, cell)`` / ``consistency_weight`` of the one-call samplers of both families
     (``ValueError`` naming "consistency"; nothing touches the device).  ``shape`` = the [B,C,P,P,P] the sampler generates: ``meas_up``
     must be a float tensor of exactly that shape, the cell must divide P.  Data consistency (DDNM) replaces the cell means of every x0
@@ -1178,7 +1208,15 @@ def check_consistency(who, consistency, weight, shape, has_inpainting=False, ini
     (off) or ``(meas_up, cell, weight, table)``, ``table`` None without a profile, else ``ops.cell_profile``'s host table.
     ``operator`` = the ``consistency_operator`` (an [m, n] matrix or ``ops.tile_operator``'s object; with neither a profile nor
     ``consistency_noise``, ``check_consistency_operator``): ``meas_up`` then carries t = A+ y and ``table`` is the operator's fp32
-    [n, n] projector, which ``ops.tile_project`` takes."""
+    [n, n] projector, which ``ops.tile_project`` takes.  ``slab`` = (pz, py, px), the overlapping slice profiles of
+    ``consistency_slab`` (``ops.slab_profile``'s rules; with none of the others, ``check_consistency_slab``): ``table`` is then the
+    ``ops.SlabTable`` for cubes of edge P, which ``ops.slab_project`` takes; every refusal then names "consistency_slab"."""
+    check_consistency_slab(who, slab, consistency is not None, profile, None, operator)
+    with naming_consistency_slab(slab):
+        return _check_consistency(who, consistency, weight, shape, has_inpainting, init_images, skip_steps, sampler, profile, operator, slab)
+
+
+def _check_consistency(who, consistency, weight, shape, has_inpainting, init_images, skip_steps, sampler, profile, operator, slab):
     check_consistency_operator(who, operator, consistency is not None, profile)
     if consistency is None:
         if profile is not None:
@@ -1200,6 +1238,9 @@ def check_consistency(who, consistency, weight, shape, has_inpainting=False, ini
                          f"onto the high-res grid, ops.cell_replicate), got {got}")
     if operator is not None:
         return meas_up, cell, weight, ops.tile_operator(cell, operator).table
+    if slab is not None:
+        ops.slab_plan(who, cell, shape[2])
+        return meas_up, cell, weight, ops.slab_profile(cell, slab, jmax=shape[2] // cell[0])
     return meas_up, cell, weight, None if profile is None else ops.cell_profile(cell, profile)
 
 
@@ -1608,7 +1649,7 @@ class Imagen(nn.Module):
                       inpaint_masks=None, inpaint_resample_times=5, init_images=None, skip_steps=None, cond_scale=1,
                       pred_objective='noise', dynamic_threshold=True, use_tqdm=True, noise=None, sampler='ddpm',
                       sample_steps=None, eta=0.0, consistency=None, consistency_weight=1.0, consistency_profile=None,
-                      consistency_noise=None, consistency_operator=None, consistency_row_noise=None):
+                      consistency_noise=None, consistency_operator=None, consistency_row_noise=None, consistency_slab=None):
         """Ancestral sampler (:2059-2160).  Per step: one U-Net eval (HIP) + ONE fused posterior-step kernel;
         the per-step coefficients for all steps are computed on the host up front.  ``noise`` (optional) is a list
         [init, step_0, ...] of injected tensors with the reference's draw order (:2080, :2051), or a callable
@@ -1666,11 +1707,22 @@ class Imagen(nn.Module):
         tensor).  The draws are unchanged.  ``ValueError`` naming "consistency_row_noise": without ``consistency_operator``,
         together with ``consistency_noise`` or ``consistency_profile``, values ``ops.tile_noise_operator`` refuses, a chain with
         no stochastic step (use a constant ``consistency_weight``), a cell whose launch plans more than 64 KiB of LDS, and
-        everything ``consistency`` / ``consistency_operator`` refuse."""
+        everything ``consistency`` / ``consistency_operator`` refuse.
+
+        ``consistency_slab=(pz, py, px)`` (with ``consistency``; ``ops.slab_profile``): slice profiles that OVERLAP between
+        neighbouring cells along z -- ``pz`` has fz + 2r entries, reach 1 <= r <= fz / 2, ``py`` / ``px`` are the in-plane profile
+        inside the cell (``ops.slab_measure`` is that operator; ``meas_up`` is its output replicated).  Every ``ops.cell_project`` of
+        the chain is then one ``ops.slab_project``: DDNM on the slices whose whole support lies inside the cube, by one tridiagonal
+        solve per column; the first and the last slice of the cube are never enforced.  ``ValueError`` naming "consistency_slab":
+        without ``consistency``, together with ``consistency_profile``, ``consistency_noise``, ``consistency_operator`` or
+        ``consistency_row_noise``, a profile ``ops.slab_profile`` refuses (a bad reach, the condition rule), and everything
+        ``consistency`` refuses."""
         if pred_objective not in ('noise', 'x_start', 'v'):
             raise ValueError(f'unknown objective {pred_objective}')
         has_inpainting = exists(inpaint_images) and exists(inpaint_masks)                  # (:2090-2091)
         self._check_sampler_args(sampler, sample_steps, skip_steps, eta, has_inpainting)
+        check_consistency_slab('p_sample_loop', consistency_slab, exists(consistency), consistency_profile, consistency_noise,
+                               consistency_operator, consistency_row_noise)
         check_consistency_row_noise('p_sample_loop', consistency_row_noise, consistency_operator, consistency_profile, consistency_noise,
                                     not (sampler == 'dpmpp2m' or (sampler == 'ddim' and eta == 0)))
         with naming_consistency_row_noise(consistency_row_noise):
@@ -1678,7 +1730,8 @@ class Imagen(nn.Module):
                                        consistency_noise)
             with naming_consistency_noise(consistency_noise):
                 consistency = check_consistency('p_sample_loop', consistency, consistency_weight, shape, has_inpainting, init_images,
-                                                skip_steps, profile=consistency_profile, operator=consistency_operator)
+                                                skip_steps, profile=consistency_profile, operator=consistency_operator,
+                                                slab=consistency_slab)
         if exists(consistency_noise):
             consistency_noise = ops.consistency_noise_sigma('p_sample_loop', consistency_noise, exists(consistency),
                                                             not (sampler == 'dpmpp2m' or (sampler == 'ddim' and eta == 0)))
@@ -1760,6 +1813,8 @@ class Imagen(nn.Module):
                 elif exists(consistency) and weight > 0:                      # the clamp, then the projection; the step clamps no more
                     if exists(consistency_operator):
                         pred = ops.tile_project(pred, meas_up, cell, table, weight, clamp=(lo, hi, mode))
+                    elif exists(consistency_slab):
+                        pred = ops.slab_project(pred, meas_up, cell, table, weight, clamp=(lo, hi, mode))
                     elif exists(table):
                         pred = ops.cell_project_profile(pred, meas_up, cell, table, weight, clamp=(lo, hi, mode))
                     else:
@@ -1786,7 +1841,7 @@ class Imagen(nn.Module):
                stop_at_unet_number=None, return_all_outputs=False, return_all_unet_outputs=None, return_pil_images=False,
                device=None, use_tqdm=True, noise=None, sampler='ddpm', sample_steps=None, eta=0.0, consistency=None,
                consistency_weight=1.0, consistency_profile=None, consistency_noise=None, consistency_operator=None,
-               consistency_row_noise=None):
+               consistency_row_noise=None, consistency_slab=None):
         """imagen_pytorch3D.py:2165-2274 -> (img, [noisy per step], [x0 per step]).  Accepts both spellings
         ``return_all_outputs`` / ``return_all_unet_outputs`` (test.py:182 uses the latter).  ``sampler`` / ``sample_steps`` / ``eta``
         (one value, or one per U-Net like ``skip_steps``) and the list or callable ``noise``: see ``p_sample_loop``, as for
@@ -1799,7 +1854,8 @@ class Imagen(nn.Module):
         (``p_sample_loop``): a tile-local linear measurement; ``consistency`` then carries t = A+ y, and its refusals name
         "consistency_operator".  ``consistency_row_noise=sigma`` (``p_sample_loop``; with ``consistency_operator``, the units of
         ``target_up`` as passed): the noise of each row of A; every refusal above then also names "consistency_row_noise", as do
-        its own."""
+        its own.  ``consistency_slab=(pz, py, px)`` (``p_sample_loop``): slice profiles that overlap between neighbouring cells;
+        its refusals, and those of ``consistency`` when it is given, name "consistency_slab"."""
         if exists(return_all_unet_outputs):
             return_all_outputs = return_all_unet_outputs
         num_unets = len(self.unets)
@@ -1807,6 +1863,8 @@ class Imagen(nn.Module):
         sampler, sample_steps, eta = (cast_tuple(v, num_unets) for v in (sampler, sample_steps, eta))
         for args in zip(sampler, sample_steps, skip_steps, eta):
             self._check_sampler_args(*args, exists(inpaint_images) and exists(inpaint_masks))
+        check_consistency_slab('sample', consistency_slab, exists(consistency), consistency_profile, consistency_noise,
+                               consistency_operator, consistency_row_noise)
         check_consistency_row_noise('sample', consistency_row_noise, consistency_operator, consistency_profile, consistency_noise)
         with naming_consistency_row_noise(consistency_row_noise):
             check_consistency_operator('sample', consistency_operator, exists(consistency), consistency_profile, consistency_noise)
@@ -1818,7 +1876,8 @@ class Imagen(nn.Module):
             with naming_consistency_row_noise(consistency_row_noise), naming_consistency_noise(consistency_noise):
                 check_consistency('sample', consistency, consistency_weight, (batch_size, self.channels) + (self.image_sizes[n - 1],) * 3,
                                   exists(inpaint_images) and exists(inpaint_masks), cast_tuple(init_images, num_unets)[n - 1],
-                                  skip_steps[n - 1], profile=consistency_profile, operator=consistency_operator)
+                                  skip_steps[n - 1], profile=consistency_profile, operator=consistency_operator,
+                                  slab=consistency_slab)
             if exists(consistency_noise):
                 ops.consistency_noise_sigma('sample', consistency_noise, True,
                                             not (sampler[n - 1] == 'dpmpp2m' or (sampler[n - 1] == 'ddim' and eta[n - 1] == 0)))
@@ -1854,7 +1913,8 @@ class Imagen(nn.Module):
                 pred_objective=pred_objective, dynamic_threshold=dynamic_threshold, use_tqdm=use_tqdm, noise=noise,
                 sampler=unet_sampler, sample_steps=unet_sample_steps, eta=unet_eta, consistency=consistency,
                 consistency_weight=consistency_weight, consistency_profile=consistency_profile, consistency_noise=consistency_noise,
-                consistency_operator=consistency_operator, consistency_row_noise=consistency_row_noise)
+                consistency_operator=consistency_operator, consistency_row_noise=consistency_row_noise,
+                **(dict(consistency_slab=consistency_slab) if exists(consistency_slab) else {}))
             outputs.append(img)
             if exists(stop_at_unet_number) and stop_at_unet_number == unet_number:
                 break

@@ -105,7 +105,7 @@ moved, and exact consistency at w = 1 means u . x0' = y (to fp32 rounding).  Sin
 the divisibility rules are those above.  The crop and blend modes hand ``consistency_profile=`` on to the sampler
 (``ops.cell_project_profile`` per step); ``joint=True`` launches ``ops.volume_joint_consistent_profile_step`` in the place of
 ``ops.volume_joint_consistent_step``, as many launches as before.  A uniform profile given explicitly takes this path too.  Profiles
-that overlap between neighbouring cells (slice cross-talk) are not offered.
+that overlap between neighbouring cells (slice cross-talk) are ``consistency_slab``, below.
 
 A noisy measurement (``consistency_noise=sigma``, with ``consistency``; DDNM+, Wang et al. 2023, 3.3): sigma is the standard deviation
 of the measurement's noise in the raw units of the measurement.  A constant weight pastes that noise into every prediction and the
@@ -132,7 +132,7 @@ divisibility rules are those above.  The crop and blend modes hand windows of t 
 (``ops.tile_project`` per step); ``joint=True`` launches ``ops.volume_joint_consistent_tile_step``, as many launches as before.  At
 w = 1 the corrected prediction satisfies P x0' = t (to fp32 rounding), which is A x0' = y when y lies in the range of A; stacks that
 contradict each other are fitted in the least-squares sense.  Not offered: an operator that crosses tile borders (true k-space
-truncation, overlapping slice profiles), ``consistency_profile`` or ``consistency_noise`` together with an operator, the Heun sampler,
+truncation; overlapping slice profiles are ``consistency_slab``), ``consistency_profile`` or ``consistency_noise`` with an operator, Heun,
 consistency together with inpainting; the stacks are taken as registered to each other and A as known.
 
 Noisy rows (``consistency_row_noise=sigma``, with ``consistency`` and ``consistency_operator``; DDNM+ per singular direction): sigma
@@ -148,6 +148,25 @@ those of ``consistency_noise``: sigma / std goes to the sampler calls of the cro
 every shrink 0 with one common lambda the constant-weight tile launch, otherwise ``ops.tile_project_noise`` /
 ``ops.volume_joint_consistent_tile_noise_step`` -- as many launches and the same draws as before.  Not offered: correlated row
 noise, sigma estimated from the data, measurement noise tracked across steps, a cell whose launch plans more than 64 KiB of LDS.
+
+Overlapping slice profiles (``consistency_slab=(pz, py, px)``, with ``consistency``): a real slice profile is wider than the slice
+spacing, so neighbouring thick slices share voxels.  ``pz`` has L = fz + 2r entries, reach r >= 1 and 2r <= fz (a slice overlaps its
+two neighbours only); ``py`` / ``px`` are the in-plane profile inside the cell.  With u_z = pz / sum pz and u_yx the normalised outer
+product, slice s of the in-plane cell (cy, cx) measures y_s = sum_i u_z[i] (u_yx . x[s fz - r + i, cell]); every row sums to 1, so the
+z-score, ``state_space``, the replicated measurement and its window gathers are those above.  ``ops.slab_profile`` validates the
+profile and makes the host table, ``ops.slab_measure`` is the operator.  Along z, A A^T = q G with G Toeplitz tridiagonal (d = sum
+u_z^2, e the overlap product): the first operator here whose pseudo-inverse is not local.  A row is active when its whole support
+lies inside the domain -- the window of a sampler call, the volume with ``joint=True`` -- and is covered; the first and the last
+slice of a domain never are.  The projection is DDNM on the active rows, one tridiagonal solve (pivots tabulated on the host) per
+maximal run of active rows of a column; a voxel under no active row keeps its bits.  A profile with d - 2e < d / 64 is refused, which
+bounds the condition number of any run by 128.  The crop and blend modes hand ``consistency_slab=`` on to the sampler
+(``ops.slab_project`` per step: windows enforce only their inner slices).  ``joint=True`` needs a solve along the whole depth of the
+volume, which does not fit a box-of-cells block: a step is THREE launches where the tile-local operators take one --
+``ops.volume_joint_slab_coeffs`` (the fused plane values, then the solve per column) and
+``ops.volume_joint_consistent_slab_step`` -- and the windows are walked twice; the workspace and the coefficient volume are
+allocated once per volume.  Not offered: a reach beyond half a cell, slabs along other axes (permute the volume instead),
+noise-aware weights (``consistency_noise`` / ``consistency_row_noise``), rows that leave the volume, and any of the other
+consistency keywords together with it.
 """
 from types import SimpleNamespace
 
@@ -155,8 +174,8 @@ import numpy as np
 import torch
 
 from . import ops
-from .imagen_pytorch3D import (check_consistency_operator, check_consistency_row_noise, naming_consistency_noise,
-                               naming_consistency_row_noise, scale_consistency_row_noise)
+from .imagen_pytorch3D import (check_consistency_operator, check_consistency_row_noise, check_consistency_slab, naming_consistency_noise,
+                               naming_consistency_row_noise, naming_consistency_slab, scale_consistency_row_noise)
 from .metrics import MSSIM, PSNR
 from .utils_mine import convertVolume2subVolume, merge_sub_volumes
 
@@ -373,6 +392,8 @@ class VolumeInference:
             kw.update(consistency_operator=self.consistency_op)
         if self.consistency_row_noise is not None:           # z-scored like the measurement the sampler gets
             kw.update(consistency_row_noise=scale_consistency_row_noise(self.consistency_row_noise, 1., self.std))
+        if self.consistency_slab is not None:
+            kw.update(consistency_slab=self.consistency_slab)
         return kw
 
     def _inpaint_volumes(self, win):
@@ -386,7 +407,7 @@ class VolumeInference:
 
     def __init__(self, configs, sample_fn, nonzero_ratio=0.05, blend=None, sigma_scale=0.125, samples=1, noise=None, seed=0, joint=False,
                  inpaint=None, inpaint_resample_times=5, consistency=None, consistency_weight=1.0, consistency_profile=None,
-                 consistency_noise=None, consistency_operator=None, consistency_row_noise=None):
+                 consistency_noise=None, consistency_operator=None, consistency_row_noise=None, consistency_slab=None):
         """``sample_fn(lr_patches [B,1,S,S,S]) -> hr_patches`` — e.g. ``lambda x: trainer.sample(batch_size=x.shape[0],
         start_image_or_video=x, start_at_unet_number=2)[0]`` (test_all.py:234).  ``blend`` / ``sigma_scale`` / ``samples``: weighted
         overlap blending and multi-sample statistics, see the module docstring.  ``noise='anchored'`` (with ``seed``): every call
@@ -449,7 +470,16 @@ class VolumeInference:
         "consistency_row_noise" before anything touches the device: without ``consistency_operator``, together with
         ``consistency_noise`` or ``consistency_profile``, a value ``ops.tile_noise_operator`` refuses, a joint denoiser with no
         stochastic step, a cell whose launch plans more than 64 KiB of LDS, and whatever ``consistency`` and
-        ``consistency_operator`` refuse."""
+        ``consistency_operator`` refuse.
+
+        ``consistency_slab=(pz, py, px)`` (with ``consistency``): slice profiles that overlap between neighbouring cells along z
+        (module docstring) -- ``pz`` of fz + 2r entries, ``py`` / ``px`` of fy / fx.  The crop and blend modes hand it on as
+        ``consistency_slab=`` (every window enforces its inner slices); ``joint=True`` dispatches
+        ``ops.volume_joint_slab_coeffs`` and ``ops.volume_joint_consistent_slab_step`` per step, three launches.  ``ValueError``
+        naming "consistency_slab" before anything touches the device: without ``consistency``, together with
+        ``consistency_profile``, ``consistency_noise``, ``consistency_operator`` or ``consistency_row_noise``, a profile
+        ``ops.slab_profile`` refuses (a bad reach, the condition rule), a window whose launch plans more than 64 KiB of LDS, and
+        whatever ``consistency`` refuses."""
         def stochastic():                                    # crop and blend modes: the sampler call knows its own chain
             if joint and hasattr(sample_fn, 'coefs') and not getattr(sample_fn, 'heun', False):
                 # kn is the last entry of a first-order row (kx, k0, kn) and of a sigma-space row (kx, k0, kp, kn); the DDPM family's
@@ -458,12 +488,15 @@ class VolumeInference:
                 return has_kn and any(float(r[-1]) != 0.0 for r in sample_fn.coefs.tolist())
             return True
 
+        check_consistency_slab("VolumeInference", consistency_slab, consistency is not None, consistency_profile, consistency_noise,
+                               consistency_operator, consistency_row_noise)
         check_consistency_row_noise("VolumeInference", consistency_row_noise, consistency_operator, consistency_profile,
                                     consistency_noise, consistency_row_noise is None or stochastic())
         with naming_consistency_row_noise(consistency_row_noise):
             check_consistency_operator("VolumeInference", consistency_operator, consistency is not None, consistency_profile,
                                        consistency_noise)
-        with naming_consistency_row_noise(consistency_row_noise), naming_consistency_noise(consistency_noise):
+        with naming_consistency_row_noise(consistency_row_noise), naming_consistency_noise(consistency_noise), \
+                naming_consistency_slab(consistency_slab):
             # they ride on consistency: what that refuses names them too
             self.inpaint = self._check_inpaint(inpaint, inpaint_resample_times, joint, sample_fn)
             self.consistency = self._check_consistency(consistency, consistency_weight, self.inpaint, joint, sample_fn,
@@ -481,6 +514,11 @@ class VolumeInference:
             # the profile as given (what a sampler call takes) and its host table (what the fused launch takes, moved once per volume)
             self.consistency_profile = consistency_profile
             self.consistency_table = None if consistency_profile is None else ops.cell_profile(self.consistency[1], consistency_profile)
+            # the slab profile as given (what a sampler call takes); its rules are checked here, the table of a joint chain is made per
+            # volume, whose depth sets the number of run positions
+            self.consistency_slab = consistency_slab
+            if consistency_slab is not None:
+                ops.slab_profile(self.consistency[1], consistency_slab, jmax=1)
         self.consistency_row_noise = consistency_row_noise   # as given (what a sampler call takes, divided by std)
         self.consistency_noise = None
         if consistency_noise is not None:
@@ -523,10 +561,13 @@ class VolumeInference:
         self.mean, self.std = float(configs['Data']['mean']), float(configs['Data']['std'])
         if self.consistency_row_noise is not None:           # the fused launch rides the window's taps; a sampler call sees cubes of `sub`
             ops.tile_noise_plan("VolumeInference", self.consistency[1], self.sub, None if self.joint else self.sub)
+        if self.consistency_slab is not None and not self.joint:    # a sampler call sees cubes of `sub`
+            ops.slab_plan("VolumeInference", self.consistency[1], self.sub)
         if self.consistency is not None and not self.joint:
             for f in self.consistency[1]:                    # per axis: origins are multiples of the stride, a sampler call sees `sub`
                 if self.overlap % f or self.sub % f:
-                    with naming_consistency_row_noise(consistency_row_noise), naming_consistency_noise(consistency_noise):
+                    with naming_consistency_row_noise(consistency_row_noise), naming_consistency_noise(consistency_noise), \
+                            naming_consistency_slab(consistency_slab):
                         raise ValueError(f"VolumeInference: the consistency cell {self.consistency[1]} must divide the stride "
                                          f"{self.overlap} and the window {self.sub}: a per-window projection is defined for cells "
                                          f"inside a window only (joint=True projects on the whole volume)")
@@ -546,7 +587,8 @@ class VolumeInference:
                              f"{tuple(lowres_raw.shape)}")
         if self.consistency is not None and \
                 tuple(s * f for s, f in zip(self.consistency[0].shape[-3:], self.consistency[1])) != tuple(lowres_raw.shape):
-            with naming_consistency_row_noise(self.consistency_row_noise), naming_consistency_noise(self.consistency_noise):
+            with naming_consistency_row_noise(self.consistency_row_noise), naming_consistency_noise(self.consistency_noise), \
+                    naming_consistency_slab(self.consistency_slab):
                 raise ValueError(f"VolumeInference: the consistency measurement {tuple(self.consistency[0].shape)} times the cell "
                                  f"{self.consistency[1]} is not the volume's shape {tuple(lowres_raw.shape)}")
         if self.blend is not None:
@@ -651,6 +693,10 @@ class VolumeInference:
         win.table = None if self.consistency_table is None else self.consistency_table.to(win.device)
         if self.consistency_op is not None:                  # the operator's projector in the table's place (never both)
             win.table = self.consistency_op.table.to(win.device)
+        win.slab = None                                      # consistency_slab: the table for this depth, the workspace and the
+        if self.consistency_slab is not None:                # coefficient volume of the three launches, once per volume
+            table = ops.slab_profile(self.consistency[1], self.consistency_slab, jmax=win.shape[0] // self.consistency[1][0])
+            win.slab = (table.to(win.device), *ops.slab_workspace(win.shape, self.consistency[1], win.device))
         win.noise_schedule = None                            # per step (w_i, shrink_i) in fp32, made once per volume on the host
         if self.consistency_noise is not None:
             unit = self.sample_fn.state_space(torch.tensor([0., 1.], dtype=torch.float64))
@@ -744,7 +790,13 @@ class VolumeInference:
                 form = 2 if den.sigma_space else 1 if den.multistep else 0
                 kx, k0, k2, k3 = (*den.coefs[i], 0.)[:4]     # rows (kx, k0, kn), (kx, k0, kp) or (kx, k0, kp, kn)
                 draw = den.draw_base + 1 + i if den.sigma_space else i + 1
-                if self.consistency_op is not None:
+                if win.slab is not None:                     # three launches: the solve runs along the whole depth
+                    table, workspace, coef = win.slab
+                    ops.volume_joint_slab_coeffs(y, win.slot, win.taps, win.meas_up, self.consistency[1], table, workspace, coef, *tail)
+                    ops.volume_joint_consistent_slab_step(*head, prev, self.consistency[1], table, workspace, coef, weight, form, kx,
+                                                          k0, 0. if form == 0 else k2, k2 if form == 0 else k3, *tail, self.seed,
+                                                          draw=draw, sample=s, **io)
+                elif self.consistency_op is not None:
                     ops.volume_joint_consistent_tile_step(*head, prev, win.meas_up, self.consistency[1], win.table, weight, form, kx,
                                                           k0, 0. if form == 0 else k2, k2 if form == 0 else k3, *tail, self.seed,
                                                           draw=draw, sample=s, **io)

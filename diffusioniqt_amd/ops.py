@@ -2930,6 +2930,233 @@ def volume_joint_consistent_profile_step(y, slot, taps, x_t, x0_prev, meas_up, c
     return out, x0_out
 
 
+class SlabTable:
+    """What ``slab_profile`` returns: ``cell`` = (fz, fy, fx), ``reach`` = r and ``jmax``, the run positions the table holds;
+    ``table`` the flat fp32 tensor the kernels read (include/diqt.h: u_z [fz + 2r], u_yx [fy fx], g_yx [fy fx], e, m [jmax],
+    ip [jmax]); ``d``, ``e``, ``q`` the float64 numbers it was made from and ``cond`` = (d + 2e) / (d - 2e), which bounds the condition
+    number of every run.  ``to(device)`` gives the same object around the moved tensor (once per chain or volume)."""
+
+    def __init__(self, cell, reach, jmax, table, d, e, q):
+        self.cell, self.reach, self.jmax, self.table, self.d, self.e, self.q = cell, reach, jmax, table, d, e, q
+        self.cond = (d + 2 * e) / (d - 2 * e)
+
+    def to(self, device):
+        return SlabTable(self.cell, self.reach, self.jmax, self.table.to(device), self.d, self.e, self.q)
+
+    def part(self, name):
+        """The host copy of one member of the flat table: 'uz', 'uyx', 'gyx', 'e', 'm' or 'ip'."""
+        L, n, J = self.cell[0] + 2 * self.reach, self.cell[1] * self.cell[2], self.jmax
+        lo, hi = {'uz': (0, L), 'uyx': (L, L + n), 'gyx': (L + n, L + 2 * n), 'e': (L + 2 * n, L + 2 * n + 1),
+                  'm': (L + 2 * n + 1, L + 2 * n + 1 + J), 'ip': (L + 2 * n + 1 + J, L + 2 * n + 1 + 2 * J)}[name]
+        return self.table[lo:hi].cpu()
+
+    def __repr__(self):
+        return f"SlabTable(cell={self.cell}, reach={self.reach}, jmax={self.jmax}, cond<={self.cond:.3g})"
+
+
+def slab_profile(cell, profile, jmax=64):
+    """The host table of overlapping slice profiles for the ``consistency_slab`` modes (``ValueError`` naming "consistency"; nothing
+    touches the device).  ``profile`` = (pz, py, px): ``pz`` of length L = fz + 2r with reach r >= 1 and 2r <= fz (the profile of a
+    slice along z, r voxels into each neighbouring cell), ``py`` / ``px`` of lengths fy / fx (the in-plane profile inside the cell, as
+    in ``cell_profile``); all finite and >= 0, every axis with a positive sum.  ``jmax``: the run positions to tabulate, at least the
+    number of slices of the largest domain the table will serve (a cube's P / fz, a volume's D / fz).  With u_z = pz / sum pz,
+    u_yx = py (x) px / (sum py sum px), q = sum u_yx^2, d = sum u_z^2 and e = sum_{i < 2r} u_z[i] u_z[i + fz]: the table holds u_z, u_yx,
+    g_yx = u_yx / q, e and for j < jmax the pivots pi_0 = d, pi_j = d - e^2 / pi_{j-1} as m_j = e / pi_{j-1} (m_0 = 0) and
+    ip_j = 1 / pi_j.  float64 arithmetic, every entry rounded once to fp32.  A profile with d - 2e < d / 64 is refused: the rule bounds
+    the condition number of any run by 128, well inside what the fp32 solve resolves.  Returns a ``SlabTable``."""
+    import math
+    import numbers
+    who = "slab_profile"
+    cell, _ = consistency_cell(who, cell)
+    if isinstance(jmax, bool) or not isinstance(jmax, numbers.Integral) or not 1 <= jmax <= 65535:
+        raise ValueError(f"{who}: the consistency_slab table needs 1 <= jmax <= 65535 run positions, got {jmax!r}")
+    if not isinstance(profile, (tuple, list)) or len(profile) != 3:
+        raise ValueError(f"{who}: the consistency_slab profile must be (pz, py, px), three sequences of weights, got "
+                         f"{type(profile).__name__}")
+    if not all(isinstance(p, (tuple, list)) for p in profile):
+        raise ValueError(f"{who}: every axis of the consistency_slab profile must be a sequence of numbers")
+    extra = len(profile[0]) - cell[0]
+    if extra < 2 or extra % 2 or extra > cell[0]:
+        raise ValueError(f"{who}: pz of the consistency_slab profile must have fz + 2r = {cell[0]} + 2r entries with reach r >= 1 and "
+                         f"2r <= fz (a slice overlaps its two neighbours only), got {len(profile[0])}")
+    r = extra // 2
+    axes = []
+    for axis, (p, f) in enumerate(zip(profile, (cell[0] + 2 * r, cell[1], cell[2]))):
+        if len(p) != f:
+            raise ValueError(f"{who}: axis {axis} of the consistency_slab profile must be a sequence of {f} numbers (the cell is {cell})")
+        if not all(not isinstance(v, bool) and isinstance(v, numbers.Real) and math.isfinite(v) and v >= 0 for v in p):
+            raise ValueError(f"{who}: the weights of the consistency_slab profile must be finite numbers >= 0, got {p!r} on axis {axis}")
+        p = [float(v) for v in p]
+        total = 0.0
+        for v in p:
+            total += v
+        if not (total > 0.0 and math.isfinite(total)):
+            raise ValueError(f"{who}: axis {axis} of the consistency_slab profile must have a positive finite sum, got {p!r}")
+        axes.append((p, total))
+    (pz, sz), (py, sy), (px, sx) = axes
+    uz = [v / sz for v in pz]
+    uyx = [a * b / (sy * sx) for a in py for b in px]
+    q = d = e = 0.0
+    for v in uyx:
+        q += v * v
+    for v in uz:
+        d += v * v
+    for i in range(2 * r):
+        e += uz[i] * uz[i + cell[0]]
+    if not (q > 0.0 and d > 0.0 and math.isfinite(q) and math.isfinite(d)):
+        raise ValueError(f"{who}: the consistency_slab profile {profile!r} has no usable norm (q = {q!r}, d = {d!r})")
+    if d - 2 * e < d / 64:
+        raise ValueError(f"{who}: the consistency_slab profile is too flat across the slice border: d - 2e = {d - 2 * e!r} is below "
+                         f"d / 64 = {d / 64!r} (d = sum u_z^2, e the overlap product), so neighbouring slices are nearly dependent")
+    m, ip, pivot = [], [], d
+    for j in range(int(jmax)):
+        if j:
+            m.append(e / pivot)
+            pivot = d - e * e / pivot
+        else:
+            m.append(0.0)
+        ip.append(1.0 / pivot)
+    table = torch.tensor(uz + uyx + [v / q for v in uyx] + [e] + m + ip, dtype=torch.float64).to(torch.float32).contiguous()
+    if not bool(torch.isfinite(table).all()):
+        raise ValueError(f"{who}: the consistency_slab profile {profile!r} does not fit fp32")
+    return SlabTable(cell, r, int(jmax), table, d, e, q)
+
+
+def slab_lds(cell, edge):
+    """The bytes of LDS ``slab_project`` plans for cubes of edge ``edge``: one float per slice for each of the 256 threads of a block.
+    The entry refuses a plan above 65536 with DIQT_E_SHAPE."""
+    return 4 * 256 * (int(edge) // cell[0])
+
+
+def slab_plan(who, cell, edge):
+    """``ValueError`` naming "consistency_slab" for cubes whose ``slab_project`` launch plans more than 64 KiB of LDS."""
+    need = slab_lds(cell, edge)
+    if need > 65536:
+        raise ValueError(f"{who}: consistency_slab with the cell {tuple(cell)} on cubes of edge {edge} plans {need} bytes of LDS "
+                         f"({int(edge) // cell[0]} slices for each of 256 columns), above the 65536 a launch may have")
+
+
+def _slab_table(who, table, cell, like, slices):
+    """The check of a ``slab_profile`` table handed to a kernel: a ``SlabTable`` of this cell with at least ``slices`` run positions,
+    its tensor on ``like``'s device.  Returns the cell as the table has it."""
+    if not isinstance(table, SlabTable):
+        raise ValueError(f"{who}: the consistency_slab table must be what ops.slab_profile returns, got {type(table).__name__}")
+    if tuple(cell) != table.cell:
+        raise ValueError(f"{who}: the consistency_slab table was made for the cell {table.cell}, not {tuple(cell)}")
+    if table.jmax < slices:
+        raise ValueError(f"{who}: the consistency_slab table holds {table.jmax} run positions, the domain has {slices} slices "
+                         f"(ops.slab_profile(..., jmax=))")
+    if table.table.device != like.device:
+        raise ValueError(f"{who}: the consistency_slab table is on {table.table.device}, the data on {like.device}")
+    _chk(table.table)
+    return table.cell
+
+
+def slab_measure(vol, cell, table):
+    """The measurement of a [D,H,W] volume under overlapping slice profiles (include/diqt.h, diqt_slab_measure): fp32
+    [D/fz, H/fy, W/fx], slice s of a column the u_z-weighted sum of the in-plane weighted means of planes s fz - r .. s fz + fz + r - 1;
+    a slice that leaves the volume takes the truncated sum.  ``table``: ``slab_profile``'s, on ``vol``'s device.  It simulates the
+    acquisition of the ``consistency_slab`` modes; once per volume.  One launch."""
+    who = "slab_measure"
+    _chk(vol)
+    if vol.ndim != 3 or not vol.is_contiguous() or vol.numel() == 0:
+        raise ValueError(f"{who}: vol must be a non-empty contiguous [D,H,W] tensor, got {tuple(vol.shape)}")
+    cell, _ = consistency_cell(who, cell, 1.0, [(s, a) for a, s in enumerate(vol.shape)])
+    _slab_table(who, table, cell, vol, 1)
+    out = torch.empty(tuple(s // f for s, f in zip(vol.shape, cell)), dtype=torch.float32, device=vol.device)
+    _lib.call("diqt_slab_measure", vol, table.table, out, *vol.shape, *cell, table.reach, table.jmax, _stream())
+    return out
+
+
+def slab_project(x0, meas_up, cell, table, weight=1.0, clamp=None, out=None):
+    """``cell_project_profile`` for overlapping slice profiles (include/diqt.h, diqt_slab_project): ``table`` = ``slab_profile``'s, on
+    ``x0``'s device, with jmax >= P / fz.  a = clamp(x0); the domain is each cube, whose slices 1 .. P/fz - 2 are the active rows (the
+    first and last leave the cube and are never enforced); out = a + weight A_act^T (A_act A_act^T)^-1 (y_act - A_act a) by one
+    tridiagonal solve per column, y_s read from ``meas_up`` at the first voxel of slice s' cell.  A voxel under no active row keeps
+    a.  Shapes, ``clamp`` and ``out`` as there.  Returns ``out``.  One launch."""
+    who = "slab_project"
+    _chk(x0, meas_up, out)
+    if x0.ndim != 5 or x0.numel() == 0 or len(set(x0.shape[2:])) != 1:
+        raise ValueError(f"{who}: x0 must be a non-empty [B,C,P,P,P] tensor of cubes, got {tuple(x0.shape)}")
+    if out is None:
+        out = torch.empty_like(x0)
+    for t, name in ((meas_up, 'meas_up'), (out, 'out')):
+        if t.shape != x0.shape:
+            raise ValueError(f"{who}: {name} must have x0's shape {tuple(x0.shape)}, got {tuple(t.shape)}")
+    if not (x0.is_contiguous() and meas_up.is_contiguous() and out.is_contiguous()):
+        raise RuntimeError(f"{who}: tensors must be contiguous")
+    P = x0.shape[2]
+    cell, weight = consistency_cell(who, cell, weight, [(P, a) for a in range(3)])
+    _slab_table(who, table, cell, x0, P // cell[0])
+    slab_plan(who, cell, P)
+    lo, hi, mode = (0., 0., 2) if clamp is None else clamp                # the entry's third mode: no clamp
+    if clamp is not None and int(mode) not in (0, 1):
+        raise ValueError(f"{who}: clamp mode must be 0 (min) or 1 (box), got {mode!r}")
+    _lib.call("diqt_slab_project", x0, meas_up, table.table, out, x0.shape[0] * x0.shape[1], P, *cell, table.reach, table.jmax, weight,
+              float(lo), float(hi), int(mode), _stream())
+    return out
+
+
+def slab_workspace(shape, cell, device):
+    """``(workspace, coef)`` of the joint slab launches for a [D,H,W] volume: fp32 device tensors of (2 D + D/fz) (H/fy) (W/fx) floats
+    and [D/fz, H/fy, W/fx]; allocate them once per volume."""
+    D, H, W = (int(s) for s in shape)
+    rows = (D // cell[0], H // cell[1], W // cell[2])
+    return (torch.empty((2 * D + rows[0]) * rows[1] * rows[2], dtype=torch.float32, device=device),
+            torch.empty(rows, dtype=torch.float32, device=device))
+
+
+def _slab_joint(who, x_like, cell, table, workspace, coef):
+    """The host checks the two joint slab launches share; returns the cell."""
+    cell, _ = consistency_cell(who, cell, 1.0, [(s, a) for a, s in enumerate(x_like.shape)])
+    _slab_table(who, table, cell, x_like, x_like.shape[0] // cell[0])
+    _chk(workspace, coef)
+    rows = tuple(s // f for s, f in zip(x_like.shape, cell))
+    need = (2 * x_like.shape[0] + rows[0]) * rows[1] * rows[2]
+    if workspace.ndim != 1 or workspace.numel() < need or tuple(coef.shape) != rows:
+        raise ValueError(f"{who}: the consistency_slab workspace must hold {need} floats and coef be {rows} (ops.slab_workspace), got "
+                         f"{tuple(workspace.shape)} and {tuple(coef.shape)}")
+    return cell
+
+
+def volume_joint_slab_coeffs(y, slot, taps, meas_up, cell, table, workspace, coef, lo, hi, clamp_mode, stride):
+    """The first two of the three launches of a joint step under ``consistency_slab`` (include/diqt.h,
+    diqt_volume_joint_slab_coeffs): the windows ``y`` are fused as in ``volume_joint_step`` into one weighted plane value per
+    (z, cy, cx), then every column (cy, cx) solves its runs of active rows along the whole depth; the coefficients c go into
+    ``coef`` [D/fz, H/fy, W/fx], the run positions stay in ``workspace`` for ``volume_joint_consistent_slab_step``.  ``meas_up``
+    [D,H,W]: the replicated measurement in state space.  Returns ``coef``."""
+    who = "volume_joint_slab_coeffs"
+    N, P, stride = _joint_windows(who, y, slot, taps, meas_up, clamp_mode, stride)
+    _joint_slots(who, slot, N)
+    cell = _slab_joint(who, meas_up, cell, table, workspace, coef)
+    _lib.call("diqt_volume_joint_slab_coeffs", y if N else None, slot, taps, meas_up, table.table, workspace, workspace.numel(), coef, N,
+              *meas_up.shape, P, stride, *slot.shape, *cell, table.reach, table.jmax, float(lo), float(hi), int(clamp_mode), _stream())
+    return coef
+
+
+def volume_joint_consistent_slab_step(y, slot, taps, x_t, x0_prev, cell, table, workspace, coef, weight, form, kx, k0, kp, kn, lo, hi,
+                                      clamp_mode, stride, seed=0, draw=0, sample=0, out=None, x0_out=None):
+    """The third launch (include/diqt.h, diqt_volume_joint_consistent_slab_step): ``volume_joint_consistent_step``'s three update forms
+    with the slab correction of every voxel between the fuse and the update, ``workspace`` / ``coef`` as
+    ``volume_joint_slab_coeffs`` left them for the same ``y``.  A covered voxel under no active row steps with its plain x0.
+    ``out`` / ``x0_out`` as there.  Returns ``(out, x0_out)``.  One launch, bit-reproducible."""
+    who = "volume_joint_consistent_slab_step"
+    form = int(form)
+    if form not in (0, 1, 2):
+        raise ValueError(f"{who}: form must be 0 (first order), 1 (multistep) or 2 (multistep with noise), got {form!r}")
+    N, P, stride = _joint_windows(who, y, slot, taps, x_t, clamp_mode, stride)
+    seed, draw, sample = _noise_key(who, seed, draw, sample)
+    _joint_slots(who, slot, N)
+    _, weight = consistency_cell(who, cell, weight)
+    cell = _slab_joint(who, x_t, cell, table, workspace, coef)
+    out, x0_out = _joint_volumes(who, x_t, None if form == 0 else x0_prev, out, x0_out)
+    _lib.call("diqt_volume_joint_consistent_slab_step", y if N else None, slot, taps, x_t, None if form == 0 else x0_prev, table.table,
+              coef, workspace, workspace.numel(), out, x0_out, form, N, *x_t.shape, P, stride, *slot.shape, *cell, table.reach,
+              table.jmax, weight, float(kx), float(k0), float(kp), float(kn), float(lo), float(hi), int(clamp_mode), seed, draw, sample,
+              _stream())
+    return out, x0_out
+
+
 class TileOperator:
     """What ``tile_operator`` returns: ``cell`` = (fz, fy, fx); ``A`` [m, n] and ``pinv`` = A+ [n, m], float64 host tensors; ``table``
     the fp32 host [n, n] projector P = A+ A, symmetric to the bit, which the projecting kernels read; ``rank``; ``gain`` =

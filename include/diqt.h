@@ -866,6 +866,58 @@ int diqt_volume_joint_consistent_tile_noise_step(const float* y, const int* slot
                                                  float* x0_out, int form, int N, int D, int H, int W, int P, int stride, int G0, int G1,
                                                  int G2, int fz, int fy, int fx, float kx, float k0, float kp, float kn, float lo, float hi,
                                                  int clamp_mode, unsigned long long seed, unsigned draw, unsigned sample, void* stream);
+/* Data consistency for OVERLAPPING SLICE PROFILES (the slab operator; ops.slab_profile).  Slice s of the in-plane cell (cy, cx)
+ * measures  y_s = sum_{i < L} u_z[i] (u_yx . x[s fz - r + i, cell]),  L = fz + 2r with reach 1 <= r and 2r <= fz, u_z and u_yx >= 0
+ * with sum 1: a slice overlaps its two neighbours only and a voxel lies under at most two slices.  A row is ACTIVE when its whole
+ * support lies inside the domain (the cube of the per-window entry, the volume of the joint entries) and is covered; the first and
+ * the last slice of a domain never are.  The projection is DDNM on the active rows, x0' = x0 + w A^T (A A^T)^-1 (y - A x0), and
+ * A A^T = q G with q = sum u_yx^2 and G Toeplitz tridiagonal (d = sum u_z^2, e = sum_{i < 2r} u_z[i] u_z[i + fz]) on every maximal run
+ * of consecutive active rows of a column.  `table` is device fp32, flat (the caller's; ops.slab_profile makes it on the host):
+ *     u_z [L], u_yx [fy fx], g_yx = u_yx / q [fy fx], e, m [jmax], ip [jmax]
+ * with the pivots pi_0 = d, pi_j = d - e^2 / pi_{j-1} stored as m_j = e / pi_{j-1} (m_0 = 0) and ip_j = 1 / pi_j: no kernel divides.
+ * The arithmetic, fp32 with no contraction, ONE definition for all entries:
+ *     pm[z] = 0;  pm = fmaf(u_yx[q], a[q], pm) over the fy fx voxels of the plane in (y, x) order
+ *     acc = 0;  acc = fmaf(u_z[i], pm[s fz - r + i], acc) over ascending i;  rho_s = y_s - acc, y_s read at voxel (s fz, cy fy, cx fx)
+ *     of the replicated measurement
+ *     ascending s:   zeta_s = rho_s at run position j = 0, else fmaf(-m_j, zeta_{s-1}, rho_s); a run restarts at j = 0
+ *     descending s:  c_s = fmaf(-e, c_{s+1}, zeta_s) * ip_j, c_{s+1} = 0 at the end of a run; inactive rows have c = 0
+ *     voxel at depth z = k fz + o:  t = 0;  t = fmaf(u_z[.], c_s, t) over the active ones of s = k - 1 (o < r), k, k + 1 (o >= fz - r)
+ *     inside [0, S), ascending;  a' = fmaf(w * g_yx[q], t, a), w * g_yx one rounded product; a voxel under no active row keeps its bits.
+ * Error codes: a null pointer DIQT_E_ALIGN; a cell with n outside 2 .. 64, a reach outside the rule, jmax < 1, a weight outside
+ * (0, 1] or a clamp mode the entry does not have DIQT_E_UNSUPPORTED; a cell that does not divide the shape, jmax below the number of
+ * slices of the domain, an LDS plan above 64 KiB or a workspace that is too small DIQT_E_SHAPE.
+ *
+ * diqt_slab_measure: out [D / fz][H / fy][W / fx] = A x for x [D][H][W]; a row that leaves the volume takes the truncated sum
+ * (outside counts as 0).  out may not alias x.                                                                                      */
+int diqt_slab_measure(const float* x, const float* table, float* out, int D, int H, int W, int fz, int fy, int fx, int r, int jmax,
+                      void* stream);
+/* The per-window step, diqt_cell_project_profile's contract: `cubes` cubes of edge P, a = clamp(x0) with the clamp modes 0 / 1 / 2 of
+ * diqt_cell_project, then the projection; out may alias x0 (one thread owns one column (cube, cy, cx) and reads all of it before it
+ * writes), meas_up and table may not alias out.  The column's zeta / c live in LDS, P / fz floats per thread of a 256-thread block. */
+int diqt_slab_project(const float* x0, const float* meas_up, const float* table, float* out, size_t cubes, int P, int fz, int fy, int fx,
+                      int r, int jmax, float weight, float lo, float hi, int clamp_mode, void* stream);
+/* The joint path needs a solve along the whole depth of the volume, so a step is THREE launches where the tile-local operators take
+ * one.  diqt_volume_joint_slab_coeffs is two of them: per (z, cy, cx) the fy fx voxels are fused as in diqt_volume_joint_step (the
+ * same walk and step clamp) into pm and a covered flag; then per column (cy, cx) the rows, the residuals and the two sweeps, c into
+ * coef [D / fz][H / fy][W / fx].  `workspace` is device fp32 of at least (2 D + D / fz) (H / fy) (W / fx) floats (pm, the flags, the
+ * run positions); the step entry reads the run positions from it, so it must be left alone between the two calls.  meas_up is
+ * [D][H][W] in state space.  Nothing here may alias anything else.                                                                 */
+int diqt_volume_joint_slab_coeffs(const float* y, const int* slot, const float* taps, const float* meas_up, const float* table,
+                                  float* workspace, size_t workspace_floats, float* coef, int N, int D, int H, int W, int P, int stride,
+                                  int G0, int G1, int G2, int fz, int fy, int fx, int r, int jmax, float lo, float hi, int clamp_mode,
+                                  void* stream);
+/* The three update forms of diqt_volume_joint_consistent_step with the correction of a voxel between the fuse and the update, coef
+ * and workspace as the call above left them for the same y.  A covered voxel under no active row takes the update with its plain x0;
+ * an uncovered voxel keeps x_t and gets x0_out = 0.  Normals and draw numbering are diqt_volume_joint_step's.  x_next may alias x_t
+ * and x0_out may alias x0_prev (a thread reads its own voxel of each, then writes it).  No atomics, no waiting across blocks:
+ * bit-reproducible, and with the volume equal to one window and unit taps the chain is diqt_slab_project followed by the per-window
+ * step, bit for bit.                                                                                                                */
+int diqt_volume_joint_consistent_slab_step(const float* y, const int* slot, const float* taps, const float* x_t, const float* x0_prev,
+                                           const float* table, const float* coef, const float* workspace, size_t workspace_floats,
+                                           float* x_next, float* x0_out, int form, int N, int D, int H, int W, int P, int stride, int G0,
+                                           int G1, int G2, int fz, int fy, int fx, int r, int jmax, float weight, float kx, float k0,
+                                           float kp, float kn, float lo, float hi, int clamp_mode, unsigned long long seed,
+                                           unsigned draw, unsigned sample, void* stream);
 /* The stochastic Heun sampler of the EDM family (Karras et al. 2022; elucidated_imagen.py:382-532) on the joint state: a churn, a
  * predictor and a corrector per step, two U-Net evaluations.  The state is three [D][H][W] volumes, all updated in place (every thread
  * reads only its own voxel of each, then writes it): xh = images_hat, xn = images_next, x0 = the fused prediction.  Window walk,
