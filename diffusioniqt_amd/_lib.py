@@ -240,6 +240,13 @@ PROTOTYPES = {
     "diqt_conv3d_fwd_split16_variant": (I, [I] * 15),
     "diqt_conv3d_fwd_split16": (I, [P, P, P, P, P, P, P] + [I] * 15 + [P]),
     "diqt_conv3d_fwd_gn_split16": (I, [P, P, P, P, P, P, P, P, I] + [I] * 15 + [P]),
+    "diqt_set_conv_split16_fill_tile": (I, [I]),
+    "diqt_conv3d_fwd_split16_fill_supported": (I, [I] * 15),
+    "diqt_conv3d_fwd_gn_split16_fill_supported": (I, [I] * 16),
+    "diqt_conv3d_fwd_split16_fill_stats_blocks": (I, [I] * 15),
+    "diqt_conv3d_fwd_split16_fill_variant": (I, [I] * 15),
+    "diqt_conv3d_fwd_split16_fill": (I, [P, P, P, P, P, P, P] + [I] * 15 + [P]),
+    "diqt_conv3d_fwd_gn_split16_fill": (I, [P, P, P, P, P, P, P, P, I] + [I] * 15 + [P]),
 }
 
 _lib = None

@@ -13,9 +13,10 @@ struct H9Geom {
 
 // Does conv_f9h_kernel take this launch?  16-bit x, Cin % 32 == 0, Cout % 8 == 0, a 3x3x3 or (1,3,3) filter, enough 512- / 256-voxel
 // tiles to fill the chip, tensors < 1 GiB.  yHalf: y is stored in the operand type.  split: the plan of the three-product split build
-// (conv_split16.hip) for an input of Cin 16-bit channels = Cin / 2 fp32 channels as heads and tails -- the same rules, its own tiles.
+// (conv_split16.hip) for an input of Cin 16-bit channels = Cin / 2 fp32 channels as heads and tails -- the same rules, its own tiles:
+// splitTile names the one tile tried, 6 (256 voxels, the route's plan), 7 (128) or 8 (64) -- the candidates of its fill plan.
 bool f9h_plan(H9Geom& g, size_t& lds, unsigned& grid, int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph,
-              int pw, int epd, int eph, int epw, bool yHalf, bool split = false);
+              int pw, int epd, int eph, int epw, bool yHalf, bool split = false, int splitTile = 6);
 // rows of column sums per batch entry the kernel writes for this plan
 int f9h_stats_blocks(const H9Geom& g);
 // the variant of the process's last launch, -1 if none since the previous call (read and clear)

@@ -35,7 +35,7 @@ template <class C> static bool f9h_try(H9Geom& g, size_t& lds, unsigned& grid, d
 }
 
 bool f9h_plan(H9Geom& g, size_t& lds, unsigned& grid, int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph,
-              int pw, int epd, int eph, int epw, bool yHalf, bool split) {
+              int pw, int epd, int eph, int epw, bool yHalf, bool split, int splitTile) {
     const int mode = diqt_set_conv_f9h_mode(-1);
     const bool k333 = kd == 3 && kh == 3 && kw == 3, k133 = kd == 1 && kh == 3 && kw == 3;
     if (!mode || !(k333 || k133) || Cin % h9::CK != 0 || Cout % 8 != 0 || Cout < 8) return false;
@@ -61,7 +61,9 @@ bool f9h_plan(H9Geom& g, size_t& lds, unsigned& grid, int B, int D, int H, int W
     if (split) {
         // the three-product split of an fp32 conv (Cin counts the 16-bit channels: heads and tails): 3x3x3 only, one workgroup per CU
         if (!k333 || yHalf) return false;
-        F9H_TRY(H9S_333_256, 6)
+        if (splitTile == 6) F9H_TRY(H9S_333_256, 6)
+        else if (splitTile == 7) F9H_TRY(H9S_333_128, 7)
+        else if (splitTile == 8) F9H_TRY(H9S_333_64, 8)
     } else if (k333) {
         F9H_TRY(H9_333_256, 1)
         F9H_TRY(H9_333_512, 0)

@@ -1,5 +1,6 @@
 // conv_f9h_kernel -- the 16-bit forward conv (fp16 / bf16 operands, fp32 accumulate) rebuilt on conv_fwd9_kernel's structure (round 4).
-// Included by the translation units that instantiate its variants (conv_f9h.hip, conv_f9h_b.hip, conv_f9h_c.hip; conv_split16.hip: the SPLIT build).
+// Included by the translation units that instantiate its variants (conv_f9h.hip, conv_f9h_b.hip, conv_f9h_c.hip; conv_split16.hip and
+// conv_split16_b.hip: the SPLIT build).
 //
 // What bounded the round-3 kernels (conv_fwd_h_kernel / conv_fwd_hp_kernel): every operand byte went global -> VGPR -> LDS under one or
 // two barriers per 4-36 MFMAs of a wave, two waves per SIMD at 256 registers, and a 4-way bank conflict on every fragment read
@@ -122,8 +123,10 @@ __global__ __launch_bounds__(256, C::OCC) void conv_f9h_kernel(const void* __res
     constexpr int T = C::T, HB = C::HB, NPH = C::NPH, NVB = C::NVB, HH = C::HH, HWd = C::HWd, HV = C::HV, NIMG = C::NIMG;
     constexpr int KH = C::KH, KW = C::KW;
     // SPLIT: a ring of 3 slots (a tap is 3 NVB MFMAs there, so two taps ahead is as far in cycles as 4-6 taps of the 16-bit build): the
-    // 48 registers pay for the third accumulator set
-    constexpr int PD = SPLIT ? 3 : h9::PD;
+    // 48 registers pay for the third accumulator set.  The small tiles of conv_split16_b.hip (NVB = 2 / 1: a tap is 192 / 96 MFMA cycles)
+    // have the registers for the 9-slot ring and take it: 39.9-41.3 us against 41.7-42.8 us with 3 slots on 128 -> 128 @ 8 x 8^3 (NVB = 1,
+    // pre-pass and statistics included), no difference at NVB = 2
+    constexpr int PD = SPLIT ? (NVB <= 2 ? h9::PD : 3) : h9::PD;
     static_assert(T % PD == 0, "the ring slot of a tap is static");
     constexpr int NSP = NIMG == 2 ? T - PD : T;       // taps of a chunk that issue halo pieces (two images: all older than the last tap's weight load)
     constexpr unsigned YE = YH ? 2u : 4u;
@@ -579,6 +582,8 @@ __global__ __launch_bounds__(256, C::OCC) void conv_f9h_kernel(const void* __res
 using H9_333_512 = Cfg<3, 3, 3, 8, 8, 8, 2>;
 using H9_333_256 = Cfg<3, 3, 3, 4, 8, 8, 2, 2>;      // 256-voxel tiles, TWO workgroups per CU (256 registers per wave): one's epilogue / barrier waits under the other's MFMAs
 using H9S_333_256 = Cfg<3, 3, 3, 4, 8, 8, 2>;         // the split build's 256-voxel tile: ONE workgroup per CU (two accumulator sets)
+using H9S_333_128 = Cfg<3, 3, 3, 2, 8, 8, 2>;      // the split build's fill tiles (conv_split16_b.hip): 128 voxels, NVB = 2,
+using H9S_333_64 = Cfg<3, 3, 3, 1, 8, 8, 2>;        // and 64 voxels, NVB = 1 -- launches whose 256-voxel tiles leave CUs idle
 using H9_133_A = Cfg<1, 3, 3, 1, 16, 32, 3>;
 using H9_133_B = Cfg<1, 3, 3, 2, 16, 16, 3>;
 using H9_133_C = Cfg<1, 3, 3, 4, 8, 8, 3>;
@@ -614,9 +619,11 @@ int launch_b(const void* x, const unsigned short* wp, const float* bias, const f
              unsigned grid, int bf16, bool yHalf, void* stream);
 int launch_c(const void* x, const unsigned short* wp, const float* bias, const float* residual, void* y, const H9Geom& g, size_t lds,
              unsigned grid, int bf16, bool yHalf, void* stream);
-// the split build (conv_split16.hip): variant 6 (H9S_333_256)
+// the split build (conv_split16.hip): variant 6 (H9S_333_256); conv_split16_b.hip: variants 7 (H9S_333_128) and 8 (H9S_333_64)
 int launch_split(const void* x, const unsigned short* wp, const float* bias, const float* residual, void* y, const H9Geom& g, size_t lds,
                  unsigned grid, void* stream);
+int launch_split_b(const void* x, const unsigned short* wp, const float* bias, const float* residual, void* y, const H9Geom& g, size_t lds,
+                   unsigned grid, void* stream);
 
 }  // namespace h9
 }  // namespace diqt

@@ -12,6 +12,7 @@
 //     head of the even and of the odd taps, the cross terms -- and a 3-slot weight ring, 498-512 registers without scratch in its four
 //     residual x statistics instantiations; at NVB = 8 the allocator spills) and the entry points.
 #include "conv_f9h_kernel.h"
+#include <atomic>
 
 namespace diqt {
 
@@ -83,6 +84,7 @@ namespace h9 {
 int launch_split(const void* x, const unsigned short* wp, const float* bias, const float* residual, void* y, const H9Geom& g, size_t lds,
                  unsigned grid, void* stream) {
     if (g.variant == 6) return launch_split_cfg<H9S_333_256>(x, wp, bias, residual, y, g, lds, grid, stream);
+    if (g.variant == 7 || g.variant == 8) return launch_split_b(x, wp, bias, residual, y, g, lds, grid, stream);
     set_error("conv3d_fwd_split16(v9h): no variant %d", g.variant);
     return DIQT_E_UNSUPPORTED;
 }
@@ -104,6 +106,50 @@ static bool split16_plan(H9Geom& g, size_t& lds, unsigned& grid, int B, int D, i
     if (diqt_set_conv_f9h_mode(-1) != 2 && (long long)g.MT * g.nNt < 128) return false;
     // (the activation pass addresses x and its split copy with 64-bit offsets; the kernel's descriptors are checked by the planner)
     return true;
+}
+
+// 0 (default): the fill plan chooses its tile; 6, 7, 8: it takes that variant's tile whatever the unit counts say -- honoured only
+// under diqt_set_conv_f9h_mode(2), for tests that run every tile on one shape.  v >= 0 sets it, v < 0 only queries; returns the
+// previous value.
+static std::atomic<int> g_fill_tile{0};
+extern "C" int diqt_set_conv_split16_fill_tile(int v) {
+    if (v < 0) return g_fill_tile.load();
+    return g_fill_tile.exchange(v == 6 || v == 7 || v == 8 ? v : 0);
+}
+
+// The fill plan (round 10): the same route for launches whose 256-voxel tiles leave CUs without a workgroup.  Candidates are the 256-,
+// 128- and 64-voxel tiles in that order; a smaller tile is tried only when the larger gives fewer than 256 (tile, 64-channel block)
+// units, the tiling taken must give at least 128, and the launch must hold at least 2^25 voxel x Cin x Cout products: below, the launch
+// keeps its kernel (and the tiny networks of the parity and launch-trace suites their bits).  diqt_set_conv_f9h_mode(2) lifts both floors.
+static bool split16_fill_plan(H9Geom& g, size_t& lds, unsigned& grid, int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw,
+                              int pd, int ph, int pw, int epd, int eph, int epw) {
+    if (Cin <= 0 || Cin % S16_CG != 0 || Cin > (1 << 20)) return false;
+    const bool lifted = diqt_set_conv_f9h_mode(-1) == 2;
+    const int forced = lifted ? g_fill_tile.load() : 0;
+    bool have = false;
+    for (int v = 6; v <= 8; ++v) {
+        if (forced && v != forced) continue;
+        H9Geom t; size_t l; unsigned gr;
+        if (!f9h_plan(t, l, gr, B, D, H, W, 2 * Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, false, true, v)) continue;
+        g = t; lds = l; grid = gr; have = true;
+        if ((long long)t.MT * t.nNt >= 256) break;
+    }
+    if (!have) return false;
+    if (!lifted) {
+        if ((long long)g.MT * g.nNt < 128) return false;
+        // sent back by measurement (round 10): 64-voxel tiles on less than the whole chip pay only up to Cin = 128.  Every workgroup pulls
+        // its channel block's whole weight stream through L2 for 64 voxels, so the launch grows with Cin where the Winograd tile's
+        // split-K spreads K over the chip: 256 -> 128 @ 8 x 8^3 (128 units) took 66.4 us against 61.3 us, 128 -> 128 39.9-41.3 against 43.7
+        if (g.variant == 8 && (long long)g.MT * g.nNt < 256 && Cin > 128) return false;
+        if ((unsigned long long)B * g.Do * g.Ho * g.Wo * (unsigned long long)Cin * (unsigned long long)Cout < (1ull << 25)) return false;
+    }
+    return true;
+}
+
+static bool split16_any_plan(bool fill, H9Geom& g, size_t& lds, unsigned& grid, int B, int D, int H, int W, int Cin, int Cout, int kd, int kh,
+                             int kw, int pd, int ph, int pw, int epd, int eph, int epw) {
+    return fill ? split16_fill_plan(g, lds, grid, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw)
+                : split16_plan(g, lds, grid, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw);
 }
 
 static bool split16_act_ok(int act) { return act == 0 || act == DIQT_ACT_MISH || act == DIQT_ACT_SILU || act == DIQT_ACT_GELU; }
@@ -153,7 +199,7 @@ extern "C" int diqt_conv3d_fwd_split16_variant(int B, int D, int H, int W, int C
     return g.variant;
 }
 
-static int split16_run(const char* who, const float* x, void* x16, const void* packed, const float* bias, const float* residual, float* y,
+static int split16_run(const char* who, bool fill, const float* x, void* x16, const void* packed, const float* bias, const float* residual, float* y,
                        float* stats, const float* coef, int act, int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd,
                        int ph, int pw, int epd, int eph, int epw, void* stream) {
     DIQT_REQUIRE(x && x16 && packed && y, DIQT_E_ALIGN, "%s: null pointer", who);
@@ -161,8 +207,8 @@ static int split16_run(const char* who, const float* x, void* x16, const void* p
                  (!coef || aligned16(coef)), DIQT_E_ALIGN, "%s: tensors must be 16-byte aligned", who);
     DIQT_REQUIRE(split16_act_ok(act), DIQT_E_UNSUPPORTED, "%s: activation %d", who, act);
     H9Geom g; size_t lds; unsigned grid;
-    DIQT_REQUIRE(split16_plan(g, lds, grid, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw), DIQT_E_UNSUPPORTED,
-                 "%s: shape not taken by the split route (diqt_conv3d_fwd_split16_supported == 0)", who);
+    DIQT_REQUIRE(split16_any_plan(fill, g, lds, grid, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw), DIQT_E_UNSUPPORTED,
+                 "%s: shape not taken by the split route (diqt_conv3d_fwd_split16%s_supported == 0)", who, fill ? "_fill" : "");
     const unsigned rows = (unsigned)D * H * W;
     const size_t total8 = (size_t)B * rows * (Cin / 8);
     if (coef)
@@ -182,7 +228,7 @@ static int split16_run(const char* who, const float* x, void* x16, const void* p
 extern "C" int diqt_conv3d_fwd_split16(const float* x, void* x16, const void* packed, const float* bias, const float* residual, float* y,
                                        float* stats, int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph,
                                        int pw, int epd, int eph, int epw, void* stream) {
-    return split16_run("conv3d_fwd_split16", x, x16, packed, bias, residual, y, stats, nullptr, 0, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw,
+    return split16_run("conv3d_fwd_split16", false, x, x16, packed, bias, residual, y, stats, nullptr, 0, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw,
                        epd, eph, epw, stream);
 }
 
@@ -191,6 +237,49 @@ extern "C" int diqt_conv3d_fwd_gn_split16(const float* x, void* x16, const void*
                                           float* stats, const float* coef, int act, int B, int D, int H, int W, int Cin, int Cout, int kd,
                                           int kh, int kw, int pd, int ph, int pw, int epd, int eph, int epw, void* stream) {
     DIQT_REQUIRE(coef, DIQT_E_ALIGN, "conv3d_fwd_gn_split16: null coefficients");
-    return split16_run("conv3d_fwd_gn_split16", x, x16, packed, bias, residual, y, stats, coef, act, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw,
+    return split16_run("conv3d_fwd_gn_split16", false, x, x16, packed, bias, residual, y, stats, coef, act, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw,
                        epd, eph, epw, stream);
+}
+
+// ---- the fill plan's queries and entry points: the arguments and meanings of their namesakes above, answered by split16_fill_plan ----
+extern "C" int diqt_conv3d_fwd_split16_fill_supported(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph,
+                                                      int pw, int epd, int eph, int epw) {
+    H9Geom g; size_t lds; unsigned grid;
+    return split16_fill_plan(g, lds, grid, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw) ? 1 : 0;
+}
+
+extern "C" int diqt_conv3d_fwd_gn_split16_fill_supported(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph,
+                                                         int pw, int epd, int eph, int epw, int act) {
+    return split16_act_ok(act) ? diqt_conv3d_fwd_split16_fill_supported(B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw) : 0;
+}
+
+extern "C" int diqt_conv3d_fwd_split16_fill_stats_blocks(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph,
+                                                         int pw, int epd, int eph, int epw) {
+    H9Geom g; size_t lds; unsigned grid;
+    if (!split16_fill_plan(g, lds, grid, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw)) return 0;
+    return f9h_stats_blocks(g);
+}
+
+// 6: H9S_333_256, 7: H9S_333_128, 8: H9S_333_64, -1: not taken
+extern "C" int diqt_conv3d_fwd_split16_fill_variant(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph,
+                                                    int pw, int epd, int eph, int epw) {
+    H9Geom g; size_t lds; unsigned grid;
+    if (!split16_fill_plan(g, lds, grid, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw)) return -1;
+    return g.variant;
+}
+
+extern "C" int diqt_conv3d_fwd_split16_fill(const float* x, void* x16, const void* packed, const float* bias, const float* residual, float* y,
+                                            float* stats, int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd,
+                                            int ph, int pw, int epd, int eph, int epw, void* stream) {
+    return split16_run("conv3d_fwd_split16_fill", true, x, x16, packed, bias, residual, y, stats, nullptr, 0, B, D, H, W, Cin, Cout, kd, kh, kw,
+                       pd, ph, pw, epd, eph, epw, stream);
+}
+
+extern "C" int diqt_conv3d_fwd_gn_split16_fill(const float* x, void* x16, const void* packed, const float* bias, const float* residual,
+                                               float* y, float* stats, const float* coef, int act, int B, int D, int H, int W, int Cin,
+                                               int Cout, int kd, int kh, int kw, int pd, int ph, int pw, int epd, int eph, int epw,
+                                               void* stream) {
+    DIQT_REQUIRE(coef, DIQT_E_ALIGN, "conv3d_fwd_gn_split16_fill: null coefficients");
+    return split16_run("conv3d_fwd_gn_split16_fill", true, x, x16, packed, bias, residual, y, stats, coef, act, B, D, H, W, Cin, Cout, kd, kh,
+                       kw, pd, ph, pw, epd, eph, epw, stream);
 }

@@ -282,14 +282,27 @@ def _packed_split16(weight5):
     return packed
 
 
-def _conv_fwd_split16(x5, weight, bias, residual, pad, epad, want_stats, coef=None, act=0):
+def _split16_plan(geo, act, split16):
+    """Which plan of the split route takes the launch: "" (the 256-voxel tiles, ``split16=True``), "_fill" (``split16="fill"``: the fill
+    plan is asked first -- smaller tiles where the 256-voxel ones leave CUs idle -- then the other), None: neither, or switched off.
+    The value is the suffix of the entry points' names."""
+    if not split16 or not SPLIT16:
+        return None
+    if split16 == "fill" and _lib.query("diqt_conv3d_fwd_gn_split16_fill_supported", *geo, act):
+        return "_fill"
+    return "" if _lib.query("diqt_conv3d_fwd_gn_split16_supported", *geo, act) else None
+
+
+def _conv_fwd_split16(x5, weight, bias, residual, pad, epad, want_stats, coef=None, act=0, split16=True):
     """fp32 3x3x3 forward on the fp16 matrix pipe by the three-product split (conv_split16.hip): the pass that splits x (with
     ``coef``: and applies act(A x + Bc), the GroupNorm-apply of ``gn_conv3d``), then ``conv_f9h_kernel``'s split build.  None when the
-    request is switched off (``SPLIT16``), the shape is not granted or the weight is refused; y carries ``_diqt_stats`` when asked."""
+    request is switched off (``SPLIT16``), the shape is not granted or the weight is refused; y carries ``_diqt_stats`` when asked.
+    ``split16``: True or "fill" (``_split16_plan``)."""
     B, D, H, W, Cin = x5.shape
     Cout, _, kd, kh, kw = weight.shape
     geo = (B, D, H, W, Cin, Cout, kd, kh, kw, *pad, *epad)
-    if not SPLIT16 or not _lib.query("diqt_conv3d_fwd_gn_split16_supported", *geo, act):
+    plan = _split16_plan(geo, act, split16)
+    if plan is None:
         return None
     packed = _packed_split16(weight)
     if packed is None:
@@ -302,13 +315,13 @@ def _conv_fwd_split16(x5, weight, bias, residual, pad, epad, want_stats, coef=No
         s.record()
     stats = None
     if want_stats:
-        nblk = _lib.query("diqt_conv3d_fwd_split16_stats_blocks", *geo)
+        nblk = _lib.query(f"diqt_conv3d_fwd_split16{plan}_stats_blocks", *geo)
         stats = torch.empty((B, nblk, 2, Cout), dtype=torch.float32, device=x5.device)
         y._diqt_stats = ColStats(stats, nblk, Do * Ho * Wo)
     if coef is None:
-        _lib.call("diqt_conv3d_fwd_split16", x5, x16, packed, bias, residual, y, stats, *geo, _stream())
+        _lib.call(f"diqt_conv3d_fwd_split16{plan}", x5, x16, packed, bias, residual, y, stats, *geo, _stream())
     else:
-        _lib.call("diqt_conv3d_fwd_gn_split16", x5, x16, packed, bias, residual, y, stats, coef, act, *geo, _stream())
+        _lib.call(f"diqt_conv3d_fwd_gn_split16{plan}", x5, x16, packed, bias, residual, y, stats, coef, act, *geo, _stream())
     if TIMER.enabled:
         e.record()
         TIMER.records.append((s, e, 2.0 * B * Do * Ho * Wo * Cout * Cin * kd * kh * kw, "conv_f9h_kernel_split16", geo[:9]))
@@ -690,14 +703,14 @@ def conv3d(x, weight, bias=None, padding=(0, 0, 0), residual=None, extra_pad=(0,
     """Stride-1 conv on channels-last x[B,D,H,W,Cin] with an OIDHW weight (MFMA implicit GEMM).
     Filters whose halo tile cannot fit the 160 KiB LDS (e.g. 15^3 cross-embed taps) take the direct kernel.
     ``split16`` (no autograd, no autocast): ask for the three-product split on the fp16 matrix pipe (``_conv_fwd_split16``); a launch
-    it does not grant takes the default route."""
+    it does not grant takes the default route.  ``split16="fill"`` asks its fill plan first (``_split16_plan``)."""
     if isinstance(padding, int):
         padding = (padding,) * 3
     padding = tuple(int(p) for p in padding)
     extra_pad = tuple(int(p) for p in extra_pad)
     if split16 and SPLIT16 and not torch.is_grad_enabled() and lp_mode() is None and x.dim() == 5 and x.shape[-1] == weight.shape[1]:
         _chk(x, weight, bias, residual)
-        y = _conv_fwd_split16(x, weight, bias, residual, padding, extra_pad, want_stats)
+        y = _conv_fwd_split16(x, weight, bias, residual, padding, extra_pad, want_stats, split16=split16)
         if y is not None:
             return y
     _, D, H, W, _ = x.shape
@@ -1338,7 +1351,7 @@ def gn_conv3d(x, gamma, beta, scale_shift, groups, act, eps, weight, bias, paddi
     ``conv_fwd9_kernel`` applies them to its input tiles while staging them (``diqt_conv3d_fwd_gn``).  Returns None when the shape is
     not taken (the caller then runs ``groupnorm_act`` + ``conv3d``).  ``split16``: ask for the three-product split on the fp16 matrix
     pipe instead -- the same coefficients, applied by the pass that splits x (``_conv_fwd_split16``); a launch it does not grant takes
-    the route above."""
+    the route above; ``split16="fill"`` asks the route's fill plan first (``_split16_plan``)."""
     if torch.is_grad_enabled() or lp_mode() is not None or x.dim() != 5:
         return None
     B, D, H, W, C = x.shape
@@ -1348,7 +1361,7 @@ def gn_conv3d(x, gamma, beta, scale_shift, groups, act, eps, weight, bias, paddi
     geo = (B, D, H, W, C, Cout, kd, kh, kw, *padding, *extra_pad)
     npk = sum(_packed_len(weight.shape, 0))
     # (the split route has its own planner: it also takes activations and shapes the GroupNorm-apply build of conv_fwd9_kernel does not)
-    use_split = bool(split16 and SPLIT16 and _lib.query("diqt_conv3d_fwd_gn_split16_supported", *geo, act))
+    use_split = _split16_plan(geo, act, split16) is not None
     default_ok = bool(_lib.query("diqt_conv3d_fwd_gn_supported_pk", *geo, act, npk))
     if Cin != C or C % groups != 0 or not (use_split or default_ok):
         return None
@@ -1376,7 +1389,7 @@ def gn_conv3d(x, gamma, beta, scale_shift, groups, act, eps, weight, bias, paddi
         ws, n = _reduce_ws(B, C, dev)
         _lib.call("diqt_groupnorm_stats_coef", x, gamma, beta, scale, shift, cs, mean, rstd, coef, ws, n, B, rows, C, groups, float(eps), s)
     if use_split:
-        y = _conv_fwd_split16(x, weight, bias, residual, padding, extra_pad, want_stats, coef, act)
+        y = _conv_fwd_split16(x, weight, bias, residual, padding, extra_pad, want_stats, coef, act, split16)
         if y is not None:
             return y
     if not default_ok:

@@ -136,7 +136,7 @@ int diqt_set_conv_f9h_mode(int mode);
  * 6 conv_pw_h_kernel on a pointwise conv, 7 conv_pw_h_kernel on a temporal conv, 8 conv_f9h_kernel.                                      */
 int diqt_conv3d_fwd_h_kernel_id(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw,
                                 int epd, int eph, int epw, int x_half, int y_half, int has_residual, int has_stats);
-/* the conv_f9h_kernel variant (0..5; 6: the split build of diqt_conv3d_fwd_split16) the process's last launch of it ran, -1 if none since the previous call (read and clear) */
+/* the conv_f9h_kernel variant (0..5; 6-8: the split builds of diqt_conv3d_fwd_split16*) the process's last launch of it ran, -1 if none since the previous call (read and clear) */
 int diqt_get_last_conv_f9h_variant(void);
 int diqt_conv3d_fwd_h(const float* x, const void* packed_h, const float* bias, const float* residual, float* y, int B, int D, int H,
                       int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw, int epd, int eph, int epw, int bf16,
@@ -167,6 +167,27 @@ int diqt_conv3d_fwd_split16(const float* x, void* x16, const void* packed, const
 int diqt_conv3d_fwd_gn_split16(const float* x, void* x16, const void* packed, const float* bias, const float* residual, float* y,
                                float* stats, const float* coef, int act, int B, int D, int H, int W, int Cin, int Cout, int kd, int kh,
                                int kw, int pd, int ph, int pw, int epd, int eph, int epw, void* stream);
+/* The fill plan of the same route (conv_split16_b.hip), for launches whose 256-voxel tiles leave CUs without a workgroup: the 256-,
+ * 128- and 64-voxel tiles (variants 6, 7, 8) are tried in that order, a smaller one only when the larger gives fewer than 256 (tile,
+ * 64-channel block) units; granted at 128 units or more and B Do Ho Wo Cin Cout >= 2^25 (diqt_set_conv_f9h_mode(2) lifts both floors).
+ * y is bit-identical to the plan above on a shape both take; the statistics have ..._fill_stats_blocks rows.  The arguments of the
+ * namesakes above.  diqt_set_conv_split16_fill_tile(6 | 7 | 8) pins the tile under mode 2 (tests), 0 unpins, < 0 queries; returns the
+ * previous value.                                                                                                                  */
+int diqt_set_conv_split16_fill_tile(int variant);
+int diqt_conv3d_fwd_split16_fill_supported(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw,
+                                           int epd, int eph, int epw);
+int diqt_conv3d_fwd_gn_split16_fill_supported(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw,
+                                              int epd, int eph, int epw, int act);
+int diqt_conv3d_fwd_split16_fill_stats_blocks(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw,
+                                              int epd, int eph, int epw);
+int diqt_conv3d_fwd_split16_fill_variant(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw,
+                                         int epd, int eph, int epw);
+int diqt_conv3d_fwd_split16_fill(const float* x, void* x16, const void* packed, const float* bias, const float* residual, float* y,
+                                 float* stats, int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw,
+                                 int epd, int eph, int epw, void* stream);
+int diqt_conv3d_fwd_gn_split16_fill(const float* x, void* x16, const void* packed, const float* bias, const float* residual, float* y,
+                                    float* stats, const float* coef, int act, int B, int D, int H, int W, int Cin, int Cout, int kd, int kh,
+                                    int kw, int pd, int ph, int pw, int epd, int eph, int epw, void* stream);
 
 /* Forward conv that also emits per-tile column sums of its OUTPUT for the consumer's GroupNorm statistics / SE pooling
  * (Block -> Block and Block -> SE3D inside ResnetBlock, imagen_pytorch3D.py:568-632): stats[B][nblk][2][Cout] =

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Micro-benchmark of the MFMA conv kernels on the dominant C2 shape (B=8, 32^3, 64->64, 3x3x3) — for
-rocprofv3 --pmc passes and A/B timing.  Usage: python tools/conv_bench.py [fwd|bwdw|both|gn|s16|fwdh] [iters] [B S Cin Cout]"""
+rocprofv3 --pmc passes and A/B timing.  Usage: python tools/conv_bench.py [fwd|bwdw|both|gn|s16|s16f|fwdh] [iters] [B S Cin Cout]"""
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -61,7 +61,26 @@ if mode == "s16":               # Block on the sampling path: the three-product 
         ms_s2, ms_w2 = timeit(lambda: gn(True), iters), timeit(lambda: gn(False), iters)
     print(f"GN+act+conv B={B} {SP} {Cin}->{Cout}: split16 {ms_s*1e3:.1f} / {ms_s2*1e3:.1f} us, Winograd {ms_w*1e3:.1f} / {ms_w2*1e3:.1f} us "
           f"(both incl. statistics / coefficient launch; two alternating rounds)")
-if mode in ("fwdh",):           # fp16 / bf16 operand kernel (LP=fp16|bf16)
+if mode == "s16f":              # the split route's fill plan (128- / 64-voxel tiles) vs what split16=True runs on the shape (its 256-voxel tiles or, refused, the Winograd launch)
+    gamma, beta = torch.randn(Cin, device=dev), torch.randn(Cin, device=dev)
+    ss = torch.randn(B, 2 * Cin, device=dev) * 0.3
+    gn = lambda s16: ops.gn_conv3d(x, gamma, beta, ss, 8, ops.ACT_MISH, 1e-5, w, bias, PADS, want_stats=True, split16=s16)
+    rounds = int(os.environ.get("ROUNDS", "3"))
+    with torch.no_grad():
+        assert gn("fill") is not None and "split16" in _lib.last_launch(), "shape not granted to the fill plan"
+        var = _lib.query("diqt_get_last_conv_f9h_variant")
+        fused = gn(True) is not None      # (None: no one-launch route today -- the Block then runs groupnorm_act + conv3d)
+
+        def old():
+            if fused:
+                return gn(True)
+            return ops.conv3d(ops.groupnorm_act(x, gamma, beta, ss, 8, ops.ACT_MISH), w, bias, PADS, want_stats=True)
+        old()
+        today = _lib.last_launch()
+        res = [(timeit(lambda: gn("fill"), iters), timeit(old, iters)) for _ in range(rounds)]
+    print(f"GN+act+conv B={B} {SP} {Cin}->{Cout}: fill (variant {var}) " + " / ".join(f"{a*1e3:.1f}" for a, _ in res) + f" us, today ({today}) "
+          + " / ".join(f"{b*1e3:.1f}" for _, b in res) + f" us (both incl. statistics / coefficient launch; {rounds} alternating rounds)")
+if mode in ("fwdh",):          # fp16 / bf16 operand kernel (LP=fp16|bf16)
     with torch.no_grad(), ops.low_precision(os.environ.get("LP", "fp16")):
         ms = timeit(lambda: ops.conv3d(x, w, bias, PADS), iters)
     print(f"conv fwd {os.environ.get('LP', 'fp16')}  B={B} {S}^3 {Cin}->{Cout}: {ms*1e3:.1f} us  {flops/ms/1e9:.1f} TFLOP/s")
