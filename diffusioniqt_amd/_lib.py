@@ -247,6 +247,12 @@ PROTOTYPES = {
     "diqt_conv3d_fwd_split16_fill_variant": (I, [I] * 15),
     "diqt_conv3d_fwd_split16_fill": (I, [P, P, P, P, P, P, P] + [I] * 15 + [P]),
     "diqt_conv3d_fwd_gn_split16_fill": (I, [P, P, P, P, P, P, P, P, I] + [I] * 15 + [P]),
+    "diqt_conv3d_fwd_split16_pair_supported": (I, [I] * 15),
+    "diqt_conv3d_fwd_gn_split16_pair_supported": (I, [I] * 16),
+    "diqt_conv3d_fwd_split16_pair_stats_blocks": (I, [I] * 15),
+    "diqt_conv3d_fwd_split16_pair": (I, [P, P, P, P, P, P, P] + [I] * 15 + [P]),
+    "diqt_conv3d_fwd_gn_split16_pair": (I, [P, P, P, P, P, P, P, P, I] + [I] * 15 + [P]),
+    "diqt_conv_split16_pair_lds_conflicts": (I, []),
 }
 
 _lib = None

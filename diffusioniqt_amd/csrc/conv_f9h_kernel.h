@@ -624,6 +624,9 @@ int launch_split(const void* x, const unsigned short* wp, const float* bias, con
                  unsigned grid, void* stream);
 int launch_split_b(const void* x, const unsigned short* wp, const float* bias, const float* residual, void* y, const H9Geom& g, size_t lds,
                    unsigned grid, void* stream);
+// variant 9, the tap-paired body (conv_f9p_kernel.h, conv_split16_c.hip)
+int launch_split_c(const void* x, const unsigned short* wp, const float* bias, const float* residual, void* y, const H9Geom& g, size_t lds,
+                   unsigned grid, void* stream);
 
 }  // namespace h9
 }  // namespace diqt

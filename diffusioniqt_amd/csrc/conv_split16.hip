@@ -85,6 +85,7 @@ int launch_split(const void* x, const unsigned short* wp, const float* bias, con
                  unsigned grid, void* stream) {
     if (g.variant == 6) return launch_split_cfg<H9S_333_256>(x, wp, bias, residual, y, g, lds, grid, stream);
     if (g.variant == 7 || g.variant == 8) return launch_split_b(x, wp, bias, residual, y, g, lds, grid, stream);
+    if (g.variant == 9) return launch_split_c(x, wp, bias, residual, y, g, lds, grid, stream);
     set_error("conv3d_fwd_split16(v9h): no variant %d", g.variant);
     return DIQT_E_UNSUPPORTED;
 }
@@ -146,10 +147,34 @@ static bool split16_fill_plan(H9Geom& g, size_t& lds, unsigned& grid, int B, int
     return true;
 }
 
-static bool split16_any_plan(bool fill, H9Geom& g, size_t& lds, unsigned& grid, int B, int D, int H, int W, int Cin, int Cout, int kd, int kh,
+// The pair plan (round 11): the 256-voxel tile's launches on the tap-paired 16x16x32 body (variant 9: conv_split16_c.hip) -- the tiling,
+// the statistics rows, x' and the packed weights of variant 6.  Granted where that tile fills the chip: at least 256 (tile, 64-channel
+// block) units and 2^25 voxel x Cin x Cout products (diqt_set_conv_f9h_mode(2) lifts both floors).  In C2: 64 -> 64 and 128 -> 64 @
+// 8 x 32^3, 128 -> 128 and 192 -> 128 @ 8 x 16^3.
+static bool split16_pair_plan(H9Geom& g, size_t& lds, unsigned& grid, int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw,
+                              int pd, int ph, int pw, int epd, int eph, int epw) {
+    if (Cin <= 0 || Cin % S16_CG != 0 || Cin > (1 << 20)) return false;
+    if (!f9h_plan(g, lds, grid, B, D, H, W, 2 * Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw, false, true, 6)) return false;
+    if (diqt_set_conv_f9h_mode(-1) != 2) {
+        const long long units = (long long)g.MT * g.nNt;
+        if (units < 256) return false;
+        if ((unsigned long long)B * g.Do * g.Ho * g.Wo * (unsigned long long)Cin * (unsigned long long)Cout < (1ull << 25)) return false;
+        // sent back by measurement (round 11): a workgroup whose walk is a single tile needs eight chunks to pay for the body's longer
+        // prologue -- 64 -> 128 @ 8 x 16^3 (one tile of four chunks) took 54.9-55.8 us against 53.8-54.2 us on variant 6
+        if (units <= (long long)grid && g.nChunks < 8) return false;
+    }
+    g.variant = 9;
+    return true;
+}
+
+enum { S16_PLAN = 0, S16_FILL = 1, S16_PAIR = 2 };
+static const char* const s16_suffix[3] = {"", "_fill", "_pair"};
+
+static bool split16_any_plan(int plan, H9Geom& g, size_t& lds, unsigned& grid, int B, int D, int H, int W, int Cin, int Cout, int kd, int kh,
                              int kw, int pd, int ph, int pw, int epd, int eph, int epw) {
-    return fill ? split16_fill_plan(g, lds, grid, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw)
-                : split16_plan(g, lds, grid, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw);
+    if (plan == S16_PAIR) return split16_pair_plan(g, lds, grid, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw);
+    return plan == S16_FILL ? split16_fill_plan(g, lds, grid, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw)
+                            : split16_plan(g, lds, grid, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw);
 }
 
 static bool split16_act_ok(int act) { return act == 0 || act == DIQT_ACT_MISH || act == DIQT_ACT_SILU || act == DIQT_ACT_GELU; }
@@ -199,7 +224,7 @@ extern "C" int diqt_conv3d_fwd_split16_variant(int B, int D, int H, int W, int C
     return g.variant;
 }
 
-static int split16_run(const char* who, bool fill, const float* x, void* x16, const void* packed, const float* bias, const float* residual, float* y,
+static int split16_run(const char* who, int plan, const float* x, void* x16, const void* packed, const float* bias, const float* residual, float* y,
                        float* stats, const float* coef, int act, int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd,
                        int ph, int pw, int epd, int eph, int epw, void* stream) {
     DIQT_REQUIRE(x && x16 && packed && y, DIQT_E_ALIGN, "%s: null pointer", who);
@@ -207,8 +232,8 @@ static int split16_run(const char* who, bool fill, const float* x, void* x16, co
                  (!coef || aligned16(coef)), DIQT_E_ALIGN, "%s: tensors must be 16-byte aligned", who);
     DIQT_REQUIRE(split16_act_ok(act), DIQT_E_UNSUPPORTED, "%s: activation %d", who, act);
     H9Geom g; size_t lds; unsigned grid;
-    DIQT_REQUIRE(split16_any_plan(fill, g, lds, grid, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw), DIQT_E_UNSUPPORTED,
-                 "%s: shape not taken by the split route (diqt_conv3d_fwd_split16%s_supported == 0)", who, fill ? "_fill" : "");
+    DIQT_REQUIRE(split16_any_plan(plan, g, lds, grid, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw), DIQT_E_UNSUPPORTED,
+                 "%s: shape not taken by the split route (diqt_conv3d_fwd_split16%s_supported == 0)", who, s16_suffix[plan]);
     const unsigned rows = (unsigned)D * H * W;
     const size_t total8 = (size_t)B * rows * (Cin / 8);
     if (coef)
@@ -228,7 +253,7 @@ static int split16_run(const char* who, bool fill, const float* x, void* x16, co
 extern "C" int diqt_conv3d_fwd_split16(const float* x, void* x16, const void* packed, const float* bias, const float* residual, float* y,
                                        float* stats, int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph,
                                        int pw, int epd, int eph, int epw, void* stream) {
-    return split16_run("conv3d_fwd_split16", false, x, x16, packed, bias, residual, y, stats, nullptr, 0, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw,
+    return split16_run("conv3d_fwd_split16", S16_PLAN, x, x16, packed, bias, residual, y, stats, nullptr, 0, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw,
                        epd, eph, epw, stream);
 }
 
@@ -237,7 +262,7 @@ extern "C" int diqt_conv3d_fwd_gn_split16(const float* x, void* x16, const void*
                                           float* stats, const float* coef, int act, int B, int D, int H, int W, int Cin, int Cout, int kd,
                                           int kh, int kw, int pd, int ph, int pw, int epd, int eph, int epw, void* stream) {
     DIQT_REQUIRE(coef, DIQT_E_ALIGN, "conv3d_fwd_gn_split16: null coefficients");
-    return split16_run("conv3d_fwd_gn_split16", false, x, x16, packed, bias, residual, y, stats, coef, act, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw,
+    return split16_run("conv3d_fwd_gn_split16", S16_PLAN, x, x16, packed, bias, residual, y, stats, coef, act, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw,
                        epd, eph, epw, stream);
 }
 
@@ -271,7 +296,7 @@ extern "C" int diqt_conv3d_fwd_split16_fill_variant(int B, int D, int H, int W, 
 extern "C" int diqt_conv3d_fwd_split16_fill(const float* x, void* x16, const void* packed, const float* bias, const float* residual, float* y,
                                             float* stats, int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd,
                                             int ph, int pw, int epd, int eph, int epw, void* stream) {
-    return split16_run("conv3d_fwd_split16_fill", true, x, x16, packed, bias, residual, y, stats, nullptr, 0, B, D, H, W, Cin, Cout, kd, kh, kw,
+    return split16_run("conv3d_fwd_split16_fill", S16_FILL, x, x16, packed, bias, residual, y, stats, nullptr, 0, B, D, H, W, Cin, Cout, kd, kh, kw,
                        pd, ph, pw, epd, eph, epw, stream);
 }
 
@@ -280,6 +305,42 @@ extern "C" int diqt_conv3d_fwd_gn_split16_fill(const float* x, void* x16, const 
                                                int Cout, int kd, int kh, int kw, int pd, int ph, int pw, int epd, int eph, int epw,
                                                void* stream) {
     DIQT_REQUIRE(coef, DIQT_E_ALIGN, "conv3d_fwd_gn_split16_fill: null coefficients");
-    return split16_run("conv3d_fwd_gn_split16_fill", true, x, x16, packed, bias, residual, y, stats, coef, act, B, D, H, W, Cin, Cout, kd, kh,
+    return split16_run("conv3d_fwd_gn_split16_fill", S16_FILL, x, x16, packed, bias, residual, y, stats, coef, act, B, D, H, W, Cin, Cout, kd, kh,
                        kw, pd, ph, pw, epd, eph, epw, stream);
+}
+
+// ---- the pair plan's queries and entry points: the arguments and meanings of their namesakes above, answered by split16_pair_plan ----
+extern "C" int diqt_conv3d_fwd_split16_pair_supported(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph,
+                                                      int pw, int epd, int eph, int epw) {
+    H9Geom g; size_t lds; unsigned grid;
+    return split16_pair_plan(g, lds, grid, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw) ? 1 : 0;
+}
+
+extern "C" int diqt_conv3d_fwd_gn_split16_pair_supported(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph,
+                                                         int pw, int epd, int eph, int epw, int act) {
+    return split16_act_ok(act) ? diqt_conv3d_fwd_split16_pair_supported(B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw) : 0;
+}
+
+// (variant 6's row layout)
+extern "C" int diqt_conv3d_fwd_split16_pair_stats_blocks(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph,
+                                                         int pw, int epd, int eph, int epw) {
+    H9Geom g; size_t lds; unsigned grid;
+    if (!split16_pair_plan(g, lds, grid, B, D, H, W, Cin, Cout, kd, kh, kw, pd, ph, pw, epd, eph, epw)) return 0;
+    return f9h_stats_blocks(g);
+}
+
+extern "C" int diqt_conv3d_fwd_split16_pair(const float* x, void* x16, const void* packed, const float* bias, const float* residual, float* y,
+                                            float* stats, int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd,
+                                            int ph, int pw, int epd, int eph, int epw, void* stream) {
+    return split16_run("conv3d_fwd_split16_pair", S16_PAIR, x, x16, packed, bias, residual, y, stats, nullptr, 0, B, D, H, W, Cin, Cout, kd, kh,
+                       kw, pd, ph, pw, epd, eph, epw, stream);
+}
+
+extern "C" int diqt_conv3d_fwd_gn_split16_pair(const float* x, void* x16, const void* packed, const float* bias, const float* residual,
+                                               float* y, float* stats, const float* coef, int act, int B, int D, int H, int W, int Cin,
+                                               int Cout, int kd, int kh, int kw, int pd, int ph, int pw, int epd, int eph, int epw,
+                                               void* stream) {
+    DIQT_REQUIRE(coef, DIQT_E_ALIGN, "conv3d_fwd_gn_split16_pair: null coefficients");
+    return split16_run("conv3d_fwd_gn_split16_pair", S16_PAIR, x, x16, packed, bias, residual, y, stats, coef, act, B, D, H, W, Cin, Cout, kd,
+                       kh, kw, pd, ph, pw, epd, eph, epw, stream);
 }

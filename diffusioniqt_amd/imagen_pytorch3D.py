@@ -345,13 +345,16 @@ class LearnedSinusoidalPosEmb(nn.Module):
 
 def _split16_pays(x, weight):
     """Sampling path, fp32: does this Block ask for the three-product split of its 3x3x3 conv (``ops.gn_conv3d(split16=True)``)?  No
-    autograd, no autocast, and a launch one of the route's plans grants.  The fill plan is asked first ("fill": 128- / 64-voxel tiles
+    autograd, no autocast, and a launch one of the route's plans grants.  The pair plan is asked first ("pair": the tap-paired 16x16x32
+    body where the 256-voxel tile fills the chip -- C2's 32^3 level and its 128-channel convs at 16^3), then the fill plan ("fill": 128- / 64-voxel tiles
     where the 256-voxel ones leave CUs idle, at least 128 units and 2^25 voxel x Cin x Cout products -- C2's 64-channel convs at 16^3 and
     its 8^3 level), then the 256-voxel plan (True: at least 128 (tile, 64-channel block) units, the 32^3 and 16^3 levels of the C2 / C4
     U-Nets).  Tiny networks keep the kernels and the bits the parity suite pins."""
     if torch.is_grad_enabled() or ops.lp_mode() is not None or x.dim() != 5 or tuple(weight.shape[2:]) != (3, 3, 3):
         return False
     geo = (*x.shape, weight.shape[0], 3, 3, 3, 1, 1, 1, 0, 0, 0)
+    if ops._lib.query("diqt_conv3d_fwd_split16_pair_supported", *geo):
+        return "pair"
     if ops._lib.query("diqt_conv3d_fwd_split16_fill_supported", *geo):
         return "fill"
     return bool(ops._lib.query("diqt_conv3d_fwd_split16_supported", *geo))

@@ -284,11 +284,14 @@ def _packed_split16(weight5):
 
 def _split16_plan(geo, act, split16):
     """Which plan of the split route takes the launch: "" (the 256-voxel tiles, ``split16=True``), "_fill" (``split16="fill"``: the fill
-    plan is asked first -- smaller tiles where the 256-voxel ones leave CUs idle -- then the other), None: neither, or switched off.
-    The value is the suffix of the entry points' names."""
+    plan is asked first -- smaller tiles where the 256-voxel ones leave CUs idle -- then the other), "_pair" (``split16="pair"``: the
+    pair plan is asked first -- the tap-paired 16x16x32 body where the 256-voxel tile fills the chip -- then what "fill" answers),
+    None: none of them, or switched off.  The value is the suffix of the entry points' names."""
     if not split16 or not SPLIT16:
         return None
-    if split16 == "fill" and _lib.query("diqt_conv3d_fwd_gn_split16_fill_supported", *geo, act):
+    if split16 == "pair" and _lib.query("diqt_conv3d_fwd_gn_split16_pair_supported", *geo, act):
+        return "_pair"
+    if split16 in ("fill", "pair") and _lib.query("diqt_conv3d_fwd_gn_split16_fill_supported", *geo, act):
         return "_fill"
     return "" if _lib.query("diqt_conv3d_fwd_gn_split16_supported", *geo, act) else None
 
@@ -297,7 +300,7 @@ def _conv_fwd_split16(x5, weight, bias, residual, pad, epad, want_stats, coef=No
     """fp32 3x3x3 forward on the fp16 matrix pipe by the three-product split (conv_split16.hip): the pass that splits x (with
     ``coef``: and applies act(A x + Bc), the GroupNorm-apply of ``gn_conv3d``), then ``conv_f9h_kernel``'s split build.  None when the
     request is switched off (``SPLIT16``), the shape is not granted or the weight is refused; y carries ``_diqt_stats`` when asked.
-    ``split16``: True or "fill" (``_split16_plan``)."""
+    ``split16``: True, "fill" or "pair" (``_split16_plan``)."""
     B, D, H, W, Cin = x5.shape
     Cout, _, kd, kh, kw = weight.shape
     geo = (B, D, H, W, Cin, Cout, kd, kh, kw, *pad, *epad)
@@ -703,7 +706,8 @@ def conv3d(x, weight, bias=None, padding=(0, 0, 0), residual=None, extra_pad=(0,
     """Stride-1 conv on channels-last x[B,D,H,W,Cin] with an OIDHW weight (MFMA implicit GEMM).
     Filters whose halo tile cannot fit the 160 KiB LDS (e.g. 15^3 cross-embed taps) take the direct kernel.
     ``split16`` (no autograd, no autocast): ask for the three-product split on the fp16 matrix pipe (``_conv_fwd_split16``); a launch
-    it does not grant takes the default route.  ``split16="fill"`` asks its fill plan first (``_split16_plan``)."""
+    it does not grant takes the default route.  ``split16="fill"`` asks its fill plan first, ``split16="pair"`` its pair plan and then the
+    fill plan (``_split16_plan``)."""
     if isinstance(padding, int):
         padding = (padding,) * 3
     padding = tuple(int(p) for p in padding)
@@ -1351,7 +1355,8 @@ def gn_conv3d(x, gamma, beta, scale_shift, groups, act, eps, weight, bias, paddi
     ``conv_fwd9_kernel`` applies them to its input tiles while staging them (``diqt_conv3d_fwd_gn``).  Returns None when the shape is
     not taken (the caller then runs ``groupnorm_act`` + ``conv3d``).  ``split16``: ask for the three-product split on the fp16 matrix
     pipe instead -- the same coefficients, applied by the pass that splits x (``_conv_fwd_split16``); a launch it does not grant takes
-    the route above; ``split16="fill"`` asks the route's fill plan first (``_split16_plan``)."""
+    the route above; ``split16="fill"`` asks the route's fill plan first, ``split16="pair"`` its pair plan and then the fill plan
+    (``_split16_plan``)."""
     if torch.is_grad_enabled() or lp_mode() is not None or x.dim() != 5:
         return None
     B, D, H, W, C = x.shape

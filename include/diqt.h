@@ -136,7 +136,7 @@ int diqt_set_conv_f9h_mode(int mode);
  * 6 conv_pw_h_kernel on a pointwise conv, 7 conv_pw_h_kernel on a temporal conv, 8 conv_f9h_kernel.                                      */
 int diqt_conv3d_fwd_h_kernel_id(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw,
                                 int epd, int eph, int epw, int x_half, int y_half, int has_residual, int has_stats);
-/* the conv_f9h_kernel variant (0..5; 6-8: the split builds of diqt_conv3d_fwd_split16*) the process's last launch of it ran, -1 if none since the previous call (read and clear) */
+/* the conv_f9h_kernel variant (0..5; 6-8: the split builds of diqt_conv3d_fwd_split16*, 9: its tap-paired build) the process's last launch of it ran, -1 if none since the previous call (read and clear) */
 int diqt_get_last_conv_f9h_variant(void);
 int diqt_conv3d_fwd_h(const float* x, const void* packed_h, const float* bias, const float* residual, float* y, int B, int D, int H,
                       int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw, int epd, int eph, int epw, int bf16,
@@ -188,6 +188,25 @@ int diqt_conv3d_fwd_split16_fill(const float* x, void* x16, const void* packed, 
 int diqt_conv3d_fwd_gn_split16_fill(const float* x, void* x16, const void* packed, const float* bias, const float* residual, float* y,
                                     float* stats, const float* coef, int act, int B, int D, int H, int W, int Cin, int Cout, int kd, int kh,
                                     int kw, int pd, int ph, int pw, int epd, int eph, int epw, void* stream);
+/* The pair plan of the same route (conv_split16_c.hip): the 256-voxel tile on a tap-paired v_mfma_f32_16x16x32_f16 body (variant 9; two
+ * taps per product, two accumulator sets), the same x16, packed weights, tiling and statistics rows as variant 6.  Granted for 3x3x3
+ * filters with Cin % 16 == 0 at 256 (tile, 64-channel block) units or more, B Do Ho Wo Cin Cout >= 2^25 and, where every workgroup has a
+ * single tile (units <= workgroups), Cin >= 128 = eight chunks of 16 channels (diqt_set_conv_f9h_mode(2) lifts the three floors).  y differs from variant 6's in the last bits (another order of the fp32 sums).  The arguments of the namesakes
+ * above.  diqt_conv_split16_pair_lds_conflicts (host only): the worst number of distinct addresses on one 16-byte LDS slot among the
+ * lanes a ds_read_b128 serves together, over all fragment reads of the body; 1 = conflict-free.                                      */
+int diqt_conv3d_fwd_split16_pair_supported(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw,
+                                           int epd, int eph, int epw);
+int diqt_conv3d_fwd_gn_split16_pair_supported(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw,
+                                              int epd, int eph, int epw, int act);
+int diqt_conv3d_fwd_split16_pair_stats_blocks(int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw,
+                                              int epd, int eph, int epw);
+int diqt_conv3d_fwd_split16_pair(const float* x, void* x16, const void* packed, const float* bias, const float* residual, float* y,
+                                 float* stats, int B, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int pd, int ph, int pw,
+                                 int epd, int eph, int epw, void* stream);
+int diqt_conv3d_fwd_gn_split16_pair(const float* x, void* x16, const void* packed, const float* bias, const float* residual, float* y,
+                                    float* stats, const float* coef, int act, int B, int D, int H, int W, int Cin, int Cout, int kd, int kh,
+                                    int kw, int pd, int ph, int pw, int epd, int eph, int epw, void* stream);
+int diqt_conv_split16_pair_lds_conflicts(void);
 
 /* Forward conv that also emits per-tile column sums of its OUTPUT for the consumer's GroupNorm statistics / SE pooling
  * (Block -> Block and Block -> SE3D inside ResnetBlock, imagen_pytorch3D.py:568-632): stats[B][nblk][2][Cout] =

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Micro-benchmark of the MFMA conv kernels on the dominant C2 shape (B=8, 32^3, 64->64, 3x3x3) — for
-rocprofv3 --pmc passes and A/B timing.  Usage: python tools/conv_bench.py [fwd|bwdw|both|gn|s16|s16f|fwdh] [iters] [B S Cin Cout]"""
+rocprofv3 --pmc passes and A/B timing.  Usage: python tools/conv_bench.py [fwd|bwdw|both|gn|s16|s16f|s16p|fwdh] [iters] [B S Cin Cout]"""
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -80,6 +80,21 @@ if mode == "s16f":              # the split route's fill plan (128- / 64-voxel t
         res = [(timeit(lambda: gn("fill"), iters), timeit(old, iters)) for _ in range(rounds)]
     print(f"GN+act+conv B={B} {SP} {Cin}->{Cout}: fill (variant {var}) " + " / ".join(f"{a*1e3:.1f}" for a, _ in res) + f" us, today ({today}) "
           + " / ".join(f"{b*1e3:.1f}" for _, b in res) + f" us (both incl. statistics / coefficient launch; {rounds} alternating rounds)")
+if mode == "s16p":              # the split route's pair plan (variant 9: tap-paired 16x16x32 body) vs what "fill" runs on the shape today (variant 6 where the pair plan grants)
+    gamma, beta = torch.randn(Cin, device=dev), torch.randn(Cin, device=dev)
+    ss = torch.randn(B, 2 * Cin, device=dev) * 0.3
+    gn = lambda s16: ops.gn_conv3d(x, gamma, beta, ss, 8, ops.ACT_MISH, 1e-5, w, bias, PADS, want_stats=True, split16=s16)
+    rounds = int(os.environ.get("ROUNDS", "3"))
+    with torch.no_grad():
+        _lib.query("diqt_get_last_conv_f9h_variant")
+        assert gn("pair") is not None and "split16" in _lib.last_launch(), "shape not granted to the split route"
+        var = _lib.query("diqt_get_last_conv_f9h_variant")
+        assert var == 9, f"shape not granted to the pair plan (variant {var})"
+        assert gn("fill") is not None
+        var_old = _lib.query("diqt_get_last_conv_f9h_variant")
+        res = [(timeit(lambda: gn("pair"), iters), timeit(lambda: gn("fill"), iters)) for _ in range(rounds)]
+    print(f"GN+act+conv B={B} {SP} {Cin}->{Cout}: pair (variant {var}) " + " / ".join(f"{a*1e3:.1f}" for a, _ in res) + f" us, today (variant {var_old}) "
+          + " / ".join(f"{b*1e3:.1f}" for _, b in res) + f" us (both incl. pre-pass, statistics / coefficient launch; {rounds} alternating rounds)")
 if mode in ("fwdh",):          # fp16 / bf16 operand kernel (LP=fp16|bf16)
     with torch.no_grad(), ops.low_precision(os.environ.get("LP", "fp16")):
         ms = timeit(lambda: ops.conv3d(x, w, bias, PADS), iters)

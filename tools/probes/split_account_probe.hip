@@ -6,7 +6,8 @@
 //   tools/probes/split_account_probe            (both shapes: 64 -> 64 @ 8 x 32^3 and 128 -> 128 @ 8 x 16^3)
 // PROBE_RS: the kernel's residual / statistics template argument (2 = statistics, no residual: the sampler's blocks); leave it undefined
 // for a revision of the header whose kernel has no such parameter.  PROBE_HEADER: another revision's conv_f9h_kernel.h (with the stamp
-// macro placed at the same points).  PROBE_BIAS_WAIT: the s_waitcnt in front of stamp 4 (default lgkmcnt(0): the staged bias; 0x0070 =
+// macro placed at the same points).  PROBE_PAIR: the tap-paired body instead (conv_f9p_kernel.h, variant 9, its 7-slot ring; needs PROBE_RS;
+// its "first PD taps" span is its first six pair steps, its MFMA floor per chunk 14 x 48 x 16 = 10752).  PROBE_BIAS_WAIT: the s_waitcnt in front of stamp 4 (default lgkmcnt(0): the staged bias; 0x0070 =
 // vmcnt(0) lgkmcnt(0) for a revision that loads the bias from global memory).
 //
 // Method (MI355X: the chip lowers its clock under load): random operands, at least 2 s of back-to-back launches, then the stamps of the
@@ -53,6 +54,9 @@ __device__ __forceinline__ void probe_stamp(int it, int c, int p) {
 #else
 #include "../../diffusioniqt_amd/csrc/conv_f9h_kernel.h"
 #endif
+#ifdef PROBE_PAIR
+#include "../../diffusioniqt_amd/csrc/conv_f9p_kernel.h"
+#endif
 
 namespace diqt {                     // the two host hooks of common.h that live in lib.cpp
 void set_error(const char*, ...) {}
@@ -61,7 +65,11 @@ void census_note(const char*) {}
 
 using namespace diqt;
 using Cf = h9::H9S_333_256;
-#ifdef PROBE_RS
+#if defined(PROBE_PAIR)
+static const auto kern = h9::conv_f9p_kernel<Cf, PROBE_RS, 7>;
+constexpr int RSV = PROBE_RS;
+constexpr size_t EXTRA_LDS = h9::BIASB;
+#elif defined(PROBE_RS)
 static const auto kern = h9::conv_f9h_kernel<Cf, false, false, true, PROBE_RS>;
 constexpr int RSV = PROBE_RS;
 constexpr size_t EXTRA_LDS = h9::BIASB;
@@ -164,7 +172,11 @@ static void run(int B, int S, int Cin, int Cout) {
             }
         }
     }
+#ifdef PROBE_PAIR
+    const double mfma = 14.0 * 48 * 16.0;                 // MFMA cycles of a chunk: 14 pair steps x 48 MFMAs x 16 cycles
+#else
     const double mfma = 3.0 * Cf::NVB * 27 * 32.0;       // MFMA cycles of a chunk: three products x NVB blocks x 27 taps x 32 cycles
+#endif
     printf("== %d -> %d @ %d x %d^3: grid %u, %d tile(s) per workgroup, %d chunks; %.1f us per launch (200 launches after %ld), "
            "%zu waves sampled\n", Cin, Cout, B, S, grid, tilesPerWg, g.nChunks, ms * 1e3 / 200, launches, life.size());
     printf("   in-kernel clock %.0f MHz; wave life %.0f cycles (MFMA floor %.0f = %d units x %.0f)\n", med(clk), med(life),
