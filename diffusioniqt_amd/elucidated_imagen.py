@@ -19,12 +19,11 @@ import torch
 from torch import nn
 
 from . import ops
+from .consistency import plan as consistency_plan, slope as state_slope
 from .graphs import GraphCache
 from .imagen_pytorch3D import (GaussianDiffusionContinuousTimes, Unet, NullUnet, exists, default, cast_tuple, identity, maybe,
                                normalize_neg_one_to_one, unnormalize_zero_to_one, eval_decorator, to_channels_last,
-                               to_channels_first, log_snr_to_alpha_sigma, check_consistency, check_consistency_operator,
-                               naming_consistency_noise, naming_consistency_row_noise, check_consistency_row_noise,
-                               scale_consistency_row_noise, consistency_row_noise_chain, check_consistency_slab)
+                               to_channels_first, log_snr_to_alpha_sigma)
 from .imagen_video import Unet3D
 
 Hparams_fields = ['num_sample_steps', 'sigma_min', 'sigma_max', 'sigma_data', 'rho', 'P_mean', 'P_std', 'S_churn', 'S_tmin',
@@ -437,61 +436,24 @@ class ElucidatedImagen(nn.Module):
         ``sampler='heun'``; one of the two without the other, another sampler or a count that is not a positive integer: ``ValueError``
         before anything touches the device.
 
-        ``consistency=(meas_up, cell)`` with ``consistency_weight`` (``sampler='dpmpp2m'`` only; ``check_consistency``): data-consistent
-        sampling for a block-average measurement (DDNM).  ``meas_up`` [B,C,P,P,P], the measurement replicated onto the high-res grid
-        (``ops.cell_replicate``), arrives in state space here (``sample`` takes it in the units it returns, like ``inpaint_images``).
-        Every step's clamped or thresholded prediction goes through ``ops.cell_project`` before ``ops.multistep_sde_step``; the
-        history operand and self-conditioning read the projected tensor.  The Heun sampler has two predictions per step and is
-        refused.  ``consistency_profile=(pz, py, px)`` (with ``consistency``; ``ops.cell_profile``): the measurement is the weighted
-        cell mean of a slice profile, zeros for a gap, and every ``ops.cell_project`` of the chain is one
-        ``ops.cell_project_profile`` -- a gap voxel is never moved.  ``consistency_noise=sigma`` (with ``consistency``; DDNM+): the
-        standard deviation of the measurement's noise in state space, like ``meas_up`` here.  ``ops.consistency_noise_schedule``
-        makes (w_i, shrink_i) once per chain from the host table (``consistency_weight`` is the cap); on their fp32 values a step with
-        w_i = 0 (kn = 0: the last) skips the projection, one with shrink_i = 0 projects with w_i, and any other runs ONE
-        ``ops.cell_project_noise``, which also reduces the step's normals in the range of A (into a new tensor).  The draws are
-        unchanged.  ``ValueError`` naming "consistency_noise": without ``consistency``, not a finite number > 0, eta = 0 (no
-        stochastic step: use a constant ``consistency_weight``), and everything ``consistency`` refuses.
-        ``consistency_operator=A`` (with ``consistency``; ``ops.tile_operator``): every tile of ``cell`` voxels is measured by the
-        m x n matrix A (orthogonal stacks: ``ops.stack_operator``); ``consistency=(target_up, cell)`` then carries t = A+ y
-        (``ops.tile_backproject``) in state space and every ``ops.cell_project`` of the chain is one ``ops.tile_project``.
-        ``ValueError`` naming "consistency_operator": without ``consistency``, together with ``consistency_profile`` or
-        ``consistency_noise``, or an operator ``ops.tile_operator`` refuses.
-        ``consistency_row_noise=sigma`` (with ``consistency_operator``; DDNM+ per singular direction): the deviation of the noise of
-        each row of A, one number or m of them, in state space like ``target_up``.  ``ops.tile_noise_tables`` makes (M_i, G_i) and
-        the dispatch once per chain: every lambda 0 skips the projection, one common weight and no shrink is ``ops.tile_project``,
-        any other step runs ONE ``ops.tile_project_noise`` on the step's draw.  ``ValueError`` naming "consistency_row_noise":
-        without ``consistency_operator``, with ``consistency_noise`` or ``consistency_profile``, eta = 0, values
-        ``ops.tile_noise_operator`` refuses, an LDS plan above 64 KiB, and everything ``consistency`` / ``consistency_operator``
-        refuse.
-        ``consistency_slab=(pz, py, px)`` (with ``consistency``; ``ops.slab_profile``): slice profiles that overlap between
-        neighbouring cells along z (``pz`` has fz + 2r entries, 1 <= r <= fz / 2); every ``ops.cell_project`` of the chain is one
-        ``ops.slab_project``, DDNM on the slices whose support lies inside the cube by one tridiagonal solve per column.
-        ``ValueError`` naming "consistency_slab": without ``consistency``, together with any of the four keywords above, a profile
-        ``ops.slab_profile`` refuses, and everything ``consistency`` refuses."""
+        ``consistency=(meas_up, cell)`` with ``consistency_weight`` (``sampler='dpmpp2m'`` only), ``consistency_profile``,
+        ``consistency_noise``, ``consistency_operator``, ``consistency_row_noise``, ``consistency_slab``: data-consistent sampling
+        (DDNM / DDNM+); the keywords, their rules and the launch a step takes are stated once, in ``consistency.py``.  ``meas_up``
+        [B,C,P,P,P], the measurement replicated onto the high-res grid (``ops.cell_replicate``; with an operator t = A+ y,
+        ``ops.tile_backproject``), and the noise deviations arrive in state space here (``sample`` takes them in the units it
+        returns, like ``inpaint_images``).  Every step's clamped or thresholded prediction goes through the mode's projection before
+        ``ops.multistep_sde_step``; the history operand and self-conditioning read the projected tensor.  A noise-aware step runs
+        its one launch on the step's draw and hands the step the reduced normals (a new tensor); the step with kn = 0 (the last)
+        skips the projection.  The draws are unchanged.  The Heun sampler has two predictions per step and is refused."""
         self._check_sampler_args(sampler, sample_steps, skip_steps, eta)
         has_inpainting = self._check_inpaint_args(sampler, inpaint_images, inpaint_masks, inpaint_resample_times)
-        check_consistency_slab('one_unet_sample', consistency_slab, exists(consistency), consistency_profile, consistency_noise,
-                               consistency_operator, consistency_row_noise)
-        check_consistency_row_noise('one_unet_sample', consistency_row_noise, consistency_operator, consistency_profile,
-                                    consistency_noise, eta != 0)
-        with naming_consistency_row_noise(consistency_row_noise):
-            check_consistency_operator('one_unet_sample', consistency_operator, exists(consistency), consistency_profile,
-                                       consistency_noise)
-            with naming_consistency_noise(consistency_noise):
-                consistency = check_consistency('one_unet_sample', consistency, consistency_weight, shape, has_inpainting, init_images,
-                                                skip_steps, sampler, profile=consistency_profile, operator=consistency_operator,
-                                                slab=consistency_slab)
-        if exists(consistency_noise):
-            consistency_noise = ops.consistency_noise_sigma('one_unet_sample', consistency_noise, exists(consistency), eta != 0)
-        consistency, table = (consistency[:3], consistency[3]) if exists(consistency) else (None, None)
+        plan = consistency_plan('one_unet_sample', ops, consistency, consistency_weight, consistency_profile, consistency_noise,
+                                consistency_operator, consistency_row_noise, consistency_slab, shape=shape, stochastic=eta != 0,
+                                has_inpainting=has_inpainting, init_images=init_images, skip_steps=skip_steps, sampler=sampler)
         if sampler == 'dpmpp2m':
             return self._dpmpp2m_sample(unet, shape, unet_number=unet_number, clamp=clamp, dynamic_threshold=dynamic_threshold,
                                         cond_scale=cond_scale, init_images=init_images, sigma_min=sigma_min, sigma_max=sigma_max,
-                                        noise=noise, sample_steps=sample_steps, eta=eta, consistency=consistency,
-                                        consistency_profile=table, consistency_noise=consistency_noise,
-                                        tile=exists(consistency_operator), slab=exists(consistency_slab),
-                                        row_noise=(consistency_operator, consistency_row_noise) if exists(consistency_row_noise)
-                                        else None, **kwargs)
+                                        noise=noise, sample_steps=sample_steps, eta=eta, consistency=plan, **kwargs)
         # Inpainting (:441-449, 473-530; RePaint, Lugmayr et al. 2022) is this loop with ``inpaint_resample_times`` passes per step,
         # r = R - 1 .. 0, where plain sampling has one: a pass draws ``eps``, pastes the known image under the mask and churns, runs the
         # two Heun evaluations as ever and -- unless r == 0 or it is the last step -- draws once more and re-noises,
@@ -557,51 +519,23 @@ class ElucidatedImagen(nn.Module):
         return self.unnormalize_img(images)
 
     def _dpmpp2m_sample(self, unet, shape, *, unet_number, clamp, dynamic_threshold, cond_scale, init_images, sigma_min, sigma_max, noise,
-                        sample_steps, eta, consistency=None, consistency_profile=None, consistency_noise=None, tile=False, row_noise=None,
-                        slab=False, **kwargs):
-        """``one_unet_sample(sampler='dpmpp2m')``; the arguments are checked there (``consistency``: None or the checked
-        ``(meas_up, cell, weight)``, ``meas_up`` in state space; ``consistency_profile``: None or the checked host table of
-        ``ops.cell_profile``, or (``slab``) the table of a ``consistency_slab``; ``consistency_noise``: None or the checked deviation in state space; ``tile``: the table is a
-        ``consistency_operator``'s projector and ``meas_up`` its t; ``row_noise``: None or (operator,
-        ``consistency_row_noise`` in state space))."""
+                        sample_steps, eta, consistency=None, **kwargs):
+        """``one_unet_sample(sampler='dpmpp2m')``; the arguments are checked there (``consistency``: None or the ``consistency.Plan``
+        of the call, its measurement and deviations in state space)."""
         sigmas, coefs = self._dpmpp2m_tables(unet_number - 1, sample_steps, eta, sigma_min, sigma_max)
-        kinds = None
-        if exists(row_noise):                                                   # once per chain: every step's tables, one upload
-            row_op, tables, kinds = consistency_row_noise_chain('one_unet_sample', row_noise[1], row_noise[0], consistency[1],
-                                                                consistency[2], coefs.double(), shape[2], self.device)
-            consistency_profile = row_op.table                                  # P of the whitened operator, for a constant-weight step
-        schedule = None
-        if exists(consistency_noise):                                           # once per chain, from the host table
-            schedule = ops.consistency_noise_dispatch(ops.consistency_noise_schedule(
-                coefs.double(), ops.cell_norm(consistency[1], consistency_profile), consistency_noise, consistency[2]))
+        chain = consistency.prepare(coefs.double(), self.device) if exists(consistency) else None      # once per chain
         sigmas = sigmas.tolist()
         dev, B = self.device, shape[0]
         draw, images, fwd, sc = self._start_chain(unet, shape, unet_number, sigmas[0], noise, init_images, clamp=clamp,
                                                   dynamic_threshold=dynamic_threshold, cond_scale=cond_scale, **kwargs)
         stochastic = (coefs[:, 3] != 0).tolist()
         k = coefs[:, :, None].expand(-1, -1, B).contiguous().to(dev)              # [T,4,B]: one coefficient row per sample
-        if exists(consistency):
-            meas_up, cell, weight = consistency
-            meas_up = meas_up.to(dev).float().contiguous()
-            table = consistency_profile.to(dev) if exists(consistency_profile) else None    # once per chain
         x_start = None
         for i in range(coefs.shape[0]):
             out = fwd(images, float(sigmas[i]), **sc(x_start))
-            if exists(schedule):                                                # consistency_noise: this step's own weight and shrink
-                weight, shrink = schedule[i]
-            if exists(kinds):                                                   # consistency_row_noise: plain, constant weight or tables
-                kind, weight = kinds[i]
-            shaped = None
-            if exists(kinds) and kind == 'noise':                               # one launch on the step's draw (kn != 0 here)
-                out, shaped = ops.tile_project_noise(out, meas_up, draw(), cell, tables[i])
-            elif exists(schedule) and weight > 0 and shrink > 0:                # one launch: the projection and the shaped normals;
-                out, shaped = ops.cell_project_noise(out, meas_up, draw(), cell, weight, shrink, table)   # kn != 0 here: the step's draw
-            elif exists(consistency) and weight > 0:                            # ``out`` arrives clamped or thresholded
-                out = ops.tile_project(out, meas_up, cell, table, weight) if tile else \
-                    ops.slab_project(out, meas_up, cell, table, weight) if slab else \
-                    ops.cell_project_profile(out, meas_up, cell, table, weight) if exists(table) else \
-                    ops.cell_project(out, meas_up, cell, weight)
-            eps = shaped if exists(shaped) else draw() if stochastic[i] else None
+            normals = lambda: draw() if stochastic[i] else None                 # the step's draw, where kn != 0
+            # ``out`` arrives clamped or thresholded; a launch that shapes the normals takes the draw first
+            out, eps, _ = chain.project(i, out, normals) if exists(chain) else (out, normals(), None)
             images = ops.multistep_sde_step(images, out, x_start, eps, k[i, 0], k[i, 1], k[i, 2], k[i, 3])
             x_start = out
         return self._finish_chain(images)
@@ -688,19 +622,13 @@ class ElucidatedImagen(nn.Module):
         images / masks alone, inpainting with 'dpmpp2m', or a count that is not a positive integer: ``ValueError`` naming "inpaint",
         before anything touches the device.
 
-        ``consistency=(meas_up, cell)`` / ``consistency_weight``: ``one_unet_sample``'s, for every sampled U-Net (so they must generate
-        one size); ``meas_up`` [B,C,P,P,P] in the units this returns (``normalize_img`` takes it to state space, as it does
-        ``inpaint_images``).  ``ValueError`` naming "consistency" before anything touches the device: with the Heun sampler, together
-        with inpainting, ``init_images`` or ``skip_steps``, a weight outside (0, 1], a cell that does not divide the image size or with
-        n outside 2 .. 64, a ``meas_up`` of another shape.  ``consistency_profile=(pz, py, px)``: ``one_unet_sample``'s slice profile;
-        without ``consistency``, or one ``ops.cell_profile`` refuses, it is the same ``ValueError``.  ``consistency_noise=sigma``:
-        ``one_unet_sample``'s, in the units of ``meas_up`` as passed here (it is multiplied by the slope of ``normalize_img``); every
-        refusal above then also names "consistency_noise", as do its own.  ``consistency_operator=A``: ``one_unet_sample``'s
-        tile-local linear measurement; ``consistency`` then carries t = A+ y in the units this returns, and its refusals name
-        "consistency_operator".  ``consistency_row_noise=sigma``: ``one_unet_sample``'s, in the units of ``target_up`` as passed
-        here (multiplied by the slope of ``normalize_img``); every refusal above then also names "consistency_row_noise".
-        ``consistency_slab=(pz, py, px)``: ``one_unet_sample``'s overlapping slice profiles; its refusals, and those of
-        ``consistency`` when it is given, name "consistency_slab"."""
+        ``consistency=(meas_up, cell)`` / ``consistency_weight`` and the five keywords that ride on it (``consistency_profile``,
+        ``consistency_noise``, ``consistency_operator``, ``consistency_row_noise``, ``consistency_slab``): ``one_unet_sample``'s, for
+        every sampled U-Net (so they must generate one size).  ``meas_up`` [B,C,P,P,P] (with an operator t = A+ y) is in the units
+        this returns -- ``normalize_img`` takes it to state space, as it does ``inpaint_images`` -- and the noise deviations are in
+        its units as passed here: they are multiplied by the slope of ``normalize_img``.  ``consistency.py`` states the keywords and
+        their refusals: ``ValueError`` naming the keyword at fault and the one that rides on it, raised here for every sampled
+        U-Net before anything touches the device."""
         assert texts is None and text_embeds is None and not return_pil_images
         samplers, steps_per_unet, etas = (cast_tuple(v, len(self.unets)) for v in (sampler, sample_steps, eta))
         for args in zip(samplers, steps_per_unet, cast_tuple(skip_steps, len(self.unets)), etas):
@@ -708,38 +636,16 @@ class ElucidatedImagen(nn.Module):
         sampled_samplers = samplers[start_at_unet_number - 1:default(stop_at_unet_number, len(self.unets))]
         has_inpainting = any([self._check_inpaint_args(s, inpaint_images, inpaint_masks, inpaint_resample_times)
                               for s in sampled_samplers or samplers[-1:]])
-        check_consistency_slab('sample', consistency_slab, exists(consistency), consistency_profile, consistency_noise,
-                               consistency_operator, consistency_row_noise)
-        check_consistency_row_noise('sample', consistency_row_noise, consistency_operator, consistency_profile, consistency_noise)
-        with naming_consistency_row_noise(consistency_row_noise):
-            check_consistency_operator('sample', consistency_operator, exists(consistency), consistency_profile, consistency_noise)
-        if exists(consistency_noise) and not exists(consistency):
-            ops.consistency_noise_sigma('sample', consistency_noise, False)
-        if exists(consistency_profile) and not exists(consistency):
-            check_consistency('sample', None, consistency_weight, None, profile=consistency_profile)
-        if exists(consistency):
-            span = range(start_at_unet_number, default(stop_at_unet_number, len(self.unets)) + 1)
-            frames = calc_all_frame_dims(self.temporal_downsample_factor, video_frames)
-            for n in span:
-                with naming_consistency_row_noise(consistency_row_noise), naming_consistency_noise(consistency_noise):
-                    check_consistency('sample', consistency, consistency_weight,
-                                      (batch_size, self.channels, *frames[n - 1], self.image_sizes[n - 1], self.image_sizes[n - 1]),
-                                      exists(inpaint_images), cast_tuple(init_images, len(self.unets))[n - 1],
-                                      cast_tuple(skip_steps, len(self.unets))[n - 1], samplers[n - 1], profile=consistency_profile,
-                                      operator=consistency_operator, slab=consistency_slab)
-                if exists(consistency_noise):
-                    ops.consistency_noise_sigma('sample', consistency_noise, True, etas[n - 1] != 0)
-                if exists(consistency_row_noise):
-                    check_consistency_row_noise('sample', consistency_row_noise, consistency_operator, stochastic=etas[n - 1] != 0)
-                    ops.tile_noise_plan('sample', ops.tile_noise_operator(consistency[1], consistency_operator,
-                                                                          consistency_row_noise).cell, 0, self.image_sizes[n - 1])
-            if exists(consistency_noise):                                          # into state space with the measurement: the map's slope
-                unit = self.normalize_img(torch.tensor([0., 1.], dtype=torch.float64))
-                consistency_noise = float(consistency_noise) * abs(float(unit[1] - unit[0]))
-            if exists(consistency_row_noise):                                      # the same change of units
-                unit = self.normalize_img(torch.tensor([0., 1.], dtype=torch.float64))
-                consistency_row_noise = scale_consistency_row_noise(consistency_row_noise, float(unit[1] - unit[0]))
-            consistency = (self.normalize_img(consistency[0]), consistency[1])
+        frames, plan = calc_all_frame_dims(self.temporal_downsample_factor, video_frames) if exists(consistency) else None, None
+        for n in range(start_at_unet_number, default(stop_at_unet_number, len(self.unets)) + 1):      # every sampled U-Net's rules, up front
+            plan = consistency_plan(
+                'sample', ops, consistency, consistency_weight, consistency_profile, consistency_noise, consistency_operator,
+                consistency_row_noise, consistency_slab, stochastic=etas[n - 1] != 0, has_inpainting=exists(inpaint_images),
+                shape=exists(frames) and (batch_size, self.channels, *frames[n - 1], self.image_sizes[n - 1], self.image_sizes[n - 1]),
+                init_images=cast_tuple(init_images, len(self.unets))[n - 1], skip_steps=cast_tuple(skip_steps, len(self.unets))[n - 1],
+                sampler=samplers[n - 1])
+        # what ``one_unet_sample`` takes: the measurement in state space, the deviations with it by the map's slope
+        consistent = plan.keywords(self.normalize_img(plan.measurement), slope=state_slope(self.normalize_img)) if exists(plan) else {}
         if has_inpainting:
             if batch_size == 1:                                                    # broadcast along the inpainted images (:580-583)
                 batch_size = inpaint_images.shape[0]
@@ -783,18 +689,7 @@ class ElucidatedImagen(nn.Module):
                 unet_init = self._resize(unet_init, image_size, frame_dims[0])
             shape = (batch_size, self.channels, *frame_dims, image_size, image_size)
             multistep = dict(sampler=unet_sampler, sample_steps=unet_steps, eta=unet_eta) if unet_sampler == 'dpmpp2m' else {}
-            if exists(consistency):
-                multistep.update(consistency=consistency, consistency_weight=consistency_weight)
-                if exists(consistency_profile):
-                    multistep.update(consistency_profile=consistency_profile)
-                if exists(consistency_noise):
-                    multistep.update(consistency_noise=consistency_noise)
-                if exists(consistency_operator):
-                    multistep.update(consistency_operator=consistency_operator)
-                if exists(consistency_row_noise):
-                    multistep.update(consistency_row_noise=consistency_row_noise)
-                if exists(consistency_slab):
-                    multistep.update(consistency_slab=consistency_slab)
+            multistep.update(consistent)
             inpaint = {}
             if has_inpainting:
                 inpaint = dict(inpaint_images=inpaint_images, inpaint_masks=inpaint_masks, inpaint_resample_times=inpaint_resample_times)

@@ -22,6 +22,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import ops
+from .consistency import plan as consistency_plan
 from .ops import ACT_MISH, ACT_GELU
 
 # ----------------------------------------------------------------------------------------------
@@ -1159,170 +1160,6 @@ class SRUnet256(Unet):
         super().__init__(*args, **{**default_kwargs, **kwargs})
 
 
-def check_consistency_operator(who, operator, has_consistency, profile=None, noise=None):
-    """The host rules of ``consistency_operator=`` beside its neighbours (``ValueError`` naming "consistency_operator"; nothing
-    touches the device): it rides on ``consistency``, whose first member then carries t = A+ y, and goes with neither
-    ``consistency_profile`` nor ``consistency_noise``."""
-    if operator is None:
-        return
-    if not has_consistency:
-        raise ValueError(f"{who}: consistency_operator needs consistency=(measurement, cell)")
-    if profile is not None:
-        raise ValueError(f"{who}: consistency_operator and consistency_profile are not offered together: a profile is the single row "
-                         f"u of a measurement; give the operator all its rows")
-    if noise is not None:
-        raise ValueError(f"{who}: consistency_operator and consistency_noise are not offered together (DDNM+ for a general A needs a "
-                         f"weight per singular direction: that is consistency_row_noise)")
-
-
-def check_consistency_slab(who, slab, has_consistency, profile=None, noise=None, operator=None, row_noise=None):
-    """The host rules of ``consistency_slab=`` beside its neighbours (``ValueError`` naming "consistency_slab"; nothing touches the
-    device): it rides on ``consistency`` and goes with none of ``consistency_profile`` (the profile cut at the cell border),
-    ``consistency_noise``, ``consistency_operator`` and ``consistency_row_noise`` (noise-aware weights are not offered for it)."""
-    if slab is None:
-        return
-    if not has_consistency:
-        raise ValueError(f"{who}: consistency_slab needs consistency=(meas_up, cell)")
-    for other, name in ((profile, 'consistency_profile'), (noise, 'consistency_noise'), (operator, 'consistency_operator'),
-                        (row_noise, 'consistency_row_noise')):
-        if other is not None:
-            raise ValueError(f"{who}: consistency_slab and {name} are not offered together")
-
-
-class naming_consistency_slab:
-    """``naming_consistency_noise`` for ``consistency_slab``, which rides on ``consistency``: what that refuses keeps its wording and
-    also names "consistency_slab"."""
-
-    def __init__(self, slab):
-        self.slab = slab
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, kind, err, tb):
-        if kind is ValueError and self.slab is not None and 'consistency_slab' not in str(err):
-            raise ValueError(f"{err} (consistency_slab rides on consistency)") from None
-        return False
-
-
-def check_consistency(who, consistency, weight, shape, has_inpainting=False, init_images=None, skip_steps=None, sampler=None,
-                      profile=None, operator=None, slab=None):
-    """The argument rules of ``consistency=(meas_up, cell)`` / ``consistency_weight`` of the one-call samplers of both families
-    (``ValueError`` naming "consistency"; nothing touches the device).  ``shape`` = the [B,C,P,P,P] the sampler generates: ``meas_up``
-    must be a float tensor of exactly that shape, the cell must divide P.  Data consistency (DDNM) replaces the cell means of every x0
-    prediction by the measurement's; inpainting pastes known values into the state, ``init_images`` / ``skip_steps`` start or thin the
-    chain elsewhere and the EDM Heun sampler has two predictions per step: none of them is offered with it.  ``profile`` =
-    (pz, py, px), the slice profile of ``consistency_profile`` (``ops.cell_profile``'s rules; it needs ``consistency``).  Returns None
-    (off) or ``(meas_up, cell, weight, table)``, ``table`` None without a profile, else ``ops.cell_profile``'s host table.
-    ``operator`` = the ``consistency_operator`` (an [m, n] matrix or ``ops.tile_operator``'s object; with neither a profile nor
-    ``consistency_noise``, ``check_consistency_operator``): ``meas_up`` then carries t = A+ y and ``table`` is the operator's fp32
-    [n, n] projector, which ``ops.tile_project`` takes.  ``slab`` = (pz, py, px), the overlapping slice profiles of
-    ``consistency_slab`` (``ops.slab_profile``'s rules; with none of the others, ``check_consistency_slab``): ``table`` is then the
-    ``ops.SlabTable`` for cubes of edge P, which ``ops.slab_project`` takes; every refusal then names "consistency_slab"."""
-    check_consistency_slab(who, slab, consistency is not None, profile, None, operator)
-    with naming_consistency_slab(slab):
-        return _check_consistency(who, consistency, weight, shape, has_inpainting, init_images, skip_steps, sampler, profile, operator, slab)
-
-
-def _check_consistency(who, consistency, weight, shape, has_inpainting, init_images, skip_steps, sampler, profile, operator, slab):
-    check_consistency_operator(who, operator, consistency is not None, profile)
-    if consistency is None:
-        if profile is not None:
-            raise ValueError(f"{who}: consistency_profile needs consistency=(meas_up, cell)")
-        return None
-    if not isinstance(consistency, (tuple, list)) or len(consistency) != 2:
-        raise ValueError(f"{who}: consistency must be (meas_up, cell), got {type(consistency).__name__}")
-    if sampler == 'heun':
-        raise ValueError(f"{who}: consistency is not offered with the Heun sampler (two predictions per step): use sampler='dpmpp2m'")
-    if has_inpainting:
-        raise ValueError(f"{who}: consistency and inpainting are not offered together")
-    if exists(init_images) or exists(skip_steps):
-        raise ValueError(f"{who}: consistency takes neither init_images nor skip_steps")
-    meas_up, cell = consistency
-    cell, weight = ops.consistency_cell(who, cell, weight, [(shape[2 + a], a) for a in range(3)])
-    if not torch.is_tensor(meas_up) or not meas_up.is_floating_point() or tuple(meas_up.shape) != tuple(shape):
-        got = f"{meas_up.dtype} {tuple(meas_up.shape)}" if torch.is_tensor(meas_up) else type(meas_up).__name__
-        raise ValueError(f"{who}: the consistency measurement must be a float tensor of the sampled shape {tuple(shape)} (replicated "
-                         f"onto the high-res grid, ops.cell_replicate), got {got}")
-    if operator is not None:
-        return meas_up, cell, weight, ops.tile_operator(cell, operator).table
-    if slab is not None:
-        ops.slab_plan(who, cell, shape[2])
-        return meas_up, cell, weight, ops.slab_profile(cell, slab, jmax=shape[2] // cell[0])
-    return meas_up, cell, weight, None if profile is None else ops.cell_profile(cell, profile)
-
-
-class naming_consistency_noise:
-    """``with naming_consistency_noise(sigma):`` around the ``consistency`` checks: a refusal raised inside while
-    ``consistency_noise`` is given also names "consistency_noise", which rides on ``consistency`` and inherits its refusals."""
-
-    def __init__(self, sigma):
-        self.sigma = sigma
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, kind, err, tb):
-        if kind is ValueError and self.sigma is not None and 'consistency_noise' not in str(err):
-            raise ValueError(f"{err} (consistency_noise={self.sigma!r} rides on consistency)") from None
-        return False
-
-
-class naming_consistency_row_noise:
-    """``naming_consistency_noise`` for ``consistency_row_noise``, which rides on ``consistency_operator`` and so on ``consistency``:
-    what those refuse keeps its wording and also names "consistency_row_noise"."""
-
-    def __init__(self, row_noise):
-        self.row_noise = row_noise
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, kind, err, tb):
-        if kind is ValueError and self.row_noise is not None and 'consistency_row_noise' not in str(err):
-            raise ValueError(f"{err} (consistency_row_noise={self.row_noise!r} rides on consistency_operator)") from None
-        return False
-
-
-def check_consistency_row_noise(who, row_noise, operator, profile=None, noise=None, stochastic=True):
-    """The host rules of ``consistency_row_noise=`` beside its neighbours (``ValueError`` naming "consistency_row_noise"; nothing
-    touches the device): it rides on ``consistency_operator``, goes with neither ``consistency_noise`` (the one-number model of the
-    cell mean) nor ``consistency_profile``, and needs a chain with a stochastic row, as ``consistency_noise`` does.  Its values are
-    checked by ``ops.tile_noise_operator``."""
-    if row_noise is None:
-        return
-    if operator is None:
-        raise ValueError(f"{who}: consistency_row_noise needs consistency_operator=A (and consistency=(target_up, cell)): it is the "
-                         f"noise of each row of A; the noise of a plain cell mean is consistency_noise")
-    if noise is not None or profile is not None:
-        raise ValueError(f"{who}: consistency_row_noise is not offered together with consistency_noise or consistency_profile: give "
-                         f"the operator all its rows and every row its deviation")
-    if not stochastic:
-        raise ValueError(f"{who}: consistency_row_noise needs a sampler with fresh noise per step (ddpm, ddim or dpmpp2m with eta > 0): "
-                         f"a deterministic chain would never project; use a constant consistency_weight < 1 there")
-
-
-def scale_consistency_row_noise(row_noise, slope, std=1.):
-    """``consistency_row_noise`` (one number or a sequence, already checked) divided by ``std`` and multiplied by |``slope``|, the
-    change of units that the measurement itself takes -- in this order, which is ``consistency_noise``'s."""
-    if torch.is_tensor(row_noise) or type(row_noise).__module__ == 'numpy':
-        row_noise = row_noise.tolist()
-    if isinstance(row_noise, (tuple, list)):
-        return [float(v) / float(std) * abs(float(slope)) for v in row_noise]
-    return float(row_noise) / float(std) * abs(float(slope))
-
-
-def consistency_row_noise_chain(who, row_noise, operator, cell, weight, rows, edge, device):
-    """What a per-window chain needs of ``consistency_row_noise``, made once per chain on the host: ``(op, tables, kinds)`` --
-    ``ops.tile_noise_operator``, then ``ops.tile_noise_tables`` of ``ops.tile_noise_schedule`` over ``rows`` [T, 4] =
-    (kx, k0, kp, kn) with sigma_min in the units of ``target_up``, the tables uploaded as ONE [T, 2, n, n] tensor.  ``edge`` is the
-    cubes' edge (the LDS plan is checked before anything touches the device)."""
-    op = ops.tile_noise_operator(cell, operator, row_noise)
-    ops.tile_noise_plan(who, op.cell, 0, edge)
-    tables, kinds = ops.tile_noise_tables(op, ops.tile_noise_schedule(op, rows, float(op.row_noise.min()), weight))
-    return op, tables.to(device), kinds
-
-
 # ----------------------------------------------------------------------------------------------
 # Imagen: continuous-time DDPM wrapper (imagen_pytorch3D.py:1741-2442)
 # ----------------------------------------------------------------------------------------------
@@ -1677,72 +1514,25 @@ class Imagen(nn.Module):
         draws once more for the re-noise ``q_sample_from_to(img, t_next, t)``; that re-noise and the paste of the next pass are ONE
         ``ops.ddpm_inpaint_paste`` launch.  ``inpaint_draws`` counts the draws.
 
-        ``consistency=(meas_up, cell)`` with ``consistency_weight`` (any sampler; ``check_consistency``): data-consistent sampling for a
-        block-average measurement (DDNM).  ``meas_up`` [B,C,P,P,P] is the measurement replicated onto the high-res grid
-        (``ops.cell_replicate``), in state space like ``inpaint_images``.  Per step the x0 prediction (thresholded, if configured) goes
-        through ``ops.cell_project`` with the chain's clamp -- the cell means of the clamped prediction are moved onto the measurement's
-        -- and ``ops.ddpm_step`` then runs with the clamp switched off (an infinite box is the identity bit for bit): clamping after the
-        projection would undo it.  The x0 the step returns, which self-conditioning and ``'dpmpp2m'`` read, is the projected one.
-
-        ``consistency_profile=(pz, py, px)`` (with ``consistency``; ``ops.cell_profile``): the measurement of a cell is the weighted
-        mean u . x of its voxels, u the normalised product of the three per-axis weights -- a slice profile, with zeros for a gap
-        between slices (``ops.cell_measure`` is that operator).  Every ``ops.cell_project`` of the chain is then one
-        ``ops.cell_project_profile``: the weighted means are moved onto the measurement, a gap voxel is never moved.  A uniform profile
-        given here takes this path too (equal to no profile up to rounding, not bit for bit).
-
-        ``consistency_noise=sigma`` (with ``consistency``; DDNM+): the standard deviation of the measurement's noise, in the units of
-        ``meas_up``.  ``ops.consistency_noise_schedule`` makes (w_i, shrink_i) once per chain from the host table, rows
-        (kx, k0, 0, kn), with ``consistency_weight`` as the cap.  Per step, on the fp32 values: w_i = 0 (kn = 0: the last step) is the
-        plain ``ops.ddpm_step`` with the chain's own clamp and no projection; shrink_i = 0 the projection above with w_i; otherwise ONE
-        ``ops.cell_project_noise`` replaces the projection launch -- it also reduces the step's normals in the range of A (into a new
-        tensor: an injected noise tensor is never modified).  The draws are those of the chain without it.  ``ValueError`` naming
-        "consistency_noise": without ``consistency``, not a finite number > 0, or a chain with no stochastic step (``'ddim'`` with
-        eta = 0, ``'dpmpp2m'``) -- use a constant ``consistency_weight`` there.
-
-        ``consistency_operator=A`` (with ``consistency``; ``ops.tile_operator``): every tile of ``cell`` voxels is measured by the
-        m x n matrix A -- orthogonal thick-slice stacks (``ops.stack_operator``), a block-DCT low-pass, any rank.
-        ``consistency=(target_up, cell)`` then carries t = A+ y on the high-res grid (``ops.tile_backproject``) where it carried
-        ``meas_up``, and every ``ops.cell_project`` of the chain is one ``ops.tile_project``, x0' = x0 + w (t - P x0) with P = A+ A.
-        ``ValueError`` naming "consistency_operator": without ``consistency``, together with ``consistency_profile`` or
-        ``consistency_noise``, or an operator ``ops.tile_operator`` refuses.
-
-        ``consistency_row_noise=sigma`` (with ``consistency`` and ``consistency_operator``; DDNM+ per singular direction): the
-        standard deviation of the noise of each row of A, one number or m of them, in the units of ``target_up``; the caller makes
-        t with ``ops.tile_noise_operator``'s effective pseudo-inverse.  ``ops.tile_noise_schedule`` / ``ops.tile_noise_tables``
-        make the per-step tables (M_i, G_i) once per chain (uploaded as one tensor) and the dispatch: every lambda 0 (kn = 0: the
-        last step) is the plain ``ops.ddpm_step``, one common weight w and no shrink the ``ops.tile_project`` above with w,
-        otherwise ONE ``ops.tile_project_noise`` replaces the projection launch and also shapes the step's normals (into a new
-        tensor).  The draws are unchanged.  ``ValueError`` naming "consistency_row_noise": without ``consistency_operator``,
-        together with ``consistency_noise`` or ``consistency_profile``, values ``ops.tile_noise_operator`` refuses, a chain with
-        no stochastic step (use a constant ``consistency_weight``), a cell whose launch plans more than 64 KiB of LDS, and
-        everything ``consistency`` / ``consistency_operator`` refuse.
-
-        ``consistency_slab=(pz, py, px)`` (with ``consistency``; ``ops.slab_profile``): slice profiles that OVERLAP between
-        neighbouring cells along z -- ``pz`` has fz + 2r entries, reach 1 <= r <= fz / 2, ``py`` / ``px`` are the in-plane profile
-        inside the cell (``ops.slab_measure`` is that operator; ``meas_up`` is its output replicated).  Every ``ops.cell_project`` of
-        the chain is then one ``ops.slab_project``: DDNM on the slices whose whole support lies inside the cube, by one tridiagonal
-        solve per column; the first and the last slice of the cube are never enforced.  ``ValueError`` naming "consistency_slab":
-        without ``consistency``, together with ``consistency_profile``, ``consistency_noise``, ``consistency_operator`` or
-        ``consistency_row_noise``, a profile ``ops.slab_profile`` refuses (a bad reach, the condition rule), and everything
-        ``consistency`` refuses."""
+        ``consistency=(meas_up, cell)`` with ``consistency_weight`` (any sampler), ``consistency_profile``, ``consistency_noise``,
+        ``consistency_operator``, ``consistency_row_noise``, ``consistency_slab``: data-consistent sampling (DDNM / DDNM+); the keywords,
+        their rules and the launch a step takes are stated once, in ``consistency.py``.  ``meas_up`` [B,C,P,P,P] is the measurement
+        replicated onto the high-res grid (``ops.cell_replicate``; with an operator t = A+ y, ``ops.tile_backproject``), in state space
+        like ``inpaint_images``, and the noise deviations are in its units.  Per step the x0 prediction (thresholded, if configured)
+        goes through the mode's projection with the chain's clamp -- the clamped prediction is moved onto the measurement -- and
+        ``ops.ddpm_step`` then runs with the clamp switched off (an infinite box is the identity bit for bit): clamping after the
+        projection would undo it.  The x0 the step returns, which self-conditioning and ``'dpmpp2m'`` read, is the projected one.  A
+        noise-aware step also reduces its normals, into a new tensor (an injected noise tensor is never modified); its last step
+        (kn = 0) is the plain ``ops.ddpm_step`` with the chain's own clamp.  The draws are those of the chain without it.  A uniform
+        profile given explicitly takes the profile's launch (equal to no profile up to rounding, not bit for bit)."""
         if pred_objective not in ('noise', 'x_start', 'v'):
             raise ValueError(f'unknown objective {pred_objective}')
         has_inpainting = exists(inpaint_images) and exists(inpaint_masks)                  # (:2090-2091)
         self._check_sampler_args(sampler, sample_steps, skip_steps, eta, has_inpainting)
-        check_consistency_slab('p_sample_loop', consistency_slab, exists(consistency), consistency_profile, consistency_noise,
-                               consistency_operator, consistency_row_noise)
-        check_consistency_row_noise('p_sample_loop', consistency_row_noise, consistency_operator, consistency_profile, consistency_noise,
-                                    not (sampler == 'dpmpp2m' or (sampler == 'ddim' and eta == 0)))
-        with naming_consistency_row_noise(consistency_row_noise):
-            check_consistency_operator('p_sample_loop', consistency_operator, exists(consistency), consistency_profile,
-                                       consistency_noise)
-            with naming_consistency_noise(consistency_noise):
-                consistency = check_consistency('p_sample_loop', consistency, consistency_weight, shape, has_inpainting, init_images,
-                                                skip_steps, profile=consistency_profile, operator=consistency_operator,
-                                                slab=consistency_slab)
-        if exists(consistency_noise):
-            consistency_noise = ops.consistency_noise_sigma('p_sample_loop', consistency_noise, exists(consistency),
-                                                            not (sampler == 'dpmpp2m' or (sampler == 'ddim' and eta == 0)))
+        plan = consistency_plan('p_sample_loop', ops, consistency, consistency_weight, consistency_profile, consistency_noise,
+                                consistency_operator, consistency_row_noise, consistency_slab, shape=shape,
+                                stochastic=not (sampler == 'dpmpp2m' or (sampler == 'ddim' and eta == 0)), has_inpainting=has_inpainting,
+                                init_images=init_images, skip_steps=skip_steps)
         device = self.device
         batch = shape[0]
         if callable(noise):
@@ -1762,19 +1552,10 @@ class Imagen(nn.Module):
 
         coefs, conds, x0c, last, renoise, qs = self._sampler_tables(noise_scheduler, batch, sampler, sample_steps, skip_steps, eta,
                                                                     pred_objective)
-        schedule = None
-        if exists(consistency_noise):                                       # once per chain, from the host table; rows are batch-uniform
+        chain = None
+        if exists(plan):                                                    # once per chain, from the host table; rows are batch-uniform
             assert bool((coefs == coefs[:, :, :1]).all())
-            rows = [(float(r[0]), float(r[1]), 0., float(r[2])) for r in coefs[:, :, 0].double()]
-            schedule = ops.consistency_noise_dispatch(ops.consistency_noise_schedule(
-                rows, ops.cell_norm(consistency[1], consistency[3]), consistency_noise, consistency[2]))
-        kinds = None
-        if exists(consistency_row_noise):                                   # once per chain too: the tables of every step, one upload
-            assert bool((coefs == coefs[:, :, :1]).all())
-            rows = [(float(r[0]), float(r[1]), 0., float(r[2])) for r in coefs[:, :, 0].double()]
-            row_op, tables, kinds = consistency_row_noise_chain('p_sample_loop', consistency_row_noise, consistency_operator,
-                                                                consistency[1], consistency[2], rows, shape[2], device)
-            consistency = (*consistency[:3], row_op.table)                  # P of the whitened operator, for a constant-weight step
+            chain = plan.prepare(coefs[:, :, 0].double(), device)
         multistep = sampler == 'dpmpp2m'
         if multistep or (sampler == 'ddim' and eta == 0):                   # kn == 0: the step kernel reads one zero tensor, no draw
             zero = torch.zeros(shape, device=device)
@@ -1787,10 +1568,6 @@ class Imagen(nn.Module):
         inf = float('inf')
         if dynamic_threshold:                                               # the prediction arrives thresholded: no clamp in the step
             lo, hi, mode = -inf, inf, 1
-        if exists(consistency):
-            meas_up, cell, weight, table = consistency
-            meas_up = meas_up.to(device).float().contiguous()
-            table = table.to(device) if exists(table) else None                # once per chain
 
         noisy_dev, x0_dev = [], []
         x_start = None
@@ -1808,28 +1585,10 @@ class Imagen(nn.Module):
                 pred = self._x0_prediction(unet, img, conds[i], x0c[i], lowres, x_start if unet.self_cond else None, cond_images,
                                            cond_scale, pred_objective, dynamic_threshold)
                 third = x_start if multistep and i > 0 else step_noise()      # 'dpmpp2m': the previous step's clamped x0
-                if exists(schedule):                                          # consistency_noise: this step's own weight and shrink
-                    weight, shrink = schedule[i]
-                if exists(kinds):                                             # consistency_row_noise: plain, constant weight or tables
-                    kind, weight = kinds[i]
-                if exists(kinds) and kind == 'noise':                         # one launch: both tables of this step
-                    pred, third = ops.tile_project_noise(pred, meas_up, third, cell, tables[i], clamp=(lo, hi, mode))
-                    img, x_start = ops.ddpm_step(img, pred, third, coefs[i, 0], coefs[i, 1], coefs[i, 2], -inf, inf, 1)
-                elif exists(schedule) and weight > 0 and shrink > 0:          # one launch: the projection and the shaped normals
-                    pred, third = ops.cell_project_noise(pred, meas_up, third, cell, weight, shrink, table, clamp=(lo, hi, mode))
-                    img, x_start = ops.ddpm_step(img, pred, third, coefs[i, 0], coefs[i, 1], coefs[i, 2], -inf, inf, 1)
-                elif exists(consistency) and weight > 0:                      # the clamp, then the projection; the step clamps no more
-                    if exists(consistency_operator):
-                        pred = ops.tile_project(pred, meas_up, cell, table, weight, clamp=(lo, hi, mode))
-                    elif exists(consistency_slab):
-                        pred = ops.slab_project(pred, meas_up, cell, table, weight, clamp=(lo, hi, mode))
-                    elif exists(table):
-                        pred = ops.cell_project_profile(pred, meas_up, cell, table, weight, clamp=(lo, hi, mode))
-                    else:
-                        pred = ops.cell_project(pred, meas_up, cell, weight, clamp=(lo, hi, mode))
-                    img, x_start = ops.ddpm_step(img, pred, third, coefs[i, 0], coefs[i, 1], coefs[i, 2], -inf, inf, 1)
-                else:
-                    img, x_start = ops.ddpm_step(img, pred, third, coefs[i, 0], coefs[i, 1], coefs[i, 2], lo, hi, mode)
+                clamp = (lo, hi, mode)
+                if exists(chain):                                             # the clamp, then the projection; the step clamps no more
+                    pred, third, clamp = chain.project(i, pred, lambda: third, clamp)
+                img, x_start = ops.ddpm_step(img, pred, third, coefs[i, 0], coefs[i, 1], coefs[i, 2], *clamp)
                 if has_inpainting and not (r == 0 or all_last):                            # (:2139-2146): applied by the next paste
                     renoise_n = draw()
             noisy_dev.append(img)
@@ -1853,17 +1612,11 @@ class Imagen(nn.Module):
         """imagen_pytorch3D.py:2165-2274 -> (img, [noisy per step], [x0 per step]).  Accepts both spellings
         ``return_all_outputs`` / ``return_all_unet_outputs`` (test.py:182 uses the latter).  ``sampler`` / ``sample_steps`` / ``eta``
         (one value, or one per U-Net like ``skip_steps``) and the list or callable ``noise``: see ``p_sample_loop``, as for
-        ``consistency=(meas_up, cell)`` / ``consistency_weight``, which every sampled U-Net gets (so they must generate one size).  Its
-        refusals are ``ValueError`` naming "consistency", raised before anything touches the device: together with inpainting,
-        ``init_images`` or ``skip_steps``, a weight outside (0, 1], a cell that does not divide the image size or with
-        n outside 2 .. 64, a ``meas_up`` that is not [B,C,P,P,P]; also a ``consistency_profile`` (``p_sample_loop``) without
-        ``consistency`` or one ``ops.cell_profile`` refuses.  ``consistency_noise=sigma`` (``p_sample_loop``; the units of ``meas_up``
-        as passed): every refusal above then also names "consistency_noise", as do its own.  ``consistency_operator=A``
-        (``p_sample_loop``): a tile-local linear measurement; ``consistency`` then carries t = A+ y, and its refusals name
-        "consistency_operator".  ``consistency_row_noise=sigma`` (``p_sample_loop``; with ``consistency_operator``, the units of
-        ``target_up`` as passed): the noise of each row of A; every refusal above then also names "consistency_row_noise", as do
-        its own.  ``consistency_slab=(pz, py, px)`` (``p_sample_loop``): slice profiles that overlap between neighbouring cells;
-        its refusals, and those of ``consistency`` when it is given, name "consistency_slab"."""
+        ``consistency=(meas_up, cell)`` / ``consistency_weight`` and the five keywords that ride on it (``consistency_profile``,
+        ``consistency_noise``, ``consistency_operator``, ``consistency_row_noise``, ``consistency_slab``; the deviations in the units
+        of ``meas_up`` as passed), which every sampled U-Net gets (so they must generate one size).  ``consistency.py`` states them and
+        their refusals: ``ValueError`` naming the keyword at fault and the one that rides on it, raised here for every sampled U-Net
+        before anything touches the device."""
         if exists(return_all_unet_outputs):
             return_all_outputs = return_all_unet_outputs
         num_unets = len(self.unets)
@@ -1871,29 +1624,12 @@ class Imagen(nn.Module):
         sampler, sample_steps, eta = (cast_tuple(v, num_unets) for v in (sampler, sample_steps, eta))
         for args in zip(sampler, sample_steps, skip_steps, eta):
             self._check_sampler_args(*args, exists(inpaint_images) and exists(inpaint_masks))
-        check_consistency_slab('sample', consistency_slab, exists(consistency), consistency_profile, consistency_noise,
-                               consistency_operator, consistency_row_noise)
-        check_consistency_row_noise('sample', consistency_row_noise, consistency_operator, consistency_profile, consistency_noise)
-        with naming_consistency_row_noise(consistency_row_noise):
-            check_consistency_operator('sample', consistency_operator, exists(consistency), consistency_profile, consistency_noise)
-        if exists(consistency_noise) and not exists(consistency):
-            ops.consistency_noise_sigma('sample', consistency_noise, False)
-        if exists(consistency_profile) and not exists(consistency):
-            check_consistency('sample', None, consistency_weight, None, profile=consistency_profile)
-        for n in range(start_at_unet_number, default(stop_at_unet_number, num_unets) + 1) if exists(consistency) else ():
-            with naming_consistency_row_noise(consistency_row_noise), naming_consistency_noise(consistency_noise):
-                check_consistency('sample', consistency, consistency_weight, (batch_size, self.channels) + (self.image_sizes[n - 1],) * 3,
-                                  exists(inpaint_images) and exists(inpaint_masks), cast_tuple(init_images, num_unets)[n - 1],
-                                  skip_steps[n - 1], profile=consistency_profile, operator=consistency_operator,
-                                  slab=consistency_slab)
-            if exists(consistency_noise):
-                ops.consistency_noise_sigma('sample', consistency_noise, True,
-                                            not (sampler[n - 1] == 'dpmpp2m' or (sampler[n - 1] == 'ddim' and eta[n - 1] == 0)))
-            if exists(consistency_row_noise):
-                check_consistency_row_noise('sample', consistency_row_noise, consistency_operator, stochastic=not (
-                    sampler[n - 1] == 'dpmpp2m' or (sampler[n - 1] == 'ddim' and eta[n - 1] == 0)))
-                ops.tile_noise_plan('sample', ops.tile_noise_operator(consistency[1], consistency_operator, consistency_row_noise).cell,
-                                    0, self.image_sizes[n - 1])
+        for n in range(start_at_unet_number, default(stop_at_unet_number, num_unets) + 1):      # every sampled U-Net's rules, up front
+            consistency_plan('sample', ops, consistency, consistency_weight, consistency_profile, consistency_noise, consistency_operator,
+                             consistency_row_noise, consistency_slab, shape=(batch_size, self.channels) + (self.image_sizes[n - 1],) * 3,
+                             stochastic=not (sampler[n - 1] == 'dpmpp2m' or (sampler[n - 1] == 'ddim' and eta[n - 1] == 0)),
+                             has_inpainting=exists(inpaint_images) and exists(inpaint_masks),
+                             init_images=cast_tuple(init_images, num_unets)[n - 1], skip_steps=skip_steps[n - 1])
         device = default(device, self.device)
         self.reset_unets_all_one_device(device=device)
         cond_scale = cast_tuple(cond_scale, num_unets)

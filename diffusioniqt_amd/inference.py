@@ -85,7 +85,8 @@ of A, what the network is for -- stays.  ``w = 1`` is DDNM, ``w < 1`` its relaxa
 replicated onto the high-res grid once (``ops.cell_replicate``) and z-scored like the low-res volume.  In the crop and blend modes every
 sampler call gets its windows of that volume as ``consistency=(windows, cell)`` and projects on its own (``ops.cell_project``), so the
 stride and the window must be multiples of the cell: no cell may straddle a window.  With ``joint=True`` the projection is part of the
-fused launch (``ops.volume_joint_consistent_step`` in place of the three linear steps, as many launches as before), on the fused x0 of
+fused launch (the consistent step of ``ops`` that ``consistency.Chain.joint_step`` picks, in place of the three linear steps, as many
+launches as before), on the fused x0 of
 the one state: it is defined for every cell of the volume whose voxels are all covered, windows that share a cell are corrected by the
 same amount, and only the volume has to be a multiple of the cell.  What is exactly consistent (w = 1, to fp32 rounding) is the last
 corrected prediction.  The sigma-space chain ends at sigma = 0 with (kx, k0) = (0, 1): the state it ends in IS that prediction.  The
@@ -103,8 +104,8 @@ The cells stay disjoint, so A+ = A^T / |u|^2 and the projection is x0' = x0 + w 
 moved, and exact consistency at w = 1 means u . x0' = y (to fp32 rounding).  Since sum u = 1, A commutes with the z-score and
 ``state_space``, so the replicated measurement, its window gathers, the covered-cell rule (ALL n voxels, whatever their weights) and
 the divisibility rules are those above.  The crop and blend modes hand ``consistency_profile=`` on to the sampler
-(``ops.cell_project_profile`` per step); ``joint=True`` launches ``ops.volume_joint_consistent_profile_step`` in the place of
-``ops.volume_joint_consistent_step``, as many launches as before.  A uniform profile given explicitly takes this path too.  Profiles
+(``ops.cell_project_profile`` per step); ``joint=True`` launches the profile's consistent step in the place of the plain
+mean's, as many launches as before.  A uniform profile given explicitly takes this path too.  Profiles
 that overlap between neighbouring cells (slice cross-talk) are ``consistency_slab``, below.
 
 A noisy measurement (``consistency_noise=sigma``, with ``consistency``; DDNM+, Wang et al. 2023, 3.3): sigma is the standard deviation
@@ -117,7 +118,7 @@ inside the state is not tracked.  A step with kn = 0 -- the last of every chain 
 volume is no longer exactly consistent with the (noisy) measurement, by design.  Units: sigma / std is the z-scored value the crop and
 blend modes hand on as ``consistency_noise=``; ``joint=True`` multiplies it by the slope of the denoiser's affine ``state_space`` map,
 state_space(1) - state_space(0), and dispatches per step: weight 0 the family's plain launch, shrink 0 the consistent launch,
-otherwise ``ops.volume_joint_consistent_noise_step`` -- one launch per step as before, the same draws.  Deterministic chains (ddim with
+otherwise the consistent step that also shapes the normals -- one launch per step as before, the same draws.  Deterministic chains (ddim with
 eta = 0, dpmpp2m without eta) and the Heun sampler are refused; sigma is given, not estimated.
 
 A tile-local linear operator (``consistency_operator=A``, with ``consistency``) is the general case: the volume splits into disjoint
@@ -129,7 +130,7 @@ acquisition.  The projection is x0' = x0 + w (t - P x0) with t = A+ y (``ops.til
 high-res grid where the replicated measurement stood: the constant must lie in the row space of A (P 1 = 1, checked), so t passes
 through the z-score and ``state_space`` as a plain volume, and the window gathers, the covered rule (ALL n voxels of a tile) and the
 divisibility rules are those above.  The crop and blend modes hand windows of t and ``consistency_operator=`` on to the sampler
-(``ops.tile_project`` per step); ``joint=True`` launches ``ops.volume_joint_consistent_tile_step``, as many launches as before.  At
+(``ops.tile_project`` per step); ``joint=True`` launches the tile operator's consistent step, as many launches as before.  At
 w = 1 the corrected prediction satisfies P x0' = t (to fp32 rounding), which is A x0' = y when y lies in the range of A; stacks that
 contradict each other are fitted in the least-squares sense.  Not offered: an operator that crosses tile borders (true k-space
 truncation; overlapping slice profiles are ``consistency_slab``), ``consistency_profile`` or ``consistency_noise`` with an operator, Heun,
@@ -146,7 +147,7 @@ x0' = x0 + M_i (t - x0), eps' = eps - G_i eps with M_i = V diag(lambda_i) V^T an
 those of ``consistency_noise``: sigma / std goes to the sampler calls of the crop and blend modes, ``joint=True`` multiplies by the
 |slope| of ``state_space``.  Per step, on the fp32 values: every lambda 0 is the family's plain launch (the last step: unprojected),
 every shrink 0 with one common lambda the constant-weight tile launch, otherwise ``ops.tile_project_noise`` /
-``ops.volume_joint_consistent_tile_noise_step`` -- as many launches and the same draws as before.  Not offered: correlated row
+the fused joint step that reads the same tables -- as many launches and the same draws as before.  Not offered: correlated row
 noise, sigma estimated from the data, measurement noise tracked across steps, a cell whose launch plans more than 64 KiB of LDS.
 
 Overlapping slice profiles (``consistency_slab=(pz, py, px)``, with ``consistency``): a real slice profile is wider than the slice
@@ -163,7 +164,7 @@ bounds the condition number of any run by 128.  The crop and blend modes hand ``
 (``ops.slab_project`` per step: windows enforce only their inner slices).  ``joint=True`` needs a solve along the whole depth of the
 volume, which does not fit a box-of-cells block: a step is THREE launches where the tile-local operators take one --
 ``ops.volume_joint_slab_coeffs`` (the fused plane values, then the solve per column) and
-``ops.volume_joint_consistent_slab_step`` -- and the windows are walked twice; the workspace and the coefficient volume are
+the slab's consistent step -- and the windows are walked twice; the workspace and the coefficient volume are
 allocated once per volume.  Not offered: a reach beyond half a cell, slabs along other axes (permute the volume instead),
 noise-aware weights (``consistency_noise`` / ``consistency_row_noise``), rows that leave the volume, and any of the other
 consistency keywords together with it.
@@ -174,8 +175,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .imagen_pytorch3D import (check_consistency_operator, check_consistency_row_noise, check_consistency_slab, naming_consistency_noise,
-                               naming_consistency_row_noise, naming_consistency_slab, scale_consistency_row_noise)
+from .consistency import plan as consistency_plan
 from .metrics import MSSIM, PSNR
 from .utils_mine import convertVolume2subVolume, merge_sub_volumes
 
@@ -256,7 +256,8 @@ class _Windows:
     [N,3] (after ``patch_slice``); ``fill`` / ``min_val``, the normalised empty voxel and volume minimum in fp32 arithmetic, as Python
     floats; under a blend mode the device ``slot`` table (a kept window's row, -1: dropped) and ``taps``; ``batches``, the ``(lo, host
     origins, device origins)`` of every sampler call -- ``Eval.batch_size`` windows, or ONE block in block mode (overlapping blocks are
-    written one launch at a time in candidate order: later blocks overwrite, as in the script).  ``_joint`` adds ``x0_vol``."""
+    written one launch at a time in candidate order: later blocks overwrite, as in the script).  ``_joint`` adds ``x0_vol``
+    and ``consistency``, the ``consistency.Chain`` of this volume (or None)."""
 
     def __init__(self, inf, vol, patch_slice=None):
         dev, P = vol.device, inf.patch
@@ -345,56 +346,18 @@ class VolumeInference:
                              "chains and the multistep chains have no re-noising loop")
         return known.float(), mask
 
-    @staticmethod
-    def _check_consistency(consistency, weight, inpaint, joint, sample_fn, rows=False):
-        """The argument rules of ``consistency`` (``ValueError`` naming "consistency"; nothing touches the device).  Returns None or
-        (measurement fp32, cell, weight), the tensor on the host or the device as it was given.  ``rows``: a ``consistency_operator``
-        is given and the measurement is [m, D/fz, H/fy, W/fx], one volume per row of the operator."""
-        if consistency is None:
-            return None
-        if not isinstance(consistency, (tuple, list)) or len(consistency) != 2:
-            raise ValueError(f"VolumeInference: consistency must be (measurement, cell), got {type(consistency).__name__}")
-        if inpaint is not None:
-            raise ValueError("VolumeInference: consistency and inpaint are not offered together")
-        meas, cell = consistency
-        cell, weight = ops.consistency_cell("VolumeInference", cell, weight)
-        meas = torch.as_tensor(meas)
-        if rows and (meas.ndim != 4 or not meas.is_floating_point()):
-            raise ValueError(f"VolumeInference: with consistency_operator the consistency measurement must be a float "
-                             f"[m, D/fz, H/fy, W/fx] tensor, one volume per row of the operator, got {meas.dtype} {tuple(meas.shape)}")
-        if not rows and (meas.ndim != 3 or not meas.is_floating_point()):
-            raise ValueError(f"VolumeInference: the consistency measurement must be a float [D/fz, H/fy, W/fx] tensor, got {meas.dtype} "
-                             f"{tuple(meas.shape)}")
-        if joint and getattr(sample_fn, 'heun', False):
-            raise ValueError("VolumeInference: consistency is not offered with the EDM Heun denoiser (two predictions per step and three "
-                             "joint volumes): use window_denoiser(sampler='dpmpp2m')")
-        if joint and not hasattr(sample_fn, 'state_space'):
-            raise ValueError("VolumeInference: joint=True with consistency needs a denoiser with state_space(x), the map of the "
-                             "measurement into the space of the state")
-        return meas.float(), cell, weight
+    @property
+    def consistency(self):
+        """None, or the checked ``(measurement fp32, cell, weight)`` of the plan."""
+        return None if self.plan is None else (self.plan.measurement, self.plan.cell, self.plan.weight)
 
-    def _consistency_volume(self, win):
-        """The measurement on the high-res grid, z-scored like the low-res volume, on the volume's device: fp32 [D,H,W]."""
-        meas, cell, _ = self.consistency                     # ``__call__`` has checked its shape
-        if self.consistency_op is not None:                  # t = A+ y, made once per volume: P 1 = 1, so the z-score of t is the t of
-            t = ops.tile_backproject(meas.to(win.device).contiguous(), self.consistency_op)    # the z-scored acquisition
-            return ((t - self.mean) / self.std).contiguous()
-        return ((ops.cell_replicate(meas.to(win.device), cell) - self.mean) / self.std).contiguous()
-
-    def _consistency_windows(self, cw):
-        """What a sampler call takes besides ``x``: the batch's windows of the replicated measurement."""
-        kw = dict(consistency=(cw, self.consistency[1]), consistency_weight=self.consistency[2])
-        if self.consistency_profile is not None:             # only when one was given: the keyword set is otherwise as it was
-            kw.update(consistency_profile=self.consistency_profile)
-        if self.consistency_noise is not None:               # z-scored like the measurement the sampler gets
-            kw.update(consistency_noise=self.consistency_noise / self.std)
-        if self.consistency_op is not None:
-            kw.update(consistency_operator=self.consistency_op)
-        if self.consistency_row_noise is not None:           # z-scored like the measurement the sampler gets
-            kw.update(consistency_row_noise=scale_consistency_row_noise(self.consistency_row_noise, 1., self.std))
-        if self.consistency_slab is not None:
-            kw.update(consistency_slab=self.consistency_slab)
-        return kw
+    # the other consistency keywords as the plan holds them: the operator (whitened under ``consistency_row_noise``), the profile's
+    # host table, and the checked or as-given values
+    consistency_op = property(lambda self: getattr(self.plan, 'op', None))
+    consistency_table = property(lambda self: getattr(self.plan, 'profile_table', None))
+    consistency_noise = property(lambda self: getattr(self.plan, 'noise', None))
+    consistency_row_noise = property(lambda self: getattr(self.plan, 'row_noise', None))
+    consistency_slab = property(lambda self: getattr(self.plan, 'slab', None))
 
     def _inpaint_volumes(self, win):
         """The known volume and the mask as 0/1 floats on the volume's device (``__call__`` has checked their shape)."""
@@ -432,54 +395,21 @@ class VolumeInference:
         denoiser that is neither ``heun`` nor one with the ancestral sampler's ``qs`` / ``renoise`` tables (DDIM and the multistep
         chains have no re-noising loop).
 
-        ``consistency=(measurement, cell)`` with ``consistency_weight=w``: ``measurement`` a float tensor [D/fz, H/fy, W/fx] of RAW
-        intensities (host or device), the block average of the volume to be generated over cells of ``cell`` = (fz, fy, fx) voxels;
-        every x0 prediction has its cell means moved onto it (module docstring).  In the crop and blend modes every call becomes
-        ``sample_fn(x[, noise=src], consistency=(windows, cell), consistency_weight=w)``; with ``joint=True`` the projection rides in
-        the fused launch of the three linear chains.  ``ValueError`` naming "consistency" before anything touches the device: a pair
-        that is not (float [.,.,.] tensor, (fz, fy, fx) integers >= 1 with 2 <= fz fy fx <= 64), a weight outside (0, 1], together with
-        ``inpaint``, joint mode with a Heun denoiser, a stride or window the cell does not divide (crop and blend modes) -- and, in
-        ``__call__``, a measurement that is not the volume's shape divided by the cell.
-
-        ``consistency_profile=(pz, py, px)`` (with ``consistency``): the slice profile of the measurement, three sequences of finite
-        weights >= 0 of lengths fz, fy, fx, each with a positive sum; a zero is a voxel in a slice gap (module docstring;
-        ``ops.cell_measure`` simulates such an acquisition).  The weighted cell means u . x0 are moved onto the measurement -- at
-        w = 1 exactly, u . x0' = y -- and a gap voxel is never moved.  In the crop and blend modes every sampler call also gets
-        ``consistency_profile=``; with ``joint=True`` the fused launch is ``ops.volume_joint_consistent_profile_step``.  A profile
-        without ``consistency``, or one ``ops.cell_profile`` refuses: ``ValueError`` naming "consistency".
-
-        ``consistency_noise=sigma`` (with ``consistency``): the standard deviation of the measurement's noise in raw units (module
-        docstring).  Every step projects with its own weight, capped by ``consistency_weight``, and shapes its fresh noise; the last
-        step is unprojected.  The crop and blend modes hand ``consistency_noise=sigma / std`` on to the sampler; ``joint=True``
-        dispatches per step inside the chain.  ``ValueError`` naming "consistency_noise" before anything touches the device: without
-        ``consistency``, a bool, a non-number, a non-finite or non-positive value, a joint denoiser with no stochastic step.
-
-        ``consistency_operator=A`` (with ``consistency``): a tile-local linear measurement (module docstring) -- ``A`` an [m, n]
-        matrix or what ``ops.tile_operator`` / ``ops.stack_operator`` return; the measurement of ``consistency=(y, cell)`` is then
-        [m, D/fz, H/fy, W/fx] in raw units (``ops.stack_rows`` lays stacks out so, ``ops.tile_measure`` simulates them).
-        t = A+ y is made once per volume and z-scored; the crop and blend modes hand windows of t and ``consistency_operator=`` on to
-        the sampler, ``joint=True`` launches ``ops.volume_joint_consistent_tile_step``.  ``ValueError`` naming
-        "consistency_operator" before anything touches the device: without ``consistency``, together with ``consistency_profile``
-        (a profile is one row of an operator) or ``consistency_noise``, a measurement whose leading dimension is not m, and
-        whatever ``ops.tile_operator`` refuses.
-
-        ``consistency_row_noise=sigma`` (with ``consistency_operator``): the standard deviation of the noise of each row of A in raw
-        units, one number or m of them (module docstring).  Every step weighs every singular direction of the whitened operator on its
-        own and shapes its fresh noise there; the last step is unprojected.  The crop and blend modes hand
-        ``consistency_row_noise=sigma / std`` on; ``joint=True`` dispatches per step.  ``ValueError`` naming
-        "consistency_row_noise" before anything touches the device: without ``consistency_operator``, together with
-        ``consistency_noise`` or ``consistency_profile``, a value ``ops.tile_noise_operator`` refuses, a joint denoiser with no
-        stochastic step, a cell whose launch plans more than 64 KiB of LDS, and whatever ``consistency`` and
-        ``consistency_operator`` refuse.
-
-        ``consistency_slab=(pz, py, px)`` (with ``consistency``): slice profiles that overlap between neighbouring cells along z
-        (module docstring) -- ``pz`` of fz + 2r entries, ``py`` / ``px`` of fy / fx.  The crop and blend modes hand it on as
-        ``consistency_slab=`` (every window enforces its inner slices); ``joint=True`` dispatches
-        ``ops.volume_joint_slab_coeffs`` and ``ops.volume_joint_consistent_slab_step`` per step, three launches.  ``ValueError``
-        naming "consistency_slab" before anything touches the device: without ``consistency``, together with
-        ``consistency_profile``, ``consistency_noise``, ``consistency_operator`` or ``consistency_row_noise``, a profile
-        ``ops.slab_profile`` refuses (a bad reach, the condition rule), a window whose launch plans more than 64 KiB of LDS, and
-        whatever ``consistency`` refuses."""
+        ``consistency=(measurement, cell)`` with ``consistency_weight=w``, and ``consistency_profile``, ``consistency_noise``,
+        ``consistency_operator``, ``consistency_row_noise``, ``consistency_slab`` with it: data-consistent sampling; the measurement
+        models are in the module docstring, the keywords, their rules and the launch a step takes in ``consistency.py``.
+        ``measurement`` is a float tensor [D/fz, H/fy, W/fx] of RAW intensities (host or device) -- with an operator
+        [m, D/fz, H/fy, W/fx], one volume per row (``ops.stack_rows`` lays stacks out so, ``ops.tile_measure`` simulates them) -- and
+        the noise deviations are in raw units too.  It is put on the high-res grid once per volume (``ops.cell_replicate``, or
+        t = A+ y by ``ops.tile_backproject``) and z-scored.  In the crop and blend modes every call becomes ``sample_fn(x[, noise=src],
+        consistency=(windows, cell), consistency_weight=w, ...)`` with every other keyword exactly when it was given, the deviations
+        divided by std; with ``joint=True`` the projection rides in the fused launch of the three linear chains (the slab: three
+        launches per step), the deviations also multiplied by the slope of the denoiser's ``state_space``.  ``ValueError`` naming the
+        keyword at fault, and the one that rides on it, before anything touches the device: what ``consistency.py`` lists, together
+        with ``inpaint``, joint mode with a Heun denoiser or one without ``state_space``, a joint denoiser with no stochastic step
+        under a noise deviation, an operator whose rows are not the measurement's leading dimension, a stride or window the cell
+        does not divide or cubes whose launch plans more than 64 KiB of LDS (crop and blend modes) -- and, in ``__call__``, a
+        measurement that is not the volume's shape divided by the cell."""
         def stochastic():                                    # crop and blend modes: the sampler call knows its own chain
             if joint and hasattr(sample_fn, 'coefs') and not getattr(sample_fn, 'heun', False):
                 # kn is the last entry of a first-order row (kx, k0, kn) and of a sigma-space row (kx, k0, kp, kn); the DDPM family's
@@ -488,42 +418,21 @@ class VolumeInference:
                 return has_kn and any(float(r[-1]) != 0.0 for r in sample_fn.coefs.tolist())
             return True
 
-        check_consistency_slab("VolumeInference", consistency_slab, consistency is not None, consistency_profile, consistency_noise,
-                               consistency_operator, consistency_row_noise)
-        check_consistency_row_noise("VolumeInference", consistency_row_noise, consistency_operator, consistency_profile,
-                                    consistency_noise, consistency_row_noise is None or stochastic())
-        with naming_consistency_row_noise(consistency_row_noise):
-            check_consistency_operator("VolumeInference", consistency_operator, consistency is not None, consistency_profile,
-                                       consistency_noise)
-        with naming_consistency_row_noise(consistency_row_noise), naming_consistency_noise(consistency_noise), \
-                naming_consistency_slab(consistency_slab):
-            # they ride on consistency: what that refuses names them too
-            self.inpaint = self._check_inpaint(inpaint, inpaint_resample_times, joint, sample_fn)
-            self.consistency = self._check_consistency(consistency, consistency_weight, self.inpaint, joint, sample_fn,
-                                                       consistency_operator is not None)
-            self.consistency_op = None
-            if consistency_operator is not None:
-                self.consistency_op = ops.tile_operator(self.consistency[1], consistency_operator)
-                if self.consistency[0].shape[0] != self.consistency_op.m:
-                    raise ValueError(f"VolumeInference: the consistency_operator has m = {self.consistency_op.m} rows, the consistency "
-                                     f"measurement {tuple(self.consistency[0].shape)} has {self.consistency[0].shape[0]} volumes")
-                if consistency_row_noise is not None:        # the whitened operator: its effective A+ makes t, its P the table
-                    self.consistency_op = ops.tile_noise_operator(self.consistency[1], self.consistency_op, consistency_row_noise)
-            if consistency_profile is not None and self.consistency is None:
-                raise ValueError("VolumeInference: consistency_profile needs consistency=(measurement, cell)")
-            # the profile as given (what a sampler call takes) and its host table (what the fused launch takes, moved once per volume)
-            self.consistency_profile = consistency_profile
-            self.consistency_table = None if consistency_profile is None else ops.cell_profile(self.consistency[1], consistency_profile)
-            # the slab profile as given (what a sampler call takes); its rules are checked here, the table of a joint chain is made per
-            # volume, whose depth sets the number of run positions
-            self.consistency_slab = consistency_slab
-            if consistency_slab is not None:
-                ops.slab_profile(self.consistency[1], consistency_slab, jmax=1)
-        self.consistency_row_noise = consistency_row_noise   # as given (what a sampler call takes, divided by std)
-        self.consistency_noise = None
-        if consistency_noise is not None:
-            self.consistency_noise = ops.consistency_noise_sigma("VolumeInference", consistency_noise, self.consistency is not None,
-                                                                 stochastic())
+        self.inpaint = self._check_inpaint(inpaint, inpaint_resample_times, joint, sample_fn)
+        self.cfg = configs
+        tr = configs['Train']
+        self.sub = int(tr['patch_size_sub'])
+        self.block_mode = bool(tr.get('batch_sample', False))
+        self.factor = int(tr.get('batch_sample_factor', 3))
+        self.patch = self.sub * self.factor if self.block_mode else self.sub
+        self.overlap = int(configs['Eval']['overlap'])
+        self.batch = int(configs['Eval'].get('batch_size', 27))
+        self.mean, self.std = float(configs['Data']['mean']), float(configs['Data']['std'])
+        # the fused launch of a joint chain rides the window's taps; a sampler call of the crop and blend modes sees cubes of `sub`
+        self.plan = consistency_plan("VolumeInference", ops, consistency, consistency_weight, consistency_profile, consistency_noise,
+                                     consistency_operator, consistency_row_noise, consistency_slab, stochastic=stochastic(),
+                                     window=dict(edge=self.sub, stride=self.overlap, joint=bool(joint), denoiser=sample_fn,
+                                                 inpaint=self.inpaint is not None, mean=self.mean, std=self.std))
         self.resample_times = inpaint_resample_times
         if noise not in NOISE_MODES:
             raise ValueError(f"VolumeInference: noise must be None or 'anchored', got {noise!r}")
@@ -548,29 +457,8 @@ class VolumeInference:
             if missing:
                 raise ValueError(f"VolumeInference: joint=True takes a window denoiser (Imagen.window_denoiser / "
                                  f"ImagenTrainer.window_denoiser) as its second argument; {type(sample_fn).__name__} lacks {missing}")
-        self.cfg = configs
         self.sample_fn = sample_fn
         self.ratio = nonzero_ratio
-        tr = configs['Train']
-        self.sub = int(tr['patch_size_sub'])
-        self.block_mode = bool(tr.get('batch_sample', False))
-        self.factor = int(tr.get('batch_sample_factor', 3))
-        self.patch = self.sub * self.factor if self.block_mode else self.sub
-        self.overlap = int(configs['Eval']['overlap'])
-        self.batch = int(configs['Eval'].get('batch_size', 27))
-        self.mean, self.std = float(configs['Data']['mean']), float(configs['Data']['std'])
-        if self.consistency_row_noise is not None:           # the fused launch rides the window's taps; a sampler call sees cubes of `sub`
-            ops.tile_noise_plan("VolumeInference", self.consistency[1], self.sub, None if self.joint else self.sub)
-        if self.consistency_slab is not None and not self.joint:    # a sampler call sees cubes of `sub`
-            ops.slab_plan("VolumeInference", self.consistency[1], self.sub)
-        if self.consistency is not None and not self.joint:
-            for f in self.consistency[1]:                    # per axis: origins are multiples of the stride, a sampler call sees `sub`
-                if self.overlap % f or self.sub % f:
-                    with naming_consistency_row_noise(consistency_row_noise), naming_consistency_noise(consistency_noise), \
-                            naming_consistency_slab(consistency_slab):
-                        raise ValueError(f"VolumeInference: the consistency cell {self.consistency[1]} must divide the stride "
-                                         f"{self.overlap} and the window {self.sub}: a per-window projection is defined for cells "
-                                         f"inside a window only (joint=True projects on the whole volume)")
 
     @torch.no_grad()
     def __call__(self, lowres_raw, patch_slice=None, return_std=False):
@@ -585,12 +473,8 @@ class VolumeInference:
         if self.inpaint is not None and tuple(self.inpaint[0].shape) != tuple(lowres_raw.shape):
             raise ValueError(f"VolumeInference: the inpaint volumes {tuple(self.inpaint[0].shape)} are not the volume's shape "
                              f"{tuple(lowres_raw.shape)}")
-        if self.consistency is not None and \
-                tuple(s * f for s, f in zip(self.consistency[0].shape[-3:], self.consistency[1])) != tuple(lowres_raw.shape):
-            with naming_consistency_row_noise(self.consistency_row_noise), naming_consistency_noise(self.consistency_noise), \
-                    naming_consistency_slab(self.consistency_slab):
-                raise ValueError(f"VolumeInference: the consistency measurement {tuple(self.consistency[0].shape)} times the cell "
-                                 f"{self.consistency[1]} is not the volume's shape {tuple(lowres_raw.shape)}")
+        if self.plan is not None:
+            self.plan.admit_volume(lowres_raw.shape)
         if self.blend is not None:
             if patch_slice is not None:
                 raise NotImplementedError("VolumeInference: a blend mode does not split one volume's windows over ranks (that needs a "
@@ -607,8 +491,8 @@ class VolumeInference:
         # below half a patch: one scatter launch per patch, in candidate order, keeps "later overwrites" deterministic
         serial_scatter = (not self.block_mode) and self.overlap < P and P - 2 * (self.overlap // 2) > self.overlap
         known = self._inpaint_volumes(win) if self.inpaint is not None else ()
-        if self.consistency is not None:
-            known = (self._consistency_volume(win),)
+        if self.plan is not None:
+            known = (self.plan.volume(win.device),)
         for lo, o, idx in win.batches:
             x, _ = ops.patch_gather(vol, idx, P, self.mean, self.std)
             kmw = [self._split(ops.patch_gather(v, idx, P, 0., 1.)[0]) for v in known]            # (v - 0) / 1: the volumes' own bits
@@ -632,7 +516,7 @@ class VolumeInference:
         """One sampler call on the windows at ``origins`` (block mode: ONE block, already split into its sub-volumes), sample ``s``;
         ``kw`` / ``mw``: the same windows of the known volume and of the 0/1 mask when the call inpaints -- or ``kw`` alone, the
         windows of the replicated measurement, when it is held to one."""
-        inpaint = {} if kw is None else self._consistency_windows(kw) if mw is None else self._inpaint_windows(kw, mw)
+        inpaint = {} if kw is None else self.plan.keywords(kw, self.std) if mw is None else self._inpaint_windows(kw, mw)
         if self.noise is None:
             return self.sample_fn(x, **inpaint)
         src = AnchoredNoise(win.shape, self.seed).source(win.noise_origins(origins), self.sub, sample=s, device=x.device)
@@ -658,8 +542,8 @@ class VolumeInference:
         P, S = self.patch, self.samples
         patches = torch.empty((S, win.N, P, P, P), dtype=torch.float32, device=win.device)
         known = [(v, 0., 1.) for v in self._inpaint_volumes(win)] if self.inpaint is not None else []
-        if self.consistency is not None:
-            known = [(self._consistency_volume(win), 0., 1.)]
+        if self.plan is not None:
+            known = [(self.plan.volume(win.device), 0., 1.)]
 
         def call(x, *rest):                                  # the windows of the known volume and the mask, or of the measurement (if any), then the origins
             *kmw, o = rest
@@ -678,7 +562,7 @@ class VolumeInference:
         y = torch.empty((win.N, P, P, P), dtype=torch.float32, device=win.device)          # reused by every step of every sample
         # and so is the fused x0 volume of the first-order and multistep chains; the Heun chain makes its three volumes per sample
         # (the consistent launch always writes its corrected x0)
-        win.x0_vol = torch.empty_like(vol) if (den.self_cond or den.multistep or self.consistency is not None) and not den.heun else None
+        win.x0_vol = torch.empty_like(vol) if (den.self_cond or den.multistep or self.plan is not None) and not den.heun else None
 
         def evaluate(state, cond, x0):
             self._evaluate(win, [(state, 0., 1.), (vol, self.mean, self.std), (cond, 0., 1.)], x0, y)   # (v - 0) / 1: the state's own bits
@@ -687,31 +571,8 @@ class VolumeInference:
         if self.inpaint is not None:                         # the known volume in state space, the mask as bytes (the kernels') and 0/1
             known, mask_f = self._inpaint_volumes(win)
             inp = (self.sample_fn.normalize(known).contiguous(), mask_f.to(torch.uint8), mask_f)
-        win.meas_up = None                                   # the replicated measurement in state space, for the fused launch
-        if self.consistency is not None:
-            win.meas_up = self.sample_fn.state_space(self._consistency_volume(win)).contiguous()
-        win.table = None if self.consistency_table is None else self.consistency_table.to(win.device)
-        if self.consistency_op is not None:                  # the operator's projector in the table's place (never both)
-            win.table = self.consistency_op.table.to(win.device)
-        win.slab = None                                      # consistency_slab: the table for this depth, the workspace and the
-        if self.consistency_slab is not None:                # coefficient volume of the three launches, once per volume
-            table = ops.slab_profile(self.consistency[1], self.consistency_slab, jmax=win.shape[0] // self.consistency[1][0])
-            win.slab = (table.to(win.device), *ops.slab_workspace(win.shape, self.consistency[1], win.device))
-        win.noise_schedule = None                            # per step (w_i, shrink_i) in fp32, made once per volume on the host
-        if self.consistency_noise is not None:
-            unit = self.sample_fn.state_space(torch.tensor([0., 1.], dtype=torch.float64))
-            sigma = self.consistency_noise / self.std * abs(float(unit[1] - unit[0]))
-            rows = [(r[0], r[1], 0., r[2]) if len(r) == 3 else tuple(r) for r in den.coefs]
-            win.noise_schedule = ops.consistency_noise_dispatch(ops.consistency_noise_schedule(
-                rows, ops.cell_norm(self.consistency[1], self.consistency_table), sigma, self.consistency[2]))
-        win.row_tables = win.row_kinds = None                # consistency_row_noise: [T, 2, n, n] on the device, one upload, and the
-        if self.consistency_row_noise is not None:           # per-step dispatch, made once per volume on the host
-            unit = self.sample_fn.state_space(torch.tensor([0., 1.], dtype=torch.float64))
-            sigma = float(self.consistency_op.row_noise.min()) / self.std * abs(float(unit[1] - unit[0]))
-            rows = [(r[0], r[1], 0., r[2]) if len(r) == 3 else tuple(r) for r in den.coefs]
-            tables, win.row_kinds = ops.tile_noise_tables(
-                self.consistency_op, ops.tile_noise_schedule(self.consistency_op, rows, sigma, self.consistency[2]))
-            win.row_tables = tables.to(win.device)
+        # the measurement in state space, the mode's table and the rung of every step: once per volume
+        win.consistency = None if self.plan is None else self.plan.prepare(den.coefs, win.device, win.shape)
         mean_io = m2_io = out_std = None
         for s in range(S):
             x = chain(den, win, evaluate, y, s, *inp[:2])
@@ -765,55 +626,20 @@ class VolumeInference:
         else:                                                # n(0)
             x = ops.volume_joint_init(win.shape, self.seed, sample=s, device=win.device)
         head, tail, io = (y, win.slot, win.taps, x), (*den.clamp, self.overlap), dict(out=x, x0_out=win.x0_vol)
+        form = 2 if den.sigma_space else 1 if den.multistep else 0
         for i in range(den.num_steps):
             evaluate(x, win.x0_vol if den.self_cond and i > 0 else None, self._window_x0(den, win, s, i, edm=den.sigma_space))
             prev = win.x0_vol if i else None
-            weight, shrink = 0., 0.
-            if win.meas_up is not None:                      # the constant weight, or consistency_noise's own of this step
-                weight, shrink = (self.consistency[2], 0.) if win.noise_schedule is None else win.noise_schedule[i]
-            kind = None
-            if win.row_kinds is not None:                    # consistency_row_noise: plain (weight 0), constant weight, or the tables
-                kind, weight = win.row_kinds[i]
-            if kind == 'noise':                              # every direction's own weight, the normals shaped: one launch
-                form = 2 if den.sigma_space else 0
-                kx, k0, k2, k3 = (*den.coefs[i], 0.)[:4]
-                ops.volume_joint_consistent_tile_noise_step(*head, prev, win.meas_up, self.consistency[1], win.row_tables[i], form, kx, k0,
-                                                            0. if form == 0 else k2, k2 if form == 0 else k3, *tail, self.seed,
-                                                            draw=den.draw_base + 1 + i if den.sigma_space else i + 1, sample=s, **io)
-            elif win.meas_up is not None and weight > 0 and shrink > 0:    # consistency_noise: the step's own weight, its normals shaped
-                form = 2 if den.sigma_space else 0
-                kx, k0, k2, k3 = (*den.coefs[i], 0.)[:4]
-                ops.volume_joint_consistent_noise_step(*head, prev, win.meas_up, self.consistency[1], win.table, weight, shrink, form, kx, k0,
-                                                       0. if form == 0 else k2, k2 if form == 0 else k3, *tail, self.seed,
-                                                       draw=den.draw_base + 1 + i if den.sigma_space else i + 1, sample=s, **io)
-            elif win.meas_up is not None and weight > 0:     # the same three updates behind the projection of the fused x0
-                form = 2 if den.sigma_space else 1 if den.multistep else 0
-                kx, k0, k2, k3 = (*den.coefs[i], 0.)[:4]     # rows (kx, k0, kn), (kx, k0, kp) or (kx, k0, kp, kn)
-                draw = den.draw_base + 1 + i if den.sigma_space else i + 1
-                if win.slab is not None:                     # three launches: the solve runs along the whole depth
-                    table, workspace, coef = win.slab
-                    ops.volume_joint_slab_coeffs(y, win.slot, win.taps, win.meas_up, self.consistency[1], table, workspace, coef, *tail)
-                    ops.volume_joint_consistent_slab_step(*head, prev, self.consistency[1], table, workspace, coef, weight, form, kx,
-                                                          k0, 0. if form == 0 else k2, k2 if form == 0 else k3, *tail, self.seed,
-                                                          draw=draw, sample=s, **io)
-                elif self.consistency_op is not None:
-                    ops.volume_joint_consistent_tile_step(*head, prev, win.meas_up, self.consistency[1], win.table, weight, form, kx,
-                                                          k0, 0. if form == 0 else k2, k2 if form == 0 else k3, *tail, self.seed,
-                                                          draw=draw, sample=s, **io)
-                elif win.table is not None:
-                    ops.volume_joint_consistent_profile_step(*head, prev, win.meas_up, self.consistency[1], win.table,
-                                                             weight, form, kx, k0, 0. if form == 0 else k2,
-                                                             k2 if form == 0 else k3, *tail, self.seed, draw=draw, sample=s, **io)
-                else:
-                    ops.volume_joint_consistent_step(*head, prev, win.meas_up, self.consistency[1], weight, form, kx, k0,
-                                                     0. if form == 0 else k2, k2 if form == 0 else k3, *tail, self.seed, draw=draw,
-                                                     sample=s, **io)
-            elif den.sigma_space:                            # coefs[i] = (kx, k0, kp, kn): + kp x0_prev + kn n(draw_base + 1 + i)
-                ops.volume_joint_multistep_sde(*head, prev, *den.coefs[i], *tail, self.seed, draw=den.draw_base + 1 + i, sample=s, **io)
+            draw = den.draw_base + 1 + i if den.sigma_space else i + 1
+            # under consistency the same three updates behind the projection of the fused x0, unless the step's rung is the plain one
+            if win.consistency is not None and win.consistency.joint_step(i, head, prev, form, den.coefs[i], tail, self.seed, draw, s, io):
+                continue
+            if den.sigma_space:                              # coefs[i] = (kx, k0, kp, kn): + kp x0_prev + kn n(draw_base + 1 + i)
+                ops.volume_joint_multistep_sde(*head, prev, *den.coefs[i], *tail, self.seed, draw=draw, sample=s, **io)
             elif den.multistep:                              # (kx, k0, kp): + kp x0_prev; only draw 0 of the field is used
                 ops.volume_joint_multistep(*head, prev, *den.coefs[i], *tail, **io)
             else:                                            # (kx, k0, kn): + kn n(i + 1)
-                ops.volume_joint_step(*head, *den.coefs[i], *tail, self.seed, draw=i + 1, sample=s, **io)
+                ops.volume_joint_step(*head, *den.coefs[i], *tail, self.seed, draw=draw, sample=s, **io)
         return x
 
     def _heun_chain(self, den, win, evaluate, y, s, known=None, mask=None):

@@ -2842,29 +2842,77 @@ def cell_replicate(meas, cell):
     return out.contiguous()
 
 
+def _project(who, entry, x0, meas, name, cell, weight, clamp, out, own, noise=None, out_noise=None, shaped=False):
+    """The one body of the projection launches on a window batch: the [B,C,P,P,P] cube check, ``out`` (and, for a launch that is
+    ``shaped`` -- it also reduces the step's normals ``noise`` -- ``out_noise``) allocated where None, the shape, contiguity and
+    aliasing checks, the cell against the cube and the decoding of ``clamp``.  ``meas`` is the measurement operand, ``name`` what its
+    wrapper calls it; ``own(cell, weight, P)`` runs the wrapper's own checks and returns its ``(pointers, scalars)``, the operands
+    of ``entry`` between the measurement and ``out`` and between the cell and the clamp."""
+    _chk(x0, meas, noise, out, out_noise)
+    if x0.ndim != 5 or x0.numel() == 0 or len(set(x0.shape[2:])) != 1:
+        raise ValueError(f"{who}: x0 must be a non-empty [B,C,P,P,P] tensor of cubes, got {tuple(x0.shape)}")
+    if out is None:
+        out = torch.empty_like(x0)
+    if shaped and out_noise is None:
+        out_noise = torch.empty_like(x0)
+    operands = ((meas, name), (noise, 'noise'), (out, 'out'), (out_noise, 'out_noise')) if shaped else ((meas, name), (out, 'out'))
+    for t, label in operands:
+        if t.shape != x0.shape:
+            raise ValueError(f"{who}: {label} must have x0's shape {tuple(x0.shape)}, got {tuple(t.shape)}")
+    if not (x0.is_contiguous() and all(t.is_contiguous() for t, _ in operands)):
+        raise RuntimeError(f"{who}: tensors must be contiguous")
+    if shaped and (out_noise.data_ptr() in (x0.data_ptr(), out.data_ptr(), meas.data_ptr()) or
+                   out.data_ptr() in (noise.data_ptr(), meas.data_ptr())):
+        raise ValueError(f"{who}: out may alias only x0, out_noise only noise")
+    P = x0.shape[2]
+    cell, weight = consistency_cell(who, cell, weight, [(P, a) for a in range(3)])
+    pointers, scalars = own(cell, weight, P)
+    lo, hi, mode = (0., 0., 2) if clamp is None else clamp                # the entry's third mode: no clamp
+    if clamp is not None and int(mode) not in (0, 1):
+        raise ValueError(f"{who}: clamp mode must be 0 (min) or 1 (box), got {mode!r}")
+    _lib.call(entry, x0, meas, *pointers, out, *((out_noise,) if shaped else ()), x0.shape[0] * x0.shape[1], P, *cell, *scalars,
+              float(lo), float(hi), int(mode), _stream())
+    return (out, out_noise) if shaped else out
+
+
+def _joint_form(who, form, noisy=False):
+    """``form`` of a consistent joint step as an int: 0, 1 or 2, and not 1 for a launch that shapes the step's normals."""
+    form = int(form)
+    if noisy and form not in (0, 2):
+        raise ValueError(f"{who}: form must be 0 (first order) or 2 (multistep with noise), got {form!r}")
+    if form not in (0, 1, 2):
+        raise ValueError(f"{who}: form must be 0 (first order), 1 (multistep) or 2 (multistep with noise), got {form!r}")
+    return form
+
+
+def _joint_consistent(who, entry, y, slot, taps, x_t, x0_prev, meas_up, cell, weight, form, coefs, lo, hi, clamp_mode, stride, seed, draw,
+                      sample, out, x0_out, own):
+    """The one body of the consistent joint steps, after ``_joint_form``: the window, noise-key and slot checks, the cell against the
+    volume, ``meas_up`` (None: the launch reads none) and the ``out`` / ``x0_out`` volumes.  ``own(cell, weight, P)`` runs the
+    wrapper's own checks and returns its ``(pointers, scalars)``: the operands of ``entry`` between ``x0_prev`` and ``out`` and between
+    the cell and the coefficients ``coefs`` = (kx, k0, kp, kn).  Returns ``(out, x0_out)``."""
+    N, P, stride = _joint_windows(who, y, slot, taps, x_t, clamp_mode, stride)
+    seed, draw, sample = _noise_key(who, seed, draw, sample)
+    _joint_slots(who, slot, N)
+    cell, weight = consistency_cell(who, cell, weight, [(s, a) for a, s in enumerate(x_t.shape)])
+    if meas_up is not None:
+        _chk(meas_up)
+        if meas_up.shape != x_t.shape or not meas_up.is_contiguous():
+            raise ValueError(f"{who}: meas_up must be a contiguous tensor of x_t's shape")
+    pointers, scalars = own(cell, weight, P)
+    out, x0_out = _joint_volumes(who, x_t, None if form == 0 else x0_prev, out, x0_out)
+    _lib.call(entry, y if N else None, slot, taps, x_t, None if form == 0 else x0_prev, *pointers, out, x0_out, form, N, *x_t.shape, P,
+              stride, *slot.shape, *cell, *scalars, *(float(k) for k in coefs), float(lo), float(hi), int(clamp_mode), seed, draw, sample,
+              _stream())
+    return out, x0_out
+
+
 def cell_project(x0, meas_up, cell, weight=1.0, clamp=None, out=None):
     """The data-consistency projection of a window batch (include/diqt.h, diqt_cell_project): ``x0`` / ``meas_up`` [B,C,P,P,P] the
     prediction and the replicated measurement in the same space, ``cell`` = (fz, fy, fx), ``clamp`` = (lo, hi, mode) with
     ``ddpm_step``'s meaning (None: no clamp).  a = clamp(x0); per cell m = the mean of a; out = a + weight (meas_up - m).  ``out``:
     where it goes (``x0`` itself for an in-place projection; None: a new tensor).  Returns ``out``.  One launch."""
-    who = "cell_project"
-    _chk(x0, meas_up, out)
-    if x0.ndim != 5 or x0.numel() == 0 or len(set(x0.shape[2:])) != 1:
-        raise ValueError(f"{who}: x0 must be a non-empty [B,C,P,P,P] tensor of cubes, got {tuple(x0.shape)}")
-    if out is None:
-        out = torch.empty_like(x0)
-    for t, name in ((meas_up, 'meas_up'), (out, 'out')):
-        if t.shape != x0.shape:
-            raise ValueError(f"{who}: {name} must have x0's shape {tuple(x0.shape)}, got {tuple(t.shape)}")
-    if not (x0.is_contiguous() and meas_up.is_contiguous() and out.is_contiguous()):
-        raise RuntimeError(f"{who}: tensors must be contiguous")
-    P = x0.shape[2]
-    cell, weight = consistency_cell(who, cell, weight, [(P, a) for a in range(3)])
-    lo, hi, mode = (0., 0., 2) if clamp is None else clamp                # the entry's third mode: no clamp
-    if clamp is not None and int(mode) not in (0, 1):
-        raise ValueError(f"{who}: clamp mode must be 0 (min) or 1 (box), got {mode!r}")
-    _lib.call("diqt_cell_project", x0, meas_up, out, x0.shape[0] * x0.shape[1], P, *cell, weight, float(lo), float(hi), int(mode), _stream())
-    return out
+    return _project("cell_project", "diqt_cell_project", x0, meas_up, 'meas_up', cell, weight, clamp, out, lambda cell, w, P: ((), (w,)))
 
 
 def cell_project_profile(x0, meas_up, cell, table, weight=1.0, clamp=None, out=None):
@@ -2872,26 +2920,10 @@ def cell_project_profile(x0, meas_up, cell, table, weight=1.0, clamp=None, out=N
     ``cell_profile``'s weights u and gains g, on ``x0``'s device.  a = clamp(x0); per cell m = u . a; out = a + weight g (meas_up - m):
     at weight 1 the weighted cell means land on the measurement, and a voxel in a gap (u = 0) is never moved.  Everything else --
     shapes, ``clamp``, ``out`` -- as there.  Returns ``out``.  One launch."""
-    who = "cell_project_profile"
-    _chk(x0, meas_up, out)
-    if x0.ndim != 5 or x0.numel() == 0 or len(set(x0.shape[2:])) != 1:
-        raise ValueError(f"{who}: x0 must be a non-empty [B,C,P,P,P] tensor of cubes, got {tuple(x0.shape)}")
-    if out is None:
-        out = torch.empty_like(x0)
-    for t, name in ((meas_up, 'meas_up'), (out, 'out')):
-        if t.shape != x0.shape:
-            raise ValueError(f"{who}: {name} must have x0's shape {tuple(x0.shape)}, got {tuple(t.shape)}")
-    if not (x0.is_contiguous() and meas_up.is_contiguous() and out.is_contiguous()):
-        raise RuntimeError(f"{who}: tensors must be contiguous")
-    P = x0.shape[2]
-    cell, weight = consistency_cell(who, cell, weight, [(P, a) for a in range(3)])
-    _cell_table(who, table, cell, x0)
-    lo, hi, mode = (0., 0., 2) if clamp is None else clamp                # the entry's third mode: no clamp
-    if clamp is not None and int(mode) not in (0, 1):
-        raise ValueError(f"{who}: clamp mode must be 0 (min) or 1 (box), got {mode!r}")
-    _lib.call("diqt_cell_project_profile", x0, meas_up, table, out, x0.shape[0] * x0.shape[1], P, *cell, weight, float(lo), float(hi),
-              int(mode), _stream())
-    return out
+    def own(cell, w, P):
+        _cell_table("cell_project_profile", table, cell, x0)
+        return (table,), (w,)
+    return _project("cell_project_profile", "diqt_cell_project_profile", x0, meas_up, 'meas_up', cell, weight, clamp, out, own)
 
 
 def volume_joint_consistent_step(y, slot, taps, x_t, x0_prev, meas_up, cell, weight, form, kx, k0, kp, kn, lo, hi, clamp_mode, stride,
@@ -2905,21 +2937,9 @@ def volume_joint_consistent_step(y, slot, taps, x_t, x0_prev, meas_up, cell, wei
     uncovered) go -- ``x_t`` and ``x0_prev`` themselves for an in-place step, None: new tensors.  Returns ``(out, x0_out)``.  One launch,
     bit-reproducible."""
     who = "volume_joint_consistent_step"
-    form = int(form)
-    if form not in (0, 1, 2):
-        raise ValueError(f"{who}: form must be 0 (first order), 1 (multistep) or 2 (multistep with noise), got {form!r}")
-    N, P, stride = _joint_windows(who, y, slot, taps, x_t, clamp_mode, stride)
-    seed, draw, sample = _noise_key(who, seed, draw, sample)
-    _joint_slots(who, slot, N)
-    cell, weight = consistency_cell(who, cell, weight, [(s, a) for a, s in enumerate(x_t.shape)])
-    _chk(meas_up)
-    if meas_up.shape != x_t.shape or not meas_up.is_contiguous():
-        raise ValueError(f"{who}: meas_up must be a contiguous tensor of x_t's shape")
-    out, x0_out = _joint_volumes(who, x_t, None if form == 0 else x0_prev, out, x0_out)
-    _lib.call("diqt_volume_joint_consistent_step", y if N else None, slot, taps, x_t, None if form == 0 else x0_prev, meas_up, out, x0_out,
-              form, N, *x_t.shape, P, stride, *slot.shape, *cell, weight, float(kx), float(k0), float(kp), float(kn), float(lo), float(hi),
-              int(clamp_mode), seed, draw, sample, _stream())
-    return out, x0_out
+    return _joint_consistent(who, "diqt_volume_joint_consistent_step", y, slot, taps, x_t, x0_prev, meas_up, cell, weight,
+                             _joint_form(who, form), (kx, k0, kp, kn), lo, hi, clamp_mode, stride, seed, draw, sample, out, x0_out,
+                             lambda cell, w, P: ((meas_up,), (w,)))
 
 
 def volume_joint_consistent_profile_step(y, slot, taps, x_t, x0_prev, meas_up, cell, table, weight, form, kx, k0, kp, kn, lo, hi,
@@ -2930,22 +2950,12 @@ def volume_joint_consistent_profile_step(y, slot, taps, x_t, x0_prev, meas_up, c
     measurement (by ``weight`` of the way, each voxel by its gain) before the update; everything else as there.  Returns
     ``(out, x0_out)``.  One launch, bit-reproducible."""
     who = "volume_joint_consistent_profile_step"
-    form = int(form)
-    if form not in (0, 1, 2):
-        raise ValueError(f"{who}: form must be 0 (first order), 1 (multistep) or 2 (multistep with noise), got {form!r}")
-    N, P, stride = _joint_windows(who, y, slot, taps, x_t, clamp_mode, stride)
-    seed, draw, sample = _noise_key(who, seed, draw, sample)
-    _joint_slots(who, slot, N)
-    cell, weight = consistency_cell(who, cell, weight, [(s, a) for a, s in enumerate(x_t.shape)])
-    _chk(meas_up)
-    if meas_up.shape != x_t.shape or not meas_up.is_contiguous():
-        raise ValueError(f"{who}: meas_up must be a contiguous tensor of x_t's shape")
-    _cell_table(who, table, cell, x_t)
-    out, x0_out = _joint_volumes(who, x_t, None if form == 0 else x0_prev, out, x0_out)
-    _lib.call("diqt_volume_joint_consistent_profile_step", y if N else None, slot, taps, x_t, None if form == 0 else x0_prev, meas_up,
-              table, out, x0_out, form, N, *x_t.shape, P, stride, *slot.shape, *cell, weight, float(kx), float(k0), float(kp), float(kn),
-              float(lo), float(hi), int(clamp_mode), seed, draw, sample, _stream())
-    return out, x0_out
+
+    def own(cell, w, P):
+        _cell_table(who, table, cell, x_t)
+        return (meas_up, table), (w,)
+    return _joint_consistent(who, "diqt_volume_joint_consistent_profile_step", y, slot, taps, x_t, x0_prev, meas_up, cell, weight,
+                             _joint_form(who, form), (kx, k0, kp, kn), lo, hi, clamp_mode, stride, seed, draw, sample, out, x0_out, own)
 
 
 class SlabTable:
@@ -3092,27 +3102,11 @@ def slab_project(x0, meas_up, cell, table, weight=1.0, clamp=None, out=None):
     first and last leave the cube and are never enforced); out = a + weight A_act^T (A_act A_act^T)^-1 (y_act - A_act a) by one
     tridiagonal solve per column, y_s read from ``meas_up`` at the first voxel of slice s' cell.  A voxel under no active row keeps
     a.  Shapes, ``clamp`` and ``out`` as there.  Returns ``out``.  One launch."""
-    who = "slab_project"
-    _chk(x0, meas_up, out)
-    if x0.ndim != 5 or x0.numel() == 0 or len(set(x0.shape[2:])) != 1:
-        raise ValueError(f"{who}: x0 must be a non-empty [B,C,P,P,P] tensor of cubes, got {tuple(x0.shape)}")
-    if out is None:
-        out = torch.empty_like(x0)
-    for t, name in ((meas_up, 'meas_up'), (out, 'out')):
-        if t.shape != x0.shape:
-            raise ValueError(f"{who}: {name} must have x0's shape {tuple(x0.shape)}, got {tuple(t.shape)}")
-    if not (x0.is_contiguous() and meas_up.is_contiguous() and out.is_contiguous()):
-        raise RuntimeError(f"{who}: tensors must be contiguous")
-    P = x0.shape[2]
-    cell, weight = consistency_cell(who, cell, weight, [(P, a) for a in range(3)])
-    _slab_table(who, table, cell, x0, P // cell[0])
-    slab_plan(who, cell, P)
-    lo, hi, mode = (0., 0., 2) if clamp is None else clamp                # the entry's third mode: no clamp
-    if clamp is not None and int(mode) not in (0, 1):
-        raise ValueError(f"{who}: clamp mode must be 0 (min) or 1 (box), got {mode!r}")
-    _lib.call("diqt_slab_project", x0, meas_up, table.table, out, x0.shape[0] * x0.shape[1], P, *cell, table.reach, table.jmax, weight,
-              float(lo), float(hi), int(mode), _stream())
-    return out
+    def own(cell, w, P):
+        _slab_table("slab_project", table, cell, x0, P // cell[0])
+        slab_plan("slab_project", cell, P)
+        return (table.table,), (table.reach, table.jmax, w)
+    return _project("slab_project", "diqt_slab_project", x0, meas_up, 'meas_up', cell, weight, clamp, out, own)
 
 
 def slab_workspace(shape, cell, device):
@@ -3159,20 +3153,12 @@ def volume_joint_consistent_slab_step(y, slot, taps, x_t, x0_prev, cell, table, 
     ``volume_joint_slab_coeffs`` left them for the same ``y``.  A covered voxel under no active row steps with its plain x0.
     ``out`` / ``x0_out`` as there.  Returns ``(out, x0_out)``.  One launch, bit-reproducible."""
     who = "volume_joint_consistent_slab_step"
-    form = int(form)
-    if form not in (0, 1, 2):
-        raise ValueError(f"{who}: form must be 0 (first order), 1 (multistep) or 2 (multistep with noise), got {form!r}")
-    N, P, stride = _joint_windows(who, y, slot, taps, x_t, clamp_mode, stride)
-    seed, draw, sample = _noise_key(who, seed, draw, sample)
-    _joint_slots(who, slot, N)
-    _, weight = consistency_cell(who, cell, weight)
-    cell = _slab_joint(who, x_t, cell, table, workspace, coef)
-    out, x0_out = _joint_volumes(who, x_t, None if form == 0 else x0_prev, out, x0_out)
-    _lib.call("diqt_volume_joint_consistent_slab_step", y if N else None, slot, taps, x_t, None if form == 0 else x0_prev, table.table,
-              coef, workspace, workspace.numel(), out, x0_out, form, N, *x_t.shape, P, stride, *slot.shape, *cell, table.reach,
-              table.jmax, weight, float(kx), float(k0), float(kp), float(kn), float(lo), float(hi), int(clamp_mode), seed, draw, sample,
-              _stream())
-    return out, x0_out
+
+    def own(cell, w, P):
+        _slab_joint(who, x_t, cell, table, workspace, coef)
+        return (table.table, coef, workspace, workspace.numel()), (table.reach, table.jmax, w)
+    return _joint_consistent(who, "diqt_volume_joint_consistent_slab_step", y, slot, taps, x_t, x0_prev, None, cell, weight,
+                             _joint_form(who, form), (kx, k0, kp, kn), lo, hi, clamp_mode, stride, seed, draw, sample, out, x0_out, own)
 
 
 class TileOperator:
@@ -3334,26 +3320,10 @@ def tile_project(x0, target, cell, table, weight=1.0, clamp=None, out=None):
     back-projected measurement t = A+ y, ``table`` [n, n] = ``tile_operator``'s P, on ``x0``'s device.  a = clamp(x0); per tile
     out = a + weight (t - P a): at weight 1, P out = t, and A out = y for a y in the range of A.  Everything else -- shapes,
     ``clamp``, ``out`` -- as there.  Returns ``out``.  One launch."""
-    who = "tile_project"
-    _chk(x0, target, out)
-    if x0.ndim != 5 or x0.numel() == 0 or len(set(x0.shape[2:])) != 1:
-        raise ValueError(f"{who}: x0 must be a non-empty [B,C,P,P,P] tensor of cubes, got {tuple(x0.shape)}")
-    if out is None:
-        out = torch.empty_like(x0)
-    for t, name in ((target, 'target'), (out, 'out')):
-        if t.shape != x0.shape:
-            raise ValueError(f"{who}: {name} must have x0's shape {tuple(x0.shape)}, got {tuple(t.shape)}")
-    if not (x0.is_contiguous() and target.is_contiguous() and out.is_contiguous()):
-        raise RuntimeError(f"{who}: tensors must be contiguous")
-    P = x0.shape[2]
-    cell, weight = consistency_cell(who, cell, weight, [(P, a) for a in range(3)])
-    _tile_table(who, table, cell, x0)
-    lo, hi, mode = (0., 0., 2) if clamp is None else clamp                # the entry's third mode: no clamp
-    if clamp is not None and int(mode) not in (0, 1):
-        raise ValueError(f"{who}: clamp mode must be 0 (min) or 1 (box), got {mode!r}")
-    _lib.call("diqt_tile_project", x0, target, table, out, x0.shape[0] * x0.shape[1], P, *cell, weight, float(lo), float(hi), int(mode),
-              _stream())
-    return out
+    def own(cell, w, P):
+        _tile_table("tile_project", table, cell, x0)
+        return (table,), (w,)
+    return _project("tile_project", "diqt_tile_project", x0, target, 'target', cell, weight, clamp, out, own)
 
 
 def volume_joint_consistent_tile_step(y, slot, taps, x_t, x0_prev, meas_up, cell, table, weight, form, kx, k0, kp, kn, lo, hi,
@@ -3363,22 +3333,12 @@ def volume_joint_consistent_tile_step(y, slot, taps, x_t, x0_prev, meas_up, cell
     tile whose voxels are ALL covered has its fused x0 moved to x0 + ``weight`` (t - P x0) before the update; everything else as
     there.  Returns ``(out, x0_out)``.  One launch, bit-reproducible."""
     who = "volume_joint_consistent_tile_step"
-    form = int(form)
-    if form not in (0, 1, 2):
-        raise ValueError(f"{who}: form must be 0 (first order), 1 (multistep) or 2 (multistep with noise), got {form!r}")
-    N, P, stride = _joint_windows(who, y, slot, taps, x_t, clamp_mode, stride)
-    seed, draw, sample = _noise_key(who, seed, draw, sample)
-    _joint_slots(who, slot, N)
-    cell, weight = consistency_cell(who, cell, weight, [(s, a) for a, s in enumerate(x_t.shape)])
-    _chk(meas_up)
-    if meas_up.shape != x_t.shape or not meas_up.is_contiguous():
-        raise ValueError(f"{who}: meas_up must be a contiguous tensor of x_t's shape")
-    _tile_table(who, table, cell, x_t)
-    out, x0_out = _joint_volumes(who, x_t, None if form == 0 else x0_prev, out, x0_out)
-    _lib.call("diqt_volume_joint_consistent_tile_step", y if N else None, slot, taps, x_t, None if form == 0 else x0_prev, meas_up,
-              table, out, x0_out, form, N, *x_t.shape, P, stride, *slot.shape, *cell, weight, float(kx), float(k0), float(kp), float(kn),
-              float(lo), float(hi), int(clamp_mode), seed, draw, sample, _stream())
-    return out, x0_out
+
+    def own(cell, w, P):
+        _tile_table(who, table, cell, x_t)
+        return (meas_up, table), (w,)
+    return _joint_consistent(who, "diqt_volume_joint_consistent_tile_step", y, slot, taps, x_t, x0_prev, meas_up, cell, weight,
+                             _joint_form(who, form), (kx, k0, kp, kn), lo, hi, clamp_mode, stride, seed, draw, sample, out, x0_out, own)
 
 
 def consistency_noise_sigma(who, sigma_y, has_consistency=True, stochastic=True):
@@ -3459,31 +3419,12 @@ def cell_project_noise(x0, meas_up, noise, cell, weight, shrink, table=None, cla
     who = "cell_project_noise"
     if isinstance(shrink, bool) or not isinstance(shrink, (int, float)) or not 0. < shrink <= 1.:
         raise ValueError(f"{who}: the consistency_noise shrink must be a number in (0, 1], got {shrink!r}")
-    _chk(x0, meas_up, noise, out, out_noise)
-    if x0.ndim != 5 or x0.numel() == 0 or len(set(x0.shape[2:])) != 1:
-        raise ValueError(f"{who}: x0 must be a non-empty [B,C,P,P,P] tensor of cubes, got {tuple(x0.shape)}")
-    if out is None:
-        out = torch.empty_like(x0)
-    if out_noise is None:
-        out_noise = torch.empty_like(x0)
-    for t, name in ((meas_up, 'meas_up'), (noise, 'noise'), (out, 'out'), (out_noise, 'out_noise')):
-        if t.shape != x0.shape:
-            raise ValueError(f"{who}: {name} must have x0's shape {tuple(x0.shape)}, got {tuple(t.shape)}")
-    if not all(t.is_contiguous() for t in (x0, meas_up, noise, out, out_noise)):
-        raise RuntimeError(f"{who}: tensors must be contiguous")
-    if out_noise.data_ptr() in (x0.data_ptr(), out.data_ptr(), meas_up.data_ptr()) or out.data_ptr() in (noise.data_ptr(),
-                                                                                                         meas_up.data_ptr()):
-        raise ValueError(f"{who}: out may alias only x0, out_noise only noise")
-    P = x0.shape[2]
-    cell, weight = consistency_cell(who, cell, weight, [(P, a) for a in range(3)])
-    if table is not None:
-        _cell_table(who, table, cell, x0)
-    lo, hi, mode = (0., 0., 2) if clamp is None else clamp                # the entry's third mode: no clamp
-    if clamp is not None and int(mode) not in (0, 1):
-        raise ValueError(f"{who}: clamp mode must be 0 (min) or 1 (box), got {mode!r}")
-    _lib.call("diqt_cell_project_noise", x0, meas_up, noise, table, out, out_noise, x0.shape[0] * x0.shape[1], P, *cell, weight,
-              float(shrink), float(lo), float(hi), int(mode), _stream())
-    return out, out_noise
+
+    def own(cell, w, P):
+        if table is not None:
+            _cell_table(who, table, cell, x0)
+        return (noise, table), (w, float(shrink))
+    return _project(who, "diqt_cell_project_noise", x0, meas_up, 'meas_up', cell, weight, clamp, out, own, noise, out_noise, shaped=True)
 
 
 def volume_joint_consistent_noise_step(y, slot, taps, x_t, x0_prev, meas_up, cell, table, weight, shrink, form, kx, k0, kp, kn, lo, hi,
@@ -3494,27 +3435,18 @@ def volume_joint_consistent_noise_step(y, slot, taps, x_t, x0_prev, meas_up, cel
     normals.  ``form`` 0 or 2 with ``kn != 0`` and ``shrink`` in (0, 1] only.  The normals are the plain launch's (same key, same draw
     number).  Returns ``(out, x0_out)``.  One launch, bit-reproducible."""
     who = "volume_joint_consistent_noise_step"
-    form = int(form)
-    if form not in (0, 2):
-        raise ValueError(f"{who}: form must be 0 (first order) or 2 (multistep with noise), got {form!r}")
+    form = _joint_form(who, form, noisy=True)
     if float(kn) == 0.0:
         raise ValueError(f"{who}: kn == 0: a step without a normal has no consistency_noise shaping")
     if isinstance(shrink, bool) or not isinstance(shrink, (int, float)) or not 0. < shrink <= 1.:
         raise ValueError(f"{who}: the consistency_noise shrink must be a number in (0, 1], got {shrink!r}")
-    N, P, stride = _joint_windows(who, y, slot, taps, x_t, clamp_mode, stride)
-    seed, draw, sample = _noise_key(who, seed, draw, sample)
-    _joint_slots(who, slot, N)
-    cell, weight = consistency_cell(who, cell, weight, [(s, a) for a, s in enumerate(x_t.shape)])
-    _chk(meas_up)
-    if meas_up.shape != x_t.shape or not meas_up.is_contiguous():
-        raise ValueError(f"{who}: meas_up must be a contiguous tensor of x_t's shape")
-    if table is not None:
-        _cell_table(who, table, cell, x_t)
-    out, x0_out = _joint_volumes(who, x_t, None if form == 0 else x0_prev, out, x0_out)
-    _lib.call("diqt_volume_joint_consistent_noise_step", y if N else None, slot, taps, x_t, None if form == 0 else x0_prev, meas_up, table,
-              out, x0_out, form, N, *x_t.shape, P, stride, *slot.shape, *cell, weight, float(shrink), float(kx), float(k0), float(kp),
-              float(kn), float(lo), float(hi), int(clamp_mode), seed, draw, sample, _stream())
-    return out, x0_out
+
+    def own(cell, w, P):
+        if table is not None:
+            _cell_table(who, table, cell, x_t)
+        return (meas_up, table), (w, float(shrink))
+    return _joint_consistent(who, "diqt_volume_joint_consistent_noise_step", y, slot, taps, x_t, x0_prev, meas_up, cell, weight, form,
+                             (kx, k0, kp, kn), lo, hi, clamp_mode, stride, seed, draw, sample, out, x0_out, own)
 
 
 class TileNoiseOperator(TileOperator):
@@ -3673,31 +3605,12 @@ def tile_project_noise(x0, target, noise, cell, tables_i, clamp=None, out=None, 
     who = "tile_project_noise"
     if torch.is_tensor(x0) and x0.ndim == 5:                              # the cell's and the tables' own rules first: they need no device
         _tile_noise_tables(who, tables_i, consistency_cell(who, cell, 1.0, [(x0.shape[2], a) for a in range(3)])[0], x0, device=False)
-    _chk(x0, target, noise, out, out_noise)
-    if x0.ndim != 5 or x0.numel() == 0 or len(set(x0.shape[2:])) != 1:
-        raise ValueError(f"{who}: x0 must be a non-empty [B,C,P,P,P] tensor of cubes, got {tuple(x0.shape)}")
-    if out is None:
-        out = torch.empty_like(x0)
-    if out_noise is None:
-        out_noise = torch.empty_like(x0)
-    for t, name in ((target, 'target'), (noise, 'noise'), (out, 'out'), (out_noise, 'out_noise')):
-        if t.shape != x0.shape:
-            raise ValueError(f"{who}: {name} must have x0's shape {tuple(x0.shape)}, got {tuple(t.shape)}")
-    if not all(t.is_contiguous() for t in (x0, target, noise, out, out_noise)):
-        raise RuntimeError(f"{who}: tensors must be contiguous")
-    if out_noise.data_ptr() in (x0.data_ptr(), out.data_ptr(), target.data_ptr()) or out.data_ptr() in (noise.data_ptr(),
-                                                                                                        target.data_ptr()):
-        raise ValueError(f"{who}: out may alias only x0, out_noise only noise")
-    P = x0.shape[2]
-    cell, _ = consistency_cell(who, cell, 1.0, [(P, a) for a in range(3)])
-    _tile_noise_tables(who, tables_i, cell, x0)
-    tile_noise_plan(who, cell, 0, P)
-    lo, hi, mode = (0., 0., 2) if clamp is None else clamp                # the entry's third mode: no clamp
-    if clamp is not None and int(mode) not in (0, 1):
-        raise ValueError(f"{who}: clamp mode must be 0 (min) or 1 (box), got {mode!r}")
-    _lib.call("diqt_tile_project_noise", x0, target, noise, tables_i, out, out_noise, x0.shape[0] * x0.shape[1], P, *cell, float(lo),
-              float(hi), int(mode), _stream())
-    return out, out_noise
+
+    def own(cell, w, P):
+        _tile_noise_tables(who, tables_i, cell, x0)
+        tile_noise_plan(who, cell, 0, P)
+        return (noise, tables_i), ()
+    return _project(who, "diqt_tile_project_noise", x0, target, 'target', cell, 1.0, clamp, out, own, noise, out_noise, shaped=True)
 
 
 def volume_joint_consistent_tile_noise_step(y, slot, taps, x_t, x0_prev, meas_up, cell, tables_i, form, kx, k0, kp, kn, lo, hi,
@@ -3708,25 +3621,16 @@ def volume_joint_consistent_tile_noise_step(y, slot, taps, x_t, x0_prev, meas_up
     eps - G_i eps before the update; a tile with an uncovered voxel keeps both.  ``form`` 0 or 2 with ``kn != 0`` only.  The normals
     are the plain launch's (same key, same draw number).  Returns ``(out, x0_out)``.  One launch, bit-reproducible."""
     who = "volume_joint_consistent_tile_noise_step"
-    form = int(form)
-    if form not in (0, 2):
-        raise ValueError(f"{who}: form must be 0 (first order) or 2 (multistep with noise), got {form!r}")
+    form = _joint_form(who, form, noisy=True)
     if float(kn) == 0.0:
         raise ValueError(f"{who}: kn == 0: a step without a normal has no consistency_row_noise shaping")
-    N, P, stride = _joint_windows(who, y, slot, taps, x_t, clamp_mode, stride)
-    seed, draw, sample = _noise_key(who, seed, draw, sample)
-    _joint_slots(who, slot, N)
-    cell, _ = consistency_cell(who, cell, 1.0, [(s, a) for a, s in enumerate(x_t.shape)])
-    _chk(meas_up)
-    if meas_up.shape != x_t.shape or not meas_up.is_contiguous():
-        raise ValueError(f"{who}: meas_up must be a contiguous tensor of x_t's shape")
-    _tile_noise_tables(who, tables_i, cell, x_t)
-    tile_noise_plan(who, cell, P)
-    out, x0_out = _joint_volumes(who, x_t, None if form == 0 else x0_prev, out, x0_out)
-    _lib.call("diqt_volume_joint_consistent_tile_noise_step", y if N else None, slot, taps, x_t, None if form == 0 else x0_prev, meas_up,
-              tables_i, out, x0_out, form, N, *x_t.shape, P, stride, *slot.shape, *cell, float(kx), float(k0), float(kp), float(kn),
-              float(lo), float(hi), int(clamp_mode), seed, draw, sample, _stream())
-    return out, x0_out
+
+    def own(cell, w, P):
+        _tile_noise_tables(who, tables_i, cell, x_t)
+        tile_noise_plan(who, cell, P)
+        return (meas_up, tables_i), ()
+    return _joint_consistent(who, "diqt_volume_joint_consistent_tile_noise_step", y, slot, taps, x_t, x0_prev, meas_up, cell, 1.0, form,
+                             (kx, k0, kp, kn), lo, hi, clamp_mode, stride, seed, draw, sample, out, x0_out, own)
 
 
 def volume_joint_heun_init(shape, sigma0, kc, seed, draw=0, sample=0, device=None):
