@@ -201,6 +201,13 @@ PROTOTYPES = {
     "diqt_volume_joint_slab_coeffs": (I, [P] * 6 + [Z, P] + [I] * 14 + [F, F, I, P]),
     "diqt_volume_joint_consistent_slab_step": (I, [P] * 8 + [Z, P, P] + [I] * 15 + [F] * 7 + [I, ctypes.c_ulonglong, ctypes.c_uint,
                                                                                               ctypes.c_uint, P]),
+    "diqt_band_measure": (I, [P, P, P, P, Z] + [I] * 7 + [P]),
+    "diqt_band_backproject": (I, [P, P, P, P, Z] + [I] * 7 + [P]),
+    "diqt_band_project": (I, [P, P, P, P, P, Z] + [I] * 4 + [Z, I, F, F, F, I, P]),
+    "diqt_band_apply": (I, [P, P, P, P, Z] + [I] * 4 + [P]),
+    "diqt_volume_joint_band_residual": (I, [P] * 7 + [I] * 9 + [F, F, I, P]),
+    "diqt_volume_joint_consistent_band_step": (I, [P] * 10 + [I] * 13 + [F] * 7 + [I, ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_uint,
+                                                                                   P]),
     "diqt_volume_joint_heun": (I, [P] * 6 +[I] * 10 + [F] * 7 + [I, ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_uint, P]),
     "diqt_edm_inpaint_churn": (I, [P] * 8 + [I, Z, P]),
     "diqt_volume_joint_heun_inpaint": (I, [P] * 8 + [I] * 10 + [F] * 8 + [I, ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_uint,

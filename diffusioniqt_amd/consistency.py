@@ -1,4 +1,4 @@
-"""Data-consistent sampling, the part every sampler shares: which combinations of the seven ``consistency*`` keywords are admitted, and
+"""Data-consistent sampling, the part every sampler shares: which combinations of the eight ``consistency*`` keywords are admitted, and
 which launch a step takes.  ``Imagen.sample`` / ``p_sample_loop``, ``ElucidatedImagen.sample`` / ``one_unet_sample`` and
 ``VolumeInference`` take the same keywords, hand them to ``plan`` as they received them and keep what it returns: None (no
 ``consistency``) or a ``Plan``.  The measurement models themselves are described in the docstring of ``inference``; the kernels are
@@ -16,6 +16,11 @@ The keywords:
   ``VolumeInference`` the raw [m, D/fz, H/fy, W/fx] stack.  Not with a profile (one row of an operator) or ``consistency_noise``.
 * ``consistency_slab=(pz, py, px)``: slice profiles that overlap between neighbouring cells along z (``ops.slab_profile``).  With none of
   the other modes.
+* ``consistency_band=(hz, hy, hx)`` or ``(hz, hy, hx, offset)``: the measurement is the central box of the k-space of the periodic
+  domain, sampled on the low-res grid (``ops.band_table``): per axis None (the full band of the low-res grid) or the weights of the
+  frequencies k = 0 .. len - 1; ``offset`` = three numbers in high-res voxels or 'centre'.  The measurement is then t = A+ y on the
+  grid (``ops.band_backproject``), for ``VolumeInference`` the raw [D/fz, H/fy, W/fx] volume.  The operator crosses every tile border:
+  the domain of a one-call sampler is its cube, and ``VolumeInference`` takes it with ``joint=True`` only.  With none of the other modes.
 * ``consistency_noise=sigma`` (a cell mean or a profile): the deviation of the measurement's noise (DDNM+).  Every step gets its own
   weight, capped by ``consistency_weight``, and a reduction of its fresh normals in the range of A
   (``ops.consistency_noise_schedule``).  It needs a chain with a stochastic step.
@@ -28,10 +33,10 @@ what ``consistency`` (or the operator) refuses also names the keyword that rides
 
 The ladder of a step, resolved per step once per chain (``Chain.steps``): ``plain`` -- the family's own step, no projection (weight 0:
 the step with kn = 0 of a noise-aware chain); ``constant`` -- the projection of the mode with one weight (``ops.cell_project`` /
-``cell_project_profile`` / ``tile_project`` / ``slab_project``, or the fused ``ops.volume_joint_consistent*_step``); ``noise`` -- the
-projection with the step's own weights that also shapes the step's normals (``ops.cell_project_noise`` / ``tile_project_noise`` and
-their fused launches).  A projected prediction is not clamped again: the projection launch clamps first, the step runs with the clamp
-off.
+``cell_project_profile`` / ``tile_project`` / ``slab_project`` / ``band_project``, or the fused
+``ops.volume_joint_consistent*_step``); ``noise`` -- the projection with the step's own weights that also shapes the step's normals
+(``ops.cell_project_noise`` / ``tile_project_noise`` and their fused launches).  A projected prediction is not clamped again: the
+projection launch clamps first, the step runs with the clamp off.
 
 A further measurement model adds a branch to ``plan`` (its admission rules and host table), one to ``Chain.__init__`` (its device
 table), a rung to ``Chain.project`` and ``Chain.joint_step``, and its wrappers in ``ops``."""
@@ -45,13 +50,14 @@ NO_CLAMP = (-float('inf'), float('inf'), 1)                  # ``ddpm_step``'s b
 
 
 @contextmanager
-def _riders(slab, noise, row_noise):
+def _riders(slab, noise, row_noise, band=None):
     """A ``ValueError`` raised inside keeps its wording and also names the given keyword that rides on what refused."""
     try:
         yield
     except ValueError as err:
         msg = str(err)
         for name, value, note in (('consistency_slab', slab, "consistency_slab rides on consistency"),
+                                  ('consistency_band', band, "consistency_band rides on consistency"),
                                   ('consistency_noise', noise, f"consistency_noise={noise!r} rides on consistency"),
                                   ('consistency_row_noise', row_noise,
                                    f"consistency_row_noise={row_noise!r} rides on consistency_operator")):
@@ -120,9 +126,9 @@ def _volume_pair(who, consistency, weight, window, rows):
     return meas.float(), cell, weight
 
 
-def plan(who, launch, consistency, weight=1., profile=None, noise=None, operator=None, row_noise=None, slab=None, *, shape=None, window=None,
-         stochastic=True, has_inpainting=False, init_images=None, skip_steps=None, sampler=None):
-    """The admission rules of the seven keywords (the module docstring), run once and in one order -- slab, row noise, operator, the
+def plan(who, launch, consistency, weight=1., profile=None, noise=None, operator=None, row_noise=None, slab=None, band=None, *, shape=None,
+         window=None, stochastic=True, has_inpainting=False, init_images=None, skip_steps=None, sampler=None):
+    """The admission rules of the eight keywords (the module docstring), run once and in one order -- band, slab, row noise, operator, the
     pair itself, the profile, the noise deviation, the LDS plans -- for the entry point ``who``: None without ``consistency``, else the
     ``Plan``.  ``launch`` is the ``ops`` of the calling module: the rules and host tables here are ``ops``'s own host arithmetic, but
     everything that touches the device -- the replication, the back-projection, the workspace, every projection and step -- goes
@@ -132,6 +138,18 @@ def plan(who, launch, consistency, weight=1., profile=None, noise=None, operator
     ``window`` instead: a dict of the window ``edge``, the ``stride``, ``joint``, the ``denoiser`` (its second argument), whether it
     inpaints (``inpaint``) and the z-score's ``mean`` / ``std``."""
     has = consistency is not None
+    if band is not None:
+        if not has:
+            raise ValueError(f"{who}: consistency_band needs consistency=(measurement, cell)")
+        for other, name in ((profile, 'consistency_profile'), (noise, 'consistency_noise'), (operator, 'consistency_operator'),
+                            (row_noise, 'consistency_row_noise'), (slab, 'consistency_slab')):
+            if other is not None:
+                raise ValueError(f"{who}: consistency_band and {name} are not offered together")
+        if not isinstance(band, (tuple, list)) or len(band) not in (3, 4):
+            raise ValueError(f"{who}: consistency_band must be (hz, hy, hx) or (hz, hy, hx, offset), got {band!r}")
+        if window is not None and not window['joint']:
+            raise ValueError(f"{who}: consistency_band needs joint=True: the band's projector crosses every window border, and a window "
+                             f"of t = A+ y is not the t of a window (the crop and blend modes project window by window)")
     if slab is not None:
         if not has:
             raise ValueError(f"{who}: consistency_slab needs consistency=(meas_up, cell)")
@@ -150,7 +168,7 @@ def plan(who, launch, consistency, weight=1., profile=None, noise=None, operator
             raise ValueError(f"{who}: consistency_row_noise needs a sampler with fresh noise per step (ddpm, ddim or dpmpp2m with eta > "
                              f"0): a deterministic chain would never project; use a constant consistency_weight < 1 there")
     p = None
-    with _riders(slab, noise, row_noise):
+    with _riders(slab, noise, row_noise, band):
         if operator is not None:
             if not has:
                 raise ValueError(f"{who}: consistency_operator needs consistency=(measurement, cell)")
@@ -167,8 +185,8 @@ def plan(who, launch, consistency, weight=1., profile=None, noise=None, operator
                 pair = _sampled_pair(who, consistency, weight, shape, has_inpainting, init_images, skip_steps, sampler)
             else:
                 pair = _volume_pair(who, consistency, weight, window, operator is not None)
-            p = Plan(who, launch, *pair, profile, operator, row_noise, slab, **({} if window is None else
-                                                                       dict(mean=window['mean'], std=window['std'])))
+            p = Plan(who, launch, *pair, profile, operator, row_noise, slab, band, **({} if window is None else
+                                                                             dict(mean=window['mean'], std=window['std'])))
             if operator is not None:
                 p.mode, p.op = 'tile', ops.tile_operator(p.cell, operator)
                 if window is not None and p.measurement.shape[0] != p.op.m:
@@ -178,6 +196,10 @@ def plan(who, launch, consistency, weight=1., profile=None, noise=None, operator
                     p.op = ops.tile_noise_operator(p.cell, p.op, row_noise)
                 if window is not None:                       # what a sampler call takes: the decomposition is not made again
                     p.operator = p.op
+            elif band is not None:                           # the table for the cubes of a sampler; a joint chain makes its own per
+                p.mode = 'band'                              # volume: the domain is the whole volume
+                if window is None:
+                    p.band_table = p.band_of(shape[2:])
             elif slab is not None:                           # the table for the cubes of a sampler; a joint chain makes its own per
                 p.mode = 'slab'                              # volume, whose depth sets the number of run positions
                 p.slab_table = ops.slab_profile(p.cell, slab, jmax=1 if window is not None else shape[2] // p.cell[0])
@@ -188,7 +210,7 @@ def plan(who, launch, consistency, weight=1., profile=None, noise=None, operator
     if p is None:
         return None
     p.noise = noise
-    with _riders(slab, noise, row_noise):
+    with _riders(slab, noise, row_noise, band):
         # the cubes a projection launch sees; None: the fused launch of a joint chain, which rides the window's taps
         edge = shape[2] if window is None else None if window['joint'] else window['edge']
         if row_noise is not None:
@@ -208,30 +230,49 @@ def plan(who, launch, consistency, weight=1., profile=None, noise=None, operator
 
 class Plan:
     """What ``plan`` admitted.  ``measurement``, ``cell``, ``weight``: the checked pair; ``profile``, ``operator``, ``row_noise``,
-    ``slab``: as given (what a sampler call takes); ``noise``: the checked deviation or None; ``mode``: ``'cell'``, ``'profile'``,
-    ``'tile'`` or ``'slab'``, and its host table -- ``profile_table`` (``ops.cell_profile``), ``op`` (the ``ops.TileOperator``, whitened
-    under ``row_noise``) or ``slab_table`` (the ``ops.SlabTable`` for a sampler's cubes); for ``VolumeInference`` the z-score's ``mean``
+    ``slab``, ``band``: as given (what a sampler call takes); ``noise``: the checked deviation or None; ``mode``: ``'cell'``,
+    ``'profile'``, ``'tile'``, ``'slab'`` or ``'band'``, and its host table -- ``profile_table`` (``ops.cell_profile``), ``op`` (the
+    ``ops.TileOperator``, whitened under ``row_noise``), ``slab_table`` (the ``ops.SlabTable`` for a sampler's cubes) or ``band_table``
+    (the ``ops.BandTable`` for a sampler's cubes; ``band_of(shape)`` makes the one of a volume, once); for ``VolumeInference`` the
+    z-score's ``mean``
     / ``std`` and, in joint mode, the denoiser's ``state_space``."""
-    mode, op, profile_table, slab_table, noise, state_space = 'cell', None, None, None, None, None
+    mode, op, profile_table, slab_table, band_table, noise, state_space = 'cell', None, None, None, None, None, None
 
-    def __init__(self, who, launch, measurement, cell, weight, profile, operator, row_noise, slab, mean=0., std=1.):
+    def __init__(self, who, launch, measurement, cell, weight, profile, operator, row_noise, slab, band=None, mean=0., std=1.):
         self.who, self.launch, self.measurement, self.cell, self.weight = who, launch, measurement, cell, weight
-        self.profile, self.operator, self.row_noise, self.slab = profile, operator, row_noise, slab
+        self.profile, self.operator, self.row_noise, self.slab, self.band = profile, operator, row_noise, slab, band
         self.mean, self.std = mean, std
+        self._band_tables = {}
+
+    def band_of(self, shape):
+        """The host ``ops.BandTable`` of ``consistency_band`` for the periodic domain ``shape``, made once per shape; its refusals begin
+        with the entry point's name."""
+        shape = tuple(int(s) for s in shape)
+        if shape not in self._band_tables:
+            try:
+                ops.band_plan("band_plan", shape)
+                self._band_tables[shape] = ops.band_table(shape, self.cell, tuple(self.band[:3]), *self.band[3:])
+            except ValueError as err:
+                raise ValueError(f"{self.who}: {err}") from None
+        return self._band_tables[shape]
 
     def admit_volume(self, shape):
         """``ValueError`` for a ``VolumeInference`` measurement that is not the volume's ``shape`` divided by the cell."""
         if tuple(s * f for s, f in zip(self.measurement.shape[-3:], self.cell)) != tuple(shape):
-            with _riders(self.slab, self.noise, self.row_noise):
+            with _riders(self.slab, self.noise, self.row_noise, self.band):
                 raise ValueError(f"{self.who}: the consistency measurement {tuple(self.measurement.shape)} times the cell {self.cell} "
                                  f"is not the volume's shape {tuple(shape)}")
 
     def volume(self, device):
         """The measurement of ``VolumeInference`` on the high-res grid, z-scored like the low-res volume, on ``device``: fp32 [D,H,W]
         (``admit_volume`` has checked its shape).  An operator's t = A+ y is made here, once per volume: P 1 = 1, so the z-score of t
-        is the t of the z-scored acquisition."""
+        is the t of the z-scored acquisition; the band's t = A+ y likewise, with the table of this volume."""
         meas = self.measurement.to(device)
-        up = self.launch.cell_replicate(meas, self.cell) if self.op is None else self.launch.tile_backproject(meas.contiguous(), self.op)
+        if self.mode == 'band':
+            table = self.band_of(tuple(s * f for s, f in zip(meas.shape, self.cell))).to(device)
+            up = self.launch.band_backproject(meas.contiguous(), table)
+        else:
+            up = self.launch.cell_replicate(meas, self.cell) if self.op is None else self.launch.tile_backproject(meas.contiguous(), self.op)
         return ((up - self.mean) / self.std).contiguous()
 
     def keywords(self, measurement, std=1., slope=1.):
@@ -240,7 +281,7 @@ class Plan:
         ``measurement`` has taken (``in_units``)."""
         kw = dict(consistency=(measurement, self.cell), consistency_weight=self.weight)
         given = dict(consistency_profile=self.profile, consistency_noise=self.noise, consistency_operator=self.operator,
-                     consistency_row_noise=self.row_noise, consistency_slab=self.slab)
+                     consistency_row_noise=self.row_noise, consistency_slab=self.slab, consistency_band=self.band)
         for name in ('consistency_noise', 'consistency_row_noise'):
             if given[name] is not None:
                 given[name] = in_units(given[name], std, slope)
@@ -255,16 +296,20 @@ class Plan:
 class Chain:
     """What the steps of one chain read, on the device: ``meas`` (the measurement in state space: ``meas_up`` of a sampler, the
     z-scored volume through ``state_space`` of a joint chain), ``table`` (the profile's [2, n], the operator's P, the ``SlabTable`` of
-    this depth, or None), ``tables`` ([T, 2, n, n] of ``consistency_row_noise``, one upload), ``slab`` (the workspace and coefficient
-    volume of the joint slab launches) and ``steps``: per step ``(rung, weight, shrink)`` with rung ``'plain'``, ``'constant'`` or
+    this depth, the ``BandTable`` of this cube or volume, or None), ``tables`` ([T, 2, n, n] of ``consistency_row_noise``, one upload),
+    ``slab`` (the workspace and coefficient volume of the joint slab launches), ``band_ws`` (the five volumes of the joint band
+    launches) and ``steps``: per step ``(rung, weight, shrink)`` with rung ``'plain'``, ``'constant'`` or
     ``'noise'`` (the module docstring), resolved on the fp32 values of the schedule."""
 
     def __init__(self, plan, rows, device, shape=None):
         p, joint, self.launch = plan, shape is not None, plan.launch
         self.mode, self.cell = p.mode, p.cell
         self.meas = p.state_space(p.volume(device)).contiguous() if joint else p.measurement.to(device).float().contiguous()
-        self.table = self.tables = self.slab = None
-        if p.mode == 'slab':
+        self.table = self.tables = self.slab = self.band_ws = None
+        if p.mode == 'band':                                 # the volume's table was made for ``p.volume``; the workspace once per volume
+            self.table = (p.band_of(shape) if joint else p.band_table).to(device)
+            self.band_ws = self.launch.band_workspace(shape, device) if joint else None
+        elif p.mode == 'slab':
             table = ops.slab_profile(p.cell, p.slab, jmax=shape[0] // p.cell[0]) if joint else p.slab_table
             self.table = table.to(device)
             self.slab = self.launch.slab_workspace(shape, p.cell, device) if joint else None
@@ -304,6 +349,8 @@ class Chain:
                 pred = ops.tile_project(pred, self.meas, self.cell, self.table, weight, clamp=clamp)
             elif self.mode == 'slab':
                 pred = ops.slab_project(pred, self.meas, self.cell, self.table, weight, clamp=clamp)
+            elif self.mode == 'band':
+                pred = ops.band_project(pred, self.meas, self.cell, self.table, weight, clamp=clamp)
             elif self.mode == 'profile':
                 pred = ops.cell_project_profile(pred, self.meas, self.cell, self.table, weight, clamp=clamp)
             else:
@@ -315,7 +362,7 @@ class Chain:
         """Step ``i`` of a joint chain: the fused launch of its rung in the place of the family's plain one -- ``head`` = (y, slot,
         taps, x_t), ``tail`` = (lo, hi, clamp_mode, stride) and ``io`` = dict(out=, x0_out=) as every joint step takes them, ``form``
         0 / 1 / 2 the update of ``ops.volume_joint_step`` / ``_multistep`` / ``_multistep_sde`` and ``row`` its coefficients (kx, k0,
-        kn), (kx, k0, kp) or (kx, k0, kp, kn).  The slab takes two launches.  False on a plain rung: nothing was launched."""
+        kn), (kx, k0, kp) or (kx, k0, kp, kn).  The slab takes two calls, the band three.  False on a plain rung: nothing was launched."""
         ops, (rung, weight, shrink) = self.launch, self.steps[i]        # ``ops``: the calling module's from here on
         if rung == 'plain':
             return False
@@ -329,6 +376,11 @@ class Chain:
         elif self.mode == 'slab':                            # the solve runs along the whole depth: the coefficients, then the step
             ops.volume_joint_slab_coeffs(*head[:3], self.meas, self.cell, self.table, *self.slab, *tail)
             ops.volume_joint_consistent_slab_step(*head, x0_prev, self.cell, self.table, *self.slab, weight, *update, **key)
+        elif self.mode == 'band':                            # the projector runs over the whole volume: residual, P, then the step
+            ws = self.band_ws
+            ops.volume_joint_band_residual(*head[:3], self.meas, self.table, ws, *tail)
+            ops.band_apply(ws[2], self.table, ws[3], ws[4])
+            ops.volume_joint_consistent_band_step(*head, x0_prev, self.cell, self.table, ws, weight, *update, **key)
         elif self.mode == 'cell':
             ops.volume_joint_consistent_step(*head, x0_prev, self.meas, self.cell, weight, *update, **key)
         else:                                                # the profile's table or the operator's projector

@@ -14,7 +14,9 @@
 //     blend walk over the windows' x0 predictions, the sampler step and the anchored noise fused (diffusioniqt_amd/inference.py,
 //     joint=True), and the per-sample finish (fill, background reset, statistics over the samples),
 //   * the sigma-space DPM-Solver++ 2M step of the EDM family (ElucidatedImagen(sampler='dpmpp2m'), ODE and SDE), per window batch and
-//     on the joint state.
+//     on the joint state,
+//   * data consistency between the fuse and the update of those chains: cell means, slice profiles, tile operators, overlapping slabs
+//     and the k-space band limit, whose projector is three dense passes of real circulants along the axes (band_pass_kernel).
 // All reductions are two-stage with a fixed order (bit-reproducible).
 #include "common.h"
 
@@ -1460,6 +1462,190 @@ __global__ __launch_bounds__(256) void volume_joint_slab_kernel(const float* __r
     x_next[v] = r;
 }
 
+// ---- data consistency for a k-space band limit: the band operator (ops.band_table) ------------------------------------------------------
+// The measurement keeps a box-shaped, symmetric band of the periodic domain's k-space, so A, A+ and the projector P = A+ A are Kronecker
+// products over the three axes, and every factor is a real circulant: on an axis of N voxels with cell factor f and n = N / f,
+//   projector        P[i][j]  = d[(i - j) mod N]          N x N
+//   measurement      A[s][j]  = a[(s f - j) mod N]        n x N
+//   back-projection  A+[j][s] = g[(s f - j) mod N]        N x n
+// with d, a, g the fp32 tables of the axis (float64 closed forms rounded once, ops.band_table).  The flat table holds, for z, then y,
+// then x, the three tables d, a, g of N floats each.  An axis that is the identity (f = 1, full band) is not `active`: its pass is
+// skipped, its bits stay.  ONE arithmetic definition, fp32 and kept from contraction, for every pass:
+//   out[i] = acc after  acc = 0;  acc = fmaf(T[idx(i, j)], v[j], acc) over ASCENDING j,
+// idx(i, j) = (i si + j sj) mod N with (si, sj) = (1, -1) for d, (f, -1) for a and (-1, f) for g (there j runs over the n rows).
+// The passes run z, y, x for P and A and x, y, z for A+ (the small axes first).
+//
+// band_pass_kernel: one pass along one axis of an array seen as [O][Nin][I] -> [O][Nout][I].  A column is one (o, k); a block of (64, 4)
+// owns BAND_C = 64 columns, one per lane, and BAND_I = 4 BAND_R = 32 outputs, wave w the outputs i0 + w BAND_R .. + BAND_R - 1, so the
+// table value of an FMA is uniform over a wave (an LDS broadcast) and every thread keeps BAND_R accumulators in registers.  The input
+// line goes through LDS in panels of BAND_J = 64 values of j for the 64 columns, rows padded to 65 floats: loaded with the lanes along
+// the columns (I > 1: the columns of one o are consecutive floats) or, LINES (I == 1, the x pass), with the lanes along j and stored
+// transposed, so both the global read and the LDS accesses are conflict-free; LINES also stores its outputs through the same
+// transpose.  The table sits doubled in LDS behind BAND_PAD floats of its own tail and before as many of its head:
+// T2[BAND_PAD + k] = T[k mod N] for -BAND_PAD <= k < 2 N + BAND_PAD, so no pass takes a remainder in its loop.  SLIDE (the projector,
+// si = 1, sj = -1): j is unrolled by BAND_R and the 2 BAND_R - 1 table values a block of j needs for the thread's BAND_R outputs
+// sit in registers -- 15 table reads per 64 FMAs in place of 64; the rows of a panel past Nin hold zeros and the outputs past Nout
+// read the padding, which changes no bit of what is stored (acc + T 0 = acc, and acc is never -0).  The other passes clamp the output
+// index of the table read and stop at Nin.  Load(e) gives element e of the input array, Store(e, value) takes element e of the output.
+constexpr int BAND_C = 64, BAND_R = 8, BAND_I = 4 * BAND_R, BAND_J = 64, BAND_PAD = 64, BAND_MAX_N = 512;
+struct BandLoad {
+    const float* __restrict__ x;
+    __device__ __forceinline__ float operator()(size_t e) const { return x[e]; }
+};
+struct BandStore {
+    float* __restrict__ out;
+    __device__ __forceinline__ void operator()(size_t e, float v) const { out[e] = v; }
+};
+// The loader of a projection's first pass: the residual t - clamp(x0); the storer of its last: out = fmaf(w, c, clamp(x0)), which reads
+// x0 at the element it writes and nowhere else (out may alias x0 once the pass itself reads the workspace).
+struct BandResidualLoad {
+    const float* __restrict__ t;
+    const float* x0;
+    ProjectClamp clamp;
+    __device__ __forceinline__ float operator()(size_t e) const {
+#pragma clang fp contract(off)
+        return t[e] - clamp(x0[e]);
+    }
+};
+struct BandShiftStore {
+    const float* x0;
+    float* out;
+    float w;
+    ProjectClamp clamp;
+    __device__ __forceinline__ void operator()(size_t e, float c) const { out[e] = fmaf(w, c, clamp(x0[e])); }
+};
+template <bool LINES, bool SLIDE, class Load, class Store>
+__global__ __launch_bounds__(256) void band_pass_kernel(const float* __restrict__ T, size_t C, int I, int Nin, int Nout, int N, int si,
+                                                        int sj, Load load, Store store) {
+    extern __shared__ float sh[];                      // T2 [2 N + 2 BAND_PAD], panel [BAND_J][BAND_C + 1]
+    float* T2 = sh;
+    float* panel = sh + 2 * N + 2 * BAND_PAD;
+    constexpr int LD = BAND_C + 1;
+    const int l = threadIdx.x, w = threadIdx.y;
+    for (int e = w * 64 + l; e < 2 * N + 2 * BAND_PAD; e += 256) T2[e] = T[((e - BAND_PAD) % N + N) % N];
+    const size_t c0 = (size_t)blockIdx.x * BAND_C, c = c0 + l;
+    const int i0 = blockIdx.y * BAND_I + w * BAND_R;
+    const bool cin = c < C;
+    const size_t o = LINES ? c : c / (size_t)I, k = LINES ? 0 : c - o * (size_t)I;
+    const size_t inbase = o * (size_t)Nin * I + k, outbase = o * (size_t)Nout * I + k;
+    float acc[BAND_R];
+    int ib[BAND_R];
+#pragma unroll
+    for (int r = 0; r < BAND_R; ++r) {
+        acc[r] = 0.f;
+        ib[r] = (SLIDE ? i0 + r : min(i0 + r, Nout - 1)) * si + N + BAND_PAD;
+    }
+    for (int j0 = 0; j0 < Nin; j0 += BAND_J) {
+        __syncthreads();                               // the panel of the chunk before is read; the first: nothing
+        if (LINES) {
+            const int j = j0 + l;
+            for (int cc = w; cc < BAND_C; cc += 4) {
+                const size_t cl = c0 + cc;
+                panel[l * LD + cc] = cl < C && j < Nin ? load(cl * (size_t)Nin + j) : 0.f;
+            }
+        } else {
+            for (int jj = w; jj < BAND_J; jj += 4) {
+                const int j = j0 + jj;
+                panel[jj * LD + l] = cin && j < Nin ? load(inbase + (size_t)j * I) : 0.f;
+            }
+        }
+        __syncthreads();                               // also: T2 is written
+        const int jn = min(BAND_J, Nin - j0);
+        if (SLIDE) {
+            for (int jb = 0; jb < jn; jb += BAND_R) {
+                float win[2 * BAND_R - 1];             // win[q] = T2[ib[0] - (j0 + jb) + q - (BAND_R - 1)]: offsets r - u of output r, step u
+                const float* tw = T2 + ib[0] - (j0 + jb) - (BAND_R - 1);
+#pragma unroll
+                for (int q = 0; q < 2 * BAND_R - 1; ++q) win[q] = tw[q];
+#pragma unroll
+                for (int u = 0; u < BAND_R; ++u) {
+                    const float v = panel[(jb + u) * LD + l];
+#pragma unroll
+                    for (int r = 0; r < BAND_R; ++r) acc[r] = fmaf(win[r - u + BAND_R - 1], v, acc[r]);
+                }
+            }
+        } else {
+            for (int jj = 0; jj < jn; ++jj) {
+                const float v = panel[jj * LD + l];
+                const int js = (j0 + jj) * sj;
+#pragma unroll
+                for (int r = 0; r < BAND_R; ++r) acc[r] = fmaf(T2[ib[r] + js], v, acc[r]);
+            }
+        }
+    }
+    if (LINES) {
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < BAND_R; ++r) panel[(w * BAND_R + r) * LD + l] = acc[r];
+        __syncthreads();
+        const int i = blockIdx.y * BAND_I + l;
+        if (l < BAND_I && i < Nout)
+            for (int cc = w; cc < BAND_C; cc += 4) {
+                const size_t cl = c0 + cc;
+                if (cl < C) store(cl * (size_t)Nout + i, panel[l * LD + cc]);
+            }
+    } else if (cin) {
+#pragma unroll
+        for (int r = 0; r < BAND_R; ++r)
+            if (i0 + r < Nout) store(outbase + (size_t)(i0 + r) * I, acc[r]);
+    }
+}
+// A projection with ONE active axis: its only pass reads x0 along whole lines, so it stores c in the workspace and this kernel forms
+// out = fmaf(w, c, clamp(x0)) per element -- BandShiftStore's expression -- where out may alias x0.
+__global__ __launch_bounds__(256) void band_shift_kernel(const float* x0, const float* __restrict__ c, float* out, size_t total, float w,
+                                                         ProjectClamp clamp) {
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e < total) BandShiftStore{x0, out, w, clamp}(e, c[e]);
+}
+// FIRST launch of a joint step (diqt_volume_joint_band_residual): the fuse of volume_joint_linear_kernel at every voxel, then three
+// volumes: a = the fused clamped prediction (0 where no kept window covers), the covered flag (1 / 0) and r = t - a (0 where
+// uncovered: the measurement is believed where nothing was generated).
+__global__ __launch_bounds__(256) void volume_joint_band_residual_kernel(const float* __restrict__ y, const int* __restrict__ slot,
+                                                                         const float* __restrict__ taps, const float* __restrict__ t,
+                                                                         float* __restrict__ a_out, float* __restrict__ cov_out,
+                                                                         float* __restrict__ r_out, int N, int D, int H, int W, int P,
+                                                                         int stride, int G0, int G1, int G2, float lo, float hi,
+                                                                         int clamp_mode) {
+#pragma clang fp contract(off)
+    extern __shared__ float tp[];                      // [P]
+    const Voxel p = walk_prologue(tp, taps, P, true, H, W);
+    if (!p.inside) return;
+    const Fused f = joint_fuse(y, slot, taps, tp, N, P, stride, G0, G1, G2, p, StepClamp{lo, hi, clamp_mode});
+    const float tv = t[p.v];
+    const bool cov = f.covered();
+    const float a = cov ? f.x0() : 0.f;
+    a_out[p.v] = a;
+    cov_out[p.v] = cov ? 1.f : 0.f;
+    r_out[p.v] = cov ? tv - a : 0.f;
+}
+// LAST launch of a joint step (diqt_volume_joint_consistent_band_step): volume_joint_linear_kernel's three update forms on
+// x0' = fmaf(w, c, a), with a, the covered flag and c = P r read from the workspace -- the windows are not walked again.  An uncovered
+// voxel keeps x_t and gets x0_out = 0; normals and draw numbering are the linear kernel's.  Every thread reads only its own voxel of
+// x_t / x0_prev, then writes it: x_next may alias x_t and x0_out may alias x0_prev.
+__global__ __launch_bounds__(256) void volume_joint_band_kernel(const float* x_t, const float* x0_prev, const float* __restrict__ a,
+                                                                const float* __restrict__ cov, const float* __restrict__ c, float* x_next,
+                                                                float* x0_out, int H, int W, float w, float kx, float k0, float kp,
+                                                                float kn, int third_is_normal, unsigned key0, unsigned key1,
+                                                                unsigned draw, unsigned sample) {
+    const Voxel p = block_voxel(H, W);
+    if (!p.inside) return;
+    const size_t v = p.v;
+    const unsigned v0 = (unsigned)v, v1 = (unsigned)((unsigned long long)v >> 32);
+    const float xt = x_t[v];
+    if (cov[v] == 0.f) {
+        x_next[v] = xt;
+        x0_out[v] = 0.f;
+        return;
+    }
+    const float x0 = fmaf(w, c[v], a[v]);
+    const float prev = x0_prev ? x0_prev[v] : 0.f;
+    float n = 0.f;
+    if (kn != 0.f) n = philox_normal(philox4x32_10(v0, v1, draw, sample, key0, key1));
+    const float r = third_is_normal ? sampler_update(kx, xt, k0, x0, kn, n) : sampler_update_sde(kx, xt, k0, x0, kp, prev, kn, n);
+    x0_out[v] = x0;
+    x_next[v] = r;
+}
+
 // The stochastic Heun sampler of the EDM family (elucidated_imagen.py:382-532) on the same state: a churn, a predictor and a corrector
 // per step, two U-Net evaluations, so the state is three volumes -- xh = images_hat, xn = images_next, x0 = the fused prediction (the
 // one self-conditioning reads) -- and the launch takes a `phase`, uniform over the grid:
@@ -2411,6 +2597,216 @@ extern "C" int diqt_volume_joint_consistent_slab_step(const float* y, const int*
     hipLaunchKernelGGL(volume_joint_slab_kernel, g.grid, dim3(64, 4), g.lds, STREAM, y, slot, taps, x_t, first ? nullptr : x0_prev, table,
                        coef, workspace + 2 * planes, x_next, x0_out, N, D, H, W, P, stride, G0, G1, G2, Slab{fz, fy, fx, r, jmax}, weight,
                        kx, k0, first ? 0.f : kp, noisy ? kn : 0.f, lo, hi, clamp_mode, first ? 1 : 0, (unsigned)seed,
+                       (unsigned)(seed >> 32), draw, sample);
+    return check_launch(who);
+}
+
+// ---- the band operator's entries ----------------------------------------------------------------------------------------------------------
+// The LDS of one band_pass_kernel launch on an axis of N voxels: the padded doubled table and one panel.
+static size_t band_lds(int N) { return ((size_t)2 * N + 2 * BAND_PAD + (size_t)BAND_J * (BAND_C + 1)) * sizeof(float); }
+// The domain, the cell and the active axes of the band entries: every axis 1 .. BAND_MAX_N voxels and a multiple of its factor, `active`
+// a mask of bits 0 (z), 1 (y), 2 (x) with at least one set, and an axis outside it has factor 1.
+static int band_ok(const char* who, const int* n, const int* f, int active) {
+    DIQT_REQUIRE(active >= 1 && active <= 7, DIQT_E_UNSUPPORTED, "%s: active axes %d (a mask of z = 1, y = 2, x = 4, not empty)", who, active);
+    for (int a = 0; a < 3; ++a) {
+        DIQT_REQUIRE(f[a] >= 1 && (((active >> a) & 1) || f[a] == 1), DIQT_E_UNSUPPORTED, "%s: axis %d has factor %d and is not active", who,
+                     a, f[a]);
+        DIQT_REQUIRE(n[a] > 0 && n[a] % f[a] == 0, DIQT_E_SHAPE, "%s: the factor %d does not divide the %d voxels of axis %d", who, f[a], n[a],
+                     a);
+        DIQT_REQUIRE(n[a] <= BAND_MAX_N, DIQT_E_SHAPE, "%s: axis %d has %d voxels, above the %d a band pass takes", who, a, n[a], BAND_MAX_N);
+        DIQT_REQUIRE(band_lds(n[a]) <= 65536, DIQT_E_SHAPE, "%s: axis %d needs %zu bytes of LDS", who, a, band_lds(n[a]));
+    }
+    return DIQT_OK;
+}
+// One pass: the array is [O][Nin][I] -> [O][Nout][I], T the table of the axis (N floats).
+template <class Load, class Store>
+static int band_pass(const char* who, const float* T, size_t O, int Nin, int Nout, size_t I, int N, int si, int sj, bool slide, Load load,
+                     Store store, void* stream) {
+    const size_t C = O * I, bx = (C + BAND_C - 1) / BAND_C;
+    DIQT_REQUIRE(bx <= 0x7fffffffu && I <= 0x7fffffffu, DIQT_E_SHAPE, "%s: more than 2^31 - 1 blocks", who);
+    const dim3 grid((unsigned)bx, (Nout + BAND_I - 1) / BAND_I);
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(64, 4), band_lds(N), STREAM, T, C, (int)I, Nin, Nout, N, si, sj, load, store);
+    };
+    if (I == 1)
+        slide ? launch(band_pass_kernel<true, true, Load, Store>) : launch(band_pass_kernel<true, false, Load, Store>);
+    else
+        slide ? launch(band_pass_kernel<false, true, Load, Store>) : launch(band_pass_kernel<false, false, Load, Store>);
+    return check_launch(who);
+}
+// The table of axis `a` in the flat table: 0 = d, 1 = a, 2 = g.
+static const float* band_axis_table(const float* table, const int* n, int a, int which) {
+    size_t off = 0;
+    for (int b = 0; b < a; ++b) off += 3 * (size_t)n[b];
+    return table + off + (size_t)which * n[a];
+}
+// The rectangular passes of A (`forward`: z, y, x, each axis N -> N / f) or A+ (x, y, z, each N / f -> N) from `x` to `out` through the two
+// halves of the workspace.  `plan_only`: only `need`, the floats of workspace the passes use, is computed.
+static int band_rect(const char* who, bool forward, const float* x, const float* table, float* out, float* workspace,
+                     size_t workspace_floats, const int* n, const int* f, int active, bool plan_only, size_t& need, void* stream) {
+    int dims[3], order[3], passes = 0;
+    for (int a = 0; a < 3; ++a) {
+        dims[a] = forward ? n[a] : n[a] / f[a];
+        if ((active >> a) & 1) ++passes;
+    }
+    for (int p = 0; p < 3; ++p) order[p] = forward ? p : 2 - p;
+    size_t half = 0;
+    for (int round = 0; round < 2; ++round) {          // 0: the size of an intermediate; 1: the launches
+        if (round == 1) {
+            need = passes > 1 ? 2 * half : 0;
+            if (plan_only) return DIQT_OK;
+            DIQT_REQUIRE(passes == 1 || (workspace && workspace_floats >= need), DIQT_E_SHAPE, "%s: the workspace holds %zu floats, %zu needed",
+                         who, workspace ? workspace_floats : (size_t)0, need);
+            for (int a = 0; a < 3; ++a) dims[a] = forward ? n[a] : n[a] / f[a];
+        }
+        const float* src = x;
+        for (int p = 0, done = 0; p < 3; ++p) {
+            const int a = order[p];
+            if (!((active >> a) & 1)) continue;
+            const int Nin = dims[a], Nout = forward ? n[a] / f[a] : n[a];
+            dims[a] = Nout;
+            const size_t total = (size_t)dims[0] * dims[1] * dims[2];
+            ++done;
+            if (round == 0) {
+                if (done < passes) half = total > half ? total : half;
+                continue;
+            }
+            float* dst = done == passes ? out : workspace + (done % 2) * half;
+            size_t O = 1, I = 1;
+            for (int b = 0; b < a; ++b) O *= dims[b];
+            for (int b = a + 1; b < 3; ++b) I *= dims[b];
+            int rc = band_pass(who, band_axis_table(table, n, a, forward ? 1 : 2), O, Nin, Nout, I, n[a], forward ? f[a] : -1,
+                               forward ? -1 : f[a], false, BandLoad{src}, BandStore{dst}, stream);
+            if (rc) return rc;
+            src = dst;
+        }
+    }
+    return DIQT_OK;
+}
+
+extern "C" int diqt_band_measure(const float* x, const float* table, float* out, float* workspace, size_t workspace_floats, int D, int H,
+                                 int W, int fz, int fy, int fx, int active, void* stream) {
+    DIQT_REQUIRE(x && table && out, DIQT_E_ALIGN, "band_measure: null pointer");
+    const int n[3] = {D, H, W}, f[3] = {fz, fy, fx};
+    int rc = band_ok("band_measure", n, f, active);
+    if (rc) return rc;
+    size_t need;
+    return band_rect("band_measure", true, x, table, out, workspace, workspace_floats, n, f, active, false, need, stream);
+}
+
+extern "C" int diqt_band_backproject(const float* y, const float* table, float* out, float* workspace, size_t workspace_floats, int D,
+                                     int H, int W, int fz, int fy, int fx, int active, void* stream) {
+    DIQT_REQUIRE(y && table && out, DIQT_E_ALIGN, "band_backproject: null pointer");
+    const int n[3] = {D, H, W}, f[3] = {fz, fy, fx};
+    int rc = band_ok("band_backproject", n, f, active);
+    if (rc) return rc;
+    size_t need;
+    return band_rect("band_backproject", false, y, table, out, workspace, workspace_floats, n, f, active, false, need, stream);
+}
+
+// The projector passes z, y, x over `batch` domains [n0][n1][n2]: x -> out through `ws0` / `ws1` (each batch n0 n1 n2 floats; ws1 is
+// looked at only with three active axes).  `project`: the first loader forms t - clamp(x0) from (x = x0, t) and the result is
+// out = fmaf(w, c, clamp(x0)), where out may alias x0: formed in the last storer, or with one active axis by band_shift_kernel.
+static int band_square(const char* who, const float* x, const float* t, const float* table, float* out, float* ws0, float* ws1,
+                       size_t batch, const int* n, int active, bool project, float w, ProjectClamp clamp, void* stream) {
+    int passes = 0, done = 0;
+    for (int a = 0; a < 3; ++a) passes += (active >> a) & 1;
+    const size_t total = batch * n[0] * n[1] * n[2];
+    // the chain of buffers: project x0 -> ws0 [-> ws1] -> out (one pass: x0 -> ws0, then the shift); apply x -> [out -> ws0 ->] out
+    const float* src = x;
+    for (int a = 0; a < 3; ++a) {
+        if (!((active >> a) & 1)) continue;
+        ++done;
+        const bool first = done == 1, last = done == passes;
+        float* dst = project ? (last && passes > 1 ? out : done == 1 ? ws0 : ws1) : (last ? out : passes - done == 2 ? out : ws0);
+        size_t O = batch, I = 1;
+        for (int b = 0; b < a; ++b) O *= n[b];
+        for (int b = a + 1; b < 3; ++b) I *= n[b];
+        const float* T = band_axis_table(table, n, a, 0);
+        int rc;
+        if (project && first)
+            rc = band_pass(who, T, O, n[a], n[a], I, n[a], 1, -1, true, BandResidualLoad{t, x, clamp}, BandStore{dst}, stream);
+        else if (project && last)
+            rc = band_pass(who, T, O, n[a], n[a], I, n[a], 1, -1, true, BandLoad{src}, BandShiftStore{x, out, w, clamp}, stream);
+        else
+            rc = band_pass(who, T, O, n[a], n[a], I, n[a], 1, -1, true, BandLoad{src}, BandStore{dst}, stream);
+        if (rc) return rc;
+        src = dst;
+    }
+    if (project && passes == 1) {
+        DIQT_REQUIRE((total + 255) / 256 <= 0x7fffffffu, DIQT_E_SHAPE, "%s: more than 2^31 - 1 blocks", who);
+        hipLaunchKernelGGL(band_shift_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, STREAM, x, ws0, out, total, w, clamp);
+        return check_launch(who);
+    }
+    return DIQT_OK;
+}
+
+extern "C" int diqt_band_project(const float* x0, const float* target, const float* table, float* workspace, float* out, size_t cubes,
+                                 int P, int fz, int fy, int fx, size_t workspace_floats, int active, float weight, float lo, float hi,
+                                 int clamp_mode, void* stream) {
+    const char* who = "band_project";
+    DIQT_REQUIRE(x0 && target && table && workspace && out, DIQT_E_ALIGN, "%s: null pointer", who);
+    int rc = cell_ok(who, fz, fy, fx, weight);
+    if (rc) return rc;
+    DIQT_REQUIRE(clamp_mode >= 0 && clamp_mode <= 2, DIQT_E_UNSUPPORTED, "%s: clamp_mode %d (0 = min, 1 = box, 2 = none)", who, clamp_mode);
+    const int n[3] = {P, P, P}, f[3] = {fz, fy, fx};
+    DIQT_REQUIRE(cubes > 0 && P > 0, DIQT_E_SHAPE, "%s: %zu cubes of edge %d", who, cubes, P);
+    rc = band_ok(who, n, f, active);
+    if (rc) return rc;
+    const size_t total = cubes * (size_t)P * P * P;
+    DIQT_REQUIRE(workspace_floats >= 2 * total, DIQT_E_SHAPE, "%s: the workspace holds %zu floats, %zu needed", who, workspace_floats,
+                 2 * total);
+    DIQT_REQUIRE(workspace != out && workspace != x0 && workspace + total != out && workspace + total != x0, DIQT_E_ALIGN,
+                 "%s: the workspace may alias neither x0 nor out", who);
+    return band_square(who, x0, target, table, out, workspace, workspace + total, cubes, n, active, true, weight,
+                       ProjectClamp{lo, hi, clamp_mode}, stream);
+}
+
+extern "C" int diqt_band_apply(const float* x, const float* table, float* out, float* workspace, size_t workspace_floats, int D, int H,
+                               int W, int active, void* stream) {
+    const char* who = "band_apply";
+    DIQT_REQUIRE(x && table && out && workspace, DIQT_E_ALIGN, "%s: null pointer", who);
+    DIQT_REQUIRE(x != out && x != workspace && out != workspace, DIQT_E_ALIGN, "%s: x, out and the workspace must be three volumes", who);
+    const int n[3] = {D, H, W}, f[3] = {1, 1, 1};
+    int rc = band_ok(who, n, f, 7);                    // the shape rules; the factors are not this entry's
+    if (rc) return rc;
+    DIQT_REQUIRE(active >= 1 && active <= 7, DIQT_E_UNSUPPORTED, "%s: active axes %d (a mask of z = 1, y = 2, x = 4, not empty)", who, active);
+    const size_t total = (size_t)D * H * W;
+    DIQT_REQUIRE(workspace_floats >= total, DIQT_E_SHAPE, "%s: the workspace holds %zu floats, %zu needed", who, workspace_floats, total);
+    return band_square(who, x, nullptr, table, out, workspace, nullptr, 1, n, active, false, 0.f, ProjectClamp{0.f, 0.f, 2}, stream);
+}
+
+extern "C" int diqt_volume_joint_band_residual(const float* y, const int* slot, const float* taps, const float* target, float* a_out,
+                                               float* covered_out, float* r_out, int N, int D, int H, int W, int P, int stride, int G0,
+                                               int G1, int G2, float lo, float hi, int clamp_mode, void* stream) {
+    const char* who = "volume_joint_band_residual";
+    DIQT_REQUIRE(target && a_out && covered_out && r_out && slot && taps && (y || N == 0), DIQT_E_ALIGN, "%s: null pointer", who);
+    JointGrid g;
+    int rc = joint_launch_plan(who, a_out, true, true, N, D, H, W, P, stride, G0, G1, G2, clamp_mode, g);
+    if (rc) return rc;
+    hipLaunchKernelGGL(volume_joint_band_residual_kernel, g.grid, dim3(64, 4), g.lds, STREAM, y, slot, taps, target, a_out, covered_out,
+                       r_out, N, D, H, W, P, stride, G0, G1, G2, lo, hi, clamp_mode);
+    return check_launch(who);
+}
+
+extern "C" int diqt_volume_joint_consistent_band_step(const float* y, const int* slot, const float* taps, const float* x_t,
+                                                      const float* x0_prev, const float* a, const float* covered, const float* c,
+                                                      float* x_next, float* x0_out, int form, int N, int D, int H, int W, int P,
+                                                      int stride, int G0, int G1, int G2, int fz, int fy, int fx, float weight, float kx,
+                                                      float k0, float kp, float kn, float lo, float hi, int clamp_mode,
+                                                      unsigned long long seed, unsigned draw, unsigned sample, void* stream) {
+    const char* who = "volume_joint_consistent_band_step";
+    DIQT_REQUIRE(x_t && a && covered && c && x_next && x0_out, DIQT_E_ALIGN, "%s: null pointer", who);
+    DIQT_REQUIRE(form >= 0 && form <= 2, DIQT_E_UNSUPPORTED, "%s: form %d (0 = first order, 1 = multistep, 2 = multistep with noise)", who,
+                 form);
+    int rc = cell_ok(who, fz, fy, fx, weight);
+    if (rc) return rc;
+    JointGrid g;                                       // the windows are not walked: y, slot, taps, the lattice and the clamp are not looked at
+    rc = joint_launch_plan(who, x_next, false, true, N, D, H, W, P, stride, G0, G1, G2, clamp_mode, g);
+    if (rc) return rc;
+    const bool first = form == 0, noisy = form != 1;
+    hipLaunchKernelGGL(volume_joint_band_kernel, g.grid, dim3(64, 4), 0, STREAM, x_t, first ? nullptr : x0_prev, a, covered, c, x_next,
+                       x0_out, H, W, weight, kx, k0, first ? 0.f : kp, noisy ? kn : 0.f, first ? 1 : 0, (unsigned)seed,
                        (unsigned)(seed >> 32), draw, sample);
     return check_launch(who);
 }

@@ -420,7 +420,7 @@ class ElucidatedImagen(nn.Module):
                         inpaint_images=None, inpaint_masks=None, inpaint_resample_times=5, init_images=None,
                         skip_steps=None, sigma_min=None, sigma_max=None, noise=None, sampler='heun', sample_steps=None, eta=0.,
                         consistency=None, consistency_weight=1., consistency_profile=None, consistency_noise=None,
-                        consistency_operator=None, consistency_row_noise=None, consistency_slab=None, **kwargs):
+                        consistency_operator=None, consistency_row_noise=None, consistency_slab=None, consistency_band=None, **kwargs):
         """Stochastic Heun sampler (:382-532).  ``noise``: optional injected list [init, step_0, ...], or a callable
         ``noise(shape) -> fp32 device tensor`` whose successive calls are those draws (one ``eps`` per step, also when gamma is 0).
 
@@ -437,7 +437,8 @@ class ElucidatedImagen(nn.Module):
         before anything touches the device.
 
         ``consistency=(meas_up, cell)`` with ``consistency_weight`` (``sampler='dpmpp2m'`` only), ``consistency_profile``,
-        ``consistency_noise``, ``consistency_operator``, ``consistency_row_noise``, ``consistency_slab``: data-consistent sampling
+        ``consistency_noise``, ``consistency_operator``, ``consistency_row_noise``, ``consistency_slab``, ``consistency_band``:
+        data-consistent sampling
         (DDNM / DDNM+); the keywords, their rules and the launch a step takes are stated once, in ``consistency.py``.  ``meas_up``
         [B,C,P,P,P], the measurement replicated onto the high-res grid (``ops.cell_replicate``; with an operator t = A+ y,
         ``ops.tile_backproject``), and the noise deviations arrive in state space here (``sample`` takes them in the units it
@@ -448,7 +449,8 @@ class ElucidatedImagen(nn.Module):
         self._check_sampler_args(sampler, sample_steps, skip_steps, eta)
         has_inpainting = self._check_inpaint_args(sampler, inpaint_images, inpaint_masks, inpaint_resample_times)
         plan = consistency_plan('one_unet_sample', ops, consistency, consistency_weight, consistency_profile, consistency_noise,
-                                consistency_operator, consistency_row_noise, consistency_slab, shape=shape, stochastic=eta != 0,
+                                consistency_operator, consistency_row_noise, consistency_slab, consistency_band, shape=shape,
+                                stochastic=eta != 0,
                                 has_inpainting=has_inpainting, init_images=init_images, skip_steps=skip_steps, sampler=sampler)
         if sampler == 'dpmpp2m':
             return self._dpmpp2m_sample(unet, shape, unet_number=unet_number, clamp=clamp, dynamic_threshold=dynamic_threshold,
@@ -605,7 +607,7 @@ class ElucidatedImagen(nn.Module):
                stop_at_unet_number=None, return_all_unet_outputs=False, return_pil_images=False, use_tqdm=True, device=None,
                noise=None, sampler='heun', sample_steps=None, eta=0., consistency=None, consistency_weight=1.,
                consistency_profile=None, consistency_noise=None, consistency_operator=None, consistency_row_noise=None,
-               consistency_slab=None):
+               consistency_slab=None, consistency_band=None):
         """:536-702.  ``noise``: optional injected list [lowres_noise, init, step_0, ...] per sampled unet (tests), or -- when exactly
         one U-Net is sampled -- a callable ``noise(shape) -> fp32 device tensor`` whose successive calls are those draws in that order
         (``inference.AnchoredNoise.source``: call k is draw k of the volume-anchored field).
@@ -622,8 +624,9 @@ class ElucidatedImagen(nn.Module):
         images / masks alone, inpainting with 'dpmpp2m', or a count that is not a positive integer: ``ValueError`` naming "inpaint",
         before anything touches the device.
 
-        ``consistency=(meas_up, cell)`` / ``consistency_weight`` and the five keywords that ride on it (``consistency_profile``,
-        ``consistency_noise``, ``consistency_operator``, ``consistency_row_noise``, ``consistency_slab``): ``one_unet_sample``'s, for
+        ``consistency=(meas_up, cell)`` / ``consistency_weight`` and the six keywords that ride on it (``consistency_profile``,
+        ``consistency_noise``, ``consistency_operator``, ``consistency_row_noise``, ``consistency_slab``, ``consistency_band``):
+        ``one_unet_sample``'s, for
         every sampled U-Net (so they must generate one size).  ``meas_up`` [B,C,P,P,P] (with an operator t = A+ y) is in the units
         this returns -- ``normalize_img`` takes it to state space, as it does ``inpaint_images`` -- and the noise deviations are in
         its units as passed here: they are multiplied by the slope of ``normalize_img``.  ``consistency.py`` states the keywords and
@@ -640,7 +643,7 @@ class ElucidatedImagen(nn.Module):
         for n in range(start_at_unet_number, default(stop_at_unet_number, len(self.unets)) + 1):      # every sampled U-Net's rules, up front
             plan = consistency_plan(
                 'sample', ops, consistency, consistency_weight, consistency_profile, consistency_noise, consistency_operator,
-                consistency_row_noise, consistency_slab, stochastic=etas[n - 1] != 0, has_inpainting=exists(inpaint_images),
+                consistency_row_noise, consistency_slab, consistency_band, stochastic=etas[n - 1] != 0, has_inpainting=exists(inpaint_images),
                 shape=exists(frames) and (batch_size, self.channels, *frames[n - 1], self.image_sizes[n - 1], self.image_sizes[n - 1]),
                 init_images=cast_tuple(init_images, len(self.unets))[n - 1], skip_steps=cast_tuple(skip_steps, len(self.unets))[n - 1],
                 sampler=samplers[n - 1])

@@ -1494,7 +1494,8 @@ class Imagen(nn.Module):
                       inpaint_masks=None, inpaint_resample_times=5, init_images=None, skip_steps=None, cond_scale=1,
                       pred_objective='noise', dynamic_threshold=True, use_tqdm=True, noise=None, sampler='ddpm',
                       sample_steps=None, eta=0.0, consistency=None, consistency_weight=1.0, consistency_profile=None,
-                      consistency_noise=None, consistency_operator=None, consistency_row_noise=None, consistency_slab=None):
+                      consistency_noise=None, consistency_operator=None, consistency_row_noise=None, consistency_slab=None,
+                      consistency_band=None):
         """Ancestral sampler (:2059-2160).  Per step: one U-Net eval (HIP) + ONE fused posterior-step kernel;
         the per-step coefficients for all steps are computed on the host up front.  ``noise`` (optional) is a list
         [init, step_0, ...] of injected tensors with the reference's draw order (:2080, :2051), or a callable
@@ -1515,7 +1516,8 @@ class Imagen(nn.Module):
         ``ops.ddpm_inpaint_paste`` launch.  ``inpaint_draws`` counts the draws.
 
         ``consistency=(meas_up, cell)`` with ``consistency_weight`` (any sampler), ``consistency_profile``, ``consistency_noise``,
-        ``consistency_operator``, ``consistency_row_noise``, ``consistency_slab``: data-consistent sampling (DDNM / DDNM+); the keywords,
+        ``consistency_operator``, ``consistency_row_noise``, ``consistency_slab``, ``consistency_band``: data-consistent sampling (DDNM /
+        DDNM+); the keywords,
         their rules and the launch a step takes are stated once, in ``consistency.py``.  ``meas_up`` [B,C,P,P,P] is the measurement
         replicated onto the high-res grid (``ops.cell_replicate``; with an operator t = A+ y, ``ops.tile_backproject``), in state space
         like ``inpaint_images``, and the noise deviations are in its units.  Per step the x0 prediction (thresholded, if configured)
@@ -1530,7 +1532,7 @@ class Imagen(nn.Module):
         has_inpainting = exists(inpaint_images) and exists(inpaint_masks)                  # (:2090-2091)
         self._check_sampler_args(sampler, sample_steps, skip_steps, eta, has_inpainting)
         plan = consistency_plan('p_sample_loop', ops, consistency, consistency_weight, consistency_profile, consistency_noise,
-                                consistency_operator, consistency_row_noise, consistency_slab, shape=shape,
+                                consistency_operator, consistency_row_noise, consistency_slab, consistency_band, shape=shape,
                                 stochastic=not (sampler == 'dpmpp2m' or (sampler == 'ddim' and eta == 0)), has_inpainting=has_inpainting,
                                 init_images=init_images, skip_steps=skip_steps)
         device = self.device
@@ -1608,12 +1610,13 @@ class Imagen(nn.Module):
                stop_at_unet_number=None, return_all_outputs=False, return_all_unet_outputs=None, return_pil_images=False,
                device=None, use_tqdm=True, noise=None, sampler='ddpm', sample_steps=None, eta=0.0, consistency=None,
                consistency_weight=1.0, consistency_profile=None, consistency_noise=None, consistency_operator=None,
-               consistency_row_noise=None, consistency_slab=None):
+               consistency_row_noise=None, consistency_slab=None, consistency_band=None):
         """imagen_pytorch3D.py:2165-2274 -> (img, [noisy per step], [x0 per step]).  Accepts both spellings
         ``return_all_outputs`` / ``return_all_unet_outputs`` (test.py:182 uses the latter).  ``sampler`` / ``sample_steps`` / ``eta``
         (one value, or one per U-Net like ``skip_steps``) and the list or callable ``noise``: see ``p_sample_loop``, as for
-        ``consistency=(meas_up, cell)`` / ``consistency_weight`` and the five keywords that ride on it (``consistency_profile``,
-        ``consistency_noise``, ``consistency_operator``, ``consistency_row_noise``, ``consistency_slab``; the deviations in the units
+        ``consistency=(meas_up, cell)`` / ``consistency_weight`` and the six keywords that ride on it (``consistency_profile``,
+        ``consistency_noise``, ``consistency_operator``, ``consistency_row_noise``, ``consistency_slab``, ``consistency_band``; the
+        deviations in the units
         of ``meas_up`` as passed), which every sampled U-Net gets (so they must generate one size).  ``consistency.py`` states them and
         their refusals: ``ValueError`` naming the keyword at fault and the one that rides on it, raised here for every sampled U-Net
         before anything touches the device."""
@@ -1626,7 +1629,8 @@ class Imagen(nn.Module):
             self._check_sampler_args(*args, exists(inpaint_images) and exists(inpaint_masks))
         for n in range(start_at_unet_number, default(stop_at_unet_number, num_unets) + 1):      # every sampled U-Net's rules, up front
             consistency_plan('sample', ops, consistency, consistency_weight, consistency_profile, consistency_noise, consistency_operator,
-                             consistency_row_noise, consistency_slab, shape=(batch_size, self.channels) + (self.image_sizes[n - 1],) * 3,
+                             consistency_row_noise, consistency_slab, consistency_band,
+                             shape=(batch_size, self.channels) + (self.image_sizes[n - 1],) * 3,
                              stochastic=not (sampler[n - 1] == 'dpmpp2m' or (sampler[n - 1] == 'ddim' and eta[n - 1] == 0)),
                              has_inpainting=exists(inpaint_images) and exists(inpaint_masks),
                              init_images=cast_tuple(init_images, num_unets)[n - 1], skip_steps=skip_steps[n - 1])
@@ -1658,7 +1662,8 @@ class Imagen(nn.Module):
                 sampler=unet_sampler, sample_steps=unet_sample_steps, eta=unet_eta, consistency=consistency,
                 consistency_weight=consistency_weight, consistency_profile=consistency_profile, consistency_noise=consistency_noise,
                 consistency_operator=consistency_operator, consistency_row_noise=consistency_row_noise,
-                **(dict(consistency_slab=consistency_slab) if exists(consistency_slab) else {}))
+                **(dict(consistency_slab=consistency_slab) if exists(consistency_slab) else {}),
+                **(dict(consistency_band=consistency_band) if exists(consistency_band) else {}))
             outputs.append(img)
             if exists(stop_at_unet_number) and stop_at_unet_number == unet_number:
                 break

@@ -132,8 +132,9 @@ through the z-score and ``state_space`` as a plain volume, and the window gather
 divisibility rules are those above.  The crop and blend modes hand windows of t and ``consistency_operator=`` on to the sampler
 (``ops.tile_project`` per step); ``joint=True`` launches the tile operator's consistent step, as many launches as before.  At
 w = 1 the corrected prediction satisfies P x0' = t (to fp32 rounding), which is A x0' = y when y lies in the range of A; stacks that
-contradict each other are fitted in the least-squares sense.  Not offered: an operator that crosses tile borders (true k-space
-truncation; overlapping slice profiles are ``consistency_slab``), ``consistency_profile`` or ``consistency_noise`` with an operator, Heun,
+contradict each other are fitted in the least-squares sense.  An operator that crosses tile borders is not a tile operator: true
+k-space truncation is ``consistency_band``, overlapping slice profiles are ``consistency_slab``, both below.  Not offered:
+``consistency_profile`` or ``consistency_noise`` with an operator, Heun,
 consistency together with inpainting; the stacks are taken as registered to each other and A as known.
 
 Noisy rows (``consistency_row_noise=sigma``, with ``consistency`` and ``consistency_operator``; DDNM+ per singular direction): sigma
@@ -168,6 +169,29 @@ the slab's consistent step -- and the windows are walked twice; the workspace an
 allocated once per volume.  Not offered: a reach beyond half a cell, slabs along other axes (permute the volume instead),
 noise-aware weights (``consistency_noise`` / ``consistency_row_noise``), rows that leave the volume, and any of the other
 consistency keywords together with it.
+
+A k-space band limit (``consistency_band=(hz, hy, hx)`` or ``(hz, hy, hx, offset)``, with ``consistency``): what a 3-D encoded
+low-resolution scan is -- the central, box-shaped part of k-space, taken on the periodic field of view and sampled on the low-res
+grid.  Per axis (N voxels, factor f, n = N / f) ``h`` is None, the full band |k| <= kappa = (n - 1) // 2 of the low-res grid (on an
+even n the unpaired Nyquist bin is NOT part of the band), or the weights of the frequencies k = 0 .. len - 1, symmetric in +-k: finite
+and >= 0, h[0] > 0 (they are divided by it), a zero drops its frequency, and a positive weight below max(h) / 64 is refused (the
+back-projection would amplify by more than 64).  ``offset``: where in its cell a low-res sample sits, three numbers in high-res
+voxels or 'centre' = (f - 1) / 2; default 0.  An axis with f = 1 and ``h`` None is the identity and has no pass.  The box is
+separable, so A, A+ and the projector P = A+ A are Kronecker products of real circulants with Dirichlet kernels
+(``ops.band_table``: N floats per table and axis, no FFT, no power-of-two shape; ``ops.band_measure`` is A and simulates the
+acquisition).  Rows of A sum to 1, so t = A+ y (``ops.band_backproject``, once per volume) passes through the z-score and
+``state_space`` as the tile operator's t does, and the projection is the tile operator's, x0' = a + w P (t - a) with a the clamped
+prediction: at w = 1, P x0' = t.  The periodic wrap is part of the model, as it is in the scanner.  The operator is global -- every
+voxel of a line feeds every output of that line -- and a window of t is not the t of a window: a one-call sampler projects on its cube
+(``ops.band_project``: one launch per active axis) with ``consistency=(t, cell)``, and ``VolumeInference`` takes the keyword with
+``joint=True`` only (the crop and blend modes refuse).  A joint step is three calls and up to five launches, without atomics or waits
+across workgroups: ``ops.volume_joint_band_residual`` (the fuse; a = the fused clamped prediction, the covered flags, r = t - a, or 0
+where nothing covers), ``ops.band_apply`` (c = P r, three dense passes along the axes) and
+``ops.volume_joint_consistent_band_step`` (the three update forms on x0' = a + w c; the windows are not walked again).  A residual of
+0 means the measurement is believed where nothing was generated, so exact consistency holds only on a fully covered volume.  The table
+and the five-volume workspace are made once per volume; an axis is capped at 512 voxels (``ops.band_plan``).  Not offered: a
+non-separable band (an ellipsoid, partial Fourier), phase or coil models, noise-aware weights, the crop and blend modes, and any of the
+other consistency keywords together with it; Heun, inpainting, ``init_images`` and ``skip_steps`` as for ``consistency``.
 """
 from types import SimpleNamespace
 
@@ -358,6 +382,7 @@ class VolumeInference:
     consistency_noise = property(lambda self: getattr(self.plan, 'noise', None))
     consistency_row_noise = property(lambda self: getattr(self.plan, 'row_noise', None))
     consistency_slab = property(lambda self: getattr(self.plan, 'slab', None))
+    consistency_band = property(lambda self: getattr(self.plan, 'band', None))
 
     def _inpaint_volumes(self, win):
         """The known volume and the mask as 0/1 floats on the volume's device (``__call__`` has checked their shape)."""
@@ -370,7 +395,8 @@ class VolumeInference:
 
     def __init__(self, configs, sample_fn, nonzero_ratio=0.05, blend=None, sigma_scale=0.125, samples=1, noise=None, seed=0, joint=False,
                  inpaint=None, inpaint_resample_times=5, consistency=None, consistency_weight=1.0, consistency_profile=None,
-                 consistency_noise=None, consistency_operator=None, consistency_row_noise=None, consistency_slab=None):
+                 consistency_noise=None, consistency_operator=None, consistency_row_noise=None, consistency_slab=None,
+                 consistency_band=None):
         """``sample_fn(lr_patches [B,1,S,S,S]) -> hr_patches`` — e.g. ``lambda x: trainer.sample(batch_size=x.shape[0],
         start_image_or_video=x, start_at_unet_number=2)[0]`` (test_all.py:234).  ``blend`` / ``sigma_scale`` / ``samples``: weighted
         overlap blending and multi-sample statistics, see the module docstring.  ``noise='anchored'`` (with ``seed``): every call
@@ -396,7 +422,8 @@ class VolumeInference:
         chains have no re-noising loop).
 
         ``consistency=(measurement, cell)`` with ``consistency_weight=w``, and ``consistency_profile``, ``consistency_noise``,
-        ``consistency_operator``, ``consistency_row_noise``, ``consistency_slab`` with it: data-consistent sampling; the measurement
+        ``consistency_operator``, ``consistency_row_noise``, ``consistency_slab``, ``consistency_band`` with it: data-consistent sampling;
+        the measurement
         models are in the module docstring, the keywords, their rules and the launch a step takes in ``consistency.py``.
         ``measurement`` is a float tensor [D/fz, H/fy, W/fx] of RAW intensities (host or device) -- with an operator
         [m, D/fz, H/fy, W/fx], one volume per row (``ops.stack_rows`` lays stacks out so, ``ops.tile_measure`` simulates them) -- and
@@ -430,7 +457,7 @@ class VolumeInference:
         self.mean, self.std = float(configs['Data']['mean']), float(configs['Data']['std'])
         # the fused launch of a joint chain rides the window's taps; a sampler call of the crop and blend modes sees cubes of `sub`
         self.plan = consistency_plan("VolumeInference", ops, consistency, consistency_weight, consistency_profile, consistency_noise,
-                                     consistency_operator, consistency_row_noise, consistency_slab, stochastic=stochastic(),
+                                     consistency_operator, consistency_row_noise, consistency_slab, consistency_band, stochastic=stochastic(),
                                      window=dict(edge=self.sub, stride=self.overlap, joint=bool(joint), denoiser=sample_fn,
                                                  inpaint=self.inpaint is not None, mean=self.mean, std=self.std))
         self.resample_times = inpaint_resample_times

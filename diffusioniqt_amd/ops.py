@@ -3161,6 +3161,272 @@ def volume_joint_consistent_slab_step(y, slot, taps, x_t, x0_prev, cell, table, 
                              _joint_form(who, form), (kx, k0, kp, kn), lo, hi, clamp_mode, stride, seed, draw, sample, out, x0_out, own)
 
 
+class BandTable:
+    """What ``band_table`` returns: ``shape`` = (Nz, Ny, Nx) the periodic domain, ``cell`` = (fz, fy, fx), ``offset`` = the three
+    offsets in voxels; ``axes``: per axis a dict of ``N``, ``n`` = N / f, ``f``, ``delta``, ``active``, ``kept`` (the kept k >= 1),
+    ``h`` (the normalised weights, h[0] = 1), the fp32 host tensors ``d``, ``a``, ``g`` [N] and the float64 values ``d64``, ``a64``,
+    ``g64`` they were rounded from; ``active``: the mask of the axes that
+    have a pass (1 = z, 2 = y, 4 = x); ``table``: the flat fp32 tensor the kernels read (include/diqt.h: d, a, g of z, then y, then
+    x); ``gain`` = the product over the active axes of sum_m |d[m]| on the fp32 values, the factor of the rounding bounds.
+    ``to(device)`` gives the same object around the moved tensor (once per chain or volume)."""
+
+    def __init__(self, shape, cell, offset, axes, table):
+        self.shape, self.cell, self.offset, self.axes, self.table = shape, cell, offset, axes, table
+        self.active = sum(1 << i for i, ax in enumerate(axes) if ax['active'])
+        self.gain = 1.0
+        for ax in axes:
+            if ax['active']:
+                self.gain *= float(ax['d'].double().abs().sum())
+
+    def to(self, device):
+        return BandTable(self.shape, self.cell, self.offset, self.axes, self.table.to(device))
+
+    def __repr__(self):
+        return f"BandTable(shape={self.shape}, cell={self.cell}, kept={[len(ax['kept']) for ax in self.axes]}, gain={self.gain:.3g})"
+
+
+BAND_MAX_N = 512                                                 # csrc/datapath.hip: BAND_MAX_N
+
+
+def band_table(shape, cell, band=None, offset=None):
+    """The host tables of a k-space band limit for the ``consistency_band`` modes (``ValueError`` naming "consistency_band"; nothing
+    touches the device).  ``shape`` = (Nz, Ny, Nx): the periodic domain, a cube of a sampler or a whole volume; ``cell`` = (fz, fy, fx)
+    divides it, n = N / f per axis.  ``band`` = (hz, hy, hx), or None for three times None; per axis None or a sequence of weights for
+    the frequencies k = 0 .. len - 1, the band symmetric in +-k: finite and >= 0, h[0] > 0 (the weights are divided by it),
+    len <= kappa + 1 with kappa = (n - 1) // 2 (the measurement grid holds nothing beyond), a zero drops its frequency, and a positive
+    weight below max(h) / 64 is refused (the back-projection would amplify by more than 64 on that axis).  None is the full band, ones
+    up to kappa -- on an even n the unpaired Nyquist bin is NOT part of the band -- except on an axis with f = 1, which is then the
+    identity and has no pass.  ``offset`` = (dz, dy, dx) in high-res voxels (None: zeros; 'centre': (f - 1) / 2 per axis): where in
+    its cell a low-res sample sits.  With K the kept k >= 1, in float64, every entry rounded once to fp32:
+        d[m] = (1 + 2 sum_K cos(2 pi k m / N)) / N, for m <= N / 2 and mirrored (symmetric to the bit): P[i, j] = d[(i - j) mod N];
+        a[m] = (1 + 2 sum_K h_k cos(2 pi k (m + delta) / N)) / N: A[s, j] = a[(s f - j) mod N], rows sum to 1;
+        g[m] = (1 + 2 sum_K cos(2 pi k (m + delta) / N) / h_k) / n: A+[j, s] = g[(s f - j) mod N].
+    Returns a ``BandTable``."""
+    import math
+    import numbers
+    who = "band_table"
+    real = lambda v: not isinstance(v, bool) and isinstance(v, numbers.Real) and math.isfinite(v)
+    if (not isinstance(shape, (tuple, list, torch.Size)) or len(shape) != 3 or
+            not all(not isinstance(s, bool) and isinstance(s, numbers.Integral) and s >= 1 for s in shape)):
+        raise ValueError(f"{who}: the consistency_band domain must be (Nz, Ny, Nx), three integers >= 1, got {shape!r}")
+    shape = tuple(int(s) for s in shape)
+    try:
+        cell, _ = consistency_cell(who, cell, 1.0, [(s, a) for a, s in enumerate(shape)])
+    except ValueError as err:
+        raise ValueError(f"{err} (consistency_band)") from None
+    if band is None:
+        band = (None, None, None)
+    if not isinstance(band, (tuple, list)) or len(band) != 3:
+        raise ValueError(f"{who}: consistency_band must be (hz, hy, hx), per axis None or a sequence of k-space weights, got {band!r}")
+    if offset is None:
+        offset = (0.0, 0.0, 0.0)
+    elif isinstance(offset, str) and offset == 'centre':
+        offset = tuple((f - 1) / 2 for f in cell)
+    if not isinstance(offset, (tuple, list)) or len(offset) != 3 or not all(real(v) for v in offset):
+        raise ValueError(f"{who}: the offset of consistency_band must be three finite numbers (high-res voxels) or 'centre', got {offset!r}")
+    offset = tuple(float(v) for v in offset)
+    axes = []
+    for axis, (N, f, h, delta) in enumerate(zip(shape, cell, band, offset)):
+        n = N // f
+        kappa = (n - 1) // 2
+        if h is not None and (torch.is_tensor(h) or type(h).__module__ == 'numpy'):
+            h = h.tolist()
+        if h is None and f == 1:
+            if delta != 0.0:
+                raise ValueError(f"{who}: axis {axis} of consistency_band is the identity (f = 1, full band) and takes no offset, got "
+                                 f"{delta!r}")
+            one = torch.zeros(N, dtype=torch.float32)
+            one[0] = 1.0
+            axes.append(dict(N=N, n=n, f=f, delta=0.0, active=False, kept=tuple(range(1, N // 2 + 1)), h=None, d=one, a=one, g=one,
+                             d64=one.double(), a64=one.double(), g64=one.double()))
+            continue
+        if h is None:
+            h = [1.0] * (kappa + 1)
+        if not isinstance(h, (tuple, list)) or len(h) < 1 or not all(real(v) and v >= 0 for v in h):
+            raise ValueError(f"{who}: axis {axis} of consistency_band must be None or a sequence of finite weights >= 0 for "
+                             f"k = 0 .. len - 1, got {h!r}")
+        if not h[0] > 0:
+            raise ValueError(f"{who}: axis {axis} of consistency_band must keep the mean: h[0] > 0, got {h[0]!r}")
+        if len(h) > kappa + 1:
+            raise ValueError(f"{who}: axis {axis} of consistency_band has {len(h)} weights, the measurement grid of n = {n} samples "
+                             f"holds the frequencies k <= kappa = {kappa} only (at most {kappa + 1} weights)")
+        h = [float(v) / float(h[0]) for v in h]
+        top = max(h)
+        if any(0 < v < top / 64 for v in h):
+            raise ValueError(f"{who}: axis {axis} of consistency_band has a positive weight below max(h) / 64 = {top / 64!r}: the "
+                             f"back-projection would amplify that frequency by more than 64 (drop it with a zero instead), got {h!r}")
+        kept = tuple(k for k in range(1, len(h)) if h[k] > 0)
+        w = 2.0 * math.pi / N
+        d = [0.0] * N
+        for m in range(N // 2 + 1):
+            s = 1.0
+            for k in kept:
+                s += 2.0 * math.cos(w * ((k * m) % N))
+            d[m] = d[(N - m) % N] = s / N
+        a, g = [], []
+        for m in range(N):
+            sa = sg = 1.0
+            for k in kept:
+                c = math.cos(w * (((k * m) % N) + k * delta))
+                sa += 2.0 * h[k] * c
+                sg += 2.0 * c / h[k]
+            a.append(sa / N)
+            g.append(sg / n)
+        d64, a64, g64 = (torch.tensor(v, dtype=torch.float64) for v in (d, a, g))
+        axes.append(dict(N=N, n=n, f=f, delta=delta, active=True, kept=kept, h=tuple(h), d=d64.to(torch.float32), a=a64.to(torch.float32),
+                         g=g64.to(torch.float32), d64=d64, a64=a64, g64=g64))
+    table = torch.cat([t for ax in axes for t in (ax['d'], ax['a'], ax['g'])]).contiguous()
+    return BandTable(shape, cell, offset, axes, table)
+
+
+def band_lds(N):
+    """The bytes of LDS one band pass plans on an axis of ``N`` voxels: the padded doubled table and a 64 x 65 panel."""
+    return 4 * (2 * int(N) + 128 + 64 * 65)
+
+
+def band_plan(who, shape):
+    """``ValueError`` naming "consistency_band" for a domain with an axis above 512 voxels or a pass that plans more than 64 KiB of LDS;
+    before anything touches the device."""
+    for axis, N in enumerate(shape):
+        if int(N) > BAND_MAX_N:
+            raise ValueError(f"{who}: consistency_band takes at most {BAND_MAX_N} voxels per axis, axis {axis} of {tuple(shape)} has {int(N)}")
+        if band_lds(N) > 65536:
+            raise ValueError(f"{who}: consistency_band on axis {axis} of {tuple(shape)} plans {band_lds(N)} bytes of LDS, above the 65536 "
+                             f"a launch may have")
+
+
+def band_workspace(shape, device):
+    """The workspace of the joint band launches for a [D,H,W] volume: a fp32 device tensor [5, D, H, W] -- the fused prediction a, the
+    covered flags, the residual r, c = P r and the buffer of ``band_apply``; allocate it once per volume."""
+    return torch.empty((5, *(int(s) for s in shape)), dtype=torch.float32, device=device)
+
+
+def _band_table(who, table, shape, like, cell=None):
+    """The check of a ``band_table`` table handed to a kernel: a ``BandTable`` of this domain (and cell), its tensor on ``like``'s
+    device, and the domain inside ``band_plan``."""
+    if not isinstance(table, BandTable):
+        raise ValueError(f"{who}: the consistency_band table must be what ops.band_table returns, got {type(table).__name__}")
+    if tuple(shape) != table.shape:
+        raise ValueError(f"{who}: the consistency_band table was made for the domain {table.shape}, not {tuple(shape)}")
+    if cell is not None and tuple(cell) != table.cell:
+        raise ValueError(f"{who}: the consistency_band table was made for the cell {table.cell}, not {tuple(cell)}")
+    band_plan(who, shape)
+    if table.table.device != like.device:
+        raise ValueError(f"{who}: the consistency_band table is on {table.table.device}, the data on {like.device}")
+    _chk(table.table)
+
+
+def _band_rect(who, entry, src, table, low, workspace):
+    """``band_measure`` / ``band_backproject``: ``src`` is the [D,H,W] volume or (``low``) its measurement."""
+    _chk(src, workspace)
+    _band_table(who, table, getattr(table, 'shape', ()), src)
+    rows = tuple(s // f for s, f in zip(table.shape, table.cell))
+    want = rows if low else table.shape
+    if src.ndim != 3 or not src.is_contiguous() or tuple(src.shape) != want:
+        raise ValueError(f"{who}: expected a contiguous {want} tensor for the consistency_band domain {table.shape} and cell {table.cell}, "
+                         f"got {tuple(src.shape)}")
+    need = 2 * table.shape[0] * table.shape[1] * table.shape[2]
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.float32, device=src.device)
+    if not workspace.is_contiguous() or workspace.numel() < need:
+        raise ValueError(f"{who}: the consistency_band workspace must be a contiguous fp32 tensor of twice the volume, {need} floats")
+    out = torch.empty(table.shape if low else rows, dtype=torch.float32, device=src.device)
+    _lib.call(entry, src, table.table, out, workspace, workspace.numel(), *table.shape, *table.cell, table.active, _stream())
+    return out
+
+
+def band_measure(vol, table, workspace=None):
+    """The measurement of a [D,H,W] volume under a k-space band limit (include/diqt.h, diqt_band_measure): fp32 [D/fz, H/fy, W/fx] =
+    A vol, the periodic low-pass of ``table`` (``band_table`` for this volume's shape, on its device) sampled on the low-res grid.  It
+    simulates the acquisition of the ``consistency_band`` modes; once per volume.  ``workspace``: fp32, twice the volume (None: made
+    here).  One launch per active axis."""
+    return _band_rect("band_measure", "diqt_band_measure", vol, table, False, workspace)
+
+
+def band_backproject(y, table, workspace=None):
+    """t = A+ y on the high-res grid (include/diqt.h, diqt_band_backproject): ``y`` [D/fz, H/fy, W/fx] a measurement, fp32 [D,H,W] the
+    band-limited volume whose measurement it is -- what the ``consistency_band`` projections read as their target.  Once per volume;
+    ``table`` and ``workspace`` as in ``band_measure``."""
+    return _band_rect("band_backproject", "diqt_band_backproject", y, table, True, workspace)
+
+
+def band_project(x0, target, cell, table, weight=1.0, clamp=None, out=None, workspace=None):
+    """``cell_project_profile`` for a k-space band limit (include/diqt.h, diqt_band_project): ``target`` [B,C,P,P,P] = t = A+ y of every
+    cube, ``table`` = ``band_table((P, P, P), cell, ...)`` on ``x0``'s device.  a = clamp(x0); out = a + weight P (t - a) with P the
+    band's projector on the periodic cube: at weight 1 the measurement of out is y.  ``workspace``: fp32, two batches of cubes (None:
+    made here).  Shapes, ``clamp`` and ``out`` as there.  Returns ``out``.  One launch per active axis (one more with a single axis)."""
+    who = "band_project"
+    ws = []
+
+    def own(cell, w, P):
+        _band_table(who, table, (P, P, P), x0, cell)
+        space = torch.empty(2 * x0.numel(), dtype=torch.float32, device=x0.device) if workspace is None else workspace
+        _chk(space)
+        if space.dtype != torch.float32 or not space.is_contiguous() or space.numel() < 2 * x0.numel():
+            raise ValueError(f"{who}: the consistency_band workspace must be a contiguous fp32 tensor of two cube batches, "
+                             f"{2 * x0.numel()} floats")
+        ws.append(space)
+        return (table.table, space), (space.numel(), table.active, w)
+    return _project(who, "diqt_band_project", x0, target, 'target', cell, weight, clamp, out, own)
+
+
+def _band_joint(who, x_like, table, workspace):
+    """The host checks the joint band launches share."""
+    _band_table(who, table, tuple(x_like.shape), x_like)
+    _chk(workspace)
+    if tuple(workspace.shape) != (5, *x_like.shape) or not workspace.is_contiguous():
+        raise ValueError(f"{who}: the consistency_band workspace must be a contiguous fp32 {(5, *x_like.shape)} tensor "
+                         f"(ops.band_workspace), got {tuple(workspace.shape)}")
+
+
+def volume_joint_band_residual(y, slot, taps, target, table, workspace, lo, hi, clamp_mode, stride):
+    """The first of the three calls of a joint step under ``consistency_band`` (include/diqt.h, diqt_volume_joint_band_residual): the
+    windows ``y`` are fused as in ``volume_joint_step``; ``workspace[0]`` receives the fused clamped prediction a (0 where no kept
+    window covers), ``workspace[1]`` the covered flags and ``workspace[2]`` the residual ``target`` - a, 0 where uncovered -- there the
+    measurement is believed, so only a fully covered volume is made exactly consistent.  ``target`` [D,H,W]: t = A+ y in state space.
+    Returns ``workspace``.  One launch."""
+    who = "volume_joint_band_residual"
+    N, P, stride = _joint_windows(who, y, slot, taps, target, clamp_mode, stride)
+    _joint_slots(who, slot, N)
+    _band_joint(who, target, table, workspace)
+    _lib.call("diqt_volume_joint_band_residual", y if N else None, slot, taps, target, workspace[0], workspace[1], workspace[2], N,
+              *target.shape, P, stride, *slot.shape, float(lo), float(hi), int(clamp_mode), _stream())
+    return workspace
+
+
+def band_apply(x, table, out, workspace):
+    """``out`` = P ``x``: the band's projector over a [D,H,W] volume (include/diqt.h, diqt_band_apply), through ``out`` and
+    ``workspace`` (a volume each; the three are different tensors).  The second call of a joint step: ``band_apply(ws[2], table, ws[3],
+    ws[4])``.  Returns ``out``.  One launch per active axis."""
+    who = "band_apply"
+    _chk(x, out, workspace)
+    _band_table(who, table, tuple(x.shape), x)
+    for t, name in ((x, 'x'), (out, 'out'), (workspace, 'workspace')):
+        if t.shape != x.shape or not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be a contiguous fp32 tensor of the domain {table.shape}, got {tuple(t.shape)}")
+    if len({x.data_ptr(), out.data_ptr(), workspace.data_ptr()}) != 3:
+        raise ValueError(f"{who}: x, out and the workspace must be three different volumes")
+    _lib.call("diqt_band_apply", x, table.table, out, workspace, workspace.numel(), *x.shape, table.active, _stream())
+    return out
+
+
+def volume_joint_consistent_band_step(y, slot, taps, x_t, x0_prev, cell, table, workspace, weight, form, kx, k0, kp, kn, lo, hi,
+                                      clamp_mode, stride, seed=0, draw=0, sample=0, out=None, x0_out=None):
+    """The third call (include/diqt.h, diqt_volume_joint_consistent_band_step): ``volume_joint_consistent_step``'s three update forms on
+    x0' = a + weight c, with a and the flags as ``volume_joint_band_residual`` left them in ``workspace`` for the same ``y`` and
+    c = ``workspace[3]`` from ``band_apply``; the windows are not walked again.  An uncovered voxel keeps ``x_t``.  ``out`` / ``x0_out``
+    as there.  Returns ``(out, x0_out)``.  One launch, bit-reproducible."""
+    who = "volume_joint_consistent_band_step"
+
+    def own(cell, w, P):
+        _band_joint(who, x_t, table, workspace)
+        if tuple(cell) != table.cell:
+            raise ValueError(f"{who}: the consistency_band table was made for the cell {table.cell}, not {tuple(cell)}")
+        return (workspace[0], workspace[1], workspace[3]), (w,)
+    return _joint_consistent(who, "diqt_volume_joint_consistent_band_step", y, slot, taps, x_t, x0_prev, None, cell, weight,
+                             _joint_form(who, form), (kx, k0, kp, kn), lo, hi, clamp_mode, stride, seed, draw, sample, out, x0_out, own)
+
+
 class TileOperator:
     """What ``tile_operator`` returns: ``cell`` = (fz, fy, fx); ``A`` [m, n] and ``pinv`` = A+ [n, m], float64 host tensors; ``table``
     the fp32 host [n, n] projector P = A+ A, symmetric to the bit, which the projecting kernels read; ``rank``; ``gain`` =

@@ -958,6 +958,64 @@ int diqt_volume_joint_consistent_slab_step(const float* y, const int* slot, cons
                                            int G1, int G2, int fz, int fy, int fx, int r, int jmax, float weight, float kx, float k0,
                                            float kp, float kn, float lo, float hi, int clamp_mode, unsigned long long seed,
                                            unsigned draw, unsigned sample, void* stream);
+/* Data consistency for a K-SPACE BAND LIMIT (the band operator; ops.band_table).  The measurement is the central, box-shaped part of
+ * the k-space of a PERIODIC domain (the cube of the per-window entry, the volume of the others), sampled on the low-res grid: on an
+ * axis of N voxels with factor f and n = N / f it keeps the frequencies |k| <= kappa = floor((n - 1) / 2) with weights h_k (h_0 = 1,
+ * a zero drops a frequency; on an even n the unpaired Nyquist bin is not measured), at an offset of delta voxels.  A, A+ and P = A+ A
+ * are Kronecker products over the axes of real circulants, with K the kept k >= 1 and m an index mod N:
+ *     P[i][j]  = d[(i - j) mod N],    d[m] = (1 + 2 sum_K cos(2 pi k m / N)) / N                       symmetric to the bit
+ *     A[s][j]  = a[(s f - j) mod N],  a[m] = (1 + 2 sum_K h_k cos(2 pi k (m + delta) / N)) / N         rows sum to 1
+ *     A+[j][s] = g[(s f - j) mod N],  g[m] = (1 + 2 sum_K (1 / h_k) cos(2 pi k (m + delta) / N)) / n
+ * `table` is device fp32, flat (the caller's; ops.band_table makes it on the host in float64, every entry rounded once): for z, then
+ * y, then x the tables d [N], a [N], g [N] of the axis.  `active` is a mask of the axes that have a pass (1 = z, 2 = y, 4 = x, not
+ * empty): an axis with f = 1 and the full band is the identity and stays out of it -- its pass is skipped, its bits stay; an axis
+ * outside the mask must have f = 1.  The arithmetic, fp32 with no contraction, ONE definition for every pass of every entry:
+ *     out[i] = acc after  acc = 0;  acc = fmaf(T[idx(i, j)], v[j], acc)  over ASCENDING j along the axis,
+ *     idx = (i - j) mod N with T = d,  (i f - j) mod N with T = a,  (j f - i) mod N with T = g (j runs over the n rows);
+ * P and A take their passes in the order z, y, x, A+ in the order x, y, z.  The periodic wrap is part of the model.
+ * Error codes: a null pointer or an aliasing the entry does not allow DIQT_E_ALIGN; a cell with fz fy fx outside 2 .. 64, an empty
+ * mask, an inactive axis with f > 1, a weight outside (0, 1], a form or a clamp mode the entry does not have DIQT_E_UNSUPPORTED; an
+ * axis above 512 voxels, a factor that does not divide its axis, an LDS plan above 64 KiB or a workspace that is too small
+ * DIQT_E_SHAPE.  One pass plans (2 N + 128 + 64 * 65) floats of LDS.
+ *
+ * diqt_band_measure: out [D / fz][H / fy][W / fx] = A x for x [D][H][W].  diqt_band_backproject: out [D][H][W] = A+ y.  Each is one
+ * launch per active axis; with more than one, `workspace` (device fp32) must hold twice the largest intermediate array -- 2 D H W
+ * floats always suffice.  Nothing may alias anything else.  Once per volume.                                                          */
+int diqt_band_measure(const float* x, const float* table, float* out, float* workspace, size_t workspace_floats, int D, int H, int W,
+                      int fz, int fy, int fx, int active, void* stream);
+int diqt_band_backproject(const float* y, const float* table, float* out, float* workspace, size_t workspace_floats, int D, int H, int W,
+                          int fz, int fy, int fx, int active, void* stream);
+/* The per-window step, diqt_cell_project_profile's contract: `cubes` cubes of edge P, a = clamp(x0) with the clamp modes 0 / 1 / 2 of
+ * diqt_cell_project, then the tile operator's projection onto the target t = A+ y (diqt_band_backproject of the cube's measurement):
+ *     r = t - a (formed in the loader of the first pass);  c = P r;  out = fmaf(w, c, a) (formed in the storer of the last pass).
+ * `workspace` holds two cube batches, 2 cubes P^3 floats, and every pass but the last writes there, so out may alias x0; target, table
+ * and the workspace may not alias out or x0.  With one active axis the only pass stores c and a fourth, elementwise launch forms
+ * out.  One launch per active axis (plus that one).                                                                                  */
+int diqt_band_project(const float* x0, const float* target, const float* table, float* workspace, float* out, size_t cubes, int P, int fz,
+                      int fy, int fx, size_t workspace_floats, int active, float weight, float lo, float hi, int clamp_mode, void* stream);
+/* out [D][H][W] = P x: the projector's passes over a volume, through out itself and `workspace` (D H W floats); x, out and the
+ * workspace are three different volumes.                                                                                             */
+int diqt_band_apply(const float* x, const float* table, float* out, float* workspace, size_t workspace_floats, int D, int H, int W,
+                    int active, void* stream);
+/* The joint path: the projector crosses every window border, so a step is three calls -- diqt_volume_joint_band_residual,
+ * diqt_band_apply on r, diqt_volume_joint_consistent_band_step -- and up to five launches.  The first fuses every voxel as
+ * diqt_volume_joint_step does (the same walk and step clamp) and writes three [D][H][W] volumes: a_out the fused clamped prediction
+ * (0 where no kept window covers), covered_out 1 / 0, and r_out = target - a, or 0 where nothing covers: there the measurement is
+ * believed, so the projection is exact (A x0' = y at w = 1) only on a fully covered volume.  target is t = A+ y in state space.      */
+int diqt_volume_joint_band_residual(const float* y, const int* slot, const float* taps, const float* target, float* a_out,
+                                    float* covered_out, float* r_out, int N, int D, int H, int W, int P, int stride, int G0, int G1,
+                                    int G2, float lo, float hi, int clamp_mode, void* stream);
+/* The three update forms of diqt_volume_joint_consistent_step on x0' = fmaf(w, c, a) per covered voxel, with a and covered as the
+ * residual call left them and c = P r from diqt_band_apply.  The windows are not walked again: y, slot, taps, the lattice and the
+ * clamp are not looked at.  An uncovered voxel keeps x_t and gets x0_out = 0.  Normals and draw numbering are
+ * diqt_volume_joint_step's.  x_next may alias x_t and x0_out may alias x0_prev (a thread reads its own voxel of each, then writes
+ * it).  No atomics, no waiting across blocks: bit-reproducible, and with the volume equal to one window and unit taps the chain is
+ * diqt_band_project followed by the per-window step, bit for bit.                                                                    */
+int diqt_volume_joint_consistent_band_step(const float* y, const int* slot, const float* taps, const float* x_t, const float* x0_prev,
+                                           const float* a, const float* covered, const float* c, float* x_next, float* x0_out, int form,
+                                           int N, int D, int H, int W, int P, int stride, int G0, int G1, int G2, int fz, int fy, int fx,
+                                           float weight, float kx, float k0, float kp, float kn, float lo, float hi, int clamp_mode,
+                                           unsigned long long seed, unsigned draw, unsigned sample, void* stream);
 /* The stochastic Heun sampler of the EDM family (Karras et al. 2022; elucidated_imagen.py:382-532) on the joint state: a churn, a
  * predictor and a corrector per step, two U-Net evaluations.  The state is three [D][H][W] volumes, all updated in place (every thread
  * reads only its own voxel of each, then writes it): xh = images_hat, xn = images_next, x0 = the fused prediction.  Window walk,
