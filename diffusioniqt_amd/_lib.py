@@ -209,6 +209,7 @@ PROTOTYPES = {
     "diqt_volume_joint_consistent_band_step": (I, [P] * 10 + [I] * 13 + [F] * 7 + [I, ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_uint,
                                                                                    P]),
     "diqt_volume_joint_heun": (I, [P] * 6 +[I] * 10 + [F] * 7 + [I, ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_uint, P]),
+    "diqt_volume_joint_consistent_heun": (I, [P] * 8 + [I] * 14 + [F] * 8 + [I, ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_uint, P]),
     "diqt_edm_inpaint_churn": (I, [P] * 8 + [I, Z, P]),
     "diqt_volume_joint_heun_inpaint": (I, [P] * 8 + [I] * 10 + [F] * 8 + [I, ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_uint,
                                                                           ctypes.c_uint, P]),

@@ -1,4 +1,4 @@
-"""Data-consistent sampling, the part every sampler shares: which combinations of the eight ``consistency*`` keywords are admitted, and
+"""Data-consistent sampling, the part every sampler shares: which combinations of the nine ``consistency*`` keywords are admitted, and
 which launch a step takes.  ``Imagen.sample`` / ``p_sample_loop``, ``ElucidatedImagen.sample`` / ``one_unet_sample`` and
 ``VolumeInference`` take the same keywords, hand them to ``plan`` as they received them and keep what it returns: None (no
 ``consistency``) or a ``Plan``.  The measurement models themselves are described in the docstring of ``inference``; the kernels are
@@ -8,9 +8,9 @@ The keywords:
 * ``consistency=(measurement, cell)`` with ``consistency_weight=w`` in (0, 1]: ``cell`` = (fz, fy, fx), 2 <= fz fy fx <= 64.  A one-call
   sampler takes the measurement replicated onto the grid it samples (``meas_up`` [B,C,P,P,P], ``ops.cell_replicate``), in state space
   (``ElucidatedImagen.sample`` takes it in the units it returns); ``VolumeInference`` takes the raw measurement [D/fz, H/fy, W/fx].
-  Every x0 prediction is replaced by x0 + w A+(y - A x0) (DDNM).  It goes with neither the Heun sampler (two predictions per step)
-  nor inpainting, ``init_images`` or ``skip_steps``; the cell must divide the sampled cube -- in the crop and blend modes of
-  ``VolumeInference`` the stride and the window.
+  Every x0 prediction is replaced by x0 + w A+(y - A x0) (DDNM).  The Heun sampler (two predictions per step) takes it with
+  ``consistency_heun`` only; it goes with neither inpainting, ``init_images`` nor ``skip_steps``; the cell must divide the sampled cube
+  -- in the crop and blend modes of ``VolumeInference`` the stride and the window.
 * ``consistency_profile=(pz, py, px)``: the measurement of a cell is the weighted mean of a slice profile (``ops.cell_profile``).
 * ``consistency_operator=A``: a tile-local linear measurement (``ops.tile_operator``); the measurement is then t = A+ y on the grid, for
   ``VolumeInference`` the raw [m, D/fz, H/fy, W/fx] stack.  Not with a profile (one row of an operator) or ``consistency_noise``.
@@ -27,6 +27,15 @@ The keywords:
 * ``consistency_row_noise=sigma`` (an operator): the deviation of the noise of each row of A, one number or m of them; every singular
   direction of the whitened operator takes that schedule on its own (``ops.tile_noise_operator`` / ``ops.tile_noise_tables``).  Not with
   ``consistency_noise`` or a profile; a stochastic chain; a cell whose launch plans at most 64 KiB of LDS.
+* ``consistency_heun='both'`` or ``'predictor'``: the stochastic Heun sampler of ``ElucidatedImagen`` (``sampler='heun'``, or a
+  joint denoiser with ``heun``) under ``consistency``.  ``'both'``: the prediction of either U-Net evaluation of a step is replaced by
+  its projection; ``'predictor'``: the first alone (at sigma_hat), the corrector's stays the network's.  The step that ends at
+  sigma = 0 has no corrector, and its predictor row is (0, 1): either way the chain ends in its last projected prediction.  There is
+  no "corrector only" (it would leave the final state unprojected).  Per window with any of the five modes (the band, in
+  ``VolumeInference``, with ``joint=True`` only -- and there not with Heun); with ``joint=True`` the cell mean, a profile or an
+  operator: the joint step launches of the slab and the band carry the three linear update forms only.  With no other sampler, and
+  with neither ``consistency_noise`` nor ``consistency_row_noise``: Heun's noise is the churn BEFORE the evaluation, and the shaped
+  normal that follows a step of DDNM+ has no counterpart there.  Without the keyword Heun stays refused.
 Every keyword but the first rides on ``consistency``, ``consistency_row_noise`` also on ``consistency_operator``.  A refusal is a
 ``ValueError`` raised before anything touches the device; it begins with the entry point's name and names the keyword at fault, and
 what ``consistency`` (or the operator) refuses also names the keyword that rides on it.
@@ -34,23 +43,26 @@ what ``consistency`` (or the operator) refuses also names the keyword that rides
 The ladder of a step, resolved per step once per chain (``Chain.steps``): ``plain`` -- the family's own step, no projection (weight 0:
 the step with kn = 0 of a noise-aware chain); ``constant`` -- the projection of the mode with one weight (``ops.cell_project`` /
 ``cell_project_profile`` / ``tile_project`` / ``slab_project`` / ``band_project``, or the fused
-``ops.volume_joint_consistent*_step``); ``noise`` -- the projection with the step's own weights that also shapes the step's normals
-(``ops.cell_project_noise`` / ``tile_project_noise`` and their fused launches).  A projected prediction is not clamped again: the
+``ops.volume_joint_consistent*_step``, or ``ops.volume_joint_consistent_heun`` in a phase of a joint Heun chain); ``noise`` -- the
+projection with the step's own weights that also shapes the step's normals (``ops.cell_project_noise`` / ``tile_project_noise`` and
+their fused launches).  A projected prediction is not clamped again: the
 projection launch clamps first, the step runs with the clamp off.
 
 A further measurement model adds a branch to ``plan`` (its admission rules and host table), one to ``Chain.__init__`` (its device
-table), a rung to ``Chain.project`` and ``Chain.joint_step``, and its wrappers in ``ops``."""
+table), a rung to ``Chain.project`` and ``Chain.joint_step`` (``Chain.joint_heun``, if it has a Heun launch), and its wrappers in
+``ops``."""
 from contextlib import contextmanager
 
 import torch
 
 from . import ops
 
+HEUN = ('both', 'predictor')                                 # ``consistency_heun``: which predictions of a Heun step are projected
 NO_CLAMP = (-float('inf'), float('inf'), 1)                  # ``ddpm_step``'s box mode with an infinite box: the identity, bit for bit
 
 
 @contextmanager
-def _riders(slab, noise, row_noise, band=None):
+def _riders(slab, noise, row_noise, band=None, heun=None):
     """A ``ValueError`` raised inside keeps its wording and also names the given keyword that rides on what refused."""
     try:
         yield
@@ -58,6 +70,7 @@ def _riders(slab, noise, row_noise, band=None):
         msg = str(err)
         for name, value, note in (('consistency_slab', slab, "consistency_slab rides on consistency"),
                                   ('consistency_band', band, "consistency_band rides on consistency"),
+                                  ('consistency_heun', heun, "consistency_heun rides on consistency"),
                                   ('consistency_noise', noise, f"consistency_noise={noise!r} rides on consistency"),
                                   ('consistency_row_noise', row_noise,
                                    f"consistency_row_noise={row_noise!r} rides on consistency_operator")):
@@ -82,12 +95,13 @@ def in_units(sigma, std=1., slope=1.):
     return float(sigma) / float(std) * abs(float(slope))
 
 
-def _sampled_pair(who, consistency, weight, shape, has_inpainting, init_images, skip_steps, sampler):
+def _sampled_pair(who, consistency, weight, shape, has_inpainting, init_images, skip_steps, sampler, heun=None):
     """``consistency`` of a one-call sampler that generates ``shape`` = [B,C,P,P,P]: the checked ``(meas_up, cell, weight)``."""
     if not isinstance(consistency, (tuple, list)) or len(consistency) != 2:
         raise ValueError(f"{who}: consistency must be (meas_up, cell), got {type(consistency).__name__}")
-    if sampler == 'heun':
-        raise ValueError(f"{who}: consistency is not offered with the Heun sampler (two predictions per step): use sampler='dpmpp2m'")
+    if sampler == 'heun' and heun is None:
+        raise ValueError(f"{who}: consistency is not offered with the Heun sampler (two predictions per step): use sampler='dpmpp2m' "
+                         f"(or say which predictions to project: consistency_heun='both' or 'predictor')")
     if has_inpainting:
         raise ValueError(f"{who}: consistency and inpainting are not offered together")
     if init_images is not None or skip_steps is not None:
@@ -101,7 +115,7 @@ def _sampled_pair(who, consistency, weight, shape, has_inpainting, init_images, 
     return meas_up, cell, weight
 
 
-def _volume_pair(who, consistency, weight, window, rows):
+def _volume_pair(who, consistency, weight, window, rows, heun=None):
     """``consistency`` of ``VolumeInference``: the checked ``(measurement fp32, cell, weight)``, the tensor on the host or the device as
     it was given.  ``rows``: an operator is given and the measurement is [m, D/fz, H/fy, W/fx], one volume per row of it."""
     if not isinstance(consistency, (tuple, list)) or len(consistency) != 2:
@@ -117,9 +131,10 @@ def _volume_pair(who, consistency, weight, window, rows):
     if not rows and (meas.ndim != 3 or not meas.is_floating_point()):
         raise ValueError(f"{who}: the consistency measurement must be a float [D/fz, H/fy, W/fx] tensor, got {meas.dtype} "
                          f"{tuple(meas.shape)}")
-    if window['joint'] and getattr(window['denoiser'], 'heun', False):
+    if window['joint'] and getattr(window['denoiser'], 'heun', False) and heun is None:
         raise ValueError(f"{who}: consistency is not offered with the EDM Heun denoiser (two predictions per step and three joint "
-                         f"volumes): use window_denoiser(sampler='dpmpp2m')")
+                         f"volumes): use window_denoiser(sampler='dpmpp2m') (or say which predictions to project: "
+                         f"consistency_heun='both' or 'predictor')")
     if window['joint'] and not hasattr(window['denoiser'], 'state_space'):
         raise ValueError(f"{who}: joint=True with consistency needs a denoiser with state_space(x), the map of the measurement into "
                          f"the space of the state")
@@ -127,17 +142,35 @@ def _volume_pair(who, consistency, weight, window, rows):
 
 
 def plan(who, launch, consistency, weight=1., profile=None, noise=None, operator=None, row_noise=None, slab=None, band=None, *, shape=None,
-         window=None, stochastic=True, has_inpainting=False, init_images=None, skip_steps=None, sampler=None):
-    """The admission rules of the eight keywords (the module docstring), run once and in one order -- band, slab, row noise, operator, the
-    pair itself, the profile, the noise deviation, the LDS plans -- for the entry point ``who``: None without ``consistency``, else the
-    ``Plan``.  ``launch`` is the ``ops`` of the calling module: the rules and host tables here are ``ops``'s own host arithmetic, but
-    everything that touches the device -- the replication, the back-projection, the workspace, every projection and step -- goes
-    through the namespace its sampler launches through.  A one-call sampler gives the ``shape`` [B,C,P,P,P] it generates and what
-    else its rules depend on: whether its chain has a ``stochastic`` step, ``has_inpainting``, ``init_images``, ``skip_steps`` and
-    the ``sampler`` name.  ``VolumeInference`` gives
-    ``window`` instead: a dict of the window ``edge``, the ``stride``, ``joint``, the ``denoiser`` (its second argument), whether it
-    inpaints (``inpaint``) and the z-score's ``mean`` / ``std``."""
+         window=None, stochastic=True, has_inpainting=False, init_images=None, skip_steps=None, sampler=None, heun=None):
+    """The admission rules of the nine keywords (the module docstring), run once and in one order -- Heun, band, slab, row noise,
+    operator, the pair itself, the profile, the noise deviation, the LDS plans -- for the entry point ``who``: None without
+    ``consistency``, else the ``Plan``.  ``launch`` is the ``ops`` of the calling module: the rules and host tables here are
+    ``ops``'s own host arithmetic, but everything that touches the device -- the replication, the back-projection, the workspace,
+    every projection and step -- goes through the namespace its sampler launches through.  A one-call sampler gives the ``shape``
+    [B,C,P,P,P] it generates and what else its rules depend on: whether its chain has a ``stochastic`` step, ``has_inpainting``,
+    ``init_images``, ``skip_steps`` and the ``sampler`` name; every entry point hands ``consistency_heun`` on as ``heun``.
+    ``VolumeInference`` gives ``window`` instead: a dict of the window ``edge``, the ``stride``, ``joint``, the ``denoiser`` (its
+    second argument), whether it inpaints (``inpaint``) and the z-score's ``mean`` / ``std``."""
     has = consistency is not None
+    if heun is not None:
+        if not has:
+            raise ValueError(f"{who}: consistency_heun needs consistency=(measurement, cell)")
+        if heun not in HEUN:
+            raise ValueError(f"{who}: consistency_heun must be 'both' (both predictions of a Heun step are projected) or 'predictor' "
+                             f"(the first alone), got {heun!r}")
+        joint_heun = window is not None and window['joint'] and getattr(window['denoiser'], 'heun', False)
+        if (window is None and sampler != 'heun') or (window is not None and window['joint'] and not joint_heun):
+            raise ValueError(f"{who}: consistency_heun goes with the Heun sampler of ElucidatedImagen only (sampler='heun', "
+                             f"window_denoiser()): every other sampler has one prediction per step and projects it without the keyword")
+        for other, name in ((noise, 'consistency_noise'), (row_noise, 'consistency_row_noise')):
+            if other is not None:
+                raise ValueError(f"{who}: consistency_heun and {name} are not offered together: the Heun sampler's noise is the churn "
+                                 f"before the evaluation, and the shaped normal that follows a step of DDNM+ has no counterpart there")
+        for other, name in ((slab, 'consistency_slab'), (band, 'consistency_band')):
+            if other is not None and joint_heun:
+                raise ValueError(f"{who}: consistency_heun and {name} are not offered together with joint=True: the joint step kernels "
+                                 f"of the {name[12:]} carry the three linear update forms only, not the Heun phases")
     if band is not None:
         if not has:
             raise ValueError(f"{who}: consistency_band needs consistency=(measurement, cell)")
@@ -168,7 +201,7 @@ def plan(who, launch, consistency, weight=1., profile=None, noise=None, operator
             raise ValueError(f"{who}: consistency_row_noise needs a sampler with fresh noise per step (ddpm, ddim or dpmpp2m with eta > "
                              f"0): a deterministic chain would never project; use a constant consistency_weight < 1 there")
     p = None
-    with _riders(slab, noise, row_noise, band):
+    with _riders(slab, noise, row_noise, band, heun):
         if operator is not None:
             if not has:
                 raise ValueError(f"{who}: consistency_operator needs consistency=(measurement, cell)")
@@ -182,11 +215,12 @@ def plan(who, launch, consistency, weight=1., profile=None, noise=None, operator
             raise ValueError(f"{who}: consistency_profile needs consistency=(measurement, cell)")
         if has:
             if window is None:
-                pair = _sampled_pair(who, consistency, weight, shape, has_inpainting, init_images, skip_steps, sampler)
+                pair = _sampled_pair(who, consistency, weight, shape, has_inpainting, init_images, skip_steps, sampler, heun)
             else:
-                pair = _volume_pair(who, consistency, weight, window, operator is not None)
+                pair = _volume_pair(who, consistency, weight, window, operator is not None, heun)
             p = Plan(who, launch, *pair, profile, operator, row_noise, slab, band, **({} if window is None else
                                                                              dict(mean=window['mean'], std=window['std'])))
+            p.heun = heun
             if operator is not None:
                 p.mode, p.op = 'tile', ops.tile_operator(p.cell, operator)
                 if window is not None and p.measurement.shape[0] != p.op.m:
@@ -210,7 +244,7 @@ def plan(who, launch, consistency, weight=1., profile=None, noise=None, operator
     if p is None:
         return None
     p.noise = noise
-    with _riders(slab, noise, row_noise, band):
+    with _riders(slab, noise, row_noise, band, heun):
         # the cubes a projection launch sees; None: the fused launch of a joint chain, which rides the window's taps
         edge = shape[2] if window is None else None if window['joint'] else window['edge']
         if row_noise is not None:
@@ -230,13 +264,13 @@ def plan(who, launch, consistency, weight=1., profile=None, noise=None, operator
 
 class Plan:
     """What ``plan`` admitted.  ``measurement``, ``cell``, ``weight``: the checked pair; ``profile``, ``operator``, ``row_noise``,
-    ``slab``, ``band``: as given (what a sampler call takes); ``noise``: the checked deviation or None; ``mode``: ``'cell'``,
+    ``slab``, ``band``, ``heun``: as given (what a sampler call takes); ``noise``: the checked deviation or None; ``mode``: ``'cell'``,
     ``'profile'``, ``'tile'``, ``'slab'`` or ``'band'``, and its host table -- ``profile_table`` (``ops.cell_profile``), ``op`` (the
     ``ops.TileOperator``, whitened under ``row_noise``), ``slab_table`` (the ``ops.SlabTable`` for a sampler's cubes) or ``band_table``
     (the ``ops.BandTable`` for a sampler's cubes; ``band_of(shape)`` makes the one of a volume, once); for ``VolumeInference`` the
     z-score's ``mean``
     / ``std`` and, in joint mode, the denoiser's ``state_space``."""
-    mode, op, profile_table, slab_table, band_table, noise, state_space = 'cell', None, None, None, None, None, None
+    mode, op, profile_table, slab_table, band_table, noise, state_space, heun = 'cell', None, None, None, None, None, None, None
 
     def __init__(self, who, launch, measurement, cell, weight, profile, operator, row_noise, slab, band=None, mean=0., std=1.):
         self.who, self.launch, self.measurement, self.cell, self.weight = who, launch, measurement, cell, weight
@@ -259,7 +293,7 @@ class Plan:
     def admit_volume(self, shape):
         """``ValueError`` for a ``VolumeInference`` measurement that is not the volume's ``shape`` divided by the cell."""
         if tuple(s * f for s, f in zip(self.measurement.shape[-3:], self.cell)) != tuple(shape):
-            with _riders(self.slab, self.noise, self.row_noise, self.band):
+            with _riders(self.slab, self.noise, self.row_noise, self.band, self.heun):
                 raise ValueError(f"{self.who}: the consistency measurement {tuple(self.measurement.shape)} times the cell {self.cell} "
                                  f"is not the volume's shape {tuple(shape)}")
 
@@ -281,7 +315,8 @@ class Plan:
         ``measurement`` has taken (``in_units``)."""
         kw = dict(consistency=(measurement, self.cell), consistency_weight=self.weight)
         given = dict(consistency_profile=self.profile, consistency_noise=self.noise, consistency_operator=self.operator,
-                     consistency_row_noise=self.row_noise, consistency_slab=self.slab, consistency_band=self.band)
+                     consistency_row_noise=self.row_noise, consistency_slab=self.slab, consistency_band=self.band,
+                     consistency_heun=self.heun)
         for name in ('consistency_noise', 'consistency_row_noise'):
             if given[name] is not None:
                 given[name] = in_units(given[name], std, slope)
@@ -303,7 +338,7 @@ class Chain:
 
     def __init__(self, plan, rows, device, shape=None):
         p, joint, self.launch = plan, shape is not None, plan.launch
-        self.mode, self.cell = p.mode, p.cell
+        self.mode, self.cell, self.heun = p.mode, p.cell, p.heun
         self.meas = p.state_space(p.volume(device)).contiguous() if joint else p.measurement.to(device).float().contiguous()
         self.table = self.tables = self.slab = self.band_ws = None
         if p.mode == 'band':                                 # the volume's table was made for ``p.volume``; the workspace once per volume
@@ -386,4 +421,16 @@ class Chain:
         else:                                                # the profile's table or the operator's projector
             step = ops.volume_joint_consistent_tile_step if self.mode == 'tile' else ops.volume_joint_consistent_profile_step
             step(*head, x0_prev, self.meas, self.cell, self.table, weight, *update, **key)
+        return True
+
+    def joint_heun(self, i, phase, head, coefs, kc, tail, seed, draw, sample):
+        """Phase ``phase`` (1: predictor, 2: corrector and the next churn) of step ``i`` of a joint Heun chain: the fused launch
+        ``ops.volume_joint_consistent_heun`` in the place of ``ops.volume_joint_heun`` -- ``head`` = (y, slot, taps, xh, xn, x0),
+        ``coefs``, ``kc`` and ``tail`` = (lo, hi, clamp_mode, stride) as that launch takes them.  False where this phase is not
+        projected (phase 2 under ``consistency_heun='predictor'``): nothing was launched."""
+        ops, (rung, weight, _) = self.launch, self.steps[i]             # ``ops``: the calling module's from here on
+        if rung == 'plain' or (phase == 2 and self.heun == 'predictor'):
+            return False
+        ops.volume_joint_consistent_heun(*head, self.meas, self.cell, self.table, weight, phase, coefs, kc, *tail, seed, draw=draw,
+                                         sample=sample, mode=self.mode)
         return True

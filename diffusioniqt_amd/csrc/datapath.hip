@@ -1762,6 +1762,95 @@ __global__ __launch_bounds__(256) void volume_joint_heun_kernel(const float* __r
     xh[v] = r;
     x0v[v] = x0b;
 }
+// Phases 1 and 2 of the kernel above with the data-consistency projection between the fuse and the update
+// (diqt_volume_joint_consistent_heun): the box geometry and the two passes of volume_joint_consistent_kernel -- a (64, 4) block owns a
+// box of whole cells (cell_box), pass 1 fuses every voxel of the box into LDS (x0s, dens), one barrier, pass 2 revisits the SAME voxels
+// -- and the updates of that kernel's phases, with the projected prediction in the place of the fused one.  In a cell whose voxels are
+// ALL covered the fused x0 becomes x0' = x0 + w A+(y - A x0) by the one definition of its MODE:
+//   0 (uniform)  cell_mean / cell_shift;
+//   1 (profile)  cell_wmean / cell_wshift, `table` [2][n] in LDS behind dens;
+//   2 (tile)     tile_apply on P = `table` [n][n] (in LDS behind dens) read with stride n, then cell_shift by meas_up = t.
+// A cell with an uncovered voxel is left alone: its covered voxels take the update with their plain x0.  Phase 1 stores x0v = x0' and
+// xn = a xh + b x0'; phase 2 forms t = fma(c, xn, a xh + b x0v) and r = fma(d, x0b', t), churns r by kc n(draw) (no Philox call when
+// kc == 0) and stores xh = r, x0v = x0b'.  An uncovered voxel: phase 1 writes xn = xh and x0v = 0, phase 2 leaves xh and writes
+// x0v = 0.  `phase` is uniform over the launch; there is no phase 0 here (the initial state is the plain kernel's).  A thread reads and
+// writes only its own voxels of xh / xn / x0v, each read before it is written, and whole cells lie in one block: all three are updated
+// in place, without an atomic and without waiting across blocks.  At stride = patch the chain is one_unet_sample's Heun loop with the
+// per-window projection launch after an evaluation, bit for bit.
+template <int MODE>
+__global__ __launch_bounds__(256) void volume_joint_consistent_heun_kernel(const float* __restrict__ y, const int* __restrict__ slot,
+                                                                           const float* __restrict__ taps, float* xh, float* xn,
+                                                                           float* x0v, const float* __restrict__ meas_up,
+                                                                           const float* __restrict__ table, int phase, int N, int D,
+                                                                           int H, int W, int P, int stride, int G0, int G1, int G2,
+                                                                           Cell cell, float w, float a, float b, float c, float d,
+                                                                           float kc, float lo, float hi, int clamp_mode, unsigned key0,
+                                                                           unsigned key1, unsigned draw, unsigned sample) {
+    extern __shared__ float tp[];                      // [P], then x0s [nb] and den [nb]; profile: the table [2][n]; tile: P [n][n]
+    const CellBox box = cell_box(cell);
+    const int nb = cell.fz * box.by * box.bx, t = threadIdx.y * 64 + threadIdx.x;
+    float* x0s = tp + P;
+    float* dens = x0s + nb;
+    float* tab = dens + nb;
+    const int n = cell.fz * cell.fy * cell.fx;
+    for (int e = t; e < P; e += 256) tp[e] = taps[e];
+    if constexpr (MODE != 0)
+        for (int e = t; e < (MODE == 1 ? 2 * n : n * n); e += 256) tab[e] = table[e];
+    __syncthreads();
+    const int z0 = blockIdx.z * cell.fz, y0 = blockIdx.y * box.by, xb = blockIdx.x * box.bx;
+    for (int e = t; e < nb; e += 256) {
+        const int lx = e % box.bx, ly = (e / box.bx) % box.by, lz = e / (box.bx * box.by);
+        const Voxel p{xb + lx, y0 + ly, z0 + lz, 0, y0 + ly < H && xb + lx < W};
+        Fused f{0.f, 0.f};
+        if (p.inside) f = joint_fuse(y, slot, taps, tp, N, P, stride, G0, G1, G2, p, StepClamp{lo, hi, clamp_mode});
+        x0s[e] = f.covered() ? f.x0() : 0.f;
+        dens[e] = f.den;
+    }
+    __syncthreads();
+    for (int e = t; e < nb; e += 256) {
+        const int lx = e % box.bx, ly = (e / box.bx) % box.by, lz = e / (box.bx * box.by);
+        const int x = xb + lx, h = y0 + ly, dz = z0 + lz;
+        if (h >= H || x >= W) continue;
+        const size_t v = ((size_t)dz * H + h) * W + x;
+        if (dens[e] == 0.f) {
+            if (phase == 1) xn[v] = xh[v];
+            x0v[v] = 0.f;
+            continue;
+        }
+        // the cell of this voxel inside the box (the box is one cell deep) and the voxel's index inside its cell
+        const int cb = ((ly / cell.fy) * cell.fy) * box.bx + (lx / cell.fx) * cell.fx;
+        const int q = (lz * cell.fy + ly % cell.fy) * cell.fx + lx % cell.fx;
+        bool all = true;
+        auto value = [&](int i, int j, int k) {
+            const int u = cb + (i * box.by + j) * box.bx + k;
+            all = all && dens[u] != 0.f;
+            return x0s[u];
+        };
+        float x0 = x0s[e];
+        if constexpr (MODE == 0) {
+            const float m = cell_mean(cell, value);
+            if (all) x0 = cell_shift(w, meas_up[v], m, x0);
+        } else if constexpr (MODE == 1) {
+            const float m = cell_wmean(cell, tab, value);
+            if (all) x0 = cell_wshift(w, tab[n + q], meas_up[v], m, x0);
+        } else {
+            const float s = tile_apply(cell, tab + q, n, value);
+            if (all) x0 = cell_shift(w, meas_up[v], s, x0);
+        }
+        if (phase == 1) {
+            const float h_ = xh[v];
+            x0v[v] = x0;
+            xn[v] = axpby_update(a, h_, b, x0);
+            continue;
+        }
+        const float u = fmaf(c, xn[v], axpby_update(a, xh[v], b, x0v[v]));
+        float r = fmaf(d, x0, u);                      // axpby3(tmp, out2, 1, d): 1 * tmp is tmp
+        if (kc != 0.f)
+            r = fmaf(kc, philox_normal(philox4x32_10((unsigned)v, (unsigned)((unsigned long long)v >> 32), draw, sample, key0, key1)), r);
+        xh[v] = r;
+        x0v[v] = x0;
+    }
+}
 // The same chain with the inpainting loop on the joint state (diqt_volume_joint_heun_inpaint): known [D][H][W] in state space, mask one
 // byte per voxel.  The predictor is phase 1 of the kernel above; the phases here, numbered as there, paste and churn with the helpers
 // of the per-window pass:
@@ -2825,6 +2914,44 @@ extern "C" int diqt_volume_joint_heun(const float* y, const int* slot, const flo
     hipLaunchKernelGGL(volume_joint_heun_kernel, g.grid, dim3(64, 4), g.lds, STREAM, y, slot, taps, xh, xn, x0, phase, N, D, H, W, P, stride,
                        G0, G1, G2, a, b, c, d, kc, lo, hi, clamp_mode, (unsigned)seed, (unsigned)(seed >> 32), draw, sample);
     return check_launch("volume_joint_heun");
+}
+
+extern "C" int diqt_volume_joint_consistent_heun(const float* y, const int* slot, const float* taps, float* xh, float* xn, float* x0,
+                                                 const float* meas_up, const float* table, int phase, int mode, int N, int D, int H,
+                                                 int W, int P, int stride, int G0, int G1, int G2, int fz, int fy, int fx, float weight,
+                                                 float a, float b, float c, float d, float kc, float lo, float hi, int clamp_mode,
+                                                 unsigned long long seed, unsigned draw, unsigned sample, void* stream) {
+    const char* who = "volume_joint_consistent_heun";
+    DIQT_REQUIRE(phase == 1 || phase == 2, DIQT_E_UNSUPPORTED,
+                 "%s: phase %d (1 = predictor, 2 = corrector; the init is volume_joint_heun's)", who, phase);
+    DIQT_REQUIRE(mode >= 0 && mode <= 2, DIQT_E_UNSUPPORTED, "%s: mode %d (0 = uniform, 1 = profile, 2 = tile operator)", who, mode);
+    DIQT_REQUIRE(xh && xn && x0 && meas_up && (table || mode == 0) && slot && taps && (y || N == 0), DIQT_E_ALIGN, "%s: null pointer", who);
+    int rc = cell_ok(who, fz, fy, fx, weight);
+    if (rc) return rc;
+    DIQT_REQUIRE(D > 0 && H > 0 && W > 0 && D % fz == 0 && H % fy == 0 && W % fx == 0, DIQT_E_SHAPE,
+                 "%s: the cell %dx%dx%d does not divide the volume %dx%dx%d", who, fz, fy, fx, D, H, W);
+    JointGrid g;                                       // the shape, lattice and clamp checks of the plain launch; the grid is the boxes'
+    rc = joint_launch_plan(who, xh, true, true, N, D, H, W, P, stride, G0, G1, G2, clamp_mode, g);
+    if (rc) return rc;
+    const Cell cell{fz, fy, fx};
+    const CellBox box = cell_box(cell);
+    const size_t n = (size_t)fz * fy * fx;
+    const size_t lds = ((size_t)P + 2 * (size_t)fz * box.by * box.bx + (mode == 2 ? n * n : mode == 1 ? 2 * n : 0)) * sizeof(float);
+    DIQT_REQUIRE(lds <= 65536, DIQT_E_SHAPE, "%s: P %d needs %zu bytes of LDS", who, P, lds);
+    DIQT_REQUIRE((H + box.by - 1) / box.by <= 65535, DIQT_E_SHAPE, "%s: more than 65535 rows of boxes", who);
+    const dim3 grid((W + box.bx - 1) / box.bx, (H + box.by - 1) / box.by, D / fz);
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(64, 4), lds, STREAM, y, slot, taps, xh, xn, x0, meas_up, table, phase, N, D, H, W, P, stride,
+                           G0, G1, G2, cell, weight, a, b, c, d, phase == 2 ? kc : 0.f, lo, hi, clamp_mode, (unsigned)seed,
+                           (unsigned)(seed >> 32), draw, sample);
+    };
+    if (mode == 2)
+        launch(volume_joint_consistent_heun_kernel<2>);
+    else if (mode == 1)
+        launch(volume_joint_consistent_heun_kernel<1>);
+    else
+        launch(volume_joint_consistent_heun_kernel<0>);
+    return check_launch(who);
 }
 
 extern "C" int diqt_edm_inpaint_churn(const float* x, const float* renoise, const float* known, const unsigned char* mask,

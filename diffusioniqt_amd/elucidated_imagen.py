@@ -420,7 +420,8 @@ class ElucidatedImagen(nn.Module):
                         inpaint_images=None, inpaint_masks=None, inpaint_resample_times=5, init_images=None,
                         skip_steps=None, sigma_min=None, sigma_max=None, noise=None, sampler='heun', sample_steps=None, eta=0.,
                         consistency=None, consistency_weight=1., consistency_profile=None, consistency_noise=None,
-                        consistency_operator=None, consistency_row_noise=None, consistency_slab=None, consistency_band=None, **kwargs):
+                        consistency_operator=None, consistency_row_noise=None, consistency_slab=None, consistency_band=None,
+                        consistency_heun=None, **kwargs):
         """Stochastic Heun sampler (:382-532).  ``noise``: optional injected list [init, step_0, ...], or a callable
         ``noise(shape) -> fp32 device tensor`` whose successive calls are those draws (one ``eps`` per step, also when gamma is 0).
 
@@ -436,22 +437,28 @@ class ElucidatedImagen(nn.Module):
         ``sampler='heun'``; one of the two without the other, another sampler or a count that is not a positive integer: ``ValueError``
         before anything touches the device.
 
-        ``consistency=(meas_up, cell)`` with ``consistency_weight`` (``sampler='dpmpp2m'`` only), ``consistency_profile``,
-        ``consistency_noise``, ``consistency_operator``, ``consistency_row_noise``, ``consistency_slab``, ``consistency_band``:
-        data-consistent sampling
+        ``consistency=(meas_up, cell)`` with ``consistency_weight`` (``sampler='dpmpp2m'``, or ``'heun'`` with ``consistency_heun``),
+        ``consistency_profile``, ``consistency_noise``, ``consistency_operator``, ``consistency_row_noise``, ``consistency_slab``,
+        ``consistency_band``, ``consistency_heun``: data-consistent sampling
         (DDNM / DDNM+); the keywords, their rules and the launch a step takes are stated once, in ``consistency.py``.  ``meas_up``
         [B,C,P,P,P], the measurement replicated onto the high-res grid (``ops.cell_replicate``; with an operator t = A+ y,
         ``ops.tile_backproject``), and the noise deviations arrive in state space here (``sample`` takes them in the units it
         returns, like ``inpaint_images``).  Every step's clamped or thresholded prediction goes through the mode's projection before
         ``ops.multistep_sde_step``; the history operand and self-conditioning read the projected tensor.  A noise-aware step runs
         its one launch on the step's draw and hands the step the reduced normals (a new tensor); the step with kn = 0 (the last)
-        skips the projection.  The draws are unchanged.  The Heun sampler has two predictions per step and is refused."""
+        skips the projection.  The draws are unchanged.  The Heun sampler has two predictions per step and is refused unless
+        ``consistency_heun`` says which to project: ``'both'`` -- ``out`` (at sigma_hat) and ``out2`` (at sigma_next) each go through
+        the mode's projection launch right after their evaluation, 2 T - 1 launches per chain -- or ``'predictor'`` -- ``out`` alone,
+        T launches.  The predictor's ``axpby3``, the corrector's two, ``x_start`` and self-conditioning read the projected tensors;
+        the last step (to sigma 0, no corrector, row (0, 1)) ends the chain in its projected prediction.  Every rung is the constant
+        one: no DDNM+ weights with Heun."""
         self._check_sampler_args(sampler, sample_steps, skip_steps, eta)
         has_inpainting = self._check_inpaint_args(sampler, inpaint_images, inpaint_masks, inpaint_resample_times)
         plan = consistency_plan('one_unet_sample', ops, consistency, consistency_weight, consistency_profile, consistency_noise,
                                 consistency_operator, consistency_row_noise, consistency_slab, consistency_band, shape=shape,
                                 stochastic=eta != 0,
-                                has_inpainting=has_inpainting, init_images=init_images, skip_steps=skip_steps, sampler=sampler)
+                                has_inpainting=has_inpainting, init_images=init_images, skip_steps=skip_steps, sampler=sampler,
+                                heun=consistency_heun)
         if sampler == 'dpmpp2m':
             return self._dpmpp2m_sample(unet, shape, unet_number=unet_number, clamp=clamp, dynamic_threshold=dynamic_threshold,
                                         cond_scale=cond_scale, init_images=init_images, sigma_min=sigma_min, sigma_max=sigma_max,
@@ -469,6 +476,7 @@ class ElucidatedImagen(nn.Module):
         draw, images, fwd, sc = self._start_chain(unet, shape, unet_number, sigma0, noise, init_images, clamp=clamp,
                                                   dynamic_threshold=dynamic_threshold, cond_scale=cond_scale, **kwargs)
         vec = lambda v: torch.full((shape[0],), float(v), device=self.device)
+        chain = plan.prepare(sched, self.device) if exists(plan) else None                        # once per chain
         x_start = renoise = kr = None
         for ind, ((sigma, sigma_next, _), sigma_hat, (kc, a, b, a_half, b_half, r2, neg_r2)) in enumerate(zip(sched, hats, coefs)):
             kc = vec(kc)
@@ -480,11 +488,15 @@ class ElucidatedImagen(nn.Module):
                 else:
                     images_hat = ops.axpby3(images, eps, None, vec(1.), kc, None)
                 out = fwd(images_hat, float(sigma_hat), **sc(x_start))
+                if exists(chain):                                                 # ``out`` arrives clamped or thresholded
+                    out, _, _ = chain.project(ind, out, lambda: None)
                 # x_next = x_hat + (s_next - s_hat) * (x_hat - D)/s_hat
                 images_next = ops.axpby3(images_hat, out, None, vec(a), vec(b), None)
                 x_start = out
                 if sigma_next != 0:                                               # 2nd-order correction (:502-516)
                     out2 = fwd(images_next, float(sigma_next), **sc(out))
+                    if exists(chain) and chain.heun == 'both':                    # 'predictor': the corrector's stays the network's
+                        out2, _, _ = chain.project(ind, out2, lambda: None)
                     tmp = ops.axpby3(images_hat, out, images_next, vec(a_half), vec(b_half), vec(r2))
                     images_next = ops.axpby3(tmp, out2, None, vec(1.), vec(neg_r2), None)
                     x_start = out2
@@ -607,7 +619,7 @@ class ElucidatedImagen(nn.Module):
                stop_at_unet_number=None, return_all_unet_outputs=False, return_pil_images=False, use_tqdm=True, device=None,
                noise=None, sampler='heun', sample_steps=None, eta=0., consistency=None, consistency_weight=1.,
                consistency_profile=None, consistency_noise=None, consistency_operator=None, consistency_row_noise=None,
-               consistency_slab=None, consistency_band=None):
+               consistency_slab=None, consistency_band=None, consistency_heun=None):
         """:536-702.  ``noise``: optional injected list [lowres_noise, init, step_0, ...] per sampled unet (tests), or -- when exactly
         one U-Net is sampled -- a callable ``noise(shape) -> fp32 device tensor`` whose successive calls are those draws in that order
         (``inference.AnchoredNoise.source``: call k is draw k of the volume-anchored field).
@@ -624,8 +636,9 @@ class ElucidatedImagen(nn.Module):
         images / masks alone, inpainting with 'dpmpp2m', or a count that is not a positive integer: ``ValueError`` naming "inpaint",
         before anything touches the device.
 
-        ``consistency=(meas_up, cell)`` / ``consistency_weight`` and the six keywords that ride on it (``consistency_profile``,
-        ``consistency_noise``, ``consistency_operator``, ``consistency_row_noise``, ``consistency_slab``, ``consistency_band``):
+        ``consistency=(meas_up, cell)`` / ``consistency_weight`` and the seven keywords that ride on it (``consistency_profile``,
+        ``consistency_noise``, ``consistency_operator``, ``consistency_row_noise``, ``consistency_slab``, ``consistency_band``,
+        ``consistency_heun`` -- with ``sampler='heun'``: ``'both'`` or ``'predictor'``, the predictions of a Heun step to project):
         ``one_unet_sample``'s, for
         every sampled U-Net (so they must generate one size).  ``meas_up`` [B,C,P,P,P] (with an operator t = A+ y) is in the units
         this returns -- ``normalize_img`` takes it to state space, as it does ``inpaint_images`` -- and the noise deviations are in
@@ -646,7 +659,7 @@ class ElucidatedImagen(nn.Module):
                 consistency_row_noise, consistency_slab, consistency_band, stochastic=etas[n - 1] != 0, has_inpainting=exists(inpaint_images),
                 shape=exists(frames) and (batch_size, self.channels, *frames[n - 1], self.image_sizes[n - 1], self.image_sizes[n - 1]),
                 init_images=cast_tuple(init_images, len(self.unets))[n - 1], skip_steps=cast_tuple(skip_steps, len(self.unets))[n - 1],
-                sampler=samplers[n - 1])
+                sampler=samplers[n - 1], heun=consistency_heun)
         # what ``one_unet_sample`` takes: the measurement in state space, the deviations with it by the map's slope
         consistent = plan.keywords(self.normalize_img(plan.measurement), slope=state_slope(self.normalize_img)) if exists(plan) else {}
         if has_inpainting:

@@ -1495,7 +1495,7 @@ class Imagen(nn.Module):
                       pred_objective='noise', dynamic_threshold=True, use_tqdm=True, noise=None, sampler='ddpm',
                       sample_steps=None, eta=0.0, consistency=None, consistency_weight=1.0, consistency_profile=None,
                       consistency_noise=None, consistency_operator=None, consistency_row_noise=None, consistency_slab=None,
-                      consistency_band=None):
+                      consistency_band=None, consistency_heun=None):
         """Ancestral sampler (:2059-2160).  Per step: one U-Net eval (HIP) + ONE fused posterior-step kernel;
         the per-step coefficients for all steps are computed on the host up front.  ``noise`` (optional) is a list
         [init, step_0, ...] of injected tensors with the reference's draw order (:2080, :2051), or a callable
@@ -1534,7 +1534,7 @@ class Imagen(nn.Module):
         plan = consistency_plan('p_sample_loop', ops, consistency, consistency_weight, consistency_profile, consistency_noise,
                                 consistency_operator, consistency_row_noise, consistency_slab, consistency_band, shape=shape,
                                 stochastic=not (sampler == 'dpmpp2m' or (sampler == 'ddim' and eta == 0)), has_inpainting=has_inpainting,
-                                init_images=init_images, skip_steps=skip_steps)
+                                init_images=init_images, skip_steps=skip_steps, heun=consistency_heun)
         device = self.device
         batch = shape[0]
         if callable(noise):
@@ -1610,7 +1610,7 @@ class Imagen(nn.Module):
                stop_at_unet_number=None, return_all_outputs=False, return_all_unet_outputs=None, return_pil_images=False,
                device=None, use_tqdm=True, noise=None, sampler='ddpm', sample_steps=None, eta=0.0, consistency=None,
                consistency_weight=1.0, consistency_profile=None, consistency_noise=None, consistency_operator=None,
-               consistency_row_noise=None, consistency_slab=None, consistency_band=None):
+               consistency_row_noise=None, consistency_slab=None, consistency_band=None, consistency_heun=None):
         """imagen_pytorch3D.py:2165-2274 -> (img, [noisy per step], [x0 per step]).  Accepts both spellings
         ``return_all_outputs`` / ``return_all_unet_outputs`` (test.py:182 uses the latter).  ``sampler`` / ``sample_steps`` / ``eta``
         (one value, or one per U-Net like ``skip_steps``) and the list or callable ``noise``: see ``p_sample_loop``, as for
@@ -1633,7 +1633,7 @@ class Imagen(nn.Module):
                              shape=(batch_size, self.channels) + (self.image_sizes[n - 1],) * 3,
                              stochastic=not (sampler[n - 1] == 'dpmpp2m' or (sampler[n - 1] == 'ddim' and eta[n - 1] == 0)),
                              has_inpainting=exists(inpaint_images) and exists(inpaint_masks),
-                             init_images=cast_tuple(init_images, num_unets)[n - 1], skip_steps=skip_steps[n - 1])
+                             init_images=cast_tuple(init_images, num_unets)[n - 1], skip_steps=skip_steps[n - 1], heun=consistency_heun)
         device = default(device, self.device)
         self.reset_unets_all_one_device(device=device)
         cond_scale = cast_tuple(cond_scale, num_unets)

@@ -93,8 +93,20 @@ corrected prediction.  The sigma-space chain ends at sigma = 0 with (kx, k0) = (
 schedules of the DDPM family end at a finite log-SNR, so their last step keeps a little of the state (4 ddim steps of the cosine
 schedule end on kx = 0.032, k0 = 0.971) and the final cell means are kx A x_t + k0 y.  What comes after the chain -- the denoiser's
 final clamp, and in ``ops.volume_joint_finish`` the fill of uncovered voxels and the background reset -- is not projected again, and
-cells they touch are no longer exactly consistent.  Not offered: the EDM Heun sampler (two predictions per step), and consistency
-together with inpainting.
+cells they touch are no longer exactly consistent.  Not offered: the EDM Heun sampler without ``consistency_heun`` (below), and
+consistency together with inpainting.
+
+The Heun sampler of the EDM family (``consistency_heun='both'`` or ``'predictor'``, with ``consistency``) has two predictions per
+step: ``'both'`` projects the fused prediction of either evaluation, ``'predictor'`` the first alone (one launch fewer per step for a
+per-window call; the corrector's prediction stays the network's).  The step that ends at sigma = 0 has no corrector and its predictor
+row is (0, 1), so under either value the chain ends in its last projected prediction, as the sigma-space chain does.  The crop and
+blend modes hand ``consistency_heun=`` on to the sampler call (``ElucidatedImagen.sample(sampler='heun', ...)``: one projection launch
+of the mode after each projected evaluation, any of the five modes); with ``joint=True`` and ``ElucidatedImagen.window_denoiser()``
+the projection rides in ``ops.volume_joint_consistent_heun``, which ``consistency.Chain.joint_heun`` puts in the place of
+``ops.volume_joint_heun`` in phase 1 and, under ``'both'``, in phase 2 -- 2 T - 1 fused launches as before -- for the cell mean, a
+profile or an operator; self-conditioning gathers the projected volume.  Not offered: joint Heun with the slab or the band (their
+joint step launches carry the three linear update forms only), DDNM+ weights (``consistency_noise`` / ``consistency_row_noise``:
+Heun's noise is the churn before the evaluation), and any sampler but Heun with the keyword.
 
 A slice profile (``consistency_profile=(pz, py, px)``, with ``consistency``) replaces the plain mean: the measurement of a cell is
 u . x, u_q = pz_i py_j px_k / (sum pz sum py sum px) -- the weights of the voxels under a slice, roughly Gaussian or trapezoidal for a
@@ -134,7 +146,7 @@ divisibility rules are those above.  The crop and blend modes hand windows of t 
 w = 1 the corrected prediction satisfies P x0' = t (to fp32 rounding), which is A x0' = y when y lies in the range of A; stacks that
 contradict each other are fitted in the least-squares sense.  An operator that crosses tile borders is not a tile operator: true
 k-space truncation is ``consistency_band``, overlapping slice profiles are ``consistency_slab``, both below.  Not offered:
-``consistency_profile`` or ``consistency_noise`` with an operator, Heun,
+``consistency_profile`` or ``consistency_noise`` with an operator, Heun without ``consistency_heun``,
 consistency together with inpainting; the stacks are taken as registered to each other and A as known.
 
 Noisy rows (``consistency_row_noise=sigma``, with ``consistency`` and ``consistency_operator``; DDNM+ per singular direction): sigma
@@ -191,7 +203,8 @@ where nothing covers), ``ops.band_apply`` (c = P r, three dense passes along the
 0 means the measurement is believed where nothing was generated, so exact consistency holds only on a fully covered volume.  The table
 and the five-volume workspace are made once per volume; an axis is capped at 512 voxels (``ops.band_plan``).  Not offered: a
 non-separable band (an ellipsoid, partial Fourier), phase or coil models, noise-aware weights, the crop and blend modes, and any of the
-other consistency keywords together with it; Heun, inpainting, ``init_images`` and ``skip_steps`` as for ``consistency``.
+other consistency keywords together with it; joint Heun; Heun per window without ``consistency_heun``, inpainting, ``init_images`` and
+``skip_steps`` as for ``consistency``.
 """
 from types import SimpleNamespace
 
@@ -383,6 +396,7 @@ class VolumeInference:
     consistency_row_noise = property(lambda self: getattr(self.plan, 'row_noise', None))
     consistency_slab = property(lambda self: getattr(self.plan, 'slab', None))
     consistency_band = property(lambda self: getattr(self.plan, 'band', None))
+    consistency_heun = property(lambda self: getattr(self.plan, 'heun', None))
 
     def _inpaint_volumes(self, win):
         """The known volume and the mask as 0/1 floats on the volume's device (``__call__`` has checked their shape)."""
@@ -396,7 +410,7 @@ class VolumeInference:
     def __init__(self, configs, sample_fn, nonzero_ratio=0.05, blend=None, sigma_scale=0.125, samples=1, noise=None, seed=0, joint=False,
                  inpaint=None, inpaint_resample_times=5, consistency=None, consistency_weight=1.0, consistency_profile=None,
                  consistency_noise=None, consistency_operator=None, consistency_row_noise=None, consistency_slab=None,
-                 consistency_band=None):
+                 consistency_band=None, consistency_heun=None):
         """``sample_fn(lr_patches [B,1,S,S,S]) -> hr_patches`` — e.g. ``lambda x: trainer.sample(batch_size=x.shape[0],
         start_image_or_video=x, start_at_unet_number=2)[0]`` (test_all.py:234).  ``blend`` / ``sigma_scale`` / ``samples``: weighted
         overlap blending and multi-sample statistics, see the module docstring.  ``noise='anchored'`` (with ``seed``): every call
@@ -422,8 +436,8 @@ class VolumeInference:
         chains have no re-noising loop).
 
         ``consistency=(measurement, cell)`` with ``consistency_weight=w``, and ``consistency_profile``, ``consistency_noise``,
-        ``consistency_operator``, ``consistency_row_noise``, ``consistency_slab``, ``consistency_band`` with it: data-consistent sampling;
-        the measurement
+        ``consistency_operator``, ``consistency_row_noise``, ``consistency_slab``, ``consistency_band``, ``consistency_heun`` with it:
+        data-consistent sampling; the measurement
         models are in the module docstring, the keywords, their rules and the launch a step takes in ``consistency.py``.
         ``measurement`` is a float tensor [D/fz, H/fy, W/fx] of RAW intensities (host or device) -- with an operator
         [m, D/fz, H/fy, W/fx], one volume per row (``ops.stack_rows`` lays stacks out so, ``ops.tile_measure`` simulates them) -- and
@@ -433,7 +447,8 @@ class VolumeInference:
         divided by std; with ``joint=True`` the projection rides in the fused launch of the three linear chains (the slab: three
         launches per step), the deviations also multiplied by the slope of the denoiser's ``state_space``.  ``ValueError`` naming the
         keyword at fault, and the one that rides on it, before anything touches the device: what ``consistency.py`` lists, together
-        with ``inpaint``, joint mode with a Heun denoiser or one without ``state_space``, a joint denoiser with no stochastic step
+        with ``inpaint``, joint mode with a Heun denoiser and no ``consistency_heun`` or with one that has no
+        ``state_space``, a joint denoiser with no stochastic step
         under a noise deviation, an operator whose rows are not the measurement's leading dimension, a stride or window the cell
         does not divide or cubes whose launch plans more than 64 KiB of LDS (crop and blend modes) -- and, in ``__call__``, a
         measurement that is not the volume's shape divided by the cell."""
@@ -459,7 +474,7 @@ class VolumeInference:
         self.plan = consistency_plan("VolumeInference", ops, consistency, consistency_weight, consistency_profile, consistency_noise,
                                      consistency_operator, consistency_row_noise, consistency_slab, consistency_band, stochastic=stochastic(),
                                      window=dict(edge=self.sub, stride=self.overlap, joint=bool(joint), denoiser=sample_fn,
-                                                 inpaint=self.inpaint is not None, mean=self.mean, std=self.std))
+                                                 inpaint=self.inpaint is not None, mean=self.mean, std=self.std), heun=consistency_heun)
         self.resample_times = inpaint_resample_times
         if noise not in NOISE_MODES:
             raise ValueError(f"VolumeInference: noise must be None or 'anchored', got {noise!r}")
@@ -671,8 +686,10 @@ class VolumeInference:
 
     def _heun_chain(self, den, win, evaluate, y, s, known=None, mask=None):
         """Sample ``s`` of the chain of an EDM window denoiser (module docstring): ``xh`` (images_hat), ``xn`` (images_next) and ``x0_vol``
-        (the fused prediction, which self-conditioning gathers) are advanced in place by ``ops.volume_joint_heun``; ``predict`` evaluates
-        the windows of one of them into ``y``, with draw 0 of the field at each batch as its low-res noise.  The initial image is draw
+        (the fused prediction, which self-conditioning gathers) are advanced in place by ``ops.volume_joint_heun`` -- under
+        ``consistency_heun`` by ``ops.volume_joint_consistent_heun`` in the phases ``consistency.Chain.joint_heun`` projects;
+        ``predict`` evaluates the windows of one of them into ``y``, with draw 0 of the field at each batch as its low-res noise.
+        The initial image is draw
         ``den.draw_base``, the eps of step i draw ``den.draw_base + 1 + i``.  Returns the volume the chain ends in.
 
         With ``known`` (fp32 [D,H,W] in state space) and ``mask`` (uint8 [D,H,W]) the chain inpaints: every step runs
@@ -689,6 +706,7 @@ class VolumeInference:
         else:
             xh = ops.volume_joint_heun_inpaint_init(known, mask, den.sigma0, den.coefs[0][0], self.seed, draw=base, sample=s)
         xn, x0_vol = torch.empty_like(xh), torch.empty_like(xh)
+        head, tail, dc = (y, win.slot, win.taps, xh, xn, x0_vol), (*den.clamp, self.overlap), win.consistency
 
         def predict(state, i, stage, first):
             evaluate(state, x0_vol if den.self_cond and not first else None, self._window_x0(den, win, s, i, edm=True, stage=stage))
@@ -699,7 +717,9 @@ class VolumeInference:
             sigma, sigma_next = float(den.sched[i][0]), float(den.sched[i][1])
             for r in reversed(range(R)):
                 predict(xh, i, 0, i == 0 and r == R - 1)
-                ops.volume_joint_heun(y, win.slot, win.taps, xh, xn, x0_vol, 1, (a1, b1), 0., *den.clamp, self.overlap)
+                # under consistency the same update behind the projection of the fused prediction
+                if dc is None or not dc.joint_heun(i, 1, head, (a1, b1), 0., tail, 0, 0, 0):      # the predictor reads no normal
+                    ops.volume_joint_heun(*head, 1, (a1, b1), 0., *tail)
                 corrected = sigma_next != 0
                 more = r > 0 or i + 1 < T                    # another pass follows: this launch churns for it
                 renoise = r > 0 and i + 1 < T
@@ -707,8 +727,8 @@ class VolumeInference:
                 if corrected:                                # no corrector on the step that ends at sigma 0
                     predict(xn, i, 1, False)
                     if known is None:
-                        ops.volume_joint_heun(y, win.slot, win.taps, xh, xn, x0_vol, 2, (a2, b2, c2, d2), kc, *den.clamp, self.overlap,
-                                              self.seed, draw=draw if more else 0, sample=s)
+                        if dc is None or not dc.joint_heun(i, 2, head, (a2, b2, c2, d2), kc, tail, self.seed, draw if more else 0, s):
+                            ops.volume_joint_heun(*head, 2, (a2, b2, c2, d2), kc, *tail, self.seed, draw=draw if more else 0, sample=s)
                     else:
                         ops.volume_joint_heun_inpaint(y, win.slot, win.taps, xh, xn, x0_vol, known, mask, 2, (a2, b2, c2, d2),
                                                       sigma - sigma_next if renoise else 0., kc, *den.clamp, self.overlap, self.seed,

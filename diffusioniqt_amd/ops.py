@@ -3936,6 +3936,62 @@ def volume_joint_heun(y, slot, taps, xh, xn, x0, phase, coefs, kc, lo, hi, clamp
     return xh, xn, x0
 
 
+JOINT_HEUN_MODES = {'cell': 0, 'profile': 1, 'tile': 2}          # ``mode`` of diqt_volume_joint_consistent_heun
+
+
+def volume_joint_consistent_heun_lds(cell, P, mode):
+    """The bytes of LDS ``volume_joint_consistent_heun`` plans: ``P`` taps, the two box arrays of ``cell`` and the mode's table
+    (2 n floats of a profile, n^2 of a tile operator).  The entry refuses a plan above 65536 with DIQT_E_SHAPE."""
+    fz, fy, fx = cell
+    by, bx = fy * -(-4 // (fz * fy)), fx * -(-64 // fx)
+    n = fz * fy * fx
+    return 4 * (int(P) + 2 * fz * by * bx + {'cell': 0, 'profile': 2 * n, 'tile': n * n}[mode])
+
+
+def volume_joint_consistent_heun(y, slot, taps, xh, xn, x0, meas_up, cell, table, weight, phase, coefs, kc, lo, hi, clamp_mode, stride,
+                                 seed=0, draw=0, sample=0, mode='cell'):
+    """``volume_joint_heun`` with the data-consistency projection between the fuse and the update (include/diqt.h,
+    diqt_volume_joint_consistent_heun), IN PLACE on ``xh``, ``xn`` and ``x0`` as there.  ``mode`` ``'cell'`` (``table`` None),
+    ``'profile'`` (``table`` [2, n] = ``cell_profile``'s) or ``'tile'`` (``table`` [n, n] = ``tile_operator``'s P and ``meas_up`` =
+    t); ``meas_up`` [D,H,W] in state space, ``cell`` = (fz, fy, fx) dividing the volume, ``weight`` in (0, 1].  Every cell whose voxels
+    are all covered has this phase's fused prediction replaced by x0 + weight A+(y - A x0) before the update -- phase 1: x0 = x0', xn
+    = a xh + b x0'; phase 2: x = (a xh + b x0 + c xn) + d x0b', xh = x + kc n, x0 = x0b' -- a cell with an uncovered voxel and the
+    uncovered voxels are the plain launch's.  ``phase``, ``coefs``, ``kc``, the clamp and the noise key as in ``volume_joint_heun``.
+    Returns ``(xh, xn, x0)``.  One launch, bit-reproducible."""
+    who = "volume_joint_consistent_heun"
+    phase = int(phase)
+    if phase not in (1, 2):
+        raise ValueError(f"{who}: phase must be 1 (predictor) or 2 (corrector), got {phase!r}; phase 0 is volume_joint_heun_init")
+    if mode not in JOINT_HEUN_MODES:
+        raise ValueError(f"{who}: mode must be 'cell', 'profile' or 'tile', got {mode!r}")
+    N, P, stride = _joint_windows(who, y, slot, taps, xh, clamp_mode, stride)
+    seed, draw, sample = _noise_key(who, seed, draw, sample)
+    _joint_slots(who, slot, N)
+    cell, weight = consistency_cell(who, cell, weight, [(s, a) for a, s in enumerate(xh.shape)])
+    coefs = tuple(float(v) for v in coefs)
+    if len(coefs) != 2 * phase:
+        raise ValueError(f"{who}: phase {phase} takes {2 * phase} coefficients, got {len(coefs)}")
+    for t, name in ((xn, 'xn'), (x0, 'x0'), (meas_up, 'meas_up')):
+        _chk(t)
+        if t.shape != xh.shape or not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be a contiguous tensor of xh's shape")
+    if len({xh.data_ptr(), xn.data_ptr(), x0.data_ptr(), meas_up.data_ptr()}) != 4:
+        raise ValueError(f"{who}: xh, xn, x0 and meas_up are four different volumes")
+    if mode == 'cell':
+        if table is not None:
+            raise ValueError(f"{who}: mode 'cell' takes no table")
+    else:
+        (_cell_table if mode == 'profile' else _tile_table)(who, table, cell, xh)
+    need = volume_joint_consistent_heun_lds(cell, P, mode)
+    if need > 65536:
+        raise ValueError(f"{who}: the consistency cell {cell} with windows of edge {P} plans {need} bytes of LDS (the taps, two box "
+                         f"arrays and the table), above the 65536 a launch may have")
+    _lib.call("diqt_volume_joint_consistent_heun", y if N else None, slot, taps, xh, xn, x0, meas_up, table, phase, JOINT_HEUN_MODES[mode],
+              N, *xh.shape, P, stride, *slot.shape, *cell, weight, *(coefs + (0.0, 0.0))[:4], float(kc) if phase == 2 else 0.0, float(lo),
+              float(hi), int(clamp_mode), seed, draw, sample, _stream())
+    return xh, xn, x0
+
+
 def _chk_mask(who, mask, like):
     if not mask.is_cuda:
         raise RuntimeError(f"diffusioniqt_amd.ops.{who} runs on the MI355X only (no CPU fallback); the mask is a CPU tensor")

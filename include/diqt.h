@@ -1036,6 +1036,26 @@ int diqt_volume_joint_consistent_band_step(const float* y, const int* slot, cons
 int diqt_volume_joint_heun(const float* y, const int* slot, const float* taps, float* xh, float* xn, float* x0, int phase, int N, int D,
                            int H, int W, int P, int stride, int G0, int G1, int G2, float a, float b, float c, float d, float kc,
                            float lo, float hi, int clamp_mode, unsigned long long seed, unsigned draw, unsigned sample, void* stream);
+/* Phases 1 and 2 of diqt_volume_joint_heun with the data-consistency projection between the fuse and the update (DDNM on both
+ * predictions of a Heun step, or on the predictor's alone when only phase 1 goes through here): in every cell whose voxels are ALL
+ * covered the fused prediction becomes x0' = x0 + w A+(y - A x0), and the phase's update reads x0' where the plain launch reads the
+ * fused x0; a cell with an uncovered voxel is left alone, and an uncovered voxel is treated as there (phase 1: xn = xh, x0 = 0; phase
+ * 2: xh untouched, x0 = 0).  `mode` chooses the projection, each the ONE definition of its per-window entry: 0 the cell mean
+ * (diqt_cell_project; `table` is not looked at), 1 a slice profile (diqt_cell_project_profile; `table` device fp32 [2][n]), 2 a
+ * tile operator (diqt_tile_project; `table` device fp32 [n][n] = P and meas_up = t).  `meas_up` [D][H][W] is in state space; the cell
+ * (fz, fy, fx), n = fz fy fx in 2 .. 64, must divide D, H and W; weight in (0, 1].  The geometry is diqt_volume_joint_consistent_step's:
+ * a block owns a box of whole cells, fuses it into LDS and revisits it after ONE barrier, so xh, xn and x0 are updated in place with
+ * no atomics and no waiting across blocks -- bit-reproducible.  There is no phase 0: the initial state is diqt_volume_joint_heun's.
+ * Coefficients, kc, the clamp, the normals and their numbering are that entry's.  With stride = P and unit taps the chain is the
+ * per-window Heun loop with the mode's projection launch after an evaluation, bit for bit.  Null pointers (table only for mode 0):
+ * DIQT_E_ALIGN; phase outside {1, 2}, mode outside {0, 1, 2}, n outside 2 .. 64, a weight outside (0, 1] or clamp_mode outside
+ * {0, 1}: DIQT_E_UNSUPPORTED; a cell that does not divide the volume, a lattice that does not match or a plan above 64 KiB of LDS
+ * (the taps, two box arrays and the table): DIQT_E_SHAPE.                                                                          */
+int diqt_volume_joint_consistent_heun(const float* y, const int* slot, const float* taps, float* xh, float* xn, float* x0,
+                                      const float* meas_up, const float* table, int phase, int mode, int N, int D, int H, int W, int P,
+                                      int stride, int G0, int G1, int G2, int fz, int fy, int fx, float weight, float a, float b, float c,
+                                      float d, float kc, float lo, float hi, int clamp_mode, unsigned long long seed, unsigned draw,
+                                      unsigned sample, void* stream);
 /* One pass boundary of the inpainting (RePaint) loop around that sampler, per window batch (elucidated_imagen.py:479-486 and 520-523:
  * `images = images + (sigma - sigma_next) * repaint_noise`, then `images_hat = images + added_noise` with the known image under the
  * mask) -- the re-noise that ends pass r, the paste and the churn that begins the next pass in ONE launch, in place of two diqt_axpby3
